@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- train samples/sec + logloss of the FTRL-FFM hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds what
+else the bench measures: the resident, pageable-copy and evaluation legs, the other scaling of a
+sharded run, the per-kernel table and roofline, and the CPU baseline.  `--dump-outputs DIR` writes
+what the last timed step computed (dump_outputs) after the timed steps.
 
 One "step" = one pass of the hot path (H2D of the CSR block -> group -> lazy refresh + forward ->
 FTRL update) over one block of synthetic libffm rows.  The metric is SURVEY.md 8(d)'s: rows / wall
@@ -12,8 +17,8 @@ blocks live in page-locked host memory and go through the engine's pipelined hos
 (ffm_engine_stage_batch + ffm_engine_train_staged on one GPU; + train_forward_staged + all-reduce +
 train_update_device on a sharded rank): block t+1 is DMA-ed to HBM and grouped on a side stream
 while block t trains (`--host-copy`: through ffm_engine_train_batch_async, which first copies the
-caller's pageable arrays into the engine's pinned staging slot).  The same loop over blocks already
-resident in HBM is timed afterwards and reported as `resident` (never as `value`).
+caller's pageable arrays into the engine's pinned staging slot).  Under `--full` the same loop over
+blocks already resident in HBM is timed as well and reported as `resident` (never as `value`).
 
 Workload at N = 1: BASELINE.json's headline configuration itself -- FFM n_fields=39 n_factors=16
 n_feats=33M (247 GB of (w,n,z): it fits one MI355X), block = 8192 rows, Zipf(1.1) ids, 64 distinct
@@ -24,6 +29,7 @@ per-GPU pair work is constant; `--scaling strong`: SURVEY 8(d)'s literal C5, 819
 globally.  PyTorch is plumbing here (the process group, device buffers of the resident leg).
 """
 import argparse
+import ctypes
 import glob
 import json
 import os
@@ -277,6 +283,35 @@ def matching_pmc_summary(key):
     return None, None
 
 
+DUMP_FEATS = 4096  # features whose records --dump-outputs samples (FFM c5: 31 MB of the 64 MB allowed)
+
+
+def dump_outputs(out_dir, eng, feats, logits=None, loss_sum=None):
+    """--dump-outputs: what the last timed step handed back -- its pre-update logits (train()'s
+    return values) and its loss sum, where the path returns them per step -- and the model it left
+    behind: the bias (w, n, z) and the records of a fixed, seeded sample of the features that step
+    trained (`feats`; ids ascending in state_ids).  float32 / float64 .npy files, 31 MB at the most."""
+    arrays = {}
+    if logits is not None:
+        arrays["logits"] = np.asarray(logits, np.float32)
+    if loss_sum is not None:
+        arrays["loss_sum"] = np.array([loss_sum], np.float64)
+    b = np.zeros(3, np.float32)
+    fp = lambda i: b[i:].ctypes.data_as(ctypes.POINTER(ctypes.c_float))  # noqa: E731
+    eng._check(eng.lib.ffm_engine_get_weights(eng.h, fp(0), None, None))
+    eng._check(eng.lib.ffm_engine_get_state(eng.h, fp(1), fp(2), None, None, None, None))
+    arrays["bias3"] = b
+    ids = np.unique(feats)
+    ids = np.sort(np.random.default_rng(0).choice(ids, min(ids.size, DUMP_FEATS), replace=False))
+    arrays["state_ids"] = ids.astype(np.float64)
+    for key, a in eng.get_rows(ids).items():
+        if a.size:
+            arrays["state_" + key] = a
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -319,7 +354,15 @@ def main():
     ap.add_argument("--no-field-map", action="store_true",
                     help="sharded runs: do not tell the engine the per-field id ranges (every shard "
                          "then keeps full-length records and all columns)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs, the other scaling, the per-kernel table / roofline and "
+                         "the CPU baseline (the --no-* options above switch them off one by one)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run does only what its headline figure needs
+        args.no_profile = args.no_resident = args.no_cpu_baseline = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     n_gpus = args.gpus
@@ -492,8 +535,8 @@ def main():
                 staged += 1
             if sharded:
                 sstep.train_staged(host_blocks[(first + i) % n_blocks].n_rows, loss_sum.data_ptr() + 8 * (first + i))
-            else:
-                eng.train_staged(None, loss_sum.data_ptr() + 8 * (first + i))
+            else:  # (the last step hands its logits back, what --dump-outputs writes: a store per row)
+                eng.train_staged(logit.data_ptr() if i == count - 1 else None, loss_sum.data_ptr() + 8 * (first + i))
         eng.sync()
         # (every step's loss is in HBM now; adding the K doubles up on the host -- a torch reduction, a
         # second device sync and a D2H copy, ~0.2 ms of Python and runtime latency -- is reporting, not
@@ -612,6 +655,16 @@ def main():
     if not args.no_profile:
         kname, klaunches, kms = eng.profile_read()
         eng.profile_enable(False)
+    if args.dump_outputs and rank == 0:  # before the --full legs after this point train on
+        last = args.warmup + args.steps - 1
+        if not host_leg:
+            dump_outputs(args.dump_outputs, eng, host_blocks[last % len(dev_blocks)].feat, logit.cpu().numpy(),
+                         float(loss_sum[total_steps + last].item()))
+        elif sharded or zero_copy:
+            dump_outputs(args.dump_outputs, eng, main_blocks[last % n_blocks].feat, logit.cpu().numpy(),
+                         float(loss_sum[last].item()))
+        else:  # (--host-copy: that entry point hands back neither logits nor a loss per step)
+            dump_outputs(args.dump_outputs, eng, main_blocks[last % n_blocks].feat)
     value = total_rows / elapsed
     if host_leg:
         train_loss = host_loss / total_rows
@@ -636,7 +689,7 @@ def main():
     # `--scaling weak` (default) multiplies the block with the GPUs; SURVEY.md 8(d)'s literal C5 is
     # 8192 rows per step GLOBALLY -- the strong line.  Both legs on the same engines, same process.
     other_scaling = None
-    if sharded and host_leg and zero_copy and not args.rows:
+    if sharded and host_leg and zero_copy and not args.rows and args.full:
         o_rows = cfgw["rows"] * (1 if args.scaling == "weak" else n_shards)
         if o_rows <= rows:  # (the engines were created for `rows` rows per block)
             o_blocks = make_blocks(o_rows, max(8, min(64, (1 << 19) // o_rows)))
@@ -756,7 +809,7 @@ def main():
             "train_logloss": round(train_loss, 6),
             "step_algorithmic_GBps": round(value * bytes_row / n_gpus / 1e9, 1),
         }
-        if sharded and model == "FFM":
+        if sharded and model == "FFM" and args.full:
             # what the block size of this line costs in logloss against the per-sample reference loop
             out["block_logloss_cost"] = block_logloss_cost(rows)
         if other_scaling:
