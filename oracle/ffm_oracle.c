@@ -195,6 +195,35 @@ static void ffm_update_vector_w(fo_model *m, const rowview *rv) {
     }
 }
 
+/* ffm_update_vector_w for a block's lazy refresh (fo_train_batch, sweep 1).  A slot's refresh reads
+ * only that slot's (n, z, w), and no step of the sweep changes (n, z): refreshing it once more for
+ * every further row that touches it stores the same bits again.  done[i * n_fields + field] marks
+ * the slots refreshed so far, so each one is refreshed once. */
+static void ffm_refresh_vector_w(fo_model *m, const rowview *rv, unsigned char *done) {
+  const int k = m->n_factors, F = m->n_fields;
+  const int64_t L = m->row_len;
+  for (int a = 0; a < rv->n; a++)
+    for (int b = a + 1; b < rv->n; b++) {
+      const int field1 = RV_FIELD(rv, a), i = RV_FEAT(rv, a);
+      const int field2 = RV_FIELD(rv, b), j = RV_FEAT(rv, b);
+      const int64_t s1 = (int64_t)i * F + field2, s2 = (int64_t)j * F + field1;
+      if (!done[s1]) {
+        done[s1] = 1;
+        for (int f = 0; f < k; f++) {
+          const int64_t f1 = i * L + (int64_t)field2 * k + f;
+          m->vec_w[f1] = mzw_latent(m, m->vec_n[f1], m->vec_z[f1], m->vec_w[f1]);
+        }
+      }
+      if (!done[s2]) {
+        done[s2] = 1;
+        for (int f = 0; f < k; f++) {
+          const int64_t f2 = j * L + (int64_t)field1 * k + f;
+          m->vec_w[f2] = mzw_latent(m, m->vec_n[f2], m->vec_z[f2], m->vec_w[f2]);
+        }
+      }
+    }
+}
+
 /* ffm.cpp:57-70: linear logit, then per pair inner_product(init 0.0f) * x1 * x2 */
 static float compute_ffm_logit(const fo_model *m, const rowview *rv) {
   const int k = m->n_factors;
@@ -633,19 +662,24 @@ double fo_train_batch(fo_model *m, int n_rows, const int32_t *row_ptr, const int
     if (row_ptr[r + 1] - row_ptr[r] > max_nnz) max_nnz = row_ptr[r + 1] - row_ptr[r];
   int *idx = (int *)malloc(sizeof(int) * (size_t)max_nnz);
   float *tg = (float *)malloc(sizeof(float) * (size_t)(n_rows > 0 ? n_rows : 1));
+  fo_acc *acc = (fo_acc *)malloc(sizeof(fo_acc) * (size_t)(k > 0 ? k : 1));
   float *svx = NULL;
   if (m->model_type == FO_FM)
     svx = (float *)malloc(sizeof(float) * (size_t)(n_rows > 0 ? n_rows : 1) * (size_t)(k > 0 ? k : 1));
   rowview rv;
   double tmp_loss = 0.0;
   /* sweep 1: lazy refresh of everything the batch touches, from the batch-start (n,z) */
+  unsigned char *fresh = NULL;
+  if (m->model_type == FO_FFM)
+    fresh = (unsigned char *)calloc((size_t)m->n_feats * (size_t)m->n_fields, 1);
   for (int r = 0; r < n_rows; r++) {
     const int b = row_ptr[r];
     rv_build(m, &rv, row_ptr[r + 1] - b, field + b, feat + b, val + b, idx);
     update_linear_w(m, &rv);
-    if (m->model_type == FO_FFM) ffm_update_vector_w(m, &rv);
+    if (m->model_type == FO_FFM) ffm_refresh_vector_w(m, &rv, fresh);
     else if (m->model_type == FO_FM) fm_update_vector_w(m, &rv);
   }
+  free(fresh);
   if (n_rows > 0) update_bias(m);
   /* sweep 2: forward with frozen weights */
   for (int r = 0; r < n_rows; r++) {
@@ -727,31 +761,32 @@ double fo_train_batch(fo_model *m, int n_rows, const int32_t *row_ptr, const int
       }
     } else if (m->model_type == FO_FFM) {
       /* ffm.cpp:102-121 slot by slot: slot (i, fp) is touched by every occurrence of i whose row
-       * holds an entry q of field fp other than itself (exactly one here: the slot is not serial) */
+       * holds an entry q of field fp other than itself (exactly one here: the slot is not serial).
+       * The k accumulators of a slot are walked side by side, occurrence after occurrence: each one
+       * still sees its touches in occurrence order, and the partner's k weights are read together
+       * (a block's most frequent features have thousands of occurrences). */
       for (int fp = 0; fp < F; fp++) {
         if (ser[fp]) continue;
-        for (int f = 0; f < k; f++) {
-          const int64_t o = i * L + (int64_t)fp * k + f;
-          const float w = m->vec_w[o];
-          fo_acc a;
-          acc_init(&a, m->vec_n[o]);
-          for (int t = lo; t < hi; t++) {
-            const int p = g.ent[t].p, r = g.row_of[p];
-            const int q = g.rfirst[(size_t)r * F + fp];
-            acc_at(&a, t - lo);
-            if (q < 0 || q == p) continue;
-            const float x = p < q ? val[p] * val[q] : val[q] * val[p];
-            const float vp = m->vec_w[feat[q] * L + (int64_t)field[p] * k + f];
-            const float gg = tg[r] * vp * x;
+        const int64_t o = i * L + (int64_t)fp * k;
+        for (int f = 0; f < k; f++) acc_init(&acc[f], m->vec_n[o + f]);
+        for (int t = lo; t < hi; t++) {
+          const int p = g.ent[t].p, r = g.row_of[p];
+          const int q = g.rfirst[(size_t)r * F + fp];
+          for (int f = 0; f < k; f++) acc_at(&acc[f], t - lo);
+          if (q < 0 || q == p) continue;
+          const float x = p < q ? val[p] * val[q] : val[q] * val[p];
+          const float *vq = m->vec_w + feat[q] * L + (int64_t)field[p] * k;
+          for (int f = 0; f < k; f++) {
+            const float gg = tg[r] * vq[f] * x;
             if (p < q || m->learn) {
-              acc_touch(&a, gg, gg * gg, 1); /* ffm.cpp:112-115 */
+              acc_touch(&acc[f], gg, gg * gg, 1); /* ffm.cpp:112-115 */
             } else {
-              const float g1 = tg[r] * w * x;      /* the pair's first entry's gradient */
-              acc_touch(&a, gg, gg * g1, 0); /* ffm.cpp:117-120 incl. :118 */
+              const float g1 = tg[r] * m->vec_w[o + f] * x; /* the pair's first entry's gradient */
+              acc_touch(&acc[f], gg, gg * g1, 0);            /* ffm.cpp:117-120 incl. :118 */
             }
           }
-          acc_finish_latent(m, &a, w, &m->vec_n[o], &m->vec_z[o]);
         }
+        for (int f = 0; f < k; f++) acc_finish_latent(m, &acc[f], m->vec_w[o + f], &m->vec_n[o + f], &m->vec_z[o + f]);
       }
     }
     lo = hi;
@@ -796,7 +831,7 @@ double fo_train_batch(fo_model *m, int n_rows, const int32_t *row_ptr, const int
   }
   groups_free(&g);
   free(ser_all);
-  free(idx); free(tg); free(svx);
+  free(idx); free(tg); free(svx); free(acc);
   return tmp_loss;
 }
 

@@ -284,3 +284,38 @@ def test_numpy_restatement_of_the_fold_agrees_bit_for_bit(mt, F, k, ordered):
         assert got["vec_z"].size - np.isnan(got["vec_z"]).sum() > 100
     for key in ("bias3", "lin_n", "lin_z", "vec_n", "vec_z"):
         assert_bitwise(got[key].ravel(), want[key].ravel(), key)
+
+
+@pytest.mark.parametrize("F,n_rows,counts", [(8, 6144, "ffm"), (39, 4352, "ffm"), (4, 1024, "fm")])
+def test_occurrence_block_builder_hits_every_count_exactly(F, n_rows, counts):
+    """The builder the occurrence-class GPU tests use (util.occurrence_block): each listed feature
+    occurs exactly its count times, in its own field; every other id occurs once; one entry per field
+    and row in field order; the irregular copy keeps every listed count and drops a third of one
+    field's entries; every id lies in its field's range."""
+    from util import EDGE_COUNTS, FM_EDGE_COUNTS, block_ids_per_field, irregular_copy, occurrence_block
+    want = EDGE_COUNTS if counts == "ffm" else FM_EDGE_COUNTS
+    blk, ids, field_of = occurrence_block(F, want, n_rows, seed=3)
+    per = block_ids_per_field(n_rows)
+    assert blk.n_rows == n_rows and blk.row_ptr[-1] == n_rows * F
+    assert np.array_equal(blk.field, np.tile(np.arange(F, dtype=np.int32), n_rows))
+    assert np.array_equal(blk.feat // per, blk.field)
+    u, c = np.unique(blk.feat, return_counts=True)
+    got = dict(zip(u.tolist(), c.tolist()))
+    assert [got[int(i)] for i in ids] == list(want)
+    assert np.array_equal(ids // per, field_of)
+    assert len(set(ids.tolist())) == len(want)
+    rest = np.setdiff1d(u, ids)
+    assert (c[np.isin(u, rest)] == 1).all()
+    assert rest.size == n_rows * F - sum(want)
+    hist = np.bincount(c)
+    assert hist[1] == rest.size + sum(1 for x in want if x == 1)
+    for x in set(want) - {1}:
+        assert hist[x] == list(want).count(x), x
+    irr = irregular_copy(blk, seed=4)
+    assert irr.row_ptr[-1] == n_rows * F - n_rows // 3
+    u2, c2 = np.unique(irr.feat, return_counts=True)
+    got2 = dict(zip(u2.tolist(), c2.tolist()))
+    assert [got2[int(i)] for i in ids] == list(want)
+    assert np.array_equal(irr.feat // per, irr.field)
+    order = [np.all(np.diff(irr.field[irr.row_ptr[r]:irr.row_ptr[r + 1]]) > 0) for r in range(n_rows)]
+    assert 0 < order.count(False) < n_rows

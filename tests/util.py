@@ -114,3 +114,183 @@ def make_cpu(kind, case_or_type, dims=None, hp=None):
         return CpuModel(kind, c["model_type"], nf, F, k, **c["hp_kw"])
     nf, F, k = dims
     return CpuModel(kind, case_or_type, nf, F, k, **(hp or DEFAULT_HP))
+
+
+# The per-block occurrence counts at which a feature's update changes path (kernels_group.h): once
+# only | few (2..10, gathered four at a time) | hot (11..128; tiles of 16 touches) | very hot
+# (129..256) | giant (257..2047, one workgroup; ranges of 256) | super (>= 2048, ranges all over the
+# chip) -- each edge with its neighbours, tile / segment edges and partial last ranges among them.
+EDGE_COUNTS = (1, 2, 3, 4, 5, 8, 9, 10, 11, 12, 15, 16, 17, 31, 32, 33, 127, 128, 129, 255, 256, 257,
+               258, 511, 512, 513, 2047, 2048, 2049, 2304, 2305, 4096, 4097)
+# FM: giants from 65 occurrences, folded in ranges of 64 (kFmGiantMin, kFmRange)
+FM_EDGE_COUNTS = (1, 2, 3, 4, 5, 8, 9, 10, 11, 12, 15, 16, 17, 63, 64, 65, 66, 127, 128, 129)
+
+
+def occurrence_block(n_fields, counts, n_rows, seed=0):
+    """A regular block (one entry per field and row, fields in order) in which feature number i of
+    `counts` occurs exactly counts[i] times.  Features are dealt to the fields largest first, each to
+    the least loaded field; every field's leftover rows get ids that occur nowhere else.  Field f
+    owns the ids [f * per, (f + 1) * per) with per = n_rows + 1 (block_ids_per_field).  Returns
+    (block, ids, field_of): ids[i] / field_of[i] are feature i's id and field."""
+    F = int(n_fields)
+    per = block_ids_per_field(n_rows)
+    rng = np.random.default_rng(seed)
+    load = np.zeros(F, np.int64)
+    ids = np.zeros(len(counts), np.int32)
+    field_of = np.zeros(len(counts), np.int32)
+    cols = [[] for _ in range(F)]
+    for i in sorted(range(len(counts)), key=lambda i: -counts[i]):
+        f = int(np.argmin(load))
+        assert load[f] + counts[i] <= n_rows, "n_rows too small for the counts"
+        ids[i], field_of[i] = f * per + len(cols[f]), f
+        cols[f].append(int(counts[i]))
+        load[f] += counts[i]
+    feat = np.zeros((n_rows, F), np.int32)
+    for f in range(F):
+        col = np.repeat(np.arange(len(cols[f])), cols[f])
+        fill = len(cols[f]) + np.arange(n_rows - col.size)  # once-only ids
+        feat[:, f] = f * per + rng.permutation(np.concatenate([col, fill]))
+    val = (rng.random((n_rows, F)) + 0.25).astype(np.float32)
+    val[rng.random((n_rows, F)) < 0.5] = 1.0
+    label = (rng.random(n_rows) < 0.4).astype(np.int32)
+    field = np.broadcast_to(np.arange(F, dtype=np.int32), (n_rows, F)).reshape(-1).copy()
+    row_ptr = (np.arange(n_rows + 1, dtype=np.int64) * F).astype(np.int32)
+    return Csr(row_ptr, field, feat.reshape(-1), val.reshape(-1), label), ids, field_of
+
+
+def block_ids_per_field(n_rows):
+    return int(n_rows) + 1
+
+
+def irregular_copy(blk, seed=0, n_reversed=64):
+    """The block made irregular: a third of its rows lose their entry of one field (the field with
+    the most once-only ids; only such entries go, so every other feature keeps its count), and
+    `n_reversed` rows list their entries in reverse field order."""
+    rng = np.random.default_rng(seed)
+    n_rows = blk.n_rows
+    F = int(blk.row_ptr[1] - blk.row_ptr[0])
+    feat = blk.feat.reshape(n_rows, F)
+    _, inv, cnt = np.unique(blk.feat, return_inverse=True, return_counts=True)
+    once_all = (cnt[inv] == 1).reshape(n_rows, F)
+    drop_field = int(np.argmax(once_all.sum(0)))
+    once = once_all[:, drop_field]
+    drop = rng.permutation(np.flatnonzero(once))[: n_rows // 3]
+    assert drop.size == n_rows // 3, "not enough once-only entries to drop"
+    keep = np.ones((n_rows, F), bool)
+    keep[drop, drop_field] = False
+    rev = set(rng.choice(n_rows, n_reversed, replace=False).tolist())
+    rows_f, rows_i, rows_v, row_ptr = [], [], [], [0]
+    fld = blk.field.reshape(n_rows, F)
+    val = blk.val.reshape(n_rows, F)
+    for r in range(n_rows):
+        cols = np.flatnonzero(keep[r])
+        if r in rev:
+            cols = cols[::-1]
+        rows_f.append(fld[r, cols])
+        rows_i.append(feat[r, cols])
+        rows_v.append(val[r, cols])
+        row_ptr.append(row_ptr[-1] + cols.size)
+    return Csr(np.array(row_ptr, np.int32), np.concatenate(rows_f).astype(np.int32),
+               np.concatenate(rows_i).astype(np.int32), np.concatenate(rows_v).astype(np.float32),
+               blk.label.copy())
+
+
+def fast_state(rng, model, n_hi=1.0, n_add=0.0, z_sd=0.3, w_sd=0.02, n_zero=0.0):
+    """rand_state drawn in float32 (large models): n ~ U(0, n_hi) + n_add, a fraction n_zero of
+    vec_n set to 0, z ~ N(0, z_sd), w ~ N(0, w_sd)."""
+    st = model.zero_state()
+    for k in st:
+        if k == "bias3":
+            continue
+        a = st[k]
+        if k.endswith("_n"):
+            rng.random(a.shape, dtype=np.float32, out=a)
+            a *= np.float32(n_hi)
+            a += np.float32(n_add)
+        else:
+            rng.standard_normal(a.shape, dtype=np.float32, out=a)
+            a *= np.float32(z_sd if k.endswith("_z") else w_sd)
+    if n_zero > 0 and st["vec_n"].size:
+        st["vec_n"][rng.random(st["vec_n"].shape, dtype=np.float32) < n_zero] = 0.0
+    st["bias3"][...] = np.array([0.013, 0.7, -0.4], np.float32)
+    return st
+
+
+def _f32p(a):
+    import ctypes
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def set_bias3(e, b3):
+    """The bias and its (n, z) of an engine, without the dense transfers of set_state."""
+    b = np.ascontiguousarray(b3, np.float32)
+    e._check(e.lib.ffm_engine_set_weights(e.h, _f32p(b[0:1]), None, None))
+    e._check(e.lib.ffm_engine_set_state(e.h, _f32p(b[1:2]), _f32p(b[2:3]), None, None, None, None))
+
+
+def get_bias3(e):
+    b = np.zeros(3, np.float32)
+    e._check(e.lib.ffm_engine_get_weights(e.h, _f32p(b[0:1]), None, None))
+    e._check(e.lib.ffm_engine_get_state(e.h, _f32p(b[1:2]), _f32p(b[2:3]), None, None, None, None))
+    return b
+
+
+def keep_columns(plan, rank):
+    """The fields a compact shard looks at (bench.py's loader rule): those it owns a pair or the
+    linear terms of."""
+    return (plan["pair_owner"] == rank).any(axis=1) | (plan["lin_owner"] == rank)
+
+
+def kept_copy(blk, keep):
+    """The block with only the entries of the kept fields (rows keep their order and labels)."""
+    sel = keep[blk.field]
+    row_of = np.repeat(np.arange(blk.n_rows), np.diff(blk.row_ptr))
+    per_row = np.bincount(row_of[sel], minlength=blk.n_rows)
+    return Csr(np.concatenate([[0], np.cumsum(per_row)]).astype(np.int32), blk.field[sel].copy(),
+               blk.feat[sel].copy(), blk.val[sel].copy(), blk.label.copy())
+
+
+def run_rank_staged(e, blocks, logits, ahead=2, after_step=None):
+    """One emulated rank the way bench.py drives it: blocks staged up to `ahead` in front, each
+    step train_forward_staged -> (the all-reduce, here: the given exact logits) ->
+    train_update_device.  Returns the rank's partial logits per block."""
+    import torch
+    buf = torch.zeros(max(b.n_rows for b in blocks), dtype=torch.float32, device="cuda")
+    parts, staged = [], 0
+    for i, b in enumerate(blocks):
+        while staged < min(i + 1 + ahead, len(blocks)):
+            e.stage_batch(blocks[staged])
+            staged += 1
+        e.train_forward_staged(buf.data_ptr())
+        e.sync()
+        parts.append(buf[:b.n_rows].cpu().numpy().copy())
+        buf[:b.n_rows].copy_(torch.from_numpy(np.ascontiguousarray(logits[i], np.float32)))
+        torch.cuda.synchronize()
+        e.train_update_device(buf.data_ptr())
+        e.sync()
+        if after_step is not None:
+            after_step(i)
+    return parts
+
+
+def assert_rank_rows(e, rank, ids, field_of, want, plan, k, what, chunk=16384):
+    """A compact shard's rows of features `ids` (ascending, so grouped by their fields `field_of`):
+    the latent elements and linear terms it owns equal want[key][j] (row j of the expected state,
+    any array-like a slice indexes) bit for bit, the latent elements it does not own read back zero.
+    Compared field by field, a chunk of features at a time."""
+    po, lin_owner = plan["pair_owner"], plan["lin_owner"]
+    bounds = np.searchsorted(field_of, np.arange(po.shape[0] + 1))
+    for f in range(po.shape[0]):
+        cols = np.repeat(po[f] == rank, k)
+        for lo in range(bounds[f], bounds[f + 1], chunk):
+            hi = min(bounds[f + 1], lo + chunk)
+            got = e.get_rows(ids[lo:hi])
+            for key in ("vec_n", "vec_z", "vec_w"):
+                assert_bitwise(got[key][:, cols], np.asarray(want[key][lo:hi])[:, cols],
+                               "%s rank %d field %d %s" % (what, rank, f, key))
+                assert not got[key][:, ~cols].any(), "%s rank %d field %d %s: unowned slots not zero" % (
+                    what, rank, f, key)
+            if lin_owner[f] == rank:
+                for key in ("lin_n", "lin_z", "lin_w"):
+                    assert_bitwise(got[key], np.asarray(want[key][lo:hi]), "%s rank %d field %d %s" % (
+                        what, rank, f, key))
