@@ -390,6 +390,8 @@ struct ffm_engine {
   bool single_kernel = true;  // (false: once-only features through the few-occurrence kernel)
   bool single_flat = true;    // (false: one wave per feature also for short stored records)
   int row_threads = kRowThreads;  // workgroup size of the FFM row kernel (FFM_ROW_THREADS)
+  int row_park = -1;         // FFM_ROW_PARK: bytes of w the row kernel parks in LDS (-1: what the budget leaves)
+  int row_park_budget = 0;   // FFM_ROW_PARK_BUDGET: the row kernel's LDS budget for parking (0: 24 KB)
   bool serial = false;  // FFM_ENGINE_SERIAL=1: no side streams (per-kernel timings without overlap)
   // ---- staging thread ------------------------------------------------------------------------
   // The GPU submissions of a staged block (its upload kernel and the ~10 launches of its grouping,
@@ -669,6 +671,8 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   // footprint of short rows) many more rows are in flight per CU
   if (cfg->n_shards > 1) e->row_threads = 64;
   if (const char *sv = std::getenv("FFM_ROW_THREADS")) e->row_threads = std::max(64, std::min(kRowMaxThreads, std::atoi(sv) / 64 * 64));
+  if (const char *sv = std::getenv("FFM_ROW_PARK")) e->row_park = std::atoi(sv);
+  if (const char *sv = std::getenv("FFM_ROW_PARK_BUDGET")) e->row_park_budget = std::atoi(sv);
   // (the lean once-only kernel of a compact shard holds six waves per SIMD: 1152 workgroups
   // measured 2.5 % per step better than 768 on an 8-GPU rank's blocks)
   if (cfg->n_shards > 1) e->grid_single = 1152;
@@ -1042,7 +1046,7 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
       ffm_engine_destroy(e);
       return fail(FFM_E_UNSUPPORTED, "max_row_nnz too large for the 160 KB of LDS per workgroup");
     }
-    const size_t park_budget = std::getenv("FFM_ROW_PARK_BUDGET") ? static_cast<size_t>(std::atoi(std::getenv("FFM_ROW_PARK_BUDGET"))) : 0;
+    const size_t park_budget = static_cast<size_t>(std::max(0, e->row_park_budget));
     if (lds > 32 * 1024 || park_budget > 32 * 1024) {
       const int bytes = static_cast<int>(std::max(lds, park_budget));
       TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));

@@ -89,13 +89,15 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float
     // per XCD x 31 KB of once-only w is the whole 4 MB L2).  As many as fit beside the staging arrays in
     // a 24 KB LDS budget (six rows per CU, which the kernel's 80 VGPRs allow: C5 row kernel 477 us with
     // nothing parked, 450 with 24 KB, 478 with 30 KB = five rows, 535 with 32 KB = four;
-    // profiles/r06_experiments.md), at most what the longest row of the block can use.  FFM_ROW_PARK=bytes overrides
-    // (0: off; test_row_kernel_lds_parking_is_bit_identical pins none / partial / default).
+    // profiles/r06_experiments.md), at most what the longest row of the block can use.  FFM_ROW_PARK=bytes
+    // overrides (0: off; a parked vector is 16 bytes) and FFM_ROW_PARK_BUDGET=bytes replaces the 24 KB,
+    // both read when the engine is created: test_row_kernel_lds_parking_is_bit_identical pins 0 / 96 /
+    // 1024 bytes / the default, test_gpu_launch_geometry.py also 16 bytes (one vector), 96 bytes at 64
+    // threads and a 48 KB budget (above 32 KB).
     int park = 0;
     size_t shmem_park = shmem;
     if (refreshed == 3) {
-      static const int park_env = std::getenv("FFM_ROW_PARK") ? std::atoi(std::getenv("FFM_ROW_PARK")) : -1;
-      static const int budget_env = std::getenv("FFM_ROW_PARK_BUDGET") ? std::atoi(std::getenv("FFM_ROW_PARK_BUDGET")) : 0;
+      const int park_env = e->row_park, budget_env = e->row_park_budget;
       const size_t base = (shmem + 15) & ~static_cast<size_t>(15), budget = budget_env > 0 ? budget_env : 24 * 1024;
       long long bytes = park_env >= 0 ? park_env : (base < budget ? static_cast<long long>(budget - base) : 0);
       bytes = std::min<long long>(bytes, 16ll * row_cap * (e->m.row_len / 4));

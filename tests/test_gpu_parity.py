@@ -250,9 +250,10 @@ def test_evaluation_rows_one_wave_each(k, monkeypatch):
 
 @pytest.mark.parametrize("park", ["0", "96", "1024", "default"])
 def test_row_kernel_lds_parking_is_bit_identical(park, monkeypatch):
-    """The first vectors of (n, z) of a row's once-only features stay in LDS between the row's refresh
-    and its in-row update (FFM_ROW_PARK = bytes; default: what fits 31 KB): none, three vectors (the
-    boundary falls inside the first record), 32, and the default must all give the oracle's bits --
+    """The first 16-byte vectors of w of a row's once-only features stay in LDS between the row's
+    refresh and its pair phase and in-row update (FFM_ROW_PARK = bytes, read when the engine is
+    created; default: what the 24 KB budget leaves): 0, 96 bytes (six vectors: the boundary falls
+    inside the first record), 1024 (64 vectors), and the default must all give the oracle's bits --
     warm and near-zero n (the ffm.cpp:118 NaNs), rows with once-only and hot features mixed."""
     if park != "default":
         monkeypatch.setenv("FFM_ROW_PARK", park)
