@@ -9,14 +9,17 @@ definition itself, checked on the CPU:
   shared), state within rounding distance, NaNs at the same places;
 * a second, independent restatement of the fold in numpy float32 scalars (segments of 16 occurrences
   of the feature, left to right; telescoped step sizes; per-touch terms from the first ffm.cpp:118 touch on)
-  agrees with the C bit for bit.
+  agrees with the C bit for bit -- under the reference rule and under the learning variant
+  (FFM_FLAG_LEARN), whose refresh it restates from the start state;
+* the refresh rule itself on special values of n, z and the stored w (util.special_grid).
 """
 import numpy as np
 import pytest
 
 from oracle import pyoracle
 from oracle.pyoracle import CpuModel, Csr
-from util import DEFAULT_HP, STRESS_HP, assert_bitwise, assert_close, assert_state_bitwise, rand_state
+from util import (DEFAULT_HP, STRESS_HP, assert_bitwise, assert_close, assert_state_bitwise, ftrl_w,
+                  grid_block, grid_want, latent_w, rand_state)
 
 SEG = 16  # FO_SEG
 
@@ -197,11 +200,36 @@ class Acc:
         return self.B, f32(f32(z0) + f32(self.Gacc - f32(si * w)))
 
 
-def numpy_block(model, st, c, tg, hp, F, k):
-    """(n, z) of every accumulator after one block, from the frozen w of `model` (already refreshed)
-    and the rows' tmp_grad; rows hold one entry per field at most and no repeated ids."""
+def numpy_refresh(st, c, hp, F, k, learn):
+    """The block's lazy refresh of the start state `st`, restated: the bias, every feature the rows
+    hold and every latent slot (feature, partner field) a pair of entries touches get W(n, z)
+    (util.ftrl_w); under the learning variant a latent slot with not n > 0 keeps its w instead."""
+    w = {key: st[key].copy() for key in ("bias3", "lin_w", "vec_w")}
+    if c.n_rows:
+        w["bias3"][0] = ftrl_w(st["bias3"][1], st["bias3"][2], hp)
+    for i in np.unique(c.feat):
+        w["lin_w"][i] = ftrl_w(st["lin_n"][i], st["lin_z"][i], hp)
+    L = F * k
+    if not L:
+        return w
+    vw, vn, vz = w["vec_w"].reshape(-1, L), st["vec_n"].reshape(-1, L), st["vec_z"].reshape(-1, L)
+    touched = set()
+    for r in range(c.n_rows):
+        ent = range(c.row_ptr[r], c.row_ptr[r + 1])
+        touched.update((int(c.feat[p]), int(c.field[q])) for p in ent for q in ent if p != q)
+    for i, fp in touched:
+        for e in range(fp * k, fp * k + k):
+            vw[i, e] = latent_w(vn[i, e], vz[i, e], vw[i, e], hp, learn)
+    return w
+
+
+def numpy_block(model, st, c, tg, hp, F, k, learn=False):
+    """(n, z) of every accumulator after one block, from the frozen w and the rows' tmp_grad; rows
+    hold one entry per field at most and no repeated ids.  The reference rule takes w from `model`
+    (already refreshed); the learning variant restates the refresh from `st` (numpy_refresh) and
+    makes every live latent touch a plain one (g*g: ffm.cpp:118 then takes g2*g2)."""
     alpha = hp["w_alpha"]
-    w = model.get_state()
+    w = numpy_refresh(st, c, hp, F, k, True) if learn else model.get_state()
     out = {key: st[key].copy() for key in st}
     out["lin_w"], out["vec_w"], out["bias3"][0] = w["lin_w"], w["vec_w"], w["bias3"][0]
     a = Acc(st["bias3"][1], alpha)
@@ -242,7 +270,7 @@ def numpy_block(model, st, c, tg, hp, F, k):
                     x = f32(c.val[p] * c.val[q])
                     vp = vw[int(c.feat[q]), int(c.field[p]) * k + f]
                     g = f32(f32(tg[r] * vp) * x)
-                    if p < q:
+                    if p < q or learn:
                         a.touch(wv, g, f32(g * g), True)
                     else:
                         g1 = f32(f32(tg[r] * wv) * x)
@@ -255,12 +283,21 @@ def numpy_block(model, st, c, tg, hp, F, k):
     return out
 
 
-@pytest.mark.parametrize("mt,F,k,ordered", [("FFM", 4, 2, True), ("FFM", 4, 2, False), ("LR", 1, 1, True)])
-def test_numpy_restatement_of_the_fold_agrees_bit_for_bit(mt, F, k, ordered):
+FOLD_CASES = [("FFM", 4, 2, True), ("FFM", 4, 2, False), ("LR", 1, 1, True)]
+
+
+@pytest.mark.parametrize("mt,F,k,ordered,learn",
+                         [pytest.param(*c, False, id="-".join(map(str, c))) for c in FOLD_CASES]
+                         + [pytest.param(*c, True, id="learn-" + "-".join(map(str, c))) for c in FOLD_CASES])
+def test_numpy_restatement_of_the_fold_agrees_bit_for_bit(mt, F, k, ordered, learn):
+    """The reference rule, and the learning variant (FFM_FLAG_LEARN): its refresh restated from the
+    start state and its all-plain touches."""
     rng = np.random.default_rng(21)
     nf = 24
-    m = CpuModel("oracle", mt, nf, F, k, **STRESS_HP)
+    m = CpuModel("oracle", mt, nf, F, k, learn=learn, **STRESS_HP)
     st = rand_state(rng, m, n_hi=1e-4, w_sd=0.5)  # n small, w large: some ffm.cpp:118 roots go negative (NaN)
+    if learn:  # four slots in ten have not seen a gradient yet; their w is not W(0, z)
+        st["vec_n"][np.random.default_rng(22).random(st["vec_n"].shape) < 0.4] = 0.0
     m.set_state(st)
     c = rand_rows(rng, 300, 4, nf, ordered=ordered, zipf=2.0, drop=0.1)
     if mt != "FFM":
@@ -277,11 +314,22 @@ def test_numpy_restatement_of_the_fold_agrees_bit_for_bit(mt, F, k, ordered):
         c = Csr.from_rows(rows, c.label)
     logits, _ = m.train_batch(c)
     tg = np.array([f32(m.sigmoid(float(l))) - f32(y) for l, y in zip(logits, c.label)], f32)
-    want = numpy_block(m, st, c, tg, STRESS_HP, F, k if mt == "FFM" else 0)
+    kk = k if mt == "FFM" else 0
+    want = numpy_block(m, st, c, tg, STRESS_HP, F, kk, learn=learn)
     got = m.get_state()
-    if mt == "FFM":
+    w = numpy_refresh(st, c, STRESS_HP, F, kk, learn)
+    for key in ("bias3", "lin_w", "vec_w"):
+        assert_bitwise(got[key].ravel()[:1] if key == "bias3" else got[key].ravel(),
+                       w[key].ravel()[:1] if key == "bias3" else w[key].ravel(), "refresh " + key)
+    if mt == "FFM" and not learn:
         assert np.isnan(got["vec_z"]).any(), "the case should reach ffm.cpp:118's NaN"
         assert got["vec_z"].size - np.isnan(got["vec_z"]).sum() > 100
+    if mt == "FFM" and learn:
+        assert np.isfinite(got["vec_z"]).all() and np.isfinite(got["vec_n"]).all(), "g2*g2: no negative root"
+        # the kept-w branch is live: touched slots with n = 0 whose w is not W(0, z) still hold it
+        kept = (got["vec_n"] != st["vec_n"]) & (st["vec_n"] == 0) & (got["vec_w"] == st["vec_w"])
+        w0 = np.array([ftrl_w(0.0, z, STRESS_HP) for z in st["vec_z"][kept]], f32)
+        assert (w0 != st["vec_w"][kept]).sum() > 20
     for key in ("bias3", "lin_n", "lin_z", "vec_n", "vec_z"):
         assert_bitwise(got[key].ravel(), want[key].ravel(), key)
 
@@ -319,3 +367,27 @@ def test_occurrence_block_builder_hits_every_count_exactly(F, n_rows, counts):
     assert np.array_equal(irr.feat // per, irr.field)
     order = [np.all(np.diff(irr.field[irr.row_ptr[r]:irr.row_ptr[r + 1]]) > 0) for r in range(n_rows)]
     assert 0 < order.count(False) < n_rows
+
+
+@pytest.mark.parametrize("hp", [DEFAULT_HP, STRESS_HP], ids=["default_hp", "stress_hp"])
+@pytest.mark.parametrize("mt", ["FFM", "FM"])
+@pytest.mark.parametrize("learn", [False, True], ids=["reference", "learn"])
+def test_refresh_rule_on_special_values(mt, learn, hp):
+    """The oracle's refresh (mzw_latent, mzw) against util.latent_w / util.ftrl_w on the special
+    values: n = +-0, subnormal, FLT_MIN, +inf, NaN; z = +-0, +-l1 and just past it; w_old = -0.0, a
+    subnormal, NaN.  Under the learning variant a latent slot with not n > 0 keeps its w, -0.0 and
+    subnormals bit for bit; linear terms and the bias keep the reference rule."""
+    g = grid_block(mt, 4 if mt == "FFM" else 8, hp)
+    m = CpuModel("oracle", mt, g["nf"], g["F"], g["k"], learn=learn, **hp)
+    m.set_state(g["state"])
+    m.train_batch(g["block"])
+    got = m.get_state()
+    want, want_lin = grid_want(g, hp, learn)
+    assert_bitwise(got["vec_w"][g["slots"]], want, "latent w")
+    assert_bitwise(got["lin_w"][g["lin"]], want_lin, "linear w")
+    kept = ~(g["n"][g["idx"]] > 0)
+    if learn:  # -0.0, subnormals and NaN kept, the W branch taken elsewhere
+        assert (np.signbit(want[kept]) & (want[kept] == 0)).any() and (np.abs(want[kept]) == f32(3e-41)).any()
+        assert np.isnan(want[kept]).any() and np.count_nonzero(want[~kept]) > 20
+    else:
+        assert not (np.abs(want) == f32(3e-41)).any()

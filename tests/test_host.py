@@ -115,6 +115,38 @@ def test_cli_n_gpus_shards_match_one_engine(tmp_path):
     assert tr == tr1 and ev == ev1
 
 
+@pytest.mark.gpu
+def test_cli_learn_variant(tmp_path):
+    """--learn true (FFM_FLAG_LEARN) on synth data: the range sort (--field_ranges uniform) and the
+    library sort print the same losses, two field-pair shards on one device match one engine, and
+    the losses are not the reference rule's."""
+    from ftrl_ffm_amd import synth
+    main_bin, _ = fa.build_host()
+    F, per = 12, 500
+    g = synth.Generator(F, F * per, "zipf", seed=15)
+    data = tmp_path / "s.ffm"
+    data.write_text(synth.to_libffm_text(g.block(20000)))
+    base = [main_bin, "--train_data", str(data), "--eval_data", str(data), "--model_type", "FFM", "--n_fields", str(F),
+            "--n_feats", str(F * per), "--n_factors", "8", "--online", "true", "--n_epochs", "2", "--batch_size", "1024",
+            "--w_alpha", "0.05", "--w_l1", "0.01", "--w_l2", "0.1"]
+
+    def losses(extra, env=None):
+        out = subprocess.run(base + extra, cwd=tmp_path, capture_output=True, text=True, timeout=600,
+                             env=dict(os.environ, **(env or {})))
+        assert out.returncode == 0, out.stdout + out.stderr
+        return ([float(x) for x in re.findall(r"train loss: ([0-9.]+)", out.stdout)],
+                [float(x) for x in re.findall(r"eval loss: ([0-9.]+)", out.stdout)], out.stdout)
+    tr1, ev1, _ = losses(["--learn", "true", "--field_ranges", "uniform"])
+    assert len(tr1) == 2 and len(ev1) == 2 and tr1[1] < tr1[0] < 0.6931
+    tr, ev, _ = losses(["--learn", "true", "--field_ranges", "none"])
+    assert tr == tr1 and ev == ev1, (tr, tr1, ev, ev1)
+    tr, ev, text = losses(["--learn", "true", "--field_ranges", "uniform", "--n_gpus", "2"], {"FTRL_SAME_DEVICE": "1"})
+    assert "2 field-pair shards" in text
+    assert np.allclose(tr, tr1, atol=2e-4) and np.allclose(ev, ev1, atol=2e-4), (tr, tr1, ev, ev1)
+    tr0, ev0, _ = losses(["--learn", "false", "--field_ranges", "uniform"])
+    assert tr0 != tr1 and ev0 != ev1, (tr0, tr1, ev0, ev1)
+
+
 from oracle import pyoracle  # noqa: E402
 
 needs_ref = pytest.mark.skipif(not pyoracle.have_ref(), reason="oracle/_ref not built here")

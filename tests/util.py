@@ -216,6 +216,94 @@ def fast_state(rng, model, n_hi=1.0, n_add=0.0, z_sd=0.3, w_sd=0.02, n_zero=0.0)
     return st
 
 
+def ftrl_w(n, z, hp):
+    """FtrlModel::maybe_zero_weight (ftrl_model.h:28-33) with T = float, one value: float32
+    operands; the 0.0 / -1.0 literals make the divide a double one, narrowed to float on return."""
+    f = np.float32
+    n, z = f(n), f(z)
+    a, b, l1, l2 = (f(hp[key]) for key in ("w_alpha", "w_beta", "w_l1", "w_l2"))
+    if abs(z) <= l1:
+        return f(0.0)
+    with np.errstate(all="ignore"):
+        num = f(z - f((f(1) if z > 0 else f(-1)) * l1))
+        den = f(l2 + f(f(b + np.sqrt(n)) / a))
+    return f(-1.0 * float(num) / float(den))
+
+
+def latent_w(n, z, w_old, hp, learn):
+    """The latent refresh: W(n, z); under the learning variant a slot without a gradient yet
+    (not n > 0: zero, negative or NaN) keeps its stored weight."""
+    return np.float32(w_old) if learn and not (np.float32(n) > 0) else ftrl_w(n, z, hp)
+
+
+def special_grid(hp, seed=0):
+    """(n, z, w_old) float32 arrays over the special values of the refresh rule: n in
+    {+0, -0, 2^-149, the largest subnormal, FLT_MIN, 1e-30, 0.5, +inf, NaN} x z in {+-0, +-l1,
+    +-nextafter(l1, inf), +-0.3} x w_old in {N(0, 0.02), -0.0, a subnormal, NaN}."""
+    f = np.float32
+    tiny = np.finfo(f).tiny
+    ns = np.array([0.0, -0.0, f(2.0 ** -149), np.nextafter(tiny, f(0)), tiny, 1e-30, 0.5, np.inf,
+                   np.nan], f)
+    l1 = f(hp["w_l1"])
+    zs = np.array([s * v for v in (f(0), l1, np.nextafter(l1, f(np.inf)), f(0.3)) for s in (1, -1)], f)
+    rng = np.random.default_rng(seed)
+    n, z, w = [], [], []
+    for wk in range(4):
+        for a in ns:
+            for b in zs:
+                n.append(a)
+                z.append(b)
+                w.append((f(rng.normal(0, 0.02)), f(-0.0), f(3e-41), f(np.nan))[wk])
+    return np.array(n, f), np.array(z, f), np.array(w, f)
+
+
+def grid_block(mt, k, hp, occurrences=1, seed=0):
+    """special_grid injected into a zero model as latent and as linear accumulators, and a block
+    that touches each of them `occurrences` times.  FFM (F = 2): field 0 holds ids [0, P), field 1
+    ids [P, nf); row r pairs ids r and P + r, so the slot of the other field is touched.  FM: row r
+    holds ids 2r and 2r + 1, every factor touched.  Then rows of one entry each (FFM: in field 1)
+    touch the ids that carry the linear grid and no latent slot of the grid.  Returns a dict:
+    nf, F, k, state, block, field_start, slots (the latent elements (rows, columns) of the grid),
+    idx (their grid index), lin (linear ids), lidx (their grid index), n, z, w (the grid)."""
+    gn, gz, gw = special_grid(hp, seed)
+    N = len(gn)
+    F = 2 if mt == "FFM" else 1
+    P = -(-N // k)  # latent rows per field (FFM) / latent features (FM, rounded up to pairs)
+    P += mt == "FM" and P % 2
+    nlat = 2 * P if mt == "FFM" else P
+    lin = np.arange(nlat, nlat + N // 4)  # (n, z) pairs: w_old does not enter the linear rule
+    nf = nlat + lin.size
+    st = dict(bias3=np.zeros(3, np.float32), lin_w=np.zeros(nf, np.float32),
+              lin_n=np.zeros(nf, np.float32), lin_z=np.zeros(nf, np.float32))
+    for key in ("vec_w", "vec_n", "vec_z"):
+        st[key] = np.zeros((nf, F * k), np.float32)
+    if mt == "FFM":
+        slots = [(i, (1 if i < P else 0) * k + f) for i in range(2 * P) for f in range(k)]
+        rows = [[(0, r, 1.0), (1, P + r, 0.5)] for r in range(P)]
+    else:
+        slots = [(i, f) for i in range(P) for f in range(k)]
+        rows = [[(0, 2 * r, 1.0), (0, 2 * r + 1, 0.5)] for r in range(P // 2)]
+    rows += [[(F - 1, int(i), 1.0)] for i in lin]
+    idx = np.arange(len(slots)) % N
+    rc = np.array([a for a, _ in slots]), np.array([b for _, b in slots])
+    st["vec_n"][rc], st["vec_z"][rc], st["vec_w"][rc] = gn[idx], gz[idx], gw[idx]
+    lidx = np.arange(lin.size)
+    st["lin_n"][lin], st["lin_z"][lin], st["lin_w"][lin] = gn[lidx], gz[lidx], gw[lidx]
+    rows = [r for r in rows for _ in range(occurrences)]
+    c = Csr.from_rows(rows, [r % 2 for r in range(len(rows))])
+    fs = np.array([0, P, nf], np.int32) if mt == "FFM" else None
+    return dict(nf=nf, F=F, k=k, state=st, block=c, field_start=fs, slots=rc, idx=idx, lin=lin,
+                lidx=lidx, n=gn, z=gz, w=gw)
+
+
+def grid_want(g, hp, learn):
+    """The w the refresh stores in grid_block's latent slots and linear ids (latent_w, ftrl_w)."""
+    n, z, w = g["n"], g["z"], g["w"]
+    lat = np.array([latent_w(n[j], z[j], w[j], hp, learn) for j in g["idx"]], np.float32)
+    lin = np.array([ftrl_w(n[j], z[j], hp) for j in g["lidx"]], np.float32)
+    return lat, lin
+
+
 def _f32p(a):
     import ctypes
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
