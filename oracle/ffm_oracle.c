@@ -107,6 +107,20 @@ static inline float mzw(const fo_model *m, float n, float z) {
 }
 float fo_maybe_zero_weight(const fo_model *m, float n, float z) { return mzw(m, n, z); }
 
+/* The engine's short form of x / alpha (ftrl-ffm_amd/csrc/ftrl_math.h: div_alpha_fast), restated so
+ * that a CPU test can compare it with the IEEE divide: r = RN(1 / alpha), q0 = x * r, the exact
+ * residual by FMA, one correction.  fmaf rounds once whatever the build flags are; -ffp-contract=off
+ * keeps the compiler from fusing anything else.  quick[i] gets the short form, exact[i] x[i] / alpha. */
+void fo_div_alpha_fast(float alpha, int64_t n, const float *x, float *quick, float *exact) {
+  const float r = 1.0f / alpha;
+  for (int64_t i = 0; i < n; i++) {
+    const float q0 = x[i] * r;
+    const float rem = fmaf(-q0, alpha, x[i]);
+    quick[i] = fmaf(rem, r, q0);
+    exact[i] = x[i] / alpha;
+  }
+}
+
 static inline float mzw_latent(const fo_model *m, float n, float z, float w_old) {
   if (m->learn && !(n > 0.0f)) return w_old;
   return mzw(m, n, z);

@@ -53,6 +53,8 @@ float fo_sgn(float x);                                  /* utils.h:15-18  (sgn(0
 float fo_sigmoid(float x);                              /* utils.h:20-23 */
 double fo_loss(int y, double logit);                    /* eval/loss.h:8-12 */
 float fo_maybe_zero_weight(const fo_model *m, float n, float z); /* ftrl_model.h:28-33 */
+/* the engine's short x / alpha (div_alpha_fast) next to the IEEE divide, n values at once */
+void fo_div_alpha_fast(float alpha, int64_t n, const float *x, float *quick, float *exact);
 
 /* One reference train()/predict() call: FFM::train ffm.cpp:38-49, FM::train fm.cpp:21-32,
  * LR::train lr.cpp:9-18; predict ffm.cpp:51-55, fm.cpp:34-38, lr.cpp:20-24.

@@ -117,6 +117,8 @@ def _lib(kind):
     getattr(lib, p + "maybe_zero_weight").restype = ctypes.c_float
     getattr(lib, p + "maybe_zero_weight").argtypes = [vp, ctypes.c_float, ctypes.c_float]
     if kind == "oracle":
+        lib.fo_div_alpha_fast.restype = None
+        lib.fo_div_alpha_fast.argtypes = [ctypes.c_float, ctypes.c_int64, _c_f32p, _c_f32p, _c_f32p]
         lib.fo_block_segment.restype = ctypes.c_int
         lib.fo_block_segment.argtypes = []
         for name in ("fo_train_batch", "fo_train_batch_rowwalk"):
@@ -147,6 +149,15 @@ def _lib(kind):
                           ctypes.POINTER(ctypes.c_double)]
     _libs[kind] = (lib, p)
     return _libs[kind]
+
+
+def div_alpha_fast(alpha, x):
+    """(short form, IEEE divide) of x / alpha for a float32 array x: the engine's div_alpha_fast
+    sequence restated in C (fo_div_alpha_fast) next to the plain quotient."""
+    x = np.ascontiguousarray(x, np.float32)
+    quick, exact = np.empty_like(x), np.empty_like(x)
+    _lib("oracle")[0].fo_div_alpha_fast(float(np.float32(alpha)), x.size, _f32(x), _f32(quick), _f32(exact))
+    return quick, exact
 
 
 STATE_KEYS = ("bias3", "lin_w", "lin_n", "lin_z", "vec_w", "vec_n", "vec_z")

@@ -18,8 +18,9 @@ import pytest
 
 from oracle import pyoracle
 from oracle.pyoracle import CpuModel, Csr
-from util import (DEFAULT_HP, STRESS_HP, assert_bitwise, assert_close, assert_state_bitwise, ftrl_w,
-                  grid_block, grid_want, latent_w, rand_state)
+from util import (DEFAULT_HP, HP_SETS, STRESS_HP, arith_flags, assert_bitwise, assert_close,
+                  assert_state_bitwise, bits, div_fast_ok, ftrl_w, grid_block, grid_want, latent_w, rand_state,
+                  range_grid, special_grid)
 
 SEG = 16  # FO_SEG
 
@@ -292,12 +293,29 @@ FOLD_CASES = [("FFM", 4, 2, True), ("FFM", 4, 2, False), ("LR", 1, 1, True)]
 def test_numpy_restatement_of_the_fold_agrees_bit_for_bit(mt, F, k, ordered, learn):
     """The reference rule, and the learning variant (FFM_FLAG_LEARN): its refresh restated from the
     start state and its all-plain touches."""
+    _fold_case(mt, F, k, ordered, learn, STRESS_HP, "random", strict=True)
+
+
+@pytest.mark.parametrize("start", ["random", "range_grid"])
+@pytest.mark.parametrize("mt,F,k", [("FFM", 4, 2), ("LR", 1, 1)])
+@pytest.mark.parametrize("hp_name", [h for h in HP_SETS if h != "stress_hp"])
+def test_numpy_restatement_of_the_fold_at_every_hyper_parameter_set(hp_name, mt, F, k, start):
+    """The same restatement at every util.HP_SETS entry, from the random start state and from one whose
+    n are util.range_grid's (the guard edges of the engine's short square root, 2^118, FLT_MAX)."""
+    _fold_case(mt, F, k, True, False, HP_SETS[hp_name], start, strict=False)
+
+
+def _fold_case(mt, F, k, ordered, learn, hp, start, strict):
     rng = np.random.default_rng(21)
     nf = 24
-    m = CpuModel("oracle", mt, nf, F, k, learn=learn, **STRESS_HP)
+    m = CpuModel("oracle", mt, nf, F, k, learn=learn, **hp)
     st = rand_state(rng, m, n_hi=1e-4, w_sd=0.5)  # n small, w large: some ffm.cpp:118 roots go negative (NaN)
     if learn:  # four slots in ten have not seen a gradient yet; their w is not W(0, z)
         st["vec_n"][np.random.default_rng(22).random(st["vec_n"].shape) < 0.4] = 0.0
+    if start == "range_grid":
+        gn = np.unique(range_grid(hp)[0])
+        for key in ("lin_n", "vec_n"):
+            st[key][...] = gn[np.random.default_rng(23).integers(0, gn.size, st[key].shape)]
     m.set_state(st)
     c = rand_rows(rng, 300, 4, nf, ordered=ordered, zipf=2.0, drop=0.1)
     if mt != "FFM":
@@ -315,20 +333,20 @@ def test_numpy_restatement_of_the_fold_agrees_bit_for_bit(mt, F, k, ordered, lea
     logits, _ = m.train_batch(c)
     tg = np.array([f32(m.sigmoid(float(l))) - f32(y) for l, y in zip(logits, c.label)], f32)
     kk = k if mt == "FFM" else 0
-    want = numpy_block(m, st, c, tg, STRESS_HP, F, kk, learn=learn)
+    want = numpy_block(m, st, c, tg, hp, F, kk, learn=learn)
     got = m.get_state()
-    w = numpy_refresh(st, c, STRESS_HP, F, kk, learn)
+    w = numpy_refresh(st, c, hp, F, kk, learn)
     for key in ("bias3", "lin_w", "vec_w"):
         assert_bitwise(got[key].ravel()[:1] if key == "bias3" else got[key].ravel(),
                        w[key].ravel()[:1] if key == "bias3" else w[key].ravel(), "refresh " + key)
-    if mt == "FFM" and not learn:
+    if mt == "FFM" and not learn and strict:
         assert np.isnan(got["vec_z"]).any(), "the case should reach ffm.cpp:118's NaN"
         assert got["vec_z"].size - np.isnan(got["vec_z"]).sum() > 100
     if mt == "FFM" and learn:
         assert np.isfinite(got["vec_z"]).all() and np.isfinite(got["vec_n"]).all(), "g2*g2: no negative root"
         # the kept-w branch is live: touched slots with n = 0 whose w is not W(0, z) still hold it
         kept = (got["vec_n"] != st["vec_n"]) & (st["vec_n"] == 0) & (got["vec_w"] == st["vec_w"])
-        w0 = np.array([ftrl_w(0.0, z, STRESS_HP) for z in st["vec_z"][kept]], f32)
+        w0 = np.array([ftrl_w(0.0, z, hp) for z in st["vec_z"][kept]], f32)
         assert (w0 != st["vec_w"][kept]).sum() > 20
     for key in ("bias3", "lin_n", "lin_z", "vec_n", "vec_z"):
         assert_bitwise(got[key].ravel(), want[key].ravel(), key)
@@ -369,15 +387,28 @@ def test_occurrence_block_builder_hits_every_count_exactly(F, n_rows, counts):
     assert 0 < order.count(False) < n_rows
 
 
-@pytest.mark.parametrize("hp", [DEFAULT_HP, STRESS_HP], ids=["default_hp", "stress_hp"])
+GRIDS = dict(special=special_grid, range=range_grid)
+
+
+@pytest.mark.parametrize("hp", list(HP_SETS.values()), ids=list(HP_SETS))
 @pytest.mark.parametrize("mt", ["FFM", "FM"])
 @pytest.mark.parametrize("learn", [False, True], ids=["reference", "learn"])
-def test_refresh_rule_on_special_values(mt, learn, hp):
+def test_refresh_rule_on_range_grid(mt, learn, hp):
+    """test_refresh_rule_on_special_values on util.range_grid."""
+    test_refresh_rule_on_special_values(mt, learn, hp, grid="range")
+
+
+@pytest.mark.parametrize("hp", list(HP_SETS.values()), ids=list(HP_SETS))
+@pytest.mark.parametrize("mt", ["FFM", "FM"])
+@pytest.mark.parametrize("learn", [False, True], ids=["reference", "learn"])
+def test_refresh_rule_on_special_values(mt, learn, hp, grid="special"):
     """The oracle's refresh (mzw_latent, mzw) against util.latent_w / util.ftrl_w on the special
     values: n = +-0, subnormal, FLT_MIN, +inf, NaN; z = +-0, +-l1 and just past it; w_old = -0.0, a
     subnormal, NaN.  Under the learning variant a latent slot with not n > 0 keeps its w, -0.0 and
-    subnormals bit for bit; linear terms and the bias keep the reference rule."""
-    g = grid_block(mt, 4 if mt == "FFM" else 8, hp)
+    subnormals bit for bit; linear terms and the bias keep the reference rule.  At every
+    util.HP_SETS entry; test_refresh_rule_on_range_grid runs it on util.range_grid (n on the guard edges
+    of the engine's short square root, 2^118, FLT_MAX; |z| = 2^61)."""
+    g = grid_block(mt, 4 if mt == "FFM" else 8, hp, grid=GRIDS[grid](hp))
     m = CpuModel("oracle", mt, g["nf"], g["F"], g["k"], learn=learn, **hp)
     m.set_state(g["state"])
     m.train_batch(g["block"])
@@ -385,9 +416,102 @@ def test_refresh_rule_on_special_values(mt, learn, hp):
     want, want_lin = grid_want(g, hp, learn)
     assert_bitwise(got["vec_w"][g["slots"]], want, "latent w")
     assert_bitwise(got["lin_w"][g["lin"]], want_lin, "linear w")
+    if grid == "range":  # (every n > 0: W(n, z) in every slot, under both rules)
+        assert (g["n"] > 0).all() and np.count_nonzero(want) > 20
+        return
     kept = ~(g["n"][g["idx"]] > 0)
     if learn:  # -0.0, subnormals and NaN kept, the W branch taken elsewhere
         assert (np.signbit(want[kept]) & (want[kept] == 0)).any() and (np.abs(want[kept]) == f32(3e-41)).any()
         assert np.isnan(want[kept]).any() and np.count_nonzero(want[~kept]) > 20
     else:
         assert not (np.abs(want) == f32(3e-41)).any()
+
+
+@pytest.mark.parametrize("hp", list(HP_SETS.values()), ids=list(HP_SETS))
+def test_refresh_rule_is_the_compiled_references(hp):
+    """util.ftrl_w (numpy, an IEEE double divide), the oracle's and the compiled reference's
+    maybe_zero_weight on every (n, z) of both grids and on subnormal, huge and zero operands: with l1 = 0
+    the numerator nextafter(l1) is subnormal, with l2 = 0 and beta = 0 the denominator of n = 0 is zero."""
+    if not pyoracle.have_ref():
+        pytest.skip("oracle/_ref not built here")
+    o = CpuModel("oracle", "LR", 4, **hp)
+    r = CpuModel("ref", "LR", 4, **hp)
+    pairs = set()
+    for grid in GRIDS.values():
+        gn, gz, _ = grid(hp)
+        pairs.update(zip(bits(gn).tolist(), bits(gz).tolist()))
+    ns = np.array([0, 2.0 ** -149, 2.0 ** -97, 2.0 ** -96, 2.0 ** -70, 0.37, 2.0 ** 96, 2.0 ** 118, 3e38], f32)
+    l1 = f32(hp["w_l1"])
+    zs = np.array([2.0 ** -149, -2.0 ** -149, 1e-40, -3e-39, 0.3, -0.011, 2.0 ** 61, -2.0 ** 61,
+                   np.nextafter(l1, f32(np.inf)), -np.nextafter(l1, f32(np.inf))], f32)
+    pairs.update((a, b) for a in bits(ns).tolist() for b in bits(zs).tolist())
+    pairs = np.array(sorted(pairs), np.uint32)
+    n, z = pairs[:, 0].copy().view(f32), pairs[:, 1].copy().view(f32)
+    want = np.array([ftrl_w(a, b, hp) for a, b in zip(n, z)], f32)
+    assert_bitwise(np.array([r.maybe_zero_weight(a, b) for a, b in zip(n, z)], f32), want, "reference")
+    assert_bitwise(np.array([o.maybe_zero_weight(a, b) for a, b in zip(n, z)], f32), want, "oracle")
+    if l1 == 0:
+        sub = (np.abs(z) < np.finfo(f32).tiny) & (z != 0) & (n > 0) & np.isfinite(n)
+        assert sub.sum() > 10 and np.count_nonzero(want[sub]) > 0, "subnormal numerators reach the divide"
+    if hp["w_l2"] == 0 and hp["w_beta"] == 0:
+        assert np.isinf(want[(n == 0) & (np.abs(z) > l1)]).all(), "x / 0 is inf, as in the reference"
+
+
+def test_table_of_hyper_parameter_sets_reaches_every_state_of_the_flags():
+    """util.HP_SETS: every reachable (fast_div, fast_w), both inclusive ends of both ranges and the
+    first float outside each, the zero settings, and the two sets every older test uses."""
+    flags = {name: arith_flags(hp) for name, hp in HP_SETS.items()}
+    assert set(flags.values()) == {(1, 1), (1, 0), (0, 0)}
+    assert HP_SETS["default_hp"] is DEFAULT_HP and HP_SETS["stress_hp"] is STRESS_HP
+    lo, hi = f32(2.0 ** -30), f32(2.0 ** 30)
+    alphas = {f32(hp["w_alpha"]) for hp in HP_SETS.values()}
+    assert {lo, hi, np.nextafter(lo, f32(0)), np.nextafter(hi, f32(np.inf)), f32(3e-38), f32(1.3 * 2.0 ** 31)} <= alphas
+    lo, hi = f32(2.0 ** -40), f32(2.0 ** 40)
+    betas = {f32(hp["w_beta"]) for hp in HP_SETS.values() if arith_flags(hp)[0]}
+    assert {f32(0), lo, hi, np.nextafter(lo, f32(0)), np.nextafter(hi, f32(np.inf)), f32(1.4e-38)} <= betas
+    for name, want in (("alpha_2m30", (1, 1)), ("alpha_2p30", (1, 1)), ("alpha_below_2m30", (0, 0)),
+                       ("alpha_above_2p30", (0, 0)), ("beta_2m40", (1, 1)), ("beta_2p40", (1, 1)),
+                       ("beta_below_2m40", (1, 0)), ("beta_above_2p40", (1, 0)), ("beta_zero", (1, 0))):
+        assert flags[name] == want, name
+    assert any(hp["w_l1"] == 0 for hp in HP_SETS.values()) and any(hp["w_l2"] == 0 for hp in HP_SETS.values())
+    for hp in HP_SETS.values():  # (exactly the float32 the engine gets, but for the two older sets)
+        assert all(np.float32(v) == v for v in hp.values()) or hp in (DEFAULT_HP, STRESS_HP)
+
+
+# The operands with which tests/test_gpu_arith_paths.py tells each guard of the short divide from its
+# absence: (alpha, x) with x outside the guard -- or alpha outside [2^-30, 2^30] -- and other bits.
+DIV_DISCRIMINATORS = dict(
+    below_2m60=(1e-4, f32(1.4e-38)),         # beta + sqrt(0) with beta = 1.4e-38: under div_fast_ok's 2^-60
+    alpha_out_of_range=(3e-38, f32(2.0 ** 59)),  # sqrt(2^118): inside div_fast_ok, x * (1 / alpha) overflows
+    above_2p60=(2.0 ** -30, f32(2.0 ** 100)))    # beta = 2^100: over div_fast_ok's 2^60, x * 2^30 overflows
+
+
+def test_short_divide_is_the_ieee_divide_inside_its_guards_and_not_outside():
+    """fo_div_alpha_fast (the engine's div_alpha_fast, restated with explicit fmaf) against x / alpha:
+    no differing bits for any alpha of util.HP_SETS in [2^-30, 2^30] over x = +-2^e * significand, e from
+    -60 to 60 in steps of 5 and the guard's last binade, 2^16 significands each (the top and bottom 2^14
+    of the binade and a random rest) -- the rounding of the quotient depends on the significands only
+    while nothing under- or overflows, which is why the engine's create-time proof checks one pair of
+    binades.  And outside each guard an operand that does give other bits."""
+    rng = np.random.default_rng(3)
+    sig = np.concatenate([np.arange(1 << 14), (1 << 23) - 1 - np.arange(1 << 14),
+                          rng.integers(0, 1 << 23, (1 << 16) - (1 << 15))]).astype(np.uint32)
+    assert sig.size == 1 << 16
+    exps = sorted(set(range(-60, 60, 5)) | {59})  # (and 2^60 itself, the guard's last value, below)
+    x = np.concatenate([((np.uint32(e + 127) << np.uint32(23)) | sig).view(f32) for e in exps] + [f32([2.0 ** 60, 0.0])])
+    x = np.concatenate([x, -x[:-1]])
+    assert div_fast_ok(x).all() and x.size >= 2 * len(exps) << 16
+    alphas = sorted({f32(hp["w_alpha"]) for hp in HP_SETS.values() if arith_flags(hp)[0]})
+    assert len(alphas) >= 7 and f32(2.0 ** -30) in alphas and f32(2.0 ** 30) in alphas
+    for a in alphas:
+        quick, exact = pyoracle.div_alpha_fast(a, x)
+        with np.errstate(all="ignore"):
+            assert_bitwise(exact, x / a, "the C divide is numpy's, alpha = %r" % a)
+        assert_bitwise(quick, exact, "alpha = %r" % a)
+        assert np.isfinite(exact).all()
+    for name, (a, v) in DIV_DISCRIMINATORS.items():
+        quick, exact = pyoracle.div_alpha_fast(a, np.array([v], f32))
+        in_guard = bool(div_fast_ok(v)) and arith_flags(dict(w_alpha=a, w_beta=1.0))[0] == 1
+        assert not in_guard, name
+        assert bits(quick)[0] != bits(exact)[0] and not (np.isnan(quick[0]) and np.isnan(exact[0])), (
+            name, quick, exact)

@@ -14,6 +14,73 @@ DEFAULT_HP = dict(w_alpha=1e-4, w_beta=1.0, w_l1=0.1, w_l2=5.0)
 STRESS_HP = dict(w_alpha=0.1, w_beta=1.0, w_l1=0.01, w_l2=0.1)
 
 
+def _hp(alpha, beta, l1, l2):
+    """A hyper-parameter tuple whose values are exactly the float32s the engine and the oracle get."""
+    return {key: float(np.float32(v)) for key, v in zip(("w_alpha", "w_beta", "w_l1", "w_l2"), (alpha, beta, l1, l2))}
+
+
+_F = np.float32
+_INF = _F(np.inf)
+# Every state of the engine's create-time arithmetic flags (ffm_engine_create: fast_div needs alpha in
+# [2^-30, 2^30], fast_w needs fast_div and beta in [2^-40, 2^40]) with both inclusive ends of both ranges
+# and the first float outside each; the ordinary FTRL settings l1 = 0, l2 = 0, beta = 0; in-range sets
+# that are not powers of two.  The sets with a large alpha take l2 = 5: W = -num / (l2 + tiny).
+HP_SETS = {
+    "default_hp": DEFAULT_HP,
+    "stress_hp": STRESS_HP,
+    "alpha_2m30": _hp(2.0 ** -30, 1.0, 0.01, 0.1),
+    "alpha_below_2m30": _hp(np.nextafter(_F(2.0 ** -30), _F(0)), 1.0, 0.01, 0.1),
+    "alpha_2p30": _hp(2.0 ** 30, 1.0, 0.01, 5.0),
+    "alpha_above_2p30": _hp(np.nextafter(_F(2.0 ** 30), _INF), 1.0, 0.01, 5.0),
+    "alpha_3e-38": _hp(3e-38, 1.0, 0.01, 0.1),
+    "alpha_1.3x2p31": _hp(1.3 * 2.0 ** 31, 1.0, 0.01, 5.0),
+    "beta_zero": _hp(0.1, 0.0, 0.01, 0.1),
+    "beta_2m40": _hp(0.1, 2.0 ** -40, 0.01, 0.1),
+    "beta_below_2m40": _hp(0.1, np.nextafter(_F(2.0 ** -40), _F(0)), 0.01, 0.1),
+    "beta_2p40": _hp(0.1, 2.0 ** 40, 0.01, 0.1),
+    "beta_above_2p40": _hp(0.1, np.nextafter(_F(2.0 ** 40), _INF), 0.01, 0.1),
+    "beta_1.4e-38": _hp(1e-4, 1.4e-38, 0.1, 5.0),
+    "l1_zero": _hp(0.1, 1.0, 0.0, 0.1),
+    "l2_zero": _hp(0.1, 1.0, 0.01, 0.0),
+    "l1_zero_beta_zero": _hp(0.1, 0.0, 0.0, 0.1),
+    "l2_zero_beta_zero": _hp(0.1, 0.0, 0.01, 0.0),
+    "all_zero": _hp(0.1, 0.0, 0.0, 0.0),
+    "alpha_0.3": _hp(0.3, 0.7, 0.02, 0.3),
+    "alpha_0.05": _hp(0.05, 1.0, 0.01, 1.0),
+    "ones": _hp(1.0, 1.0, 1.0, 1.0),
+}
+
+
+def arith_flags(hp):
+    """(fast_div, fast_w) as ffm_engine_create sets them (engine.hip), the create-time proof of the
+    short divide taken to pass for every alpha in range (tests/test_block_semantics.py checks the C
+    restatement of that sequence for the alphas of HP_SETS)."""
+    a, b = _F(hp["w_alpha"]), _F(hp["w_beta"])
+    fast_div = bool(_F(2.0 ** -30) <= a <= _F(2.0 ** 30))
+    fast_w = bool(fast_div and _F(2.0 ** -40) <= b <= _F(2.0 ** 40))
+    return int(fast_div), int(fast_w)
+
+
+# The operand guards of the short sequences (ftrl_math.h, kernels_fold.h), restated on float32 arrays.
+def sqrt_fast_ok(x):
+    """+0 or [2^-96, 2^96]."""
+    x = np.asarray(x, _F)
+    return (bits(x) == 0) | ((x >= _F(2.0 ** -96)) & (x <= _F(2.0 ** 96)))
+
+
+def chain_operand_ok(x):
+    """[2^-70, 2^96] (also fold_strict_ok; fold_zero_ok adds +0): false for 0, negative, NaN, inf."""
+    x = np.asarray(x, _F)
+    return (x >= _F(2.0 ** -70)) & (x <= _F(2.0 ** 96))
+
+
+def div_fast_ok(x):
+    """+0 or |x| in [2^-60, 2^60]."""
+    x = np.asarray(x, _F)
+    ax = np.abs(x)
+    return (bits(x) == 0) | ((ax >= _F(2.0 ** -60)) & (ax <= _F(2.0 ** 60)))
+
+
 def golden_cases():
     """All replayable cases (those written by make_golden.run_case)."""
     out = []
@@ -227,7 +294,7 @@ def ftrl_w(n, z, hp):
     with np.errstate(all="ignore"):
         num = f(z - f((f(1) if z > 0 else f(-1)) * l1))
         den = f(l2 + f(f(b + np.sqrt(n)) / a))
-    return f(-1.0 * float(num) / float(den))
+        return f(np.float64(-1.0) * np.float64(num) / np.float64(den))  # (IEEE: x / 0 is inf or NaN)
 
 
 def latent_w(n, z, w_old, hp, learn):
@@ -257,15 +324,38 @@ def special_grid(hp, seed=0):
     return np.array(n, f), np.array(z, f), np.array(w, f)
 
 
-def grid_block(mt, k, hp, occurrences=1, seed=0):
-    """special_grid injected into a zero model as latent and as linear accumulators, and a block
+def range_grid(hp, seed=0):
+    """A second grid, laid out like special_grid, on the operand guards of the short square root and
+    divide: n in {every guard edge 2^-96, 2^-70, 2^96 with its two neighbours, 2^118, FLT_MAX} x z in
+    {special_grid's z, +-2^61 (a divide operand above 2^60)} x the same four kinds of w_old."""
+    f = np.float32
+    ns = []
+    for e in (-96, -70, 96):
+        v = f(2.0 ** e)
+        ns += [np.nextafter(v, f(0)), v, np.nextafter(v, f(np.inf))]
+    ns = np.array(ns + [f(2.0 ** 118), np.finfo(f).max], f)
+    l1 = f(hp["w_l1"])
+    zs = np.array([s * v for v in (f(0), l1, np.nextafter(l1, f(np.inf)), f(0.3), f(2.0 ** 61)) for s in (1, -1)], f)
+    rng = np.random.default_rng(seed)
+    n, z, w = [], [], []
+    for wk in range(4):
+        for a in ns:
+            for b in zs:
+                n.append(a)
+                z.append(b)
+                w.append((f(rng.normal(0, 0.02)), f(-0.0), f(3e-41), f(np.nan))[wk])
+    return np.array(n, f), np.array(z, f), np.array(w, f)
+
+
+def grid_block(mt, k, hp, occurrences=1, seed=0, grid=None):
+    """A grid of (n, z, w_old) -- special_grid(hp, seed) unless `grid` gives another -- injected into a zero model as latent and as linear accumulators, and a block
     that touches each of them `occurrences` times.  FFM (F = 2): field 0 holds ids [0, P), field 1
     ids [P, nf); row r pairs ids r and P + r, so the slot of the other field is touched.  FM: row r
     holds ids 2r and 2r + 1, every factor touched.  Then rows of one entry each (FFM: in field 1)
     touch the ids that carry the linear grid and no latent slot of the grid.  Returns a dict:
     nf, F, k, state, block, field_start, slots (the latent elements (rows, columns) of the grid),
     idx (their grid index), lin (linear ids), lidx (their grid index), n, z, w (the grid)."""
-    gn, gz, gw = special_grid(hp, seed)
+    gn, gz, gw = special_grid(hp, seed) if grid is None else grid
     N = len(gn)
     F = 2 if mt == "FFM" else 1
     P = -(-N // k)  # latent rows per field (FFM) / latent features (FM, rounded up to pairs)
