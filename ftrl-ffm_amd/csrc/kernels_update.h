@@ -230,6 +230,46 @@ __global__ __launch_bounds__(kUpdThreads) void bias_update_kernel(ModelDev m, in
 //    (n, z) like the reference's one-thread loop (ffm.cpp:104-120).
 // (one element e of the stored record of the feature described by ud = {feature, start, count, field};
 // cm = its serial slots)
+// The row-order walk of ONE row that holds the feature d >= 2 times (a repeated id; occurrences
+// s.occ2[occ0 .. occ0 + d), ascending entries), slot fp, factor kk: the touches in the order of the
+// reference's pair loop (ffm.cpp:104-120: a outer, c inner over the row's entries, a < c) -- with
+// occurrences e1 < e2 and entries q of field fp that is (q, e1), (q, e2) for each q < e1 in turn,
+// (e1, q) for every q > e1, (q, e2) for e1 < q < e2, (e2, q) for q > e2 -- not occurrence by occurrence,
+// which adds the same terms to n in another order.  Where the feature's own field is fp its
+// occurrences are each other's partners: the pair (e1, e2) steps the slot from e1's side, then e2's.
+__device__ inline bool ffm_walk_repeated(const ModelDev &m, const Rows &rows, const Scratch &s, int occ0, int d,
+                                         int r, int fp, int kk, float w, float &n, float &z) {
+  constexpr int kEnd = 0x7fffffff;
+  const float tg = s.tg[r];
+  bool touched = false;
+  auto touch = [&](int e, int q) {  // occurrence e of the feature, partner entry q of field fp
+    const int fm = rows.field[e];
+    if (!owns_pair(m, fm, fp)) return;
+    const float vp = m.lat[w_slot_offset(m, rows.feat[q], fp, fm) + kk];
+    ffm_touch(m.h, e < q, tg, rows.val[e], rows.val[q], vp, w, n, z);
+    touched = true;
+  };
+  // a, then c > a, over the merged ascending entries of the two lists
+  int ea = 0, qa = s.head[static_cast<int64_t>(r) * m.n_fields + fp];
+  while (ea < d || qa >= 0) {
+    const int pe = ea < d ? s.occ2[occ0 + ea].x : kEnd, pq = qa >= 0 ? qa : kEnd;
+    const int a = pe < pq ? pe : pq;
+    const bool a_occ = pe == a, a_partner = pq == a;
+    if (a_occ) ea++;
+    if (a_partner) qa = s.next[qa];
+    int ec = ea, qc = qa;
+    while (ec < d || qc >= 0) {
+      const int ce = ec < d ? s.occ2[occ0 + ec].x : kEnd, cq = qc >= 0 ? qc : kEnd;
+      const int cc = ce < cq ? ce : cq;
+      if (a_occ && cq == cc) touch(a, cc);
+      if (a_partner && ce == cc) touch(cc, a);
+      if (ce == cc) ec++;
+      if (cq == cc) qc = s.next[qc];
+    }
+  }
+  return touched;
+}
+
 __device__ __forceinline__ void ffm_generic_element(const ModelDev &m, const Rows &rows, const Scratch &s,
                                                     int4 ud, unsigned long long cm, int e, int serial_only) {
   const int RL = m.row_len, k = m.n_factors, F = m.n_fields;
@@ -249,6 +289,13 @@ __device__ __forceinline__ void ffm_generic_element(const ModelDev &m, const Row
     for (int t = 0; t < c; t++) {
       const int2 pr = s.occ2[start + t];
       const int p = pr.x, r = pr.y;
+      int d = 1;  // the feature's occurrences in this row (neighbours: equal keys are in entry order)
+      while (t + d < c && s.occ2[start + t + d].y == r) d++;
+      if (d > 1) {
+        touched |= ffm_walk_repeated(m, rows, s, start + t, d, r, fp, kk, w, n, z);
+        t += d - 1;
+        continue;
+      }
       const int fm = rows.field[p];
       if (!owns_pair(m, fm, fp)) continue;
       const float tg = s.tg[r], xm = rows.val[p];

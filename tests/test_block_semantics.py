@@ -387,6 +387,158 @@ def test_occurrence_block_builder_hits_every_count_exactly(F, n_rows, counts):
     assert 0 < order.count(False) < n_rows
 
 
+def _in_range(blk, nf, F):
+    return (blk.feat >= 0) & (blk.feat < nf) & (blk.field >= 0) & (blk.field < F)
+
+
+@pytest.mark.parametrize("mt", ["FFM", "FM"])
+def test_row_length_block_builder_has_every_listed_property(mt):
+    """The builder the row-length GPU tests use (util.row_length_block, row_cap_prefixes), for FFM F = 6
+    and for FM: every property its docstring lists, asserted from the arrays."""
+    from util import (ROW_CAPS, ROW_ERASED_AT, ROW_FIELDS, ROW_IDS_PER_FIELD, ROW_LENGTHS, ROW_POOL,
+                      ROW_POSITION_CLASSES, ROW_SEED, row_cap_prefixes, row_length_block)
+    F, per, repeats = ROW_FIELDS, ROW_IDS_PER_FIELD, 3
+    for seed in (ROW_SEED, ROW_SEED + 1, ROW_SEED + 2):
+        blk, nf = row_length_block(mt, F, per, seed)
+        assert nf == F * per
+        lens = np.diff(blk.row_ptr)
+        n_rows = blk.n_rows
+        # the ladder, shuffled, between an empty first row and last rows of 0 and 1 entries; one
+        # two-entry row more, since 3 * 27 + 3 is a multiple of 4
+        assert n_rows == len(ROW_LENGTHS) * repeats + 4 and n_rows % 4 != 0
+        assert lens[0] == 0 and lens[-2] == 0 and lens[-1] == 1
+        extra = {0: 2, 1: 1, 2: 1}
+        for n in ROW_LENGTHS:
+            assert (lens == n).sum() == repeats + extra.get(n, 0), n
+        assert set(lens.tolist()) == set(ROW_LENGTHS)
+        body = lens[2:-2]
+        assert (np.diff(body) < 0).any() and (np.diff(body) > 0).any()
+        assert blk.label.size == n_rows and set(blk.label.tolist()) == {0, 1}
+        row_of = np.repeat(np.arange(n_rows), lens)
+        pos = np.arange(lens.sum()) - blk.row_ptr[:-1][row_of]
+        ok = _in_range(blk, nf, F if mt == "FFM" else 1)
+        # FM / LR: field 0 everywhere; FFM: the field of an id (where it was not put out of range)
+        if mt == "FFM":
+            fld_ok = (blk.field >= 0) & (blk.field < F)
+            assert np.array_equal(blk.field[ok], blk.feat[ok] // per)
+            multi = [np.unique(blk.field[blk.row_ptr[r]:blk.row_ptr[r + 1]]).size < lens[r] for r in range(n_rows)
+                     if lens[r] >= 8]
+            assert all(multi), "fields repeat within a row"
+        else:
+            assert not blk.field.any()
+        # once-only ids and pool ids, both in every position class
+        u, inv, cnt = np.unique(blk.feat[ok], return_inverse=True, return_counts=True)
+        once = np.zeros(ok.size, bool)
+        once[ok] = cnt[inv] == 1
+        pooled = ok & (blk.feat % per < ROW_POOL)
+        assert 0.42 < once.sum() / ok.sum() < 0.58, once.sum() / ok.sum()
+        assert not (once & pooled).sum() > 0.02 * ok.sum()  # (a pool id may happen to occur once)
+        assert (ok & ~once & ~pooled).sum() <= 2 * 10  # (only the ids that a row holds twice)
+        pool_ids, pool_cnt = np.unique(blk.feat[pooled], return_counts=True)
+        assert pool_ids.size > 0.9 * F * ROW_POOL and np.median(pool_cnt) >= 4
+        rows_of_pool = [np.unique(row_of[blk.feat == i]).size for i in pool_ids[pool_cnt >= 4][:50]]
+        assert min(rows_of_pool) >= 3, "pool features repeat across rows"
+        for lo, hi in ROW_POSITION_CLASSES:
+            in_class = (pos >= lo) & (pos < hi)
+            assert (once & in_class).sum() >= 8 and (pooled & ~once & in_class).sum() >= 8, (lo, hi)
+        # the erased entries: in every fifth non-empty row (16 rows), at ROW_ERASED_AT clamped to the
+        # row's last entry and nowhere else; ids -7 and n_feats + 3, FFM also fields F + 2 and -1
+        bad_rows = np.unique(row_of[~ok])
+        assert bad_rows.size == (len(ROW_LENGTHS) - 1) * repeats // 5 + 1
+        for r in bad_rows:
+            want = sorted({min(p, lens[r] - 1) for p in ROW_ERASED_AT})
+            assert pos[~ok & (row_of == r)].tolist() == want, (r, lens[r])
+        bad_lens = set(lens[bad_rows].tolist())
+        assert {1, 3, 5, 64, 65, 128, 130, 150} <= bad_lens, bad_lens
+        assert set(blk.feat[(blk.feat < 0) | (blk.feat >= nf)].tolist()) == {-7, nf + 3}
+        if mt == "FFM":
+            assert set(blk.field[~fld_ok].tolist()) == {F + 2, -1}
+            assert 0 < np.unique(row_of[~fld_ok]).size < bad_rows.size
+            assert ((blk.feat[~fld_ok] >= 0) & (blk.feat[~fld_ok] < nf)).all()
+        for p in ROW_ERASED_AT:  # a parked position, a chunk, both sides of the 64-entry pass boundary
+            assert (~ok & (pos == p) & (lens[row_of] > 64)).any(), p
+        # ... and the lengths still count them: a row of more than 128 entries with at most 128 survivors
+        nv = np.bincount(row_of[ok], minlength=n_rows)
+        assert ((lens > 128) & (nv <= 128)).any() and ((lens > 64) & (nv <= 64)).any()
+        assert ((lens == 130) & (nv == 125)).any() and ((lens == 128) & (nv == 123)).any()
+        # one id twice, below position 64 and above, in ten rows of at least 66 entries
+        twice = 0
+        for r in range(n_rows):
+            sl = slice(blk.row_ptr[r], blk.row_ptr[r + 1])
+            ids, okr = blk.feat[sl], ok[sl]
+            uu, cc = np.unique(ids[okr], return_counts=True)
+            if (cc > 1).any():
+                assert lens[r] >= 66 and (cc > 1).sum() == 1 and cc.max() == 2
+                at = np.flatnonzero(okr & (ids == uu[cc > 1][0]))
+                assert 5 <= at[0] < 63 and at[1] >= 65
+                twice += 1
+        assert twice == 10
+        # FFM: some rows in descending field order, the others not
+        if mt == "FFM":
+            desc = [r for r in range(n_rows) if lens[r] >= 8 and r not in set(bad_rows.tolist())
+                    and (np.diff(blk.field[blk.row_ptr[r]:blk.row_ptr[r + 1]]) <= 0).all()]
+            assert 3 <= len(desc) <= 12
+        # values: 1.0 for half of the entries, [0.25, 1.25) otherwise
+        assert 0.45 < (blk.val == 1.0).mean() < 0.55
+        assert (blk.val >= 0.25).all() and (blk.val < 1.25).all() and blk.val.dtype == np.float32
+        # the pieces: rows in a stable order by length, the longest exactly L, an empty row first
+        order = np.argsort(lens, kind="stable")
+        pieces = list(row_cap_prefixes(blk))
+        assert len(pieces) == len(ROW_CAPS) == 8
+        for cap, piece in zip(ROW_CAPS, pieces):
+            pl = np.diff(piece.row_ptr)
+            assert pl.max() == cap and pl[0] == 0 and (np.diff(pl) >= 0).all()
+            assert piece.n_rows == (lens <= cap).sum()
+            idx = order[:piece.n_rows]
+            assert np.array_equal(piece.label, blk.label[idx])
+            assert np.array_equal(piece.feat, np.concatenate([blk.feat[blk.row_ptr[r]:blk.row_ptr[r + 1]] for r in idx]))
+            assert np.array_equal(piece.val, np.concatenate([blk.val[blk.row_ptr[r]:blk.row_ptr[r + 1]] for r in idx]))
+        assert pieces[-1].n_rows == n_rows
+
+
+def _assert_all_finite(o, logits, what):
+    assert np.isfinite(logits).all(), what + ": logits"
+    for key, a in o.get_state().items():
+        assert np.isfinite(a).all(), "%s: %s" % (what, key)
+
+
+def test_oracle_stays_finite_on_every_row_length_case():
+    """What keeps tests/test_gpu_row_lengths.py from passing on NaNs alone: on every shape of
+    util.ROW_SHAPES, from the warm start state, the oracle's logits of both training blocks, its
+    predict outputs and its whole state (so every word it touched) are finite -- all of them --; the
+    same over the row-cap pieces chained as blocks, for the shapes that run them (util.row_pieces_shape),
+    all logits below 16; and training does touch the state."""
+    from util import (ROW_ENTRY_SHAPES, ROW_SEED, ROW_SHAPES, row_cap_prefixes, row_length_case, row_pieces_shape,
+                      row_shape_id)
+    top = 0.0
+    for shape in ROW_SHAPES:
+        o, st, blocks, _ = row_length_case(shape, ROW_SEED)
+        what = row_shape_id(shape)
+        for j in (0, 1):
+            lg, loss = o.train_batch(blocks[j])
+            _assert_all_finite(o, lg, "%s block %d" % (what, j))
+            assert np.isfinite(loss)
+            top = max(top, float(np.abs(lg).max()))
+        after = o.get_state()
+        assert sum(int(np.count_nonzero(after[key] != st[key])) for key in after) > 4000
+        for prob in (False, True):
+            out, loss = o.predict_batch(blocks[2], output_prob=prob)
+            assert np.isfinite(out).all() and np.isfinite(loss), what + " predict"
+    for shape in ROW_ENTRY_SHAPES:
+        shape = row_pieces_shape(shape)
+        o, st, blocks, _ = row_length_case(shape, ROW_SEED)
+        what = row_shape_id(shape)
+        for j in (0, 1):
+            for piece in row_cap_prefixes(blocks[j]):
+                lg, loss = o.train_batch(piece)
+                _assert_all_finite(o, lg, "%s pieces of block %d" % (what, j))
+                assert np.isfinite(loss) and np.abs(lg).max() < 16.0, what
+        for piece in row_cap_prefixes(blocks[2]):
+            out, loss = o.predict_batch(piece)
+            assert np.isfinite(out).all() and np.isfinite(loss), what + " predict pieces"
+    assert top < 16.0, top  # (sigmoid's argument stays out of the range where a float sigmoid is exactly 1)
+
+
 GRIDS = dict(special=special_grid, range=range_grid)
 
 

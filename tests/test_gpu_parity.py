@@ -5,7 +5,7 @@ Tolerances (written here, as the contract asks): logits, tmp_grad-driven state (
 weights are compared BIT FOR BIT with the oracle / the reference's golden outputs -- the kernels
 perform the reference's fp32 operations in the reference's order (csrc/ftrl_math.h).  The only
 floating-point slack is on double logloss sums, where device exp/log may differ from glibc in the
-last ulp: |gpu - cpu| <= 1e-12 * max(1, |cpu|) per row summed, stated as LOSS_RTOL below.  The
+last ulp: |gpu - cpu| <= 1e-12 * max(1, |cpu|) per row summed, stated as util.LOSS_RTOL.  The
 north-star bound (epoch logloss within 1e-4 of the reference CPU path) is asserted on top.
 """
 import os
@@ -18,19 +18,11 @@ import torch  # noqa: F401  -- first: torch bundles its own HIP runtime; loading
 import ftrl_ffm_amd as fa
 from ftrl_ffm_amd import synth
 from oracle.pyoracle import CpuModel, Csr
-from util import (DEFAULT_HP, GOLDEN, STRESS_HP, STATE_KEYS, assert_bitwise, assert_state_bitwise,
-                  bundled_rows, golden_cases, load_case, make_cpu, rand_state)
+from util import (DEFAULT_HP, GOLDEN, LOSS_RTOL, STRESS_HP, STATE_KEYS, assert_bitwise, assert_state_bitwise,
+                  bundled_rows, golden_cases, load_case, loss_close, make_cpu, rand_state)
 
 pytestmark = pytest.mark.gpu
-LOSS_RTOL = 1e-12
-
-
-def loss_close(a, b):
-    if np.isnan(a) or np.isnan(b):
-        return np.isnan(a) and np.isnan(b)
-    if np.isinf(a) or np.isinf(b):
-        return a == b
-    return abs(a - b) <= LOSS_RTOL * max(1.0, abs(b)) * 64
+assert LOSS_RTOL == 1e-12  # (util.loss_close applies it; shared with test_gpu_row_lengths.py)
 
 
 def engine_for(case, **kw):

@@ -389,8 +389,9 @@ def test_duplicate_ids_one_id_under_two_fields_and_65_fields():
     running (n, z).  With TWO copies of an entry that order is the reference's pair order and the
     engine must equal the oracle bit for bit.  When one slot receives touches from several
     occurrences of its feature inside one row (an id under two fields next to a multi-valued
-    partner field, three copies of an entry), the engine walks them occurrence by occurrence, the
-    oracle pair by pair: the same touches in another order, compared to rtol 1e-5 / atol 1e-7.
+    partner field, three copies of an entry), both walk them pair by pair (ffm_walk_repeated;
+    test_gpu_row_lengths.py pins that order bit for bit on long rows that hold one id twice); the
+    foreign-field case here keeps its older comparison to rtol 1e-5 / atol 1e-7.
     n_fields = 65 takes the paths without 64-bit field masks."""
     from util import assert_close, STATE_KEYS
     rng = np.random.default_rng(31)

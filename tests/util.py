@@ -262,6 +262,231 @@ def irregular_copy(blk, seed=0, n_reversed=64):
                blk.label.copy())
 
 
+# The entry counts of a row at which a row kernel changes path, each edge with its neighbours:
+# 0 (no entry: the bias alone; row 0 stores the refreshed bias) | 1, 2, 3 (fm_row_wave_kernel: a
+# partly filled parking step, kFmPark = 4) | 4, 5 (all parked | the first chunk of kFmChunk = 8) | 12,
+# 13 (4 + 8: a whole chunk | one entry of the next), 11, 20 (partial and whole chunks; the lengths the
+# older suites use) | 31, 32, 33 (half a wave of entries) | 63, 64, 65, 66 (fm_row_wave_kernel: the
+# linear part runs lane = entry, 64 per pass -- a later pass reads lin_n / lin_z / lin_w back;
+# ffm_predict_wave_kernel: staging passes of 64 entries, the survivors compacted across them;
+# ffm_row_kernel: 64 entries are 2016 pairs, one pass under kTermsCap = 2048, 65 are 2080, two) | 71,
+# 72 (where the older suites' long rows begin) | 91, 92 (ffm_row_kernel: 4095 pairs, two passes | 4186,
+# three) | 127, 128, 129, 130 (kPredLdsCap = 128: a longer row is the second predict launch's, and a
+# third 64-entry pass of the FM linear part) | 150 (the longest row an older suite feeds).
+ROW_LENGTHS = (0, 1, 2, 3, 4, 5, 8, 11, 12, 13, 20, 31, 32, 33, 63, 64, 65, 66, 71, 72, 91, 92, 127, 128,
+               129, 130, 150)
+ROW_POOL = 48                        # ids per field shared by all rows of a row_length_block
+ROW_ERASED_AT = (0, 3, 4, 63, 64)    # positions erased in every fifth non-empty row (clamped to the last)
+ROW_CAPS = (1, 3, 5, 64, 65, 128, 129, 150)  # row_cap_prefixes: the longest row of each piece
+ROW_POSITION_CLASSES = ((0, 4), (4, 12), (12, 64), (64, 128), (128, 1 << 30))
+
+
+ROW_FIELDS, ROW_IDS_PER_FIELD = 6, 2000  # the model of the row-length cases: 12000 features
+# (model type, factors, hyper-parameters, learning variant) of tests/test_gpu_row_lengths.py; the CPU
+# side (tests/test_block_semantics.py) checks that the oracle stays finite on every one of them
+ROW_SHAPES = ([("FM", k, "stress_hp", False) for k in (8, 33, 64, 65, 128)] + [("LR", 1, "stress_hp", False)]
+              + [("FFM", k, "stress_hp", False) for k in (4, 6, 12, 16, 64)]
+              + [("FFM", 16, "default_hp", False), ("FM", 8, "default_hp", False),
+                 ("FM", 8, "stress_hp", True), ("FFM", 16, "stress_hp", True)])
+
+
+# the shapes whose every entry point is compared (host calls on the whole block and on its row-cap
+# pieces, device calls, the split step)
+ROW_ENTRY_SHAPES = [("FM", 8, "stress_hp", False), ("FM", 128, "stress_hp", False), ("LR", 1, "stress_hp", False),
+                    ("FFM", 16, "stress_hp", False)]
+
+
+
+def row_pieces_shape(shape):
+    """The shape with which the row-cap pieces are chained (16 training blocks that hold the short rows
+    up to eight times each).  FM takes HP_SETS["alpha_0.05"] there: under the stress set its logits
+    reach 65 (k = 8) and pass 2000 (k = 128) along the chain (the oracle on the CPU; sigmoid saturated,
+    the logloss inf / NaN), with alpha = 0.05 and l2 = 1 they stay below 11.  LR and FFM keep their set
+    (|logit| < 6)."""
+    mt, k, hp_name, learn = shape
+    return (mt, k, "alpha_0.05", learn) if mt == "FM" else shape
+
+
+ROW_SEED = 40  # the cases' blocks are row_length_block seeds ROW_SEED, + 1 (trained), + 2 (predicted)
+
+
+def row_shape_id(shape):
+    mt, k, hp_name, learn = shape
+    return "%s-k%d-%s%s" % (mt, k, hp_name, "-learn" if learn else "")
+
+
+def row_length_case(shape, seed):
+    """(oracle model with the warm start state set, that state, three row_length_blocks of seeds seed,
+    seed + 1, seed + 2, n_feats) of one row-length case: two blocks to train, one to predict."""
+    mt, k, hp_name, learn = shape
+    blocks = [row_length_block(mt, ROW_FIELDS, ROW_IDS_PER_FIELD, seed + j)[0] for j in range(3)]
+    nf = ROW_FIELDS * ROW_IDS_PER_FIELD
+    o = CpuModel("oracle", mt, nf, ROW_FIELDS if mt == "FFM" else 1, k, learn=learn, **HP_SETS[hp_name])
+    st = row_length_state(o, seed + 100)
+    o.set_state(st)
+    return o, st, blocks, nf
+
+
+def take_rows(blk, idx):
+    """The block's rows `idx`, in that order."""
+    idx = np.asarray(idx, np.int64)
+    lens = np.diff(blk.row_ptr)[idx]
+    row_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    pos = np.concatenate([np.arange(blk.row_ptr[r], blk.row_ptr[r + 1]) for r in idx] + [np.zeros(0, np.int64)])
+    pos = pos.astype(np.int64)
+    return Csr(row_ptr, blk.field[pos].copy(), blk.feat[pos].copy(), blk.val[pos].copy(), blk.label[idx].copy())
+
+
+def row_length_block(model_type, n_fields, ids_per_field, seed, lengths=ROW_LENGTHS, repeats=3):
+    """A block whose rows have every length of `lengths`, `repeats` times each, in shuffled order,
+    between an empty first row and two last rows of 0 and 1 entries (one more two-entry row where
+    the count would be a multiple of 4, the rows per workgroup of both wave kernels).  Returns
+    (block, n_feats), n_feats = n_fields * ids_per_field; id i belongs to field i // ids_per_field
+    (FM / LR: the field array is 0 everywhere).
+
+    * Each entry is, by a fair coin, an id that occurs nowhere else in the block (the in-row
+      once-only update) or one of a pool of ROW_POOL ids per field shared by all rows (the update
+      kernels); no id twice in a row, so FFM's fields repeat within a row (serial slots).
+    * FFM: every seventh non-empty row lists its entries in descending field order.
+    * Every third row of at least 66 entries holds one id twice: the entry at a position in [5, 62]
+      again at a position from 65 on (the touch-by-touch walk).
+    * Every fifth non-empty row (all three counted in ladder order, whatever the seed: rows of 1, 3,
+      64, 128, 130 and 150 entries among them) has the entries at ROW_ERASED_AT (clamped to its last entry) replaced
+      by out-of-range ones: id -7 or n_feats + 3, in every other such row of FFM an out-of-range field
+      (n_fields + 2 or -1, the id kept).  The row's length still counts them.
+    * Values: 1.0 for half of the entries, uniform in [0.25, 1.25) otherwise; labels 1 in four of ten."""
+    rng = np.random.default_rng(seed)
+    F, per = int(n_fields), int(ids_per_field)
+    nf = F * per
+    ffm = model_type == "FFM"
+    assert per > ROW_POOL
+    # what each row is, counted over the non-empty rows in ladder order (so that which lengths are
+    # erased, reversed or hold an id twice does not depend on the seed): (length, erased, descending, twice)
+    specs, n_nonempty, n_long = [], 0, 0
+    for n in np.repeat(np.asarray(lengths, np.int64), repeats).tolist():
+        erased = n_nonempty // 5 if n > 0 and n_nonempty % 5 == 2 else -1
+        specs.append((n, erased, ffm and n > 0 and n_nonempty % 7 == 3, n >= 66 and n_long % 3 == 0))
+        n_nonempty += n > 0
+        n_long += n >= 66
+    specs = [specs[j] for j in rng.permutation(len(specs))]
+    plain = lambda n: (n, -1, False, False)  # noqa: E731
+    specs = [plain(0)] + ([plain(2)] if (len(specs) + 3) % 4 == 0 else []) + specs + [plain(0), plain(1)]
+    lens = np.array([sp[0] for sp in specs], np.int64)
+    pool = (np.arange(F)[:, None] * per + np.arange(ROW_POOL)[None, :]).reshape(-1)
+    fresh = rng.permutation(np.setdiff1d(np.arange(nf), pool))
+    assert fresh.size >= lens.sum(), "ids_per_field too small for once-only ids"
+    n_fresh = 0
+    fields, feats = [], []
+    for n, k5, descending, twice in specs:
+        once = rng.random(n) < 0.5
+        ids = np.empty(n, np.int64)
+        ids[once] = fresh[n_fresh:n_fresh + int(once.sum())]
+        n_fresh += int(once.sum())
+        ids[~once] = rng.choice(pool, int((~once).sum()), replace=False)
+        fld = ids // per
+        if descending:
+            order = np.argsort(-fld, kind="stable")
+            ids, fld = ids[order], fld[order]
+        if twice:
+            lo, hi = int(rng.integers(5, 63)), int(rng.integers(65, n))
+            ids[hi], fld[hi] = ids[lo], fld[lo]
+        if k5 >= 0:
+            for j, p in enumerate(sorted({min(p, n - 1) for p in ROW_ERASED_AT})):
+                if ffm and k5 % 2 == 1:
+                    fld[p] = F + 2 if (j + k5 // 2) % 2 == 0 else -1
+                else:
+                    ids[p] = -7 if (j + k5) % 2 == 0 else nf + 3
+        fields.append(fld)
+        feats.append(ids)
+    nnz = int(lens.sum())
+    val = (rng.random(nnz) + 0.25).astype(np.float32)
+    val[rng.random(nnz) < 0.5] = 1.0
+    label = (rng.random(lens.size) < 0.4).astype(np.int32)
+    field = np.concatenate(fields).astype(np.int32)
+    if not ffm:
+        field[:] = 0
+    row_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    return Csr(row_ptr, field, np.concatenate(feats).astype(np.int32), val, label), nf
+
+
+def row_cap_prefixes(blk, caps=ROW_CAPS):
+    """The block's rows in a stable order by length, cut after the last row of exactly L entries, for
+    each L of `caps`: pieces whose longest row is L, each beginning with the block's empty rows.  An
+    entry point that sizes its kernels by the longest row of the block runs with that row cap."""
+    lens = np.diff(blk.row_ptr)
+    order = np.argsort(lens, kind="stable")
+    for cap in caps:
+        assert (lens == cap).any() and lens[order[0]] == 0
+        yield take_rows(blk, order[:int(np.searchsorted(lens[order], cap, side="right"))])
+
+
+def row_length_state(model, seed):
+    """The warm start state of the row-length cases: rand_state with 0.05 added to vec_n and lin_n."""
+    st = rand_state(np.random.default_rng(seed), model)
+    for key in ("vec_n", "lin_n"):
+        st[key] += np.float32(0.05)
+    return st
+
+
+def row_lengths_of(blk, what):
+    """' (rows of N entries)' for the row index / the feature id `what` = ("row", r) / ("feat", i): the
+    length of that row, or the lengths of the rows that hold the feature."""
+    lens = np.diff(blk.row_ptr)
+    if what[0] == "row":
+        return "rows of %d entries (row %d)" % (lens[what[1]], what[1])
+    row_of = np.repeat(np.arange(blk.n_rows), lens)
+    held = sorted(set(lens[row_of[blk.feat == what[1]]].tolist()))
+    return "feature %d, held by rows of %s entries" % (what[1], "/".join(map(str, held)) or "no")
+
+
+def _first_difference(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    both_nan = (np.isnan(a) & np.isnan(b)).ravel()
+    bad = np.flatnonzero((bits(a).ravel() != bits(b).ravel()) & ~both_nan)
+    return int(bad[0]) if bad.size else None
+
+
+def assert_rows_bitwise(got, want, blk, what):
+    """assert_bitwise on one value per row of `blk`; the message names the first differing row's length
+    and every length that differs."""
+    try:
+        assert_bitwise(got, want, what)
+    except AssertionError as err:
+        a, b = np.ascontiguousarray(got), np.ascontiguousarray(want)
+        lens = np.diff(blk.row_ptr)
+        bad = (bits(a) != bits(b)) & ~(np.isnan(a) & np.isnan(b))
+        raise AssertionError("%s: first in %s; differing row lengths %s" % (
+            err, row_lengths_of(blk, ("row", _first_difference(got, want))),
+            sorted(set(lens[bad].tolist())))) from None
+
+
+def assert_state_rows_bitwise(got, want, blk, what):
+    """assert_state_bitwise; the message names the lengths of the rows that hold the first differing
+    feature (the bias belongs to every row)."""
+    for key in STATE_KEYS:
+        try:
+            assert_bitwise(got[key], want[key], what + ":" + key)
+        except AssertionError as err:
+            if key == "bias3":
+                raise
+            at = _first_difference(got[key], want[key])
+            width = got[key].shape[1] if got[key].ndim == 2 else 1
+            raise AssertionError("%s: %s" % (err, row_lengths_of(blk, ("feat", at // width)))) from None
+
+
+LOSS_RTOL = 1e-12
+
+
+def loss_close(a, b):
+    """Double logloss sums: device exp / log may differ from glibc in the last ulp, so |gpu - cpu| <=
+    1e-12 * max(1, |cpu|) per row summed (64 rows' worth); NaN with NaN, an infinity with itself."""
+    if np.isnan(a) or np.isnan(b):
+        return np.isnan(a) and np.isnan(b)
+    if np.isinf(a) or np.isinf(b):
+        return a == b
+    return abs(a - b) <= LOSS_RTOL * max(1.0, abs(b)) * 64
+
+
 def fast_state(rng, model, n_hi=1.0, n_add=0.0, z_sd=0.3, w_sd=0.02, n_zero=0.0):
     """rand_state drawn in float32 (large models): n ~ U(0, n_hi) + n_add, a fraction n_zero of
     vec_n set to 0, z ~ N(0, z_sd), w ~ N(0, w_sd)."""
