@@ -44,6 +44,7 @@
 #include "kernels_fm.h"
 #include "kernels_predict.h"
 #include "kernels_sort.h"
+#include "kernels_scan.h"
 
 using namespace ftrl_dev;
 

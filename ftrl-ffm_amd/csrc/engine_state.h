@@ -1,5 +1,6 @@
 // engine_state.h -- weights and optimizer state in and out of the engine: dense arrays in the
-// reference's save order <-> the stored records (get/set_weights, get/set_state, get/set_rows).
+// reference's save order <-> the stored records (get/set_weights, get/set_state, get/set_rows), and the
+// list of features that no longer hold their create-time state (ffm_engine_changed_features).
 // Part of engine.hip's translation unit (included inside its extern "C" block).
 
 // ---- dense <-> record layout transfers ----------------------------------------------------
@@ -127,4 +128,56 @@ int ffm_engine_set_rows(ffm_engine *e, int32_t n, const int32_t *feat_ids, const
   float *const lin[3] = {const_cast<float *>(lin_n), const_cast<float *>(lin_z), const_cast<float *>(lin_w)};
   float *const vec[3] = {const_cast<float *>(vec_n), const_cast<float *>(vec_z), const_cast<float *>(vec_w)};
   return rows_transfer(e, n, feat_ids, lin, vec, false);
+}
+
+// ---- which features changed since ffm_engine_create (kernels_scan.h) -----------------------------
+
+static int train_one_staged(ffm_engine *e);  // (engine_stage.h)
+
+int ffm_engine_changed_features(ffm_engine *e, int32_t *ids, int64_t cap, int64_t *n_changed) {
+  if (n_changed) *n_changed = 0;
+  if (!e) return fail(FFM_E_INVALID, "null engine");
+  if (!n_changed) return fail(FFM_E_INVALID, "null n_changed");
+  if (ids && cap < 0) return fail(FFM_E_INVALID, "negative capacity");
+  if (e->m.n_shards > 1)
+    return fail(FFM_E_UNSUPPORTED, "the changed-feature scan covers whole-model engines (n_shards == 1)");
+  if (e->has_pending) return fail(FFM_E_INVALID, "the previous block still awaits train_update");
+  HIP_TRY(hipSetDevice(e->cfg.device_id));
+  // everything handed over so far is part of the model the scan sees: the deferred evaluation block, the
+  // staged training blocks a flush would train (their losses stay in the flush's sum), the staging thread
+  if (int rc_e = eval_launch_pending(e)) return rc_e;
+  while (e->n_staged > 0)
+    if (int rc_t = train_one_staged(e)) return rc_t;
+  // ... and a block the device refused (a row too long, an id outside its field's range) did not reach
+  // the model: report it here, as ffm_engine_sync would, instead of listing a model that lacks it
+  if (int rc_d = check_device_errors(e)) return rc_d;
+  const int64_t n_words = (static_cast<int64_t>(e->m.n_feats) + 63) / 64;
+  std::vector<unsigned long long> bits(static_cast<size_t>(n_words));
+  unsigned long long *d_bits = reinterpret_cast<unsigned long long *>(e->d_stage);
+  const int64_t per = e->stage_floats / 2;  // words the staging buffer holds
+  const bool vec4 = e->m.row_len % 4 == 0, skip = (e->cfg.flags & FFM_FLAG_SKIP_INIT) != 0;
+  for (int64_t w0 = 0; w0 < n_words; w0 += per) {
+    const int64_t nw = std::min(per, n_words - w0);
+    const dim3 grid(static_cast<unsigned>((nw + kScanWaves - 1) / kScanWaves)), block(kScanThreads);
+#define SCAN_LAUNCH(V, S)                                                                              \
+    hipLaunchKernelGGL((changed_scan_kernel<V, S>), grid, block, 0, e->stream, e->m, e->cfg.init_mean, \
+                       e->cfg.init_stddev, e->cfg.seed, w0, nw, d_bits)
+    if (vec4) { if (skip) SCAN_LAUNCH(true, true); else SCAN_LAUNCH(true, false); }
+    else      { if (skip) SCAN_LAUNCH(false, true); else SCAN_LAUNCH(false, false); }
+#undef SCAN_LAUNCH
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(bits.data() + w0, d_bits, static_cast<size_t>(nw) * sizeof(unsigned long long),
+                           hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+  }
+  int64_t count = 0;
+  for (unsigned long long b : bits) count += __builtin_popcountll(b);
+  *n_changed = count;
+  if (!ids) return FFM_OK;
+  if (cap < count) return fail(FFM_E_CAPACITY, "ids holds " + std::to_string(cap) + " entries, " + std::to_string(count) + " features changed");
+  int64_t at = 0;
+  for (int64_t w = 0; w < n_words; w++)
+    for (unsigned long long b = bits[static_cast<size_t>(w)]; b; b &= b - 1)
+      ids[at++] = static_cast<int32_t>(w * 64 + __builtin_ctzll(b));
+  return FFM_OK;
 }

@@ -14,6 +14,7 @@ LR, FM, FFM = 0, 1, 2
 MODEL_TYPES = {"LR": LR, "FM": FM, "FFM": FFM}
 FLAG_SKIP_INIT = 1
 FLAG_LEARN = 4
+E_INVALID, E_DEVICE, E_NOMEM, E_CAPACITY, E_UNSUPPORTED = -1, -2, -3, -4, -5  # FFM_E_*
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _f32p = ctypes.POINTER(ctypes.c_float)
@@ -65,6 +66,8 @@ ABI = [
     ("ffm_engine_get_state", ctypes.c_int, [_vp] + [_f32p] * 6),
     ("ffm_engine_get_rows", ctypes.c_int, [_vp, ctypes.c_int32, _i32p] + [_f32p] * 6),
     ("ffm_engine_set_rows", ctypes.c_int, [_vp, ctypes.c_int32, _i32p] + [_f32p] * 6),
+    ("ffm_engine_changed_features", ctypes.c_int,
+     [_vp, _i32p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     ("ffm_engine_train_batch", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [_f32p, _f64p]),
     ("ffm_engine_predict_batch", ctypes.c_int,
      [_vp, ctypes.c_int32] + _CSR + [ctypes.c_int32, _f32p, _f64p]),
@@ -282,6 +285,46 @@ class Engine:
         st = {k: np.ascontiguousarray(v, np.float32) for k, v in st.items() if k in self.ROW_KEYS}
         args = [_f(st[k]) if k in st and st[k].size else None for k in self.ROW_KEYS]
         self._check(self.lib.ffm_engine_set_rows(self.h, ids.size, _i(ids), *args))
+
+    # ---- sparse checkpoints: only what differs from a fresh engine of the same config ----
+    def changed_features(self):
+        """Ascending int32 ids of the features that no longer hold what the constructor gave them
+        (ffm_engine_changed_features: one device scan, bit patterns compared)."""
+        n = ctypes.c_int64(0)
+        # ONE scan: a count-first call would scan the model twice (a fresh 33 M-feature model: every w against
+        # its fp64 draw, both times).  The buffer is address space only: pages nobody writes are never committed.
+        ids = np.empty(self.n_feats, np.int32)
+        self._check(self.lib.ffm_engine_changed_features(self.h, _i(ids), ids.size, ctypes.byref(n)))
+        return ids[:n.value].copy()
+
+    def _bias3(self):
+        b = np.zeros(3, np.float32)
+        self._check(self.lib.ffm_engine_get_weights(self.h, _f(b[0:1]), None, None))
+        self._check(self.lib.ffm_engine_get_state(self.h, _f(b[1:2]), _f(b[2:3]), None, None, None, None))
+        return b
+
+    def sparse_state(self):
+        """The model as a delta to a fresh engine of the same config: dict(ids, bias3, ROW_KEYS arrays
+        of the changed features).  load_sparse_state() of it on such an engine reproduces this one bit
+        for bit."""
+        ids = self.changed_features()
+        out = dict(ids=ids, bias3=self._bias3())
+        out.update(self.get_rows(ids))
+        return out
+
+    def load_sparse_state(self, d):
+        """Applies sparse_state() of an engine of the same config; refused unless this engine still
+        holds exactly what its constructor gave it (no changed feature)."""
+        n = ctypes.c_int64(0)
+        self._check(self.lib.ffm_engine_changed_features(self.h, None, 0, ctypes.byref(n)))
+        if n.value != 0:
+            raise EngineError(E_INVALID, "load_sparse_state needs a fresh engine: %d features already changed" % n.value)
+        ids = np.ascontiguousarray(d["ids"], np.int32)
+        if ids.size:
+            self.set_rows(ids, d)
+        b = np.ascontiguousarray(d["bias3"], np.float32)
+        self._check(self.lib.ffm_engine_set_weights(self.h, _f(b[0:1]), None, None))
+        self._check(self.lib.ffm_engine_set_state(self.h, _f(b[1:2]), _f(b[2:3]), None, None, None, None))
 
     # ---- blocks of rows in host memory ----
     def _csr(self, c):

@@ -25,7 +25,7 @@ const std::string_view cmd_help =
     "--w_l1 <w_L1_reg>: L1 regularization parameter of w\tdefault:0.1\n"
     "--w_l2 <w_L2_reg>: L2 regularization parameter of w\tdefault:5.0\n"
     "--n_threads <threads_num>: host threads for parsing\tdefault:1\n"
-    "--n_epochs <epochs>: how many epochs to train\tdefault:1\n"
+    "--n_epochs <epochs>: how many epochs to train; with --resume_from: how many MORE\tdefault:1\n"
     "--online <online>: whether to online training mode\tdefault:true\n"
     "--batch_size <rows>: rows per block sent to the GPU\tdefault:4096\n"
     "--batch_ramp <r>: block size grows as rows_seen/r (0 disables)\tdefault: by w_alpha (32 up to 1e-3)\n"
@@ -35,6 +35,13 @@ const std::string_view cmd_help =
     "              partial logits per block)\tdefault:1\n"
     "--field_ranges <uniform|none>: uniform = field f owns ids [f*n_feats/n_fields, (f+1)*n_feats/n_fields),\n"
     "              shards then store only their own slots\tdefault:none\n"
+    "--checkpoint_path <path>: after training, write a sparse resumable checkpoint: only the features that\n"
+    "              differ from a fresh model of this seed (found by a device scan), with w, n, z, the bias and the\n"
+    "              trainer's progress (one GPU only)\n"
+    "--resume_from <path>: load such a checkpoint before training; needs the same model shape, --seed,\n"
+    "              --init_mean, --init_stddev and --learn (checked); the FTRL hyper-parameters (--w_alpha, --w_beta,\n"
+    "              --w_l1, --w_l2), --batch_size and --batch_ramp are NOT recorded in the file: pass the same ones\n"
+    "              and the resumed run continues the interrupted one bit for bit\n"
     "--learn <bool>: keep initial latent weights until their first gradient and use g2*g2 at\n"
     "                ffm.cpp:118, so FM/FFM factors train (NOT the reference's results)\tdefault:false\n";
 
@@ -86,6 +93,8 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--w_l2") w_l2 = std::stof(v);
     else if (k == "--n_threads") thread_num = std::stoi(v);
     else if (k == "--n_epochs") epoch = std::stoi(v);
+    else if (k == "--checkpoint_path") checkpoint_path = v;
+    else if (k == "--resume_from") resume_from = v;
     else if (k == "--cmd") cmd = assign_bool(v);
     else if (k == "--batch_size") batch_size = std::stoi(v);
     else if (k == "--batch_ramp") batch_ramp = std::stoi(v);

@@ -27,6 +27,8 @@ struct config_options {
   std::string field_ranges = "none";  // --field_ranges uniform: field f owns ids [f*n_feats/F, (f+1)*n_feats/F)
                                       //   (the layout of python/generate_data.py:272-306): shards then store
                                       //   only their slots; none: every shard keeps whole records
+  std::string checkpoint_path;  // --checkpoint_path: write a sparse resumable checkpoint after training
+  std::string resume_from;      // --resume_from: load one before training; --n_epochs then counts MORE epochs
 
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };

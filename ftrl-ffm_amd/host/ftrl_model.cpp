@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 
 namespace ftrl {
@@ -49,6 +50,10 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
   cfg.device_id = opt.device;
   if (opt.learn) cfg.flags |= FFM_FLAG_LEARN;
   n_gpus_ = std::max(1, opt.n_gpus);
+  seed_ = cfg.seed;
+  init_mean_ = cfg.init_mean;
+  init_stddev_ = cfg.init_stddev;
+  flags_ = cfg.flags;
   int rc;
   const char *force_group = std::getenv("FFM_GROUP_RCCL");  // (a group of one: the RCCL path on a one-GPU box)
   if (n_gpus_ > 1 || (force_group && force_group[0] == '1' && mt == FFM_MODEL_FFM)) {
@@ -533,6 +538,99 @@ void FtrlModel::load_state(std::string_view file_name) {
       need(buf.data(), n * rl);
       set_latent_rows(comp, f0, n, buf.data());
     }
+}
+
+// ---- sparse checkpoint: the records that differ from a freshly constructed model ------------------
+
+static uint32_t float_bits(float v) {
+  uint32_t b;
+  std::memcpy(&b, &v, sizeof b);
+  return b;
+}
+
+void FtrlModel::save_checkpoint(std::string_view file_name, int compress_level, TrainProgress progress) {
+  if (n_gpus_ > 1) throw std::runtime_error("sparse checkpoints are not supported for sharded models (--n_gpus > 1)");
+  const size_t rl = static_cast<size_t>(row_len_);
+  // one scan; the id buffer is sized for every feature and only the pages written are ever committed
+  std::unique_ptr<int32_t[]> ids(new int32_t[static_cast<size_t>(n_feats)]);
+  int64_t n = 0;
+  check(ffm_engine_changed_features(eng_, ids.get(), n_feats, &n), "ffm_engine_changed_features");
+  SparseCheckpointHeader h;
+  h.model_type = static_cast<int32_t>(model_type);
+  h.n_feats = n_feats;
+  h.n_fields = n_fields;
+  h.n_factors = n_factors;
+  h.flags = static_cast<uint32_t>(flags_);
+  h.row_len = row_len_;
+  h.seed = seed_;
+  h.init_mean_bits = float_bits(init_mean_);
+  h.init_stddev_bits = float_bits(init_stddev_);
+  h.n_changed = n;
+  h.chunk = static_cast<int64_t>(stream_chunk());
+  float b3[3] = {0.0f, 0.0f, 0.0f};
+  check(ffm_engine_get_weights(eng_, &b3[0], nullptr, nullptr), "ffm_engine_get_weights");
+  check(ffm_engine_get_state(eng_, &b3[1], &b3[2], nullptr, nullptr, nullptr, nullptr), "ffm_engine_get_state");
+  for (int i = 0; i < 3; i++) h.bias_bits[i] = float_bits(b3[i]);
+  h.rows_seen = progress.rows_seen;
+  h.epochs_done = progress.epochs_done;
+  SparseCheckpointWriter w(std::string(file_name), h, ids.get(), compress_level);
+  const size_t chunk = std::min(static_cast<size_t>(h.chunk), static_cast<size_t>(std::max<int64_t>(n, 1)));
+  std::vector<float> lin(3 * chunk), vec(3 * chunk * rl);
+  for (size_t j0 = 0; j0 < static_cast<size_t>(n); j0 += chunk) {
+    const size_t c = std::min(chunk, static_cast<size_t>(n) - j0);
+    float *lw = lin.data(), *ln = lw + c, *lz = ln + c;
+    float *vw = rl ? vec.data() : nullptr, *vn = rl ? vw + c * rl : nullptr, *vz = rl ? vn + c * rl : nullptr;
+    check(ffm_engine_get_rows(eng_, static_cast<int32_t>(c), ids.get() + j0, lw, ln, lz, vw, vn, vz), "ffm_engine_get_rows");
+    w.chunk(c, lw, ln, lz, vw, vn, vz);
+  }
+  w.finish();
+}
+
+FtrlModel::TrainProgress FtrlModel::load_checkpoint(std::string_view file_name) {
+  if (n_gpus_ > 1) throw std::runtime_error("sparse checkpoints are not supported for sharded models (--n_gpus > 1)");
+  const std::string name(file_name);
+  SparseCheckpointReader r(name);
+  const SparseCheckpointHeader &h = r.header();
+  if (h.model_type != static_cast<int32_t>(model_type) || h.n_feats != n_feats || h.row_len != row_len_ ||
+      (row_len_ > 0 && h.n_factors != n_factors) || (model_type == ModelType::FFM && h.n_fields != n_fields))
+    throw std::runtime_error(name + ": holds a model of a different shape");
+  if (h.seed != seed_ || h.init_mean_bits != float_bits(init_mean_) || h.init_stddev_bits != float_bits(init_stddev_) ||
+      ((h.flags ^ static_cast<uint32_t>(flags_)) & FFM_FLAG_SKIP_INIT))
+    throw std::runtime_error(name + ": was saved from a model with another seed or other init parameters "
+                                    "(its records are deltas to THAT fresh model)");
+  if ((h.flags ^ static_cast<uint32_t>(flags_)) & FFM_FLAG_LEARN)
+    throw std::runtime_error(name + ": was saved " + ((h.flags & FFM_FLAG_LEARN) ? "with" : "without") +
+                             " --learn, this model is the other variant: the resumed run would not be the interrupted one");
+  int64_t touched = 0;
+  check(ffm_engine_changed_features(eng_, nullptr, 0, &touched), "ffm_engine_changed_features");
+  if (touched != 0)
+    throw std::runtime_error(name + ": a sparse checkpoint loads into a fresh model only; " + std::to_string(touched) +
+                             " features of this one have changed already");
+  float b3[3];
+  for (int i = 0; i < 3; i++) std::memcpy(&b3[i], &h.bias_bits[i], sizeof(float));
+  check(ffm_engine_set_weights(eng_, &b3[0], nullptr, nullptr), "ffm_engine_set_weights");
+  check(ffm_engine_set_state(eng_, &b3[1], &b3[2], nullptr, nullptr, nullptr, nullptr), "ffm_engine_set_state");
+  const size_t rl = static_cast<size_t>(row_len_), n = r.ids().size();
+  const size_t cap = std::min(static_cast<size_t>(h.chunk), std::max<size_t>(n, 1));
+  std::vector<float> lin(3 * cap), vec(3 * cap * rl);
+  size_t j0 = 0;
+  while (const size_t c = r.next_chunk_size()) {
+    float *lw = lin.data(), *ln = lw + c, *lz = ln + c;
+    float *vw = rl ? vec.data() : nullptr, *vn = rl ? vw + c * rl : nullptr, *vz = rl ? vn + c * rl : nullptr;
+    r.chunk(lw, ln, lz, vw, vn, vz);
+    check(ffm_engine_set_rows(eng_, static_cast<int32_t>(c), r.ids().data() + j0, lw, ln, lz, vw, vn, vz), "ffm_engine_set_rows");
+    j0 += c;
+  }
+  r.finish();
+  std::printf("loading from %s, changed features: %zu of %d\n", name.c_str(), n, n_feats);
+  pull_linear();
+  vec_w.dense_ready_ = false;
+  vec_w.dense_.clear();
+  vec_w.cache_.clear();
+  TrainProgress p;
+  p.rows_seen = h.rows_seen;
+  p.epochs_done = h.epochs_done;
+  return p;
 }
 
 bool FtrlModel::has_zero_weights() {  // utils.h:63-76 over lin_w, then vec_w (ftrl_offline.cpp:105-119)

@@ -67,6 +67,11 @@ class LatentMirror {
   std::unordered_map<size_t, row> cache_;  // rows touched one by one
 };
 
+// what a trainer saves with a checkpoint and continues from (trainer.h)
+struct TrainProgress {
+  long long rows_seen = 0, epochs_done = 0;
+};
+
 class FtrlModel {
  public:
   explicit FtrlModel(const config_options &opt, int model_type);
@@ -112,6 +117,15 @@ class FtrlModel {
   void load_compressed_model(std::string_view file_name);
   void save_state(std::string_view file_name, int compress_level = 3);
   void load_state(std::string_view file_name);
+  // Sparse resumable checkpoint (persist.h): only the features that no longer hold what the
+  // constructor gave them (ffm_engine_changed_features, one device scan), their full records
+  // (w, n, z), the bias triple and the trainer's progress.  load_checkpoint wants a model built with the
+  // same shape, seed, init parameters and --learn setting that has not been touched yet (throws std::runtime_error
+  // otherwise) and makes it the saved model bit for bit; returns the progress saved with it.  Not
+  // supported for sharded models (--n_gpus > 1): both throw.
+  using TrainProgress = ftrl::TrainProgress;
+  void save_checkpoint(std::string_view file_name, int compress_level = 3, TrainProgress progress = TrainProgress());
+  TrainProgress load_checkpoint(std::string_view file_name);
 
   void pull_linear();   // device -> bias, lin_w (from the shards that own them)
   void push_linear();
@@ -146,6 +160,10 @@ class FtrlModel {
   ffm_engine *shard(int r) const;
   int field_of(int feat) const { return per_field_ > 0 ? std::min(feat / per_field_, n_fields - 1) : 0; }
   int per_field_ = 0;  // ids per field under --field_ranges uniform
+  // what the engine was created from, as far as it decides a fresh model's contents (checkpoints)
+  uint64_t seed_ = 0;
+  float init_mean_ = 0.0f, init_stddev_ = 0.0f;
+  int32_t flags_ = 0;
   CsrBlock one_;  // scratch for the one-row shims
   // engine capacities chosen at construction; blocks beyond max_nnz_ are split into several
   // engine calls (each still a block in row order), a single row beyond max_row_nnz_ is an error

@@ -27,14 +27,20 @@ int main(int argc, char *argv[]) {
       if (zst) m.save_compressed_model(opt.model_path, 3); else m.save_model(opt.model_path);
       m.save_state(opt.model_path + ".nz");
     };
+    // --resume_from / --checkpoint_path: the sparse checkpoint (persist.h) -- the model's changed records
+    // and the task's progress, so that a run cut in two gives the files and losses of the run in one piece
+    auto run = [&](auto &task) {
+      if (!opt.resume_from.empty()) task.restore(task.model_ptr->load_checkpoint(opt.resume_from));
+      task.train();
+      save(*task.model_ptr);
+      if (!opt.checkpoint_path.empty()) task.model_ptr->save_checkpoint(opt.checkpoint_path, 3, task.progress());
+    };
     if (opt.online) {
       ftrl::FtrlOnline task(opt);
-      task.train();
-      save(*task.model_ptr);
+      run(task);
     } else {
       ftrl::FtrlOffline task(opt);
-      task.train();
-      save(*task.model_ptr);
+      run(task);
     }
   } catch (const std::exception &e) {
     std::fprintf(stderr, "error: %s\n", e.what());

@@ -102,7 +102,8 @@ double FtrlOffline::csr_epoch(const CsrData &d, bool train) {
 }
 
 void FtrlOffline::train() {
-  for (int i = 1; i <= n_epochs; i++) {
+  const int first = resumed_epochs_;  // (epochs a resumed run has behind it: the numbering continues; else 0)
+  for (int i = first + 1; i <= first + n_epochs; i++) {
     const auto t0 = timer::now();
     const double train_loss = csr_epoch(train_csr_, true);
     std::printf("epoch %d train time: %.4lfs, train loss: %.4lf\n", i, seconds_since(t0), train_loss);
@@ -198,9 +199,11 @@ double FtrlOnline::get_loss() {
 
 void FtrlOnline::train() {
   if (cmd_) return;  // stdin mode is a TODO stub in the reference too (ftrl_online.cpp:55-57)
-  for (int i = 1; i <= n_epochs; i++) {
+  for (int n = 0; n < n_epochs; n++) {
     const auto t0 = timer::now();
     run_train_file();
+    passes_++;
+    const int i = static_cast<int>(resumed_epochs_) + n + 1;  // (a resumed run's numbering continues; else 1..n_epochs)
     const double train_loss = get_loss();
     std::printf("epoch %d train time: %.4lfs, train loss: %.4lf\n", i, seconds_since(t0), train_loss);
     if (evaluator) evaluate(i);

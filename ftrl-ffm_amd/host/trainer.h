@@ -35,6 +35,7 @@ class BlockScheduler {
   int max_block_rows() const { return batch_; }  // evaluation has no staleness: full blocks
   void consumed(int rows) { seen_ += rows; }
   long long rows_seen() const { return seen_; }
+  void restore(long long rows_seen) { seen_ = rows_seen; }  // a resumed run continues the ramp
 
  private:
   int batch_, ramp_;
@@ -91,13 +92,23 @@ class FtrlOffline {
   void evaluate(int epoch = 0);
   double one_epoch(std::vector<Sample> &samples, bool train, bool use_pool);
   bool has_zero_weights() { return model_ptr->has_zero_weights(); }
+  // What a checkpoint carries beside the model so that an interrupted and resumed run IS the
+  // uninterrupted one: the rows seen (block-size ramp) and the epochs done (the shuffle of epoch e is
+  // seeded seed + e).  restore() before train(): --n_epochs then means that many MORE epochs.
+  // (Without restore() nothing changes: train() numbers its epochs from 1 on every call.)
+  FtrlModel::TrainProgress progress() const { return {sched_.rows_seen(), epoch_no_}; }
+  void restore(const FtrlModel::TrainProgress &p) {
+    sched_.restore(p.rows_seen);
+    epoch_no_ = resumed_epochs_ = static_cast<int>(p.epochs_done);
+  }
 
   std::unique_ptr<FtrlModel> model_ptr;
 
  private:
   int n_epochs, n_threads;
   uint64_t seed_;
-  int epoch_no_ = 0;
+  int epoch_no_ = 0;        // training passes so far (the shuffle of pass e is seeded seed + e)
+  int resumed_epochs_ = 0;  // epochs a checkpoint brought along: train() prints its epochs after them
   BlockScheduler sched_;
   std::unique_ptr<Reader> train_data_loader, eval_data_loader;  // API parity (data stays empty
                                                                 // unless load_samples() is called)
@@ -116,6 +127,8 @@ class FtrlOnline {
   void evaluate(int epoch = 0);
   double get_loss();
   bool has_zero_weights() { return model_ptr->has_zero_weights(); }
+  FtrlModel::TrainProgress progress() const { return {sched_.rows_seen(), resumed_epochs_ + passes_}; }  // (as FtrlOffline's)
+  void restore(const FtrlModel::TrainProgress &p) { sched_.restore(p.rows_seen); resumed_epochs_ = p.epochs_done; }
 
   std::shared_ptr<FtrlModel> model_ptr;
   std::unique_ptr<Evaluator> evaluator;  // (ftrl_online.h:31; null without --eval_data)
@@ -123,6 +136,8 @@ class FtrlOnline {
  private:
   void run_train_file();
   int n_epochs;
+  long long passes_ = 0;          // passes over the training file made by this object
+  long long resumed_epochs_ = 0;  // epochs a checkpoint brought along: train() prints its epochs after them
   bool cmd_;
   BlockScheduler sched_;
   std::unique_ptr<CsrStream> train_stream_;  // chunks of <= 20 000 lines parsed by n_threads workers

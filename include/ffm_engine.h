@@ -184,6 +184,25 @@ int ffm_engine_set_rows(ffm_engine *e, int32_t n, const int32_t *feat_ids, const
                         const float *lin_n, const float *lin_z, const float *vec_w,
                         const float *vec_n, const float *vec_z);
 
+/* Which features no longer hold what ffm_engine_create gave them: feature i is CHANGED when any 32-bit
+ * pattern of lin_w[i], lin_n[i], lin_z[i] or of its latent record (n, z, w) differs from the create-time
+ * one -- zero bits for n and z, ffm_engine_init_weights_host's draw for w (zero bits under
+ * FFM_FLAG_SKIP_INIT).  Patterns, not values (-0.0f and NaN count as changed); exact whatever touched
+ * the model (training, set_rows, set_weights, fill_state, the learning variant).  One device pass over
+ * the model (csrc/kernels_scan.h) fills a bitmap, the host expands it: ids[0 .. *n_changed) ascending.
+ * *n_changed is always set; ids == NULL only counts; cap < *n_changed with ids != NULL is
+ * FFM_E_CAPACITY.  Blocks handed over by the pipelined entry points and not trained yet are trained
+ * first (as ffm_engine_train_flush would; their losses stay in the flush's sum), and what the device
+ * flagged since the last report is returned (and cleared) as by ffm_engine_sync -- a refused block is an
+ * error here, not a model that silently lacks it.  Whole-model engines only: FFM_E_UNSUPPORTED when
+ * n_shards > 1.  Synchronous.
+ *   What it serves: the reference's persistence writes w only and densely (src/model/ffm.cpp:138-200,
+ * lr.cpp:26-39), and SURVEY.md 8(f) rank 2 asks for checkpoints that are "actually resumable" -- a
+ * fresh engine is a pure function of (seed, init_mean, init_stddev, flags), so these records
+ * (ffm_engine_get_rows) plus the bias, loaded into a fresh engine of the same config with
+ * ffm_engine_set_rows, reproduce the model bit for bit, and only the trained part moves. */
+int ffm_engine_changed_features(ffm_engine *e, int32_t *ids, int64_t cap, int64_t *n_changed);
+
 /* Replaces the loop over FtrlModel::train (ffm.cpp:38-49, fm.cpp:21-32, lr.cpp:9-18) in
  * FtrlOffline::one_epoch / FtrlOnline::run_task for one block of rows held in HOST memory.
  * logit_out[n_rows] receives each row's pre-update logit (train()'s return value); *loss_sum_out
