@@ -3,8 +3,9 @@ include/ffm_engine.h (csrc/), plus the host-side mirror of the reference's model
 (host/) and this thin ctypes binding (engine.py).  No CPU fallback: importing is cheap, but
 creating an Engine without libffm_engine.so or without a GPU raises."""
 from . import build as _build
-from .engine import (ABI, FFM, FM, LR, Config, Engine, EngineError, Group, LIB_PATH,  # noqa: F401
-                     default_batch_ramp, init_weights_host, load_library, page_aligned, shard_plan)
+from .engine import (ABI, FFM, FM, LR, METRIC_BINS, METRIC_EVAL, METRIC_TRAIN, Config, Engine,  # noqa: F401
+                     EngineError, Group, LIB_PATH, Metrics, default_batch_ramp, init_weights_host,
+                     load_library, metrics_from_histogram, page_aligned, shard_plan)
 
 
 def build(force=False, verbose=False):

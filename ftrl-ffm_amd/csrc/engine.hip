@@ -45,6 +45,8 @@
 #include "kernels_predict.h"
 #include "kernels_sort.h"
 #include "kernels_scan.h"
+#include "kernels_metric.h"
+#include "metrics_host.h"
 
 using namespace ftrl_dev;
 
@@ -107,13 +109,13 @@ int fail(int code, const std::string &msg) {
 enum KernelId {
   K_GROUP_KEYS, K_GROUP_SORT, K_GROUP_FINISH, K_ROW, K_TMP_GRAD,
   K_LOSS_SUM, K_LINEAR_UPDATE, K_BIAS_UPDATE, K_LATENT_UPDATE, K_LATENT_UPDATE_FEW, K_LATENT_UPDATE_WALK, K_LATENT_UPDATE_GIANT,
-  K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE,
+  K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC,
   K_COUNT
 };
 const char *kKernelNames[K_COUNT] = {
     "group_keys_kernel", "group_radix_sort", "group_finish_kernel", "row_kernel<train>", "tmp_grad_kernel", "loss_sum_kernel",
     "linear_update_kernel", "bias_update_kernel", "update_kernel", "update_few_kernel", "update_walk_kernel", "update_giant_kernel",
-    "row_kernel<predict>", "refresh_kernel", "update_single_kernel"};
+    "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel"};
 
 struct ProfRec {
   int kid;
@@ -352,6 +354,9 @@ struct ffm_engine {
   int *d_ids = nullptr;      // feature ids of one ffm_engine_get_rows / set_rows chunk
   static constexpr int kIdsCap = 1 << 20;
   int *d_err = nullptr;      // [1] sticky ERR_* flags of every block since the last report
+  // the AUC channels (include/ffm_engine.h "Metrics"): hist = pos[kMetricBins], neg[kMetricBins], n_nan;
+  // allocated when the channel is first turned on
+  struct MetricChannel { bool on = false; unsigned long long *hist = nullptr; } metric[2];
   std::vector<void *> allocs;
   // split-phase bookkeeping
   Rows pending{};
@@ -1073,6 +1078,12 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   TRY_HIP(hipStreamSynchronize(e->stream));
 #undef TRY_ALLOC
 #undef TRY_HIP
+  // FFM_ENGINE_METRICS=<mask>: channels on from the start (rank 0 of a group keeps them)
+  if (const char *sv = std::getenv("FFM_ENGINE_METRICS")) {
+    const int mask = std::atoi(sv) & 3;
+    if (mask && cfg->shard_rank == 0)
+      if (int rc_m = ffm_engine_metrics_enable(e, mask)) { ffm_engine_destroy(e); return rc_m; }
+  }
   *out = e;
   return FFM_OK;
 }
@@ -1180,6 +1191,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_step.h"
 #include "engine_stage.h"
 #include "engine_profile.h"
+#include "engine_metrics.h"
 }  // extern "C"
 
 #include "engine_group.h"

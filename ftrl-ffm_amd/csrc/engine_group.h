@@ -317,4 +317,16 @@ int ffm_group_predict_batch(ffm_group *g, int32_t n_rows, const int32_t *row_ptr
   return FFM_OK;
 }
 
+// Every rank sees the labels and, after the all-reduce, the whole logits; rank 0's engine keeps the
+// channels (its predict_finish / train_update are the ones that report the loss as well).
+int ffm_group_metrics_enable(ffm_group *g, int32_t channel_mask) {
+  if (!g || g->eng.empty()) return fail(FFM_E_INVALID, "null group");
+  return ffm_engine_metrics_enable(g->eng[0], channel_mask);
+}
+
+int ffm_group_metrics_read(ffm_group *g, int32_t channel, int32_t reset, ffm_metrics *out) {
+  if (!g || g->eng.empty()) return fail(FFM_E_INVALID, "null group");
+  return ffm_engine_metrics_read(g->eng[0], channel, reset, out);
+}
+
 }  // extern "C"

@@ -5,6 +5,7 @@
 // ---- one block of rows ---------------------------------------------------------------------
 
 static int eval_launch_pending(ffm_engine *e);
+static void launch_metric(ffm_engine *e, int channel, int n_rows, const float *score, int is_prob, const int *label);  // (engine_metrics.h)
 __global__ void loss_accumulate_kernel(double *acc, const double *one) { *acc += *one; }
 
 static int check_block(ffm_engine *e, int32_t n_rows, int32_t nnz, const void *row_ptr,
@@ -293,6 +294,8 @@ int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *log
   e->has_pending = false;
   const float *lg = logit ? logit : e->sc[e->cur].logit;
   const bool own_tg = e->own_tg_cur && !logit;
+  // progressive validation: the block's whole pre-update logits into the train channel (when it is on)
+  launch_metric(e, FFM_METRIC_TRAIN, rows.n_rows, lg, 0, rows.label);
   if (rows.n_rows > 0 && !own_tg)
     LAUNCH(e, K_TMP_GRAD, tmp_grad_kernel, cdiv(rows.n_rows, 256), 256, 0, rows.n_rows, lg, rows.label, e->sc[e->cur].tg, e->sc[e->cur].loss, logit_out);
   // Everything below runs on the main stream: the update has no long dependent chains (every
@@ -493,6 +496,7 @@ int ffm_engine_predict_batch_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   Rows rows{n_rows, nnz, row_ptr, field, feat, val, label};
   launch_row_kernel(e, rows, false, out ? out : e->d_out, output_prob);
+  if (label) launch_metric(e, FFM_METRIC_EVAL, n_rows, out ? out : e->d_out, output_prob, label);
   if (loss_sum_out && label)
     LAUNCH(e, K_LOSS_SUM, loss_sum_kernel, loss_grid(n_rows), 256, 0, n_rows, e->sc[e->cur].loss, loss_sum_out, e->d_loss_part);
   HIP_TRY(hipGetLastError());
@@ -526,6 +530,8 @@ int ffm_engine_predict_finish_device(ffm_engine *e, int32_t n_rows, const float 
   if (n_rows < 0 || n_rows > e->max_rows) return fail(FFM_E_CAPACITY, "n_rows out of range");
   if (n_rows > 0 && !logit) return fail(FFM_E_INVALID, "null logit array");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
+  // (from the logits, ahead of the kernel that may overwrite them: `out` may alias `logit` or be NULL)
+  if (label) launch_metric(e, FFM_METRIC_EVAL, n_rows, logit, 0, label);
   if (n_rows > 0)
     LAUNCH(e, K_TMP_GRAD, predict_finish_kernel, cdiv(n_rows, 256), 256, 0, n_rows, logit, label, output_prob, out, e->sc[e->cur].loss);
   if (loss_sum_out) {

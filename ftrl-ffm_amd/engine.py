@@ -43,6 +43,20 @@ class Config(ctypes.Structure):
                 ("reserved", ctypes.c_int32 * 4)]
 
 
+class Metrics(ctypes.Structure):
+    """struct ffm_metrics (include/ffm_engine.h "Metrics")."""
+    _fields_ = [("n_pos", ctypes.c_int64), ("n_neg", ctypes.c_int64), ("n_nan", ctypes.c_int64),
+                ("n_mixed_bins", ctypes.c_int64), ("auc", ctypes.c_double), ("auc_slack", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+METRIC_EVAL, METRIC_TRAIN = 0, 1  # FFM_METRIC_*
+METRIC_BINS = 1 << 20             # FFM_METRIC_BINS
+_METRIC_CHANNELS = {"eval": METRIC_EVAL, "train": METRIC_TRAIN}
+_u64p = ctypes.POINTER(ctypes.c_uint64)
+
 # every symbol include/ffm_engine.h declares: (name, restype, argtypes)
 _CSR = [_i32p, _i32p, _i32p, _f32p, _i32p]
 _DCSR = [_vp, _vp, _vp, _vp, _vp]
@@ -103,6 +117,12 @@ ABI = [
      [_vp, _i32p, _f64p, ctypes.c_char_p, ctypes.c_size_t]),
     ("ffm_engine_profile_focus", ctypes.c_int, [_vp]),
     ("ffm_engine_profile_dump", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
+    ("ffm_engine_metrics_enable", ctypes.c_int, [_vp, ctypes.c_int32]),
+    ("ffm_engine_metrics_read", ctypes.c_int,
+     [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Metrics)]),
+    ("ffm_engine_metrics_histogram", ctypes.c_int, [_vp, ctypes.c_int32, _u64p, _u64p]),
+    ("ffm_engine_metrics_from_histogram", ctypes.c_int,
+     [_u64p, _u64p, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(Metrics)]),
     # several GPUs in one process (ffm_group_*)
     ("ffm_group_create", ctypes.c_int, [ctypes.POINTER(Config), ctypes.c_int32, _i32p, ctypes.POINTER(_vp)]),
     ("ffm_group_destroy", None, [_vp]),
@@ -115,6 +135,9 @@ ABI = [
     ("ffm_group_blocks_pulled", ctypes.c_int64, [_vp]),
     ("ffm_group_predict_batch", ctypes.c_int,
      [_vp, ctypes.c_int32] + _CSR + [ctypes.c_int32, _f32p, _f64p]),
+    ("ffm_group_metrics_enable", ctypes.c_int, [_vp, ctypes.c_int32]),
+    ("ffm_group_metrics_read", ctypes.c_int,
+     [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Metrics)]),
 ]
 
 _lib = None
@@ -138,6 +161,27 @@ def shard_plan(n_fields, n_shards, field_map=False):
     if rc != 0:
         raise EngineError(rc, lib.ffm_engine_last_error().decode())
     return dict(pair_owner=po, lin_owner=lo, bias_owner=int(bo.value))
+
+
+def _channel(channel):
+    return _METRIC_CHANNELS[channel] if isinstance(channel, str) else int(channel)
+
+
+def metrics_from_histogram(pos, neg, n_nan=0):
+    """Histogram -> dict(n_pos, n_neg, n_nan, n_mixed_bins, auc, auc_slack) in exact integer
+    arithmetic on the host (ffm_engine_metrics_from_histogram: no engine, no device).  pos / neg:
+    equally long arrays of counts per score bin, ascending."""
+    lib = load_library()
+    pos = np.ascontiguousarray(pos, np.uint64)
+    neg = np.ascontiguousarray(neg, np.uint64)
+    if pos.shape != neg.shape or pos.ndim != 1:
+        raise ValueError("pos and neg must be one-dimensional and equally long")
+    m = Metrics()
+    rc = lib.ffm_engine_metrics_from_histogram(pos.ctypes.data_as(_u64p), neg.ctypes.data_as(_u64p),
+                                               pos.size, int(n_nan), ctypes.byref(m))
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
+    return m.as_dict()
 
 
 def init_weights_host(seed, mean, stddev, latent, first, count):
@@ -471,6 +515,28 @@ class Engine:
         """The hipStream_t (as an int) the engine runs on."""
         return int(self.lib.ffm_engine_stream(self.h) or 0)
 
+    # ---- AUC accumulated on the device (include/ffm_engine.h "Metrics") ----
+    def metrics_enable(self, eval=False, train=False):
+        """Turns the two channels on / off: eval = every labelled predict, train = the pre-update
+        logits of every training block.  A channel that turns on starts from zero, one that stays
+        on keeps its counts."""
+        self._check(self.lib.ffm_engine_metrics_enable(self.h, (1 if eval else 0) | (2 if train else 0)))
+
+    def metrics(self, channel, reset=False):
+        """dict(n_pos, n_neg, n_nan, n_mixed_bins, auc, auc_slack) of "eval" / "train" so far.  Blocks
+        that are staged and not trained yet are not in it: train_flush() first."""
+        m = Metrics()
+        self._check(self.lib.ffm_engine_metrics_read(self.h, _channel(channel), int(bool(reset)), ctypes.byref(m)))
+        return m.as_dict()
+
+    def metrics_histogram(self, channel):
+        """(pos, neg): the channel's raw counters, two uint64 arrays of METRIC_BINS."""
+        pos = np.zeros(METRIC_BINS, np.uint64)
+        neg = np.zeros(METRIC_BINS, np.uint64)
+        self._check(self.lib.ffm_engine_metrics_histogram(self.h, _channel(channel), pos.ctypes.data_as(_u64p),
+                                                          neg.ctypes.data_as(_u64p)))
+        return pos, neg
+
     # ---- kernel timing (HIP events on the engine's stream) ----
     def profile_enable(self, on=True):
         self._check(self.lib.ffm_engine_profile_enable(self.h, int(on)))
@@ -567,6 +633,18 @@ class Group:
         self._check(self.lib.ffm_group_predict_batch(self.h, n, rp, fld, ft, v, lab if with_loss else None,
                                                      int(output_prob), _f(out), ctypes.byref(loss)))
         return out[:c.n_rows], float(loss.value)
+
+    def metrics_enable(self, eval=False, train=False):
+        """Engine.metrics_enable on the rank that keeps the channels (rank 0)."""
+        self._check(self.lib.ffm_group_metrics_enable(self.h, (1 if eval else 0) | (2 if train else 0)))
+
+    def metrics(self, channel, reset=False):
+        m = Metrics()
+        self._check(self.lib.ffm_group_metrics_read(self.h, _channel(channel), int(bool(reset)), ctypes.byref(m)))
+        return m.as_dict()
+
+    def metrics_histogram(self, channel):
+        return self.engines[0].metrics_histogram(channel)
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:

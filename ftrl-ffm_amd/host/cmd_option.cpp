@@ -42,6 +42,9 @@ const std::string_view cmd_help =
     "              --init_mean, --init_stddev and --learn (checked); the FTRL hyper-parameters (--w_alpha, --w_beta,\n"
     "              --w_l1, --w_l2), --batch_size and --batch_ramp are NOT recorded in the file: pass the same ones\n"
     "              and the resumed run continues the interrupted one bit for bit\n"
+    "--metrics <auc|none>: auc = after each epoch's loss line one more line with the AUC of the same rows -- training:\n"
+    "              of the pre-update predictions (progressive validation) --, histogrammed on the device in 2^20\n"
+    "              score bins; the +- is the most the exact rank AUC can differ\tdefault:none\n"
     "--learn <bool>: keep initial latent weights until their first gradient and use g2*g2 at\n"
     "                ffm.cpp:118, so FM/FFM factors train (NOT the reference's results)\tdefault:false\n";
 
@@ -103,6 +106,10 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--learn") learn = assign_bool(v);
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
     else if (k == "--field_ranges") field_ranges = v;
+    else if (k == "--metrics") {
+      if (v != "auc" && v != "none") throw std::invalid_argument("--metrics takes auc or none");
+      metrics = v;
+    }
     else throw std::invalid_argument("unknown argument: " + k + "\n");
   }
   file_type = detect_file_type(train_path);

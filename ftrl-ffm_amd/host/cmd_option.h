@@ -29,6 +29,7 @@ struct config_options {
                                       //   only their slots; none: every shard keeps whole records
   std::string checkpoint_path;  // --checkpoint_path: write a sparse resumable checkpoint after training
   std::string resume_from;      // --resume_from: load one before training; --n_epochs then counts MORE epochs
+  std::string metrics = "none";  // --metrics auc: one AUC line after every loss line (accumulated on the device)
 
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };

@@ -282,6 +282,20 @@ double FtrlModel::train_flush() {
   return loss_sum;
 }
 
+void FtrlModel::enable_metrics(bool eval, bool train) {
+  const int mask = (eval ? 1 << FFM_METRIC_EVAL : 0) | (train ? 1 << FFM_METRIC_TRAIN : 0);
+  if (grp_) check(ffm_group_metrics_enable(grp_, mask), "ffm_group_metrics_enable");
+  else check(ffm_engine_metrics_enable(eng_, mask), "ffm_engine_metrics_enable");
+  metrics_mask_ = mask;
+}
+
+ffm_metrics FtrlModel::read_metrics(int channel, bool reset) {
+  ffm_metrics m{};
+  if (grp_) check(ffm_group_metrics_read(grp_, channel, reset ? 1 : 0, &m), "ffm_group_metrics_read");
+  else check(ffm_engine_metrics_read(eng_, channel, reset ? 1 : 0, &m), "ffm_engine_metrics_read");
+  return m;
+}
+
 long long FtrlModel::predict_block_async(const CsrBlock &blk, bool pinned) {
   const int n = blk.n_rows();
   bool fits = n <= max_rows_ && blk.row_ptr[n] <= max_nnz_;

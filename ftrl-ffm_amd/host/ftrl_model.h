@@ -107,6 +107,13 @@ class FtrlModel {
   long long predict_block_async(const CsrBlock &blk, bool pinned);
   double eval_flush();
   int n_gpus() const { return n_gpus_; }
+  // AUC accumulated on the device (include/ffm_engine.h "Metrics"), one engine or a group alike:
+  // `eval` takes every labelled predict, `train` the pre-update logits of every training block.
+  // read_metrics(FFM_METRIC_EVAL / FFM_METRIC_TRAIN) returns the channel's numbers so far (after a
+  // train_flush() / eval_flush(): everything handed over) and, with reset, starts it from zero.
+  void enable_metrics(bool eval, bool train);
+  ffm_metrics read_metrics(int channel, bool reset);
+  bool metrics_on(int channel) const { return (metrics_mask_ >> channel) & 1; }
 
   // Model files in the reference's formats (ffm.cpp:138-200, lr.cpp:26-39); available for every
   // model type here (the reference has none for FM).  save_state/load_state add the FTRL
@@ -154,6 +161,7 @@ class FtrlModel {
   // block (include/ffm_engine.h: ffm_group_*)
   ffm_group *grp_ = nullptr;
   int n_gpus_ = 1;
+  int metrics_mask_ = 0;
   std::vector<int32_t> lin_owner_of_field_;  // [n_fields] shard that owns a field's linear terms
   int bias_owner_ = 0;
   double eval_loss_pending_ = 0.0;  // group: evaluation blocks are predicted synchronously

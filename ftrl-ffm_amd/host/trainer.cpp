@@ -15,6 +15,11 @@ static double seconds_since(timer::time_point t0) {
   return std::chrono::duration<double>(timer::now() - t0).count();
 }
 
+void print_auc_line(FtrlModel &m, int epoch, int channel) {
+  const ffm_metrics r = m.read_metrics(channel, true);
+  std::printf("epoch %d %s auc: %.6lf (+-%.1e)\n", epoch, channel == FFM_METRIC_TRAIN ? "train" : "eval", r.auc, r.auc_slack);
+}
+
 // ---------------- offline: data in memory, seeded shuffle per epoch ----------------
 
 FtrlOffline::FtrlOffline(const config_options &opt)
@@ -33,6 +38,8 @@ FtrlOffline::FtrlOffline(const config_options &opt)
     eval_csr_ = load_csr(opt.eval_path, opt.file_type, n_threads);
     has_eval_ = true;
   }
+  metrics_ = opt.metrics == "auc";
+  if (metrics_) model_ptr->enable_metrics(true, true);
 }
 
 FtrlOffline::~FtrlOffline() = default;
@@ -107,6 +114,7 @@ void FtrlOffline::train() {
     const auto t0 = timer::now();
     const double train_loss = csr_epoch(train_csr_, true);
     std::printf("epoch %d train time: %.4lfs, train loss: %.4lf\n", i, seconds_since(t0), train_loss);
+    if (metrics_) print_auc_line(*model_ptr, i, FFM_METRIC_TRAIN);
     if (has_eval_) evaluate(i);
   }
 }
@@ -115,6 +123,7 @@ void FtrlOffline::evaluate(int epoch) {
   const auto t0 = timer::now();
   const double eval_loss = csr_epoch(eval_csr_, false);
   std::printf("epoch %d eval time: %.4lfs, eval loss: %.4lf\n", epoch, seconds_since(t0), eval_loss);
+  if (metrics_) print_auc_line(*model_ptr, epoch, FFM_METRIC_EVAL);
 }
 
 // One pass over `samples`: training visits them in a seeded shuffle (the reference shuffles from
@@ -146,6 +155,8 @@ double FtrlOffline::one_epoch(std::vector<Sample> &samples, bool train, bool /*u
 FtrlOnline::FtrlOnline(const config_options &opt)
     : model_ptr(make_model(opt)), n_epochs(opt.epoch), cmd_(opt.cmd),
       sched_(opt.batch_size, opt.batch_ramp < 0 ? ffm_engine_default_batch_ramp(opt.w_alpha) : opt.batch_ramp) {
+  metrics_ = opt.metrics == "auc";
+  if (metrics_) model_ptr->enable_metrics(true, true);
   if (!cmd_) {
     train_stream_ = std::make_unique<CsrStream>(opt.train_path, opt.file_type, opt.thread_num);
     if (!opt.eval_path.empty()) {
@@ -206,6 +217,7 @@ void FtrlOnline::train() {
     const int i = static_cast<int>(resumed_epochs_) + n + 1;  // (a resumed run's numbering continues; else 1..n_epochs)
     const double train_loss = get_loss();
     std::printf("epoch %d train time: %.4lfs, train loss: %.4lf\n", i, seconds_since(t0), train_loss);
+    if (metrics_) print_auc_line(*model_ptr, i, FFM_METRIC_TRAIN);
     if (evaluator) evaluate(i);
   }
 }
@@ -216,17 +228,24 @@ void FtrlOnline::evaluate(int epoch) {
   evaluator->run();
   const double eval_loss = evaluator->get_loss();
   std::printf("epoch %d eval time: %.4lfs, eval loss: %.4lf\n", epoch, seconds_since(t0), eval_loss);
+  if (metrics_) {
+    double slack = 0.0;
+    const double auc = evaluator->get_auc(&slack);
+    std::printf("epoch %d eval auc: %.6lf (+-%.1e)\n", epoch, auc, slack);
+  }
 }
 
 // ---------------- Evaluator ----------------
 
 Evaluator::Evaluator(const config_options &opt)
     : stream_(std::make_unique<CsrStream>(opt.eval_path, opt.file_type, opt.thread_num)),
-      batch_(std::max(1, opt.batch_size)) {}
+      batch_(std::max(1, opt.batch_size)), want_auc_(opt.metrics == "auc") {}
 Evaluator::~Evaluator() = default;
 
 void Evaluator::load_trained_model(std::shared_ptr<FtrlModel> &train_model) {  // evaluate.cpp:35-37
   eval_model = train_model;
+  // (--metrics auc: the eval channel on; whatever the owner of the model set for training stays)
+  if (want_auc_ && !eval_model->metrics_on(FFM_METRIC_EVAL)) eval_model->enable_metrics(true, eval_model->metrics_on(FFM_METRIC_TRAIN));
   ring_ = std::make_unique<BlockRing>(eval_model.get());
 }
 
@@ -252,6 +271,13 @@ void Evaluator::run() {
   loss_sum_ = eval_model->eval_flush();
   rows_ = rows;
   stream_->rewind();
+}
+
+double Evaluator::get_auc(double *slack) {
+  if (!eval_model) throw std::logic_error("Evaluator::get_auc before load_trained_model");
+  const ffm_metrics r = eval_model->read_metrics(FFM_METRIC_EVAL, true);
+  if (slack) *slack = r.auc_slack;
+  return r.auc;
 }
 
 double Evaluator::get_loss() {

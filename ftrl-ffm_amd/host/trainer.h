@@ -74,15 +74,22 @@ class Evaluator {
   void load_trained_model(std::shared_ptr<FtrlModel> &train_model);
   void run();          // one pass over the eval file (PcTask::run in the reference)
   double get_loss();   // mean loss of the last pass (resets it)
+  // AUC of the last pass from the model's eval channel (resets the channel); *slack: the most the exact
+  // rank AUC can differ.  The channel is turned on by --metrics auc (or FtrlModel::enable_metrics).
+  double get_auc(double *slack = nullptr);
 
  private:
   std::shared_ptr<FtrlModel> eval_model;
   std::unique_ptr<CsrStream> stream_;
   std::unique_ptr<BlockRing> ring_;
   int batch_;
+  bool want_auc_ = false;
   double loss_sum_ = 0.0;
   unsigned long long rows_ = 0;
 };
+
+// --metrics auc: the line that follows an epoch's loss line ("train" / "eval"); resets the channel.
+void print_auc_line(FtrlModel &m, int epoch, int channel);
 
 class FtrlOffline {
  public:
@@ -110,6 +117,7 @@ class FtrlOffline {
   int epoch_no_ = 0;        // training passes so far (the shuffle of pass e is seeded seed + e)
   int resumed_epochs_ = 0;  // epochs a checkpoint brought along: train() prints its epochs after them
   BlockScheduler sched_;
+  bool metrics_ = false;    // --metrics auc
   std::unique_ptr<Reader> train_data_loader, eval_data_loader;  // API parity (data stays empty
                                                                 // unless load_samples() is called)
   CsrData train_csr_, eval_csr_;                                // what train()/evaluate() walk
@@ -139,6 +147,7 @@ class FtrlOnline {
   long long passes_ = 0;          // passes over the training file made by this object
   long long resumed_epochs_ = 0;  // epochs a checkpoint brought along: train() prints its epochs after them
   bool cmd_;
+  bool metrics_ = false;          // --metrics auc
   BlockScheduler sched_;
   std::unique_ptr<CsrStream> train_stream_;  // chunks of <= 20 000 lines parsed by n_threads workers
   std::unique_ptr<BlockRing> ring_;

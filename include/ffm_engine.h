@@ -410,6 +410,59 @@ int ffm_engine_profile_focus(ffm_engine *e);
 /* Text table (one line per kernel: launches, total ms, average us) into buf. */
 int ffm_engine_profile_dump(ffm_engine *e, char *buf, size_t cap);
 
+/* ---- Metrics: AUC accumulated on the device -----------------------------------------------------
+ * The reference reports mean logloss and nothing else (ftrl_offline.cpp:101-102, evaluate.cpp:39-49).
+ * Ranking quality is what click-through-rate models are compared by, and the pipelined entry points
+ * return nothing per row on purpose -- so the engine can keep a histogram of its own scores in HBM:
+ * two independent channels, both off by default (off: no launch, no allocation, nothing else changes).
+ *   FFM_METRIC_EVAL  takes every labelled predict: ffm_engine_predict_batch[_device / _async] and
+ *                    ffm_engine_predict_finish_device with label != NULL (so ffm_group_predict_batch).
+ *   FFM_METRIC_TRAIN takes the PRE-update logits of every training block (progressive validation),
+ *                    in ffm_engine_train_update_device -- the engine's own logit or, on a shard, the
+ *                    summed `logit` argument -- which every training entry point ends in.
+ * Definition (part of the contract):
+ *   score   p = sigmoid(logit) in fp32: the bits predict(..., output_prob = 1) returns.
+ *   bin     bin(p) = min((int)(p * 1048576.0f), 1048575): the product is an fp32 multiply by a power of
+ *           two, hence exact; the conversion truncates; FFM_METRIC_BINS = 2^20 bins; p = 1.0f (logit
+ *           +inf, or saturated) goes to the last bin, p = 0 to bin 0.
+ *   NaN     a NaN score goes into no bin and is counted in n_nan (the NaNs of ffm.cpp:118, and the
+ *           NaN outputs of a block the device voided).
+ *   class   a row is positive iff label > 0.
+ *   state   per channel pos[BINS] and neg[BINS], unsigned 64-bit counters in HBM (16 MiB), and one
+ *           n_nan counter; allocated when the channel is first turned on, freed by ffm_engine_destroy.
+ *           Integer counts: the result does not depend on the order rows arrive in.
+ *   numbers on the host, exact integer arithmetic in a 128-bit accumulator (csrc/metrics_host.h):
+ *           P = sum pos_b, N = sum neg_b, T = sum_b pos_b * neg_b (the mixed-bin tie mass),
+ *           U2 = 2 * sum_b pos_b * (sum_{c<b} neg_c) + T,
+ *           auc = (double)U2 / (double)(2 P N), auc_slack = (double)T / (double)(2 P N);
+ *           with P * N == 0 both are NaN and the call still succeeds.  n_mixed_bins = bins that hold
+ *           rows of both classes.
+ *   guarantee  the exact rank AUC of the p values (ties counted 1/2) lies in
+ *           [auc - auc_slack, auc + auc_slack], and equals auc when no bin holds two distinct scores
+ *           of opposite labels. */
+enum { FFM_METRIC_EVAL = 0, FFM_METRIC_TRAIN = 1 };
+#define FFM_METRIC_BINS (1 << 20)
+typedef struct { int64_t n_pos, n_neg, n_nan, n_mixed_bins; double auc, auc_slack; } ffm_metrics;
+/* bit c of channel_mask = channel c on.  A channel that turns on starts from zero; one that stays on
+ * keeps its counts; one that turns off stops counting (reading it is then FFM_E_INVALID).  The
+ * environment variable FFM_ENGINE_METRICS=<mask>, read by ffm_engine_create, turns channels on at
+ * create (of a group: on rank 0's engine). */
+int ffm_engine_metrics_enable(ffm_engine *e, int32_t channel_mask);
+/* The channel's numbers so far; reset != 0 also zeroes its counters.  Like every entry point it first
+ * launches an evaluation block ffm_engine_predict_batch_async deferred, then waits for the engine's
+ * stream.  It does NOT train blocks that are staged and not trained yet: a caller that wants every
+ * block it handed over counted calls ffm_engine_train_flush first.  A channel that is off:
+ * FFM_E_INVALID. */
+int ffm_engine_metrics_read(ffm_engine *e, int32_t channel, int32_t reset, ffm_metrics *out);
+/* The raw counters: pos / neg are host arrays of FFM_METRIC_BINS (either may be NULL).  Same waits. */
+int ffm_engine_metrics_histogram(ffm_engine *e, int32_t channel, uint64_t *pos, uint64_t *neg);
+/* The reduction alone: pure host arithmetic, no engine, no device; any n_bins >= 0. */
+int ffm_engine_metrics_from_histogram(const uint64_t *pos, const uint64_t *neg, int64_t n_bins,
+                                      int64_t n_nan, ffm_metrics *out);
+/* A group's labels are seen by every rank; rank 0's engine keeps the channels. */
+int ffm_group_metrics_enable(ffm_group *g, int32_t channel_mask);
+int ffm_group_metrics_read(ffm_group *g, int32_t channel, int32_t reset, ffm_metrics *out);
+
 #ifdef __cplusplus
 }
 #endif
