@@ -109,13 +109,13 @@ int fail(int code, const std::string &msg) {
 enum KernelId {
   K_GROUP_KEYS, K_GROUP_SORT, K_GROUP_FINISH, K_ROW, K_TMP_GRAD,
   K_LOSS_SUM, K_LINEAR_UPDATE, K_BIAS_UPDATE, K_LATENT_UPDATE, K_LATENT_UPDATE_FEW, K_LATENT_UPDATE_WALK, K_LATENT_UPDATE_GIANT,
-  K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC,
+  K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC, K_PUSH_SCORES,
   K_COUNT
 };
 const char *kKernelNames[K_COUNT] = {
     "group_keys_kernel", "group_radix_sort", "group_finish_kernel", "row_kernel<train>", "tmp_grad_kernel", "loss_sum_kernel",
     "linear_update_kernel", "bias_update_kernel", "update_kernel", "update_few_kernel", "update_walk_kernel", "update_giant_kernel",
-    "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel"};
+    "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel", "push_scores_kernel"};
 
 struct ProfRec {
   int kid;
@@ -263,7 +263,12 @@ struct ffm_engine {
   bool cur_prepared = false;   // ... was grouped ahead (ev_grouped[cur] marks the end of its grouping)
   int *h_super = nullptr;      // [kSets] page-locked: Scratch::n_super of every set, as the host reads it
   // evaluation block whose predict launch ffm_engine_predict_batch_async deferred by one call
-  struct { bool on = false; int slot = 0; bool labelled = false; } eval_pending;
+  // (scores: where its predictions go in the caller's page-locked memory, as the device sees it, or
+  // null; seq: its staging number, which push_scores_kernel publishes)
+  struct {
+    bool on = false; int slot = 0; bool labelled = false;
+    float *scores = nullptr; int output_prob = 0; int64_t seq = 0;
+  } eval_pending;
   bool eval_hold = false;       // inside predict_batch_async, before its upload is submitted
   bool eval_defer_off = false;  // FFM_EVAL_DEFER=0
   bool super_wait = true;       // wait for a block's grouping before deciding on its super launches (FFM_SUPER_WAIT=0: only ask)
@@ -344,6 +349,12 @@ struct ffm_engine {
   long long *h_pulled = nullptr;       // hipHostMalloc
   long long *d_pulled = nullptr;       // the same word as the device sees it
   unsigned *d_pull_ticket = nullptr;   // workgroups of the running upload kernel that are done
+  // The same for the scores going the other way (ffm_engine_predict_batch_async_scores): the
+  // download kernel of a scored block writes the block's staging number into a word of its own.
+  long long *h_scored = nullptr;       // hipHostMalloc
+  long long *d_scored = nullptr;       // the same word as the device sees it
+  unsigned *d_score_ticket = nullptr;  // workgroups of the running download kernel that are done
+  int64_t n_scored = 0;                // the largest number read from h_scored so far
   double *d_loss_acc = nullptr;  // [1] sum of the async blocks' losses since the last flush
   double *d_loss_part = nullptr; // [kLossParts + 1] loss_sum_kernel's partial sums and ticket
   void *d_sort_tmp[kSets] = {};  // rocPRIM radix sort workspace per scratch set
@@ -393,6 +404,9 @@ struct ffm_engine {
   // slowed the HBM-bound kernels they ran beside up to 4x (refresh of a 65536-row block 70 -> 330 us),
   // 24 (96 KB, about the link's bandwidth-delay product) still move the block at link rate.
   int grid_pull = 24;
+  // workgroups of push_scores_kernel (FFM_GRID_PUSH, at most the upload's 24): one 16-byte store per
+  // lane moves an 8192-row block with 8 (profiles/score_cost.md)
+  int grid_push = 8;
   bool single_kernel = true;  // (false: once-only features through the few-occurrence kernel)
   bool single_flat = true;    // (false: one wave per feature also for short stored records)
   int row_threads = kRowThreads;  // workgroup size of the FFM row kernel (FFM_ROW_THREADS)
@@ -611,6 +625,7 @@ void ffm_engine_destroy(ffm_engine *e) {
     if (e->ev_row_done[i]) (void)hipEventDestroy(e->ev_row_done[i]);
   }
   if (e->h_pulled) (void)hipHostFree(e->h_pulled);
+  if (e->h_scored) (void)hipHostFree(e->h_scored);
   if (e->h_super) (void)hipHostFree(e->h_super);
   if (e->prep) (void)hipStreamDestroy(e->prep);
 
@@ -667,6 +682,7 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   if (const char *sv = std::getenv("FFM_PREDICT_WAVE")) e->predict_waves = std::atoi(sv) != 0;
   if (const char *sv = std::getenv("FFM_WIDE_NNZ")) e->wide_max_nnz = std::atoi(sv);
   if (const char *sv = std::getenv("FFM_GRID_PULL")) e->grid_pull = std::max(1, std::atoi(sv));
+  if (const char *sv = std::getenv("FFM_GRID_PUSH")) e->grid_push = std::min(24, std::max(1, std::atoi(sv)));
   if (const char *sv = std::getenv("FFM_GRID_HOT")) e->grid_hot = std::max(1, std::atoi(sv));
   if (const char *sv = std::getenv("FFM_GRID_SMALL")) e->grid_small = std::max(1, std::atoi(sv));
   if (const char *sv = std::getenv("FFM_GRID_WALK")) e->grid_walk = std::max(1, std::atoi(sv));
@@ -1089,7 +1105,7 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
 }
 
 // What init_weights_kernel stored, computed on the host (csrc/init_rng.h: same bits).
-static int eval_launch_pending(ffm_engine *e);  // (engine_step.h)
+static int eval_launch_pending(ffm_engine *e);  // (engine_stage.h)
 
 int ffm_engine_init_weights_host(uint64_t seed, float init_mean, float init_stddev, int32_t latent,
                                  int64_t first, int64_t count, float *out) {

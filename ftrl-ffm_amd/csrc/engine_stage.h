@@ -1,5 +1,6 @@
 // engine_stage.h -- rows streaming from host memory inside the training loop: staging slots, the
-// upload kernel, stage_batch / train_staged / train_batch_async[_pinned] / predict_batch_async.
+// upload kernel, the score download kernel, stage_batch / train_staged / train_batch_async[_pinned] /
+// predict_batch_async[_scores].
 // Part of engine.hip's translation unit (included inside its extern "C" block).
 
 // ---- pipelined host-buffer training ---------------------------------------------------------
@@ -54,6 +55,37 @@ __global__ __launch_bounds__(256) void pull_block_kernel(PullJob job) {
   }
 }
 
+// The mirror image of the upload: the scores of one predicted block go from e->d_out to the caller's
+// page-locked (device-mapped) host memory, 16 bytes per lane -- a lane carries four rows --, the last
+// n % 4 floats as single stores.  A kernel for the reason pull_block_kernel is one: a hipMemcpyAsync
+// makes the submitting thread wait for the stream's earlier kernels.  Launched on the MAIN stream
+// right behind the block's predict kernel (eval_launch_pending), so it needs no event.
+// The stores leave the device: every lane follows its own with a system-scope release fence (the
+// upload's agent-scope __threadfence() orders nothing towards the host), and the workgroup that
+// finishes last publishes the block's staging number into h_scored, again at system scope -- a host
+// that reads the number (ffm_engine_blocks_scored, an acquire load) then reads whole scores.
+// It writes n floats and nothing behind them.
+struct PushJob {
+  const float *src; float *dst; unsigned n;
+  long long ordinal; long long *scored; unsigned *ticket;  // completion word (host memory), see h_scored
+};
+__global__ __launch_bounds__(256) void push_scores_kernel(PushJob job) {
+  const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+  const unsigned n4 = job.n >> 2;
+  const float4 *s = reinterpret_cast<const float4 *>(job.src);
+  float4 *d = reinterpret_cast<float4 *>(job.dst);
+  for (unsigned i = tid; i < n4; i += stride) d[i] = s[i];
+  if (tid < (job.n & 3u)) job.dst[(n4 << 2) + tid] = job.src[(n4 << 2) + tid];
+  __threadfence_system();
+  __syncthreads();  // (every wave of this workgroup is past its fence: its scores are in host memory)
+  if (threadIdx.x == 0) {
+    if (__hip_atomic_fetch_add(job.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+      *job.ticket = 0u;
+      __hip_atomic_store(job.scored, job.ordinal, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
 static int slots_init(ffm_engine *e) {
   if (e->slots_ready) return FFM_OK;
   const size_t R = static_cast<size_t>(e->max_rows), E = static_cast<size_t>(e->max_nnz);
@@ -74,6 +106,11 @@ static int slots_init(ffm_engine *e) {
   HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&e->d_pulled), e->h_pulled, 0));
   if (int rc_t = e->alloc(&e->d_pull_ticket, 1)) return rc_t;
   HIP_TRY(hipMemsetAsync(e->d_pull_ticket, 0, sizeof(unsigned), e->copy));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_scored), 64, hipHostMallocPortable | hipHostMallocMapped));
+  *e->h_scored = 0;
+  HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&e->d_scored), e->h_scored, 0));
+  if (int rc_t = e->alloc(&e->d_score_ticket, 1)) return rc_t;
+  HIP_TRY(hipMemsetAsync(e->d_score_ticket, 0, sizeof(unsigned), e->stream));
   int rc = e->alloc(&e->d_loss_acc, 1);
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(e->d_loss_acc, 0, sizeof(double), e->stream));
@@ -232,6 +269,17 @@ int64_t ffm_engine_blocks_pulled(ffm_engine *e) {
   return e->n_pulled;
 }
 
+// The staging number of the last block whose scores are whole in the caller's buffer.  (Scored
+// blocks finish in staging order on the main stream; the max only keeps a second reader of a
+// number it has already seen from ever getting less.)
+int64_t ffm_engine_blocks_scored(ffm_engine *e) {
+  if (!e || !e->slots_ready) return 0;
+  const int64_t seen = __atomic_load_n(e->h_scored, __ATOMIC_ACQUIRE);
+  int64_t had = __atomic_load_n(&e->n_scored, __ATOMIC_RELAXED);
+  while (seen > had && !__atomic_compare_exchange_n(&e->n_scored, &had, seen, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+  return std::max(seen, had);
+}
+
 // Phase 1 (grouping is done: refresh + forward) on the oldest staged block.
 int ffm_engine_train_forward_staged(ffm_engine *e, float *partial_logit) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
@@ -303,6 +351,44 @@ int ffm_engine_train_batch_async_pinned(ffm_engine *e, int32_t n_rows, const int
   return FFM_OK;
 }
 
+// The predict launch of the block ffm_engine_predict_batch_async uploaded one call ago,
+// and the download of its scores where the caller gave a buffer for them.
+static int eval_launch_pending(ffm_engine *e) {
+  if (!e->eval_pending.on) return FFM_OK;
+  e->eval_pending.on = false;  // (first: the launch below passes check_block)
+  ffm_engine::Slot &sl = e->slots[e->eval_pending.slot];
+  const bool labelled = e->eval_pending.labelled;
+  float *const scores = e->eval_pending.scores;
+  const int output_prob = e->eval_pending.output_prob;
+  const int64_t seq = e->eval_pending.seq;
+  HIP_TRY(hipSetDevice(e->cfg.device_id));
+  auto launch = [&]() -> int {
+    HIP_TRY(hipStreamWaitEvent(e->stream, sl.ev_copied, 0));
+    e->staged_row_cap = sl.row_cap;
+    int rc = ffm_engine_predict_batch_device(e, sl.n_rows, sl.nnz, sl.row_ptr, sl.has_field ? sl.field : nullptr, sl.feat,
+                                             sl.val, labelled ? sl.label : nullptr, output_prob, e->d_out,
+                                             labelled ? e->d_loss_sum : nullptr);
+    if (rc) return rc;
+    if (labelled) hipLaunchKernelGGL(loss_accumulate_kernel, dim3(1), dim3(1), 0, e->stream, e->d_loss_acc, e->d_loss_sum);
+    if (scores) {
+      // the block's scores to the caller's buffer, behind its predict kernel on the same stream
+      // (a block without rows still publishes its number, in order)
+      const PushJob job{e->d_out, scores, static_cast<unsigned>(sl.n_rows), static_cast<long long>(seq), e->d_scored, e->d_score_ticket};
+      const int grid = std::max(1, std::min(e->grid_push, cdiv(sl.n_rows >> 2, 256)));
+      LAUNCH(e, K_PUSH_SCORES, push_scores_kernel, grid, 256, 0, job);
+    }
+    HIP_TRY(hipGetLastError());
+    return FFM_OK;
+  };
+  const int rc = launch();
+  // (also after a failure: the slot's device arrays are free again -- nothing else will ever say so)
+  const hipError_t err_ev = hipEventRecord(sl.ev_trained, e->stream);
+  sl.free_ev = sl.ev_trained;
+  if (rc) return fail(rc, "deferred predict_batch_async block " + std::to_string(seq) + ": " + g_last_error);
+  HIP_TRY(err_ev);
+  return FFM_OK;
+}
+
 // Pipelined evaluation: upload through a staging slot on the side stream, predict on the main one.
 // The predict launch of a block is DEFERRED by one call (the caller reads nothing before
 // ffm_engine_train_flush): call t submits the upload of block t and then the predict of block t-1, so
@@ -310,9 +396,12 @@ int ffm_engine_train_batch_async_pinned(ffm_engine *e, int32_t n_rows, const int
 // the predict kernel that fills every wave slot, not behind it (round 5: 51.9 M rows/s with the H2D
 // against 68.6 M resident).  The deferred launch is made by the next call of any entry point that
 // puts work on the main stream (check_block), by ffm_engine_sync / check_errors and by the flush.
-int ffm_engine_predict_batch_async(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
-                                   const int32_t *field, const int32_t *feat, const float *val,
-                                   const int32_t *label, int32_t zero_copy) {
+// scores_host (may be NULL): the block's predictions also go to the caller's page-locked buffer
+// (push_scores_kernel, behind the deferred predict launch).
+int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                                          const int32_t *field, const int32_t *feat, const float *val,
+                                          const int32_t *label, int32_t zero_copy, int32_t output_prob,
+                                          float *scores_host) {
   int32_t nnz = 0;
   int longest = 1;
   if (e && e->m.type != FFM_MODEL_FFM) field = nullptr;  // (LR / FM: no fields to upload)
@@ -324,6 +413,18 @@ int ffm_engine_predict_batch_async(ffm_engine *e, int32_t n_rows, const int32_t 
   if (e->m.n_shards > 1) return fail(FFM_E_INVALID, "a sharded engine predicts through predict_batch_device + predict_finish_device");
   if (e->n_staged > 0 || e->has_pending) return fail(FFM_E_INVALID, "staged training blocks are still waiting");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
+  // (refused before the upload is launched: that kernel publishes the block's number)
+  float *scores_dev = nullptr;
+  if (scores_host) {
+    if ((reinterpret_cast<uintptr_t>(scores_host) & 15u) != 0) return fail(FFM_E_INVALID, "scores_host must be 16-byte aligned");
+    void *mapped = nullptr;
+    if (hipHostGetDevicePointer(&mapped, scores_host, 0) != hipSuccess || !mapped) {
+      (void)hipGetLastError();
+      return fail(FFM_E_INVALID, "scores_host must be page-locked, device-mapped host memory (ffm_engine_pin_host)");
+    }
+    if ((reinterpret_cast<uintptr_t>(mapped) & 15u) != 0) return fail(FFM_E_INVALID, "scores_host must be 16-byte aligned");
+    scores_dev = static_cast<float *>(mapped);
+  }
   if ((rc = e->drain())) return rc;
   int this_slot = 0;
   bool slot_was_used = false;
@@ -351,8 +452,17 @@ int ffm_engine_predict_batch_async(ffm_engine *e, int32_t n_rows, const int32_t 
   e->eval_pending.on = true;
   e->eval_pending.slot = this_slot;
   e->eval_pending.labelled = label != nullptr;
+  e->eval_pending.scores = scores_dev;
+  e->eval_pending.output_prob = scores_dev ? (output_prob != 0) : 0;
+  e->eval_pending.seq = sl.seq;
   if (e->eval_defer_off) return eval_launch_pending(e);  // (FFM_EVAL_DEFER=0: as rounds 3-5)
   return FFM_OK;
+}
+
+int ffm_engine_predict_batch_async(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                                   const int32_t *field, const int32_t *feat, const float *val,
+                                   const int32_t *label, int32_t zero_copy) {
+  return ffm_engine_predict_batch_async_scores(e, n_rows, row_ptr, field, feat, val, label, zero_copy, 0, nullptr);
 }
 
 int ffm_engine_train_flush(ffm_engine *e, double *loss_sum_out) {

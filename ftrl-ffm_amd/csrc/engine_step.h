@@ -4,7 +4,7 @@
 
 // ---- one block of rows ---------------------------------------------------------------------
 
-static int eval_launch_pending(ffm_engine *e);
+static int eval_launch_pending(ffm_engine *e);  // (engine_stage.h)
 static void launch_metric(ffm_engine *e, int channel, int n_rows, const float *score, int is_prob, const int *label);  // (engine_metrics.h)
 __global__ void loss_accumulate_kernel(double *acc, const double *one) { *acc += *one; }
 
@@ -499,26 +499,6 @@ int ffm_engine_predict_batch_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
   if (label) launch_metric(e, FFM_METRIC_EVAL, n_rows, out ? out : e->d_out, output_prob, label);
   if (loss_sum_out && label)
     LAUNCH(e, K_LOSS_SUM, loss_sum_kernel, loss_grid(n_rows), 256, 0, n_rows, e->sc[e->cur].loss, loss_sum_out, e->d_loss_part);
-  HIP_TRY(hipGetLastError());
-  return FFM_OK;
-}
-
-// The predict launch of the block ffm_engine_predict_batch_async uploaded one call ago (engine_stage.h).
-static int eval_launch_pending(ffm_engine *e) {
-  if (!e->eval_pending.on) return FFM_OK;
-  e->eval_pending.on = false;  // (first: the launch below passes check_block)
-  ffm_engine::Slot &sl = e->slots[e->eval_pending.slot];
-  const bool labelled = e->eval_pending.labelled;
-  HIP_TRY(hipSetDevice(e->cfg.device_id));
-  HIP_TRY(hipStreamWaitEvent(e->stream, sl.ev_copied, 0));
-  e->staged_row_cap = sl.row_cap;
-  int rc = ffm_engine_predict_batch_device(e, sl.n_rows, sl.nnz, sl.row_ptr, sl.has_field ? sl.field : nullptr, sl.feat,
-                                           sl.val, labelled ? sl.label : nullptr, 0, e->d_out,
-                                           labelled ? e->d_loss_sum : nullptr);
-  if (rc) return rc;
-  if (labelled) hipLaunchKernelGGL(loss_accumulate_kernel, dim3(1), dim3(1), 0, e->stream, e->d_loss_acc, e->d_loss_sum);
-  HIP_TRY(hipEventRecord(sl.ev_trained, e->stream));  // the slot's device arrays are free again
-  sl.free_ev = sl.ev_trained;
   HIP_TRY(hipGetLastError());
   return FFM_OK;
 }

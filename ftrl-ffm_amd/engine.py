@@ -95,6 +95,9 @@ ABI = [
     ("ffm_engine_train_batch_async_pinned", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR),
     ("ffm_engine_train_flush", ctypes.c_int, [_vp, _f64p]),
     ("ffm_engine_predict_batch_async", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [ctypes.c_int32]),
+    ("ffm_engine_predict_batch_async_scores", ctypes.c_int,
+     [_vp, ctypes.c_int32] + _CSR + [ctypes.c_int32, ctypes.c_int32, _vp]),
+    ("ffm_engine_blocks_scored", ctypes.c_int64, [_vp]),
     ("ffm_engine_stage_batch", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [ctypes.c_int32]),
     ("ffm_engine_blocks_pulled", ctypes.c_int64, [_vp]),
     ("ffm_engine_train_forward_staged", ctypes.c_int, [_vp, _vp]),
@@ -440,10 +443,34 @@ class Engine:
         self._check(self.lib.ffm_engine_train_flush(self.h, ctypes.byref(loss)))
         return float(loss.value)
 
-    def predict_batch_async(self, c, zero_copy=False):
+    def predict_batch_async(self, c, zero_copy=False, scores=None, output_prob=False):
         """Pipelined evaluation: uploads the block on the side stream and predicts it; the loss sum
-        of all blocks since the last flush comes back from train_flush()."""
-        self._check(self.lib.ffm_engine_predict_batch_async(self.h, *self._csr(c), int(zero_copy)))
+        of all blocks since the last flush comes back from train_flush().
+        scores: a float32 array of at least c.n_rows elements in page-locked memory (score_buffer())
+        that receives the block's logits (probabilities with output_prob), bit for bit what
+        predict_batch returns; it is complete once blocks_scored() has reached the block's staging
+        number, or after sync() / train_flush()."""
+        if scores is None:
+            self._check(self.lib.ffm_engine_predict_batch_async(self.h, *self._csr(c), int(zero_copy)))
+            return
+        if scores.dtype != np.float32 or scores.ndim != 1 or scores.size < c.n_rows or not scores.flags.c_contiguous:
+            raise ValueError("scores: a contiguous float32 array of at least n_rows elements")
+        self._check(self.lib.ffm_engine_predict_batch_async_scores(
+            self.h, *self._csr(c), int(zero_copy), int(bool(output_prob)), scores.ctypes.data))
+
+    def blocks_scored(self):
+        """Staging number of the last block whose scores are whole in its buffer (non-blocking)."""
+        return int(self.lib.ffm_engine_blocks_scored(self.h))
+
+    def score_buffer(self, n):
+        """A page-locked float32 array of n elements for predict_batch_async(scores=...): pages of
+        its own (page_aligned), locked in place (ffm_engine_pin_host).  Release with free_score_buffer."""
+        a = page_aligned(n, np.float32)
+        self._check(self.lib.ffm_engine_pin_host(a.ctypes.data, max(1, a.size) * 4))
+        return a
+
+    def free_score_buffer(self, a):
+        self.lib.ffm_engine_unpin_host(a.ctypes.data)
 
     def train_rows(self, c):
         """Row after row (n_rows == 1 per call): the reference's sequential train() loop."""

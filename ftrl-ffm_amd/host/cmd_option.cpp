@@ -25,7 +25,9 @@ const std::string_view cmd_help =
     "--w_l1 <w_L1_reg>: L1 regularization parameter of w\tdefault:0.1\n"
     "--w_l2 <w_L2_reg>: L2 regularization parameter of w\tdefault:5.0\n"
     "--n_threads <threads_num>: host threads for parsing\tdefault:1\n"
-    "--n_epochs <epochs>: how many epochs to train; with --resume_from: how many MORE\tdefault:1\n"
+    "--n_epochs <epochs>: how many epochs to train; with --resume_from: how many MORE; 0 trains nothing\n"
+    "              (--resume_from ck --n_epochs 0 --predict_data F --predict_out P scores a saved model;\n"
+    "              --train_data may then be left out)\tdefault:1\n"
     "--online <online>: whether to online training mode\tdefault:true\n"
     "--batch_size <rows>: rows per block sent to the GPU\tdefault:4096\n"
     "--batch_ramp <r>: block size grows as rows_seen/r (0 disables)\tdefault: by w_alpha (32 up to 1e-3)\n"
@@ -45,6 +47,13 @@ const std::string_view cmd_help =
     "--metrics <auc|none>: auc = after each epoch's loss line one more line with the AUC of the same rows -- training:\n"
     "              of the pre-update predictions (progressive validation) --, histogrammed on the device in 2^20\n"
     "              score bins; the +- is the most the exact rank AUC can differ\tdefault:none\n"
+    "--predict_data <data_path>: after training (and after the model / checkpoint is written) score this file:\n"
+    "              one prediction per row, in file order; its label column is parsed and ignored\n"
+    "--predict_out <path>: where the predictions go, one per line, each the shortest decimal that parses back\n"
+    "              to the same float (nan, inf, -inf by name); needs --predict_data and the other way round.\n"
+    "              Prints `scored N rows time: Ts`.  With --n_gpus > 1 the blocks are predicted one by one\n"
+    "              (the synchronous group call), on one GPU they stream through the pipelined prediction\n"
+    "--predict_output <prob|logit>: what is written\tdefault:prob\n"
     "--learn <bool>: keep initial latent weights until their first gradient and use g2*g2 at\n"
     "                ffm.cpp:118, so FM/FFM factors train (NOT the reference's results)\tdefault:false\n";
 
@@ -110,9 +119,18 @@ void config_options::parse_option(int argc, char *argv[]) {
       if (v != "auc" && v != "none") throw std::invalid_argument("--metrics takes auc or none");
       metrics = v;
     }
+    else if (k == "--predict_data") predict_path = v;
+    else if (k == "--predict_out") predict_out = v;
+    else if (k == "--predict_output") {
+      if (v != "prob" && v != "logit") throw std::invalid_argument("--predict_output takes prob or logit");
+      predict_prob = v == "prob";
+    }
     else throw std::invalid_argument("unknown argument: " + k + "\n");
   }
-  file_type = detect_file_type(train_path);
+  if (predict_path.empty() != predict_out.empty())
+    throw std::invalid_argument("--predict_data and --predict_out go together: one was given without the other");
+  // (--n_epochs 0 with a file to score needs no training file: the format is then the scored file's)
+  file_type = detect_file_type(train_path.empty() && epoch == 0 && !predict_path.empty() ? predict_path : train_path);
   if (model_type == "FFM" && file_type != "libffm") {
     std::fprintf(stderr, "FFM model requires libffm data format...\n");
     std::exit(EXIT_FAILURE);

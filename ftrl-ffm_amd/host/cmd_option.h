@@ -30,6 +30,8 @@ struct config_options {
   std::string checkpoint_path;  // --checkpoint_path: write a sparse resumable checkpoint after training
   std::string resume_from;      // --resume_from: load one before training; --n_epochs then counts MORE epochs
   std::string metrics = "none";  // --metrics auc: one AUC line after every loss line (accumulated on the device)
+  std::string predict_path, predict_out;  // --predict_data / --predict_out: score a file after training, one line per row
+  bool predict_prob = true;               // --predict_output prob | logit
 
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };

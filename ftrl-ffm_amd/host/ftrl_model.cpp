@@ -296,18 +296,44 @@ ffm_metrics FtrlModel::read_metrics(int channel, bool reset) {
   return m;
 }
 
-long long FtrlModel::predict_block_async(const CsrBlock &blk, bool pinned) {
+long long FtrlModel::predict_block_async(const CsrBlock &blk, bool pinned, float *scores, bool output_prob, bool *complete) {
   const int n = blk.n_rows();
   bool fits = n <= max_rows_ && blk.row_ptr[n] <= max_nnz_;
   for (int r = 0; r < n && fits; r++) fits = blk.row_ptr[r + 1] - blk.row_ptr[r] <= max_row_nnz_;
-  if (grp_ || !fits) {  // a group predicts block by block (every shard, then the sum); so do split blocks
-    eval_loss_pending_ += predict_block(blk, false);
+  bool device_writes = scores == nullptr;  // (nothing to write: the pipelined call as it always was)
+  for (const auto &range : pinned_scores_)
+    device_writes = device_writes || (scores >= range.first && scores + n <= range.first + range.second);
+  if (complete) *complete = grp_ || !fits || !device_writes;
+  if (grp_ || !fits || !device_writes) {  // a group predicts block by block (every shard, then the sum); so do split blocks
+    eval_loss_pending_ += predict_block(blk, scores && output_prob, scores);
     return handed_over_;
   }
-  check(ffm_engine_predict_batch_async(eng_, n, blk.row_ptr.data(), blk.field.data(), blk.feat.data(),
-                                       blk.val.data(), blk.label.data(), pinned ? 1 : 0),
-        "ffm_engine_predict_batch_async");
+  if (scores)
+    check(ffm_engine_predict_batch_async_scores(eng_, n, blk.row_ptr.data(), blk.field.data(), blk.feat.data(),
+                                                blk.val.data(), blk.label.data(), pinned ? 1 : 0, output_prob ? 1 : 0, scores),
+          "ffm_engine_predict_batch_async_scores");
+  else
+    check(ffm_engine_predict_batch_async(eng_, n, blk.row_ptr.data(), blk.field.data(), blk.feat.data(),
+                                         blk.val.data(), blk.label.data(), pinned ? 1 : 0),
+          "ffm_engine_predict_batch_async");
   return ++handed_over_;
+}
+
+long long FtrlModel::blocks_scored() { return grp_ ? 0 : ffm_engine_blocks_scored(eng_); }
+
+bool FtrlModel::pin_scores(float *p, size_t n) {
+  if (!p || !n || ffm_engine_pin_host(p, (4 * n + 4095) & ~static_cast<size_t>(4095)) != FFM_OK) return false;
+  pinned_scores_.emplace_back(p, n);
+  return true;
+}
+
+void FtrlModel::unpin_scores(float *p) {
+  for (size_t i = 0; i < pinned_scores_.size(); i++)
+    if (pinned_scores_[i].first == p) {
+      ffm_engine_unpin_host(p);
+      pinned_scores_.erase(pinned_scores_.begin() + static_cast<long>(i));
+      return;
+    }
 }
 
 double FtrlModel::eval_flush() {

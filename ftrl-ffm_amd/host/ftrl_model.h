@@ -104,8 +104,24 @@ class FtrlModel {
   // is uploaded on the side stream while the previous one is predicted; `pinned`: a pin_block()ed
   // block, pulled in place and untouched until blocks_pulled() has reached the returned ordinal.
   // eval_flush() waits and returns the sum of loss(y, predict(x)) since the last flush.
-  long long predict_block_async(const CsrBlock &blk, bool pinned);
+  // With `scores` the block's predictions come back as well, one float per row (logits, or
+  // probabilities with output_prob), the bits predict_block(blk, output_prob, out) gives.  When
+  // `scores` lies in memory page-locked by pin_scores() and the block fits one engine call, they are
+  // written by the device behind the block's predict kernel (ffm_engine_predict_batch_async_scores):
+  // *complete = false, and they are whole once blocks_scored() has reached the returned ordinal, or
+  // after eval_flush().  Otherwise -- a group (--n_gpus > 1: the synchronous ffm_group_predict_batch is
+  // the only way there), a block split into several calls, a buffer that is not page-locked -- they
+  // are written before the call returns: *complete = true.
+  long long predict_block_async(const CsrBlock &blk, bool pinned, float *scores = nullptr, bool output_prob = false,
+                                bool *complete = nullptr);
   double eval_flush();
+  // Ordinal of the last block whose scores are whole (non-blocking, never decreases; may be asked
+  // from another thread than the one that hands blocks over); 0 for a group.
+  long long blocks_scored();
+  // Page-locks [p, p + n) for predict_block_async's scores; give it pages of its own (PageAllocator).
+  // false: no page-locked memory to be had (the scores then come back synchronously).
+  bool pin_scores(float *p, size_t n);
+  void unpin_scores(float *p);
   int n_gpus() const { return n_gpus_; }
   // AUC accumulated on the device (include/ffm_engine.h "Metrics"), one engine or a group alike:
   // `eval` takes every labelled predict, `train` the pre-update logits of every training block.
@@ -165,6 +181,7 @@ class FtrlModel {
   std::vector<int32_t> lin_owner_of_field_;  // [n_fields] shard that owns a field's linear terms
   int bias_owner_ = 0;
   double eval_loss_pending_ = 0.0;  // group: evaluation blocks are predicted synchronously
+  std::vector<std::pair<float *, size_t>> pinned_scores_;  // pin_scores() ranges (floats)
   ffm_engine *shard(int r) const;
   int field_of(int feat) const { return per_field_ > 0 ? std::min(feat / per_field_, n_fields - 1) : 0; }
   int per_field_ = 0;  // ids per field under --field_ranges uniform

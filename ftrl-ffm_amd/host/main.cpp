@@ -2,6 +2,7 @@
 // offline task, train.
 #include <cstdio>
 #include <cstdlib>
+#include <chrono>
 #include <stdexcept>
 #include <string>
 
@@ -34,6 +35,14 @@ int main(int argc, char *argv[]) {
       task.train();
       save(*task.model_ptr);
       if (!opt.checkpoint_path.empty()) task.model_ptr->save_checkpoint(opt.checkpoint_path, 3, task.progress());
+      // --predict_data / --predict_out: last, so the scores are those of the model that was written
+      if (!opt.predict_path.empty()) {
+        const auto t0 = std::chrono::steady_clock::now();
+        ftrl::Scorer scorer(opt, &*task.model_ptr);
+        const unsigned long long n = scorer.run();
+        std::printf("scored %llu rows time: %.4lfs\n", n,
+                    std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+      }
     };
     if (opt.online) {
       ftrl::FtrlOnline task(opt);

@@ -1,12 +1,17 @@
 #include "trainer.h"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
+#include <mutex>
 #include <numeric>
 #include <random>
 #include <thread>
+
+#include "score_writer.h"
 
 namespace ftrl {
 
@@ -28,11 +33,13 @@ FtrlOffline::FtrlOffline(const config_options &opt)
   // the files go straight into CSR (csr_reader.h); the Sample-based readers exist for callers
   // that use one_epoch(std::vector<Sample>&, ...) as the reference's tests do
   train_data_loader = std::make_unique<Reader>(opt.file_type);
-  std::printf("Loading data from file: %s\n", opt.train_path.c_str());
-  const auto t0 = timer::now();
-  train_csr_ = load_csr(opt.train_path, opt.file_type, n_threads);
-  std::printf("Total number of samples loaded: %zu\nparsing data time: %.4lfs\n",
-              train_csr_.n_rows(), seconds_since(t0));
+  if (!opt.train_path.empty()) {  // (--n_epochs 0 needs no training file)
+    std::printf("Loading data from file: %s\n", opt.train_path.c_str());
+    const auto t0 = timer::now();
+    train_csr_ = load_csr(opt.train_path, opt.file_type, n_threads);
+    std::printf("Total number of samples loaded: %zu\nparsing data time: %.4lfs\n",
+                train_csr_.n_rows(), seconds_since(t0));
+  }
   if (!opt.eval_path.empty()) {
     eval_data_loader = std::make_unique<Reader>(opt.file_type);
     eval_csr_ = load_csr(opt.eval_path, opt.file_type, n_threads);
@@ -158,7 +165,8 @@ FtrlOnline::FtrlOnline(const config_options &opt)
   metrics_ = opt.metrics == "auc";
   if (metrics_) model_ptr->enable_metrics(true, true);
   if (!cmd_) {
-    train_stream_ = std::make_unique<CsrStream>(opt.train_path, opt.file_type, opt.thread_num);
+    if (!opt.train_path.empty())  // (--n_epochs 0 needs no training file)
+      train_stream_ = std::make_unique<CsrStream>(opt.train_path, opt.file_type, opt.thread_num);
     if (!opt.eval_path.empty()) {
       evaluator = std::make_unique<Evaluator>(opt);
       evaluator->load_trained_model(model_ptr);
@@ -285,6 +293,127 @@ double Evaluator::get_loss() {
   loss_sum_ = 0.0;
   rows_ = 0;
   return r;
+}
+
+// ---------------- Scorer ----------------
+
+Scorer::Scorer(const config_options &opt, FtrlModel *model)
+    : model_(model), stream_(std::make_unique<CsrStream>(opt.predict_path, opt.file_type, opt.thread_num)),
+      out_path_(opt.predict_out), batch_(std::max(1, opt.batch_size)), n_threads_(std::max(1, opt.thread_num)),
+      prob_(opt.predict_prob) {}
+Scorer::~Scorer() = default;
+
+unsigned long long Scorer::run() {
+  std::FILE *f = std::fopen(out_path_.c_str(), "wb");
+  if (!f) throw std::runtime_error("cannot open " + out_path_ + " for writing");
+  BlockRing ring(model_);
+  const bool pinned_rows = ring.ready();
+  // the ring of score buffers: entry i % kScoreRing carries block i from its hand-over to its write
+  struct Entry {
+    std::vector<float, PageAllocator<float>> buf;
+    bool pinned = false;
+    size_t rows = 0;
+    long long wait_for = 0;  // the ordinal blocks_scored() must reach; 0: the scores are already there
+  };
+  std::vector<Entry> ent(kScoreRing);
+  for (auto &en : ent) {
+    en.buf.resize(static_cast<size_t>(batch_));
+    en.pinned = model_->pin_scores(en.buf.data(), en.buf.size());
+  }
+  std::mutex mu;
+  std::condition_variable cv;
+  size_t submitted = 0, written = 0;
+  bool done = false;
+  std::atomic<bool> give_up{false};
+  bool write_failed = false;
+  // (formatting is ~50 ns per score on one thread -- a fifth of the rate the device predicts at: a block is
+  // formatted in up to --n_threads slices side by side, then written in order)
+  const int fmt_threads = std::max(1, n_threads_);
+  std::thread writer([&] {
+    std::vector<std::string> text(static_cast<size_t>(fmt_threads));
+    for (size_t i = 0;; i++) {
+      {
+        std::unique_lock<std::mutex> lock(mu);
+        cv.wait(lock, [&] { return submitted > i || done; });
+        if (submitted <= i) return;
+      }
+      const Entry &en = ent[i % kScoreRing];
+      // (the block's predict launch is deferred by one call: it is whole after the next hand-over, or
+      // after the flush that ends the pass)
+      while (en.wait_for > 0 && model_->blocks_scored() < en.wait_for) {
+        if (give_up.load()) return;
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+      }
+      const int slices = static_cast<int>(std::min<size_t>(static_cast<size_t>(fmt_threads), (en.rows + 1023) / 1024));
+      const size_t per = slices > 0 ? (en.rows + static_cast<size_t>(slices) - 1) / static_cast<size_t>(slices) : 0;
+#pragma omp parallel for schedule(static, 1) num_threads(slices) if (slices > 1)
+      for (int t = 0; t < slices; t++) {
+        const size_t lo = std::min(en.rows, per * static_cast<size_t>(t)), hi = std::min(en.rows, lo + per);
+        text[static_cast<size_t>(t)].clear();
+        append_scores(en.buf.data() + lo, hi - lo, text[static_cast<size_t>(t)]);
+      }
+      for (int t = 0; t < slices && !write_failed; t++)
+        write_failed = std::fwrite(text[static_cast<size_t>(t)].data(), 1, text[static_cast<size_t>(t)].size(), f) != text[static_cast<size_t>(t)].size();
+      {
+        std::lock_guard<std::mutex> lock(mu);
+        written = i + 1;
+      }
+      cv.notify_all();
+    }
+  });
+  auto finish = [&](bool failed) {
+    if (failed) give_up.store(true);
+    {
+      std::lock_guard<std::mutex> lock(mu);
+      done = true;
+    }
+    cv.notify_all();
+    writer.join();
+    for (auto &en : ent)
+      if (en.pinned) model_->unpin_scores(en.buf.data());
+  };
+  unsigned long long rows = 0;
+  try {
+    CsrBlock blk;
+    for (size_t i = 0;; i++) {
+      {  // entry i % kScoreRing is free once block i - kScoreRing is in the file
+        std::unique_lock<std::mutex> lock(mu);
+        cv.wait(lock, [&] { return written + kScoreRing > i; });
+      }
+      Entry &en = ent[i % kScoreRing];
+      const CsrBlock *b = &blk;
+      size_t got;
+      if (pinned_rows) {
+        CsrBlock &rb = ring.acquire();
+        got = stream_->next(std::min<size_t>(batch_, ring.row_capacity()), rb, ring.nnz_capacity(), true);
+        b = &rb;
+      } else {
+        got = stream_->next(static_cast<size_t>(batch_), blk);
+      }
+      if (got == 0) break;
+      bool complete = false;
+      const long long ordinal = model_->predict_block_async(*b, pinned_rows, en.buf.data(), prob_, &complete);
+      if (pinned_rows) ring.handed_over(ordinal);
+      en.rows = got;
+      en.wait_for = complete ? 0 : ordinal;
+      {
+        std::lock_guard<std::mutex> lock(mu);
+        submitted = i + 1;
+      }
+      cv.notify_all();
+      rows += got;
+    }
+    model_->eval_flush();  // (launches the last block and waits; the labels' loss is not reported)
+  } catch (...) {
+    finish(true);
+    std::fclose(f);
+    throw;
+  }
+  finish(false);
+  const bool closed = std::fclose(f) == 0;
+  if (write_failed || !closed) throw std::runtime_error("writing " + out_path_ + " failed");
+  stream_->rewind();
+  return rows;
 }
 
 }  // namespace ftrl

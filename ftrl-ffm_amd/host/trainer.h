@@ -88,6 +88,30 @@ class Evaluator {
   unsigned long long rows_ = 0;
 };
 
+// Scorer (--predict_data / --predict_out): streams a file through the model and writes one prediction
+// per row, in file order.  Modelled on Evaluator: chunks parsed by n_threads workers (CsrStream), blocks
+// gathered in the page-locked BlockRing, uploaded and predicted pipelined (FtrlModel::
+// predict_block_async) -- with a small ring of page-locked score buffers which the device fills behind
+// each block's predict kernel.  A writer thread waits for FtrlModel::blocks_scored(), formats the block
+// (score_writer.h; in up to --n_threads slices side by side, never by the machine's core count) and
+// appends it while the next blocks are parsed and predicted.  Memory is bounded by the two rings, never by the file.  The file's label
+// column is parsed and ignored: nothing of the pass is reported but the rows.
+// On a group (--n_gpus > 1) every block is predicted by the synchronous ffm_group_predict_batch.
+class Scorer {
+ public:
+  static constexpr int kScoreRing = 6;
+  Scorer(const config_options &opt, FtrlModel *model);
+  ~Scorer();
+  unsigned long long run();  // one pass over the file; returns the rows written
+
+ private:
+  FtrlModel *model_;
+  std::unique_ptr<CsrStream> stream_;
+  std::string out_path_;
+  int batch_, n_threads_;
+  bool prob_;
+};
+
 // --metrics auc: the line that follows an epoch's loss line ("train" / "eval"); resets the channel.
 void print_auc_line(FtrlModel &m, int epoch, int channel);
 

@@ -284,6 +284,34 @@ int ffm_engine_train_batch_async_pinned(ffm_engine *e, int32_t n_rows, const int
 int ffm_engine_predict_batch_async(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
                                    const int32_t *field, const int32_t *feat, const float *val,
                                    const int32_t *label, int32_t zero_copy);
+/* The same, and the block's predictions come back, one float per row, without a wait:
+ *   scores_host[n_rows]: page-locked, device-mapped host memory (hipHostMalloc, hipHostRegister or
+ * ffm_engine_pin_host), 16-byte aligned.  It receives what ffm_engine_predict_batch(..., output_prob,
+ * out, ...) puts in `out` for the same rows and model state, bit for bit (logits, or probabilities when
+ * output_prob != 0).  A kernel on the engine's stream writes them right behind the block's predict
+ * kernel -- exactly n_rows floats and nothing behind them -- and then publishes the block's number.
+ *   scores_host == NULL is exactly ffm_engine_predict_batch_async: no extra launch, no allocation,
+ * output_prob is ignored.  Loss accumulation, the flush sum, the eval metrics channel and the
+ * deferral by one call are the same with and without scores.
+ *   Numbering: a block's number is its 1-based staging number, the one ffm_engine_blocks_pulled()
+ * counts in -- one numbering, two questions (is the block uploaded? are its scores back?).
+ * ffm_engine_blocks_scored() is non-blocking and never decreases; once it has reached a block's
+ * number, that block's n_rows floats are complete and visible to the host.  Blocks passed without a
+ * score buffer publish nothing (the count moves from scored block to scored block).  Since a
+ * block's predict launch is deferred by one call, blocks_scored() reaches block t only after the
+ * call for block t+1 (or any engine call that launches the deferred block: ffm_engine_sync,
+ * ffm_engine_train_flush, ...).  After ffm_engine_sync or ffm_engine_train_flush has returned, every
+ * score requested so far is written and blocks_scored() has reached the last scored block.  A block
+ * with n_rows == 0 is accepted and still publishes its number, in order.
+ *   Refused with FFM_E_INVALID and a message: a scores_host that is not 16-byte aligned or not
+ * page-locked, a sharded engine, staged training blocks still waiting (as for the call above).
+ *   An error of the deferred launch of block t is returned by the engine call that made the launch
+ * -- the next one --, its text prefixed with "deferred predict_batch_async block t". */
+int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                                          const int32_t *field, const int32_t *feat, const float *val,
+                                          const int32_t *label, int32_t zero_copy, int32_t output_prob,
+                                          float *scores_host);
+int64_t ffm_engine_blocks_scored(ffm_engine *e);
 
 /* The two halves of ffm_engine_train_batch_async, for callers that put something between forward
  * and update -- the sharded trainer's all-reduce: ffm_engine_stage_batch copies the host block into
