@@ -317,6 +317,7 @@ struct ffm_engine {
   // staging for the host-buffer entry points
   int *d_row_ptr = nullptr, *d_field = nullptr, *d_feat = nullptr, *d_label = nullptr;
   float *d_val = nullptr, *d_out = nullptr;
+  float *d_weight = nullptr;  // [max_rows] sample weights of a ffm_engine_train_batch_weighted block (allocated by the first)
   double *d_loss_sum = nullptr;
   // pipelined host-buffer training (ffm_engine_train_batch_async): kSlots staging slots, each a
   // pinned host image and device arrays of one block; block t is copied + grouped on the prep
@@ -334,7 +335,14 @@ struct ffm_engine {
     int64_t seq = 0;  // 1-based number of the block staged in it
     int n_rows = 0, nnz = 0, row_cap = 0;
     bool has_field = false;
+    // sample weights of the block (ffm_engine_stage_batch_weighted): the device array and its pinned
+    // image, both allocated when the engine first stages a weighted block; valid, like the labels, until
+    // the slot is refilled -- after its block's update
+    float *weight = nullptr;
+    char *pinned_w = nullptr;
+    bool has_weight = false;
   } slots[kSlots];
+  bool slot_weights_ready = false;
   bool slots_ready = false;
   int slot_next = 0;
   int staged[kSlots] = {};  // slots staged and not yet in training, oldest first
@@ -371,6 +379,7 @@ struct ffm_engine {
   std::vector<void *> allocs;
   // split-phase bookkeeping
   Rows pending{};
+  const float *pending_weight = nullptr;  // sample weights of the pending block (device) or null
   bool has_pending = false;
   bool whole_step = false;  // the call in flight is train_batch_device (forward + update in one)
   // train_batch_device on one shard: the row kernel has the whole logit, so it also produces
@@ -615,6 +624,7 @@ void ffm_engine_destroy(ffm_engine *e) {
   for (auto ev : e->event_pool) (void)hipEventDestroy(ev);
   for (auto &sl : e->slots) {
     if (sl.pinned) (void)hipHostFree(sl.pinned);
+    if (sl.pinned_w) (void)hipHostFree(sl.pinned_w);
     if (sl.ev_copied) (void)hipEventDestroy(sl.ev_copied);
     if (sl.ev_trained) (void)hipEventDestroy(sl.ev_trained);
   }

@@ -223,14 +223,14 @@ const char *ffm_group_collective(const ffm_group *g) {
   return !g ? "" : g->use_rccl ? "rccl" : g->eng.size() > 1 ? "device-local sum" : "none";
 }
 
-int ffm_group_train_batch_async(ffm_group *g, int32_t n_rows, const int32_t *row_ptr,
-                                const int32_t *field, const int32_t *feat, const float *val,
-                                const int32_t *label, int32_t zero_copy) {
+int ffm_group_train_batch_async_weighted(ffm_group *g, int32_t n_rows, const int32_t *row_ptr,
+                                         const int32_t *field, const int32_t *feat, const float *val,
+                                         const int32_t *label, const float *weight, int32_t zero_copy) {
   if (!g) return fail(FFM_E_INVALID, "null group");
   if (g->poisoned) return fail(FFM_E_INVALID, "an earlier block reached only some of the group's engines: destroy the group");
   int rc;
   for (size_t r = 0; r < g->eng.size(); r++)
-    if ((rc = ffm_engine_stage_batch(g->eng[r], n_rows, row_ptr, field, feat, val, label, zero_copy))) {
+    if ((rc = ffm_engine_stage_batch_weighted(g->eng[r], n_rows, row_ptr, field, feat, val, label, weight, zero_copy))) {
       // (engine 0 refuses what any engine would refuse -- the checks are the block's -- so r > 0 means
       // a device error; the engines before r hold one block more than the rest)
       if (r > 0) g->poisoned = true;
@@ -244,6 +244,12 @@ int ffm_group_train_batch_async(ffm_group *g, int32_t n_rows, const int32_t *row
   while (g->n_staged > keep)
     if ((rc = group_train_one_staged(g, nullptr))) return rc;
   return FFM_OK;
+}
+
+int ffm_group_train_batch_async(ffm_group *g, int32_t n_rows, const int32_t *row_ptr,
+                                const int32_t *field, const int32_t *feat, const float *val,
+                                const int32_t *label, int32_t zero_copy) {
+  return ffm_group_train_batch_async_weighted(g, n_rows, row_ptr, field, feat, val, label, nullptr, zero_copy);
 }
 
 int ffm_group_train_flush(ffm_group *g, double *loss_sum_out) {
@@ -261,15 +267,15 @@ int ffm_group_train_flush(ffm_group *g, double *loss_sum_out) {
   return FFM_OK;
 }
 
-int ffm_group_train_batch(ffm_group *g, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
-                          const int32_t *feat, const float *val, const int32_t *label,
-                          float *logit_out, double *loss_sum_out) {
+int ffm_group_train_batch_weighted(ffm_group *g, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
+                                   const int32_t *feat, const float *val, const int32_t *label,
+                                   const float *weight, float *logit_out, double *loss_sum_out) {
   if (!g) return fail(FFM_E_INVALID, "null group");
   if (g->n_staged > 0) return fail(FFM_E_INVALID, "pipelined blocks are still waiting: flush first");
   if (g->poisoned) return fail(FFM_E_INVALID, "an earlier block reached only some of the group's engines: destroy the group");
   int rc;
   for (size_t r = 0; r < g->eng.size(); r++)
-    if ((rc = ffm_engine_stage_batch(g->eng[r], n_rows, row_ptr, field, feat, val, label, 0))) {
+    if ((rc = ffm_engine_stage_batch_weighted(g->eng[r], n_rows, row_ptr, field, feat, val, label, weight, 0))) {
       if (r > 0) g->poisoned = true;
       return rc;
     }
@@ -277,6 +283,12 @@ int ffm_group_train_batch(ffm_group *g, int32_t n_rows, const int32_t *row_ptr, 
   g->handed++;
   if ((rc = group_train_one_staged(g, logit_out))) return rc;
   return ffm_group_train_flush(g, loss_sum_out);
+}
+
+int ffm_group_train_batch(ffm_group *g, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
+                          const int32_t *feat, const float *val, const int32_t *label,
+                          float *logit_out, double *loss_sum_out) {
+  return ffm_group_train_batch_weighted(g, n_rows, row_ptr, field, feat, val, label, nullptr, logit_out, loss_sum_out);
 }
 
 int64_t ffm_group_blocks_pulled(ffm_group *g) {

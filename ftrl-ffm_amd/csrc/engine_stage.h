@@ -21,39 +21,67 @@ struct PullJob {
   // array is written here -- entry j of the block is field j mod n_fields -- instead of crossing PCIe
   int *gen_field; unsigned gen_n; int gen_fields;
 };
+// The kernel's text, shared with the weighted variant below.  Macros on purpose: the same text as a
+// `__device__ __forceinline__` function called by both kernels compiles pull_block_kernel to 48 SGPRs and 16
+// VGPRs instead of 22 and 14 (the job struct, passed on by reference, is then loaded whole up front), and an
+// unweighted block's upload has to stay the kernel it was (profiles/sample_weights.md).
+#define FFM_PULL_BLOCK_ARRAYS(job)                                                                          \
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");                                                             \
+  const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;              \
+  _Pragma("unroll")                                                                                         \
+  for (int a = 0; a < 5; a++) {                                                                             \
+    const unsigned n16 = job.bytes[a] >> 4;                                                                 \
+    const int4 *s = reinterpret_cast<const int4 *>(job.src[a]);                                             \
+    int4 *d = reinterpret_cast<int4 *>(job.dst[a]);                                                         \
+    /* (one load per lane in flight: two, four and eight measured the same -- 42 GB/s is what a kernel reads over PCIe here) */ \
+    for (unsigned i = tid; i < n16; i += stride) d[i] = s[i];                                               \
+    const unsigned tail = job.bytes[a] & 15u; /* sizes are multiples of 4 */                                \
+    if (tid < (tail >> 2))                                                                                  \
+      reinterpret_cast<int *>(job.dst[a])[(n16 << 2) + tid] = reinterpret_cast<const int *>(job.src[a])[(n16 << 2) + tid]; \
+  }
+#define FFM_PULL_BLOCK_FINISH(job)                                                                          \
+  if (job.gen_n) {                                                                                          \
+    const unsigned n4 = job.gen_n >> 2, F = static_cast<unsigned>(job.gen_fields);                          \
+    for (unsigned i = tid; i < n4; i += stride) {                                                           \
+      const unsigned f0 = (4u * i) % F, f1 = f0 + 1u < F ? f0 + 1u : 0u, f2 = f1 + 1u < F ? f1 + 1u : 0u;   \
+      reinterpret_cast<int4 *>(job.gen_field)[i] = make_int4(static_cast<int>(f0), static_cast<int>(f1), static_cast<int>(f2), \
+                                                             static_cast<int>(f2 + 1u < F ? f2 + 1u : 0u)); \
+    }                                                                                                       \
+    if (tid < (job.gen_n & 3u)) job.gen_field[(n4 << 2) + tid] = static_cast<int>(((n4 << 2) + tid) % F);   \
+  }                                                                                                         \
+  /* the workgroup that finishes last publishes the block's number to the host */                           \
+  __syncthreads(); /* (every load of this workgroup has returned: its stores were issued after them) */     \
+  if (threadIdx.x == 0) {                                                                                   \
+    __threadfence();                                                                                        \
+    if (atomicAdd(job.ticket, 1u) == gridDim.x - 1) {                                                       \
+      *job.ticket = 0u;                                                                                     \
+      __hip_atomic_store(job.pulled, job.ordinal, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);             \
+    }                                                                                                       \
+  }
 __global__ __launch_bounds__(256) void pull_block_kernel(PullJob job) {
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-  const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
-#pragma unroll
-  for (int a = 0; a < 5; a++) {
-    const unsigned n16 = job.bytes[a] >> 4;
-    const int4 *s = reinterpret_cast<const int4 *>(job.src[a]);
-    int4 *d = reinterpret_cast<int4 *>(job.dst[a]);
-    // (one load per lane in flight: two, four and eight measured the same -- 42 GB/s is what a kernel reads over PCIe here)
-    for (unsigned i = tid; i < n16; i += stride) d[i] = s[i];
-    const unsigned tail = job.bytes[a] & 15u;  // sizes are multiples of 4
-    if (tid < (tail >> 2))
-      reinterpret_cast<int *>(job.dst[a])[(n16 << 2) + tid] = reinterpret_cast<const int *>(job.src[a])[(n16 << 2) + tid];
-  }
-  if (job.gen_n) {
-    const unsigned n4 = job.gen_n >> 2, F = static_cast<unsigned>(job.gen_fields);
-    for (unsigned i = tid; i < n4; i += stride) {
-      const unsigned f0 = (4u * i) % F, f1 = f0 + 1u < F ? f0 + 1u : 0u, f2 = f1 + 1u < F ? f1 + 1u : 0u;
-      reinterpret_cast<int4 *>(job.gen_field)[i] = make_int4(static_cast<int>(f0), static_cast<int>(f1), static_cast<int>(f2),
-                                                             static_cast<int>(f2 + 1u < F ? f2 + 1u : 0u));
-    }
-    if (tid < (job.gen_n & 3u)) job.gen_field[(n4 << 2) + tid] = static_cast<int>(((n4 << 2) + tid) % F);
-  }
-  // the workgroup that finishes last publishes the block's number to the host
-  __syncthreads();  // (every load of this workgroup has returned: its stores were issued after them)
-  if (threadIdx.x == 0) {
-    __threadfence();
-    if (atomicAdd(job.ticket, 1u) == gridDim.x - 1) {
-      *job.ticket = 0u;
-      __hip_atomic_store(job.pulled, job.ordinal, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  FFM_PULL_BLOCK_ARRAYS(job)
+  FFM_PULL_BLOCK_FINISH(job)
 }
+// A block with sample weights: the sixth array, n_rows floats, moves with the other five (whole 16-byte
+// vectors, then the last n_rows % 4 floats as single words) -- a kernel of its own, so that an
+// unweighted block's upload is the launch, and the kernel, it always was.
+struct PullWeightedJob { PullJob block; const char *wsrc; char *wdst; unsigned wbytes; };
+__global__ __launch_bounds__(256) void pull_block_weighted_kernel(PullWeightedJob wjob) {
+  const PullJob &job = wjob.block;
+  FFM_PULL_BLOCK_ARRAYS(job)
+  {
+    const unsigned n16 = wjob.wbytes >> 4;
+    const int4 *s = reinterpret_cast<const int4 *>(wjob.wsrc);
+    int4 *d = reinterpret_cast<int4 *>(wjob.wdst);
+    for (unsigned i = tid; i < n16; i += stride) d[i] = s[i];
+    const unsigned tail = wjob.wbytes & 15u;
+    if (tid < (tail >> 2))
+      reinterpret_cast<int *>(wjob.wdst)[(n16 << 2) + tid] = reinterpret_cast<const int *>(wjob.wsrc)[(n16 << 2) + tid];
+  }
+  FFM_PULL_BLOCK_FINISH(job)
+}
+#undef FFM_PULL_BLOCK_ARRAYS
+#undef FFM_PULL_BLOCK_FINISH
 
 // The mirror image of the upload: the scores of one predicted block go from e->d_out to the caller's
 // page-locked (device-mapped) host memory, 16 bytes per lane -- a lane carries four rows --, the last
@@ -118,6 +146,20 @@ static int slots_init(ffm_engine *e) {
   return FFM_OK;
 }
 
+// The slots' weight arrays (device) and their pinned images: made by the first weighted block.
+static int slot_weights_init(ffm_engine *e) {
+  if (e->slot_weights_ready) return FFM_OK;
+  const size_t R = static_cast<size_t>(e->max_rows);
+  for (auto &sl : e->slots) {
+    if (!sl.pinned_w)
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sl.pinned_w), 4 * R + 16, hipHostMallocPortable | hipHostMallocMapped));
+    if (!sl.weight)
+      if (int rc = e->alloc(&sl.weight, R)) return rc;
+  }
+  e->slot_weights_ready = true;
+  return FFM_OK;
+}
+
 int ffm_engine_pin_host(void *p, size_t bytes) {
   if (!p || !bytes) return fail(FFM_E_INVALID, "null range");
   // portable: one registration serves every GPU of the process (an ffm_group stages the same host
@@ -136,9 +178,11 @@ int ffm_engine_unpin_host(void *p) {
 // argument; the block's ordinal is n_staged_total + 1).  Bookkeeping of the slot is the caller's.
 static int claim_slot(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
                       const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
-                      int32_t zero_copy, int *slot_out, bool *was_used, PullJob *job_out) {
+                      int32_t zero_copy, int *slot_out, bool *was_used, PullJob *job_out,
+                      const float *weight = nullptr, PullWeightedJob *wjob_out = nullptr) {
   int rc;
   if ((rc = slots_init(e))) return rc;
+  if (weight && n_rows > 0 && (rc = slot_weights_init(e))) return rc;
   ffm_engine::Slot &sl = e->slots[e->slot_next];
   *slot_out = e->slot_next;
   *was_used = sl.used;
@@ -186,6 +230,19 @@ static int claim_slot(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t 
   HIP_TRY(put(feat, 4 * E, sl.feat));
   HIP_TRY(put(val, 4 * E, sl.val));
   HIP_TRY(put(label, 4 * static_cast<size_t>(n_rows), sl.label));
+  if (weight && n_rows > 0) {  // the sixth array: beside the job's five (its image: the slot's pinned_w)
+    const size_t wbytes = 4 * static_cast<size_t>(n_rows);
+    const void *host = weight;
+    if (!zero_copy) {
+      std::memcpy(sl.pinned_w, weight, wbytes);
+      host = sl.pinned_w;
+    }
+    void *mapped = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&mapped, const_cast<void *>(host), 0));
+    wjob_out->wsrc = static_cast<const char *>(mapped);
+    wjob_out->wdst = reinterpret_cast<char *>(sl.weight);
+    wjob_out->wbytes = static_cast<unsigned>(wbytes);
+  }
   job.ordinal = e->n_staged_total + 1;
   job.pulled = e->d_pulled;
   job.ticket = e->d_pull_ticket;
@@ -193,9 +250,9 @@ static int claim_slot(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t 
 }
 
 // Stage one block of host rows: (pinned image ->) HBM -> grouping, all on the prep stream.
-int ffm_engine_stage_batch(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
-                           const int32_t *field, const int32_t *feat, const float *val,
-                           const int32_t *label, int32_t zero_copy) {
+int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                                    const int32_t *field, const int32_t *feat, const float *val,
+                                    const int32_t *label, const float *weight, int32_t zero_copy) {
   int32_t nnz = 0;
   int longest = 1;
   // (LR / FM rows have no fields -- libsvm: src/data/parser.cpp:20 gives every entry field 0 -- so a
@@ -205,6 +262,19 @@ int ffm_engine_stage_batch(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr
   if (rc) return rc;
   const bool has_field = field != nullptr || (e->m.type == FFM_MODEL_FFM && nnz > 0);  // (uploaded or written by the upload kernel)
   if (n_rows > 0 && !label) return fail(FFM_E_INVALID, "training needs labels");
+  if (n_rows == 0) weight = nullptr;
+  if (weight) {  // refused here, on the caller's thread, before anything of the block is queued
+    if ((rc = validate_host_weights(n_rows, weight))) return rc;
+    if (zero_copy) {
+      if ((reinterpret_cast<uintptr_t>(weight) & 15u) != 0) return fail(FFM_E_INVALID, "a zero_copy weight array must be 16-byte aligned");
+      void *mapped = nullptr;
+      if (hipHostGetDevicePointer(&mapped, const_cast<float *>(weight), 0) != hipSuccess || !mapped) {
+        (void)hipGetLastError();
+        return fail(FFM_E_INVALID, "a zero_copy weight array must be page-locked, device-mapped host memory (ffm_engine_pin_host)");
+      }
+      if ((reinterpret_cast<uintptr_t>(mapped) & 15u) != 0) return fail(FFM_E_INVALID, "a zero_copy weight array must be 16-byte aligned");
+    }
+  }
   if ((rc = eval_launch_pending(e))) return rc;
   if (e->n_staged >= ffm_engine::kSlots - 1) return fail(FFM_E_CAPACITY, "three staged blocks are already waiting");
   if (e->has_pending) return fail(FFM_E_INVALID, "stage between train_forward and train_update");
@@ -215,8 +285,9 @@ int ffm_engine_stage_batch(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   int this_slot = 0;
   bool slot_was_used = false;
-  PullJob job{};
-  if ((rc = claim_slot(e, n_rows, nnz, row_ptr, field, feat, val, label, zero_copy, &this_slot, &slot_was_used, &job)))
+  PullWeightedJob job{};
+  if ((rc = claim_slot(e, n_rows, nnz, row_ptr, field, feat, val, label, zero_copy, &this_slot, &slot_was_used, &job.block,
+                       weight, &job)))
     return rc;
   ffm_engine::Slot &sl = e->slots[this_slot];
   // its grouping, behind its own upload on the prep stream: planned here, submitted with the upload
@@ -237,7 +308,8 @@ int ffm_engine_stage_batch(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr
       // (long steps: the upload too waits for the running block's row kernel to end -- beside the update
       // launches it costs nothing, beside the row kernel, which is bound by the bytes it moves, it does)
       if (e->pull_after_row && plan.ws >= 0) HIP_TRY(hipStreamWaitEvent(e->copy, e->prep_after_row ? e->ev_row_done[plan.ws] : e->ev_set_free[plan.ws], 0));
-      hipLaunchKernelGGL(pull_block_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job);
+      if (job.wbytes) hipLaunchKernelGGL(pull_block_weighted_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job);
+      else hipLaunchKernelGGL(pull_block_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job.block);
       HIP_TRY(hipEventRecord(s2.ev_copied, e->copy));
       if (e->copy != e->prep) HIP_TRY(hipStreamWaitEvent(e->prep, s2.ev_copied, 0));  // the grouping reads the slot
       return prepare_submit(e, plan, timed);
@@ -256,10 +328,16 @@ int ffm_engine_stage_batch(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr
   sl.nnz = nnz;
   sl.row_cap = longest;
   sl.has_field = has_field;
+  sl.has_weight = weight != nullptr;
   sl.seq = ++e->n_staged_total;
   e->slot_next = (e->slot_next + 1) % ffm_engine::kSlots;
   e->staged[e->n_staged++] = this_slot;
   return FFM_OK;
+}
+int ffm_engine_stage_batch(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                           const int32_t *field, const int32_t *feat, const float *val,
+                           const int32_t *label, int32_t zero_copy) {
+  return ffm_engine_stage_batch_weighted(e, n_rows, row_ptr, field, feat, val, label, nullptr, zero_copy);
 }
 
 // How many of the blocks staged so far have been uploaded (their host arrays are free again).
@@ -295,8 +373,8 @@ int ffm_engine_train_forward_staged(ffm_engine *e, float *partial_logit) {
   const Rows staged_rows{sl.n_rows, sl.nnz, sl.row_ptr, sl.has_field ? sl.field : nullptr, sl.feat, sl.val, nullptr};
   if (!(e->n_prepared > 0 && same_block(e->prepared_rows[0], staged_rows)))
     HIP_TRY(hipStreamWaitEvent(e->stream, sl.ev_copied, 0));
-  int rc = ffm_engine_train_forward_device(e, sl.n_rows, sl.nnz, sl.row_ptr, sl.has_field ? sl.field : nullptr,
-                                           sl.feat, sl.val, sl.label, partial_logit);
+  int rc = train_forward_core(e, sl.n_rows, sl.nnz, sl.row_ptr, sl.has_field ? sl.field : nullptr,
+                              sl.feat, sl.val, sl.label, sl.has_weight ? sl.weight : nullptr, partial_logit);
   if (rc) return rc;
   for (int i = 1; i < e->n_staged; i++) e->staged[i - 1] = e->staged[i];
   e->n_staged--;
@@ -323,32 +401,33 @@ static int train_one_staged(ffm_engine *e) {
   return FFM_OK;
 }
 
+// zero_copy == 0: train what the previous call staged; the block staged just now keeps uploading and
+// grouping beside it (and beside the caller's preparation of the next one).  zero_copy != 0: block t+2
+// is staged: train block t (bench.py's schedule; the grouping of t+2 then has its window beside
+// block t and until block t+1 ends)
+int ffm_engine_train_batch_async_weighted(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                                          const int32_t *field, const int32_t *feat, const float *val,
+                                          const int32_t *label, const float *weight, int32_t zero_copy) {
+  if (e && e->m.n_shards > 1)
+    return fail(FFM_E_INVALID, "sharded engines train with stage_batch + train_forward_staged + all-reduce + train_update");
+  int rc = ffm_engine_stage_batch_weighted(e, n_rows, row_ptr, field, feat, val, label, weight, zero_copy ? 1 : 0);
+  if (rc) return rc;
+  const int keep = zero_copy ? 2 : 1;
+  while (e->n_staged > keep)
+    if ((rc = train_one_staged(e))) return rc;
+  return FFM_OK;
+}
+
 int ffm_engine_train_batch_async(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
                                  const int32_t *field, const int32_t *feat, const float *val,
                                  const int32_t *label) {
-  if (e && e->m.n_shards > 1)
-    return fail(FFM_E_INVALID, "sharded engines train with stage_batch + train_forward_staged + all-reduce + train_update");
-  int rc = ffm_engine_stage_batch(e, n_rows, row_ptr, field, feat, val, label, 0);
-  if (rc) return rc;
-  // train what the previous call staged; the block staged just now keeps uploading and grouping
-  // beside it (and beside the caller's preparation of the next one)
-  while (e->n_staged > 1)
-    if ((rc = train_one_staged(e))) return rc;
-  return FFM_OK;
+  return ffm_engine_train_batch_async_weighted(e, n_rows, row_ptr, field, feat, val, label, nullptr, 0);
 }
 
 int ffm_engine_train_batch_async_pinned(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
                                         const int32_t *field, const int32_t *feat, const float *val,
                                         const int32_t *label) {
-  if (e && e->m.n_shards > 1)
-    return fail(FFM_E_INVALID, "sharded engines train with stage_batch + train_forward_staged + all-reduce + train_update");
-  int rc = ffm_engine_stage_batch(e, n_rows, row_ptr, field, feat, val, label, 1);
-  if (rc) return rc;
-  // block t+2 is staged: train block t (bench.py's schedule; the grouping of t+2 then has its
-  // window beside block t and until block t+1 ends)
-  while (e->n_staged > 2)
-    if ((rc = train_one_staged(e))) return rc;
-  return FFM_OK;
+  return ffm_engine_train_batch_async_weighted(e, n_rows, row_ptr, field, feat, val, label, nullptr, 1);
 }
 
 // The predict launch of the block ffm_engine_predict_batch_async uploaded one call ago,

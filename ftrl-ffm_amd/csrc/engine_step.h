@@ -52,7 +52,10 @@ static bool launch_predict_waves(ffm_engine *e, const Rows &rows, int row_cap, f
 #undef PRED_LAUNCH
 }
 
-static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float *out, int output_prob, int own_tg = 0) {
+// weight: the block's sample weights (device) or null; only the launches that produce tmp_grad
+// themselves (own_tg) take them -- otherwise tmp_grad_weighted_kernel does, after the logits are whole.
+static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float *out, int output_prob, int own_tg = 0,
+                              const float *weight = nullptr) {
   const int row_cap = e->staged_row_cap > 0 ? e->staged_row_cap : e->max_row_nnz;
   e->staged_row_cap = 0;
   if (rows.n_rows == 0) return;
@@ -65,7 +68,8 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float
     // one wave per row, lane = factor (kernels_fm.h)
     if (train) e->singles_in_row = own_tg != 0;
     const int grid = cdiv(rows.n_rows, kFmRowsPerBlock);
-    if (train) LAUNCH(e, kid, fm_row_wave_kernel<true>, grid, 64 * kFmRowsPerBlock, 0, e->m, rows, e->sc[e->cur], row_cap, out, output_prob, own_tg);
+    if (train && own_tg && weight) LAUNCH(e, kid, (fm_row_wave_kernel<true, const float *>), grid, 64 * kFmRowsPerBlock, 0, e->m, rows, e->sc[e->cur], row_cap, out, output_prob, own_tg, weight);
+    else if (train) LAUNCH(e, kid, fm_row_wave_kernel<true>, grid, 64 * kFmRowsPerBlock, 0, e->m, rows, e->sc[e->cur], row_cap, out, output_prob, own_tg);
     else LAUNCH(e, kid, fm_row_wave_kernel<false>, grid, 64 * kFmRowsPerBlock, 0, e->m, rows, e->sc[e->cur], row_cap, out, output_prob, 0);
   } else if (e->m.type == FFM_MODEL_FM) {
     if (train) e->singles_in_row = false;
@@ -107,11 +111,14 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float
       if (park > 0) shmem_park = base + 16 * static_cast<size_t>(park);
     }
     if (train && vec4) {
-      if (own_tg)
+      if (own_tg && weight)
+        LAUNCH(e, kid, (ffm_row_kernel<true, true, true, const float *>), rows.n_rows, e->row_threads, shmem_park, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, park, weight);
+      else if (own_tg)
         LAUNCH(e, kid, (ffm_row_kernel<true, true, true>), rows.n_rows, e->row_threads, shmem_park, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, park);
       else  // a shard: the logit is whole only after the all-reduce
         LAUNCH(e, kid, (ffm_row_kernel<true, true, false>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, 0, 0, 0);
     }
+    else if (train && own_tg && weight) LAUNCH(e, kid, (ffm_row_kernel<true, false, true, const float *>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, 0, weight);
     else if (train) LAUNCH(e, kid, (ffm_row_kernel<true, false>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, 0);
     else if (launch_predict_waves(e, rows, row_cap, out, output_prob)) {
       // rows that may be longer than a wave stages (kernels_predict.h): the workgroup-per-row kernel
@@ -236,10 +243,11 @@ int ffm_engine_prepare_device(ffm_engine *e, int32_t n_rows, int32_t nnz, const 
   return prepare_submit(e, pl, true);
 }
 
-int ffm_engine_train_forward_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
-                                    const int32_t *row_ptr, const int32_t *field,
-                                    const int32_t *feat, const float *val, const int32_t *label,
-                                    float *partial_logit) {
+// weight: the block's sample weights (device, [n_rows]) or null; remembered with the pending block
+static int train_forward_core(ffm_engine *e, int32_t n_rows, int32_t nnz,
+                              const int32_t *row_ptr, const int32_t *field,
+                              const int32_t *feat, const float *val, const int32_t *label,
+                              const float *weight, float *partial_logit) {
   ScopedTimer tm_fwd("train:forward");
   int rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val);
   if (rc) return rc;
@@ -247,6 +255,7 @@ int ffm_engine_train_forward_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   Rows rows{n_rows, nnz, row_ptr, field, feat, val, label};
   e->pending = rows;
+  e->pending_weight = n_rows > 0 ? weight : nullptr;
   e->has_pending = true;
   // only train_batch_device has the whole logit in its row kernel (one shard, FFM / LR)
   e->own_tg_cur = e->whole_step && e->m.n_shards == 1 &&
@@ -276,12 +285,25 @@ int ffm_engine_train_forward_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
     if (rc) return rc;
   }
   e->set_used[e->cur] = true;
-  launch_row_kernel(e, rows, true, e->own_tg_cur ? e->own_logit_out : nullptr, 0, e->own_tg_cur ? 1 : 0);
+  launch_row_kernel(e, rows, true, e->own_tg_cur ? e->own_logit_out : nullptr, 0, e->own_tg_cur ? 1 : 0, e->pending_weight);
   if (e->prep_after_row) HIP_TRY(hipEventRecord(e->ev_row_done[e->cur], e->stream));
   if (partial_logit && n_rows > 0)
     HIP_TRY(hipMemcpyAsync(partial_logit, e->sc[e->cur].logit, sizeof(float) * n_rows, hipMemcpyDeviceToDevice, e->stream));
   HIP_TRY(hipGetLastError());
   return FFM_OK;
+}
+
+int ffm_engine_train_forward_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
+                                    const int32_t *row_ptr, const int32_t *field,
+                                    const int32_t *feat, const float *val, const int32_t *label,
+                                    float *partial_logit) {
+  return train_forward_core(e, n_rows, nnz, row_ptr, field, feat, val, label, nullptr, partial_logit);
+}
+int ffm_engine_train_forward_device_weighted(ffm_engine *e, int32_t n_rows, int32_t nnz,
+                                             const int32_t *row_ptr, const int32_t *field,
+                                             const int32_t *feat, const float *val, const int32_t *label,
+                                             const float *weight, float *partial_logit) {
+  return train_forward_core(e, n_rows, nnz, row_ptr, field, feat, val, label, weight, partial_logit);
 }
 
 int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *logit_out,
@@ -296,8 +318,13 @@ int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *log
   const bool own_tg = e->own_tg_cur && !logit;
   // progressive validation: the block's whole pre-update logits into the train channel (when it is on)
   launch_metric(e, FFM_METRIC_TRAIN, rows.n_rows, lg, 0, rows.label);
-  if (rows.n_rows > 0 && !own_tg)
-    LAUNCH(e, K_TMP_GRAD, tmp_grad_kernel, cdiv(rows.n_rows, 256), 256, 0, rows.n_rows, lg, rows.label, e->sc[e->cur].tg, e->sc[e->cur].loss, logit_out);
+  if (rows.n_rows > 0 && !own_tg) {
+    if (e->pending_weight)
+      LAUNCH(e, K_TMP_GRAD, tmp_grad_weighted_kernel, cdiv(rows.n_rows, 256), 256, 0, rows.n_rows, lg, rows.label, e->pending_weight, e->sc[e->cur].tg, e->sc[e->cur].loss, logit_out);
+    else
+      LAUNCH(e, K_TMP_GRAD, tmp_grad_kernel, cdiv(rows.n_rows, 256), 256, 0, rows.n_rows, lg, rows.label, e->sc[e->cur].tg, e->sc[e->cur].loss, logit_out);
+  }
+  e->pending_weight = nullptr;
   // Everything below runs on the main stream: the update has no long dependent chains (every
   // accumulator is folded by reductions, kernels_fold.h), so nothing needs a queue of its own.
   // FM, whole step: fm_row_wave_kernel has applied the touches of the once-only features itself
@@ -471,17 +498,24 @@ int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *log
   return FFM_OK;
 }
 
+int ffm_engine_train_batch_device_weighted(ffm_engine *e, int32_t n_rows, int32_t nnz,
+                                           const int32_t *row_ptr, const int32_t *field,
+                                           const int32_t *feat, const float *val, const int32_t *label,
+                                           const float *weight, float *logit_out, double *loss_sum_out) {
+  if (e && e->m.n_shards > 1)
+    return fail(FFM_E_INVALID, "sharded engines train with train_forward + all-reduce + train_update");
+  if (e) { e->whole_step = true; e->own_logit_out = logit_out; }
+  int rc = train_forward_core(e, n_rows, nnz, row_ptr, field, feat, val, label, weight, nullptr);
+  if (e) e->whole_step = false;
+  if (rc) return rc;
+  return ffm_engine_train_update_device(e, nullptr, logit_out, loss_sum_out);
+}
 int ffm_engine_train_batch_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
                                   const int32_t *row_ptr, const int32_t *field,
                                   const int32_t *feat, const float *val, const int32_t *label,
                                   float *logit_out, double *loss_sum_out) {
-  if (e && e->m.n_shards > 1)
-    return fail(FFM_E_INVALID, "sharded engines train with train_forward + all-reduce + train_update");
-  if (e) { e->whole_step = true; e->own_logit_out = logit_out; }
-  int rc = ffm_engine_train_forward_device(e, n_rows, nnz, row_ptr, field, feat, val, label, nullptr);
-  if (e) e->whole_step = false;
-  if (rc) return rc;
-  return ffm_engine_train_update_device(e, nullptr, logit_out, loss_sum_out);
+  return ffm_engine_train_batch_device_weighted(e, n_rows, nnz, row_ptr, field, feat, val, label, nullptr, logit_out,
+                                                loss_sum_out);
 }
 
 int ffm_engine_predict_batch_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
@@ -553,13 +587,30 @@ static int validate_host_block(ffm_engine *e, int32_t n_rows, const int32_t *row
   return FFM_OK;
 }
 
+// Sample weights handed over in host memory: finite and >= 0, checked on the caller's thread before
+// anything of the block is queued (the device entry points look at weights no more than at val).
+static int validate_host_weights(int32_t n_rows, const float *weight) {
+  for (int r = 0; r < n_rows; r++)
+    if (!(weight[r] >= 0.0f) || std::isinf(weight[r]))
+      return fail(FFM_E_INVALID, "sample weight of row " + std::to_string(r) + " is " +
+                                     (std::isnan(weight[r]) ? "NaN" : std::isinf(weight[r]) ? "infinite" : "negative") +
+                                     ": weights must be finite and >= 0");
+  return FFM_OK;
+}
+
 static int stage_block(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
-                       const int32_t *feat, const float *val, const int32_t *label, int32_t *nnz_out) {
+                       const int32_t *feat, const float *val, const int32_t *label, int32_t *nnz_out,
+                       const float *weight = nullptr) {
   int32_t nnz = 0;
   int longest = 1;
   if (e && e->m.type != FFM_MODEL_FFM) field = nullptr;  // (LR / FM: no fields to upload)
   int rc = validate_host_block(e, n_rows, row_ptr, field, feat, val, &nnz, &longest);
   if (rc) return rc;
+  if (weight) {
+    if ((rc = validate_host_weights(n_rows, weight))) return rc;
+    // (allocated by the first weighted block: an engine that never sees weights holds nothing for them)
+    if (!e->d_weight && (rc = e->alloc(&e->d_weight, static_cast<size_t>(e->max_rows)))) return rc;
+  }
   e->staged_row_cap = longest;
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   HIP_TRY(hipMemcpyAsync(e->d_row_ptr, row_ptr, sizeof(int32_t) * (n_rows + 1), hipMemcpyHostToDevice, e->stream));
@@ -570,25 +621,33 @@ static int stage_block(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, co
   }
   if (label && n_rows > 0)
     HIP_TRY(hipMemcpyAsync(e->d_label, label, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, e->stream));
+  if (weight && n_rows > 0)
+    HIP_TRY(hipMemcpyAsync(e->d_weight, weight, sizeof(float) * n_rows, hipMemcpyHostToDevice, e->stream));
   *nnz_out = nnz;
   return FFM_OK;
 }
 
-int ffm_engine_train_batch(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
-                           const int32_t *field, const int32_t *feat, const float *val,
-                           const int32_t *label, float *logit_out, double *loss_sum_out) {
+int ffm_engine_train_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                                    const int32_t *field, const int32_t *feat, const float *val,
+                                    const int32_t *label, const float *weight, float *logit_out,
+                                    double *loss_sum_out) {
   int32_t nnz = 0;
-  int rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &nnz);
+  int rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &nnz, weight);
   if (rc) return rc;
   if (n_rows > 0 && !label) return fail(FFM_E_INVALID, "training needs labels");
-  rc = ffm_engine_train_batch_device(e, n_rows, nnz, e->d_row_ptr, (field && e->m.type == FFM_MODEL_FFM) ? e->d_field : nullptr,
-                                     e->d_feat, e->d_val, e->d_label, e->d_out, e->d_loss_sum);
+  rc = ffm_engine_train_batch_device_weighted(e, n_rows, nnz, e->d_row_ptr, (field && e->m.type == FFM_MODEL_FFM) ? e->d_field : nullptr,
+                                              e->d_feat, e->d_val, e->d_label, weight ? e->d_weight : nullptr, e->d_out, e->d_loss_sum);
   if (rc) return rc;
   if (logit_out && n_rows > 0)
     HIP_TRY(hipMemcpyAsync(logit_out, e->d_out, sizeof(float) * n_rows, hipMemcpyDeviceToHost, e->stream));
   if (loss_sum_out)
     HIP_TRY(hipMemcpyAsync(loss_sum_out, e->d_loss_sum, sizeof(double), hipMemcpyDeviceToHost, e->stream));
   return check_device_errors(e);
+}
+int ffm_engine_train_batch(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                           const int32_t *field, const int32_t *feat, const float *val,
+                           const int32_t *label, float *logit_out, double *loss_sum_out) {
+  return ffm_engine_train_batch_weighted(e, n_rows, row_ptr, field, feat, val, label, nullptr, logit_out, loss_sum_out);
 }
 
 int ffm_engine_predict_batch(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,

@@ -49,11 +49,15 @@ constexpr int kFmParkStep = kFmPark < kFmChunk ? kFmPark : kFmChunk;  // parked 
 #ifndef FFM_FM_WAVES
 #define FFM_FM_WAVES 8
 #endif
-template <bool TRAIN>
+// W...: nothing, or `const float *` -- per-row sample weights: tmp_grad and the row's loss term scaled
+// by weight[r].  The extra argument exists only in that variant: the unweighted ones are what they were.
+template <bool TRAIN, typename... W>
 __global__ __launch_bounds__(64 * kFmRowsPerBlock) __attribute__((amdgpu_waves_per_eu(TRAIN ? FFM_FM_WAVES : 8, 8)))
 void fm_row_wave_kernel(ModelDev m, Rows rows, Scratch s,
                                                                            int max_row_nnz, float *out,
-                                                                           int output_prob, int own_tg) {
+                                                                           int output_prob, int own_tg, W... weight) {
+  constexpr bool WGT = sizeof...(W) > 0;
+  static_assert(!WGT || TRAIN, "weights are a training argument");
   __shared__ uint64_t s_tab[32];  // expf's table (sigmoid_ref_tab)
   if (threadIdx.x < 32) s_tab[threadIdx.x] = kExpTab[threadIdx.x];
   __syncthreads();
@@ -204,10 +208,14 @@ void fm_row_wave_kernel(ModelDev m, Rows rows, Scratch s,
 
   // ---- tmp_grad = sigmoid(logit) - y (fm.cpp:27), the row's logloss (ftrl_offline.cpp:80)
   const int y = rows.label[r];
-  const float tg = sigmoid_ref_tab(result, s_tab) - static_cast<float>(y);
+  float wr = 1.0f;
+  if constexpr (WGT) wr = row_weight(r, weight...);
+  // (weighted: one fp32 multiply after the subtraction; the loss term in double)
+  const float tg = WGT ? (sigmoid_ref_tab(result, s_tab) - static_cast<float>(y)) * wr
+                       : sigmoid_ref_tab(result, s_tab) - static_cast<float>(y);
   if (lane == 0) {
     s.tg[r] = tg;
-    s.loss[r] = logloss_ref(y, result);
+    s.loss[r] = WGT ? static_cast<double>(wr) * logloss_ref(y, result) : logloss_ref(y, result);
     if (out) out[r] = result;
   }
 

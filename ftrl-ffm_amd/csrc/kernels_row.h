@@ -218,19 +218,30 @@ __device__ __forceinline__ float wave_add_terms_in_order(const float *terms, int
 // !TRAIN: logit from the stored weights; out = logit or sigmoid(logit); per-row loss if labelled.
 // VEC4: n_factors is a multiple of 4, so every slot is a whole number of 16-byte vectors.
 // ------------------------------------------------------------------------------------------
+__device__ __forceinline__ float row_weight(int r, const float *weight) { return weight[r]; }
 #ifdef FFM_ROW_WAVES
 #define FFM_ROW_OCC __attribute__((amdgpu_waves_per_eu(FFM_ROW_WAVES, FFM_ROW_WAVES)))
 #else
-#define FFM_ROW_OCC
+// The weighted variant is held to the six rows per SIMD of its twin: left alone it takes 81 VGPRs, one
+// more than six waves allow, and its launch is 30 us longer at the headline shape; held to 80 it spills
+// six VGPRs to 12 bytes of scratch and costs nothing measurable (profiles/sample_weights.md).  A
+// minimum of 0 emits no attribute: the unweighted instantiations carry none, as before.
+#define FFM_ROW_OCC __attribute__((amdgpu_waves_per_eu(sizeof...(W) > 0 ? 6 : 0)))
 #endif
 // WHOLE: the kernel has the whole logit (one shard): it also produces tmp_grad / loss and may
 // apply the once-only features' update (own_tg, refreshed == 3).  A shard's instantiation leaves all
 // of that out -- and the registers it costs: more rows in flight per SIMD.
-template <bool TRAIN, bool VEC4, bool WHOLE = TRAIN>
+// W...: nothing, or `const float *` -- per-row sample weights (include/ffm_engine.h "Sample weights"):
+// tmp_grad and the row's loss term are scaled by weight[r].  A compile-time variant whose extra
+// argument exists only there, so that the unweighted instantiations are what they always were.
+template <bool TRAIN, bool VEC4, bool WHOLE = TRAIN, typename... W>
 __global__ __launch_bounds__(kRowMaxThreads) FFM_ROW_OCC void ffm_row_kernel(ModelDev m, Rows rows, Scratch s,
                                                               int max_row_nnz, float *out,
                                                               int output_prob, int refreshed,
-                                                              int own_tg_arg, int row0, int park_vecs) {
+                                                              int own_tg_arg, int row0, int park_vecs,
+                                                              W... weight) {
+  constexpr bool WGT = sizeof...(W) > 0;
+  static_assert(!WGT || (TRAIN && WHOLE), "weights go to the kernel that produces tmp_grad");
   const int own_tg = WHOLE ? own_tg_arg : 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int s_nv, s_ns;
@@ -561,11 +572,20 @@ __global__ __launch_bounds__(kRowMaxThreads) FFM_ROW_OCC void ffm_row_kernel(Mod
         // the whole logit is here (one shard): tmp_grad = sigmoid(logit) - y (ffm.cpp:44) and the
         // row's logloss (ftrl_offline.cpp:80) without a pass of their own
         const int y = rows.label[r];
-        const float tg = sigmoid_ref_tab(result, s_tab) - static_cast<float>(y);
-        s.tg[r] = tg;
-        s.loss[r] = logloss_ref(y, result);
-        if (out) out[r] = result;
-        s_tg = tg;
+        if constexpr (WGT) {  // one fp32 multiply after the subtraction; the loss term in double
+          const float wr = row_weight(r, weight...);
+          const float tg = (sigmoid_ref_tab(result, s_tab) - static_cast<float>(y)) * wr;
+          s.tg[r] = tg;
+          s.loss[r] = static_cast<double>(wr) * logloss_ref(y, result);
+          if (out) out[r] = result;
+          s_tg = tg;
+        } else {
+          const float tg = sigmoid_ref_tab(result, s_tab) - static_cast<float>(y);
+          s.tg[r] = tg;
+          s.loss[r] = logloss_ref(y, result);
+          if (out) out[r] = result;
+          s_tg = tg;
+        }
       }
     } else {
       out[r] = output_prob ? sigmoid_ref(result) : result;
@@ -825,6 +845,19 @@ __global__ void tmp_grad_kernel(int n_rows, const float *logit, const int *label
   const int y = label[r];
   tg[r] = sigmoid_ref(lg) - static_cast<float>(y);
   loss[r] = logloss_ref(y, lg);
+  if (logit_out) logit_out[r] = lg;
+}
+// The same with sample weights: tmp_grad = (sigmoid(logit) - y) * weight, loss = (double)weight * loss.
+__global__ void tmp_grad_weighted_kernel(int n_rows, const float *logit, const int *label, const float *weight,
+                                         float *tg, double *loss, float *logit_out) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rows) return;
+  const float lg = logit[r];
+  const int y = label[r];
+  const float wr = weight[r];
+  const float g = sigmoid_ref(lg) - static_cast<float>(y);
+  tg[r] = g * wr;
+  loss[r] = static_cast<double>(wr) * logloss_ref(y, lg);
   if (logit_out) logit_out[r] = lg;
 }
 

@@ -141,6 +141,18 @@ ABI = [
     ("ffm_group_metrics_enable", ctypes.c_int, [_vp, ctypes.c_int32]),
     ("ffm_group_metrics_read", ctypes.c_int,
      [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Metrics)]),
+    # sample weights: one float32 per row, after `label` (include/ffm_engine.h "Sample weights")
+    ("ffm_engine_train_batch_weighted", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [_f32p, _f32p, _f64p]),
+    ("ffm_engine_train_batch_device_weighted", ctypes.c_int,
+     [_vp, ctypes.c_int32, ctypes.c_int32] + _DCSR + [_vp, _vp, _vp]),
+    ("ffm_engine_train_forward_device_weighted", ctypes.c_int,
+     [_vp, ctypes.c_int32, ctypes.c_int32] + _DCSR + [_vp, _vp]),
+    ("ffm_engine_stage_batch_weighted", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [_vp, ctypes.c_int32]),
+    ("ffm_engine_train_batch_async_weighted", ctypes.c_int,
+     [_vp, ctypes.c_int32] + _CSR + [_vp, ctypes.c_int32]),
+    ("ffm_group_train_batch_weighted", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [_f32p, _f32p, _f64p]),
+    ("ffm_group_train_batch_async_weighted", ctypes.c_int,
+     [_vp, ctypes.c_int32] + _CSR + [_vp, ctypes.c_int32]),
 ]
 
 _lib = None
@@ -233,6 +245,14 @@ def _f(a):
 
 def _i(a):
     return None if a is None else a.ctypes.data_as(_i32p)
+
+
+def _w(weight, n_rows):
+    """A block's sample weights as the address the *_weighted entry points take: a contiguous float32
+    array of at least n_rows elements (the caller keeps it alive; a zero_copy one page-locked)."""
+    if weight.dtype != np.float32 or weight.ndim != 1 or weight.size < n_rows or not weight.flags.c_contiguous:
+        raise ValueError("weight: a contiguous float32 array of at least n_rows elements")
+    return weight.ctypes.data
 
 
 STATE_KEYS = ("bias3", "lin_w", "lin_n", "lin_z", "vec_w", "vec_n", "vec_z")
@@ -391,27 +411,45 @@ class Engine:
             pass
         return args
 
-    def train_batch(self, c):
-        """One block with the engine's batch semantics.  Returns (logits, loss_sum)."""
+    def train_batch(self, c, weight=None):
+        """One block with the engine's batch semantics.  Returns (logits, loss_sum).
+        weight: one float32 per row (include/ffm_engine.h "Sample weights"); the loss sum is then
+        sum(weight * loss).  None: the unweighted call."""
         out = np.zeros(max(c.n_rows, 1), np.float32)
         loss = ctypes.c_double(0.0)
-        self._check(self.lib.ffm_engine_train_batch(self.h, *self._csr(c), _f(out),
-                                                    ctypes.byref(loss)))
+        if weight is None:
+            self._check(self.lib.ffm_engine_train_batch(self.h, *self._csr(c), _f(out),
+                                                        ctypes.byref(loss)))
+        else:
+            _w(weight, c.n_rows)
+            self._check(self.lib.ffm_engine_train_batch_weighted(self.h, *self._csr(c), _f(weight), _f(out),
+                                                                 ctypes.byref(loss)))
         return out[:c.n_rows], float(loss.value)
 
-    def train_batch_async(self, c):
+    def train_batch_async(self, c, weight=None):
         """Pipelined: stages and groups this block, trains the one passed by the previous call."""
-        self._check(self.lib.ffm_engine_train_batch_async(self.h, *self._csr(c)))
+        if weight is None:
+            self._check(self.lib.ffm_engine_train_batch_async(self.h, *self._csr(c)))
+        else:
+            self._check(self.lib.ffm_engine_train_batch_async_weighted(self.h, *self._csr(c), _w(weight, c.n_rows), 0))
 
-    def train_batch_async_pinned(self, c):
+    def train_batch_async_pinned(self, c, weight=None):
         """The same for a block in page-locked memory (pin_block): no host copy, three blocks in
-        flight; the block stays untouched until blocks_pulled() has reached its ordinal."""
-        self._check(self.lib.ffm_engine_train_batch_async_pinned(self.h, *self._csr(c)))
+        flight; the block (and its weight array, page-locked as well) stays untouched until
+        blocks_pulled() has reached its ordinal."""
+        if weight is None:
+            self._check(self.lib.ffm_engine_train_batch_async_pinned(self.h, *self._csr(c)))
+        else:
+            self._check(self.lib.ffm_engine_train_batch_async_weighted(self.h, *self._csr(c), _w(weight, c.n_rows), 1))
 
-    def stage_batch(self, c, zero_copy=False):
+    def stage_batch(self, c, zero_copy=False, weight=None):
         """Host block -> (pinned slot ->) HBM + grouping on the side stream (returns at once).
         zero_copy: the block's arrays are page-locked (pin_block) and stay untouched until trained."""
-        self._check(self.lib.ffm_engine_stage_batch(self.h, *self._csr(c), int(zero_copy)))
+        if weight is None:
+            self._check(self.lib.ffm_engine_stage_batch(self.h, *self._csr(c), int(zero_copy)))
+        else:
+            self._check(self.lib.ffm_engine_stage_batch_weighted(self.h, *self._csr(c), _w(weight, c.n_rows),
+                                                                 int(zero_copy)))
 
     def blocks_pulled(self):
         """How many staged blocks have been uploaded so far (their host arrays may be reused)."""
@@ -494,17 +532,27 @@ class Engine:
 
     # ---- blocks already in HBM (raw device addresses as ints) ----
     def train_batch_device(self, n_rows, nnz, row_ptr, field, feat, val, label, logit_out=None,
-                           loss_sum_out=None):
-        self._check(self.lib.ffm_engine_train_batch_device(self.h, n_rows, nnz, row_ptr, field, feat,
-                                                           val, label, logit_out, loss_sum_out))
+                           loss_sum_out=None, weight=None):
+        """weight: device address of n_rows floats, or None."""
+        if weight is None:
+            self._check(self.lib.ffm_engine_train_batch_device(self.h, n_rows, nnz, row_ptr, field, feat,
+                                                               val, label, logit_out, loss_sum_out))
+        else:
+            self._check(self.lib.ffm_engine_train_batch_device_weighted(self.h, n_rows, nnz, row_ptr, field, feat,
+                                                                        val, label, weight, logit_out, loss_sum_out))
 
     def prepare_device(self, n_rows, nnz, row_ptr, field, feat, val):
         """Look-ahead: group the next block on a side stream (see include/ffm_engine.h)."""
         self._check(self.lib.ffm_engine_prepare_device(self.h, n_rows, nnz, row_ptr, field, feat, val))
 
-    def train_forward_device(self, n_rows, nnz, row_ptr, field, feat, val, label, partial_logit):
-        self._check(self.lib.ffm_engine_train_forward_device(self.h, n_rows, nnz, row_ptr, field,
-                                                             feat, val, label, partial_logit))
+    def train_forward_device(self, n_rows, nnz, row_ptr, field, feat, val, label, partial_logit, weight=None):
+        """weight: device address of n_rows floats (valid until train_update_device has run), or None."""
+        if weight is None:
+            self._check(self.lib.ffm_engine_train_forward_device(self.h, n_rows, nnz, row_ptr, field,
+                                                                 feat, val, label, partial_logit))
+        else:
+            self._check(self.lib.ffm_engine_train_forward_device_weighted(self.h, n_rows, nnz, row_ptr, field,
+                                                                          feat, val, label, weight, partial_logit))
 
     def train_update_device(self, logit, logit_out=None, loss_sum_out=None):
         self._check(self.lib.ffm_engine_train_update_device(self.h, logit, logit_out, loss_sum_out))
@@ -636,14 +684,23 @@ class Group:
     def _csr(self, c):
         return self.engines[0]._csr(c)
 
-    def train_batch(self, c):
+    def train_batch(self, c, weight=None):
         out = np.zeros(max(c.n_rows, 1), np.float32)
         loss = ctypes.c_double(0.0)
-        self._check(self.lib.ffm_group_train_batch(self.h, *self._csr(c), _f(out), ctypes.byref(loss)))
+        if weight is None:
+            self._check(self.lib.ffm_group_train_batch(self.h, *self._csr(c), _f(out), ctypes.byref(loss)))
+        else:
+            _w(weight, c.n_rows)
+            self._check(self.lib.ffm_group_train_batch_weighted(self.h, *self._csr(c), _f(weight), _f(out),
+                                                                ctypes.byref(loss)))
         return out[:c.n_rows], float(loss.value)
 
-    def train_batch_async(self, c, zero_copy=False):
-        self._check(self.lib.ffm_group_train_batch_async(self.h, *self._csr(c), int(zero_copy)))
+    def train_batch_async(self, c, zero_copy=False, weight=None):
+        if weight is None:
+            self._check(self.lib.ffm_group_train_batch_async(self.h, *self._csr(c), int(zero_copy)))
+        else:
+            self._check(self.lib.ffm_group_train_batch_async_weighted(self.h, *self._csr(c), _w(weight, c.n_rows),
+                                                                      int(zero_copy)))
 
     def train_flush(self):
         loss = ctypes.c_double(0.0)

@@ -54,6 +54,13 @@ const std::string_view cmd_help =
     "              Prints `scored N rows time: Ts`.  With --n_gpus > 1 the blocks are predicted one by one\n"
     "              (the synchronous group call), on one GPU they stream through the pipelined prediction\n"
     "--predict_output <prob|logit>: what is written\tdefault:prob\n"
+    "--pos_weight <P> / --neg_weight <N>: weight of every positive / negative training row: finite, >= 0.  The\n"
+    "              row's gradient is scaled by it (the correction for down-sampled negatives)\tdefault:1\n"
+    "--weight_data <path>: one decimal weight per line, as many lines as --train_data has rows; a row's weight is\n"
+    "              the float product of its line and its class weight; the file is checked in full before a model exists, for\n"
+    "              which --train_data is read once more to count its rows.  With any of the three flags the `train loss`\n"
+    "              line is sum(w * loss) / sum(w); eval loss, AUC lines and predictions stay unweighted.  Weights are\n"
+    "              not saved with the model or the checkpoint: a run resumed with --resume_from needs the same flags\n"
     "--learn <bool>: keep initial latent weights until their first gradient and use g2*g2 at\n"
     "                ffm.cpp:118, so FM/FFM factors train (NOT the reference's results)\tdefault:false\n";
 
@@ -119,6 +126,16 @@ void config_options::parse_option(int argc, char *argv[]) {
       if (v != "auc" && v != "none") throw std::invalid_argument("--metrics takes auc or none");
       metrics = v;
     }
+    else if (k == "--pos_weight" || k == "--neg_weight") {
+      float w = -1.0f;
+      size_t used = 0;
+      try { w = std::stof(v, &used); } catch (const std::exception &) { used = 0; }
+      if (used != v.size() || used == 0 || !(w >= 0.0f) || w > 3.4028234e38f)
+        throw std::invalid_argument(k + " takes a finite value >= 0, got `" + v + "`");
+      (k == "--pos_weight" ? pos_weight : neg_weight) = w;
+      weights_given = true;
+    }
+    else if (k == "--weight_data") { weight_path = v; weights_given = true; }
     else if (k == "--predict_data") predict_path = v;
     else if (k == "--predict_out") predict_out = v;
     else if (k == "--predict_output") {

@@ -32,6 +32,10 @@ struct config_options {
   std::string metrics = "none";  // --metrics auc: one AUC line after every loss line (accumulated on the device)
   std::string predict_path, predict_out;  // --predict_data / --predict_out: score a file after training, one line per row
   bool predict_prob = true;               // --predict_output prob | logit
+  // --pos_weight / --neg_weight / --weight_data: per-row training weights (sample_weights.h)
+  float pos_weight = 1.0f, neg_weight = 1.0f;
+  std::string weight_path;
+  bool weights_given = false;  // one of the three was passed: training blocks carry a weight array
 
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };

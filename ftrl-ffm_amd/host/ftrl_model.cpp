@@ -194,6 +194,8 @@ void FtrlModel::for_each_fitting(const CsrBlock &blk, Fn fn) {
     part_.feat.assign(blk.feat.begin() + b, blk.feat.begin() + e);
     part_.val.assign(blk.val.begin() + b, blk.val.begin() + e);
     part_.label.assign(blk.label.begin() + r0, blk.label.begin() + r1);
+    if (blk.weight.empty()) part_.weight.clear();
+    else part_.weight.assign(blk.weight.begin() + r0, blk.weight.begin() + r1);
     fn(part_, r0);
     r0 = r1;
   }
@@ -203,14 +205,15 @@ double FtrlModel::train_block(const CsrBlock &blk, float *logit_out) {
   double total = 0.0;
   for_each_fitting(blk, [&](const CsrBlock &b, int r0) {
     double loss_sum = 0.0;
+    const float *w = b.weight.empty() ? nullptr : b.weight.data();  // (null: the unweighted call)
     if (grp_)
-      check(ffm_group_train_batch(grp_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(),
-                                  b.val.data(), b.label.data(), logit_out ? logit_out + r0 : nullptr, &loss_sum),
+      check(ffm_group_train_batch_weighted(grp_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(),
+                                           b.val.data(), b.label.data(), w, logit_out ? logit_out + r0 : nullptr, &loss_sum),
             "ffm_group_train_batch"), handed_over_++;  // (a group stages every block: its ordinal counts)
     else
-      check(ffm_engine_train_batch(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(),
-                                   b.val.data(), b.label.data(), logit_out ? logit_out + r0 : nullptr,
-                                   &loss_sum),
+      check(ffm_engine_train_batch_weighted(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(),
+                                            b.val.data(), b.label.data(), w, logit_out ? logit_out + r0 : nullptr,
+                                            &loss_sum),
             "ffm_engine_train_batch");
     total += loss_sum;
   });
@@ -219,19 +222,20 @@ double FtrlModel::train_block(const CsrBlock &blk, float *logit_out) {
 
 void FtrlModel::train_block_async(const CsrBlock &blk) {
   for_each_fitting(blk, [&](const CsrBlock &b, int) {
+    const float *w = b.weight.empty() ? nullptr : b.weight.data();  // (null: the unweighted call)
     if (grp_)
-      check(ffm_group_train_batch_async(grp_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(),
-                                        b.val.data(), b.label.data(), 0),
+      check(ffm_group_train_batch_async_weighted(grp_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(),
+                                                 b.val.data(), b.label.data(), w, 0),
             "ffm_group_train_batch_async");
     else
-      check(ffm_engine_train_batch_async(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(),
-                                         b.feat.data(), b.val.data(), b.label.data()),
+      check(ffm_engine_train_batch_async_weighted(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(),
+                                                  b.feat.data(), b.val.data(), b.label.data(), w, 0),
             "ffm_engine_train_batch_async");
     handed_over_++;
   });
 }
 
-bool FtrlModel::pin_block(CsrBlock &blk) {
+bool FtrlModel::pin_block(CsrBlock &blk, bool with_weights) {
   blk.row_ptr.reserve(static_cast<size_t>(max_rows_) + 1);
   blk.label.reserve(static_cast<size_t>(max_rows_));
   blk.field.reserve(static_cast<size_t>(max_nnz_));
@@ -246,12 +250,20 @@ bool FtrlModel::pin_block(CsrBlock &blk) {
       for (int j = 0; j < i; j++) ffm_engine_unpin_host(ptr[j]);
       return false;
     }
+  if (with_weights) {
+    blk.weight.reserve(static_cast<size_t>(max_rows_));
+    if (ffm_engine_pin_host(blk.weight.data(), pages(blk.weight.capacity())) != FFM_OK) {
+      for (void *p : ptr) ffm_engine_unpin_host(p);
+      return false;
+    }
+  }
   return true;
 }
 
 void FtrlModel::unpin_block(CsrBlock &blk) {
   void *ptr[5] = {blk.row_ptr.data(), blk.label.data(), blk.field.data(), blk.feat.data(), blk.val.data()};
   for (void *p : ptr) ffm_engine_unpin_host(p);
+  if (blk.weight.capacity() > 0) ffm_engine_unpin_host(blk.weight.data());  // (pinned with the block: pin_block)
 }
 
 long long FtrlModel::train_block_pinned(const CsrBlock &blk) {
@@ -262,13 +274,14 @@ long long FtrlModel::train_block_pinned(const CsrBlock &blk) {
     train_block_async(blk);
     return handed_over_;
   }
+  const float *w = blk.weight.empty() ? nullptr : blk.weight.data();  // (null: the unweighted call)
   if (grp_)
-    check(ffm_group_train_batch_async(grp_, n, blk.row_ptr.data(), blk.field.data(), blk.feat.data(),
-                                      blk.val.data(), blk.label.data(), 1),
+    check(ffm_group_train_batch_async_weighted(grp_, n, blk.row_ptr.data(), blk.field.data(), blk.feat.data(),
+                                               blk.val.data(), blk.label.data(), w, 1),
           "ffm_group_train_batch_async");
   else
-    check(ffm_engine_train_batch_async_pinned(eng_, n, blk.row_ptr.data(), blk.field.data(), blk.feat.data(),
-                                              blk.val.data(), blk.label.data()),
+    check(ffm_engine_train_batch_async_weighted(eng_, n, blk.row_ptr.data(), blk.field.data(), blk.feat.data(),
+                                                blk.val.data(), blk.label.data(), w, 1),
           "ffm_engine_train_batch_async_pinned");
   return ++handed_over_;
 }

@@ -84,6 +84,9 @@ class FtrlModel {
   virtual void remove_out_range(feat_vec &feats);
 
   // Block entry points used by FtrlOffline / FtrlOnline.  Return sum of loss(y, logit).
+  // A training block whose `weight` array is not empty (one float per row; include/ffm_engine.h "Sample
+  // weights") goes through the *_weighted entry points: its gradients are scaled row by row and the
+  // sums returned are sum(weight * loss).  Where a block is split into several calls, so are its weights.
   double train_block(const CsrBlock &blk, float *logit_out = nullptr);
   double predict_block(const CsrBlock &blk, bool output_prob, float *out = nullptr);
   // Pipelined training for callers that need only the loss (the trainers): queue blocks, then
@@ -96,7 +99,8 @@ class FtrlModel {
   // path); train_block_pinned() hands such a block over -- it must then stay untouched until
   // blocks_pulled() has reached the number it returns (blocks handed over so far).  A block that
   // does not fit one engine call goes through the copying path instead.
-  bool pin_block(CsrBlock &blk);
+  // with_weights: the block's weight array is sized and page-locked too (a ring of weighted blocks)
+  bool pin_block(CsrBlock &blk, bool with_weights = false);
   void unpin_block(CsrBlock &blk);
   long long train_block_pinned(const CsrBlock &blk);
   long long blocks_pulled();

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "cmd_option.h"
+#include "sample_weights.h"
 #include "trainer.h"
 
 int main(int argc, char *argv[]) {
@@ -44,11 +45,15 @@ int main(int argc, char *argv[]) {
                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
       }
     };
+    // --pos_weight / --neg_weight / --weight_data: read and checked in full before a model exists
+    ftrl::SampleWeights weights = ftrl::load_sample_weights(opt);
     if (opt.online) {
       ftrl::FtrlOnline task(opt);
+      if (weights.on) task.set_sample_weights(std::move(weights));
       run(task);
     } else {
       ftrl::FtrlOffline task(opt);
+      if (weights.on) task.set_sample_weights(std::move(weights));
       run(task);
     }
   } catch (const std::exception &e) {

@@ -6,6 +6,7 @@
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <mutex>
 #include <numeric>
 #include <random>
@@ -51,6 +52,20 @@ FtrlOffline::FtrlOffline(const config_options &opt)
 
 FtrlOffline::~FtrlOffline() = default;
 
+static void check_weight_rows(const SampleWeights &w, size_t rows) {
+  if (!w.file.empty() && w.file.size() != rows)
+    throw std::runtime_error("sample weights: " + std::to_string(w.file.size()) + " weights for " + std::to_string(rows) +
+                             " training rows");
+}
+void FtrlOffline::set_sample_weights(SampleWeights w) {
+  check_weight_rows(w, train_csr_.n_rows());
+  weights_ = std::move(w);
+}
+// mean of a weighted epoch: sum(w * loss) / sum(w); no weight at all has no mean
+static double weighted_mean(double loss_sum, double weight_sum) {
+  return weight_sum > 0.0 ? loss_sum / weight_sum : std::numeric_limits<double>::quiet_NaN();
+}
+
 // ---------------- the ring of page-locked blocks ----------------
 
 BlockRing::~BlockRing() {
@@ -62,7 +77,7 @@ bool BlockRing::ready() {
   ring_.resize(kRing);
   seq_.assign(kRing, 0);
   for (int i = 0; i < kRing; i++)
-    if (!model_->pin_block(ring_[i])) {  // no page-locked memory to be had: the copying path
+    if (!model_->pin_block(ring_[i], with_weights_)) {  // no page-locked memory to be had: the copying path
       for (int j = 0; j < i; j++) model_->unpin_block(ring_[j]);
       ring_.clear();
       return false;
@@ -85,9 +100,10 @@ double FtrlOffline::csr_epoch(const CsrData &d, bool train) {
     std::iota(indices.begin(), indices.end(), 0);
     std::shuffle(indices.begin(), indices.end(), std::mt19937_64{seed_ + (++epoch_no_)});
   }
-  double total_loss = 0.0;
+  double total_loss = 0.0, weight_sum = 0.0;
+  const bool weighted = train && weights_.on;
   CsrBlock blk;
-  if (!ring_) ring_ = std::make_unique<BlockRing>(model_ptr.get());
+  if (!ring_) ring_ = std::make_unique<BlockRing>(model_ptr.get(), weights_.on);
   const bool ring = ring_->ready();
   size_t pos = 0;
   while (pos < total) {
@@ -100,9 +116,11 @@ double FtrlOffline::csr_epoch(const CsrData &d, bool train) {
     if (ring && rows <= ring_->row_capacity() && nnz <= ring_->nnz_capacity()) {
       CsrBlock &rb = ring_->acquire();
       if (train) d.gather(indices.data() + pos, rows, rb, n_threads); else d.slice(pos, pos + rows, rb);
+      if (weighted) weight_sum += weights_.fill(rb, indices.data() + pos, 0);
       ring_->handed_over(train ? model_ptr->train_block_pinned(rb) : model_ptr->predict_block_async(rb, true));
     } else if (train) {
       d.gather(indices.data() + pos, rows, blk, n_threads);
+      if (weighted) weight_sum += weights_.fill(blk, indices.data() + pos, 0);
       model_ptr->train_block_async(blk);
     } else {
       d.slice(pos, pos + rows, blk);
@@ -112,6 +130,7 @@ double FtrlOffline::csr_epoch(const CsrData &d, bool train) {
     pos += rows;
   }
   total_loss = train ? model_ptr->train_flush() : model_ptr->eval_flush();
+  if (weighted) return weighted_mean(total_loss, weight_sum);
   return total_loss / static_cast<double>(total);
 }
 
@@ -174,16 +193,26 @@ FtrlOnline::FtrlOnline(const config_options &opt)
   }
 }
 
+void FtrlOnline::set_sample_weights(SampleWeights w) { weights_ = std::move(w); }
+
 // One pass over the training file in FILE ORDER (the reference's deterministic order at one
 // thread): worker threads parse chunks of <= 20 000 lines ahead (parse time is inside
 // the timed region, as in the reference's online mode), the rows are cut into blocks by the
 // block-size ramp, gathered in page-locked ring entries and handed to the engine, which uploads
 // and groups block t+2 while block t trains.
 void FtrlOnline::run_train_file() {
-  if (!ring_) ring_ = std::make_unique<BlockRing>(model_ptr.get());
+  if (!ring_) ring_ = std::make_unique<BlockRing>(model_ptr.get(), weights_.on);
   const bool ring = ring_->ready();
   CsrBlock blk;
   unsigned long long rows = 0, next_report = 1000000;
+  double weight_sum = 0.0;
+  // (the rows come in file order: row j of a block is row `rows + j` of the file)
+  auto weigh = [&](CsrBlock &b, size_t got) {
+    if (!weights_.on) return;
+    if (!weights_.file.empty() && rows + got > weights_.file.size())
+      throw std::runtime_error("sample weights: the training file has more rows than the weight file has lines");
+    weight_sum += weights_.fill(b, nullptr, static_cast<size_t>(rows));
+  };
   for (;;) {
     const size_t want = static_cast<size_t>(sched_.next_block_rows());
     size_t got;
@@ -191,10 +220,12 @@ void FtrlOnline::run_train_file() {
       CsrBlock &rb = ring_->acquire();
       got = train_stream_->next(std::min(want, ring_->row_capacity()), rb, ring_->nnz_capacity(), true);
       if (got == 0) break;
+      weigh(rb, got);
       ring_->handed_over(model_ptr->train_block_pinned(rb));
     } else {
       got = train_stream_->next(want, blk);
       if (got == 0) break;
+      weigh(blk, got);
       model_ptr->train_block_async(blk);
     }
     sched_.consumed(static_cast<int>(got));
@@ -206,13 +237,16 @@ void FtrlOnline::run_train_file() {
   }
   loss_sum_ = model_ptr->train_flush();
   loss_rows_ = rows;
+  weight_sum_ = weight_sum;
   train_stream_->rewind();
 }
 
 double FtrlOnline::get_loss() {
-  const double r = loss_rows_ ? loss_sum_ / static_cast<double>(loss_rows_) : 0.0;
+  double r = loss_rows_ ? loss_sum_ / static_cast<double>(loss_rows_) : 0.0;
+  if (weights_.on && loss_rows_) r = weighted_mean(loss_sum_, weight_sum_);
   loss_sum_ = 0.0;
   loss_rows_ = 0;
+  weight_sum_ = 0.0;
   return r;
 }
 

@@ -21,6 +21,7 @@
 #include "csr_reader.h"
 #include "csr_stream.h"
 #include "reader.h"
+#include "sample_weights.h"
 
 namespace ftrl {
 
@@ -47,7 +48,8 @@ class BlockScheduler {
 class BlockRing {
  public:
   static constexpr int kRing = 6;
-  explicit BlockRing(FtrlModel *m) : model_(m) {}
+  // with_weights: the entries' weight arrays are page-locked too (training with sample weights)
+  explicit BlockRing(FtrlModel *m, bool with_weights = false) : model_(m), with_weights_(with_weights) {}
   ~BlockRing();
   bool ready();                       // pins the entries on first use; false: no page-locked memory
   CsrBlock &acquire();                // the next entry, free to be refilled
@@ -57,6 +59,7 @@ class BlockRing {
 
  private:
   FtrlModel *model_;
+  bool with_weights_ = false;
   std::vector<CsrBlock> ring_;
   std::vector<long long> seq_;
   int slot_ = 0;
@@ -133,9 +136,15 @@ class FtrlOffline {
     epoch_no_ = resumed_epochs_ = static_cast<int>(p.epochs_done);
   }
 
+  // Per-row training weights (sample_weights.h), to be set before train(): row i of the training file
+  // trains with w.of(i, label) -- the shuffled gather carries every row's weight along -- and the
+  // `train loss` line becomes sum(w * loss) / sum(w) (nan when sum(w) is 0).  Evaluation is unweighted.
+  void set_sample_weights(SampleWeights w);
+
   std::unique_ptr<FtrlModel> model_ptr;
 
  private:
+  SampleWeights weights_;
   int n_epochs, n_threads;
   uint64_t seed_;
   int epoch_no_ = 0;        // training passes so far (the shuffle of pass e is seeded seed + e)
@@ -162,11 +171,17 @@ class FtrlOnline {
   FtrlModel::TrainProgress progress() const { return {sched_.rows_seen(), resumed_epochs_ + passes_}; }  // (as FtrlOffline's)
   void restore(const FtrlModel::TrainProgress &p) { sched_.restore(p.rows_seen); resumed_epochs_ = p.epochs_done; }
 
+  // Per-row training weights (sample_weights.h), to be set before train(): as FtrlOffline's, by the
+  // row's number in the training file (file order).
+  void set_sample_weights(SampleWeights w);
+
   std::shared_ptr<FtrlModel> model_ptr;
   std::unique_ptr<Evaluator> evaluator;  // (ftrl_online.h:31; null without --eval_data)
 
  private:
   void run_train_file();
+  SampleWeights weights_;
+  double weight_sum_ = 0.0;  // sum of the weights of the rows behind loss_sum_
   int n_epochs;
   long long passes_ = 0;          // passes over the training file made by this object
   long long resumed_epochs_ = 0;  // epochs a checkpoint brought along: train() prints its epochs after them

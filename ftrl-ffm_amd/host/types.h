@@ -48,10 +48,12 @@ struct PageAllocator {
 struct CsrBlock {
   std::vector<int32_t, PageAllocator<int32_t>> row_ptr{0}, field, feat, label;
   std::vector<float, PageAllocator<float>> val;
+  // sample weights, one per row (include/ffm_engine.h "Sample weights"), or empty: an unweighted block
+  std::vector<float, PageAllocator<float>> weight;
   int32_t n_rows() const { return static_cast<int32_t>(row_ptr.size()) - 1; }
   void clear() {
     row_ptr.assign(1, 0);
-    field.clear(); feat.clear(); label.clear(); val.clear();
+    field.clear(); feat.clear(); label.clear(); val.clear(); weight.clear();
   }
   void push(const Sample &s) {
     for (const auto &[f, i, v] : s.x) { field.push_back(f); feat.push_back(i); val.push_back(v); }

@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 /* 3: + ffm_engine_predict_batch_async, ffm_group_* (additions only: a caller built against 2 runs
- * unchanged) */
+ * unchanged).  The *_weighted entry points ("Sample weights" below) are additions as well. */
 #define FFM_ENGINE_ABI_VERSION 4
 
 /* ModelType, reference src/include/utils/types.h:21-25 */
@@ -404,6 +404,64 @@ int64_t ffm_group_blocks_pulled(ffm_group *g); /* blocks every engine has upload
 int ffm_group_predict_batch(ffm_group *g, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
                             const int32_t *feat, const float *val, const int32_t *label,
                             int32_t output_prob, float *out, double *loss_sum_out);
+
+/* ---- Sample weights: one float32 per training row ------------------------------------------------
+ * The reference has none (ffm.cpp:38-49 takes a Sample{x, y}); click logs are trained with the
+ * negatives down-sampled (python/generate_data.py has the option), and the correction is an importance
+ * weight per row or per class.  Every training entry point has a twin that takes
+ * `const float *weight` -- weight[n_rows], placed after `label` -- and is otherwise its twin.
+ *   gradient   tmp_grad[r] = (sigmoid(logit[r]) - (float)y[r]) * weight[r]: ONE fp32 multiply, after the
+ *              subtraction, never contracted.  Nothing else of the update changes: every (n, z) step of
+ *              the row takes this scalar where it took the unweighted one.  FFM_FLAG_LEARN composes:
+ *              its gradient is scaled the same way.
+ *   forward    weights do not touch it: the lazy refresh, the logit and logit_out are what they are
+ *              without weights.  A row of weight 0 still refreshes what it touches and still returns
+ *              its logit; it only contributes zero gradients.
+ *   loss       the row's term is (double)weight[r] * loss(y, logit), summed in the same fixed order;
+ *              the entry points (and ffm_engine_train_flush / ffm_group_train_flush) return this
+ *              weighted sum.  Normalising it -- by sum(weight), say -- is the caller's.
+ *   NULL       weight == NULL is exactly the unweighted call: no extra launch, no allocation, no byte
+ *              moved.  An array of all 1.0f gives bit-identical state, logits and loss sum to NULL
+ *              (both products are exact).  Weighted and unweighted blocks may be mixed in one pipeline.
+ *   checks     the entry points that take HOST arrays (zero_copy included) check the weights on the
+ *              caller's thread before anything of the block is queued: a NaN, infinite or negative
+ *              weight is FFM_E_INVALID with a message, and the model is untouched.  A zero_copy weight
+ *              array must be page-locked and 16-byte aligned like the other five, and stays untouched
+ *              until ffm_engine_blocks_pulled() has reached the block.  The _device entry points do
+ *              not inspect weights (they do not inspect val either).
+ *   metrics    FFM_METRIC_TRAIN keeps counting rows, not weights.  Prediction and evaluation take no
+ *              weights.  Weights are not model state: nothing of them is kept after the block's update.
+ * ffm_engine_train_forward_device_weighted: the weights (device) are remembered with the pending
+ * block and used by ffm_engine_train_update_device, whether the logits are its own or summed outside;
+ * they must stay valid until that update has run.  ffm_engine_stage_batch_weighted: the weights travel
+ * with the block (a sixth array of the upload, kept in the staging slot until the block's update has
+ * run, as its labels are); ffm_engine_train_staged / train_forward_staged pick them up.
+ * ffm_engine_train_batch_async_weighted covers both pipelines: zero_copy == 0 is
+ * ffm_engine_train_batch_async, zero_copy != 0 ffm_engine_train_batch_async_pinned. */
+int ffm_engine_train_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                                    const int32_t *field, const int32_t *feat, const float *val,
+                                    const int32_t *label, const float *weight, float *logit_out,
+                                    double *loss_sum_out);
+int ffm_engine_train_batch_device_weighted(ffm_engine *e, int32_t n_rows, int32_t nnz,
+                                           const int32_t *row_ptr, const int32_t *field,
+                                           const int32_t *feat, const float *val, const int32_t *label,
+                                           const float *weight, float *logit_out, double *loss_sum_out);
+int ffm_engine_train_forward_device_weighted(ffm_engine *e, int32_t n_rows, int32_t nnz,
+                                             const int32_t *row_ptr, const int32_t *field,
+                                             const int32_t *feat, const float *val, const int32_t *label,
+                                             const float *weight, float *partial_logit);
+int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                                    const int32_t *field, const int32_t *feat, const float *val,
+                                    const int32_t *label, const float *weight, int32_t zero_copy);
+int ffm_engine_train_batch_async_weighted(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                                          const int32_t *field, const int32_t *feat, const float *val,
+                                          const int32_t *label, const float *weight, int32_t zero_copy);
+int ffm_group_train_batch_weighted(ffm_group *g, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
+                                   const int32_t *feat, const float *val, const int32_t *label,
+                                   const float *weight, float *logit_out, double *loss_sum_out);
+int ffm_group_train_batch_async_weighted(ffm_group *g, int32_t n_rows, const int32_t *row_ptr,
+                                         const int32_t *field, const int32_t *feat, const float *val,
+                                         const int32_t *label, const float *weight, int32_t zero_copy);
 
 /* Measurement utility: overwrite ALL accumulators with a reproducible "warm" state drawn on the
  * device -- n ~ U[n_lo, n_hi), z ~ N(0, z_stddev) for bias, linear and latent -- so that
