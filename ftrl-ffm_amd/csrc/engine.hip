@@ -738,6 +738,8 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   m.huge_min = std::min(m.huge_min, m.giant_min - 1);  // (the lists: big <= huge_min < huge < giant_min <= giant)
   m.super_min = kSuperMin;
   if (const char *sv = std::getenv("FFM_SUPER_MIN")) m.super_min = std::max(kGiantMin, std::atoi(sv));
+  m.few_stage = 1;
+  if (const char *sv = std::getenv("FFM_FEW_STAGE")) m.few_stage = sv[0] != '0';
   m.rec_slots = m.n_fields;
   e->n_records = cfg->n_feats;
   // field-pair partition: this shard's ranges, and (with per-field id ranges) compact storage

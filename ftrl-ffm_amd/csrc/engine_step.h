@@ -389,6 +389,9 @@ int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *log
     const bool wide = nf == 1 && !side_launches && split == 0 && rows.nnz < e->wide_max_nnz;
     const int wpb = wide ? kWideWaves : tile_waves(nf), scale = wpb / kUpdWaves, threads = 64 * wpb;
     const size_t lds = tile_lds_bytes(nf, wpb);
+    // (the few-occurrence launch of the three side by side has no tiles: only its staging of the touches' rows,
+    // and that only where a block of this engine can be staged -- else it launches without dynamic LDS)
+    const size_t few_lds = few_stage_possible(e->m) ? few_stage_bytes(wpb, e->m.n_fields) : 0;
     // (... and to the block: a workgroup that finds its range's lists empty still costs a dispatch and
     // a few dependent loads -- 4100 of them were a fifth of a 4096 x 8 block's update)
     auto sized = [&](int grid, int per_wg, int least) { return std::max(least, std::min(grid, cdiv(rows.nnz, per_wg))); };
@@ -405,7 +408,7 @@ int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *log
         HIP_TRY(hipEventRecord(e->ev_fork2, e->stream));                                                      \
         if (ns + nw + lb > 0) {                                                                               \
           HIP_TRY(hipStreamWaitEvent(e->aux3, e->ev_fork2, 0));                                               \
-          LAUNCH_ON(e, e->aux3, K_LATENT_UPDATE_FEW, (ffm_update_all_kernel<NF, UPD_FEW | UPD_REST>), ns + nw + lb, threads, 0, e->m, rows, e->sc[e->cur], \
+          LAUNCH_ON(e, e->aux3, K_LATENT_UPDATE_FEW, (ffm_update_all_kernel<NF, UPD_FEW | UPD_REST>), ns + nw + lb, threads, few_lds, e->m, rows, e->sc[e->cur], \
                  0, 0, 0, ns, single ? 1 : 0, nw, lb, loss_sum_out, e->d_loss_part, order);                       \
           HIP_TRY(hipEventRecord(e->ev_join, e->aux3));                                                       \
         }                                                                                                     \

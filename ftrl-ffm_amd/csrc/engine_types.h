@@ -63,6 +63,8 @@ struct ModelDev {
   int range_len;              // occurrences per range of such a feature (a multiple of kSeg): FFM kRange,
                               //     FM kFmRange -- an FM touch is three dependent loads and a dozen instructions,
                               //     its ranges are short so that many waves share one feature
+  int few_stage;              // FFM_FEW_STAGE: 1 = on regular blocks the few-occurrence range stages its touches' rows
+                              //     in LDS once per feature (kernels_update.h); 0 = the row table, batch by batch
 };
 
 enum { LAT_N = 0, LAT_Z = 1, LAT_W = 2 };

@@ -684,6 +684,9 @@ constexpr size_t tile_lds_bytes(int nf, int waves) {
   return static_cast<size_t>(waves) * (kTileT * kTileRow * sizeof(float) + kTileNR * kTileT * 4 * nf * sizeof(float4));
 }
 constexpr size_t tile_lds_bytes(int nf) { return tile_lds_bytes(nf, tile_waves(nf)); }
+// (a launch that carries the tile ranges AND the few-occurrence range: a workgroup runs one range, so the few
+// range's staging of its touches' rows -- few_stage_bytes, kernels_update.h -- lives in the tile region)
+static_assert(few_stage_bytes(1, 64) <= tile_lds_bytes(1, 1), "the few-occurrence range's staging fits a wave's tile region");
 // Small blocks (a 4096 x 8 block: ~1000-occurrence giants are 16 super-steps of four tiles) run the
 // launch with EIGHT waves per workgroup: half the super-steps -- 80 -> 70 us per launch; a C5 block
 // that way 438 -> 693 us (profiles/archive/r05_experiments.md).
@@ -751,7 +754,7 @@ __global__ __launch_bounds__(64 * WAVES) FFM_UPD_OCC void ffm_update_all_kernel(
       ffm_tile_items<NF>(m, rows, s, r * WAVES + wv, nt * WAVES, T, R);
     }
   } else if (kind == 2) {
-    if (KINDS & UPD_FEW) ffm_small_body(m, rows, s, few_only, r, ns);
+    if (KINDS & UPD_FEW) ffm_small_body(m, rows, s, few_only, r, ns, few_stage_possible(m) ? reinterpret_cast<int2 *>(lds_dyn) : nullptr);
   }
   if (kind >= 0) return;
   if (KINDS & UPD_REST) {

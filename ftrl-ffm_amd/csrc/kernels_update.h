@@ -17,6 +17,8 @@
 //  * "hot" features: one wave per 64 elements of the record, sixteen touches at a time, their
 //    operands loaded touch-parallel and transposed through LDS (kernels_tile.h).
 #pragma once
+#include <type_traits>
+
 #include "engine_types.h"
 #include "kernels_touch.h"
 #include "kernels_fold.h"
@@ -392,6 +394,46 @@ __global__ __launch_bounds__(kUpdThreads) void ffm_update_generic_kernel(ModelDe
 #define FFM_SMALL_BATCH 4
 #endif
 constexpr int kSmallBatch = FFM_SMALL_BATCH < kSmallMax ? FFM_SMALL_BATCH : kSmallMax;  // touches whose gathers fly together
+// The batch loops are unrolled over WHOLE batches: their last batch indexes the per-touch arrays up to
+// kSmallPad - 1 (10 and 11 at kSmallMax = 10, batches of 4) with only the runtime `j < c` in front of
+// it, so every per-touch array -- registers or LDS -- has kSmallPad entries.
+constexpr int kSmallPad = (kSmallMax + kSmallBatch - 1) / kSmallBatch * kSmallBatch;
+static_assert(kSmallPad % kSmallBatch == 0 && kSmallPad >= kSmallMax && kSmallPad < kSmallMax + kSmallBatch,
+              "the per-touch arrays of the few-occurrence range hold kSmallMax rounded up to whole batches");
+static_assert(kSmallPad <= 64, "lane j of the owning wave fetches touch j");
+// Regular blocks (every row one entry per field, in field order: the row table's entry of (row, field)
+// is the CSR's own entry row * n_fields + field): the partner ids and values of ALL of a feature's
+// touches -- two contiguous runs of n_fields words per touch -- are fetched once per feature, in the
+// trip that fetches the touches' own facts, and parked in the wave's part of the launch's dynamic LDS
+// as {partner id, partner value bits}[touch][field].  A pass then makes ONE dependent trip per batch
+// (the partners' weights) where it made two (row table, then weights).  n_fields <= 64 (s.cmask).
+// A workgroup of the few-occurrence launch now holds: the touches' own facts, 208 B per wave (static),
+// the giant range's CoopLds (static, unused here), and kSmallPad * n_fields * 8 B per wave of staging:
+// 3.7 KB per wave, 15 KB per four-wave workgroup at 39 fields, 24.6 KB at 64.  Four such workgroups
+// per CU (four waves per SIMD) are under 100 KB of the CU's 160 KB, and a workgroup is smaller than
+// one of the hot or giant launches (28.7 KB of tiles at k >= 16) that it shares a CU with.  The one-launch
+// forms run the few range inside the tile region, which is larger (static_assert in kernels_tile.h).
+#ifndef FFM_STAGE_FLY
+#define FFM_STAGE_FLY 7
+#endif
+constexpr int kStageFly = FFM_STAGE_FLY;  // staging steps (64 words each) whose loads are in flight together
+constexpr size_t few_stage_bytes(int waves, int n_fields) {
+  return static_cast<size_t>(waves) * kSmallPad * static_cast<size_t>(n_fields) * sizeof(int2);
+}
+// Can a block of this engine be staged at all?  What the host sizes the few launch's dynamic LDS by and the
+// kernel tests before it looks at the block (ffm_small_body adds: the block is regular, the launch handed the
+// area over).  Each term is one the staged passes lean on:
+//   few_stage            the switch (FFM_FEW_STAGE)
+//   sort_start           blocks of this engine can be regular at all (the caller gave field_start)
+//   n_shards == 1, !own_n  every pair is owned: no ownership test per touch
+//   !field_start         full-length records: record = feature id (m.lat + id * 3 * row_len), slot = partner field
+//   !learn               the learning variant keeps its own flags per touch
+//   record_span > 64     more than ONE pass of 64 vectors: with one pass there is no later pass whose row-table
+//                        trip the staging saves, and its own instructions are a cost (k = 4, few fields)
+__host__ __device__ inline bool few_stage_possible(const ModelDev &m) {
+  return m.few_stage != 0 && m.sort_start != nullptr && m.n_shards == 1 && m.own_n == nullptr &&
+         m.field_start == nullptr && m.h.learn == 0 && m.rec_slots * (m.n_factors >> 2) > 64;
+}
 #ifdef FFM_SMALL_WAVES
 #define FFM_SMALL_OCC __attribute__((amdgpu_waves_per_eu(FFM_SMALL_WAVES, FFM_SMALL_WAVES)))
 #else
@@ -403,13 +445,17 @@ constexpr int kSmallBatch = FFM_SMALL_BATCH < kSmallMax ? FFM_SMALL_BATCH : kSma
 #ifndef FFM_FOLD_REGULAR
 #define FFM_FOLD_REGULAR 1
 #endif
-__device__ __forceinline__ void ffm_small_body(const ModelDev &m, const Rows &rows, const Scratch &s,
-                                               int few_only, unsigned bidx, unsigned gdim) {
-#if FFM_FEW_LDS
-  __shared__ int4 few_facts[kUpdMaxThreads / 64][kSmallMax];  // per wave: {entry, row, own field, own value}
-  __shared__ float few_tg[kUpdMaxThreads / 64][kSmallMax];    // ... and the row's tmp_grad
-  const int wv_in_block = wave_uniform(threadIdx.x >> 6);
-#endif
+// staged: the block is regular and `stage` is the wave's staging area (above); else the row table is read batch
+// by batch.  ONE feature loop, ONE prologue; the passes over the record are two instantiations of one lambda
+// behind one branch per feature, so that the register allocation is the larger of the two paths', not that
+// of both at once: tested as a flag inside the batch loop the few launch took 133-140 VGPRs (three waves)
+// against 115 this way, and two copies of the whole feature loop spilled 25 scalar registers more.
+// The staged passes know what a regular block implies: one shard with every pair owned and full-length
+// records -- record = feature id, slot = partner field, no ownership test.
+// facts / tgs: the wave's LDS records of its feature's touches (FFM_FEW_LDS).
+__device__ __forceinline__ void ffm_small_items(bool staged, const ModelDev &m, const Rows &rows, const Scratch &s,
+                                                int few_only, unsigned bidx, unsigned gdim, bool regular,
+                                                int4 *facts, float *tgs, int2 *stage) {
   const int RL = m.row_len, k = m.n_factors, F = m.n_fields;
   const int RL4 = RL >> 2, k4 = k >> 2;
   const int lane = threadIdx.x & 63;
@@ -420,11 +466,7 @@ __device__ __forceinline__ void ffm_small_body(const ModelDev &m, const Rows &ro
   const int n_small = s.counters[few_only ? CNT_NFEW : CNT_NSMALL];
   const float inv_k4 = 1.0f / static_cast<float>(k4);
   const int span4 = record_span(m, k4);
-#if FFM_FOLD_REGULAR
-  const bool regular = m.sort_start != nullptr && m.n_shards == 1 && m.own_n == nullptr && s.counters[CNT_IRREGULAR] == 0;
-#else
-  const bool regular = false;
-#endif
+  const float inv_F = 1.0f / static_cast<float>(F);
   // (a feature is a chain of dependent loads -- list, descriptor, touches, their entries and rows,
   // row table, partner weights: the list entry is requested two features ahead, the descriptor one)
   auto uniform4 = [](int4 v) { return make_int4(wave_uniform(v.x), wave_uniform(v.y), wave_uniform(v.z), wave_uniform(v.w)); };
@@ -439,7 +481,7 @@ __device__ __forceinline__ void ffm_small_body(const ModelDev &m, const Rows &ro
     const int i = ud.x;
     const int start = ud.y, c = ud.z;
     const int fa = ud.w;
-    float4 *rec4 = reinterpret_cast<float4 *>(lat_row(m, i, fa));
+    float4 *rec4 = reinterpret_cast<float4 *>(staged ? m.lat + static_cast<long long>(i) * 3 * RL : lat_row(m, i, fa));
     // slots that one row touches twice keep the row-order walk (ffm_generic_body, serial_only)
     const unsigned long long cm = s.cmask[start];
     // The feature's (at most kSmallMax) touches, read ONCE for all passes over its record: entry,
@@ -449,29 +491,65 @@ __device__ __forceinline__ void ffm_small_body(const ModelDev &m, const Rows &ro
     // VGPR lanes, 36 bytes per lane into scratch memory -- VERDICT r05.)
 #if FFM_FEW_LDS
     {
-      if (lane < kSmallMax) {
-        int4 f = make_int4(0, 0, 0, 0);
-        float g = 0.0f;
-        if (lane < c) {
-          const int2 pr = s.occ2[start + lane];
-          f = make_int4(pr.x, pr.y, rows.field[pr.x], __float_as_int(rows.val[pr.x]));
-          g = s.tg[pr.y];
+      int2 pr = make_int2(0, 0);
+      if (lane < c) pr = s.occ2[start + lane];
+      int4 f = make_int4(0, 0, 0, 0);
+      float g = 0.0f;
+      if (lane < c) {
+        f = make_int4(pr.x, pr.y, rows.field[pr.x], __float_as_int(rows.val[pr.x]));
+        g = s.tg[pr.y];
+      }
+      if (staged) {
+        // ... and, in the same trip, the touches' rows: lanes run over (touch, field), 64 words of the c runs
+        // of F per step, every step's two loads in flight together.  The row of touch j starts at its entry
+        // minus the feature's field (one entry per field, in field order); a lane takes its touch's entry
+        // from lane j (a per-lane value: a wave-uniform start per touch is ten pairs of scalar registers more
+        // than the launch has).  Staged word j * F + field = step * 64 + lane.  kStageFly steps' loads fly
+        // together -- all of them up to 448 words, every count at up to 44 fields; unrolled over all kSmallMax steps
+        // the prologue, not the passes, set the launch's VGPR count: 136).
+        const int n_stage = c * F;
+#pragma unroll 1
+        for (int i0 = 0; i0 < n_stage; i0 += 64 * kStageFly) {  // (one round unless c * F > 64 * kStageFly)
+          int sf[kStageFly];
+          float sv[kStageFly];
+#pragma unroll
+          for (int it = 0; it < kStageFly; it++) {
+            sf[it] = 0;
+            sv[it] = 0.0f;
+            const int idx = i0 + it * 64 + lane;
+            if (i0 + it * 64 < n_stage) {
+              const int j = static_cast<int>((idx + 0.5f) * inv_F);  // idx / F (exact: idx < 640, F <= 64)
+              const int pe = __shfl(pr.x, j < c ? j : 0);
+              if (idx < n_stage) {
+                const int q = pe - fa + (idx - j * F);  // the row's entry of that field
+                sf[it] = rows.feat[q];
+                sv[it] = rows.val[q];
+              }
+            }
+          }
+#pragma unroll
+          for (int it = 0; it < kStageFly; it++) {
+            const int idx = i0 + it * 64 + lane;
+            if (idx < n_stage) stage[idx] = make_int2(sf[it], __float_as_int(sv[it]));
+          }
         }
-        few_facts[wv_in_block][lane] = f;
-        few_tg[wv_in_block][lane] = g;
+      }
+      if (lane < kSmallPad) {
+        facts[lane] = f;
+        tgs[lane] = g;
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     }
-#define FEW_TP(j) (few_facts[wv_in_block][j].x)
-#define FEW_TR(j) (few_facts[wv_in_block][j].y)
-#define FEW_TFM(j) (few_facts[wv_in_block][j].z)
-#define FEW_TXM(j) (__int_as_float(few_facts[wv_in_block][j].w))
-#define FEW_TTG(j) (few_tg[wv_in_block][j])
+#define FEW_TP(j) (facts[j].x)
+#define FEW_TR(j) (facts[j].y)
+#define FEW_TFM(j) (facts[j].z)
+#define FEW_TXM(j) (__int_as_float(facts[j].w))
+#define FEW_TTG(j) (tgs[j])
 #else
-    int tp[kSmallMax], tr[kSmallMax], tfm[kSmallMax];
-    float txm[kSmallMax], ttg[kSmallMax];
+    int tp[kSmallPad], tr[kSmallPad], tfm[kSmallPad];
+    float txm[kSmallPad], ttg[kSmallPad];
 #pragma unroll
-    for (int j = 0; j < kSmallMax; j++) {
+    for (int j = 0; j < kSmallPad; j++) {
       tp[j] = tr[j] = tfm[j] = 0;
       txm[j] = ttg[j] = 0.0f;
       if (j < c) {
@@ -489,17 +567,19 @@ __device__ __forceinline__ void ffm_small_body(const ModelDev &m, const Rows &ro
 #define FEW_TXM(j) (txm[j])
 #define FEW_TTG(j) (ttg[j])
 #endif
+    auto passes = [&](auto staged_tag) {
+    constexpr bool STAGED = decltype(staged_tag)::value;
     for (int l0 = 0; l0 < span4; l0 += 64) {
       const int l = l0 + lane;  // 16-byte vector of the stored record
       const int lc = l < span4 ? l : 0;
       int sl = static_cast<int>((lc + 0.5f) * inv_k4);  // its slot
       sl += (sl + 1) * k4 <= lc ? 1 : (sl * k4 > lc ? -1 : 0);
-      int fp = l < span4 ? walk_field(m, fa, sl) : -1;  // partner field of this lane's slot
+      int fp = l < span4 ? (STAGED ? sl : walk_field(m, fa, sl)) : -1;  // partner field of this lane's slot
       if (fp >= 0 && ((cm >> fp) & 1ull)) fp = -1;      // serial
       const bool mine = fp >= 0;
       fp = mine ? fp : 0;
       const int kq = lc - sl * k4;  // which 16-byte quarter of the slot
-      const unsigned long long own_bits = owner_bits(m, fp);
+      const unsigned long long own_bits = STAGED ? ~0ull : owner_bits(m, fp);
       float n[4] = {0.0f, 0.0f, 0.0f, 0.0f}, z[4] = {0.0f, 0.0f, 0.0f, 0.0f}, w[4] = {0.0f, 0.0f, 0.0f, 0.0f};
       if (mine) {
         // (the record's (n, z) pass through once per block: the non-temporal hint keeps them from pushing the
@@ -518,6 +598,30 @@ __device__ __forceinline__ void ffm_small_body(const ModelDev &m, const Rows &ro
 #pragma unroll
       for (int j0 = 0; j0 < kSmallMax; j0 += kSmallBatch) {
         if (j0 >= c) break;
+        float4 vp4[kSmallBatch];
+        if constexpr (STAGED) {
+          // the partners' ids and values wait in LDS: the batch's weights are its only trip to memory
+          float xp[kSmallBatch];
+#pragma unroll
+          for (int jj = 0; jj < kSmallBatch; jj++) {
+            const int j = j0 + jj;
+            xp[jj] = 0.0f;
+            vp4[jj] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (j < c && lv) {
+              const int2 pv = stage[j * F + fp];
+              xp[jj] = __int_as_float(pv.y);
+              vp4[jj] = reinterpret_cast<const float4 *>(m.lat + static_cast<long long>(pv.x) * 3 * RL)[LAT_W * RL4 + fa * k4 + kq];
+            }
+          }
+#pragma unroll
+          for (int jj = 0; jj < kSmallBatch; jj++) {
+            const int j = j0 + jj;
+            if (j >= c) continue;
+            const float vp[4] = {vp4[jj].x, vp4[jj].y, vp4[jj].z, vp4[jj].w};
+            a.touch_regular(n, w, lv, q118, FEW_TTG(j), FEW_TXM(j) * xp[jj], vp);
+          }
+          continue;
+        }
         int4 rt[kSmallBatch];
 #pragma unroll
         for (int jj = 0; jj < kSmallBatch; jj++) {
@@ -525,7 +629,6 @@ __device__ __forceinline__ void ffm_small_body(const ModelDev &m, const Rows &ro
           rt[jj] = make_int4(0, 0, -1, 0);  // "no entry of that field in the row"
           if (mine && j < c && owns_bit(own_bits, FEW_TFM(j))) rt[jj] = s.rowtab[static_cast<int64_t>(FEW_TR(j)) * F + fp];
         }
-        float4 vp4[kSmallBatch];
 #pragma unroll
         for (int jj = 0; jj < kSmallBatch; jj++) {
           const int j = j0 + jj;
@@ -552,6 +655,9 @@ __device__ __forceinline__ void ffm_small_body(const ModelDev &m, const Rows &ro
         store_nt(rec4 + LAT_Z * RL4 + lc, make_float4(z[0], z[1], z[2], z[3]));
       }
     }
+    };
+    if (staged) passes(std::true_type{});
+    else passes(std::false_type{});
 #if FFM_FEW_LDS
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the next feature overwrites the records)
 #endif
@@ -561,6 +667,31 @@ __device__ __forceinline__ void ffm_small_body(const ModelDev &m, const Rows &ro
 #undef FEW_TFM
 #undef FEW_TXM
 #undef FEW_TTG
+}
+// stage_all: the launch's dynamic LDS when it holds few_stage_bytes(waves of the workgroup, n_fields) for the
+// staging described above, else null
+__device__ __forceinline__ void ffm_small_body(const ModelDev &m, const Rows &rows, const Scratch &s,
+                                               int few_only, unsigned bidx, unsigned gdim, int2 *stage_all = nullptr) {
+#if FFM_FEW_LDS
+  __shared__ int4 few_facts[kUpdMaxThreads / 64][kSmallPad];  // per wave: {entry, row, own field, own value}
+  __shared__ float few_tg[kUpdMaxThreads / 64][kSmallPad];    // ... and the row's tmp_grad
+  const int wv_in_block = wave_uniform(threadIdx.x >> 6);
+  int4 *facts = few_facts[wv_in_block];
+  float *tgs = few_tg[wv_in_block];
+#else
+  const int wv_in_block = 0;
+  int4 *facts = nullptr;
+  float *tgs = nullptr;
+#endif
+#if FFM_FOLD_REGULAR
+  const bool regular = m.sort_start != nullptr && m.n_shards == 1 && m.own_n == nullptr && s.counters[CNT_IRREGULAR] == 0;
+#else
+  const bool regular = false;
+#endif
+  // staged implies regular (and with it everything few_stage_possible lists)
+  const bool staged = FFM_FEW_LDS && regular && stage_all != nullptr && few_stage_possible(m);
+  int2 *stage = staged ? stage_all + static_cast<size_t>(wv_in_block) * kSmallPad * m.n_fields : nullptr;
+  ffm_small_items(staged, m, rows, s, few_only, bidx, gdim, regular, facts, tgs, stage);
 }
 __global__ __launch_bounds__(kUpdThreads) FFM_SMALL_OCC void ffm_update_small_kernel(ModelDev m, Rows rows,
                                                                        Scratch s, int few_only) {
