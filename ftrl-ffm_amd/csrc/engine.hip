@@ -45,6 +45,7 @@
 #include "kernels_predict.h"
 #include "kernels_sort.h"
 #include "kernels_scan.h"
+#include "kernels_refresh.h"
 #include "kernels_metric.h"
 #include "metrics_host.h"
 
@@ -376,6 +377,9 @@ struct ffm_engine {
   // the AUC channels (include/ffm_engine.h "Metrics"): hist = pos[kMetricBins], neg[kMetricBins], n_nan;
   // allocated when the channel is first turned on
   struct MetricChannel { bool on = false; unsigned long long *hist = nullptr; } metric[2];
+  // ffm_engine_refresh_weights (engine_refresh.h): its six counters and its grid, both made by the first call
+  unsigned long long *d_refresh = nullptr;
+  int refresh_grid = 0;
   std::vector<void *> allocs;
   // split-phase bookkeeping
   Rows pending{};
@@ -1218,6 +1222,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_state.h"
 #include "engine_step.h"
 #include "engine_stage.h"
+#include "engine_refresh.h"
 #include "engine_profile.h"
 #include "engine_metrics.h"
 }  // extern "C"

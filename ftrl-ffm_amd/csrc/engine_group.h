@@ -329,6 +329,27 @@ int ffm_group_predict_batch(ffm_group *g, int32_t n_rows, const int32_t *row_ptr
   return FFM_OK;
 }
 
+// ffm_engine_refresh_weights on every shard.  Blocks the group still holds staged are trained first, as a
+// flush would train them (their losses stay in the flush's sum).  Every stored slot that can be live
+// belongs to exactly one shard, so the group's counters are plain sums.
+int ffm_group_refresh_weights(ffm_group *g, ffm_refresh_stats *out) {
+  if (out) std::memset(out, 0, sizeof(*out));
+  if (!g || g->eng.empty()) return fail(FFM_E_INVALID, "null group");
+  if (g->poisoned) return fail(FFM_E_INVALID, "an earlier block reached only some of the group's engines: destroy the group");
+  int rc;
+  while (g->n_staged > 0)
+    if ((rc = group_train_one_staged(g, nullptr))) return rc;
+  ffm_refresh_stats total{};
+  for (auto *e : g->eng) {
+    ffm_refresh_stats part{};
+    if ((rc = ffm_engine_refresh_weights(e, &part))) return rc;
+    total.lin_live += part.lin_live; total.lin_nonzero += part.lin_nonzero; total.lin_moved += part.lin_moved;
+    total.lat_live += part.lat_live; total.lat_nonzero += part.lat_nonzero; total.lat_moved += part.lat_moved;
+  }
+  if (out) *out = total;
+  return FFM_OK;
+}
+
 // Every rank sees the labels and, after the all-reduce, the whole logits; rank 0's engine keeps the
 // channels (its predict_finish / train_update are the ones that report the loss as well).
 int ffm_group_metrics_enable(ffm_group *g, int32_t channel_mask) {

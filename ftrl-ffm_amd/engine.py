@@ -52,6 +52,15 @@ class Metrics(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RefreshStats(ctypes.Structure):
+    """struct ffm_refresh_stats (include/ffm_engine.h "Refresh")."""
+    _fields_ = [(k, ctypes.c_int64) for k in ("lin_live", "lin_nonzero", "lin_moved",
+                                              "lat_live", "lat_nonzero", "lat_moved")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 METRIC_EVAL, METRIC_TRAIN = 0, 1  # FFM_METRIC_*
 METRIC_BINS = 1 << 20             # FFM_METRIC_BINS
 _METRIC_CHANNELS = {"eval": METRIC_EVAL, "train": METRIC_TRAIN}
@@ -153,6 +162,9 @@ ABI = [
     ("ffm_group_train_batch_weighted", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [_f32p, _f32p, _f64p]),
     ("ffm_group_train_batch_async_weighted", ctypes.c_int,
      [_vp, ctypes.c_int32] + _CSR + [_vp, ctypes.c_int32]),
+    # every stored weight from its accumulators (include/ffm_engine.h "Refresh")
+    ("ffm_engine_refresh_weights", ctypes.c_int, [_vp, ctypes.POINTER(RefreshStats)]),
+    ("ffm_group_refresh_weights", ctypes.c_int, [_vp, ctypes.POINTER(RefreshStats)]),
 ]
 
 _lib = None
@@ -363,6 +375,15 @@ class Engine:
         ids = np.empty(self.n_feats, np.int32)
         self._check(self.lib.ffm_engine_changed_features(self.h, _i(ids), ids.size, ctypes.byref(n)))
         return ids[:n.value].copy()
+
+    def refresh_weights(self):
+        """Sets every stored w to W(n, z) where the accumulators are live, so that prediction and
+        persistence see the model that was learned (ffm_engine_refresh_weights; (n, z) untouched, the
+        training trajectory unchanged).  Returns dict(lin_live, lin_nonzero, lin_moved, lat_live,
+        lat_nonzero, lat_moved)."""
+        st = RefreshStats()
+        self._check(self.lib.ffm_engine_refresh_weights(self.h, ctypes.byref(st)))
+        return st.as_dict()
 
     def _bias3(self):
         b = np.zeros(3, np.float32)
@@ -642,7 +663,7 @@ class Group:
     def __init__(self, devices, model_type="FFM", n_feats=10000, n_fields=8, n_factors=16, w_alpha=1e-4,
                  w_beta=1.0, w_l1=0.1, w_l2=5.0, init_mean=0.0, init_stddev=0.02, seed=42,
                  max_batch_rows=8192, max_batch_nnz=None, skip_init=False, max_row_nnz=0,
-                 field_start=None):
+                 field_start=None, learn=False):
         self.lib = load_library()
         cfg = Config()
         self.lib.ffm_engine_default_config(ctypes.byref(cfg))
@@ -652,7 +673,7 @@ class Group:
         cfg.init_mean, cfg.init_stddev, cfg.seed = init_mean, init_stddev, int(seed)
         cfg.max_batch_rows = int(max_batch_rows)
         cfg.max_batch_nnz = int(max_batch_nnz if max_batch_nnz else max_batch_rows * 64)
-        cfg.flags = FLAG_SKIP_INIT if skip_init else 0
+        cfg.flags = (FLAG_SKIP_INIT if skip_init else 0) | (FLAG_LEARN if learn else 0)
         cfg.max_row_nnz = int(max_row_nnz)
         self._field_start = None
         if field_start is not None:
@@ -729,6 +750,12 @@ class Group:
 
     def metrics_histogram(self, channel):
         return self.engines[0].metrics_histogram(channel)
+
+    def refresh_weights(self):
+        """Engine.refresh_weights on every shard (ffm_group_refresh_weights); the counters summed."""
+        st = RefreshStats()
+        self._check(self.lib.ffm_group_refresh_weights(self.h, ctypes.byref(st)))
+        return st.as_dict()
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:

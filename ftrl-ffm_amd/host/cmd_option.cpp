@@ -62,7 +62,15 @@ const std::string_view cmd_help =
     "              line is sum(w * loss) / sum(w); eval loss, AUC lines and predictions stay unweighted.  Weights are\n"
     "              not saved with the model or the checkpoint: a run resumed with --resume_from needs the same flags\n"
     "--learn <bool>: keep initial latent weights until their first gradient and use g2*g2 at\n"
-    "                ffm.cpp:118, so FM/FFM factors train (NOT the reference's results)\tdefault:false\n";
+    "                ffm.cpp:118, so FM/FFM factors train (NOT the reference's results)\tdefault:false\n"
+    "--refresh_weights <bool>: training refreshes a weight from its accumulators only BEFORE it updates them, so what\n"
+    "              evaluation, --model_path, --checkpoint_path and --predict_data read is one update behind: a feature\n"
+    "              seen in one block only is scored as if never seen.  true = one pass over the model sets every stored\n"
+    "              w = W(n, z) where (n, z) are not both zero bits (under --learn a latent slot whose n is not > 0 keeps\n"
+    "              its w) after each epoch's training and before its evaluation, before the model and the checkpoint are\n"
+    "              written and before --predict_data is scored (also with --resume_from ck --n_epochs 0), and prints\n"
+    "              `epoch N weights: linear L live, Z nonzero, M moved; latent L live, Z nonzero, M moved`.  (n, z) and\n"
+    "              the `train loss` lines do not change by a bit\tdefault:false\n";
 
 static bool assign_bool(std::string arg) {
   std::transform(arg.begin(), arg.end(), arg.begin(), [](unsigned char c) { return std::tolower(c); });
@@ -120,6 +128,7 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--seed") seed = std::stoull(v);
     else if (k == "--device") device = std::stoi(v);
     else if (k == "--learn") learn = assign_bool(v);
+    else if (k == "--refresh_weights") refresh_weights = assign_bool(v);
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
     else if (k == "--field_ranges") field_ranges = v;
     else if (k == "--metrics") {

@@ -36,6 +36,7 @@ struct config_options {
   float pos_weight = 1.0f, neg_weight = 1.0f;
   std::string weight_path;
   bool weights_given = false;  // one of the three was passed: training blocks carry a weight array
+  bool refresh_weights = false;  // --refresh_weights: every stored w = W(n, z) before it is evaluated, saved or scored
 
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };

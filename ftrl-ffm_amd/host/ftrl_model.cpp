@@ -309,6 +309,17 @@ ffm_metrics FtrlModel::read_metrics(int channel, bool reset) {
   return m;
 }
 
+ffm_refresh_stats FtrlModel::refresh_weights() {
+  ffm_refresh_stats st{};
+  if (grp_) check(ffm_group_refresh_weights(grp_, &st), "ffm_group_refresh_weights");
+  else check(ffm_engine_refresh_weights(eng_, &st), "ffm_engine_refresh_weights");
+  pull_linear();
+  vec_w.dense_ready_ = false;
+  vec_w.dense_.clear();
+  vec_w.cache_.clear();
+  return st;
+}
+
 long long FtrlModel::predict_block_async(const CsrBlock &blk, bool pinned, float *scores, bool output_prob, bool *complete) {
   const int n = blk.n_rows();
   bool fits = n <= max_rows_ && blk.row_ptr[n] <= max_nnz_;

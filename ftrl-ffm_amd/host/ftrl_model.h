@@ -134,6 +134,11 @@ class FtrlModel {
   void enable_metrics(bool eval, bool train);
   ffm_metrics read_metrics(int channel, bool reset);
   bool metrics_on(int channel) const { return (metrics_mask_ >> channel) & 1; }
+  // Every stored w from its accumulators (include/ffm_engine.h "Refresh"), one engine or a group alike:
+  // what prediction and the model files read is otherwise one update behind (n, z).  Blocks queued and
+  // not trained yet are trained first (their losses stay in train_flush()'s sum).  The host mirrors
+  // (bias, lin_w, vec_w) are pulled again / dropped, as after load_checkpoint.  Returns the six counts.
+  ffm_refresh_stats refresh_weights();
 
   // Model files in the reference's formats (ffm.cpp:138-200, lr.cpp:26-39); available for every
   // model type here (the reference has none for FM).  save_state/load_state add the FTRL

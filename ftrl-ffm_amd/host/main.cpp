@@ -34,6 +34,10 @@ int main(int argc, char *argv[]) {
     auto run = [&](auto &task) {
       if (!opt.resume_from.empty()) task.restore(task.model_ptr->load_checkpoint(opt.resume_from));
       task.train();
+      // --refresh_weights: every epoch ended with a refresh and nothing has trained since, so the model, the
+      // checkpoint and the scores below are those of refreshed weights; a run that trains nothing (--n_epochs 0
+      // on a resumed model) refreshes what it loaded here
+      if (opt.refresh_weights && (opt.epoch <= 0 || opt.cmd)) ftrl::refresh_and_print(*task.model_ptr, task.progress().epochs_done);
       save(*task.model_ptr);
       if (!opt.checkpoint_path.empty()) task.model_ptr->save_checkpoint(opt.checkpoint_path, 3, task.progress());
       // --predict_data / --predict_out: last, so the scores are those of the model that was written

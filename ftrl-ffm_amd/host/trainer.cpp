@@ -26,6 +26,13 @@ void print_auc_line(FtrlModel &m, int epoch, int channel) {
   std::printf("epoch %d %s auc: %.6lf (+-%.1e)\n", epoch, channel == FFM_METRIC_TRAIN ? "train" : "eval", r.auc, r.auc_slack);
 }
 
+void refresh_and_print(FtrlModel &m, long long epoch) {
+  const ffm_refresh_stats r = m.refresh_weights();
+  std::printf("epoch %lld weights: linear %lld live, %lld nonzero, %lld moved; latent %lld live, %lld nonzero, %lld moved\n", epoch,
+              static_cast<long long>(r.lin_live), static_cast<long long>(r.lin_nonzero), static_cast<long long>(r.lin_moved),
+              static_cast<long long>(r.lat_live), static_cast<long long>(r.lat_nonzero), static_cast<long long>(r.lat_moved));
+}
+
 // ---------------- offline: data in memory, seeded shuffle per epoch ----------------
 
 FtrlOffline::FtrlOffline(const config_options &opt)
@@ -48,6 +55,7 @@ FtrlOffline::FtrlOffline(const config_options &opt)
   }
   metrics_ = opt.metrics == "auc";
   if (metrics_) model_ptr->enable_metrics(true, true);
+  refresh_ = opt.refresh_weights;
 }
 
 FtrlOffline::~FtrlOffline() = default;
@@ -141,6 +149,7 @@ void FtrlOffline::train() {
     const double train_loss = csr_epoch(train_csr_, true);
     std::printf("epoch %d train time: %.4lfs, train loss: %.4lf\n", i, seconds_since(t0), train_loss);
     if (metrics_) print_auc_line(*model_ptr, i, FFM_METRIC_TRAIN);
+    if (refresh_) refresh_and_print(*model_ptr, i);
     if (has_eval_) evaluate(i);
   }
 }
@@ -183,6 +192,7 @@ FtrlOnline::FtrlOnline(const config_options &opt)
       sched_(opt.batch_size, opt.batch_ramp < 0 ? ffm_engine_default_batch_ramp(opt.w_alpha) : opt.batch_ramp) {
   metrics_ = opt.metrics == "auc";
   if (metrics_) model_ptr->enable_metrics(true, true);
+  refresh_ = opt.refresh_weights;
   if (!cmd_) {
     if (!opt.train_path.empty())  // (--n_epochs 0 needs no training file)
       train_stream_ = std::make_unique<CsrStream>(opt.train_path, opt.file_type, opt.thread_num);
@@ -260,6 +270,7 @@ void FtrlOnline::train() {
     const double train_loss = get_loss();
     std::printf("epoch %d train time: %.4lfs, train loss: %.4lf\n", i, seconds_since(t0), train_loss);
     if (metrics_) print_auc_line(*model_ptr, i, FFM_METRIC_TRAIN);
+    if (refresh_) refresh_and_print(*model_ptr, i);
     if (evaluator) evaluate(i);
   }
 }

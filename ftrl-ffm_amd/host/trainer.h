@@ -117,6 +117,10 @@ class Scorer {
 
 // --metrics auc: the line that follows an epoch's loss line ("train" / "eval"); resets the channel.
 void print_auc_line(FtrlModel &m, int epoch, int channel);
+// --refresh_weights true: FtrlModel::refresh_weights() and its line,
+// `epoch N weights: linear L live, Z nonzero, M moved; latent L live, Z nonzero, M moved`.
+// The tasks call it after each epoch's training, before that epoch's evaluation; main() where no epoch ran.
+void refresh_and_print(FtrlModel &m, long long epoch);
 
 class FtrlOffline {
  public:
@@ -151,6 +155,7 @@ class FtrlOffline {
   int resumed_epochs_ = 0;  // epochs a checkpoint brought along: train() prints its epochs after them
   BlockScheduler sched_;
   bool metrics_ = false;    // --metrics auc
+  bool refresh_ = false;    // --refresh_weights
   std::unique_ptr<Reader> train_data_loader, eval_data_loader;  // API parity (data stays empty
                                                                 // unless load_samples() is called)
   CsrData train_csr_, eval_csr_;                                // what train()/evaluate() walk
@@ -187,6 +192,7 @@ class FtrlOnline {
   long long resumed_epochs_ = 0;  // epochs a checkpoint brought along: train() prints its epochs after them
   bool cmd_;
   bool metrics_ = false;          // --metrics auc
+  bool refresh_ = false;          // --refresh_weights
   BlockScheduler sched_;
   std::unique_ptr<CsrStream> train_stream_;  // chunks of <= 20 000 lines parsed by n_threads workers
   std::unique_ptr<BlockRing> ring_;

@@ -40,7 +40,8 @@ extern "C" {
 #endif
 
 /* 3: + ffm_engine_predict_batch_async, ffm_group_* (additions only: a caller built against 2 runs
- * unchanged).  The *_weighted entry points ("Sample weights" below) are additions as well. */
+ * unchanged).  The *_weighted entry points ("Sample weights" below) and ffm_engine_refresh_weights /
+ * ffm_group_refresh_weights ("Refresh" below) are additions as well. */
 #define FFM_ENGINE_ABI_VERSION 4
 
 /* ModelType, reference src/include/utils/types.h:21-25 */
@@ -548,6 +549,42 @@ int ffm_engine_metrics_from_histogram(const uint64_t *pos, const uint64_t *neg, 
 /* A group's labels are seen by every rank; rank 0's engine keeps the channels. */
 int ffm_group_metrics_enable(ffm_group *g, int32_t channel_mask);
 int ffm_group_metrics_read(ffm_group *g, int32_t channel, int32_t reset, ffm_metrics *out);
+
+/* ---- Refresh: every stored weight from its accumulators -----------------------------------------
+ * train() refreshes w = W(n, z) lazily, for what a row touches, BEFORE it updates (n, z), and leaves the
+ * stored w alone afterwards (ffm.cpp:38-49, :72-88); predict() reads the stored w and nothing else
+ * (ffm.cpp:51-55).  So what prediction, evaluation and the model files see is one update behind the
+ * accumulators -- with this engine's block semantics one whole block per feature: a feature that occurred
+ * in exactly one block of a run is scored as if it had never been seen, though its (n, z) hold a real
+ * update.  This call makes one streaming pass over everything the engine STORES -- the bias triple, the
+ * linear arrays, every latent record, by position, so a compact or full-length shard is served like a
+ * whole model (csrc/kernels_refresh.h) -- and sets w = W(n, z) wherever the accumulators are live.
+ * Rule per element (the contract):
+ *   live     (bits(n) | bits(z)) != 0: bit patterns, so -0.0f and NaN are live.
+ *   dead     w is not counted and keeps its bits (create-time draws, padding slots, slots and linear
+ *            entries another shard owns).
+ *   linear, bias   w_new = maybe_zero_weight(n, z) (ftrl_model.h:28-33), the bits the lazy refresh stores.
+ *   latent   the same; under FFM_FLAG_LEARN a slot whose n is not > 0 keeps w_old, as its refresh does.
+ *   counters live = live elements; nonzero = live and !(w_new == 0.0f) (a NaN weight counts, -0.0f does
+ *            not); moved = live and bits(w_new) != bits(w_old).  lin_* cover the linear weights and the
+ *            bias (on the engine that owns it), lat_* the latent elements (0 for LR).
+ * (n, z) are never written.  The next training block recomputes the same w from the same (n, z) for what
+ * it touches, so training after a refresh is bit-identical -- logits, losses, state -- to training without
+ * it; only what prediction and persistence see changes.  The set ffm_engine_changed_features reports is
+ * the same before and after: a live element was already changed, a dead one is not written.  A second
+ * call right after the first moves nothing and stores nothing.
+ *   Synchronous.  Before its kernel it drains as ffm_engine_changed_features does: a deferred evaluation
+ * block is launched (it sees the weights as they were), blocks staged by the pipelined entry points and
+ * not trained yet are trained (their losses stay in the flush's sum), the staging thread is waited for,
+ * and what the device flagged since the last report is returned and cleared here.  Works on sharded
+ * engines; one whose group still holds staged blocks is refused (FFM_E_INVALID) -- the group's call trains
+ * them first.  ffm_group_refresh_weights runs every shard; every slot that can be live belongs to exactly
+ * one shard, so its counters are plain sums and equal those of the unsharded model.  out may be NULL.
+ * The counter buffer (48 bytes of HBM) is allocated by the first call and freed by ffm_engine_destroy: an
+ * engine that never calls this allocates nothing, launches nothing and changes in nothing. */
+typedef struct { int64_t lin_live, lin_nonzero, lin_moved, lat_live, lat_nonzero, lat_moved; } ffm_refresh_stats;
+int ffm_engine_refresh_weights(ffm_engine *e, ffm_refresh_stats *out);
+int ffm_group_refresh_weights(ffm_group *g, ffm_refresh_stats *out);
 
 #ifdef __cplusplus
 }
