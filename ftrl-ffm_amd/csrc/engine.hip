@@ -36,6 +36,7 @@
 #include "../../include/ffm_engine.h"
 #include "engine_types.h"
 #include "init_rng.h"
+#include "hash_ids.h"
 #include "kernels_group.h"
 #include "kernels_row.h"
 #include "kernels_fold.h"
@@ -377,6 +378,11 @@ struct ffm_engine {
   // the AUC channels (include/ffm_engine.h "Metrics"): hist = pos[kMetricBins], neg[kMetricBins], n_nan;
   // allocated when the channel is first turned on
   struct MetricChannel { bool on = false; unsigned long long *hist = nullptr; } metric[2];
+  // FFM_FLAG_HASH_IDS (engine_hash.h): host rows have their ids hashed on the device before any kernel reads
+  // them; hm.start = the device copy of field_start (FFM with per-field id ranges) or null = [0, n_feats)
+  bool hash_ids = false;
+  ftrl_hash::Map hm{};
+  int *d_hash_start = nullptr;
   // ffm_engine_refresh_weights (engine_refresh.h): its six counters and its grid, both made by the first call
   unsigned long long *d_refresh = nullptr;
   int refresh_grid = 0;
@@ -648,9 +654,14 @@ void ffm_engine_destroy(ffm_engine *e) {
   delete e;
 }
 
+static int hash_ids_check(int32_t model_type, int32_t n_feats, int32_t n_fields, const int32_t *field_start);  // (engine_hash.h)
+
 int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   if (!cfg || !out) return fail(FFM_E_INVALID, "null config or output pointer");
   *out = nullptr;
+  // FFM_ENGINE_HASH_IDS=1: FFM_FLAG_HASH_IDS on whatever the caller's flags say (every rank of a group)
+  bool hash_ids = (cfg->flags & FFM_FLAG_HASH_IDS) != 0;
+  if (const char *sv = std::getenv("FFM_ENGINE_HASH_IDS")) hash_ids = hash_ids || sv[0] == '1';
   if (cfg->model_type < FFM_MODEL_LR || cfg->model_type > FFM_MODEL_FFM)
     return fail(FFM_E_INVALID, "invalid model_type, expect LR(0), FM(1) or FFM(2)");
   if (cfg->n_feats <= 0) return fail(FFM_E_INVALID, "n_feats must be positive");
@@ -668,6 +679,9 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
     return fail(FFM_E_UNSUPPORTED, "field-pair sharding applies to FFM only");
   if (cfg->n_shards > 1 && cfg->n_fields > 64)
     return fail(FFM_E_UNSUPPORTED, "field-pair sharding supports up to 64 fields");
+  // (an argument error like the ones above: reported whether or not there is a device)
+  if (hash_ids)
+    if (int rc_h = hash_ids_check(cfg->model_type, cfg->n_feats, cfg->n_fields, cfg->field_start)) return rc_h;
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
     return fail(FFM_E_DEVICE, "no HIP device available (this library has no CPU fallback)");
@@ -678,6 +692,8 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   ffm_engine *e = new (std::nothrow) ffm_engine;
   if (!e) return fail(FFM_E_NOMEM, "host allocation failed");
   e->cfg = *cfg;
+  if (hash_ids) e->cfg.flags |= FFM_FLAG_HASH_IDS;
+  e->hash_ids = hash_ids;
   e->max_rows = cfg->max_batch_rows;
   e->max_nnz = cfg->max_batch_nnz;
   if (cfg->max_row_nnz > 0) e->max_row_nnz = cfg->max_row_nnz;
@@ -888,6 +904,14 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
       TRY_HIP(hipMemcpy(d_base, base.data(), base.size() * sizeof(long long), hipMemcpyHostToDevice));
       m.field_start = d_fs;
       m.rec_base = d_base;
+    }
+  }
+  if (e->hash_ids) {
+    e->hm = ftrl_hash::Map{nullptr, cfg->n_feats, m.n_fields, m.type == FFM_MODEL_FFM ? 1 : 0};
+    if (!e->field_start.empty()) {  // (kept for FFM only; widths checked above)
+      TRY_ALLOC(e->alloc(&e->d_hash_start, e->field_start.size()));
+      TRY_HIP(hipMemcpy(e->d_hash_start, e->field_start.data(), e->field_start.size() * sizeof(int), hipMemcpyHostToDevice));
+      e->hm.start = e->d_hash_start;
     }
   }
   TRY_ALLOC(e->alloc(&s.logit, R));
@@ -1220,6 +1244,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 }
 
 #include "engine_state.h"
+#include "engine_hash.h"
 #include "engine_step.h"
 #include "engine_stage.h"
 #include "engine_refresh.h"

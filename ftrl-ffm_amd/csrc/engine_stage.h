@@ -80,6 +80,63 @@ __global__ __launch_bounds__(256) void pull_block_weighted_kernel(PullWeightedJo
   }
   FFM_PULL_BLOCK_FINISH(job)
 }
+// FFM_FLAG_HASH_IDS: the same two kernels with the ids hashed on their way through (csrc/hash_ids.h) --
+// kernels of their own, so that an unflagged engine's upload is the launch, and the kernel, it always was.
+// feat and field are taken out of the block's five arrays (their byte counts there are 0) and move in ONE
+// loop instead: they are equally long, so a lane loads the int4 of feat and the int4 of field, hashes four
+// entries and stores both; the last nnz % 4 entries go one by one.  No byte crosses PCIe twice, and the
+// integer work hides behind the link (the kernel is bound by PCIe).  fsrc == nullptr: no field array came
+// -- LR / FM, or FFM rows of one entry per field in field order, whose fields FFM_PULL_BLOCK_FINISH writes
+// and this loop recomputes the same way.
+struct PullHashJob {
+  PullWeightedJob w;
+  ftrl_hash::Map hm;
+  const char *isrc, *fsrc; char *idst, *fdst; unsigned hbytes;
+};
+#define FFM_PULL_BLOCK_HASHED(hj)                                                                           \
+  {                                                                                                         \
+    const unsigned n16 = hj.hbytes >> 4, F = static_cast<unsigned>(hj.hm.n_fields);                         \
+    for (unsigned i = tid; i < n16; i += stride) {                                                          \
+      const int4 ft = reinterpret_cast<const int4 *>(hj.isrc)[i];                                           \
+      int4 fl;                                                                                              \
+      if (hj.fsrc) {                                                                                        \
+        fl = reinterpret_cast<const int4 *>(hj.fsrc)[i];                                                    \
+        reinterpret_cast<int4 *>(hj.fdst)[i] = fl;                                                          \
+      } else fl = hj.hm.ffm ? hash_implicit_fields4(i, F) : make_int4(0, 0, 0, 0);                          \
+      reinterpret_cast<int4 *>(hj.idst)[i] = hash_entries4(hj.hm, fl, ft);                                  \
+    }                                                                                                       \
+    if (tid < ((hj.hbytes & 15u) >> 2)) {                                                                   \
+      const unsigned p = (n16 << 2) + tid;                                                                  \
+      int f = hj.hm.ffm ? static_cast<int>(p % F) : 0;                                                      \
+      if (hj.fsrc) {                                                                                        \
+        f = reinterpret_cast<const int *>(hj.fsrc)[p];                                                      \
+        reinterpret_cast<int *>(hj.fdst)[p] = f;                                                            \
+      }                                                                                                     \
+      reinterpret_cast<int *>(hj.idst)[p] = ftrl_hash::hash_entry(hj.hm, f, reinterpret_cast<const int *>(hj.isrc)[p]); \
+    }                                                                                                       \
+  }
+__global__ __launch_bounds__(256) void pull_block_hashed_kernel(PullHashJob hjob) {
+  const PullJob &job = hjob.w.block;
+  FFM_PULL_BLOCK_ARRAYS(job)
+  FFM_PULL_BLOCK_HASHED(hjob)
+  FFM_PULL_BLOCK_FINISH(job)
+}
+__global__ __launch_bounds__(256) void pull_block_weighted_hashed_kernel(PullHashJob hjob) {
+  const PullJob &job = hjob.w.block;
+  FFM_PULL_BLOCK_ARRAYS(job)
+  {
+    const unsigned n16 = hjob.w.wbytes >> 4;
+    const int4 *s = reinterpret_cast<const int4 *>(hjob.w.wsrc);
+    int4 *d = reinterpret_cast<int4 *>(hjob.w.wdst);
+    for (unsigned i = tid; i < n16; i += stride) d[i] = s[i];
+    const unsigned tail = hjob.w.wbytes & 15u;
+    if (tid < (tail >> 2))
+      reinterpret_cast<int *>(hjob.w.wdst)[(n16 << 2) + tid] = reinterpret_cast<const int *>(hjob.w.wsrc)[(n16 << 2) + tid];
+  }
+  FFM_PULL_BLOCK_HASHED(hjob)
+  FFM_PULL_BLOCK_FINISH(job)
+}
+#undef FFM_PULL_BLOCK_HASHED
 #undef FFM_PULL_BLOCK_ARRAYS
 #undef FFM_PULL_BLOCK_FINISH
 
@@ -179,7 +236,7 @@ int ffm_engine_unpin_host(void *p) {
 static int claim_slot(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
                       const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
                       int32_t zero_copy, int *slot_out, bool *was_used, PullJob *job_out,
-                      const float *weight = nullptr, PullWeightedJob *wjob_out = nullptr) {
+                      const float *weight = nullptr, PullWeightedJob *wjob_out = nullptr, PullHashJob *hjob_out = nullptr) {
   int rc;
   if ((rc = slots_init(e))) return rc;
   if (weight && n_rows > 0 && (rc = slot_weights_init(e))) return rc;
@@ -201,7 +258,9 @@ static int claim_slot(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t 
   int n_job = 0;
   // page-locked source of each array: the caller's own (zero_copy: untouched until the block has
   // trained) or its image in the slot's pinned buffer; the device then pulls it (pull_block_kernel)
-  auto put = [&](const void *src, size_t bytes, void *dst) -> hipError_t {
+  // (hashed_src: the array is feat or field of a flagged engine's block -- it goes to the hashed loop of the
+  // upload kernel, *hashed_src / *hashed_dst, instead of into the job's five)
+  auto put = [&](const void *src, size_t bytes, void *dst, const char **hashed_src = nullptr, char **hashed_dst = nullptr) -> hipError_t {
     if (!bytes || !src) return hipSuccess;
     const void *host = src;
     if (!zero_copy) {
@@ -213,21 +272,31 @@ static int claim_slot(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t 
     hipError_t err = hipHostGetDevicePointer(&mapped, const_cast<void *>(host), 0);
     if (err != hipSuccess) return err;
     if ((reinterpret_cast<uintptr_t>(mapped) & 15u) != 0) return hipErrorInvalidValue;  // 16-byte aligned arrays only
+    if (hashed_src) {
+      *hashed_src = static_cast<const char *>(mapped);
+      *hashed_dst = static_cast<char *>(dst);
+      return hipSuccess;
+    }
     job.src[n_job] = static_cast<const char *>(mapped);
     job.dst[n_job] = static_cast<char *>(dst);
     job.bytes[n_job] = static_cast<unsigned>(bytes);
     n_job++;
     return hipSuccess;
   };
+  PullHashJob *const hj = e->hash_ids ? hjob_out : nullptr;
+  if (hj) {
+    hj->hm = e->hm;
+    hj->hbytes = static_cast<unsigned>(4 * E);
+  }
   ScopedTimer tm("stage:copies");
   HIP_TRY(put(row_ptr, 4 * R1, sl.row_ptr));
-  if (field) HIP_TRY(put(field, 4 * E, sl.field));
+  if (field) HIP_TRY(put(field, 4 * E, sl.field, hj ? &hj->fsrc : nullptr, hj ? &hj->fdst : nullptr));
   else if (e->m.type == FFM_MODEL_FFM && E > 0) {  // (validated: one entry per field in field order)
     job.gen_field = sl.field;
     job.gen_n = static_cast<unsigned>(E);
     job.gen_fields = e->m.n_fields;
   }
-  HIP_TRY(put(feat, 4 * E, sl.feat));
+  HIP_TRY(put(feat, 4 * E, sl.feat, hj ? &hj->isrc : nullptr, hj ? &hj->idst : nullptr));
   HIP_TRY(put(val, 4 * E, sl.val));
   HIP_TRY(put(label, 4 * static_cast<size_t>(n_rows), sl.label));
   if (weight && n_rows > 0) {  // the sixth array: beside the job's five (its image: the slot's pinned_w)
@@ -285,9 +354,10 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   int this_slot = 0;
   bool slot_was_used = false;
-  PullWeightedJob job{};
+  PullHashJob hjob{};  // (the hashed loop's part is filled on a flagged engine only)
+  PullWeightedJob &job = hjob.w;
   if ((rc = claim_slot(e, n_rows, nnz, row_ptr, field, feat, val, label, zero_copy, &this_slot, &slot_was_used, &job.block,
-                       weight, &job)))
+                       weight, &job, &hjob)))
     return rc;
   ffm_engine::Slot &sl = e->slots[this_slot];
   // its grouping, behind its own upload on the prep stream: planned here, submitted with the upload
@@ -298,7 +368,9 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
   const int grid_pull = e->grid_pull;
   const bool timed = !e->stage_thread_on || e->prof_on;
   hipEvent_t free_ev = slot_was_used ? sl.free_ev : nullptr;
-  rc = e->submit([e, this_slot, free_ev, job, plan, seq, grid_pull, timed]() -> int {
+  const bool hashed = e->hash_ids;
+  rc = e->submit([e, this_slot, free_ev, hjob, hashed, plan, seq, grid_pull, timed]() -> int {
+    const PullWeightedJob &job = hjob.w;
     ScopedTimer tm("stage:submit");
     ffm_engine::Slot &s2 = e->slots[this_slot];
     int rc2 = FFM_OK;
@@ -308,7 +380,9 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
       // (long steps: the upload too waits for the running block's row kernel to end -- beside the update
       // launches it costs nothing, beside the row kernel, which is bound by the bytes it moves, it does)
       if (e->pull_after_row && plan.ws >= 0) HIP_TRY(hipStreamWaitEvent(e->copy, e->prep_after_row ? e->ev_row_done[plan.ws] : e->ev_set_free[plan.ws], 0));
-      if (job.wbytes) hipLaunchKernelGGL(pull_block_weighted_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job);
+      if (hashed && job.wbytes) hipLaunchKernelGGL(pull_block_weighted_hashed_kernel, dim3(grid_pull), dim3(256), 0, e->copy, hjob);
+      else if (hashed) hipLaunchKernelGGL(pull_block_hashed_kernel, dim3(grid_pull), dim3(256), 0, e->copy, hjob);
+      else if (job.wbytes) hipLaunchKernelGGL(pull_block_weighted_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job);
       else hipLaunchKernelGGL(pull_block_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job.block);
       HIP_TRY(hipEventRecord(s2.ev_copied, e->copy));
       if (e->copy != e->prep) HIP_TRY(hipStreamWaitEvent(e->prep, s2.ev_copied, 0));  // the grouping reads the slot
@@ -507,12 +581,15 @@ int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const i
   if ((rc = e->drain())) return rc;
   int this_slot = 0;
   bool slot_was_used = false;
-  PullJob job{};
-  if ((rc = claim_slot(e, n_rows, nnz, row_ptr, field, feat, val, label, zero_copy, &this_slot, &slot_was_used, &job)))
+  PullHashJob hjob{};  // (the hashed loop's part is filled on a flagged engine only)
+  PullJob &job = hjob.w.block;
+  if ((rc = claim_slot(e, n_rows, nnz, row_ptr, field, feat, val, label, zero_copy, &this_slot, &slot_was_used, &job, nullptr,
+                       nullptr, &hjob)))
     return rc;
   ffm_engine::Slot &sl = e->slots[this_slot];
   if (slot_was_used && sl.free_ev) HIP_TRY(hipStreamWaitEvent(e->copy, sl.free_ev, 0));  // nothing reads its device arrays
-  hipLaunchKernelGGL(pull_block_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, job);
+  if (e->hash_ids) hipLaunchKernelGGL(pull_block_hashed_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, hjob);
+  else hipLaunchKernelGGL(pull_block_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, job);
   HIP_TRY(hipEventRecord(sl.ev_copied, e->copy));
   sl.used = true;
   sl.zero_copy = zero_copy != 0;

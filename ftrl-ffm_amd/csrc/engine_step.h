@@ -626,6 +626,8 @@ static int stage_block(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, co
     HIP_TRY(hipMemcpyAsync(e->d_label, label, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, e->stream));
   if (weight && n_rows > 0)
     HIP_TRY(hipMemcpyAsync(e->d_weight, weight, sizeof(float) * n_rows, hipMemcpyHostToDevice, e->stream));
+  // FFM_FLAG_HASH_IDS: the ids in place, behind their copy and ahead of every kernel that reads them
+  if (e->hash_ids) launch_hash_ids(e, e->stream, nnz, field ? e->d_field : nullptr, e->d_feat, e->d_feat);
   *nnz_out = nnz;
   return FFM_OK;
 }

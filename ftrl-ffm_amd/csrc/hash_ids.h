@@ -1,0 +1,56 @@
+// hash_ids.h -- the hashing trick, per field: id' = lo[f] + h(f, id) mod-like-into width[f], IDENTICAL
+// BITS on the device and on the host (the contract is stated in include/ffm_engine.h, "Hashed ids").
+//
+// The reference has no counterpart: FtrlModel::remove_out_range / FFM::remove_out_range
+// (ftrl_model.cpp:36-42, ffm.cpp:30-36) erase every id >= n_feats, so a file whose id space is larger than
+// the model trains on a fraction of its entries.  Here such an id is folded into the range of its field
+// instead -- which also gives any data the one-range-per-field layout the compact shards, the range sort
+// and the regular-block forms are built around.  Unsigned 32-bit wrap-around arithmetic only, then one
+// 32 x 32 -> 64 multiply whose high half scales the hash into [0, width): no divide, no table.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define FTRL_HASH_HD __host__ __device__ __forceinline__
+#else
+#define FTRL_HASH_HD inline
+#endif
+
+namespace ftrl_hash {
+
+FTRL_HASH_HD uint32_t mix32(uint32_t x) {  // the murmur3 finaliser
+  x ^= x >> 16;
+  x *= 0x85ebca6bu;
+  x ^= x >> 13;
+  x *= 0xc2b2ae35u;
+  x ^= x >> 16;
+  return x;
+}
+
+// A valid entry's model id: `field` salts the hash (0 for LR / FM), [lo, lo + width) is where it lands.
+FTRL_HASH_HD int32_t hash_into(int32_t field, int32_t feat, int32_t lo, uint32_t width) {
+  const uint32_t salt = (static_cast<uint32_t>(field) + 1u) * 0x9e3779b9u;  // ((uint32)(field + 1), without signed overflow)
+  const uint32_t x = mix32(static_cast<uint32_t>(feat) ^ salt);
+  return lo + static_cast<int32_t>((static_cast<uint64_t>(x) * static_cast<uint64_t>(width)) >> 32);
+}
+
+// Where the ids of a model go: `start` = the fields' id ranges (n_fields + 1 ascending values; FFM with
+// field_start) or null = one range [0, n_feats); ffm: fields are checked and salt the hash.
+struct Map {
+  const int32_t *start;
+  int32_t n_feats, n_fields, ffm;
+};
+
+// One entry.  Entries the reference erases stay erased: a negative id, or (FFM) a field outside
+// [0, n_fields), gives -1, which every kernel downstream drops as it drops any id outside [0, n_feats).
+FTRL_HASH_HD int32_t hash_entry(const Map &m, int32_t field, int32_t feat) {
+  if (feat < 0) return -1;
+  if (!m.ffm) return hash_into(0, feat, 0, static_cast<uint32_t>(m.n_feats));
+  if (static_cast<uint32_t>(field) >= static_cast<uint32_t>(m.n_fields)) return -1;
+  if (!m.start) return hash_into(field, feat, 0, static_cast<uint32_t>(m.n_feats));
+  const int32_t lo = m.start[field];
+  return hash_into(field, feat, lo, static_cast<uint32_t>(m.start[field + 1] - lo));
+}
+
+}  // namespace ftrl_hash

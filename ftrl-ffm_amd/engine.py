@@ -14,6 +14,7 @@ LR, FM, FFM = 0, 1, 2
 MODEL_TYPES = {"LR": LR, "FM": FM, "FFM": FFM}
 FLAG_SKIP_INIT = 1
 FLAG_LEARN = 4
+FLAG_HASH_IDS = 8
 E_INVALID, E_DEVICE, E_NOMEM, E_CAPACITY, E_UNSUPPORTED = -1, -2, -3, -4, -5  # FFM_E_*
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -165,6 +166,10 @@ ABI = [
     # every stored weight from its accumulators (include/ffm_engine.h "Refresh")
     ("ffm_engine_refresh_weights", ctypes.c_int, [_vp, ctypes.POINTER(RefreshStats)]),
     ("ffm_group_refresh_weights", ctypes.c_int, [_vp, ctypes.POINTER(RefreshStats)]),
+    # ids hashed into their field's range (include/ffm_engine.h "Hashed ids")
+    ("ffm_engine_hash_ids_device", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, _vp]),
+    ("ffm_engine_hash_ids_host", ctypes.c_int,
+     [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.c_int32, _i32p, _i32p, _i32p]),
 ]
 
 _lib = None
@@ -218,6 +223,30 @@ def init_weights_host(seed, mean, stddev, latent, first, count):
                                                      int(first), int(count), _f(out))
     if rc != 0:
         raise EngineError(rc, load_library().ffm_engine_last_error().decode())
+    return out
+
+
+def hash_ids(field, feat, n_feats, field_start=None, model="ffm", n_fields=None):
+    """The model ids a flagged engine (hash_ids=True) gives raw ids, computed on the host
+    (ffm_engine_hash_ids_host: the device's bits, no device needed).  field: the entries' fields, or None
+    (LR / FM have none; FFM: rows of one entry per field in field order, n_fields needed).  field_start:
+    the fields' id ranges the engine was given, or None = one range [0, n_feats).  n_fields: fields outside
+    [0, n_fields) erase their entry (id -1); default len(field_start) - 1, else every field >= 0 is valid."""
+    lib = load_library()
+    mt = MODEL_TYPES[model.upper()] if isinstance(model, str) else int(model)
+    feat = np.ascontiguousarray(feat, np.int32)
+    fld = None if field is None or mt != FFM else np.ascontiguousarray(field, np.int32)
+    fs = None if field_start is None or mt != FFM else np.ascontiguousarray(field_start, np.int32)
+    if n_fields is None:
+        if fs is None and fld is None and mt == FFM:
+            raise ValueError("FFM rows without a field array need n_fields")
+        n_fields = fs.size - 1 if fs is not None else 2 ** 31 - 1
+    if fld is not None and fld.shape != feat.shape:
+        raise ValueError("field and feat must be equally long")
+    out = np.empty_like(feat)
+    rc = lib.ffm_engine_hash_ids_host(mt, int(n_feats), int(n_fields), _i(fs), feat.size, _i(fld), _i(feat), _i(out))
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
     return out
 
 
@@ -276,7 +305,7 @@ class Engine:
     def __init__(self, model_type="FFM", n_feats=10000, n_fields=8, n_factors=16, w_alpha=1e-4,
                  w_beta=1.0, w_l1=0.1, w_l2=5.0, init_mean=0.0, init_stddev=0.02, seed=42,
                  max_batch_rows=8192, max_batch_nnz=None, device_id=0, n_shards=1, shard_rank=0,
-                 stream=None, skip_init=False, max_row_nnz=0, learn=False, field_start=None):
+                 stream=None, skip_init=False, max_row_nnz=0, learn=False, field_start=None, hash_ids=False):
         self.lib = load_library()
         cfg = Config()
         self.lib.ffm_engine_default_config(ctypes.byref(cfg))
@@ -288,7 +317,7 @@ class Engine:
         cfg.max_batch_nnz = int(max_batch_nnz if max_batch_nnz else max_batch_rows * 64)
         cfg.device_id, cfg.n_shards, cfg.shard_rank = int(device_id), int(n_shards), int(shard_rank)
         cfg.stream = stream
-        cfg.flags = (FLAG_SKIP_INIT if skip_init else 0) | (FLAG_LEARN if learn else 0)
+        cfg.flags = (FLAG_SKIP_INIT if skip_init else 0) | (FLAG_LEARN if learn else 0) | (FLAG_HASH_IDS if hash_ids else 0)
         cfg.max_row_nnz = int(max_row_nnz)
         self._field_start = None
         if field_start is not None:
@@ -562,6 +591,13 @@ class Engine:
             self._check(self.lib.ffm_engine_train_batch_device_weighted(self.h, n_rows, nnz, row_ptr, field, feat,
                                                                         val, label, weight, logit_out, loss_sum_out))
 
+    def hash_ids_device(self, nnz, field, feat_in, feat_out):
+        """The engine's id mapping (hash_ids=True engines) applied to a block already in HBM, for callers of
+        the _device entry points, which take ids as they are.  Device addresses; feat_out may be feat_in;
+        field None: LR / FM, or FFM rows of one entry per field in field order.  Asynchronous on the
+        engine's stream."""
+        self._check(self.lib.ffm_engine_hash_ids_device(self.h, int(nnz), field, feat_in, feat_out))
+
     def prepare_device(self, n_rows, nnz, row_ptr, field, feat, val):
         """Look-ahead: group the next block on a side stream (see include/ffm_engine.h)."""
         self._check(self.lib.ffm_engine_prepare_device(self.h, n_rows, nnz, row_ptr, field, feat, val))
@@ -663,7 +699,7 @@ class Group:
     def __init__(self, devices, model_type="FFM", n_feats=10000, n_fields=8, n_factors=16, w_alpha=1e-4,
                  w_beta=1.0, w_l1=0.1, w_l2=5.0, init_mean=0.0, init_stddev=0.02, seed=42,
                  max_batch_rows=8192, max_batch_nnz=None, skip_init=False, max_row_nnz=0,
-                 field_start=None, learn=False):
+                 field_start=None, learn=False, hash_ids=False):
         self.lib = load_library()
         cfg = Config()
         self.lib.ffm_engine_default_config(ctypes.byref(cfg))
@@ -673,7 +709,7 @@ class Group:
         cfg.init_mean, cfg.init_stddev, cfg.seed = init_mean, init_stddev, int(seed)
         cfg.max_batch_rows = int(max_batch_rows)
         cfg.max_batch_nnz = int(max_batch_nnz if max_batch_nnz else max_batch_rows * 64)
-        cfg.flags = (FLAG_SKIP_INIT if skip_init else 0) | (FLAG_LEARN if learn else 0)
+        cfg.flags = (FLAG_SKIP_INIT if skip_init else 0) | (FLAG_LEARN if learn else 0) | (FLAG_HASH_IDS if hash_ids else 0)
         cfg.max_row_nnz = int(max_row_nnz)
         self._field_start = None
         if field_start is not None:

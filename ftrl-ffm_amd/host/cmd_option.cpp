@@ -41,9 +41,10 @@ const std::string_view cmd_help =
     "              differ from a fresh model of this seed (found by a device scan), with w, n, z, the bias and the\n"
     "              trainer's progress (one GPU only)\n"
     "--resume_from <path>: load such a checkpoint before training; needs the same model shape, --seed,\n"
-    "              --init_mean, --init_stddev and --learn (checked); the FTRL hyper-parameters (--w_alpha, --w_beta,\n"
-    "              --w_l1, --w_l2), --batch_size and --batch_ramp are NOT recorded in the file: pass the same ones\n"
-    "              and the resumed run continues the interrupted one bit for bit\n"
+    "              --init_mean, --init_stddev, --learn and --hash_feats (checked); the FTRL hyper-parameters (--w_alpha,\n"
+    "              --w_beta, --w_l1, --w_l2), --batch_size and --batch_ramp are NOT recorded in the file: pass the same ones\n"
+    "              and the resumed run continues the interrupted one bit for bit.  Under --hash_feats, --field_ranges\n"
+    "              shapes the id mapping and is not recorded either: a resumed run must pass the same value\n"
     "--metrics <auc|none>: auc = after each epoch's loss line one more line with the AUC of the same rows -- training:\n"
     "              of the pre-update predictions (progressive validation) --, histogrammed on the device in 2^20\n"
     "              score bins; the +- is the most the exact rank AUC can differ\tdefault:none\n"
@@ -70,7 +71,13 @@ const std::string_view cmd_help =
     "              its w) after each epoch's training and before its evaluation, before the model and the checkpoint are\n"
     "              written and before --predict_data is scored (also with --resume_from ck --n_epochs 0), and prints\n"
     "              `epoch N weights: linear L live, Z nonzero, M moved; latent L live, Z nonzero, M moved`.  (n, z) and\n"
-    "              the `train loss` lines do not change by a bit\tdefault:false\n";
+    "              the `train loss` lines do not change by a bit\tdefault:false\n"
+    "--hash_feats <bool>: the hashing trick, on the device: every non-negative id of the data, of any size, is hashed\n"
+    "              into the model's id space instead of being dropped when it is >= n_feats, salted by its field -- into\n"
+    "              [0, n_feats) with --field_ranges none, into its field's own range with uniform, which lets --n_gpus N\n"
+    "              train any libffm file and gives one GPU the per-field sort and the regular-block forms; LR / FM hash\n"
+    "              libsvm ids into [0, n_feats).  Negative ids (FFM: and fields outside [0, n_fields)) stay dropped.  The\n"
+    "              model, the checkpoint and every id printed are hashed ids; --n_feats bounds the model, not the data\tdefault:false\n";
 
 static bool assign_bool(std::string arg) {
   std::transform(arg.begin(), arg.end(), arg.begin(), [](unsigned char c) { return std::tolower(c); });
@@ -129,6 +136,7 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--device") device = std::stoi(v);
     else if (k == "--learn") learn = assign_bool(v);
     else if (k == "--refresh_weights") refresh_weights = assign_bool(v);
+    else if (k == "--hash_feats") hash_feats = assign_bool(v);
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
     else if (k == "--field_ranges") field_ranges = v;
     else if (k == "--metrics") {

@@ -37,6 +37,7 @@ struct config_options {
   std::string weight_path;
   bool weights_given = false;  // one of the three was passed: training blocks carry a weight array
   bool refresh_weights = false;  // --refresh_weights: every stored w = W(n, z) before it is evaluated, saved or scored
+  bool hash_feats = false;  // --hash_feats: FFM_FLAG_HASH_IDS, ids hashed into their field's id range on the device
 
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };

@@ -49,6 +49,10 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
   cfg.max_row_nnz = max_row_nnz_;
   cfg.device_id = opt.device;
   if (opt.learn) cfg.flags |= FFM_FLAG_LEARN;
+  // --hash_feats: the device hashes every id into range (include/ffm_engine.h "Hashed ids"); from here on
+  // get/set_latent_rows, pull/push_linear, the model files and checkpoints speak MODEL (hashed) ids
+  if (opt.hash_feats) cfg.flags |= FFM_FLAG_HASH_IDS;
+  hash_ids_ = opt.hash_feats;
   n_gpus_ = std::max(1, opt.n_gpus);
   seed_ = cfg.seed;
   init_mean_ = cfg.init_mean;
@@ -70,7 +74,7 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
         throw std::invalid_argument("--field_ranges uniform needs n_feats >= n_fields (every field owns an id range)");
       per_field_ = opt.n_feats / opt.n_fields;
       for (int f = 0; f <= opt.n_fields; f++) fs[f] = f == opt.n_fields ? opt.n_feats : f * per_field_;
-      if (n_gpus_ > 1) cfg.field_start = fs.data();
+      if (n_gpus_ > 1 || opt.hash_feats) cfg.field_start = fs.data();  // (hashed: the ranges shape the mapping)
     }
     std::vector<int32_t> devs(static_cast<size_t>(n_gpus_));
     const bool same = std::getenv("FTRL_SAME_DEVICE") != nullptr;  // one-GPU dry run of the orchestration
@@ -136,7 +140,7 @@ void FtrlModel::remove_out_range(feat_vec &feats) {  // ftrl_model.cpp:36-42
   feats.erase(std::remove_if(feats.begin(), feats.end(),
                              [&](const feat &f) {
                                const int i = std::get<1>(f);
-                               return i < 0 || i >= n_feats;
+                               return i < 0 || (i >= n_feats && !hash_ids_);  // (hashed into range on the device)
                              }),
               feats.end());
 }
@@ -146,7 +150,7 @@ void FFM::remove_out_range(feat_vec &feats) {
                              [&](const feat &f) {
                                const auto [field, i, v] = f;
                                (void)v;
-                               return field < 0 || i < 0 || field >= n_fields || i >= n_feats;
+                               return field < 0 || i < 0 || field >= n_fields || (i >= n_feats && !hash_ids_);
                              }),
               feats.end());
 }
@@ -665,6 +669,9 @@ FtrlModel::TrainProgress FtrlModel::load_checkpoint(std::string_view file_name) 
   if ((h.flags ^ static_cast<uint32_t>(flags_)) & FFM_FLAG_LEARN)
     throw std::runtime_error(name + ": was saved " + ((h.flags & FFM_FLAG_LEARN) ? "with" : "without") +
                              " --learn, this model is the other variant: the resumed run would not be the interrupted one");
+  if ((h.flags ^ static_cast<uint32_t>(flags_)) & FFM_FLAG_HASH_IDS)
+    throw std::runtime_error(name + ": was saved " + ((h.flags & FFM_FLAG_HASH_IDS) ? "with" : "without") +
+                             " --hash_feats, this model is the other variant: the resumed run would not be the interrupted one");
   int64_t touched = 0;
   check(ffm_engine_changed_features(eng_, nullptr, 0, &touched), "ffm_engine_changed_features");
   if (touched != 0)

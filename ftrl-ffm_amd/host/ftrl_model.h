@@ -152,7 +152,7 @@ class FtrlModel {
   // Sparse resumable checkpoint (persist.h): only the features that no longer hold what the
   // constructor gave them (ffm_engine_changed_features, one device scan), their full records
   // (w, n, z), the bias triple and the trainer's progress.  load_checkpoint wants a model built with the
-  // same shape, seed, init parameters and --learn setting that has not been touched yet (throws std::runtime_error
+  // same shape, seed, init parameters, --learn and --hash_feats setting that has not been touched yet (throws std::runtime_error
   // otherwise) and makes it the saved model bit for bit; returns the progress saved with it.  Not
   // supported for sharded models (--n_gpus > 1): both throw.
   using TrainProgress = ftrl::TrainProgress;
@@ -198,6 +198,7 @@ class FtrlModel {
   uint64_t seed_ = 0;
   float init_mean_ = 0.0f, init_stddev_ = 0.0f;
   int32_t flags_ = 0;
+  bool hash_ids_ = false;  // --hash_feats: ids >= n_feats are not erased on the host, the device hashes them
   CsrBlock one_;  // scratch for the one-row shims
   // engine capacities chosen at construction; blocks beyond max_nnz_ are split into several
   // engine calls (each still a block in row order), a single row beyond max_row_nnz_ is an error

@@ -22,7 +22,8 @@
  *   of crossing PCIe, a third of the block's bytes.  Same results as with the array passed.
  *   Entries whose feat (FFM: or field) is out of range are ignored exactly as
  *   FtrlModel::remove_out_range / FFM::remove_out_range erase them (ftrl_model.cpp:36-42,
- *   ffm.cpp:30-36); the caller's buffers are never modified.
+ *   ffm.cpp:30-36); the caller's buffers are never modified.  (FFM_FLAG_HASH_IDS: ids >= n_feats are
+ *   hashed into range instead -- "Hashed ids" below.)
  *
  * Batch semantics: all rows of one train call see the weights refreshed from the
  * call-start (n,z); each touched (n,z) then receives the reference's per-sample update once per
@@ -41,7 +42,8 @@ extern "C" {
 
 /* 3: + ffm_engine_predict_batch_async, ffm_group_* (additions only: a caller built against 2 runs
  * unchanged).  The *_weighted entry points ("Sample weights" below) and ffm_engine_refresh_weights /
- * ffm_group_refresh_weights ("Refresh" below) are additions as well. */
+ * ffm_group_refresh_weights ("Refresh" below) are additions as well, and so are FFM_FLAG_HASH_IDS and
+ * ffm_engine_hash_ids_device / _host ("Hashed ids" below). */
 #define FFM_ENGINE_ABI_VERSION 4
 
 /* ModelType, reference src/include/utils/types.h:21-25 */
@@ -102,13 +104,15 @@ typedef struct ffm_engine_config {
 
 enum {
   FFM_FLAG_SKIP_INIT = 1, /* leave w zeroed; the caller will ffm_engine_set_weights */
-  FFM_FLAG_LEARN = 4      /* opt-in "learning" variant, NOT the reference's arithmetic (SURVEY.md
+  FFM_FLAG_LEARN = 4,     /* opt-in "learning" variant, NOT the reference's arithmetic (SURVEY.md
                            * 8(f) rank 4): (1) the lazy refresh keeps a latent slot's initial
                            * weight until its first gradient (n > 0) instead of overwriting it
                            * with W(0,0) = 0 (ffm.cpp:72-88, fm.cpp:69-78), (2) ffm.cpp:118 uses
                            * g2*g2 instead of g2*g1 -- so that FM / FFM factors actually train.
                            * Off: the reference bit for bit.  (Flag value 2 was round 1's
                            * optional fused row kernel: measured slower, removed.) */
+  FFM_FLAG_HASH_IDS = 8   /* feature ids of HOST rows are hashed into their field's id range on the device
+                           * before any kernel reads them: "Hashed ids" below */
 };
 
 void ffm_engine_default_config(ffm_engine_config *cfg);
@@ -549,6 +553,47 @@ int ffm_engine_metrics_from_histogram(const uint64_t *pos, const uint64_t *neg, 
 /* A group's labels are seen by every rank; rank 0's engine keeps the channels. */
 int ffm_group_metrics_enable(ffm_group *g, int32_t channel_mask);
 int ffm_group_metrics_read(ffm_group *g, int32_t channel, int32_t reset, ffm_metrics *out);
+
+/* ---- Hashed ids: FFM_FLAG_HASH_IDS ----------------------------------------------------------------
+ * The reference erases every entry whose id is not in [0, n_feats) (remove_out_range, ftrl_model.cpp:36-42,
+ * ffm.cpp:30-36); real click logs come with one global id space, fields interleaved, often larger than the
+ * model one can afford.  With this flag the engine applies the hashing trick, per field, to every block of
+ * HOST rows: the model then sees id' where the caller wrote feat.  The mapping (csrc/hash_ids.h; unsigned
+ * 32-bit wrap-around arithmetic except the last step) is part of the contract:
+ *   salt = (uint32)(field + 1) * 0x9e3779b9                     (LR / FM: field taken as 0)
+ *   x  = (uint32)feat ^ salt
+ *   x ^= x >> 16;  x *= 0x85ebca6b;  x ^= x >> 13;  x *= 0xc2b2ae35;  x ^= x >> 16
+ *   id' = lo + (int32)(((uint64)x * (uint64)width) >> 32)       (multiply-high: no divide)
+ *   (lo, width) = (field_start[f], field_start[f+1] - field_start[f]) for FFM with cfg->field_start,
+ *                 (0, n_feats) in every other case.
+ * Entries the reference erases stay erased: feat < 0 gives id' = -1, and so does, for FFM, a field outside
+ * [0, n_fields).  Every non-negative id up to INT32_MAX is hashed into range.  There is no seed: the mapping
+ * is a pure function of (field, feat, field_start / n_feats).  Two raw ids of one row that collide under one
+ * field make a row that holds one id twice -- the serial case of DESIGN.md section 3, nothing special.
+ *   create     with the flag, a field of width 0 is FFM_E_INVALID (nothing can land in it).  The environment
+ *              variable FFM_ENGINE_HASH_IDS=1, read by ffm_engine_create, turns the flag on (every rank of a
+ *              group), as FFM_ENGINE_METRICS does for the metrics channels.
+ *   where      every entry point that takes HOST rows: training and prediction, synchronous, pipelined,
+ *              page-locked / zero_copy, weighted, with scores, and the ffm_group_* calls.  The pipelined ones
+ *              hash inside the upload kernel (feat and field move in one loop; no byte crosses PCIe twice), the
+ *              synchronous ones by one in-place kernel behind their copies.  The caller's buffers are never
+ *              written.  With field_start the hashed ids lie in their fields' ranges: compact shards accept
+ *              any data, and rows of one entry per field are regular blocks.
+ *   _device    the entry points that take DEVICE rows take ids as they are, as they take val as it is:
+ *              their callers hash with ffm_engine_hash_ids_device -- the same kernel, asynchronous on the
+ *              engine's stream; feat_out may be feat_in; field == NULL means, for FFM, rows of one entry per
+ *              field in field order (entry p is field p mod n_fields); FFM_E_INVALID on an engine without
+ *              the flag.
+ *   host       ffm_engine_hash_ids_host is the same function of (model_type, n_feats, n_fields, field_start)
+ *              on the host, bit for bit, and needs no device (field_start may be NULL; n_fields is ignored
+ *              for LR / FM).
+ *   ids        ffm_engine_get_rows / set_rows, get / set_weights and _state, changed_features, the model
+ *              files and checkpoints all speak MODEL ids, i.e. hashed ones.
+ * Without the flag nothing changes: the same kernels, the same launches, no allocation. */
+int ffm_engine_hash_ids_device(ffm_engine *e, int32_t nnz, const int32_t *field, const int32_t *feat_in,
+                               int32_t *feat_out);
+int ffm_engine_hash_ids_host(int32_t model_type, int32_t n_feats, int32_t n_fields, const int32_t *field_start,
+                             int32_t nnz, const int32_t *field, const int32_t *feat_in, int32_t *feat_out);
 
 /* ---- Refresh: every stored weight from its accumulators -----------------------------------------
  * train() refreshes w = W(n, z) lazily, for what a row touches, BEFORE it updates (n, z), and leaves the
