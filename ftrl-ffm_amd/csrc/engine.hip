@@ -48,6 +48,7 @@
 #include "kernels_scan.h"
 #include "kernels_refresh.h"
 #include "kernels_metric.h"
+#include "kernels_serve.h"
 #include "metrics_host.h"
 
 using namespace ftrl_dev;
@@ -111,13 +112,13 @@ int fail(int code, const std::string &msg) {
 enum KernelId {
   K_GROUP_KEYS, K_GROUP_SORT, K_GROUP_FINISH, K_ROW, K_TMP_GRAD,
   K_LOSS_SUM, K_LINEAR_UPDATE, K_BIAS_UPDATE, K_LATENT_UPDATE, K_LATENT_UPDATE_FEW, K_LATENT_UPDATE_WALK, K_LATENT_UPDATE_GIANT,
-  K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC, K_PUSH_SCORES,
+  K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC, K_PUSH_SCORES, K_SERVE_ROW,
   K_COUNT
 };
 const char *kKernelNames[K_COUNT] = {
     "group_keys_kernel", "group_radix_sort", "group_finish_kernel", "row_kernel<train>", "tmp_grad_kernel", "loss_sum_kernel",
     "linear_update_kernel", "bias_update_kernel", "update_kernel", "update_few_kernel", "update_walk_kernel", "update_giant_kernel",
-    "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel", "push_scores_kernel"};
+    "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel", "push_scores_kernel", "serve_wave_kernel"};
 
 struct ProfRec {
   int kid;
@@ -386,6 +387,8 @@ struct ffm_engine {
   // ffm_engine_refresh_weights (engine_refresh.h): its six counters and its grid, both made by the first call
   unsigned long long *d_refresh = nullptr;
   int refresh_grid = 0;
+  // ffm_engine_pack_weights (engine_serve.h): the four counters of a serving engine, made by the first call
+  unsigned long long *d_pack = nullptr;
   std::vector<void *> allocs;
   // split-phase bookkeeping
   Rows pending{};
@@ -559,6 +562,13 @@ struct ffm_engine {
   }
 };
 
+// A serving engine (FFM_FLAG_SERVE_F32 / _F16, engine_serve.h) stores w alone: whatever needs (n, z) is refused.
+static inline bool serving(const ffm_engine *e) { return e->m.lat_fmt != SERVE_NONE; }
+static int serve_refuse(const char *what) {
+  return fail(FFM_E_UNSUPPORTED, std::string("a serving engine holds no accumulators: ") + what + " needs a training engine");
+}
+#define SERVE_REFUSE(e, what) do { if ((e) && serving(e)) return serve_refuse(what); } while (0)
+
 #define LAUNCH_ON(e, st, kid, kernel, grid, block, shmem, ...)                   \
   do {                                                                           \
     (e)->prof_begin(kid, st);                                                    \
@@ -655,6 +665,7 @@ void ffm_engine_destroy(ffm_engine *e) {
 }
 
 static int hash_ids_check(int32_t model_type, int32_t n_feats, int32_t n_fields, const int32_t *field_start);  // (engine_hash.h)
+static int serve_create_check(const ffm_engine_config *cfg);  // (engine_serve.h)
 
 int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   if (!cfg || !out) return fail(FFM_E_INVALID, "null config or output pointer");
@@ -679,6 +690,10 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
     return fail(FFM_E_UNSUPPORTED, "field-pair sharding applies to FFM only");
   if (cfg->n_shards > 1 && cfg->n_fields > 64)
     return fail(FFM_E_UNSUPPORTED, "field-pair sharding supports up to 64 fields");
+  // FFM_FLAG_SERVE_F32 / _F16: a serving engine (engine_serve.h) -- its shape is checked like the arguments above
+  const int serve_fmt = (cfg->flags & FFM_FLAG_SERVE_F32 ? SERVE_F32 : 0) | (cfg->flags & FFM_FLAG_SERVE_F16 ? SERVE_F16 : 0);
+  if (serve_fmt)
+    if (int rc_s = serve_create_check(cfg)) return rc_s;
   // (an argument error like the ones above: reported whether or not there is a device)
   if (hash_ids)
     if (int rc_h = hash_ids_check(cfg->model_type, cfg->n_feats, cfg->n_fields, cfg->field_start)) return rc_h;
@@ -697,6 +712,7 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   e->max_rows = cfg->max_batch_rows;
   e->max_nnz = cfg->max_batch_nnz;
   if (cfg->max_row_nnz > 0) e->max_row_nnz = cfg->max_row_nnz;
+  else if (serve_fmt) e->max_row_nnz = kPredLdsCap;  // (a serving engine's rows are one wave's: no longer ones)
   if (const char *sv = std::getenv("FFM_ENGINE_SERIAL")) e->serial = sv[0] == '1';
   if (const char *sv = std::getenv("FFM_UPDATE_SPLIT")) e->update_split = std::atoi(sv);
   if (const char *sv = std::getenv("FFM_UPDATE_ORDER")) {
@@ -759,6 +775,7 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   m.super_min = kSuperMin;
   if (const char *sv = std::getenv("FFM_SUPER_MIN")) m.super_min = std::max(kGiantMin, std::atoi(sv));
   m.few_stage = 1;
+  m.lat_fmt = serve_fmt;
   if (const char *sv = std::getenv("FFM_FEW_STAGE")) m.few_stage = sv[0] != '0';
   m.rec_slots = m.n_fields;
   e->n_records = cfg->n_feats;
@@ -813,10 +830,16 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   TRY_HIP(hipEventCreateWithFlags(&e->ev_join2, hipEventDisableTiming));
   TRY_HIP(hipStreamCreateWithFlags(&e->aux4, hipStreamNonBlocking));
   const size_t nf = static_cast<size_t>(cfg->n_feats);
-  const size_t n_lat = static_cast<size_t>(e->n_records) * 3 * static_cast<size_t>(m.row_len);
-  TRY_ALLOC(e->alloc(&m.bias3, 4));
-  TRY_ALLOC(e->alloc(&m.lin_n, nf));
-  TRY_ALLOC(e->alloc(&m.lin_z, nf));
+  // floats allocated for the latent part: records of (n, z, w), or a serving engine's table of w alone in
+  // 4- or 2-byte elements (row_len is a multiple of 4 there) -- and then no (n, z) of the bias or the linear part
+  const size_t n_w = static_cast<size_t>(e->n_records) * static_cast<size_t>(m.row_len);
+  const size_t n_lat = serve_fmt == SERVE_F16 ? n_w / 2 : serve_fmt == SERVE_F32 ? n_w : 3 * n_w;
+  const size_t n_bias = serve_fmt ? 1 : 4;
+  TRY_ALLOC(e->alloc(&m.bias3, n_bias));
+  if (!serve_fmt) {
+    TRY_ALLOC(e->alloc(&m.lin_n, nf));
+    TRY_ALLOC(e->alloc(&m.lin_z, nf));
+  }
   TRY_ALLOC(e->alloc(&m.lin_w, nf));
   TRY_ALLOC(e->alloc(&m.lat, n_lat));
   const size_t R = static_cast<size_t>(e->max_rows), E = static_cast<size_t>(e->max_nnz);
@@ -1063,9 +1086,11 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   if (static_cast<int64_t>(e->logical_len) > e->stage_floats) e->stage_floats = e->logical_len;
   TRY_ALLOC(e->alloc(&e->d_stage, static_cast<size_t>(e->stage_floats)));
 
-  TRY_HIP(hipMemsetAsync(m.bias3, 0, 4 * sizeof(float), e->stream));
-  TRY_HIP(hipMemsetAsync(m.lin_n, 0, nf * sizeof(float), e->stream));
-  TRY_HIP(hipMemsetAsync(m.lin_z, 0, nf * sizeof(float), e->stream));
+  TRY_HIP(hipMemsetAsync(m.bias3, 0, n_bias * sizeof(float), e->stream));
+  if (!serve_fmt) {
+    TRY_HIP(hipMemsetAsync(m.lin_n, 0, nf * sizeof(float), e->stream));
+    TRY_HIP(hipMemsetAsync(m.lin_z, 0, nf * sizeof(float), e->stream));
+  }
   TRY_HIP(hipMemsetAsync(m.lin_w, 0, nf * sizeof(float), e->stream));
   if (n_lat) TRY_HIP(hipMemsetAsync(m.lat, 0, n_lat * sizeof(float), e->stream));
   TRY_HIP(hipMemsetAsync(s.counters, 0, kNumCounters * sizeof(int), e->stream));
@@ -1127,7 +1152,10 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
     TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_update_all_kernel<2, UPD_ALL & ~UPD_FEW>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_lds_bytes(2))));
     TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_update_all_kernel<4, UPD_ALL & ~UPD_FEW>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_lds_bytes(4))));
   }
-  if (!(cfg->flags & FFM_FLAG_SKIP_INIT))
+  if (serve_fmt) {
+    if (!(cfg->flags & FFM_FLAG_SKIP_INIT))
+      hipLaunchKernelGGL(serve_init_kernel, dim3(2048), dim3(256), 0, e->stream, m, cfg->init_mean, cfg->init_stddev, cfg->seed);
+  } else if (!(cfg->flags & FFM_FLAG_SKIP_INIT))
     hipLaunchKernelGGL(init_weights_kernel, dim3(2048), dim3(256), 0, e->stream, m, e->logical_len,
                        cfg->init_mean, cfg->init_stddev, cfg->seed);
   TRY_HIP(hipGetLastError());
@@ -1146,6 +1174,9 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
 
 // What init_weights_kernel stored, computed on the host (csrc/init_rng.h: same bits).
 static int eval_launch_pending(ffm_engine *e);  // (engine_stage.h)
+// (engine_serve.h: the packed table <-> host arrays, for get / set_weights and get / set_rows)
+static int serve_vec_transfer(ffm_engine *e, float *host, bool to_host);
+static int serve_rows_vec_transfer(ffm_engine *e, int nf, float *host, bool to_host);
 
 int ffm_engine_init_weights_host(uint64_t seed, float init_mean, float init_stddev, int32_t latent,
                                  int64_t first, int64_t count, float *out) {
@@ -1157,6 +1188,7 @@ int ffm_engine_init_weights_host(uint64_t seed, float init_mean, float init_stdd
 
 int ffm_engine_fill_state(ffm_engine *e, uint64_t seed, float n_lo, float n_hi, float z_stddev) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
+  SERVE_REFUSE(e, "ffm_engine_fill_state");
   if (!(n_lo >= 0.0f) || !(n_hi >= n_lo)) return fail(FFM_E_INVALID, "need 0 <= n_lo <= n_hi");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   if (int rc_e = eval_launch_pending(e)) return rc_e;
@@ -1248,6 +1280,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_step.h"
 #include "engine_stage.h"
 #include "engine_refresh.h"
+#include "engine_serve.h"
 #include "engine_profile.h"
 #include "engine_metrics.h"
 }  // extern "C"

@@ -147,6 +147,8 @@ extern "C" {
 int ffm_group_create(const ffm_engine_config *cfg, int32_t n, const int32_t *device_ids, ffm_group **out) {
   if (!cfg || !out || n < 1 || n > 16 || !device_ids) return fail(FFM_E_INVALID, "bad group arguments (1 .. 16 engines)");
   *out = nullptr;
+  if (cfg->flags & (FFM_FLAG_SERVE_F32 | FFM_FLAG_SERVE_F16))
+    return fail(FFM_E_UNSUPPORTED, "a serving engine is one whole model on one device: not inside ffm_group_create");
   auto *g = new (std::nothrow) ffm_group();
   if (!g) return fail(FFM_E_NOMEM, "out of host memory");
   bool distinct = true;

@@ -7,6 +7,7 @@ static_assert(sizeof(ffm_refresh_stats) == RC_COUNT * sizeof(int64_t), "the kern
 int ffm_engine_refresh_weights(ffm_engine *e, ffm_refresh_stats *out) {
   if (out) std::memset(out, 0, sizeof(*out));
   if (!e) return fail(FFM_E_INVALID, "null engine");
+  SERVE_REFUSE(e, "ffm_engine_refresh_weights");
   if (e->has_pending) return fail(FFM_E_INVALID, "the previous block still awaits train_update");
   if (e->m.n_shards > 1 && e->n_staged > 0)
     return fail(FFM_E_INVALID, "a shard's staged blocks are trained by its group: ffm_group_refresh_weights, or flush first");

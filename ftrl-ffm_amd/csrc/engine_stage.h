@@ -322,6 +322,7 @@ static int claim_slot(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t 
 int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
                                     const int32_t *field, const int32_t *feat, const float *val,
                                     const int32_t *label, const float *weight, int32_t zero_copy) {
+  SERVE_REFUSE(e, "training");  // (staging is training's: prediction stages through predict_batch_async)
   int32_t nnz = 0;
   int longest = 1;
   // (LR / FM rows have no fields -- libsvm: src/data/parser.cpp:20 gives every entry field 0 -- so a
@@ -435,6 +436,7 @@ int64_t ffm_engine_blocks_scored(ffm_engine *e) {
 // Phase 1 (grouping is done: refresh + forward) on the oldest staged block.
 int ffm_engine_train_forward_staged(ffm_engine *e, float *partial_logit) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
+  SERVE_REFUSE(e, "training");
   if (e->n_staged == 0) return fail(FFM_E_INVALID, "no staged block");
   if (e->has_pending) return fail(FFM_E_INVALID, "the previous block still awaits train_update");
   const int slot = e->staged[0];

@@ -7,6 +7,7 @@
 
 static int vec_transfer(ffm_engine *e, int comp, float *host, bool to_host) {
   if (!host || e->logical_len == 0) return FFM_OK;
+  if (serving(e)) return serve_vec_transfer(e, host, to_host);  // (comp is LAT_W: the (n, z) callers are refused)
   const int64_t RL = e->logical_len;
   const int64_t chunk = e->stage_floats / RL;
   for (int64_t f0 = 0; f0 < e->m.n_feats; f0 += chunk) {
@@ -53,6 +54,7 @@ int ffm_engine_set_state(ffm_engine *e, const float *bias_n, const float *bias_z
                          const float *lin_n, const float *lin_z, const float *vec_n,
                          const float *vec_z) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
+  if (bias_n || bias_z || lin_n || lin_z || vec_n || vec_z) SERVE_REFUSE(e, "ffm_engine_set_state");
   if (int rc_e = eval_launch_pending(e)) return rc_e;  // (a deferred evaluation block sees the state as it was)
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   int rc;
@@ -67,6 +69,7 @@ int ffm_engine_set_state(ffm_engine *e, const float *bias_n, const float *bias_z
 int ffm_engine_get_state(ffm_engine *e, float *bias_n, float *bias_z, float *lin_n, float *lin_z,
                          float *vec_n, float *vec_z) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
+  if (bias_n || bias_z || lin_n || lin_z || vec_n || vec_z) SERVE_REFUSE(e, "ffm_engine_get_state");
   if (int rc_e = eval_launch_pending(e)) return rc_e;  // (a deferred evaluation block sees the state as it was)
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   int rc;
@@ -82,6 +85,7 @@ int ffm_engine_get_state(ffm_engine *e, float *bias_n, float *bias_z, float *lin
 static int rows_transfer(ffm_engine *e, int32_t n, const int32_t *ids, float *const lin[3],
                          float *const vec[3], bool to_host) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
+  if (lin[LAT_N] || lin[LAT_Z] || vec[LAT_N] || vec[LAT_Z]) SERVE_REFUSE(e, "the n / z arrays of ffm_engine_get_rows / set_rows");
   if (n < 0 || (n > 0 && !ids)) return fail(FFM_E_INVALID, "bad feature id list");
   for (int32_t j = 0; j < n; j++)
     if (ids[j] < 0 || ids[j] >= e->m.n_feats) return fail(FFM_E_INVALID, "feature id out of range");
@@ -103,6 +107,10 @@ static int rows_transfer(ffm_engine *e, int32_t n, const int32_t *ids, float *co
       }
       if (vec[comp] && RL > 0) {
         const size_t bytes = static_cast<size_t>(nf) * RL * sizeof(float);
+        if (serving(e)) {
+          if (int rc_s = serve_rows_vec_transfer(e, nf, vec[comp] + j0 * RL, to_host)) return rc_s;
+          continue;
+        }
         if (!to_host) HIP_TRY(hipMemcpyAsync(e->d_stage, vec[comp] + j0 * RL, bytes, hipMemcpyHostToDevice, e->stream));
         hipLaunchKernelGGL(lat_rows_copy_kernel, dim3(1024), dim3(256), 0, e->stream, e->m,
                            static_cast<int>(RL), comp, e->d_stage, e->d_ids,
@@ -138,6 +146,7 @@ int ffm_engine_changed_features(ffm_engine *e, int32_t *ids, int64_t cap, int64_
   if (n_changed) *n_changed = 0;
   if (!e) return fail(FFM_E_INVALID, "null engine");
   if (!n_changed) return fail(FFM_E_INVALID, "null n_changed");
+  SERVE_REFUSE(e, "ffm_engine_changed_features");
   if (ids && cap < 0) return fail(FFM_E_INVALID, "negative capacity");
   if (e->m.n_shards > 1)
     return fail(FFM_E_UNSUPPORTED, "the changed-feature scan covers whole-model engines (n_shards == 1)");

@@ -52,6 +52,8 @@ static bool launch_predict_waves(ffm_engine *e, const Rows &rows, int row_cap, f
 #undef PRED_LAUNCH
 }
 
+static void launch_serve_waves(ffm_engine *e, const Rows &rows, int row_cap, float *out, int output_prob);  // (engine_serve.h)
+
 // weight: the block's sample weights (device) or null; only the launches that produce tmp_grad
 // themselves (own_tg) take them -- otherwise tmp_grad_weighted_kernel does, after the logits are whole.
 static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float *out, int output_prob, int own_tg = 0,
@@ -59,6 +61,10 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float
   const int row_cap = e->staged_row_cap > 0 ? e->staged_row_cap : e->max_row_nnz;
   e->staged_row_cap = 0;
   if (rows.n_rows == 0) return;
+  if (serving(e)) {  // (predict only: every training entry point is refused) -- its own kernel and nothing else
+    launch_serve_waves(e, rows, row_cap, out, output_prob);
+    return;
+  }
   // (the kernels recompute the same terms capacity from the same arguments)
   const int terms_cap = e->m.type == FFM_MODEL_FM ? row_terms_cap(2, 0, e->m.n_factors)
                         : row_terms_cap(row_cap, e->m.n_shards > 1 ? e->m.rec_slots : 0, 0);
@@ -235,6 +241,7 @@ static int prepare_submit(ffm_engine *e, const PrepPlan &pl, bool timed) {
 
 int ffm_engine_prepare_device(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
                               const int32_t *field, const int32_t *feat, const float *val) {
+  SERVE_REFUSE(e, "ffm_engine_prepare_device");
   int rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val);
   if (rc) return rc;
   if ((rc = e->drain())) return rc;  // (staged blocks' submissions come first on the prep stream)
@@ -249,6 +256,7 @@ static int train_forward_core(ffm_engine *e, int32_t n_rows, int32_t nnz,
                               const int32_t *feat, const float *val, const int32_t *label,
                               const float *weight, float *partial_logit) {
   ScopedTimer tm_fwd("train:forward");
+  SERVE_REFUSE(e, "training");
   int rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val);
   if (rc) return rc;
   if (n_rows > 0 && !label) return fail(FFM_E_INVALID, "training needs labels");
@@ -309,6 +317,7 @@ int ffm_engine_train_forward_device_weighted(ffm_engine *e, int32_t n_rows, int3
 int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *logit_out,
                                    double *loss_sum_out) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
+  SERVE_REFUSE(e, "training");
   if (!e->has_pending) return fail(FFM_E_INVALID, "train_update without a preceding train_forward");
   ScopedTimer tm_upd("train:update");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
@@ -636,6 +645,7 @@ int ffm_engine_train_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
                                     const int32_t *field, const int32_t *feat, const float *val,
                                     const int32_t *label, const float *weight, float *logit_out,
                                     double *loss_sum_out) {
+  SERVE_REFUSE(e, "training");  // (before anything of the block is copied)
   int32_t nnz = 0;
   int rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &nnz, weight);
   if (rc) return rc;

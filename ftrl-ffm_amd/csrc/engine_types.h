@@ -65,6 +65,9 @@ struct ModelDev {
                               //     its ranges are short so that many waves share one feature
   int few_stage;              // FFM_FEW_STAGE: 1 = on regular blocks the few-occurrence range stages its touches' rows
                               //     in LDS once per feature (kernels_update.h); 0 = the row table, batch by batch
+  int lat_fmt;                // 0: records as above.  A serving engine (kernels_serve.h): lat is a table of w alone,
+                              //     [n_feats][row_len] elements of fp32 (1) or IEEE binary16 (2); no n or z anywhere,
+                              //     lin_n / lin_z null -- only the serving kernels ever see a nonzero value
 };
 
 enum { LAT_N = 0, LAT_Z = 1, LAT_W = 2 };

@@ -1,0 +1,269 @@
+// kernels_serve.h -- a SERVING engine's device code (include/ffm_engine.h "Serving engines"): the model is
+// the bias, lin_w and a latent table of w ALONE, [n_feats][n_fields * n_factors] elements of 4 bytes (the
+// training engine's fp32 bits) or 2 (IEEE binary16) -- no n, no z, no record stride.
+//   ffm_serve_wave_kernel   ffm_predict_wave_kernel (kernels_predict.h) over that table: the same rows per
+//                           workgroup, staging, erasure, pair order, factor-order dot, term sum; only the
+//                           address of a slot and (fp16) the conversion of what was loaded differ.
+//   serve_init_kernel       the create-time contents: the training engine's draw, rounded to the format
+//   serve_dense_copy_kernel / serve_rows_copy_kernel   packed table <-> the fp32 staging buffer
+//   serve_pack_kernel       a training engine's stored bias, lin_w and w into a serving engine, counted
+// The fp16 rule is the hardware's conversion pair (v_cvt_f16_f32 / v_cvt_f32_f16 with 16-bit denormals on and
+// no overflow clamp): round to nearest even, subnormals kept, beyond the half range +-inf, NaN stays NaN;
+// decoding is exact.  tests/test_gpu_serve.py pins it against numpy's astype(float16).
+#pragma once
+#include <hip/hip_fp16.h>
+
+#include <type_traits>
+
+#include "engine_types.h"
+#include "init_rng.h"
+#include "kernels_predict.h"
+
+namespace ftrl_dev {
+
+enum { SERVE_NONE = 0, SERVE_F32 = 1, SERVE_F16 = 2 };  // ModelDev::lat_fmt
+
+__device__ __forceinline__ unsigned short serve_enc16(float x) { return __half_as_ushort(__float2half_rn(x)); }
+__device__ __forceinline__ float serve_dec16(unsigned short h) { return __half2float(__ushort_as_half(h)); }
+// four consecutive halves as a lane loads them (8 bytes): element j in bits [16 j, 16 j + 16)
+__device__ __forceinline__ float4 serve_dec16x4(uint2 r) {
+  return make_float4(serve_dec16(static_cast<unsigned short>(r.x & 0xffffu)), serve_dec16(static_cast<unsigned short>(r.x >> 16)),
+                     serve_dec16(static_cast<unsigned short>(r.y & 0xffffu)), serve_dec16(static_cast<unsigned short>(r.y >> 16)));
+}
+__device__ __forceinline__ uint2 serve_enc16x4(float4 w) {
+  return make_uint2(static_cast<unsigned>(serve_enc16(w.x)) | (static_cast<unsigned>(serve_enc16(w.y)) << 16),
+                    static_cast<unsigned>(serve_enc16(w.z)) | (static_cast<unsigned>(serve_enc16(w.w)) << 16));
+}
+__device__ __forceinline__ float4 serve_widen(float4 r) { return r; }
+__device__ __forceinline__ float4 serve_widen(uint2 r) { return serve_dec16x4(r); }
+
+// Element `idx` of the packed table, whatever its format.
+__device__ __forceinline__ float serve_load_elem(const ModelDev &m, int64_t idx) {
+  return m.lat_fmt == SERVE_F16 ? serve_dec16(reinterpret_cast<const unsigned short *>(m.lat)[idx]) : m.lat[idx];
+}
+__device__ __forceinline__ void serve_store_elem(const ModelDev &m, int64_t idx, float w) {
+  if (m.lat_fmt == SERVE_F16) reinterpret_cast<unsigned short *>(m.lat)[idx] = serve_enc16(w);
+  else m.lat[idx] = w;
+}
+
+// Lane c of a pair's LPP lanes holds factors [4 VPL c, 4 VPL (c + 1)) of both slots, as in the fp32 kernel:
+// a vector is four factors -- 16 bytes of an fp32 slot, 8 bytes of an fp16 one.
+template <int FMT, int LPP, int VPL, int U>
+__global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void ffm_serve_wave_kernel(ModelDev m, Rows rows, Scratch s,
+                                                                       int max_row_nnz, int lds_cap, float *out,
+                                                                       int output_prob) {
+  static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
+  static_assert(LPP >= 1 && LPP <= 16 && (LPP & (LPP - 1)) == 0, "a pair's lanes sit inside one DPP row");
+  constexpr int PPS = 64 / LPP;  // pairs per step
+  static_assert(kPredTerms % (PPS * U) == 0, "a batch of terms is whole unrolled steps");
+  using Raw = typename std::conditional<FMT == SERVE_F16, uint2, float4>::type;  // four factors as stored
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int r = wave_uniform(blockIdx.x * kPredRows + wv);
+  if (r >= rows.n_rows) return;
+  int4 *E = reinterpret_cast<int4 *>(smem + static_cast<size_t>(wv) * (static_cast<size_t>(lds_cap) * 16 + kPredTerms * 4));
+  float *terms = reinterpret_cast<float *>(E + lds_cap);
+  const int b = wave_uniform(rows.row_ptr[r]);
+  const int nnz = wave_uniform(rows.row_ptr[r + 1]) - b;
+  // beyond the validated capacity -- for a serving engine also everything a wave cannot stage (create
+  // keeps max_row_nnz <= kPredLdsCap; there is no workgroup-per-row launch behind this one): flagged, NaN
+  if (nnz > max_row_nnz || nnz > lds_cap) {
+    if (lane == 0) {
+      atomicOr(s.err, ERR_ROW_TOO_LONG);
+      const float nan = __int_as_float(0x7fc00000);
+      s.loss[r] = static_cast<double>(nan);
+      if (out) out[r] = nan;
+    }
+    return;
+  }
+  const int k = m.n_factors, RL = m.row_len;
+  const Raw *const table = reinterpret_cast<const Raw *>(m.lat);
+  const int k4 = k >> 2;  // vectors per slot
+
+  // ---- entries: the survivors in row order into LDS, the linear logit as a strictly sequential prefix
+  float result = m.bias3[0];
+  int nv = 0;
+  for (int base = 0; base < nnz; base += 64) {
+    const int p = base + lane;
+    int i = 0, f = 0;
+    float x = 0.0f, lw = 0.0f;
+    bool valid = false;
+    if (p < nnz) {
+      i = rows.feat[b + p];
+      f = rows.field[b + p];
+      x = rows.val[b + p];
+      valid = i >= 0 && i < m.n_feats && f >= 0 && f < m.n_fields;
+    }
+    if (valid) lw = m.lin_w[i];
+    const unsigned long long mask = __ballot(valid);
+    if (valid) E[nv + __popcll(mask & ((1ull << lane) - 1ull))] = make_int4(i, f, __float_as_int(x), 0);
+    nv += __popcll(mask);
+    const float run = wave_sequential_prefix(result, valid ? lw * x : -0.0f);
+    result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+
+  // ---- pairs in the reference's order (a outer, b inner)
+  const int n_pairs = nv * (nv - 1) / 2;
+  const int g = lane / LPP, c = lane - g * LPP;
+  int pa = 0, pb = 1 + g;
+  if (g < n_pairs)
+    while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
+  const int64_t RL4 = RL >> 2;  // vectors per feature
+  for (int q0 = 0; q0 < n_pairs; q0 += kPredTerms) {
+    const int cnt = min(kPredTerms, n_pairs - q0);
+    for (int st = 0; st * PPS < cnt; st += U) {
+      Raw x[U][VPL], y[U][VPL];
+      float xa[U], xb[U];
+      bool ok[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int q = q0 + (st + u) * PPS + g;
+        ok[u] = q < n_pairs;
+        const int a = ok[u] ? pa : 0, bb = ok[u] ? pb : (nv > 1 ? 1 : 0);
+        const int4 ea = E[a], eb = E[bb];
+        xa[u] = __int_as_float(ea.z);
+        xb[u] = __int_as_float(eb.z);
+        const Raw *va = table + static_cast<int64_t>(ea.x) * RL4 + eb.y * k4 + c * VPL;
+        const Raw *vb = table + static_cast<int64_t>(eb.x) * RL4 + ea.y * k4 + c * VPL;
+#pragma unroll
+        for (int v = 0; v < VPL; v++) { x[u][v] = va[v]; y[u][v] = vb[v]; }
+        if (q + PPS < n_pairs) {  // the pair PPS further on
+          pb += PPS;
+          while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        float pr[VPL][4];
+#pragma unroll
+        for (int v = 0; v < VPL; v++) {
+          const float4 xf = serve_widen(x[u][v]), yf = serve_widen(y[u][v]);
+          pr[v][0] = xf.x * yf.x;
+          pr[v][1] = xf.y * yf.y;
+          pr[v][2] = xf.z * yf.z;
+          pr[v][3] = xf.w * yf.w;
+        }
+        // stage t finalises the lanes c == t: dot = ((0 + w0*v0) + w1*v1) + ... in factor order
+        float dot = 0.0f;
+#pragma unroll
+        for (int t = 0; t < LPP; t++) {
+          float in = LPP > 1 ? pred_lane_below(dot) : 0.0f;
+          in = c == 0 ? 0.0f : in;
+#pragma unroll
+          for (int v = 0; v < VPL; v++) {
+            in = in + pr[v][0];
+            in = in + pr[v][1];
+            in = in + pr[v][2];
+            in = in + pr[v][3];
+          }
+          dot = in;
+        }
+        const float term = dot * xa[u] * xb[u];
+        if (c == LPP - 1 && ok[u]) terms[(st + u) * PPS + g] = term;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    for (int t0 = 0; t0 < cnt; t0 += 64) {
+      const float t = t0 + lane < cnt ? terms[t0 + lane] : -0.0f;
+      const float run = wave_sequential_prefix(result, t);
+      result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  }
+
+  if (lane == 0) {
+    out[r] = output_prob ? sigmoid_ref(result) : result;
+    if (rows.label) s.loss[r] = logloss_ref(rows.label[r], result);
+  }
+}
+
+// ---- the small streaming kernels -----------------------------------------------------------------
+
+// Create-time contents: the element a training engine would draw (same seed, same index), in the format.
+__global__ void serve_init_kernel(ModelDev m, float mean, float stddev, uint64_t seed) {
+  const int64_t n_lat = static_cast<int64_t>(m.n_feats) * m.row_len;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  const int64_t t0 = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  for (int64_t idx = t0; idx < n_lat; idx += stride)
+    serve_store_elem(m, idx, ftrl_rng::init_weight(seed, 1, idx, mean, stddev));
+  for (int64_t i = t0; i < m.n_feats; i += stride) m.lin_w[i] = ftrl_rng::init_weight(seed, 0, i, mean, stddev);
+}
+
+// Features [feat0, feat0 + nf) of the packed table <-> dense[nf][row_len] fp32 (lat_component_copy_kernel's
+// analogue: the table IS the reference's save order, so it is one contiguous range).
+__global__ void serve_dense_copy_kernel(ModelDev m, float *dense, int64_t feat0, int64_t nf, int to_dense) {
+  const int64_t total = nf * m.row_len, first = feat0 * m.row_len;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+    if (to_dense) dense[idx] = serve_load_elem(m, first + idx);
+    else serve_store_elem(m, first + idx, dense[idx]);
+  }
+}
+
+// The same for a list of features: ids[j] <-> dense[j][row_len] (lat_rows_copy_kernel's analogue).
+__global__ void serve_rows_copy_kernel(ModelDev m, float *dense, const int *ids, int64_t nf, int to_dense) {
+  const int64_t RL = m.row_len, total = nf * RL;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; idx < total; idx += stride) {
+    const int64_t j = idx / RL;
+    const int i = ids[j];
+    const bool in = i >= 0 && i < m.n_feats;
+    const int64_t at = static_cast<int64_t>(i) * RL + (idx - j * RL);
+    if (to_dense) dense[idx] = in ? serve_load_elem(m, at) : 0.0f;
+    else if (in) serve_store_elem(m, at, dense[idx]);
+  }
+}
+
+// ffm_engine_pack_weights: src (a whole training engine's records) -> dst (packed), one pass.  Every
+// counter on a 64-byte line of its own (kPackLine 64-bit words apart), one atomic per counter and wave.
+enum { PK_LATENT = 0, PK_INEXACT = 1, PK_TO_INF = 2, PK_TO_ZERO = 3, PK_COUNT = 4 };
+constexpr int kPackLine = 8;
+constexpr int kPackThreads = 256;
+
+__device__ __forceinline__ unsigned long long serve_wave_sum(unsigned v) {
+  unsigned long long s = v;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+  return s;
+}
+
+template <int FMT>
+__global__ __launch_bounds__(kPackThreads) void serve_pack_kernel(ModelDev src, ModelDev dst, unsigned long long *counters) {
+  const int64_t T = static_cast<int64_t>(gridDim.x) * kPackThreads;
+  const int64_t g = static_cast<int64_t>(blockIdx.x) * kPackThreads + threadIdx.x;
+  for (int64_t i = g; i < src.n_feats; i += T) dst.lin_w[i] = __builtin_nontemporal_load(src.lin_w + i);
+  if (g == 0) dst.bias3[0] = src.bias3[0];
+  // item = four consecutive elements of a feature's w row (row_len is a multiple of 4: n_factors is)
+  const int64_t RL4 = src.row_len / 4, total = static_cast<int64_t>(src.n_feats) * RL4;
+  const float4 *const rec = reinterpret_cast<const float4 *>(src.lat);
+  unsigned part[PK_COUNT] = {0u, 0u, 0u, 0u};
+  for (int64_t it = g; it < total; it += T) {
+    const int64_t f = it / RL4, v = it - f * RL4;
+    const float4 w = load_nt(rec + f * 3 * RL4 + LAT_W * RL4 + v);
+    if (FMT == SERVE_F32) {
+      store_nt(reinterpret_cast<float4 *>(dst.lat) + it, w);
+    } else {
+      const uint2 h = serve_enc16x4(w);
+      reinterpret_cast<uint2 *>(dst.lat)[it] = h;
+      const float4 d = serve_dec16x4(h);
+      const float ws[4] = {w.x, w.y, w.z, w.w}, ds[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        const bool nan = ws[c] != ws[c];
+        part[PK_INEXACT] += (!nan && __float_as_uint(ds[c]) != __float_as_uint(ws[c])) ? 1u : 0u;
+        part[PK_TO_INF] += (!nan && !isinf(ws[c]) && isinf(ds[c])) ? 1u : 0u;
+        part[PK_TO_ZERO] += (!nan && ws[c] != 0.0f && ds[c] == 0.0f) ? 1u : 0u;
+      }
+    }
+    part[PK_LATENT] += 4u;
+  }
+#pragma unroll
+  for (int k = 0; k < PK_COUNT; k++) {
+    const unsigned long long sum = serve_wave_sum(part[k]);
+    if ((threadIdx.x & 63) == 0 && sum != 0ull)
+      __hip_atomic_fetch_add(counters + k * kPackLine, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+}  // namespace ftrl_dev

@@ -15,6 +15,8 @@ MODEL_TYPES = {"LR": LR, "FM": FM, "FFM": FFM}
 FLAG_SKIP_INIT = 1
 FLAG_LEARN = 4
 FLAG_HASH_IDS = 8
+FLAG_SERVE_F32, FLAG_SERVE_F16 = 16, 32
+SERVE_FLAGS = {None: 0, "none": 0, "f32": FLAG_SERVE_F32, "f16": FLAG_SERVE_F16}
 E_INVALID, E_DEVICE, E_NOMEM, E_CAPACITY, E_UNSUPPORTED = -1, -2, -3, -4, -5  # FFM_E_*
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -57,6 +59,14 @@ class RefreshStats(ctypes.Structure):
     """struct ffm_refresh_stats (include/ffm_engine.h "Refresh")."""
     _fields_ = [(k, ctypes.c_int64) for k in ("lin_live", "lin_nonzero", "lin_moved",
                                               "lat_live", "lat_nonzero", "lat_moved")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class PackStats(ctypes.Structure):
+    """struct ffm_pack_stats (include/ffm_engine.h "Serving engines")."""
+    _fields_ = [(k, ctypes.c_int64) for k in ("n_latent", "n_inexact", "n_to_inf", "n_to_zero")]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -170,6 +180,9 @@ ABI = [
     ("ffm_engine_hash_ids_device", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, _vp]),
     ("ffm_engine_hash_ids_host", ctypes.c_int,
      [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.c_int32, _i32p, _i32p, _i32p]),
+    # weights only, for prediction (include/ffm_engine.h "Serving engines")
+    ("ffm_engine_pack_weights", ctypes.c_int, [_vp, _vp, ctypes.POINTER(PackStats)]),
+    ("ffm_engine_model_bytes", ctypes.c_int64, [_vp]),
 ]
 
 _lib = None
@@ -305,8 +318,14 @@ class Engine:
     def __init__(self, model_type="FFM", n_feats=10000, n_fields=8, n_factors=16, w_alpha=1e-4,
                  w_beta=1.0, w_l1=0.1, w_l2=5.0, init_mean=0.0, init_stddev=0.02, seed=42,
                  max_batch_rows=8192, max_batch_nnz=None, device_id=0, n_shards=1, shard_rank=0,
-                 stream=None, skip_init=False, max_row_nnz=0, learn=False, field_start=None, hash_ids=False):
+                 stream=None, skip_init=False, max_row_nnz=0, learn=False, field_start=None, hash_ids=False,
+                 serve=None):
+        """serve: None = a training engine; "f32" / "f16" = a serving engine (include/ffm_engine.h "Serving
+        engines"): bias, lin_w and a latent table of w alone in fp32 bits or IEEE binary16 -- prediction only."""
         self.lib = load_library()
+        if serve not in SERVE_FLAGS:
+            raise ValueError("serve: None, 'f32' or 'f16'")
+        self.serve = serve if SERVE_FLAGS[serve] else None
         cfg = Config()
         self.lib.ffm_engine_default_config(ctypes.byref(cfg))
         cfg.model_type = MODEL_TYPES[model_type] if isinstance(model_type, str) else int(model_type)
@@ -317,7 +336,8 @@ class Engine:
         cfg.max_batch_nnz = int(max_batch_nnz if max_batch_nnz else max_batch_rows * 64)
         cfg.device_id, cfg.n_shards, cfg.shard_rank = int(device_id), int(n_shards), int(shard_rank)
         cfg.stream = stream
-        cfg.flags = (FLAG_SKIP_INIT if skip_init else 0) | (FLAG_LEARN if learn else 0) | (FLAG_HASH_IDS if hash_ids else 0)
+        cfg.flags = ((FLAG_SKIP_INIT if skip_init else 0) | (FLAG_LEARN if learn else 0) | (FLAG_HASH_IDS if hash_ids else 0)
+                     | SERVE_FLAGS[serve])
         cfg.max_row_nnz = int(max_row_nnz)
         self._field_start = None
         if field_start is not None:
@@ -353,7 +373,46 @@ class Engine:
                     vec_w=np.zeros((nf, L), np.float32), vec_n=np.zeros((nf, L), np.float32),
                     vec_z=np.zeros((nf, L), np.float32))
 
+    def get_weights(self):
+        """dict(bias, lin_w, vec_w): the weights alone (a serving engine: its table decoded to fp32)."""
+        b = np.zeros(1, np.float32)
+        lw = np.zeros(self.n_feats, np.float32)
+        vw = np.zeros((self.n_feats, self.row_len), np.float32)
+        self._check(self.lib.ffm_engine_get_weights(self.h, _f(b), _f(lw), _f(vw) if self.row_len else None))
+        return dict(bias=b, lin_w=lw, vec_w=vw)
+
+    def set_weights(self, bias=None, lin_w=None, vec_w=None):
+        """Overwrites the given weights (fp32 host arrays; a serving engine rounds vec_w to its format)."""
+        c = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
+        b, lw, vw = c(bias), c(lin_w), c(vec_w)
+        self._check(self.lib.ffm_engine_set_weights(self.h, _f(b.reshape(-1)[:1].copy()) if b is not None else None,
+                                                    _f(lw), _f(vw) if vw is not None and vw.size else None))
+
+    def model_bytes(self):
+        """Bytes of HBM requested for the model arrays: bias, linear, latent (ffm_engine_model_bytes)."""
+        return int(self.lib.ffm_engine_model_bytes(self.h))
+
+    def pack_from(self, src):
+        """This serving engine's weights from a training engine of the same shape on the same device, in one
+        device pass (ffm_engine_pack_weights): src's STORED bias, lin_w and w -- src.refresh_weights() first
+        when the learned model is wanted.  Returns dict(n_latent, n_inexact, n_to_inf, n_to_zero)."""
+        st = PackStats()
+        self._check(self.lib.ffm_engine_pack_weights(self.h, src.h, ctypes.byref(st)))
+        return st.as_dict()
+
+    def load_sparse_weights(self, d):
+        """sparse_state() of a training engine of the same config into this SERVING engine: the listed
+        features' lin_w and vec_w (rounded to the format) and the bias; (n, z) are not looked at.  The
+        engine must still hold its create-time contents -- which are the training engine's, rounded."""
+        ids = np.ascontiguousarray(d["ids"], np.int32)
+        if ids.size:
+            self.set_rows(ids, {k: d[k] for k in ("lin_w", "vec_w") if k in d})
+        b = np.ascontiguousarray(d["bias3"], np.float32)
+        self._check(self.lib.ffm_engine_set_weights(self.h, _f(b[0:1].copy()), None, None))
+
     def get_state(self):
+        if self.serve:
+            raise EngineError(E_UNSUPPORTED, "a serving engine holds no accumulators: get_weights() reads what it stores")
         st = self.zero_state()
         b = np.zeros(3, np.float32)
         vw = st["vec_w"] if self.row_len else None
@@ -382,8 +441,9 @@ class Engine:
         """State of the listed features only: dict of lin_* [n] and vec_* [n, row_len]."""
         ids = np.ascontiguousarray(ids, np.int32)
         n, L = ids.size, self.row_len
-        out = {k: np.zeros((n, L) if k.startswith("vec") else n, np.float32) for k in self.ROW_KEYS}
-        args = [_f(out[k]) if out[k].size else None for k in self.ROW_KEYS]
+        keys = ("lin_w", "vec_w") if self.serve else self.ROW_KEYS  # (a serving engine: decoded w, no n / z)
+        out = {k: np.zeros((n, L) if k.startswith("vec") else n, np.float32) for k in keys}
+        args = [_f(out[k]) if k in out and out[k].size else None for k in self.ROW_KEYS]
         self._check(self.lib.ffm_engine_get_rows(self.h, n, _i(ids), *args))
         return out
 
@@ -424,6 +484,8 @@ class Engine:
         """The model as a delta to a fresh engine of the same config: dict(ids, bias3, ROW_KEYS arrays
         of the changed features).  load_sparse_state() of it on such an engine reproduces this one bit
         for bit."""
+        if self.serve:
+            raise EngineError(E_UNSUPPORTED, "a serving engine holds no accumulators: the sparse checkpoint is a training engine's")
         ids = self.changed_features()
         out = dict(ids=ids, bias3=self._bias3())
         out.update(self.get_rows(ids))
@@ -726,7 +788,7 @@ class Group:
         self.engines = []
         for r in range(self.size):
             e = Engine.__new__(Engine)
-            e.lib, e.cfg, e.model_type = self.lib, cfg, cfg.model_type
+            e.lib, e.cfg, e.model_type, e.serve = self.lib, cfg, cfg.model_type, None
             e.h = _vp(self.lib.ffm_group_engine(self.h, r))
             e._field_start = self._field_start
             e.n_feats, e.n_fields, e.n_factors = cfg.n_feats, cfg.n_fields, cfg.n_factors

@@ -77,7 +77,14 @@ const std::string_view cmd_help =
     "              [0, n_feats) with --field_ranges none, into its field's own range with uniform, which lets --n_gpus N\n"
     "              train any libffm file and gives one GPU the per-field sort and the regular-block forms; LR / FM hash\n"
     "              libsvm ids into [0, n_feats).  Negative ids (FFM: and fields outside [0, n_fields)) stay dropped.  The\n"
-    "              model, the checkpoint and every id printed are hashed ids; --n_feats bounds the model, not the data\tdefault:false\n";
+    "              model, the checkpoint and every id printed are hashed ids; --n_feats bounds the model, not the data\tdefault:false\n"
+    "--serve_weights <none|f32|f16>: score a saved model from a serving engine, which holds the weights alone (no n, z):\n"
+    "              f32 = the same fp32 bits in a third of the memory, the same predictions bit for bit; f16 = IEEE half\n"
+    "              precision (round to nearest even) in a sixth of the memory, half the bytes read per prediction.  Only\n"
+    "              with --resume_from ck --n_epochs 0 (then --predict_data / --predict_out, --predict_output, --metrics auc\n"
+    "              and --hash_feats as always); FFM only, one GPU, rows of at most 128 entries, no training: refused with\n"
+    "              --n_epochs > 0, --model_path, --checkpoint_path, --n_gpus > 1 and --refresh_weights true (write the\n"
+    "              checkpoint with --refresh_weights true instead).  Prints `serving weights: <fmt>, <bytes> bytes of model`\tdefault:none\n";
 
 static bool assign_bool(std::string arg) {
   std::transform(arg.begin(), arg.end(), arg.begin(), [](unsigned char c) { return std::tolower(c); });
@@ -153,6 +160,10 @@ void config_options::parse_option(int argc, char *argv[]) {
       weights_given = true;
     }
     else if (k == "--weight_data") { weight_path = v; weights_given = true; }
+    else if (k == "--serve_weights") {
+      if (v != "none" && v != "f32" && v != "f16") throw std::invalid_argument("--serve_weights takes none, f32 or f16");
+      serve_weights = v;
+    }
     else if (k == "--predict_data") predict_path = v;
     else if (k == "--predict_out") predict_out = v;
     else if (k == "--predict_output") {
@@ -163,6 +174,18 @@ void config_options::parse_option(int argc, char *argv[]) {
   }
   if (predict_path.empty() != predict_out.empty())
     throw std::invalid_argument("--predict_data and --predict_out go together: one was given without the other");
+  if (serve_weights != "none") {
+    // a serving engine holds no accumulators: it can only score a saved model (refused here, before a device is opened)
+    const std::string what = "--serve_weights " + serve_weights + " ";
+    if (resume_from.empty()) throw std::invalid_argument(what + "scores a saved model: it needs --resume_from <checkpoint> --n_epochs 0");
+    if (epoch > 0) throw std::invalid_argument(what + "cannot train: it needs --n_epochs 0 (got --n_epochs " + std::to_string(epoch) + ")");
+    if (!model_path.empty()) throw std::invalid_argument(what + "writes no model: --model_path is not allowed with it");
+    if (!checkpoint_path.empty()) throw std::invalid_argument(what + "holds no accumulators to checkpoint: --checkpoint_path is not allowed with it");
+    if (n_gpus > 1) throw std::invalid_argument(what + "is one whole model on one GPU: --n_gpus > 1 is not allowed with it");
+    if (refresh_weights)
+      throw std::invalid_argument(what + "holds no accumulators to refresh from: write the checkpoint with --refresh_weights true instead");
+    if (model_type != "FFM") throw std::invalid_argument(what + "is for FFM models only (got --model_type " + model_type + ")");
+  }
   // (--n_epochs 0 with a file to score needs no training file: the format is then the scored file's)
   file_type = detect_file_type(train_path.empty() && epoch == 0 && !predict_path.empty() ? predict_path : train_path);
   if (model_type == "FFM" && file_type != "libffm") {

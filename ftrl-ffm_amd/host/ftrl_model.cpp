@@ -53,6 +53,18 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
   // get/set_latent_rows, pull/push_linear, the model files and checkpoints speak MODEL (hashed) ids
   if (opt.hash_feats) cfg.flags |= FFM_FLAG_HASH_IDS;
   hash_ids_ = opt.hash_feats;
+  // --serve_weights: a serving engine (include/ffm_engine.h "Serving engines") -- the weights alone, rows of at
+  // most 128 entries, prediction only; load_checkpoint then passes the saved w and nothing else
+  serving_ = opt.serve_weights != "none";
+  if (serving_) {
+    if (opt.serve_weights != "f32" && opt.serve_weights != "f16") throw std::invalid_argument("serve_weights: none, f32 or f16");
+    if (opt.n_gpus > 1) throw std::invalid_argument("a serving engine is one whole model on one GPU (n_gpus == 1)");
+    cfg.flags |= opt.serve_weights == "f16" ? FFM_FLAG_SERVE_F16 : FFM_FLAG_SERVE_F32;
+    max_row_nnz_ = 128;
+    max_nnz_ = static_cast<int>(std::min<long long>(std::max<long long>(256ll * max_rows_, max_row_nnz_), 1ll << 28));
+    cfg.max_batch_nnz = max_nnz_;
+    cfg.max_row_nnz = max_row_nnz_;
+  }
   n_gpus_ = std::max(1, opt.n_gpus);
   seed_ = cfg.seed;
   init_mean_ = cfg.init_mean;
@@ -102,6 +114,8 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
     if (rc == FFM_E_INVALID) throw std::invalid_argument(ffm_engine_last_error());
     check(rc, "ffm_engine_create");
   }
+  if (serving_)
+    std::printf("serving weights: %s, %lld bytes of model\n", opt.serve_weights.c_str(), static_cast<long long>(ffm_engine_model_bytes(eng_)));
   row_len_ = ffm_engine_row_len(eng_);
   lin_w.resize(static_cast<size_t>(n_feats));
   vec_w.owner_ = this;
@@ -673,14 +687,15 @@ FtrlModel::TrainProgress FtrlModel::load_checkpoint(std::string_view file_name) 
     throw std::runtime_error(name + ": was saved " + ((h.flags & FFM_FLAG_HASH_IDS) ? "with" : "without") +
                              " --hash_feats, this model is the other variant: the resumed run would not be the interrupted one");
   int64_t touched = 0;
-  check(ffm_engine_changed_features(eng_, nullptr, 0, &touched), "ffm_engine_changed_features");
+  // (a serving model is built and loaded once by the CLI; it has no scan to prove that it is fresh)
+  if (!serving_) check(ffm_engine_changed_features(eng_, nullptr, 0, &touched), "ffm_engine_changed_features");
   if (touched != 0)
     throw std::runtime_error(name + ": a sparse checkpoint loads into a fresh model only; " + std::to_string(touched) +
                              " features of this one have changed already");
   float b3[3];
   for (int i = 0; i < 3; i++) std::memcpy(&b3[i], &h.bias_bits[i], sizeof(float));
   check(ffm_engine_set_weights(eng_, &b3[0], nullptr, nullptr), "ffm_engine_set_weights");
-  check(ffm_engine_set_state(eng_, &b3[1], &b3[2], nullptr, nullptr, nullptr, nullptr), "ffm_engine_set_state");
+  if (!serving_) check(ffm_engine_set_state(eng_, &b3[1], &b3[2], nullptr, nullptr, nullptr, nullptr), "ffm_engine_set_state");
   const size_t rl = static_cast<size_t>(row_len_), n = r.ids().size();
   const size_t cap = std::min(static_cast<size_t>(h.chunk), std::max<size_t>(n, 1));
   std::vector<float> lin(3 * cap), vec(3 * cap * rl);
@@ -689,6 +704,9 @@ FtrlModel::TrainProgress FtrlModel::load_checkpoint(std::string_view file_name) 
     float *lw = lin.data(), *ln = lw + c, *lz = ln + c;
     float *vw = rl ? vec.data() : nullptr, *vn = rl ? vw + c * rl : nullptr, *vz = rl ? vn + c * rl : nullptr;
     r.chunk(lw, ln, lz, vw, vn, vz);
+    if (serving_)  // only the ids, lin_w and vec_w (rounded to the engine's format on the device)
+      check(ffm_engine_set_rows(eng_, static_cast<int32_t>(c), r.ids().data() + j0, lw, nullptr, nullptr, vw, nullptr, nullptr), "ffm_engine_set_rows");
+    else
     check(ffm_engine_set_rows(eng_, static_cast<int32_t>(c), r.ids().data() + j0, lw, ln, lz, vw, vn, vz), "ffm_engine_set_rows");
     j0 += c;
   }

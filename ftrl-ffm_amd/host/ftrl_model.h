@@ -198,6 +198,7 @@ class FtrlModel {
   uint64_t seed_ = 0;
   float init_mean_ = 0.0f, init_stddev_ = 0.0f;
   int32_t flags_ = 0;
+  bool serving_ = false;   // --serve_weights f32 | f16: a serving engine behind this model (prediction only)
   bool hash_ids_ = false;  // --hash_feats: ids >= n_feats are not erased on the host, the device hashes them
   CsrBlock one_;  // scratch for the one-row shims
   // engine capacities chosen at construction; blocks beyond max_nnz_ are split into several

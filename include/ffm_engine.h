@@ -85,7 +85,7 @@ typedef struct ffm_engine_config {
   int32_t shard_rank;      /* 0 */
   void *stream;            /* hipStream_t to run on; NULL = the engine creates its own */
   int32_t flags;           /* FFM_FLAG_* */
-  int32_t max_row_nnz;     /* longest row a call may hold (LDS staging of the row kernels); 0 = 1024 */
+  int32_t max_row_nnz;     /* longest row a call may hold (LDS staging of the row kernels); 0 = 1024 (serving engines: 128) */
   /* Per-field id ranges: field f owns the ids [field_start[f], field_start[f+1]), n_fields + 1
    * ascending values from 0 to n_feats (python/generate_data.py:272-306 and the bundled data lay
    * ids out like this).  NULL = unknown.  With it a sharded engine stores only the records of the
@@ -111,8 +111,10 @@ enum {
                            * g2*g2 instead of g2*g1 -- so that FM / FFM factors actually train.
                            * Off: the reference bit for bit.  (Flag value 2 was round 1's
                            * optional fused row kernel: measured slower, removed.) */
-  FFM_FLAG_HASH_IDS = 8   /* feature ids of HOST rows are hashed into their field's id range on the device
+  FFM_FLAG_HASH_IDS = 8,  /* feature ids of HOST rows are hashed into their field's id range on the device
                            * before any kernel reads them: "Hashed ids" below */
+  FFM_FLAG_SERVE_F32 = 16, /* a SERVING engine: weights only, for prediction -- "Serving engines" below; */
+  FFM_FLAG_SERVE_F16 = 32  /* its latent table in fp32 bits or in IEEE binary16 (both: FFM_E_INVALID) */
 };
 
 void ffm_engine_default_config(ffm_engine_config *cfg);
@@ -630,6 +632,57 @@ int ffm_engine_hash_ids_host(int32_t model_type, int32_t n_feats, int32_t n_fiel
 typedef struct { int64_t lin_live, lin_nonzero, lin_moved, lat_live, lat_nonzero, lat_moved; } ffm_refresh_stats;
 int ffm_engine_refresh_weights(ffm_engine *e, ffm_refresh_stats *out);
 int ffm_group_refresh_weights(ffm_group *g, ffm_refresh_stats *out);
+
+/* ---- Serving engines: FFM_FLAG_SERVE_F32 / FFM_FLAG_SERVE_F16 -----------------------------------------
+ * predict() reads the stored w and nothing else (ffm.cpp:51-70), but a training engine's latent record is
+ * [n][z][w]: scoring a saved model holds three times the bytes it reads.  With one of these flags
+ * ffm_engine_create makes an engine that stores the bias (1 float), lin_w[n_feats] (fp32) and a latent table
+ * [n_feats][n_fields * n_factors] of w ALONE -- no n or z anywhere, linear part included -- in
+ *   FFM_FLAG_SERVE_F32   the training engine's fp32 bits: a third of the memory, bit-identical predictions;
+ *   FFM_FLAG_SERVE_F16   IEEE binary16: a sixth of the memory, half the bytes per prediction.
+ * LIMITS  FFM only, one whole model on one device (n_shards == 1, not inside ffm_group_create), n_factors in
+ *         {4, 8, 16, 32, 64}: anything else is FFM_E_UNSUPPORTED.  Rows of at most 128 entries: max_row_nnz == 0
+ *         means 128 here, a larger value is FFM_E_INVALID -- a serving engine has no kernel for longer rows (a
+ *         longer host row is FFM_E_CAPACITY before anything is queued; a longer device row voids its block as
+ *         usual: NaN outputs, FFM_E_CAPACITY at the next sync).  No training.  field_start is accepted and
+ *         used for FFM_FLAG_HASH_IDS's per-field ranges only.
+ * fp16    the contract: w -> binary16 by round to nearest even, subnormals kept, finite values beyond the
+ *         half range to +-inf, NaN stays NaN (payload unspecified) -- numpy's astype(float16); decoding is the
+ *         exact half -> float conversion.  A prediction is, bit for bit, the fp32 arithmetic of
+ *         ffm_engine_predict_batch on the DECODED weights, in the same order.  The linear weights stay fp32.
+ * create  every element is what a training engine of the same config would draw
+ *         (ffm_engine_init_weights_host: same seed and index), rounded to the format; FFM_FLAG_SKIP_INIT gives
+ *         zero bits.  So a sparse checkpoint -- a delta to a fresh engine -- means on a serving engine what it
+ *         means on a training engine: set_rows its ids' lin_w / vec_w, set_weights its bias.
+ * works   every prediction entry point, unchanged: ffm_engine_predict_batch, _device, _async, _async_scores
+ *         (zero_copy included), ffm_engine_predict_finish_device; FFM_METRIC_EVAL; FFM_FLAG_HASH_IDS and
+ *         ffm_engine_hash_ids_device; field == NULL rows; ffm_engine_sync, the profile calls (the predict
+ *         kernel's label is "serve_wave_kernel"), ffm_engine_train_flush as the evaluation flush.
+ *         ffm_engine_set_weights / set_rows take fp32 host arrays as always (w is rounded to the format on the
+ *         device); ffm_engine_get_weights / get_rows return the decoded fp32 values.
+ * refused with FFM_E_UNSUPPORTED ("a serving engine holds no accumulators"): every training entry point
+ *         (synchronous, device, staged, pipelined, weighted, forward / update), ffm_engine_prepare_device,
+ *         ffm_engine_set_state / get_state with any non-NULL pointer, set_rows / get_rows with a non-NULL n or
+ *         z pointer, ffm_engine_changed_features, ffm_engine_refresh_weights, ffm_engine_fill_state.
+ * A training engine is unchanged by all this: the same bytes, kernels and launches. */
+
+/* src's stored bias, lin_w and the w component of every latent record into dst, in one streaming pass on the
+ * device (no host copy of the model).  dst: a serving engine; src: an unsharded FFM training engine of the
+ * same (n_feats, n_fields, n_factors) on the same device; anything else is FFM_E_INVALID.  It copies the
+ * STORED w -- one update behind the accumulators ("Refresh" above): call ffm_engine_refresh_weights(src)
+ * first when the learned model is wanted.  src is drained first as ffm_engine_refresh_weights drains it and
+ * is not written; synchronous.  Counters (all but n_latent are 0 for FFM_FLAG_SERVE_F32):
+ *   n_latent   latent elements written;
+ *   n_inexact  elements whose decoded value differs in bits from the source (NaN to NaN does not count);
+ *   n_to_inf   finite elements that became infinite;   n_to_zero  nonzero elements that became +-0.
+ * out may be NULL.  The counter buffer (256 bytes of HBM) is allocated by dst's first call. */
+typedef struct { int64_t n_latent, n_inexact, n_to_inf, n_to_zero; } ffm_pack_stats;
+int ffm_engine_pack_weights(ffm_engine *dst, ffm_engine *src, ffm_pack_stats *out);
+
+/* Bytes of HBM requested for the model arrays (bias, linear, latent) of any engine: an unsharded FFM
+ * training engine 12 + 12 * n_feats + 12 * n_feats * row_len, a serving engine 4 + 4 * n_feats +
+ * B * n_feats * row_len with B = 4 (fp32) or 2 (fp16); a shard counts the records it stores. */
+int64_t ffm_engine_model_bytes(const ffm_engine *e);
 
 #ifdef __cplusplus
 }
