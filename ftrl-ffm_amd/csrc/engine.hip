@@ -434,6 +434,7 @@ struct ffm_engine {
   int row_threads = kRowThreads;  // workgroup size of the FFM row kernel (FFM_ROW_THREADS)
   int row_park = -1;         // FFM_ROW_PARK: bytes of w the row kernel parks in LDS (-1: what the budget leaves)
   int row_park_budget = 0;   // FFM_ROW_PARK_BUDGET: the row kernel's LDS budget for parking (0: 24 KB)
+  int row_hold = -1;         // FFM_ROW_HOLD: (n, z) vectors per thread the row kernel holds in registers (-1: chosen by the launcher, 0: none)
   bool serial = false;  // FFM_ENGINE_SERIAL=1: no side streams (per-kernel timings without overlap)
   // ---- staging thread ------------------------------------------------------------------------
   // The GPU submissions of a staged block (its upload kernel and the ~10 launches of its grouping,
@@ -741,6 +742,7 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   if (const char *sv = std::getenv("FFM_ROW_THREADS")) e->row_threads = std::max(64, std::min(kRowMaxThreads, std::atoi(sv) / 64 * 64));
   if (const char *sv = std::getenv("FFM_ROW_PARK")) e->row_park = std::atoi(sv);
   if (const char *sv = std::getenv("FFM_ROW_PARK_BUDGET")) e->row_park_budget = std::atoi(sv);
+  if (const char *sv = std::getenv("FFM_ROW_HOLD")) e->row_hold = std::max(0, std::atoi(sv));
   // (the lean once-only kernel of a compact shard holds six waves per SIMD: 1152 workgroups
   // measured 2.5 % per step better than 768 on an 8-GPU rank's blocks)
   if (cfg->n_shards > 1) e->grid_single = 1152;
@@ -1137,6 +1139,14 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
     if (lds > 32 * 1024 || park_budget > 32 * 1024) {
       const int bytes = static_cast<int>(std::max(lds, park_budget));
       TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 2, const float *>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 4, const float *>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 6, const float *>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 8, const float *>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
       TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
       TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
       TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));

@@ -105,6 +105,20 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float
     // both read when the engine is created: test_row_kernel_lds_parking_is_bit_identical pins 0 / 96 /
     // 1024 bytes / the default, test_gpu_launch_geometry.py also 16 bytes (one vector), 96 bytes at 64
     // threads and a 48 KB budget (above 32 KB).
+    //
+    // Held (n, z) (kernels_row.h, HOLD): the in-row update takes the first HOLD vectors each thread refreshed
+    // from registers.  HOLD is the smallest of 2 / 4 / 6 / 8 that covers the longest row's once-only vectors per
+    // thread, at most kRowHoldDefault (the measured best: profiles/row_hold.md), so that short records (k = 4,
+    // few fields) hold what they need and no more; FFM_ROW_HOLD=n (read when the engine is created) replaces
+    // that count, 0 = the kernel that holds nothing.  The parking budget does not follow the occupancy of the
+    // instantiation: more LDS per row at fewer rows per CU measured slower at every count.
+    int hold = 0;
+    if (refreshed == 3 && train && vec4 && own_tg) {
+      const long long vecs = static_cast<long long>(row_cap) * (e->m.rec_slots * (e->m.n_factors / 4));
+      const long long need = (vecs + e->row_threads - 1) / e->row_threads;
+      const long long want = e->row_hold >= 0 ? e->row_hold : std::min<long long>(need, kRowHoldDefault);
+      hold = want <= 0 ? 0 : want <= 2 ? 2 : want <= 4 ? 4 : want <= 6 ? 6 : 8;
+    }
     int park = 0;
     size_t shmem_park = shmem;
     if (refreshed == 3) {
@@ -117,14 +131,23 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float
       if (park > 0) shmem_park = base + 16 * static_cast<size_t>(park);
     }
     if (train && vec4) {
-      if (own_tg && weight)
-        LAUNCH(e, kid, (ffm_row_kernel<true, true, true, const float *>), rows.n_rows, e->row_threads, shmem_park, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, park, weight);
-      else if (own_tg)
-        LAUNCH(e, kid, (ffm_row_kernel<true, true, true>), rows.n_rows, e->row_threads, shmem_park, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, park);
+#define ROW_LAUNCH_HOLD(H)                                                                                             \
+  do {                                                                                                                 \
+    if (weight)                                                                                                        \
+      LAUNCH(e, kid, (ffm_row_kernel<true, true, true, H, const float *>), rows.n_rows, e->row_threads, shmem_park, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, park, weight); \
+    else                                                                                                               \
+      LAUNCH(e, kid, (ffm_row_kernel<true, true, true, H>), rows.n_rows, e->row_threads, shmem_park, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, park); \
+  } while (0)
+      if (own_tg && hold == 8) ROW_LAUNCH_HOLD(8);
+      else if (own_tg && hold == 6) ROW_LAUNCH_HOLD(6);
+      else if (own_tg && hold == 4) ROW_LAUNCH_HOLD(4);
+      else if (own_tg && hold == 2) ROW_LAUNCH_HOLD(2);
+      else if (own_tg) ROW_LAUNCH_HOLD(0);
+#undef ROW_LAUNCH_HOLD
       else  // a shard: the logit is whole only after the all-reduce
         LAUNCH(e, kid, (ffm_row_kernel<true, true, false>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, 0, 0, 0);
     }
-    else if (train && own_tg && weight) LAUNCH(e, kid, (ffm_row_kernel<true, false, true, const float *>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, 0, weight);
+    else if (train && own_tg && weight) LAUNCH(e, kid, (ffm_row_kernel<true, false, true, 0, const float *>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, 0, weight);
     else if (train) LAUNCH(e, kid, (ffm_row_kernel<true, false>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, 0);
     else if (launch_predict_waves(e, rows, row_cap, out, output_prob)) {
       // rows that may be longer than a wave stages (kernels_predict.h): the workgroup-per-row kernel

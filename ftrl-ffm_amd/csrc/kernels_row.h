@@ -43,6 +43,20 @@ constexpr int kRowThreads = 256;
 #endif
 constexpr int kRowMaxThreads = FFM_ROW_MAXT;  // launch bound of the FFM row kernel (experiments: 512 / 1024)
 constexpr int kTermsCap = 2048;  // most pair terms staged in LDS per pass
+// Waves per SIMD of the row kernel's instantiation that holds `hold` (n, z) vectors per thread in registers
+// (8 VGPRs each): by themselves the instantiations take 80 / 95 / 111 / 128 VGPRs at 2 / 4 / 6 / 8, so none of
+// them spills at its bound of six / five / four / four waves.
+#ifndef FFM_ROW_HOLD_WAVES
+#define FFM_ROW_HOLD_WAVES(hold) ((hold) <= 2 ? 6 : (hold) <= 4 ? 5 : 4)
+#endif
+__host__ __device__ constexpr int row_hold_waves(int hold) { return FFM_ROW_HOLD_WAVES(hold); }
+// Most vectors per thread the launcher chooses to hold by itself (0: never; FFM_ROW_HOLD still selects one).
+// Two: the only count that keeps six rows per CU, and rows per CU are worth more than held vectors
+// (profiles/row_hold.md: every count at five or four rows measured slower than holding nothing at six).
+#ifndef FFM_ROW_HOLD_DEFAULT
+#define FFM_ROW_HOLD_DEFAULT 2
+#endif
+constexpr int kRowHoldDefault = FFM_ROW_HOLD_DEFAULT;
 // Terms buffer a row kernel actually needs (a multiple of 4, at most kTermsCap): all pairs of the
 // longest admissible row -- or, on a shard, its entries times the slots of a record -- or the
 // FM factor count.  Short rows then cost little LDS and many more of them are resident per CU.
@@ -226,7 +240,8 @@ __device__ __forceinline__ float row_weight(int r, const float *weight) { return
 // more than six waves allow, and its launch is 30 us longer at the headline shape; held to 80 it spills
 // six VGPRs to 12 bytes of scratch and costs nothing measurable (profiles/sample_weights.md).  A
 // minimum of 0 emits no attribute: the unweighted instantiations carry none, as before.
-#define FFM_ROW_OCC __attribute__((amdgpu_waves_per_eu(sizeof...(W) > 0 ? 6 : 0)))
+// A holding instantiation (HOLD > 0, below) is bound to the waves its held registers are meant to leave.
+#define FFM_ROW_OCC __attribute__((amdgpu_waves_per_eu(HOLD > 0 ? row_hold_waves(HOLD) : (sizeof...(W) > 0 ? 6 : 0))))
 #endif
 // WHOLE: the kernel has the whole logit (one shard): it also produces tmp_grad / loss and may
 // apply the once-only features' update (own_tg, refreshed == 3).  A shard's instantiation leaves all
@@ -234,7 +249,16 @@ __device__ __forceinline__ float row_weight(int r, const float *weight) { return
 // W...: nothing, or `const float *` -- per-row sample weights (include/ffm_engine.h "Sample weights"):
 // tmp_grad and the row's loss term are scaled by weight[r].  A compile-time variant whose extra
 // argument exists only there, so that the unweighted instantiations are what they always were.
-template <bool TRAIN, bool VEC4, bool WHOLE = TRAIN, typename... W>
+//
+// HOLD (TRAIN && VEC4 && WHOLE only): the (n, z) of the first HOLD vectors a thread refreshes (items
+// threadIdx.x + u * blockDim.x, u < HOLD, of the row's once-only records) stay in registers -- 8 VGPRs a
+// vector -- through the pair phase, and the in-row update (refreshed == 3) takes them from there instead of
+// loading them a second time: nobody else touches a once-only feature's record inside the block, so they
+// are the bits the second read would bring (~534 MB of the 2.5 GB a C5 launch moves past the L2).  Items
+// beyond HOLD * blockDim.x take the re-read path.  A holding instantiation is bound to row_hold_waves(HOLD)
+// waves per SIMD (= rows per CU at 256 threads).  HOLD = 0 is the kernel without any of it.
+// profiles/row_hold.md.
+template <bool TRAIN, bool VEC4, bool WHOLE = TRAIN, int HOLD = 0, typename... W>
 __global__ __launch_bounds__(kRowMaxThreads) FFM_ROW_OCC void ffm_row_kernel(ModelDev m, Rows rows, Scratch s,
                                                               int max_row_nnz, float *out,
                                                               int output_prob, int refreshed,
@@ -242,6 +266,11 @@ __global__ __launch_bounds__(kRowMaxThreads) FFM_ROW_OCC void ffm_row_kernel(Mod
                                                               W... weight) {
   constexpr bool WGT = sizeof...(W) > 0;
   static_assert(!WGT || (TRAIN && WHOLE), "weights go to the kernel that produces tmp_grad");
+  static_assert(HOLD == 0 || (TRAIN && VEC4 && WHOLE), "only the kernel with the in-row update holds (n, z)");
+  // held (n, z): slot u is item threadIdx.x + u * blockDim.x; bit u of held: the slot holds a live vector.
+  // (Indexed by unrolled constants only, so that they are registers and not scratch.)
+  float4 hn[HOLD > 0 ? HOLD : 1], hz[HOLD > 0 ? HOLD : 1];
+  unsigned held = 0;
   const int own_tg = WHOLE ? own_tg_arg : 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int s_nv, s_ns;
@@ -344,12 +373,56 @@ __global__ __launch_bounds__(kRowMaxThreads) FFM_ROW_OCC void ffm_row_kernel(Mod
 #define FFM_REFRESH_FLY 4
 #endif
       // (a shard's instantiation: two, its records are short -- 49 VGPRs instead of 77, a wave more per SIMD)
-      constexpr int kRefreshFly = WHOLE ? FFM_REFRESH_FLY : 2;
+      // (a holding instantiation: two as well, for what is left beyond its held slots)
+      constexpr int kRefreshFly = WHOLE && HOLD == 0 ? FFM_REFRESH_FLY : 2;
       const int RL4 = RL >> 2, k4 = k >> 2;
       const int per = record_span(m, k4);  // vectors walked per record
       const float inv_per = 1.0f / static_cast<float>(per), inv_k4 = 1.0f / static_cast<float>(k4);
       const int total = s_ns * per;
-      for (int t0 = threadIdx.x; t0 < total; t0 += kRefreshFly * blockDim.x) {
+      if constexpr (HOLD > 0) {
+        // the held slots: all of the thread's (n, z) loads are issued before the first W(n, z)
+        float4 *hwp[HOLD];
+#pragma unroll
+        for (int u = 0; u < HOLD; u++) {
+          const int t = threadIdx.x + u * blockDim.x;
+          hwp[u] = nullptr;
+          if (t >= total) continue;
+          int j = static_cast<int>((t + 0.5f) * inv_per);
+          j += (j + 1) * per <= t ? 1 : (j * per > t ? -1 : 0);
+          const int a = lds.slist[j];
+          const int c4 = t - j * per;
+          int sl = static_cast<int>((c4 + 0.5f) * inv_k4);
+          sl += (sl + 1) * k4 <= c4 ? 1 : (sl * k4 > c4 ? -1 : 0);
+          const int fa = lds.field[a];
+          const int fp = walk_field(m, fa, sl);
+          const bool touched = fp >= 0 && (lds.fcnt[fp] - (fa == fp ? 1 : 0)) > 0 && owns_pair(m, fa, fp);
+          if (touched) {
+            float4 *row = reinterpret_cast<float4 *>(lat_row(m, lds.feat[a], fa));
+            if (FFM_ROW_NT & 2) {
+              hn[u] = load_nt(row + LAT_N * RL4 + c4);
+              hz[u] = load_nt(row + LAT_Z * RL4 + c4);
+            } else {
+              hn[u] = row[LAT_N * RL4 + c4];
+              hz[u] = row[LAT_Z * RL4 + c4];
+            }
+            hwp[u] = row + LAT_W * RL4 + c4;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < HOLD; u++)
+          if (hwp[u]) {
+            // (the learning variant's old w: asked for here, not held beside the (n, z) of every slot)
+            const float4 wn = latent_weight4(m.h, hn[u], hz[u], m.h.learn ? *hwp[u] : hn[u]);
+            if (FFM_ROW_NT & 16) store_nt(hwp[u], wn);
+            else *hwp[u] = wn;
+            const int t = threadIdx.x + u * blockDim.x;
+            if (t < park_vecs) park_w[t] = wn;
+            held |= 1u << u;
+          }
+      }
+      int t_rest = threadIdx.x;  // the first item beyond the held slots
+      if constexpr (HOLD > 0) t_rest += HOLD * blockDim.x;
+      for (int t0 = t_rest; t0 < total; t0 += kRefreshFly * blockDim.x) {
         float4 *wp[kRefreshFly];
         float4 n4[kRefreshFly], z4[kRefreshFly], w4[kRefreshFly];
 #pragma unroll
@@ -610,7 +683,80 @@ __global__ __launch_bounds__(kRowMaxThreads) FFM_ROW_OCC void ffm_row_kernel(Mod
       const int per = record_span(m, k4);
       const float inv_per = 1.0f / static_cast<float>(per), inv_k4 = 1.0f / static_cast<float>(k4);
       const int total = s_ns * per;
-      for (int t0 = threadIdx.x; t0 < total; t0 += kUpdFly * blockDim.x) {
+      if constexpr (HOLD > 0) {
+        // The held slots: (n, z) are in registers, so what is left to fetch is the own w (LDS where parked)
+        // and the partner's w, one vector's arithmetic after the other as below.  FFM_ROW_HOLD_AHEAD=1 asks
+        // for both kLag = one slot ahead of the arithmetic (buffer u & 1): 10-12 VGPRs, which cost every count a
+        // wave per SIMD (86 / 107 / 123 / 140 VGPRs) and measured no faster at equal rows per CU.
+#ifndef FFM_ROW_HOLD_AHEAD
+#define FFM_ROW_HOLD_AHEAD 0
+#endif
+        constexpr int kLag = FFM_ROW_HOLD_AHEAD ? 1 : 0;
+        float4 *rp[2];
+        float4 w4[2], vp[2];
+        int ia[2], ifp[2], ikq[2];
+#pragma unroll
+        for (int u = 0; u < HOLD + kLag; u++) {
+          if (u < HOLD) {
+            const int c = u & kLag;
+            rp[c] = nullptr;
+            if ((held >> u) & 1u) {
+              const int t = threadIdx.x + u * blockDim.x;
+              int j = static_cast<int>((t + 0.5f) * inv_per);
+              j += (j + 1) * per <= t ? 1 : (j * per > t ? -1 : 0);
+              const int a = lds.slist[j];
+              const int c4 = t - j * per;
+              int sl = static_cast<int>((c4 + 0.5f) * inv_k4);
+              sl += (sl + 1) * k4 <= c4 ? 1 : (sl * k4 > c4 ? -1 : 0);
+              const int fa = lds.field[a];
+              const int fp = walk_field(m, fa, sl);  // (held: the slot is live, fp >= 0 with an entry in the row)
+              float4 *row = reinterpret_cast<float4 *>(lat_row(m, lds.feat[a], fa));
+              if (t < park_vecs) w4[c] = park_w[t];
+              else w4[c] = (FFM_ROW_NT & 8) ? load_nt(row + LAT_W * RL4 + c4) : row[LAT_W * RL4 + c4];
+              rp[c] = row + c4;
+              ia[c] = a;
+              ifp[c] = fp;
+              ikq[c] = c4 - sl * k4;
+              if (lds.fcnt[fp] == 1) {
+                const int bb = lds.ffirst[fp];
+                const int jb = lds.sidx[bb];
+                const int tp = jb * per + slot_of(m, fp, fa) * k4 + ikq[c];
+                if (jb >= 0 && tp < park_vecs) vp[c] = park_w[tp];
+                else vp[c] = reinterpret_cast<const float4 *>(lat_row(m, lds.feat[bb], fp))
+                    [LAT_W * RL4 + slot_of(m, fp, fa) * k4 + ikq[c]];
+              }
+            }
+          }
+          if (u >= kLag) {
+            const int v = u - kLag, c = v & kLag;
+            __builtin_amdgcn_sched_barrier(0);
+            if (rp[c]) {
+              const int a = ia[c], fp = ifp[c], fa = lds.field[a];
+              if (lds.fcnt[fp] == 1) {
+                const int bb = lds.ffirst[fp];
+                ffm_touch4(m.h, a < bb, tg, lds.val[a], lds.val[bb], vp[c], w4[c], hn[v], hz[v]);
+              } else {
+                for (int bb = lds.ffirst[fp]; bb < nv; bb++) {
+                  if (bb == a || lds.field[bb] != fp) continue;
+                  const float4 vq = reinterpret_cast<const float4 *>(lat_row(m, lds.feat[bb], fp))
+                      [LAT_W * RL4 + slot_of(m, fp, fa) * k4 + ikq[c]];
+                  ffm_touch4(m.h, a < bb, tg, lds.val[a], lds.val[bb], vq, w4[c], hn[v], hz[v]);
+                }
+              }
+              if (FFM_ROW_NT & 1) {
+                store_nt(rp[c] + LAT_N * RL4, hn[v]);
+                store_nt(rp[c] + LAT_Z * RL4, hz[v]);
+              } else {
+                rp[c][LAT_N * RL4] = hn[v];
+                rp[c][LAT_Z * RL4] = hz[v];
+              }
+            }
+          }
+        }
+      }
+      int t_rest = threadIdx.x;
+      if constexpr (HOLD > 0) t_rest += HOLD * blockDim.x;
+      for (int t0 = t_rest; t0 < total; t0 += kUpdFly * blockDim.x) {
         float4 *rp[kUpdFly];
         float4 n4[kUpdFly], z4[kUpdFly], w4[kUpdFly], vp[kUpdFly];
         int ia[kUpdFly], ifp[kUpdFly], ikq[kUpdFly];
