@@ -136,6 +136,59 @@ __global__ __launch_bounds__(256) void pull_block_weighted_hashed_kernel(PullHas
   FFM_PULL_BLOCK_HASHED(hjob)
   FFM_PULL_BLOCK_FINISH(job)
 }
+// A block handed over without values (val == NULL: every value is 1.0f, include/ffm_engine.h "Rows without
+// values"): nothing of val is in the job's five arrays, and the upload writes the slot's val array itself,
+// over its own grid stride, the way FFM_PULL_BLOCK_FINISH writes a missing field array -- a lane stores four
+// 1.0f as one 16-byte vector, the last n % 4 go singly.  The stores hide behind the link (the kernel is bound
+// by PCIe).  Every such block writes them again: a block that brought its values may have used the slot in
+// between.  Kernels of their own once more, so that a block WITH its values is uploaded by the launch, and
+// the kernel, it always was; the four above keep their text (profiles/implicit_ones.md).
+#define FFM_PULL_BLOCK_ONES(dst, n)                                                                         \
+  {                                                                                                         \
+    const unsigned n4 = (n) >> 2;                                                                           \
+    const float4 ones4 = make_float4(1.0f, 1.0f, 1.0f, 1.0f);                                               \
+    for (unsigned i = tid; i < n4; i += stride) reinterpret_cast<float4 *>(dst)[i] = ones4;                 \
+    if (tid < ((n) & 3u)) (dst)[(n4 << 2) + tid] = 1.0f;                                                    \
+  }
+#define FFM_PULL_BLOCK_WEIGHTS(wj)                                                                          \
+  {                                                                                                         \
+    const unsigned n16 = wj.wbytes >> 4;                                                                    \
+    const int4 *s = reinterpret_cast<const int4 *>(wj.wsrc);                                                \
+    int4 *d = reinterpret_cast<int4 *>(wj.wdst);                                                            \
+    for (unsigned i = tid; i < n16; i += stride) d[i] = s[i];                                               \
+    const unsigned tail = wj.wbytes & 15u;                                                                  \
+    if (tid < (tail >> 2))                                                                                  \
+      reinterpret_cast<int *>(wj.wdst)[(n16 << 2) + tid] = reinterpret_cast<const int *>(wj.wsrc)[(n16 << 2) + tid]; \
+  }
+__global__ __launch_bounds__(256) void pull_block_ones_kernel(PullJob job, float *ones, unsigned n_ones) {
+  FFM_PULL_BLOCK_ARRAYS(job)
+  FFM_PULL_BLOCK_ONES(ones, n_ones)
+  FFM_PULL_BLOCK_FINISH(job)
+}
+__global__ __launch_bounds__(256) void pull_block_weighted_ones_kernel(PullWeightedJob wjob, float *ones, unsigned n_ones) {
+  const PullJob &job = wjob.block;
+  FFM_PULL_BLOCK_ARRAYS(job)
+  FFM_PULL_BLOCK_WEIGHTS(wjob)
+  FFM_PULL_BLOCK_ONES(ones, n_ones)
+  FFM_PULL_BLOCK_FINISH(job)
+}
+__global__ __launch_bounds__(256) void pull_block_hashed_ones_kernel(PullHashJob hjob, float *ones, unsigned n_ones) {
+  const PullJob &job = hjob.w.block;
+  FFM_PULL_BLOCK_ARRAYS(job)
+  FFM_PULL_BLOCK_HASHED(hjob)
+  FFM_PULL_BLOCK_ONES(ones, n_ones)
+  FFM_PULL_BLOCK_FINISH(job)
+}
+__global__ __launch_bounds__(256) void pull_block_weighted_hashed_ones_kernel(PullHashJob hjob, float *ones, unsigned n_ones) {
+  const PullJob &job = hjob.w.block;
+  FFM_PULL_BLOCK_ARRAYS(job)
+  FFM_PULL_BLOCK_WEIGHTS(hjob.w)
+  FFM_PULL_BLOCK_HASHED(hjob)
+  FFM_PULL_BLOCK_ONES(ones, n_ones)
+  FFM_PULL_BLOCK_FINISH(job)
+}
+#undef FFM_PULL_BLOCK_WEIGHTS
+#undef FFM_PULL_BLOCK_ONES
 #undef FFM_PULL_BLOCK_HASHED
 #undef FFM_PULL_BLOCK_ARRAYS
 #undef FFM_PULL_BLOCK_FINISH
@@ -297,7 +350,7 @@ static int claim_slot(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t 
     job.gen_fields = e->m.n_fields;
   }
   HIP_TRY(put(feat, 4 * E, sl.feat, hj ? &hj->isrc : nullptr, hj ? &hj->idst : nullptr));
-  HIP_TRY(put(val, 4 * E, sl.val));
+  HIP_TRY(put(val, 4 * E, sl.val));  // (val == NULL: nothing to copy or describe -- the upload kernel writes ones)
   HIP_TRY(put(label, 4 * static_cast<size_t>(n_rows), sl.label));
   if (weight && n_rows > 0) {  // the sixth array: beside the job's five (its image: the slot's pinned_w)
     const size_t wbytes = 4 * static_cast<size_t>(n_rows);
@@ -370,7 +423,10 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
   const bool timed = !e->stage_thread_on || e->prof_on;
   hipEvent_t free_ev = slot_was_used ? sl.free_ev : nullptr;
   const bool hashed = e->hash_ids;
-  rc = e->submit([e, this_slot, free_ev, hjob, hashed, plan, seq, grid_pull, timed]() -> int {
+  // (val == NULL: the upload writes the slot's values -- every time, whatever the slot held before)
+  float *const ones = sl.val;
+  const unsigned n_ones = val ? 0u : static_cast<unsigned>(nnz);
+  rc = e->submit([e, this_slot, free_ev, hjob, hashed, plan, seq, grid_pull, timed, ones, n_ones]() -> int {
     const PullWeightedJob &job = hjob.w;
     ScopedTimer tm("stage:submit");
     ffm_engine::Slot &s2 = e->slots[this_slot];
@@ -381,7 +437,13 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
       // (long steps: the upload too waits for the running block's row kernel to end -- beside the update
       // launches it costs nothing, beside the row kernel, which is bound by the bytes it moves, it does)
       if (e->pull_after_row && plan.ws >= 0) HIP_TRY(hipStreamWaitEvent(e->copy, e->prep_after_row ? e->ev_row_done[plan.ws] : e->ev_set_free[plan.ws], 0));
-      if (hashed && job.wbytes) hipLaunchKernelGGL(pull_block_weighted_hashed_kernel, dim3(grid_pull), dim3(256), 0, e->copy, hjob);
+      if (n_ones) {
+        if (hashed && job.wbytes) hipLaunchKernelGGL(pull_block_weighted_hashed_ones_kernel, dim3(grid_pull), dim3(256), 0, e->copy, hjob, ones, n_ones);
+        else if (hashed) hipLaunchKernelGGL(pull_block_hashed_ones_kernel, dim3(grid_pull), dim3(256), 0, e->copy, hjob, ones, n_ones);
+        else if (job.wbytes) hipLaunchKernelGGL(pull_block_weighted_ones_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job, ones, n_ones);
+        else hipLaunchKernelGGL(pull_block_ones_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job.block, ones, n_ones);
+      }
+      else if (hashed && job.wbytes) hipLaunchKernelGGL(pull_block_weighted_hashed_kernel, dim3(grid_pull), dim3(256), 0, e->copy, hjob);
       else if (hashed) hipLaunchKernelGGL(pull_block_hashed_kernel, dim3(grid_pull), dim3(256), 0, e->copy, hjob);
       else if (job.wbytes) hipLaunchKernelGGL(pull_block_weighted_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job);
       else hipLaunchKernelGGL(pull_block_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job.block);
@@ -590,7 +652,11 @@ int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const i
     return rc;
   ffm_engine::Slot &sl = e->slots[this_slot];
   if (slot_was_used && sl.free_ev) HIP_TRY(hipStreamWaitEvent(e->copy, sl.free_ev, 0));  // nothing reads its device arrays
-  if (e->hash_ids) hipLaunchKernelGGL(pull_block_hashed_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, hjob);
+  if (!val && nnz > 0) {  // (no values came: the upload writes the slot's)
+    if (e->hash_ids) hipLaunchKernelGGL(pull_block_hashed_ones_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, hjob, sl.val, static_cast<unsigned>(nnz));
+    else hipLaunchKernelGGL(pull_block_ones_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, job, sl.val, static_cast<unsigned>(nnz));
+  }
+  else if (e->hash_ids) hipLaunchKernelGGL(pull_block_hashed_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, hjob);
   else hipLaunchKernelGGL(pull_block_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, job);
   HIP_TRY(hipEventRecord(sl.ev_copied, e->copy));
   sl.used = true;

@@ -9,7 +9,8 @@ static void launch_metric(ffm_engine *e, int channel, int n_rows, const float *s
 __global__ void loss_accumulate_kernel(double *acc, const double *one) { *acc += *one; }
 
 static int check_block(ffm_engine *e, int32_t n_rows, int32_t nnz, const void *row_ptr,
-                       const void *field, const void *feat, const void *val, bool implicit_fields = false) {
+                       const void *field, const void *feat, const void *val, bool implicit_fields = false,
+                       bool implicit_ones = false) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
   // an evaluation block whose predict launch predict_batch_async deferred goes first (every entry
   // point that puts work on the main stream passes here)
@@ -18,7 +19,8 @@ static int check_block(ffm_engine *e, int32_t n_rows, int32_t nnz, const void *r
   if (n_rows < 0 || nnz < 0) return fail(FFM_E_INVALID, "negative n_rows / nnz");
   if (n_rows > e->max_rows || nnz > e->max_nnz)
     return fail(FFM_E_CAPACITY, "block exceeds max_batch_rows / max_batch_nnz");
-  if (!row_ptr || (nnz > 0 && (!feat || !val))) return fail(FFM_E_INVALID, "null CSR array");
+  // (implicit_ones: rows in host memory, val == NULL -- every value is 1.0f, written on the device)
+  if (!row_ptr || (nnz > 0 && (!feat || (!val && !implicit_ones)))) return fail(FFM_E_INVALID, "null CSR array");
   if (e->m.type == FFM_MODEL_FFM && nnz > 0 && !field && !implicit_fields)
     return fail(FFM_E_INVALID, "FFM requires the field array (libffm rows)");
   return FFM_OK;
@@ -594,6 +596,8 @@ int ffm_engine_predict_finish_device(ffm_engine *e, int32_t n_rows, const float 
 // Checks one block of host arrays; returns its nnz and its longest row.
 // implicit_fields (the staged entry points, FFM, field == NULL): every row must then hold exactly one
 // entry per field, entry j of a row being field j's -- the upload kernel writes the field array itself.
+// Rows in host memory may always come without values (val == NULL: every value is 1.0f): the array is written
+// on the device, by the upload kernel (engine_stage.h) or, on the synchronous calls, by stage_block's fill.
 static int validate_host_block(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
                                const int32_t *field, const int32_t *feat, const float *val,
                                int32_t *nnz_out, int *longest_out, bool implicit_fields = false) {
@@ -605,7 +609,7 @@ static int validate_host_block(ffm_engine *e, int32_t n_rows, const int32_t *row
   for (int r = 0; r < n_rows; r++)
     if (row_ptr[r + 1] < row_ptr[r]) return fail(FFM_E_INVALID, "row_ptr must be non-decreasing");
   const int32_t nnz = row_ptr[n_rows];
-  int rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val, implicit_fields);
+  int rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val, implicit_fields, true);
   if (rc) return rc;
   if (implicit_fields && !field && e->m.type == FFM_MODEL_FFM)
     for (int r = 0; r < n_rows; r++)
@@ -633,6 +637,16 @@ static int validate_host_weights(int32_t n_rows, const float *weight) {
   return FFM_OK;
 }
 
+// The synchronous calls' share of val == NULL (the staged calls': the upload kernel, engine_stage.h): n values
+// of 1.0f written in place of the array's copy, four per lane as one 16-byte vector, the last n % 4 singly.
+__global__ __launch_bounds__(256) void fill_ones_kernel(float *val, unsigned n) {
+  const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+  const unsigned n4 = n >> 2;
+  const float4 ones4 = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+  for (unsigned i = tid; i < n4; i += stride) reinterpret_cast<float4 *>(val)[i] = ones4;
+  if (tid < (n & 3u)) val[(n4 << 2) + tid] = 1.0f;
+}
+
 static int stage_block(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
                        const int32_t *feat, const float *val, const int32_t *label, int32_t *nnz_out,
                        const float *weight = nullptr) {
@@ -652,7 +666,10 @@ static int stage_block(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, co
   if (nnz > 0) {
     if (field) HIP_TRY(hipMemcpyAsync(e->d_field, field, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(e->d_feat, feat, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->d_val, val, sizeof(float) * nnz, hipMemcpyHostToDevice, e->stream));
+    if (val) HIP_TRY(hipMemcpyAsync(e->d_val, val, sizeof(float) * nnz, hipMemcpyHostToDevice, e->stream));
+    else  // (no values came: a kernel writes them in place of the copy)
+      hipLaunchKernelGGL(fill_ones_kernel, dim3(std::max(1, std::min(256, cdiv(cdiv(nnz, 4), 256)))), dim3(256), 0, e->stream,
+                         e->d_val, static_cast<unsigned>(nnz));
   }
   if (label && n_rows > 0)
     HIP_TRY(hipMemcpyAsync(e->d_label, label, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, e->stream));

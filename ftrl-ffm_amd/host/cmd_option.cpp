@@ -84,7 +84,13 @@ const std::string_view cmd_help =
     "              with --resume_from ck --n_epochs 0 (then --predict_data / --predict_out, --predict_output, --metrics auc\n"
     "              and --hash_feats as always); FFM only, one GPU, rows of at most 128 entries, no training: refused with\n"
     "              --n_epochs > 0, --model_path, --checkpoint_path, --n_gpus > 1 and --refresh_weights true (write the\n"
-    "              checkpoint with --refresh_weights true instead).  Prints `serving weights: <fmt>, <bytes> bytes of model`\tdefault:none\n";
+    "              checkpoint with --refresh_weights true instead).  Prints `serving weights: <fmt>, <bytes> bytes of model`\tdefault:none\n"
+    "--compact_rows <bool>: a block whose values are all 1 (what a categorical libffm file is after --hash_feats) goes\n"
+    "              to the GPU without its value array, and an FFM block whose rows are one entry per field in field order\n"
+    "              without its field array: the device writes both itself, a third of the block's bytes over PCIe each.\n"
+    "              Noted per row while the file is parsed; training, evaluation, --predict_data and --serve_weights.  Losses,\n"
+    "              AUC lines, scores, model files and checkpoints do not change by a bit.  Prints\n"
+    "              `compact rows: V of B blocks without values, F without fields`\tdefault:false\n";
 
 static bool assign_bool(std::string arg) {
   std::transform(arg.begin(), arg.end(), arg.begin(), [](unsigned char c) { return std::tolower(c); });
@@ -144,6 +150,7 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--learn") learn = assign_bool(v);
     else if (k == "--refresh_weights") refresh_weights = assign_bool(v);
     else if (k == "--hash_feats") hash_feats = assign_bool(v);
+    else if (k == "--compact_rows") compact_rows = assign_bool(v);
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
     else if (k == "--field_ranges") field_ranges = v;
     else if (k == "--metrics") {

@@ -41,6 +41,9 @@ struct config_options {
   // --serve_weights none | f32 | f16: score a saved model from a serving engine (FFM_FLAG_SERVE_F32 / _F16: the
   // weights alone, in fp32 bits or IEEE binary16); only with --resume_from ck --n_epochs 0
   std::string serve_weights = "none";
+  // --compact_rows: blocks whose values are all 1.0f / whose rows are one entry per field in field order cross
+  // PCIe without their val / field array (include/ffm_engine.h "Rows without values"); no result changes by a bit
+  bool compact_rows = false;
 
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };

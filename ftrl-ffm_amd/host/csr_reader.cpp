@@ -113,6 +113,7 @@ void parse_range(const char *p, const char *end, bool has_field, Part &out) {
       while (t < stop && *t != ' ') t++;
       out.label.push_back(to_int(q, t, lb, le) > 0 ? 1 : 0);
       int n = 0;
+      uint8_t flags = kRowOnes | kRowOrdered;  // (what the row is until an entry says otherwise)
       q = t;
       while (true) {
         while (q < stop && *q == ' ') q++;
@@ -122,6 +123,8 @@ void parse_range(const char *p, const char *end, bool has_field, Part &out) {
           float fv;
           if (fast_token(q, stop, has_field, ffld, fft, fv)) {
             if (fv != 0.0f) {
+              if (!is_one_bits(fv)) flags &= static_cast<uint8_t>(~kRowOnes);
+              if (ffld != n) flags &= static_cast<uint8_t>(~kRowOrdered);
               out.field.push_back(ffld);
               out.feat.push_back(fft);
               out.val.push_back(fv);
@@ -151,6 +154,8 @@ void parse_range(const char *p, const char *end, bool has_field, Part &out) {
         if (vb >= t) bad_line(lb, le);
         const float v = to_float(vb, t, lb, le);
         if (v != 0.0f) {
+          if (!is_one_bits(v)) flags &= static_cast<uint8_t>(~kRowOnes);
+          if (fld != n) flags &= static_cast<uint8_t>(~kRowOrdered);
           out.field.push_back(fld);
           out.feat.push_back(ft);
           out.val.push_back(v);
@@ -159,6 +164,7 @@ void parse_range(const char *p, const char *end, bool has_field, Part &out) {
         q = t;
       }
       out.nnz.push_back(n);
+      out.flags.push_back(flags);
     }
     p = le + 1;
   }
@@ -179,6 +185,7 @@ void CsrData::slice(size_t r0, size_t r1, CsrBlock &out) const {
   out.label.assign(label.begin() + r0, label.begin() + r1);
   out.row_ptr.resize(r1 - r0 + 1);
   for (size_t r = r0; r <= r1; r++) out.row_ptr[r - r0] = static_cast<int32_t>(row_ptr[r] - b);
+  for (size_t r = r0; r < r1; r++) out.note_row(flags[r], static_cast<int32_t>(row_ptr[r + 1] - row_ptr[r]));
 }
 
 size_t CsrData::gather_nnz(const int *idx, size_t n) const {
@@ -191,9 +198,12 @@ void CsrData::gather(const int *idx, size_t n, CsrBlock &out, int n_threads) con
   out.row_ptr.resize(n + 1);
   out.label.resize(n);
   out.row_ptr[0] = 0;
+  out.reset_facts();
   int32_t total = 0;
   for (size_t j = 0; j < n; j++) {
-    total += static_cast<int32_t>(row_ptr[idx[j] + 1] - row_ptr[idx[j]]);
+    const int32_t len = static_cast<int32_t>(row_ptr[idx[j] + 1] - row_ptr[idx[j]]);
+    out.note_row(flags[idx[j]], len);  // (the rows' flag bytes ANDed: no pass over the gathered entries)
+    total += len;
     out.row_ptr[j + 1] = total;
   }
   out.field.resize(static_cast<size_t>(total));
@@ -244,6 +254,7 @@ CsrData load_csr(const std::string &path, const std::string &file_type, int n_th
   try_reserve(out.val, bytes / tok);
   try_reserve(out.row_ptr, bytes / 8 + 2);
   try_reserve(out.label, bytes / 8 + 1);
+  try_reserve(out.flags, bytes / 8 + 1);
   // first touch of ~1 GB per million rows is what this loop would otherwise spend its time on: ask for
   // huge pages (512 times fewer faults where transparent huge pages are on "madvise" or "always")
   auto huge = [](void *p, size_t n) {
@@ -300,7 +311,7 @@ CsrData load_csr(const std::string &path, const std::string &file_type, int n_th
       const size_t got = part->nnz.size(), ne = part->feat.size();
       const size_t e0 = out.feat.size(), r0 = out.label.size();
       out.field.resize(e0 + ne); out.feat.resize(e0 + ne); out.val.resize(e0 + ne);
-      out.label.resize(r0 + got); out.row_ptr.resize(r0 + got + 1);
+      out.label.resize(r0 + got); out.row_ptr.resize(r0 + got + 1); out.flags.resize(r0 + got);
       {
         std::lock_guard<std::mutex> lock(mu);
         jobs[0] = {out.field.data() + e0, part->field.data(), 4 * ne};
@@ -311,6 +322,7 @@ CsrData load_csr(const std::string &path, const std::string &file_type, int n_th
       }
       cv_go.notify_all();
       if (got) std::memcpy(out.label.data() + r0, part->label.data(), 4 * got);
+      if (got) std::memcpy(out.flags.data() + r0, part->flags.data(), got);
       for (size_t r = 0; r < got; r++) out.row_ptr[r0 + r + 1] = static_cast<int64_t>(e0) + (*rp)[r + 1];
       {
         std::unique_lock<std::mutex> lock(mu);

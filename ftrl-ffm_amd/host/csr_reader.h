@@ -31,6 +31,7 @@ struct CsrData {
   pod_vector<int64_t> row_ptr{0};
   pod_vector<int32_t> field, feat, label;
   pod_vector<float> val;
+  pod_vector<uint8_t> flags;  // per row: kRowOnes | kRowOrdered (types.h), from the parser; slice / gather AND them
   size_t n_rows() const { return row_ptr.size() - 1; }
   // rows [r0, r1) as one block
   void slice(size_t r0, size_t r1, CsrBlock &out) const;
@@ -48,7 +49,8 @@ CsrData load_csr(const std::string &path, const std::string &file_type, int n_th
 struct CsrPart {
   std::vector<int32_t> nnz, field, feat, label;  // nnz, label: per row
   std::vector<float> val;
-  void clear() { nnz.clear(); field.clear(); feat.clear(); label.clear(); val.clear(); }
+  std::vector<uint8_t> flags;  // per row: kRowOnes | kRowOrdered (types.h), noted as the row's tokens are written
+  void clear() { nnz.clear(); field.clear(); feat.clear(); label.clear(); val.clear(); flags.clear(); }
   void swap_clear(CsrPart &other) { CsrPart empty; std::swap(other, empty); }  // releases other's memory
 };
 void parse_csr_range(const char *begin, const char *end, bool has_field, CsrPart &out);

@@ -174,8 +174,10 @@ size_t CsrStream::next(size_t want, CsrBlock &out, size_t max_nnz, bool fixed_ca
     out.feat.insert(out.feat.end(), c->part.feat.begin() + e0, c->part.feat.begin() + e1);
     out.val.insert(out.val.end(), c->part.val.begin() + e0, c->part.val.begin() + e1);
     out.label.insert(out.label.end(), c->part.label.begin() + consume_row_, c->part.label.begin() + consume_row_ + take);
-    for (size_t r = 0; r < take; r++)
+    for (size_t r = 0; r < take; r++) {
       out.row_ptr.push_back(static_cast<int32_t>(base + static_cast<size_t>(c->row_ptr[consume_row_ + r + 1] - e0)));
+      out.note_row(c->part.flags[consume_row_ + r], c->part.nnz[consume_row_ + r]);
+    }
     got += take;
     consume_row_ += take;
     if (consume_row_ == rows) {

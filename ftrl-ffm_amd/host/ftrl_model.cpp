@@ -53,6 +53,7 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
   // get/set_latent_rows, pull/push_linear, the model files and checkpoints speak MODEL (hashed) ids
   if (opt.hash_feats) cfg.flags |= FFM_FLAG_HASH_IDS;
   hash_ids_ = opt.hash_feats;
+  compact_rows_ = opt.compact_rows;
   // --serve_weights: a serving engine (include/ffm_engine.h "Serving engines") -- the weights alone, rows of at
   // most 128 entries, prediction only; load_checkpoint then passes the saved w and nothing else
   serving_ = opt.serve_weights != "none";
@@ -173,6 +174,7 @@ float FtrlModel::train(feat_vec &features, int label) {
   remove_out_range(features);
   one_.clear();
   one_.push(Sample{features, label});
+  one_.forget_facts();  // (the one-row shims hand over all five arrays, --compact_rows or not)
   float logit = 0.0f;
   train_block(one_, &logit);
   return logit;
@@ -182,9 +184,28 @@ float FtrlModel::predict(feat_vec &features, bool output_prob) {
   remove_out_range(features);
   one_.clear();
   one_.push(Sample{features, 0});
+  one_.forget_facts();
   float out = 0.0f;
   predict_block(one_, output_prob, &out);
   return out;
+}
+
+// --compact_rows: the field and val arrays a block crosses PCIe with -- NULL where the block's facts
+// (types.h: noted by whoever wrote its entries) say that the engine can write the array itself
+// (include/ffm_engine.h: val == NULL is 1.0f; field == NULL is one entry per field in field order).
+// staged: the call uploads through a staging slot -- the synchronous engine calls want an FFM block's field array.
+FtrlModel::Wire FtrlModel::wire(const CsrBlock &b, bool staged) {
+  Wire w{b.field.data(), b.val.data()};
+  if (!compact_rows_) return w;
+  compact_blocks_++;
+  if (b.all_ones) { w.val = nullptr; compact_no_val_++; }
+  if (staged && model_type == ModelType::FFM && b.one_entry_per_field(n_fields)) { w.field = nullptr; compact_no_field_++; }
+  return w;
+}
+
+void FtrlModel::print_compact_rows() const {
+  if (compact_rows_)
+    std::printf("compact rows: %lld of %lld blocks without values, %lld without fields\n", compact_no_val_, compact_blocks_, compact_no_field_);
 }
 
 template <typename Fn>
@@ -214,6 +235,7 @@ void FtrlModel::for_each_fitting(const CsrBlock &blk, Fn fn) {
     part_.label.assign(blk.label.begin() + r0, blk.label.begin() + r1);
     if (blk.weight.empty()) part_.weight.clear();
     else part_.weight.assign(blk.weight.begin() + r0, blk.weight.begin() + r1);
+    part_.inherit_facts(blk);  // (a split block keeps its facts)
     fn(part_, r0);
     r0 = r1;
   }
@@ -224,13 +246,14 @@ double FtrlModel::train_block(const CsrBlock &blk, float *logit_out) {
   for_each_fitting(blk, [&](const CsrBlock &b, int r0) {
     double loss_sum = 0.0;
     const float *w = b.weight.empty() ? nullptr : b.weight.data();  // (null: the unweighted call)
+    const Wire a = wire(b, grp_ != nullptr);  // (a group stages every block)
     if (grp_)
-      check(ffm_group_train_batch_weighted(grp_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(),
-                                           b.val.data(), b.label.data(), w, logit_out ? logit_out + r0 : nullptr, &loss_sum),
+      check(ffm_group_train_batch_weighted(grp_, b.n_rows(), b.row_ptr.data(), a.field, b.feat.data(),
+                                           a.val, b.label.data(), w, logit_out ? logit_out + r0 : nullptr, &loss_sum),
             "ffm_group_train_batch"), handed_over_++;  // (a group stages every block: its ordinal counts)
     else
-      check(ffm_engine_train_batch_weighted(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(),
-                                            b.val.data(), b.label.data(), w, logit_out ? logit_out + r0 : nullptr,
+      check(ffm_engine_train_batch_weighted(eng_, b.n_rows(), b.row_ptr.data(), a.field, b.feat.data(),
+                                            a.val, b.label.data(), w, logit_out ? logit_out + r0 : nullptr,
                                             &loss_sum),
             "ffm_engine_train_batch");
     total += loss_sum;
@@ -241,13 +264,14 @@ double FtrlModel::train_block(const CsrBlock &blk, float *logit_out) {
 void FtrlModel::train_block_async(const CsrBlock &blk) {
   for_each_fitting(blk, [&](const CsrBlock &b, int) {
     const float *w = b.weight.empty() ? nullptr : b.weight.data();  // (null: the unweighted call)
+    const Wire a = wire(b, true);
     if (grp_)
-      check(ffm_group_train_batch_async_weighted(grp_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(),
-                                                 b.val.data(), b.label.data(), w, 0),
+      check(ffm_group_train_batch_async_weighted(grp_, b.n_rows(), b.row_ptr.data(), a.field, b.feat.data(),
+                                                 a.val, b.label.data(), w, 0),
             "ffm_group_train_batch_async");
     else
-      check(ffm_engine_train_batch_async_weighted(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(),
-                                                  b.feat.data(), b.val.data(), b.label.data(), w, 0),
+      check(ffm_engine_train_batch_async_weighted(eng_, b.n_rows(), b.row_ptr.data(), a.field,
+                                                  b.feat.data(), a.val, b.label.data(), w, 0),
             "ffm_engine_train_batch_async");
     handed_over_++;
   });
@@ -293,13 +317,14 @@ long long FtrlModel::train_block_pinned(const CsrBlock &blk) {
     return handed_over_;
   }
   const float *w = blk.weight.empty() ? nullptr : blk.weight.data();  // (null: the unweighted call)
+  const Wire a = wire(blk, true);
   if (grp_)
-    check(ffm_group_train_batch_async_weighted(grp_, n, blk.row_ptr.data(), blk.field.data(), blk.feat.data(),
-                                               blk.val.data(), blk.label.data(), w, 1),
+    check(ffm_group_train_batch_async_weighted(grp_, n, blk.row_ptr.data(), a.field, blk.feat.data(),
+                                               a.val, blk.label.data(), w, 1),
           "ffm_group_train_batch_async");
   else
-    check(ffm_engine_train_batch_async_weighted(eng_, n, blk.row_ptr.data(), blk.field.data(), blk.feat.data(),
-                                                blk.val.data(), blk.label.data(), w, 1),
+    check(ffm_engine_train_batch_async_weighted(eng_, n, blk.row_ptr.data(), a.field, blk.feat.data(),
+                                                a.val, blk.label.data(), w, 1),
           "ffm_engine_train_batch_async_pinned");
   return ++handed_over_;
 }
@@ -350,13 +375,14 @@ long long FtrlModel::predict_block_async(const CsrBlock &blk, bool pinned, float
     eval_loss_pending_ += predict_block(blk, scores && output_prob, scores);
     return handed_over_;
   }
+  const Wire a = wire(blk, true);
   if (scores)
-    check(ffm_engine_predict_batch_async_scores(eng_, n, blk.row_ptr.data(), blk.field.data(), blk.feat.data(),
-                                                blk.val.data(), blk.label.data(), pinned ? 1 : 0, output_prob ? 1 : 0, scores),
+    check(ffm_engine_predict_batch_async_scores(eng_, n, blk.row_ptr.data(), a.field, blk.feat.data(),
+                                                a.val, blk.label.data(), pinned ? 1 : 0, output_prob ? 1 : 0, scores),
           "ffm_engine_predict_batch_async_scores");
   else
-    check(ffm_engine_predict_batch_async(eng_, n, blk.row_ptr.data(), blk.field.data(), blk.feat.data(),
-                                         blk.val.data(), blk.label.data(), pinned ? 1 : 0),
+    check(ffm_engine_predict_batch_async(eng_, n, blk.row_ptr.data(), a.field, blk.feat.data(),
+                                         a.val, blk.label.data(), pinned ? 1 : 0),
           "ffm_engine_predict_batch_async");
   return ++handed_over_;
 }
@@ -390,14 +416,15 @@ double FtrlModel::predict_block(const CsrBlock &blk, bool output_prob, float *ou
   double total = 0.0;
   for_each_fitting(blk, [&](const CsrBlock &b, int r0) {
     double loss_sum = 0.0;
+    const Wire a = wire(b, false);
     if (grp_)
-      check(ffm_group_predict_batch(grp_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(),
-                                    b.val.data(), b.label.data(), output_prob ? 1 : 0,
+      check(ffm_group_predict_batch(grp_, b.n_rows(), b.row_ptr.data(), a.field, b.feat.data(),
+                                    a.val, b.label.data(), output_prob ? 1 : 0,
                                     out ? out + r0 : nullptr, &loss_sum),
             "ffm_group_predict_batch");
     else
-      check(ffm_engine_predict_batch(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(),
-                                     b.feat.data(), b.val.data(), b.label.data(), output_prob ? 1 : 0,
+      check(ffm_engine_predict_batch(eng_, b.n_rows(), b.row_ptr.data(), a.field,
+                                     b.feat.data(), a.val, b.label.data(), output_prob ? 1 : 0,
                                      out ? out + r0 : nullptr, &loss_sum),
             "ffm_engine_predict_batch");
     total += loss_sum;

@@ -127,6 +127,9 @@ class FtrlModel {
   bool pin_scores(float *p, size_t n);
   void unpin_scores(float *p);
   int n_gpus() const { return n_gpus_; }
+  // --compact_rows: prints `compact rows: V of B blocks without values, F without fields` -- of the B engine
+  // calls the block entry points made, how many passed val == NULL / field == NULL (nothing without the flag)
+  void print_compact_rows() const;
   // AUC accumulated on the device (include/ffm_engine.h "Metrics"), one engine or a group alike:
   // `eval` takes every labelled predict, `train` the pre-update logits of every training block.
   // read_metrics(FFM_METRIC_EVAL / FFM_METRIC_TRAIN) returns the channel's numbers so far (after a
@@ -200,6 +203,10 @@ class FtrlModel {
   int32_t flags_ = 0;
   bool serving_ = false;   // --serve_weights f32 | f16: a serving engine behind this model (prediction only)
   bool hash_ids_ = false;  // --hash_feats: ids >= n_feats are not erased on the host, the device hashes them
+  bool compact_rows_ = false;  // --compact_rows: blocks go without the arrays their facts make redundant
+  long long compact_blocks_ = 0, compact_no_val_ = 0, compact_no_field_ = 0;
+  struct Wire { const int32_t *field; const float *val; };
+  Wire wire(const CsrBlock &b, bool staged);  // the two optional arrays of one engine call (counted)
   CsrBlock one_;  // scratch for the one-row shims
   // engine capacities chosen at construction; blocks beyond max_nnz_ are split into several
   // engine calls (each still a block in row order), a single row beyond max_row_nnz_ is an error

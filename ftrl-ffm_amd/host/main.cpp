@@ -48,6 +48,7 @@ int main(int argc, char *argv[]) {
         std::printf("scored %llu rows time: %.4lfs\n", n,
                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
       }
+      task.model_ptr->print_compact_rows();  // (--compact_rows: one line, last)
     };
     // --pos_weight / --neg_weight / --weight_data: read and checked in full before a model exists
     ftrl::SampleWeights weights = ftrl::load_sample_weights(opt);

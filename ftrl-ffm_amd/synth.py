@@ -12,7 +12,8 @@ import numpy as np
 
 @dataclass
 class Block:
-    """Rows in the engine's CSR wire format."""
+    """Rows in the engine's CSR wire format.  val None: every value is 1.0 (include/ffm_engine.h "Rows
+    without values"); field None: one entry per field in field order."""
     row_ptr: np.ndarray
     field: np.ndarray
     feat: np.ndarray
@@ -29,12 +30,18 @@ class Block:
 
     def rows(self, lo, hi):
         b, e = int(self.row_ptr[lo]), int(self.row_ptr[hi])
-        return Block((self.row_ptr[lo:hi + 1] - b).astype(np.int32), self.field[b:e].copy(),
-                     self.feat[b:e].copy(), self.val[b:e].copy(), self.label[lo:hi].copy())
+        return Block((self.row_ptr[lo:hi + 1] - b).astype(np.int32),
+                     None if self.field is None else self.field[b:e].copy(), self.feat[b:e].copy(),
+                     None if self.val is None else self.val[b:e].copy(), self.label[lo:hi].copy())
 
 
 class Generator:
-    def __init__(self, n_fields, n_feats, dist="zipf", zipf_s=1.1, seed=42):
+    def __init__(self, n_fields, n_feats, dist="zipf", zipf_s=1.1, seed=42, ones=None):
+        """ones (default None: the last field carries a real value, as always): "array" -- every value is
+        1.0, spelled out; "none" -- the same rows with val=None.  The ids are those of the default."""
+        if ones not in (None, "array", "none"):
+            raise ValueError("ones must be None, 'array' or 'none'")
+        self.ones = ones
         self.F = int(n_fields)
         self.per = int(n_feats) // self.F
         assert self.per >= 1, "need at least one id per field"
@@ -66,13 +73,14 @@ class Generator:
         feat = (local + np.arange(F, dtype=np.int64)[None, :] * per).astype(np.int32)
         val = np.ones((n_rows, F), np.float32)
         last = np.round(rng.random(n_rows), 4).astype(np.float32)
-        val[:, F - 1] = np.maximum(last, np.float32(1e-4))  # the parsers drop zeros
+        if self.ones is None:
+            val[:, F - 1] = np.maximum(last, np.float32(1e-4))  # the parsers drop zeros
         logit = (self.planted[feat] * val).sum(axis=1)
         label = (rng.random(n_rows) < 1.0 / (1.0 + np.exp(-logit))).astype(np.int32)
         field = np.broadcast_to(np.arange(F, dtype=np.int32)[None, :], (n_rows, F))
         row_ptr = (np.arange(n_rows + 1, dtype=np.int64) * F).astype(np.int32)
         return Block(row_ptr, np.ascontiguousarray(field).reshape(-1), feat.reshape(-1),
-                     val.reshape(-1), label)
+                     None if self.ones == "none" else val.reshape(-1), label)
 
 
 def to_libffm_text(block, libsvm=False):
@@ -82,8 +90,8 @@ def to_libffm_text(block, libsvm=False):
         b, e = int(block.row_ptr[r]), int(block.row_ptr[r + 1])
         toks = [str(int(block.label[r]))]
         for p in range(b, e):
-            v = "%.6g" % float(block.val[p])
+            v = "1" if block.val is None else "%.6g" % float(block.val[p])
             toks.append(("%d:%s" % (block.feat[p], v)) if libsvm
-                        else ("%d:%d:%s" % (block.field[p], block.feat[p], v)))
+                        else ("%d:%d:%s" % (p - b if block.field is None else block.field[p], block.feat[p], v)))
         lines.append(" ".join(toks))
     return "\n".join(lines) + "\n"

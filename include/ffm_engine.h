@@ -20,6 +20,8 @@
  *   field j's (what python/generate_data.py:272-306 writes and a libffm file without dropped zeros
  *   is; anything else is FFM_E_INVALID) -- the field array is then written on the device instead
  *   of crossing PCIe, a third of the block's bytes.  Same results as with the array passed.
+ *   Every entry point that takes rows in HOST memory, the synchronous ones included, takes val == NULL: every
+ *   value is 1.0f -- "Rows without values" below.
  *   Entries whose feat (FFM: or field) is out of range are ignored exactly as
  *   FtrlModel::remove_out_range / FFM::remove_out_range erase them (ftrl_model.cpp:36-42,
  *   ffm.cpp:30-36); the caller's buffers are never modified.  (FFM_FLAG_HASH_IDS: ids >= n_feats are
@@ -597,6 +599,27 @@ int ffm_engine_hash_ids_device(ffm_engine *e, int32_t nnz, const int32_t *field,
 int ffm_engine_hash_ids_host(int32_t model_type, int32_t n_feats, int32_t n_fields, const int32_t *field_start,
                              int32_t nnz, const int32_t *field, const int32_t *feat_in, int32_t *feat_out);
 
+/* ---- Rows without values: val == NULL is 1.0f -------------------------------------------------------
+ * Click logs are categorical: after hashing every entry of a libffm file is field:id:1, and an array of
+ * 1.0f is a third of a block's bytes over PCIe (half of what is left once the field array stays at home).
+ * On every entry point that takes rows in HOST memory, val == NULL with nnz > 0 means "every value is 1.0f"
+ * (bits 0x3f800000), for LR, FM and FFM:
+ *   where      ffm_engine_train_batch[_weighted], ffm_engine_predict_batch; ffm_engine_stage_batch[_weighted],
+ *              ffm_engine_train_batch_async[_pinned|_weighted], ffm_engine_predict_batch_async[_scores], with
+ *              zero_copy 0 and 1; ffm_group_train_batch[_async][_weighted], ffm_group_predict_batch.
+ *   contract   a block handed over without values gives, bit for bit, what the same block gives with an
+ *              array of 1.0f: logits, losses, w, n, z, scores and the metrics channels.
+ *   combines   freely with field == NULL (where that is taken: the staged calls), sample weights, FFM_FLAG_HASH_IDS, serving engines (both formats)
+ *              and FFM_FLAG_LEARN; blocks with and without values mix freely in one pipeline.
+ *   how        nothing of val is copied, page-locked or read.  The pipelined calls' upload kernel writes the
+ *              staging slot's value array itself (16-byte stores over its own grid stride, behind the link),
+ *              again for every such block; the synchronous calls run one small fill kernel in place of the
+ *              copy.  Every kernel downstream reads values as always.
+ *   _device    the entry points that take DEVICE rows, and ffm_engine_prepare_device, take arrays as they
+ *              are: there val == NULL with nnz > 0 stays FFM_E_INVALID.
+ * A block that brings its val array runs exactly the launches, kernels and kernel arguments it ran before.
+ * No new symbol, no new ABI version: callers that always pass val see no change. */
+
 /* ---- Refresh: every stored weight from its accumulators -----------------------------------------
  * train() refreshes w = W(n, z) lazily, for what a row touches, BEFORE it updates (n, z), and leaves the
  * stored w alone afterwards (ffm.cpp:38-49, :72-88); predict() reads the stored w and nothing else
@@ -656,7 +679,7 @@ int ffm_group_refresh_weights(ffm_group *g, ffm_refresh_stats *out);
  *         means on a training engine: set_rows its ids' lin_w / vec_w, set_weights its bias.
  * works   every prediction entry point, unchanged: ffm_engine_predict_batch, _device, _async, _async_scores
  *         (zero_copy included), ffm_engine_predict_finish_device; FFM_METRIC_EVAL; FFM_FLAG_HASH_IDS and
- *         ffm_engine_hash_ids_device; field == NULL rows; ffm_engine_sync, the profile calls (the predict
+ *         ffm_engine_hash_ids_device; field == NULL and val == NULL rows; ffm_engine_sync, the profile calls (the predict
  *         kernel's label is "serve_wave_kernel"), ffm_engine_train_flush as the evaluation flush.
  *         ffm_engine_set_weights / set_rows take fp32 host arrays as always (w is rounded to the format on the
  *         device); ffm_engine_get_weights / get_rows return the decoded fp32 values.
