@@ -5,7 +5,7 @@ creating an Engine without libffm_engine.so or without a GPU raises."""
 from . import build as _build
 from .engine import (ABI, FFM, FM, LR, METRIC_BINS, METRIC_EVAL, METRIC_TRAIN, Config, Engine,  # noqa: F401
                      EngineError, Group, LIB_PATH, Metrics, default_batch_ramp, hash_ids, init_weights_host,
-                     load_library, metrics_from_histogram, page_aligned, shard_plan)
+                     load_library, metrics_from_histogram, page_aligned, shard_plan, spell_out_candidates)
 
 
 def build(force=False, verbose=False):

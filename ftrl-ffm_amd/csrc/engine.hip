@@ -113,12 +113,14 @@ enum KernelId {
   K_GROUP_KEYS, K_GROUP_SORT, K_GROUP_FINISH, K_ROW, K_TMP_GRAD,
   K_LOSS_SUM, K_LINEAR_UPDATE, K_BIAS_UPDATE, K_LATENT_UPDATE, K_LATENT_UPDATE_FEW, K_LATENT_UPDATE_WALK, K_LATENT_UPDATE_GIANT,
   K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC, K_PUSH_SCORES, K_SERVE_ROW,
+  K_SERVE_CTX, K_SERVE_CAND,
   K_COUNT
 };
 const char *kKernelNames[K_COUNT] = {
     "group_keys_kernel", "group_radix_sort", "group_finish_kernel", "row_kernel<train>", "tmp_grad_kernel", "loss_sum_kernel",
     "linear_update_kernel", "bias_update_kernel", "update_kernel", "update_few_kernel", "update_walk_kernel", "update_giant_kernel",
-    "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel", "push_scores_kernel", "serve_wave_kernel"};
+    "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel", "push_scores_kernel", "serve_wave_kernel",
+    "serve_context_kernel", "serve_candidate_kernel"};
 
 struct ProfRec {
   int kid;
@@ -389,6 +391,14 @@ struct ffm_engine {
   int refresh_grid = 0;
   // ffm_engine_pack_weights (engine_serve.h): the four counters of a serving engine, made by the first call
   unsigned long long *d_pack = nullptr;
+  // ffm_engine_score_candidates[_device] (engine_serve.h): what serve_context_kernel leaves for the candidates'
+  // waves (cx) and the host call's staging of the context arrays, made by the first call, grown to the largest
+  // call seen; the capacities in elements
+  ftrl_dev::CandCtx cx{};
+  int *d_ctx_ptr = nullptr, *d_req_ptr = nullptr, *d_ctx_field = nullptr, *d_ctx_feat = nullptr;
+  float *d_ctx_val = nullptr;
+  size_t cx_ent_cap = 0, cx_head_cap = 0, cx_terms_cap = 0, cx_cand_cap = 0;
+  size_t ctx_ptr_cap = 0, req_ptr_cap = 0, ctx_field_cap = 0, ctx_feat_cap = 0, ctx_val_cap = 0;
   std::vector<void *> allocs;
   // split-phase bookkeeping
   Rows pending{};
@@ -530,6 +540,21 @@ struct ffm_engine {
                                    " bytes failed: " + hipGetErrorString(err));
     allocs.push_back(q);
     *p = static_cast<T *>(q);
+    return FFM_OK;
+  }
+  // *p holds at least `need` elements afterwards.  The new array is made before the old one is let go, so a
+  // failed allocation (FFM_E_NOMEM) leaves the engine as it was; hipFree waits for what still reads the old one.
+  template <typename T>
+  int grow(T **p, size_t *cap, size_t need) {
+    if (*p && *cap >= need) return FFM_OK;
+    T *q = nullptr;
+    if (int rc = alloc(&q, need)) return rc;
+    if (*p) {
+      allocs.erase(std::find(allocs.begin(), allocs.end(), static_cast<void *>(*p)));
+      (void)hipFree(*p);
+    }
+    *p = q;
+    *cap = need;
     return FFM_OK;
   }
 

@@ -47,6 +47,147 @@ static void launch_serve_waves(ffm_engine *e, const Rows &rows, int row_cap, flo
 #undef SERVE_LAUNCH
 }
 
+// ---- one context against many candidates (include/ffm_engine.h "Scoring candidates") --------------------
+
+static int cand_common_check(ffm_engine *e, int32_t n_req, int32_t n_cand) {
+  if (!e) return fail(FFM_E_INVALID, "null engine");
+  if (!serving(e))
+    return fail(FFM_E_UNSUPPORTED, "score_candidates needs a serving engine (FFM_FLAG_SERVE_F32 / _F16): "
+                                   "ffm_engine_pack_weights copies a training engine's weights into one");
+  HIP_TRY(hipSetDevice(e->cfg.device_id));
+  if (int rc_e = eval_launch_pending(e)) return rc_e;
+  if (n_req < 0 || n_cand < 0) return fail(FFM_E_INVALID, "negative n_req / n_cand");
+  if (n_cand > e->max_rows) return fail(FFM_E_CAPACITY, "more candidates than max_batch_rows");
+  return FFM_OK;
+}
+
+// Both launches, on arrays in device memory.  ctx_cap >= 1; row_cap: the longest concatenated row, if known.
+static int cand_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                       const float *ctx_val, const int32_t *cand_req_ptr, int32_t n_cand, const int32_t *cand_ptr,
+                       const int32_t *cand_field, const int32_t *cand_feat, const float *cand_val, int32_t cand_nnz,
+                       int ctx_cap, int row_cap, int32_t output_prob, float *out) {
+  const size_t stride = static_cast<size_t>(cand_terms_stride(ctx_cap));
+  int rc;
+  if ((rc = e->grow(&e->cx.ent, &e->cx_ent_cap, static_cast<size_t>(n_req) * ctx_cap))) return rc;
+  if ((rc = e->grow(&e->cx.head, &e->cx_head_cap, static_cast<size_t>(n_req)))) return rc;
+  if ((rc = e->grow(&e->cx.terms, &e->cx_terms_cap, std::max<size_t>(1, static_cast<size_t>(n_req) * stride)))) return rc;
+  if ((rc = e->grow(&e->cx.cand_req, &e->cx_cand_cap, static_cast<size_t>(n_cand)))) return rc;
+  CandCtx cx = e->cx;
+  cx.ctx_cap = ctx_cap;
+  const ModelDev &m = e->m;
+  const int ctx_lds = std::min(ctx_cap, kPredLdsCap), lds_cap = std::min(row_cap, kPredLdsCap);
+  const size_t ctx_shmem = cand_ctx_lds_bytes(ctx_lds), shmem = pred_lds_bytes(lds_cap);
+  const int ctx_grid = cdiv(n_req, kPredRows), grid = cdiv(n_cand, kPredRows), threads = 64 * kPredRows;
+  const Rows rows{n_cand, cand_nnz, cand_ptr, cand_field, cand_feat, cand_val, nullptr};
+  int *err = e->d_err;
+  // (the lane shapes of launch_serve_waves)
+#define CAND_LAUNCH_FMT(FMT, LPP, VPL, U)                                                                                      \
+  do {                                                                                                                        \
+    LAUNCH(e, K_SERVE_CTX, (serve_context_kernel<FMT, LPP, VPL, U>), ctx_grid, threads, ctx_shmem, m, n_req, ctx_ptr,         \
+           ctx_field, ctx_feat, ctx_val, cand_req_ptr, n_cand, cx, e->max_row_nnz, ctx_lds, err);                             \
+    LAUNCH(e, K_SERVE_CAND, (serve_candidate_kernel<FMT, LPP, VPL, U>), grid, threads, shmem, m, n_req, ctx_ptr, cx, rows,    \
+           row_cap, lds_cap, err, out, output_prob);                                                                          \
+  } while (0)
+#define CAND_LAUNCH(LPP, VPL, U)                                       \
+  do {                                                                 \
+    if (m.lat_fmt == SERVE_F16) CAND_LAUNCH_FMT(SERVE_F16, LPP, VPL, U); \
+    else CAND_LAUNCH_FMT(SERVE_F32, LPP, VPL, U);                      \
+  } while (0)
+  switch (m.n_factors) {
+    case 4: CAND_LAUNCH(1, 1, 4); break;
+    case 8: CAND_LAUNCH(2, 1, 4); break;
+    case 16: CAND_LAUNCH(FFM_PRED_LPP, 4 / FFM_PRED_LPP, FFM_PRED_U); break;
+    case 32: CAND_LAUNCH(8, 1, 2); break;
+    default: CAND_LAUNCH(16, 1, 1); break;  // 64 (create admits nothing else)
+  }
+#undef CAND_LAUNCH
+#undef CAND_LAUNCH_FMT
+  HIP_TRY(hipGetLastError());
+  return FFM_OK;
+}
+
+int ffm_engine_score_candidates_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                       const int32_t *ctx_feat, const float *ctx_val, const int32_t *cand_req_ptr,
+                                       int32_t n_cand, const int32_t *cand_ptr, const int32_t *cand_field,
+                                       const int32_t *cand_feat, const float *cand_val, int32_t ctx_nnz, int32_t cand_nnz,
+                                       int32_t ctx_cap, int32_t output_prob, float *out) {
+  if (int rc = cand_common_check(e, n_req, n_cand)) return rc;
+  if (n_req == 0 || n_cand == 0) return FFM_OK;
+  if (ctx_nnz < 0 || cand_nnz < 0 || ctx_cap < 0) return fail(FFM_E_INVALID, "negative ctx_nnz / cand_nnz / ctx_cap");
+  if (!ctx_ptr || !cand_req_ptr || !cand_ptr || !out || (ctx_nnz > 0 && (!ctx_field || !ctx_feat || !ctx_val)) ||
+      (cand_nnz > 0 && (!cand_field || !cand_feat || !cand_val)))
+    return fail(FFM_E_INVALID, "null array");
+  // (a context beyond the engine's row limit is flagged by its kernel whatever the cap says)
+  const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
+  return cand_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, cand_req_ptr, n_cand, cand_ptr, cand_field, cand_feat,
+                     cand_val, cand_nnz, cap, e->max_row_nnz, output_prob, out);
+}
+
+static int cand_check_ptr(const int32_t *ptr, int32_t n, const char *name) {
+  if (ptr[0] != 0) return fail(FFM_E_INVALID, std::string(name) + "[0] must be 0");
+  for (int32_t r = 0; r < n; r++)
+    if (ptr[r + 1] < ptr[r]) return fail(FFM_E_INVALID, std::string(name) + " must be non-decreasing");
+  return FFM_OK;
+}
+
+int ffm_engine_score_candidates(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                const int32_t *ctx_feat, const float *ctx_val, const int32_t *cand_req_ptr, int32_t n_cand,
+                                const int32_t *cand_ptr, const int32_t *cand_field, const int32_t *cand_feat,
+                                const float *cand_val, int32_t output_prob, float *out) {
+  int rc = cand_common_check(e, n_req, n_cand);
+  if (rc) return rc;
+  if (n_req == 0 || n_cand == 0) return FFM_OK;
+  // ---- on the caller's thread, before anything is queued
+  if (!ctx_ptr || !cand_req_ptr || !cand_ptr || !out) return fail(FFM_E_INVALID, "null array");
+  if ((rc = cand_check_ptr(ctx_ptr, n_req, "ctx_ptr"))) return rc;
+  if ((rc = cand_check_ptr(cand_req_ptr, n_req, "cand_req_ptr"))) return rc;
+  if (cand_req_ptr[n_req] != n_cand) return fail(FFM_E_INVALID, "cand_req_ptr[n_req] must be n_cand");
+  if ((rc = cand_check_ptr(cand_ptr, n_cand, "cand_ptr"))) return rc;
+  const int32_t ctx_nnz = ctx_ptr[n_req], cand_nnz = cand_ptr[n_cand];
+  if ((ctx_nnz > 0 && (!ctx_field || !ctx_feat)) || (cand_nnz > 0 && (!cand_field || !cand_feat)))
+    return fail(FFM_E_INVALID, "null field / feat array");
+  if (cand_nnz > e->max_nnz) return fail(FFM_E_CAPACITY, "the candidates exceed max_batch_nnz");
+  int ctx_cap = 1, longest = 1;
+  for (int32_t r = 0; r < n_req; r++) {
+    const int nc = ctx_ptr[r + 1] - ctx_ptr[r];
+    int most = 0;
+    for (int32_t c = cand_req_ptr[r]; c < cand_req_ptr[r + 1]; c++) most = std::max(most, cand_ptr[c + 1] - cand_ptr[c]);
+    if (nc + most > e->max_row_nnz)
+      return fail(FFM_E_CAPACITY, "a context and candidate together have more entries than max_row_nnz");
+    ctx_cap = std::max(ctx_cap, nc);
+    longest = std::max(longest, nc + most);
+  }
+  const size_t n_ptr = static_cast<size_t>(n_req) + 1, n_ctx = std::max<size_t>(1, static_cast<size_t>(ctx_nnz));
+  if ((rc = e->grow(&e->d_ctx_ptr, &e->ctx_ptr_cap, n_ptr))) return rc;
+  if ((rc = e->grow(&e->d_req_ptr, &e->req_ptr_cap, n_ptr))) return rc;
+  if ((rc = e->grow(&e->d_ctx_field, &e->ctx_field_cap, n_ctx))) return rc;
+  if ((rc = e->grow(&e->d_ctx_feat, &e->ctx_feat_cap, n_ctx))) return rc;
+  if ((rc = e->grow(&e->d_ctx_val, &e->ctx_val_cap, n_ctx))) return rc;
+  // ---- copies, the values nobody sent, hashed ids: behind one another on the engine's stream, as stage_block
+  hipStream_t st = e->stream;
+  HIP_TRY(hipMemcpyAsync(e->d_ctx_ptr, ctx_ptr, sizeof(int32_t) * (n_req + 1), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_req_ptr, cand_req_ptr, sizeof(int32_t) * (n_req + 1), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_row_ptr, cand_ptr, sizeof(int32_t) * (n_cand + 1), hipMemcpyHostToDevice, st));
+  struct Side { int32_t nnz; const int32_t *field, *feat; const float *val; int *d_field, *d_feat; float *d_val; };
+  const Side sides[2] = {{ctx_nnz, ctx_field, ctx_feat, ctx_val, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val},
+                         {cand_nnz, cand_field, cand_feat, cand_val, e->d_field, e->d_feat, e->d_val}};
+  for (const Side &s : sides) {
+    if (s.nnz <= 0) continue;
+    HIP_TRY(hipMemcpyAsync(s.d_field, s.field, sizeof(int32_t) * s.nnz, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.d_feat, s.feat, sizeof(int32_t) * s.nnz, hipMemcpyHostToDevice, st));
+    if (s.val) HIP_TRY(hipMemcpyAsync(s.d_val, s.val, sizeof(float) * s.nnz, hipMemcpyHostToDevice, st));
+    else
+      hipLaunchKernelGGL(fill_ones_kernel, dim3(std::max(1, std::min(256, cdiv(cdiv(s.nnz, 4), 256)))), dim3(256), 0, st, s.d_val,
+                         static_cast<unsigned>(s.nnz));
+    if (e->hash_ids) launch_hash_ids(e, st, s.nnz, s.d_field, s.d_feat, s.d_feat);
+  }
+  rc = cand_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, e->d_req_ptr, n_cand, e->d_row_ptr,
+                   e->d_field, e->d_feat, e->d_val, cand_nnz, ctx_cap, longest, output_prob, e->d_out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, e->d_out, sizeof(float) * n_cand, hipMemcpyDeviceToHost, st));
+  return check_device_errors(e);
+}
+
 // ---- packed table <-> host arrays (fp32 on the host; rounded / decoded on the device) ------------------
 
 static int serve_vec_transfer(ffm_engine *e, float *host, bool to_host) {

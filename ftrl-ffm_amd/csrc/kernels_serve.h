@@ -178,6 +178,296 @@ __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void ffm_serve_wave_ke
   }
 }
 
+// ---- one context against many candidates (include/ffm_engine.h "Scoring candidates") ---------------
+//
+// A candidate's score is ffm_serve_wave_kernel's on the row [context entries ..., candidate entries ...].  What
+// every candidate of a request shares is made once per request by serve_context_kernel and read by each
+// candidate's wave in serve_candidate_kernel: the context's survivors as staged entries, the running value
+// after the bias and the context's linear terms, and the TERM of every context x context pair (the sum itself
+// cannot be shared: in pair order those terms interleave with the context x candidate ones).  The candidate's
+// wave feeds a stored term into the same ordered sum at the pair's position in the concatenated row and issues
+// no gathers for it.
+struct CandCtx {
+  int4 *ent;      // [n_req][ctx_cap] the context's survivors {id, field, val bits, 0}, in order
+  int2 *head;     // [n_req] {survivors, or kCandVoid; bits of the linear prefix}
+  float *terms;   // [n_req][ctx_cap (ctx_cap - 1) / 2] pair (a, b) of nc survivors at a nc - a (a + 1) / 2 + (b - a - 1)
+  int *cand_req;  // [n_cand] the request of every candidate
+  int ctx_cap;    // entries of a context at most (raw, before erasure)
+};
+constexpr int kCandVoid = -1;  // head.x of a request whose context is too long: its candidates are NaN
+
+__host__ __device__ inline size_t cand_ctx_lds_bytes(int lds_cap) {
+  return static_cast<size_t>(kPredRows) * static_cast<size_t>(lds_cap) * 16;
+}
+__host__ __device__ inline int64_t cand_terms_stride(int ctx_cap) {
+  return static_cast<int64_t>(ctx_cap) * (ctx_cap - 1) / 2;
+}
+
+// One wave per request, kPredRows requests per workgroup.  Also writes the request of each of its candidates
+// (cand_req_ptr[r] .. cand_req_ptr[r + 1], kept inside [0, n_cand)).
+template <int FMT, int LPP, int VPL, int U>
+__global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void serve_context_kernel(ModelDev m, int n_req, const int *ctx_ptr,
+                                                                      const int *field, const int *feat, const float *val,
+                                                                      const int *cand_req_ptr, int n_cand, CandCtx cx,
+                                                                      int max_row_nnz, int lds_cap, int *err) {
+  static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
+  static_assert(LPP >= 1 && LPP <= 16 && (LPP & (LPP - 1)) == 0, "a pair's lanes sit inside one DPP row");
+  constexpr int PPS = 64 / LPP;  // pairs per step
+  using Raw = typename std::conditional<FMT == SERVE_F16, uint2, float4>::type;  // four factors as stored
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int r = wave_uniform(blockIdx.x * kPredRows + wv);
+  if (r >= n_req) return;
+  int4 *E = reinterpret_cast<int4 *>(smem) + static_cast<size_t>(wv) * lds_cap;
+  const int c0 = wave_uniform(cand_req_ptr[r]), c1 = wave_uniform(cand_req_ptr[r + 1]);
+  for (int cc = max(c0, 0) + lane; cc < min(c1, n_cand); cc += 64) cx.cand_req[cc] = r;
+  const int b = wave_uniform(ctx_ptr[r]);
+  const int nnz = wave_uniform(ctx_ptr[r + 1]) - b;
+  if (nnz > cx.ctx_cap || nnz > max_row_nnz || nnz > lds_cap) {
+    if (lane == 0) {
+      atomicOr(err, ERR_ROW_TOO_LONG);
+      cx.head[r] = make_int2(kCandVoid, 0);
+    }
+    return;
+  }
+  const int k = m.n_factors, RL = m.row_len;
+  const Raw *const table = reinterpret_cast<const Raw *>(m.lat);
+  const int k4 = k >> 2;  // vectors per slot
+  int4 *const ent = cx.ent + static_cast<int64_t>(r) * cx.ctx_cap;
+
+  // ---- entries: as ffm_serve_wave_kernel stages a row's, and a copy for the candidates' waves
+  float result = m.bias3[0];
+  int nv = 0;
+  for (int base = 0; base < nnz; base += 64) {
+    const int p = base + lane;
+    int i = 0, f = 0;
+    float x = 0.0f, lw = 0.0f;
+    bool valid = false;
+    if (p < nnz) {
+      i = feat[b + p];
+      f = field[b + p];
+      x = val[b + p];
+      valid = i >= 0 && i < m.n_feats && f >= 0 && f < m.n_fields;
+    }
+    if (valid) lw = m.lin_w[i];
+    const unsigned long long mask = __ballot(valid);
+    if (valid) {
+      const int at = nv + __popcll(mask & ((1ull << lane) - 1ull));
+      const int4 en = make_int4(i, f, __float_as_int(x), 0);
+      E[at] = en;
+      ent[at] = en;
+    }
+    nv += __popcll(mask);
+    const float run = wave_sequential_prefix(result, valid ? lw * x : -0.0f);
+    result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
+  }
+  if (lane == 0) cx.head[r] = make_int2(nv, __float_as_int(result));
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+
+  // ---- the context x context terms in pair order (a outer, b inner), each as the row kernel computes it
+  const int n_pairs = nv * (nv - 1) / 2;
+  float *const T = cx.terms + static_cast<int64_t>(r) * cand_terms_stride(cx.ctx_cap);
+  const int g = lane / LPP, c = lane - g * LPP;
+  int pa = 0, pb = 1 + g;
+  if (g < n_pairs)
+    while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
+  const int64_t RL4 = RL >> 2;  // vectors per feature
+  for (int st = 0; st * PPS < n_pairs; st += U) {
+    Raw x[U][VPL], y[U][VPL];
+    float xa[U], xb[U];
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int q = (st + u) * PPS + g;
+      ok[u] = q < n_pairs;
+      const int a = ok[u] ? pa : 0, bb = ok[u] ? pb : 1;  // (n_pairs > 0 here: entries 0 and 1 exist)
+      const int4 ea = E[a], eb = E[bb];
+      xa[u] = __int_as_float(ea.z);
+      xb[u] = __int_as_float(eb.z);
+      const Raw *va = table + static_cast<int64_t>(ea.x) * RL4 + eb.y * k4 + c * VPL;
+      const Raw *vb = table + static_cast<int64_t>(eb.x) * RL4 + ea.y * k4 + c * VPL;
+#pragma unroll
+      for (int v = 0; v < VPL; v++) { x[u][v] = va[v]; y[u][v] = vb[v]; }
+      if (q + PPS < n_pairs) {  // the pair PPS further on
+        pb += PPS;
+        while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      float pr[VPL][4];
+#pragma unroll
+      for (int v = 0; v < VPL; v++) {
+        const float4 xf = serve_widen(x[u][v]), yf = serve_widen(y[u][v]);
+        pr[v][0] = xf.x * yf.x;
+        pr[v][1] = xf.y * yf.y;
+        pr[v][2] = xf.z * yf.z;
+        pr[v][3] = xf.w * yf.w;
+      }
+      float dot = 0.0f;
+#pragma unroll
+      for (int t = 0; t < LPP; t++) {
+        float in = LPP > 1 ? pred_lane_below(dot) : 0.0f;
+        in = c == 0 ? 0.0f : in;
+#pragma unroll
+        for (int v = 0; v < VPL; v++) {
+          in = in + pr[v][0];
+          in = in + pr[v][1];
+          in = in + pr[v][2];
+          in = in + pr[v][3];
+        }
+        dot = in;
+      }
+      const float term = dot * xa[u] * xb[u];
+      if (c == LPP - 1 && ok[u]) T[(st + u) * PPS + g] = term;
+    }
+  }
+}
+
+// One wave per candidate, kPredRows candidates per workgroup: ffm_serve_wave_kernel on the concatenated row,
+// with the request's staged survivors copied in place of the context's entries, the linear prefix continued,
+// and the stored term loaded (4 bytes, one lane, no gathers) for every pair whose members are both context.
+template <int FMT, int LPP, int VPL, int U>
+__global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void serve_candidate_kernel(ModelDev m, int n_req, const int *ctx_ptr,
+                                                                        CandCtx cx, Rows rows, int max_row_nnz, int lds_cap,
+                                                                        int *err, float *out, int output_prob) {
+  static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
+  static_assert(LPP >= 1 && LPP <= 16 && (LPP & (LPP - 1)) == 0, "a pair's lanes sit inside one DPP row");
+  constexpr int PPS = 64 / LPP;  // pairs per step
+  static_assert(kPredTerms % (PPS * U) == 0, "a batch of terms is whole unrolled steps");
+  using Raw = typename std::conditional<FMT == SERVE_F16, uint2, float4>::type;  // four factors as stored
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int r = wave_uniform(blockIdx.x * kPredRows + wv);
+  if (r >= rows.n_rows) return;
+  int4 *E = reinterpret_cast<int4 *>(smem + static_cast<size_t>(wv) * (static_cast<size_t>(lds_cap) * 16 + kPredTerms * 4));
+  float *terms = reinterpret_cast<float *>(E + lds_cap);
+  const int b = wave_uniform(rows.row_ptr[r]);
+  const int nnz = wave_uniform(rows.row_ptr[r + 1]) - b;
+  const int req = wave_uniform(cx.cand_req[r]);
+  const bool known = req >= 0 && req < n_req;  // (a candidate no request lists: NaN)
+  const int2 head = known ? cx.head[req] : make_int2(kCandVoid, 0);
+  const int nc = wave_uniform(head.x);
+  const int raw = known ? wave_uniform(ctx_ptr[req + 1]) - wave_uniform(ctx_ptr[req]) + nnz : 0;
+  // the row's raw length against the validated capacity and what a wave stages, as in the row kernel
+  if (nc == kCandVoid || raw > max_row_nnz || raw > lds_cap) {
+    if (lane == 0) {
+      atomicOr(err, ERR_ROW_TOO_LONG);
+      out[r] = __int_as_float(0x7fc00000);
+    }
+    return;
+  }
+  const int k = m.n_factors, RL = m.row_len;
+  const Raw *const table = reinterpret_cast<const Raw *>(m.lat);
+  const int k4 = k >> 2;  // vectors per slot
+
+  // ---- entries: the request's survivors as staged, then the candidate's behind them; the linear logit goes
+  // on from the context's prefix
+  const int4 *const ent = cx.ent + static_cast<int64_t>(req) * cx.ctx_cap;
+  for (int p = lane; p < nc; p += 64) E[p] = ent[p];
+  float result = __int_as_float(wave_uniform(head.y));
+  int nv = nc;
+  for (int base = 0; base < nnz; base += 64) {
+    const int p = base + lane;
+    int i = 0, f = 0;
+    float x = 0.0f, lw = 0.0f;
+    bool valid = false;
+    if (p < nnz) {
+      i = rows.feat[b + p];
+      f = rows.field[b + p];
+      x = rows.val[b + p];
+      valid = i >= 0 && i < m.n_feats && f >= 0 && f < m.n_fields;
+    }
+    if (valid) lw = m.lin_w[i];
+    const unsigned long long mask = __ballot(valid);
+    if (valid) E[nv + __popcll(mask & ((1ull << lane) - 1ull))] = make_int4(i, f, __float_as_int(x), 0);
+    nv += __popcll(mask);
+    const float run = wave_sequential_prefix(result, valid ? lw * x : -0.0f);
+    result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+
+  // ---- pairs in the reference's order (a outer, b inner) over the concatenated survivors
+  const int n_pairs = nv * (nv - 1) / 2;
+  const float *const T = cx.terms + static_cast<int64_t>(req) * cand_terms_stride(cx.ctx_cap);
+  const int g = lane / LPP, c = lane - g * LPP;
+  int pa = 0, pb = 1 + g;
+  if (g < n_pairs)
+    while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
+  const int64_t RL4 = RL >> 2;  // vectors per feature
+  for (int q0 = 0; q0 < n_pairs; q0 += kPredTerms) {
+    const int cnt = min(kPredTerms, n_pairs - q0);
+    for (int st = 0; st * PPS < cnt; st += U) {
+      Raw x[U][VPL], y[U][VPL];
+      float xa[U], xb[U], kept[U];
+      bool ok[U], shared[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int q = q0 + (st + u) * PPS + g;
+        ok[u] = q < n_pairs;
+        const int a = ok[u] ? pa : 0, bb = ok[u] ? pb : (nv > 1 ? 1 : 0);
+        shared[u] = ok[u] && bb < nc;  // (a < bb: both members are the context's)
+        const int4 ea = E[a], eb = E[bb];
+        xa[u] = __int_as_float(ea.z);
+        xb[u] = __int_as_float(eb.z);
+        kept[u] = 0.0f;
+#pragma unroll
+        for (int v = 0; v < VPL; v++) { x[u][v] = Raw{}; y[u][v] = Raw{}; }
+        if (shared[u]) {
+          if (c == LPP - 1) kept[u] = T[a * nc - a * (a + 1) / 2 + (bb - a - 1)];
+        } else if (ok[u]) {
+          const Raw *va = table + static_cast<int64_t>(ea.x) * RL4 + eb.y * k4 + c * VPL;
+          const Raw *vb = table + static_cast<int64_t>(eb.x) * RL4 + ea.y * k4 + c * VPL;
+#pragma unroll
+          for (int v = 0; v < VPL; v++) { x[u][v] = va[v]; y[u][v] = vb[v]; }
+        }
+        if (q + PPS < n_pairs) {  // the pair PPS further on
+          pb += PPS;
+          while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        float pr[VPL][4];
+#pragma unroll
+        for (int v = 0; v < VPL; v++) {
+          const float4 xf = serve_widen(x[u][v]), yf = serve_widen(y[u][v]);
+          pr[v][0] = xf.x * yf.x;
+          pr[v][1] = xf.y * yf.y;
+          pr[v][2] = xf.z * yf.z;
+          pr[v][3] = xf.w * yf.w;
+        }
+        // stage t finalises the lanes c == t: dot = ((0 + w0*v0) + w1*v1) + ... in factor order
+        float dot = 0.0f;
+#pragma unroll
+        for (int t = 0; t < LPP; t++) {
+          float in = LPP > 1 ? pred_lane_below(dot) : 0.0f;
+          in = c == 0 ? 0.0f : in;
+#pragma unroll
+          for (int v = 0; v < VPL; v++) {
+            in = in + pr[v][0];
+            in = in + pr[v][1];
+            in = in + pr[v][2];
+            in = in + pr[v][3];
+          }
+          dot = in;
+        }
+        const float term = dot * xa[u] * xb[u];
+        if (c == LPP - 1 && ok[u]) terms[(st + u) * PPS + g] = shared[u] ? kept[u] : term;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    for (int t0 = 0; t0 < cnt; t0 += 64) {
+      const float t = t0 + lane < cnt ? terms[t0 + lane] : -0.0f;
+      const float run = wave_sequential_prefix(result, t);
+      result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  }
+
+  if (lane == 0) out[r] = output_prob ? sigmoid_ref(result) : result;
+}
+
 // ---- the small streaming kernels -----------------------------------------------------------------
 
 // Create-time contents: the element a training engine would draw (same seed, same index), in the format.

@@ -183,6 +183,13 @@ ABI = [
     # weights only, for prediction (include/ffm_engine.h "Serving engines")
     ("ffm_engine_pack_weights", ctypes.c_int, [_vp, _vp, ctypes.POINTER(PackStats)]),
     ("ffm_engine_model_bytes", ctypes.c_int64, [_vp]),
+    # one context against many candidates (include/ffm_engine.h "Scoring candidates")
+    ("ffm_engine_score_candidates", ctypes.c_int,
+     [_vp, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, _i32p, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p,
+      ctypes.c_int32, _f32p]),
+    ("ffm_engine_score_candidates_device", ctypes.c_int,
+     [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp,
+      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp]),
 ]
 
 _lib = None
@@ -261,6 +268,38 @@ def hash_ids(field, feat, n_feats, field_start=None, model="ffm", n_fields=None)
     if rc != 0:
         raise EngineError(rc, lib.ffm_engine_last_error().decode())
     return out
+
+
+def spell_out_candidates(ctx, cand_req_ptr, cand):
+    """The block of rows [context entries ..., candidate entries ...] that Engine.score_candidates scores:
+    row c is the context of candidate c's request followed by the candidate's own entries (include/ffm_engine.h
+    "Scoring candidates" in executable form; numpy only).  ctx: one row per request; cand_req_ptr[n_req + 1]:
+    the candidates of request r are rows [cand_req_ptr[r], cand_req_ptr[r + 1]) of cand.  A val of None reads as
+    ones; the result always carries its values, and labels of 0."""
+    from .synth import Block
+    cand_req_ptr = np.asarray(cand_req_ptr, np.int64)
+    n_req, n_cand = ctx.n_rows, cand.n_rows
+    if cand_req_ptr.shape != (n_req + 1,) or cand_req_ptr[0] != 0 or cand_req_ptr[-1] != n_cand or (np.diff(cand_req_ptr) < 0).any():
+        raise ValueError("cand_req_ptr must ascend from 0 to the number of candidates, one step per request")
+    req = np.repeat(np.arange(n_req, dtype=np.int64), np.diff(cand_req_ptr))  # the request of every candidate
+    cp, kp = np.asarray(ctx.row_ptr, np.int64), np.asarray(cand.row_ptr, np.int64)
+    n_ctx, n_own = np.diff(cp)[req], np.diff(kp)
+    row_ptr = np.concatenate([[0], np.cumsum(n_ctx + n_own)])
+    nnz = int(row_ptr[-1])
+    row = np.repeat(np.arange(n_cand, dtype=np.int64), n_ctx + n_own)   # the row of every output entry
+    at = np.arange(nnz, dtype=np.int64) - row_ptr[row]                 # its position in that row
+    from_ctx = at < n_ctx[row]
+    src = np.where(from_ctx, cp[req[row]] + at, kp[row] + at - n_ctx[row])
+
+    def merged(a, b, dtype):
+        a = np.ones(int(cp[-1]), dtype) if a is None else np.asarray(a, dtype)
+        b = np.ones(int(kp[-1]), dtype) if b is None else np.asarray(b, dtype)
+        out = np.empty(nnz, dtype)
+        out[from_ctx] = a[src[from_ctx]]
+        out[~from_ctx] = b[src[~from_ctx]]
+        return out
+    return Block(row_ptr.astype(np.int32), merged(ctx.field, cand.field, np.int32), merged(ctx.feat, cand.feat, np.int32),
+                 merged(ctx.val, cand.val, np.float32), np.zeros(n_cand, np.int32))
 
 
 def load_library(path=None):
@@ -642,7 +681,31 @@ class Engine:
                                                       ctypes.byref(loss)))
         return out[:c.n_rows], float(loss.value)
 
+    def score_candidates(self, ctx, cand_req_ptr, cand, output_prob=False):
+        """One context against many candidates on a serving engine (include/ffm_engine.h "Scoring
+        candidates"): ctx holds one row per request, cand one row per candidate; the candidates of request r
+        are rows [cand_req_ptr[r], cand_req_ptr[r + 1]) of cand.  Returns the candidates' scores: bit for bit
+        predict_batch(spell_out_candidates(ctx, cand_req_ptr, cand)).  Labels are ignored; val may be None
+        (every value is 1.0)."""
+        rq = np.ascontiguousarray(cand_req_ptr, np.int32)
+        if rq.shape != (ctx.n_rows + 1,):
+            raise ValueError("cand_req_ptr needs one entry per request and one more")
+        out = np.zeros(max(cand.n_rows, 1), np.float32)
+        _, cp, cfld, cft, cv, _ = self._csr(ctx)
+        n_cand, kp, kfld, kft, kv, _ = self._csr(cand)
+        self._check(self.lib.ffm_engine_score_candidates(self.h, ctx.n_rows, cp, cfld, cft, cv, _i(rq), n_cand, kp, kfld,
+                                                         kft, kv, int(output_prob), _f(out)))
+        return out[:cand.n_rows]
+
     # ---- blocks already in HBM (raw device addresses as ints) ----
+    def score_candidates_device(self, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, cand_req_ptr, n_cand, cand_ptr,
+                                cand_field, cand_feat, cand_val, ctx_nnz, cand_nnz, ctx_cap, output_prob, out):
+        """score_candidates on arrays already in HBM (device addresses); ctx_cap: the longest context of the
+        call.  Asynchronous on the engine's stream; sync() reports a too-long context or row."""
+        self._check(self.lib.ffm_engine_score_candidates_device(
+            self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, cand_req_ptr, int(n_cand), cand_ptr, cand_field,
+            cand_feat, cand_val, int(ctx_nnz), int(cand_nnz), int(ctx_cap), int(output_prob), out))
+
     def train_batch_device(self, n_rows, nnz, row_ptr, field, feat, val, label, logit_out=None,
                            loss_sum_out=None, weight=None):
         """weight: device address of n_rows floats, or None."""

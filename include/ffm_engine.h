@@ -707,6 +707,58 @@ int ffm_engine_pack_weights(ffm_engine *dst, ffm_engine *src, ffm_pack_stats *ou
  * B * n_feats * row_len with B = 4 (fp32) or 2 (fp16); a shard counts the records it stores. */
 int64_t ffm_engine_model_bytes(const ffm_engine *e);
 
+/* ---- Scoring candidates: one context against many candidates, on a serving engine ----------------------
+ * A REQUEST is a list of context entries (field, feat, val); each of its CANDIDATES is a list of entries.  The
+ * score of a candidate is, bit for bit, what ffm_engine_predict_batch on the same engine returns for the
+ * spelled-out row [context entries ..., candidate entries ...] -- logits and probabilities -- that is
+ * FFM::predict (ffm.cpp:51-55) on that row:
+ *   erasure  an id outside [0, n_feats) or a field outside [0, n_fields) is erased, in the context and in the
+ *            candidate; the survivors keep their order;
+ *   linear   summed sequentially from the bias: the context's survivors first, then the candidate's;
+ *   pairs    each term is (dot * xa) * xb with the factor-order dot; the terms are summed one dependent add
+ *            after another in the reference's pair order (a outer, b inner) over the concatenated survivors.
+ * ROW ORDER  A caller whose rows are in field order, with the candidate fields after the context fields, gets
+ *   the reference's bits.  Any other split gets the same terms added in the order of the concatenation.
+ * What is shared between the candidates of a request, without giving up a bit: the running value after the
+ * bias and the context's linear terms (a candidate continues from it), and the TERM of every context x context
+ * pair -- computed once per request, stored, and fed by every candidate's wave into the same sequential sum at
+ * the position the pair has in the concatenated row (the sum itself cannot be cut in two: in pair order those
+ * terms interleave with the context x candidate ones).  The context's entries cross the link once per request,
+ * and its pairs' latent slots are gathered once per request instead of once per candidate.
+ *   Arrays: ctx_ptr[n_req + 1] delimits the requests' entries in ctx_field / ctx_feat / ctx_val;
+ * cand_req_ptr[n_req + 1]: the candidates of request r are rows [cand_req_ptr[r], cand_req_ptr[r + 1]) of the
+ * candidate block cand_ptr[n_cand + 1], cand_field / cand_feat / cand_val; a request may have none.
+ * out[n_cand].  Candidates carry no labels: no loss is computed and the metrics channels are not fed.
+ * LIMITS  The raw length of a row (context entries + candidate entries, before erasure) obeys the engine's
+ *   max_row_nnz, at most 128; n_cand at most max_batch_rows, the candidates' entries at most max_batch_nnz.
+ * ffm_engine_score_candidates: arrays in host memory; synchronous, like ffm_engine_predict_batch.  A deferred
+ *   evaluation block is launched first.  Checked on the caller's thread before anything is queued: a null array
+ *   or a pointer array that does not start at 0 or decreases, or cand_req_ptr[n_req] != n_cand: FFM_E_INVALID;
+ *   n_cand > max_batch_rows, or a context + candidate longer than max_row_nnz: FFM_E_CAPACITY (out untouched).
+ *   ctx_val == NULL / cand_val == NULL: every value is 1.0f.  On an engine with FFM_FLAG_HASH_IDS both id
+ *   arrays are hashed on the device behind their copies.
+ * ffm_engine_score_candidates_device: the same arrays in device memory (values required, ids taken as they
+ *   are); ctx_nnz / cand_nnz: their entry counts; ctx_cap: the longest context of the call (raw); asynchronous
+ *   on the engine's stream.  A request whose context is longer than ctx_cap or max_row_nnz has all of its
+ *   candidates NaN; a candidate whose row is longer than max_row_nnz is NaN alone; either is reported as
+ *   FFM_E_CAPACITY by ffm_engine_check_errors / ffm_engine_sync, as for ffm_engine_predict_batch_device.
+ * Both: a training engine is refused with FFM_E_UNSUPPORTED (ffm_engine_pack_weights makes a serving engine
+ *   from it); n_req == 0 or n_cand == 0 is FFM_OK with nothing written.  The per-request buffers (survivors,
+ *   prefix, n_req * ctx_cap * (ctx_cap - 1) / 2 stored terms) are allocated at the first call, grown to the
+ *   largest call seen and freed by ffm_engine_destroy; a failed allocation is FFM_E_NOMEM and leaves the engine
+ *   usable.  The profile calls label the kernels "serve_context_kernel" and "serve_candidate_kernel".
+ * OUT OF SCOPE  the CLI (there is no request file format to mirror); groups, shards, FM and LR; training
+ *   engines; a pipelined or zero-copy variant; rows beyond 128 entries. */
+int ffm_engine_score_candidates(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                const int32_t *ctx_feat, const float *ctx_val, const int32_t *cand_req_ptr,
+                                int32_t n_cand, const int32_t *cand_ptr, const int32_t *cand_field,
+                                const int32_t *cand_feat, const float *cand_val, int32_t output_prob, float *out);
+int ffm_engine_score_candidates_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                       const int32_t *ctx_feat, const float *ctx_val, const int32_t *cand_req_ptr,
+                                       int32_t n_cand, const int32_t *cand_ptr, const int32_t *cand_field,
+                                       const int32_t *cand_feat, const float *cand_val, int32_t ctx_nnz,
+                                       int32_t cand_nnz, int32_t ctx_cap, int32_t output_prob, float *out);
+
 #ifdef __cplusplus
 }
 #endif
