@@ -48,6 +48,7 @@
 #include "kernels_scan.h"
 #include "kernels_refresh.h"
 #include "kernels_metric.h"
+#include "kernels_keyed.h"
 #include "kernels_serve.h"
 #include "metrics_host.h"
 
@@ -114,13 +115,15 @@ enum KernelId {
   K_LOSS_SUM, K_LINEAR_UPDATE, K_BIAS_UPDATE, K_LATENT_UPDATE, K_LATENT_UPDATE_FEW, K_LATENT_UPDATE_WALK, K_LATENT_UPDATE_GIANT,
   K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC, K_PUSH_SCORES, K_SERVE_ROW,
   K_SERVE_CTX, K_SERVE_CAND,
+  K_KEYED_CAPTURE, K_KEYED_SORT_HIST, K_KEYED_SORT_SCAN, K_KEYED_SORT_SCATTER, K_KEYED_RANK,
   K_COUNT
 };
 const char *kKernelNames[K_COUNT] = {
     "group_keys_kernel", "group_radix_sort", "group_finish_kernel", "row_kernel<train>", "tmp_grad_kernel", "loss_sum_kernel",
     "linear_update_kernel", "bias_update_kernel", "update_kernel", "update_few_kernel", "update_walk_kernel", "update_giant_kernel",
     "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel", "push_scores_kernel", "serve_wave_kernel",
-    "serve_context_kernel", "serve_candidate_kernel"};
+    "serve_context_kernel", "serve_candidate_kernel",
+    "keyed_capture_kernel", "keyed_sort_hist_kernel", "keyed_sort_scan_kernels", "keyed_sort_scatter_kernel", "keyed_rank_kernels"};
 
 struct ProfRec {
   int kid;
@@ -381,6 +384,22 @@ struct ffm_engine {
   // the AUC channels (include/ffm_engine.h "Metrics"): hist = pos[kMetricBins], neg[kMetricBins], n_nan;
   // allocated when the channel is first turned on
   struct MetricChannel { bool on = false; unsigned long long *hist = nullptr; } metric[2];
+  // keyed capture (include/ffm_engine.h "Metrics", engine_keyed.h): per channel the captured words and the four
+  // counters of kernels_keyed.h; shared by both, since reads run one after another on the stream: the sort's
+  // scratch buffer and histogram, the scans' tile sums, the per-key table.  All made by ffm_engine_metrics_key_field.
+  struct KeyedChannel {
+    bool on = false;
+    unsigned long long *words = nullptr, *counters = nullptr;
+    size_t words_cap = 0;
+  } keyed[2];
+  int keyed_field = -1;
+  int64_t keyed_capacity = 0;  // rows a channel stores at the most (the buffers may be larger)
+  unsigned long long *keyed_scratch = nullptr, *keyed_tab = nullptr;
+  unsigned *keyed_hist = nullptr, *keyed_hist_sums = nullptr, *keyed_n_keys = nullptr;
+  ftrl_dev::RankState *keyed_rank_sums = nullptr;
+  int *keyed_tab_key = nullptr;
+  size_t keyed_scratch_cap = 0, keyed_tab_cap = 0, keyed_tab_key_cap = 0, keyed_rank_sums_cap = 0;
+  bool in_group = false;  // made by ffm_group_create
   // FFM_FLAG_HASH_IDS (engine_hash.h): host rows have their ids hashed on the device before any kernel reads
   // them; hm.start = the device copy of field_start (FFM with per-field id ranges) or null = [0, n_feats)
   bool hash_ids = false;
@@ -1318,6 +1337,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_serve.h"
 #include "engine_profile.h"
 #include "engine_metrics.h"
+#include "engine_keyed.h"
 }  // extern "C"
 
 #include "engine_group.h"

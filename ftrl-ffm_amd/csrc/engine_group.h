@@ -168,6 +168,7 @@ int ffm_group_create(const ffm_engine_config *cfg, int32_t n, const int32_t *dev
     ffm_engine *e = nullptr;
     rc = ffm_engine_create(&c, &e);
     if (rc) break;
+    e->in_group = true;
     g->eng.push_back(e);
     g->dev.push_back(device_ids[r]);
     float *lg = nullptr;

@@ -6,6 +6,7 @@
 
 static int eval_launch_pending(ffm_engine *e);  // (engine_stage.h)
 static void launch_metric(ffm_engine *e, int channel, int n_rows, const float *score, int is_prob, const int *label);  // (engine_metrics.h)
+static void launch_keyed(ffm_engine *e, int channel, const Rows &rows, const float *score, int is_prob);  // (engine_keyed.h)
 __global__ void loss_accumulate_kernel(double *acc, const double *one) { *acc += *one; }
 
 static int check_block(ffm_engine *e, int32_t n_rows, int32_t nnz, const void *row_ptr,
@@ -352,6 +353,7 @@ int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *log
   const bool own_tg = e->own_tg_cur && !logit;
   // progressive validation: the block's whole pre-update logits into the train channel (when it is on)
   launch_metric(e, FFM_METRIC_TRAIN, rows.n_rows, lg, 0, rows.label);
+  launch_keyed(e, FFM_METRIC_TRAIN, rows, lg, 0);
   if (rows.n_rows > 0 && !own_tg) {
     if (e->pending_weight)
       LAUNCH(e, K_TMP_GRAD, tmp_grad_weighted_kernel, cdiv(rows.n_rows, 256), 256, 0, rows.n_rows, lg, rows.label, e->pending_weight, e->sc[e->cur].tg, e->sc[e->cur].loss, logit_out);
@@ -568,6 +570,7 @@ int ffm_engine_predict_batch_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
   Rows rows{n_rows, nnz, row_ptr, field, feat, val, label};
   launch_row_kernel(e, rows, false, out ? out : e->d_out, output_prob);
   if (label) launch_metric(e, FFM_METRIC_EVAL, n_rows, out ? out : e->d_out, output_prob, label);
+  if (label) launch_keyed(e, FFM_METRIC_EVAL, rows, out ? out : e->d_out, output_prob);
   if (loss_sum_out && label)
     LAUNCH(e, K_LOSS_SUM, loss_sum_kernel, loss_grid(n_rows), 256, 0, n_rows, e->sc[e->cur].loss, loss_sum_out, e->d_loss_part);
   HIP_TRY(hipGetLastError());

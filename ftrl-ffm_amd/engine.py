@@ -55,6 +55,15 @@ class Metrics(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KeyedMetrics(ctypes.Structure):
+    """struct ffm_keyed_metrics (include/ffm_engine.h "Metrics", keyed capture)."""
+    _fields_ = [(k, ctypes.c_int64) for k in ("n_rows", "n_keys", "n_keys_mixed", "n_rows_mixed", "n_nan", "n_unkeyed",
+                                              "n_overflow")] + [("gauc", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RefreshStats(ctypes.Structure):
     """struct ffm_refresh_stats (include/ffm_engine.h "Refresh")."""
     _fields_ = [(k, ctypes.c_int64) for k in ("lin_live", "lin_nonzero", "lin_moved",
@@ -76,6 +85,7 @@ METRIC_EVAL, METRIC_TRAIN = 0, 1  # FFM_METRIC_*
 METRIC_BINS = 1 << 20             # FFM_METRIC_BINS
 _METRIC_CHANNELS = {"eval": METRIC_EVAL, "train": METRIC_TRAIN}
 _u64p = ctypes.POINTER(ctypes.c_uint64)
+_i64p = ctypes.POINTER(ctypes.c_int64)
 
 # every symbol include/ffm_engine.h declares: (name, restype, argtypes)
 _CSR = [_i32p, _i32p, _i32p, _f32p, _i32p]
@@ -146,6 +156,12 @@ ABI = [
     ("ffm_engine_metrics_histogram", ctypes.c_int, [_vp, ctypes.c_int32, _u64p, _u64p]),
     ("ffm_engine_metrics_from_histogram", ctypes.c_int,
      [_u64p, _u64p, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(Metrics)]),
+    # the grouped AUC (include/ffm_engine.h "Metrics", keyed capture)
+    ("ffm_engine_metrics_key_field", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]),
+    ("ffm_engine_metrics_read_keyed", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(KeyedMetrics)]),
+    ("ffm_engine_metrics_keyed_table", ctypes.c_int,
+     [_vp, ctypes.c_int32, ctypes.c_int64, _i32p, _i64p, _i64p, _u64p, _i64p]),
+    ("ffm_engine_metrics_from_keyed", ctypes.c_int, [_i64p, _i64p, _u64p, ctypes.c_int64, ctypes.POINTER(KeyedMetrics)]),
     # several GPUs in one process (ffm_group_*)
     ("ffm_group_create", ctypes.c_int, [ctypes.POINTER(Config), ctypes.c_int32, _i32p, ctypes.POINTER(_vp)]),
     ("ffm_group_destroy", None, [_vp]),
@@ -234,6 +250,72 @@ def metrics_from_histogram(pos, neg, n_nan=0):
     if rc != 0:
         raise EngineError(rc, lib.ffm_engine_last_error().decode())
     return m.as_dict()
+
+
+def metrics_from_keyed(pos, neg, u2):
+    """Per-key table -> dict(n_rows, n_keys, n_keys_mixed, n_rows_mixed, n_nan, n_unkeyed, n_overflow, gauc) on the
+    host (ffm_engine_metrics_from_keyed: no engine, no device).  pos / neg / u2: P_g, N_g, U2_g of every key,
+    keys ascending; the three counters a table does not know come out 0."""
+    lib = load_library()
+    pos = np.ascontiguousarray(pos, np.int64)
+    neg = np.ascontiguousarray(neg, np.int64)
+    u2 = np.ascontiguousarray(u2, np.uint64)
+    if not (pos.shape == neg.shape == u2.shape) or pos.ndim != 1:
+        raise ValueError("pos, neg and u2 must be one-dimensional and equally long")
+    m = KeyedMetrics()
+    rc = lib.ffm_engine_metrics_from_keyed(pos.ctypes.data_as(_i64p), neg.ctypes.data_as(_i64p), u2.ctypes.data_as(_u64p),
+                                           pos.size, ctypes.byref(m))
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
+    return m.as_dict()
+
+
+def keyed_auc_reference(keys, p, labels):
+    """The grouped AUC of include/ffm_engine.h "Metrics" (keyed capture) in executable form: numpy integers and
+    a Python float loop in the header's order of operations, no library call.  keys: one int per row, negative
+    = the row has no key (counted in n_unkeyed); p: float32 scores, NaN rows counted in n_nan; labels: positive
+    iff > 0.  Returns the dict Engine.metrics_read_keyed returns (n_overflow 0) plus the table "key", "pos",
+    "neg", "u2" (int64 / int64 / int64 / uint64 arrays, keys ascending)."""
+    keys = np.asarray(keys, np.int64).reshape(-1)
+    p = np.asarray(p, np.float32).reshape(-1)
+    y = np.asarray(labels).reshape(-1) > 0
+    if not (keys.shape == p.shape == y.shape):
+        raise ValueError("keys, p and labels must be equally long")
+    nan = np.isnan(p)
+    unkeyed = ~nan & (keys < 0)
+    ok = ~nan & ~unkeyed
+    k, s, y = keys[ok], p[ok].astype(np.float64), y[ok]
+    order = np.lexsort((y, s, k))  # key, then score, negatives first inside a tie
+    k, s, y = k[order], s[order], y[order]
+    n = k.size
+    idx = np.arange(n, dtype=np.int64)
+    key_start = np.ones(n, bool)
+    key_start[1:] = k[1:] != k[:-1]
+    run_start = key_start.copy()
+    run_start[1:] |= s[1:] != s[:-1]
+    neg_before = np.cumsum(~y) - (~y)                       # negatives in [0, i)
+    at_key = neg_before[np.maximum.accumulate(np.where(key_start, idx, 0))] if n else neg_before
+    at_run = neg_before[np.maximum.accumulate(np.where(run_start, idx, 0))] if n else neg_before
+    contrib = np.where(y, 2 * (neg_before - at_key) - (neg_before - at_run), 0).astype(np.int64)
+    g = np.cumsum(key_start) - 1                            # the row's key number
+    n_keys = int(g[-1]) + 1 if n else 0
+    pos = np.bincount(g[y], minlength=n_keys).astype(np.int64)
+    neg = np.bincount(g[~y], minlength=n_keys).astype(np.int64)
+    u2 = np.zeros(n_keys, np.int64)
+    np.add.at(u2, g, contrib)
+    num = den = 0.0
+    n_mixed = rows_mixed = 0
+    for P, N, U in zip(pos.tolist(), neg.tolist(), u2.tolist()):
+        if P == 0 or N == 0:
+            continue
+        auc_g = float(U) / (2.0 * float(P) * float(N))
+        num += float(P + N) * auc_g
+        den += float(P + N)
+        n_mixed += 1
+        rows_mixed += P + N
+    return dict(n_rows=int(n), n_keys=n_keys, n_keys_mixed=n_mixed, n_rows_mixed=rows_mixed, n_nan=int(nan.sum()),
+                n_unkeyed=int(unkeyed.sum()), n_overflow=0, gauc=num / den if den else float("nan"),
+                key=k[key_start].astype(np.int64), pos=pos, neg=neg, u2=u2.astype(np.uint64))
 
 
 def init_weights_host(seed, mean, stddev, latent, first, count):
@@ -794,6 +876,33 @@ class Engine:
                                                           neg.ctypes.data_as(_u64p)))
         return pos, neg
 
+    # ---- the grouped AUC (include/ffm_engine.h "Metrics", keyed capture) ----
+    def metrics_key_field(self, field, capacity_rows=1 << 24, eval=True, train=False):
+        """Keyed capture on / off: eval = every labelled block that is predicted, train = the pre-update logits of
+        every training block; a row's key is its first entry of `field`, at most capacity_rows rows are kept per
+        channel.  eval = train = False turns it off."""
+        self._check(self.lib.ffm_engine_metrics_key_field(self.h, (1 if eval else 0) | (2 if train else 0), int(field),
+                                                          int(capacity_rows)))
+
+    def metrics_read_keyed(self, channel, reset=False):
+        """dict(n_rows, n_keys, n_keys_mixed, n_rows_mixed, n_nan, n_unkeyed, n_overflow, gauc) of "eval" / "train"."""
+        m = KeyedMetrics()
+        self._check(self.lib.ffm_engine_metrics_read_keyed(self.h, _channel(channel), int(bool(reset)), ctypes.byref(m)))
+        return m.as_dict()
+
+    def metrics_keyed_table(self, channel):
+        """dict(key, pos, neg, u2): the per-key integers of the channel's stored rows, keys ascending."""
+        n = ctypes.c_int64(0)
+        rc = self.lib.ffm_engine_metrics_keyed_table(self.h, _channel(channel), 0, None, None, None, None, ctypes.byref(n))
+        if rc not in (0, E_CAPACITY):
+            self._check(rc)
+        nk = int(n.value)
+        key = np.zeros(nk, np.int32)
+        pos, neg, u2 = np.zeros(nk, np.int64), np.zeros(nk, np.int64), np.zeros(nk, np.uint64)
+        self._check(self.lib.ffm_engine_metrics_keyed_table(self.h, _channel(channel), nk, _i(key), pos.ctypes.data_as(_i64p),
+                                                            neg.ctypes.data_as(_i64p), u2.ctypes.data_as(_u64p), ctypes.byref(n)))
+        return dict(key=key.astype(np.int64), pos=pos, neg=neg, u2=u2)
+
     # ---- kernel timing (HIP events on the engine's stream) ----
     def profile_enable(self, on=True):
         self._check(self.lib.ffm_engine_profile_enable(self.h, int(on)))
@@ -811,8 +920,8 @@ class Engine:
         return name.value.decode(), int(n.value), float(ms.value)
 
     def profile_dump(self):
-        buf = ctypes.create_string_buffer(4096)
-        self._check(self.lib.ffm_engine_profile_dump(self.h, buf, 4096))
+        buf = ctypes.create_string_buffer(8192)
+        self._check(self.lib.ffm_engine_profile_dump(self.h, buf, 8192))
         return buf.value.decode()
 
 

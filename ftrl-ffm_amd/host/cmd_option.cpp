@@ -48,6 +48,14 @@ const std::string_view cmd_help =
     "--metrics <auc|none>: auc = after each epoch's loss line one more line with the AUC of the same rows -- training:\n"
     "              of the pre-update predictions (progressive validation) --, histogrammed on the device in 2^20\n"
     "              score bins; the +- is the most the exact rank AUC can differ\tdefault:none\n"
+    "--auc_key_field <F>: with --metrics auc, after each AUC line one more with the grouped AUC (GAUC): the AUC inside\n"
+    "              each value of field F (the first entry of field F in a row is its key: a user, a request, a placement),\n"
+    "              averaged over the keys that hold both classes, weighted by their rows; sorted and ranked on the device\n"
+    "              in exact integers.  Prints `epoch N <train|eval> gauc: G (K keys, M mixed, R of T rows; U unkeyed,\n"
+    "              O over capacity, X nan)`: R rows of the M keys with both classes, of T rows kept.  FFM only, one GPU.\n"
+    "              With --resume_from ck --n_epochs 0 --eval_data F (and --serve_weights or not) the loaded model is\n"
+    "              evaluated once, numbered by the epochs it has behind it\n"
+    "--auc_key_rows <N>: rows kept per pass for it (8 bytes each, twice, in HBM); the rest count as over capacity\tdefault:16777216\n"
     "--predict_data <data_path>: after training (and after the model / checkpoint is written) score this file:\n"
     "              one prediction per row, in file order; its label column is parsed and ignored\n"
     "--predict_out <path>: where the predictions go, one per line, each the shortest decimal that parses back\n"
@@ -171,6 +179,15 @@ void config_options::parse_option(int argc, char *argv[]) {
       if (v != "none" && v != "f32" && v != "f16") throw std::invalid_argument("--serve_weights takes none, f32 or f16");
       serve_weights = v;
     }
+    else if (k == "--auc_key_field" || k == "--auc_key_rows") {
+      long long x = 0;
+      size_t used = 0;
+      try { x = std::stoll(v, &used); } catch (const std::exception &) { used = 0; }
+      if (used != v.size() || used == 0) throw std::invalid_argument(k + " takes an integer, got `" + v + "`");
+      if (k == "--auc_key_rows") { auc_key_rows = x; continue; }
+      if (x < 0 || x > 2147483647) throw std::invalid_argument("--auc_key_field names a field: >= 0, got `" + v + "`");
+      auc_key_field = static_cast<int>(x);
+    }
     else if (k == "--predict_data") predict_path = v;
     else if (k == "--predict_out") predict_out = v;
     else if (k == "--predict_output") {
@@ -192,6 +209,16 @@ void config_options::parse_option(int argc, char *argv[]) {
     if (refresh_weights)
       throw std::invalid_argument(what + "holds no accumulators to refresh from: write the checkpoint with --refresh_weights true instead");
     if (model_type != "FFM") throw std::invalid_argument(what + "is for FFM models only (got --model_type " + model_type + ")");
+  }
+  if (auc_key_field >= 0) {
+    // the grouped AUC rides on the AUC lines of one whole FFM model (refused here, before a device is opened)
+    const std::string what = "--auc_key_field " + std::to_string(auc_key_field) + " ";
+    if (metrics != "auc") throw std::invalid_argument(what + "adds a line to the AUC lines: it needs --metrics auc");
+    if (model_type != "FFM") throw std::invalid_argument(what + "names a field, which only FFM rows have (got --model_type " + model_type + ")");
+    if (n_gpus > 1) throw std::invalid_argument(what + "is kept by one whole model on one GPU: --n_gpus > 1 is not allowed with it");
+    if (auc_key_field >= n_fields)
+      throw std::invalid_argument(what + "is not a field of this model: --n_fields is " + std::to_string(n_fields));
+    if (auc_key_rows <= 0) throw std::invalid_argument("--auc_key_rows must be positive, got " + std::to_string(auc_key_rows));
   }
   // (--n_epochs 0 with a file to score needs no training file: the format is then the scored file's)
   file_type = detect_file_type(train_path.empty() && epoch == 0 && !predict_path.empty() ? predict_path : train_path);

@@ -44,6 +44,10 @@ struct config_options {
   // --compact_rows: blocks whose values are all 1.0f / whose rows are one entry per field in field order cross
   // PCIe without their val / field array (include/ffm_engine.h "Rows without values"); no result changes by a bit
   bool compact_rows = false;
+  // --auc_key_field F / --auc_key_rows N: after every AUC line one more with the grouped AUC, the AUC inside each
+  // value of field F averaged by impressions (include/ffm_engine.h "Metrics", keyed capture); -1 = not asked for
+  int auc_key_field = -1;
+  long long auc_key_rows = 16777216;
 
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };

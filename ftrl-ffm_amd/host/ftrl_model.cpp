@@ -54,6 +54,8 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
   if (opt.hash_feats) cfg.flags |= FFM_FLAG_HASH_IDS;
   hash_ids_ = opt.hash_feats;
   compact_rows_ = opt.compact_rows;
+  keyed_field_ = opt.auc_key_field;  // (turned on with the AUC channels: enable_metrics)
+  keyed_rows_ = opt.auc_key_rows;
   // --serve_weights: a serving engine (include/ffm_engine.h "Serving engines") -- the weights alone, rows of at
   // most 128 entries, prediction only; load_checkpoint then passes the saved w and nothing else
   serving_ = opt.serve_weights != "none";
@@ -343,6 +345,21 @@ void FtrlModel::enable_metrics(bool eval, bool train) {
   if (grp_) check(ffm_group_metrics_enable(grp_, mask), "ffm_group_metrics_enable");
   else check(ffm_engine_metrics_enable(eng_, mask), "ffm_engine_metrics_enable");
   metrics_mask_ = mask;
+  if (keyed_field_ >= 0) enable_keyed_metrics(keyed_field_, keyed_rows_, eval, train);
+}
+
+void FtrlModel::enable_keyed_metrics(int field, long long capacity_rows, bool eval, bool train) {
+  if (grp_) throw std::invalid_argument("keyed metrics: one GPU only");
+  const int mask = (eval ? 1 << FFM_METRIC_EVAL : 0) | (train ? 1 << FFM_METRIC_TRAIN : 0);
+  check(ffm_engine_metrics_key_field(eng_, mask, field, capacity_rows), "ffm_engine_metrics_key_field");
+  keyed_mask_ = mask;
+}
+
+ffm_keyed_metrics FtrlModel::read_keyed_metrics(int channel, bool reset) {
+  ffm_keyed_metrics m{};
+  if (grp_) throw std::invalid_argument("keyed metrics: one GPU only");
+  check(ffm_engine_metrics_read_keyed(eng_, channel, reset ? 1 : 0, &m), "ffm_engine_metrics_read_keyed");
+  return m;
 }
 
 ffm_metrics FtrlModel::read_metrics(int channel, bool reset) {

@@ -137,6 +137,12 @@ class FtrlModel {
   void enable_metrics(bool eval, bool train);
   ffm_metrics read_metrics(int channel, bool reset);
   bool metrics_on(int channel) const { return (metrics_mask_ >> channel) & 1; }
+  // The grouped AUC (include/ffm_engine.h "Metrics", keyed capture): the rows of the same two channels kept with
+  // their key, the first entry of `field`; at most capacity_rows per channel.  A model made from options with
+  // --auc_key_field turns it on and off together with enable_metrics.  One FFM engine only (throws otherwise).
+  void enable_keyed_metrics(int field, long long capacity_rows, bool eval, bool train);
+  ffm_keyed_metrics read_keyed_metrics(int channel, bool reset);
+  bool keyed_metrics_on(int channel) const { return (keyed_mask_ >> channel) & 1; }
   // Every stored w from its accumulators (include/ffm_engine.h "Refresh"), one engine or a group alike:
   // what prediction and the model files read is otherwise one update behind (n, z).  Blocks queued and
   // not trained yet are trained first (their losses stay in train_flush()'s sum).  The host mirrors
@@ -190,6 +196,8 @@ class FtrlModel {
   ffm_group *grp_ = nullptr;
   int n_gpus_ = 1;
   int metrics_mask_ = 0;
+  int keyed_mask_ = 0, keyed_field_ = -1;  // --auc_key_field (-1: not asked for)
+  long long keyed_rows_ = 0;               // --auc_key_rows
   std::vector<int32_t> lin_owner_of_field_;  // [n_fields] shard that owns a field's linear terms
   int bias_owner_ = 0;
   double eval_loss_pending_ = 0.0;  // group: evaluation blocks are predicted synchronously

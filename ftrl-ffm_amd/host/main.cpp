@@ -34,6 +34,10 @@ int main(int argc, char *argv[]) {
     auto run = [&](auto &task) {
       if (!opt.resume_from.empty()) task.restore(task.model_ptr->load_checkpoint(opt.resume_from));
       task.train();
+      // --auc_key_field on a run that trains nothing (--resume_from ck --n_epochs 0 --eval_data F): one evaluation pass
+      // of the loaded model, numbered by the epochs it has behind it -- there is no epoch to print the line after
+      if (opt.auc_key_field >= 0 && opt.epoch <= 0 && !opt.cmd && !opt.eval_path.empty())
+        task.evaluate(static_cast<int>(task.progress().epochs_done));
       // --refresh_weights: every epoch ended with a refresh and nothing has trained since, so the model, the
       // checkpoint and the scores below are those of refreshed weights; a run that trains nothing (--n_epochs 0
       // on a resumed model) refreshes what it loaded here

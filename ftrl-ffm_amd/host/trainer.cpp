@@ -24,6 +24,16 @@ static double seconds_since(timer::time_point t0) {
 void print_auc_line(FtrlModel &m, int epoch, int channel) {
   const ffm_metrics r = m.read_metrics(channel, true);
   std::printf("epoch %d %s auc: %.6lf (+-%.1e)\n", epoch, channel == FFM_METRIC_TRAIN ? "train" : "eval", r.auc, r.auc_slack);
+  print_gauc_line(m, epoch, channel);
+}
+
+void print_gauc_line(FtrlModel &m, int epoch, int channel) {
+  if (!m.keyed_metrics_on(channel)) return;
+  const ffm_keyed_metrics r = m.read_keyed_metrics(channel, true);
+  std::printf("epoch %d %s gauc: %.6lf (%lld keys, %lld mixed, %lld of %lld rows; %lld unkeyed, %lld over capacity, %lld nan)\n", epoch,
+              channel == FFM_METRIC_TRAIN ? "train" : "eval", r.gauc, static_cast<long long>(r.n_keys),
+              static_cast<long long>(r.n_keys_mixed), static_cast<long long>(r.n_rows_mixed), static_cast<long long>(r.n_rows),
+              static_cast<long long>(r.n_unkeyed), static_cast<long long>(r.n_overflow), static_cast<long long>(r.n_nan));
 }
 
 void refresh_and_print(FtrlModel &m, long long epoch) {
@@ -285,6 +295,7 @@ void FtrlOnline::evaluate(int epoch) {
     double slack = 0.0;
     const double auc = evaluator->get_auc(&slack);
     std::printf("epoch %d eval auc: %.6lf (+-%.1e)\n", epoch, auc, slack);
+    print_gauc_line(*model_ptr, epoch, FFM_METRIC_EVAL);  // (the evaluator scores with this model)
   }
 }
 

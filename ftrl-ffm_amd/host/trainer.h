@@ -117,6 +117,8 @@ class Scorer {
 
 // --metrics auc: the line that follows an epoch's loss line ("train" / "eval"); resets the channel.
 void print_auc_line(FtrlModel &m, int epoch, int channel);
+// --auc_key_field: the grouped-AUC line that follows it (nothing when the model keeps no keys); resets the capture.
+void print_gauc_line(FtrlModel &m, int epoch, int channel);
 // --refresh_weights true: FtrlModel::refresh_weights() and its line,
 // `epoch N weights: linear L live, Z nonzero, M moved; latent L live, Z nonzero, M moved`.
 // The tasks call it after each epoch's training, before that epoch's evaluation; main() where no epoch ran.

@@ -558,6 +558,62 @@ int ffm_engine_metrics_from_histogram(const uint64_t *pos, const uint64_t *neg, 
 int ffm_group_metrics_enable(ffm_group *g, int32_t channel_mask);
 int ffm_group_metrics_read(ffm_group *g, int32_t channel, int32_t reset, ffm_metrics *out);
 
+/* Keyed capture: the grouped AUC (GAUC).  A global AUC mixes how well the model orders the rows ONE user,
+ * request or placement sees -- what serving does -- with how well it tells keys of a high click rate
+ * from keys of a low one, which no ranker can use.  GAUC takes the AUC inside each key and averages
+ * those, weighted by impressions.  Keyed capture is independent of the histogram channels above and
+ * uses the same channel numbers; it is off until ffm_engine_metrics_key_field turns it on (off: no
+ * launch, no allocation).
+ *   FFM_METRIC_EVAL  takes every labelled block that passes through ffm_engine_predict_batch_device:
+ *                    the copying, async, async-scores and deferred forms all end in it.
+ *   FFM_METRIC_TRAIN takes the pre-update logits in ffm_engine_train_update_device, where the
+ *                    histogram channel takes them.
+ *   ffm_engine_predict_finish_device has no rows, hence no keys: it is NOT captured.
+ * Definition (part of the contract), per captured row:
+ *   key     the feat of the first entry in row order with field == key_field and 0 <= feat < n_feats,
+ *           as the kernels see it: after FFM_FLAG_HASH_IDS, so ids that collide there merge their keys.
+ *           A row with no such entry counts in n_unkeyed and is left out.
+ *   score   p = sigmoid(logit) in fp32, the bits output_prob = 1 returns.  A NaN p counts in n_nan and
+ *           is left out.
+ *   class   the row is positive iff label > 0.
+ *   state   one 64-bit word per captured row, key << 32 | (bits of p) << 1 | class, in a buffer of
+ *           capacity_rows words in HBM, allocated (with a scratch buffer of the same size and the per-key
+ *           table) when capture is turned on, freed by ffm_engine_destroy.  A row that arrives when the
+ *           buffer is full is not stored and counts in n_overflow.
+ *   per key g, in exact integers: P_g, N_g = its positive / negative rows;
+ *           U2_g = sum over its positives of (2 * #{neg of g with smaller p} + #{neg of g with equal p}).
+ *   over the captured rows, on the host in double, keys ascending, one running sum each, in this order:
+ *           auc_g = (double)U2_g / (2.0 * (double)P_g * (double)N_g)     for keys with P_g * N_g > 0 only
+ *           num += (double)(P_g + N_g) * auc_g;   den += (double)(P_g + N_g);
+ *           gauc = num / den, NaN when den == 0 (the call still succeeds).
+ *   The result does not depend on the order rows arrive in (which rows a full buffer turns away does).
+ *   n_rows = rows stored, n_keys = distinct keys among them, n_keys_mixed / n_rows_mixed = the keys with
+ *   rows of both classes and their rows (den).
+ * Out of scope: groups and shards (every ffm_group_* engine, n_shards > 1), LR and FM (no fields) --
+ * all FFM_E_UNSUPPORTED; a per-row key array passed by the caller; weighting other than by impressions
+ * (ffm_engine_metrics_keyed_table hands out the integers for any other); an exact global AUC.  Serving
+ * engines are allowed: they predict. */
+typedef struct { int64_t n_rows, n_keys, n_keys_mixed, n_rows_mixed, n_nan, n_unkeyed, n_overflow; double gauc; } ffm_keyed_metrics;
+/* bit c of channel_mask = capture on channel c on, with this key field and capacity.  A channel that
+ * turns on starts empty; one that stays on keeps its rows unless key_field or capacity_rows changed,
+ * which empties it.  channel_mask == 0 turns capture off and frees nothing (the other two arguments
+ * are then ignored).  key_field outside [0, n_fields) or capacity_rows <= 0: FFM_E_INVALID;
+ * capacity_rows above 2^30: FFM_E_UNSUPPORTED. */
+int ffm_engine_metrics_key_field(ffm_engine *e, int32_t channel_mask, int32_t key_field, int64_t capacity_rows);
+/* The channel's numbers so far: sorts the captured words and ranks them on the device, averages on the
+ * host.  Waits as ffm_engine_metrics_read does (a deferred evaluation block first, then the stream);
+ * reset != 0 empties the buffer and the three counters after the snapshot, on the stream.  A channel
+ * whose capture is off: FFM_E_INVALID. */
+int ffm_engine_metrics_read_keyed(ffm_engine *e, int32_t channel, int32_t reset, ffm_keyed_metrics *out);
+/* The per-key integers, keys ascending: key[g], pos[g] = P_g, neg[g] = N_g, u2[g] = U2_g for g < *n_keys.
+ * cap = the arrays' length; too small: FFM_E_CAPACITY with *n_keys set (any array may be NULL with
+ * cap == 0 to ask for the count).  Same waits, no reset. */
+int ffm_engine_metrics_keyed_table(ffm_engine *e, int32_t channel, int64_t cap, int32_t *key, int64_t *pos, int64_t *neg,
+                                   uint64_t *u2, int64_t *n_keys);
+/* The average alone: pure host arithmetic, no engine, no device; n_nan, n_unkeyed, n_overflow come out 0. */
+int ffm_engine_metrics_from_keyed(const int64_t *pos, const int64_t *neg, const uint64_t *u2, int64_t n_keys,
+                                  ffm_keyed_metrics *out);
+
 /* ---- Hashed ids: FFM_FLAG_HASH_IDS ----------------------------------------------------------------
  * The reference erases every entry whose id is not in [0, n_feats) (remove_out_range, ftrl_model.cpp:36-42,
  * ffm.cpp:30-36); real click logs come with one global id space, fields interleaved, often larger than the
