@@ -12,8 +12,6 @@
 // There is no CPU fallback anywhere in this library.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
@@ -24,6 +22,8 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <memory>
+#include <optional>
 #include <mutex>
 #include <thread>
 #include <cstdio>
@@ -256,6 +256,7 @@ __global__ void lin_rows_copy_kernel(float *lin, int n_feats, float *dense, cons
 }
 
 #include "engine_plan.h"
+#include "engine_select.h"
 }  // namespace
 
 struct ffm_engine {
@@ -292,8 +293,7 @@ struct ffm_engine {
   // grouping.  (A fifth stream for them shares a hardware queue with one of the four and
   // serialises with it: measured 1.45-1.70 ms per step instead of 1.3.)
   bool pull_after_row = false;  // a staged block's upload waits for the running block's row kernel to end (long steps)
-  hipStream_t copy = nullptr;  // the upload kernel's stream: the prep stream (round 4 had it on aux3 for long steps)
-  bool own_sort = false;        // the grouping's sort: kernels_sort.h (short steps) or rocPRIM Onesweep (ffm_engine_create)
+  bool own_sort = false;        // the grouping's sort: kernels_sort.h (short steps) or rocPRIM Onesweep (engine_create.h: choose_sort)
   bool range_sort = false;      // ... or, when the id ranges of the fields are known, a workgroup per range (kernels_sort.h)
   int *d_sort_start = nullptr;  // [n_sort_ranges + 1] the ranges' boundaries, the last one = n_feats
   int n_sort_ranges = 0;
@@ -308,7 +308,6 @@ struct ffm_engine {
   // update phase, where the update's kernels starve it (a Onesweep pass then takes 250-300 us
   // instead of 7) and it slows them.  trained_set[0] / [1]: the scratch sets of the
   // training blocks enqueued last / before that (their ev_set_free marks the end of the update).
-  bool prep_window = true;
   int trained_set[2] = {-1, -1};
   hipStream_t stream = nullptr;
   bool own_stream = false;
@@ -458,8 +457,6 @@ struct ffm_engine {
   // workgroups of push_scores_kernel (FFM_GRID_PUSH, at most the upload's 24): one 16-byte store per
   // lane moves an 8192-row block with 8 (profiles/score_cost.md)
   int grid_push = 8;
-  bool single_kernel = true;  // (false: once-only features through the few-occurrence kernel)
-  bool single_flat = true;    // (false: one wave per feature also for short stored records)
   int row_threads = kRowThreads;  // workgroup size of the FFM row kernel (FFM_ROW_THREADS)
   int row_park = -1;         // FFM_ROW_PARK: bytes of w the row kernel parks in LDS (-1: what the budget leaves)
   int row_park_budget = 0;   // FFM_ROW_PARK_BUDGET: the row kernel's LDS budget for parking (0: 24 KB)
@@ -476,7 +473,6 @@ struct ffm_engine {
   // with the resident step unchanged.  All bookkeeping stays on the caller's thread; the worker only
   // replays closures in order.  staged_issued: ordinal of the last staged block whose launches are
   // out (a training call waits for ITS block only, never for the look-ahead's).
-  bool stage_thread_on = true;  // FFM_STAGE_THREAD=0: the caller's thread submits everything
   std::thread worker;
   std::mutex wmu;
   std::condition_variable wcv_job, wcv_done;
@@ -506,9 +502,9 @@ struct ffm_engine {
       wcv_done.notify_all();
     }
   }
-  // Runs `job` on the staging thread (or right here when it is off / while kernels are being timed).
+  // Runs `job` on the staging thread (or right here while kernels are being timed).
   int submit(std::function<int()> job) {
-    if (!stage_thread_on || prof_on) return job();
+    if (prof_on) return job();
     {
       std::lock_guard<std::mutex> lock(wmu);
       if (!worker.joinable()) worker = std::thread([this] { worker_main(); });
@@ -637,7 +633,7 @@ static int tile_nf(const ffm_engine *e) {
 // compact shard's records (40 vectors at 8 shards, 80 at 2 or 4).  For full-length records (156
 // vectors, 81 % lane use) the flat shape measured no better.
 static bool flat_pays(const ffm_engine *e, int span4) {
-  if (!e->single_flat || e->m.n_shards <= 1 || span4 <= 0) return false;
+  if (e->m.n_shards <= 1 || span4 <= 0) return false;
   const int lanes = (span4 + 63) / 64 * 64;
   return span4 * 6 < lanes * 5;
 }
@@ -709,522 +705,7 @@ void ffm_engine_destroy(ffm_engine *e) {
   delete e;
 }
 
-static int hash_ids_check(int32_t model_type, int32_t n_feats, int32_t n_fields, const int32_t *field_start);  // (engine_hash.h)
-static int serve_create_check(const ffm_engine_config *cfg);  // (engine_serve.h)
-
-int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
-  if (!cfg || !out) return fail(FFM_E_INVALID, "null config or output pointer");
-  *out = nullptr;
-  // FFM_ENGINE_HASH_IDS=1: FFM_FLAG_HASH_IDS on whatever the caller's flags say (every rank of a group)
-  bool hash_ids = (cfg->flags & FFM_FLAG_HASH_IDS) != 0;
-  if (const char *sv = std::getenv("FFM_ENGINE_HASH_IDS")) hash_ids = hash_ids || sv[0] == '1';
-  if (cfg->model_type < FFM_MODEL_LR || cfg->model_type > FFM_MODEL_FFM)
-    return fail(FFM_E_INVALID, "invalid model_type, expect LR(0), FM(1) or FFM(2)");
-  if (cfg->n_feats <= 0) return fail(FFM_E_INVALID, "n_feats must be positive");
-  if (cfg->model_type == FFM_MODEL_FFM && cfg->n_fields <= 0)
-    return fail(FFM_E_INVALID, "n_fields must be positive for FFM");
-  if (cfg->model_type != FFM_MODEL_LR && cfg->n_factors <= 0)
-    return fail(FFM_E_INVALID, "n_factors must be positive for FM/FFM");
-  if (cfg->model_type == FFM_MODEL_FM && cfg->n_factors > kTermsCap)
-    return fail(FFM_E_UNSUPPORTED, "FM n_factors above 2048 is not supported");
-  if (cfg->max_batch_rows <= 0 || cfg->max_batch_nnz <= 0)
-    return fail(FFM_E_INVALID, "max_batch_rows / max_batch_nnz must be positive");
-  if (cfg->n_shards < 1 || cfg->shard_rank < 0 || cfg->shard_rank >= cfg->n_shards)
-    return fail(FFM_E_INVALID, "invalid n_shards / shard_rank");
-  if (cfg->n_shards > 1 && cfg->model_type != FFM_MODEL_FFM)
-    return fail(FFM_E_UNSUPPORTED, "field-pair sharding applies to FFM only");
-  if (cfg->n_shards > 1 && cfg->n_fields > 64)
-    return fail(FFM_E_UNSUPPORTED, "field-pair sharding supports up to 64 fields");
-  // FFM_FLAG_SERVE_F32 / _F16: a serving engine (engine_serve.h) -- its shape is checked like the arguments above
-  const int serve_fmt = (cfg->flags & FFM_FLAG_SERVE_F32 ? SERVE_F32 : 0) | (cfg->flags & FFM_FLAG_SERVE_F16 ? SERVE_F16 : 0);
-  if (serve_fmt)
-    if (int rc_s = serve_create_check(cfg)) return rc_s;
-  // (an argument error like the ones above: reported whether or not there is a device)
-  if (hash_ids)
-    if (int rc_h = hash_ids_check(cfg->model_type, cfg->n_feats, cfg->n_fields, cfg->field_start)) return rc_h;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-    return fail(FFM_E_DEVICE, "no HIP device available (this library has no CPU fallback)");
-  if (cfg->device_id < 0 || cfg->device_id >= n_dev)
-    return fail(FFM_E_INVALID, "device_id out of range");
-  HIP_TRY(hipSetDevice(cfg->device_id));
-
-  ffm_engine *e = new (std::nothrow) ffm_engine;
-  if (!e) return fail(FFM_E_NOMEM, "host allocation failed");
-  e->cfg = *cfg;
-  if (hash_ids) e->cfg.flags |= FFM_FLAG_HASH_IDS;
-  e->hash_ids = hash_ids;
-  e->max_rows = cfg->max_batch_rows;
-  e->max_nnz = cfg->max_batch_nnz;
-  if (cfg->max_row_nnz > 0) e->max_row_nnz = cfg->max_row_nnz;
-  else if (serve_fmt) e->max_row_nnz = kPredLdsCap;  // (a serving engine's rows are one wave's: no longer ones)
-  if (const char *sv = std::getenv("FFM_ENGINE_SERIAL")) e->serial = sv[0] == '1';
-  if (const char *sv = std::getenv("FFM_UPDATE_SPLIT")) e->update_split = std::atoi(sv);
-  if (const char *sv = std::getenv("FFM_UPDATE_ORDER")) {
-    // a permutation of the digits {0, 1, 2} (first range last) or nothing: any other value would run
-    // one range of the update launch twice and drop another
-    const int o = std::atoi(sv);
-    const int d0 = o % 10, d1 = o / 10 % 10, d2 = o / 100;
-    if (o >= 0 && d2 <= 2 && d0 <= 2 && d1 <= 2 && d0 != d1 && d0 != d2 && d1 != d2) e->update_order = o;
-  }
-  if (const char *sv = std::getenv("FFM_SUPER_WAIT")) e->super_wait = sv[0] != '0';
-  if (const char *sv = std::getenv("FFM_PREP_AFTER_ROW")) e->prep_after_row = sv[0] == '1';
-  if (const char *sv = std::getenv("FFM_EVAL_DEFER")) e->eval_defer_off = sv[0] == '0';
-  if (const char *sv = std::getenv("FFM_PREDICT_WAVE")) e->predict_waves = std::atoi(sv) != 0;
-  if (const char *sv = std::getenv("FFM_WIDE_NNZ")) e->wide_max_nnz = std::atoi(sv);
-  if (const char *sv = std::getenv("FFM_GRID_PULL")) e->grid_pull = std::max(1, std::atoi(sv));
-  if (const char *sv = std::getenv("FFM_GRID_PUSH")) e->grid_push = std::min(24, std::max(1, std::atoi(sv)));
-  if (const char *sv = std::getenv("FFM_GRID_HOT")) e->grid_hot = std::max(1, std::atoi(sv));
-  if (const char *sv = std::getenv("FFM_GRID_SMALL")) e->grid_small = std::max(1, std::atoi(sv));
-  if (const char *sv = std::getenv("FFM_GRID_WALK")) e->grid_walk = std::max(1, std::atoi(sv));
-  if (const char *sv = std::getenv("FFM_GRID_GIANT")) e->grid_giant = std::max(1, std::atoi(sv));
-  // (a sharded rank's row holds 1/n_shards of the pairs and facts, walked directly; 64-thread row
-  // workgroups measured the same as 256)
-  // a shard's row holds ~1/n_shards of the pairs: one wave per row, so that (with the small LDS
-  // footprint of short rows) many more rows are in flight per CU
-  if (cfg->n_shards > 1) e->row_threads = 64;
-  if (const char *sv = std::getenv("FFM_ROW_THREADS")) e->row_threads = std::max(64, std::min(kRowMaxThreads, std::atoi(sv) / 64 * 64));
-  if (const char *sv = std::getenv("FFM_ROW_PARK")) e->row_park = std::atoi(sv);
-  if (const char *sv = std::getenv("FFM_ROW_PARK_BUDGET")) e->row_park_budget = std::atoi(sv);
-  if (const char *sv = std::getenv("FFM_ROW_HOLD")) e->row_hold = std::max(0, std::atoi(sv));
-  // (the lean once-only kernel of a compact shard holds six waves per SIMD: 1152 workgroups
-  // measured 2.5 % per step better than 768 on an 8-GPU rank's blocks)
-  if (cfg->n_shards > 1) e->grid_single = 1152;
-  // (... and its flat few-occurrence kernel, 126 VGPRs = four waves per SIMD, fills the chip at 1024
-  // workgroups: an emulated rank's step 1.615 -> 1.605 ms)
-  if (cfg->n_shards > 1 && !std::getenv("FFM_GRID_SMALL")) e->grid_small = 1024;
-
-  {
-    const char *rr = std::getenv("FFM_ENGINE_ROW_REFRESH");
-    const int64_t per = cfg->n_factors % 4 == 0 ? static_cast<int64_t>(cfg->n_fields) * cfg->n_factors / 4
-                                                : static_cast<int64_t>(cfg->n_fields) * cfg->n_factors;
-    e->pre_refresh = cfg->model_type == FFM_MODEL_FFM && cfg->n_fields <= 64 &&
-                     static_cast<int64_t>(e->max_nnz) * per < (1ll << 31) && !(rr && rr[0] == '1');
-    if (rr && rr[0] == '0') e->refresh_mode = 1;
-    if (rr && rr[0] == '2') e->refresh_mode = 2;
-    if (rr && rr[0] == '3') e->refresh_mode = 3;
-  }
-  ModelDev &m = e->m;
-  m.type = cfg->model_type;
-  m.n_feats = cfg->n_feats;
-  m.n_fields = cfg->model_type == FFM_MODEL_FFM ? cfg->n_fields : 1;
-  m.n_factors = cfg->model_type == FFM_MODEL_LR ? 0 : cfg->n_factors;
-  e->logical_len = cfg->model_type == FFM_MODEL_FFM ? cfg->n_fields * cfg->n_factors
-                   : cfg->model_type == FFM_MODEL_FM ? cfg->n_factors : 0;
-  m.n_shards = cfg->n_shards;
-  m.shard_rank = cfg->shard_rank;
-  m.bias_own = 1;
-  m.huge_min = kHugeMin;
-  m.giant_min = cfg->model_type == FFM_MODEL_FM ? kFmGiantMin : kGiantMin;
-  m.range_len = cfg->model_type == FFM_MODEL_FM ? kFmRange : kRange;
-  m.huge_min = std::min(m.huge_min, m.giant_min - 1);  // (the lists: big <= huge_min < huge < giant_min <= giant)
-  m.super_min = kSuperMin;
-  if (const char *sv = std::getenv("FFM_SUPER_MIN")) m.super_min = std::max(kGiantMin, std::atoi(sv));
-  m.few_stage = 1;
-  m.lat_fmt = serve_fmt;
-  if (const char *sv = std::getenv("FFM_FEW_STAGE")) m.few_stage = sv[0] != '0';
-  m.rec_slots = m.n_fields;
-  e->n_records = cfg->n_feats;
-  // field-pair partition: this shard's ranges, and (with per-field id ranges) compact storage
-  ShardPlan plan;
-  const bool compact = cfg->n_shards > 1 && cfg->field_start != nullptr;
-  if (cfg->field_start && cfg->model_type == FFM_MODEL_FFM) {
-    e->field_start.assign(cfg->field_start, cfg->field_start + cfg->n_fields + 1);
-    bool ok = e->field_start[0] == 0 && e->field_start[cfg->n_fields] == cfg->n_feats;
-    for (int f = 0; f < cfg->n_fields; f++) ok = ok && e->field_start[f] <= e->field_start[f + 1];
-    if (!ok) { delete e; return fail(FFM_E_INVALID, "field_start must ascend from 0 to n_feats"); }
-  }
-  if (cfg->n_shards > 1) {
-    plan = make_shard_plan(cfg->n_fields, cfg->n_shards, compact);
-    m.bias_own = plan.bias_owner == cfg->shard_rank ? 1 : 0;
-    if (compact) {
-      int widest = 1;
-      for (int f = 0; f < cfg->n_fields; f++) widest = std::max(widest, plan.n(cfg->shard_rank, f));
-      m.rec_slots = widest;
-      e->n_records = 0;
-      for (int f = 0; f < cfg->n_fields; f++)
-        if (plan.n(cfg->shard_rank, f) > 0) e->n_records += e->field_start[f + 1] - e->field_start[f];
-      if (e->n_records == 0) e->n_records = 1;
-    }
-  }
-  m.row_len = cfg->model_type == FFM_MODEL_FFM ? m.rec_slots * cfg->n_factors
-              : cfg->model_type == FFM_MODEL_FM ? cfg->n_factors : 0;
-  m.h = Hyper{cfg->w_alpha, cfg->w_beta, cfg->w_l1, cfg->w_l2, 1.0f / cfg->w_alpha, 0,
-              (cfg->flags & FFM_FLAG_LEARN) ? 1 : 0};
-  if (static_cast<int64_t>(cfg->n_fields) * cfg->n_factors > (1 << 24))
-    { delete e; return fail(FFM_E_UNSUPPORTED, "n_fields*n_factors too large"); }
-  if (static_cast<int64_t>(cfg->max_batch_nnz) / (kSmallMax + 1) * ((m.row_len + 7) / 8 + 1) >= (1ll << 31))
-    { delete e; return fail(FFM_E_UNSUPPORTED, "max_batch_nnz * row_len too large for 32-bit work-item ids"); }
-
-  int rc = FFM_OK;
-#define TRY_ALLOC(call) do { rc = (call); if (rc != FFM_OK) { ffm_engine_destroy(e); return rc; } } while (0)
-#define TRY_HIP(expr) do { hipError_t err__ = (expr); if (err__ != hipSuccess) { \
-    rc = fail(FFM_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(err__)); \
-    ffm_engine_destroy(e); return rc; } } while (0)
-  if (cfg->stream) {
-    e->stream = static_cast<hipStream_t>(cfg->stream);
-  } else {
-    TRY_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    e->own_stream = true;
-  }
-  // (priority streams for the hot / very hot update: measured +45 % per step; for the look-ahead
-  // grouping: the same)
-  TRY_HIP(hipStreamCreateWithFlags(&e->aux3, hipStreamNonBlocking));
-  TRY_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-  TRY_HIP(hipEventCreateWithFlags(&e->ev_fork2, hipEventDisableTiming));
-  TRY_HIP(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-  TRY_HIP(hipEventCreateWithFlags(&e->ev_join2, hipEventDisableTiming));
-  TRY_HIP(hipStreamCreateWithFlags(&e->aux4, hipStreamNonBlocking));
-  const size_t nf = static_cast<size_t>(cfg->n_feats);
-  // floats allocated for the latent part: records of (n, z, w), or a serving engine's table of w alone in
-  // 4- or 2-byte elements (row_len is a multiple of 4 there) -- and then no (n, z) of the bias or the linear part
-  const size_t n_w = static_cast<size_t>(e->n_records) * static_cast<size_t>(m.row_len);
-  const size_t n_lat = serve_fmt == SERVE_F16 ? n_w / 2 : serve_fmt == SERVE_F32 ? n_w : 3 * n_w;
-  const size_t n_bias = serve_fmt ? 1 : 4;
-  TRY_ALLOC(e->alloc(&m.bias3, n_bias));
-  if (!serve_fmt) {
-    TRY_ALLOC(e->alloc(&m.lin_n, nf));
-    TRY_ALLOC(e->alloc(&m.lin_z, nf));
-  }
-  TRY_ALLOC(e->alloc(&m.lin_w, nf));
-  TRY_ALLOC(e->alloc(&m.lat, n_lat));
-  const size_t R = static_cast<size_t>(e->max_rows), E = static_cast<size_t>(e->max_nnz);
-  Scratch &s = e->sc[0];
-  TRY_ALLOC(e->alloc(&s.key, E));
-  TRY_ALLOC(e->alloc(&s.skey, E));
-  TRY_ALLOC(e->alloc(&s.row_of, E));
-  TRY_ALLOC(e->alloc(&s.occ, E));
-  TRY_ALLOC(e->alloc(&s.occ2, E));
-  TRY_ALLOC(e->alloc(&s.udesc, E));
-  TRY_ALLOC(e->alloc(&s.small, E));
-  TRY_ALLOC(e->alloc(&s.few, E));
-  TRY_ALLOC(e->alloc(&s.sdesc, E));
-  TRY_ALLOC(e->alloc(&s.big, E));
-  TRY_ALLOC(e->alloc(&s.huge, E));
-  TRY_ALLOC(e->alloc(&s.giant, E / kChainMin + 1));
-  TRY_ALLOC(e->alloc(&s.gseg, E / kChainMin + 1));
-  TRY_ALLOC(e->alloc(&s.grange, E / kFmRange + E / kFmGiantMin + 2));
-  {
-    // partial sums of the giant features' folds (shared by the scratch sets)
-    const size_t max_segs = E / kSeg + E / kFmGiantMin + 2, rl = static_cast<size_t>(std::max(1, m.row_len));
-    const bool lat_model = cfg->model_type != FFM_MODEL_LR, ffm_m = cfg->model_type == FFM_MODEL_FFM;
-    const size_t chunks = !ffm_m ? 1 : cfg->n_factors <= 64
-                              ? (static_cast<size_t>(m.rec_slots) + 64 / cfg->n_factors - 1) / (64 / cfg->n_factors)
-                              : static_cast<size_t>(m.rec_slots) * ((cfg->n_factors + 63) / 64);
-    TRY_ALLOC(e->alloc(&s.segP, lat_model ? max_segs * rl : 1));
-    TRY_ALLOC(e->alloc(&s.segG, lat_model ? max_segs * rl : 1));
-    TRY_ALLOC(e->alloc(&s.segD, ffm_m ? max_segs * rl : 1));
-    TRY_ALLOC(e->alloc(&s.segF, ffm_m ? max_segs * chunks * 3 : 1));
-    TRY_ALLOC(e->alloc(&s.gcap, ffm_m ? (E / kGiantMin + 2) * rl : 1));
-  }
-  TRY_ALLOC(e->alloc(&s.counters, kNumCounters));
-  TRY_ALLOC(e->alloc(&e->d_err, 1));
-  TRY_HIP(hipMemsetAsync(e->d_err, 0, sizeof(int), e->stream));
-  s.err = e->d_err;
-  TRY_ALLOC(e->alloc(&e->d_ids, static_cast<size_t>(ffm_engine::kIdsCap)));
-  TRY_ALLOC(e->alloc(&s.head, R * static_cast<size_t>(m.n_fields)));
-  TRY_ALLOC(e->alloc(&s.next, E));
-  TRY_ALLOC(e->alloc(&s.rowtab, R * static_cast<size_t>(m.n_fields)));
-  TRY_ALLOC(e->alloc(&s.occpos, E));
-  TRY_ALLOC(e->alloc(&s.uflag, E));
-  const bool ffm_model = m.type == FFM_MODEL_FFM;
-  const bool masks = ffm_model && m.n_fields <= 64;
-  if (masks) {
-    TRY_ALLOC(e->alloc(&s.rowmask, 2 * R));
-    TRY_ALLOC(e->alloc(&s.gmask, E));
-    TRY_ALLOC(e->alloc(&s.cmask, E));
-    std::vector<unsigned long long> own(m.n_fields, 0ull);
-    for (int fa = 0; fa < m.n_fields; fa++)
-      for (int fb = 0; fb < m.n_fields; fb++)
-        if (m.n_shards <= 1 || plan.owns(m.shard_rank, fa, fb)) own[fa] |= 1ull << fb;
-    TRY_ALLOC(e->alloc(&e->d_ownmask, static_cast<size_t>(m.n_fields)));
-    TRY_HIP(hipMemcpy(e->d_ownmask, own.data(), own.size() * sizeof(own[0]), hipMemcpyHostToDevice));
-    m.ownmask = e->d_ownmask;
-  }
-  if (m.n_shards > 1) {
-    // this shard's ranges (and, compact, the record index of every kept field) on the device
-    const int F = m.n_fields, r = m.shard_rank;
-    std::vector<int> lo(F), cnt(F), lin(F);
-    std::vector<long long> base(F, -1);
-    long long next = 0;
-    for (int f = 0; f < F; f++) {
-      lo[f] = plan.lo(r, f);
-      cnt[f] = plan.n(r, f);
-      lin[f] = plan.lin_owner[f] == r ? 1 : 0;
-      if (compact && cnt[f] > 0) { base[f] = next; next += e->field_start[f + 1] - e->field_start[f]; }
-    }
-    int *d_lo = nullptr, *d_n = nullptr, *d_lin = nullptr;
-    TRY_ALLOC(e->alloc(&d_lo, lo.size()));
-    TRY_ALLOC(e->alloc(&d_n, cnt.size()));
-    TRY_ALLOC(e->alloc(&d_lin, lin.size()));
-    TRY_HIP(hipMemcpy(d_lo, lo.data(), lo.size() * sizeof(int), hipMemcpyHostToDevice));
-    TRY_HIP(hipMemcpy(d_n, cnt.data(), cnt.size() * sizeof(int), hipMemcpyHostToDevice));
-    TRY_HIP(hipMemcpy(d_lin, lin.data(), lin.size() * sizeof(int), hipMemcpyHostToDevice));
-    m.own_lo = d_lo;
-    m.own_n = d_n;
-    m.lin_own = d_lin;
-    e->lin_any = std::any_of(lin.begin(), lin.end(), [](int v) { return v != 0; });
-    if (compact) {
-      int *d_fs = nullptr;
-      long long *d_base = nullptr;
-      TRY_ALLOC(e->alloc(&d_fs, e->field_start.size()));
-      TRY_ALLOC(e->alloc(&d_base, base.size()));
-      TRY_HIP(hipMemcpy(d_fs, e->field_start.data(), e->field_start.size() * sizeof(int), hipMemcpyHostToDevice));
-      TRY_HIP(hipMemcpy(d_base, base.data(), base.size() * sizeof(long long), hipMemcpyHostToDevice));
-      m.field_start = d_fs;
-      m.rec_base = d_base;
-    }
-  }
-  if (e->hash_ids) {
-    e->hm = ftrl_hash::Map{nullptr, cfg->n_feats, m.n_fields, m.type == FFM_MODEL_FFM ? 1 : 0};
-    if (!e->field_start.empty()) {  // (kept for FFM only; widths checked above)
-      TRY_ALLOC(e->alloc(&e->d_hash_start, e->field_start.size()));
-      TRY_HIP(hipMemcpy(e->d_hash_start, e->field_start.data(), e->field_start.size() * sizeof(int), hipMemcpyHostToDevice));
-      e->hm.start = e->d_hash_start;
-    }
-  }
-  TRY_ALLOC(e->alloc(&s.logit, R));
-  TRY_ALLOC(e->alloc(&s.tg, R));
-  TRY_ALLOC(e->alloc(&s.loss, R));
-  TRY_ALLOC(e->alloc(&s.svx, R * static_cast<size_t>(m.type == FFM_MODEL_FM ? m.n_factors : 1)));
-  {
-    // stable LSD radix sort of (feature id, entry) pairs: key bits = those of the sentinel n_feats
-    e->sort_bits = 1;
-    while (e->sort_bits < 32 && (static_cast<uint64_t>(cfg->n_feats) >> e->sort_bits) != 0) e->sort_bits++;
-    TRY_HIP(rocprim::radix_sort_pairs<GroupSortConfig>(nullptr, e->sort_tmp_bytes, s.key, s.skey,
-                                      rocprim::counting_iterator<int>(0), s.occ, E, 0u, e->sort_bits,
-                                      e->stream));
-    e->sort_tmp_bytes = std::max(e->sort_tmp_bytes, sort_scratch_bytes(E));
-    unsigned char *tmp = nullptr;
-    TRY_ALLOC(e->alloc(&tmp, e->sort_tmp_bytes));
-    e->d_sort_tmp[0] = tmp;
-  }
-  {
-    TRY_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->h_super), sizeof(int) * ffm_engine::kSets, hipHostMallocMapped));
-    std::memset(e->h_super, 0, sizeof(int) * ffm_engine::kSets);
-    int *d_super = nullptr;
-    TRY_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&d_super), e->h_super, 0));
-    s.n_super = d_super;
-    // The host skips the longest features' two extra launches when it reads 0 here -- which is only
-    // safe if a device store to this mapping actually lands: prove it once, else the
-    // launches are always made.
-    hipLaunchKernelGGL(host_word_probe_kernel, dim3(1), dim3(64), 0, e->stream, d_super, ffm_engine::kSets);
-    TRY_HIP(hipStreamSynchronize(e->stream));
-    e->super_flag_ok = true;
-    for (int si = 0; si < ffm_engine::kSets; si++) e->super_flag_ok = e->super_flag_ok && e->h_super[si] == 0x5eed + si;
-    std::memset(e->h_super, 0, sizeof(int) * ffm_engine::kSets);
-  }
-  for (int si = 1; si < ffm_engine::kSets; si++) {
-    Scratch &t = e->sc[si];
-    t = s;  // shared: head/next/rowtab/logit/tg/loss/svx
-    t.n_super = s.n_super + si;
-    TRY_ALLOC(e->alloc(&t.key, E));
-    TRY_ALLOC(e->alloc(&t.skey, E));
-    TRY_ALLOC(e->alloc(&t.row_of, E));
-    TRY_ALLOC(e->alloc(&t.occ, E));
-    TRY_ALLOC(e->alloc(&t.occ2, E));
-    TRY_ALLOC(e->alloc(&t.udesc, E));
-    TRY_ALLOC(e->alloc(&t.small, E));
-    TRY_ALLOC(e->alloc(&t.few, E));
-    TRY_ALLOC(e->alloc(&t.sdesc, E));
-    TRY_ALLOC(e->alloc(&t.big, E));
-    TRY_ALLOC(e->alloc(&t.huge, E));
-    TRY_ALLOC(e->alloc(&t.giant, E / kChainMin + 1));
-    TRY_ALLOC(e->alloc(&t.gseg, E / kChainMin + 1));
-    TRY_ALLOC(e->alloc(&t.grange, E / kFmRange + E / kFmGiantMin + 2));
-    TRY_ALLOC(e->alloc(&t.counters, kNumCounters));
-    TRY_ALLOC(e->alloc(&t.occpos, E));
-    TRY_ALLOC(e->alloc(&t.uflag, E));
-    if (masks) {
-      TRY_ALLOC(e->alloc(&t.rowmask, 2 * R));
-      TRY_ALLOC(e->alloc(&t.gmask, E));
-      TRY_ALLOC(e->alloc(&t.cmask, E));
-    }
-    unsigned char *tmp = nullptr;
-    TRY_ALLOC(e->alloc(&tmp, e->sort_tmp_bytes));
-    e->d_sort_tmp[si] = tmp;
-    TRY_HIP(hipMemsetAsync(t.counters, 0, kNumCounters * sizeof(int), e->stream));
-  }
-  TRY_HIP(hipStreamCreateWithFlags(&e->prep, hipStreamNonBlocking));
-  // Which sort the grouping uses depends on how long a step of this engine is (estimated from the
-  // largest block the engine was sized for).  Short steps wait for the look-ahead queue's chain of ~17
-  // launches one to one (FM k = 64: 0.32 ms per step of which 0.23 ms are its two kernels) and take the
-  // one-launch sort of kernels_sort.h (FM 0.323 -> 0.294 ms, FFM 8 x 16 at 4096 rows 0.139 -> 0.122); a
-  // long FFM step is saturated by its row kernel, a sort that actually runs beside it slows it (r05:
-  // 1.048 -> 1.094 ms), and the library sort's 1024-thread workgroups -- which only find room in the
-  // gaps -- are the better neighbour.  FFM 39 x 4 is the crossover (no difference).
-  // The upload kernel runs on the prep queue, ahead of the block's grouping.  (Round 4 moved it, for
-  // long steps, behind the update's chain kernel on that kernel's stream; the update is one launch on
-  // the main stream now and that stream is otherwise empty: 1.060 ms there, 1.048 ms on the prep
-  // queue.)
-  {
-    const double per_row = e->max_rows > 0 ? static_cast<double>(e->max_nnz) / e->max_rows : 0.0;
-    const double phase_us = static_cast<double>(e->max_nnz) * std::max(0.0, per_row - 1.0) * m.n_factors / 0.44e6;
-    const bool ffm4 = m.type == FFM_MODEL_FFM && m.n_factors % 4 == 0;
-    e->copy = e->prep;
-    e->own_sort = !(ffm4 && phase_us / std::max(1, m.n_shards) >= 100.0);  // (a shard does 1/n_shards of the pairs)
-    if (const char *sv = std::getenv("FFM_OWN_SORT")) e->own_sort = std::atoi(sv) != 0;
-    // The fields' id ranges are known (cfg->field_start): every range is sorted by a workgroup of its
-    // own, one launch, no grid barrier (kernels_sort.h: group_sort_ranges_kernel).  FFM_RANGE_SORT=0/1
-    // overrides; 1 without field_start cuts the id space into n_fields equal ranges (a block whose ids
-    // crowd into one of them is still sorted correctly, by one workgroup).
-    {
-      const char *sv = std::getenv("FFM_RANGE_SORT");
-      const bool have = !e->field_start.empty();
-      // (by default only where a workgroup per range is quick: a whole model -- a compact shard's dropped
-      // columns make every block irregular, so every workgroup would scan all keys twice -- and at most
-      // 16 k entries per range -- a rank's 65 536-row blocks are 256 tiles per pass for ONE workgroup:
-      // an emulated 8-GPU rank went 1.72 -> 2.25 ms per step with it)
-      const bool quick = cfg->n_shards == 1 && static_cast<int64_t>(e->max_nnz) <= 16384ll * std::max(1, cfg->n_fields);
-      const bool want = sv ? std::atoi(sv) != 0 : (have && quick);
-      if (want && (m.type == FFM_MODEL_FFM || sv)) {
-        const int nr = have ? cfg->n_fields : (sv && std::atoi(sv) > 1 ? std::min(1024, std::atoi(sv)) : std::max(1, std::min(64, cfg->n_fields)));
-        std::vector<int> st(static_cast<size_t>(nr) + 1);
-        for (int f = 0; f <= nr; f++)
-          st[f] = have ? e->field_start[f] : static_cast<int>(static_cast<int64_t>(cfg->n_feats) * f / nr);
-        TRY_ALLOC(e->alloc(&e->d_sort_start, st.size()));
-        TRY_HIP(hipMemcpy(e->d_sort_start, st.data(), st.size() * sizeof(int), hipMemcpyHostToDevice));
-        e->n_sort_ranges = nr;
-        e->range_sort = true;
-        // (the regular-block short cut needs range f to be field f's: only with the caller's field_start)
-        if (have && m.type == FFM_MODEL_FFM) m.sort_start = e->d_sort_start;
-        // ... and its look-ahead starts when the ROW kernel of the block enqueued last has ended, beside
-        // that block's update launches (half of their wave slots are free, and they are not bound by
-        // bandwidth) instead of at the block's end, beside the next block's saturated row kernel -- where
-        // this sort, unlike the library's (whose 1024-thread workgroups wait for a CU to drain and so only
-        // ever fill gaps), costs the row kernel 5 %: C5 driver shape 0.970 -> 0.949 ms, C3 0.531 -> 0.521
-        // (profiles/r06_experiments.md).  FFM_PREP_AFTER_ROW=0/1 overrides.
-        // (long steps only: a 4096 x 8 block's update phase is 70 us, shorter than the chain)
-        if (!std::getenv("FFM_PREP_AFTER_ROW")) e->prep_after_row = !e->own_sort;
-        // ... and from 4 M slot-factors per block on the block's upload waits for that event as well (C5: the
-        // driver's 20-step shape 0.887-0.896 -> 0.877-0.884 ms, 200 steps 0.870 -> 0.868; C3, 1.2 M: 0.472 ->
-        // 0.478, not taken).  FFM_PULL_AFTER_ROW=0/1 overrides.
-        e->pull_after_row = e->prep_after_row && static_cast<int64_t>(e->max_nnz) * m.n_factors >= (1ll << 22);
-        if (const char *pv = std::getenv("FFM_PULL_AFTER_ROW")) e->pull_after_row = pv[0] == '1';
-      }
-    }
-    // the one-launch sort meets at a grid barrier: never more workgroups than the device holds of it,
-    // and only on the architecture its hand-over of data between workgroups was validated on
-    {
-      hipDeviceProp_t prop;
-      TRY_HIP(hipGetDeviceProperties(&prop, cfg->device_id));
-      int per_cu = 0;
-      TRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, group_sort_kernel, kSortThreads, 0));
-      e->sort_grid_cap = std::max(1, per_cu * prop.multiProcessorCount);
-      if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0 && std::strncmp(prop.gcnArchName, "gfx942", 6) != 0) e->own_sort = false;
-    }
-  }
-  for (int i = 0; i < ffm_engine::kSets; i++) {
-    TRY_HIP(hipEventCreateWithFlags(&e->ev_grouped[i], hipEventDisableTiming));
-    TRY_HIP(hipEventCreateWithFlags(&e->ev_set_free[i], hipEventDisableTiming));
-    TRY_HIP(hipEventCreateWithFlags(&e->ev_row_done[i], hipEventDisableTiming));
-  }
-  TRY_ALLOC(e->alloc(&e->d_row_ptr, R + 1));
-  TRY_ALLOC(e->alloc(&e->d_field, E));
-  TRY_ALLOC(e->alloc(&e->d_feat, E));
-  TRY_ALLOC(e->alloc(&e->d_val, E));
-  TRY_ALLOC(e->alloc(&e->d_label, R));
-  TRY_ALLOC(e->alloc(&e->d_out, R));
-  TRY_ALLOC(e->alloc(&e->d_loss_sum, 2));
-  TRY_ALLOC(e->alloc(&e->d_loss_part, kLossParts + 1));
-  TRY_HIP(hipMemsetAsync(e->d_loss_part, 0, sizeof(double) * (kLossParts + 1), e->stream));
-  e->stage_floats = 16 << 20;  // 64 MiB dense staging for get/set
-  if (static_cast<int64_t>(e->logical_len) > e->stage_floats) e->stage_floats = e->logical_len;
-  TRY_ALLOC(e->alloc(&e->d_stage, static_cast<size_t>(e->stage_floats)));
-
-  TRY_HIP(hipMemsetAsync(m.bias3, 0, n_bias * sizeof(float), e->stream));
-  if (!serve_fmt) {
-    TRY_HIP(hipMemsetAsync(m.lin_n, 0, nf * sizeof(float), e->stream));
-    TRY_HIP(hipMemsetAsync(m.lin_z, 0, nf * sizeof(float), e->stream));
-  }
-  TRY_HIP(hipMemsetAsync(m.lin_w, 0, nf * sizeof(float), e->stream));
-  if (n_lat) TRY_HIP(hipMemsetAsync(m.lat, 0, n_lat * sizeof(float), e->stream));
-  TRY_HIP(hipMemsetAsync(s.counters, 0, kNumCounters * sizeof(int), e->stream));
-  {
-    // the five-instruction square root rests on this device's v_sqrt_f32 / v_rsq_f32: compare it
-    // with sqrtf over its whole range (1.6e9 inputs, a few milliseconds) before any kernel uses it
-    // (once per device and process: the answer is a property of the hardware)
-    static std::atomic<int> verdict[64];  // 0 unknown, 1 exact, -1 differs
-    const int dev = cfg->device_id & 63;
-    int bad = verdict[dev].load() < 0 ? 1 : 0;
-    if (verdict[dev].load() == 0) {
-      hipLaunchKernelGGL(verify_sqrt_fast_kernel, dim3(16384), dim3(256), 0, e->stream, s.counters);
-      TRY_HIP(hipMemcpyAsync(&bad, s.counters, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-      TRY_HIP(hipStreamSynchronize(e->stream));
-      TRY_HIP(hipMemsetAsync(s.counters, 0, kNumCounters * sizeof(int), e->stream));
-      verdict[dev].store(bad ? -1 : 1);
-    }
-    if (bad) {
-      ffm_engine_destroy(e);
-      return fail(FFM_E_UNSUPPORTED, "this device's v_sqrt_f32 / v_rsq_f32 do not give the correctly rounded "
-                                     "square root in the short sequence the kernels use (built and proven for gfx950)");
-    }
-  }
-  if (cfg->w_alpha >= 0x1p-30f && cfg->w_alpha <= 0x1p30f) {
-    // prove the short x/alpha sequence exact for this alpha before any kernel may use it
-    int bad = 0;
-    Hyper probe = m.h;
-    probe.fast_div = 1;
-    hipLaunchKernelGGL(verify_div_alpha_kernel, dim3(1u << 17), dim3(256), 0, e->stream, probe, s.counters);
-    TRY_HIP(hipMemcpyAsync(&bad, s.counters, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    TRY_HIP(hipStreamSynchronize(e->stream));
-    TRY_HIP(hipMemsetAsync(s.counters, 0, kNumCounters * sizeof(int), e->stream));
-    m.h.fast_div = bad ? 0 : 1;
-    m.h.fast_w = m.h.fast_div && cfg->w_beta >= 0x1p-40f && cfg->w_beta <= 0x1p40f ? 1 : 0;
-  }
-  {
-    // the row kernels stage one row in dynamic LDS: opt in to what the longest admissible row needs
-    const size_t lds = row_lds_bytes(e->max_row_nnz, m.n_fields, kTermsCap);
-    if (lds > 150 * 1024) {
-      ffm_engine_destroy(e);
-      return fail(FFM_E_UNSUPPORTED, "max_row_nnz too large for the 160 KB of LDS per workgroup");
-    }
-    const size_t park_budget = static_cast<size_t>(std::max(0, e->row_park_budget));
-    if (lds > 32 * 1024 || park_budget > 32 * 1024) {
-      const int bytes = static_cast<int>(std::max(lds, park_budget));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 2, const float *>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 4, const float *>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 6, const float *>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, true, 8, const float *>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_row_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fm_row_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fm_row_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    }
-    // the FFM update launch: the tile pipelines' per-wave LDS regions of its (up to 16-wave) workgroups
-    TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_update_all_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_lds_bytes(1))));
-    TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_update_all_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_lds_bytes(2))));
-    TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_update_all_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_lds_bytes(4))));
-    TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_update_all_kernel<1, UPD_ALL & ~UPD_FEW>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_lds_bytes(1))));
-    TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_update_all_kernel<2, UPD_ALL & ~UPD_FEW>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_lds_bytes(2))));
-    TRY_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ffm_update_all_kernel<4, UPD_ALL & ~UPD_FEW>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(tile_lds_bytes(4))));
-  }
-  if (serve_fmt) {
-    if (!(cfg->flags & FFM_FLAG_SKIP_INIT))
-      hipLaunchKernelGGL(serve_init_kernel, dim3(2048), dim3(256), 0, e->stream, m, cfg->init_mean, cfg->init_stddev, cfg->seed);
-  } else if (!(cfg->flags & FFM_FLAG_SKIP_INIT))
-    hipLaunchKernelGGL(init_weights_kernel, dim3(2048), dim3(256), 0, e->stream, m, e->logical_len,
-                       cfg->init_mean, cfg->init_stddev, cfg->seed);
-  TRY_HIP(hipGetLastError());
-  TRY_HIP(hipStreamSynchronize(e->stream));
-#undef TRY_ALLOC
-#undef TRY_HIP
-  // FFM_ENGINE_METRICS=<mask>: channels on from the start (rank 0 of a group keeps them)
-  if (const char *sv = std::getenv("FFM_ENGINE_METRICS")) {
-    const int mask = std::atoi(sv) & 3;
-    if (mask && cfg->shard_rank == 0)
-      if (int rc_m = ffm_engine_metrics_enable(e, mask)) { ffm_engine_destroy(e); return rc_m; }
-  }
-  *out = e;
-  return FFM_OK;
-}
+#include "engine_create.h"
 
 // What init_weights_kernel stored, computed on the host (csrc/init_rng.h: same bits).
 static int eval_launch_pending(ffm_engine *e);  // (engine_stage.h)

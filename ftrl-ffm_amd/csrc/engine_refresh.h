@@ -21,15 +21,13 @@ int ffm_engine_refresh_weights(ffm_engine *e, ffm_refresh_stats *out) {
   if (int rc_d = check_device_errors(e)) return rc_d;
   if (!e->d_refresh)
     if (int rc = e->alloc(&e->d_refresh, static_cast<size_t>(RC_COUNT))) return rc;
+  const auto kernel = e->m.row_len % 4 == 0 ? refresh_weights_kernel<true> : refresh_weights_kernel<false>;
   if (e->refresh_grid == 0) {
     // as many workgroups as the chip holds at once (every workgroup does the same number of turns, so a
     // second, partly filled round would only lengthen the pass)
     int cus = 0, per_cu = 0;
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device_id));
-    if (e->m.row_len % 4 == 0)
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, refresh_weights_kernel<true>, kRefreshThreads, 0));
-    else
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, refresh_weights_kernel<false>, kRefreshThreads, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kRefreshThreads, 0));
     e->refresh_grid = std::max(1, cus) * std::max(1, per_cu);
   }
   // a persistent grid: never more workgroups than the chip holds, fewer only when the model has fewer lanes' work
@@ -37,10 +35,7 @@ int ffm_engine_refresh_weights(ffm_engine *e, ffm_refresh_stats *out) {
   const int64_t items = std::max<int64_t>(lat_items, (static_cast<int64_t>(e->m.n_feats) + 4) / 4);
   const int grid = static_cast<int>(std::min<int64_t>(e->refresh_grid, std::max<int64_t>(1, (items + kRefreshThreads - 1) / kRefreshThreads)));
   HIP_TRY(hipMemsetAsync(e->d_refresh, 0, RC_COUNT * sizeof(unsigned long long), e->stream));
-  if (e->m.row_len % 4 == 0)
-    hipLaunchKernelGGL(refresh_weights_kernel<true>, dim3(grid), dim3(kRefreshThreads), 0, e->stream, e->m, e->n_records, e->d_refresh);
-  else
-    hipLaunchKernelGGL(refresh_weights_kernel<false>, dim3(grid), dim3(kRefreshThreads), 0, e->stream, e->m, e->n_records, e->d_refresh);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRefreshThreads), 0, e->stream, e->m, e->n_records, e->d_refresh);
   HIP_TRY(hipGetLastError());
   unsigned long long h[RC_COUNT] = {};
   HIP_TRY(hipMemcpyAsync(h, e->d_refresh, sizeof(h), hipMemcpyDeviceToHost, e->stream));

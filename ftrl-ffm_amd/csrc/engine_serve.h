@@ -6,8 +6,8 @@
 
 static_assert(sizeof(ffm_pack_stats) == PK_COUNT * sizeof(int64_t), "the kernel and the ABI agree on the counters");
 
-// The shapes launch_predict_waves serves: FFM, a whole model on this device, k in {4, 8, 16, 32, 64}, rows
-// one wave stages.
+// The shapes the wave kernels serve (launch_row_waves, engine_step.h): FFM, a whole model on this device, a k
+// with a lane shape (engine_select.h: 4, 8, 16, 32, 64), rows one wave stages.
 static int serve_create_check(const ffm_engine_config *cfg) {
   if ((cfg->flags & FFM_FLAG_SERVE_F32) && (cfg->flags & FFM_FLAG_SERVE_F16))
     return fail(FFM_E_INVALID, "FFM_FLAG_SERVE_F32 and FFM_FLAG_SERVE_F16 exclude each other");
@@ -16,35 +16,9 @@ static int serve_create_check(const ffm_engine_config *cfg) {
                                    " entries (max_row_nnz): it has no kernel for longer ones");
   if (cfg->model_type != FFM_MODEL_FFM) return fail(FFM_E_UNSUPPORTED, "serving engines are FFM only (not LR / FM)");
   if (cfg->n_shards > 1) return fail(FFM_E_UNSUPPORTED, "a serving engine is one whole model on one device (n_shards == 1)");
-  const int k = cfg->n_factors;
-  if (k != 4 && k != 8 && k != 16 && k != 32 && k != 64)
+  if (!row_wave_fn(SERVE_F32, cfg->n_factors))
     return fail(FFM_E_UNSUPPORTED, "serving engines support n_factors 4, 8, 16, 32 or 64");
   return FFM_OK;
-}
-
-static void launch_serve_waves(ffm_engine *e, const Rows &rows, int row_cap, float *out, int output_prob) {
-  const ModelDev &m = e->m;
-  const int lds_cap = std::min(row_cap, kPredLdsCap);
-  const size_t shmem = pred_lds_bytes(lds_cap);
-  const int grid = cdiv(rows.n_rows, kPredRows), threads = 64 * kPredRows;
-  // (the lane shapes of launch_predict_waves, engine_step.h)
-#define SERVE_LAUNCH(LPP, VPL, U)                                                                                          \
-  do {                                                                                                                      \
-    if (m.lat_fmt == SERVE_F16)                                                                                             \
-      LAUNCH(e, K_SERVE_ROW, (ffm_serve_wave_kernel<SERVE_F16, LPP, VPL, U>), grid, threads, shmem, m, rows, e->sc[e->cur], \
-             row_cap, lds_cap, out, output_prob);                                                                           \
-    else                                                                                                                    \
-      LAUNCH(e, K_SERVE_ROW, (ffm_serve_wave_kernel<SERVE_F32, LPP, VPL, U>), grid, threads, shmem, m, rows, e->sc[e->cur], \
-             row_cap, lds_cap, out, output_prob);                                                                           \
-  } while (0)
-  switch (m.n_factors) {
-    case 4: SERVE_LAUNCH(1, 1, 4); break;
-    case 8: SERVE_LAUNCH(2, 1, 4); break;
-    case 16: SERVE_LAUNCH(FFM_PRED_LPP, 4 / FFM_PRED_LPP, FFM_PRED_U); break;
-    case 32: SERVE_LAUNCH(8, 1, 2); break;
-    default: SERVE_LAUNCH(16, 1, 1); break;  // 64 (create admits nothing else)
-  }
-#undef SERVE_LAUNCH
 }
 
 // ---- one context against many candidates (include/ffm_engine.h "Scoring candidates") --------------------
@@ -80,28 +54,11 @@ static int cand_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, con
   const int ctx_grid = cdiv(n_req, kPredRows), grid = cdiv(n_cand, kPredRows), threads = 64 * kPredRows;
   const Rows rows{n_cand, cand_nnz, cand_ptr, cand_field, cand_feat, cand_val, nullptr};
   int *err = e->d_err;
-  // (the lane shapes of launch_serve_waves)
-#define CAND_LAUNCH_FMT(FMT, LPP, VPL, U)                                                                                      \
-  do {                                                                                                                        \
-    LAUNCH(e, K_SERVE_CTX, (serve_context_kernel<FMT, LPP, VPL, U>), ctx_grid, threads, ctx_shmem, m, n_req, ctx_ptr,         \
-           ctx_field, ctx_feat, ctx_val, cand_req_ptr, n_cand, cx, e->max_row_nnz, ctx_lds, err);                             \
-    LAUNCH(e, K_SERVE_CAND, (serve_candidate_kernel<FMT, LPP, VPL, U>), grid, threads, shmem, m, n_req, ctx_ptr, cx, rows,    \
-           row_cap, lds_cap, err, out, output_prob);                                                                          \
-  } while (0)
-#define CAND_LAUNCH(LPP, VPL, U)                                       \
-  do {                                                                 \
-    if (m.lat_fmt == SERVE_F16) CAND_LAUNCH_FMT(SERVE_F16, LPP, VPL, U); \
-    else CAND_LAUNCH_FMT(SERVE_F32, LPP, VPL, U);                      \
-  } while (0)
-  switch (m.n_factors) {
-    case 4: CAND_LAUNCH(1, 1, 4); break;
-    case 8: CAND_LAUNCH(2, 1, 4); break;
-    case 16: CAND_LAUNCH(FFM_PRED_LPP, 4 / FFM_PRED_LPP, FFM_PRED_U); break;
-    case 32: CAND_LAUNCH(8, 1, 2); break;
-    default: CAND_LAUNCH(16, 1, 1); break;  // 64 (create admits nothing else)
-  }
-#undef CAND_LAUNCH
-#undef CAND_LAUNCH_FMT
+  // (never null on a serving engine: create admitted only a k that has these kernels, serve_create_check)
+  LAUNCH(e, K_SERVE_CTX, serve_context_fn(m.lat_fmt, m.n_factors), ctx_grid, threads, ctx_shmem, m, n_req, ctx_ptr, ctx_field,
+         ctx_feat, ctx_val, cand_req_ptr, n_cand, cx, e->max_row_nnz, ctx_lds, err);
+  LAUNCH(e, K_SERVE_CAND, serve_candidate_fn(m.lat_fmt, m.n_factors), grid, threads, shmem, m, n_req, ctx_ptr, cx, rows, row_cap,
+         lds_cap, err, out, output_prob);
   HIP_TRY(hipGetLastError());
   return FFM_OK;
 }
@@ -243,10 +200,8 @@ int ffm_engine_pack_weights(ffm_engine *dst, ffm_engine *src, ffm_pack_stats *ou
   const int64_t items = std::max<int64_t>(static_cast<int64_t>(src->m.n_feats) * (src->m.row_len / 4), src->m.n_feats);
   const int grid = static_cast<int>(std::min<int64_t>(std::max(1, cus) * 8, std::max<int64_t>(1, (items + kPackThreads - 1) / kPackThreads)));
   HIP_TRY(hipMemsetAsync(dst->d_pack, 0, PK_COUNT * kPackLine * sizeof(unsigned long long), dst->stream));
-  if (dst->m.lat_fmt == SERVE_F16)
-    hipLaunchKernelGGL(serve_pack_kernel<SERVE_F16>, dim3(grid), dim3(kPackThreads), 0, dst->stream, src->m, dst->m, dst->d_pack);
-  else
-    hipLaunchKernelGGL(serve_pack_kernel<SERVE_F32>, dim3(grid), dim3(kPackThreads), 0, dst->stream, src->m, dst->m, dst->d_pack);
+  const auto pack = dst->m.lat_fmt == SERVE_F16 ? serve_pack_kernel<SERVE_F16> : serve_pack_kernel<SERVE_F32>;
+  hipLaunchKernelGGL(pack, dim3(grid), dim3(kPackThreads), 0, dst->stream, src->m, dst->m, dst->d_pack);
   HIP_TRY(hipGetLastError());
   unsigned long long h[PK_COUNT * kPackLine] = {};
   HIP_TRY(hipMemcpyAsync(h, dst->d_pack, sizeof(h), hipMemcpyDeviceToHost, dst->stream));

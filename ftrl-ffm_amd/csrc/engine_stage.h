@@ -243,7 +243,7 @@ static int slots_init(ffm_engine *e) {
   *e->h_pulled = 0;
   HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&e->d_pulled), e->h_pulled, 0));
   if (int rc_t = e->alloc(&e->d_pull_ticket, 1)) return rc_t;
-  HIP_TRY(hipMemsetAsync(e->d_pull_ticket, 0, sizeof(unsigned), e->copy));
+  HIP_TRY(hipMemsetAsync(e->d_pull_ticket, 0, sizeof(unsigned), e->prep));
   HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_scored), 64, hipHostMallocPortable | hipHostMallocMapped));
   *e->h_scored = 0;
   HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&e->d_scored), e->h_scored, 0));
@@ -420,7 +420,7 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
     return rc;
   const int64_t seq = e->n_staged_total + 1;
   const int grid_pull = e->grid_pull;
-  const bool timed = !e->stage_thread_on || e->prof_on;
+  const bool timed = e->prof_on;  // (then submit runs the job on this thread)
   hipEvent_t free_ev = slot_was_used ? sl.free_ev : nullptr;
   const bool hashed = e->hash_ids;
   // (val == NULL: the upload writes the slot's values -- every time, whatever the slot held before)
@@ -433,22 +433,21 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
     int rc2 = FFM_OK;
     auto body = [&]() -> int {
       HIP_TRY(hipSetDevice(e->cfg.device_id));
-      if (free_ev) HIP_TRY(hipStreamWaitEvent(e->copy, free_ev, 0));  // nothing reads its device arrays
+      if (free_ev) HIP_TRY(hipStreamWaitEvent(e->prep, free_ev, 0));  // nothing reads its device arrays
       // (long steps: the upload too waits for the running block's row kernel to end -- beside the update
       // launches it costs nothing, beside the row kernel, which is bound by the bytes it moves, it does)
-      if (e->pull_after_row && plan.ws >= 0) HIP_TRY(hipStreamWaitEvent(e->copy, e->prep_after_row ? e->ev_row_done[plan.ws] : e->ev_set_free[plan.ws], 0));
+      if (e->pull_after_row && plan.ws >= 0) HIP_TRY(hipStreamWaitEvent(e->prep, e->prep_after_row ? e->ev_row_done[plan.ws] : e->ev_set_free[plan.ws], 0));
       if (n_ones) {
-        if (hashed && job.wbytes) hipLaunchKernelGGL(pull_block_weighted_hashed_ones_kernel, dim3(grid_pull), dim3(256), 0, e->copy, hjob, ones, n_ones);
-        else if (hashed) hipLaunchKernelGGL(pull_block_hashed_ones_kernel, dim3(grid_pull), dim3(256), 0, e->copy, hjob, ones, n_ones);
-        else if (job.wbytes) hipLaunchKernelGGL(pull_block_weighted_ones_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job, ones, n_ones);
-        else hipLaunchKernelGGL(pull_block_ones_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job.block, ones, n_ones);
+        if (hashed && job.wbytes) hipLaunchKernelGGL(pull_block_weighted_hashed_ones_kernel, dim3(grid_pull), dim3(256), 0, e->prep, hjob, ones, n_ones);
+        else if (hashed) hipLaunchKernelGGL(pull_block_hashed_ones_kernel, dim3(grid_pull), dim3(256), 0, e->prep, hjob, ones, n_ones);
+        else if (job.wbytes) hipLaunchKernelGGL(pull_block_weighted_ones_kernel, dim3(grid_pull), dim3(256), 0, e->prep, job, ones, n_ones);
+        else hipLaunchKernelGGL(pull_block_ones_kernel, dim3(grid_pull), dim3(256), 0, e->prep, job.block, ones, n_ones);
       }
-      else if (hashed && job.wbytes) hipLaunchKernelGGL(pull_block_weighted_hashed_kernel, dim3(grid_pull), dim3(256), 0, e->copy, hjob);
-      else if (hashed) hipLaunchKernelGGL(pull_block_hashed_kernel, dim3(grid_pull), dim3(256), 0, e->copy, hjob);
-      else if (job.wbytes) hipLaunchKernelGGL(pull_block_weighted_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job);
-      else hipLaunchKernelGGL(pull_block_kernel, dim3(grid_pull), dim3(256), 0, e->copy, job.block);
-      HIP_TRY(hipEventRecord(s2.ev_copied, e->copy));
-      if (e->copy != e->prep) HIP_TRY(hipStreamWaitEvent(e->prep, s2.ev_copied, 0));  // the grouping reads the slot
+      else if (hashed && job.wbytes) hipLaunchKernelGGL(pull_block_weighted_hashed_kernel, dim3(grid_pull), dim3(256), 0, e->prep, hjob);
+      else if (hashed) hipLaunchKernelGGL(pull_block_hashed_kernel, dim3(grid_pull), dim3(256), 0, e->prep, hjob);
+      else if (job.wbytes) hipLaunchKernelGGL(pull_block_weighted_kernel, dim3(grid_pull), dim3(256), 0, e->prep, job);
+      else hipLaunchKernelGGL(pull_block_kernel, dim3(grid_pull), dim3(256), 0, e->prep, job.block);
+      HIP_TRY(hipEventRecord(s2.ev_copied, e->prep));
       return prepare_submit(e, plan, timed);
     };
     rc2 = body();
@@ -651,14 +650,14 @@ int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const i
                        nullptr, &hjob)))
     return rc;
   ffm_engine::Slot &sl = e->slots[this_slot];
-  if (slot_was_used && sl.free_ev) HIP_TRY(hipStreamWaitEvent(e->copy, sl.free_ev, 0));  // nothing reads its device arrays
+  if (slot_was_used && sl.free_ev) HIP_TRY(hipStreamWaitEvent(e->prep, sl.free_ev, 0));  // nothing reads its device arrays
   if (!val && nnz > 0) {  // (no values came: the upload writes the slot's)
-    if (e->hash_ids) hipLaunchKernelGGL(pull_block_hashed_ones_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, hjob, sl.val, static_cast<unsigned>(nnz));
-    else hipLaunchKernelGGL(pull_block_ones_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, job, sl.val, static_cast<unsigned>(nnz));
+    if (e->hash_ids) hipLaunchKernelGGL(pull_block_hashed_ones_kernel, dim3(e->grid_pull), dim3(256), 0, e->prep, hjob, sl.val, static_cast<unsigned>(nnz));
+    else hipLaunchKernelGGL(pull_block_ones_kernel, dim3(e->grid_pull), dim3(256), 0, e->prep, job, sl.val, static_cast<unsigned>(nnz));
   }
-  else if (e->hash_ids) hipLaunchKernelGGL(pull_block_hashed_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, hjob);
-  else hipLaunchKernelGGL(pull_block_kernel, dim3(e->grid_pull), dim3(256), 0, e->copy, job);
-  HIP_TRY(hipEventRecord(sl.ev_copied, e->copy));
+  else if (e->hash_ids) hipLaunchKernelGGL(pull_block_hashed_kernel, dim3(e->grid_pull), dim3(256), 0, e->prep, hjob);
+  else hipLaunchKernelGGL(pull_block_kernel, dim3(e->grid_pull), dim3(256), 0, e->prep, job);
+  HIP_TRY(hipEventRecord(sl.ev_copied, e->prep));
   sl.used = true;
   sl.zero_copy = zero_copy != 0;
   sl.n_rows = n_rows;

@@ -165,15 +165,12 @@ int ffm_engine_changed_features(ffm_engine *e, int32_t *ids, int64_t cap, int64_
   unsigned long long *d_bits = reinterpret_cast<unsigned long long *>(e->d_stage);
   const int64_t per = e->stage_floats / 2;  // words the staging buffer holds
   const bool vec4 = e->m.row_len % 4 == 0, skip = (e->cfg.flags & FFM_FLAG_SKIP_INIT) != 0;
+  const auto scan = vec4 ? (skip ? changed_scan_kernel<true, true> : changed_scan_kernel<true, false>)
+                         : (skip ? changed_scan_kernel<false, true> : changed_scan_kernel<false, false>);
   for (int64_t w0 = 0; w0 < n_words; w0 += per) {
     const int64_t nw = std::min(per, n_words - w0);
     const dim3 grid(static_cast<unsigned>((nw + kScanWaves - 1) / kScanWaves)), block(kScanThreads);
-#define SCAN_LAUNCH(V, S)                                                                              \
-    hipLaunchKernelGGL((changed_scan_kernel<V, S>), grid, block, 0, e->stream, e->m, e->cfg.init_mean, \
-                       e->cfg.init_stddev, e->cfg.seed, w0, nw, d_bits)
-    if (vec4) { if (skip) SCAN_LAUNCH(true, true); else SCAN_LAUNCH(true, false); }
-    else      { if (skip) SCAN_LAUNCH(false, true); else SCAN_LAUNCH(false, false); }
-#undef SCAN_LAUNCH
+    hipLaunchKernelGGL(scan, grid, block, 0, e->stream, e->m, e->cfg.init_mean, e->cfg.init_stddev, e->cfg.seed, w0, nw, d_bits);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(bits.data() + w0, d_bits, static_cast<size_t>(nw) * sizeof(unsigned long long),
                            hipMemcpyDeviceToHost, e->stream));

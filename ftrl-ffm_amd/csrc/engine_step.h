@@ -29,33 +29,18 @@ static int check_block(ffm_engine *e, int32_t n_rows, int32_t nnz, const void *r
 
 
 // FFM evaluation rows one wave each (kernels_predict.h) where that kernel applies: a whole model on
-// this device, k in {4, 8, 16, 32, 64}, the rows' entries within 64 KB of LDS per workgroup.
-#ifndef FFM_PRED_LPP
-#define FFM_PRED_LPP 4  // k = 16: lanes per pair (1, 2, 4) ...
-#endif
-#ifndef FFM_PRED_U
-#define FFM_PRED_U 4    // ... and steps of loads in flight together
-#endif
-static bool launch_predict_waves(ffm_engine *e, const Rows &rows, int row_cap, float *out, int output_prob) {
+// this device, a k with a lane shape (engine_select.h), the rows' entries within 64 KB of LDS per workgroup.
+// A serving engine (engine_serve.h) has this kernel's twin and no other: create admitted only what it serves.
+static bool launch_row_waves(ffm_engine *e, const Rows &rows, int row_cap, float *out, int output_prob) {
   const ModelDev &m = e->m;
-  if (!e->predict_waves || m.type != FFM_MODEL_FFM || m.n_shards > 1 || m.field_start || m.own_n || m.lin_own) return false;
+  if (!serving(e) && (!e->predict_waves || m.type != FFM_MODEL_FFM || m.n_shards > 1 || m.field_start || m.own_n || m.lin_own)) return false;
+  const RowWaveFn fn = row_wave_fn(m.lat_fmt, m.n_factors);
+  if (!fn) return false;
   const int lds_cap = std::min(row_cap, kPredLdsCap);
-  const size_t shmem = pred_lds_bytes(lds_cap);
-  const int grid = cdiv(rows.n_rows, kPredRows), threads = 64 * kPredRows;
-#define PRED_LAUNCH(LPP, VPL, U) \
-  LAUNCH(e, K_PREDICT_ROW, (ffm_predict_wave_kernel<LPP, VPL, U>), grid, threads, shmem, m, rows, e->sc[e->cur], row_cap, lds_cap, out, output_prob)
-  switch (m.n_factors) {
-    case 4: PRED_LAUNCH(1, 1, 4); return true;
-    case 8: PRED_LAUNCH(2, 1, 4); return true;
-    case 16: PRED_LAUNCH(FFM_PRED_LPP, 4 / FFM_PRED_LPP, FFM_PRED_U); return true;
-    case 32: PRED_LAUNCH(8, 1, 2); return true;
-    case 64: PRED_LAUNCH(16, 1, 1); return true;
-    default: return false;
-  }
-#undef PRED_LAUNCH
+  LAUNCH(e, serving(e) ? K_SERVE_ROW : K_PREDICT_ROW, fn, cdiv(rows.n_rows, kPredRows), 64 * kPredRows, pred_lds_bytes(lds_cap),
+         m, rows, e->sc[e->cur], row_cap, lds_cap, out, output_prob);
+  return true;
 }
-
-static void launch_serve_waves(ffm_engine *e, const Rows &rows, int row_cap, float *out, int output_prob);  // (engine_serve.h)
 
 // weight: the block's sample weights (device) or null; only the launches that produce tmp_grad
 // themselves (own_tg) take them -- otherwise tmp_grad_weighted_kernel does, after the logits are whole.
@@ -65,7 +50,7 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float
   e->staged_row_cap = 0;
   if (rows.n_rows == 0) return;
   if (serving(e)) {  // (predict only: every training entry point is refused) -- its own kernel and nothing else
-    launch_serve_waves(e, rows, row_cap, out, output_prob);
+    launch_row_waves(e, rows, row_cap, out, output_prob);
     return;
   }
   // (the kernels recompute the same terms capacity from the same arguments)
@@ -77,25 +62,22 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float
     // one wave per row, lane = factor (kernels_fm.h)
     if (train) e->singles_in_row = own_tg != 0;
     const int grid = cdiv(rows.n_rows, kFmRowsPerBlock);
-    if (train && own_tg && weight) LAUNCH(e, kid, (fm_row_wave_kernel<true, const float *>), grid, 64 * kFmRowsPerBlock, 0, e->m, rows, e->sc[e->cur], row_cap, out, output_prob, own_tg, weight);
-    else if (train) LAUNCH(e, kid, fm_row_wave_kernel<true>, grid, 64 * kFmRowsPerBlock, 0, e->m, rows, e->sc[e->cur], row_cap, out, output_prob, own_tg);
-    else LAUNCH(e, kid, fm_row_wave_kernel<false>, grid, 64 * kFmRowsPerBlock, 0, e->m, rows, e->sc[e->cur], row_cap, out, output_prob, 0);
+    if (train && own_tg && weight) LAUNCH(e, kid, fm_row_wave_fn<const float *>(train), grid, 64 * kFmRowsPerBlock, 0, e->m, rows, e->sc[e->cur], row_cap, out, output_prob, own_tg, weight);
+    else LAUNCH(e, kid, fm_row_wave_fn<>(train), grid, 64 * kFmRowsPerBlock, 0, e->m, rows, e->sc[e->cur], row_cap, out, output_prob, train ? own_tg : 0);
   } else if (e->m.type == FFM_MODEL_FM) {
     if (train) e->singles_in_row = false;
-    if (train) LAUNCH(e, kid, fm_row_kernel<true>, rows.n_rows, kRowThreads, shmem, e->m, rows, e->sc[e->cur], row_cap, out, output_prob);
-    else LAUNCH(e, kid, fm_row_kernel<false>, rows.n_rows, kRowThreads, shmem, e->m, rows, e->sc[e->cur], row_cap, out, output_prob);
+    LAUNCH(e, kid, fm_row_fn(train), rows.n_rows, kRowThreads, shmem, e->m, rows, e->sc[e->cur], row_cap, out, output_prob);
   } else {
     const bool vec4 = e->m.n_factors > 0 && e->m.n_factors % 4 == 0;
     const int mr = row_cap;
     int refreshed = train && e->pre_refresh ? e->refresh_mode : 0;
-    if (refreshed == 3 && !(own_tg && vec4 && e->single_kernel)) refreshed = 2;
+    if (refreshed == 3 && !(own_tg && vec4)) refreshed = 2;
     if (train) e->singles_in_row = refreshed == 3;
     if (refreshed && rows.nnz > 0) {
       const int per = vec4 ? e->m.row_len / 4 : e->m.row_len;
       const int64_t items = static_cast<int64_t>(std::min(rows.nnz, e->max_nnz)) * per;
       const int grid = static_cast<int>(std::min<int64_t>((items + 255) / 256, 8192));
-      if (vec4) LAUNCH(e, K_REFRESH, ffm_refresh_kernel<true>, grid, 256, 0, e->m, e->sc[e->cur], refreshed >= 2);
-      else LAUNCH(e, K_REFRESH, ffm_refresh_kernel<false>, grid, 256, 0, e->m, e->sc[e->cur], refreshed >= 2);
+      LAUNCH(e, K_REFRESH, ffm_refresh_fn(vec4), grid, 256, 0, e->m, e->sc[e->cur], refreshed >= 2);
     }
     // LDS parking (round 6: of w; round 4 parked (n, z)): the first vectors of w that a row's refresh
     // computes for its once-only features stay in LDS, where the row's pair phase and its in-row update
@@ -133,33 +115,21 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float
       park = static_cast<int>(std::max<long long>(0, bytes) / 16);
       if (park > 0) shmem_park = base + 16 * static_cast<size_t>(park);
     }
-    if (train && vec4) {
-#define ROW_LAUNCH_HOLD(H)                                                                                             \
-  do {                                                                                                                 \
-    if (weight)                                                                                                        \
-      LAUNCH(e, kid, (ffm_row_kernel<true, true, true, H, const float *>), rows.n_rows, e->row_threads, shmem_park, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, park, weight); \
-    else                                                                                                               \
-      LAUNCH(e, kid, (ffm_row_kernel<true, true, true, H>), rows.n_rows, e->row_threads, shmem_park, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, park); \
-  } while (0)
-      if (own_tg && hold == 8) ROW_LAUNCH_HOLD(8);
-      else if (own_tg && hold == 6) ROW_LAUNCH_HOLD(6);
-      else if (own_tg && hold == 4) ROW_LAUNCH_HOLD(4);
-      else if (own_tg && hold == 2) ROW_LAUNCH_HOLD(2);
-      else if (own_tg) ROW_LAUNCH_HOLD(0);
-#undef ROW_LAUNCH_HOLD
-      else  // a shard: the logit is whole only after the all-reduce
-        LAUNCH(e, kid, (ffm_row_kernel<true, true, false>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, 0, 0, 0);
-    }
-    else if (train && own_tg && weight) LAUNCH(e, kid, (ffm_row_kernel<true, false, true, 0, const float *>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, 0, weight);
-    else if (train) LAUNCH(e, kid, (ffm_row_kernel<true, false>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, 0);
-    else if (launch_predict_waves(e, rows, row_cap, out, output_prob)) {
+    // the template's WHOLE (engine_select.h): the general-k training kernel is always the WHOLE one and learns
+    // from own_tg whether the logit is (a shard's is whole only after the all-reduce: own_tg = 0)
+    const bool whole = train && (own_tg || !vec4);
+    int last = park;  // the kernels' last argument: vectors parked when training ...
+    if (!train && launch_row_waves(e, rows, row_cap, out, output_prob)) {
       // rows that may be longer than a wave stages (kernels_predict.h): the workgroup-per-row kernel
       // for those alone (its last argument: rows of at most that many entries are not its)
-      if (row_cap > kPredLdsCap)
-        LAUNCH(e, kid, (ffm_row_kernel<false, true>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, 0, 0, 0, kPredLdsCap);
+      if (row_cap <= kPredLdsCap) return;
+      last = kPredLdsCap;
     }
-    else if (vec4) LAUNCH(e, kid, (ffm_row_kernel<false, true>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, 0, 0, 0, 0);
-    else LAUNCH(e, kid, (ffm_row_kernel<false, false>), rows.n_rows, e->row_threads, shmem, e->m, rows, e->sc[e->cur], mr, out, output_prob, 0, 0, 0, 0);
+    // (shmem_park == shmem and park == 0 unless refreshed == 3, the in-row update's kernel)
+    if (weight && own_tg)
+      LAUNCH(e, kid, ffm_row_fn<const float *>(train, vec4, whole, hold), rows.n_rows, e->row_threads, shmem_park, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, last, weight);
+    else
+      LAUNCH(e, kid, ffm_row_fn<>(train, vec4, whole, hold), rows.n_rows, e->row_threads, shmem_park, e->m, rows, e->sc[e->cur], mr, out, output_prob, refreshed, own_tg, 0, last);
   }
 }
 
@@ -229,7 +199,7 @@ static int launch_grouping(ffm_engine *e, int set, const Rows &rows, hipStream_t
 struct PrepPlan {
   int set = 0;
   bool wait_free = false;  // the set carried an earlier block: wait for its ev_set_free
-  int ws = -1;             // prep_window: start when this set's block has trained (-1: at once)
+  int ws = -1;             // start when this set's block has trained (-1: at once); ffm_engine::trained_set
   Rows rows{};
 };
 static int prepare_plan(ffm_engine *e, const Rows &rows, PrepPlan *pl) {
@@ -239,13 +209,10 @@ static int prepare_plan(ffm_engine *e, const Rows &rows, PrepPlan *pl) {
   pl->set = set;
   pl->rows = rows;
   pl->wait_free = e->set_used[set];
-  pl->ws = -1;
-  if (e->prep_window) {
-    // n_prepared == 1: the predecessor is prepared but not enqueued yet -> wait for the block
-    // enqueued last; n_prepared == 0: the predecessor IS the block enqueued last -> the one before
-    const int ws = e->trained_set[e->n_prepared >= 1 ? 0 : 1];
-    if (ws >= 0 && ws != set) pl->ws = ws;
-  }
+  // n_prepared == 1: the predecessor is prepared but not enqueued yet -> wait for the block
+  // enqueued last; n_prepared == 0: the predecessor IS the block enqueued last -> the one before
+  const int ws = e->trained_set[e->n_prepared >= 1 ? 0 : 1];
+  pl->ws = ws >= 0 && ws != set ? ws : -1;
   // the set is in use from now on, also when this look-ahead ends up discarded: whoever takes the
   // set next must wait for ev_set_free (recorded when the block trains or the look-ahead is dropped)
   e->set_used[set] = true;
@@ -374,23 +341,20 @@ int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *log
   const int side_blocks = lin_owner && rows.n_rows > 0 ? 1 + lin_blocks : 0;
   bool loss_done = false;
   if (ffm && vec4 && masks) {
-    const bool single = e->single_kernel;
     const int span4 = e->m.rec_slots * (e->m.n_factors / 4);  // 16-byte vectors of a stored record
     const bool flat = flat_pays(e, span4);
     // A shard's once-only features (their logit was only whole after the all-reduce) and, on compact
     // storage, its few-occurrence features have launches of their own: on the side stream, beside the
     // update launch (disjoint features; a rank's step is long, the two queue hops are not)
-    const bool side_launches = (single && !e->singles_in_row) || flat;
+    const bool side_launches = !e->singles_in_row || flat;
     hipStream_t sst = side_launches && !e->serial ? e->aux3 : e->stream;
     if (sst != e->stream) {
       HIP_TRY(hipEventRecord(e->ev_fork, e->stream));
       HIP_TRY(hipStreamWaitEvent(sst, e->ev_fork, 0));
     }
-    if (single && !e->singles_in_row) {  // (else: already applied by the row kernel)
+    if (!e->singles_in_row) {  // (else: already applied by the row kernel)
       if (flat) LAUNCH_ON(e, sst, K_LATENT_UPDATE_SINGLE, ffm_update_single_flat_kernel, e->grid_single, kUpdThreads, 0, e->m, rows, e->sc[e->cur]);
-      else if (span4 <= 64) LAUNCH_ON(e, sst, K_LATENT_UPDATE_SINGLE, ffm_update_single_kernel<1>, e->grid_single, kUpdThreads, 0, e->m, rows, e->sc[e->cur]);
-      else if (span4 <= 128) LAUNCH_ON(e, sst, K_LATENT_UPDATE_SINGLE, ffm_update_single_kernel<2>, e->grid_single, kUpdThreads, 0, e->m, rows, e->sc[e->cur]);
-      else LAUNCH_ON(e, sst, K_LATENT_UPDATE_SINGLE, ffm_update_single_kernel<3>, e->grid_single, kUpdThreads, 0, e->m, rows, e->sc[e->cur]);
+      else LAUNCH_ON(e, sst, K_LATENT_UPDATE_SINGLE, update_single_fn(span4), e->grid_single, kUpdThreads, 0, e->m, rows, e->sc[e->cur]);
     }
     // (the few-occurrence launch further down: beside the longest features' second pass and join,
     // which are chains of dependent loads on an otherwise idle chip)
@@ -409,7 +373,7 @@ int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *log
     // (... and only then is the few-occurrence kernel worth deferring: a block without such features -- the
     // strong-scaling leg's 8192 rows -- has no second pass to run it beside: 0.349 -> 0.341 ms)
     const bool few_late = flat && sst != e->stream && supers;
-    if (flat && !few_late) LAUNCH_ON(e, sst, K_LATENT_UPDATE_FEW, ffm_update_small_flat_kernel, e->grid_small, kUpdThreads, 0, e->m, rows, e->sc[e->cur], single ? 1 : 0);
+    if (flat && !few_late) LAUNCH_ON(e, sst, K_LATENT_UPDATE_FEW, ffm_update_small_flat_kernel, e->grid_small, kUpdThreads, 0, e->m, rows, e->sc[e->cur], 1);
     if (sst != e->stream && !few_late) HIP_TRY(hipEventRecord(e->ev_join, sst));
     // (the ranges' sizes are kept in 256-thread units and scaled to the launch's workgroup size)
     // One launch, or three side by side: the one launch runs every range at the register / LDS footprint
@@ -437,71 +401,57 @@ int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *log
     const int order = e->update_order;  // (which of the three big ranges the dispatcher sees first)
     const int lb = loss_sum_out ? loss_grid(rows.n_rows) : 0;
     const int side = side_blocks > 0 ? 1 + cdiv(lin_blocks, scale) : 0;
-    const int grid = side + ng + nt + ns + nw + lb;
-#define FTRL_LAUNCH_ALL(NF)                                                                                   \
-    do {                                                                                                      \
-      if (split == 2 && !e->serial) { /* side by side: few on aux3, giant on aux4 */                        \
-        HIP_TRY(hipEventRecord(e->ev_fork2, e->stream));                                                      \
-        if (ns + nw + lb > 0) {                                                                               \
-          HIP_TRY(hipStreamWaitEvent(e->aux3, e->ev_fork2, 0));                                               \
-          LAUNCH_ON(e, e->aux3, K_LATENT_UPDATE_FEW, (ffm_update_all_kernel<NF, UPD_FEW | UPD_REST>), ns + nw + lb, threads, few_lds, e->m, rows, e->sc[e->cur], \
-                 0, 0, 0, ns, single ? 1 : 0, nw, lb, loss_sum_out, e->d_loss_part, order);                       \
-          HIP_TRY(hipEventRecord(e->ev_join, e->aux3));                                                       \
-        }                                                                                                     \
-        if (ng > 0) {                                                                                         \
-          HIP_TRY(hipStreamWaitEvent(e->aux4, e->ev_fork2, 0));                                               \
-          LAUNCH_ON(e, e->aux4, K_LATENT_UPDATE_GIANT, (ffm_update_all_kernel<NF, UPD_GIANT>), ng, threads, lds, e->m, rows, e->sc[e->cur], \
-                 0, ng, 0, 0, single ? 1 : 0, 0, 0, loss_sum_out, e->d_loss_part, order);                         \
-          HIP_TRY(hipEventRecord(e->ev_join2, e->aux4));                                                      \
-        }                                                                                                     \
-        LAUNCH(e, K_LATENT_UPDATE, (ffm_update_all_kernel<NF, UPD_HOT | UPD_SIDE>), side + nt, threads, lds, e->m, rows, e->sc[e->cur], \
-               side, 0, nt, 0, single ? 1 : 0, 0, 0, loss_sum_out, e->d_loss_part, 1);                            \
-        if (ns + nw + lb > 0) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_join, 0));                          \
-        if (ng > 0) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_join2, 0));                                   \
-      } else if (split) { /* (timing aid: one launch per range, each under a name of its own) */              \
-        if (ng > 0)                                                                                           \
-          LAUNCH(e, K_LATENT_UPDATE_GIANT, (ffm_update_all_kernel<NF, UPD_GIANT>), ng, threads, lds, e->m, rows, e->sc[e->cur], \
-                 0, ng, 0, 0, single ? 1 : 0, 0, 0, loss_sum_out, e->d_loss_part, order);                         \
-        LAUNCH(e, K_LATENT_UPDATE, (ffm_update_all_kernel<NF, UPD_HOT | UPD_SIDE>), side + nt, threads, lds, e->m, rows, e->sc[e->cur], \
-               side, 0, nt, 0, single ? 1 : 0, 0, 0, loss_sum_out, e->d_loss_part, order);                        \
-        if (ns > 0)                                                                                           \
-          LAUNCH(e, K_LATENT_UPDATE_FEW, (ffm_update_all_kernel<NF, UPD_FEW>), ns, threads, lds, e->m, rows, e->sc[e->cur], \
-                 0, 0, 0, ns, single ? 1 : 0, 0, 0, loss_sum_out, e->d_loss_part, order);                         \
-        LAUNCH(e, K_LATENT_UPDATE_WALK, (ffm_update_all_kernel<NF, UPD_REST>), nw + lb, threads, lds, e->m, rows, e->sc[e->cur], \
-               0, 0, 0, 0, single ? 1 : 0, nw, lb, loss_sum_out, e->d_loss_part, order);                          \
-      } else if (ns == 0) { /* a shard: its few-occurrence features have a kernel of their own, and without   \
-           that range's registers the launch holds four waves per SIMD (128 VGPRs, 11 spilled) instead of    \
-           three at 143: an emulated 8-GPU rank's step 1.658 -> 1.619 ms */                                   \
-        LAUNCH(e, K_LATENT_UPDATE, (ffm_update_all_kernel<NF, UPD_ALL & ~UPD_FEW>), grid, threads, lds, e->m, rows, e->sc[e->cur], \
-               side, ng, nt, ns, single ? 1 : 0, nw, lb, loss_sum_out, e->d_loss_part, order);                  \
-      } else {                                                                                                \
-        LAUNCH(e, K_LATENT_UPDATE, (ffm_update_all_kernel<NF>), grid, threads, lds, e->m, rows, e->sc[e->cur], \
-               side, ng, nt, ns, single ? 1 : 0, nw, lb, loss_sum_out, e->d_loss_part, order);                  \
-      }                                                                                                       \
-    } while (0)
-    if (wide)
-      LAUNCH(e, K_LATENT_UPDATE, (ffm_update_all_kernel<1, UPD_ALL, kWideWaves>), grid, threads, lds, e->m, rows, e->sc[e->cur],
-             side, ng, nt, ns, single ? 1 : 0, nw, lb, loss_sum_out, e->d_loss_part, order);
-    else if (nf == 1) FTRL_LAUNCH_ALL(1);  // k >= 16
-    else if (nf == 2) FTRL_LAUNCH_ALL(2);  // k = 8 / 12
-    else FTRL_LAUNCH_ALL(4);               // k = 4
+    // One launch of the ranges `kinds` (the arguments of every other range are 0), from the instantiation
+    // that carries those ranges alone: nf = 1 for k >= 16, 2 for k = 8 / 12, 4 for k = 4 (engine_select.h).
+    // few_only is 1: a once-only feature is its row's or the once-only kernel's, never the few-occurrence range's.
+    auto launch_ranges = [&](hipStream_t st, int kid, int kinds, size_t shm, int ord) {
+      const int a_side = kinds & UPD_SIDE ? side : 0, a_ng = kinds & UPD_GIANT ? ng : 0, a_nt = kinds & UPD_HOT ? nt : 0;
+      const int a_ns = kinds & UPD_FEW ? ns : 0, a_nw = kinds & UPD_REST ? nw : 0, a_lb = kinds & UPD_REST ? lb : 0;
+      LAUNCH_ON(e, st, kid, update_all_fn(nf, kinds, wpb), a_side + a_ng + a_nt + a_ns + a_nw + a_lb, threads, shm, e->m, rows,
+                e->sc[e->cur], a_side, a_ng, a_nt, a_ns, 1, a_nw, a_lb, loss_sum_out, e->d_loss_part, ord);
+    };
+    if (split == 2 && !e->serial) {  // side by side: few on aux3, giant on aux4
+      HIP_TRY(hipEventRecord(e->ev_fork2, e->stream));
+      if (ns + nw + lb > 0) {
+        HIP_TRY(hipStreamWaitEvent(e->aux3, e->ev_fork2, 0));
+        launch_ranges(e->aux3, K_LATENT_UPDATE_FEW, UPD_FEW | UPD_REST, few_lds, order);
+        HIP_TRY(hipEventRecord(e->ev_join, e->aux3));
+      }
+      if (ng > 0) {
+        HIP_TRY(hipStreamWaitEvent(e->aux4, e->ev_fork2, 0));
+        launch_ranges(e->aux4, K_LATENT_UPDATE_GIANT, UPD_GIANT, lds, order);
+        HIP_TRY(hipEventRecord(e->ev_join2, e->aux4));
+      }
+      launch_ranges(e->stream, K_LATENT_UPDATE, UPD_HOT | UPD_SIDE, lds, 1);
+      if (ns + nw + lb > 0) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_join, 0));
+      if (ng > 0) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_join2, 0));
+    } else if (split) {  // (timing aid: one launch per range, each under a name of its own)
+      if (ng > 0) launch_ranges(e->stream, K_LATENT_UPDATE_GIANT, UPD_GIANT, lds, order);
+      launch_ranges(e->stream, K_LATENT_UPDATE, UPD_HOT | UPD_SIDE, lds, order);
+      if (ns > 0) launch_ranges(e->stream, K_LATENT_UPDATE_FEW, UPD_FEW, lds, order);
+      launch_ranges(e->stream, K_LATENT_UPDATE_WALK, UPD_REST, lds, order);
+    } else if (ns == 0) {
+      // a shard: its few-occurrence features have a kernel of their own, and without that range's registers
+      // the launch holds four waves per SIMD (128 VGPRs, 11 spilled) instead of three at 143: an emulated
+      // 8-GPU rank's step 1.658 -> 1.619 ms
+      launch_ranges(e->stream, K_LATENT_UPDATE, UPD_ALL & ~UPD_FEW, lds, order);
+    } else {  // (wide: the eight-wave instantiation, by wpb)
+      launch_ranges(e->stream, K_LATENT_UPDATE, UPD_ALL, lds, order);
+    }
     if (few_late) {
       HIP_TRY(hipEventRecord(e->ev_fork2, e->stream));
       HIP_TRY(hipStreamWaitEvent(sst, e->ev_fork2, 0));
-      LAUNCH_ON(e, sst, K_LATENT_UPDATE_FEW, ffm_update_small_flat_kernel, e->grid_small, kUpdThreads, 0, e->m, rows, e->sc[e->cur], single ? 1 : 0);
+      LAUNCH_ON(e, sst, K_LATENT_UPDATE_FEW, ffm_update_small_flat_kernel, e->grid_small, kUpdThreads, 0, e->m, rows, e->sc[e->cur], 1);
       HIP_TRY(hipEventRecord(e->ev_join, sst));
     }
     if (supers) {
       // the longest features' ranges: second pass (root differences) and the join of their tiles
       const int gg = e->grid_giant;
       e->prof_begin(K_LATENT_UPDATE_GIANT, e->stream);
-      if (nf == 1) hipLaunchKernelGGL(ffm_update_super_b_kernel<1>, dim3(gg), dim3(kUpdThreads), 0, e->stream, e->m, rows, e->sc[e->cur]);
-      else if (nf == 2) hipLaunchKernelGGL(ffm_update_super_b_kernel<2>, dim3(gg), dim3(kUpdThreads), 0, e->stream, e->m, rows, e->sc[e->cur]);
-      else hipLaunchKernelGGL(ffm_update_super_b_kernel<4>, dim3(gg), dim3(kUpdThreads), 0, e->stream, e->m, rows, e->sc[e->cur]);
+      hipLaunchKernelGGL(update_super_b_fn(nf), dim3(gg), dim3(kUpdThreads), 0, e->stream, e->m, rows, e->sc[e->cur]);
       hipLaunchKernelGGL(ffm_update_super_join_kernel, dim3(gg), dim3(kUpdThreads), 0, e->stream, e->m, e->sc[e->cur]);
       e->prof_end(e->stream);
     }
-#undef FTRL_LAUNCH_ALL
     if (sst != e->stream) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_join, 0));
     loss_done = loss_sum_out != nullptr;
   } else {

@@ -15,7 +15,8 @@ y[r]) * weight[r], one fp32 multiply; the loss term (double)weight[r] * loss; no
   4. the weighted loss sum is sum((double)w * loss(y, logit_out));
   5. the pipeline: seven blocks of 515 rows, each with other weights, one with NULL, copying and
      zero_copy, against the sync weighted calls;
-  6. groups of 2 and 4 shards on one device; 7. refusals.
+  6. groups of 2 and 4 shards on one device; 6b. the weighted row kernels that hold no (n, z), with rows
+     staged above 64 KB of dynamic LDS; 7. refusals.
 """
 import ctypes
 import functools
@@ -498,6 +499,42 @@ def test_weighted_group_on_one_device(n):
             merged = np.where(lin_owner == r, states[r][key], merged)
         np.testing.assert_allclose(merged, want[key], rtol=2e-4, atol=2e-5, err_msg=key)
     g.close()
+
+
+# ---- 6b. the weighted row kernels that hold nothing, above 64 KB of dynamic LDS ------------------------------
+
+
+@pytest.mark.parametrize("k,row_hold", [(4, "0"), (3, None)], ids=["k4-FFM_ROW_HOLD=0", "k3"])
+def test_weighted_row_kernel_with_rows_staged_above_64kb_of_lds(monkeypatch, k, row_hold):
+    """A device entry point stages every row for max_row_nnz entries.  At max_row_nnz = 2048 and three
+    fields that is 8192 + 32 * 2048 + 32 = 73 760 bytes of dynamic LDS -- above 64 KB, which a kernel only
+    gets when create opted it in.  The two weighted instantiations that hold no (n, z) -- k % 4 == 0 with
+    FFM_ROW_HOLD=0, and k % 4 != 0 -- must be among them: one weighted whole step on such an engine
+    and on one with max_row_nnz = 3 (the path the rest of this module pins to the oracle) are bit-identical."""
+    if row_hold is None:
+        monkeypatch.delenv("FFM_ROW_HOLD", raising=False)
+    else:
+        monkeypatch.setenv("FFM_ROW_HOLD", row_hold)
+    F, rows, per = 3, 8, 5
+    rng = np.random.default_rng(31)
+    feat = (np.arange(F) * per + rng.integers(0, per, (rows, F))).astype(np.int32)  # 5 ids per field: rows share them
+    c = Csr(np.arange(rows + 1, dtype=np.int32) * F, np.tile(np.arange(F, dtype=np.int32), rows),
+            np.ascontiguousarray(feat.reshape(-1)), rng.uniform(0.5, 1.5, rows * F).astype(f32),
+            rng.integers(0, 2, rows).astype(np.int32))
+    weight = np.array([0, 0.25, 1, 3.5, 1e-3, 64, 1.75, 0.5], f32)
+    got = []
+    for max_row_nnz in (F, 2048):
+        e = fa.Engine("FFM", F * per, F, k, max_batch_rows=rows, max_batch_nnz=rows * F, max_row_nnz=max_row_nnz,
+                      seed=3, **STRESS_HP)
+        e.fill_state(seed=6)
+        lg, ls = _run(e, "device", c, weight)
+        e.check_errors()
+        got.append((lg, ls, e.get_state()))
+        e.close()
+    assert np.isfinite(got[0][0]).all()
+    assert_bitwise(got[1][0], got[0][0], "logits, max_row_nnz 2048 vs 3")
+    assert bits(np.float64(got[1][1])) == bits(np.float64(got[0][1])), ("loss sum", got[1][1], got[0][1])
+    assert_state_bitwise(got[1][2], got[0][2], "state, max_row_nnz 2048 vs 3")
 
 
 # ---- 7. refusals -------------------------------------------------------------------------------------------
