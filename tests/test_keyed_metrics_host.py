@@ -102,6 +102,46 @@ def rows_of(rng, n, n_keys, n_scores):
     return keys, p, rng.integers(-1, 2, n)
 
 
+def pair_by_pair(keys, p, label, ref):
+    """Every (positive, negative) pair of every key, compared as the float32 scores they are."""
+    for g, key in enumerate(ref["key"]):
+        sel = keys == key
+        pk, yk = p[sel], label[sel] > 0
+        u2 = sum(2 * int((pk[~yk] < s).sum()) + int((pk[~yk] == s).sum()) for s in pk[yk])
+        assert (int(ref["pos"][g]), int(ref["neg"][g]), int(ref["u2"][g])) == (int(yk.sum()), int((~yk).sum()), u2)
+
+
+def test_pair_by_pair_on_scores_an_ulp_apart_subnormals_zero_and_one():
+    """The score population tests/test_gpu_keyed_sort.py relies on: float32 neighbours one ulp apart, subnormals, 0.0
+    and 1.0, exact ties -- each value in both classes of one key."""
+    f = np.float32
+    up = lambda x: np.nextafter(f(x), f(np.inf))  # noqa: E731
+    down = lambda x: np.nextafter(f(x), f(-np.inf))  # noqa: E731
+    tiny = f(2.0 ** -126)
+    values = np.array([0.0, up(0.0), up(up(0.0)), 1e-39, up(1e-39), down(tiny), tiny, up(tiny), 0.25, up(0.25), 0.5, down(0.5),
+                       up(0.5), down(down(1.0)), down(1.0), 1.0], np.float32)
+    assert np.unique(values).size == values.size == 16 and up(0.0) == f(2.0 ** -149) and (values[1:8] > 0).all()
+    assert ((values > 0) & (values < tiny)).sum() == 5
+    rng = np.random.default_rng(16)
+    n, n_keys = 300, 3
+    p = np.concatenate([np.tile(values, 2 * n_keys), rng.choice(values, n - 2 * n_keys * values.size)])
+    keys = np.concatenate([np.repeat(np.arange(n_keys), 2 * values.size), rng.integers(0, n_keys, n - 2 * n_keys * values.size)])
+    label = np.concatenate([np.tile(np.repeat([1, 0], values.size), n_keys), rng.integers(-1, 2, n - 2 * n_keys * values.size)])
+    perm = rng.permutation(n)
+    keys, p, label = keys[perm], p[perm], label[perm]
+    assert p.dtype == np.float32 and p.size == n
+    ref = fa.keyed_auc_reference(keys, p, label)
+    assert ref["n_rows"] == n and ref["n_keys"] == ref["n_keys_mixed"] == n_keys
+    pair_by_pair(keys, p, label, ref)
+    got = fa.metrics_from_keyed(ref["pos"], ref["neg"], ref["u2"])
+    assert bits(got["gauc"]) == bits(ref["gauc"]) and 0.0 < ref["gauc"] < 1.0
+    # one ulp decides a pair: a positive moved from a tie to its upper neighbour gains exactly one half-pair
+    one = fa.keyed_auc_reference([0, 0], np.array([0.25, 0.25], np.float32), [1, 0])
+    two = fa.keyed_auc_reference([0, 0], np.array([up(0.25), 0.25], np.float32), [1, 0])
+    sub = fa.keyed_auc_reference([0, 0], np.array([up(0.0), 0.0], np.float32), [1, 0])
+    assert (one["u2"].tolist(), two["u2"].tolist(), sub["u2"].tolist()) == ([1], [2], [2])
+
+
 @pytest.mark.parametrize("n,n_keys,n_scores", [(1, 1, 1), (50, 1, 3), (300, 7, 4), (5000, 40, 1000), (5000, 5000, 2), (20000, 300, 5)])
 def test_rows_through_the_reference_and_the_library(n, n_keys, n_scores):
     """keyed_auc_reference counts (numpy) and averages (Python floats); the library averages the same table to
@@ -116,11 +156,7 @@ def test_rows_through_the_reference_and_the_library(n, n_keys, n_scores):
     assert ref["n_rows"] == n and int(ref["pos"].sum() + ref["neg"].sum()) == n
     assert np.array_equal(ref["key"], np.unique(keys))
     if n <= 300:
-        for g, key in enumerate(ref["key"]):
-            sel = keys == key
-            pk, yk = p[sel], label[sel] > 0
-            u2 = sum(2 * int((pk[~yk] < s).sum()) + int((pk[~yk] == s).sum()) for s in pk[yk])
-            assert (int(ref["pos"][g]), int(ref["neg"][g]), int(ref["u2"][g])) == (int(yk.sum()), int((~yk).sum()), u2)
+        pair_by_pair(keys, p, label, ref)
     # the order the rows come in does not matter
     perm = rng.permutation(n)
     again = fa.keyed_auc_reference(keys[perm], p[perm], label[perm])
