@@ -50,6 +50,7 @@
 #include "kernels_metric.h"
 #include "kernels_keyed.h"
 #include "kernels_serve.h"
+#include "kernels_stage.h"
 #include "metrics_host.h"
 
 using namespace ftrl_dev;
@@ -278,7 +279,6 @@ struct ffm_engine {
     bool on = false; int slot = 0; bool labelled = false;
     float *scores = nullptr; int output_prob = 0; int64_t seq = 0;
   } eval_pending;
-  bool eval_hold = false;       // inside predict_batch_async, before its upload is submitted
   bool eval_defer_off = false;  // FFM_EVAL_DEFER=0
   bool super_wait = true;       // wait for a block's grouping before deciding on its super launches (FFM_SUPER_WAIT=0: only ask)
   bool super_flag_ok = false;  // create proved that a device store to h_super reaches the host
@@ -318,9 +318,6 @@ struct ffm_engine {
   hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_join = nullptr, ev_join2 = nullptr;
   hipStream_t aux4 = nullptr;  // second side stream of the update (FFM_UPDATE_SPLIT=2)
   int max_rows = 0, max_nnz = 0, max_row_nnz = 1024;
-  // longest row of the block being staged from host memory (known there; 0 = unknown: device
-  // callers).  The row kernels size their LDS by it, which decides how many rows a CU holds.
-  int staged_row_cap = 0;
   // staging for the host-buffer entry points
   int *d_row_ptr = nullptr, *d_field = nullptr, *d_feat = nullptr, *d_label = nullptr;
   float *d_val = nullptr, *d_out = nullptr;
@@ -422,11 +419,9 @@ struct ffm_engine {
   Rows pending{};
   const float *pending_weight = nullptr;  // sample weights of the pending block (device) or null
   bool has_pending = false;
-  bool whole_step = false;  // the call in flight is train_batch_device (forward + update in one)
   // train_batch_device on one shard: the row kernel has the whole logit, so it also produces
   // tmp_grad and the row losses (no tmp_grad pass)
   bool own_tg_cur = false;
-  float *own_logit_out = nullptr;
   // the block's lazy refresh as one pass over its distinct features (ffm_refresh_kernel) instead
   // of per occurrence inside the row kernel; FFM_ENGINE_ROW_REFRESH=1 keeps it in the row kernel
   bool pre_refresh = false;

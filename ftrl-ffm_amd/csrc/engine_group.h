@@ -308,13 +308,13 @@ int ffm_group_predict_batch(ffm_group *g, int32_t n_rows, const int32_t *row_ptr
   if (g->n_staged > 0) return fail(FFM_E_INVALID, "pipelined blocks are still waiting: flush first");
   const int n = static_cast<int>(g->eng.size());
   int rc;
-  int32_t nnz = 0;
   for (int r = 0; r < n; r++) {
     ffm_engine *e = g->eng[r];
-    if ((rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &nnz))) return rc;
-    if ((rc = ffm_engine_predict_batch_device(e, n_rows, nnz, e->d_row_ptr, field ? e->d_field : nullptr, e->d_feat,
-                                              e->d_val, nullptr, 0, g->logit[r], nullptr)))
-      return rc;
+    Rows dev{};
+    int row_cap = 0;
+    if ((rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &dev, &row_cap))) return rc;
+    dev.label = nullptr;  // (a shard predicts partial logits only: rank 0 finishes them below)
+    if ((rc = predict_core(e, dev, 0, g->logit[r], nullptr, row_cap))) return rc;
   }
   if ((rc = group_allreduce(g, n_rows))) return rc;
   ffm_engine *e0 = g->eng[0];

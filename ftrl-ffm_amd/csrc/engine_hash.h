@@ -1,19 +1,7 @@
 // engine_hash.h -- FFM_FLAG_HASH_IDS: feature ids hashed into their field's id range on the device
 // (csrc/hash_ids.h; include/ffm_engine.h "Hashed ids").  The in-place kernel of the synchronous path and
-// of ffm_engine_hash_ids_device, the pieces the upload kernel's hashed variants are built from
-// (engine_stage.h), and the host twin.
+// of ffm_engine_hash_ids_device, and the host twin.  (The upload kernel's hashed variants: kernels_stage.h.)
 // Part of engine.hip's translation unit (included inside its extern "C" block).
-
-// The fields of entries 4i .. 4i + 3 of a block handed over without a field array: one entry per field in
-// field order, so entry p is field p mod n_fields (what FFM_PULL_BLOCK_FINISH writes, engine_stage.h).
-__device__ __forceinline__ int4 hash_implicit_fields4(unsigned i, unsigned F) {
-  const unsigned f0 = (4u * i) % F, f1 = f0 + 1u < F ? f0 + 1u : 0u, f2 = f1 + 1u < F ? f1 + 1u : 0u;
-  return make_int4(static_cast<int>(f0), static_cast<int>(f1), static_cast<int>(f2), static_cast<int>(f2 + 1u < F ? f2 + 1u : 0u));
-}
-__device__ __forceinline__ int4 hash_entries4(const ftrl_hash::Map &hm, const int4 fl, const int4 ft) {
-  return make_int4(ftrl_hash::hash_entry(hm, fl.x, ft.x), ftrl_hash::hash_entry(hm, fl.y, ft.y),
-                   ftrl_hash::hash_entry(hm, fl.z, ft.z), ftrl_hash::hash_entry(hm, fl.w, ft.w));
-}
 
 // feat_out[p] = hash(field[p], feat_in[p]) for p < nnz; in place (feat_out == feat_in) is fine: a lane
 // reads its entries before it writes them and no lane reads another's.  A lane carries four entries as
@@ -25,8 +13,8 @@ __global__ __launch_bounds__(256) void hash_ids_kernel(ftrl_hash::Map hm, unsign
   const unsigned n4 = vec ? nnz >> 2 : 0u, F = static_cast<unsigned>(hm.n_fields);
   for (unsigned i = tid; i < n4; i += stride) {
     const int4 ft = reinterpret_cast<const int4 *>(feat_in)[i];
-    const int4 fl = field ? reinterpret_cast<const int4 *>(field)[i] : hm.ffm ? hash_implicit_fields4(i, F) : make_int4(0, 0, 0, 0);
-    reinterpret_cast<int4 *>(feat_out)[i] = hash_entries4(hm, fl, ft);
+    const int4 fl = field ? reinterpret_cast<const int4 *>(field)[i] : hm.ffm ? ftrl_hash::hash_implicit_fields4(i, F) : make_int4(0, 0, 0, 0);
+    reinterpret_cast<int4 *>(feat_out)[i] = ftrl_hash::hash_entries4(hm, fl, ft);
   }
   for (unsigned p = (n4 << 2) + tid; p < nnz; p += stride)
     feat_out[p] = ftrl_hash::hash_entry(hm, field ? field[p] : hm.ffm ? static_cast<int>(p % F) : 0, feat_in[p]);

@@ -1,228 +1,9 @@
-// engine_stage.h -- rows streaming from host memory inside the training loop: staging slots, the
-// upload kernel, the score download kernel, stage_batch / train_staged / train_batch_async[_pinned] /
-// predict_batch_async[_scores].
+// engine_stage.h -- rows streaming from host memory inside the training loop, host side: the staging slots,
+// the launches of the upload and score download kernels (kernels_stage.h), stage_batch / train_staged /
+// train_batch_async[_pinned] / predict_batch_async[_scores].
 // Part of engine.hip's translation unit (included inside its extern "C" block).
 
 // ---- pipelined host-buffer training ---------------------------------------------------------
-
-// Upload of one staged block by a kernel: the five CSR arrays are read straight out of page-locked
-// (device-mapped) host memory, 16 bytes per lane, and written to the staging slot's device arrays.
-// A hipMemcpyAsync here makes the SUBMITTING THREAD wait until the stream's earlier kernels have
-// finished (measured: mean 0.38 ms, up to 16 ms per call) -- the host then cannot run ahead of the
-// GPU and every other step starts ~230 us late; a kernel launch never blocks.
-// Every wave starts with a system-scope acquire (it drops the non-coherent lines of its L2): a
-// caller that refills a block buffer it has used before (the trainers' ring) must not be served
-// lines of the previous block that are still on-die, should the runtime map its page-locked memory
-// cacheable.  (System-scope LOADS instead -- 8 bytes per lane -- halved the upload rate.)
-struct PullJob {
-  const char *src[5]; char *dst[5]; unsigned bytes[5];
-  long long ordinal; long long *pulled; unsigned *ticket;  // completion word (host memory), see h_pulled
-  // rows handed over without a field array (one entry per field in field order): the slot's field
-  // array is written here -- entry j of the block is field j mod n_fields -- instead of crossing PCIe
-  int *gen_field; unsigned gen_n; int gen_fields;
-};
-// The kernel's text, shared with the weighted variant below.  Macros on purpose: the same text as a
-// `__device__ __forceinline__` function called by both kernels compiles pull_block_kernel to 48 SGPRs and 16
-// VGPRs instead of 22 and 14 (the job struct, passed on by reference, is then loaded whole up front), and an
-// unweighted block's upload has to stay the kernel it was (profiles/sample_weights.md).
-#define FFM_PULL_BLOCK_ARRAYS(job)                                                                          \
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");                                                             \
-  const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;              \
-  _Pragma("unroll")                                                                                         \
-  for (int a = 0; a < 5; a++) {                                                                             \
-    const unsigned n16 = job.bytes[a] >> 4;                                                                 \
-    const int4 *s = reinterpret_cast<const int4 *>(job.src[a]);                                             \
-    int4 *d = reinterpret_cast<int4 *>(job.dst[a]);                                                         \
-    /* (one load per lane in flight: two, four and eight measured the same -- 42 GB/s is what a kernel reads over PCIe here) */ \
-    for (unsigned i = tid; i < n16; i += stride) d[i] = s[i];                                               \
-    const unsigned tail = job.bytes[a] & 15u; /* sizes are multiples of 4 */                                \
-    if (tid < (tail >> 2))                                                                                  \
-      reinterpret_cast<int *>(job.dst[a])[(n16 << 2) + tid] = reinterpret_cast<const int *>(job.src[a])[(n16 << 2) + tid]; \
-  }
-#define FFM_PULL_BLOCK_FINISH(job)                                                                          \
-  if (job.gen_n) {                                                                                          \
-    const unsigned n4 = job.gen_n >> 2, F = static_cast<unsigned>(job.gen_fields);                          \
-    for (unsigned i = tid; i < n4; i += stride) {                                                           \
-      const unsigned f0 = (4u * i) % F, f1 = f0 + 1u < F ? f0 + 1u : 0u, f2 = f1 + 1u < F ? f1 + 1u : 0u;   \
-      reinterpret_cast<int4 *>(job.gen_field)[i] = make_int4(static_cast<int>(f0), static_cast<int>(f1), static_cast<int>(f2), \
-                                                             static_cast<int>(f2 + 1u < F ? f2 + 1u : 0u)); \
-    }                                                                                                       \
-    if (tid < (job.gen_n & 3u)) job.gen_field[(n4 << 2) + tid] = static_cast<int>(((n4 << 2) + tid) % F);   \
-  }                                                                                                         \
-  /* the workgroup that finishes last publishes the block's number to the host */                           \
-  __syncthreads(); /* (every load of this workgroup has returned: its stores were issued after them) */     \
-  if (threadIdx.x == 0) {                                                                                   \
-    __threadfence();                                                                                        \
-    if (atomicAdd(job.ticket, 1u) == gridDim.x - 1) {                                                       \
-      *job.ticket = 0u;                                                                                     \
-      __hip_atomic_store(job.pulled, job.ordinal, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);             \
-    }                                                                                                       \
-  }
-__global__ __launch_bounds__(256) void pull_block_kernel(PullJob job) {
-  FFM_PULL_BLOCK_ARRAYS(job)
-  FFM_PULL_BLOCK_FINISH(job)
-}
-// A block with sample weights: the sixth array, n_rows floats, moves with the other five (whole 16-byte
-// vectors, then the last n_rows % 4 floats as single words) -- a kernel of its own, so that an
-// unweighted block's upload is the launch, and the kernel, it always was.
-struct PullWeightedJob { PullJob block; const char *wsrc; char *wdst; unsigned wbytes; };
-__global__ __launch_bounds__(256) void pull_block_weighted_kernel(PullWeightedJob wjob) {
-  const PullJob &job = wjob.block;
-  FFM_PULL_BLOCK_ARRAYS(job)
-  {
-    const unsigned n16 = wjob.wbytes >> 4;
-    const int4 *s = reinterpret_cast<const int4 *>(wjob.wsrc);
-    int4 *d = reinterpret_cast<int4 *>(wjob.wdst);
-    for (unsigned i = tid; i < n16; i += stride) d[i] = s[i];
-    const unsigned tail = wjob.wbytes & 15u;
-    if (tid < (tail >> 2))
-      reinterpret_cast<int *>(wjob.wdst)[(n16 << 2) + tid] = reinterpret_cast<const int *>(wjob.wsrc)[(n16 << 2) + tid];
-  }
-  FFM_PULL_BLOCK_FINISH(job)
-}
-// FFM_FLAG_HASH_IDS: the same two kernels with the ids hashed on their way through (csrc/hash_ids.h) --
-// kernels of their own, so that an unflagged engine's upload is the launch, and the kernel, it always was.
-// feat and field are taken out of the block's five arrays (their byte counts there are 0) and move in ONE
-// loop instead: they are equally long, so a lane loads the int4 of feat and the int4 of field, hashes four
-// entries and stores both; the last nnz % 4 entries go one by one.  No byte crosses PCIe twice, and the
-// integer work hides behind the link (the kernel is bound by PCIe).  fsrc == nullptr: no field array came
-// -- LR / FM, or FFM rows of one entry per field in field order, whose fields FFM_PULL_BLOCK_FINISH writes
-// and this loop recomputes the same way.
-struct PullHashJob {
-  PullWeightedJob w;
-  ftrl_hash::Map hm;
-  const char *isrc, *fsrc; char *idst, *fdst; unsigned hbytes;
-};
-#define FFM_PULL_BLOCK_HASHED(hj)                                                                           \
-  {                                                                                                         \
-    const unsigned n16 = hj.hbytes >> 4, F = static_cast<unsigned>(hj.hm.n_fields);                         \
-    for (unsigned i = tid; i < n16; i += stride) {                                                          \
-      const int4 ft = reinterpret_cast<const int4 *>(hj.isrc)[i];                                           \
-      int4 fl;                                                                                              \
-      if (hj.fsrc) {                                                                                        \
-        fl = reinterpret_cast<const int4 *>(hj.fsrc)[i];                                                    \
-        reinterpret_cast<int4 *>(hj.fdst)[i] = fl;                                                          \
-      } else fl = hj.hm.ffm ? hash_implicit_fields4(i, F) : make_int4(0, 0, 0, 0);                          \
-      reinterpret_cast<int4 *>(hj.idst)[i] = hash_entries4(hj.hm, fl, ft);                                  \
-    }                                                                                                       \
-    if (tid < ((hj.hbytes & 15u) >> 2)) {                                                                   \
-      const unsigned p = (n16 << 2) + tid;                                                                  \
-      int f = hj.hm.ffm ? static_cast<int>(p % F) : 0;                                                      \
-      if (hj.fsrc) {                                                                                        \
-        f = reinterpret_cast<const int *>(hj.fsrc)[p];                                                      \
-        reinterpret_cast<int *>(hj.fdst)[p] = f;                                                            \
-      }                                                                                                     \
-      reinterpret_cast<int *>(hj.idst)[p] = ftrl_hash::hash_entry(hj.hm, f, reinterpret_cast<const int *>(hj.isrc)[p]); \
-    }                                                                                                       \
-  }
-__global__ __launch_bounds__(256) void pull_block_hashed_kernel(PullHashJob hjob) {
-  const PullJob &job = hjob.w.block;
-  FFM_PULL_BLOCK_ARRAYS(job)
-  FFM_PULL_BLOCK_HASHED(hjob)
-  FFM_PULL_BLOCK_FINISH(job)
-}
-__global__ __launch_bounds__(256) void pull_block_weighted_hashed_kernel(PullHashJob hjob) {
-  const PullJob &job = hjob.w.block;
-  FFM_PULL_BLOCK_ARRAYS(job)
-  {
-    const unsigned n16 = hjob.w.wbytes >> 4;
-    const int4 *s = reinterpret_cast<const int4 *>(hjob.w.wsrc);
-    int4 *d = reinterpret_cast<int4 *>(hjob.w.wdst);
-    for (unsigned i = tid; i < n16; i += stride) d[i] = s[i];
-    const unsigned tail = hjob.w.wbytes & 15u;
-    if (tid < (tail >> 2))
-      reinterpret_cast<int *>(hjob.w.wdst)[(n16 << 2) + tid] = reinterpret_cast<const int *>(hjob.w.wsrc)[(n16 << 2) + tid];
-  }
-  FFM_PULL_BLOCK_HASHED(hjob)
-  FFM_PULL_BLOCK_FINISH(job)
-}
-// A block handed over without values (val == NULL: every value is 1.0f, include/ffm_engine.h "Rows without
-// values"): nothing of val is in the job's five arrays, and the upload writes the slot's val array itself,
-// over its own grid stride, the way FFM_PULL_BLOCK_FINISH writes a missing field array -- a lane stores four
-// 1.0f as one 16-byte vector, the last n % 4 go singly.  The stores hide behind the link (the kernel is bound
-// by PCIe).  Every such block writes them again: a block that brought its values may have used the slot in
-// between.  Kernels of their own once more, so that a block WITH its values is uploaded by the launch, and
-// the kernel, it always was; the four above keep their text (profiles/implicit_ones.md).
-#define FFM_PULL_BLOCK_ONES(dst, n)                                                                         \
-  {                                                                                                         \
-    const unsigned n4 = (n) >> 2;                                                                           \
-    const float4 ones4 = make_float4(1.0f, 1.0f, 1.0f, 1.0f);                                               \
-    for (unsigned i = tid; i < n4; i += stride) reinterpret_cast<float4 *>(dst)[i] = ones4;                 \
-    if (tid < ((n) & 3u)) (dst)[(n4 << 2) + tid] = 1.0f;                                                    \
-  }
-#define FFM_PULL_BLOCK_WEIGHTS(wj)                                                                          \
-  {                                                                                                         \
-    const unsigned n16 = wj.wbytes >> 4;                                                                    \
-    const int4 *s = reinterpret_cast<const int4 *>(wj.wsrc);                                                \
-    int4 *d = reinterpret_cast<int4 *>(wj.wdst);                                                            \
-    for (unsigned i = tid; i < n16; i += stride) d[i] = s[i];                                               \
-    const unsigned tail = wj.wbytes & 15u;                                                                  \
-    if (tid < (tail >> 2))                                                                                  \
-      reinterpret_cast<int *>(wj.wdst)[(n16 << 2) + tid] = reinterpret_cast<const int *>(wj.wsrc)[(n16 << 2) + tid]; \
-  }
-__global__ __launch_bounds__(256) void pull_block_ones_kernel(PullJob job, float *ones, unsigned n_ones) {
-  FFM_PULL_BLOCK_ARRAYS(job)
-  FFM_PULL_BLOCK_ONES(ones, n_ones)
-  FFM_PULL_BLOCK_FINISH(job)
-}
-__global__ __launch_bounds__(256) void pull_block_weighted_ones_kernel(PullWeightedJob wjob, float *ones, unsigned n_ones) {
-  const PullJob &job = wjob.block;
-  FFM_PULL_BLOCK_ARRAYS(job)
-  FFM_PULL_BLOCK_WEIGHTS(wjob)
-  FFM_PULL_BLOCK_ONES(ones, n_ones)
-  FFM_PULL_BLOCK_FINISH(job)
-}
-__global__ __launch_bounds__(256) void pull_block_hashed_ones_kernel(PullHashJob hjob, float *ones, unsigned n_ones) {
-  const PullJob &job = hjob.w.block;
-  FFM_PULL_BLOCK_ARRAYS(job)
-  FFM_PULL_BLOCK_HASHED(hjob)
-  FFM_PULL_BLOCK_ONES(ones, n_ones)
-  FFM_PULL_BLOCK_FINISH(job)
-}
-__global__ __launch_bounds__(256) void pull_block_weighted_hashed_ones_kernel(PullHashJob hjob, float *ones, unsigned n_ones) {
-  const PullJob &job = hjob.w.block;
-  FFM_PULL_BLOCK_ARRAYS(job)
-  FFM_PULL_BLOCK_WEIGHTS(hjob.w)
-  FFM_PULL_BLOCK_HASHED(hjob)
-  FFM_PULL_BLOCK_ONES(ones, n_ones)
-  FFM_PULL_BLOCK_FINISH(job)
-}
-#undef FFM_PULL_BLOCK_WEIGHTS
-#undef FFM_PULL_BLOCK_ONES
-#undef FFM_PULL_BLOCK_HASHED
-#undef FFM_PULL_BLOCK_ARRAYS
-#undef FFM_PULL_BLOCK_FINISH
-
-// The mirror image of the upload: the scores of one predicted block go from e->d_out to the caller's
-// page-locked (device-mapped) host memory, 16 bytes per lane -- a lane carries four rows --, the last
-// n % 4 floats as single stores.  A kernel for the reason pull_block_kernel is one: a hipMemcpyAsync
-// makes the submitting thread wait for the stream's earlier kernels.  Launched on the MAIN stream
-// right behind the block's predict kernel (eval_launch_pending), so it needs no event.
-// The stores leave the device: every lane follows its own with a system-scope release fence (the
-// upload's agent-scope __threadfence() orders nothing towards the host), and the workgroup that
-// finishes last publishes the block's staging number into h_scored, again at system scope -- a host
-// that reads the number (ffm_engine_blocks_scored, an acquire load) then reads whole scores.
-// It writes n floats and nothing behind them.
-struct PushJob {
-  const float *src; float *dst; unsigned n;
-  long long ordinal; long long *scored; unsigned *ticket;  // completion word (host memory), see h_scored
-};
-__global__ __launch_bounds__(256) void push_scores_kernel(PushJob job) {
-  const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
-  const unsigned n4 = job.n >> 2;
-  const float4 *s = reinterpret_cast<const float4 *>(job.src);
-  float4 *d = reinterpret_cast<float4 *>(job.dst);
-  for (unsigned i = tid; i < n4; i += stride) d[i] = s[i];
-  if (tid < (job.n & 3u)) job.dst[(n4 << 2) + tid] = job.src[(n4 << 2) + tid];
-  __threadfence_system();
-  __syncthreads();  // (every wave of this workgroup is past its fence: its scores are in host memory)
-  if (threadIdx.x == 0) {
-    if (__hip_atomic_fetch_add(job.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-      *job.ticket = 0u;
-      __hip_atomic_store(job.scored, job.ordinal, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-}
 
 static int slots_init(ffm_engine *e) {
   if (e->slots_ready) return FFM_OK;
@@ -283,19 +64,52 @@ int ffm_engine_unpin_host(void *p) {
   return FFM_OK;
 }
 
-// The next staging slot for a host block: waits until the slot's own pinned image is free, copies
-// the caller's arrays into it (unless zero_copy) and describes the upload (pull_block_kernel's
-// argument; the block's ordinal is n_staged_total + 1).  Bookkeeping of the slot is the caller's.
-static int claim_slot(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
-                      const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
-                      int32_t zero_copy, int *slot_out, bool *was_used, PullJob *job_out,
-                      const float *weight = nullptr, PullWeightedJob *wjob_out = nullptr, PullHashJob *hjob_out = nullptr) {
+// The device's address of host memory that the 16-byte lanes of the upload and download kernels can move:
+// page-locked, device-mapped and 16-byte aligned.  Null where it is not, and *why says what is wrong: the
+// runtime's error (not page-locked), or hipSuccess for memory that is only not aligned.
+static void *mapped16(const void *host, hipError_t *why) {
+  *why = hipSuccess;
+  if ((reinterpret_cast<uintptr_t>(host) & 15u) != 0) return nullptr;
+  void *mapped = nullptr;
+  *why = hipHostGetDevicePointer(&mapped, const_cast<void *>(host), 0);
+  if (*why == hipSuccess && !mapped) *why = hipErrorInvalidValue;
+  if (*why != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return (reinterpret_cast<uintptr_t>(mapped) & 15u) == 0 ? mapped : nullptr;
+}
+// ... for an array of the caller's own: refused (FFM_E_INVALID, last error set) where it is null.
+static void *mapped16_or_refuse(const void *host, const char *what) {
+  hipError_t why;
+  void *mapped = mapped16(host, &why);
+  if (!mapped)
+    fail(FFM_E_INVALID, std::string(what) + (why == hipSuccess ? " must be 16-byte aligned"
+                                                               : " must be page-locked, device-mapped host memory (ffm_engine_pin_host)"));
+  return mapped;
+}
+
+// What claim_slot hands back: the slot, whether it held a block before, whether the slot's field array will
+// hold the block's fields (uploaded, or written by the upload kernel), and the upload's argument -- the
+// whole PullHashJob, of which an instantiation takes the part it needs (launch_upload).
+struct SlotClaim {
+  int slot = 0;
+  bool was_used = false, has_field = false;
+  PullHashJob job{};  // (the hashed loop's part is filled on a flagged engine only)
+};
+
+// The next staging slot for a host block (`host`: the caller's arrays, field == nullptr on LR / FM): waits
+// until the slot's own pinned image is free, copies the caller's arrays into it (unless zero_copy) and
+// describes the upload (the block's ordinal is n_staged_total + 1).  Bookkeeping of the slot is the
+// caller's: slot_commit.
+static int claim_slot(ffm_engine *e, const Rows &host, const float *weight, int32_t zero_copy, SlotClaim *claim) {
+  const auto [n_rows, nnz, row_ptr, field, feat, val, label] = host;
   int rc;
   if ((rc = slots_init(e))) return rc;
   if (weight && n_rows > 0 && (rc = slot_weights_init(e))) return rc;
   ffm_engine::Slot &sl = e->slots[e->slot_next];
-  *slot_out = e->slot_next;
-  *was_used = sl.used;
+  claim->slot = e->slot_next;
+  claim->was_used = sl.used;
   if (sl.used && !sl.zero_copy) {
     ScopedTimer tm("stage:slot_wait");
     // the slot's own pinned image must have been pulled before it is overwritten.  (Not so for a
@@ -305,70 +119,92 @@ static int claim_slot(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t 
     HIP_TRY(hipEventSynchronize(sl.ev_copied));
   }
   // host arrays -> pinned image (the caller may reuse its buffers on return) -> device, prep stream
-  const size_t R1 = static_cast<size_t>(n_rows) + 1, E = static_cast<size_t>(nnz);
-  char *p = sl.pinned;
-  PullJob &job = *job_out;
+  const size_t R1 = static_cast<size_t>(n_rows) + 1, E = static_cast<size_t>(nnz), R = static_cast<size_t>(n_rows);
+  char *p = sl.pinned, *pw = sl.pinned_w;
+  PullHashJob &hj = claim->job;
+  PullJob &job = hj.w.block;
   int n_job = 0;
+  // Where put describes an array: as the next of the job's five, or as a part of the job of its own.
+  struct Part { const char **src; char **dst; unsigned *bytes; };
   // page-locked source of each array: the caller's own (zero_copy: untouched until the block has
-  // trained) or its image in the slot's pinned buffer; the device then pulls it (pull_block_kernel)
-  // (hashed_src: the array is feat or field of a flagged engine's block -- it goes to the hashed loop of the
-  // upload kernel, *hashed_src / *hashed_dst, instead of into the job's five)
-  auto put = [&](const void *src, size_t bytes, void *dst, const char **hashed_src = nullptr, char **hashed_dst = nullptr) -> hipError_t {
+  // trained) or its image in the slot's pinned buffer (*image, which moves on); the device then pulls it
+  // (pull_block_kernel)
+  auto put = [&](const void *src, size_t bytes, void *dst, const Part *own = nullptr, char **image = nullptr) -> hipError_t {
     if (!bytes || !src) return hipSuccess;
-    const void *host = src;
+    const void *host_src = src;
     if (!zero_copy) {
-      std::memcpy(p, src, bytes);
-      host = p;
-      p += (bytes + 15) & ~static_cast<size_t>(15);
+      char *&at = image ? *image : p;
+      std::memcpy(at, src, bytes);
+      host_src = at;
+      at += (bytes + 15) & ~static_cast<size_t>(15);
     }
-    void *mapped = nullptr;
-    hipError_t err = hipHostGetDevicePointer(&mapped, const_cast<void *>(host), 0);
-    if (err != hipSuccess) return err;
-    if ((reinterpret_cast<uintptr_t>(mapped) & 15u) != 0) return hipErrorInvalidValue;  // 16-byte aligned arrays only
-    if (hashed_src) {
-      *hashed_src = static_cast<const char *>(mapped);
-      *hashed_dst = static_cast<char *>(dst);
-      return hipSuccess;
-    }
-    job.src[n_job] = static_cast<const char *>(mapped);
-    job.dst[n_job] = static_cast<char *>(dst);
-    job.bytes[n_job] = static_cast<unsigned>(bytes);
-    n_job++;
+    hipError_t why;
+    void *mapped = mapped16(host_src, &why);
+    if (!mapped) return why != hipSuccess ? why : hipErrorInvalidValue;  // 16-byte aligned arrays only
+    const Part next{&job.src[n_job], &job.dst[n_job], &job.bytes[n_job]};
+    const Part &to = own ? *own : next;
+    *to.src = static_cast<const char *>(mapped);
+    *to.dst = static_cast<char *>(dst);
+    *to.bytes = static_cast<unsigned>(bytes);
+    if (!own) n_job++;
     return hipSuccess;
   };
-  PullHashJob *const hj = e->hash_ids ? hjob_out : nullptr;
-  if (hj) {
-    hj->hm = e->hm;
-    hj->hbytes = static_cast<unsigned>(4 * E);
-  }
+  // a flagged engine: feat and field go to the hashed loop of the upload kernel instead of into the job's five
+  const Part hashed_ids{&hj.isrc, &hj.idst, &hj.hbytes}, hashed_fields{&hj.fsrc, &hj.fdst, &hj.hbytes};
+  // the sixth array: beside the job's five (its image: the slot's pinned_w)
+  const Part weights{&hj.w.wsrc, &hj.w.wdst, &hj.w.wbytes};
+  if (e->hash_ids) hj.hm = e->hm;
   ScopedTimer tm("stage:copies");
   HIP_TRY(put(row_ptr, 4 * R1, sl.row_ptr));
-  if (field) HIP_TRY(put(field, 4 * E, sl.field, hj ? &hj->fsrc : nullptr, hj ? &hj->fdst : nullptr));
+  if (field) HIP_TRY(put(field, 4 * E, sl.field, e->hash_ids ? &hashed_fields : nullptr));
   else if (e->m.type == FFM_MODEL_FFM && E > 0) {  // (validated: one entry per field in field order)
     job.gen_field = sl.field;
     job.gen_n = static_cast<unsigned>(E);
     job.gen_fields = e->m.n_fields;
   }
-  HIP_TRY(put(feat, 4 * E, sl.feat, hj ? &hj->isrc : nullptr, hj ? &hj->idst : nullptr));
+  claim->has_field = field != nullptr || job.gen_n != 0;
+  HIP_TRY(put(feat, 4 * E, sl.feat, e->hash_ids ? &hashed_ids : nullptr));
   HIP_TRY(put(val, 4 * E, sl.val));  // (val == NULL: nothing to copy or describe -- the upload kernel writes ones)
-  HIP_TRY(put(label, 4 * static_cast<size_t>(n_rows), sl.label));
-  if (weight && n_rows > 0) {  // the sixth array: beside the job's five (its image: the slot's pinned_w)
-    const size_t wbytes = 4 * static_cast<size_t>(n_rows);
-    const void *host = weight;
-    if (!zero_copy) {
-      std::memcpy(sl.pinned_w, weight, wbytes);
-      host = sl.pinned_w;
-    }
-    void *mapped = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&mapped, const_cast<void *>(host), 0));
-    wjob_out->wsrc = static_cast<const char *>(mapped);
-    wjob_out->wdst = reinterpret_cast<char *>(sl.weight);
-    wjob_out->wbytes = static_cast<unsigned>(wbytes);
-  }
+  HIP_TRY(put(label, 4 * R, sl.label));
+  HIP_TRY(put(weight, 4 * R, sl.weight, &weights, &pw));
   job.ordinal = e->n_staged_total + 1;
   job.pulled = e->d_pulled;
   job.ticket = e->d_pull_ticket;
   return FFM_OK;
+}
+
+// The upload of one claimed block on stream `st`: the one place that names an instantiation of the upload kernel.
+// ones / n_ones: the slot's val array and how many 1.0f the kernel writes there (0: the block brought its values).
+static void launch_upload(ffm_engine *e, hipStream_t st, int grid, const PullHashJob &hj, float *ones, unsigned n_ones) {
+  auto launch = [&](auto weighted, auto hashed, const auto &arg) {
+    constexpr bool W = decltype(weighted)::value, H = decltype(hashed)::value;
+    if (n_ones) hipLaunchKernelGGL((pull_block_kernel<W, H, float *, unsigned>), dim3(grid), dim3(256), 0, st, arg, ones, n_ones);
+    else hipLaunchKernelGGL((pull_block_kernel<W, H>), dim3(grid), dim3(256), 0, st, arg);
+  };
+  const std::true_type yes{};
+  const std::false_type no{};
+  if (e->hash_ids && hj.w.wbytes) launch(yes, yes, hj);
+  else if (e->hash_ids) launch(no, yes, hj);
+  else if (hj.w.wbytes) launch(yes, no, hj.w);
+  else launch(no, no, hj.w.block);
+}
+
+// The claimed slot holds the block from here on (its upload is submitted): number seq = n_staged_total + 1.
+static void slot_commit(ffm_engine *e, const SlotClaim &claim, const Rows &host, int row_cap, bool has_weight, int32_t zero_copy) {
+  ffm_engine::Slot &sl = e->slots[claim.slot];
+  sl.used = true;
+  sl.zero_copy = zero_copy != 0;
+  sl.n_rows = host.n_rows;
+  sl.nnz = host.nnz;
+  sl.row_cap = row_cap;
+  sl.has_field = claim.has_field;
+  sl.has_weight = has_weight;
+  sl.seq = ++e->n_staged_total;
+  e->slot_next = (e->slot_next + 1) % ffm_engine::kSlots;
+}
+// The block a slot holds, as the kernels take it.
+static Rows slot_rows(const ffm_engine::Slot &sl, const int *label) {
+  return Rows{sl.n_rows, sl.nnz, sl.row_ptr, sl.has_field ? sl.field : nullptr, sl.feat, sl.val, label};
 }
 
 // Stage one block of host rows: (pinned image ->) HBM -> grouping, all on the prep stream.
@@ -378,25 +214,13 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
   SERVE_REFUSE(e, "training");  // (staging is training's: prediction stages through predict_batch_async)
   int32_t nnz = 0;
   int longest = 1;
-  // (LR / FM rows have no fields -- libsvm: src/data/parser.cpp:20 gives every entry field 0 -- so a
-  // field array the caller passes along is not uploaded: a third of the block's bytes over PCIe)
-  if (e && e->m.type != FFM_MODEL_FFM) field = nullptr;
-  int rc = validate_host_block(e, n_rows, row_ptr, field, feat, val, &nnz, &longest, true);
+  int rc = validate_host_block(e, n_rows, row_ptr, &field, feat, val, &nnz, &longest, true);
   if (rc) return rc;
-  const bool has_field = field != nullptr || (e->m.type == FFM_MODEL_FFM && nnz > 0);  // (uploaded or written by the upload kernel)
   if (n_rows > 0 && !label) return fail(FFM_E_INVALID, "training needs labels");
   if (n_rows == 0) weight = nullptr;
   if (weight) {  // refused here, on the caller's thread, before anything of the block is queued
     if ((rc = validate_host_weights(n_rows, weight))) return rc;
-    if (zero_copy) {
-      if ((reinterpret_cast<uintptr_t>(weight) & 15u) != 0) return fail(FFM_E_INVALID, "a zero_copy weight array must be 16-byte aligned");
-      void *mapped = nullptr;
-      if (hipHostGetDevicePointer(&mapped, const_cast<float *>(weight), 0) != hipSuccess || !mapped) {
-        (void)hipGetLastError();
-        return fail(FFM_E_INVALID, "a zero_copy weight array must be page-locked, device-mapped host memory (ffm_engine_pin_host)");
-      }
-      if ((reinterpret_cast<uintptr_t>(mapped) & 15u) != 0) return fail(FFM_E_INVALID, "a zero_copy weight array must be 16-byte aligned");
-    }
+    if (zero_copy && !mapped16_or_refuse(weight, "a zero_copy weight array")) return FFM_E_INVALID;
   }
   if ((rc = eval_launch_pending(e))) return rc;
   if (e->n_staged >= ffm_engine::kSlots - 1) return fail(FFM_E_CAPACITY, "three staged blocks are already waiting");
@@ -406,28 +230,23 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
   // that then failed to stage would leave the count one ahead for good
   if (e->n_prepared >= ffm_engine::kSets - 1) return fail(FFM_E_CAPACITY, "three prepared blocks are already waiting");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
-  int this_slot = 0;
-  bool slot_was_used = false;
-  PullHashJob hjob{};  // (the hashed loop's part is filled on a flagged engine only)
-  PullWeightedJob &job = hjob.w;
-  if ((rc = claim_slot(e, n_rows, nnz, row_ptr, field, feat, val, label, zero_copy, &this_slot, &slot_was_used, &job.block,
-                       weight, &job, &hjob)))
-    return rc;
+  const Rows host{n_rows, nnz, row_ptr, field, feat, val, label};
+  SlotClaim claim;
+  if ((rc = claim_slot(e, host, weight, zero_copy, &claim))) return rc;
+  const int this_slot = claim.slot;
   ffm_engine::Slot &sl = e->slots[this_slot];
   // its grouping, behind its own upload on the prep stream: planned here, submitted with the upload
   PrepPlan plan;
-  if ((rc = prepare_plan(e, Rows{n_rows, nnz, sl.row_ptr, has_field ? sl.field : nullptr, sl.feat, sl.val, nullptr}, &plan)))
+  if ((rc = prepare_plan(e, Rows{n_rows, nnz, sl.row_ptr, claim.has_field ? sl.field : nullptr, sl.feat, sl.val, nullptr}, &plan)))
     return rc;
   const int64_t seq = e->n_staged_total + 1;
   const int grid_pull = e->grid_pull;
   const bool timed = e->prof_on;  // (then submit runs the job on this thread)
-  hipEvent_t free_ev = slot_was_used ? sl.free_ev : nullptr;
-  const bool hashed = e->hash_ids;
+  hipEvent_t free_ev = claim.was_used ? sl.free_ev : nullptr;
   // (val == NULL: the upload writes the slot's values -- every time, whatever the slot held before)
   float *const ones = sl.val;
   const unsigned n_ones = val ? 0u : static_cast<unsigned>(nnz);
-  rc = e->submit([e, this_slot, free_ev, hjob, hashed, plan, seq, grid_pull, timed, ones, n_ones]() -> int {
-    const PullWeightedJob &job = hjob.w;
+  rc = e->submit([e, this_slot, free_ev, hjob = claim.job, plan, seq, grid_pull, timed, ones, n_ones]() -> int {
     ScopedTimer tm("stage:submit");
     ffm_engine::Slot &s2 = e->slots[this_slot];
     int rc2 = FFM_OK;
@@ -437,16 +256,7 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
       // (long steps: the upload too waits for the running block's row kernel to end -- beside the update
       // launches it costs nothing, beside the row kernel, which is bound by the bytes it moves, it does)
       if (e->pull_after_row && plan.ws >= 0) HIP_TRY(hipStreamWaitEvent(e->prep, e->prep_after_row ? e->ev_row_done[plan.ws] : e->ev_set_free[plan.ws], 0));
-      if (n_ones) {
-        if (hashed && job.wbytes) hipLaunchKernelGGL(pull_block_weighted_hashed_ones_kernel, dim3(grid_pull), dim3(256), 0, e->prep, hjob, ones, n_ones);
-        else if (hashed) hipLaunchKernelGGL(pull_block_hashed_ones_kernel, dim3(grid_pull), dim3(256), 0, e->prep, hjob, ones, n_ones);
-        else if (job.wbytes) hipLaunchKernelGGL(pull_block_weighted_ones_kernel, dim3(grid_pull), dim3(256), 0, e->prep, job, ones, n_ones);
-        else hipLaunchKernelGGL(pull_block_ones_kernel, dim3(grid_pull), dim3(256), 0, e->prep, job.block, ones, n_ones);
-      }
-      else if (hashed && job.wbytes) hipLaunchKernelGGL(pull_block_weighted_hashed_kernel, dim3(grid_pull), dim3(256), 0, e->prep, hjob);
-      else if (hashed) hipLaunchKernelGGL(pull_block_hashed_kernel, dim3(grid_pull), dim3(256), 0, e->prep, hjob);
-      else if (job.wbytes) hipLaunchKernelGGL(pull_block_weighted_kernel, dim3(grid_pull), dim3(256), 0, e->prep, job);
-      else hipLaunchKernelGGL(pull_block_kernel, dim3(grid_pull), dim3(256), 0, e->prep, job.block);
+      launch_upload(e, e->prep, grid_pull, hjob, ones, n_ones);
       HIP_TRY(hipEventRecord(s2.ev_copied, e->prep));
       return prepare_submit(e, plan, timed);
     };
@@ -458,15 +268,7 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
     return rc2;
   });
   if (rc) return rc;
-  sl.used = true;
-  sl.zero_copy = zero_copy != 0;
-  sl.n_rows = n_rows;
-  sl.nnz = nnz;
-  sl.row_cap = longest;
-  sl.has_field = has_field;
-  sl.has_weight = weight != nullptr;
-  sl.seq = ++e->n_staged_total;
-  e->slot_next = (e->slot_next + 1) % ffm_engine::kSlots;
+  slot_commit(e, claim, host, longest, weight != nullptr, zero_copy);
   e->staged[e->n_staged++] = this_slot;
   return FFM_OK;
 }
@@ -494,38 +296,37 @@ int64_t ffm_engine_blocks_scored(ffm_engine *e) {
   return std::max(seen, had);
 }
 
-// Phase 1 (grouping is done: refresh + forward) on the oldest staged block.
-int ffm_engine_train_forward_staged(ffm_engine *e, float *partial_logit) {
+// Phase 1 (grouping is done: refresh + forward) on the oldest staged block; opts.row_cap: set here, the slot's.
+static int forward_staged(ffm_engine *e, float *partial_logit, ForwardOpts opts) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
   SERVE_REFUSE(e, "training");
   if (e->n_staged == 0) return fail(FFM_E_INVALID, "no staged block");
   if (e->has_pending) return fail(FFM_E_INVALID, "the previous block still awaits train_update");
   const int slot = e->staged[0];
   ffm_engine::Slot &sl = e->slots[slot];
-  e->staged_row_cap = sl.row_cap;
+  opts.row_cap = sl.row_cap;
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   if (int rc_w = e->wait_issued(sl.seq)) return rc_w;  // its upload + grouping launches are out
   // its grouping (behind the upload on the prep stream, or waiting for it there) implies the upload:
   // the main stream waits for ev_copied itself only when that grouping was discarded
-  const Rows staged_rows{sl.n_rows, sl.nnz, sl.row_ptr, sl.has_field ? sl.field : nullptr, sl.feat, sl.val, nullptr};
-  if (!(e->n_prepared > 0 && same_block(e->prepared_rows[0], staged_rows)))
+  if (!(e->n_prepared > 0 && same_block(e->prepared_rows[0], slot_rows(sl, nullptr))))
     HIP_TRY(hipStreamWaitEvent(e->stream, sl.ev_copied, 0));
-  int rc = train_forward_core(e, sl.n_rows, sl.nnz, sl.row_ptr, sl.has_field ? sl.field : nullptr,
-                              sl.feat, sl.val, sl.label, sl.has_weight ? sl.weight : nullptr, partial_logit);
+  int rc = train_forward_core(e, slot_rows(sl, sl.label), sl.has_weight ? sl.weight : nullptr, partial_logit, opts);
   if (rc) return rc;
   for (int i = 1; i < e->n_staged; i++) e->staged[i - 1] = e->staged[i];
   e->n_staged--;
   e->cur_slot = slot;  // released (ev_trained) by the train_update that follows
   return FFM_OK;
 }
+int ffm_engine_train_forward_staged(ffm_engine *e, float *partial_logit) {
+  return forward_staged(e, partial_logit, ForwardOpts{});
+}
 
 // Whole step (ffm_engine_train_batch_device) on the oldest staged block.
 int ffm_engine_train_staged(ffm_engine *e, float *logit_out, double *loss_sum_out) {
   if (e && e->m.n_shards > 1)
     return fail(FFM_E_INVALID, "sharded engines train with train_forward_staged + all-reduce + train_update");
-  if (e) { e->whole_step = true; e->own_logit_out = logit_out; }
-  int rc = ffm_engine_train_forward_staged(e, nullptr);
-  if (e) e->whole_step = false;
+  int rc = forward_staged(e, nullptr, ForwardOpts{0, true, logit_out});
   if (rc) return rc;
   return ffm_engine_train_update_device(e, nullptr, logit_out, loss_sum_out);
 }
@@ -580,10 +381,8 @@ static int eval_launch_pending(ffm_engine *e) {
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   auto launch = [&]() -> int {
     HIP_TRY(hipStreamWaitEvent(e->stream, sl.ev_copied, 0));
-    e->staged_row_cap = sl.row_cap;
-    int rc = ffm_engine_predict_batch_device(e, sl.n_rows, sl.nnz, sl.row_ptr, sl.has_field ? sl.field : nullptr, sl.feat,
-                                             sl.val, labelled ? sl.label : nullptr, output_prob, e->d_out,
-                                             labelled ? e->d_loss_sum : nullptr);
+    int rc = predict_core(e, slot_rows(sl, labelled ? sl.label : nullptr), output_prob, e->d_out,
+                          labelled ? e->d_loss_sum : nullptr, sl.row_cap);
     if (rc) return rc;
     if (labelled) hipLaunchKernelGGL(loss_accumulate_kernel, dim3(1), dim3(1), 0, e->stream, e->d_loss_acc, e->d_loss_sum);
     if (scores) {
@@ -620,56 +419,30 @@ int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const i
                                           float *scores_host) {
   int32_t nnz = 0;
   int longest = 1;
-  if (e && e->m.type != FFM_MODEL_FFM) field = nullptr;  // (LR / FM: no fields to upload)
-  if (e) e->eval_hold = true;  // (the deferred block waits until this one's upload is submitted)
-  int rc = validate_host_block(e, n_rows, row_ptr, field, feat, val, &nnz, &longest, true);
-  if (e) e->eval_hold = false;
+  // (hold_eval: the deferred block waits until this one's upload is submitted)
+  int rc = validate_host_block(e, n_rows, row_ptr, &field, feat, val, &nnz, &longest, true, true);
   if (rc) return rc;
-  const bool has_field = field != nullptr || (e->m.type == FFM_MODEL_FFM && nnz > 0);  // (uploaded or written by the upload kernel)
   if (e->m.n_shards > 1) return fail(FFM_E_INVALID, "a sharded engine predicts through predict_batch_device + predict_finish_device");
   if (e->n_staged > 0 || e->has_pending) return fail(FFM_E_INVALID, "staged training blocks are still waiting");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   // (refused before the upload is launched: that kernel publishes the block's number)
   float *scores_dev = nullptr;
-  if (scores_host) {
-    if ((reinterpret_cast<uintptr_t>(scores_host) & 15u) != 0) return fail(FFM_E_INVALID, "scores_host must be 16-byte aligned");
-    void *mapped = nullptr;
-    if (hipHostGetDevicePointer(&mapped, scores_host, 0) != hipSuccess || !mapped) {
-      (void)hipGetLastError();
-      return fail(FFM_E_INVALID, "scores_host must be page-locked, device-mapped host memory (ffm_engine_pin_host)");
-    }
-    if ((reinterpret_cast<uintptr_t>(mapped) & 15u) != 0) return fail(FFM_E_INVALID, "scores_host must be 16-byte aligned");
-    scores_dev = static_cast<float *>(mapped);
-  }
+  if (scores_host && !(scores_dev = static_cast<float *>(mapped16_or_refuse(scores_host, "scores_host")))) return FFM_E_INVALID;
   if ((rc = e->drain())) return rc;
-  int this_slot = 0;
-  bool slot_was_used = false;
-  PullHashJob hjob{};  // (the hashed loop's part is filled on a flagged engine only)
-  PullJob &job = hjob.w.block;
-  if ((rc = claim_slot(e, n_rows, nnz, row_ptr, field, feat, val, label, zero_copy, &this_slot, &slot_was_used, &job, nullptr,
-                       nullptr, &hjob)))
-    return rc;
+  const Rows host{n_rows, nnz, row_ptr, field, feat, val, label};
+  SlotClaim claim;
+  if ((rc = claim_slot(e, host, nullptr, zero_copy, &claim))) return rc;
+  const int this_slot = claim.slot;
   ffm_engine::Slot &sl = e->slots[this_slot];
-  if (slot_was_used && sl.free_ev) HIP_TRY(hipStreamWaitEvent(e->prep, sl.free_ev, 0));  // nothing reads its device arrays
-  if (!val && nnz > 0) {  // (no values came: the upload writes the slot's)
-    if (e->hash_ids) hipLaunchKernelGGL(pull_block_hashed_ones_kernel, dim3(e->grid_pull), dim3(256), 0, e->prep, hjob, sl.val, static_cast<unsigned>(nnz));
-    else hipLaunchKernelGGL(pull_block_ones_kernel, dim3(e->grid_pull), dim3(256), 0, e->prep, job, sl.val, static_cast<unsigned>(nnz));
-  }
-  else if (e->hash_ids) hipLaunchKernelGGL(pull_block_hashed_kernel, dim3(e->grid_pull), dim3(256), 0, e->prep, hjob);
-  else hipLaunchKernelGGL(pull_block_kernel, dim3(e->grid_pull), dim3(256), 0, e->prep, job);
+  if (claim.was_used && sl.free_ev) HIP_TRY(hipStreamWaitEvent(e->prep, sl.free_ev, 0));  // nothing reads its device arrays
+  // (no values came: the upload writes the slot's)
+  launch_upload(e, e->prep, e->grid_pull, claim.job, sl.val, val ? 0u : static_cast<unsigned>(nnz));
   HIP_TRY(hipEventRecord(sl.ev_copied, e->prep));
-  sl.used = true;
-  sl.zero_copy = zero_copy != 0;
-  sl.n_rows = n_rows;
-  sl.nnz = nnz;
-  sl.row_cap = longest;
-  sl.has_field = has_field;
-  sl.seq = ++e->n_staged_total;
+  slot_commit(e, claim, host, longest, false, zero_copy);
   {
     std::lock_guard<std::mutex> lock(e->wmu);
     e->staged_issued = sl.seq;
   }
-  e->slot_next = (e->slot_next + 1) % ffm_engine::kSlots;
   HIP_TRY(hipGetLastError());
   if ((rc = eval_launch_pending(e))) return rc;  // the block of the call before, behind this upload
   e->eval_pending.on = true;

@@ -9,13 +9,15 @@ static void launch_metric(ffm_engine *e, int channel, int n_rows, const float *s
 static void launch_keyed(ffm_engine *e, int channel, const Rows &rows, const float *score, int is_prob);  // (engine_keyed.h)
 __global__ void loss_accumulate_kernel(double *acc, const double *one) { *acc += *one; }
 
+// hold_eval: do not launch the deferred evaluation block now (predict_batch_async: it waits until this
+// block's upload is submitted)
 static int check_block(ffm_engine *e, int32_t n_rows, int32_t nnz, const void *row_ptr,
                        const void *field, const void *feat, const void *val, bool implicit_fields = false,
-                       bool implicit_ones = false) {
+                       bool implicit_ones = false, bool hold_eval = false) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
   // an evaluation block whose predict launch predict_batch_async deferred goes first (every entry
   // point that puts work on the main stream passes here)
-  if (e->eval_pending.on && !e->eval_hold)
+  if (e->eval_pending.on && !hold_eval)
     if (int rc_e = eval_launch_pending(e)) return rc_e;
   if (n_rows < 0 || nnz < 0) return fail(FFM_E_INVALID, "negative n_rows / nnz");
   if (n_rows > e->max_rows || nnz > e->max_nnz)
@@ -42,12 +44,13 @@ static bool launch_row_waves(ffm_engine *e, const Rows &rows, int row_cap, float
   return true;
 }
 
+// row_cap: the longest row of the block where the caller knows it (rows that came in host memory), 0 = unknown
+// (device callers: max_row_nnz).  The row kernels size their LDS by it, which decides how many rows a CU holds.
 // weight: the block's sample weights (device) or null; only the launches that produce tmp_grad
 // themselves (own_tg) take them -- otherwise tmp_grad_weighted_kernel does, after the logits are whole.
-static void launch_row_kernel(ffm_engine *e, const Rows &rows, bool train, float *out, int output_prob, int own_tg = 0,
+static void launch_row_kernel(ffm_engine *e, const Rows &rows, int row_cap, bool train, float *out, int output_prob, int own_tg = 0,
                               const float *weight = nullptr) {
-  const int row_cap = e->staged_row_cap > 0 ? e->staged_row_cap : e->max_row_nnz;
-  e->staged_row_cap = 0;
+  if (row_cap <= 0) row_cap = e->max_row_nnz;
   if (rows.n_rows == 0) return;
   if (serving(e)) {  // (predict only: every training entry point is refused) -- its own kernel and nothing else
     launch_row_waves(e, rows, row_cap, out, output_prob);
@@ -243,25 +246,29 @@ int ffm_engine_prepare_device(ffm_engine *e, int32_t n_rows, int32_t nnz, const 
   return prepare_submit(e, pl, true);
 }
 
+// What a forward call is told by its caller about this one block (nothing of it outlives the call).
+struct ForwardOpts {
+  int row_cap = 0;             // the block's longest row where the caller knows it (launch_row_kernel)
+  bool whole_step = false;     // forward + update in one call (train_batch_device, train_staged) ...
+  float *logit_out = nullptr;  // ... whose row kernel, where it has the whole logit, writes the logits here
+};
+
 // weight: the block's sample weights (device, [n_rows]) or null; remembered with the pending block
-static int train_forward_core(ffm_engine *e, int32_t n_rows, int32_t nnz,
-                              const int32_t *row_ptr, const int32_t *field,
-                              const int32_t *feat, const float *val, const int32_t *label,
-                              const float *weight, float *partial_logit) {
+static int train_forward_core(ffm_engine *e, const Rows &rows, const float *weight, float *partial_logit,
+                              const ForwardOpts &opts) {
   ScopedTimer tm_fwd("train:forward");
   SERVE_REFUSE(e, "training");
-  int rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val);
+  const int32_t n_rows = rows.n_rows;
+  int rc = check_block(e, n_rows, rows.nnz, rows.row_ptr, rows.field, rows.feat, rows.val);
   if (rc) return rc;
-  if (n_rows > 0 && !label) return fail(FFM_E_INVALID, "training needs labels");
+  if (n_rows > 0 && !rows.label) return fail(FFM_E_INVALID, "training needs labels");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
-  Rows rows{n_rows, nnz, row_ptr, field, feat, val, label};
   e->pending = rows;
   e->pending_weight = n_rows > 0 ? weight : nullptr;
   e->has_pending = true;
   // only train_batch_device has the whole logit in its row kernel (one shard, FFM / LR)
-  e->own_tg_cur = e->whole_step && e->m.n_shards == 1 &&
+  e->own_tg_cur = opts.whole_step && e->m.n_shards == 1 &&
                   (e->m.type != FFM_MODEL_FM || e->m.n_factors <= 64);  // (FM: fm_row_wave_kernel)
-  e->whole_step = false;
   const bool use_prepared = e->n_prepared > 0 && same_block(e->prepared_rows[0], rows);
   if (e->n_prepared > 0 && !use_prepared) {
     // groupings made ahead for some other block: forget them all
@@ -286,7 +293,7 @@ static int train_forward_core(ffm_engine *e, int32_t n_rows, int32_t nnz,
     if (rc) return rc;
   }
   e->set_used[e->cur] = true;
-  launch_row_kernel(e, rows, true, e->own_tg_cur ? e->own_logit_out : nullptr, 0, e->own_tg_cur ? 1 : 0, e->pending_weight);
+  launch_row_kernel(e, rows, opts.row_cap, true, e->own_tg_cur ? opts.logit_out : nullptr, 0, e->own_tg_cur ? 1 : 0, e->pending_weight);
   if (e->prep_after_row) HIP_TRY(hipEventRecord(e->ev_row_done[e->cur], e->stream));
   if (partial_logit && n_rows > 0)
     HIP_TRY(hipMemcpyAsync(partial_logit, e->sc[e->cur].logit, sizeof(float) * n_rows, hipMemcpyDeviceToDevice, e->stream));
@@ -298,13 +305,13 @@ int ffm_engine_train_forward_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
                                     const int32_t *row_ptr, const int32_t *field,
                                     const int32_t *feat, const float *val, const int32_t *label,
                                     float *partial_logit) {
-  return train_forward_core(e, n_rows, nnz, row_ptr, field, feat, val, label, nullptr, partial_logit);
+  return train_forward_core(e, Rows{n_rows, nnz, row_ptr, field, feat, val, label}, nullptr, partial_logit, ForwardOpts{});
 }
 int ffm_engine_train_forward_device_weighted(ffm_engine *e, int32_t n_rows, int32_t nnz,
                                              const int32_t *row_ptr, const int32_t *field,
                                              const int32_t *feat, const float *val, const int32_t *label,
                                              const float *weight, float *partial_logit) {
-  return train_forward_core(e, n_rows, nnz, row_ptr, field, feat, val, label, weight, partial_logit);
+  return train_forward_core(e, Rows{n_rows, nnz, row_ptr, field, feat, val, label}, weight, partial_logit, ForwardOpts{});
 }
 
 int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *logit_out,
@@ -487,17 +494,20 @@ int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *log
   return FFM_OK;
 }
 
+// The whole step on a block in HBM; row_cap as launch_row_kernel takes it.
+static int train_batch_core(ffm_engine *e, const Rows &rows, const float *weight, float *logit_out, double *loss_sum_out,
+                            int row_cap) {
+  if (e && e->m.n_shards > 1)
+    return fail(FFM_E_INVALID, "sharded engines train with train_forward + all-reduce + train_update");
+  int rc = train_forward_core(e, rows, weight, nullptr, ForwardOpts{row_cap, true, logit_out});
+  if (rc) return rc;
+  return ffm_engine_train_update_device(e, nullptr, logit_out, loss_sum_out);
+}
 int ffm_engine_train_batch_device_weighted(ffm_engine *e, int32_t n_rows, int32_t nnz,
                                            const int32_t *row_ptr, const int32_t *field,
                                            const int32_t *feat, const float *val, const int32_t *label,
                                            const float *weight, float *logit_out, double *loss_sum_out) {
-  if (e && e->m.n_shards > 1)
-    return fail(FFM_E_INVALID, "sharded engines train with train_forward + all-reduce + train_update");
-  if (e) { e->whole_step = true; e->own_logit_out = logit_out; }
-  int rc = train_forward_core(e, n_rows, nnz, row_ptr, field, feat, val, label, weight, nullptr);
-  if (e) e->whole_step = false;
-  if (rc) return rc;
-  return ffm_engine_train_update_device(e, nullptr, logit_out, loss_sum_out);
+  return train_batch_core(e, Rows{n_rows, nnz, row_ptr, field, feat, val, label}, weight, logit_out, loss_sum_out, 0);
 }
 int ffm_engine_train_batch_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
                                   const int32_t *row_ptr, const int32_t *field,
@@ -507,24 +517,29 @@ int ffm_engine_train_batch_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
                                                 loss_sum_out);
 }
 
-int ffm_engine_predict_batch_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
-                                    const int32_t *row_ptr, const int32_t *field,
-                                    const int32_t *feat, const float *val, const int32_t *label,
-                                    int32_t output_prob, float *out, double *loss_sum_out) {
-  int rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val);
+// Prediction of a block in HBM; row_cap as launch_row_kernel takes it.
+static int predict_core(ffm_engine *e, const Rows &rows, int32_t output_prob, float *out, double *loss_sum_out, int row_cap) {
+  const int32_t n_rows = rows.n_rows;
+  const int32_t *const label = rows.label;
+  int rc = check_block(e, n_rows, rows.nnz, rows.row_ptr, rows.field, rows.feat, rows.val);
   if (rc) return rc;
   if (e->m.n_shards > 1 && (label || output_prob || loss_sum_out))
     return fail(FFM_E_INVALID, "a sharded engine predicts partial logits only (label = NULL, output_prob = 0, "
                                "no loss): sum them across shards, then ffm_engine_predict_finish_device");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
-  Rows rows{n_rows, nnz, row_ptr, field, feat, val, label};
-  launch_row_kernel(e, rows, false, out ? out : e->d_out, output_prob);
+  launch_row_kernel(e, rows, row_cap, false, out ? out : e->d_out, output_prob);
   if (label) launch_metric(e, FFM_METRIC_EVAL, n_rows, out ? out : e->d_out, output_prob, label);
   if (label) launch_keyed(e, FFM_METRIC_EVAL, rows, out ? out : e->d_out, output_prob);
   if (loss_sum_out && label)
     LAUNCH(e, K_LOSS_SUM, loss_sum_kernel, loss_grid(n_rows), 256, 0, n_rows, e->sc[e->cur].loss, loss_sum_out, e->d_loss_part);
   HIP_TRY(hipGetLastError());
   return FFM_OK;
+}
+int ffm_engine_predict_batch_device(ffm_engine *e, int32_t n_rows, int32_t nnz,
+                                    const int32_t *row_ptr, const int32_t *field,
+                                    const int32_t *feat, const float *val, const int32_t *label,
+                                    int32_t output_prob, float *out, double *loss_sum_out) {
+  return predict_core(e, Rows{n_rows, nnz, row_ptr, field, feat, val, label}, output_prob, out, loss_sum_out, 0);
 }
 
 int ffm_engine_predict_finish_device(ffm_engine *e, int32_t n_rows, const float *logit,
@@ -547,14 +562,19 @@ int ffm_engine_predict_finish_device(ffm_engine *e, int32_t n_rows, const float 
 }
 
 // Checks one block of host arrays; returns its nnz and its longest row.
+// *field: null afterwards on LR / FM, whose rows have no fields (libsvm: src/data/parser.cpp:20 gives every
+// entry field 0) -- a field array the caller passes along is not uploaded: a third of the block's bytes over PCIe.
+// hold_eval: as check_block takes it.
 // implicit_fields (the staged entry points, FFM, field == NULL): every row must then hold exactly one
 // entry per field, entry j of a row being field j's -- the upload kernel writes the field array itself.
 // Rows in host memory may always come without values (val == NULL: every value is 1.0f): the array is written
 // on the device, by the upload kernel (engine_stage.h) or, on the synchronous calls, by stage_block's fill.
 static int validate_host_block(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
-                               const int32_t *field, const int32_t *feat, const float *val,
-                               int32_t *nnz_out, int *longest_out, bool implicit_fields = false) {
+                               const int32_t **field_io, const int32_t *feat, const float *val,
+                               int32_t *nnz_out, int *longest_out, bool implicit_fields = false, bool hold_eval = false) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
+  if (e->m.type != FFM_MODEL_FFM) *field_io = nullptr;
+  const int32_t *const field = *field_io;
   if (n_rows < 0) return fail(FFM_E_INVALID, "negative n_rows");
   if (!row_ptr) return fail(FFM_E_INVALID, "null row_ptr");
   if (n_rows > e->max_rows) return fail(FFM_E_CAPACITY, "block exceeds max_batch_rows");
@@ -562,7 +582,7 @@ static int validate_host_block(ffm_engine *e, int32_t n_rows, const int32_t *row
   for (int r = 0; r < n_rows; r++)
     if (row_ptr[r + 1] < row_ptr[r]) return fail(FFM_E_INVALID, "row_ptr must be non-decreasing");
   const int32_t nnz = row_ptr[n_rows];
-  int rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val, implicit_fields, true);
+  int rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val, implicit_fields, true, hold_eval);
   if (rc) return rc;
   if (implicit_fields && !field && e->m.type == FFM_MODEL_FFM)
     for (int r = 0; r < n_rows; r++)
@@ -600,20 +620,20 @@ __global__ __launch_bounds__(256) void fill_ones_kernel(float *val, unsigned n) 
   if (tid < (n & 3u)) val[(n4 << 2) + tid] = 1.0f;
 }
 
+// The synchronous calls' copy of a host block into the engine's own device arrays, on the main stream.
+// Returns the block as the _device cores take it (*dev) and its longest row (*row_cap_out).
 static int stage_block(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
-                       const int32_t *feat, const float *val, const int32_t *label, int32_t *nnz_out,
+                       const int32_t *feat, const float *val, const int32_t *label, Rows *dev, int *row_cap_out,
                        const float *weight = nullptr) {
   int32_t nnz = 0;
   int longest = 1;
-  if (e && e->m.type != FFM_MODEL_FFM) field = nullptr;  // (LR / FM: no fields to upload)
-  int rc = validate_host_block(e, n_rows, row_ptr, field, feat, val, &nnz, &longest);
+  int rc = validate_host_block(e, n_rows, row_ptr, &field, feat, val, &nnz, &longest);
   if (rc) return rc;
   if (weight) {
     if ((rc = validate_host_weights(n_rows, weight))) return rc;
     // (allocated by the first weighted block: an engine that never sees weights holds nothing for them)
     if (!e->d_weight && (rc = e->alloc(&e->d_weight, static_cast<size_t>(e->max_rows)))) return rc;
   }
-  e->staged_row_cap = longest;
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   HIP_TRY(hipMemcpyAsync(e->d_row_ptr, row_ptr, sizeof(int32_t) * (n_rows + 1), hipMemcpyHostToDevice, e->stream));
   if (nnz > 0) {
@@ -630,7 +650,8 @@ static int stage_block(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, co
     HIP_TRY(hipMemcpyAsync(e->d_weight, weight, sizeof(float) * n_rows, hipMemcpyHostToDevice, e->stream));
   // FFM_FLAG_HASH_IDS: the ids in place, behind their copy and ahead of every kernel that reads them
   if (e->hash_ids) launch_hash_ids(e, e->stream, nnz, field ? e->d_field : nullptr, e->d_feat, e->d_feat);
-  *nnz_out = nnz;
+  *dev = Rows{n_rows, nnz, e->d_row_ptr, field ? e->d_field : nullptr, e->d_feat, e->d_val, label ? e->d_label : nullptr};
+  *row_cap_out = longest;
   return FFM_OK;
 }
 
@@ -639,13 +660,13 @@ int ffm_engine_train_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
                                     const int32_t *label, const float *weight, float *logit_out,
                                     double *loss_sum_out) {
   SERVE_REFUSE(e, "training");  // (before anything of the block is copied)
-  int32_t nnz = 0;
-  int rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &nnz, weight);
+  Rows dev{};
+  int row_cap = 0;
+  int rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &dev, &row_cap, weight);
   if (rc) return rc;
   if (n_rows > 0 && !label) return fail(FFM_E_INVALID, "training needs labels");
-  rc = ffm_engine_train_batch_device_weighted(e, n_rows, nnz, e->d_row_ptr, (field && e->m.type == FFM_MODEL_FFM) ? e->d_field : nullptr,
-                                              e->d_feat, e->d_val, e->d_label, weight ? e->d_weight : nullptr, e->d_out, e->d_loss_sum);
-  if (rc) return rc;
+  dev.label = e->d_label;  // (also for a block of no rows that came without labels)
+  if ((rc = train_batch_core(e, dev, weight ? e->d_weight : nullptr, e->d_out, e->d_loss_sum, row_cap))) return rc;
   if (logit_out && n_rows > 0)
     HIP_TRY(hipMemcpyAsync(logit_out, e->d_out, sizeof(float) * n_rows, hipMemcpyDeviceToHost, e->stream));
   if (loss_sum_out)
@@ -662,14 +683,12 @@ int ffm_engine_predict_batch(ffm_engine *e, int32_t n_rows, const int32_t *row_p
                              const int32_t *field, const int32_t *feat, const float *val,
                              const int32_t *label, int32_t output_prob, float *out,
                              double *loss_sum_out) {
-  int32_t nnz = 0;
-  int rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &nnz);
+  Rows dev{};
+  int row_cap = 0;
+  int rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &dev, &row_cap);
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(e->sc[e->cur].counters, 0, kNumCounters * sizeof(int), e->stream));
-  rc = ffm_engine_predict_batch_device(e, n_rows, nnz, e->d_row_ptr, (field && e->m.type == FFM_MODEL_FFM) ? e->d_field : nullptr,
-                                       e->d_feat, e->d_val, label ? e->d_label : nullptr,
-                                       output_prob, e->d_out, e->d_loss_sum);
-  if (rc) return rc;
+  if ((rc = predict_core(e, dev, output_prob, e->d_out, e->d_loss_sum, row_cap))) return rc;
   if (out && n_rows > 0)
     HIP_TRY(hipMemcpyAsync(out, e->d_out, sizeof(float) * n_rows, hipMemcpyDeviceToHost, e->stream));
   if (loss_sum_out) {

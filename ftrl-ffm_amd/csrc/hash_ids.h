@@ -53,4 +53,17 @@ FTRL_HASH_HD int32_t hash_entry(const Map &m, int32_t field, int32_t feat) {
   return hash_into(field, feat, lo, static_cast<uint32_t>(m.start[field + 1] - lo));
 }
 
+#if defined(__HIPCC__)
+// Four entries at a time, for the kernels that carry them as 16-byte vectors (hash_ids_kernel, the upload kernel).
+// The fields of entries 4i .. 4i + 3 of a block handed over without a field array: one entry per field in
+// field order, so entry p is field p mod n_fields (what the upload kernel writes as the slot's field array).
+__device__ __forceinline__ int4 hash_implicit_fields4(unsigned i, unsigned F) {
+  const unsigned f0 = (4u * i) % F, f1 = f0 + 1u < F ? f0 + 1u : 0u, f2 = f1 + 1u < F ? f1 + 1u : 0u;
+  return make_int4(static_cast<int>(f0), static_cast<int>(f1), static_cast<int>(f2), static_cast<int>(f2 + 1u < F ? f2 + 1u : 0u));
+}
+__device__ __forceinline__ int4 hash_entries4(const Map &hm, const int4 fl, const int4 ft) {
+  return make_int4(hash_entry(hm, fl.x, ft.x), hash_entry(hm, fl.y, ft.y), hash_entry(hm, fl.z, ft.z), hash_entry(hm, fl.w, ft.w));
+}
+#endif
+
 }  // namespace ftrl_hash
