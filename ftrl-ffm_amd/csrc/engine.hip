@@ -51,6 +51,7 @@
 #include "kernels_keyed.h"
 #include "kernels_serve.h"
 #include "kernels_stage.h"
+#include "kernels_sketch.h"
 #include "metrics_host.h"
 
 using namespace ftrl_dev;
@@ -814,6 +815,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_profile.h"
 #include "engine_metrics.h"
 #include "engine_keyed.h"
+#include "engine_sketch.h"
 }  // extern "C"
 
 #include "engine_group.h"

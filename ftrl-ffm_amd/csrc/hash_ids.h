@@ -28,10 +28,16 @@ FTRL_HASH_HD uint32_t mix32(uint32_t x) {  // the murmur3 finaliser
   return x;
 }
 
-// A valid entry's model id: `field` salts the hash (0 for LR / FM), [lo, lo + width) is where it lands.
-FTRL_HASH_HD int32_t hash_into(int32_t field, int32_t feat, int32_t lo, uint32_t width) {
+// The 32 hashed bits of a valid entry: `field` salts the hash (0 for LR / FM).  mix32 is a bijection, so two
+// ids of one field never share them (what the field sketches count, kernels_sketch.h).
+FTRL_HASH_HD uint32_t hash_bits(int32_t field, int32_t feat) {
   const uint32_t salt = (static_cast<uint32_t>(field) + 1u) * 0x9e3779b9u;  // ((uint32)(field + 1), without signed overflow)
-  const uint32_t x = mix32(static_cast<uint32_t>(feat) ^ salt);
+  return mix32(static_cast<uint32_t>(feat) ^ salt);
+}
+
+// A valid entry's model id: [lo, lo + width) is where its hashed bits land.
+FTRL_HASH_HD int32_t hash_into(int32_t field, int32_t feat, int32_t lo, uint32_t width) {
+  const uint32_t x = hash_bits(field, feat);
   return lo + static_cast<int32_t>((static_cast<uint64_t>(x) * static_cast<uint64_t>(width)) >> 32);
 }
 

@@ -206,7 +206,16 @@ ABI = [
     ("ffm_engine_score_candidates_device", ctypes.c_int,
      [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp,
       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp]),
+    # the fields' cardinalities counted on the device, id ranges sized by them (include/ffm_engine.h "Field sketches")
+    ("ffm_engine_sketch_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
+    ("ffm_engine_sketch_add", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32]),
+    ("ffm_engine_sketch_add_device", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp]),
+    ("ffm_engine_sketch_read", ctypes.c_int, [_vp, _vp, _i64p, _i64p]),
+    ("ffm_engine_sketch_destroy", None, [_vp]),
+    ("ffm_engine_sketch_estimate", ctypes.c_int, [_vp, ctypes.c_int32, _f64p]),
+    ("ffm_engine_field_ranges", ctypes.c_int, [_i64p, ctypes.c_int32, ctypes.c_int32, _i32p]),
 ]
+SKETCH_REGS = 16384  # FFM_SKETCH_REGS
 
 _lib = None
 
@@ -347,6 +356,34 @@ def hash_ids(field, feat, n_feats, field_start=None, model="ffm", n_fields=None)
         raise ValueError("field and feat must be equally long")
     out = np.empty_like(feat)
     rc = lib.ffm_engine_hash_ids_host(mt, int(n_feats), int(n_fields), _i(fs), feat.size, _i(fld), _i(feat), _i(out))
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
+    return out
+
+
+def sketch_estimate(reg):
+    """Distinct ids per field from a sketch's registers (uint8 [n_fields, SKETCH_REGS]), float64 [n_fields]
+    (ffm_engine_sketch_estimate: host arithmetic, no device)."""
+    lib = load_library()
+    reg = np.ascontiguousarray(reg, np.uint8)
+    if reg.ndim != 2 or reg.shape[1] != SKETCH_REGS:
+        raise ValueError("reg: uint8 [n_fields, %d]" % SKETCH_REGS)
+    out = np.zeros(reg.shape[0], np.float64)
+    rc = lib.ffm_engine_sketch_estimate(reg.ctypes.data, reg.shape[0], out.ctypes.data_as(_f64p))
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
+    return out
+
+
+def field_ranges(count, n_feats):
+    """field_start (int32 [n_fields + 1]) for per-field counts of distinct ids: every field's share of n_feats
+    in proportion to its count above a floor (ffm_engine_field_ranges: exact integers, no device)."""
+    lib = load_library()
+    count = np.ascontiguousarray(count, np.int64)
+    if count.ndim != 1:
+        raise ValueError("count: one integer per field")
+    out = np.zeros(count.size + 1, np.int32)
+    rc = lib.ffm_engine_field_ranges(count.ctypes.data_as(_i64p), count.size, int(n_feats), _i(out))
     if rc != 0:
         raise EngineError(rc, lib.ffm_engine_last_error().decode())
     return out
@@ -923,6 +960,67 @@ class Engine:
         buf = ctypes.create_string_buffer(8192)
         self._check(self.lib.ffm_engine_profile_dump(self.h, buf, 8192))
         return buf.value.decode()
+
+
+class FieldSketch:
+    """One HyperLogLog sketch per field, filled on the device (include/ffm_engine.h "Field sketches"): how many
+    distinct ids each field of a data set holds, before a model exists.  Needs no engine."""
+
+    def __init__(self, n_fields, device=0):
+        self.lib = load_library()
+        self.h = _vp()
+        self.n_fields = int(n_fields)
+        self._check(self.lib.ffm_engine_sketch_create(self.n_fields, int(device), ctypes.byref(self.h)))
+
+    def _check(self, rc):
+        if rc != 0:
+            raise EngineError(rc, self.lib.ffm_engine_last_error().decode())
+
+    @staticmethod
+    def _ids(a, what):
+        if a is None:
+            return None
+        if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous):
+            a = np.ascontiguousarray(a, np.int32)
+        if a.ndim != 1:
+            raise ValueError(what + ": a one-dimensional int32 array")
+        return a
+
+    def add(self, field, feat, zero_copy=False):
+        """Counts the entries (field[p], feat[p]); field None: entry p is field p mod n_fields.  zero_copy: the
+        arrays are page-locked (ffm_engine_pin_host) int32 arrays, read in place.  Back once they may be reused."""
+        feat = self._ids(feat, "feat")
+        field = self._ids(field, "field")
+        if field is not None and field.size != feat.size:
+            raise ValueError("field and feat must be equally long")
+        self._check(self.lib.ffm_engine_sketch_add(self.h, feat.size, None if field is None else field.ctypes.data,
+                                                   feat.ctypes.data, int(bool(zero_copy))))
+
+    def add_device(self, nnz, field, feat):
+        """The same for int32 arrays in device memory (addresses; field may be None); asynchronous."""
+        self._check(self.lib.ffm_engine_sketch_add_device(self.h, int(nnz), field, feat))
+
+    def read(self):
+        """(reg uint8 [n_fields, SKETCH_REGS], n_valid, n_bad) after everything added so far."""
+        reg = np.zeros((self.n_fields, SKETCH_REGS), np.uint8)
+        nv, nb = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self.lib.ffm_engine_sketch_read(self.h, reg.ctypes.data, ctypes.byref(nv), ctypes.byref(nb)))
+        return reg, int(nv.value), int(nb.value)
+
+    def estimate(self):
+        """Distinct ids per field, float64 [n_fields]."""
+        return sketch_estimate(self.read()[0])
+
+    def close(self):
+        if self.h:
+            self.lib.ffm_engine_sketch_destroy(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Group:

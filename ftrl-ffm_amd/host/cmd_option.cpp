@@ -35,8 +35,18 @@ const std::string_view cmd_help =
     "--device <id>: HIP device ordinal\tdefault:0\n"
     "--n_gpus <n>: shard the field pairs over n devices (one engine each, RCCL all-reduce of the\n"
     "              partial logits per block)\tdefault:1\n"
-    "--field_ranges <uniform|none>: uniform = field f owns ids [f*n_feats/n_fields, (f+1)*n_feats/n_fields),\n"
-    "              shards then store only their own slots\tdefault:none\n"
+    "--field_ranges <uniform|none|counted|@FILE>: uniform = field f owns ids [f*n_feats/n_fields, (f+1)*n_feats/n_fields),\n"
+    "              shards then store only their own slots.  counted (FFM, one GPU) = before a model exists --train_data is\n"
+    "              streamed once and the distinct ids of every field are counted on the device (a HyperLogLog sketch per\n"
+    "              field, +-0.8 %); every field then owns a share of n_feats in proportion to its count, above a floor of\n"
+    "              min(4096, n_feats/(2*n_fields)) ids.  Prints one `field f: ~D distinct ids, ids [lo, hi)` per field and\n"
+    "              `field ranges: counted from R rows (E entries, B erased) in T s; ~S distinct ids for N features (load X)`:\n"
+    "              a load above 1 means collisions, raise --n_feats.  @FILE = the ranges of such a run, read from FILE:\n"
+    "              n_fields + 1 ascending integers, one per line, from 0 to n_feats.  Both are honoured wherever uniform is\n"
+    "              on one GPU: they shape the id mapping under --hash_feats and are a hint to the grouping otherwise.  The\n"
+    "              ranges are not recorded in checkpoints: counted is refused with --resume_from, a resumed or scoring run\n"
+    "              passes @FILE.  --n_gpus > 1 takes uniform only\tdefault:none\n"
+    "--field_ranges_out <path>: write the ranges in use (uniform, counted or @FILE) to path, one integer per line\n"
     "--checkpoint_path <path>: after training, write a sparse resumable checkpoint: only the features that\n"
     "              differ from a fresh model of this seed (found by a device scan), with w, n, z, the bias and the\n"
     "              trainer's progress (one GPU only)\n"
@@ -161,6 +171,7 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--compact_rows") compact_rows = assign_bool(v);
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
     else if (k == "--field_ranges") field_ranges = v;
+    else if (k == "--field_ranges_out") field_ranges_out = v;
     else if (k == "--metrics") {
       if (v != "auc" && v != "none") throw std::invalid_argument("--metrics takes auc or none");
       metrics = v;
@@ -209,6 +220,26 @@ void config_options::parse_option(int argc, char *argv[]) {
     if (refresh_weights)
       throw std::invalid_argument(what + "holds no accumulators to refresh from: write the checkpoint with --refresh_weights true instead");
     if (model_type != "FFM") throw std::invalid_argument(what + "is for FFM models only (got --model_type " + model_type + ")");
+  }
+  if (field_ranges == "counted") {
+    // the counting pass reads the training file on one GPU before an FFM model exists (refused here, before a device is opened)
+    const std::string what = "--field_ranges counted ";
+    if (model_type != "FFM") throw std::invalid_argument(what + "counts the ids of fields, which only FFM rows have (got --model_type " + model_type + ")");
+    if (!resume_from.empty())
+      throw std::invalid_argument(what + "is not allowed with --resume_from: a saved model's ranges are the ones it was trained with; "
+                                         "write them with --field_ranges_out and pass --field_ranges @FILE");
+    if (train_path.empty()) throw std::invalid_argument(what + "counts the ids of the training file: it needs --train_data");
+    if (n_gpus > 1) throw std::invalid_argument(what + "sizes the ranges of one whole model on one GPU: --n_gpus > 1 is not allowed with it");
+  }
+  if (!field_ranges.empty() && field_ranges[0] == '@') {
+    if (field_ranges.size() == 1) throw std::invalid_argument("--field_ranges @FILE needs a file name after the @");
+    if (model_type != "FFM")
+      throw std::invalid_argument("--field_ranges " + field_ranges + " names the ranges of fields, which only FFM has (got --model_type " + model_type + ")");
+  }
+  if (!field_ranges_out.empty()) {
+    const bool ranged = field_ranges == "uniform" || field_ranges == "counted" || field_ranges[0] == '@';
+    if (!ranged || model_type != "FFM")
+      throw std::invalid_argument("--field_ranges_out writes the fields' id ranges: it needs an FFM model and --field_ranges uniform, counted or @FILE");
   }
   if (auc_key_field >= 0) {
     // the grouped AUC rides on the AUC lines of one whole FFM model (refused here, before a device is opened)

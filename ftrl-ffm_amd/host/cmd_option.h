@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <string>
 #include <string_view>
+#include <vector>
 
 struct config_options {
   std::string model_path, train_path, eval_path;
@@ -27,6 +28,12 @@ struct config_options {
   std::string field_ranges = "none";  // --field_ranges uniform: field f owns ids [f*n_feats/F, (f+1)*n_feats/F)
                                       //   (the layout of python/generate_data.py:272-306): shards then store
                                       //   only their slots; none: every shard keeps whole records
+  // --field_ranges counted: the ranges are sized by the fields' cardinalities, counted on the device in one pass
+  // over --train_data before a model exists; @PATH: read from a file of n_fields + 1 integers, one per line
+  // (field_ranges.h).  field_start: what either resolved to (filled by main.cpp before a model exists; empty:
+  // uniform or none, as ever).  --field_ranges_out PATH writes the ranges in that format.
+  std::vector<int32_t> field_start;
+  std::string field_ranges_out;
   std::string checkpoint_path;  // --checkpoint_path: write a sparse resumable checkpoint after training
   std::string resume_from;      // --resume_from: load one before training; --n_epochs then counts MORE epochs
   std::string metrics = "none";  // --metrics auc: one AUC line after every loss line (accumulated on the device)

@@ -82,6 +82,8 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
     if (mt != FFM_MODEL_FFM) throw std::invalid_argument("--n_gpus > 1 shards the FFM field pairs: model_type must be FFM");
     if (n_gpus_ > 1 && opt.field_ranges != "uniform")
       throw std::invalid_argument("--n_gpus > 1 needs --field_ranges uniform (per-field id ranges)");
+    if (!opt.field_start.empty())
+      throw std::invalid_argument("--field_ranges " + opt.field_ranges + " is for one engine: the group path takes uniform ranges only");
     std::vector<int32_t> fs(static_cast<size_t>(opt.n_fields) + 1);
     if (n_gpus_ <= 1) std::printf("FFM_GROUP_RCCL=1: one engine behind the group path (synchronous evaluation, RCCL all-reduce of one rank)\n");
     if (opt.field_ranges == "uniform") {
@@ -90,6 +92,7 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
       per_field_ = opt.n_feats / opt.n_fields;
       for (int f = 0; f <= opt.n_fields; f++) fs[f] = f == opt.n_fields ? opt.n_feats : f * per_field_;
       if (n_gpus_ > 1 || opt.hash_feats) cfg.field_start = fs.data();  // (hashed: the ranges shape the mapping)
+      field_start_ = fs;
     }
     std::vector<int32_t> devs(static_cast<size_t>(n_gpus_));
     const bool same = std::getenv("FTRL_SAME_DEVICE") != nullptr;  // one-GPU dry run of the orchestration
@@ -106,13 +109,21 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
   } else {
     // one engine: --field_ranges uniform is a hint (the grouping sorts every field's id range by itself,
     // and a block whose rows are one entry per field in field order takes the short forms of the fold)
+    // (--field_ranges counted | @FILE: the ranges main.cpp resolved, honoured where uniform ones are)
     std::vector<int32_t> fs;
-    if (mt == FFM_MODEL_FFM && opt.field_ranges == "uniform" && opt.n_feats >= opt.n_fields) {
+    if (mt == FFM_MODEL_FFM && !opt.field_start.empty()) {
+      if (opt.field_start.size() != static_cast<size_t>(opt.n_fields) + 1)
+        throw std::invalid_argument("field ranges: " + std::to_string(opt.field_start.size()) + " values for " +
+                                    std::to_string(opt.n_fields) + " fields (n_fields + 1 expected)");
+      fs = opt.field_start;
+      cfg.field_start = fs.data();
+    } else if (mt == FFM_MODEL_FFM && opt.field_ranges == "uniform" && opt.n_feats >= opt.n_fields) {
       fs.resize(static_cast<size_t>(opt.n_fields) + 1);
       const int per = opt.n_feats / opt.n_fields;
       for (int f = 0; f <= opt.n_fields; f++) fs[f] = f == opt.n_fields ? opt.n_feats : f * per;
       cfg.field_start = fs.data();  // (copied by ffm_engine_create)
     }
+    field_start_ = fs;
     rc = ffm_engine_create(&cfg, &eng_);
     if (rc == FFM_E_INVALID) throw std::invalid_argument(ffm_engine_last_error());
     check(rc, "ffm_engine_create");

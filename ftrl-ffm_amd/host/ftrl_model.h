@@ -17,6 +17,7 @@
 // training, push_weights() writes edited mirrors back (the reference's tests poke them directly).
 // Model files are streamed record chunk by record chunk (persist.h): host memory stays bounded.
 #pragma once
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <string_view>
@@ -203,8 +204,14 @@ class FtrlModel {
   double eval_loss_pending_ = 0.0;  // group: evaluation blocks are predicted synchronously
   std::vector<std::pair<float *, size_t>> pinned_scores_;  // pin_scores() ranges (floats)
   ffm_engine *shard(int r) const;
-  int field_of(int feat) const { return per_field_ > 0 ? std::min(feat / per_field_, n_fields - 1) : 0; }
+  // the field that owns a model id: a search in the ranges (uniform ranges: one divide; no ranges: 0)
+  int field_of(int feat) const {
+    if (per_field_ > 0) return std::min(feat / per_field_, n_fields - 1);
+    if (field_start_.size() < 2) return 0;
+    return static_cast<int>(std::upper_bound(field_start_.begin() + 1, field_start_.end() - 1, feat) - (field_start_.begin() + 1));
+  }
   int per_field_ = 0;  // ids per field under --field_ranges uniform
+  std::vector<int32_t> field_start_;  // [n_fields + 1] the fields' id ranges (--field_ranges uniform | counted | @FILE), or empty
   // what the engine was created from, as far as it decides a fresh model's contents (checkpoints)
   uint64_t seed_ = 0;
   float init_mean_ = 0.0f, init_stddev_ = 0.0f;

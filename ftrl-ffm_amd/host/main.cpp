@@ -7,6 +7,7 @@
 #include <string>
 
 #include "cmd_option.h"
+#include "field_ranges.h"
 #include "sample_weights.h"
 #include "trainer.h"
 
@@ -56,6 +57,9 @@ int main(int argc, char *argv[]) {
     };
     // --pos_weight / --neg_weight / --weight_data: read and checked in full before a model exists
     ftrl::SampleWeights weights = ftrl::load_sample_weights(opt);
+    // --field_ranges counted | @FILE, --field_ranges_out: the ranges every model of this run is created with
+    // (counted: one pass over the training file, on the device, before a model exists)
+    ftrl::resolve_field_ranges(opt);
     if (opt.online) {
       ftrl::FtrlOnline task(opt);
       if (weights.on) task.set_sample_weights(std::move(weights));

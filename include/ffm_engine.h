@@ -655,6 +655,61 @@ int ffm_engine_hash_ids_device(ffm_engine *e, int32_t nnz, const int32_t *field,
 int ffm_engine_hash_ids_host(int32_t model_type, int32_t n_feats, int32_t n_fields, const int32_t *field_start,
                              int32_t nnz, const int32_t *field, const int32_t *feat_in, int32_t *feat_out);
 
+/* ---- Field sketches: the fields' cardinalities counted on the device, and id ranges sized by them ----
+ * Under FFM_FLAG_HASH_IDS with cfg->field_start every field hashes into its own id range; how wide each range
+ * should be depends on how many distinct ids the field holds, which nothing knows before the data is read.  A
+ * SKETCH counts that: one HyperLogLog sketch per field, filled by one kernel from rows in host memory (or in
+ * HBM) before a model exists.  It touches no engine and needs none.
+ *   sketch     n_fields x M registers, M = FFM_SKETCH_REGS = 2^14, all zero at create.
+ *   counting   an entry (field, feat) COUNTS iff feat >= 0 and 0 <= field < n_fields -- exactly the entries the
+ *              mapping of "Hashed ids" keeps for an FFM model.  Every other entry adds one to n_bad and nothing
+ *              else.  n_valid counts the counting entries.  For a counting entry
+ *                x    = the 32 hashed bits of "Hashed ids" (after the last x ^= x >> 16, before the multiply)
+ *                idx  = x >> 18
+ *                w    = x << 14                                 (32 bits)
+ *                rank = (w == 0) ? 19 : clz32(w) + 1
+ *                reg[field][idx] = max(reg[field][idx], rank)
+ *   fields     field == NULL: entry p of the call belongs to field p mod n_fields (rows of one entry per field
+ *              in field order, as for ffm_engine_hash_ids_device).
+ *   exactness  the mix is a bijection on 32 bits: distinct ids of a field are distinct x, so the estimator needs
+ *              no large-range correction.  Registers are maxima and the counters integer sums: the result does
+ *              not depend on the order or the batching of the entries, and two sketches fed the halves of a
+ *              file hold, register by register, the maximum of what one sketch fed the whole file holds.
+ *   add        zero_copy != 0: the arrays are page-locked (ffm_engine_pin_host) and the kernel reads them in
+ *              place (16-byte aligned arrays move as 16-byte vectors).  Otherwise they are copied into one of two
+ *              page-locked staging buffers owned by the sketch, grown on demand.  Either way the call returns
+ *              once the caller may reuse the arrays; no host-to-device copy is queued, a kernel pulls the
+ *              entries.  _add_device: the arrays are in device memory; asynchronous on the
+ *              sketch's stream.  nnz == 0 is a no-op.  FFM_E_INVALID: feat == NULL with nnz > 0, nnz < 0,
+ *              n_fields <= 0; FFM_E_DEVICE without a device.
+ *   read       waits for the sketch's stream; reg may be NULL; the sketch keeps counting afterwards.
+ *   estimate   pure host arithmetic, no device; in double, the registers of a field in ascending index:
+ *                S = sum of 2^(-reg)          (exact: 16384 terms of at most 19 fractional bits)
+ *                E = alpha * M^2 / S          alpha = 0.7213 / (1 + 1.079 / M)
+ *                if E <= 2.5 * M and V > 0 registers are zero: E = M * ln(M / V)
+ *              an empty field gives 0.0.  Standard error 1.04 / sqrt(M) = 0.81 %.
+ *   ranges     ffm_engine_field_ranges: pure host arithmetic in exact integers.  count[f] is clamped to
+ *              [1, 2^31]; a negative count, or n_feats < 2 * n_fields, is FFM_E_INVALID.
+ *                base     = min(4096, n_feats / (2 * n_fields))
+ *                R        = n_feats - n_fields * base,  C = sum of count
+ *                width[f] = base + (R * count[f]) / C        (unsigned 64-bit; the product is below 2^63)
+ *              the L ids still left over go one each to the L fields with the largest (R * count[f]) mod C,
+ *              ties to the lower field.  field_start is the prefix sum: field_start[0] = 0,
+ *              field_start[n_fields] = n_feats.  The floor `base` keeps a two-valued field from sharing three
+ *              slots and costs at most 4096 * n_fields ids.
+ * OUT OF SCOPE  groups, shards and several GPUs with ranges other than uniform ones; LR / FM, which have no
+ *   fields; recording ranges in checkpoints; sketching evaluation data; choosing n_feats for the caller. */
+typedef struct ffm_sketch ffm_sketch;
+#define FFM_SKETCH_REGS 16384
+int ffm_engine_sketch_create(int32_t n_fields, int32_t device_id, ffm_sketch **out);
+int ffm_engine_sketch_add(ffm_sketch *s, int32_t nnz, const int32_t *field, const int32_t *feat, int32_t zero_copy);
+int ffm_engine_sketch_add_device(ffm_sketch *s, int32_t nnz, const int32_t *field, const int32_t *feat);
+int ffm_engine_sketch_read(ffm_sketch *s, uint8_t *reg /* [n_fields][REGS], may be NULL */, int64_t *n_valid, int64_t *n_bad);
+void ffm_engine_sketch_destroy(ffm_sketch *s);
+/* pure host arithmetic, no device: */
+int ffm_engine_sketch_estimate(const uint8_t *reg, int32_t n_fields, double *distinct /* [n_fields] */);
+int ffm_engine_field_ranges(const int64_t *count, int32_t n_fields, int32_t n_feats, int32_t *field_start /* [n_fields + 1] */);
+
 /* ---- Rows without values: val == NULL is 1.0f -------------------------------------------------------
  * Click logs are categorical: after hashing every entry of a libffm file is field:id:1, and an array of
  * 1.0f is a third of a block's bytes over PCIe (half of what is left once the field array stays at home).
