@@ -50,6 +50,7 @@
 #include "kernels_metric.h"
 #include "kernels_keyed.h"
 #include "kernels_serve.h"
+#include "kernels_ablate.h"
 #include "kernels_stage.h"
 #include "kernels_sketch.h"
 #include "metrics_host.h"
@@ -415,6 +416,16 @@ struct ffm_engine {
   float *d_ctx_val = nullptr;
   size_t cx_ent_cap = 0, cx_head_cap = 0, cx_terms_cap = 0, cx_cand_cap = 0;
   size_t ctx_ptr_cap = 0, req_ptr_cap = 0, ctx_field_cap = 0, ctx_feat_cap = 0, ctx_val_cap = 0;
+  // field ablation (include/ffm_engine.h "Field ablation", engine_ablate.h), all made by ffm_engine_ablation_enable:
+  // out [(n_fields + 1)][max_rows] scores and loss the same shape (the kernel's variant-major outputs), sums
+  // [n_fields + 1], part [n_fields + 1][kLossParts + 1] the loss sums' partial sums and tickets, hist
+  // [n_fields + 1][2 * kMetricBins + 1] with with_auc
+  struct {
+    bool on = false, auc = false;
+    float *out = nullptr;
+    double *loss = nullptr, *sums = nullptr, *part = nullptr;
+    unsigned long long *hist = nullptr;
+  } abl;
   std::vector<void *> allocs;
   // split-phase bookkeeping
   Rows pending{};
@@ -816,6 +827,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_metrics.h"
 #include "engine_keyed.h"
 #include "engine_sketch.h"
+#include "engine_ablate.h"
 }  // extern "C"
 
 #include "engine_group.h"

@@ -119,5 +119,16 @@ inline ServeCandidateFn serve_candidate_fn(int fmt, int n_factors) {
     default: return nullptr;
   }
 }
+// field ablation (kernels_ablate.h): one template for the three formats
+using AblateWaveFn = void (*)(ModelDev, Rows, int *, int, int, float *, double *, int, int);
+inline AblateWaveFn ablate_wave_fn(int fmt, int n_factors) {
+  switch (n_factors) {
+#define X(K, LPP, VPL, U) \
+  case K: return fmt == SERVE_NONE ? ffm_ablate_wave_kernel<SERVE_NONE, LPP, VPL, U> : FFM_BY_FMT(ffm_ablate_wave_kernel, LPP, VPL, U);
+    FFM_LANE_SHAPES(X)
+#undef X
+    default: return nullptr;
+  }
+}
 #undef FFM_BY_FMT
 #undef FFM_LANE_SHAPES

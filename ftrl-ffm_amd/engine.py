@@ -214,6 +214,12 @@ ABI = [
     ("ffm_engine_sketch_destroy", None, [_vp]),
     ("ffm_engine_sketch_estimate", ctypes.c_int, [_vp, ctypes.c_int32, _f64p]),
     ("ffm_engine_field_ranges", ctypes.c_int, [_i64p, ctypes.c_int32, ctypes.c_int32, _i32p]),
+    # the loss and AUC of the model without each field, in one pass (include/ffm_engine.h "Field ablation")
+    ("ffm_engine_ablation_enable", ctypes.c_int, [_vp, ctypes.c_int32]),
+    ("ffm_engine_predict_ablated", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [ctypes.c_int32, _f32p, _f64p]),
+    ("ffm_engine_predict_ablated_device", ctypes.c_int,
+     [_vp, ctypes.c_int32, ctypes.c_int32] + _DCSR + [ctypes.c_int32, _vp, _vp]),
+    ("ffm_engine_ablation_read", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(Metrics)]),
 ]
 SKETCH_REGS = 16384  # FFM_SKETCH_REGS
 
@@ -387,6 +393,18 @@ def field_ranges(count, n_feats):
     if rc != 0:
         raise EngineError(rc, lib.ffm_engine_last_error().decode())
     return out
+
+
+def drop_field(block, f):
+    """The block without every entry whose field is f (include/ffm_engine.h "Field ablation"): rows, labels and
+    the order of the remaining entries stay as they are; val may be None."""
+    from .synth import Block
+    field = np.asarray(block.field)
+    keep = field != f
+    kept = np.concatenate(([0], np.cumsum(keep, dtype=np.int64)))
+    row_ptr = kept[np.asarray(block.row_ptr, np.int64)].astype(np.int32)
+    return Block(row_ptr, np.ascontiguousarray(field[keep], np.int32), np.ascontiguousarray(np.asarray(block.feat)[keep], np.int32),
+                 None if block.val is None else np.ascontiguousarray(np.asarray(block.val)[keep], np.float32), block.label)
 
 
 def spell_out_candidates(ctx, cand_req_ptr, cand):
@@ -912,6 +930,37 @@ class Engine:
         self._check(self.lib.ffm_engine_metrics_histogram(self.h, _channel(channel), pos.ctypes.data_as(_u64p),
                                                           neg.ctypes.data_as(_u64p)))
         return pos, neg
+
+    # ---- field ablation (include/ffm_engine.h "Field ablation") ----
+    def ablation_enable(self, auc=False):
+        """Allocates what predict_ablated needs: (n_fields + 1) x max_batch_rows scores and losses and, with auc,
+        n_fields + 1 score histograms of 16 MiB each.  FFM, one whole model on one device, n_factors in {4, 8, 16,
+        32, 64}, at most 64 fields; training and serving engines."""
+        self._check(self.lib.ffm_engine_ablation_enable(self.h, int(bool(auc))))
+
+    def predict_ablated(self, c, output_prob=False, with_loss=True):
+        """(out[n_fields + 1, n_rows], loss_sums[n_fields + 1]): row v is predict_batch(drop_field(c, v)) for
+        v < n_fields and predict_batch(c) for v = n_fields, bit for bit, from one pass over c."""
+        V = self.n_fields + 1
+        out = np.zeros((V, c.n_rows), np.float32)  # (variant-major with stride n_rows: what the call writes)
+        loss = np.zeros(V, np.float64)
+        n, rp, fld, ft, v, lab = self._csr(c)
+        self._check(self.lib.ffm_engine_predict_ablated(self.h, n, rp, fld, ft, v, lab if with_loss else None,
+                                                        int(output_prob), _f(out), loss.ctypes.data_as(_f64p)))
+        return out[:, :c.n_rows], loss
+
+    def predict_ablated_device(self, n_rows, nnz, row_ptr, field, feat, val, label, output_prob, out, loss_sum_out=None):
+        """predict_ablated on arrays already in HBM (device addresses; out[(n_fields + 1) * n_rows] variant-major,
+        loss_sum_out[n_fields + 1]).  Asynchronous on the engine's stream; sync() reports a too-long row."""
+        self._check(self.lib.ffm_engine_predict_ablated_device(self.h, int(n_rows), int(nnz), row_ptr, field, feat, val, label,
+                                                               int(output_prob), out, loss_sum_out))
+
+    def ablation_metrics(self, reset=False):
+        """One dict per variant (n_fields + 1), as metrics() returns for a channel: the AUC of the model without
+        field v over every labelled block predict_ablated has seen (ablation_enable(auc=True))."""
+        m = (Metrics * (self.n_fields + 1))()
+        self._check(self.lib.ffm_engine_ablation_read(self.h, int(bool(reset)), m))
+        return [x.as_dict() for x in m]
 
     # ---- the grouped AUC (include/ffm_engine.h "Metrics", keyed capture) ----
     def metrics_key_field(self, field, capacity_rows=1 << 24, eval=True, train=False):

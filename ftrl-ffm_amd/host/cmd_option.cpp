@@ -108,7 +108,15 @@ const std::string_view cmd_help =
     "              without its field array: the device writes both itself, a third of the block's bytes over PCIe each.\n"
     "              Noted per row while the file is parsed; training, evaluation, --predict_data and --serve_weights.  Losses,\n"
     "              AUC lines, scores, model files and checkpoints do not change by a bit.  Prints\n"
-    "              `compact rows: V of B blocks without values, F without fields`\tdefault:false\n";
+    "              `compact rows: V of B blocks without values, F without fields`\tdefault:false\n"
+    "--field_importance <bool>: which fields earn their place?  true = after the last epoch's evaluation (with\n"
+    "              --resume_from ck --n_epochs 0 --eval_data F, and --serve_weights or not: after the one evaluation of the\n"
+    "              loaded model) --eval_data is streamed once more and every row is predicted n_fields + 1 ways in one pass\n"
+    "              on the device: as it is, and without each field (every entry of the field removed; exact, not an\n"
+    "              approximation).  Prints `field importance: R rows, loss L, auc A`, then per field, in field order,\n"
+    "              `field f: without it loss L (delta D), auc A (delta D)`; the AUC parts only with --metrics auc.  Needs\n"
+    "              --eval_data; FFM only, one GPU, --n_fields <= 64, --n_factors 4, 8, 16, 32 or 64, rows of at most 128\n"
+    "              entries.  Nothing else of the output changes\tdefault:false\n";
 
 static bool assign_bool(std::string arg) {
   std::transform(arg.begin(), arg.end(), arg.begin(), [](unsigned char c) { return std::tolower(c); });
@@ -169,6 +177,7 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--refresh_weights") refresh_weights = assign_bool(v);
     else if (k == "--hash_feats") hash_feats = assign_bool(v);
     else if (k == "--compact_rows") compact_rows = assign_bool(v);
+    else if (k == "--field_importance") field_importance = assign_bool(v);
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
     else if (k == "--field_ranges") field_ranges = v;
     else if (k == "--field_ranges_out") field_ranges_out = v;
@@ -250,6 +259,18 @@ void config_options::parse_option(int argc, char *argv[]) {
     if (auc_key_field >= n_fields)
       throw std::invalid_argument(what + "is not a field of this model: --n_fields is " + std::to_string(n_fields));
     if (auc_key_rows <= 0) throw std::invalid_argument("--auc_key_rows must be positive, got " + std::to_string(auc_key_rows));
+  }
+  if (field_importance) {
+    // one more pass over the eval file through one whole FFM model's wave kernel (refused here, before a device is opened)
+    const std::string what = "--field_importance true ";
+    if (eval_path.empty()) throw std::invalid_argument(what + "ablates the fields on the evaluation file: it needs --eval_data");
+    if (model_type != "FFM") throw std::invalid_argument(what + "drops fields, which only FFM rows have (got --model_type " + model_type + ")");
+    if (n_gpus > 1) throw std::invalid_argument(what + "runs on one whole model on one GPU: --n_gpus > 1 is not allowed with it");
+    if (n_fields > 64)
+      throw std::invalid_argument(what + "keeps one lane of a 64-lane wave per field: --n_fields is " + std::to_string(n_fields) + ", at most 64");
+    if (n_factors != 4 && n_factors != 8 && n_factors != 16 && n_factors != 32 && n_factors != 64)
+      throw std::invalid_argument(what + "runs the one-wave-per-row kernel: --n_factors must be 4, 8, 16, 32 or 64 (got " +
+                                  std::to_string(n_factors) + ")");
   }
   // (--n_epochs 0 with a file to score needs no training file: the format is then the scored file's)
   file_type = detect_file_type(train_path.empty() && epoch == 0 && !predict_path.empty() ? predict_path : train_path);

@@ -55,6 +55,9 @@ struct config_options {
   // value of field F averaged by impressions (include/ffm_engine.h "Metrics", keyed capture); -1 = not asked for
   int auc_key_field = -1;
   long long auc_key_rows = 16777216;
+  // --field_importance true: after the last evaluation, the eval loss (and, with --metrics auc, the AUC) of the model
+  // without each field, from one more pass over --eval_data (include/ffm_engine.h "Field ablation", field_importance.h)
+  bool field_importance = false;
 
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };

@@ -149,6 +149,14 @@ class FtrlModel {
   // not trained yet are trained first (their losses stay in train_flush()'s sum).  The host mirrors
   // (bias, lin_w, vec_w) are pulled again / dropped, as after load_checkpoint.  Returns the six counts.
   ffm_refresh_stats refresh_weights();
+  // Field ablation (include/ffm_engine.h "Field ablation"): the loss -- and, with_auc, the AUC -- of this model
+  // without each field, all n_fields + 1 variants from one pass.  enable_ablation allocates the engine's scratch
+  // (one FFM engine only: throws otherwise); predict_ablated_block runs one block through the synchronous call
+  // and ADDS its per-variant loss sums to loss_sums[n_fields + 1] (variant n_fields: the rows themselves);
+  // read_ablation_metrics returns the n_fields + 1 variants' numbers so far and, with reset, starts them from zero.
+  void enable_ablation(bool with_auc);
+  void predict_ablated_block(const CsrBlock &blk, std::vector<double> &loss_sums);
+  std::vector<ffm_metrics> read_ablation_metrics(bool reset);
 
   // Model files in the reference's formats (ffm.cpp:138-200, lr.cpp:26-39); available for every
   // model type here (the reference has none for FM).  save_state/load_state add the FTRL

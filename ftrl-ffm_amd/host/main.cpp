@@ -7,6 +7,7 @@
 #include <string>
 
 #include "cmd_option.h"
+#include "field_importance.h"
 #include "field_ranges.h"
 #include "sample_weights.h"
 #include "trainer.h"
@@ -37,8 +38,11 @@ int main(int argc, char *argv[]) {
       task.train();
       // --auc_key_field on a run that trains nothing (--resume_from ck --n_epochs 0 --eval_data F): one evaluation pass
       // of the loaded model, numbered by the epochs it has behind it -- there is no epoch to print the line after
-      if (opt.auc_key_field >= 0 && opt.epoch <= 0 && !opt.cmd && !opt.eval_path.empty())
+      // (--field_importance asks for the same one pass: its lines follow an evaluation)
+      if ((opt.auc_key_field >= 0 || opt.field_importance) && opt.epoch <= 0 && !opt.cmd && !opt.eval_path.empty())
         task.evaluate(static_cast<int>(task.progress().epochs_done));
+      // --field_importance: after the last evaluation, the same model without each field (field_importance.h)
+      if (opt.field_importance && !opt.cmd) ftrl::FieldImportance(opt, &*task.model_ptr).run();
       // --refresh_weights: every epoch ended with a refresh and nothing has trained since, so the model, the
       // checkpoint and the scores below are those of refreshed weights; a run that trains nothing (--n_epochs 0
       // on a resumed model) refreshes what it loaded here

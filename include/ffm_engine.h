@@ -870,6 +870,55 @@ int ffm_engine_score_candidates_device(ffm_engine *e, int32_t n_req, const int32
                                        const int32_t *cand_feat, const float *cand_val, int32_t ctx_nnz,
                                        int32_t cand_nnz, int32_t ctx_cap, int32_t output_prob, float *out);
 
+/* ---- Field ablation: the loss and AUC of the model without each field, in one pass -------------------
+ * Which fields earn their place?  The standard answer is the evaluation loss and AUC of the same model with
+ * field f removed from every row -- n_fields more passes over rewritten copies of the evaluation data.  The
+ * wave kernels already stage everything those answers need: a row's surviving entries and every pair term,
+ * added in the reference's order.  The logit of the row without field v is the same ordered sum with the terms
+ * that touch v left out, and x + -0.0f == x, so it is exact.  The gathers and the k-long dots -- the cost of a
+ * prediction -- are made once per row; what is new per variant is one dependent add per term.
+ * DEFINITION  For a block and a field v in [0, n_fields), drop(block, v) is the block without every entry whose
+ *   field is v; rows, labels and the order of the remaining entries stay as they are.
+ *   variant v         of a row is ffm_engine_predict_batch of drop(block, v) at that row: the logit, the
+ *                     probability and the logloss term, bit for bit, on this engine's stored weights.
+ *   variant n_fields  is the row itself: ffm_engine_predict_batch of the block.
+ *   erased entries    (an id or field out of range, negative) are erased before ablation, as always.
+ *   a row without field v  has variant v equal to variant n_fields, bit for bit.
+ *   multi-valued fields    every entry of the field goes.
+ * ffm_engine_ablation_enable  allocates the (n_fields + 1) x max_batch_rows score and loss scratch and, with
+ *   with_auc, n_fields + 1 score histograms of 16 MiB each (640 MiB at 39 fields), zeroed; a second call keeps
+ *   what is on and its counts.  All of it is freed by ffm_engine_destroy.  Refused with FFM_E_UNSUPPORTED and a
+ *   message that says why: anything but a whole FFM model on one device (LR, FM, n_shards > 1, a group's
+ *   engine, compact storage); n_factors outside {4, 8, 16, 32, 64}; n_fields > 64 (one lane per variant means
+ *   one wave).  Works on training engines and on FFM_FLAG_SERVE_F32 / _F16 serving engines.
+ * ffm_engine_predict_ablated  rows in host memory, synchronous, staged like ffm_engine_predict_batch: val == NULL
+ *   is 1.0f, an engine with FFM_FLAG_HASH_IDS hashes the ids first (fields are not touched by hashing),
+ *   field == NULL is FFM_E_INVALID.  out[(n_fields + 1) * n_rows] is variant-major (variant v of row r at
+ *   v * n_rows + r; logits, or probabilities with output_prob) and may be NULL; loss_sum_out[n_fields + 1], may
+ *   be NULL, holds per variant the double ffm_engine_predict_batch(drop(block, v)) returns (0 without labels).
+ *   Before ffm_engine_ablation_enable: FFM_E_INVALID.
+ * ffm_engine_predict_ablated_device  the same on arrays in device memory (values and fields required, ids taken
+ *   as they are; out and loss_sum_out device arrays or NULL); asynchronous on the engine's stream.
+ * rows too long  a row longer than max_row_nnz, or than the 128 entries a wave stages, is NaN in every variant
+ *   and reported as FFM_E_CAPACITY (by the host call itself, by ffm_engine_sync after the device call), as a
+ *   serving engine's rows are: there is no second launch behind this one.
+ * ffm_engine_ablation_read  out[n_fields + 1]: per variant the ffm_metrics of its histogram -- the definition
+ *   of "Metrics": same bins, integer counters, one entry per labelled row of every ablated block since the
+ *   enable or the last reset.  Without with_auc: FFM_E_INVALID.
+ * The calls feed neither FFM_METRIC_EVAL nor FFM_METRIC_TRAIN, and neither keyed capture.  An engine that
+ * never enables ablation allocates nothing, launches nothing and changes in nothing; no existing kernel, launch
+ * or argument list changed, FFM_ENGINE_ABI_VERSION and ffm_engine_config are what they were.
+ * OUT OF SCOPE  a pipelined or staged form; groups and shards; ablation of field pairs. */
+int ffm_engine_ablation_enable(ffm_engine *e, int32_t with_auc);
+int ffm_engine_predict_ablated(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
+                               const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob,
+                               float *out /* [(n_fields + 1) * n_rows], variant-major, may be NULL */,
+                               double *loss_sum_out /* [n_fields + 1], may be NULL */);
+int ffm_engine_predict_ablated_device(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
+                                      const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
+                                      int32_t output_prob, float *out, double *loss_sum_out);
+int ffm_engine_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out /* [n_fields + 1] */);
+
 #ifdef __cplusplus
 }
 #endif
