@@ -50,6 +50,7 @@
 #include "kernels_metric.h"
 #include "kernels_keyed.h"
 #include "kernels_serve.h"
+#include "kernels_delta.h"
 #include "kernels_ablate.h"
 #include "kernels_stage.h"
 #include "kernels_sketch.h"
@@ -408,6 +409,10 @@ struct ffm_engine {
   int refresh_grid = 0;
   // ffm_engine_pack_weights (engine_serve.h): the four counters of a serving engine, made by the first call
   unsigned long long *d_pack = nullptr;
+  // ffm_engine_sync_weights (engine_delta.h), both made by a serving engine's first call: its four counters, and
+  // the features the LAST call moved as a bitmap of ceil(n_feats / 64) words
+  unsigned long long *d_sync = nullptr, *d_moved = nullptr;
+  bool synced = false;
   // ffm_engine_score_candidates[_device] (engine_serve.h): what serve_context_kernel leaves for the candidates'
   // waves (cx) and the host call's staging of the context arrays, made by the first call, grown to the largest
   // call seen; the capacities in elements
@@ -823,6 +828,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_stage.h"
 #include "engine_refresh.h"
 #include "engine_serve.h"
+#include "engine_delta.h"
 #include "engine_profile.h"
 #include "engine_metrics.h"
 #include "engine_keyed.h"

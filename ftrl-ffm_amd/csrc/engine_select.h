@@ -132,3 +132,13 @@ inline AblateWaveFn ablate_wave_fn(int fmt, int n_factors) {
 }
 #undef FFM_BY_FMT
 #undef FFM_LANE_SHAPES
+
+// ---- serving deltas (kernels_delta.h): one instantiation per format of the packed table ---------------------
+using ServeSyncFn = void (*)(ModelDev, ModelDev, int64_t, unsigned long long *, unsigned long long *);
+using ServeRowsRawFn = void (*)(ModelDev, void *, const int *, int64_t, int);
+inline ServeSyncFn serve_sync_fn(int fmt) {
+  return fmt == SERVE_F16 ? serve_sync_kernel<SERVE_F16> : fmt == SERVE_F32 ? serve_sync_kernel<SERVE_F32> : nullptr;
+}
+inline ServeRowsRawFn serve_rows_raw_fn(int fmt) {  // elements of 2 or 4 bytes, moved as they are
+  return fmt == SERVE_F16 ? serve_rows_raw_kernel<unsigned short> : fmt == SERVE_F32 ? serve_rows_raw_kernel<unsigned> : nullptr;
+}

@@ -81,6 +81,16 @@ class PackStats(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class SyncStats(ctypes.Structure):
+    """struct ffm_sync_stats (include/ffm_engine.h "Serving deltas")."""
+    _fields_ = [(k, ctypes.c_int64) for k in ("n_moved", "n_lin_moved", "n_lat_moved", "bias_moved")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+RAW_DTYPES = {"f32": np.float32, "f16": np.uint16}  # a serving table's own elements, per format
+
 METRIC_EVAL, METRIC_TRAIN = 0, 1  # FFM_METRIC_*
 METRIC_BINS = 1 << 20             # FFM_METRIC_BINS
 _METRIC_CHANNELS = {"eval": METRIC_EVAL, "train": METRIC_TRAIN}
@@ -220,6 +230,11 @@ ABI = [
     ("ffm_engine_predict_ablated_device", ctypes.c_int,
      [_vp, ctypes.c_int32, ctypes.c_int32] + _DCSR + [ctypes.c_int32, _vp, _vp]),
     ("ffm_engine_ablation_read", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(Metrics)]),
+    # sync a serving engine, publish only what moved (include/ffm_engine.h "Serving deltas")
+    ("ffm_engine_sync_weights", ctypes.c_int, [_vp, _vp, ctypes.POINTER(SyncStats)]),
+    ("ffm_engine_sync_moved", ctypes.c_int, [_vp, _i32p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    ("ffm_engine_get_rows_raw", ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p, _vp]),
+    ("ffm_engine_set_rows_raw", ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p, _vp]),
 ]
 SKETCH_REGS = 16384  # FFM_SKETCH_REGS
 
@@ -575,6 +590,76 @@ class Engine:
         st = PackStats()
         self._check(self.lib.ffm_engine_pack_weights(self.h, src.h, ctypes.byref(st)))
         return st.as_dict()
+
+    # ---- serving deltas (include/ffm_engine.h "Serving deltas") ----
+    def sync_from(self, src):
+        """pack_from(src) by comparison (ffm_engine_sync_weights): afterwards this serving engine holds, bit for
+        bit, what pack_from(src) would have left, but only the features whose patterns differed were written, and
+        their set stays on the device for sync_moved().  Returns dict(n_moved, n_lin_moved, n_lat_moved, bias_moved)."""
+        st = SyncStats()
+        self._check(self.lib.ffm_engine_sync_weights(self.h, src.h, ctypes.byref(st)))
+        return st.as_dict()
+
+    def sync_moved(self):
+        """Ascending int32 ids of the features the last sync_from() moved (ffm_engine_sync_moved)."""
+        n = ctypes.c_int64(0)
+        self._check(self.lib.ffm_engine_sync_moved(self.h, None, 0, ctypes.byref(n)))
+        ids = np.empty(n.value, np.int32)
+        self._check(self.lib.ffm_engine_sync_moved(self.h, _i(ids), ids.size, ctypes.byref(n)))
+        return ids[:n.value]
+
+    def _raw_dtype(self):
+        if not self.serve:
+            raise EngineError(E_UNSUPPORTED, "raw rows are a serving engine's: a training engine has get_rows / set_rows")
+        return RAW_DTYPES[self.serve]
+
+    def get_rows_raw(self, ids):
+        """The listed features as this serving engine stores them (ffm_engine_get_rows_raw): (lin_w float32 [n],
+        lat [n, row_len] of np.float32 (f32) or np.uint16 (f16: the halves' bits)); no conversion."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        lw = np.zeros(ids.size, np.float32)
+        lat = np.zeros((ids.size, self.row_len), RAW_DTYPES.get(self.serve, np.float32))
+        self._check(self.lib.ffm_engine_get_rows_raw(self.h, ids.size, _i(ids), _f(lw), lat.ctypes.data if lat.size else None))
+        return lw, lat
+
+    def set_rows_raw(self, ids, lin_w=None, lat=None):
+        """Overwrites the listed features' lin_w and / or rows with the given bits (ffm_engine_set_rows_raw);
+        lat: [n, row_len] of the format's own dtype (np.float32 / np.uint16), taken as it is."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        lw = None if lin_w is None else np.ascontiguousarray(lin_w, np.float32)
+        if lw is not None and lw.size != ids.size:
+            raise ValueError("lin_w: one float32 per id")
+        if lat is not None:
+            dt = RAW_DTYPES.get(self.serve, np.float32)
+            lat = np.ascontiguousarray(lat)
+            if lat.dtype != dt or lat.size != ids.size * self.row_len:
+                raise ValueError("lat: [n, row_len] of %s" % np.dtype(dt).name)
+        self._check(self.lib.ffm_engine_set_rows_raw(self.h, ids.size, _i(ids), _f(lw),
+                                                     lat.ctypes.data if lat is not None and lat.size else None))
+
+    def export_delta(self):
+        """What the last sync_from() moved, in this engine's own bits: dict(fmt, ids, bias, lin_w, lat).
+        apply_delta() of it on an engine that held what this one held before that sync reproduces this one."""
+        self._raw_dtype()
+        ids = self.sync_moved()
+        lw, lat = self.get_rows_raw(ids)
+        b = np.zeros(1, np.float32)
+        self._check(self.lib.ffm_engine_get_weights(self.h, _f(b), None, None))
+        return dict(fmt=self.serve, ids=ids, bias=b, lin_w=lw, lat=lat)
+
+    def apply_delta(self, d):
+        """set_rows_raw of an export_delta() plus its bias; refuses a fmt or row_len that is not this engine's."""
+        dt = self._raw_dtype()
+        ids = np.ascontiguousarray(d["ids"], np.int32)
+        lat = np.asarray(d["lat"])
+        if d["fmt"] != self.serve or lat.dtype != dt:
+            raise EngineError(E_INVALID, "apply_delta: a delta of format %r on a %r engine" % (d["fmt"], self.serve))
+        if lat.ndim != 2 or lat.shape != (ids.size, self.row_len):
+            raise EngineError(E_INVALID, "apply_delta: rows of %r elements on an engine of row_len %d" % (lat.shape[1:], self.row_len))
+        if ids.size:
+            self.set_rows_raw(ids, d["lin_w"], lat)
+        b = np.ascontiguousarray(d["bias"], np.float32).reshape(-1)[:1].copy()
+        self._check(self.lib.ffm_engine_set_weights(self.h, _f(b), None, None))
 
     def load_sparse_weights(self, d):
         """sparse_state() of a training engine of the same config into this SERVING engine: the listed

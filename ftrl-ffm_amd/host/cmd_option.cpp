@@ -116,7 +116,20 @@ const std::string_view cmd_help =
     "              approximation).  Prints `field importance: R rows, loss L, auc A`, then per field, in field order,\n"
     "              `field f: without it loss L (delta D), auc A (delta D)`; the AUC parts only with --metrics auc.  Needs\n"
     "              --eval_data; FFM only, one GPU, --n_fields <= 64, --n_factors 4, 8, 16, 32 or 64, rows of at most 128\n"
-    "              entries.  Nothing else of the output changes\tdefault:false\n";
+    "              entries.  Nothing else of the output changes\tdefault:false\n"
+    "--publish_path <prefix>: after every epoch's training (after that epoch's --refresh_weights refresh when it is on,\n"
+    "              before its evaluation) write <prefix>.<epochs_done>.delta: the features whose serving bits moved since\n"
+    "              the previous delta, in a serving engine's own format -- delta 1 is relative to a fresh serving engine of\n"
+    "              the same --seed and init.  A shadow serving engine on the same GPU does the comparing: it costs a third\n"
+    "              (f32) or a sixth (f16) of the training engine's memory on top of it.  Prints `epoch N published: M of F\n"
+    "              features moved, B bytes -> FILE`.  With --resume_from ck the shadow first applies <prefix>.1 ..\n"
+    "              <prefix>.<epochs of ck>; a missing or mismatching file is an error before any training.  FFM only, one\n"
+    "              GPU, --n_factors 4, 8, 16, 32 or 64; not with --cmd true or --serve_weights\tdefault:(none)\n"
+    "--publish_weights <f32|f16>: the format of the deltas --publish_path writes\tdefault:f32\n"
+    "--apply_deltas <prefix[:N]>: with --serve_weights <fmt> --n_epochs 0: a fresh serving engine takes <prefix>.1.delta,\n"
+    "              <prefix>.2.delta .. up to N (default: every consecutive file that exists; at least one must), prints\n"
+    "              `applied D deltas: M features, B bytes`, then evaluates or scores as --resume_from ck --n_epochs 0 does.\n"
+    "              Not with --resume_from, --n_epochs > 0 or a --serve_weights other than the files' format\tdefault:(none)\n";
 
 static bool assign_bool(std::string arg) {
   std::transform(arg.begin(), arg.end(), arg.begin(), [](unsigned char c) { return std::tolower(c); });
@@ -139,6 +152,20 @@ std::string detect_file_type(const std::string &file_path) {
   if (colons == 2) return "libffm";
   std::fprintf(stderr, "unknown file format...\n");
   std::exit(EXIT_FAILURE);
+}
+
+// The format a serving delta file names in its header (serve_delta.h: 8 bytes of magic, the version, then 32-bit
+// little-endian fields, the format the sixth of them): "f32", "f16", or "" for anything else.  Read here by hand so
+// that parsing options needs nothing but this file; the loader checks the whole header again.
+static std::string serve_delta_format(const std::string &path) {
+  unsigned char raw[36];
+  std::FILE *f = std::fopen(path.c_str(), "rb");
+  if (!f) return "";
+  const size_t got = std::fread(raw, 1, sizeof raw, f);
+  std::fclose(f);
+  if (got != sizeof raw || std::string(reinterpret_cast<const char *>(raw), 8) != "FFMSDLT\n") return "";
+  const unsigned format = raw[32] | raw[33] << 8 | raw[34] << 16 | static_cast<unsigned>(raw[35]) << 24;
+  return format == 1 ? "f32" : format == 2 ? "f16" : "";
 }
 
 void config_options::parse_option(int argc, char *argv[]) {
@@ -208,6 +235,29 @@ void config_options::parse_option(int argc, char *argv[]) {
       if (x < 0 || x > 2147483647) throw std::invalid_argument("--auc_key_field names a field: >= 0, got `" + v + "`");
       auc_key_field = static_cast<int>(x);
     }
+    else if (k == "--publish_path") {
+      if (v.empty()) throw std::invalid_argument("--publish_path needs a file name prefix");
+      publish_path = v;
+    }
+    else if (k == "--publish_weights") {
+      if (v != "f32" && v != "f16") throw std::invalid_argument("--publish_weights takes f32 or f16");
+      publish_weights = v;
+    }
+    else if (k == "--apply_deltas") {
+      // PREFIX, or PREFIX:N with N a positive count (a prefix may hold colons itself: only a numeric tail counts)
+      apply_deltas = v;
+      apply_deltas_n = 0;
+      const size_t colon = v.rfind(':');
+      if (colon != std::string::npos && colon + 1 < v.size() &&
+          std::all_of(v.begin() + static_cast<std::ptrdiff_t>(colon) + 1, v.end(), [](unsigned char c) { return std::isdigit(c); })) {
+        long long n = 0;
+        try { n = std::stoll(v.substr(colon + 1)); } catch (const std::exception &) { n = 0; }
+        if (n <= 0 || n > 1000000) throw std::invalid_argument("--apply_deltas PREFIX:N takes a positive count, got `" + v + "`");
+        apply_deltas = v.substr(0, colon);
+        apply_deltas_n = static_cast<int>(n);
+      }
+      if (apply_deltas.empty()) throw std::invalid_argument("--apply_deltas needs a file name prefix");
+    }
     else if (k == "--predict_data") predict_path = v;
     else if (k == "--predict_out") predict_out = v;
     else if (k == "--predict_output") {
@@ -221,7 +271,10 @@ void config_options::parse_option(int argc, char *argv[]) {
   if (serve_weights != "none") {
     // a serving engine holds no accumulators: it can only score a saved model (refused here, before a device is opened)
     const std::string what = "--serve_weights " + serve_weights + " ";
-    if (resume_from.empty()) throw std::invalid_argument(what + "scores a saved model: it needs --resume_from <checkpoint> --n_epochs 0");
+    if (!publish_path.empty())
+      throw std::invalid_argument("--publish_path publishes what training moved: a serving run (" + what + ") trains nothing");
+    if (resume_from.empty() && apply_deltas.empty())
+      throw std::invalid_argument(what + "scores a saved model: it needs --resume_from <checkpoint> --n_epochs 0");
     if (epoch > 0) throw std::invalid_argument(what + "cannot train: it needs --n_epochs 0 (got --n_epochs " + std::to_string(epoch) + ")");
     if (!model_path.empty()) throw std::invalid_argument(what + "writes no model: --model_path is not allowed with it");
     if (!checkpoint_path.empty()) throw std::invalid_argument(what + "holds no accumulators to checkpoint: --checkpoint_path is not allowed with it");
@@ -229,6 +282,27 @@ void config_options::parse_option(int argc, char *argv[]) {
     if (refresh_weights)
       throw std::invalid_argument(what + "holds no accumulators to refresh from: write the checkpoint with --refresh_weights true instead");
     if (model_type != "FFM") throw std::invalid_argument(what + "is for FFM models only (got --model_type " + model_type + ")");
+  }
+  if (!publish_path.empty()) {
+    // a shadow serving engine beside one whole FFM training engine (refused here, before a device is opened)
+    const std::string what = "--publish_path " + publish_path + " ";
+    if (model_type != "FFM") throw std::invalid_argument(what + "publishes a serving engine's rows: FFM only (got --model_type " + model_type + ")");
+    if (n_gpus > 1) throw std::invalid_argument(what + "follows one whole model on one GPU: --n_gpus > 1 is not allowed with it");
+    if (n_factors != 4 && n_factors != 8 && n_factors != 16 && n_factors != 32 && n_factors != 64)
+      throw std::invalid_argument(what + "keeps a serving engine: --n_factors must be 4, 8, 16, 32 or 64 (got " + std::to_string(n_factors) + ")");
+    if (cmd) throw std::invalid_argument(what + "publishes after an epoch over --train_data: --cmd true has none");
+  }
+  if (!apply_deltas.empty()) {
+    // a fresh serving engine plus the published deltas (refused here, before a device is opened)
+    const std::string what = "--apply_deltas " + apply_deltas + " ";
+    if (serve_weights == "none") throw std::invalid_argument(what + "fills a serving engine: it needs --serve_weights f32 or f16");
+    if (!resume_from.empty()) throw std::invalid_argument(what + "starts from a fresh serving engine: --resume_from is not allowed with it");
+    if (epoch > 0) throw std::invalid_argument(what + "cannot train: it needs --n_epochs 0 (got --n_epochs " + std::to_string(epoch) + ")");
+    const std::string first = apply_deltas + ".1.delta";
+    const std::string fmt = serve_delta_format(first);
+    if (fmt.empty()) throw std::invalid_argument(what + "needs at least " + first + ": no serving delta of that name can be read");
+    if (fmt != serve_weights)
+      throw std::invalid_argument(what + "holds " + fmt + " rows (" + first + "): --serve_weights " + serve_weights + " cannot take them");
   }
   if (field_ranges == "counted") {
     // the counting pass reads the training file on one GPU before an FFM model exists (refused here, before a device is opened)

@@ -58,6 +58,13 @@ struct config_options {
   // --field_importance true: after the last evaluation, the eval loss (and, with --metrics auc, the AUC) of the model
   // without each field, from one more pass over --eval_data (include/ffm_engine.h "Field ablation", field_importance.h)
   bool field_importance = false;
+  // --publish_path PREFIX [--publish_weights f32|f16]: after every epoch's training (and refresh) a serving delta
+  // PREFIX.<epochs_done>.delta -- what a shadow serving engine had to move to follow the model (serve_delta.h)
+  std::string publish_path, publish_weights = "f32";
+  // --apply_deltas PREFIX[:N] with --serve_weights fmt --n_epochs 0: a fresh serving engine brought to the published
+  // model by PREFIX.1.delta .. (apply_deltas_n = 0: every consecutive file that exists)
+  std::string apply_deltas;
+  int apply_deltas_n = 0;
 
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };

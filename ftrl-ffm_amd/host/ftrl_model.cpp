@@ -1,8 +1,10 @@
 #include "ftrl_model.h"
 
 #include "persist.h"
+#include "serve_delta.h"
 
 #include <algorithm>
+#include <fstream>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -59,6 +61,8 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
   // --serve_weights: a serving engine (include/ffm_engine.h "Serving engines") -- the weights alone, rows of at
   // most 128 entries, prediction only; load_checkpoint then passes the saved w and nothing else
   serving_ = opt.serve_weights != "none";
+  serve_fmt_ = opt.serve_weights;
+  device_ = opt.device;
   if (serving_) {
     if (opt.serve_weights != "f32" && opt.serve_weights != "f16") throw std::invalid_argument("serve_weights: none, f32 or f16");
     if (opt.n_gpus > 1) throw std::invalid_argument("a serving engine is one whole model on one GPU (n_gpus == 1)");
@@ -139,6 +143,7 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
 }
 
 FtrlModel::~FtrlModel() {
+  if (shadow_) ffm_engine_destroy(shadow_);
   if (grp_) ffm_group_destroy(grp_); else ffm_engine_destroy(eng_);
 }
 
@@ -800,6 +805,142 @@ FtrlModel::TrainProgress FtrlModel::load_checkpoint(std::string_view file_name) 
   p.rows_seen = h.rows_seen;
   p.epochs_done = h.epochs_done;
   return p;
+}
+
+// ---- serving deltas: what a shadow serving engine had to move to follow this model -----------------
+
+void FtrlModel::make_shadow(const std::string &fmt) {
+  if (shadow_) {
+    if (fmt != shadow_fmt_) throw std::invalid_argument("publish_delta: the shadow is " + shadow_fmt_ + ", not " + fmt);
+    return;
+  }
+  if (fmt != "f32" && fmt != "f16") throw std::invalid_argument("publish_delta: the format is f32 or f16");
+  if (serving_ || grp_ || n_gpus_ > 1 || model_type != ModelType::FFM)
+    throw std::invalid_argument("publish_delta follows one whole FFM training engine on one GPU");
+  // a serving engine of this model's shape, seed and init: fresh, it is what a consumer starts from
+  ffm_engine_config cfg;
+  ffm_engine_default_config(&cfg);
+  cfg.model_type = FFM_MODEL_FFM;
+  cfg.n_feats = n_feats;
+  cfg.n_fields = n_fields;
+  cfg.n_factors = n_factors;
+  cfg.init_mean = init_mean_;
+  cfg.init_stddev = init_stddev_;
+  cfg.seed = seed_;
+  cfg.max_batch_rows = 1;  // (it never predicts)
+  cfg.max_batch_nnz = 128;
+  cfg.max_row_nnz = 128;
+  cfg.device_id = device_;
+  cfg.flags = (flags_ & FFM_FLAG_SKIP_INIT) | (fmt == "f16" ? FFM_FLAG_SERVE_F16 : FFM_FLAG_SERVE_F32);
+  const int rc = ffm_engine_create(&cfg, &shadow_);
+  if (rc == FFM_E_INVALID || rc == FFM_E_UNSUPPORTED) throw std::invalid_argument(ffm_engine_last_error());
+  check(rc, "ffm_engine_create (the publishing shadow)");
+  shadow_fmt_ = fmt;
+  shadow_seq_ = 0;
+}
+
+void FtrlModel::prepare_publish(const std::string &prefix, const std::string &fmt, long long seq_done) {
+  make_shadow(fmt);
+  while (shadow_seq_ < seq_done) {
+    apply_delta_to(shadow_, shadow_fmt_, prefix + "." + std::to_string(shadow_seq_ + 1) + ".delta", shadow_seq_ + 1);
+    shadow_seq_++;
+  }
+}
+
+static long long file_bytes(const std::string &path) {
+  std::ifstream f(path, std::ios::binary | std::ios::ate);
+  return f.good() ? static_cast<long long>(f.tellg()) : 0;
+}
+
+FtrlModel::DeltaResult FtrlModel::publish_delta(const std::string &prefix, const std::string &fmt, long long seq) {
+  make_shadow(fmt);
+  if (seq != shadow_seq_ + 1)
+    throw std::runtime_error("publish_delta: delta " + std::to_string(seq) + " asked for, the shadow has " +
+                             std::to_string(shadow_seq_) + " behind it");
+  ffm_sync_stats st;
+  check(ffm_engine_sync_weights(shadow_, eng_, &st), "ffm_engine_sync_weights");
+  int64_t n = 0;
+  check(ffm_engine_sync_moved(shadow_, nullptr, 0, &n), "ffm_engine_sync_moved");
+  std::vector<int32_t> ids(static_cast<size_t>(std::max<int64_t>(n, 1)));
+  check(ffm_engine_sync_moved(shadow_, ids.data(), n, &n), "ffm_engine_sync_moved");
+  ServeDeltaHeader h;
+  h.model_type = static_cast<int32_t>(model_type);
+  h.n_feats = n_feats;
+  h.n_fields = n_fields;
+  h.n_factors = n_factors;
+  h.hash_ids = (flags_ & FFM_FLAG_HASH_IDS) ? 1u : 0u;
+  h.format = fmt == "f16" ? kServeDeltaF16 : kServeDeltaF32;
+  h.row_len = row_len_;
+  h.seed = seed_;
+  h.init_mean_bits = float_bits(init_mean_);
+  h.init_stddev_bits = float_bits(init_stddev_);
+  h.seq = seq;
+  h.n_moved = n;
+  h.chunk = static_cast<int64_t>(stream_chunk());
+  float b = 0.0f;
+  check(ffm_engine_get_weights(shadow_, &b, nullptr, nullptr), "ffm_engine_get_weights");
+  h.bias_bits = float_bits(b);
+  DeltaResult res;
+  res.file = prefix + "." + std::to_string(seq) + ".delta";
+  res.n_moved = n;
+  ServeDeltaWriter w(res.file, h, ids.data(), 3);
+  const size_t chunk = std::min(static_cast<size_t>(h.chunk), static_cast<size_t>(std::max<int64_t>(n, 1)));
+  std::vector<float> lin(chunk), lat(chunk * h.row_words());
+  for (size_t j0 = 0; j0 < static_cast<size_t>(n); j0 += chunk) {
+    const size_t c = std::min(chunk, static_cast<size_t>(n) - j0);
+    check(ffm_engine_get_rows_raw(shadow_, static_cast<int32_t>(c), ids.data() + j0, lin.data(), lat.data()), "ffm_engine_get_rows_raw");
+    w.chunk(c, lin.data(), lat.data());
+  }
+  w.finish();
+  shadow_seq_ = seq;
+  res.bytes = file_bytes(res.file);
+  return res;
+}
+
+FtrlModel::DeltaResult FtrlModel::apply_delta_to(ffm_engine *e, const std::string &fmt, const std::string &path, long long want_seq) {
+  ServeDeltaReader r(path);
+  const ServeDeltaHeader &h = r.header();
+  if (h.model_type != static_cast<int32_t>(model_type) || h.n_feats != n_feats || h.n_fields != n_fields ||
+      h.n_factors != n_factors || h.row_len != row_len_)
+    throw std::runtime_error(path + ": holds the rows of a model of a different shape");
+  if (h.format != (fmt == "f16" ? kServeDeltaF16 : kServeDeltaF32))
+    throw std::runtime_error(path + ": holds " + (h.format == kServeDeltaF16 ? "f16" : "f32") + " rows, this serving engine is " + fmt);
+  if (h.hash_ids != ((flags_ & FFM_FLAG_HASH_IDS) ? 1u : 0u))
+    throw std::runtime_error(path + ": was published " + (h.hash_ids ? "with" : "without") + " --hash_feats, this model is the other variant");
+  if (h.seed != seed_ || h.init_mean_bits != float_bits(init_mean_) || h.init_stddev_bits != float_bits(init_stddev_))
+    throw std::runtime_error(path + ": was published from a model with another seed or other init parameters "
+                                    "(delta 1 is relative to THAT fresh model)");
+  if (h.seq != want_seq)
+    throw std::runtime_error(path + ": is delta " + std::to_string(h.seq) + ", the next one to apply is " + std::to_string(want_seq));
+  const size_t n = r.ids().size();
+  const size_t cap = std::min(static_cast<size_t>(h.chunk), std::max<size_t>(n, 1));
+  std::vector<float> lin(cap), lat(cap * h.row_words());
+  size_t j0 = 0;
+  while (const size_t c = r.next_chunk_size()) {
+    r.chunk(lin.data(), lat.data());
+    check(ffm_engine_set_rows_raw(e, static_cast<int32_t>(c), r.ids().data() + j0, lin.data(), lat.data()), "ffm_engine_set_rows_raw");
+    j0 += c;
+  }
+  r.finish();
+  float b;
+  std::memcpy(&b, &h.bias_bits, sizeof b);
+  check(ffm_engine_set_weights(e, &b, nullptr, nullptr), "ffm_engine_set_weights");
+  DeltaResult res;
+  res.file = path;
+  res.n_moved = static_cast<long long>(n);
+  res.bytes = file_bytes(path);
+  return res;
+}
+
+FtrlModel::DeltaResult FtrlModel::apply_delta(const std::string &path) {
+  if (!serving_) throw std::invalid_argument("apply_delta fills a serving model (--serve_weights f32 | f16)");
+  const DeltaResult res = apply_delta_to(eng_, serve_fmt_, path, deltas_applied_ + 1);
+  deltas_applied_++;
+  pull_linear();
+  vec_w.dense_ready_ = false;
+  vec_w.dense_.clear();
+  vec_w.cache_.clear();
+  return res;
 }
 
 bool FtrlModel::has_zero_weights() {  // utils.h:63-76 over lin_w, then vec_w (ftrl_offline.cpp:105-119)

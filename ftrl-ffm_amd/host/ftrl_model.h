@@ -177,6 +177,21 @@ class FtrlModel {
   void save_checkpoint(std::string_view file_name, int compress_level = 3, TrainProgress progress = TrainProgress());
   TrainProgress load_checkpoint(std::string_view file_name);
 
+  // Serving deltas (serve_delta.h; include/ffm_engine.h "Serving deltas").
+  // publish_delta, on a training model (one FFM engine): a SHADOW serving engine of format `fmt` ("f32" / "f16")
+  // on the same device, made by the first call (or by prepare_publish), is synced from the training engine; the
+  // ids it had to move and their raw rows, pulled chunk by chunk, go to PREFIX.<seq>.delta.  The shadow costs a
+  // third (f32) or a sixth (f16) of the training engine's memory on top of it.
+  // prepare_publish makes the shadow and brings it to a resumed run's epoch by applying PREFIX.1 .. PREFIX.<seq_done>
+  // (throws std::runtime_error on a missing or mismatching file).
+  // apply_delta, on a serving model: checks every header field against the model and seq == deltas applied + 1,
+  // then pushes the rows chunk by chunk and sets the bias.
+  struct DeltaResult { long long n_moved = 0, bytes = 0; std::string file; };
+  void prepare_publish(const std::string &prefix, const std::string &fmt, long long seq_done);
+  DeltaResult publish_delta(const std::string &prefix, const std::string &fmt, long long seq);
+  DeltaResult apply_delta(const std::string &path);
+  long long deltas_applied() const { return deltas_applied_; }
+
   void pull_linear();   // device -> bias, lin_w (from the shards that own them)
   void push_linear();
   void pull_weights();  // device -> bias, lin_w and the rows of vec_w that are mirrored
@@ -225,6 +240,15 @@ class FtrlModel {
   float init_mean_ = 0.0f, init_stddev_ = 0.0f;
   int32_t flags_ = 0;
   bool serving_ = false;   // --serve_weights f32 | f16: a serving engine behind this model (prediction only)
+  std::string serve_fmt_ = "none";  // ... its format
+  // serving deltas: the shadow serving engine of publish_delta (null until asked for), its format, the deltas it
+  // has behind it; deltas_applied_: those apply_delta has pushed into this (serving) model
+  ffm_engine *shadow_ = nullptr;
+  std::string shadow_fmt_;
+  long long shadow_seq_ = 0, deltas_applied_ = 0;
+  int device_ = 0;
+  void make_shadow(const std::string &fmt);
+  DeltaResult apply_delta_to(ffm_engine *e, const std::string &fmt, const std::string &path, long long want_seq);
   bool hash_ids_ = false;  // --hash_feats: ids >= n_feats are not erased on the host, the device hashes them
   bool compact_rows_ = false;  // --compact_rows: blocks go without the arrays their facts make redundant
   long long compact_blocks_ = 0, compact_no_val_ = 0, compact_no_field_ = 0;

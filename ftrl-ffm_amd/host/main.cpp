@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
+#include <fstream>
 #include <stdexcept>
 #include <string>
 
@@ -35,6 +36,28 @@ int main(int argc, char *argv[]) {
     // and the task's progress, so that a run cut in two gives the files and losses of the run in one piece
     auto run = [&](auto &task) {
       if (!opt.resume_from.empty()) task.restore(task.model_ptr->load_checkpoint(opt.resume_from));
+      // --publish_path: the shadow serving engine, brought to a resumed run's epoch by the deltas published so far
+      // (a missing or mismatching one ends the run here, before any training)
+      if (!opt.publish_path.empty())
+        task.model_ptr->prepare_publish(opt.publish_path, opt.publish_weights, task.progress().epochs_done);
+      // --apply_deltas PREFIX[:N]: the fresh serving engine takes PREFIX.1.delta .. (every consecutive file that exists,
+      // or exactly N of them)
+      if (!opt.apply_deltas.empty()) {
+        long long features = 0, bytes = 0;
+        int applied = 0;
+        for (int seq = 1; opt.apply_deltas_n == 0 || seq <= opt.apply_deltas_n; seq++) {
+          const std::string file = opt.apply_deltas + "." + std::to_string(seq) + ".delta";
+          if (opt.apply_deltas_n == 0 && seq > 1 && !std::ifstream(file).good()) break;
+          const ftrl::FtrlModel::DeltaResult r = task.model_ptr->apply_delta(file);
+          features += r.n_moved;
+          bytes += r.bytes;
+          applied++;
+        }
+        std::printf("applied %d deltas: %lld features, %lld bytes\n", applied, features, bytes);
+        ftrl::FtrlModel::TrainProgress behind;  // (one delta per epoch: what is printed is numbered as a checkpoint's would be)
+        behind.epochs_done = applied;
+        task.restore(behind);
+      }
       task.train();
       // --auc_key_field on a run that trains nothing (--resume_from ck --n_epochs 0 --eval_data F): one evaluation pass
       // of the loaded model, numbered by the epochs it has behind it -- there is no epoch to print the line after

@@ -43,6 +43,11 @@ void refresh_and_print(FtrlModel &m, long long epoch) {
               static_cast<long long>(r.lat_live), static_cast<long long>(r.lat_nonzero), static_cast<long long>(r.lat_moved));
 }
 
+void publish_and_print(FtrlModel &m, const std::string &prefix, const std::string &fmt, long long epoch, long long n_feats) {
+  const FtrlModel::DeltaResult r = m.publish_delta(prefix, fmt, epoch);
+  std::printf("epoch %lld published: %lld of %lld features moved, %lld bytes -> %s\n", epoch, r.n_moved, n_feats, r.bytes, r.file.c_str());
+}
+
 // ---------------- offline: data in memory, seeded shuffle per epoch ----------------
 
 FtrlOffline::FtrlOffline(const config_options &opt)
@@ -66,6 +71,9 @@ FtrlOffline::FtrlOffline(const config_options &opt)
   metrics_ = opt.metrics == "auc";
   if (metrics_) model_ptr->enable_metrics(true, true);
   refresh_ = opt.refresh_weights;
+  publish_ = opt.publish_path;
+  publish_fmt_ = opt.publish_weights;
+  n_feats_ = opt.n_feats;
 }
 
 FtrlOffline::~FtrlOffline() = default;
@@ -160,6 +168,7 @@ void FtrlOffline::train() {
     std::printf("epoch %d train time: %.4lfs, train loss: %.4lf\n", i, seconds_since(t0), train_loss);
     if (metrics_) print_auc_line(*model_ptr, i, FFM_METRIC_TRAIN);
     if (refresh_) refresh_and_print(*model_ptr, i);
+    if (!publish_.empty()) publish_and_print(*model_ptr, publish_, publish_fmt_, i, n_feats_);
     if (has_eval_) evaluate(i);
   }
 }
@@ -203,6 +212,9 @@ FtrlOnline::FtrlOnline(const config_options &opt)
   metrics_ = opt.metrics == "auc";
   if (metrics_) model_ptr->enable_metrics(true, true);
   refresh_ = opt.refresh_weights;
+  publish_ = opt.publish_path;
+  publish_fmt_ = opt.publish_weights;
+  n_feats_ = opt.n_feats;
   if (!cmd_) {
     if (!opt.train_path.empty())  // (--n_epochs 0 needs no training file)
       train_stream_ = std::make_unique<CsrStream>(opt.train_path, opt.file_type, opt.thread_num);
@@ -281,6 +293,7 @@ void FtrlOnline::train() {
     std::printf("epoch %d train time: %.4lfs, train loss: %.4lf\n", i, seconds_since(t0), train_loss);
     if (metrics_) print_auc_line(*model_ptr, i, FFM_METRIC_TRAIN);
     if (refresh_) refresh_and_print(*model_ptr, i);
+    if (!publish_.empty()) publish_and_print(*model_ptr, publish_, publish_fmt_, i, n_feats_);
     if (evaluator) evaluate(i);
   }
 }

@@ -123,6 +123,9 @@ void print_gauc_line(FtrlModel &m, int epoch, int channel);
 // `epoch N weights: linear L live, Z nonzero, M moved; latent L live, Z nonzero, M moved`.
 // The tasks call it after each epoch's training, before that epoch's evaluation; main() where no epoch ran.
 void refresh_and_print(FtrlModel &m, long long epoch);
+// --publish_path: FtrlModel::publish_delta(prefix, fmt, epoch) and its line,
+// `epoch N published: M of F features moved, B bytes -> FILE`
+void publish_and_print(FtrlModel &m, const std::string &prefix, const std::string &fmt, long long epoch, long long n_feats);
 
 class FtrlOffline {
  public:
@@ -158,6 +161,8 @@ class FtrlOffline {
   BlockScheduler sched_;
   bool metrics_ = false;    // --metrics auc
   bool refresh_ = false;    // --refresh_weights
+  std::string publish_, publish_fmt_;  // --publish_path / --publish_weights
+  long long n_feats_ = 0;
   std::unique_ptr<Reader> train_data_loader, eval_data_loader;  // API parity (data stays empty
                                                                 // unless load_samples() is called)
   CsrData train_csr_, eval_csr_;                                // what train()/evaluate() walk
@@ -195,6 +200,8 @@ class FtrlOnline {
   bool cmd_;
   bool metrics_ = false;          // --metrics auc
   bool refresh_ = false;          // --refresh_weights
+  std::string publish_, publish_fmt_;  // --publish_path / --publish_weights
+  long long n_feats_ = 0;
   BlockScheduler sched_;
   std::unique_ptr<CsrStream> train_stream_;  // chunks of <= 20 000 lines parsed by n_threads workers
   std::unique_ptr<BlockRing> ring_;

@@ -919,6 +919,45 @@ int ffm_engine_predict_ablated_device(ffm_engine *e, int32_t n_rows, int32_t nnz
                                       int32_t output_prob, float *out, double *loss_sum_out);
 int ffm_engine_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out /* [n_fields + 1] */);
 
+/* ---- Serving deltas: sync a serving engine, publish only what moved --------------------------------------
+ * ffm_engine_pack_weights takes all of a model: it streams every record of the training engine and writes the
+ * whole table.  A trainer that never stops moves a few per cent of its features between two publications;
+ * these entry points find those features, list them, and move their rows in the table's own bits.
+ * ffm_engine_sync_weights  dst, src, the drains and the stream are those of ffm_engine_pack_weights, with the
+ *   same checks and the same errors.  Per feature i:
+ *   target    the linear pattern is the bits of src.lin_w[i]; the row is enc(src w[i][e]) for every e < row_len,
+ *             enc the format's own encoding (the identity for fp32, the fp16 rule of "Serving engines").
+ *   moved     i is MOVED iff its target linear pattern differs from the bits dst.lin_w[i] holds, or any target
+ *             element differs from the bits stored in dst's row -- patterns, not values, in the table's own
+ *             width: -0.0f against +0.0f is moved; a NaN whose encoded bits are the stored ones is not; an fp32
+ *             change that rounds to the same half is not moved on an fp16 engine.
+ *   dst       afterwards dst's bias, lin_w and table are, bit for bit, what ffm_engine_pack_weights(dst, src)
+ *             would have left; a feature that is not moved is not written.
+ *   stats     n_moved: the moved features; n_lin_moved, n_lat_moved: the elements whose patterns differed;
+ *             bias_moved: 0 or 1 (the bias is in no list).  out may be NULL.
+ *   bitmap    the moved set of the LAST call stays in dst as a bitmap in HBM, ceil(n_feats / 64) 64-bit words,
+ *             allocated (with 256 bytes of counters) by dst's first call and freed by ffm_engine_destroy; each
+ *             call overwrites it.
+ *   ordering  everything runs on dst's stream: predictions queued before the call see the old weights, those
+ *             queued after it the new ones.  Synchronous, like ffm_engine_pack_weights.
+ * ffm_engine_sync_moved  the bitmap as ascending ids, with the argument conventions of
+ *   ffm_engine_changed_features: ids == NULL counts; a cap below the count is FFM_E_CAPACITY with *n_moved set;
+ *   before any ffm_engine_sync_weights on this engine: FFM_E_INVALID.
+ * ffm_engine_get_rows_raw / set_rows_raw  the listed features' lin_w (fp32) and rows as the table stores them:
+ *   lat is [n][row_len] elements of 4 bytes (FFM_FLAG_SERVE_F32) or 2 (FFM_FLAG_SERVE_F16), no conversion in
+ *   either direction -- an fp16 engine's delta is half the bytes and keeps NaN payloads.  Either array may be
+ *   NULL.  Serving engines only: a training engine is FFM_E_UNSUPPORTED; an id outside [0, n_feats) is
+ *   FFM_E_INVALID before anything is moved, as for ffm_engine_get_rows / set_rows.  Synchronous.
+ * An engine that never calls these allocates nothing and launches nothing; no existing kernel, launch or
+ * argument list changed, FFM_ENGINE_ABI_VERSION and ffm_engine_config are what they were.
+ * OUT OF SCOPE  groups and shards, LR / FM; deltas between two training engines. */
+typedef struct { int64_t n_moved, n_lin_moved, n_lat_moved, bias_moved; } ffm_sync_stats;
+int ffm_engine_sync_weights(ffm_engine *dst, ffm_engine *src, ffm_sync_stats *out);
+int ffm_engine_sync_moved(ffm_engine *dst, int32_t *ids, int64_t cap, int64_t *n_moved);
+int ffm_engine_get_rows_raw(ffm_engine *e, int32_t n, const int32_t *ids, float *lin_w,
+                            void *lat /* [n][row_len] of 2 or 4 bytes */);
+int ffm_engine_set_rows_raw(ffm_engine *e, int32_t n, const int32_t *ids, const float *lin_w, const void *lat);
+
 #ifdef __cplusplus
 }
 #endif
