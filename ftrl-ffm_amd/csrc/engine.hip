@@ -43,7 +43,7 @@
 #include "kernels_update.h"
 #include "kernels_tile.h"
 #include "kernels_fm.h"
-#include "kernels_predict.h"
+#include "kernels_wave.h"
 #include "kernels_sort.h"
 #include "kernels_scan.h"
 #include "kernels_refresh.h"

@@ -74,7 +74,7 @@ inline UpdateRowsFn update_super_b_fn(int nf) {
   return nf == 1 ? ffm_update_super_b_kernel<1> : nf == 2 ? ffm_update_super_b_kernel<2> : nf == 4 ? ffm_update_super_b_kernel<4> : nullptr;
 }
 
-// ---- the wave kernels: a row (a context, a candidate) per wave (kernels_predict.h, kernels_serve.h) --------
+// ---- the wave kernels: a row (a context, a candidate) per wave (kernels_wave.h, kernels_serve.h, kernels_ablate.h)
 // The lane shape of n_factors, X(k, LPP, VPL, U): lanes per pair, vectors per lane, steps of loads in flight
 // together.  These are the n_factors the wave kernels exist for; every selector below is null for any other.
 #ifndef FFM_PRED_LPP
@@ -86,18 +86,21 @@ inline UpdateRowsFn update_super_b_fn(int nf) {
 #define FFM_LANE_SHAPES(X) \
   X(4, 1, 1, 4) X(8, 2, 1, 4) X(16, FFM_PRED_LPP, 4 / FFM_PRED_LPP, FFM_PRED_U) X(32, 8, 1, 2) X(64, 16, 1, 1)
 
-using RowWaveFn = void (*)(ModelDev, Rows, Scratch, int, int, float *, int);  // predict and serve alike
+using RowWaveFn = void (*)(ModelDev, Rows, Scratch, int, int, float *, int);  // ffm_row_wave_kernel: predict and serve alike
 using ServeContextFn = void (*)(ModelDev, int, const int *, const int *, const int *, const float *, const int *, int,
                                 CandCtx, int, int, int *);
 using ServeCandidateFn = void (*)(ModelDev, int, const int *, CandCtx, Rows, int, int, int *, float *, int);
 
-// fmt: ModelDev::lat_fmt -- SERVE_NONE (a training engine's records), SERVE_F32 or SERVE_F16 (a packed table of w)
+// fmt: ModelDev::lat_fmt -- SERVE_NONE (a training engine's records), SERVE_F32 or SERVE_F16 (a packed table of w).
+// FFM_BY_FMT: a family of the packed tables alone (a context and a candidate exist on a serving engine only: null
+// for SERVE_NONE); FFM_BY_ANY_FMT: one of all three (rows, field ablation).
 #define FFM_BY_FMT(KERNEL, LPP, VPL, U) \
   (fmt == SERVE_F16 ? KERNEL<SERVE_F16, LPP, VPL, U> : fmt == SERVE_F32 ? KERNEL<SERVE_F32, LPP, VPL, U> : nullptr)
+#define FFM_BY_ANY_FMT(KERNEL, LPP, VPL, U) \
+  (fmt == SERVE_NONE ? KERNEL<SERVE_NONE, LPP, VPL, U> : FFM_BY_FMT(KERNEL, LPP, VPL, U))
 inline RowWaveFn row_wave_fn(int fmt, int n_factors) {
   switch (n_factors) {
-#define X(K, LPP, VPL, U) \
-  case K: return fmt == SERVE_NONE ? ffm_predict_wave_kernel<LPP, VPL, U> : FFM_BY_FMT(ffm_serve_wave_kernel, LPP, VPL, U);
+#define X(K, LPP, VPL, U) case K: return FFM_BY_ANY_FMT(ffm_row_wave_kernel, LPP, VPL, U);
     FFM_LANE_SHAPES(X)
 #undef X
     default: return nullptr;
@@ -119,17 +122,17 @@ inline ServeCandidateFn serve_candidate_fn(int fmt, int n_factors) {
     default: return nullptr;
   }
 }
-// field ablation (kernels_ablate.h): one template for the three formats
+// field ablation (kernels_ablate.h)
 using AblateWaveFn = void (*)(ModelDev, Rows, int *, int, int, float *, double *, int, int);
 inline AblateWaveFn ablate_wave_fn(int fmt, int n_factors) {
   switch (n_factors) {
-#define X(K, LPP, VPL, U) \
-  case K: return fmt == SERVE_NONE ? ffm_ablate_wave_kernel<SERVE_NONE, LPP, VPL, U> : FFM_BY_FMT(ffm_ablate_wave_kernel, LPP, VPL, U);
+#define X(K, LPP, VPL, U) case K: return FFM_BY_ANY_FMT(ffm_ablate_wave_kernel, LPP, VPL, U);
     FFM_LANE_SHAPES(X)
 #undef X
     default: return nullptr;
   }
 }
+#undef FFM_BY_ANY_FMT
 #undef FFM_BY_FMT
 #undef FFM_LANE_SHAPES
 

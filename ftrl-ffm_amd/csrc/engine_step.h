@@ -30,7 +30,7 @@ static int check_block(ffm_engine *e, int32_t n_rows, int32_t nnz, const void *r
 }
 
 
-// FFM evaluation rows one wave each (kernels_predict.h) where that kernel applies: a whole model on
+// FFM evaluation rows one wave each (kernels_wave.h) where that kernel applies: a whole model on
 // this device, a k with a lane shape (engine_select.h), the rows' entries within 64 KB of LDS per workgroup.
 // A serving engine (engine_serve.h) has this kernel's twin and no other: create admitted only what it serves.
 static bool launch_row_waves(ffm_engine *e, const Rows &rows, int row_cap, float *out, int output_prob) {
@@ -123,7 +123,7 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, int row_cap, bool
     const bool whole = train && (own_tg || !vec4);
     int last = park;  // the kernels' last argument: vectors parked when training ...
     if (!train && launch_row_waves(e, rows, row_cap, out, output_prob)) {
-      // rows that may be longer than a wave stages (kernels_predict.h): the workgroup-per-row kernel
+      // rows that may be longer than a wave stages (kernels_wave.h): the workgroup-per-row kernel
       // for those alone (its last argument: rows of at most that many entries are not its)
       if (row_cap <= kPredLdsCap) return;
       last = kPredLdsCap;

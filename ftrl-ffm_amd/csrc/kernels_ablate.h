@@ -1,8 +1,7 @@
 // kernels_ablate.h -- field ablation in one pass (include/ffm_engine.h "Field ablation"): for every row the
 // n_fields + 1 logits "the row without field v" (v < n_fields) and "the row itself" (v = n_fields).
-//   ffm_ablate_wave_kernel   ffm_predict_wave_kernel / ffm_serve_wave_kernel with one more reader of what they
-//                            stage: the same rows per workgroup, LDS carve, erasure, pair order, factor-order
-//                            dot and ordered term sum -- the gathers and the k-long dots are made once per row.
+//   ffm_ablate_wave_kernel   ffm_row_wave_kernel's pieces (kernels_wave.h) with one more reader of what they
+//                            stage -- the gathers and the k-long dots are made once per row.
 //   ablate_loss_sum_kernel   loss_sum_kernel's arithmetic over each variant's slice of the loss scratch
 //   ablate_hist_kernel       metric_hist_kernel's body (a second copy), one grid row (blockIdx.y) per variant
 // The logit of the row without field v is the row's ordered sum with the terms that touch v left out; leaving a
@@ -12,13 +11,10 @@
 // terms it walks the batch in pair order; every lane reads the same LDS address (a broadcast), compares the
 // entry's field with its own number, and makes one dependent add per term.
 #pragma once
-#include <type_traits>
-
 #include "engine_types.h"
 #include "kernels_metric.h"
-#include "kernels_predict.h"
 #include "kernels_row.h"
-#include "kernels_serve.h"
+#include "kernels_wave.h"
 
 namespace ftrl_dev {
 
@@ -35,24 +31,20 @@ __device__ __forceinline__ void ablate_pin4(int (&f)[4], int (&t)[4]) {
   asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
 }
 
-// FMT: SERVE_NONE (a training engine's [n][z][w] records), SERVE_F32 or SERVE_F16 (a packed table of w): the
-// address of a slot and the conversion of what was loaded differ, nothing else.
-// out[(n_fields + 1) * n_rows] variant-major; loss[(n_fields + 1) * loss_stride], written when labels came.
+// FMT: WaveTable's.  out[(n_fields + 1) * n_rows] variant-major; loss[(n_fields + 1) * loss_stride], written when labels came.
 template <int FMT, int LPP, int VPL, int U>
 __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void ffm_ablate_wave_kernel(ModelDev m, Rows rows, int *err,
                                                                         int max_row_nnz, int lds_cap, float *out,
                                                                         double *loss, int loss_stride, int output_prob) {
-  static_assert(FMT == SERVE_NONE || FMT == SERVE_F32 || FMT == SERVE_F16, "records, or a packed table of w");
-  static_assert(LPP >= 1 && LPP <= 16 && (LPP & (LPP - 1)) == 0, "a pair's lanes sit inside one DPP row");
-  constexpr int PPS = 64 / LPP;  // pairs per step
-  static_assert(kPredTerms % (PPS * U) == 0, "a batch of terms is whole unrolled steps");
-  using Raw = typename std::conditional<FMT == SERVE_F16, uint2, float4>::type;  // four factors as stored
+  constexpr int PPS = wave_pairs_per_step<LPP, U>();
+  using Raw = typename WaveTable<FMT>::Raw;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int r = wave_uniform(blockIdx.x * kPredRows + wv);
   if (r >= rows.n_rows) return;
-  int4 *E = reinterpret_cast<int4 *>(smem + static_cast<size_t>(wv) * (static_cast<size_t>(lds_cap) * 16 + kPredTerms * 4));
-  float *terms = reinterpret_cast<float *>(E + lds_cap);
+  const WaveLds lds = wave_lds(smem, wv, lds_cap, kPredTerms);
+  int4 *const E = lds.E;
+  float *const terms = lds.terms;
   const int b = wave_uniform(rows.row_ptr[r]);
   const int nnz = wave_uniform(rows.row_ptr[r + 1]) - b;
   const int F = m.n_fields;  // (<= 64: one lane per variant v < F, lane 0 also variant F)
@@ -74,37 +66,15 @@ __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void ffm_ablate_wave_k
     }
     return;
   }
-  const int k = m.n_factors, RL = m.row_len;
-  const Raw *const table = reinterpret_cast<const Raw *>(m.lat);
-  const int k4 = k >> 2;  // vectors (of four factors) per slot
-  const int64_t RL4 = RL >> 2;
-  const int64_t rec4 = FMT == SERVE_NONE ? 3 * RL4 : RL4;      // vectors per feature
-  const int64_t w4 = FMT == SERVE_NONE ? LAT_W * RL4 : 0;      // ... before its w row
+  const WaveTable<FMT> table(m);
 
-  // ---- entries: the survivors in row order into LDS as {feature, field, value, lin_w * value}; the linear
-  // logit as a strictly sequential prefix
+  // ---- entries: the survivors as {feature, field, value, lin_w * value}, the product for the variants' walk
   float result = m.bias3[0];
   int nv = 0;
-  for (int base = 0; base < nnz; base += 64) {
-    const int p = base + lane;
-    int i = 0, f = 0;
-    float x = 0.0f, lw = 0.0f;
-    bool valid = false;
-    if (p < nnz) {
-      i = rows.feat[b + p];
-      f = rows.field[b + p];
-      x = rows.val[b + p];
-      valid = i >= 0 && i < m.n_feats && f >= 0 && f < m.n_fields;
-    }
-    if (valid) lw = m.lin_w[i];
-    const float lin = lw * x;
-    const unsigned long long mask = __ballot(valid);
-    if (valid) E[nv + __popcll(mask & ((1ull << lane) - 1ull))] = make_int4(i, f, __float_as_int(x), __float_as_int(lin));
-    nv += __popcll(mask);
-    const float run = wave_sequential_prefix(result, valid ? lin : -0.0f);
-    result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  wave_stage_entries(m, rows.feat, rows.field, rows.val, b, nnz, lane, result, nv, [&](int at, int4 en, float lin) {
+    en.w = __float_as_int(lin);
+    E[at] = en;
+  });
 
   // ---- the variants' linear part: lane v adds the survivors' products in order, field v's left out
   float acc = m.bias3[0];
@@ -125,12 +95,11 @@ __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void ffm_ablate_wave_k
     }
   }
 
-  // ---- pairs in the reference's order (a outer, b inner)
+  // ---- pairs, as the row kernel walks them
   const int n_pairs = nv * (nv - 1) / 2;
   const int g = lane / LPP, c = lane - g * LPP;
-  int pa = 0, pb = 1 + g;
-  if (g < n_pairs)
-    while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
+  WavePairCursor cur;
+  cur.start(g, n_pairs, nv);
   int wa = 0, wb = 1;  // the variants' walker: the pair of the next term, the same in every lane
   for (int q0 = 0; q0 < n_pairs; q0 += kPredTerms) {
     const int cnt = min(kPredTerms, n_pairs - q0);
@@ -142,55 +111,23 @@ __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void ffm_ablate_wave_k
       for (int u = 0; u < U; u++) {
         const int q = q0 + (st + u) * PPS + g;
         ok[u] = q < n_pairs;
-        const int a = ok[u] ? pa : 0, bb = ok[u] ? pb : (nv > 1 ? 1 : 0);
+        const int a = ok[u] ? cur.pa : 0, bb = ok[u] ? cur.pb : (nv > 1 ? 1 : 0);
         const int4 ea = E[a], eb = E[bb];
         xa[u] = __int_as_float(ea.z);
         xb[u] = __int_as_float(eb.z);
-        const Raw *va = table + static_cast<int64_t>(ea.x) * rec4 + w4 + eb.y * k4 + c * VPL;
-        const Raw *vb = table + static_cast<int64_t>(eb.x) * rec4 + w4 + ea.y * k4 + c * VPL;
+        const Raw *va = table.slot(ea.x, eb.y) + c * VPL, *vb = table.slot(eb.x, ea.y) + c * VPL;
 #pragma unroll
         for (int v = 0; v < VPL; v++) { x[u][v] = va[v]; y[u][v] = vb[v]; }
-        if (q + PPS < n_pairs) {  // the pair PPS further on
-          pb += PPS;
-          while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
-        }
+        if (q + PPS < n_pairs) cur.advance(PPS, nv);
       }
 #pragma unroll
       for (int u = 0; u < U; u++) {
-        float pr[VPL][4];
-#pragma unroll
-        for (int v = 0; v < VPL; v++) {
-          const float4 xf = serve_widen(x[u][v]), yf = serve_widen(y[u][v]);
-          pr[v][0] = xf.x * yf.x;
-          pr[v][1] = xf.y * yf.y;
-          pr[v][2] = xf.z * yf.z;
-          pr[v][3] = xf.w * yf.w;
-        }
-        // stage t finalises the lanes c == t: dot = ((0 + w0*v0) + w1*v1) + ... in factor order
-        float dot = 0.0f;
-#pragma unroll
-        for (int t = 0; t < LPP; t++) {
-          float in = LPP > 1 ? pred_lane_below(dot) : 0.0f;
-          in = c == 0 ? 0.0f : in;
-#pragma unroll
-          for (int v = 0; v < VPL; v++) {
-            in = in + pr[v][0];
-            in = in + pr[v][1];
-            in = in + pr[v][2];
-            in = in + pr[v][3];
-          }
-          dot = in;
-        }
-        const float term = dot * xa[u] * xb[u];
+        const float term = wave_pair_term<LPP, VPL>(x[u], y[u], c, xa[u], xb[u]);
         if (c == LPP - 1 && ok[u]) terms[(st + u) * PPS + g] = term;
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    for (int t0 = 0; t0 < cnt; t0 += 64) {
-      const float t = t0 + lane < cnt ? terms[t0 + lane] : -0.0f;
-      const float run = wave_sequential_prefix(result, t);
-      result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
-    }
+    result = wave_ordered_sum(result, terms, cnt, lane);
     // ---- the variants' share of the batch: its terms in order, one `a` at a time (every term of an `a` shares
     // field(wa): hoisted), lane v leaving out what touches field v
     for (int t = 0; t < cnt;) {

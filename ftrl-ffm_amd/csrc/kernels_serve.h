@@ -1,10 +1,10 @@
 // kernels_serve.h -- a SERVING engine's device code (include/ffm_engine.h "Serving engines"): the model is
 // the bias, lin_w and a latent table of w ALONE, [n_feats][n_fields * n_factors] elements of 4 bytes (the
 // training engine's fp32 bits) or 2 (IEEE binary16) -- no n, no z, no record stride.
-//   ffm_serve_wave_kernel   ffm_predict_wave_kernel (kernels_predict.h) over that table: the same rows per
-//                           workgroup, staging, erasure, pair order, factor-order dot, term sum; only the
-//                           address of a slot and (fp16) the conversion of what was loaded differ.
-//   serve_init_kernel       the create-time contents: the training engine's draw, rounded to the format
+// Rows are scored by ffm_row_wave_kernel<SERVE_F32 | SERVE_F16> (kernels_wave.h: WaveTable<FMT> is the address
+// of a slot in that table and the conversion of what was loaded).  Here:
+//   serve_context_kernel / serve_candidate_kernel   one context against many candidates, from the same pieces
+//   serve_init_kernel      the create-time contents: the training engine's draw, rounded to the format
 //   serve_dense_copy_kernel / serve_rows_copy_kernel   packed table <-> the fp32 staging buffer
 //   serve_pack_kernel       a training engine's stored bias, lin_w and w into a serving engine, counted
 // The fp16 rule is the hardware's conversion pair (v_cvt_f16_f32 / v_cvt_f32_f16 with 16-bit denormals on and
@@ -13,29 +13,18 @@
 #pragma once
 #include <hip/hip_fp16.h>
 
-#include <type_traits>
-
 #include "engine_types.h"
 #include "init_rng.h"
-#include "kernels_predict.h"
+#include "kernels_wave.h"
 
 namespace ftrl_dev {
 
-enum { SERVE_NONE = 0, SERVE_F32 = 1, SERVE_F16 = 2 };  // ModelDev::lat_fmt
-
+// (SERVE_NONE / SERVE_F32 / SERVE_F16 and the decoding half of the pair, serve_dec16 / serve_dec16x4: kernels_wave.h)
 __device__ __forceinline__ unsigned short serve_enc16(float x) { return __half_as_ushort(__float2half_rn(x)); }
-__device__ __forceinline__ float serve_dec16(unsigned short h) { return __half2float(__ushort_as_half(h)); }
-// four consecutive halves as a lane loads them (8 bytes): element j in bits [16 j, 16 j + 16)
-__device__ __forceinline__ float4 serve_dec16x4(uint2 r) {
-  return make_float4(serve_dec16(static_cast<unsigned short>(r.x & 0xffffu)), serve_dec16(static_cast<unsigned short>(r.x >> 16)),
-                     serve_dec16(static_cast<unsigned short>(r.y & 0xffffu)), serve_dec16(static_cast<unsigned short>(r.y >> 16)));
-}
 __device__ __forceinline__ uint2 serve_enc16x4(float4 w) {
   return make_uint2(static_cast<unsigned>(serve_enc16(w.x)) | (static_cast<unsigned>(serve_enc16(w.y)) << 16),
                     static_cast<unsigned>(serve_enc16(w.z)) | (static_cast<unsigned>(serve_enc16(w.w)) << 16));
 }
-__device__ __forceinline__ float4 serve_widen(float4 r) { return r; }
-__device__ __forceinline__ float4 serve_widen(uint2 r) { return serve_dec16x4(r); }
 
 // Element `idx` of the packed table, whatever its format.
 __device__ __forceinline__ float serve_load_elem(const ModelDev &m, int64_t idx) {
@@ -46,141 +35,9 @@ __device__ __forceinline__ void serve_store_elem(const ModelDev &m, int64_t idx,
   else m.lat[idx] = w;
 }
 
-// Lane c of a pair's LPP lanes holds factors [4 VPL c, 4 VPL (c + 1)) of both slots, as in the fp32 kernel:
-// a vector is four factors -- 16 bytes of an fp32 slot, 8 bytes of an fp16 one.
-template <int FMT, int LPP, int VPL, int U>
-__global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void ffm_serve_wave_kernel(ModelDev m, Rows rows, Scratch s,
-                                                                       int max_row_nnz, int lds_cap, float *out,
-                                                                       int output_prob) {
-  static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
-  static_assert(LPP >= 1 && LPP <= 16 && (LPP & (LPP - 1)) == 0, "a pair's lanes sit inside one DPP row");
-  constexpr int PPS = 64 / LPP;  // pairs per step
-  static_assert(kPredTerms % (PPS * U) == 0, "a batch of terms is whole unrolled steps");
-  using Raw = typename std::conditional<FMT == SERVE_F16, uint2, float4>::type;  // four factors as stored
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int r = wave_uniform(blockIdx.x * kPredRows + wv);
-  if (r >= rows.n_rows) return;
-  int4 *E = reinterpret_cast<int4 *>(smem + static_cast<size_t>(wv) * (static_cast<size_t>(lds_cap) * 16 + kPredTerms * 4));
-  float *terms = reinterpret_cast<float *>(E + lds_cap);
-  const int b = wave_uniform(rows.row_ptr[r]);
-  const int nnz = wave_uniform(rows.row_ptr[r + 1]) - b;
-  // beyond the validated capacity -- for a serving engine also everything a wave cannot stage (create
-  // keeps max_row_nnz <= kPredLdsCap; there is no workgroup-per-row launch behind this one): flagged, NaN
-  if (nnz > max_row_nnz || nnz > lds_cap) {
-    if (lane == 0) {
-      atomicOr(s.err, ERR_ROW_TOO_LONG);
-      const float nan = __int_as_float(0x7fc00000);
-      s.loss[r] = static_cast<double>(nan);
-      if (out) out[r] = nan;
-    }
-    return;
-  }
-  const int k = m.n_factors, RL = m.row_len;
-  const Raw *const table = reinterpret_cast<const Raw *>(m.lat);
-  const int k4 = k >> 2;  // vectors per slot
-
-  // ---- entries: the survivors in row order into LDS, the linear logit as a strictly sequential prefix
-  float result = m.bias3[0];
-  int nv = 0;
-  for (int base = 0; base < nnz; base += 64) {
-    const int p = base + lane;
-    int i = 0, f = 0;
-    float x = 0.0f, lw = 0.0f;
-    bool valid = false;
-    if (p < nnz) {
-      i = rows.feat[b + p];
-      f = rows.field[b + p];
-      x = rows.val[b + p];
-      valid = i >= 0 && i < m.n_feats && f >= 0 && f < m.n_fields;
-    }
-    if (valid) lw = m.lin_w[i];
-    const unsigned long long mask = __ballot(valid);
-    if (valid) E[nv + __popcll(mask & ((1ull << lane) - 1ull))] = make_int4(i, f, __float_as_int(x), 0);
-    nv += __popcll(mask);
-    const float run = wave_sequential_prefix(result, valid ? lw * x : -0.0f);
-    result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-
-  // ---- pairs in the reference's order (a outer, b inner)
-  const int n_pairs = nv * (nv - 1) / 2;
-  const int g = lane / LPP, c = lane - g * LPP;
-  int pa = 0, pb = 1 + g;
-  if (g < n_pairs)
-    while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
-  const int64_t RL4 = RL >> 2;  // vectors per feature
-  for (int q0 = 0; q0 < n_pairs; q0 += kPredTerms) {
-    const int cnt = min(kPredTerms, n_pairs - q0);
-    for (int st = 0; st * PPS < cnt; st += U) {
-      Raw x[U][VPL], y[U][VPL];
-      float xa[U], xb[U];
-      bool ok[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const int q = q0 + (st + u) * PPS + g;
-        ok[u] = q < n_pairs;
-        const int a = ok[u] ? pa : 0, bb = ok[u] ? pb : (nv > 1 ? 1 : 0);
-        const int4 ea = E[a], eb = E[bb];
-        xa[u] = __int_as_float(ea.z);
-        xb[u] = __int_as_float(eb.z);
-        const Raw *va = table + static_cast<int64_t>(ea.x) * RL4 + eb.y * k4 + c * VPL;
-        const Raw *vb = table + static_cast<int64_t>(eb.x) * RL4 + ea.y * k4 + c * VPL;
-#pragma unroll
-        for (int v = 0; v < VPL; v++) { x[u][v] = va[v]; y[u][v] = vb[v]; }
-        if (q + PPS < n_pairs) {  // the pair PPS further on
-          pb += PPS;
-          while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        float pr[VPL][4];
-#pragma unroll
-        for (int v = 0; v < VPL; v++) {
-          const float4 xf = serve_widen(x[u][v]), yf = serve_widen(y[u][v]);
-          pr[v][0] = xf.x * yf.x;
-          pr[v][1] = xf.y * yf.y;
-          pr[v][2] = xf.z * yf.z;
-          pr[v][3] = xf.w * yf.w;
-        }
-        // stage t finalises the lanes c == t: dot = ((0 + w0*v0) + w1*v1) + ... in factor order
-        float dot = 0.0f;
-#pragma unroll
-        for (int t = 0; t < LPP; t++) {
-          float in = LPP > 1 ? pred_lane_below(dot) : 0.0f;
-          in = c == 0 ? 0.0f : in;
-#pragma unroll
-          for (int v = 0; v < VPL; v++) {
-            in = in + pr[v][0];
-            in = in + pr[v][1];
-            in = in + pr[v][2];
-            in = in + pr[v][3];
-          }
-          dot = in;
-        }
-        const float term = dot * xa[u] * xb[u];
-        if (c == LPP - 1 && ok[u]) terms[(st + u) * PPS + g] = term;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    for (int t0 = 0; t0 < cnt; t0 += 64) {
-      const float t = t0 + lane < cnt ? terms[t0 + lane] : -0.0f;
-      const float run = wave_sequential_prefix(result, t);
-      result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  }
-
-  if (lane == 0) {
-    out[r] = output_prob ? sigmoid_ref(result) : result;
-    if (rows.label) s.loss[r] = logloss_ref(rows.label[r], result);
-  }
-}
-
 // ---- one context against many candidates (include/ffm_engine.h "Scoring candidates") ---------------
 //
-// A candidate's score is ffm_serve_wave_kernel's on the row [context entries ..., candidate entries ...].  What
+// A candidate's score is ffm_row_wave_kernel's on the row [context entries ..., candidate entries ...].  What
 // every candidate of a request shares is made once per request by serve_context_kernel and read by each
 // candidate's wave in serve_candidate_kernel: the context's survivors as staged entries, the running value
 // after the bias and the context's linear terms, and the TERM of every context x context pair (the sum itself
@@ -211,14 +68,13 @@ __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void serve_context_ker
                                                                       const int *cand_req_ptr, int n_cand, CandCtx cx,
                                                                       int max_row_nnz, int lds_cap, int *err) {
   static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
-  static_assert(LPP >= 1 && LPP <= 16 && (LPP & (LPP - 1)) == 0, "a pair's lanes sit inside one DPP row");
-  constexpr int PPS = 64 / LPP;  // pairs per step
-  using Raw = typename std::conditional<FMT == SERVE_F16, uint2, float4>::type;  // four factors as stored
+  constexpr int PPS = wave_pairs_per_step<LPP, U>();
+  using Raw = typename WaveTable<FMT>::Raw;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int r = wave_uniform(blockIdx.x * kPredRows + wv);
   if (r >= n_req) return;
-  int4 *E = reinterpret_cast<int4 *>(smem) + static_cast<size_t>(wv) * lds_cap;
+  int4 *const E = wave_lds(smem, wv, lds_cap, 0).E;  // (entries only: the terms go to cx.terms)
   const int c0 = wave_uniform(cand_req_ptr[r]), c1 = wave_uniform(cand_req_ptr[r + 1]);
   for (int cc = max(c0, 0) + lane; cc < min(c1, n_cand); cc += 64) cx.cand_req[cc] = r;
   const int b = wave_uniform(ctx_ptr[r]);
@@ -230,48 +86,21 @@ __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void serve_context_ker
     }
     return;
   }
-  const int k = m.n_factors, RL = m.row_len;
-  const Raw *const table = reinterpret_cast<const Raw *>(m.lat);
-  const int k4 = k >> 2;  // vectors per slot
+  const WaveTable<FMT> table(m);
   int4 *const ent = cx.ent + static_cast<int64_t>(r) * cx.ctx_cap;
 
-  // ---- entries: as ffm_serve_wave_kernel stages a row's, and a copy for the candidates' waves
+  // ---- entries: as the row kernel stages a row's, and a copy for the candidates' waves
   float result = m.bias3[0];
   int nv = 0;
-  for (int base = 0; base < nnz; base += 64) {
-    const int p = base + lane;
-    int i = 0, f = 0;
-    float x = 0.0f, lw = 0.0f;
-    bool valid = false;
-    if (p < nnz) {
-      i = feat[b + p];
-      f = field[b + p];
-      x = val[b + p];
-      valid = i >= 0 && i < m.n_feats && f >= 0 && f < m.n_fields;
-    }
-    if (valid) lw = m.lin_w[i];
-    const unsigned long long mask = __ballot(valid);
-    if (valid) {
-      const int at = nv + __popcll(mask & ((1ull << lane) - 1ull));
-      const int4 en = make_int4(i, f, __float_as_int(x), 0);
-      E[at] = en;
-      ent[at] = en;
-    }
-    nv += __popcll(mask);
-    const float run = wave_sequential_prefix(result, valid ? lw * x : -0.0f);
-    result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
-  }
+  wave_stage_entries(m, feat, field, val, b, nnz, lane, result, nv, [&](int at, int4 en, float) { E[at] = en; ent[at] = en; });
   if (lane == 0) cx.head[r] = make_int2(nv, __float_as_int(result));
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 
-  // ---- the context x context terms in pair order (a outer, b inner), each as the row kernel computes it
+  // ---- the context x context terms in pair order, each as the row kernel computes it
   const int n_pairs = nv * (nv - 1) / 2;
   float *const T = cx.terms + static_cast<int64_t>(r) * cand_terms_stride(cx.ctx_cap);
   const int g = lane / LPP, c = lane - g * LPP;
-  int pa = 0, pb = 1 + g;
-  if (g < n_pairs)
-    while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
-  const int64_t RL4 = RL >> 2;  // vectors per feature
+  WavePairCursor cur;
+  cur.start(g, n_pairs, nv);
   for (int st = 0; st * PPS < n_pairs; st += U) {
     Raw x[U][VPL], y[U][VPL];
     float xa[U], xb[U];
@@ -280,68 +109,39 @@ __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void serve_context_ker
     for (int u = 0; u < U; u++) {
       const int q = (st + u) * PPS + g;
       ok[u] = q < n_pairs;
-      const int a = ok[u] ? pa : 0, bb = ok[u] ? pb : 1;  // (n_pairs > 0 here: entries 0 and 1 exist)
+      const int a = ok[u] ? cur.pa : 0, bb = ok[u] ? cur.pb : 1;  // (n_pairs > 0 here: entries 0 and 1 exist)
       const int4 ea = E[a], eb = E[bb];
       xa[u] = __int_as_float(ea.z);
       xb[u] = __int_as_float(eb.z);
-      const Raw *va = table + static_cast<int64_t>(ea.x) * RL4 + eb.y * k4 + c * VPL;
-      const Raw *vb = table + static_cast<int64_t>(eb.x) * RL4 + ea.y * k4 + c * VPL;
+      const Raw *va = table.slot(ea.x, eb.y) + c * VPL, *vb = table.slot(eb.x, ea.y) + c * VPL;
 #pragma unroll
       for (int v = 0; v < VPL; v++) { x[u][v] = va[v]; y[u][v] = vb[v]; }
-      if (q + PPS < n_pairs) {  // the pair PPS further on
-        pb += PPS;
-        while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
-      }
+      if (q + PPS < n_pairs) cur.advance(PPS, nv);
     }
 #pragma unroll
     for (int u = 0; u < U; u++) {
-      float pr[VPL][4];
-#pragma unroll
-      for (int v = 0; v < VPL; v++) {
-        const float4 xf = serve_widen(x[u][v]), yf = serve_widen(y[u][v]);
-        pr[v][0] = xf.x * yf.x;
-        pr[v][1] = xf.y * yf.y;
-        pr[v][2] = xf.z * yf.z;
-        pr[v][3] = xf.w * yf.w;
-      }
-      float dot = 0.0f;
-#pragma unroll
-      for (int t = 0; t < LPP; t++) {
-        float in = LPP > 1 ? pred_lane_below(dot) : 0.0f;
-        in = c == 0 ? 0.0f : in;
-#pragma unroll
-        for (int v = 0; v < VPL; v++) {
-          in = in + pr[v][0];
-          in = in + pr[v][1];
-          in = in + pr[v][2];
-          in = in + pr[v][3];
-        }
-        dot = in;
-      }
-      const float term = dot * xa[u] * xb[u];
+      const float term = wave_pair_term<LPP, VPL>(x[u], y[u], c, xa[u], xb[u]);
       if (c == LPP - 1 && ok[u]) T[(st + u) * PPS + g] = term;
     }
   }
 }
 
-// One wave per candidate, kPredRows candidates per workgroup: ffm_serve_wave_kernel on the concatenated row,
-// with the request's staged survivors copied in place of the context's entries, the linear prefix continued,
-// and the stored term loaded (4 bytes, one lane, no gathers) for every pair whose members are both context.
+// One wave per candidate, kPredRows candidates per workgroup: the row kernel on the concatenated row, with the
+// request's staged survivors copied in place of the context's entries, the linear prefix continued, and the
+// stored term loaded (4 bytes, one lane, no gathers) for every pair whose members are both context.
 template <int FMT, int LPP, int VPL, int U>
 __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void serve_candidate_kernel(ModelDev m, int n_req, const int *ctx_ptr,
                                                                         CandCtx cx, Rows rows, int max_row_nnz, int lds_cap,
                                                                         int *err, float *out, int output_prob) {
   static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
-  static_assert(LPP >= 1 && LPP <= 16 && (LPP & (LPP - 1)) == 0, "a pair's lanes sit inside one DPP row");
-  constexpr int PPS = 64 / LPP;  // pairs per step
-  static_assert(kPredTerms % (PPS * U) == 0, "a batch of terms is whole unrolled steps");
-  using Raw = typename std::conditional<FMT == SERVE_F16, uint2, float4>::type;  // four factors as stored
+  constexpr int PPS = wave_pairs_per_step<LPP, U>();
+  using Raw = typename WaveTable<FMT>::Raw;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int r = wave_uniform(blockIdx.x * kPredRows + wv);
   if (r >= rows.n_rows) return;
-  int4 *E = reinterpret_cast<int4 *>(smem + static_cast<size_t>(wv) * (static_cast<size_t>(lds_cap) * 16 + kPredTerms * 4));
-  float *terms = reinterpret_cast<float *>(E + lds_cap);
+  const WaveLds lds = wave_lds(smem, wv, lds_cap, kPredTerms);
+  int4 *const E = lds.E;
   const int b = wave_uniform(rows.row_ptr[r]);
   const int nnz = wave_uniform(rows.row_ptr[r + 1]) - b;
   const int req = wave_uniform(cx.cand_req[r]);
@@ -357,9 +157,7 @@ __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void serve_candidate_k
     }
     return;
   }
-  const int k = m.n_factors, RL = m.row_len;
-  const Raw *const table = reinterpret_cast<const Raw *>(m.lat);
-  const int k4 = k >> 2;  // vectors per slot
+  const WaveTable<FMT> table(m);
 
   // ---- entries: the request's survivors as staged, then the candidate's behind them; the linear logit goes
   // on from the context's prefix
@@ -367,34 +165,14 @@ __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void serve_candidate_k
   for (int p = lane; p < nc; p += 64) E[p] = ent[p];
   float result = __int_as_float(wave_uniform(head.y));
   int nv = nc;
-  for (int base = 0; base < nnz; base += 64) {
-    const int p = base + lane;
-    int i = 0, f = 0;
-    float x = 0.0f, lw = 0.0f;
-    bool valid = false;
-    if (p < nnz) {
-      i = rows.feat[b + p];
-      f = rows.field[b + p];
-      x = rows.val[b + p];
-      valid = i >= 0 && i < m.n_feats && f >= 0 && f < m.n_fields;
-    }
-    if (valid) lw = m.lin_w[i];
-    const unsigned long long mask = __ballot(valid);
-    if (valid) E[nv + __popcll(mask & ((1ull << lane) - 1ull))] = make_int4(i, f, __float_as_int(x), 0);
-    nv += __popcll(mask);
-    const float run = wave_sequential_prefix(result, valid ? lw * x : -0.0f);
-    result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  wave_stage_entries(m, rows.feat, rows.field, rows.val, b, nnz, lane, result, nv, [&](int at, int4 en, float) { E[at] = en; });
 
-  // ---- pairs in the reference's order (a outer, b inner) over the concatenated survivors
+  // ---- pairs over the concatenated survivors
   const int n_pairs = nv * (nv - 1) / 2;
   const float *const T = cx.terms + static_cast<int64_t>(req) * cand_terms_stride(cx.ctx_cap);
   const int g = lane / LPP, c = lane - g * LPP;
-  int pa = 0, pb = 1 + g;
-  if (g < n_pairs)
-    while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
-  const int64_t RL4 = RL >> 2;  // vectors per feature
+  WavePairCursor cur;
+  cur.start(g, n_pairs, nv);
   for (int q0 = 0; q0 < n_pairs; q0 += kPredTerms) {
     const int cnt = min(kPredTerms, n_pairs - q0);
     for (int st = 0; st * PPS < cnt; st += U) {
@@ -405,7 +183,7 @@ __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void serve_candidate_k
       for (int u = 0; u < U; u++) {
         const int q = q0 + (st + u) * PPS + g;
         ok[u] = q < n_pairs;
-        const int a = ok[u] ? pa : 0, bb = ok[u] ? pb : (nv > 1 ? 1 : 0);
+        const int a = ok[u] ? cur.pa : 0, bb = ok[u] ? cur.pb : (nv > 1 ? 1 : 0);
         shared[u] = ok[u] && bb < nc;  // (a < bb: both members are the context's)
         const int4 ea = E[a], eb = E[bb];
         xa[u] = __int_as_float(ea.z);
@@ -416,52 +194,20 @@ __global__ __launch_bounds__(64 * kPredRows) FFM_PRED_OCC void serve_candidate_k
         if (shared[u]) {
           if (c == LPP - 1) kept[u] = T[a * nc - a * (a + 1) / 2 + (bb - a - 1)];
         } else if (ok[u]) {
-          const Raw *va = table + static_cast<int64_t>(ea.x) * RL4 + eb.y * k4 + c * VPL;
-          const Raw *vb = table + static_cast<int64_t>(eb.x) * RL4 + ea.y * k4 + c * VPL;
+          const Raw *va = table.slot(ea.x, eb.y) + c * VPL, *vb = table.slot(eb.x, ea.y) + c * VPL;
 #pragma unroll
           for (int v = 0; v < VPL; v++) { x[u][v] = va[v]; y[u][v] = vb[v]; }
         }
-        if (q + PPS < n_pairs) {  // the pair PPS further on
-          pb += PPS;
-          while (pb >= nv) { pb = pb - nv + pa + 2; pa++; }
-        }
+        if (q + PPS < n_pairs) cur.advance(PPS, nv);
       }
 #pragma unroll
       for (int u = 0; u < U; u++) {
-        float pr[VPL][4];
-#pragma unroll
-        for (int v = 0; v < VPL; v++) {
-          const float4 xf = serve_widen(x[u][v]), yf = serve_widen(y[u][v]);
-          pr[v][0] = xf.x * yf.x;
-          pr[v][1] = xf.y * yf.y;
-          pr[v][2] = xf.z * yf.z;
-          pr[v][3] = xf.w * yf.w;
-        }
-        // stage t finalises the lanes c == t: dot = ((0 + w0*v0) + w1*v1) + ... in factor order
-        float dot = 0.0f;
-#pragma unroll
-        for (int t = 0; t < LPP; t++) {
-          float in = LPP > 1 ? pred_lane_below(dot) : 0.0f;
-          in = c == 0 ? 0.0f : in;
-#pragma unroll
-          for (int v = 0; v < VPL; v++) {
-            in = in + pr[v][0];
-            in = in + pr[v][1];
-            in = in + pr[v][2];
-            in = in + pr[v][3];
-          }
-          dot = in;
-        }
-        const float term = dot * xa[u] * xb[u];
-        if (c == LPP - 1 && ok[u]) terms[(st + u) * PPS + g] = shared[u] ? kept[u] : term;
+        const float term = wave_pair_term<LPP, VPL>(x[u], y[u], c, xa[u], xb[u]);
+        if (c == LPP - 1 && ok[u]) lds.terms[(st + u) * PPS + g] = shared[u] ? kept[u] : term;
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    for (int t0 = 0; t0 < cnt; t0 += 64) {
-      const float t = t0 + lane < cnt ? terms[t0 + lane] : -0.0f;
-      const float run = wave_sequential_prefix(result, t);
-      result = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(run), 63));
-    }
+    result = wave_ordered_sum(result, lds.terms, cnt, lane);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   }
 

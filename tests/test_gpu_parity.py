@@ -197,7 +197,7 @@ def test_ragged_empty_and_multivalued_rows():
 @pytest.mark.parametrize("k", [4, 8, 16, 32, 64, 12])
 def test_evaluation_rows_one_wave_each(k, monkeypatch):
     """FFM predict (ffm.cpp:24-70 with the stored w; evaluate.cpp:23-33): the wave-per-row kernel
-    (kernels_predict.h; k = 12 keeps the workgroup-per-row kernel) against the oracle and against
+    (kernels_wave.h; k = 12 keeps the workgroup-per-row kernel) against the oracle and against
     the workgroup-per-row kernel, bitwise -- rows longer than a wave (up to 150 entries, several
     per field), empty and one-entry rows, entries outside the feature / field range, logits,
     probabilities and the logloss sum."""

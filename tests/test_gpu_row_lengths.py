@@ -1,5 +1,5 @@
 """Every row kernel against the oracle on a ladder of row lengths (util.ROW_LENGTHS: each entry count
-at which fm_row_wave_kernel, fm_row_kernel, ffm_row_kernel or ffm_predict_wave_kernel changes path,
+at which fm_row_wave_kernel, fm_row_kernel, ffm_row_kernel or ffm_row_wave_kernel changes path,
 with its neighbours), in blocks built by util.row_length_block: empty rows first and last, once-only
 and repeated features at every position of a row, out-of-range entries in a parked position, in a
 chunk and on both sides of the 64-entry pass boundary, an id twice in a long row, FFM rows with

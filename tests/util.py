@@ -268,7 +268,7 @@ def irregular_copy(blk, seed=0, n_reversed=64):
 # 13 (4 + 8: a whole chunk | one entry of the next), 11, 20 (partial and whole chunks; the lengths the
 # older suites use) | 31, 32, 33 (half a wave of entries) | 63, 64, 65, 66 (fm_row_wave_kernel: the
 # linear part runs lane = entry, 64 per pass -- a later pass reads lin_n / lin_z / lin_w back;
-# ffm_predict_wave_kernel: staging passes of 64 entries, the survivors compacted across them;
+# ffm_row_wave_kernel: staging passes of 64 entries, the survivors compacted across them;
 # ffm_row_kernel: 64 entries are 2016 pairs, one pass under kTermsCap = 2048, 65 are 2080, two) | 71,
 # 72 (where the older suites' long rows begin) | 91, 92 (ffm_row_kernel: 4095 pairs, two passes | 4186,
 # three) | 127, 128, 129, 130 (kPredLdsCap = 128: a longer row is the second predict launch's, and a
