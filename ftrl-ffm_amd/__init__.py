@@ -6,7 +6,8 @@ from . import build as _build
 from .engine import (ABI, FFM, FM, LR, METRIC_BINS, METRIC_EVAL, METRIC_TRAIN, Config, Engine,  # noqa: F401
                      EngineError, FieldSketch, Group, KeyedMetrics, LIB_PATH, Metrics, default_batch_ramp, hash_ids, init_weights_host,
                      keyed_auc_reference, metrics_from_keyed,
-                     load_library, metrics_from_histogram, page_aligned, shard_plan, sketch_estimate, field_ranges, spell_out_candidates, drop_field)
+                     load_library, metrics_from_histogram, page_aligned, shard_plan, sketch_estimate, field_ranges, spell_out_candidates, drop_field,
+                     IdCounter, RARE_ID, fold_rare, rare_slot)
 
 
 def build(force=False, verbose=False):

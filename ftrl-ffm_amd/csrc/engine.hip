@@ -54,6 +54,7 @@
 #include "kernels_ablate.h"
 #include "kernels_stage.h"
 #include "kernels_sketch.h"
+#include "kernels_idcount.h"
 #include "metrics_host.h"
 
 using namespace ftrl_dev;
@@ -404,6 +405,9 @@ struct ffm_engine {
   bool hash_ids = false;
   ftrl_hash::Map hm{};
   int *d_hash_start = nullptr;
+  // ffm_engine_set_rare_fold (engine_idcount.h): the keep-map in HBM (its own allocation, freed when the fold is
+  // turned off or the engine destroyed) and its shift; words == nullptr: no fold, and nothing here is read
+  ftrl_hash::Rare rare{};
   // ffm_engine_refresh_weights (engine_refresh.h): its six counters and its grid, both made by the first call
   unsigned long long *d_refresh = nullptr;
   int refresh_grid = 0;
@@ -702,6 +706,7 @@ void ffm_engine_destroy(ffm_engine *e) {
     if (sl.ev_trained) (void)hipEventDestroy(sl.ev_trained);
   }
   for (void *p : e->allocs) (void)hipFree(p);
+  if (e->rare.words) (void)hipFree(const_cast<uint64_t *>(e->rare.words));
   for (int i = 0; i < ffm_engine::kSets; i++) {
     if (e->ev_grouped[i]) (void)hipEventDestroy(e->ev_grouped[i]);
     if (e->ev_set_free[i]) (void)hipEventDestroy(e->ev_set_free[i]);
@@ -833,6 +838,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_metrics.h"
 #include "engine_keyed.h"
 #include "engine_sketch.h"
+#include "engine_idcount.h"
 #include "engine_ablate.h"
 }  // extern "C"
 

@@ -25,8 +25,12 @@ static void launch_hash_ids(ffm_engine *e, hipStream_t st, int32_t nnz, const in
   const uintptr_t bits = reinterpret_cast<uintptr_t>(field) | reinterpret_cast<uintptr_t>(feat_in) | reinterpret_cast<uintptr_t>(feat_out);
   const int vec = (bits & 15u) == 0 ? 1 : 0;
   const int lanes = vec ? cdiv(nnz, 4) : nnz;
-  hipLaunchKernelGGL(hash_ids_kernel, dim3(std::max(1, std::min(1024, cdiv(lanes, 256)))), dim3(256), 0, st, e->hm,
-                     static_cast<unsigned>(nnz), field, feat_in, feat_out, vec);
+  if (e->rare.words)  // (ffm_engine_set_rare_fold: the folding kernel, kernels_idcount.h)
+    hipLaunchKernelGGL(hash_ids_rare_kernel, dim3(std::max(1, std::min(1024, cdiv(lanes, 256)))), dim3(256), 0, st, e->hm, e->rare,
+                       static_cast<unsigned>(nnz), field, feat_in, feat_out, vec);
+  else
+    hipLaunchKernelGGL(hash_ids_kernel, dim3(std::max(1, std::min(1024, cdiv(lanes, 256)))), dim3(256), 0, st, e->hm,
+                       static_cast<unsigned>(nnz), field, feat_in, feat_out, vec);
 }
 
 // For callers of the _device entry points, which take ids as they are: the engine's mapping applied to a

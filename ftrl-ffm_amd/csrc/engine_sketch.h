@@ -11,6 +11,7 @@ struct ffm_sketch {
   // pageable callers' entries go through one of two page-locked images: feat, then field, each padded to 16 bytes
   struct Stage { char *pinned = nullptr; size_t cap = 0; hipEvent_t ev_read = nullptr; bool used = false; } stage[2];
   int stage_next = 0;
+  ftrl_hash::Rare filter{};  // ffm_engine_sketch_set_filter: the keep-map in HBM (the sketch's own copy) or none
 };
 
 // Entries per launch of a call from host memory: a multiple of 4 (the kernel's `first`), 32 MB of staging at the most.
@@ -26,6 +27,7 @@ void ffm_engine_sketch_destroy(ffm_sketch *s) {
   }
   if (s->d_reg) (void)hipFree(s->d_reg);
   if (s->d_cnt) (void)hipFree(s->d_cnt);
+  if (s->filter.words) (void)hipFree(const_cast<uint64_t *>(s->filter.words));
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -74,12 +76,47 @@ static void launch_sketch(ffm_sketch *s, int32_t nnz, const int32_t *field, cons
   const int lanes = vec ? cdiv(nnz, 4) : nnz;
   const int grid = pcie ? 24 : std::max(1, std::min(1024, cdiv(lanes, 256)));
   const unsigned F = static_cast<unsigned>(s->n_fields);
-  if (field)
-    hipLaunchKernelGGL((field_sketch_kernel<true>), dim3(grid), dim3(256), 0, s->stream, static_cast<unsigned>(nnz), field, feat,
+  if (s->filter.words) {
+    if (field)
+      hipLaunchKernelGGL((field_sketch_kernel<true, true, ftrl_hash::Rare>), dim3(grid), dim3(256), 0, s->stream,
+                         static_cast<unsigned>(nnz), field, feat, first, F, vec, s->d_reg, s->d_cnt, s->filter);
+    else
+      hipLaunchKernelGGL((field_sketch_kernel<false, true, ftrl_hash::Rare>), dim3(grid), dim3(256), 0, s->stream,
+                         static_cast<unsigned>(nnz), field, feat, first, F, vec, s->d_reg, s->d_cnt, s->filter);
+  } else if (field)
+    hipLaunchKernelGGL((field_sketch_kernel<true, false>), dim3(grid), dim3(256), 0, s->stream, static_cast<unsigned>(nnz), field, feat,
                        first, F, vec, s->d_reg, s->d_cnt);
   else
-    hipLaunchKernelGGL((field_sketch_kernel<false>), dim3(grid), dim3(256), 0, s->stream, static_cast<unsigned>(nnz), field, feat,
+    hipLaunchKernelGGL((field_sketch_kernel<false, false>), dim3(grid), dim3(256), 0, s->stream, static_cast<unsigned>(nnz), field, feat,
                        first, F, vec, s->d_reg, s->d_cnt);
+}
+
+// A keep-map of 2^bits slots from host memory into an allocation of its own on the current device (engine_idcount.h
+// makes such maps; an engine and a sketch each hold their copy).
+static int rare_map_upload(int32_t bits, const uint64_t *words, ftrl_hash::Rare *out) {
+  const size_t bytes = (static_cast<size_t>(1) << bits) / 8;
+  uint64_t *d = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), bytes));
+  const hipError_t err = hipMemcpy(d, words, bytes, hipMemcpyHostToDevice);
+  if (err != hipSuccess) {
+    (void)hipFree(d);
+    HIP_TRY(err);
+  }
+  *out = ftrl_hash::Rare{d, 32u - static_cast<uint32_t>(bits)};
+  return FFM_OK;
+}
+
+int ffm_engine_sketch_set_filter(ffm_sketch *s, int32_t bits, const uint64_t *words) {
+  if (!s) return fail(FFM_E_INVALID, "null sketch");
+  if (words && (bits < 8 || bits > 30)) return fail(FFM_E_INVALID, "bits must lie in [8, 30]");
+  HIP_TRY(hipSetDevice(s->device_id));
+  HIP_TRY(hipStreamSynchronize(s->stream));  // (launches behind earlier adds still read the map they were given)
+  ftrl_hash::Rare next{};
+  if (words)
+    if (int rc = rare_map_upload(bits, words, &next)) return rc;
+  if (s->filter.words) (void)hipFree(const_cast<uint64_t *>(s->filter.words));
+  s->filter = next;
+  return FFM_OK;
 }
 
 static int sketch_args(ffm_sketch *s, int32_t nnz, const int32_t *feat) {

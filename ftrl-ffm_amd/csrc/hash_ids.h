@@ -59,6 +59,30 @@ FTRL_HASH_HD int32_t hash_entry(const Map &m, int32_t field, int32_t feat) {
   return hash_into(field, feat, lo, static_cast<uint32_t>(m.start[field + 1] - lo));
 }
 
+// Rare ids (include/ffm_engine.h "Rare ids"): a keep-map of 2^bits slots, bit j of word i = slot 64 i + j, and
+// shift = 32 - bits.  An entry's slot is the top `bits` of its hashed bits.  Beside Map, never inside it: the
+// kernels of an engine without a map take the Map they always took.
+constexpr int32_t kRareId = 0x7fffffff;  // FFM_RARE_ID
+struct Rare {
+  const uint64_t *words;
+  uint32_t shift;
+};
+FTRL_HASH_HD bool rare_kept(const Rare &r, int32_t field, int32_t feat) {
+  const uint32_t slot = hash_bits(field, feat) >> r.shift;
+  return (r.words[slot >> 6] >> (slot & 63u)) & 1u;
+}
+// The raw id the hash then takes: kRareId for a counting entry (feat >= 0 and, for FFM, 0 <= field < n_fields;
+// LR / FM: field taken as 0) whose slot's bit is 0, feat for every other entry.
+FTRL_HASH_HD int32_t fold_entry(bool ffm, int32_t n_fields, const Rare &r, int32_t field, int32_t feat) {
+  if (feat < 0) return feat;
+  if (!ffm) field = 0;
+  else if (static_cast<uint32_t>(field) >= static_cast<uint32_t>(n_fields)) return feat;
+  return rare_kept(r, field, feat) ? feat : kRareId;
+}
+FTRL_HASH_HD int32_t hash_entry_rare(const Map &m, const Rare &r, int32_t field, int32_t feat) {
+  return hash_entry(m, field, fold_entry(m.ffm != 0, m.n_fields, r, field, feat));
+}
+
 #if defined(__HIPCC__)
 // Four entries at a time, for the kernels that carry them as 16-byte vectors (hash_ids_kernel, the upload kernel).
 // The fields of entries 4i .. 4i + 3 of a block handed over without a field array: one entry per field in
@@ -69,6 +93,10 @@ __device__ __forceinline__ int4 hash_implicit_fields4(unsigned i, unsigned F) {
 }
 __device__ __forceinline__ int4 hash_entries4(const Map &hm, const int4 fl, const int4 ft) {
   return make_int4(hash_entry(hm, fl.x, ft.x), hash_entry(hm, fl.y, ft.y), hash_entry(hm, fl.z, ft.z), hash_entry(hm, fl.w, ft.w));
+}
+__device__ __forceinline__ int4 hash_entries4_rare(const Map &hm, const Rare &r, const int4 fl, const int4 ft) {
+  return make_int4(hash_entry_rare(hm, r, fl.x, ft.x), hash_entry_rare(hm, r, fl.y, ft.y), hash_entry_rare(hm, r, fl.z, ft.z),
+                   hash_entry_rare(hm, r, fl.w, ft.w));
 }
 #endif
 

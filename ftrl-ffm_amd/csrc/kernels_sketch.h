@@ -32,9 +32,18 @@ __device__ __forceinline__ bool sketch_entry(unsigned F, int field, int feat, un
 // Entries [0, nnz) of a call.  field / feat: device-visible; vec != 0: both are 16-byte aligned.  HAS_FIELD ==
 // false: entry p of the call is field (first + p) mod F, first a multiple of 4 (a call cut into chunks).
 // counters: n_valid, n_bad.  Every loop is wave-uniform (a lane past the end idles): the ballots see whole waves.
-template <bool HAS_FIELD>
+// FILTERED (ffm_engine_sketch_set_filter): one more argument, the keep-map of "Rare ids" -- an entry whose bit
+// there is 0 counts as the one id kRareId of its field (ftrl_hash::fold_entry).  An instantiation of its own:
+// the unfiltered kernel keeps its arguments and its instructions.
+template <bool HAS_FIELD, bool FILTERED, typename... Filter>
 __global__ __launch_bounds__(256) void field_sketch_kernel(unsigned nnz, const int *field, const int *feat, unsigned first,
-                                                           unsigned F, int vec, unsigned *reg, unsigned long long *counters) {
+                                                           unsigned F, int vec, unsigned *reg, unsigned long long *counters,
+                                                           Filter... filter) {
+  static_assert(sizeof...(Filter) == (FILTERED ? 1 : 0), "Filter: nothing, or <ftrl_hash::Rare>");
+  const auto sketch_entry = [&](unsigned F_, int fld, int ft, unsigned *reg_) {
+    if constexpr (FILTERED) ft = ftrl_hash::fold_entry(true, static_cast<int>(F_), filter..., fld, ft);
+    return ftrl_dev::sketch_entry(F_, fld, ft, reg_);
+  };
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // (a refilled page-locked buffer: pull_block_kernel's reason)
   const unsigned lane = threadIdx.x & 63u;
   const unsigned wave0 = blockIdx.x * blockDim.x + threadIdx.x - lane, stride = gridDim.x * blockDim.x;

@@ -40,13 +40,17 @@ struct PullHashJob {
   ftrl_hash::Map hm;
   const char *isrc, *fsrc; char *idst, *fdst; unsigned hbytes;
 };
+// A flagged engine with a keep-map (include/ffm_engine.h "Rare ids"): the hashed loop folds every entry by the
+// map before it hashes it (ftrl_hash::hash_entry_rare).  The map and its shift stand behind the hashed job, so
+// an engine without a map hands over the PullHashJob it always did.
+struct PullRareJob { PullHashJob h; ftrl_hash::Rare rare; };
 
 // What an instantiation takes: the smallest of the three jobs that holds its parts.  Every variant is a
 // kernel of its own -- an instantiation, not a run-time branch -- so that a block without weights, on an
 // unflagged engine, with its values is uploaded by the launch, the argument and the kernel it always was
 // (profiles/sample_weights.md, profiles/implicit_ones.md).
-template <bool WEIGHTED, bool HASHED>
-using PullArg = std::conditional_t<HASHED, PullHashJob, std::conditional_t<WEIGHTED, PullWeightedJob, PullJob>>;
+template <bool WEIGHTED, bool HASHED, bool RARE>
+using PullArg = std::conditional_t<RARE, PullRareJob, std::conditional_t<HASHED, PullHashJob, std::conditional_t<WEIGHTED, PullWeightedJob, PullJob>>>;
 
 // Ones: nothing, or <float *, unsigned> = the slot's val array and the number of 1.0f to write there.
 // The parts in order: the five arrays, the weights, the hashed loop, the ones, a missing field array, the ticket.
@@ -55,11 +59,13 @@ using PullArg = std::conditional_t<HASHED, PullHashJob, std::conditional_t<WEIGH
 // registers but not its instruction count), and so is the job when a function hands out its inner parts by
 // reference -- hence the two pointers picked by `if constexpr`.  As it stands every instantiation compiles to
 // the instructions of the kernel it replaces.
-template <bool WEIGHTED, bool HASHED, typename... Ones>
-__global__ __launch_bounds__(256) void pull_block_kernel(PullArg<WEIGHTED, HASHED> arg, Ones... ones) {
+// RARE (with HASHED only): the hashed loop below runs on the job's hashed part and folds by the job's map.
+template <bool WEIGHTED, bool HASHED, bool RARE, typename... Ones>
+__global__ __launch_bounds__(256) void pull_block_kernel(PullArg<WEIGHTED, HASHED, RARE> arg, Ones... ones) {
   static_assert(sizeof...(Ones) == 0 || sizeof...(Ones) == 2, "Ones: nothing, or <float *, unsigned>");
+  static_assert(HASHED || !RARE, "RARE: a variant of the hashed loop");
   const PullJob *block;
-  if constexpr (HASHED) block = &arg.w.block; else if constexpr (WEIGHTED) block = &arg.block; else block = &arg;
+  if constexpr (RARE) block = &arg.h.w.block; else if constexpr (HASHED) block = &arg.w.block; else if constexpr (WEIGHTED) block = &arg.block; else block = &arg;
   const PullJob &job = *block;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
   const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
@@ -76,7 +82,7 @@ __global__ __launch_bounds__(256) void pull_block_kernel(PullArg<WEIGHTED, HASHE
   }
   if constexpr (WEIGHTED) {
     const PullWeightedJob *weights;
-    if constexpr (HASHED) weights = &arg.w; else weights = &arg;
+    if constexpr (RARE) weights = &arg.h.w; else if constexpr (HASHED) weights = &arg.w; else weights = &arg;
     const PullWeightedJob &wj = *weights;
     const unsigned n16 = wj.wbytes >> 4;
     const int4 *s = reinterpret_cast<const int4 *>(wj.wsrc);
@@ -86,7 +92,7 @@ __global__ __launch_bounds__(256) void pull_block_kernel(PullArg<WEIGHTED, HASHE
     if (tid < (tail >> 2))
       reinterpret_cast<int *>(wj.wdst)[(n16 << 2) + tid] = reinterpret_cast<const int *>(wj.wsrc)[(n16 << 2) + tid];
   }
-  if constexpr (HASHED) {
+  if constexpr (HASHED && !RARE) {
     const unsigned n16 = arg.hbytes >> 4, F = static_cast<unsigned>(arg.hm.n_fields);
     for (unsigned i = tid; i < n16; i += stride) {
       const int4 ft = reinterpret_cast<const int4 *>(arg.isrc)[i];
@@ -105,6 +111,31 @@ __global__ __launch_bounds__(256) void pull_block_kernel(PullArg<WEIGHTED, HASHE
         reinterpret_cast<int *>(arg.fdst)[p] = f;
       }
       reinterpret_cast<int *>(arg.idst)[p] = ftrl_hash::hash_entry(arg.hm, f, reinterpret_cast<const int *>(arg.isrc)[p]);
+    }
+  }
+  // (the hashed loop once more, folding.  Its own text: as ONE loop that picks the job's hashed part and the entry
+  // function by `if constexpr`, the two unweighted hashed instantiations above came out two instructions longer than
+  // the kernels they replace -- the effect the comment ahead of the kernel describes)
+  if constexpr (RARE) {
+    const PullHashJob &hj = arg.h;
+    const unsigned n16 = hj.hbytes >> 4, F = static_cast<unsigned>(hj.hm.n_fields);
+    for (unsigned i = tid; i < n16; i += stride) {
+      const int4 ft = reinterpret_cast<const int4 *>(hj.isrc)[i];
+      int4 fl;
+      if (hj.fsrc) {
+        fl = reinterpret_cast<const int4 *>(hj.fsrc)[i];
+        reinterpret_cast<int4 *>(hj.fdst)[i] = fl;
+      } else fl = hj.hm.ffm ? ftrl_hash::hash_implicit_fields4(i, F) : make_int4(0, 0, 0, 0);
+      reinterpret_cast<int4 *>(hj.idst)[i] = ftrl_hash::hash_entries4_rare(hj.hm, arg.rare, fl, ft);
+    }
+    if (tid < ((hj.hbytes & 15u) >> 2)) {
+      const unsigned p = (n16 << 2) + tid;
+      int f = hj.hm.ffm ? static_cast<int>(p % F) : 0;
+      if (hj.fsrc) {
+        f = reinterpret_cast<const int *>(hj.fsrc)[p];
+        reinterpret_cast<int *>(hj.fdst)[p] = f;
+      }
+      reinterpret_cast<int *>(hj.idst)[p] = ftrl_hash::hash_entry_rare(hj.hm, arg.rare, f, reinterpret_cast<const int *>(hj.isrc)[p]);
     }
   }
   // A block handed over without values (val == NULL: every value is 1.0f, include/ffm_engine.h "Rows without

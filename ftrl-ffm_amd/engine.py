@@ -224,6 +224,19 @@ ABI = [
     ("ffm_engine_sketch_destroy", None, [_vp]),
     ("ffm_engine_sketch_estimate", ctypes.c_int, [_vp, ctypes.c_int32, _f64p]),
     ("ffm_engine_field_ranges", ctypes.c_int, [_i64p, ctypes.c_int32, ctypes.c_int32, _i32p]),
+    # ids seen fewer than T times share one id per field (include/ffm_engine.h "Rare ids")
+    ("ffm_engine_idcount_create", ctypes.c_int,
+     [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
+    ("ffm_engine_idcount_add", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32]),
+    ("ffm_engine_idcount_add_device", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp]),
+    ("ffm_engine_idcount_read", ctypes.c_int, [_vp, _vp, _i64p, _i64p]),
+    ("ffm_engine_idcount_keep", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _i64p, _i64p]),
+    ("ffm_engine_idcount_destroy", None, [_vp]),
+    ("ffm_engine_set_rare_fold", ctypes.c_int, [_vp, ctypes.c_int32, _vp]),
+    ("ffm_engine_sketch_set_filter", ctypes.c_int, [_vp, ctypes.c_int32, _vp]),
+    ("ffm_engine_fold_ids_host", ctypes.c_int,
+     [ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, _i32p, _i32p, _i32p]),
+    ("ffm_engine_rare_slots_host", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, _vp]),
     # the loss and AUC of the model without each field, in one pass (include/ffm_engine.h "Field ablation")
     ("ffm_engine_ablation_enable", ctypes.c_int, [_vp, ctypes.c_int32]),
     ("ffm_engine_predict_ablated", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [ctypes.c_int32, _f32p, _f64p]),
@@ -237,6 +250,7 @@ ABI = [
     ("ffm_engine_set_rows_raw", ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p, _vp]),
 ]
 SKETCH_REGS = 16384  # FFM_SKETCH_REGS
+RARE_ID = 2 ** 31 - 1  # FFM_RARE_ID
 
 _lib = None
 
@@ -377,6 +391,49 @@ def hash_ids(field, feat, n_feats, field_start=None, model="ffm", n_fields=None)
         raise ValueError("field and feat must be equally long")
     out = np.empty_like(feat)
     rc = lib.ffm_engine_hash_ids_host(mt, int(n_feats), int(n_fields), _i(fs), feat.size, _i(fld), _i(feat), _i(out))
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
+    return out
+
+
+def _rare_words(bits, words):
+    """A keep-map as the library takes it: uint64 [2^bits / 64], contiguous."""
+    bits = int(bits)
+    if not 8 <= bits <= 30:
+        raise ValueError("bits must lie in [8, 30]")
+    words = np.ascontiguousarray(words, np.uint64)
+    if words.shape != ((1 << bits) // 64,):
+        raise ValueError("words: uint64 [2^bits / 64] = [%d]" % ((1 << bits) // 64))
+    return bits, words
+
+
+def rare_slot(field, feat, bits):
+    """The slot of every entry (uint32): the top `bits` of its hashed bits, what an IdCounter counts and a
+    keep-map tests (ffm_engine_rare_slots_host: no device).  field None: LR / FM, the field is taken as 0."""
+    lib = load_library()
+    feat = np.ascontiguousarray(feat, np.int32)
+    fld = None if field is None else np.ascontiguousarray(field, np.int32)
+    if fld is not None and fld.shape != feat.shape:
+        raise ValueError("field and feat must be equally long")
+    out = np.zeros(feat.shape, np.uint32)
+    rc = lib.ffm_engine_rare_slots_host(int(bits), feat.size, _i(fld), _i(feat), out.ctypes.data)
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
+    return out
+
+
+def fold_rare(field, feat, n_fields, bits, words):
+    """The raw ids an engine with the keep-map `words` hashes (ffm_engine_fold_ids_host: the device's bits, no
+    device): RARE_ID where a counting entry's bit is 0, feat elsewhere.  n_fields 0: LR / FM (field ignored);
+    field None with n_fields > 0: entry p is field p mod n_fields.  hash_ids of the result gives the model ids."""
+    lib = load_library()
+    bits, words = _rare_words(bits, words)
+    feat = np.ascontiguousarray(feat, np.int32)
+    fld = None if field is None or int(n_fields) == 0 else np.ascontiguousarray(field, np.int32)
+    if fld is not None and fld.shape != feat.shape:
+        raise ValueError("field and feat must be equally long")
+    out = np.empty_like(feat)
+    rc = lib.ffm_engine_fold_ids_host(int(n_fields), bits, words.ctypes.data, feat.size, _i(fld), _i(feat), _i(out))
     if rc != 0:
         raise EngineError(rc, lib.ffm_engine_last_error().decode())
     return out
@@ -945,6 +1002,15 @@ class Engine:
         engine's stream."""
         self._check(self.lib.ffm_engine_hash_ids_device(self.h, int(nnz), field, feat_in, feat_out))
 
+    def set_rare_fold(self, bits=None, words=None):
+        """Folds rare ids in every block handed over from now on (include/ffm_engine.h "Rare ids"): words = a
+        keep-map of 2^bits slots (IdCounter.keep); None turns the fold off.  hash_ids=True engines only, idle."""
+        if words is None:
+            self._check(self.lib.ffm_engine_set_rare_fold(self.h, 0, None))
+            return
+        bits, words = _rare_words(bits, words)
+        self._check(self.lib.ffm_engine_set_rare_fold(self.h, bits, words.ctypes.data))
+
     def prepare_device(self, n_rows, nnz, row_ptr, field, feat, val):
         """Look-ahead: group the next block on a side stream (see include/ffm_engine.h)."""
         self._check(self.lib.ffm_engine_prepare_device(self.h, n_rows, nnz, row_ptr, field, feat, val))
@@ -1145,9 +1211,75 @@ class FieldSketch:
         """Distinct ids per field, float64 [n_fields]."""
         return sketch_estimate(self.read()[0])
 
+    def set_filter(self, bits=None, words=None):
+        """From now on an entry whose bit in the keep-map `words` (2^bits slots) is 0 counts as the one id RARE_ID
+        of its field (include/ffm_engine.h "Rare ids"); None turns the filter off."""
+        if words is None:
+            self._check(self.lib.ffm_engine_sketch_set_filter(self.h, 0, None))
+            return
+        bits, words = _rare_words(bits, words)
+        self._check(self.lib.ffm_engine_sketch_set_filter(self.h, bits, words.ctypes.data))
+
     def close(self):
         if self.h:
             self.lib.ffm_engine_sketch_destroy(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IdCounter:
+    """How often every hashed slot occurs, counted on the device up to a cap (include/ffm_engine.h "Rare ids"),
+    and the keep-map of a minimum count.  n_fields 0: LR / FM.  Needs no engine."""
+
+    def __init__(self, n_fields, bits, cap, device=0):
+        self.lib = load_library()
+        self.h = _vp()
+        self.n_fields, self.bits, self.cap = int(n_fields), int(bits), int(cap)
+        self._check(self.lib.ffm_engine_idcount_create(self.n_fields, self.bits, self.cap, int(device),
+                                                       ctypes.byref(self.h)))
+
+    def _check(self, rc):
+        if rc != 0:
+            raise EngineError(rc, self.lib.ffm_engine_last_error().decode())
+
+    def add(self, field, feat, zero_copy=False):
+        """Counts the entries (field[p], feat[p]); field None: LR / FM, or entry p is field p mod n_fields.
+        zero_copy: page-locked (ffm_engine_pin_host) int32 arrays, read in place.  Back once they may be reused."""
+        feat = FieldSketch._ids(feat, "feat")
+        field = FieldSketch._ids(field, "field")
+        if field is not None and field.size != feat.size:
+            raise ValueError("field and feat must be equally long")
+        self._check(self.lib.ffm_engine_idcount_add(self.h, feat.size, None if field is None else field.ctypes.data,
+                                                    feat.ctypes.data, int(bool(zero_copy))))
+
+    def add_device(self, nnz, field, feat):
+        """The same for int32 arrays in device memory (addresses; field may be None); asynchronous."""
+        self._check(self.lib.ffm_engine_idcount_add_device(self.h, int(nnz), field, feat))
+
+    def read(self):
+        """(counts uint32 [2^bits] = min(count, cap), n_valid, n_bad) after everything added so far."""
+        counts = np.zeros(1 << self.bits, np.uint32)
+        nv, nb = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self.lib.ffm_engine_idcount_read(self.h, counts.ctypes.data, ctypes.byref(nv), ctypes.byref(nb)))
+        return counts, int(nv.value), int(nb.value)
+
+    def keep(self, min_count):
+        """(words uint64 [2^bits / 64], n_kept_slots, n_folded_entries): bit j of word i is set iff slot 64 i + j
+        was counted at least min_count times; 1 <= min_count <= cap."""
+        words = np.zeros((1 << self.bits) // 64, np.uint64)
+        nk, nf = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self.lib.ffm_engine_idcount_keep(self.h, int(min_count), words.ctypes.data, ctypes.byref(nk),
+                                                     ctypes.byref(nf)))
+        return words, int(nk.value), int(nf.value)
+
+    def close(self):
+        if self.h:
+            self.lib.ffm_engine_idcount_destroy(self.h)
             self.h = _vp()
 
     def __del__(self):

@@ -129,7 +129,21 @@ const std::string_view cmd_help =
     "--apply_deltas <prefix[:N]>: with --serve_weights <fmt> --n_epochs 0: a fresh serving engine takes <prefix>.1.delta,\n"
     "              <prefix>.2.delta .. up to N (default: every consecutive file that exists; at least one must), prints\n"
     "              `applied D deltas: M features, B bytes`, then evaluates or scores as --resume_from ck --n_epochs 0 does.\n"
-    "              Not with --resume_from, --n_epochs > 0 or a --serve_weights other than the files' format\tdefault:(none)\n";
+    "              Not with --resume_from, --n_epochs > 0 or a --serve_weights other than the files' format\tdefault:(none)\n"
+    "--min_count <T>: ids seen fewer than T times in --train_data share one \"rare\" id per field (libffm's Criteo recipe\n"
+    "              used 10).  --train_data is streamed once before a model exists and the device counts every id's hashed\n"
+    "              slot up to T; with --field_ranges counted it is then streamed a second time so that the ranges are sized\n"
+    "              by the ids that stay.  From then on every id whose slot was seen fewer than T times is replaced by\n"
+    "              2147483647 before it is hashed: training, evaluation, --predict_data, --serve_weights, --field_importance\n"
+    "              and --publish_path alike.  Prints `rare ids: counted R rows (E entries, X erased) in S s; K of 2^B slots\n"
+    "              kept at min_count T, F entries folded`.  Needs --hash_feats true and --train_data; one GPU; not with\n"
+    "              --resume_from or --rare_ids (a saved model takes its map from --rare_ids @FILE: it is not in the\n"
+    "              checkpoint).  0 and 1 are off\tdefault:0\n"
+    "--rare_bits <B>: the counter of --min_count has 2^B slots (ids that share a slot are counted together), 8 .. 30\n"
+    "              \tdefault:the smallest B with 2^B >= 4 * n_feats, at least 16 and at most 30\n"
+    "--rare_ids_out <file>: write the keep-map of --min_count (or of --rare_ids @FILE) there\tdefault:(none)\n"
+    "--rare_ids <@file>: fold by the keep-map an earlier run wrote with --rare_ids_out instead of counting one; the run\n"
+    "              goes on exactly as the counting run did.  Needs --hash_feats true; one GPU\tdefault:(none)\n";
 
 static bool assign_bool(std::string arg) {
   std::transform(arg.begin(), arg.end(), arg.begin(), [](unsigned char c) { return std::tolower(c); });
@@ -258,6 +272,21 @@ void config_options::parse_option(int argc, char *argv[]) {
       }
       if (apply_deltas.empty()) throw std::invalid_argument("--apply_deltas needs a file name prefix");
     }
+    else if (k == "--min_count" || k == "--rare_bits") {
+      long long x = 0;
+      size_t used = 0;
+      try { x = std::stoll(v, &used); } catch (const std::exception &) { used = 0; }
+      if (used != v.size() || used == 0) throw std::invalid_argument(k + " takes an integer, got `" + v + "`");
+      if (k == "--min_count") {
+        if (x < 0 || x > 65535) throw std::invalid_argument("--min_count takes a count in [0, 65535], got `" + v + "`");
+        min_count = static_cast<int>(x);
+      } else {
+        if (x < 8 || x > 30) throw std::invalid_argument("--rare_bits takes a number of bits in [8, 30], got `" + v + "`");
+        rare_bits = static_cast<int>(x);
+      }
+    }
+    else if (k == "--rare_ids") rare_ids = v;
+    else if (k == "--rare_ids_out") rare_ids_out = v;
     else if (k == "--predict_data") predict_path = v;
     else if (k == "--predict_out") predict_out = v;
     else if (k == "--predict_output") {
@@ -324,6 +353,22 @@ void config_options::parse_option(int argc, char *argv[]) {
     if (!ranged || model_type != "FFM")
       throw std::invalid_argument("--field_ranges_out writes the fields' id ranges: it needs an FFM model and --field_ranges uniform, counted or @FILE");
   }
+  if (min_count > 1 || !rare_ids.empty()) {
+    // the fold works on raw ids, on one whole model on one GPU (refused here, before a device is opened)
+    const std::string what = min_count > 1 ? "--min_count " + std::to_string(min_count) + " " : "--rare_ids " + rare_ids + " ";
+    if (min_count > 1 && !rare_ids.empty())
+      throw std::invalid_argument("--min_count counts a keep-map and --rare_ids names one: give one of the two");
+    if (!rare_ids.empty() && (rare_ids[0] != '@' || rare_ids.size() == 1))
+      throw std::invalid_argument("--rare_ids takes @FILE, the keep-map --rare_ids_out wrote, got `" + rare_ids + "`");
+    if (!hash_feats) throw std::invalid_argument(what + "folds raw ids before they are hashed: it needs --hash_feats true");
+    if (n_gpus > 1) throw std::invalid_argument(what + "folds on one whole model on one GPU: --n_gpus > 1 is not allowed with it");
+    if (min_count > 1 && !resume_from.empty())
+      throw std::invalid_argument(what + "is not allowed with --resume_from: a saved model's keep-map is the one it was trained with; "
+                                         "write it with --rare_ids_out and pass --rare_ids @FILE");
+    if (min_count > 1 && train_path.empty()) throw std::invalid_argument(what + "counts the ids of the training file: it needs --train_data");
+  }
+  if (!rare_ids_out.empty() && min_count <= 1 && rare_ids.empty())
+    throw std::invalid_argument("--rare_ids_out writes the keep-map of rare ids: it needs --min_count > 1 or --rare_ids @FILE");
   if (auc_key_field >= 0) {
     // the grouped AUC rides on the AUC lines of one whole FFM model (refused here, before a device is opened)
     const std::string what = "--auc_key_field " + std::to_string(auc_key_field) + " ";

@@ -65,6 +65,15 @@ struct config_options {
   // model by PREFIX.1.delta .. (apply_deltas_n = 0: every consecutive file that exists)
   std::string apply_deltas;
   int apply_deltas_n = 0;
+  // --min_count T: ids seen fewer than T times in --train_data share one id per field (include/ffm_engine.h "Rare
+  // ids"): counted on the device in one pass before a model exists; 0 and 1 both mean off.  --rare_bits B: the
+  // counter has 2^B slots (0 = the smallest B with 2^B >= 4 * n_feats, inside [16, 30]).  --rare_ids @FILE: the
+  // keep-map of an earlier run (rare_ids.h); --rare_ids_out FILE writes it.  rare_map_bits / rare_words: what either
+  // resolved to (filled by main.cpp before a model exists; empty: no fold).
+  int min_count = 0, rare_bits = 0;
+  std::string rare_ids, rare_ids_out;
+  int rare_map_bits = 0;
+  std::vector<uint64_t> rare_words;
 
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };

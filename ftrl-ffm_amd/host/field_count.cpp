@@ -7,8 +7,7 @@
 #include <cstdio>
 #include <stdexcept>
 
-#include "../../include/ffm_engine.h"
-#include "csr_stream.h"
+#include "count_block.h"
 #include "field_ranges.h"
 
 namespace ftrl {
@@ -19,37 +18,9 @@ void check_rc(int rc, const char *what) {
   if (rc != FFM_OK) throw std::runtime_error(std::string(what) + ": " + ffm_engine_last_error());
 }
 
-// rows / entries of one counted block: large, so that the launch and the wait per block stay small beside its parse
-constexpr size_t kCountRows = 32768, kCountNnz = kCountRows * 64;
-
 struct SketchHandle {
   ffm_sketch *s = nullptr;
   ~SketchHandle() { ffm_engine_sketch_destroy(s); }
-};
-
-// The block the stream fills: its field and feat arrays page-locked at their capacity (the others stay pageable).
-struct CountBlock {
-  CsrBlock blk;
-  bool pinned = false;
-  CountBlock() {
-    blk.row_ptr.reserve(kCountRows + 1);
-    blk.label.reserve(kCountRows);
-    blk.field.reserve(kCountNnz);
-    blk.feat.reserve(kCountNnz);
-    blk.val.reserve(kCountNnz);
-    auto pages = [](size_t n) { return (4 * n + 4095) & ~static_cast<size_t>(4095); };  // (PageAllocator's)
-    if (ffm_engine_pin_host(blk.field.data(), pages(blk.field.capacity())) != FFM_OK) return;
-    if (ffm_engine_pin_host(blk.feat.data(), pages(blk.feat.capacity())) != FFM_OK) {
-      ffm_engine_unpin_host(blk.field.data());
-      return;
-    }
-    pinned = true;
-  }
-  ~CountBlock() {
-    if (!pinned) return;
-    ffm_engine_unpin_host(blk.field.data());
-    ffm_engine_unpin_host(blk.feat.data());
-  }
 };
 
 }  // namespace
@@ -63,6 +34,9 @@ std::vector<int32_t> count_field_ranges(const config_options &opt) {
     if (rc == FFM_E_INVALID) throw std::invalid_argument(ffm_engine_last_error());
     check_rc(rc, "ffm_engine_sketch_create");
   }
+  // --min_count / --rare_ids: the ranges are sized by the ids that stay -- a rare id counts as its field's one rare id
+  if (!opt.rare_words.empty())
+    check_rc(ffm_engine_sketch_set_filter(sk.s, opt.rare_map_bits, opt.rare_words.data()), "ffm_engine_sketch_set_filter");
   unsigned long long rows = 0;
   {
     CountBlock cb;  // (no page-locked memory to be had: the sketch copies each block into its own)

@@ -132,6 +132,13 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
     if (rc == FFM_E_INVALID) throw std::invalid_argument(ffm_engine_last_error());
     check(rc, "ffm_engine_create");
   }
+  // --min_count / --rare_ids: the keep-map main.cpp resolved -- training, serving and scoring engines alike fold by
+  // it wherever they hash (include/ffm_engine.h "Rare ids"; a group is refused there as on the command line)
+  if (!opt.rare_words.empty()) {
+    rc = ffm_engine_set_rare_fold(eng_, opt.rare_map_bits, opt.rare_words.data());
+    if (rc == FFM_E_INVALID || rc == FFM_E_UNSUPPORTED) throw std::invalid_argument(std::string("rare ids: ") + ffm_engine_last_error());
+    check(rc, "ffm_engine_set_rare_fold");
+  }
   if (serving_)
     std::printf("serving weights: %s, %lld bytes of model\n", opt.serve_weights.c_str(), static_cast<long long>(ffm_engine_model_bytes(eng_)));
   row_len_ = ffm_engine_row_len(eng_);

@@ -10,6 +10,7 @@
 #include "cmd_option.h"
 #include "field_importance.h"
 #include "field_ranges.h"
+#include "rare_ids.h"
 #include "sample_weights.h"
 #include "trainer.h"
 
@@ -86,6 +87,10 @@ int main(int argc, char *argv[]) {
     ftrl::SampleWeights weights = ftrl::load_sample_weights(opt);
     // --field_ranges counted | @FILE, --field_ranges_out: the ranges every model of this run is created with
     // (counted: one pass over the training file, on the device, before a model exists)
+    // --min_count T | --rare_ids @FILE, --rare_ids_out: the keep-map every engine of this run folds rare ids by
+    // (--min_count: one pass over the training file, on the device, before a model exists) -- ahead of the ranges,
+    // which --field_ranges counted then sizes by the ids that stay
+    ftrl::resolve_rare_ids(opt);
     ftrl::resolve_field_ranges(opt);
     if (opt.online) {
       ftrl::FtrlOnline task(opt);

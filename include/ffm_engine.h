@@ -710,6 +710,69 @@ void ffm_engine_sketch_destroy(ffm_sketch *s);
 int ffm_engine_sketch_estimate(const uint8_t *reg, int32_t n_fields, double *distinct /* [n_fields] */);
 int ffm_engine_field_ranges(const int64_t *count, int32_t n_fields, int32_t n_feats, int32_t *field_start /* [n_fields + 1] */);
 
+/* ---- Rare ids: ids seen fewer than T times share one id per field ------------------------------------
+ * A feature seen once or twice keeps a latent row that is still its random draw, adds noise to every
+ * prediction that touches it after its one update, and occupies a slot of the hashed id space that frequent
+ * ids then collide with.  The usual remedy (libffm's Criteo recipe: T = 10) maps every id seen fewer than T
+ * times to one "rare" id per field.  Here the counting runs on the device before a model exists, and the
+ * fold runs wherever an engine hashes.
+ *   counter    ffm_idcount: 2^bits 32-bit words in HBM, all zero at create, plus n_valid and n_bad.  bits in
+ *              [8, 30], cap in [1, 65535]; n_fields == 0 means LR / FM, and the field is taken as 0.
+ *   counting   an entry (field, feat) COUNTS iff feat >= 0 and, with n_fields > 0, 0 <= field < n_fields --
+ *              the entries "Hashed ids" keeps.  Every other entry adds one to n_bad and nothing else.  For a
+ *              counting entry
+ *                slot = x >> (32 - bits)          x = the 32 hashed bits of "Hashed ids"
+ *              and the counter of slot goes up by one -- until it has reached cap: read gives min(count, cap)
+ *              EXACTLY, whatever the order, the batching or the split of the entries across calls (integer
+ *              sums only).  Two ids that share a slot are counted together: a rare id may be kept because
+ *              of its neighbour, a frequent one is never folded.  field == NULL with n_fields > 0: entry p
+ *              of the call is field p mod n_fields, as for a sketch.
+ *   add        _add (zero_copy 0 / 1), _add_device, _read and _destroy: the arguments, the chunking and the
+ *              refusals of the sketch's calls of the same names.
+ *   keep       ffm_engine_idcount_keep: the KEEP-MAP of min_count T, 1 <= T <= cap (anything else is
+ *              FFM_E_INVALID: counts above the cap are not known).  2^bits / 64 words; bit j of word i is set
+ *              iff min(count[64 i + j], cap) >= T.  n_kept_slots = the set bits; n_folded_entries = the sum
+ *              of the counts below T = how many counted entries the map folds (counts below cap are exact).
+ *   fold       ffm_engine_set_rare_fold copies a map into HBM (words == NULL: turns the fold off and frees
+ *              it).  The engine must have FFM_FLAG_HASH_IDS (else FFM_E_INVALID); training and serving engines
+ *              alike; a group's or a shard's engine is FFM_E_UNSUPPORTED.  The engine must be idle: a staged
+ *              block that waits to be trained, or one between train_forward and train_update, is
+ *              FFM_E_INVALID; the call then waits for whatever the engine still has in flight.  The fold holds
+ *              for every block handed over afterwards: a counting entry whose slot's bit is 0 has its raw id
+ *              replaced by FFM_RARE_ID before the hash of "Hashed ids" runs.  Nothing else changes; erased
+ *              entries stay erased.  The rare id of a field is therefore the model id of (field, FFM_RARE_ID):
+ *              it lies in the field's own range under every ranges setting, and in [0, n_feats) for LR / FM.
+ *              A genuine raw id INT32_MAX shares it.  No id of the model is reserved.
+ *   where      everywhere an engine hashes: the upload kernel of the pipelined calls, the in-place kernel
+ *              behind the synchronous copies (training, prediction, ffm_engine_score_candidates) and
+ *              ffm_engine_hash_ids_device.  The other _device entry points keep taking ids as they are.
+ *              An engine without a map runs the kernels, launches and kernel arguments it always ran.
+ *   host       ffm_engine_fold_ids_host is the fold on the host, bit for bit, and needs no device; composed
+ *              with ffm_engine_hash_ids_host it gives the model ids.  ffm_engine_rare_slots_host gives the
+ *              slots (field == NULL: field 0).
+ *   sketch     ffm_engine_sketch_set_filter: with a filter, an entry whose bit is 0 counts as the one id
+ *              FFM_RARE_ID of its field, so counted ranges are sized by the ids that stay.  words == NULL
+ *              turns it off.
+ * OUT OF SCOPE  groups, shards and several GPUs; admission while training (a running count that lets an id
+ *   in once it has been seen T times); recording the map or its checksum in checkpoints; counting evaluation
+ *   data; choosing T for the caller. */
+typedef struct ffm_idcount ffm_idcount;
+#define FFM_RARE_ID 2147483647
+int ffm_engine_idcount_create(int32_t n_fields, int32_t bits, int32_t cap, int32_t device_id, ffm_idcount **out);
+int ffm_engine_idcount_add(ffm_idcount *s, int32_t nnz, const int32_t *field, const int32_t *feat, int32_t zero_copy);
+int ffm_engine_idcount_add_device(ffm_idcount *s, int32_t nnz, const int32_t *field, const int32_t *feat);
+int ffm_engine_idcount_read(ffm_idcount *s, uint32_t *counts /* [2^bits], already min(., cap), may be NULL */,
+                            int64_t *n_valid, int64_t *n_bad);
+int ffm_engine_idcount_keep(ffm_idcount *s, int32_t min_count, uint64_t *words /* [2^bits / 64] */,
+                            int64_t *n_kept_slots, int64_t *n_folded_entries);
+void ffm_engine_idcount_destroy(ffm_idcount *s);
+int ffm_engine_set_rare_fold(ffm_engine *e, int32_t bits, const uint64_t *words /* [2^bits / 64] or NULL */);
+int ffm_engine_sketch_set_filter(ffm_sketch *s, int32_t bits, const uint64_t *words /* [2^bits / 64] or NULL */);
+/* pure host arithmetic, no device: */
+int ffm_engine_fold_ids_host(int32_t n_fields, int32_t bits, const uint64_t *words, int32_t nnz, const int32_t *field,
+                             const int32_t *feat_in, int32_t *feat_out);
+int ffm_engine_rare_slots_host(int32_t bits, int32_t nnz, const int32_t *field, const int32_t *feat, uint32_t *slot);
+
 /* ---- Rows without values: val == NULL is 1.0f -------------------------------------------------------
  * Click logs are categorical: after hashing every entry of a libffm file is field:id:1, and an array of
  * 1.0f is a third of a block's bytes over PCIe (half of what is left once the field array stays at home).
