@@ -55,6 +55,7 @@
 #include "kernels_stage.h"
 #include "kernels_sketch.h"
 #include "kernels_idcount.h"
+#include "kernels_valhist.h"
 #include "metrics_host.h"
 
 using namespace ftrl_dev;
@@ -408,6 +409,9 @@ struct ffm_engine {
   // ffm_engine_set_rare_fold (engine_idcount.h): the keep-map in HBM (its own allocation, freed when the fold is
   // turned off or the engine destroyed) and its shift; words == nullptr: no fold, and nothing here is read
   ftrl_hash::Rare rare{};
+  // ffm_engine_set_buckets (engine_valhist.h): the bucket table in HBM (one allocation of its own, n_edges first, freed
+  // when the table is taken off or the engine destroyed); n_edges == nullptr: none, and nothing here is read
+  ftrl_hash::Buckets buckets{};
   // ffm_engine_refresh_weights (engine_refresh.h): its six counters and its grid, both made by the first call
   unsigned long long *d_refresh = nullptr;
   int refresh_grid = 0;
@@ -707,6 +711,7 @@ void ffm_engine_destroy(ffm_engine *e) {
   }
   for (void *p : e->allocs) (void)hipFree(p);
   if (e->rare.words) (void)hipFree(const_cast<uint64_t *>(e->rare.words));
+  if (e->buckets.n_edges) (void)hipFree(const_cast<int32_t *>(e->buckets.n_edges));
   for (int i = 0; i < ffm_engine::kSets; i++) {
     if (e->ev_grouped[i]) (void)hipEventDestroy(e->ev_grouped[i]);
     if (e->ev_set_free[i]) (void)hipEventDestroy(e->ev_set_free[i]);
@@ -839,6 +844,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_keyed.h"
 #include "engine_sketch.h"
 #include "engine_idcount.h"
+#include "engine_valhist.h"
 #include "engine_ablate.h"
 }  // extern "C"
 

@@ -20,8 +20,28 @@ __global__ __launch_bounds__(256) void hash_ids_kernel(ftrl_hash::Map hm, unsign
     feat_out[p] = ftrl_hash::hash_entry(hm, field ? field[p] : hm.ffm ? static_cast<int>(p % F) : 0, feat_in[p]);
 }
 
-static void launch_hash_ids(ffm_engine *e, hipStream_t st, int32_t nnz, const int32_t *field, const int32_t *feat_in, int32_t *feat_out) {
+// val: the block's values beside feat_in (the synchronous copies), mapped in place by an engine with a bucket table
+// (ffm_engine_set_buckets: the bucketing kernel, kernels_valhist.h); nullptr: ids alone, as they always went.
+// The whole mapping of an FFM engine with a bucket table: bucket, fold, hash; val moves with feat.
+static void launch_bucket_ids(ffm_engine *e, hipStream_t st, int32_t nnz, const int32_t *field, const int32_t *feat_in, int32_t *feat_out,
+                              const float *val_in, float *val_out) {
   if (nnz <= 0) return;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(field) | reinterpret_cast<uintptr_t>(feat_in) | reinterpret_cast<uintptr_t>(feat_out) |
+                         reinterpret_cast<uintptr_t>(val_in) | reinterpret_cast<uintptr_t>(val_out);
+  const int vec = (bits & 15u) == 0 ? 1 : 0;
+  const int lanes = vec ? cdiv(nnz, 4) : nnz;
+  hipLaunchKernelGGL(hash_ids_bucket_kernel, dim3(std::max(1, std::min(1024, cdiv(lanes, 256)))), dim3(256), 0, st, e->hm, e->rare, e->buckets,
+                     static_cast<unsigned>(nnz), field, feat_in, feat_out, reinterpret_cast<const unsigned *>(val_in),
+                     reinterpret_cast<unsigned *>(val_out), vec);
+}
+
+static void launch_hash_ids(ffm_engine *e, hipStream_t st, int32_t nnz, const int32_t *field, const int32_t *feat_in, int32_t *feat_out,
+                            float *val = nullptr) {
+  if (nnz <= 0) return;
+  if (val && e->buckets.n_edges) {
+    launch_bucket_ids(e, st, nnz, field, feat_in, feat_out, val, val);
+    return;
+  }
   const uintptr_t bits = reinterpret_cast<uintptr_t>(field) | reinterpret_cast<uintptr_t>(feat_in) | reinterpret_cast<uintptr_t>(feat_out);
   const int vec = (bits & 15u) == 0 ? 1 : 0;
   const int lanes = vec ? cdiv(nnz, 4) : nnz;

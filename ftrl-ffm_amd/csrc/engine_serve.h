@@ -136,7 +136,7 @@ int ffm_engine_score_candidates(ffm_engine *e, int32_t n_req, const int32_t *ctx
     else
       hipLaunchKernelGGL(fill_ones_kernel, dim3(std::max(1, std::min(256, cdiv(cdiv(s.nnz, 4), 256)))), dim3(256), 0, st, s.d_val,
                          static_cast<unsigned>(s.nnz));
-    if (e->hash_ids) launch_hash_ids(e, st, s.nnz, s.d_field, s.d_feat, s.d_feat);
+    if (e->hash_ids) launch_hash_ids(e, st, s.nnz, s.d_field, s.d_feat, s.d_feat, s.d_val);
   }
   rc = cand_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, e->d_req_ptr, n_cand, e->d_row_ptr,
                    e->d_field, e->d_feat, e->d_val, cand_nnz, ctx_cap, longest, output_prob, e->d_out);

@@ -97,6 +97,8 @@ struct SlotClaim {
   bool was_used = false, has_field = false;
   PullHashJob job{};  // (the hashed loop's part is filled on a flagged engine only)
   ftrl_hash::Rare rare{};  // the engine's keep-map when the block was claimed (words == nullptr: none)
+  // the engine's bucket table when the block was claimed (bk.n_edges == nullptr: none), and where val moves then
+  PullBucketPart bucket{};
 };
 
 // The next staging slot for a host block (`host`: the caller's arrays, field == nullptr on LR / FM): waits
@@ -156,6 +158,14 @@ static int claim_slot(ffm_engine *e, const Rows &host, const float *weight, int3
   const Part weights{&hj.w.wsrc, &hj.w.wdst, &hj.w.wbytes};
   if (e->hash_ids) hj.hm = e->hm;
   claim->rare = e->rare;
+  // a bucket table (flagged FFM engines only): val too goes to the hashed loop, which writes all of the slot's val
+  const bool bucketed = e->hash_ids && e->buckets.n_edges;
+  unsigned vbytes = 0;
+  const Part bucketed_vals{&claim->bucket.vsrc, &claim->bucket.vdst, &vbytes};
+  if (bucketed) {
+    claim->bucket.bk = e->buckets;
+    claim->bucket.vdst = reinterpret_cast<char *>(sl.val);
+  }
   ScopedTimer tm("stage:copies");
   HIP_TRY(put(row_ptr, 4 * R1, sl.row_ptr));
   if (field) HIP_TRY(put(field, 4 * E, sl.field, e->hash_ids ? &hashed_fields : nullptr));
@@ -166,7 +176,7 @@ static int claim_slot(ffm_engine *e, const Rows &host, const float *weight, int3
   }
   claim->has_field = field != nullptr || job.gen_n != 0;
   HIP_TRY(put(feat, 4 * E, sl.feat, e->hash_ids ? &hashed_ids : nullptr));
-  HIP_TRY(put(val, 4 * E, sl.val));  // (val == NULL: nothing to copy or describe -- the upload kernel writes ones)
+  HIP_TRY(put(val, 4 * E, sl.val, bucketed ? &bucketed_vals : nullptr));  // (val == NULL: nothing to copy or describe -- the upload kernel writes ones)
   HIP_TRY(put(label, 4 * R, sl.label));
   HIP_TRY(put(weight, 4 * R, sl.weight, &weights, &pw));
   job.ordinal = e->n_staged_total + 1;
@@ -178,16 +188,21 @@ static int claim_slot(ffm_engine *e, const Rows &host, const float *weight, int3
 // The upload of one claimed block on stream `st`: the one place that names an instantiation of the upload kernel.
 // ones / n_ones: the slot's val array and how many 1.0f the kernel writes there (0: the block brought its values).
 // rare: the claim's keep-map (set on a flagged engine only, ffm_engine_set_rare_fold); none: the launches below it.
-static void launch_upload(ffm_engine *e, hipStream_t st, int grid, const PullHashJob &hj, const ftrl_hash::Rare &rare, float *ones,
-                          unsigned n_ones) {
+// bucket: the claim's bucket table and val's own part (ffm_engine_set_buckets); those launches write val themselves.
+static void launch_upload(ffm_engine *e, hipStream_t st, int grid, const PullHashJob &hj, const ftrl_hash::Rare &rare,
+                          const PullBucketPart &bucket, float *ones, unsigned n_ones) {
   auto launch = [&](auto weighted, auto hashed, auto folded, const auto &arg) {
     constexpr bool W = decltype(weighted)::value, H = decltype(hashed)::value, R = decltype(folded)::value;
-    if (n_ones) hipLaunchKernelGGL((pull_block_kernel<W, H, R, float *, unsigned>), dim3(grid), dim3(256), 0, st, arg, ones, n_ones);
-    else hipLaunchKernelGGL((pull_block_kernel<W, H, R>), dim3(grid), dim3(256), 0, st, arg);
+    if (n_ones) hipLaunchKernelGGL((pull_block_kernel<W, H, R, false, float *, unsigned>), dim3(grid), dim3(256), 0, st, arg, ones, n_ones);
+    else hipLaunchKernelGGL((pull_block_kernel<W, H, R, false>), dim3(grid), dim3(256), 0, st, arg);
   };
   const std::true_type yes{};
   const std::false_type no{};
-  if (e->hash_ids && rare.words) {
+  if (e->hash_ids && bucket.bk.n_edges) {
+    const PullBucketJob bj{PullRareJob{hj, rare}, bucket};
+    if (hj.w.wbytes) hipLaunchKernelGGL((pull_block_kernel<true, true, false, true>), dim3(grid), dim3(256), 0, st, bj);
+    else hipLaunchKernelGGL((pull_block_kernel<false, true, false, true>), dim3(grid), dim3(256), 0, st, bj);
+  } else if (e->hash_ids && rare.words) {
     const PullRareJob rj{hj, rare};
     if (hj.w.wbytes) launch(yes, yes, yes, rj);
     else launch(no, yes, yes, rj);
@@ -254,7 +269,7 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
   // (val == NULL: the upload writes the slot's values -- every time, whatever the slot held before)
   float *const ones = sl.val;
   const unsigned n_ones = val ? 0u : static_cast<unsigned>(nnz);
-  rc = e->submit([e, this_slot, free_ev, hjob = claim.job, rare = claim.rare, plan, seq, grid_pull, timed, ones, n_ones]() -> int {
+  rc = e->submit([e, this_slot, free_ev, hjob = claim.job, rare = claim.rare, bucket = claim.bucket, plan, seq, grid_pull, timed, ones, n_ones]() -> int {
     ScopedTimer tm("stage:submit");
     ffm_engine::Slot &s2 = e->slots[this_slot];
     int rc2 = FFM_OK;
@@ -264,7 +279,7 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
       // (long steps: the upload too waits for the running block's row kernel to end -- beside the update
       // launches it costs nothing, beside the row kernel, which is bound by the bytes it moves, it does)
       if (e->pull_after_row && plan.ws >= 0) HIP_TRY(hipStreamWaitEvent(e->prep, e->prep_after_row ? e->ev_row_done[plan.ws] : e->ev_set_free[plan.ws], 0));
-      launch_upload(e, e->prep, grid_pull, hjob, rare, ones, n_ones);
+      launch_upload(e, e->prep, grid_pull, hjob, rare, bucket, ones, n_ones);
       HIP_TRY(hipEventRecord(s2.ev_copied, e->prep));
       return prepare_submit(e, plan, timed);
     };
@@ -444,7 +459,7 @@ int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const i
   ffm_engine::Slot &sl = e->slots[this_slot];
   if (claim.was_used && sl.free_ev) HIP_TRY(hipStreamWaitEvent(e->prep, sl.free_ev, 0));  // nothing reads its device arrays
   // (no values came: the upload writes the slot's)
-  launch_upload(e, e->prep, e->grid_pull, claim.job, claim.rare, sl.val, val ? 0u : static_cast<unsigned>(nnz));
+  launch_upload(e, e->prep, e->grid_pull, claim.job, claim.rare, claim.bucket, sl.val, val ? 0u : static_cast<unsigned>(nnz));
   HIP_TRY(hipEventRecord(sl.ev_copied, e->prep));
   slot_commit(e, claim, host, longest, false, zero_copy);
   {

@@ -649,7 +649,7 @@ static int stage_block(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, co
   if (weight && n_rows > 0)
     HIP_TRY(hipMemcpyAsync(e->d_weight, weight, sizeof(float) * n_rows, hipMemcpyHostToDevice, e->stream));
   // FFM_FLAG_HASH_IDS: the ids in place, behind their copy and ahead of every kernel that reads them
-  if (e->hash_ids) launch_hash_ids(e, e->stream, nnz, field ? e->d_field : nullptr, e->d_feat, e->d_feat);
+  if (e->hash_ids) launch_hash_ids(e, e->stream, nnz, field ? e->d_field : nullptr, e->d_feat, e->d_feat, e->d_val);
   *dev = Rows{n_rows, nnz, e->d_row_ptr, field ? e->d_field : nullptr, e->d_feat, e->d_val, label ? e->d_label : nullptr};
   *row_cap_out = longest;
   return FFM_OK;

@@ -83,6 +83,48 @@ FTRL_HASH_HD int32_t hash_entry_rare(const Map &m, const Rare &r, int32_t field,
   return hash_entry(m, field, fold_entry(m.ffm != 0, m.n_fields, r, field, feat));
 }
 
+// Value buckets (include/ffm_engine.h "Value buckets"): a numeric column's value, taken by its bit pattern, gives
+// one of 65536 order-preserving bins; a field's table of at most 255 ascending bins (its edges) cuts them into
+// buckets, and a bucketed entry becomes (bucket, 1.0f).  Integer instructions only.  Beside Map and Rare, never
+// inside them: the kernels of an engine without a table take what they always took.
+constexpr int32_t kBucketBins = 65536, kBucketMaxEdges = 255, kBucketNanId = 65536;  // FFM_BUCKET_*
+constexpr uint32_t kOneBits = 0x3f800000u;  // 1.0f
+FTRL_HASH_HD bool value_is_nan(uint32_t u) { return (u & 0x7fffffffu) > 0x7f800000u; }
+FTRL_HASH_HD uint32_t value_bin(uint32_t u) {
+  if ((u & 0x7fffffffu) == 0u) u = 0u;  // (-0.0 and +0.0: one key)
+  return ((u >> 31) ? ~u : (u | 0x80000000u)) >> 16;
+}
+// n_edges[f]: -1 = field f is not bucketed, else its number of edges; edges[f * kBucketMaxEdges ..]: its edges.
+struct Buckets {
+  const int32_t *n_edges;
+  const uint16_t *edges;
+};
+// The number of edges < bin: a binary search of at most 8 steps (n <= 255).
+FTRL_HASH_HD int32_t bucket_of(const uint16_t *edges, int32_t n, uint32_t bin) {
+  int32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int32_t mid = (lo + hi) >> 1;
+    if (edges[mid] < bin) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// One entry: true iff it is bucketed (feat >= 0, 0 <= field < n_fields, the field has a table); *feat and *vbits
+// (the value's bits) are then replaced.  Every other entry is left as it is.
+FTRL_HASH_HD bool bucket_entry(int32_t n_fields, const Buckets &b, int32_t field, int32_t *feat, uint32_t *vbits) {
+  if (*feat < 0 || static_cast<uint32_t>(field) >= static_cast<uint32_t>(n_fields)) return false;
+  const int32_t n = b.n_edges[field];
+  if (n < 0) return false;
+  *feat = value_is_nan(*vbits) ? kBucketNanId : bucket_of(b.edges + field * kBucketMaxEdges, n, value_bin(*vbits));
+  *vbits = kOneBits;
+  return true;
+}
+// An engine's whole mapping of one FFM entry: bucket, else fold (r.words != nullptr), then hash.  Returns the model
+// id; *vbits is the value the kernels downstream take.
+FTRL_HASH_HD int32_t hash_entry_bucket(const Map &m, const Rare &r, const Buckets &b, int32_t field, int32_t feat, uint32_t *vbits) {
+  if (bucket_entry(m.n_fields, b, field, &feat, vbits)) return hash_entry(m, field, feat);
+  return r.words ? hash_entry_rare(m, r, field, feat) : hash_entry(m, field, feat);
+}
+
 #if defined(__HIPCC__)
 // Four entries at a time, for the kernels that carry them as 16-byte vectors (hash_ids_kernel, the upload kernel).
 // The fields of entries 4i .. 4i + 3 of a block handed over without a field array: one entry per field in
@@ -97,6 +139,11 @@ __device__ __forceinline__ int4 hash_entries4(const Map &hm, const int4 fl, cons
 __device__ __forceinline__ int4 hash_entries4_rare(const Map &hm, const Rare &r, const int4 fl, const int4 ft) {
   return make_int4(hash_entry_rare(hm, r, fl.x, ft.x), hash_entry_rare(hm, r, fl.y, ft.y), hash_entry_rare(hm, r, fl.z, ft.z),
                    hash_entry_rare(hm, r, fl.w, ft.w));
+}
+// ... bucketing: v = the four values' bits, replaced where an entry is bucketed.
+__device__ __forceinline__ int4 hash_entries4_bucket(const Map &hm, const Rare &r, const Buckets &b, const int4 fl, const int4 ft, uint4 *v) {
+  return make_int4(hash_entry_bucket(hm, r, b, fl.x, ft.x, &v->x), hash_entry_bucket(hm, r, b, fl.y, ft.y, &v->y),
+                   hash_entry_bucket(hm, r, b, fl.z, ft.z, &v->z), hash_entry_bucket(hm, r, b, fl.w, ft.w, &v->w));
 }
 #endif
 

@@ -44,13 +44,20 @@ struct PullHashJob {
 // map before it hashes it (ftrl_hash::hash_entry_rare).  The map and its shift stand behind the hashed job, so
 // an engine without a map hands over the PullHashJob it always did.
 struct PullRareJob { PullHashJob h; ftrl_hash::Rare rare; };
+// A flagged FFM engine with a bucket table (include/ffm_engine.h "Value buckets"): val too is taken out of the
+// block's five arrays and moves in the hashed loop, which maps (field, id, value) to (field, id', value')
+// (ftrl_hash::hash_entry_bucket).  vsrc == nullptr: the block brought no values, every one is 1.0f -- the loop
+// writes the slot's val array itself, so these instantiations take no Ones.  rare.words == nullptr: no keep-map
+// (a run-time branch here, where the bucketing work is anyway).
+struct PullBucketPart { ftrl_hash::Buckets bk; const char *vsrc; char *vdst; };
+struct PullBucketJob { PullRareJob r; PullBucketPart b; };
 
 // What an instantiation takes: the smallest of the three jobs that holds its parts.  Every variant is a
 // kernel of its own -- an instantiation, not a run-time branch -- so that a block without weights, on an
 // unflagged engine, with its values is uploaded by the launch, the argument and the kernel it always was
 // (profiles/sample_weights.md, profiles/implicit_ones.md).
-template <bool WEIGHTED, bool HASHED, bool RARE>
-using PullArg = std::conditional_t<RARE, PullRareJob, std::conditional_t<HASHED, PullHashJob, std::conditional_t<WEIGHTED, PullWeightedJob, PullJob>>>;
+template <bool WEIGHTED, bool HASHED, bool RARE, bool BUCKET>
+using PullArg = std::conditional_t<BUCKET, PullBucketJob, std::conditional_t<RARE, PullRareJob, std::conditional_t<HASHED, PullHashJob, std::conditional_t<WEIGHTED, PullWeightedJob, PullJob>>>>;
 
 // Ones: nothing, or <float *, unsigned> = the slot's val array and the number of 1.0f to write there.
 // The parts in order: the five arrays, the weights, the hashed loop, the ones, a missing field array, the ticket.
@@ -60,12 +67,14 @@ using PullArg = std::conditional_t<RARE, PullRareJob, std::conditional_t<HASHED,
 // reference -- hence the two pointers picked by `if constexpr`.  As it stands every instantiation compiles to
 // the instructions of the kernel it replaces.
 // RARE (with HASHED only): the hashed loop below runs on the job's hashed part and folds by the job's map.
-template <bool WEIGHTED, bool HASHED, bool RARE, typename... Ones>
-__global__ __launch_bounds__(256) void pull_block_kernel(PullArg<WEIGHTED, HASHED, RARE> arg, Ones... ones) {
+// BUCKET (with HASHED, without RARE and without Ones): the hashed loop's third text, at the end of the three.
+template <bool WEIGHTED, bool HASHED, bool RARE, bool BUCKET, typename... Ones>
+__global__ __launch_bounds__(256) void pull_block_kernel(PullArg<WEIGHTED, HASHED, RARE, BUCKET> arg, Ones... ones) {
   static_assert(sizeof...(Ones) == 0 || sizeof...(Ones) == 2, "Ones: nothing, or <float *, unsigned>");
   static_assert(HASHED || !RARE, "RARE: a variant of the hashed loop");
+  static_assert(!BUCKET || (HASHED && !RARE && sizeof...(Ones) == 0), "BUCKET: a variant of the hashed loop that holds the fold and the ones");
   const PullJob *block;
-  if constexpr (RARE) block = &arg.h.w.block; else if constexpr (HASHED) block = &arg.w.block; else if constexpr (WEIGHTED) block = &arg.block; else block = &arg;
+  if constexpr (BUCKET) block = &arg.r.h.w.block; else if constexpr (RARE) block = &arg.h.w.block; else if constexpr (HASHED) block = &arg.w.block; else if constexpr (WEIGHTED) block = &arg.block; else block = &arg;
   const PullJob &job = *block;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
   const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
@@ -82,7 +91,7 @@ __global__ __launch_bounds__(256) void pull_block_kernel(PullArg<WEIGHTED, HASHE
   }
   if constexpr (WEIGHTED) {
     const PullWeightedJob *weights;
-    if constexpr (RARE) weights = &arg.h.w; else if constexpr (HASHED) weights = &arg.w; else weights = &arg;
+    if constexpr (BUCKET) weights = &arg.r.h.w; else if constexpr (RARE) weights = &arg.h.w; else if constexpr (HASHED) weights = &arg.w; else weights = &arg;
     const PullWeightedJob &wj = *weights;
     const unsigned n16 = wj.wbytes >> 4;
     const int4 *s = reinterpret_cast<const int4 *>(wj.wsrc);
@@ -92,7 +101,7 @@ __global__ __launch_bounds__(256) void pull_block_kernel(PullArg<WEIGHTED, HASHE
     if (tid < (tail >> 2))
       reinterpret_cast<int *>(wj.wdst)[(n16 << 2) + tid] = reinterpret_cast<const int *>(wj.wsrc)[(n16 << 2) + tid];
   }
-  if constexpr (HASHED && !RARE) {
+  if constexpr (HASHED && !RARE && !BUCKET) {
     const unsigned n16 = arg.hbytes >> 4, F = static_cast<unsigned>(arg.hm.n_fields);
     for (unsigned i = tid; i < n16; i += stride) {
       const int4 ft = reinterpret_cast<const int4 *>(arg.isrc)[i];
@@ -136,6 +145,36 @@ __global__ __launch_bounds__(256) void pull_block_kernel(PullArg<WEIGHTED, HASHE
         reinterpret_cast<int *>(hj.fdst)[p] = f;
       }
       reinterpret_cast<int *>(hj.idst)[p] = ftrl_hash::hash_entry_rare(hj.hm, arg.rare, f, reinterpret_cast<const int *>(hj.isrc)[p]);
+    }
+  }
+  // (and once more, bucketing: val moves here too -- loaded, or 1.0f where the block brought none -- and every
+  // entry stores its field, its model id and its value)
+  if constexpr (BUCKET) {
+    const PullHashJob &hj = arg.r.h;
+    const PullBucketPart &bp = arg.b;
+    const unsigned n16 = hj.hbytes >> 4, F = static_cast<unsigned>(hj.hm.n_fields);
+    for (unsigned i = tid; i < n16; i += stride) {
+      const int4 ft = reinterpret_cast<const int4 *>(hj.isrc)[i];
+      int4 fl;
+      if (hj.fsrc) {
+        fl = reinterpret_cast<const int4 *>(hj.fsrc)[i];
+        reinterpret_cast<int4 *>(hj.fdst)[i] = fl;
+      } else fl = ftrl_hash::hash_implicit_fields4(i, F);
+      uint4 v = make_uint4(ftrl_hash::kOneBits, ftrl_hash::kOneBits, ftrl_hash::kOneBits, ftrl_hash::kOneBits);
+      if (bp.vsrc) v = reinterpret_cast<const uint4 *>(bp.vsrc)[i];
+      reinterpret_cast<int4 *>(hj.idst)[i] = ftrl_hash::hash_entries4_bucket(hj.hm, arg.r.rare, bp.bk, fl, ft, &v);
+      reinterpret_cast<uint4 *>(bp.vdst)[i] = v;
+    }
+    if (tid < ((hj.hbytes & 15u) >> 2)) {
+      const unsigned p = (n16 << 2) + tid;
+      int f = static_cast<int>(p % F);
+      if (hj.fsrc) {
+        f = reinterpret_cast<const int *>(hj.fsrc)[p];
+        reinterpret_cast<int *>(hj.fdst)[p] = f;
+      }
+      unsigned v = bp.vsrc ? reinterpret_cast<const unsigned *>(bp.vsrc)[p] : ftrl_hash::kOneBits;
+      reinterpret_cast<int *>(hj.idst)[p] = ftrl_hash::hash_entry_bucket(hj.hm, arg.r.rare, bp.bk, f, reinterpret_cast<const int *>(hj.isrc)[p], &v);
+      reinterpret_cast<unsigned *>(bp.vdst)[p] = v;
     }
   }
   // A block handed over without values (val == NULL: every value is 1.0f, include/ffm_engine.h "Rows without

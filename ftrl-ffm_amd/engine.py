@@ -237,6 +237,17 @@ ABI = [
     ("ffm_engine_fold_ids_host", ctypes.c_int,
      [ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, _i32p, _i32p, _i32p]),
     ("ffm_engine_rare_slots_host", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, _vp]),
+    # numeric fields as quantile buckets (include/ffm_engine.h "Value buckets")
+    ("ffm_engine_valhist_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
+    ("ffm_engine_valhist_add", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32]),
+    ("ffm_engine_valhist_add_device", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp]),
+    ("ffm_engine_valhist_read", ctypes.c_int, [_vp, _vp, _i64p, _i64p, _i64p]),
+    ("ffm_engine_valhist_destroy", None, [_vp]),
+    ("ffm_engine_set_buckets", ctypes.c_int, [_vp, _vp, _vp]),
+    ("ffm_engine_bucket_ids_device", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    ("ffm_engine_bucket_edges", ctypes.c_int, [_vp, ctypes.c_int32, _vp, ctypes.POINTER(ctypes.c_int32)]),
+    ("ffm_engine_bucket_ids_host", ctypes.c_int,
+     [ctypes.c_int32, _vp, _vp, ctypes.c_int32, _i32p, _i32p, _f32p, _i32p, _f32p, _vp]),
     # the loss and AUC of the model without each field, in one pass (include/ffm_engine.h "Field ablation")
     ("ffm_engine_ablation_enable", ctypes.c_int, [_vp, ctypes.c_int32]),
     ("ffm_engine_predict_ablated", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [ctypes.c_int32, _f32p, _f64p]),
@@ -251,6 +262,7 @@ ABI = [
 ]
 SKETCH_REGS = 16384  # FFM_SKETCH_REGS
 RARE_ID = 2 ** 31 - 1  # FFM_RARE_ID
+BUCKET_BINS, BUCKET_MAX_EDGES, BUCKET_NAN_ID = 65536, 255, 65536  # FFM_BUCKET_*
 
 _lib = None
 
@@ -437,6 +449,70 @@ def fold_rare(field, feat, n_fields, bits, words):
     if rc != 0:
         raise EngineError(rc, lib.ffm_engine_last_error().decode())
     return out
+
+
+def value_bins(val):
+    """(bin int32, is_nan bool) of float32 values (include/ffm_engine.h "Value buckets"): the top 16 bits of the
+    order-preserving key of every value's bit pattern; a NaN has no bin (-1 here).  Integer arithmetic only."""
+    u = np.ascontiguousarray(val, np.float32).view(np.uint32).copy()
+    u[(u & np.uint32(0x7fffffff)) == 0] = 0
+    nan = (u & np.uint32(0x7fffffff)) > np.uint32(0x7f800000)
+    key = np.where((u >> np.uint32(31)) != 0, ~u, u | np.uint32(0x80000000))
+    bins = (key >> np.uint32(16)).astype(np.int32)
+    bins[nan] = -1
+    return bins, nan
+
+
+def bucket_edges(counts, n_buckets):
+    """The edges (uint16, strictly ascending, at most BUCKET_MAX_EDGES) that cut one field's value histogram
+    (BUCKET_BINS counts) into n_buckets buckets of equal mass (ffm_engine_bucket_edges: exact integers, no device)."""
+    lib = load_library()
+    counts = np.ascontiguousarray(counts, np.uint64)
+    if counts.shape != (BUCKET_BINS,):
+        raise ValueError("counts: uint64 [%d]" % BUCKET_BINS)
+    edges = np.zeros(BUCKET_MAX_EDGES, np.uint16)
+    n = ctypes.c_int32(0)
+    rc = lib.ffm_engine_bucket_edges(counts.ctypes.data, int(n_buckets), edges.ctypes.data, ctypes.byref(n))
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
+    return edges[:n.value].copy()
+
+
+def _bucket_table(n_fields, buckets):
+    """{field: edges} as the library takes a table: (n_edges int32 [n_fields], edges uint16 [n_fields, 255])."""
+    n_fields = int(n_fields)
+    n_edges = np.full(n_fields, -1, np.int32)
+    edges = np.zeros((max(n_fields, 1), BUCKET_MAX_EDGES), np.uint16)
+    for f, e in buckets.items():
+        f = int(f)
+        if not 0 <= f < n_fields:
+            raise ValueError("bucketed field %d outside [0, %d)" % (f, n_fields))
+        e = np.asarray(e)
+        if e.ndim != 1 or e.size > BUCKET_MAX_EDGES or (e.size and (e.min() < 0 or e.max() >= BUCKET_BINS)):
+            raise ValueError("field %d: at most %d edges, each a bin in [0, %d)" % (f, BUCKET_MAX_EDGES, BUCKET_BINS))
+        n_edges[f] = e.size
+        edges[f, :e.size] = e.astype(np.uint16)
+    return n_edges, edges
+
+
+def bucket_ids(field, feat, val, n_fields, buckets):
+    """The bucket step of an engine with the table `buckets` = {field: edges} on the host
+    (ffm_engine_bucket_ids_host: the device's bits, no device): (feat', val', bucketed bool).  A bucketed entry is
+    (bucket, 1.0); every other entry comes back untouched.  field None: entry p is field p mod n_fields; val None:
+    every value is 1.0."""
+    lib = load_library()
+    n_edges, edges = _bucket_table(n_fields, buckets)
+    feat = np.ascontiguousarray(feat, np.int32)
+    fld = None if field is None else np.ascontiguousarray(field, np.int32)
+    v = None if val is None else np.ascontiguousarray(val, np.float32)
+    if (fld is not None and fld.shape != feat.shape) or (v is not None and v.shape != feat.shape):
+        raise ValueError("field, feat and val must be equally long")
+    feat_out, val_out, hit = np.empty_like(feat), np.empty(feat.shape, np.float32), np.zeros(feat.shape, np.uint8)
+    rc = lib.ffm_engine_bucket_ids_host(int(n_fields), n_edges.ctypes.data, edges.ctypes.data, feat.size, _i(fld), _i(feat),
+                                        _f(v), _i(feat_out), _f(val_out), hit.ctypes.data)
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
+    return feat_out, val_out, hit.astype(bool)
 
 
 def sketch_estimate(reg):
@@ -1011,6 +1087,21 @@ class Engine:
         bits, words = _rare_words(bits, words)
         self._check(self.lib.ffm_engine_set_rare_fold(self.h, bits, words.ctypes.data))
 
+    def set_buckets(self, buckets=None):
+        """Maps numeric fields to quantile buckets in every block handed over from now on (include/ffm_engine.h
+        "Value buckets"): buckets = {field: edges} (bucket_edges); None takes the table off.  hash_ids=True FFM
+        engines only, idle."""
+        if buckets is None:
+            self._check(self.lib.ffm_engine_set_buckets(self.h, None, None))
+            return
+        n_edges, edges = _bucket_table(self.cfg.n_fields, buckets)
+        self._check(self.lib.ffm_engine_set_buckets(self.h, n_edges.ctypes.data, edges.ctypes.data))
+
+    def bucket_ids_device(self, nnz, field, feat_in, val_in, feat_out, val_out):
+        """The engine's whole mapping (bucket, fold, hash) of a block already in HBM (addresses; in place is
+        fine); asynchronous on the engine's stream."""
+        self._check(self.lib.ffm_engine_bucket_ids_device(self.h, int(nnz), field, feat_in, val_in, feat_out, val_out))
+
     def prepare_device(self, n_rows, nnz, row_ptr, field, feat, val):
         """Look-ahead: group the next block on a side stream (see include/ffm_engine.h)."""
         self._check(self.lib.ffm_engine_prepare_device(self.h, n_rows, nnz, row_ptr, field, feat, val))
@@ -1223,6 +1314,57 @@ class FieldSketch:
     def close(self):
         if self.h:
             self.lib.ffm_engine_sketch_destroy(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ValueHistogram:
+    """How often every (field, bin) of numeric columns occurs, counted exactly on the device
+    (include/ffm_engine.h "Value buckets").  FFM only.  Needs no engine."""
+
+    def __init__(self, n_fields, device=0):
+        self.lib = load_library()
+        self.h = _vp()
+        self.n_fields = int(n_fields)
+        self._check(self.lib.ffm_engine_valhist_create(self.n_fields, int(device), ctypes.byref(self.h)))
+
+    def _check(self, rc):
+        if rc != 0:
+            raise EngineError(rc, self.lib.ffm_engine_last_error().decode())
+
+    def add(self, field, val, zero_copy=False):
+        """Counts the entries (field[p], val[p]); field None: entry p is field p mod n_fields.  zero_copy:
+        page-locked (ffm_engine_pin_host) int32 / float32 arrays, read in place.  Back once they may be reused."""
+        if not (isinstance(val, np.ndarray) and val.dtype == np.float32 and val.flags.c_contiguous):
+            val = np.ascontiguousarray(val, np.float32)
+        if val.ndim != 1:
+            raise ValueError("val: a one-dimensional float32 array")
+        field = FieldSketch._ids(field, "field")
+        if field is not None and field.size != val.size:
+            raise ValueError("field and val must be equally long")
+        self._check(self.lib.ffm_engine_valhist_add(self.h, val.size, None if field is None else field.ctypes.data,
+                                                    val.ctypes.data, int(bool(zero_copy))))
+
+    def add_device(self, nnz, field, val):
+        """The same for arrays in device memory (addresses; field may be None); asynchronous."""
+        self._check(self.lib.ffm_engine_valhist_add_device(self.h, int(nnz), field, val))
+
+    def read(self):
+        """(counts uint64 [n_fields, BUCKET_BINS], n_valid, n_bad, n_nan) after everything added so far."""
+        counts = np.zeros((self.n_fields, BUCKET_BINS), np.uint64)
+        nv, nb, nn = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self.lib.ffm_engine_valhist_read(self.h, counts.ctypes.data, ctypes.byref(nv), ctypes.byref(nb),
+                                                     ctypes.byref(nn)))
+        return counts, int(nv.value), int(nb.value), int(nn.value)
+
+    def close(self):
+        if self.h:
+            self.lib.ffm_engine_valhist_destroy(self.h)
             self.h = _vp()
 
     def __del__(self):

@@ -143,7 +143,19 @@ const std::string_view cmd_help =
     "              \tdefault:the smallest B with 2^B >= 4 * n_feats, at least 16 and at most 30\n"
     "--rare_ids_out <file>: write the keep-map of --min_count (or of --rare_ids @FILE) there\tdefault:(none)\n"
     "--rare_ids <@file>: fold by the keep-map an earlier run wrote with --rare_ids_out instead of counting one; the run\n"
-    "              goes on exactly as the counting run did.  Needs --hash_feats true; one GPU\tdefault:(none)\n";
+    "              goes on exactly as the counting run did.  Needs --hash_feats true; one GPU\tdefault:(none)\n"
+    "--bucket_fields <list>: numeric fields, such as 0-12,20, whose entries field:id:value become field:bucket:1 with\n"
+    "              quantile buckets of the value.  --train_data is streamed once before a model exists (ahead of the\n"
+    "              --min_count and --field_ranges counted passes) and the device counts a histogram of 65536 value bins per\n"
+    "              field; the host cuts each into --n_buckets buckets of equal mass.  Prints `field f: N values in D bins ->\n"
+    "              K buckets` per field and `value buckets: counted R rows (E entries, X nan) in S s`.  A bucketed entry is\n"
+    "              never folded by --min_count; --field_ranges counted takes such a field's count as its edges + 2.  Needs\n"
+    "              --hash_feats true, an FFM model and --train_data; one GPU; not with --resume_from or --buckets (a saved\n"
+    "              model takes its table from --buckets @FILE: it is not in the checkpoint)\tdefault:(none)\n"
+    "--n_buckets <B>: buckets per field of --bucket_fields, 2 .. 256\tdefault:32\n"
+    "--buckets_out <file>: write the bucket table of --bucket_fields (or of --buckets @FILE) there\tdefault:(none)\n"
+    "--buckets <@file>: bucket by the table an earlier run wrote with --buckets_out instead of counting one; the run goes\n"
+    "              on exactly as the counting run did.  Needs --hash_feats true and an FFM model; one GPU\tdefault:(none)\n";
 
 static bool assign_bool(std::string arg) {
   std::transform(arg.begin(), arg.end(), arg.begin(), [](unsigned char c) { return std::tolower(c); });
@@ -285,6 +297,17 @@ void config_options::parse_option(int argc, char *argv[]) {
         rare_bits = static_cast<int>(x);
       }
     }
+    else if (k == "--n_buckets") {
+      long long x = 0;
+      size_t used = 0;
+      try { x = std::stoll(v, &used); } catch (const std::exception &) { used = 0; }
+      if (used != v.size() || used == 0 || x < 2 || x > 256)
+        throw std::invalid_argument("--n_buckets takes a number of buckets in [2, 256], got `" + v + "`");
+      n_buckets = static_cast<int>(x);
+    }
+    else if (k == "--bucket_fields") bucket_fields = v;
+    else if (k == "--buckets") buckets = v;
+    else if (k == "--buckets_out") buckets_out = v;
     else if (k == "--rare_ids") rare_ids = v;
     else if (k == "--rare_ids_out") rare_ids_out = v;
     else if (k == "--predict_data") predict_path = v;
@@ -369,6 +392,53 @@ void config_options::parse_option(int argc, char *argv[]) {
   }
   if (!rare_ids_out.empty() && min_count <= 1 && rare_ids.empty())
     throw std::invalid_argument("--rare_ids_out writes the keep-map of rare ids: it needs --min_count > 1 or --rare_ids @FILE");
+  if (!bucket_fields.empty() || !buckets.empty()) {
+    // buckets become raw ids of one whole FFM model on one GPU (refused here, before a device is opened)
+    const std::string what = !bucket_fields.empty() ? "--bucket_fields " + bucket_fields + " " : "--buckets " + buckets + " ";
+    if (!bucket_fields.empty() && !buckets.empty())
+      throw std::invalid_argument("--bucket_fields counts a bucket table and --buckets names one: give one of the two");
+    if (!buckets.empty() && (buckets[0] != '@' || buckets.size() == 1))
+      throw std::invalid_argument("--buckets takes @FILE, the table --buckets_out wrote, got `" + buckets + "`");
+    if (!hash_feats) throw std::invalid_argument(what + "turns values into ids that are then hashed: it needs --hash_feats true");
+    if (model_type != "FFM") throw std::invalid_argument(what + "buckets the values of fields, which only FFM rows have (got --model_type " + model_type + ")");
+    if (n_gpus > 1) throw std::invalid_argument(what + "buckets on one whole model on one GPU: --n_gpus > 1 is not allowed with it");
+    if (!bucket_fields.empty()) {
+      if (!resume_from.empty())
+        throw std::invalid_argument(what + "is not allowed with --resume_from: a saved model's buckets are the ones it was trained with; "
+                                           "write them with --buckets_out and pass --buckets @FILE");
+      if (train_path.empty()) throw std::invalid_argument(what + "counts the values of the training file: it needs --train_data");
+      // LIST: items a or a-b, comma separated
+      std::vector<char> chosen(static_cast<size_t>(std::max(n_fields, 0)), 0);
+      size_t at = 0;
+      const std::string &s = bucket_fields;
+      auto number = [&]() -> long long {
+        const size_t from = at;
+        while (at < s.size() && std::isdigit(static_cast<unsigned char>(s[at]))) at++;
+        if (at == from || at - from > 9) throw std::invalid_argument("--bucket_fields takes a list such as 0-12,20, got `" + s + "`");
+        return std::stoll(s.substr(from, at - from));
+      };
+      for (;;) {
+        const long long a = number();
+        long long b = a;
+        if (at < s.size() && s[at] == '-') {
+          at++;
+          b = number();
+        }
+        if (b < a) throw std::invalid_argument("--bucket_fields takes a list such as 0-12,20, got `" + s + "`");
+        if (b >= n_fields)
+          throw std::invalid_argument(what + "names field " + std::to_string(b) + ", which is not a field of this model: --n_fields is " + std::to_string(n_fields));
+        for (long long f = a; f <= b; f++) chosen[static_cast<size_t>(f)] = 1;
+        if (at == s.size()) break;
+        if (s[at] != ',') throw std::invalid_argument("--bucket_fields takes a list such as 0-12,20, got `" + s + "`");
+        at++;
+      }
+      bucket_field_list.clear();
+      for (int f = 0; f < n_fields; f++)
+        if (chosen[static_cast<size_t>(f)]) bucket_field_list.push_back(f);
+    }
+  }
+  if (!buckets_out.empty() && bucket_fields.empty() && buckets.empty())
+    throw std::invalid_argument("--buckets_out writes the bucket table: it needs --bucket_fields or --buckets @FILE");
   if (auc_key_field >= 0) {
     // the grouped AUC rides on the AUC lines of one whole FFM model (refused here, before a device is opened)
     const std::string what = "--auc_key_field " + std::to_string(auc_key_field) + " ";

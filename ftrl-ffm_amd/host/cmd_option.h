@@ -75,6 +75,17 @@ struct config_options {
   int rare_map_bits = 0;
   std::vector<uint64_t> rare_words;
 
+  // --bucket_fields LIST (such as 0-12,20) with --n_buckets B: the numeric fields whose values become quantile buckets
+  // (include/ffm_engine.h "Value buckets"), their histograms counted on the device in one pass over --train_data before
+  // a model exists.  --buckets @FILE: the table of an earlier run (value_buckets.h); --buckets_out FILE writes it.
+  // bucket_field_list: the parsed LIST, ascending, no repeats.  bucket_n_edges / bucket_edges: what either resolved to,
+  // as ffm_engine_set_buckets takes it (filled by main.cpp before a model exists; empty: no table).
+  std::string bucket_fields, buckets, buckets_out;
+  int n_buckets = 32;
+  std::vector<int> bucket_field_list;
+  std::vector<int32_t> bucket_n_edges;
+  std::vector<uint16_t> bucket_edges;
+
   void parse_option(int argc, char *argv[]);  // throws std::invalid_argument like the reference
 };
 

@@ -59,6 +59,8 @@ std::vector<int32_t> count_field_ranges(const config_options &opt) {
   long long total = 0;
   for (int f = 0; f < F; f++) {
     count[f] = std::max<long long>(1, std::llround(est[f]));
+    // --bucket_fields / --buckets: a bucketed field's ids are its buckets and the NaN id, whatever its one raw id
+    if (!opt.bucket_n_edges.empty() && opt.bucket_n_edges[static_cast<size_t>(f)] >= 0) count[f] = opt.bucket_n_edges[static_cast<size_t>(f)] + 2;
     total += count[f];
   }
   std::vector<int32_t> fs(static_cast<size_t>(F) + 1);

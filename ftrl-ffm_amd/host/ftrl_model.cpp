@@ -139,6 +139,13 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
     if (rc == FFM_E_INVALID || rc == FFM_E_UNSUPPORTED) throw std::invalid_argument(std::string("rare ids: ") + ffm_engine_last_error());
     check(rc, "ffm_engine_set_rare_fold");
   }
+  // --bucket_fields / --buckets: the table main.cpp resolved, on training, serving and scoring engines alike
+  // (include/ffm_engine.h "Value buckets")
+  if (!opt.bucket_n_edges.empty()) {
+    rc = ffm_engine_set_buckets(eng_, opt.bucket_n_edges.data(), opt.bucket_edges.data());
+    if (rc == FFM_E_INVALID || rc == FFM_E_UNSUPPORTED) throw std::invalid_argument(std::string("value buckets: ") + ffm_engine_last_error());
+    check(rc, "ffm_engine_set_buckets");
+  }
   if (serving_)
     std::printf("serving weights: %s, %lld bytes of model\n", opt.serve_weights.c_str(), static_cast<long long>(ffm_engine_model_bytes(eng_)));
   row_len_ = ffm_engine_row_len(eng_);

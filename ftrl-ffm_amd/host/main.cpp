@@ -13,6 +13,7 @@
 #include "rare_ids.h"
 #include "sample_weights.h"
 #include "trainer.h"
+#include "value_buckets.h"
 
 int main(int argc, char *argv[]) {
   config_options opt;
@@ -90,6 +91,9 @@ int main(int argc, char *argv[]) {
     // --min_count T | --rare_ids @FILE, --rare_ids_out: the keep-map every engine of this run folds rare ids by
     // (--min_count: one pass over the training file, on the device, before a model exists) -- ahead of the ranges,
     // which --field_ranges counted then sizes by the ids that stay
+    // --bucket_fields LIST | --buckets @FILE, --buckets_out: the bucket table every engine of this run maps numeric
+    // fields by (--bucket_fields: one pass over the training file, on the device) -- ahead of both
+    ftrl::resolve_value_buckets(opt);
     ftrl::resolve_rare_ids(opt);
     ftrl::resolve_field_ranges(opt);
     if (opt.online) {

@@ -773,6 +773,76 @@ int ffm_engine_fold_ids_host(int32_t n_fields, int32_t bits, const uint64_t *wor
                              const int32_t *feat_in, int32_t *feat_out);
 int ffm_engine_rare_slots_host(int32_t bits, int32_t nnz, const int32_t *field, const int32_t *feat, uint32_t *slot);
 
+/* ---- Value buckets: numeric fields as quantile buckets -------------------------------------------------
+ * A numeric column (a count, a price, a dwell time) is field:one_id:value in libffm text, and the value
+ * multiplies straight into the linear term and every pair term: an unbounded count scales gradients by
+ * orders of magnitude, and one latent row per field cannot express a non-monotone effect.  The usual remedy
+ * is quantile buckets.  Here a value histogram per field is counted on the device before a model exists, the
+ * host cuts it into buckets of equal mass with exact integers, and every place an engine hashes replaces
+ * (id, value) by (bucket, 1.0f).  All of it is integer work on the float's bit pattern -- no floating-point
+ * instruction, so denormal modes cannot matter.
+ *   key(v)     u = bits(v); if (u & 0x7fffffff) == 0 then u = 0 (-0.0 and +0.0 give one key);
+ *              key = (u >> 31) ? ~u : (u | 0x80000000), which preserves the order of the values.
+ *              bin(v) = key >> 16, one of FFM_BUCKET_BINS = 65536: sign, exponent and 7 mantissa bits, a
+ *              relative resolution below 1 %.  NaN is (u & 0x7fffffff) > 0x7f800000; a NaN has no bin.
+ *   histogram  ffm_valhist (FFM only, 1 <= n_fields <= 4096): n_fields x 65536 64-bit counters in HBM, all
+ *              zero at create, plus n_valid, n_bad and n_nan.  An entry (field, val) COUNTS iff
+ *              0 <= field < n_fields (n_valid); every other entry adds one to n_bad and nothing else.  A
+ *              counting NaN adds one to n_nan and to no bin.  field == NULL: entry p of the call is field
+ *              p mod n_fields, as for a sketch.  Counts are EXACT whatever the order, the batching or the
+ *              split of the entries across calls (integer sums only).  _add (zero_copy 0 / 1), _add_device,
+ *              _read and _destroy: the arguments, the chunking and the refusals of the sketch's calls.
+ *   edges      ffm_engine_bucket_edges (host arithmetic): one field's counts c[0 .. 65535], N = sum c,
+ *              B = n_buckets in [2, 256].  For j = 1 .. B - 1: t_j = (j N + B - 1) / B in integer division,
+ *              e_j = the smallest bin whose inclusive cumulative count is >= t_j.  The edges are the e_j
+ *              with repeats dropped, strictly ascending, at most FFM_BUCKET_MAX_EDGES = 255.  N == 0: no
+ *              edges.  bucket(bin) = the number of edges < bin, in [0, n_edges].
+ *   table      n_edges [n_fields] (-1: the field is not bucketed) and edges [n_fields][FFM_BUCKET_MAX_EDGES]
+ *              (field f's edges are the first n_edges[f] of its row; the rest is not read).
+ *   apply      ffm_engine_set_buckets copies a table into HBM (n_edges == NULL: takes it off and frees it).
+ *              The engine must have FFM_FLAG_HASH_IDS and be FFM (else FFM_E_INVALID); training and serving
+ *              engines alike; a group's or a shard's engine is FFM_E_UNSUPPORTED; edges that do not ascend
+ *              strictly or n_edges > 255 are FFM_E_INVALID; the engine must be idle, as for
+ *              ffm_engine_set_rare_fold.  From then on an entry (f, id, v) with id >= 0, 0 <= f < n_fields
+ *              and n_edges[f] >= 0 becomes id' = bucket(bin(v)), v' = 1.0f; a NaN gives id' =
+ *              FFM_BUCKET_NAN_ID = 65536.  The raw id is ignored (a numeric column has one).  A bucketed
+ *              entry is NEVER rare-folded -- its id is one of at most 257 chosen by the data's own
+ *              quantiles -- and then goes through the hash of "Hashed ids".  Every other entry takes the
+ *              path it takes without a table: fold if there is a keep-map, then hash.  A block with
+ *              val == NULL is, as ever, the block with an array of 1.0f.
+ *   where      everywhere an engine hashes rows that came with (or without) their values: the upload kernel
+ *              of the pipelined calls, the in-place kernel behind the synchronous copies (training,
+ *              prediction, ffm_engine_score_candidates, ffm_engine_predict_ablated).
+ *              ffm_engine_bucket_ids_device is the whole mapping (bucket, fold, hash) for blocks already in
+ *              HBM; ffm_engine_hash_ids_device and the other _device entry points keep taking arrays as they
+ *              are.  An engine without a table runs the kernels, launches and kernel arguments it always ran.
+ *   host       ffm_engine_bucket_ids_host is the bucket step alone, bit for bit, and needs no device
+ *              (field == NULL: entry p is field p mod n_fields; val_in == NULL: every value is 1.0f);
+ *              composed with the fold of the entries it left alone and ffm_engine_hash_ids_host it gives the
+ *              model ids.
+ * OUT OF SCOPE  groups, shards and several GPUs; LR / FM; buckets learnt while training; keeping the value
+ *   next to the bucket; recording the table in checkpoints; counting evaluation data. */
+typedef struct ffm_valhist ffm_valhist;
+#define FFM_BUCKET_BINS 65536
+#define FFM_BUCKET_MAX_EDGES 255
+#define FFM_BUCKET_NAN_ID 65536
+int ffm_engine_valhist_create(int32_t n_fields, int32_t device_id, ffm_valhist **out);
+int ffm_engine_valhist_add(ffm_valhist *s, int32_t nnz, const int32_t *field, const float *val, int32_t zero_copy);
+int ffm_engine_valhist_add_device(ffm_valhist *s, int32_t nnz, const int32_t *field, const float *val);
+int ffm_engine_valhist_read(ffm_valhist *s, uint64_t *counts /* [n_fields][FFM_BUCKET_BINS], may be NULL */,
+                            int64_t *n_valid, int64_t *n_bad, int64_t *n_nan);
+void ffm_engine_valhist_destroy(ffm_valhist *s);
+int ffm_engine_set_buckets(ffm_engine *e, const int32_t *n_edges /* [n_fields] or NULL */,
+                           const uint16_t *edges /* [n_fields][FFM_BUCKET_MAX_EDGES] */);
+int ffm_engine_bucket_ids_device(ffm_engine *e, int32_t nnz, const int32_t *field, const int32_t *feat_in, const float *val_in,
+                                 int32_t *feat_out, float *val_out);
+/* pure host arithmetic, no device: */
+int ffm_engine_bucket_edges(const uint64_t *counts /* [FFM_BUCKET_BINS] */, int32_t n_buckets,
+                            uint16_t *edges /* [FFM_BUCKET_MAX_EDGES] */, int32_t *n_edges);
+int ffm_engine_bucket_ids_host(int32_t n_fields, const int32_t *n_edges, const uint16_t *edges, int32_t nnz, const int32_t *field,
+                               const int32_t *feat_in, const float *val_in, int32_t *feat_out, float *val_out,
+                               uint8_t *bucketed /* [nnz], may be NULL */);
+
 /* ---- Rows without values: val == NULL is 1.0f -------------------------------------------------------
  * Click logs are categorical: after hashing every entry of a libffm file is field:id:1, and an array of
  * 1.0f is a third of a block's bytes over PCIe (half of what is left once the field array stays at home).
