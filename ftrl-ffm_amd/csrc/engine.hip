@@ -56,6 +56,7 @@
 #include "kernels_sketch.h"
 #include "kernels_idcount.h"
 #include "kernels_valhist.h"
+#include "kernels_norm.h"
 #include "metrics_host.h"
 
 using namespace ftrl_dev;
@@ -122,6 +123,7 @@ enum KernelId {
   K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC, K_PUSH_SCORES, K_SERVE_ROW,
   K_SERVE_CTX, K_SERVE_CAND,
   K_KEYED_CAPTURE, K_KEYED_SORT_HIST, K_KEYED_SORT_SCAN, K_KEYED_SORT_SCATTER, K_KEYED_RANK,
+  K_UPLOAD, K_NORM_ROWS,
   K_COUNT
 };
 const char *kKernelNames[K_COUNT] = {
@@ -129,7 +131,8 @@ const char *kKernelNames[K_COUNT] = {
     "linear_update_kernel", "bias_update_kernel", "update_kernel", "update_few_kernel", "update_walk_kernel", "update_giant_kernel",
     "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel", "push_scores_kernel", "serve_wave_kernel",
     "serve_context_kernel", "serve_candidate_kernel",
-    "keyed_capture_kernel", "keyed_sort_hist_kernel", "keyed_sort_scan_kernels", "keyed_sort_scatter_kernel", "keyed_rank_kernels"};
+    "keyed_capture_kernel", "keyed_sort_hist_kernel", "keyed_sort_scan_kernels", "keyed_sort_scatter_kernel", "keyed_rank_kernels",
+    "pull_block_kernel", "normalize_rows_kernel"};
 
 struct ProfRec {
   int kid;
@@ -412,6 +415,14 @@ struct ffm_engine {
   // ffm_engine_set_buckets (engine_valhist.h): the bucket table in HBM (one allocation of its own, n_edges first, freed
   // when the table is taken off or the engine destroyed); n_edges == nullptr: none, and nothing here is read
   ftrl_hash::Buckets buckets{};
+  // FFM_FLAG_NORM_ROWS (engine_norm.h): every row of a host block is scaled to unit length on the device behind its
+  // upload and id rewriting.  d_norm_unscaled: [1] rows the kernel left as they came (made at create on a flagged
+  // engine, else by the first ffm_engine_normalize_rows_device); norm_rows: rows it was launched on (the staging
+  // thread counts too); grid_norm: its workgroups at the most, a run of 64 rows each (FFM_GRID_NORM)
+  bool norm_rows_on = false;
+  unsigned long long *d_norm_unscaled = nullptr;
+  std::atomic<int64_t> norm_rows{0};
+  int grid_norm = 1024;
   // ffm_engine_refresh_weights (engine_refresh.h): its six counters and its grid, both made by the first call
   unsigned long long *d_refresh = nullptr;
   int refresh_grid = 0;
@@ -834,6 +845,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 
 #include "engine_state.h"
 #include "engine_hash.h"
+#include "engine_norm.h"
 #include "engine_step.h"
 #include "engine_stage.h"
 #include "engine_refresh.h"

@@ -7,6 +7,7 @@
 
 static int hash_ids_check(int32_t model_type, int32_t n_feats, int32_t n_fields, const int32_t *field_start);  // (engine_hash.h)
 static int serve_create_check(const ffm_engine_config *cfg);  // (engine_serve.h)
+static int norm_ready(ffm_engine *e);  // (engine_norm.h)
 
 // What the environment sets.  An empty optional: the switch is not set, and the default -- an ffm_engine member's
 // initializer, or what a later step works out for the shape -- stands.
@@ -15,7 +16,7 @@ struct Switches {
   int metrics = 0;        // FFM_ENGINE_METRICS=<mask>: channels on from the start (rank 0 of a group keeps them)
   char row_refresh = 0;   // FFM_ENGINE_ROW_REFRESH: its first character ('0' .. '3')
   std::optional<bool> serial, super_wait, prep_after_row, pull_after_row, eval_defer_off, predict_waves, few_stage, own_sort;
-  std::optional<int> update_split, update_order, wide_max_nnz, grid_pull, grid_push, grid_hot, grid_small, grid_walk, grid_giant;
+  std::optional<int> update_split, update_order, wide_max_nnz, grid_pull, grid_push, grid_hot, grid_small, grid_walk, grid_giant, grid_norm;
   std::optional<int> row_threads, row_park, row_park_budget, row_hold, super_min;
   std::optional<int> range_sort;  // FFM_RANGE_SORT: 0 off, 1 on, more: that many equal ranges
 };
@@ -59,6 +60,7 @@ static Switches read_switches() {
   if (const char *sv = std::getenv("FFM_WIDE_NNZ")) sw.wide_max_nnz = std::atoi(sv);
   if (const char *sv = std::getenv("FFM_GRID_PULL")) sw.grid_pull = std::max(1, std::atoi(sv));
   if (const char *sv = std::getenv("FFM_GRID_PUSH")) sw.grid_push = std::min(24, std::max(1, std::atoi(sv)));
+  if (const char *sv = std::getenv("FFM_GRID_NORM")) sw.grid_norm = std::max(1, std::atoi(sv));
   if (const char *sv = std::getenv("FFM_GRID_HOT")) sw.grid_hot = std::max(1, std::atoi(sv));
   if (const char *sv = std::getenv("FFM_GRID_SMALL")) sw.grid_small = std::max(1, std::atoi(sv));
   if (const char *sv = std::getenv("FFM_GRID_WALK")) sw.grid_walk = std::max(1, std::atoi(sv));
@@ -93,6 +95,9 @@ static int check_config(const ffm_engine_config *cfg, bool hash_ids) {
     return fail(FFM_E_UNSUPPORTED, "field-pair sharding applies to FFM only");
   if (cfg->n_shards > 1 && cfg->n_fields > 64)
     return fail(FFM_E_UNSUPPORTED, "field-pair sharding supports up to 64 fields");
+  // FFM_FLAG_NORM_ROWS (engine_norm.h): a row's length is a sum over ALL of its entries
+  if ((cfg->flags & FFM_FLAG_NORM_ROWS) && cfg->n_shards > 1)
+    return fail(FFM_E_INVALID, "FFM_FLAG_NORM_ROWS needs a whole model (n_shards == 1): a shard does not own whole rows");
   // FFM_FLAG_SERVE_F32 / _F16: a serving engine (engine_serve.h) -- its shape is checked like the arguments above
   if (cfg->flags & (FFM_FLAG_SERVE_F32 | FFM_FLAG_SERVE_F16))
     if (int rc_s = serve_create_check(cfg)) return rc_s;
@@ -121,6 +126,7 @@ static void apply_switches(ffm_engine *e, const Switches &sw) {
   take(e->wide_max_nnz, sw.wide_max_nnz);
   take(e->grid_pull, sw.grid_pull);
   take(e->grid_push, sw.grid_push);
+  take(e->grid_norm, sw.grid_norm);
   take(e->grid_hot, sw.grid_hot);
   take(e->grid_small, sw.grid_small);
   take(e->grid_walk, sw.grid_walk);
@@ -552,6 +558,8 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
     return rc;
   for (int si = 0; si < ffm_engine::kSets; si++)
     if ((rc = alloc_set(e, si, shared))) return rc;
+  e->norm_rows_on = (cfg->flags & FFM_FLAG_NORM_ROWS) != 0;
+  if (e->norm_rows_on && (rc = norm_ready(e))) return rc;
   if ((rc = choose_sort(e, sw)) || (rc = prove_fast_math(e)) || (rc = opt_in_lds(e)) || (rc = init_weights(e))) return rc;
   if (sw.metrics && cfg->shard_rank == 0)
     if ((rc = ffm_engine_metrics_enable(e, sw.metrics))) return rc;

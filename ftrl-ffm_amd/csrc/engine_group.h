@@ -149,6 +149,9 @@ int ffm_group_create(const ffm_engine_config *cfg, int32_t n, const int32_t *dev
   *out = nullptr;
   if (cfg->flags & (FFM_FLAG_SERVE_F32 | FFM_FLAG_SERVE_F16))
     return fail(FFM_E_UNSUPPORTED, "a serving engine is one whole model on one device: not inside ffm_group_create");
+  if (cfg->flags & FFM_FLAG_NORM_ROWS)
+    return fail(FFM_E_INVALID, "FFM_FLAG_NORM_ROWS needs a whole model on one device: not inside ffm_group_create "
+                               "(a shard does not own whole rows)");
   auto *g = new (std::nothrow) ffm_group();
   if (!g) return fail(FFM_E_NOMEM, "out of host memory");
   bool distinct = true;

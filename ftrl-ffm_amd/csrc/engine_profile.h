@@ -19,10 +19,14 @@ static int profile_totals(ffm_engine *e, double *ms, int *n);
 
 // The kernel with the largest total time among those on the step's critical path.  The look-ahead
 // grouping is left out: it runs beside the step on its own queue, and its "time" is mostly waiting.
+// So are the labels of what runs ahead of it there on an engine with FFM_FLAG_NORM_ROWS (engine_norm.h), which
+// ffm_engine_profile_dump lists: "normalize_rows_kernel" and, to read it next to, "pull_block_kernel" (the staged
+// block's upload; no label on any other engine).
 static int dominant_kernel(const double *ms) {
   int best = K_ROW;
   for (int k = 0; k < K_COUNT; k++) {
     if (k == K_GROUP_KEYS || k == K_GROUP_SORT || k == K_GROUP_FINISH) continue;
+    if (k == K_UPLOAD || k == K_NORM_ROWS) continue;  // (the prep stream's too: a staged block's upload and its rows' normalisation)
     if (ms[k] > ms[best]) best = k;
   }
   return best;

@@ -28,6 +28,9 @@ static int cand_common_check(ffm_engine *e, int32_t n_req, int32_t n_cand) {
   if (!serving(e))
     return fail(FFM_E_UNSUPPORTED, "score_candidates needs a serving engine (FFM_FLAG_SERVE_F32 / _F16): "
                                    "ffm_engine_pack_weights copies a training engine's weights into one");
+  if (e->norm_rows_on)
+    return fail(FFM_E_INVALID, "score_candidates is not available on an engine with FFM_FLAG_NORM_ROWS: the shared context "
+                               "terms would need a scale per candidate");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   if (int rc_e = eval_launch_pending(e)) return rc_e;
   if (n_req < 0 || n_cand < 0) return fail(FFM_E_INVALID, "negative n_req / n_cand");

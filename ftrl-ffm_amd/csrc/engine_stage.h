@@ -191,6 +191,14 @@ static int claim_slot(ffm_engine *e, const Rows &host, const float *weight, int3
 // bucket: the claim's bucket table and val's own part (ffm_engine_set_buckets); those launches write val themselves.
 static void launch_upload(ffm_engine *e, hipStream_t st, int grid, const PullHashJob &hj, const ftrl_hash::Rare &rare,
                           const PullBucketPart &bucket, float *ones, unsigned n_ones) {
+  // (an engine with FFM_FLAG_NORM_ROWS, while profiling is on -- submissions then all come from the caller's thread --,
+  // times it as "pull_block_kernel", the figure to read normalize_rows_kernel's next to; on every other engine the
+  // upload carries no label, as always)
+  struct Timed {
+    ffm_engine *e; hipStream_t st;
+    Timed(ffm_engine *e_, hipStream_t st_) : e(e_->prof_on && e_->norm_rows_on ? e_ : nullptr), st(st_) { if (e) e->prof_begin(K_UPLOAD, st); }
+    ~Timed() { if (e) e->prof_end(st); }
+  } timed(e, st);
   auto launch = [&](auto weighted, auto hashed, auto folded, const auto &arg) {
     constexpr bool W = decltype(weighted)::value, H = decltype(hashed)::value, R = decltype(folded)::value;
     if (n_ones) hipLaunchKernelGGL((pull_block_kernel<W, H, R, false, float *, unsigned>), dim3(grid), dim3(256), 0, st, arg, ones, n_ones);
@@ -269,7 +277,10 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
   // (val == NULL: the upload writes the slot's values -- every time, whatever the slot held before)
   float *const ones = sl.val;
   const unsigned n_ones = val ? 0u : static_cast<unsigned>(nnz);
-  rc = e->submit([e, this_slot, free_ev, hjob = claim.job, rare = claim.rare, bucket = claim.bucket, plan, seq, grid_pull, timed, ones, n_ones]() -> int {
+  // FFM_FLAG_NORM_ROWS: the slot's values in place, right behind the upload that writes them and the ids
+  const NormJob norm = e->norm_rows_on ? norm_job(e, Rows{n_rows, nnz, sl.row_ptr, claim.has_field ? sl.field : nullptr, sl.feat, sl.val, nullptr}, sl.val)
+                                       : NormJob{};
+  rc = e->submit([e, this_slot, free_ev, hjob = claim.job, rare = claim.rare, bucket = claim.bucket, plan, seq, grid_pull, timed, ones, n_ones, norm]() -> int {
     ScopedTimer tm("stage:submit");
     ffm_engine::Slot &s2 = e->slots[this_slot];
     int rc2 = FFM_OK;
@@ -280,6 +291,7 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
       // launches it costs nothing, beside the row kernel, which is bound by the bytes it moves, it does)
       if (e->pull_after_row && plan.ws >= 0) HIP_TRY(hipStreamWaitEvent(e->prep, e->prep_after_row ? e->ev_row_done[plan.ws] : e->ev_set_free[plan.ws], 0));
       launch_upload(e, e->prep, grid_pull, hjob, rare, bucket, ones, n_ones);
+      if (e->norm_rows_on) launch_normalize_rows(e, e->prep, norm);  // (on the slot's device copy: the caller's arrays are never written)
       HIP_TRY(hipEventRecord(s2.ev_copied, e->prep));
       return prepare_submit(e, plan, timed);
     };
@@ -460,6 +472,8 @@ int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const i
   if (claim.was_used && sl.free_ev) HIP_TRY(hipStreamWaitEvent(e->prep, sl.free_ev, 0));  // nothing reads its device arrays
   // (no values came: the upload writes the slot's)
   launch_upload(e, e->prep, e->grid_pull, claim.job, claim.rare, claim.bucket, sl.val, val ? 0u : static_cast<unsigned>(nnz));
+  if (e->norm_rows_on)  // (FFM_FLAG_NORM_ROWS: the slot's values in place, behind the upload)
+    launch_normalize_rows(e, e->prep, norm_job(e, Rows{n_rows, nnz, sl.row_ptr, claim.has_field ? sl.field : nullptr, sl.feat, sl.val, nullptr}, sl.val));
   HIP_TRY(hipEventRecord(sl.ev_copied, e->prep));
   slot_commit(e, claim, host, longest, false, zero_copy);
   {

@@ -651,6 +651,8 @@ static int stage_block(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, co
   // FFM_FLAG_HASH_IDS: the ids in place, behind their copy and ahead of every kernel that reads them
   if (e->hash_ids) launch_hash_ids(e, e->stream, nnz, field ? e->d_field : nullptr, e->d_feat, e->d_feat, e->d_val);
   *dev = Rows{n_rows, nnz, e->d_row_ptr, field ? e->d_field : nullptr, e->d_feat, e->d_val, label ? e->d_label : nullptr};
+  // FFM_FLAG_NORM_ROWS: the values in place, behind the ids they are kept by and ahead of every kernel that reads them
+  if (e->norm_rows_on) launch_normalize_rows(e, e->stream, norm_job(e, *dev, e->d_val));
   *row_cap_out = longest;
   return FFM_OK;
 }

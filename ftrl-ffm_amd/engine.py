@@ -16,6 +16,7 @@ FLAG_SKIP_INIT = 1
 FLAG_LEARN = 4
 FLAG_HASH_IDS = 8
 FLAG_SERVE_F32, FLAG_SERVE_F16 = 16, 32
+FLAG_NORM_ROWS = 64
 SERVE_FLAGS = {None: 0, "none": 0, "f32": FLAG_SERVE_F32, "f16": FLAG_SERVE_F16}
 E_INVALID, E_DEVICE, E_NOMEM, E_CAPACITY, E_UNSUPPORTED = -1, -2, -3, -4, -5  # FFM_E_*
 
@@ -259,6 +260,11 @@ ABI = [
     ("ffm_engine_sync_moved", ctypes.c_int, [_vp, _i32p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     ("ffm_engine_get_rows_raw", ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p, _vp]),
     ("ffm_engine_set_rows_raw", ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _f32p, _vp]),
+    # every row scaled to unit length on the device (include/ffm_engine.h "Normalised rows")
+    ("ffm_engine_normalize_rows_device", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    ("ffm_engine_normalize_rows_host", ctypes.c_int,
+     [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, _f32p]),
+    ("ffm_engine_norm_stats", ctypes.c_int, [_vp, ctypes.c_int32, _i64p, _i64p]),
 ]
 SKETCH_REGS = 16384  # FFM_SKETCH_REGS
 RARE_ID = 2 ** 31 - 1  # FFM_RARE_ID
@@ -403,6 +409,61 @@ def hash_ids(field, feat, n_feats, field_start=None, model="ffm", n_fields=None)
         raise ValueError("field and feat must be equally long")
     out = np.empty_like(feat)
     rc = lib.ffm_engine_hash_ids_host(mt, int(n_feats), int(n_fields), _i(fs), feat.size, _i(fld), _i(feat), _i(out))
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
+    return out
+
+
+def _norm_args(row_ptr, field, feat, val, n_fields, model):
+    """normalize_rows / normalize_rows_host: the arrays as int32 / float32 and the model type, checked."""
+    mt = MODEL_TYPES[model.upper()] if isinstance(model, str) else int(model)
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    feat = np.ascontiguousarray(feat, np.int32)
+    fld = None if field is None or mt != FFM else np.ascontiguousarray(field, np.int32)
+    val = None if val is None else np.ascontiguousarray(val, np.float32)
+    if mt == FFM and n_fields is None:
+        raise ValueError("FFM needs n_fields")
+    if row_ptr.ndim != 1 or row_ptr.size < 1 or row_ptr[0] != 0 or np.any(np.diff(row_ptr) < 0) or row_ptr[-1] != feat.size:
+        raise ValueError("row_ptr must ascend from 0 to len(feat)")
+    if (fld is not None and fld.shape != feat.shape) or (val is not None and val.shape != feat.shape):
+        raise ValueError("field, feat and val must be equally long")
+    return mt, row_ptr, fld, feat, val
+
+
+def normalize_rows(row_ptr, field, feat, val, n_feats, n_fields=None, model="ffm"):
+    """What an engine created with normalize=True makes of a block's values (include/ffm_engine.h "Normalised
+    rows"), in numpy: per row s = fl(s + fl(v * v)) over the kept entries in entry order (0 <= feat < n_feats;
+    FFM with a field array also 0 <= field < n_fields), scale = fl(1 / fl(sqrt(s))) where s > 0 and finite, else
+    the row stays as it came; every entry of the row, kept or not, becomes fl(v * scale).  np.float32 scalars
+    throughout: one rounding per operation, sequential on purpose.  val None: ones.  Returns a new float32 array."""
+    mt, row_ptr, fld, feat, val = _norm_args(row_ptr, field, feat, val, n_fields, model)
+    out = np.ones(feat.size, np.float32) if val is None else val.copy()
+    keep = (feat >= 0) & (feat < int(n_feats))
+    if fld is not None:
+        keep &= (fld >= 0) & (fld < int(n_fields))
+    one, inf = np.float32(1.0), np.float32(np.inf)
+    with np.errstate(all="ignore"):
+        for r in range(row_ptr.size - 1):
+            b, e = int(row_ptr[r]), int(row_ptr[r + 1])
+            s = np.float32(0.0)
+            for p in range(b, e):
+                if keep[p]:
+                    s = np.float32(s + np.float32(out[p] * out[p]))
+            if s > 0 and s < inf:
+                scale = np.float32(one / np.float32(np.sqrt(s)))
+                for p in range(b, e):
+                    out[p] = np.float32(out[p] * scale)
+    return out
+
+
+def normalize_rows_host(row_ptr, field, feat, val, n_feats, n_fields=None, model="ffm"):
+    """normalize_rows by the library's plain C++ twin (ffm_engine_normalize_rows_host: the kernel's bits, no
+    device needed)."""
+    lib = load_library()
+    mt, row_ptr, fld, feat, val = _norm_args(row_ptr, field, feat, val, n_fields, model)
+    out = np.empty(feat.size, np.float32)
+    rc = lib.ffm_engine_normalize_rows_host(mt, int(n_feats), int(n_fields or 0), row_ptr.size - 1, _i(row_ptr), _i(fld), _i(feat),
+                                            _f(val), _f(out))
     if rc != 0:
         raise EngineError(rc, lib.ffm_engine_last_error().decode())
     return out
@@ -643,8 +704,10 @@ class Engine:
                  w_beta=1.0, w_l1=0.1, w_l2=5.0, init_mean=0.0, init_stddev=0.02, seed=42,
                  max_batch_rows=8192, max_batch_nnz=None, device_id=0, n_shards=1, shard_rank=0,
                  stream=None, skip_init=False, max_row_nnz=0, learn=False, field_start=None, hash_ids=False,
-                 serve=None):
-        """serve: None = a training engine; "f32" / "f16" = a serving engine (include/ffm_engine.h "Serving
+                 serve=None, normalize=False):
+        """normalize: every row handed over in host memory is scaled to unit Euclidean length on the device before
+        any kernel reads its values (include/ffm_engine.h "Normalised rows"; normalize_rows is the same on the host).
+        serve: None = a training engine; "f32" / "f16" = a serving engine (include/ffm_engine.h "Serving
         engines"): bias, lin_w and a latent table of w alone in fp32 bits or IEEE binary16 -- prediction only."""
         self.lib = load_library()
         if serve not in SERVE_FLAGS:
@@ -661,7 +724,7 @@ class Engine:
         cfg.device_id, cfg.n_shards, cfg.shard_rank = int(device_id), int(n_shards), int(shard_rank)
         cfg.stream = stream
         cfg.flags = ((FLAG_SKIP_INIT if skip_init else 0) | (FLAG_LEARN if learn else 0) | (FLAG_HASH_IDS if hash_ids else 0)
-                     | SERVE_FLAGS[serve])
+                     | SERVE_FLAGS[serve] | (FLAG_NORM_ROWS if normalize else 0))
         cfg.max_row_nnz = int(max_row_nnz)
         self._field_start = None
         if field_start is not None:
@@ -1078,6 +1141,19 @@ class Engine:
         engine's stream."""
         self._check(self.lib.ffm_engine_hash_ids_device(self.h, int(nnz), field, feat_in, feat_out))
 
+    def normalize_rows_device(self, n_rows, nnz, row_ptr, field, feat, val_in, val_out):
+        """normalize_rows of a block already in HBM, for callers of the _device entry points, which take values as
+        they are.  Device addresses; val_out may be val_in; val_in None: ones; field None: LR / FM, or FFM rows
+        whose fields are all valid.  Any engine, normalize=True or not.  Asynchronous on the engine's stream."""
+        self._check(self.lib.ffm_engine_normalize_rows_device(self.h, int(n_rows), int(nnz), row_ptr, field, feat, val_in, val_out))
+
+    def norm_stats(self, reset=False):
+        """(rows normalised since create or the last reset, how many of them were left as they came: zero or
+        non-finite norm)."""
+        rows, left = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self.lib.ffm_engine_norm_stats(self.h, 1 if reset else 0, ctypes.byref(rows), ctypes.byref(left)))
+        return int(rows.value), int(left.value)
+
     def set_rare_fold(self, bits=None, words=None):
         """Folds rare ids in every block handed over from now on (include/ffm_engine.h "Rare ids"): words = a
         keep-map of 2^bits slots (IdCounter.keep); None turns the fold off.  hash_ids=True engines only, idle."""
@@ -1439,7 +1515,8 @@ class Group:
     def __init__(self, devices, model_type="FFM", n_feats=10000, n_fields=8, n_factors=16, w_alpha=1e-4,
                  w_beta=1.0, w_l1=0.1, w_l2=5.0, init_mean=0.0, init_stddev=0.02, seed=42,
                  max_batch_rows=8192, max_batch_nnz=None, skip_init=False, max_row_nnz=0,
-                 field_start=None, learn=False, hash_ids=False):
+                 field_start=None, learn=False, hash_ids=False, normalize=False):
+        """normalize: refused by the library (a shard does not own whole rows); here so that the refusal is the engine's."""
         self.lib = load_library()
         cfg = Config()
         self.lib.ffm_engine_default_config(ctypes.byref(cfg))
@@ -1449,7 +1526,8 @@ class Group:
         cfg.init_mean, cfg.init_stddev, cfg.seed = init_mean, init_stddev, int(seed)
         cfg.max_batch_rows = int(max_batch_rows)
         cfg.max_batch_nnz = int(max_batch_nnz if max_batch_nnz else max_batch_rows * 64)
-        cfg.flags = (FLAG_SKIP_INIT if skip_init else 0) | (FLAG_LEARN if learn else 0) | (FLAG_HASH_IDS if hash_ids else 0)
+        cfg.flags = ((FLAG_SKIP_INIT if skip_init else 0) | (FLAG_LEARN if learn else 0) | (FLAG_HASH_IDS if hash_ids else 0)
+                     | (FLAG_NORM_ROWS if normalize else 0))
         cfg.max_row_nnz = int(max_row_nnz)
         self._field_start = None
         if field_start is not None:

@@ -155,7 +155,16 @@ const std::string_view cmd_help =
     "--n_buckets <B>: buckets per field of --bucket_fields, 2 .. 256\tdefault:32\n"
     "--buckets_out <file>: write the bucket table of --bucket_fields (or of --buckets @FILE) there\tdefault:(none)\n"
     "--buckets <@file>: bucket by the table an earlier run wrote with --buckets_out instead of counting one; the run goes\n"
-    "              on exactly as the counting run did.  Needs --hash_feats true and an FFM model; one GPU\tdefault:(none)\n";
+    "              on exactly as the counting run did.  Needs --hash_feats true and an FFM model; one GPU\tdefault:(none)\n"
+    "--normalize_rows <bool>: instance-wise normalisation, on the device: every row's values are divided by the row's\n"
+    "              Euclidean length, sqrt(sum v^2) over the entries the model keeps, before anything reads them (libffm and\n"
+    "              xLearn do this by default, so their --w_alpha / --w_beta / L1 / L2 carry over); after --hash_feats,\n"
+    "              --min_count and --bucket_fields, a bucketed entry counting as the 1 it became.  A row whose length is zero\n"
+    "              or not finite stays as it came.  Training, evaluation, --predict_data, --serve_weights and\n"
+    "              --field_importance alike (which drops a field after normalising).  Prints `normalized rows: R scaled, U\n"
+    "              left as they came (zero or non-finite norm)`.  The checkpoint records the setting and --resume_from\n"
+    "              refuses the other one; model files and serving deltas do not: a run that scores or serves such a model\n"
+    "              passes the flag again, as it passes --field_ranges @FILE.  One GPU\tdefault:false\n";
 
 static bool assign_bool(std::string arg) {
   std::transform(arg.begin(), arg.end(), arg.begin(), [](unsigned char c) { return std::tolower(c); });
@@ -229,6 +238,7 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--learn") learn = assign_bool(v);
     else if (k == "--refresh_weights") refresh_weights = assign_bool(v);
     else if (k == "--hash_feats") hash_feats = assign_bool(v);
+    else if (k == "--normalize_rows") normalize_rows = assign_bool(v);
     else if (k == "--compact_rows") compact_rows = assign_bool(v);
     else if (k == "--field_importance") field_importance = assign_bool(v);
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
@@ -376,6 +386,9 @@ void config_options::parse_option(int argc, char *argv[]) {
     if (!ranged || model_type != "FFM")
       throw std::invalid_argument("--field_ranges_out writes the fields' id ranges: it needs an FFM model and --field_ranges uniform, counted or @FILE");
   }
+  // a row's length is a sum over all of its entries (refused here, before a device is opened)
+  if (normalize_rows && n_gpus > 1)
+    throw std::invalid_argument("--normalize_rows true scales whole rows, which a shard does not own: --n_gpus > 1 is not allowed with it");
   if (min_count > 1 || !rare_ids.empty()) {
     // the fold works on raw ids, on one whole model on one GPU (refused here, before a device is opened)
     const std::string what = min_count > 1 ? "--min_count " + std::to_string(min_count) + " " : "--rare_ids " + rare_ids + " ";

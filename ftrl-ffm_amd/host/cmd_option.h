@@ -45,6 +45,9 @@ struct config_options {
   bool weights_given = false;  // one of the three was passed: training blocks carry a weight array
   bool refresh_weights = false;  // --refresh_weights: every stored w = W(n, z) before it is evaluated, saved or scored
   bool hash_feats = false;  // --hash_feats: FFM_FLAG_HASH_IDS, ids hashed into their field's id range on the device
+  // --normalize_rows: FFM_FLAG_NORM_ROWS, every row scaled to unit Euclidean length on the device (include/ffm_engine.h
+  // "Normalised rows"); every engine of the run that takes rows, one GPU
+  bool normalize_rows = false;
   // --serve_weights none | f32 | f16: score a saved model from a serving engine (FFM_FLAG_SERVE_F32 / _F16: the
   // weights alone, in fp32 bits or IEEE binary16); only with --resume_from ck --n_epochs 0
   std::string serve_weights = "none";

@@ -55,6 +55,9 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
   // get/set_latent_rows, pull/push_linear, the model files and checkpoints speak MODEL (hashed) ids
   if (opt.hash_feats) cfg.flags |= FFM_FLAG_HASH_IDS;
   hash_ids_ = opt.hash_feats;
+  // --normalize_rows: the device scales every row it is handed to unit length (include/ffm_engine.h "Normalised
+  // rows"); the one-row shims below hand over the row of survivors, which gives what a block gives
+  if (opt.normalize_rows) cfg.flags |= FFM_FLAG_NORM_ROWS;
   compact_rows_ = opt.compact_rows;
   keyed_field_ = opt.auc_key_field;  // (turned on with the AUC channels: enable_metrics)
   keyed_rows_ = opt.auc_key_rows;
@@ -233,6 +236,14 @@ FtrlModel::Wire FtrlModel::wire(const CsrBlock &b, bool staged) {
   if (b.all_ones) { w.val = nullptr; compact_no_val_++; }
   if (staged && model_type == ModelType::FFM && b.one_entry_per_field(n_fields)) { w.field = nullptr; compact_no_field_++; }
   return w;
+}
+
+void FtrlModel::print_norm_rows() {
+  if (!(flags_ & FFM_FLAG_NORM_ROWS)) return;
+  int64_t rows = 0, left = 0;
+  check(ffm_engine_norm_stats(eng_, 0, &rows, &left), "ffm_engine_norm_stats");
+  std::printf("normalized rows: %lld scaled, %lld left as they came (zero or non-finite norm)\n", static_cast<long long>(rows - left),
+              static_cast<long long>(left));
 }
 
 void FtrlModel::print_compact_rows() const {
@@ -785,6 +796,9 @@ FtrlModel::TrainProgress FtrlModel::load_checkpoint(std::string_view file_name) 
   if ((h.flags ^ static_cast<uint32_t>(flags_)) & FFM_FLAG_HASH_IDS)
     throw std::runtime_error(name + ": was saved " + ((h.flags & FFM_FLAG_HASH_IDS) ? "with" : "without") +
                              " --hash_feats, this model is the other variant: the resumed run would not be the interrupted one");
+  if ((h.flags ^ static_cast<uint32_t>(flags_)) & FFM_FLAG_NORM_ROWS)
+    throw std::runtime_error(name + ": was saved " + ((h.flags & FFM_FLAG_NORM_ROWS) ? "with" : "without") +
+                             " --normalize_rows, this model is the other variant: the resumed run would not be the interrupted one");
   int64_t touched = 0;
   // (a serving model is built and loaded once by the CLI; it has no scan to prove that it is fresh)
   if (!serving_) check(ffm_engine_changed_features(eng_, nullptr, 0, &touched), "ffm_engine_changed_features");

@@ -131,6 +131,9 @@ class FtrlModel {
   // --compact_rows: prints `compact rows: V of B blocks without values, F without fields` -- of the B engine
   // calls the block entry points made, how many passed val == NULL / field == NULL (nothing without the flag)
   void print_compact_rows() const;
+  // --normalize_rows: `normalized rows: R scaled, U left as they came (zero or non-finite norm)`, the engine's counts
+  // of every row it took so far (training and evaluation); nothing without the flag
+  void print_norm_rows();
   // AUC accumulated on the device (include/ffm_engine.h "Metrics"), one engine or a group alike:
   // `eval` takes every labelled predict, `train` the pre-update logits of every training block.
   // read_metrics(FFM_METRIC_EVAL / FFM_METRIC_TRAIN) returns the channel's numbers so far (after a

@@ -66,6 +66,7 @@ int main(int argc, char *argv[]) {
       // (--field_importance asks for the same one pass: its lines follow an evaluation)
       if ((opt.auc_key_field >= 0 || opt.field_importance) && opt.epoch <= 0 && !opt.cmd && !opt.eval_path.empty())
         task.evaluate(static_cast<int>(task.progress().epochs_done));
+      task.model_ptr->print_norm_rows();  // (--normalize_rows: one line, after the last epoch or that one evaluation)
       // --field_importance: after the last evaluation, the same model without each field (field_importance.h)
       if (opt.field_importance && !opt.cmd) ftrl::FieldImportance(opt, &*task.model_ptr).run();
       // --refresh_weights: every epoch ended with a refresh and nothing has trained since, so the model, the

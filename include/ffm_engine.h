@@ -116,7 +116,10 @@ enum {
   FFM_FLAG_HASH_IDS = 8,  /* feature ids of HOST rows are hashed into their field's id range on the device
                            * before any kernel reads them: "Hashed ids" below */
   FFM_FLAG_SERVE_F32 = 16, /* a SERVING engine: weights only, for prediction -- "Serving engines" below; */
-  FFM_FLAG_SERVE_F16 = 32  /* its latent table in fp32 bits or in IEEE binary16 (both: FFM_E_INVALID) */
+  FFM_FLAG_SERVE_F16 = 32, /* its latent table in fp32 bits or in IEEE binary16 (both: FFM_E_INVALID) */
+  FFM_FLAG_NORM_ROWS = 64  /* every HOST row is scaled to unit Euclidean length on the device before any kernel
+                            * reads its values (libffm's and xLearn's instance-wise normalisation):
+                            * "Normalised rows" below */
 };
 
 void ffm_engine_default_config(ffm_engine_config *cfg);
@@ -863,6 +866,53 @@ int ffm_engine_bucket_ids_host(int32_t n_fields, const int32_t *n_edges, const u
  *              are: there val == NULL with nnz > 0 stays FFM_E_INVALID.
  * A block that brings its val array runs exactly the launches, kernels and kernel arguments it ran before.
  * No new symbol, no new ABI version: callers that always pass val see no change. */
+
+/* ---- Normalised rows: FFM_FLAG_NORM_ROWS -----------------------------------------------------------------
+ * libffm and xLearn multiply every pair term by 1 / sum(v^2) of its row (their default; --no-norm switches it
+ * off), which is dividing every value by the row's Euclidean length.  An engine created with
+ * FFM_FLAG_NORM_ROWS does that to every block that arrives in HOST memory, on the device, behind the block's
+ * upload and id rewriting and ahead of every kernel that reads val (normalize_rows_kernel, csrc/kernels_norm.h).
+ * The definition, fixed so that host and device agree bit for bit -- per row, in entry order, over the entries
+ * the model keeps (LR / FM: 0 <= feat < n_feats; FFM also 0 <= field < n_fields; on the ids as the kernels see
+ * them: after hashing, rare folding and bucketing, a bucketed entry counting as the 1 it became):
+ *     s = 0.0f
+ *     for each kept entry p of the row, in order:   s = fl(s + fl(v[p] * v[p]))     two roundings, never an FMA
+ *     scale = (s > 0 and s finite) ? fl(1.0f / fl(sqrt(s))) : 1.0f                  IEEE sqrt and divide, denormals kept
+ *     for every entry p of the row (kept or not):   v'[p] = fl(v[p] * scale)
+ *   unscaled   a row whose s is zero, infinite or NaN passes through unchanged: an empty row, a row of zeros or of
+ *              erased entries only, an overflowing sum, a NaN value -- NaN rows behave as on an unflagged engine.
+ *   order      the sum is sequential on purpose (what a host loop gives); a tree order gives other bits.
+ *   val NULL   a block without values is normalised like the array of 1.0f it stands for.
+ *   where      every entry point that takes rows in HOST memory: ffm_engine_train_batch[_weighted],
+ *              ffm_engine_predict_batch, ffm_engine_predict_ablated, ffm_engine_stage_batch[_weighted],
+ *              ffm_engine_train_batch_async[_pinned|_weighted], ffm_engine_predict_batch_async[_scores] (zero_copy 0
+ *              and 1).  The caller's buffers are never written: with zero_copy the kernel works on the staging
+ *              slot's device copy.  LR, FM and FFM; training engines and both serving formats; sample weights,
+ *              FFM_FLAG_LEARN, FFM_FLAG_HASH_IDS with keep-map and buckets, field == NULL, the metrics channels and
+ *              keyed capture all combine.
+ *   contract   a flagged engine fed raw blocks gives, bit for bit, what an unflagged engine of the same
+ *              configuration gives when fed ffm_engine_normalize_rows_host of them.
+ *   ablation   ffm_engine_predict_ablated drops a field AFTER normalisation: variant v is predict_batch of the
+ *              normalised block without field v; the norm is not recomputed without the field.
+ *   refused    FFM_E_INVALID with a message that says so, before anything is queued: ffm_group_create with the
+ *              flag; ffm_engine_create with the flag and n_shards > 1 (a shard does not own whole rows);
+ *              ffm_engine_score_candidates[_device] on a flagged engine (the shared context terms would need a
+ *              scale per candidate).
+ *   _device    the entry points that take DEVICE rows take arrays as they are, flag or no flag.  For their callers:
+ * ffm_engine_normalize_rows_device: the definition applied to a block in device memory, asynchronous on the
+ *   engine's stream; val_out == val_in (in place) is allowed, val_in == NULL means ones, field is NULL for LR / FM.
+ *   Works on any engine, flagged or not (the engine gives n_feats, n_fields and the model type).
+ * ffm_engine_normalize_rows_host: the same in plain C++, no device needed; field == NULL on FFM: the id decides.
+ * ffm_engine_norm_stats: rows that went through the kernel since create or the last reset, and how many of them
+ *   were left unscaled (counted on the device, one atomic per wave); waits for the launches counted.
+ * The flag is not stored in weights, model files or serving deltas: whoever scores a model trained with it passes
+ * it again.  An unflagged engine launches exactly what it launched before; FFM_ENGINE_ABI_VERSION and
+ * ffm_engine_config are what they were. */
+int ffm_engine_normalize_rows_device(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr, const int32_t *field,
+                                     const int32_t *feat, const float *val_in, float *val_out);
+int ffm_engine_normalize_rows_host(int32_t model_type, int32_t n_feats, int32_t n_fields, int32_t n_rows, const int32_t *row_ptr,
+                                   const int32_t *field, const int32_t *feat, const float *val_in /* NULL: ones */, float *val_out);
+int ffm_engine_norm_stats(ffm_engine *e, int32_t reset, int64_t *rows, int64_t *unscaled);
 
 /* ---- Refresh: every stored weight from its accumulators -----------------------------------------
  * train() refreshes w = W(n, z) lazily, for what a row touches, BEFORE it updates (n, z), and leaves the
