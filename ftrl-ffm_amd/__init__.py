@@ -9,7 +9,9 @@ from .engine import (ABI, FFM, FM, LR, METRIC_BINS, METRIC_EVAL, METRIC_TRAIN, C
                      load_library, metrics_from_histogram, page_aligned, shard_plan, sketch_estimate, field_ranges, spell_out_candidates, drop_field,
                      IdCounter, RARE_ID, fold_rare, rare_slot,
                      ValueHistogram, BUCKET_BINS, BUCKET_MAX_EDGES, BUCKET_NAN_ID, value_bins, bucket_edges, bucket_ids,
-                     FLAG_NORM_ROWS, normalize_rows, normalize_rows_host)
+                     FLAG_NORM_ROWS, normalize_rows, normalize_rows_host,
+                     TextParser, TextBlock, parse_text_host, TEXT_MAX_LINE, TEXT_TILE_BYTES, TEXT_SCAN_BYTES, TEXT_LINE_TILE,
+                     TEXT_SCAN_CHUNK)
 
 
 def build(force=False, verbose=False):

@@ -90,6 +90,16 @@ class SyncStats(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class TextBlock(ctypes.Structure):
+    """struct ffm_text_block (include/ffm_engine.h "Text blocks")."""
+    _fields_ = ([(k, ctypes.c_int64) for k in ("n_lines", "n_rows", "nnz", "n_slow", "first_slow_byte")] +
+                [("overflow", ctypes.c_int32)] +
+                [(k, ctypes.c_void_p) for k in ("row_ptr", "field", "feat", "label", "val")])
+
+    def as_dict(self):
+        return {k: (getattr(self, k) if t is ctypes.c_void_p else int(getattr(self, k))) for k, t in self._fields_}
+
+
 RAW_DTYPES = {"f32": np.float32, "f16": np.uint16}  # a serving table's own elements, per format
 
 METRIC_EVAL, METRIC_TRAIN = 0, 1  # FFM_METRIC_*
@@ -265,10 +275,23 @@ ABI = [
     ("ffm_engine_normalize_rows_host", ctypes.c_int,
      [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, _f32p]),
     ("ffm_engine_norm_stats", ctypes.c_int, [_vp, ctypes.c_int32, _i64p, _i64p]),
+    # libffm / libsvm text parsed on the device (include/ffm_engine.h "Text blocks")
+    ("ffm_engine_textparse_create", ctypes.c_int,
+     [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
+    ("ffm_engine_textparse_parse", ctypes.c_int, [_vp, ctypes.c_int32, _vp, ctypes.c_int64, ctypes.c_int32]),
+    ("ffm_engine_textparse_wait", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(TextBlock)]),
+    ("ffm_engine_textparse_destroy", None, [_vp]),
+    ("ffm_engine_textparse_host", ctypes.c_int,
+     [ctypes.c_int32, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, _i32p,
+      ctypes.POINTER(TextBlock)]),
 ]
 SKETCH_REGS = 16384  # FFM_SKETCH_REGS
 RARE_ID = 2 ** 31 - 1  # FFM_RARE_ID
 BUCKET_BINS, BUCKET_MAX_EDGES, BUCKET_NAN_ID = 65536, 255, 65536  # FFM_BUCKET_*
+TEXT_MAX_LINE = 65536  # FFM_TEXT_MAX_LINE
+# the text kernels' own constants (csrc/kernels_text.h): bytes of a line one wave step reads, bytes per workgroup of
+# the newline count, lines per workgroup of the line passes, elements per step of the one-workgroup scans
+TEXT_TILE_BYTES, TEXT_SCAN_BYTES, TEXT_LINE_TILE, TEXT_SCAN_CHUNK = 1024, 4096, 64, 256
 
 _lib = None
 
@@ -1441,6 +1464,84 @@ class ValueHistogram:
     def close(self):
         if self.h:
             self.lib.ffm_engine_valhist_destroy(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _text_bytes(data):
+    """(address, n_bytes, keep-alive) of a text given as bytes / bytearray / memoryview / a uint8 or int8 array."""
+    if isinstance(data, np.ndarray):
+        if data.dtype.itemsize != 1 or not data.flags.c_contiguous or data.ndim != 1:
+            raise ValueError("text: a one-dimensional contiguous array of bytes")
+        return data.ctypes.data, data.size, data
+    a = np.frombuffer(bytes(data) if not isinstance(data, (bytes, bytearray)) else data, np.uint8)
+    return (a.ctypes.data if a.size else None), a.size, a
+
+
+def parse_text_host(data, has_field=True, max_rows=None, max_nnz=None):
+    """The text grammar on the host (ffm_engine_textparse_host, no device): dict(n_lines, n_rows, nnz, n_slow,
+    first_slow_byte, overflow, row_ptr, field, feat, val, label) with numpy arrays cut to the block's size -- valid
+    only when n_slow == 0 and overflow == 0 (else they come back empty).  Default capacities: what the bytes can hold."""
+    lib = load_library()
+    addr, n, keep = _text_bytes(data)
+    max_rows = n // 2 + 1 if max_rows is None else int(max_rows)
+    max_nnz = n // 4 + 1 if max_nnz is None else int(max_nnz)
+    row_ptr = np.zeros(max_rows + 1, np.int32)
+    label = np.zeros(max(max_rows, 1), np.int32)
+    field, feat = np.zeros(max(max_nnz, 1), np.int32), np.zeros(max(max_nnz, 1), np.int32)
+    val = np.zeros(max(max_nnz, 1), np.float32)
+    blk = TextBlock()
+    rc = lib.ffm_engine_textparse_host(int(bool(has_field)), addr, n, max_rows, max_nnz, _i(row_ptr), _i(field), _i(feat),
+                                       _f(val), _i(label), ctypes.byref(blk))
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
+    out = {k: int(getattr(blk, k)) for k in ("n_lines", "n_rows", "nnz", "n_slow", "first_slow_byte", "overflow")}
+    ok = out["n_slow"] == 0 and out["overflow"] == 0
+    r, e = (out["n_rows"], out["nnz"]) if ok else (0, 0)
+    out.update(row_ptr=row_ptr[:r + 1] if ok else row_ptr[:0], label=label[:r], field=field[:e], feat=feat[:e], val=val[:e])
+    return out
+
+
+class TextParser:
+    """libffm / libsvm text to a CSR block on the device (include/ffm_engine.h "Text blocks"): two slots, so that
+    one chunk is copied and parsed while the caller consumes the other.  Needs no engine."""
+
+    def __init__(self, has_field=True, max_bytes=1 << 20, max_rows=1 << 16, max_nnz=1 << 20, device=0):
+        self.lib = load_library()
+        self.h = _vp()
+        self.max_bytes, self.max_rows, self.max_nnz = int(max_bytes), int(max_rows), int(max_nnz)
+        self._keep = [None, None]
+        self._check(self.lib.ffm_engine_textparse_create(int(bool(has_field)), self.max_bytes, self.max_rows, self.max_nnz,
+                                                         int(device), ctypes.byref(self.h)))
+
+    def _check(self, rc):
+        if rc != 0:
+            raise EngineError(rc, self.lib.ffm_engine_last_error().decode())
+
+    def parse(self, data, slot=0, zero_copy=False):
+        """Starts the parse of `data` (bytes, or an array of bytes) into `slot`; asynchronous.  zero_copy: `data` is a
+        page-locked array (ffm_engine_pin_host) that stays untouched until wait(slot) returns."""
+        addr, n, keep = _text_bytes(data)
+        self._check(self.lib.ffm_engine_textparse_parse(self.h, int(slot), addr, n, int(bool(zero_copy))))
+        self._keep[int(slot)] = keep
+
+    def wait(self, slot=0):
+        """The block parsed into `slot`: dict(n_lines, n_rows, nnz, n_slow, first_slow_byte, overflow, row_ptr, field,
+        feat, val, label) -- the arrays as device addresses, valid until the slot's next parse, and only when
+        n_slow == 0 and overflow == 0."""
+        blk = TextBlock()
+        self._check(self.lib.ffm_engine_textparse_wait(self.h, int(slot), ctypes.byref(blk)))
+        self._keep[int(slot)] = None
+        return blk.as_dict()
+
+    def close(self):
+        if self.h:
+            self.lib.ffm_engine_textparse_destroy(self.h)
             self.h = _vp()
 
     def __del__(self):

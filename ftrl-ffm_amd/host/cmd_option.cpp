@@ -164,7 +164,16 @@ const std::string_view cmd_help =
     "              --field_importance alike (which drops a field after normalising).  Prints `normalized rows: R scaled, U\n"
     "              left as they came (zero or non-finite norm)`.  The checkpoint records the setting and --resume_from\n"
     "              refuses the other one; model files and serving deltas do not: a run that scores or serves such a model\n"
-    "              passes the flag again, as it passes --field_ranges @FILE.  One GPU\tdefault:false\n";
+    "              passes the flag again, as it passes --field_ranges @FILE.  One GPU\tdefault:false\n"
+    "--device_parse <bool>: the counting passes over --train_data (--bucket_fields, --min_count, --field_ranges counted)\n"
+    "              read the file as raw bytes and the device parses them: plain ids of at most 9 digits and plain decimals\n"
+    "              of at most 7 significant and 10 fraction digits, exactly as the host parser reads them.  A chunk with\n"
+    "              any other line (an exponent, nan, a tab, a malformed token ..) is parsed by the host, whole, so no\n"
+    "              result changes and a malformed line ends the run as it does without the flag.  Prints per pass\n"
+    "              `device parse: C chunks, B bytes, H parsed by the host (first at byte N)`.  Training, evaluation and\n"
+    "              --predict_data still read through the host parser.  Needs one of the three passes; not with --cmd\n"
+    "              true.  (Environment FFM_TEXT_SLOT_BYTES sets the chunk size: a test hook, results do not depend on\n"
+    "              it)\tdefault:false\n";
 
 static bool assign_bool(std::string arg) {
   std::transform(arg.begin(), arg.end(), arg.begin(), [](unsigned char c) { return std::tolower(c); });
@@ -239,6 +248,7 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--refresh_weights") refresh_weights = assign_bool(v);
     else if (k == "--hash_feats") hash_feats = assign_bool(v);
     else if (k == "--normalize_rows") normalize_rows = assign_bool(v);
+    else if (k == "--device_parse") device_parse = assign_bool(v);
     else if (k == "--compact_rows") compact_rows = assign_bool(v);
     else if (k == "--field_importance") field_importance = assign_bool(v);
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
@@ -385,6 +395,13 @@ void config_options::parse_option(int argc, char *argv[]) {
     const bool ranged = field_ranges == "uniform" || field_ranges == "counted" || field_ranges[0] == '@';
     if (!ranged || model_type != "FFM")
       throw std::invalid_argument("--field_ranges_out writes the fields' id ranges: it needs an FFM model and --field_ranges uniform, counted or @FILE");
+  }
+  if (device_parse) {
+    // only the counting pre-passes read text through the device parser (refused here, before a device is opened)
+    if (min_count <= 1 && bucket_fields.empty() && field_ranges != "counted")
+      throw std::invalid_argument("--device_parse true parses the text of the counting passes on the device: it needs --min_count > 1, "
+                                  "--bucket_fields or --field_ranges counted (training and evaluation do not read through it yet)");
+    if (cmd) throw std::invalid_argument("--device_parse true is not allowed with --cmd true");
   }
   // a row's length is a sum over all of its entries (refused here, before a device is opened)
   if (normalize_rows && n_gpus > 1)

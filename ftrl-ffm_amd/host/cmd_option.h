@@ -48,6 +48,9 @@ struct config_options {
   // --normalize_rows: FFM_FLAG_NORM_ROWS, every row scaled to unit Euclidean length on the device (include/ffm_engine.h
   // "Normalised rows"); every engine of the run that takes rows, one GPU
   bool normalize_rows = false;
+  // --device_parse: the counting pre-passes (--bucket_fields, --min_count, --field_ranges counted) read --train_data
+  // as raw bytes and parse them on the device (include/ffm_engine.h "Text blocks", text_stream.h); no result changes
+  bool device_parse = false;
   // --serve_weights none | f32 | f16: score a saved model from a serving engine (FFM_FLAG_SERVE_F32 / _F16: the
   // weights alone, in fp32 bits or IEEE binary16); only with --resume_from ck --n_epochs 0
   std::string serve_weights = "none";

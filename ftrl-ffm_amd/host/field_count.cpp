@@ -9,6 +9,7 @@
 
 #include "count_block.h"
 #include "field_ranges.h"
+#include "text_stream.h"
 
 namespace ftrl {
 
@@ -38,7 +39,18 @@ std::vector<int32_t> count_field_ranges(const config_options &opt) {
   if (!opt.rare_words.empty())
     check_rc(ffm_engine_sketch_set_filter(sk.s, opt.rare_map_bits, opt.rare_words.data()), "ffm_engine_sketch_set_filter");
   unsigned long long rows = 0;
-  {
+  if (opt.device_parse) {
+    // --device_parse true: the file as raw bytes, parsed on the device into the arrays the sketch reads in HBM
+    DeviceParseHooks hooks;
+    hooks.device = [&](const ffm_text_block &b) {
+      check_rc(ffm_engine_sketch_add_device(sk.s, static_cast<int32_t>(b.nnz), b.field, b.feat), "ffm_engine_sketch_add_device");
+    };
+    hooks.host = [&](const CsrPart &p) {
+      check_rc(ffm_engine_sketch_add(sk.s, static_cast<int32_t>(p.feat.size()), p.field.data(), p.feat.data(), 0), "ffm_engine_sketch_add");
+    };
+    hooks.sync = [&] { check_rc(ffm_engine_sketch_read(sk.s, nullptr, nullptr, nullptr), "ffm_engine_sketch_read"); };
+    rows = device_parse_pass(opt, hooks);
+  } else {
     CountBlock cb;  // (no page-locked memory to be had: the sketch copies each block into its own)
     CsrStream stream(opt.train_path, opt.file_type, opt.thread_num);
     for (;;) {

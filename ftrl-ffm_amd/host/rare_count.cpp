@@ -9,6 +9,7 @@
 
 #include "count_block.h"
 #include "rare_ids.h"
+#include "text_stream.h"
 
 namespace ftrl {
 
@@ -39,7 +40,20 @@ RareIds count_rare_ids(const config_options &opt) {
     if (rc == FFM_E_INVALID) throw std::invalid_argument(std::string("--min_count: ") + ffm_engine_last_error());
     check_rc(rc, "ffm_engine_idcount_create");
   }
-  {
+  if (opt.device_parse) {
+    // --device_parse true: the file as raw bytes, parsed on the device into the arrays the counter reads in HBM
+    DeviceParseHooks hooks;
+    hooks.device = [&](const ffm_text_block &b) {
+      check_rc(ffm_engine_idcount_add_device(ct.s, static_cast<int32_t>(b.nnz), map.n_fields ? b.field : nullptr, b.feat),
+               "ffm_engine_idcount_add_device");
+    };
+    hooks.host = [&](const CsrPart &p) {
+      check_rc(ffm_engine_idcount_add(ct.s, static_cast<int32_t>(p.feat.size()), map.n_fields ? p.field.data() : nullptr, p.feat.data(), 0),
+               "ffm_engine_idcount_add");
+    };
+    hooks.sync = [&] { check_rc(ffm_engine_idcount_read(ct.s, nullptr, nullptr, nullptr), "ffm_engine_idcount_read"); };
+    map.rows = device_parse_pass(opt, hooks);
+  } else {
     CountBlock cb;  // (no page-locked memory to be had: the counter copies each block into its own)
     CsrStream stream(opt.train_path, opt.file_type, opt.thread_num);
     for (;;) {

@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "count_block.h"
+#include "text_stream.h"
 #include "value_buckets.h"
 
 namespace ftrl {
@@ -34,7 +35,18 @@ ValueBuckets count_value_buckets(const config_options &opt) {
     check_rc(rc, "ffm_engine_valhist_create");
   }
   unsigned long long rows = 0;
-  {
+  if (opt.device_parse) {
+    // --device_parse true: the file as raw bytes, parsed on the device into the arrays the histogram reads in HBM
+    DeviceParseHooks hooks;
+    hooks.device = [&](const ffm_text_block &b) {
+      check_rc(ffm_engine_valhist_add_device(vh.s, static_cast<int32_t>(b.nnz), b.field, b.val), "ffm_engine_valhist_add_device");
+    };
+    hooks.host = [&](const CsrPart &p) {
+      check_rc(ffm_engine_valhist_add(vh.s, static_cast<int32_t>(p.val.size()), p.field.data(), p.val.data(), 0), "ffm_engine_valhist_add");
+    };
+    hooks.sync = [&] { check_rc(ffm_engine_valhist_read(vh.s, nullptr, nullptr, nullptr, nullptr), "ffm_engine_valhist_read"); };
+    rows = device_parse_pass(opt, hooks);
+  } else {
     CountBlock cb(true);  // (no page-locked memory to be had: the histogram copies each block into its own)
     CsrStream stream(opt.train_path, opt.file_type, opt.thread_num);
     for (;;) {

@@ -1141,6 +1141,58 @@ int ffm_engine_get_rows_raw(ffm_engine *e, int32_t n, const int32_t *ids, float 
                             void *lat /* [n][row_len] of 2 or 4 bytes */);
 int ffm_engine_set_rows_raw(ffm_engine *e, int32_t n, const int32_t *ids, const float *lin_w, const void *lat);
 
+/* ---- Text blocks: libffm / libsvm text parsed on the device ------------------------------------------------
+ * Every row enters as text, and a libffm row of 39 entries is about as many bytes of text as of field / feat / val.
+ * A text parser takes the BYTES of whole lines and leaves, in HBM, the CSR block the host parser (parse_csr_range,
+ * host/csr_reader.cpp) would have produced for them: row_ptr [n_rows + 1], label [n_rows], field / feat / val [nnz],
+ * as every _device entry point and every *_add_device takes them.  It needs no engine.
+ *   grammar    the host parser's fast path and nothing else, stated rule by rule in csrc/text_parse.h ("Text
+ *              blocks"), which host and device share bit for bit: lines end at '\n' or the text's end, one trailing
+ *              '\r' is stripped, the only blank is ' ', a line of blanks is no row; the label is [+-] and 1 to 9
+ *              digits (1 if > 0, else 0); an entry is field:feat:value (has_field) or feat:value (field = 0) with ids
+ *              of 1 to 9 digits and a value [-]digits[.digits] of at most 7 significant and 10 fraction digits,
+ *              float(digits) / 10^n_frac in one correctly rounded division; an entry that compares equal to 0.0f is
+ *              dropped.
+ *   slow       every other line -- an exponent, nan, inf, a tab, a '+' on a value, a missing part, a 10-digit id, a
+ *              label such as 1.0, more than FFM_TEXT_MAX_LINE bytes before the '\n'.  A slow line is not parsed and
+ *              nothing is guessed: it counts in n_slow, gives no row and no entry, and the caller hands the text to
+ *              the host parser.
+ *   block      n_lines (lines of the text, an unterminated last one included), n_rows and nnz (of the lines that
+ *              are not slow: TRUE totals, also when they exceed the capacities), n_slow, first_slow_byte (offset of
+ *              the first slow line's first byte, -1 without one) and overflow (n_rows > max_rows or nnz > max_nnz)
+ *              are always valid; the arrays only when n_slow == 0 and overflow == 0.  The pointers are DEVICE
+ *              pointers into the slot, valid until the slot's next parse.
+ *   slots      two: _parse (asynchronous, on the parser's own stream) copies and parses chunk t + 1 while the
+ *              caller consumes chunk t; _wait is the one host wait per chunk (the consumers take nnz from the host).
+ *              zero_copy != 0: text is page-locked (ffm_engine_pin_host) and stays untouched until _wait on that
+ *              slot returns; otherwise the parser copies it into a page-locked image of its own first, and text is
+ *              free when _parse returns.  Whoever reads a slot's arrays on another stream has them read before the
+ *              slot is parsed into again.
+ *   refused    FFM_E_INVALID: n_bytes > max_bytes or negative, a slot outside {0, 1}, _parse on a slot whose last
+ *              parse was not waited for, _wait on a slot nothing was parsed into, max_bytes outside [1, 2^31 - 4096],
+ *              a capacity below 1; FFM_E_DEVICE without a device.
+ *   host       ffm_engine_textparse_host is the same grammar on the host, bit for bit, and needs no device: it
+ *              fills the caller's arrays (row_ptr [max_rows + 1], label [max_rows], field / feat / val [max_nnz])
+ *              under the same rule and stores nothing past them; the block's pointers come back NULL.
+ * OUT OF SCOPE  parsing the slow grammar on the device; a fallback per line (a block falls back whole). */
+typedef struct ffm_textparse ffm_textparse;
+#define FFM_TEXT_MAX_LINE 65536
+typedef struct {
+  int64_t n_lines, n_rows, nnz;       /* true totals, also on overflow                  */
+  int64_t n_slow, first_slow_byte;    /* slow lines; offset of the first one's first byte */
+  int32_t overflow;                   /* n_rows > max_rows or nnz > max_nnz: arrays not valid */
+  const int32_t *row_ptr, *field, *feat, *label;  /* DEVICE pointers, valid until the slot's next parse */
+  const float *val;
+} ffm_text_block;
+int ffm_engine_textparse_create(int32_t has_field, int64_t max_bytes, int32_t max_rows, int32_t max_nnz, int32_t device_id,
+                                ffm_textparse **out);
+int ffm_engine_textparse_parse(ffm_textparse *p, int32_t slot /* 0 or 1 */, const char *text, int64_t n_bytes,
+                               int32_t zero_copy); /* asynchronous */
+int ffm_engine_textparse_wait(ffm_textparse *p, int32_t slot, ffm_text_block *out);
+void ffm_engine_textparse_destroy(ffm_textparse *p);
+int ffm_engine_textparse_host(int32_t has_field, const char *text, int64_t n_bytes, int32_t max_rows, int32_t max_nnz,
+                              int32_t *row_ptr, int32_t *field, int32_t *feat, float *val, int32_t *label, ffm_text_block *out);
+
 #ifdef __cplusplus
 }
 #endif
