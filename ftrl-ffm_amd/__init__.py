@@ -11,7 +11,7 @@ from .engine import (ABI, FFM, FM, LR, METRIC_BINS, METRIC_EVAL, METRIC_TRAIN, C
                      ValueHistogram, BUCKET_BINS, BUCKET_MAX_EDGES, BUCKET_NAN_ID, value_bins, bucket_edges, bucket_ids,
                      FLAG_NORM_ROWS, normalize_rows, normalize_rows_host,
                      TextParser, TextBlock, parse_text_host, TEXT_MAX_LINE, TEXT_TILE_BYTES, TEXT_SCAN_BYTES, TEXT_LINE_TILE,
-                     TEXT_SCAN_CHUNK)
+                     TEXT_SCAN_CHUNK, RowCutter, RowsBlock)
 
 
 def build(force=False, verbose=False):

@@ -58,6 +58,7 @@
 #include "kernels_valhist.h"
 #include "kernels_norm.h"
 #include "kernels_text.h"
+#include "kernels_rows.h"
 #include "metrics_host.h"
 
 using namespace ftrl_dev;
@@ -859,6 +860,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_idcount.h"
 #include "engine_valhist.h"
 #include "engine_text.h"
+#include "engine_rows.h"
 #include "engine_ablate.h"
 }  // extern "C"
 

@@ -105,7 +105,9 @@ struct SlotClaim {
 // until the slot's own pinned image is free, copies the caller's arrays into it (unless zero_copy) and
 // describes the upload (the block's ordinal is n_staged_total + 1).  Bookkeeping of the slot is the
 // caller's: slot_commit.
-static int claim_slot(ffm_engine *e, const Rows &host, const float *weight, int32_t zero_copy, SlotClaim *claim) {
+// resident (with zero_copy): the arrays of `host` are DEVICE addresses, 16-byte aligned (a closed block of a row cutter,
+// engine_rows.h) -- the upload then reads HBM, and nothing is asked about host memory.
+static int claim_slot(ffm_engine *e, const Rows &host, const float *weight, int32_t zero_copy, SlotClaim *claim, bool resident = false) {
   const auto [n_rows, nnz, row_ptr, field, feat, val, label] = host;
   int rc;
   if ((rc = slots_init(e))) return rc;
@@ -141,8 +143,8 @@ static int claim_slot(ffm_engine *e, const Rows &host, const float *weight, int3
       host_src = at;
       at += (bytes + 15) & ~static_cast<size_t>(15);
     }
-    hipError_t why;
-    void *mapped = mapped16(host_src, &why);
+    hipError_t why = hipSuccess;
+    void *mapped = resident ? const_cast<void *>(host_src) : mapped16(host_src, &why);
     if (!mapped) return why != hipSuccess ? why : hipErrorInvalidValue;  // 16-byte aligned arrays only
     const Part next{&job.src[n_job], &job.dst[n_job], &job.bytes[n_job]};
     const Part &to = own ? *own : next;
@@ -239,20 +241,12 @@ static Rows slot_rows(const ffm_engine::Slot &sl, const int *label) {
 }
 
 // Stage one block of host rows: (pinned image ->) HBM -> grouping, all on the prep stream.
-int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
-                                    const int32_t *field, const int32_t *feat, const float *val,
-                                    const int32_t *label, const float *weight, int32_t zero_copy) {
-  SERVE_REFUSE(e, "training");  // (staging is training's: prediction stages through predict_batch_async)
-  int32_t nnz = 0;
-  int longest = 1;
-  int rc = validate_host_block(e, n_rows, row_ptr, &field, feat, val, &nnz, &longest, true);
-  if (rc) return rc;
-  if (n_rows > 0 && !label) return fail(FFM_E_INVALID, "training needs labels");
-  if (n_rows == 0) weight = nullptr;
-  if (weight) {  // refused here, on the caller's thread, before anything of the block is queued
-    if ((rc = validate_host_weights(n_rows, weight))) return rc;
-    if (zero_copy && !mapped16_or_refuse(weight, "a zero_copy weight array")) return FFM_E_INVALID;
-  }
+// ... of a validated block `host` (its longest row: `longest`), from eval_launch_pending on.  resident: `host` lies
+// in HBM (claim_slot) and is whole once `ready` (may be null) has happened: the upload waits for it on the prep stream.
+static int stage_block_from(ffm_engine *e, const Rows &host, int longest, const float *weight, int32_t zero_copy, bool resident = false,
+                            hipEvent_t ready = nullptr) {
+  const auto [n_rows, nnz, row_ptr, field, feat, val, label] = host;
+  int rc;
   if ((rc = eval_launch_pending(e))) return rc;
   if (e->n_staged >= ffm_engine::kSlots - 1) return fail(FFM_E_CAPACITY, "three staged blocks are already waiting");
   if (e->has_pending) return fail(FFM_E_INVALID, "stage between train_forward and train_update");
@@ -261,9 +255,8 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
   // that then failed to stage would leave the count one ahead for good
   if (e->n_prepared >= ffm_engine::kSets - 1) return fail(FFM_E_CAPACITY, "three prepared blocks are already waiting");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
-  const Rows host{n_rows, nnz, row_ptr, field, feat, val, label};
   SlotClaim claim;
-  if ((rc = claim_slot(e, host, weight, zero_copy, &claim))) return rc;
+  if ((rc = claim_slot(e, host, weight, zero_copy, &claim, resident))) return rc;
   const int this_slot = claim.slot;
   ffm_engine::Slot &sl = e->slots[this_slot];
   // its grouping, behind its own upload on the prep stream: planned here, submitted with the upload
@@ -280,13 +273,14 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
   // FFM_FLAG_NORM_ROWS: the slot's values in place, right behind the upload that writes them and the ids
   const NormJob norm = e->norm_rows_on ? norm_job(e, Rows{n_rows, nnz, sl.row_ptr, claim.has_field ? sl.field : nullptr, sl.feat, sl.val, nullptr}, sl.val)
                                        : NormJob{};
-  rc = e->submit([e, this_slot, free_ev, hjob = claim.job, rare = claim.rare, bucket = claim.bucket, plan, seq, grid_pull, timed, ones, n_ones, norm]() -> int {
+  rc = e->submit([e, this_slot, free_ev, hjob = claim.job, rare = claim.rare, bucket = claim.bucket, plan, seq, grid_pull, timed, ones, n_ones, norm, ready]() -> int {
     ScopedTimer tm("stage:submit");
     ffm_engine::Slot &s2 = e->slots[this_slot];
     int rc2 = FFM_OK;
     auto body = [&]() -> int {
       HIP_TRY(hipSetDevice(e->cfg.device_id));
       if (free_ev) HIP_TRY(hipStreamWaitEvent(e->prep, free_ev, 0));  // nothing reads its device arrays
+      if (ready) HIP_TRY(hipStreamWaitEvent(e->prep, ready, 0));  // (a resident block: its last take has run)
       // (long steps: the upload too waits for the running block's row kernel to end -- beside the update
       // launches it costs nothing, beside the row kernel, which is bound by the bytes it moves, it does)
       if (e->pull_after_row && plan.ws >= 0) HIP_TRY(hipStreamWaitEvent(e->prep, e->prep_after_row ? e->ev_row_done[plan.ws] : e->ev_set_free[plan.ws], 0));
@@ -306,6 +300,22 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
   slot_commit(e, claim, host, longest, weight != nullptr, zero_copy);
   e->staged[e->n_staged++] = this_slot;
   return FFM_OK;
+}
+int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                                    const int32_t *field, const int32_t *feat, const float *val,
+                                    const int32_t *label, const float *weight, int32_t zero_copy) {
+  SERVE_REFUSE(e, "training");  // (staging is training's: prediction stages through predict_batch_async)
+  int32_t nnz = 0;
+  int longest = 1;
+  int rc = validate_host_block(e, n_rows, row_ptr, &field, feat, val, &nnz, &longest, true);
+  if (rc) return rc;
+  if (n_rows > 0 && !label) return fail(FFM_E_INVALID, "training needs labels");
+  if (n_rows == 0) weight = nullptr;
+  if (weight) {  // refused here, on the caller's thread, before anything of the block is queued
+    if ((rc = validate_host_weights(n_rows, weight))) return rc;
+    if (zero_copy && !mapped16_or_refuse(weight, "a zero_copy weight array")) return FFM_E_INVALID;
+  }
+  return stage_block_from(e, Rows{n_rows, nnz, row_ptr, field, feat, val, label}, longest, weight, zero_copy);
 }
 int ffm_engine_stage_batch(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
                            const int32_t *field, const int32_t *feat, const float *val,
@@ -448,15 +458,11 @@ static int eval_launch_pending(ffm_engine *e) {
 // puts work on the main stream (check_block), by ffm_engine_sync / check_errors and by the flush.
 // scores_host (may be NULL): the block's predictions also go to the caller's page-locked buffer
 // (push_scores_kernel, behind the deferred predict launch).
-int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
-                                          const int32_t *field, const int32_t *feat, const float *val,
-                                          const int32_t *label, int32_t zero_copy, int32_t output_prob,
-                                          float *scores_host) {
-  int32_t nnz = 0;
-  int longest = 1;
-  // (hold_eval: the deferred block waits until this one's upload is submitted)
-  int rc = validate_host_block(e, n_rows, row_ptr, &field, feat, val, &nnz, &longest, true, true);
-  if (rc) return rc;
+// (the entry point's steps behind the validation of `host`; resident / ready: as stage_block_from takes them)
+static int predict_block_from(ffm_engine *e, const Rows &host, int longest, int32_t zero_copy, bool resident, hipEvent_t ready,
+                              int32_t output_prob, float *scores_host) {
+  const auto [n_rows, nnz, row_ptr, field, feat, val, label] = host;
+  int rc;
   if (e->m.n_shards > 1) return fail(FFM_E_INVALID, "a sharded engine predicts through predict_batch_device + predict_finish_device");
   if (e->n_staged > 0 || e->has_pending) return fail(FFM_E_INVALID, "staged training blocks are still waiting");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
@@ -464,12 +470,12 @@ int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const i
   float *scores_dev = nullptr;
   if (scores_host && !(scores_dev = static_cast<float *>(mapped16_or_refuse(scores_host, "scores_host")))) return FFM_E_INVALID;
   if ((rc = e->drain())) return rc;
-  const Rows host{n_rows, nnz, row_ptr, field, feat, val, label};
   SlotClaim claim;
-  if ((rc = claim_slot(e, host, nullptr, zero_copy, &claim))) return rc;
+  if ((rc = claim_slot(e, host, nullptr, zero_copy, &claim, resident))) return rc;
   const int this_slot = claim.slot;
   ffm_engine::Slot &sl = e->slots[this_slot];
   if (claim.was_used && sl.free_ev) HIP_TRY(hipStreamWaitEvent(e->prep, sl.free_ev, 0));  // nothing reads its device arrays
+  if (ready) HIP_TRY(hipStreamWaitEvent(e->prep, ready, 0));  // (a resident block: its last take has run)
   // (no values came: the upload writes the slot's)
   launch_upload(e, e->prep, e->grid_pull, claim.job, claim.rare, claim.bucket, sl.val, val ? 0u : static_cast<unsigned>(nnz));
   if (e->norm_rows_on)  // (FFM_FLAG_NORM_ROWS: the slot's values in place, behind the upload)
@@ -490,6 +496,17 @@ int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const i
   e->eval_pending.seq = sl.seq;
   if (e->eval_defer_off) return eval_launch_pending(e);  // (FFM_EVAL_DEFER=0: as rounds 3-5)
   return FFM_OK;
+}
+int ffm_engine_predict_batch_async_scores(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,
+                                          const int32_t *field, const int32_t *feat, const float *val,
+                                          const int32_t *label, int32_t zero_copy, int32_t output_prob,
+                                          float *scores_host) {
+  int32_t nnz = 0;
+  int longest = 1;
+  // (hold_eval: the deferred block waits until this one's upload is submitted)
+  int rc = validate_host_block(e, n_rows, row_ptr, &field, feat, val, &nnz, &longest, true, true);
+  if (rc) return rc;
+  return predict_block_from(e, Rows{n_rows, nnz, row_ptr, field, feat, val, label}, longest, zero_copy, false, nullptr, output_prob, scores_host);
 }
 
 int ffm_engine_predict_batch_async(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr,

@@ -19,7 +19,13 @@ struct ffm_textparse {
     long long *h_counters = nullptr;  // page-locked [TC_COUNT]
     hipEvent_t ev_done = nullptr;
     bool in_flight = false;
+    // the page-locked mirror of row_ptr (ffm_engine_textparse_wait_rows; made by the first such wait): whether this
+    // slot's last parse copied into it, and how many rows of it a waited block vouches for (-1: none)
+    int32_t *h_row_ptr = nullptr, *d_row_ptr_mirror = nullptr;  // (the second: the device's address of the first)
+    bool mirror_copied = false;
+    int64_t mirror_rows = -1;
   } slot[2];
+  bool mirror_on = false;  // every parse copies its slot's row_ptr to the mirror, ahead of the slot's event
   int32_t cap_lines = 0, cap_btiles = 0, cap_ltiles = 0;
 };
 
@@ -34,6 +40,7 @@ void ffm_engine_textparse_destroy(ffm_textparse *p) {
       if (d) (void)hipFree(d);
     if (s.pinned) (void)hipHostFree(s.pinned);
     if (s.h_counters) (void)hipHostFree(s.h_counters);
+    if (s.h_row_ptr) (void)hipHostFree(s.h_row_ptr);
     if (s.ev_done) (void)hipEventDestroy(s.ev_done);
   }
   if (p->stream) (void)hipStreamDestroy(p->stream);
@@ -99,6 +106,14 @@ int ffm_engine_textparse_create(int32_t has_field, int64_t max_bytes, int32_t ma
   return FFM_OK;
 }
 
+// The slot's row_ptr [n_rows + 1] to its page-locked mirror, behind the parse on the parser's stream (rows_mirror_kernel,
+// kernels_rows.h; the grid by the rows n_bytes of text can hold at two bytes a row, a real row being hundreds).
+static void textparse_mirror(ffm_textparse *p, ffm_textparse::Slot &s, int64_t n_bytes) {
+  const int grid = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(64, n_bytes / (64 * 256))));
+  hipLaunchKernelGGL(rows_mirror_kernel, dim3(grid), dim3(256), 0, p->stream, s.d_row_ptr, s.d_counters, s.d_row_ptr_mirror,
+                     static_cast<unsigned>(p->max_rows));
+}
+
 int ffm_engine_textparse_parse(ffm_textparse *p, int32_t slot, const char *text, int64_t n_bytes, int32_t zero_copy) {
   if (!p) return fail(FFM_E_INVALID, "null text parser");
   if (slot != 0 && slot != 1) return fail(FFM_E_INVALID, "slot must be 0 or 1");
@@ -156,6 +171,13 @@ int ffm_engine_textparse_parse(ffm_textparse *p, int32_t slot, const char *text,
   hipLaunchKernelGGL((text_lines_kernel<true>), dim3(grid_l), dim3(kTextThreads), 0, p->stream, a);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(s.h_counters, s.d_counters, sizeof(long long) * TC_COUNT, hipMemcpyDeviceToHost, p->stream));
+  s.mirror_copied = false;
+  s.mirror_rows = -1;
+  if (p->mirror_on) {
+    textparse_mirror(p, s, n_bytes);
+    HIP_TRY(hipGetLastError());
+    s.mirror_copied = true;
+  }
   HIP_TRY(hipEventRecord(s.ev_done, p->stream));
   s.in_flight = true;
   return FFM_OK;
@@ -182,6 +204,35 @@ int ffm_engine_textparse_wait(ffm_textparse *p, int32_t slot, ffm_text_block *ou
   out->feat = s.d_feat;
   out->label = s.d_label;
   out->val = s.d_val;
+  return FFM_OK;
+}
+
+// _wait, and the page-locked host mirror of the slot's row_ptr [n_rows + 1] (include/ffm_engine.h "Resident rows"):
+// what the host needs of a chunk to cut blocks out of it.  The first such wait makes the mirrors and copies its own
+// slot's behind the parse; from then on every parse copies its slot's on the parser's stream, ahead of the slot's event.
+int ffm_engine_textparse_wait_rows(ffm_textparse *p, int32_t slot, ffm_text_block *out, const int32_t **row_ptr_host) {
+  if (!row_ptr_host) return fail(FFM_E_INVALID, "null output");
+  *row_ptr_host = nullptr;
+  if (int rc = ffm_engine_textparse_wait(p, slot, out)) return rc;
+  ffm_textparse::Slot &s = p->slot[slot];
+  if (out->n_slow != 0 || out->overflow != 0) return FFM_OK;  // (the arrays are not valid: nothing to mirror)
+  if (!p->mirror_on) {
+    for (auto &t : p->slot)
+      if (!t.h_row_ptr) {
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_row_ptr), sizeof(int32_t) * (static_cast<size_t>(p->max_rows) + 1),
+                              hipHostMallocPortable | hipHostMallocMapped));
+        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&t.d_row_ptr_mirror), t.h_row_ptr, 0));
+      }
+    p->mirror_on = true;
+  }
+  if (!s.mirror_copied) {
+    textparse_mirror(p, s, static_cast<int64_t>(out->n_rows) * 2);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    s.mirror_copied = true;
+  }
+  s.mirror_rows = out->n_rows;
+  *row_ptr_host = s.h_row_ptr;
   return FFM_OK;
 }
 

@@ -100,6 +100,12 @@ class TextBlock(ctypes.Structure):
         return {k: (getattr(self, k) if t is ctypes.c_void_p else int(getattr(self, k))) for k, t in self._fields_}
 
 
+class RowsBlock(ctypes.Structure):
+    """struct ffm_rows_block (include/ffm_engine.h "Resident rows"): a block of rows in HBM."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ("n_rows", "nnz", "longest_row", "index")] + [("seq", ctypes.c_int64)] +
+                [(k, ctypes.c_void_p) for k in ("row_ptr", "field", "feat", "label", "val", "ready")])
+
+
 RAW_DTYPES = {"f32": np.float32, "f16": np.uint16}  # a serving table's own elements, per format
 
 METRIC_EVAL, METRIC_TRAIN = 0, 1  # FFM_METRIC_*
@@ -284,6 +290,17 @@ ABI = [
     ("ffm_engine_textparse_host", ctypes.c_int,
      [ctypes.c_int32, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, _i32p,
       ctypes.POINTER(TextBlock)]),
+    # blocks cut out of parsed text in HBM and staged from there (include/ffm_engine.h "Resident rows")
+    ("ffm_engine_textparse_wait_rows", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(TextBlock), ctypes.POINTER(_vp)]),
+    ("ffm_engine_rowcut_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
+    ("ffm_engine_rowcut_take", ctypes.c_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    ("ffm_engine_rowcut_take_host", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR),
+    ("ffm_engine_rowcut_close", ctypes.c_int, [_vp, ctypes.POINTER(RowsBlock)]),
+    ("ffm_engine_rowcut_release", ctypes.c_int, [_vp, ctypes.c_int32]),
+    ("ffm_engine_rowcut_destroy", None, [_vp]),
+    ("ffm_engine_stage_batch_resident", ctypes.c_int, [_vp, ctypes.POINTER(RowsBlock)]),
+    ("ffm_engine_train_batch_async_resident", ctypes.c_int, [_vp, ctypes.POINTER(RowsBlock)]),
+    ("ffm_engine_predict_batch_async_resident", ctypes.c_int, [_vp, ctypes.POINTER(RowsBlock), ctypes.c_int32, _vp]),
 ]
 SKETCH_REGS = 16384  # FFM_SKETCH_REGS
 RARE_ID = 2 ** 31 - 1  # FFM_RARE_ID
@@ -1088,6 +1105,24 @@ class Engine:
         self._check(self.lib.ffm_engine_predict_batch_async_scores(
             self.h, *self._csr(c), int(zero_copy), int(bool(output_prob)), scores.ctypes.data))
 
+    # ---- blocks of rows that already lie in HBM (include/ffm_engine.h "Resident rows") ----
+    def stage_resident(self, block):
+        """stage_batch(zero_copy=True) for a RowsBlock in HBM (RowCutter.close); block.seq is its staging number."""
+        self._check(self.lib.ffm_engine_stage_batch_resident(self.h, ctypes.byref(block)))
+
+    def train_async_resident(self, block):
+        """train_batch_async_pinned for a RowsBlock in HBM: three blocks in flight; the block's buffer is free
+        (RowCutter.release) once blocks_pulled() has reached block.seq."""
+        self._check(self.lib.ffm_engine_train_batch_async_resident(self.h, ctypes.byref(block)))
+
+    def predict_async_resident(self, block, scores=None, output_prob=False):
+        """predict_batch_async(zero_copy=True, scores=...) for a RowsBlock in HBM."""
+        if scores is not None and (scores.dtype != np.float32 or scores.ndim != 1 or scores.size < block.n_rows
+                                   or not scores.flags.c_contiguous):
+            raise ValueError("scores: a contiguous float32 array of at least n_rows elements")
+        self._check(self.lib.ffm_engine_predict_batch_async_resident(
+            self.h, ctypes.byref(block), int(bool(output_prob)), None if scores is None else scores.ctypes.data))
+
     def blocks_scored(self):
         """Staging number of the last block whose scores are whole in its buffer (non-blocking)."""
         return int(self.lib.ffm_engine_blocks_scored(self.h))
@@ -1530,14 +1565,26 @@ class TextParser:
         self._check(self.lib.ffm_engine_textparse_parse(self.h, int(slot), addr, n, int(bool(zero_copy))))
         self._keep[int(slot)] = keep
 
-    def wait(self, slot=0):
+    def wait(self, slot=0, rows=False):
         """The block parsed into `slot`: dict(n_lines, n_rows, nnz, n_slow, first_slow_byte, overflow, row_ptr, field,
         feat, val, label) -- the arrays as device addresses, valid until the slot's next parse, and only when
-        n_slow == 0 and overflow == 0."""
+        n_slow == 0 and overflow == 0.
+        rows: also "row_ptr_host", the page-locked host mirror of row_ptr as an int32 array of n_rows + 1 elements (a
+        view, valid until the slot's next parse; None where the arrays are not valid), and "slot" -- what
+        RowCutter.take takes (include/ffm_engine.h "Resident rows")."""
         blk = TextBlock()
-        self._check(self.lib.ffm_engine_textparse_wait(self.h, int(slot), ctypes.byref(blk)))
+        if not rows:
+            self._check(self.lib.ffm_engine_textparse_wait(self.h, int(slot), ctypes.byref(blk)))
+            self._keep[int(slot)] = None
+            return blk.as_dict()
+        mirror = _vp()
+        self._check(self.lib.ffm_engine_textparse_wait_rows(self.h, int(slot), ctypes.byref(blk), ctypes.byref(mirror)))
         self._keep[int(slot)] = None
-        return blk.as_dict()
+        out = blk.as_dict()
+        out["slot"], out["parser"], out["row_ptr_host"] = int(slot), self, None
+        if mirror.value:
+            out["row_ptr_host"] = np.ctypeslib.as_array(ctypes.cast(mirror.value, _i32p), shape=(int(blk.n_rows) + 1,))
+        return out
 
     def close(self):
         if self.h:
@@ -1547,6 +1594,55 @@ class TextParser:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+class RowCutter:
+    """Blocks cut out of parsed text in HBM (include/ffm_engine.h "Resident rows"): a ring of n_blocks buffers of
+    max_rows rows and max_nnz entries.  take / take_host append rows to the block being assembled, close ends it
+    (a RowsBlock for Engine.*_resident), release frees its buffer once the engine has pulled it, destroy frees the cutter."""
+
+    def __init__(self, max_rows, max_nnz, n_blocks=4, device=0):
+        self.lib = load_library()
+        self.h = _vp()
+        self.max_rows, self.max_nnz, self.n_blocks = int(max_rows), int(max_nnz), int(n_blocks)
+        self._check(self.lib.ffm_engine_rowcut_create(self.max_rows, self.max_nnz, self.n_blocks, int(device), ctypes.byref(self.h)))
+
+    def _check(self, rc):
+        if rc != 0:
+            raise EngineError(rc, self.lib.ffm_engine_last_error().decode())
+
+    def take(self, src, r0, r1):
+        """Rows [r0, r1) of `src`, what TextParser.wait(slot, rows=True) returned; asynchronous."""
+        self._check(self.lib.ffm_engine_rowcut_take(self.h, src["parser"].h, int(src["slot"]), int(r0), int(r1)))
+
+    def take_host(self, n_rows, row_ptr, field, feat, val, label):
+        """n_rows rows the host parsed: row_ptr [n_rows + 1] may start anywhere, field / feat / val begin at entry
+        row_ptr[0] and label at the first row (int32 / float32 arrays)."""
+        for a, t in ((row_ptr, np.int32), (field, np.int32), (feat, np.int32), (val, np.float32), (label, np.int32)):
+            if a is not None and (a.dtype != t or not a.flags.c_contiguous):
+                raise ValueError("take_host: contiguous int32 / float32 arrays")
+        self._check(self.lib.ffm_engine_rowcut_take_host(self.h, int(n_rows), _i(row_ptr), _i(field), _i(feat), _f(val), _i(label)))
+
+    def close(self):
+        """Ends the block being assembled: its RowsBlock.  (The cutter itself goes with destroy().)"""
+        blk = RowsBlock()
+        self._check(self.lib.ffm_engine_rowcut_close(self.h, ctypes.byref(blk)))
+        return blk
+
+    def release(self, block):
+        """The block's buffer may be written again (the engine has pulled it: blocks_pulled() >= block.seq)."""
+        self._check(self.lib.ffm_engine_rowcut_release(self.h, int(block.index if isinstance(block, RowsBlock) else block)))
+
+    def destroy(self):
+        if self.h:
+            self.lib.ffm_engine_rowcut_destroy(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
         except Exception:
             pass
 

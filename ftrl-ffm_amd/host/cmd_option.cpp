@@ -171,9 +171,20 @@ const std::string_view cmd_help =
     "              any other line (an exponent, nan, a tab, a malformed token ..) is parsed by the host, whole, so no\n"
     "              result changes and a malformed line ends the run as it does without the flag.  Prints per pass\n"
     "              `device parse: C chunks, B bytes, H parsed by the host (first at byte N)`.  Training, evaluation and\n"
-    "              --predict_data still read through the host parser.  Needs one of the three passes; not with --cmd\n"
-    "              true.  (Environment FFM_TEXT_SLOT_BYTES sets the chunk size: a test hook, results do not depend on\n"
-    "              it)\tdefault:false\n";
+    "              --predict_data read through the host parser unless --device_rows true is given as well.  Needs one of\n"
+    "              the three passes; not with --cmd true.  (Environment FFM_TEXT_SLOT_BYTES sets the chunk size: a test\n"
+    "              hook, results do not depend on it)\tdefault:false\n"
+    "--device_rows <bool>: online training, evaluation and --predict_data read their files as raw bytes; the device parses\n"
+    "              them (the grammar of --device_parse, a chunk with any other line parsed by the host, whole) and cuts the\n"
+    "              parsed rows, in HBM, into the blocks the host would have cut, which the engine stages from there: no\n"
+    "              entry is touched by the host or crosses PCIe a second time.  Losses, AUC / GAUC lines, scores, model\n"
+    "              files and checkpoints do not change by a bit.  Prints per pass `device rows: <train|eval|predict> C\n"
+    "              chunks, B bytes, H parsed by the host (first at byte N), K blocks`.  LR, FM and FFM; one GPU.  Not with\n"
+    "              --online false, --cmd true, --n_gpus > 1, --compact_rows true, or sample weights (--pos_weight,\n"
+    "              --neg_weight, --weight_data) on a run that trains; needs a file to read: --train_data with --n_epochs >\n"
+    "              0, --eval_data or --predict_data.  --field_importance keeps reading --eval_data through the host\n"
+    "              parser.  Independent of --device_parse (the counting passes); with both no text is parsed on the host\n"
+    "              \tdefault:false\n";
 
 static bool assign_bool(std::string arg) {
   std::transform(arg.begin(), arg.end(), arg.begin(), [](unsigned char c) { return std::tolower(c); });
@@ -249,6 +260,7 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--hash_feats") hash_feats = assign_bool(v);
     else if (k == "--normalize_rows") normalize_rows = assign_bool(v);
     else if (k == "--device_parse") device_parse = assign_bool(v);
+    else if (k == "--device_rows") device_rows = assign_bool(v);
     else if (k == "--compact_rows") compact_rows = assign_bool(v);
     else if (k == "--field_importance") field_importance = assign_bool(v);
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
@@ -400,8 +412,23 @@ void config_options::parse_option(int argc, char *argv[]) {
     // only the counting pre-passes read text through the device parser (refused here, before a device is opened)
     if (min_count <= 1 && bucket_fields.empty() && field_ranges != "counted")
       throw std::invalid_argument("--device_parse true parses the text of the counting passes on the device: it needs --min_count > 1, "
-                                  "--bucket_fields or --field_ranges counted (training and evaluation do not read through it yet)");
+                                  "--bucket_fields or --field_ranges counted (training and evaluation read through the device with --device_rows true)");
     if (cmd) throw std::invalid_argument("--device_parse true is not allowed with --cmd true");
+  }
+  if (device_rows) {
+    // the rows of one engine's online passes are cut in HBM (refused here, before a device is opened)
+    const std::string what = "--device_rows true ";
+    if (!online)
+      throw std::invalid_argument(what + "cuts the blocks of a file read in order: --online false loads whole files and shuffles them on the host");
+    if (cmd) throw std::invalid_argument(what + "reads files: --cmd true is not allowed with it");
+    if (n_gpus > 1) throw std::invalid_argument(what + "feeds one whole model on one GPU: --n_gpus > 1 is not allowed with it");
+    if (compact_rows)
+      throw std::invalid_argument(what + "is not allowed with --compact_rows true: the arrays never cross PCIe on this path");
+    if (weights_given && epoch > 0)
+      throw std::invalid_argument(what + "trains without sample weights, which are filled from labels on the host: --pos_weight / "
+                                         "--neg_weight / --weight_data are not allowed with it while --n_epochs > 0");
+    if (!(epoch > 0 && !train_path.empty()) && eval_path.empty() && predict_path.empty())
+      throw std::invalid_argument(what + "needs a file to read: --train_data with --n_epochs > 0, --eval_data or --predict_data");
   }
   // a row's length is a sum over all of its entries (refused here, before a device is opened)
   if (normalize_rows && n_gpus > 1)

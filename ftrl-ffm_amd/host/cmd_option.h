@@ -51,6 +51,9 @@ struct config_options {
   // --device_parse: the counting pre-passes (--bucket_fields, --min_count, --field_ranges counted) read --train_data
   // as raw bytes and parse them on the device (include/ffm_engine.h "Text blocks", text_stream.h); no result changes
   bool device_parse = false;
+  // --device_rows: online training, evaluation and --predict_data read their files as raw bytes, the device parses
+  // them and cuts the blocks in HBM (include/ffm_engine.h "Resident rows", row_stream.h); no result changes
+  bool device_rows = false;
   // --serve_weights none | f32 | f16: score a saved model from a serving engine (FFM_FLAG_SERVE_F32 / _F16: the
   // weights alone, in fp32 bits or IEEE binary16); only with --resume_from ck --n_epochs 0
   std::string serve_weights = "none";

@@ -470,6 +470,30 @@ long long FtrlModel::predict_block_async(const CsrBlock &blk, bool pinned, float
   return ++handed_over_;
 }
 
+void FtrlModel::check_resident(const ffm_rows_block &blk) const {
+  if (grp_) throw std::invalid_argument("resident rows: one GPU only");
+  if (blk.longest_row > max_row_nnz_)
+    throw std::length_error("a row has " + std::to_string(blk.longest_row) + " entries; this engine handles up to " + std::to_string(max_row_nnz_));
+}
+
+long long FtrlModel::stage_block_resident(ffm_rows_block &blk) {
+  check_resident(blk);
+  check(ffm_engine_stage_batch_resident(eng_, &blk), "ffm_engine_stage_batch_resident");
+  return ++handed_over_;
+}
+
+long long FtrlModel::train_block_resident(ffm_rows_block &blk) {
+  check_resident(blk);
+  check(ffm_engine_train_batch_async_resident(eng_, &blk), "ffm_engine_train_batch_async_resident");
+  return ++handed_over_;
+}
+
+long long FtrlModel::predict_block_resident(ffm_rows_block &blk, float *scores, bool output_prob) {
+  check_resident(blk);
+  check(ffm_engine_predict_batch_async_resident(eng_, &blk, output_prob ? 1 : 0, scores), "ffm_engine_predict_batch_async_resident");
+  return ++handed_over_;
+}
+
 long long FtrlModel::blocks_scored() { return grp_ ? 0 : ffm_engine_blocks_scored(eng_); }
 
 bool FtrlModel::pin_scores(float *p, size_t n) {

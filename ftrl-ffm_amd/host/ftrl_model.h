@@ -120,6 +120,17 @@ class FtrlModel {
   long long predict_block_async(const CsrBlock &blk, bool pinned, float *scores = nullptr, bool output_prob = false,
                                 bool *complete = nullptr);
   double eval_flush();
+  // --device_rows: the same three for a block that already lies in HBM (include/ffm_engine.h "Resident rows"; a closed
+  // block of a row cutter, row_stream.h): ffm_engine_stage_batch_resident, _train_batch_async_resident (three blocks in
+  // flight, as train_block_pinned) and _predict_batch_async_resident (scores: page-locked by pin_scores, or null).
+  // The block's buffer is free once blocks_pulled() has reached the ordinal returned (also left in blk.seq).  One
+  // engine only; a row beyond the engine's row capacity throws the std::length_error of the host forms.
+  long long stage_block_resident(ffm_rows_block &blk);
+  long long train_block_resident(ffm_rows_block &blk);
+  long long predict_block_resident(ffm_rows_block &blk, float *scores = nullptr, bool output_prob = false);
+  // what one engine call takes: the rows and entries of a block
+  size_t block_rows_capacity() const { return static_cast<size_t>(max_rows_); }
+  size_t block_nnz_capacity() const { return static_cast<size_t>(max_nnz_); }
   // Ordinal of the last block whose scores are whole (non-blocking, never decreases; may be asked
   // from another thread than the one that hands blocks over); 0 for a group.
   long long blocks_scored();
@@ -265,6 +276,7 @@ class FtrlModel {
   CsrBlock part_;
   // calls `fn(sub-block)` for consecutive row ranges of blk that fit the engine
   template <typename Fn> void for_each_fitting(const CsrBlock &blk, Fn fn);
+  void check_resident(const ffm_rows_block &blk) const;
 };
 
 class LR : public FtrlModel {

@@ -141,14 +141,22 @@ bool TextChunkStream::next(TextChunk *out) {
   return true;
 }
 
-unsigned long long device_parse_pass(const config_options &opt, const DeviceParseHooks &hooks) {
-  const bool has_field = opt.file_type == "libffm";
-  // FFM_TEXT_SLOT_BYTES: a TEST HOOK (`--device_parse true`): the slots' size, a test's way to many chunks,
-  // carried tails and over-long lines from a small file; results do not depend on it
+void TextChunkStream::rewind() {
+  pos_ = 0;
+  tail_ = nullptr;
+  tail_len_ = 0;
+  turn_ = 0;
+}
+
+size_t TextChunkStream::slot_bytes_from_env() {
   const char *slot_env = std::getenv("FFM_TEXT_SLOT_BYTES");
   const long long slot_bytes = slot_env ? std::atoll(slot_env) : 0;
-  TextChunkStream ts(opt.train_path, opt.thread_num,
-                     slot_bytes >= 16 && slot_bytes <= (1ll << 30) ? static_cast<size_t>(slot_bytes) : TextChunkStream::kSlotBytes);
+  return slot_bytes >= 16 && slot_bytes <= (1ll << 30) ? static_cast<size_t>(slot_bytes) : kSlotBytes;
+}
+
+unsigned long long device_parse_pass(const config_options &opt, const DeviceParseHooks &hooks) {
+  const bool has_field = opt.file_type == "libffm";
+  TextChunkStream ts(opt.train_path, opt.thread_num, TextChunkStream::slot_bytes_from_env());
   ParserHandle tp;
   {
     // capacities no chunk can exceed: a row is at least 2 bytes of text ("1\n"), an entry at least 4 ("1:1 ")

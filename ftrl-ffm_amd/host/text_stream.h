@@ -36,6 +36,10 @@ class TextChunkStream {
   // The next chunk; false at the end of the file.  It stays valid until the call after the next one.
   bool next(TextChunk *out);
   size_t slot_bytes() const { return slot_bytes_; }
+  void rewind();  // back to the file's first byte (the next pass); chunks handed out before are no longer valid
+  // kSlotBytes, or what FFM_TEXT_SLOT_BYTES says: a TEST HOOK (`--device_parse true`), a test's way to many
+  // chunks, carried tails and over-long lines from a small file; results do not depend on it
+  static size_t slot_bytes_from_env();
 
  private:
   void read_at(char *dst, size_t n, unsigned long long off);  // pread by n_threads_ threads

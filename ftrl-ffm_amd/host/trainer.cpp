@@ -216,7 +216,11 @@ FtrlOnline::FtrlOnline(const config_options &opt)
   publish_fmt_ = opt.publish_weights;
   n_feats_ = opt.n_feats;
   if (!cmd_) {
-    if (!opt.train_path.empty())  // (--n_epochs 0 needs no training file)
+    if (!opt.train_path.empty() && opt.device_rows && opt.epoch > 0) {
+      FtrlModel *m = model_ptr.get();
+      train_rows_ = std::make_unique<RowStream>(opt.train_path, opt.file_type, opt.thread_num, opt.device, m->block_rows_capacity(),
+                                                m->block_nnz_capacity(), "train", [m] { return m->blocks_pulled(); });
+    } else if (!opt.train_path.empty())  // (--n_epochs 0 needs no training file)
       train_stream_ = std::make_unique<CsrStream>(opt.train_path, opt.file_type, opt.thread_num);
     if (!opt.eval_path.empty()) {
       evaluator = std::make_unique<Evaluator>(opt);
@@ -233,6 +237,27 @@ void FtrlOnline::set_sample_weights(SampleWeights w) { weights_ = std::move(w); 
 // block-size ramp, gathered in page-locked ring entries and handed to the engine, which uploads
 // and groups block t+2 while block t trains.
 void FtrlOnline::run_train_file() {
+  if (train_rows_) {  // --device_rows true: the same blocks, cut in HBM
+    unsigned long long rows = 0, next_report = 1000000;
+    for (;;) {
+      ffm_rows_block blk{};
+      const size_t got = train_rows_->next(static_cast<size_t>(sched_.next_block_rows()), &blk);
+      if (got == 0) break;
+      model_ptr->train_block_resident(blk);
+      train_rows_->handed_over(blk);
+      sched_.consumed(static_cast<int>(got));
+      rows += got;
+      if (rows >= next_report) {  // pc_task.cpp:47-49
+        std::printf("%llu lines finished...\n", next_report);
+        next_report += 1000000;
+      }
+    }
+    loss_sum_ = model_ptr->train_flush();
+    loss_rows_ = rows;
+    weight_sum_ = 0.0;
+    train_rows_->rewind();
+    return;
+  }
   if (!ring_) ring_ = std::make_unique<BlockRing>(model_ptr.get(), weights_.on);
   const bool ring = ring_->ready();
   CsrBlock blk;
@@ -315,8 +340,15 @@ void FtrlOnline::evaluate(int epoch) {
 // ---------------- Evaluator ----------------
 
 Evaluator::Evaluator(const config_options &opt)
-    : stream_(std::make_unique<CsrStream>(opt.eval_path, opt.file_type, opt.thread_num)),
-      batch_(std::max(1, opt.batch_size)), want_auc_(opt.metrics == "auc") {}
+    : stream_(opt.device_rows ? nullptr : std::make_unique<CsrStream>(opt.eval_path, opt.file_type, opt.thread_num)),
+      batch_(std::max(1, opt.batch_size)), want_auc_(opt.metrics == "auc") {
+  if (opt.device_rows) {
+    rows_path_ = opt.eval_path;
+    rows_type_ = opt.file_type;
+    rows_threads_ = opt.thread_num;
+    rows_device_ = opt.device;
+  }
+}
 Evaluator::~Evaluator() = default;
 
 void Evaluator::load_trained_model(std::shared_ptr<FtrlModel> &train_model) {  // evaluate.cpp:35-37
@@ -324,10 +356,30 @@ void Evaluator::load_trained_model(std::shared_ptr<FtrlModel> &train_model) {  /
   // (--metrics auc: the eval channel on; whatever the owner of the model set for training stays)
   if (want_auc_ && !eval_model->metrics_on(FFM_METRIC_EVAL)) eval_model->enable_metrics(true, eval_model->metrics_on(FFM_METRIC_TRAIN));
   ring_ = std::make_unique<BlockRing>(eval_model.get());
+  if (!rows_path_.empty()) {  // --device_rows true (the blocks' capacities are the model's)
+    FtrlModel *m = eval_model.get();
+    row_stream_ = std::make_unique<RowStream>(rows_path_, rows_type_, rows_threads_, rows_device_, m->block_rows_capacity(), m->block_nnz_capacity(),
+                                        "eval", [m] { return m->blocks_pulled(); });
+  }
 }
 
 void Evaluator::run() {
   if (!eval_model) throw std::logic_error("Evaluator::run before load_trained_model");
+  if (row_stream_) {  // --device_rows true: the same blocks, cut in HBM
+    unsigned long long rows = 0;
+    for (;;) {
+      ffm_rows_block blk{};
+      const size_t got = row_stream_->next(static_cast<size_t>(batch_), &blk);
+      if (got == 0) break;
+      eval_model->predict_block_resident(blk);
+      row_stream_->handed_over(blk);
+      rows += got;
+    }
+    loss_sum_ = eval_model->eval_flush();
+    rows_ = rows;
+    row_stream_->rewind();
+    return;
+  }
   const bool ring = ring_->ready();
   CsrBlock blk;
   unsigned long long rows = 0;
@@ -367,16 +419,20 @@ double Evaluator::get_loss() {
 // ---------------- Scorer ----------------
 
 Scorer::Scorer(const config_options &opt, FtrlModel *model)
-    : model_(model), stream_(std::make_unique<CsrStream>(opt.predict_path, opt.file_type, opt.thread_num)),
+    : model_(model), stream_(opt.device_rows ? nullptr : std::make_unique<CsrStream>(opt.predict_path, opt.file_type, opt.thread_num)),
       out_path_(opt.predict_out), batch_(std::max(1, opt.batch_size)), n_threads_(std::max(1, opt.thread_num)),
-      prob_(opt.predict_prob) {}
+      prob_(opt.predict_prob) {
+  if (opt.device_rows)
+    row_stream_ = std::make_unique<RowStream>(opt.predict_path, opt.file_type, opt.thread_num, opt.device, model->block_rows_capacity(),
+                                        model->block_nnz_capacity(), "predict", [model] { return model->blocks_pulled(); });
+}
 Scorer::~Scorer() = default;
 
 unsigned long long Scorer::run() {
   std::FILE *f = std::fopen(out_path_.c_str(), "wb");
   if (!f) throw std::runtime_error("cannot open " + out_path_ + " for writing");
   BlockRing ring(model_);
-  const bool pinned_rows = ring.ready();
+  const bool pinned_rows = !row_stream_ && ring.ready();
   // the ring of score buffers: entry i % kScoreRing carries block i from its hand-over to its write
   struct Entry {
     std::vector<float, PageAllocator<float>> buf;
@@ -452,6 +508,23 @@ unsigned long long Scorer::run() {
       Entry &en = ent[i % kScoreRing];
       const CsrBlock *b = &blk;
       size_t got;
+      if (row_stream_) {  // --device_rows true: the same blocks, cut in HBM; the score ring and the writer as they are
+        if (!en.pinned) throw std::runtime_error("--device_rows true needs page-locked score buffers, and none could be had");
+        ffm_rows_block rb{};
+        got = row_stream_->next(static_cast<size_t>(batch_), &rb);
+        if (got == 0) break;
+        const long long ordinal = model_->predict_block_resident(rb, en.buf.data(), prob_);
+        row_stream_->handed_over(rb);
+        en.rows = got;
+        en.wait_for = ordinal;
+        {
+          std::lock_guard<std::mutex> lock(mu);
+          submitted = i + 1;
+        }
+        cv.notify_all();
+        rows += got;
+        continue;
+      }
       if (pinned_rows) {
         CsrBlock &rb = ring.acquire();
         got = stream_->next(std::min<size_t>(batch_, ring.row_capacity()), rb, ring.nnz_capacity(), true);
@@ -481,7 +554,7 @@ unsigned long long Scorer::run() {
   finish(false);
   const bool closed = std::fclose(f) == 0;
   if (write_failed || !closed) throw std::runtime_error("writing " + out_path_ + " failed");
-  stream_->rewind();
+  if (row_stream_) row_stream_->rewind(); else stream_->rewind();
   return rows;
 }
 

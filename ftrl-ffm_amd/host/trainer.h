@@ -21,6 +21,7 @@
 #include "csr_reader.h"
 #include "csr_stream.h"
 #include "reader.h"
+#include "row_stream.h"
 #include "sample_weights.h"
 
 namespace ftrl {
@@ -85,6 +86,10 @@ class Evaluator {
   std::shared_ptr<FtrlModel> eval_model;
   std::unique_ptr<CsrStream> stream_;
   std::unique_ptr<BlockRing> ring_;
+  // --device_rows true: the file is read through these instead (row_stream.h; made by load_trained_model)
+  std::unique_ptr<RowStream> row_stream_;
+  std::string rows_path_, rows_type_;
+  int rows_threads_ = 1, rows_device_ = 0;
   int batch_;
   bool want_auc_ = false;
   double loss_sum_ = 0.0;
@@ -110,6 +115,7 @@ class Scorer {
  private:
   FtrlModel *model_;
   std::unique_ptr<CsrStream> stream_;
+  std::unique_ptr<RowStream> row_stream_;  // --device_rows true: instead of stream_
   std::string out_path_;
   int batch_, n_threads_;
   bool prob_;
@@ -204,6 +210,7 @@ class FtrlOnline {
   long long n_feats_ = 0;
   BlockScheduler sched_;
   std::unique_ptr<CsrStream> train_stream_;  // chunks of <= 20 000 lines parsed by n_threads workers
+  std::unique_ptr<RowStream> train_rows_;    // --device_rows true: instead of train_stream_ (row_stream.h)
   std::unique_ptr<BlockRing> ring_;
   double loss_sum_ = 0.0;
   unsigned long long loss_rows_ = 0;

@@ -1193,6 +1193,78 @@ void ffm_engine_textparse_destroy(ffm_textparse *p);
 int ffm_engine_textparse_host(int32_t has_field, const char *text, int64_t n_bytes, int32_t max_rows, int32_t max_nnz,
                               int32_t *row_ptr, int32_t *field, int32_t *feat, float *val, int32_t *label, ffm_text_block *out);
 
+/* ---- Resident rows: blocks cut out of parsed text in HBM, staged without crossing PCIe again ------------------
+ * A text parser leaves a chunk's rows in HBM in the layout the engine wants.  A ROW CUTTER cuts them into the blocks
+ * a trainer would have cut -- so many rows, so many entries at the most, across chunk borders -- without the host
+ * touching an entry, and the three staged entry points have twins that take such a block.  Everything behind the
+ * source of the bytes is shared with the host forms: the same upload kernel instantiations (hashing, rare-id folding,
+ * bucketing), the same row normalisation, grouping, schedule and numbering (ffm_engine_blocks_pulled / _scored), so
+ * every result is the host form's bit for bit.
+ *   mirror     ffm_engine_textparse_wait_rows is ffm_engine_textparse_wait and also hands back a page-locked HOST
+ *              mirror of the slot's row_ptr [n_rows + 1] -- all the host needs of a chunk to place the cuts.  NULL
+ *              when the block's arrays are not valid (n_slow != 0 or overflow).  It is valid until the slot's next
+ *              parse.  The first such wait allocates the mirrors (4 bytes per row of max_rows, both slots) and
+ *              copies its own behind the parse; from then on every parse copies its slot's on the parser's stream
+ *              ahead of the slot's event, and the wait stays the one host wait per chunk.  A parser that never asks
+ *              allocates and copies nothing.
+ *   cutter     ffm_engine_rowcut_create: a ring of n_blocks (1 .. 64) buffers in HBM, each row_ptr [max_rows + 1],
+ *              label [max_rows], field / feat / val [max_nnz], 16-byte aligned.  It needs no engine.
+ *   take       appends rows [r0, r1) of the block waited for in `slot` (with _wait_rows) to the block being
+ *              assembled: ONE kernel launch on the PARSER's stream -- so the slot's arrays are read before the slot
+ *              is parsed into again, by stream order -- copies the entries and labels, 16 bytes per lane where the
+ *              alignments allow, and rebases row_ptr to the block's running entry count (row_ptr[0] of a block is
+ *              0).  The launch is sized by the host from the mirror; the kernel reads no count from memory, and every
+ *              store is guarded by the buffer's capacity.  Asynchronous.
+ *   take_host  the same for rows the HOST parsed (a chunk the device will not parse: ffm_text_block.n_slow,
+ *              overflow, a line longer than a slot): row_ptr [n_rows + 1] may start at any value, field / feat / val
+ *              point at entry row_ptr[0] and label at the first row.  It appends at the same position, so device-
+ *              and host-parsed rows may meet in one block.  The arrays are free when it returns.
+ *   close      ends the block: its n_rows, nnz and longest row (all known on the host), the DEVICE pointers, `index`
+ *              (its buffer) and `ready`, an event behind the block's last take.  A block of no rows is valid.  The
+ *              ring moves on.
+ *   release    the buffer `index` may be written again.  The caller releases a block once the engine has pulled it:
+ *              the resident entry points store the block's staging number in ffm_rows_block.seq, and the block is
+ *              free when ffm_engine_blocks_pulled has reached it -- the rule of page-locked blocks.  Until then a
+ *              take or close into that buffer is FFM_E_CAPACITY, and nothing is launched.
+ *   staging    ffm_engine_stage_batch_resident / _train_batch_async_resident / _predict_batch_async_resident are
+ *              ffm_engine_stage_batch / _train_batch_async_pinned (three blocks in flight) /
+ *              _predict_batch_async_scores (scores_host may be NULL) with zero_copy != 0, for a block whose arrays
+ *              are DEVICE memory of the engine's device, 16-byte aligned: the upload waits for `ready` (may be NULL:
+ *              the block is whole) on the engine's side stream and reads HBM.  Any such block will do, a cutter's or
+ *              the caller's own.  field is ignored on LR / FM; FFM needs it, and every block brings val.
+ *   refused    what the host forms refuse, with their codes and texts: n_rows > max_batch_rows and nnz >
+ *              max_batch_nnz (FFM_E_CAPACITY), longest_row > max_row_nnz (FFM_E_CAPACITY), training on a serving
+ *              engine (FFM_E_UNSUPPORTED), a missing array; longest_row outside [0, nnz] and an array that is not
+ *              16-byte aligned are FFM_E_INVALID.  longest_row is trusted beyond that, as nnz is on every _device
+ *              entry point.  A take beyond max_rows / max_nnz of the cutter is FFM_E_CAPACITY before anything is
+ *              launched; rows outside the slot's block, a slot that was not waited for with _wait_rows, a parser on
+ *              another device are FFM_E_INVALID.
+ * An engine that never calls these allocates nothing and launches nothing new; no existing kernel changed.
+ * OUT OF SCOPE  sample weights on this path; offline mode (whole files shuffled on the host); groups and shards;
+ *               copying chunk t + 1 on a second stream while chunk t parses; any change to the text kernels; a
+ *               fallback per line (a chunk falls back whole). */
+typedef struct ffm_rowcut ffm_rowcut;
+typedef struct {
+  int32_t n_rows, nnz, longest_row;  /* longest_row: the most entries of one row (0 in a block without entries) */
+  int32_t index;                     /* the cutter's buffer (ffm_engine_rowcut_release); unused by the engine */
+  int64_t seq;                       /* OUT of the resident entry points: the block's staging number */
+  const int32_t *row_ptr, *field, *feat, *label;  /* DEVICE pointers, 16-byte aligned */
+  const float *val;
+  void *ready;                       /* hipEvent_t behind the block's last write, or NULL */
+} ffm_rows_block;
+int ffm_engine_textparse_wait_rows(ffm_textparse *p, int32_t slot, ffm_text_block *out, const int32_t **row_ptr_host);
+int ffm_engine_rowcut_create(int32_t max_rows, int32_t max_nnz, int32_t n_blocks, int32_t device_id, ffm_rowcut **out);
+int ffm_engine_rowcut_take(ffm_rowcut *c, ffm_textparse *p, int32_t slot, int32_t r0, int32_t r1); /* asynchronous */
+int ffm_engine_rowcut_take_host(ffm_rowcut *c, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
+                                const int32_t *feat, const float *val, const int32_t *label);
+int ffm_engine_rowcut_close(ffm_rowcut *c, ffm_rows_block *out);
+int ffm_engine_rowcut_release(ffm_rowcut *c, int32_t index);
+void ffm_engine_rowcut_destroy(ffm_rowcut *c);
+int ffm_engine_stage_batch_resident(ffm_engine *e, ffm_rows_block *block);
+int ffm_engine_train_batch_async_resident(ffm_engine *e, ffm_rows_block *block);
+int ffm_engine_predict_batch_async_resident(ffm_engine *e, ffm_rows_block *block, int32_t output_prob,
+                                            float *scores_host);
+
 #ifdef __cplusplus
 }
 #endif
