@@ -52,6 +52,7 @@
 #include "kernels_serve.h"
 #include "kernels_delta.h"
 #include "kernels_ablate.h"
+#include "kernels_ablate_pairs.h"
 #include "kernels_stage.h"
 #include "kernels_sketch.h"
 #include "kernels_idcount.h"
@@ -452,6 +453,14 @@ struct ffm_engine {
     double *loss = nullptr, *sums = nullptr, *part = nullptr;
     unsigned long long *hist = nullptr;
   } abl;
+  // pair ablation (include/ffm_engine.h "Pair ablation", engine_ablate_pairs.h), all made by
+  // ffm_engine_pair_ablation_enable: the same five arrays for V + 1 = n_fields (n_fields + 1) / 2 + 1 variants
+  struct {
+    bool on = false, auc = false;
+    float *out = nullptr;
+    double *loss = nullptr, *sums = nullptr, *part = nullptr;
+    unsigned long long *hist = nullptr;
+  } pabl;
   std::vector<void *> allocs;
   // split-phase bookkeeping
   Rows pending{};
@@ -862,6 +871,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_text.h"
 #include "engine_rows.h"
 #include "engine_ablate.h"
+#include "engine_ablate_pairs.h"
 }  // extern "C"
 
 #include "engine_group.h"

@@ -132,6 +132,33 @@ inline AblateWaveFn ablate_wave_fn(int fmt, int n_factors) {
     default: return nullptr;
   }
 }
+// pair ablation (kernels_ablate_pairs.h): a lane keeps ceil(V / 64) running values in registers, V = F (F + 1) / 2,
+// and their number is a template bound -- 2 (up to 15 fields), 13 (up to 40: the headline shape's 39 need all 13)
+// or 33 (up to 64 fields).  A smaller model pays for the idle accumulators of its bound, never for scratch.
+inline int ablate_pairs_rounds(int n_fields) {
+  if (n_fields < 1 || n_fields > kPairFields) return 0;
+  const int rounds = (pair_variants(n_fields) + 63) / 64;
+  return rounds <= 2 ? 2 : rounds <= 13 ? 13 : 33;
+}
+template <int FMT, int LPP, int VPL, int U>
+constexpr AblateWaveFn ablate_pairs_2 = ffm_ablate_pairs_kernel<FMT, LPP, VPL, U, 2>;
+template <int FMT, int LPP, int VPL, int U>
+constexpr AblateWaveFn ablate_pairs_13 = ffm_ablate_pairs_kernel<FMT, LPP, VPL, U, 13>;
+template <int FMT, int LPP, int VPL, int U>
+constexpr AblateWaveFn ablate_pairs_33 = ffm_ablate_pairs_kernel<FMT, LPP, VPL, U, 33>;
+// rounds: ablate_pairs_rounds(n_fields); the arguments are ffm_ablate_wave_kernel's
+inline AblateWaveFn ablate_pairs_fn(int fmt, int n_factors, int rounds) {
+  switch (n_factors) {
+#define X(K, LPP, VPL, U)                                                            \
+  case K:                                                                            \
+    return rounds == 2    ? FFM_BY_ANY_FMT(ablate_pairs_2, LPP, VPL, U)              \
+           : rounds == 13 ? FFM_BY_ANY_FMT(ablate_pairs_13, LPP, VPL, U)             \
+           : rounds == 33 ? FFM_BY_ANY_FMT(ablate_pairs_33, LPP, VPL, U) : nullptr;
+    FFM_LANE_SHAPES(X)
+#undef X
+    default: return nullptr;
+  }
+}
 #undef FFM_BY_ANY_FMT
 #undef FFM_BY_FMT
 #undef FFM_LANE_SHAPES

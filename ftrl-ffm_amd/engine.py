@@ -271,6 +271,16 @@ ABI = [
     ("ffm_engine_predict_ablated_device", ctypes.c_int,
      [_vp, ctypes.c_int32, ctypes.c_int32] + _DCSR + [ctypes.c_int32, _vp, _vp]),
     ("ffm_engine_ablation_read", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(Metrics)]),
+    # the loss and AUC of the model without each field pair, in one pass (include/ffm_engine.h "Pair ablation")
+    ("ffm_engine_pair_count", ctypes.c_int32, [ctypes.c_int32]),
+    ("ffm_engine_pair_index", ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    ("ffm_engine_pair_fields", ctypes.c_int,
+     [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    ("ffm_engine_pair_ablation_enable", ctypes.c_int, [_vp, ctypes.c_int32]),
+    ("ffm_engine_predict_pair_ablated", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [ctypes.c_int32, _f32p, _f64p]),
+    ("ffm_engine_predict_pair_ablated_device", ctypes.c_int,
+     [_vp, ctypes.c_int32, ctypes.c_int32] + _DCSR + [ctypes.c_int32, _vp, _vp]),
+    ("ffm_engine_pair_ablation_read", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(Metrics)]),
     # sync a serving engine, publish only what moved (include/ffm_engine.h "Serving deltas")
     ("ffm_engine_sync_weights", ctypes.c_int, [_vp, _vp, ctypes.POINTER(SyncStats)]),
     ("ffm_engine_sync_moved", ctypes.c_int, [_vp, _i32p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
@@ -654,6 +664,50 @@ def drop_field(block, f):
     row_ptr = kept[np.asarray(block.row_ptr, np.int64)].astype(np.int32)
     return Block(row_ptr, np.ascontiguousarray(field[keep], np.int32), np.ascontiguousarray(np.asarray(block.feat)[keep], np.int32),
                  None if block.val is None else np.ascontiguousarray(np.asarray(block.val)[keep], np.float32), block.label)
+
+
+def pair_count(n_fields):
+    """V = n_fields (n_fields + 1) / 2: the unordered field pairs with the diagonal (include/ffm_engine.h "Pair
+    ablation"; host arithmetic, no device).  n_fields in 1 .. 64."""
+    lib = load_library()
+    v = lib.ffm_engine_pair_count(int(n_fields))
+    if v < 0:
+        raise EngineError(E_INVALID, lib.ffm_engine_last_error().decode())
+    return int(v)
+
+
+def pair_index(n_fields, f, g):
+    """The variant of the pair {f, g}, in either order: for f <= g, f * F - f * (f - 1) / 2 + (g - f)."""
+    lib = load_library()
+    v = lib.ffm_engine_pair_index(int(n_fields), int(f), int(g))
+    if v < 0:
+        raise EngineError(E_INVALID, lib.ffm_engine_last_error().decode())
+    return int(v)
+
+
+def pair_fields(n_fields, v):
+    """(f, g) with f <= g and pair_index(n_fields, f, g) == v, for v in [0, pair_count(n_fields))."""
+    lib = load_library()
+    f, g = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    rc = lib.ffm_engine_pair_fields(int(n_fields), int(v), ctypes.byref(f), ctypes.byref(g))
+    if rc != 0:
+        raise EngineError(rc, lib.ffm_engine_last_error().decode())
+    return int(f.value), int(g.value)
+
+
+def drop_pair_weights(vec_w, ids_of_field_f, g):
+    """A copy of vec_w [n_feats, n_fields, k] (a 2-d table: vec_w.reshape(n_feats, n_fields, k)) with the slot
+    "towards field g" set to +0.0 for every id in ids_of_field_f: the weights on which predict_batch gives
+    variant (f, g) of pair ablation bit for bit (include/ffm_engine.h "Pair ablation", "as weights"; f == g
+    zeroes the field's own slot).  Two conditions, both the caller's: every feature id of the block occurs under
+    one field only (else the zeroed slot also removes terms of another pair), and the model's bias is not -0.0 (a
+    running sum that starts anywhere else is never -0.0, so adding the +-0.0 such a term becomes changes no bit)."""
+    w = np.array(vec_w, np.float32, copy=True)
+    if w.ndim != 3:
+        raise ValueError("vec_w: [n_feats, n_fields, k] (reshape a 2-d table first)")
+    ids = np.asarray(ids_of_field_f, np.int64).reshape(-1)
+    w[ids, int(g), :] = np.float32(0.0)
+    return w
 
 
 def spell_out_candidates(ctx, cand_req_ptr, cand):
@@ -1336,6 +1390,39 @@ class Engine:
         field v over every labelled block predict_ablated has seen (ablation_enable(auc=True))."""
         m = (Metrics * (self.n_fields + 1))()
         self._check(self.lib.ffm_engine_ablation_read(self.h, int(bool(reset)), m))
+        return [x.as_dict() for x in m]
+
+    # ---- pair ablation (include/ffm_engine.h "Pair ablation") ----
+    def pair_ablation_enable(self, auc=False):
+        """Allocates what predict_pair_ablated needs: (V + 1) x max_batch_rows scores and losses, V =
+        pair_count(n_fields), and, with auc, V + 1 score histograms of 16.8 MB each (13 GB at 39 fields, 35 GB at
+        64).  FFM, one whole model on one device, n_factors in {4, 8, 16, 32, 64}, at most 64 fields; training
+        and serving engines."""
+        self._check(self.lib.ffm_engine_pair_ablation_enable(self.h, int(bool(auc))))
+
+    def predict_pair_ablated(self, c, output_prob=False, with_loss=True, scores=True):
+        """(out[V + 1, n_rows] or None, loss_sums[V + 1]): row pair_index(n_fields, f, g) is the prediction
+        without the terms between fields f and g, row V is predict_batch(c), bit for bit, from one pass over c.
+        scores=False leaves the scores in HBM and returns None for them: only the loss sums come back."""
+        V = self.n_fields * (self.n_fields + 1) // 2 + 1
+        out = np.zeros((V, c.n_rows), np.float32) if scores else None  # (variant-major with stride n_rows)
+        loss = np.zeros(V, np.float64)
+        n, rp, fld, ft, v, lab = self._csr(c)
+        self._check(self.lib.ffm_engine_predict_pair_ablated(self.h, n, rp, fld, ft, v, lab if with_loss else None,
+                                                             int(output_prob), _f(out), loss.ctypes.data_as(_f64p)))
+        return out, loss
+
+    def predict_pair_ablated_device(self, n_rows, nnz, row_ptr, field, feat, val, label, output_prob, out, loss_sum_out=None):
+        """predict_pair_ablated on arrays already in HBM (device addresses; out[(V + 1) * n_rows] variant-major or
+        None, loss_sum_out[V + 1]).  Asynchronous on the engine's stream; sync() reports a too-long row."""
+        self._check(self.lib.ffm_engine_predict_pair_ablated_device(self.h, int(n_rows), int(nnz), row_ptr, field, feat, val,
+                                                                    label, int(output_prob), out, loss_sum_out))
+
+    def pair_ablation_metrics(self, reset=False):
+        """One dict per variant (V + 1), as metrics() returns for a channel: the AUC of the model without the pair
+        over every labelled block predict_pair_ablated has seen (pair_ablation_enable(auc=True))."""
+        m = (Metrics * (self.n_fields * (self.n_fields + 1) // 2 + 1))()
+        self._check(self.lib.ffm_engine_pair_ablation_read(self.h, int(bool(reset)), m))
         return [x.as_dict() for x in m]
 
     # ---- the grouped AUC (include/ffm_engine.h "Metrics", keyed capture) ----

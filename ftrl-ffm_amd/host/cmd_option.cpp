@@ -117,6 +117,17 @@ const std::string_view cmd_help =
     "              `field f: without it loss L (delta D), auc A (delta D)`; the AUC parts only with --metrics auc.  Needs\n"
     "              --eval_data; FFM only, one GPU, --n_fields <= 64, --n_factors 4, 8, 16, 32 or 64, rows of at most 128\n"
     "              entries.  Nothing else of the output changes\tdefault:false\n"
+    "--pair_importance <bool>: which interactions carry the model?  true = one more pass over --eval_data after the last\n"
+    "              evaluation (after --field_importance's when both are given; with --resume_from ck --n_epochs 0 as that\n"
+    "              flag, --serve_weights or not): every row is predicted n_fields (n_fields + 1) / 2 + 1 ways in one pass\n"
+    "              on the device: as it is, and without the terms between fields f and g for every pair f <= g (f = g:\n"
+    "              between two entries of one field; linear terms stay; exact, not an approximation).  Prints `pair\n"
+    "              importance: R rows, loss L, auc A`, then `pair f g: without it loss L (delta D), auc A (delta D)` per\n"
+    "              pair whose loss sum differs from the whole row's, in index order, then `pair importance: P of V pairs\n"
+    "              listed, Q never changed a row`; the AUC parts only with --metrics auc, which keeps a 16.8 MB histogram\n"
+    "              per pair on the device (13 GB at 39 fields, 35 GB at 64; printed before it is allocated).  Reads through\n"
+    "              the host parser.  Needs --eval_data; FFM only, one GPU, --n_fields <= 64, --n_factors 4, 8, 16, 32 or\n"
+    "              64, rows of at most 128 entries.  Nothing else of the output changes\tdefault:false\n"
     "--publish_path <prefix>: after every epoch's training (after that epoch's --refresh_weights refresh when it is on,\n"
     "              before its evaluation) write <prefix>.<epochs_done>.delta: the features whose serving bits moved since\n"
     "              the previous delta, in a serving engine's own format -- delta 1 is relative to a fresh serving engine of\n"
@@ -263,6 +274,7 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--device_rows") device_rows = assign_bool(v);
     else if (k == "--compact_rows") compact_rows = assign_bool(v);
     else if (k == "--field_importance") field_importance = assign_bool(v);
+    else if (k == "--pair_importance") pair_importance = assign_bool(v);
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
     else if (k == "--field_ranges") field_ranges = v;
     else if (k == "--field_ranges_out") field_ranges_out = v;
@@ -514,6 +526,19 @@ void config_options::parse_option(int argc, char *argv[]) {
     if (n_gpus > 1) throw std::invalid_argument(what + "runs on one whole model on one GPU: --n_gpus > 1 is not allowed with it");
     if (n_fields > 64)
       throw std::invalid_argument(what + "keeps one lane of a 64-lane wave per field: --n_fields is " + std::to_string(n_fields) + ", at most 64");
+    if (n_factors != 4 && n_factors != 8 && n_factors != 16 && n_factors != 32 && n_factors != 64)
+      throw std::invalid_argument(what + "runs the one-wave-per-row kernel: --n_factors must be 4, 8, 16, 32 or 64 (got " +
+                                  std::to_string(n_factors) + ")");
+  }
+  if (pair_importance) {
+    // the same pass with a variant per field pair (refused here, before a device is opened)
+    const std::string what = "--pair_importance true ";
+    if (eval_path.empty()) throw std::invalid_argument(what + "ablates the field pairs on the evaluation file: it needs --eval_data");
+    if (model_type != "FFM") throw std::invalid_argument(what + "drops field pairs, which only FFM rows have (got --model_type " + model_type + ")");
+    if (n_gpus > 1) throw std::invalid_argument(what + "runs on one whole model on one GPU: --n_gpus > 1 is not allowed with it");
+    if (n_fields > 64)
+      throw std::invalid_argument(what + "keeps the pairs of at most 64 fields in the registers of a 64-lane wave: --n_fields is " +
+                                  std::to_string(n_fields) + ", at most 64");
     if (n_factors != 4 && n_factors != 8 && n_factors != 16 && n_factors != 32 && n_factors != 64)
       throw std::invalid_argument(what + "runs the one-wave-per-row kernel: --n_factors must be 4, 8, 16, 32 or 64 (got " +
                                   std::to_string(n_factors) + ")");

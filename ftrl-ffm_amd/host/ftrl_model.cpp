@@ -446,6 +446,35 @@ std::vector<ffm_metrics> FtrlModel::read_ablation_metrics(bool reset) {
   return m;
 }
 
+void FtrlModel::enable_pair_ablation(bool with_auc) {
+  if (grp_) throw std::invalid_argument("pair ablation: one GPU only");
+  check(ffm_engine_pair_ablation_enable(eng_, with_auc ? 1 : 0), "ffm_engine_pair_ablation_enable");
+}
+
+void FtrlModel::predict_pair_ablated_block(const CsrBlock &blk, std::vector<double> &loss_sums) {
+  if (grp_) throw std::invalid_argument("pair ablation: one GPU only");
+  const int32_t pairs = ffm_engine_pair_count(n_fields);
+  if (pairs < 0) throw std::invalid_argument("pair ablation: at most 64 fields");
+  const size_t variants = static_cast<size_t>(pairs) + 1;
+  if (loss_sums.size() != variants) throw std::invalid_argument("pair ablation: loss_sums needs n_fields (n_fields + 1) / 2 + 1 entries");
+  std::vector<double> part(variants);
+  for_each_fitting(blk, [&](const CsrBlock &b, int) {
+    check(ffm_engine_predict_pair_ablated(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(), b.val.data(),
+                                          b.label.data(), 0, nullptr, part.data()),
+          "ffm_engine_predict_pair_ablated");
+    for (size_t v = 0; v < variants; v++) loss_sums[v] += part[v];
+  });
+}
+
+std::vector<ffm_metrics> FtrlModel::read_pair_ablation_metrics(bool reset) {
+  if (grp_) throw std::invalid_argument("pair ablation: one GPU only");
+  const int32_t pairs = ffm_engine_pair_count(n_fields);
+  if (pairs < 0) throw std::invalid_argument("pair ablation: at most 64 fields");
+  std::vector<ffm_metrics> m(static_cast<size_t>(pairs) + 1);
+  check(ffm_engine_pair_ablation_read(eng_, reset ? 1 : 0, m.data()), "ffm_engine_pair_ablation_read");
+  return m;
+}
+
 long long FtrlModel::predict_block_async(const CsrBlock &blk, bool pinned, float *scores, bool output_prob, bool *complete) {
   const int n = blk.n_rows();
   bool fits = n <= max_rows_ && blk.row_ptr[n] <= max_nnz_;

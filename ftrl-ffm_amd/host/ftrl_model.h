@@ -171,6 +171,12 @@ class FtrlModel {
   void enable_ablation(bool with_auc);
   void predict_ablated_block(const CsrBlock &blk, std::vector<double> &loss_sums);
   std::vector<ffm_metrics> read_ablation_metrics(bool reset);
+  // Pair ablation (include/ffm_engine.h "Pair ablation"): the same three for the V + 1 variants "without the
+  // interaction of fields f and g", V = ffm_engine_pair_count(n_fields); loss_sums[V + 1], variant V the rows
+  // themselves.  The scores stay on the device: only the loss sums come back.
+  void enable_pair_ablation(bool with_auc);
+  void predict_pair_ablated_block(const CsrBlock &blk, std::vector<double> &loss_sums);
+  std::vector<ffm_metrics> read_pair_ablation_metrics(bool reset);
 
   // Model files in the reference's formats (ffm.cpp:138-200, lr.cpp:26-39); available for every
   // model type here (the reference has none for FM).  save_state/load_state add the FTRL

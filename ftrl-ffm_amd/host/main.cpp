@@ -64,11 +64,13 @@ int main(int argc, char *argv[]) {
       // --auc_key_field on a run that trains nothing (--resume_from ck --n_epochs 0 --eval_data F): one evaluation pass
       // of the loaded model, numbered by the epochs it has behind it -- there is no epoch to print the line after
       // (--field_importance asks for the same one pass: its lines follow an evaluation)
-      if ((opt.auc_key_field >= 0 || opt.field_importance) && opt.epoch <= 0 && !opt.cmd && !opt.eval_path.empty())
+      if ((opt.auc_key_field >= 0 || opt.field_importance || opt.pair_importance) && opt.epoch <= 0 && !opt.cmd && !opt.eval_path.empty())
         task.evaluate(static_cast<int>(task.progress().epochs_done));
       task.model_ptr->print_norm_rows();  // (--normalize_rows: one line, after the last epoch or that one evaluation)
       // --field_importance: after the last evaluation, the same model without each field (field_importance.h)
       if (opt.field_importance && !opt.cmd) ftrl::FieldImportance(opt, &*task.model_ptr).run();
+      // --pair_importance: then the same model without each field pair (pair_importance.h)
+      if (opt.pair_importance && !opt.cmd) ftrl::run_pair_importance(opt, *task.model_ptr);
       // --refresh_weights: every epoch ended with a refresh and nothing has trained since, so the model, the
       // checkpoint and the scores below are those of refreshed weights; a run that trains nothing (--n_epochs 0
       // on a resumed model) refreshes what it loaded here

@@ -12,6 +12,7 @@
 #include <random>
 #include <thread>
 
+#include "pair_importance.h"
 #include "score_writer.h"
 
 namespace ftrl {
@@ -41,6 +42,29 @@ void refresh_and_print(FtrlModel &m, long long epoch) {
   std::printf("epoch %lld weights: linear %lld live, %lld nonzero, %lld moved; latent %lld live, %lld nonzero, %lld moved\n", epoch,
               static_cast<long long>(r.lin_live), static_cast<long long>(r.lin_nonzero), static_cast<long long>(r.lin_moved),
               static_cast<long long>(r.lat_live), static_cast<long long>(r.lat_nonzero), static_cast<long long>(r.lat_moved));
+}
+
+void run_pair_importance(const config_options &opt, FtrlModel &m) {
+  const bool want_auc = opt.metrics == "auc";
+  if (want_auc) {
+    print_pair_histogram_memory(stdout, opt.n_fields);
+    std::fflush(stdout);  // (the line is there when the allocation is refused)
+  }
+  m.enable_pair_ablation(want_auc);
+  CsrStream stream(opt.eval_path, opt.file_type, opt.thread_num);
+  const size_t batch = static_cast<size_t>(std::max(1, opt.batch_size));
+  std::vector<double> loss(static_cast<size_t>(pair_count(opt.n_fields)) + 1, 0.0);
+  CsrBlock blk;
+  unsigned long long rows = 0;
+  for (;;) {
+    const size_t got = stream.next(batch, blk);
+    if (got == 0) break;
+    m.predict_pair_ablated_block(blk, loss);
+    rows += got;
+  }
+  std::vector<ffm_metrics> auc;
+  if (want_auc) auc = m.read_pair_ablation_metrics(true);
+  print_pair_importance(stdout, opt.n_fields, rows, loss, want_auc ? &auc : nullptr);
 }
 
 void publish_and_print(FtrlModel &m, const std::string &prefix, const std::string &fmt, long long epoch, long long n_feats) {

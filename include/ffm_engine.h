@@ -1091,7 +1091,7 @@ int ffm_engine_score_candidates_device(ffm_engine *e, int32_t n_req, const int32
  * The calls feed neither FFM_METRIC_EVAL nor FFM_METRIC_TRAIN, and neither keyed capture.  An engine that
  * never enables ablation allocates nothing, launches nothing and changes in nothing; no existing kernel, launch
  * or argument list changed, FFM_ENGINE_ABI_VERSION and ffm_engine_config are what they were.
- * OUT OF SCOPE  a pipelined or staged form; groups and shards; ablation of field pairs. */
+ * OUT OF SCOPE  a pipelined or staged form; groups and shards.  (Field pairs: "Pair ablation" below.) */
 int ffm_engine_ablation_enable(ffm_engine *e, int32_t with_auc);
 int ffm_engine_predict_ablated(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
                                const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob,
@@ -1101,6 +1101,76 @@ int ffm_engine_predict_ablated_device(ffm_engine *e, int32_t n_rows, int32_t nnz
                                       const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
                                       int32_t output_prob, float *out, double *loss_sum_out);
 int ffm_engine_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out /* [n_fields + 1] */);
+
+/* ---- Pair ablation: the loss and AUC of the model without each field pair, in one pass ---------------
+ * Which interactions carry the model?  An FFM model is a set of field-pair interactions (39 fields: 741 cross
+ * pairs and 39 diagonal ones); a field can matter only through its linear term and two or three partners.  The
+ * answer by hand is one evaluation pass per pair, and no rewrite of the rows removes a pair.  Here the gathers
+ * and the k-long dots are made once per row, as for field ablation, and every pair's variant is one more ordered
+ * sum of the same terms.
+ * DEFINITION  F = n_fields <= 64.  The variants are the unordered field pairs with the diagonal, V = F (F + 1) / 2
+ *   (at most 2080), numbered for f <= g by
+ *     pair_index(f, g) = f * F - f * (f - 1) / 2 + (g - f);
+ *   variant V is the row itself.
+ *   variant (f, g)    of a row is the prediction's ordered sum -- bias, the survivors' linear products, then the
+ *                     pair terms in ffm_engine_predict_batch's pair order -- with every term whose two entries
+ *                     have the fields {f, g} left out (f == g: the terms between two entries of field f).  Linear
+ *                     terms are never left out.  Leaving a term out and adding -0.0f in its place are the same
+ *                     bits.  Every term belongs to exactly one variant.
+ *   variant V         is ffm_engine_predict_batch of the block, bit for bit.
+ *   a row without an entry of f, or of g (f == g: with fewer than two of f)  has variant (f, g) equal to variant V.
+ *   as weights        in a block where every feature id occurs under one field only, on a model whose bias is not
+ *                     -0.0f, variant (f, g) is ffm_engine_predict_batch of the block on the same model with the
+ *                     latent slot "towards field g" set to +0.0f for every id of field f: those terms become
+ *                     +-0.0f, and a running sum that starts at a bias other than -0.0f is never -0.0f, so adding
+ *                     them changes no bit (engine.py: drop_pair_weights; this is how the tests check it).
+ * ffm_engine_pair_count / _pair_index / _pair_fields  the numbering, on the host (no device, no engine):
+ *   pair_count(F) = V; pair_index takes f, g in either order; pair_fields is its inverse (*f <= *g).  n_fields
+ *   outside [1, 64], a field outside [0, n_fields) or v outside [0, V) sets the last error; the two counting calls
+ *   then return -1 and pair_fields FFM_E_INVALID.
+ * ffm_engine_pair_ablation_enable  allocates the (V + 1) x max_batch_rows score (fp32) and loss (fp64) scratch --
+ *   12 bytes per variant and row: 77 MB for 39 fields and 8192-row blocks -- and, with with_auc, V + 1 score
+ *   histograms of 16.8 MB each, zeroed: 13 GB at 39 fields, 35 GB at 64.  A later call allocates only what is
+ *   missing.  with_auc decides whether histograms are collected from then on: with_auc == 1 while they are
+ *   collected keeps their counts; with_auc == 0 on a later call stops the collection (the memory stays, and
+ *   ffm_engine_pair_ablation_read is FFM_E_INVALID again); a later with_auc == 1 starts from zero.  A failed
+ *   allocation is FFM_E_NOMEM and leaves the engine as it was, in state and in memory: everything the call has to
+ *   make is made before anything changes, and what it had made before the failure is given back (pair ablation
+ *   stays off, or on without histograms).  All of it is freed by ffm_engine_destroy.  Refused with FFM_E_UNSUPPORTED and a message that
+ *   says why: anything but a whole FFM model on one device (LR, FM, n_shards > 1, a group's engine, compact
+ *   storage); n_factors outside {4, 8, 16, 32, 64}; n_fields > 64.  Works on training engines and on
+ *   FFM_FLAG_SERVE_F32 / _F16 serving engines.
+ * ffm_engine_predict_pair_ablated  rows in host memory, synchronous, staged like ffm_engine_predict_ablated (the
+ *   same upload: val == NULL is 1.0f; hashed ids, the rare fold, buckets and FFM_FLAG_NORM_ROWS apply first;
+ *   field == NULL is FFM_E_INVALID; n_rows > max_batch_rows is refused as always).  out[(V + 1) * n_rows] is
+ *   variant-major (variant v of row r at v * n_rows + r; logits, or probabilities with output_prob) and may be
+ *   NULL: the scores then stay in HBM and only the loss sums come back.  loss_sum_out[V + 1], may be NULL, holds
+ *   per variant the double sum of the rows' logloss terms as ffm_engine_predict_batch sums them (0 without
+ *   labels).  Before ffm_engine_pair_ablation_enable: FFM_E_INVALID.
+ * ffm_engine_predict_pair_ablated_device  the same on arrays in device memory (values and fields required, ids
+ *   taken as they are; out and loss_sum_out device arrays or NULL); asynchronous on the engine's stream.
+ * rows too long  a row longer than max_row_nnz, or than the 128 entries a wave stages, is NaN in every variant
+ *   and reported as FFM_E_CAPACITY, exactly as for field ablation.
+ * ffm_engine_pair_ablation_read  out[V + 1]: per variant the ffm_metrics of its histogram, as
+ *   ffm_engine_ablation_read.  Without with_auc: FFM_E_INVALID.
+ * The calls feed neither FFM_METRIC_EVAL nor FFM_METRIC_TRAIN, neither keyed capture, and nothing of field
+ * ablation.  An engine that never enables pair ablation allocates nothing, launches nothing and changes in
+ * nothing; the section adds functions only: no struct, no existing kernel, launch or argument list changed, and
+ * FFM_ENGINE_ABI_VERSION is what it was.
+ * OUT OF SCOPE  pair masks or pruned tables on the prediction and serving kernels; pair variants of
+ *   ffm_engine_score_candidates; groups, shards, LR and FM; a pipelined or staged form. */
+int32_t ffm_engine_pair_count(int32_t n_fields);
+int32_t ffm_engine_pair_index(int32_t n_fields, int32_t f, int32_t g);
+int ffm_engine_pair_fields(int32_t n_fields, int32_t v, int32_t *f, int32_t *g);
+int ffm_engine_pair_ablation_enable(ffm_engine *e, int32_t with_auc);
+int ffm_engine_predict_pair_ablated(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
+                                    const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob,
+                                    float *out /* [(V + 1) * n_rows], variant-major, may be NULL */,
+                                    double *loss_sum_out /* [V + 1], may be NULL */);
+int ffm_engine_predict_pair_ablated_device(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
+                                           const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
+                                           int32_t output_prob, float *out, double *loss_sum_out);
+int ffm_engine_pair_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out /* [V + 1] */);
 
 /* ---- Serving deltas: sync a serving engine, publish only what moved --------------------------------------
  * ffm_engine_pack_weights takes all of a model: it streams every record of the training engine and writes the
