@@ -443,24 +443,16 @@ struct ffm_engine {
   float *d_ctx_val = nullptr;
   size_t cx_ent_cap = 0, cx_head_cap = 0, cx_terms_cap = 0, cx_cand_cap = 0;
   size_t ctx_ptr_cap = 0, req_ptr_cap = 0, ctx_field_cap = 0, ctx_feat_cap = 0, ctx_val_cap = 0;
-  // field ablation (include/ffm_engine.h "Field ablation", engine_ablate.h), all made by ffm_engine_ablation_enable:
-  // out [(n_fields + 1)][max_rows] scores and loss the same shape (the kernel's variant-major outputs), sums
-  // [n_fields + 1], part [n_fields + 1][kLossParts + 1] the loss sums' partial sums and tickets, hist
-  // [n_fields + 1][2 * kMetricBins + 1] with with_auc
-  struct {
+  // field and pair ablation (include/ffm_engine.h "Field ablation", "Pair ablation"; engine_ablate.h), each set all
+  // made by its enable call for its V variants -- n_fields + 1, or n_fields (n_fields + 1) / 2 + 1 --: out [V][max_rows]
+  // scores and loss the same shape (the kernel's variant-major outputs), sums [V], part [V][kLossParts + 1] the loss
+  // sums' partial sums and tickets, hist [V][2 * kMetricBins + 1] with with_auc
+  struct AblateSet {
     bool on = false, auc = false;
     float *out = nullptr;
     double *loss = nullptr, *sums = nullptr, *part = nullptr;
     unsigned long long *hist = nullptr;
-  } abl;
-  // pair ablation (include/ffm_engine.h "Pair ablation", engine_ablate_pairs.h), all made by
-  // ffm_engine_pair_ablation_enable: the same five arrays for V + 1 = n_fields (n_fields + 1) / 2 + 1 variants
-  struct {
-    bool on = false, auc = false;
-    float *out = nullptr;
-    double *loss = nullptr, *sums = nullptr, *part = nullptr;
-    unsigned long long *hist = nullptr;
-  } pabl;
+  } abl, pabl;
   std::vector<void *> allocs;
   // split-phase bookkeeping
   Rows pending{};
@@ -606,13 +598,18 @@ struct ffm_engine {
     if (*p && *cap >= need) return FFM_OK;
     T *q = nullptr;
     if (int rc = alloc(&q, need)) return rc;
-    if (*p) {
-      allocs.erase(std::find(allocs.begin(), allocs.end(), static_cast<void *>(*p)));
-      (void)hipFree(*p);
-    }
+    release(p);
     *p = q;
     *cap = need;
     return FFM_OK;
+  }
+  // An array alloc made, given back; *p is null afterwards.
+  template <typename T>
+  void release(T **p) {
+    if (!*p) return;
+    allocs.erase(std::find(allocs.begin(), allocs.end(), static_cast<void *>(*p)));
+    (void)hipFree(*p);
+    *p = nullptr;
   }
 
   hipEvent_t get_event() {
@@ -871,7 +868,6 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_text.h"
 #include "engine_rows.h"
 #include "engine_ablate.h"
-#include "engine_ablate_pairs.h"
 }  // extern "C"
 
 #include "engine_group.h"

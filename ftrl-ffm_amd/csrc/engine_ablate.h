@@ -1,65 +1,141 @@
-// engine_ablate.h -- field ablation (include/ffm_engine.h "Field ablation"): ffm_engine_ablation_enable makes
-// the variant-major scratch, ffm_engine_predict_ablated[_device] run ffm_ablate_wave_kernel (kernels_ablate.h)
-// and, per variant, the loss sum and the score histogram; ffm_engine_ablation_read reduces the histograms on the
-// host as ffm_engine_metrics_read does.  Nothing here feeds the metric channels or the keyed capture, and an
-// engine that never calls ffm_engine_ablation_enable allocates and launches nothing of it.
-// (The kernel's dynamic LDS is pred_lds_bytes(kPredLdsCap) = 12 KB at the most, like the other wave kernels':
+// engine_ablate.h -- field and pair ablation (include/ffm_engine.h "Field ablation", "Pair ablation"): enable makes a
+// kind's variant-major scratch (ffm_engine::abl, ::pabl), predict runs its wave kernel -- ffm_ablate_wave_kernel
+// (kernels_ablate.h) or ffm_ablate_pairs_kernel (kernels_ablate_pairs.h) -- and, per variant, the loss sum and the
+// score histogram (kernels_ablate.h, gridDim.y = the variants); read reduces the histograms on the host as
+// ffm_engine_metrics_read does.  The two kinds differ in what an AblateKind says and in nothing else; the pairs'
+// numbering (host arithmetic, no device) is here too.  Nothing here feeds the metric channels, the keyed capture or
+// the other kind's state, and an engine that never calls an enable allocates and launches nothing of it.
+// (A kernel's dynamic LDS is pred_lds_bytes(kPredLdsCap) = 12 KB at the most, like the other wave kernels':
 // within the default limit, so opt_in_lds has nothing to ask for.)
 // Part of engine.hip's translation unit (included inside its extern "C" block).
 
-static int ablate_variants(const ffm_engine *e) { return e->m.n_fields + 1; }
+// ---- the pairs' numbering ---------------------------------------------------------------------------------
+int32_t ffm_engine_pair_count(int32_t n_fields) {
+  if (n_fields < 1 || n_fields > kPairFields) {
+    fail(FFM_E_INVALID, "pair ablation numbers the pairs of 1 .. 64 fields, got n_fields = " + std::to_string(n_fields));
+    return -1;
+  }
+  return pair_variants(n_fields);
+}
 
-int ffm_engine_ablation_enable(ffm_engine *e, int32_t with_auc) {
+int32_t ffm_engine_pair_index(int32_t n_fields, int32_t f, int32_t g) {
+  if (ffm_engine_pair_count(n_fields) < 0) return -1;
+  if (f < 0 || g < 0 || f >= n_fields || g >= n_fields) {
+    fail(FFM_E_INVALID, "pair (" + std::to_string(f) + ", " + std::to_string(g) + ") names a field outside [0, n_fields)");
+    return -1;
+  }
+  return pair_base(n_fields, std::min(f, g)) + std::max(f, g);
+}
+
+int ffm_engine_pair_fields(int32_t n_fields, int32_t v, int32_t *f, int32_t *g) {
+  const int V = ffm_engine_pair_count(n_fields);
+  if (V < 0) return FFM_E_INVALID;
+  if (!f || !g) return fail(FFM_E_INVALID, "null output");
+  if (v < 0 || v >= V)
+    return fail(FFM_E_INVALID, "variant " + std::to_string(v) + " is no pair: the pairs of " + std::to_string(n_fields) +
+                                   " fields are 0 .. " + std::to_string(V - 1) + " (variant " + std::to_string(V) + " is the row itself)");
+  int lo = 0;  // the last f whose first pair (f, f) is at or before v
+  while (lo + 1 < n_fields && pair_base(n_fields, lo + 1) + lo + 1 <= v) lo++;
+  *f = lo;
+  *g = v - pair_base(n_fields, lo);
+  return FFM_OK;
+}
+
+// ---- what a kind is ---------------------------------------------------------------------------------------
+struct AblateKind {
+  ffm_engine::AblateSet ffm_engine::*set;
+  int (*variants)(int n_fields);  // the row itself included
+  AblateWaveFn (*kernel)(const ModelDev &m);
+  const char *noun, *prefix;  // "field ablation"; the entry points are ffm_engine_<prefix>_enable, _read
+  const char *why_64;         // the reason behind "at most 64 fields"
+  const char *fail_env;       // the failure hook of the histograms' allocation (ablate_enable)
+};
+static int field_variants(int n_fields) { return n_fields + 1; }
+static int pair_variants_all(int n_fields) { return pair_variants(n_fields) + 1; }
+static AblateWaveFn field_kernel(const ModelDev &m) { return ablate_wave_fn(m.lat_fmt, m.n_factors); }
+static AblateWaveFn pair_kernel(const ModelDev &m) { return ablate_pairs_fn(m.lat_fmt, m.n_factors, ablate_pairs_rounds(m.n_fields)); }
+static const AblateKind kFieldAblation = {&ffm_engine::abl, field_variants, field_kernel, "field ablation", "ablation",
+                                          "a row is one wave and a variant one lane of it", "FFM_FIELD_HIST_FAIL"};
+static const AblateKind kPairAblation = {&ffm_engine::pabl, pair_variants_all, pair_kernel, "pair ablation", "pair_ablation",
+                                         "a row is one wave and its 2080 pairs are 33 registers of every lane", "FFM_PAIR_HIST_FAIL"};
+
+static int ablate_enable(const AblateKind &k, ffm_engine *e, int32_t with_auc) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
   const ModelDev &m = e->m;
-  if (m.type != FFM_MODEL_FFM) return fail(FFM_E_UNSUPPORTED, "field ablation is FFM only: LR and FM rows have no fields");
+  const std::string noun = k.noun;
+  if (m.type != FFM_MODEL_FFM) return fail(FFM_E_UNSUPPORTED, noun + " is FFM only: LR and FM rows have no fields");
   if (m.n_shards > 1 || e->in_group)
-    return fail(FFM_E_UNSUPPORTED, "field ablation needs a whole model on one device (n_shards == 1, not a group's engine)");
+    return fail(FFM_E_UNSUPPORTED, noun + " needs a whole model on one device (n_shards == 1, not a group's engine)");
   if (m.field_start || m.own_n || m.lin_own)
-    return fail(FFM_E_UNSUPPORTED, "field ablation needs full-length records (not a shard's compact storage)");
-  if (!ablate_wave_fn(m.lat_fmt, m.n_factors))
-    return fail(FFM_E_UNSUPPORTED, "field ablation supports n_factors 4, 8, 16, 32 or 64 (the wave kernels' lane shapes)");
-  if (m.n_fields > 64)
-    return fail(FFM_E_UNSUPPORTED, "field ablation supports at most 64 fields: a row is one wave and a variant one lane of it");
+    return fail(FFM_E_UNSUPPORTED, noun + " needs full-length records (not a shard's compact storage)");
+  if (m.n_fields > kPairFields) return fail(FFM_E_UNSUPPORTED, noun + " supports at most 64 fields: " + k.why_64);
+  if (!k.kernel(m))
+    return fail(FFM_E_UNSUPPORTED, noun + " supports n_factors 4, 8, 16, 32 or 64 (the wave kernels' lane shapes)");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   if (int rc_e = eval_launch_pending(e)) return rc_e;
-  const size_t V = static_cast<size_t>(ablate_variants(e)), R = static_cast<size_t>(std::max(1, e->max_rows));
-  int rc;
-  if (!e->abl.out) {
-    if ((rc = e->alloc(&e->abl.out, V * R)) || (rc = e->alloc(&e->abl.loss, V * R)) || (rc = e->alloc(&e->abl.sums, V)) ||
-        (rc = e->alloc(&e->abl.part, V * (kLossParts + 1))))
-      return rc;
-    HIP_TRY(hipMemsetAsync(e->abl.part, 0, sizeof(double) * V * (kLossParts + 1), e->stream));
+  ffm_engine::AblateSet &s = e->*k.set;
+  const size_t V = static_cast<size_t>(k.variants(m.n_fields)), R = static_cast<size_t>(std::max(1, e->max_rows));
+  // Everything this call has to make is made before anything of the engine changes: a failed allocation gives
+  // back what the call made so far and leaves the engine -- its state and its memory -- as it was.
+  const bool make_scratch = !s.out, make_hist = with_auc && !s.hist;
+  ffm_engine::AblateSet made;
+  int rc = FFM_OK;
+  if (make_scratch && !(rc = e->alloc(&made.out, V * R)) && !(rc = e->alloc(&made.loss, V * R)) && !(rc = e->alloc(&made.sums, V)))
+    rc = e->alloc(&made.part, V * (kLossParts + 1));
+  if (!rc && make_hist) {
+    // The one allocation here that can be tens of gigabytes.  FFM_FIELD_HIST_FAIL=1 / FFM_PAIR_HIST_FAIL=1 (read at
+    // each call; a test hook, like FFM_TEXT_SLOT_BYTES) makes it fail as an exhausted device does, so that what this
+    // function does then can be pinned without filling a device's memory.
+    const char *sv = std::getenv(k.fail_env);
+    if (sv && sv[0] == '1')
+      rc = fail(FFM_E_NOMEM, "hipMalloc of " + std::to_string(V * kMetricWords * sizeof(unsigned long long)) + " bytes failed: " + k.fail_env + " is set");
+    else
+      rc = e->alloc(&made.hist, V * kMetricWords);
   }
-  if (with_auc && !e->abl.auc) {  // (a channel that turns on starts from zero, one that stays on keeps its counts)
-    if (!e->abl.hist && (rc = e->alloc(&e->abl.hist, V * kMetricWords))) return rc;
-    HIP_TRY(hipMemsetAsync(e->abl.hist, 0, sizeof(unsigned long long) * V * kMetricWords, e->stream));
+  if (rc) {
+    e->release(&made.out);
+    e->release(&made.loss);
+    e->release(&made.sums);
+    e->release(&made.part);
+    e->release(&made.hist);
+    return rc;
   }
-  e->abl.auc = with_auc != 0;
-  e->abl.on = true;
+  if (make_scratch) {
+    s.out = made.out;
+    s.loss = made.loss;
+    s.sums = made.sums;
+    s.part = made.part;
+    HIP_TRY(hipMemsetAsync(s.part, 0, sizeof(double) * V * (kLossParts + 1), e->stream));
+  }
+  if (make_hist) s.hist = made.hist;
+  if (with_auc && !s.auc)  // (collection that turns on starts from zero, collection that stays on keeps its counts)
+    HIP_TRY(hipMemsetAsync(s.hist, 0, sizeof(unsigned long long) * V * kMetricWords, e->stream));
+  s.auc = with_auc != 0;
+  s.on = true;
   return FFM_OK;
 }
 
 // The launches, on a block in device memory; row_cap as launch_row_kernel takes it.  out / loss_sum_out: device
 // arrays of the variants' scores and loss sums, or null (the scores then stay in the engine's scratch).
-static int ablate_core(ffm_engine *e, const Rows &rows, int row_cap, int32_t output_prob, float *out, double *loss_sum_out) {
+static int ablate_core(const AblateKind &k, ffm_engine *e, const Rows &rows, int row_cap, int32_t output_prob, float *out,
+                       double *loss_sum_out) {
   const ModelDev &m = e->m;
-  const int V = ablate_variants(e), n_rows = rows.n_rows;
-  float *const score = out ? out : e->abl.out;
+  const ffm_engine::AblateSet &s = e->*k.set;
+  const int V = k.variants(m.n_fields), n_rows = rows.n_rows;
+  float *const score = out ? out : s.out;
   if (n_rows > 0) {
     if (row_cap <= 0) row_cap = e->max_row_nnz;
     const int lds_cap = std::min(row_cap, kPredLdsCap);
-    hipLaunchKernelGGL(ablate_wave_fn(m.lat_fmt, m.n_factors), dim3(cdiv(n_rows, kPredRows)), dim3(64 * kPredRows),
-                       pred_lds_bytes(lds_cap), e->stream, m, rows, e->d_err, row_cap, lds_cap, score, e->abl.loss, e->max_rows,
-                       output_prob);
-    if (rows.label && e->abl.auc)
+    hipLaunchKernelGGL(k.kernel(m), dim3(cdiv(n_rows, kPredRows)), dim3(64 * kPredRows), pred_lds_bytes(lds_cap), e->stream, m,
+                       rows, e->d_err, row_cap, lds_cap, score, s.loss, e->max_rows, output_prob);
+    if (rows.label && s.auc)
       hipLaunchKernelGGL(ablate_hist_kernel, dim3(cdiv(n_rows, kMetricThreads), V), dim3(kMetricThreads), 0, e->stream, n_rows,
-                         score, output_prob, rows.label, e->abl.hist);
+                         score, output_prob, rows.label, s.hist);
   }
   if (loss_sum_out) {
     if (rows.label && n_rows > 0)
-      hipLaunchKernelGGL(ablate_loss_sum_kernel, dim3(loss_grid(n_rows), V), dim3(256), 0, e->stream, n_rows, e->abl.loss,
-                         e->max_rows, loss_sum_out, e->abl.part);
+      hipLaunchKernelGGL(ablate_loss_sum_kernel, dim3(loss_grid(n_rows), V), dim3(256), 0, e->stream, n_rows, s.loss, e->max_rows,
+                         loss_sum_out, s.part);
     else
       HIP_TRY(hipMemsetAsync(loss_sum_out, 0, sizeof(double) * V, e->stream));
   }
@@ -67,55 +143,56 @@ static int ablate_core(ffm_engine *e, const Rows &rows, int row_cap, int32_t out
   return FFM_OK;
 }
 
-static int ablate_ready(ffm_engine *e) {
+static int ablate_ready(const AblateKind &k, ffm_engine *e) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
-  if (!e->abl.on) return fail(FFM_E_INVALID, "field ablation is off (ffm_engine_ablation_enable)");
+  if (!(e->*k.set).on) return fail(FFM_E_INVALID, std::string(k.noun) + " is off (ffm_engine_" + k.prefix + "_enable)");
   return FFM_OK;
 }
 
-int ffm_engine_predict_ablated_device(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr, const int32_t *field,
-                                      const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob,
-                                      float *out, double *loss_sum_out) {
-  int rc = ablate_ready(e);
+static int ablate_predict_device(const AblateKind &k, ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
+                                 const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
+                                 int32_t output_prob, float *out, double *loss_sum_out) {
+  int rc = ablate_ready(k, e);
   if (rc) return rc;
   if ((rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val))) return rc;
   HIP_TRY(hipSetDevice(e->cfg.device_id));
-  return ablate_core(e, Rows{n_rows, nnz, row_ptr, field, feat, val, label}, 0, output_prob, out, loss_sum_out);
+  return ablate_core(k, e, Rows{n_rows, nnz, row_ptr, field, feat, val, label}, 0, output_prob, out, loss_sum_out);
 }
 
-int ffm_engine_predict_ablated(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
-                               const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob, float *out,
-                               double *loss_sum_out) {
-  int rc = ablate_ready(e);
+static int ablate_predict(const AblateKind &k, ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
+                          const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob, float *out,
+                          double *loss_sum_out) {
+  int rc = ablate_ready(k, e);
   if (rc) return rc;
   Rows dev{};
   int row_cap = 0;
   if ((rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &dev, &row_cap))) return rc;
-  const int V = ablate_variants(e);
-  if ((rc = ablate_core(e, dev, row_cap, output_prob, nullptr, label ? e->abl.sums : nullptr))) return rc;
-  if (out && n_rows > 0)
-    HIP_TRY(hipMemcpyAsync(out, e->abl.out, sizeof(float) * V * n_rows, hipMemcpyDeviceToHost, e->stream));
+  const ffm_engine::AblateSet &s = e->*k.set;
+  const size_t V = static_cast<size_t>(k.variants(e->m.n_fields));
+  if ((rc = ablate_core(k, e, dev, row_cap, output_prob, nullptr, label ? s.sums : nullptr))) return rc;
+  if (out && n_rows > 0) HIP_TRY(hipMemcpyAsync(out, s.out, sizeof(float) * V * n_rows, hipMemcpyDeviceToHost, e->stream));
   if (loss_sum_out) {
-    if (label && n_rows > 0) HIP_TRY(hipMemcpyAsync(loss_sum_out, e->abl.sums, sizeof(double) * V, hipMemcpyDeviceToHost, e->stream));
+    if (label && n_rows > 0) HIP_TRY(hipMemcpyAsync(loss_sum_out, s.sums, sizeof(double) * V, hipMemcpyDeviceToHost, e->stream));
     else std::fill(loss_sum_out, loss_sum_out + V, 0.0);
   }
   return check_device_errors(e);
 }
 
-int ffm_engine_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out) {
-  int rc = ablate_ready(e);
+static int ablate_read(const AblateKind &k, ffm_engine *e, int32_t reset, ffm_metrics *out) {
+  int rc = ablate_ready(k, e);
   if (rc) return rc;
   if (!out) return fail(FFM_E_INVALID, "null output");
-  if (!e->abl.auc) return fail(FFM_E_INVALID, "field ablation was enabled without histograms (with_auc == 0)");
+  const ffm_engine::AblateSet &s = e->*k.set;
+  if (!s.auc) return fail(FFM_E_INVALID, std::string(k.noun) + " was enabled without histograms (with_auc == 0)");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   if (int rc_e = eval_launch_pending(e)) return rc_e;
-  const int V = ablate_variants(e);
+  const int V = k.variants(e->m.n_fields);
   const size_t bytes = kMetricWords * sizeof(unsigned long long);
   std::vector<unsigned long long> h;
   try { h.assign(kMetricWords, 0ull); } catch (const std::bad_alloc &) { return fail(FFM_E_NOMEM, "host allocation failed"); }
   static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are 64-bit");
-  for (int v = 0; v < V; v++) {  // (one histogram at a time: 16 MiB of host memory, not 16 MiB per field)
-    unsigned long long *const hist = e->abl.hist + static_cast<size_t>(v) * kMetricWords;
+  for (int v = 0; v < V; v++) {  // (one histogram at a time: 16 MiB of host memory, not 16 MiB per variant)
+    unsigned long long *const hist = s.hist + static_cast<size_t>(v) * kMetricWords;
     HIP_TRY(hipMemcpyAsync(h.data(), hist, bytes, hipMemcpyDeviceToHost, e->stream));
     if (reset) HIP_TRY(hipMemsetAsync(hist, 0, bytes, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -125,4 +202,30 @@ int ffm_engine_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out) {
       return rc;
   }
   return FFM_OK;
+}
+
+// ---- the exports ------------------------------------------------------------------------------------------
+int ffm_engine_ablation_enable(ffm_engine *e, int32_t with_auc) { return ablate_enable(kFieldAblation, e, with_auc); }
+int ffm_engine_pair_ablation_enable(ffm_engine *e, int32_t with_auc) { return ablate_enable(kPairAblation, e, with_auc); }
+int ffm_engine_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out) { return ablate_read(kFieldAblation, e, reset, out); }
+int ffm_engine_pair_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out) { return ablate_read(kPairAblation, e, reset, out); }
+int ffm_engine_predict_ablated_device(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr, const int32_t *field,
+                                      const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob,
+                                      float *out, double *loss_sum_out) {
+  return ablate_predict_device(kFieldAblation, e, n_rows, nnz, row_ptr, field, feat, val, label, output_prob, out, loss_sum_out);
+}
+int ffm_engine_predict_pair_ablated_device(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
+                                           const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
+                                           int32_t output_prob, float *out, double *loss_sum_out) {
+  return ablate_predict_device(kPairAblation, e, n_rows, nnz, row_ptr, field, feat, val, label, output_prob, out, loss_sum_out);
+}
+int ffm_engine_predict_ablated(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
+                               const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob, float *out,
+                               double *loss_sum_out) {
+  return ablate_predict(kFieldAblation, e, n_rows, row_ptr, field, feat, val, label, output_prob, out, loss_sum_out);
+}
+int ffm_engine_predict_pair_ablated(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
+                                    const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob,
+                                    float *out, double *loss_sum_out) {
+  return ablate_predict(kPairAblation, e, n_rows, row_ptr, field, feat, val, label, output_prob, out, loss_sum_out);
 }

@@ -363,13 +363,13 @@ static int alloc_shared(ffm_engine *e, Scratch *shared) {
   return e->alloc(&e->d_stage, static_cast<size_t>(e->stage_floats));
 }
 
-// (Not made here, and no scratch set's: the variant-major arrays of field ablation, ffm_engine::abl, and of pair
-// ablation, ffm_engine::pabl -- scores, losses, loss sums with their partial sums and, on request, histograms for
-// n_fields + 1 and n_fields (n_fields + 1) / 2 + 1 variants.  Each set is the engine's own, one per engine whatever
-// kSets is: its calls are synchronous or ordered on the main stream, so no two blocks use it at once.  It is made
-// by ffm_engine_ablation_enable / ffm_engine_pair_ablation_enable (engine_ablate.h, engine_ablate_pairs.h) through
-// ffm_engine::alloc, so ffm_engine_destroy frees it with everything else; an engine that never enables either
-// holds none of it.)
+// (Not made here, and no scratch set's: the two ffm_engine::AblateSet, abl of field ablation and pabl of pair
+// ablation -- scores, losses, loss sums with their partial sums and, on request, histograms for n_fields + 1 and
+// n_fields (n_fields + 1) / 2 + 1 variants.  Each set is the engine's own, one per engine whatever kSets is: its
+// calls are synchronous or ordered on the main stream, so no two blocks use it at once.  It is made by
+// ffm_engine_ablation_enable / ffm_engine_pair_ablation_enable (engine_ablate.h: all of a call's arrays or none)
+// through ffm_engine::alloc, so ffm_engine_destroy frees it with everything else; an engine that never enables
+// either holds none of it.)
 //
 // Scratch set si: the one place that names a per-set array and its size.  The set starts as a copy of
 // `shared` (alloc_shared), so a Scratch member that is named neither here nor there is null in every set.

@@ -518,31 +518,20 @@ void config_options::parse_option(int argc, char *argv[]) {
       throw std::invalid_argument(what + "is not a field of this model: --n_fields is " + std::to_string(n_fields));
     if (auc_key_rows <= 0) throw std::invalid_argument("--auc_key_rows must be positive, got " + std::to_string(auc_key_rows));
   }
-  if (field_importance) {
-    // one more pass over the eval file through one whole FFM model's wave kernel (refused here, before a device is opened)
-    const std::string what = "--field_importance true ";
-    if (eval_path.empty()) throw std::invalid_argument(what + "ablates the fields on the evaluation file: it needs --eval_data");
-    if (model_type != "FFM") throw std::invalid_argument(what + "drops fields, which only FFM rows have (got --model_type " + model_type + ")");
+  // --field_importance, --pair_importance: one more pass over the eval file through one whole FFM model's wave kernel,
+  // with a variant per `things` (refused here, before a device is opened)
+  auto check_importance = [&](const std::string &what, const std::string &things, const std::string &keeps) {
+    if (eval_path.empty()) throw std::invalid_argument(what + "ablates the " + things + " on the evaluation file: it needs --eval_data");
+    if (model_type != "FFM") throw std::invalid_argument(what + "drops " + things + ", which only FFM rows have (got --model_type " + model_type + ")");
     if (n_gpus > 1) throw std::invalid_argument(what + "runs on one whole model on one GPU: --n_gpus > 1 is not allowed with it");
-    if (n_fields > 64)
-      throw std::invalid_argument(what + "keeps one lane of a 64-lane wave per field: --n_fields is " + std::to_string(n_fields) + ", at most 64");
+    if (n_fields > 64) throw std::invalid_argument(what + keeps + ": --n_fields is " + std::to_string(n_fields) + ", at most 64");
     if (n_factors != 4 && n_factors != 8 && n_factors != 16 && n_factors != 32 && n_factors != 64)
       throw std::invalid_argument(what + "runs the one-wave-per-row kernel: --n_factors must be 4, 8, 16, 32 or 64 (got " +
                                   std::to_string(n_factors) + ")");
-  }
-  if (pair_importance) {
-    // the same pass with a variant per field pair (refused here, before a device is opened)
-    const std::string what = "--pair_importance true ";
-    if (eval_path.empty()) throw std::invalid_argument(what + "ablates the field pairs on the evaluation file: it needs --eval_data");
-    if (model_type != "FFM") throw std::invalid_argument(what + "drops field pairs, which only FFM rows have (got --model_type " + model_type + ")");
-    if (n_gpus > 1) throw std::invalid_argument(what + "runs on one whole model on one GPU: --n_gpus > 1 is not allowed with it");
-    if (n_fields > 64)
-      throw std::invalid_argument(what + "keeps the pairs of at most 64 fields in the registers of a 64-lane wave: --n_fields is " +
-                                  std::to_string(n_fields) + ", at most 64");
-    if (n_factors != 4 && n_factors != 8 && n_factors != 16 && n_factors != 32 && n_factors != 64)
-      throw std::invalid_argument(what + "runs the one-wave-per-row kernel: --n_factors must be 4, 8, 16, 32 or 64 (got " +
-                                  std::to_string(n_factors) + ")");
-  }
+  };
+  if (field_importance) check_importance("--field_importance true ", "fields", "keeps one lane of a 64-lane wave per field");
+  if (pair_importance)
+    check_importance("--pair_importance true ", "field pairs", "keeps the pairs of at most 64 fields in the registers of a 64-lane wave");
   // (--n_epochs 0 with a file to score needs no training file: the format is then the scored file's)
   file_type = detect_file_type(train_path.empty() && epoch == 0 && !predict_path.empty() ? predict_path : train_path);
   if (model_type == "FFM" && file_type != "libffm") {

@@ -65,10 +65,10 @@ struct config_options {
   int auc_key_field = -1;
   long long auc_key_rows = 16777216;
   // --field_importance true: after the last evaluation, the eval loss (and, with --metrics auc, the AUC) of the model
-  // without each field, from one more pass over --eval_data (include/ffm_engine.h "Field ablation", field_importance.h)
+  // without each field, from one more pass over --eval_data (include/ffm_engine.h "Field ablation", importance.h)
   bool field_importance = false;
   // --pair_importance true: the same for every field pair -- the model without the interaction of fields f and g,
-  // all n_fields (n_fields + 1) / 2 of them from one more pass (include/ffm_engine.h "Pair ablation", pair_importance.h)
+  // all n_fields (n_fields + 1) / 2 of them from one more pass (include/ffm_engine.h "Pair ablation", importance.h)
   bool pair_importance = false;
   // --publish_path PREFIX [--publish_weights f32|f16]: after every epoch's training (and refresh) a serving delta
   // PREFIX.<epochs_done>.delta -- what a shadow serving engine had to move to follow the model (serve_delta.h)

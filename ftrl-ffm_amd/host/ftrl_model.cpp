@@ -421,57 +421,42 @@ ffm_refresh_stats FtrlModel::refresh_weights() {
   return st;
 }
 
-void FtrlModel::enable_ablation(bool with_auc) {
-  if (grp_) throw std::invalid_argument("field ablation: one GPU only");
-  check(ffm_engine_ablation_enable(eng_, with_auc ? 1 : 0), "ffm_engine_ablation_enable");
+// What differs between the two kinds of ablation: the noun of the messages and the engine's entry points.
+static std::string ablation_noun(FtrlModel::Ablation kind) { return kind == FtrlModel::Ablation::Pairs ? "pair ablation" : "field ablation"; }
+
+size_t FtrlModel::ablation_variants(Ablation kind) const {
+  if (kind == Ablation::Fields) return static_cast<size_t>(n_fields) + 1;
+  const int32_t pairs = ffm_engine_pair_count(n_fields);
+  if (pairs < 0) throw std::invalid_argument("pair ablation: at most 64 fields");
+  return static_cast<size_t>(pairs) + 1;
 }
 
-void FtrlModel::predict_ablated_block(const CsrBlock &blk, std::vector<double> &loss_sums) {
-  if (grp_) throw std::invalid_argument("field ablation: one GPU only");
-  const size_t variants = static_cast<size_t>(n_fields) + 1;
-  if (loss_sums.size() != variants) throw std::invalid_argument("field ablation: loss_sums needs n_fields + 1 entries");
+void FtrlModel::enable_ablation(Ablation kind, bool with_auc) {
+  if (grp_) throw std::invalid_argument(ablation_noun(kind) + ": one GPU only");
+  if (kind == Ablation::Pairs) check(ffm_engine_pair_ablation_enable(eng_, with_auc ? 1 : 0), "ffm_engine_pair_ablation_enable");
+  else check(ffm_engine_ablation_enable(eng_, with_auc ? 1 : 0), "ffm_engine_ablation_enable");
+}
+
+void FtrlModel::predict_ablated_block(Ablation kind, const CsrBlock &blk, std::vector<double> &loss_sums) {
+  if (grp_) throw std::invalid_argument(ablation_noun(kind) + ": one GPU only");
+  const bool pairs = kind == Ablation::Pairs;
+  const size_t variants = ablation_variants(kind);
+  if (loss_sums.size() != variants)
+    throw std::invalid_argument(ablation_noun(kind) + ": loss_sums needs " + (pairs ? "n_fields (n_fields + 1) / 2 + 1" : "n_fields + 1") + " entries");
   std::vector<double> part(variants);
   for_each_fitting(blk, [&](const CsrBlock &b, int) {
-    check(ffm_engine_predict_ablated(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(), b.val.data(),
-                                     b.label.data(), 0, nullptr, part.data()),
-          "ffm_engine_predict_ablated");
+    check((pairs ? ffm_engine_predict_pair_ablated : ffm_engine_predict_ablated)(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(),
+                                                                                 b.val.data(), b.label.data(), 0, nullptr, part.data()),
+          pairs ? "ffm_engine_predict_pair_ablated" : "ffm_engine_predict_ablated");
     for (size_t v = 0; v < variants; v++) loss_sums[v] += part[v];
   });
 }
 
-std::vector<ffm_metrics> FtrlModel::read_ablation_metrics(bool reset) {
-  if (grp_) throw std::invalid_argument("field ablation: one GPU only");
-  std::vector<ffm_metrics> m(static_cast<size_t>(n_fields) + 1);
-  check(ffm_engine_ablation_read(eng_, reset ? 1 : 0, m.data()), "ffm_engine_ablation_read");
-  return m;
-}
-
-void FtrlModel::enable_pair_ablation(bool with_auc) {
-  if (grp_) throw std::invalid_argument("pair ablation: one GPU only");
-  check(ffm_engine_pair_ablation_enable(eng_, with_auc ? 1 : 0), "ffm_engine_pair_ablation_enable");
-}
-
-void FtrlModel::predict_pair_ablated_block(const CsrBlock &blk, std::vector<double> &loss_sums) {
-  if (grp_) throw std::invalid_argument("pair ablation: one GPU only");
-  const int32_t pairs = ffm_engine_pair_count(n_fields);
-  if (pairs < 0) throw std::invalid_argument("pair ablation: at most 64 fields");
-  const size_t variants = static_cast<size_t>(pairs) + 1;
-  if (loss_sums.size() != variants) throw std::invalid_argument("pair ablation: loss_sums needs n_fields (n_fields + 1) / 2 + 1 entries");
-  std::vector<double> part(variants);
-  for_each_fitting(blk, [&](const CsrBlock &b, int) {
-    check(ffm_engine_predict_pair_ablated(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(), b.val.data(),
-                                          b.label.data(), 0, nullptr, part.data()),
-          "ffm_engine_predict_pair_ablated");
-    for (size_t v = 0; v < variants; v++) loss_sums[v] += part[v];
-  });
-}
-
-std::vector<ffm_metrics> FtrlModel::read_pair_ablation_metrics(bool reset) {
-  if (grp_) throw std::invalid_argument("pair ablation: one GPU only");
-  const int32_t pairs = ffm_engine_pair_count(n_fields);
-  if (pairs < 0) throw std::invalid_argument("pair ablation: at most 64 fields");
-  std::vector<ffm_metrics> m(static_cast<size_t>(pairs) + 1);
-  check(ffm_engine_pair_ablation_read(eng_, reset ? 1 : 0, m.data()), "ffm_engine_pair_ablation_read");
+std::vector<ffm_metrics> FtrlModel::read_ablation_metrics(Ablation kind, bool reset) {
+  if (grp_) throw std::invalid_argument(ablation_noun(kind) + ": one GPU only");
+  std::vector<ffm_metrics> m(ablation_variants(kind));
+  if (kind == Ablation::Pairs) check(ffm_engine_pair_ablation_read(eng_, reset ? 1 : 0, m.data()), "ffm_engine_pair_ablation_read");
+  else check(ffm_engine_ablation_read(eng_, reset ? 1 : 0, m.data()), "ffm_engine_ablation_read");
   return m;
 }
 

@@ -163,20 +163,18 @@ class FtrlModel {
   // not trained yet are trained first (their losses stay in train_flush()'s sum).  The host mirrors
   // (bias, lin_w, vec_w) are pulled again / dropped, as after load_checkpoint.  Returns the six counts.
   ffm_refresh_stats refresh_weights();
-  // Field ablation (include/ffm_engine.h "Field ablation"): the loss -- and, with_auc, the AUC -- of this model
-  // without each field, all n_fields + 1 variants from one pass.  enable_ablation allocates the engine's scratch
-  // (one FFM engine only: throws otherwise); predict_ablated_block runs one block through the synchronous call
-  // and ADDS its per-variant loss sums to loss_sums[n_fields + 1] (variant n_fields: the rows themselves);
-  // read_ablation_metrics returns the n_fields + 1 variants' numbers so far and, with reset, starts them from zero.
-  void enable_ablation(bool with_auc);
-  void predict_ablated_block(const CsrBlock &blk, std::vector<double> &loss_sums);
-  std::vector<ffm_metrics> read_ablation_metrics(bool reset);
-  // Pair ablation (include/ffm_engine.h "Pair ablation"): the same three for the V + 1 variants "without the
-  // interaction of fields f and g", V = ffm_engine_pair_count(n_fields); loss_sums[V + 1], variant V the rows
-  // themselves.  The scores stay on the device: only the loss sums come back.
-  void enable_pair_ablation(bool with_auc);
-  void predict_pair_ablated_block(const CsrBlock &blk, std::vector<double> &loss_sums);
-  std::vector<ffm_metrics> read_pair_ablation_metrics(bool reset);
+  // Ablation (include/ffm_engine.h "Field ablation", "Pair ablation"): the loss -- and, with_auc, the AUC -- of this
+  // model without each field (Fields: n_fields + 1 variants) or without the interaction of fields f and g (Pairs:
+  // ffm_engine_pair_count(n_fields) + 1 variants), all from one pass; the last variant is the rows themselves.
+  // ablation_variants is that count (throws for the pairs of more than 64 fields).  enable_ablation allocates the
+  // engine's scratch (one FFM engine only: throws otherwise); predict_ablated_block runs one block through the
+  // synchronous call and ADDS its per-variant loss sums to loss_sums[variants] (the scores stay on the device);
+  // read_ablation_metrics returns the variants' numbers so far and, with reset, starts them from zero.
+  enum class Ablation { Fields, Pairs };
+  size_t ablation_variants(Ablation kind) const;
+  void enable_ablation(Ablation kind, bool with_auc);
+  void predict_ablated_block(Ablation kind, const CsrBlock &blk, std::vector<double> &loss_sums);
+  std::vector<ffm_metrics> read_ablation_metrics(Ablation kind, bool reset);
 
   // Model files in the reference's formats (ffm.cpp:138-200, lr.cpp:26-39); available for every
   // model type here (the reference has none for FM).  save_state/load_state add the FTRL

@@ -1,4 +1,4 @@
-#include "pair_importance.h"
+#include "importance.h"
 
 namespace ftrl {
 
@@ -11,6 +11,22 @@ unsigned long long pair_histogram_bytes(int n_fields) {
 void print_pair_histogram_memory(std::FILE *out, int n_fields) {
   std::fprintf(out, "pair importance: %d score histograms, %llu bytes of device memory\n", pair_count(n_fields) + 1,
                pair_histogram_bytes(n_fields));
+}
+
+int print_field_importance(std::FILE *out, int n_fields, unsigned long long rows, const std::vector<double> &loss,
+                           const std::vector<ffm_metrics> *auc) {
+  const size_t whole = static_cast<size_t>(n_fields);
+  if (loss.size() != whole + 1 || (auc && auc->size() != whole + 1)) return -1;
+  const double n = rows ? static_cast<double>(rows) : 1.0;
+  std::fprintf(out, "field importance: %llu rows, loss %.6lf", rows, loss[whole] / n);
+  if (auc) std::fprintf(out, ", auc %.6lf", (*auc)[whole].auc);
+  std::fprintf(out, "\n");
+  for (size_t f = 0; f < whole; f++) {
+    std::fprintf(out, "field %zu: without it loss %.6lf (delta %+.6lf)", f, loss[f] / n, (loss[f] - loss[whole]) / n);
+    if (auc) std::fprintf(out, ", auc %.6lf (delta %+.6lf)", (*auc)[f].auc, (*auc)[f].auc - (*auc)[whole].auc);
+    std::fprintf(out, "\n");
+  }
+  return n_fields;
 }
 
 int print_pair_importance(std::FILE *out, int n_fields, unsigned long long rows, const std::vector<double> &loss,

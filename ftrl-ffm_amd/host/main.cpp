@@ -8,7 +8,6 @@
 #include <string>
 
 #include "cmd_option.h"
-#include "field_importance.h"
 #include "field_ranges.h"
 #include "rare_ids.h"
 #include "sample_weights.h"
@@ -67,10 +66,10 @@ int main(int argc, char *argv[]) {
       if ((opt.auc_key_field >= 0 || opt.field_importance || opt.pair_importance) && opt.epoch <= 0 && !opt.cmd && !opt.eval_path.empty())
         task.evaluate(static_cast<int>(task.progress().epochs_done));
       task.model_ptr->print_norm_rows();  // (--normalize_rows: one line, after the last epoch or that one evaluation)
-      // --field_importance: after the last evaluation, the same model without each field (field_importance.h)
-      if (opt.field_importance && !opt.cmd) ftrl::FieldImportance(opt, &*task.model_ptr).run();
-      // --pair_importance: then the same model without each field pair (pair_importance.h)
-      if (opt.pair_importance && !opt.cmd) ftrl::run_pair_importance(opt, *task.model_ptr);
+      // --field_importance: after the last evaluation, the same model without each field (importance.h);
+      // --pair_importance: then the same model without each field pair
+      if (opt.field_importance && !opt.cmd) ftrl::run_importance(opt, *task.model_ptr, ftrl::FtrlModel::Ablation::Fields);
+      if (opt.pair_importance && !opt.cmd) ftrl::run_importance(opt, *task.model_ptr, ftrl::FtrlModel::Ablation::Pairs);
       // --refresh_weights: every epoch ended with a refresh and nothing has trained since, so the model, the
       // checkpoint and the scores below are those of refreshed weights; a run that trains nothing (--n_epochs 0
       // on a resumed model) refreshes what it loaded here

@@ -12,7 +12,7 @@
 #include <random>
 #include <thread>
 
-#include "pair_importance.h"
+#include "importance.h"
 #include "score_writer.h"
 
 namespace ftrl {
@@ -44,27 +44,27 @@ void refresh_and_print(FtrlModel &m, long long epoch) {
               static_cast<long long>(r.lat_live), static_cast<long long>(r.lat_nonzero), static_cast<long long>(r.lat_moved));
 }
 
-void run_pair_importance(const config_options &opt, FtrlModel &m) {
-  const bool want_auc = opt.metrics == "auc";
-  if (want_auc) {
+void run_importance(const config_options &opt, FtrlModel &m, FtrlModel::Ablation kind) {
+  const bool want_auc = opt.metrics == "auc", pairs = kind == FtrlModel::Ablation::Pairs;
+  if (want_auc && pairs) {
     print_pair_histogram_memory(stdout, opt.n_fields);
     std::fflush(stdout);  // (the line is there when the allocation is refused)
   }
-  m.enable_pair_ablation(want_auc);
+  m.enable_ablation(kind, want_auc);
   CsrStream stream(opt.eval_path, opt.file_type, opt.thread_num);
   const size_t batch = static_cast<size_t>(std::max(1, opt.batch_size));
-  std::vector<double> loss(static_cast<size_t>(pair_count(opt.n_fields)) + 1, 0.0);
+  std::vector<double> loss(m.ablation_variants(kind), 0.0);
   CsrBlock blk;
   unsigned long long rows = 0;
   for (;;) {
     const size_t got = stream.next(batch, blk);
     if (got == 0) break;
-    m.predict_pair_ablated_block(blk, loss);
+    m.predict_ablated_block(kind, blk, loss);
     rows += got;
   }
   std::vector<ffm_metrics> auc;
-  if (want_auc) auc = m.read_pair_ablation_metrics(true);
-  print_pair_importance(stdout, opt.n_fields, rows, loss, want_auc ? &auc : nullptr);
+  if (want_auc) auc = m.read_ablation_metrics(kind, true);
+  (pairs ? print_pair_importance : print_field_importance)(stdout, opt.n_fields, rows, loss, want_auc ? &auc : nullptr);
 }
 
 void publish_and_print(FtrlModel &m, const std::string &prefix, const std::string &fmt, long long epoch, long long n_feats) {

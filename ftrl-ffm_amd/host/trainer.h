@@ -129,10 +129,11 @@ void print_gauc_line(FtrlModel &m, int epoch, int channel);
 // `epoch N weights: linear L live, Z nonzero, M moved; latent L live, Z nonzero, M moved`.
 // The tasks call it after each epoch's training, before that epoch's evaluation; main() where no epoch ran.
 void refresh_and_print(FtrlModel &m, long long epoch);
-// --pair_importance true: one more pass over --eval_data through FtrlModel::predict_pair_ablated_block (the host
-// parser's blocks, the synchronous call, loss sums added in block order) and the lines of pair_importance.h; with
-// --metrics auc the histograms' memory is printed before FtrlModel::enable_pair_ablation allocates it.
-void run_pair_importance(const config_options &opt, FtrlModel &m);
+// --field_importance true, --pair_importance true: one more pass over --eval_data through
+// FtrlModel::predict_ablated_block (the host parser's blocks, the synchronous call, loss sums added in block order)
+// and the kind's lines of importance.h; for the pairs with --metrics auc the histograms' memory is printed before
+// FtrlModel::enable_ablation allocates it.
+void run_importance(const config_options &opt, FtrlModel &m, FtrlModel::Ablation kind);
 // --publish_path: FtrlModel::publish_delta(prefix, fmt, epoch) and its line,
 // `epoch N published: M of F features moved, B bytes -> FILE`
 void publish_and_print(FtrlModel &m, const std::string &prefix, const std::string &fmt, long long epoch, long long n_feats);

@@ -1069,8 +1069,14 @@ int ffm_engine_score_candidates_device(ffm_engine *e, int32_t n_req, const int32
  *   a row without field v  has variant v equal to variant n_fields, bit for bit.
  *   multi-valued fields    every entry of the field goes.
  * ffm_engine_ablation_enable  allocates the (n_fields + 1) x max_batch_rows score and loss scratch and, with
- *   with_auc, n_fields + 1 score histograms of 16 MiB each (640 MiB at 39 fields), zeroed; a second call keeps
- *   what is on and its counts.  All of it is freed by ffm_engine_destroy.  Refused with FFM_E_UNSUPPORTED and a
+ *   with_auc, n_fields + 1 score histograms of 16 MiB each (640 MiB at 39 fields), zeroed; a later call
+ *   allocates only what is missing, and with_auc on it means what it means for ffm_engine_pair_ablation_enable
+ *   (1 keeps what is collected, 0 stops the collection, a later 1 starts from zero).  The call is all or nothing:
+ *   everything it has to make is made before anything of the engine changes, so a failed allocation is
+ *   FFM_E_NOMEM, gives back what the call had made and leaves state and memory as they were (field ablation
+ *   stays off, or on without histograms).  FFM_FIELD_HIST_FAIL=1 in the environment (and FFM_PAIR_HIST_FAIL=1
+ *   for the pairs), a test hook read at each call, fails the histograms' allocation that way without filling a
+ *   device.  All of it is freed by ffm_engine_destroy.  Refused with FFM_E_UNSUPPORTED and a
  *   message that says why: anything but a whole FFM model on one device (LR, FM, n_shards > 1, a group's
  *   engine, compact storage); n_factors outside {4, 8, 16, 32, 64}; n_fields > 64 (one lane per variant means
  *   one wave).  Works on training engines and on FFM_FLAG_SERVE_F32 / _F16 serving engines.

@@ -1,6 +1,6 @@
-// Stand-alone check of --pair_importance in host/cmd_option.cpp and of host/pair_importance.cpp (no GPU, no engine
+// Stand-alone check of --pair_importance in host/cmd_option.cpp and of host/importance.cpp (no GPU, no engine
 // library): the default, what is accepted, every refusal -- all made while the options are parsed, before a device
-// is opened --, the pairs' numbering, the histogram memory and the printed lines.  Built and run by
+// is opened --, the pairs' numbering, the histogram memory and the printed lines of both flags.  Built and run by
 // tests/test_pair_ablation_host.py, once plainly and once under -fsanitize=address,undefined.
 //   usage: pair_option <libffm file> <libsvm file> <scratch file> [libffm_engine.so: its numbering is compared too]
 #include <dlfcn.h>
@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "../ftrl-ffm_amd/host/cmd_option.h"
-#include "../ftrl-ffm_amd/host/pair_importance.h"
+#include "../ftrl-ffm_amd/host/importance.h"
 
 static int n_ok = 0, n_fail = 0;
 static void check(bool cond, const char *what) {
@@ -42,10 +42,11 @@ static std::string refusal(std::vector<std::string> args) {
 static bool has(const std::string &msg, const char *part) { return msg.find(part) != std::string::npos; }
 
 static std::string printed(const char *path, int n_fields, unsigned long long rows, const std::vector<double> &loss,
-                           const std::vector<ffm_metrics> *auc, int *listed) {
+                           const std::vector<ffm_metrics> *auc, int *listed,
+                           decltype(&ftrl::print_pair_importance) print = ftrl::print_pair_importance) {
   std::FILE *f = std::fopen(path, "w");
   if (!f) return "<cannot open>";
-  *listed = ftrl::print_pair_importance(f, n_fields, rows, loss, auc);
+  *listed = print(f, n_fields, rows, loss, auc);
   std::fclose(f);
   std::ifstream in(path);
   std::stringstream s;
@@ -98,7 +99,7 @@ int main(int argc, char **argv) {
         "none of it without the flag");
   check(std::string(cmd_help).find("--pair_importance <bool>") != std::string::npos, "the help names the flag");
 
-  // ---- host/pair_importance.cpp
+  // ---- host/importance.cpp
   {
     bool ok = true;
     for (int F = 1; F <= 64; F++) {
@@ -137,6 +138,38 @@ int main(int argc, char **argv) {
     check(listed == 0 && none == "pair importance: 0 rows, loss 0.000000\npair importance: 0 of 3 pairs listed, 3 never changed a row\n",
           "an empty file");
   }
+  {
+    // 3 fields; the lines of every field, moved or not
+    std::vector<double> loss = {5.0, 4.0, 3.5, 4.0};
+    int lines = -1;
+    const std::string s = printed(argv[3], 3, 8, loss, nullptr, &lines, ftrl::print_field_importance);
+    check(lines == 3 &&
+              s == "field importance: 8 rows, loss 0.500000\n"
+                   "field 0: without it loss 0.625000 (delta +0.125000)\n"
+                   "field 1: without it loss 0.500000 (delta +0.000000)\n"
+                   "field 2: without it loss 0.437500 (delta -0.062500)\n",
+          "the fields' lines without AUC");
+    std::vector<ffm_metrics> auc(4);
+    for (size_t v = 0; v < auc.size(); v++) auc[v].auc = 0.75;
+    auc[0].auc = 0.5;
+    const std::string t = printed(argv[3], 3, 8, loss, &auc, &lines, ftrl::print_field_importance);
+    check(lines == 3 &&
+              t == "field importance: 8 rows, loss 0.500000, auc 0.750000\n"
+                   "field 0: without it loss 0.625000 (delta +0.125000), auc 0.500000 (delta -0.250000)\n"
+                   "field 1: without it loss 0.500000 (delta +0.000000), auc 0.750000 (delta +0.000000)\n"
+                   "field 2: without it loss 0.437500 (delta -0.062500), auc 0.750000 (delta +0.000000)\n",
+          "the fields' lines with AUC");
+    auc.pop_back();
+    const std::string short_auc = printed(argv[3], 3, 8, loss, &auc, &lines, ftrl::print_field_importance);
+    loss.pop_back();
+    check(lines == -1 && short_auc.empty() && ftrl::print_field_importance(stdout, 3, 8, loss, nullptr) == -1,
+          "a loss or AUC vector of the wrong length prints no field line");
+    const std::string none = printed(argv[3], 2, 0, {0.0, 0.0, 0.0}, nullptr, &lines, ftrl::print_field_importance);
+    check(lines == 2 && none == "field importance: 0 rows, loss 0.000000\n"
+                                "field 0: without it loss 0.000000 (delta +0.000000)\n"
+                                "field 1: without it loss 0.000000 (delta +0.000000)\n",
+          "the fields' lines of an empty file");
+  }
   if (argc == 5) {
     // the engine library's numbering -- ffm_engine_pair_count / _pair_index, which are the kernel header's pair_base
     // and pair_variants -- against this file's copy, every pair of 1 .. 64 fields in both orders
@@ -151,7 +184,7 @@ int main(int argc, char **argv) {
       for (int f = 0; ok && f < F; f++)
         for (int g = f; ok && g < F; g++) ok = index(F, f, g) == ftrl::pair_index(F, f, g) && index(F, g, f) == ftrl::pair_index(F, f, g);
     }
-    check(ok, "the engine library numbers the pairs as host/pair_importance.h does");
+    check(ok, "the engine library numbers the pairs as host/importance.h does");
   }
   std::printf("%d ok, %d failed\n", n_ok, n_fail);
   return n_fail == 0 ? 0 : 1;

@@ -305,6 +305,51 @@ def code_of(call):
     return ei.value.code, str(ei.value)
 
 
+def test_failed_histogram_allocation_leaves_the_engine_as_it_was(monkeypatch):
+    """FFM_FIELD_HIST_FAIL=1 makes the histograms' allocation fail as an exhausted device does (the library's test
+    hook).  A first enable(auc=True) then is FFM_E_NOMEM, field ablation stays off and the scratch the call had made
+    is given back; on an engine that is already on, the same failure leaves it on without histograms and its
+    results unchanged.  Then with_auc on later calls: 0 stops the collection, 1 starts it from zero."""
+    k = 16
+    lens = np.diff(ladder_block().row_ptr)
+    five = tuple(int(np.flatnonzero(lens == n)[0]) for n in (127, 0, 65, 1, 33))  # (test_ladder's five rows)
+    b = take_rows(ladder_block(), list(five))
+    want = ladder_expected(k, "f32", five)
+    rows = 1 << 16  # (7 variants x 65536 rows x 12 bytes = 5.5 MB of scratch: visible in the device's free memory)
+    E_NOMEM = fa.engine.E_NOMEM
+    e = training(k, ladder_weights(k), max_batch_rows=rows)
+    e.sync()
+    free_before = torch.cuda.mem_get_info()[0]
+    monkeypatch.setenv("FFM_FIELD_HIST_FAIL", "1")
+    code, msg = code_of(lambda: e.ablation_enable(auc=True))
+    assert code == E_NOMEM and "bytes failed" in msg, msg
+    assert torch.cuda.mem_get_info()[0] >= free_before - (4 << 20), "the scratch made before the failure was given back"
+    code, msg = code_of(lambda: e.predict_ablated(b))
+    assert code == E_INVALID and "ablation_enable" in msg
+    e.ablation_enable()  # (no histograms asked for: nothing to fail)
+    check_ablated(e, b, want, "on, after a failed enable")
+    code, msg = code_of(lambda: e.ablation_enable(auc=True))
+    assert code == E_NOMEM
+    code, msg = code_of(e.ablation_metrics)
+    assert code == E_INVALID and "with_auc" in msg
+    check_ablated(e, b, want, "still on without histograms")
+    monkeypatch.delenv("FFM_FIELD_HIST_FAIL")
+    e.ablation_enable(auc=True)
+    e.predict_ablated(b)
+    counts = lambda m: (m["n_pos"], m["n_neg"], m["n_nan"])  # noqa: E731
+    counted = counts(e.ablation_metrics()[ROW_FIELDS])
+    assert counted[0] + counted[1] == b.n_rows and counted[2] == 0
+    e.ablation_enable(auc=True)  # collection that stays on keeps its counts
+    assert counts(e.ablation_metrics()[ROW_FIELDS]) == counted
+    e.ablation_enable(auc=False)  # stops it
+    assert code_of(e.ablation_metrics)[0] == E_INVALID
+    e.predict_ablated(b)
+    e.ablation_enable(auc=True)  # and a later one starts from zero
+    assert counts(e.ablation_metrics()[ROW_FIELDS]) == (0, 0, 0)
+    check_ablated(e, b, want, "after the switches")
+    e.close()
+
+
 def test_refusals():
     b = ladder_block()
     for what, e in (("LR", fa.Engine("LR", 64, 1, 1, max_batch_rows=16)), ("FM", fa.Engine("FM", 64, 1, 4, max_batch_rows=16)),

@@ -24,7 +24,7 @@ IMPORTANCE = re.compile(r"^(field importance: .*|field \d+: without it .*)\n", r
 
 
 def expected_lines(e, data):
-    """The lines of FieldImportance::run from the binding: the file in blocks of BATCH rows through
+    """The lines of run_importance for the fields from the binding: the file in blocks of BATCH rows through
     predict_ablated, the loss sums added in block order."""
     n = data.n_rows
     loss = np.zeros(F + 1)

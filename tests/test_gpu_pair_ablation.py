@@ -1,4 +1,4 @@
-"""Pair ablation (include/ffm_engine.h "Pair ablation"; csrc/kernels_ablate_pairs.h, csrc/engine_ablate_pairs.h):
+"""Pair ablation (include/ffm_engine.h "Pair ablation"; csrc/kernels_ablate_pairs.h, csrc/engine_ablate.h):
 the V + 1 = n_fields (n_fields + 1) / 2 + 1 variants of every row from one pass.
 
 The expected value of variant (f, g) is predict_batch of the SAME block on weights whose latent slot "towards field

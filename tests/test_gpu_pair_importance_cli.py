@@ -26,7 +26,7 @@ NUMBER = re.compile(r"[-+]?\d+\.\d+")
 
 
 def expected_lines(e, data, auc):
-    """The lines of run_pair_importance from the binding: the file in blocks of BATCH rows through
+    """The lines of run_importance for the pairs from the binding: the file in blocks of BATCH rows through
     predict_pair_ablated (scores left on the device), the loss sums added in block order."""
     n = data.n_rows
     loss = np.zeros(V + 1)

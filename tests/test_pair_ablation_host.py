@@ -1,7 +1,7 @@
 """Pair ablation, the part that needs no GPU (include/ffm_engine.h "Pair ablation"): the numbering of the variants,
 C against numpy, for every n_fields in 1 .. 64; the zeroed-slot argument that the GPU tests rest on, checked on the
 oracle alone; the header declares the entry points and keeps its ABI version, the library exports them; the CLI
-flag, its refusals and host/pair_importance.cpp through tests/pair_option_main.cpp, plainly and under
+flag, its refusals and host/importance.cpp through tests/pair_option_main.cpp, plainly and under
 -fsanitize=address,undefined."""
 import ctypes
 import os
@@ -146,13 +146,13 @@ SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-f
 
 @pytest.mark.parametrize("flags", [[], SAN], ids=["plain", "asan_ubsan"])
 def test_cli_flag_refusals_and_lines(tmp_path, flags):
-    """host/cmd_option.cpp and host/pair_importance.cpp alone (tests/pair_option_main.cpp): the default, what is
-    accepted, every refusal with its message, the numbering, the histogram memory, the printed lines."""
+    """host/cmd_option.cpp and host/importance.cpp alone (tests/pair_option_main.cpp): the default, what is
+    accepted, every refusal with its message, the numbering, the histogram memory, the printed lines of both flags."""
     exe = str(tmp_path / "pair_option")
     host = os.path.join(ROOT, "ftrl-ffm_amd", "host")
     cc = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra"] + flags +
                         ["-o", exe, os.path.join(ROOT, "tests", "pair_option_main.cpp"), os.path.join(host, "cmd_option.cpp"),
-                         os.path.join(host, "pair_importance.cpp"), "-ldl"], capture_output=True, text=True, timeout=300)
+                         os.path.join(host, "importance.cpp"), "-ldl"], capture_output=True, text=True, timeout=300)
     assert cc.returncode == 0, cc.stderr
     assert "warning" not in cc.stderr, cc.stderr
     ffm = tmp_path / "d.ffm"
@@ -166,7 +166,7 @@ def test_cli_flag_refusals_and_lines(tmp_path, flags):
     out = subprocess.run([exe, str(ffm), str(svm), str(tmp_path / "lines.txt")] + more, capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "0 failed" in out.stdout and "FAIL" not in out.stdout, out.stdout
-    assert out.stdout.count("ok  ") == 18 + len(more), out.stdout
+    assert out.stdout.count("ok  ") == 22 + len(more), out.stdout
     assert ("the engine library numbers the pairs" in out.stdout) == bool(more)
     assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
 
