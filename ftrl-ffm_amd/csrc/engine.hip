@@ -677,6 +677,8 @@ static bool flat_pays(const ffm_engine *e, int span4) {
   return span4 * 6 < lanes * 5;
 }
 
+#include "engine_count.h"
+
 extern "C" {
 
 int ffm_engine_abi_version(void) { return FFM_ENGINE_ABI_VERSION; }

@@ -3,16 +3,15 @@
 // the in-place hash of an engine that folds by such a map.  Host side: engine_idcount.h.  (The upload kernel's
 // folding variants: kernels_stage.h; the filtered sketch: kernels_sketch.h; the fold itself: hash_ids.h.)
 //
-// idcount_kernel has the shape of field_sketch_kernel (kernels_sketch.h): few workgroups when it reads over
-// PCIe, a lane loads the int4 of feat and the int4 of field over a grid stride, what is left goes entry by
-// entry.  Counters are 32-bit words in HBM.  Per counting entry: a plain load of its word, and an integer
+// idcount_kernel walks its entries as every counting kernel does (count_walk, kernels_count.h).  Counters are
+// 32-bit words in HBM.  Per counting entry: a plain load of its word, and an integer
 // atomic add only while the loaded value is below the cap.  Words only grow, so a stale load can cause a
 // superfluous add and never a missed one: min(word, cap) == min(true count, cap) whatever the order, the
 // batching or the split across calls -- and the Zipf head stops issuing atomics after its first `cap`
 // occurrences.  (A word exceeds the cap by at most the adds in flight at once: far from 2^32.)
-// n_valid / n_bad: ballots, one atomic per wave, as in field_sketch_kernel.  No LDS, no float atomics.
+// n_valid / n_bad: the walk's ballots, one atomic per wave.  No LDS, no float atomics.
 #pragma once
-#include "hash_ids.h"
+#include "kernels_count.h"
 
 namespace ftrl_dev {
 
@@ -26,53 +25,15 @@ __device__ __forceinline__ bool idcount_entry(unsigned F, int field, int feat, u
   return true;
 }
 
-// Entries [0, nnz) of a call.  field / feat: device-visible; vec != 0: both are 16-byte aligned.  HAS_FIELD ==
-// false: LR / FM (F == 0), or entry p of the call is field (first + p) mod F, first a multiple of 4 (a call cut
-// into chunks).  cnt: 2^(32 - shift) words.  counters: n_valid, n_bad.  Every loop is wave-uniform (a lane past
-// the end idles): the ballots see whole waves.
+// Entries [0, nnz) of a call, walked by count_walk (kernels_count.h); without a field array F == 0 is LR / FM, the
+// field taken as 0.  cnt: 2^(32 - shift) words.  counters: n_valid, n_bad.
 template <bool HAS_FIELD>
 __global__ __launch_bounds__(256) void idcount_kernel(unsigned nnz, const int *field, const int *feat, unsigned first, unsigned F,
                                                       int vec, unsigned shift, unsigned cap, unsigned *cnt,
                                                       unsigned long long *counters) {
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // (a refilled page-locked buffer: pull_block_kernel's reason)
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave0 = blockIdx.x * blockDim.x + threadIdx.x - lane, stride = gridDim.x * blockDim.x;
-  const unsigned n4 = vec ? nnz >> 2 : 0u;
-  unsigned n_ok = 0, n_seen = 0;  // wave-uniform
-  for (unsigned base = wave0; base < n4; base += stride) {
-    const unsigned i = base + lane;
-    const bool live = i < n4;
-    bool ok0 = false, ok1 = false, ok2 = false, ok3 = false;
-    if (live) {
-      const int4 ft = reinterpret_cast<const int4 *>(feat)[i];
-      int4 fl;
-      if constexpr (HAS_FIELD) fl = reinterpret_cast<const int4 *>(field)[i];
-      else fl = F ? ftrl_hash::hash_implicit_fields4((first >> 2) + i, F) : make_int4(0, 0, 0, 0);
-      ok0 = idcount_entry(F, fl.x, ft.x, shift, cap, cnt);
-      ok1 = idcount_entry(F, fl.y, ft.y, shift, cap, cnt);
-      ok2 = idcount_entry(F, fl.z, ft.z, shift, cap, cnt);
-      ok3 = idcount_entry(F, fl.w, ft.w, shift, cap, cnt);
-    }
-    n_ok += __popcll(__ballot(ok0)) + __popcll(__ballot(ok1)) + __popcll(__ballot(ok2)) + __popcll(__ballot(ok3));
-    n_seen += 4u * __popcll(__ballot(live));
-  }
-  for (unsigned base = (n4 << 2) + wave0; base < nnz; base += stride) {
-    const unsigned p = base + lane;
-    const bool live = p < nnz;
-    bool ok = false;
-    if (live) {
-      int f;
-      if constexpr (HAS_FIELD) f = field[p]; else f = F ? static_cast<int>((first % F + p % F) % F) : 0;
-      ok = idcount_entry(F, f, feat[p], shift, cap, cnt);
-    }
-    n_ok += __popcll(__ballot(ok));
-    n_seen += __popcll(__ballot(live));
-  }
-  if (lane == 0u) {
-    if (n_ok) __hip_atomic_fetch_add(counters, static_cast<unsigned long long>(n_ok), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (n_seen != n_ok)
-      __hip_atomic_fetch_add(counters + 1, static_cast<unsigned long long>(n_seen - n_ok), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  count_walk<HAS_FIELD, true, false>(nnz, field, reinterpret_cast<const unsigned *>(feat), first, F, vec, counters, [&](int fld, unsigned bits) {
+    return idcount_entry(F, fld, static_cast<int>(bits), shift, cap, cnt);
+  });
 }
 
 // The keep-map of n_slots counters (a multiple of 64: bits >= 8): a lane is a slot, the ballot of

@@ -3,8 +3,7 @@
 // in-place mapping of an engine that holds a bucket table.  Host side: engine_valhist.h.  (The upload kernel's
 // bucketing variants: kernels_stage.h; the mapping of one entry: hash_ids.h.)
 //
-// valhist_kernel has the shape of field_sketch_kernel and idcount_kernel: few workgroups when it reads over PCIe,
-// a lane loads the int4 of field and the 16 bytes of val over a grid stride, what is left goes entry by entry.
+// valhist_kernel walks its entries as every counting kernel does (count_walk, kernels_count.h).
 // The histogram is n_fields x 65536 64-bit words in HBM.  The hazard is skew -- half of a count column is one
 // value -- so a workgroup sums in LDS first: a write-back cache of kValhistSets sets of two ways.  A way is ONE
 // 64-bit word, key << 32 | count, the key being field << 16 | bin (the word's index in the histogram) and an
@@ -18,9 +17,9 @@
 // empty one evicts the way with the smaller count (a plain read: a heuristic, never a correctness matter), so of
 // two hot keys in one set both stay.  Global atomics per entry: one per eviction plus the final flush -- for a
 // column of D distinct bins per workgroup at most D when D <= the cache, and for the hot value one per
-// workgroup.  n_valid / n_bad / n_nan: ballots, one atomic per wave.  No float instruction touches a value.
+// workgroup.  n_valid / n_bad / n_nan: the walk's ballots, one atomic per wave.  No float instruction touches a value.
 #pragma once
-#include "hash_ids.h"
+#include "kernels_count.h"
 
 namespace ftrl_dev {
 
@@ -63,58 +62,16 @@ __device__ __forceinline__ unsigned valhist_entry(unsigned F, int field, unsigne
   return 1u;
 }
 
-// Entries [0, nnz) of a call.  field / val: device-visible; vec != 0: both are 16-byte aligned.  HAS_FIELD ==
-// false: entry p of the call is field (first + p) mod F, first a multiple of 4 (a call cut into chunks).
-// hist: F x 65536 words.  counters: n_valid, n_bad, n_nan.  Every loop is wave-uniform (a lane past the end
-// idles): the ballots see whole waves.
+// Entries [0, nnz) of a call, walked by count_walk (kernels_count.h) between the cache's set-up and its flush.
+// hist: F x 65536 words.  counters: n_valid, n_bad, n_nan.
 template <bool HAS_FIELD>
 __global__ __launch_bounds__(256) void valhist_kernel(unsigned nnz, const int *field, const unsigned *val, unsigned first, unsigned F,
                                                       int vec, unsigned long long *hist, unsigned long long *counters) {
   __shared__ unsigned long long cache[2 * kValhistSets];
   for (unsigned i = threadIdx.x; i < 2 * kValhistSets; i += blockDim.x) cache[i] = ~0ull;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // (a refilled page-locked buffer: pull_block_kernel's reason)
   __syncthreads();
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned wave0 = blockIdx.x * blockDim.x + threadIdx.x - lane, stride = gridDim.x * blockDim.x;
-  const unsigned n4 = vec ? nnz >> 2 : 0u;
-  unsigned n_ok = 0, n_seen = 0, n_nan = 0;  // wave-uniform
-  for (unsigned base = wave0; base < n4; base += stride) {
-    const unsigned i = base + lane;
-    const bool live = i < n4;
-    unsigned r0 = 0, r1 = 0, r2 = 0, r3 = 0;
-    if (live) {
-      const uint4 v = reinterpret_cast<const uint4 *>(val)[i];
-      int4 fl;
-      if constexpr (HAS_FIELD) fl = reinterpret_cast<const int4 *>(field)[i];
-      else fl = ftrl_hash::hash_implicit_fields4((first >> 2) + i, F);
-      r0 = valhist_entry(F, fl.x, v.x, cache, hist);
-      r1 = valhist_entry(F, fl.y, v.y, cache, hist);
-      r2 = valhist_entry(F, fl.z, v.z, cache, hist);
-      r3 = valhist_entry(F, fl.w, v.w, cache, hist);
-    }
-    n_ok += __popcll(__ballot(r0 != 0u)) + __popcll(__ballot(r1 != 0u)) + __popcll(__ballot(r2 != 0u)) + __popcll(__ballot(r3 != 0u));
-    n_nan += __popcll(__ballot(r0 == 2u)) + __popcll(__ballot(r1 == 2u)) + __popcll(__ballot(r2 == 2u)) + __popcll(__ballot(r3 == 2u));
-    n_seen += 4u * __popcll(__ballot(live));
-  }
-  for (unsigned base = (n4 << 2) + wave0; base < nnz; base += stride) {
-    const unsigned p = base + lane;
-    const bool live = p < nnz;
-    unsigned r = 0;
-    if (live) {
-      int f;
-      if constexpr (HAS_FIELD) f = field[p]; else f = static_cast<int>((first % F + p % F) % F);
-      r = valhist_entry(F, f, val[p], cache, hist);
-    }
-    n_ok += __popcll(__ballot(r != 0u));
-    n_nan += __popcll(__ballot(r == 2u));
-    n_seen += __popcll(__ballot(live));
-  }
-  if (lane == 0u) {
-    if (n_ok) __hip_atomic_fetch_add(counters, static_cast<unsigned long long>(n_ok), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (n_seen != n_ok)
-      __hip_atomic_fetch_add(counters + 1, static_cast<unsigned long long>(n_seen - n_ok), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (n_nan) __hip_atomic_fetch_add(counters + 2, static_cast<unsigned long long>(n_nan), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  count_walk<HAS_FIELD, false, true>(nnz, field, val, first, F, vec, counters,
+                                     [&](int fld, unsigned vbits) { return valhist_entry(F, fld, vbits, cache, hist); });
   // the flush: every wave of the workgroup is past its last swap
   __syncthreads();
   for (unsigned i = threadIdx.x; i < 2 * kValhistSets; i += blockDim.x) {

@@ -1474,43 +1474,79 @@ class Engine:
         return buf.value.decode()
 
 
-class FieldSketch:
-    """One HyperLogLog sketch per field, filled on the device (include/ffm_engine.h "Field sketches"): how many
-    distinct ids each field of a data set holds, before a model exists.  Needs no engine."""
+class _CountingObject:
+    """What FieldSketch, ValueHistogram and IdCounter share: the handle, and entries added from host or device
+    arrays.  A subclass names its entry points (_prefix) and its second array (_second: name, dtype)."""
+    _prefix = None
+    _second = ("feat", np.int32)
 
-    def __init__(self, n_fields, device=0):
+    def _create(self, *args):
         self.lib = load_library()
         self.h = _vp()
-        self.n_fields = int(n_fields)
-        self._check(self.lib.ffm_engine_sketch_create(self.n_fields, int(device), ctypes.byref(self.h)))
+        self._check(self._fn("create")(*args, ctypes.byref(self.h)))
+
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + "_" + name)
 
     def _check(self, rc):
         if rc != 0:
             raise EngineError(rc, self.lib.ffm_engine_last_error().decode())
 
     @staticmethod
-    def _ids(a, what):
+    def _array(a, dtype, what):
         if a is None:
             return None
-        if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous):
-            a = np.ascontiguousarray(a, np.int32)
+        if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.flags.c_contiguous):
+            a = np.ascontiguousarray(a, dtype)
         if a.ndim != 1:
-            raise ValueError(what + ": a one-dimensional int32 array")
+            raise ValueError("%s: a one-dimensional %s array" % (what, np.dtype(dtype).name))
         return a
+
+    @staticmethod
+    def _ids(a, what):
+        return _CountingObject._array(a, np.int32, what)
+
+    def _add(self, field, second, zero_copy):
+        name, dtype = self._second
+        second = self._array(second, dtype, name)
+        field = self._ids(field, "field")
+        if field is not None and field.size != second.size:
+            raise ValueError("field and %s must be equally long" % name)
+        self._check(self._fn("add")(self.h, second.size, None if field is None else field.ctypes.data,
+                                    second.ctypes.data, int(bool(zero_copy))))
+
+    def _add_device(self, nnz, field, second):
+        self._check(self._fn("add_device")(self.h, int(nnz), field, second))
+
+    def close(self):
+        if self.h:
+            self._fn("destroy")(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FieldSketch(_CountingObject):
+    """One HyperLogLog sketch per field, filled on the device (include/ffm_engine.h "Field sketches"): how many
+    distinct ids each field of a data set holds, before a model exists.  Needs no engine."""
+    _prefix = "ffm_engine_sketch"
+
+    def __init__(self, n_fields, device=0):
+        self.n_fields = int(n_fields)
+        self._create(self.n_fields, int(device))
 
     def add(self, field, feat, zero_copy=False):
         """Counts the entries (field[p], feat[p]); field None: entry p is field p mod n_fields.  zero_copy: the
         arrays are page-locked (ffm_engine_pin_host) int32 arrays, read in place.  Back once they may be reused."""
-        feat = self._ids(feat, "feat")
-        field = self._ids(field, "field")
-        if field is not None and field.size != feat.size:
-            raise ValueError("field and feat must be equally long")
-        self._check(self.lib.ffm_engine_sketch_add(self.h, feat.size, None if field is None else field.ctypes.data,
-                                                   feat.ctypes.data, int(bool(zero_copy))))
+        self._add(field, feat, zero_copy)
 
     def add_device(self, nnz, field, feat):
         """The same for int32 arrays in device memory (addresses; field may be None); asynchronous."""
-        self._check(self.lib.ffm_engine_sketch_add_device(self.h, int(nnz), field, feat))
+        self._add_device(nnz, field, feat)
 
     def read(self):
         """(reg uint8 [n_fields, SKETCH_REGS], n_valid, n_bad) after everything added so far."""
@@ -1532,48 +1568,25 @@ class FieldSketch:
         bits, words = _rare_words(bits, words)
         self._check(self.lib.ffm_engine_sketch_set_filter(self.h, bits, words.ctypes.data))
 
-    def close(self):
-        if self.h:
-            self.lib.ffm_engine_sketch_destroy(self.h)
-            self.h = _vp()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ValueHistogram:
+class ValueHistogram(_CountingObject):
     """How often every (field, bin) of numeric columns occurs, counted exactly on the device
     (include/ffm_engine.h "Value buckets").  FFM only.  Needs no engine."""
+    _prefix = "ffm_engine_valhist"
+    _second = ("val", np.float32)
 
     def __init__(self, n_fields, device=0):
-        self.lib = load_library()
-        self.h = _vp()
         self.n_fields = int(n_fields)
-        self._check(self.lib.ffm_engine_valhist_create(self.n_fields, int(device), ctypes.byref(self.h)))
-
-    def _check(self, rc):
-        if rc != 0:
-            raise EngineError(rc, self.lib.ffm_engine_last_error().decode())
+        self._create(self.n_fields, int(device))
 
     def add(self, field, val, zero_copy=False):
         """Counts the entries (field[p], val[p]); field None: entry p is field p mod n_fields.  zero_copy:
         page-locked (ffm_engine_pin_host) int32 / float32 arrays, read in place.  Back once they may be reused."""
-        if not (isinstance(val, np.ndarray) and val.dtype == np.float32 and val.flags.c_contiguous):
-            val = np.ascontiguousarray(val, np.float32)
-        if val.ndim != 1:
-            raise ValueError("val: a one-dimensional float32 array")
-        field = FieldSketch._ids(field, "field")
-        if field is not None and field.size != val.size:
-            raise ValueError("field and val must be equally long")
-        self._check(self.lib.ffm_engine_valhist_add(self.h, val.size, None if field is None else field.ctypes.data,
-                                                    val.ctypes.data, int(bool(zero_copy))))
+        self._add(field, val, zero_copy)
 
     def add_device(self, nnz, field, val):
         """The same for arrays in device memory (addresses; field may be None); asynchronous."""
-        self._check(self.lib.ffm_engine_valhist_add_device(self.h, int(nnz), field, val))
+        self._add_device(nnz, field, val)
 
     def read(self):
         """(counts uint64 [n_fields, BUCKET_BINS], n_valid, n_bad, n_nan) after everything added so far."""
@@ -1582,17 +1595,6 @@ class ValueHistogram:
         self._check(self.lib.ffm_engine_valhist_read(self.h, counts.ctypes.data, ctypes.byref(nv), ctypes.byref(nb),
                                                      ctypes.byref(nn)))
         return counts, int(nv.value), int(nb.value), int(nn.value)
-
-    def close(self):
-        if self.h:
-            self.lib.ffm_engine_valhist_destroy(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _text_bytes(data):
@@ -1734,34 +1736,23 @@ class RowCutter:
             pass
 
 
-class IdCounter:
+class IdCounter(_CountingObject):
     """How often every hashed slot occurs, counted on the device up to a cap (include/ffm_engine.h "Rare ids"),
     and the keep-map of a minimum count.  n_fields 0: LR / FM.  Needs no engine."""
+    _prefix = "ffm_engine_idcount"
 
     def __init__(self, n_fields, bits, cap, device=0):
-        self.lib = load_library()
-        self.h = _vp()
         self.n_fields, self.bits, self.cap = int(n_fields), int(bits), int(cap)
-        self._check(self.lib.ffm_engine_idcount_create(self.n_fields, self.bits, self.cap, int(device),
-                                                       ctypes.byref(self.h)))
-
-    def _check(self, rc):
-        if rc != 0:
-            raise EngineError(rc, self.lib.ffm_engine_last_error().decode())
+        self._create(self.n_fields, self.bits, self.cap, int(device))
 
     def add(self, field, feat, zero_copy=False):
         """Counts the entries (field[p], feat[p]); field None: LR / FM, or entry p is field p mod n_fields.
         zero_copy: page-locked (ffm_engine_pin_host) int32 arrays, read in place.  Back once they may be reused."""
-        feat = FieldSketch._ids(feat, "feat")
-        field = FieldSketch._ids(field, "field")
-        if field is not None and field.size != feat.size:
-            raise ValueError("field and feat must be equally long")
-        self._check(self.lib.ffm_engine_idcount_add(self.h, feat.size, None if field is None else field.ctypes.data,
-                                                    feat.ctypes.data, int(bool(zero_copy))))
+        self._add(field, feat, zero_copy)
 
     def add_device(self, nnz, field, feat):
         """The same for int32 arrays in device memory (addresses; field may be None); asynchronous."""
-        self._check(self.lib.ffm_engine_idcount_add_device(self.h, int(nnz), field, feat))
+        self._add_device(nnz, field, feat)
 
     def read(self):
         """(counts uint32 [2^bits] = min(count, cap), n_valid, n_bad) after everything added so far."""
@@ -1778,17 +1769,6 @@ class IdCounter:
         self._check(self.lib.ffm_engine_idcount_keep(self.h, int(min_count), words.ctypes.data, ctypes.byref(nk),
                                                      ctypes.byref(nf)))
         return words, int(nk.value), int(nf.value)
-
-    def close(self):
-        if self.h:
-            self.lib.ffm_engine_idcount_destroy(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Group:

@@ -1,35 +1,20 @@
-// field_count.cpp -- --field_ranges counted: one pass over the training file before a model exists.  The
-// parser's threads fill a page-locked block, the device counts its (field, feat) entries into a sketch
-// straight from there (the host does nothing per entry), and the estimates size the fields' id ranges.
+// field_count.cpp -- --field_ranges counted: one pass over the training file before a model exists (count_pass.h).
+// The device counts the (field, feat) entries into a sketch, and the estimates size the fields' id ranges.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <stdexcept>
 
-#include "count_block.h"
+#include "count_pass.h"
 #include "field_ranges.h"
-#include "text_stream.h"
 
 namespace ftrl {
-
-namespace {
-
-void check_rc(int rc, const char *what) {
-  if (rc != FFM_OK) throw std::runtime_error(std::string(what) + ": " + ffm_engine_last_error());
-}
-
-struct SketchHandle {
-  ffm_sketch *s = nullptr;
-  ~SketchHandle() { ffm_engine_sketch_destroy(s); }
-};
-
-}  // namespace
 
 std::vector<int32_t> count_field_ranges(const config_options &opt) {
   const auto t0 = std::chrono::steady_clock::now();
   const int F = opt.n_fields;
-  SketchHandle sk;
+  CountHandle<ffm_sketch, ffm_engine_sketch_destroy> sk;
   {
     const int rc = ffm_engine_sketch_create(F, opt.device, &sk.s);
     if (rc == FFM_E_INVALID) throw std::invalid_argument(ffm_engine_last_error());
@@ -38,30 +23,15 @@ std::vector<int32_t> count_field_ranges(const config_options &opt) {
   // --min_count / --rare_ids: the ranges are sized by the ids that stay -- a rare id counts as its field's one rare id
   if (!opt.rare_words.empty())
     check_rc(ffm_engine_sketch_set_filter(sk.s, opt.rare_map_bits, opt.rare_words.data()), "ffm_engine_sketch_set_filter");
-  unsigned long long rows = 0;
-  if (opt.device_parse) {
-    // --device_parse true: the file as raw bytes, parsed on the device into the arrays the sketch reads in HBM
-    DeviceParseHooks hooks;
-    hooks.device = [&](const ffm_text_block &b) {
-      check_rc(ffm_engine_sketch_add_device(sk.s, static_cast<int32_t>(b.nnz), b.field, b.feat), "ffm_engine_sketch_add_device");
-    };
-    hooks.host = [&](const CsrPart &p) {
-      check_rc(ffm_engine_sketch_add(sk.s, static_cast<int32_t>(p.feat.size()), p.field.data(), p.feat.data(), 0), "ffm_engine_sketch_add");
-    };
-    hooks.sync = [&] { check_rc(ffm_engine_sketch_read(sk.s, nullptr, nullptr, nullptr), "ffm_engine_sketch_read"); };
-    rows = device_parse_pass(opt, hooks);
-  } else {
-    CountBlock cb;  // (no page-locked memory to be had: the sketch copies each block into its own)
-    CsrStream stream(opt.train_path, opt.file_type, opt.thread_num);
-    for (;;) {
-      const size_t got = stream.next(kCountRows, cb.blk, kCountNnz, true);
-      if (got == 0) break;
-      rows += got;
-      check_rc(ffm_engine_sketch_add(sk.s, static_cast<int32_t>(cb.blk.feat.size()), cb.blk.field.data(), cb.blk.feat.data(),
-                                     cb.pinned ? 1 : 0),
-               "ffm_engine_sketch_add");
-    }
-  }
+  CountPass pass;
+  pass.add_device = [&](int32_t nnz, const int32_t *field, const int32_t *feat, const float *) {
+    check_rc(ffm_engine_sketch_add_device(sk.s, nnz, field, feat), "ffm_engine_sketch_add_device");
+  };
+  pass.add = [&](int32_t nnz, const int32_t *field, const int32_t *feat, const float *, int zero_copy) {
+    check_rc(ffm_engine_sketch_add(sk.s, nnz, field, feat, zero_copy), "ffm_engine_sketch_add");
+  };
+  pass.sync = [&] { check_rc(ffm_engine_sketch_read(sk.s, nullptr, nullptr, nullptr), "ffm_engine_sketch_read"); };
+  const unsigned long long rows = count_pass(opt, pass);
   std::vector<uint8_t> reg(static_cast<size_t>(F) * FFM_SKETCH_REGS);
   int64_t n_valid = 0, n_bad = 0;
   check_rc(ffm_engine_sketch_read(sk.s, reg.data(), &n_valid, &n_bad), "ffm_engine_sketch_read");

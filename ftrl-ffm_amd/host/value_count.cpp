@@ -1,63 +1,34 @@
-// value_count.cpp -- --bucket_fields LIST: one pass over the training file before a model exists, as field_count.cpp
-// and rare_count.cpp make theirs.  The parser's threads fill a block whose field and val arrays are page-locked, the
-// device counts the (field, value bin) of its entries straight from there (the host does nothing per entry), and the
-// host cuts each chosen field's 65536 counts into buckets of equal mass (ffm_engine_bucket_edges: exact integers).
+// value_count.cpp -- --bucket_fields LIST: one pass over the training file before a model exists (count_pass.h).  The
+// device counts the (field, value bin) of the entries, and the host cuts each chosen field's 65536 counts into
+// buckets of equal mass (ffm_engine_bucket_edges: exact integers).
 #include <chrono>
 #include <cstdio>
 #include <stdexcept>
 
-#include "count_block.h"
-#include "text_stream.h"
+#include "count_pass.h"
 #include "value_buckets.h"
 
 namespace ftrl {
 
-namespace {
-
-void check_rc(int rc, const char *what) {
-  if (rc != FFM_OK) throw std::runtime_error(std::string(what) + ": " + ffm_engine_last_error());
-}
-
-struct HistHandle {
-  ffm_valhist *s = nullptr;
-  ~HistHandle() { ffm_engine_valhist_destroy(s); }
-};
-
-}  // namespace
-
 ValueBuckets count_value_buckets(const config_options &opt) {
   const auto t0 = std::chrono::steady_clock::now();
   const int F = opt.n_fields;
-  HistHandle vh;
+  CountHandle<ffm_valhist, ffm_engine_valhist_destroy> vh;
   {
     const int rc = ffm_engine_valhist_create(F, opt.device, &vh.s);
     if (rc == FFM_E_INVALID) throw std::invalid_argument(std::string("--bucket_fields: ") + ffm_engine_last_error());
     check_rc(rc, "ffm_engine_valhist_create");
   }
-  unsigned long long rows = 0;
-  if (opt.device_parse) {
-    // --device_parse true: the file as raw bytes, parsed on the device into the arrays the histogram reads in HBM
-    DeviceParseHooks hooks;
-    hooks.device = [&](const ffm_text_block &b) {
-      check_rc(ffm_engine_valhist_add_device(vh.s, static_cast<int32_t>(b.nnz), b.field, b.val), "ffm_engine_valhist_add_device");
-    };
-    hooks.host = [&](const CsrPart &p) {
-      check_rc(ffm_engine_valhist_add(vh.s, static_cast<int32_t>(p.val.size()), p.field.data(), p.val.data(), 0), "ffm_engine_valhist_add");
-    };
-    hooks.sync = [&] { check_rc(ffm_engine_valhist_read(vh.s, nullptr, nullptr, nullptr, nullptr), "ffm_engine_valhist_read"); };
-    rows = device_parse_pass(opt, hooks);
-  } else {
-    CountBlock cb(true);  // (no page-locked memory to be had: the histogram copies each block into its own)
-    CsrStream stream(opt.train_path, opt.file_type, opt.thread_num);
-    for (;;) {
-      const size_t got = stream.next(kCountRows, cb.blk, kCountNnz, true);
-      if (got == 0) break;
-      rows += got;
-      check_rc(ffm_engine_valhist_add(vh.s, static_cast<int32_t>(cb.blk.val.size()), cb.blk.field.data(), cb.blk.val.data(),
-                                      cb.pinned ? 1 : 0),
-               "ffm_engine_valhist_add");
-    }
-  }
+  CountPass pass;
+  pass.with_val = true;
+  pass.add_device = [&](int32_t nnz, const int32_t *field, const int32_t *, const float *val) {
+    check_rc(ffm_engine_valhist_add_device(vh.s, nnz, field, val), "ffm_engine_valhist_add_device");
+  };
+  pass.add = [&](int32_t nnz, const int32_t *field, const int32_t *, const float *val, int zero_copy) {
+    check_rc(ffm_engine_valhist_add(vh.s, nnz, field, val, zero_copy), "ffm_engine_valhist_add");
+  };
+  pass.sync = [&] { check_rc(ffm_engine_valhist_read(vh.s, nullptr, nullptr, nullptr, nullptr), "ffm_engine_valhist_read"); };
+  const unsigned long long rows = count_pass(opt, pass);
   std::vector<uint64_t> counts(static_cast<size_t>(F) * FFM_BUCKET_BINS);
   int64_t n_valid = 0, n_bad = 0, n_nan = 0;
   check_rc(ffm_engine_valhist_read(vh.s, counts.data(), &n_valid, &n_bad, &n_nan), "ffm_engine_valhist_read");

@@ -185,6 +185,30 @@ def test_halves_in_two_calls_and_any_way_of_feeding():
     ct.close()
 
 
+def test_pageable_call_longer_than_a_staging_chunk():
+    """A pageable call is staged in chunks of 2^22 entries; without a field array the second chunk's fields go on
+    where the first one's stopped (2^22 mod 7 = 2), with one both chunks' entries land where they belong."""
+    nnz, F, bits, cap = (1 << 22) + 7, 7, 22, 7
+    rng = np.random.default_rng(3)
+    feat = rng.integers(0, 1 << 20, size=nnz, dtype=np.int64).astype(np.int32)
+    feat[rng.integers(0, nnz, size=1000)] = -5
+    assert_same(gpu_counts(F, bits, cap, None, feat), rare_ref.np_counts(None, feat, F, bits, cap), "no field array")
+    field = ((np.arange(nnz, dtype=np.int64) * 5 + 3) % (F + 1)).astype(np.int32)  # (field 7 of 7: does not count)
+    assert_same(gpu_counts(F, bits, cap, field, feat), rare_ref.np_counts(field, feat, F, bits, cap), "with a field array")
+
+
+def test_pageable_call_of_three_staging_chunks():
+    """The third chunk goes into the first chunk's image, once the first launch has read it; its fields go on where
+    the second chunk's stopped (2^23 mod 7 = 4)."""
+    nnz, F, bits, cap = 2 * (1 << 22) + 5, 7, 22, 15
+    rng = np.random.default_rng(4)
+    feat = rng.integers(0, 1 << 20, size=nnz, dtype=np.int64).astype(np.int32)
+    feat[rng.integers(0, nnz, size=1000)] = -5
+    want = rare_ref.np_counts(None, feat, F, bits, cap)
+    assert np.unique(want[0]).size > 4 and want[2] > 0  # (the cap leaves the counts apart: a misplaced entry shows)
+    assert_same(gpu_counts(F, bits, cap, None, feat), want, "three chunks")
+
+
 def test_counter_arguments():
     lib = fa.load_library()
     for bad in ((4, 7, 3), (4, 31, 3), (4, 8, 0), (4, 8, 65536), (-1, 8, 3)):

@@ -165,6 +165,34 @@ def test_one_value_4096_times_and_keys_that_share_a_set():
         assert_same(gpu_hist(field, val, how), want, ("one set", how))
 
 
+def test_pageable_call_longer_than_a_staging_chunk():
+    """A pageable call is staged in chunks of 2^22 entries; without a field array the second chunk's fields go on
+    where the first one's stopped (2^22 mod 7 = 2), with one both chunks' entries land where they belong.  NaNs and
+    fields that do not count lie on both sides of the cut."""
+    nnz, n_fields, cut = (1 << 22) + 7, 7, 1 << 22
+    rng = np.random.default_rng(5)
+    val = rng.integers(1, 200, size=nnz).astype(f32)  # (a count column: few bins, so a field that is off by two shows)
+    val[cut:] = 2.0 ** np.arange(10, 17)  # (the second chunk's entries: a bin each)
+    val[[5, 1000, cut - 2, cut - 1, cut, cut + 3, nnz - 1]] = np.nan
+
+    def hist(field):
+        vh = fa.ValueHistogram(n_fields)
+        try:
+            vh.add(field, val)
+            got, want = vh.read(), bucket_ref.np_hist(field, val, n_fields)
+        finally:
+            vh.close()
+        assert got[1:] == want[1:], (got[1:], want[1:])
+        bad = np.argwhere(got[0] != want[0])
+        assert bad.size == 0, (len(bad), bad[:5].tolist())
+        return want
+
+    assert hist(None)[1:] == (nnz, 0, 7)
+    field = (np.arange(nnz, dtype=np.int64) * 5 + 3) % n_fields
+    field[[7, cut - 3, cut - 1, cut + 1, cut + 3, nnz - 2]] = [-1, n_fields, -1, n_fields, 9, -7]  # (cut - 1, cut + 3: NaNs too)
+    assert hist(field.astype(np.int32))[1:] == (nnz - 6, 6, 5)
+
+
 def test_histogram_arguments():
     lib = fa.load_library()
     for bad in (0, -1, 4097):
