@@ -40,7 +40,7 @@ def build(force=False, verbose=False):
 
 HOST = os.path.join(HERE, "host")
 HOST_SRCS = ["cmd_option.cpp", "parser.cpp", "reader.cpp", "ftrl_model.cpp", "trainer.cpp",
-             "persist.cpp", "serve_delta.cpp", "csr_reader.cpp", "csr_stream.cpp", "score_writer.cpp", "sample_weights.cpp", "field_ranges.cpp", "count_pass.cpp", "field_count.cpp", "importance.cpp",
+             "persist.cpp", "serve_delta.cpp", "csr_reader.cpp", "csr_stream.cpp", "score_writer.cpp", "sample_weights.cpp", "field_ranges.cpp", "count_pass.cpp", "field_count.cpp", "importance.cpp", "pair_mask.cpp",
              "rare_ids.cpp", "rare_count.cpp", "value_buckets.cpp", "value_count.cpp", "text_stream.cpp", "row_stream.cpp"]
 MAIN_BIN = os.path.join(HOST, "ftrl_ffm_main")
 TEST_BIN = os.path.join(HOST, "host_tests")

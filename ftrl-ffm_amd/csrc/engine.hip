@@ -53,6 +53,7 @@
 #include "kernels_delta.h"
 #include "kernels_ablate.h"
 #include "kernels_ablate_pairs.h"
+#include "kernels_mask.h"
 #include "kernels_stage.h"
 #include "kernels_sketch.h"
 #include "kernels_idcount.h"
@@ -453,6 +454,11 @@ struct ffm_engine {
     double *loss = nullptr, *sums = nullptr, *part = nullptr;
     unsigned long long *hist = nullptr;
   } abl, pabl;
+  // ffm_engine_set_pair_mask (include/ffm_engine.h "Pair masks", engine_mask.h): the words in HBM (made by the first
+  // call that sets a mask) and their copy on the host; pair_mask_on == false: no mask, and nothing here is read
+  bool pair_mask_on = false;
+  unsigned long long *d_pair_mask = nullptr;  // [kMaskFields]
+  uint64_t pair_mask[ftrl_dev::kMaskFields] = {};
   std::vector<void *> allocs;
   // split-phase bookkeeping
   Rows pending{};
@@ -648,6 +654,12 @@ static int serve_refuse(const char *what) {
   return fail(FFM_E_UNSUPPORTED, std::string("a serving engine holds no accumulators: ") + what + " needs a training engine");
 }
 #define SERVE_REFUSE(e, what) do { if ((e) && serving(e)) return serve_refuse(what); } while (0)
+// An engine with a pair mask (engine_mask.h) predicts rows and nothing else: whatever would run unmasked is refused.
+static int mask_refuse(const char *what) {
+  return fail(FFM_E_INVALID, std::string(what) + " is not available while a pair mask is set (ffm_engine_set_pair_mask "
+                                                 "with keep == NULL clears it): it would run without the mask");
+}
+#define MASK_REFUSE(e, what) do { if ((e) && (e)->pair_mask_on) return mask_refuse(what); } while (0)
 
 #define LAUNCH_ON(e, st, kid, kernel, grid, block, shmem, ...)                   \
   do {                                                                           \
@@ -870,6 +882,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_text.h"
 #include "engine_rows.h"
 #include "engine_ablate.h"
+#include "engine_mask.h"
 }  // extern "C"
 
 #include "engine_group.h"

@@ -145,8 +145,7 @@ static int ablate_core(const AblateKind &k, ffm_engine *e, const Rows &rows, int
 
 static int ablate_ready(const AblateKind &k, ffm_engine *e) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
-  if (!(e->*k.set).on) return fail(FFM_E_INVALID, std::string(k.noun) + " is off (ffm_engine_" + k.prefix + "_enable)");
-  return FFM_OK;
+  if (!(e->*k.set).on) return fail(FFM_E_INVALID, std::string(k.noun) + " is off (ffm_engine_" + k.prefix + "_enable)");  return FFM_OK;
 }
 
 static int ablate_predict_device(const AblateKind &k, ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
@@ -154,6 +153,7 @@ static int ablate_predict_device(const AblateKind &k, ffm_engine *e, int32_t n_r
                                  int32_t output_prob, float *out, double *loss_sum_out) {
   int rc = ablate_ready(k, e);
   if (rc) return rc;
+  MASK_REFUSE(e, k.noun);  // (its variants are the whole model's: include/ffm_engine.h "Pair masks")
   if ((rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val))) return rc;
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   return ablate_core(k, e, Rows{n_rows, nnz, row_ptr, field, feat, val, label}, 0, output_prob, out, loss_sum_out);
@@ -164,6 +164,7 @@ static int ablate_predict(const AblateKind &k, ffm_engine *e, int32_t n_rows, co
                           double *loss_sum_out) {
   int rc = ablate_ready(k, e);
   if (rc) return rc;
+  MASK_REFUSE(e, k.noun);  // (its variants are the whole model's: include/ffm_engine.h "Pair masks")
   Rows dev{};
   int row_cap = 0;
   if ((rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &dev, &row_cap))) return rc;

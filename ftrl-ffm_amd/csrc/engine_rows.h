@@ -254,6 +254,7 @@ static int validate_resident_block(ffm_engine *e, const ffm_rows_block *blk, Row
 
 int ffm_engine_stage_batch_resident(ffm_engine *e, ffm_rows_block *blk) {
   SERVE_REFUSE(e, "training");
+  MASK_REFUSE(e, "training");
   Rows dev{};
   int rc = validate_resident_block(e, blk, &dev, false);
   if (rc) return rc;

@@ -106,6 +106,16 @@ inline RowWaveFn row_wave_fn(int fmt, int n_factors) {
     default: return nullptr;
   }
 }
+// prediction under a pair mask (kernels_mask.h): ffm_row_wave_kernel's arguments, then the mask words in HBM
+using RowMaskFn = void (*)(ModelDev, Rows, Scratch, int, int, float *, int, const unsigned long long *);
+inline RowMaskFn row_mask_fn(int fmt, int n_factors) {
+  switch (n_factors) {
+#define X(K, LPP, VPL, U) case K: return FFM_BY_ANY_FMT(ffm_row_mask_kernel, LPP, VPL, U);
+    FFM_LANE_SHAPES(X)
+#undef X
+    default: return nullptr;
+  }
+}
 inline ServeContextFn serve_context_fn(int fmt, int n_factors) {
   switch (n_factors) {
 #define X(K, LPP, VPL, U) case K: return FFM_BY_FMT(serve_context_kernel, LPP, VPL, U);

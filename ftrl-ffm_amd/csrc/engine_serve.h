@@ -28,6 +28,7 @@ static int cand_common_check(ffm_engine *e, int32_t n_req, int32_t n_cand) {
   if (!serving(e))
     return fail(FFM_E_UNSUPPORTED, "score_candidates needs a serving engine (FFM_FLAG_SERVE_F32 / _F16): "
                                    "ffm_engine_pack_weights copies a training engine's weights into one");
+  MASK_REFUSE(e, "score_candidates");
   if (e->norm_rows_on)
     return fail(FFM_E_INVALID, "score_candidates is not available on an engine with FFM_FLAG_NORM_ROWS: the shared context "
                                "terms would need a scale per candidate");

@@ -305,6 +305,7 @@ int ffm_engine_stage_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
                                     const int32_t *field, const int32_t *feat, const float *val,
                                     const int32_t *label, const float *weight, int32_t zero_copy) {
   SERVE_REFUSE(e, "training");  // (staging is training's: prediction stages through predict_batch_async)
+  MASK_REFUSE(e, "training");
   int32_t nnz = 0;
   int longest = 1;
   int rc = validate_host_block(e, n_rows, row_ptr, &field, feat, val, &nnz, &longest, true);
@@ -345,6 +346,7 @@ int64_t ffm_engine_blocks_scored(ffm_engine *e) {
 static int forward_staged(ffm_engine *e, float *partial_logit, ForwardOpts opts) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
   SERVE_REFUSE(e, "training");
+  MASK_REFUSE(e, "training");
   if (e->n_staged == 0) return fail(FFM_E_INVALID, "no staged block");
   if (e->has_pending) return fail(FFM_E_INVALID, "the previous block still awaits train_update");
   const int slot = e->staged[0];

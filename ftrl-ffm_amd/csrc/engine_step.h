@@ -44,6 +44,15 @@ static bool launch_row_waves(ffm_engine *e, const Rows &rows, int row_cap, float
   return true;
 }
 
+// An engine with a pair mask (engine_mask.h: set admitted only what this kernel serves) predicts every row through
+// ffm_row_mask_kernel; a row beyond what a wave stages is flagged there, on a training engine too.
+static void launch_row_mask(ffm_engine *e, const Rows &rows, int row_cap, float *out, int output_prob) {
+  const ModelDev &m = e->m;
+  const int lds_cap = std::min(row_cap, kPredLdsCap);
+  LAUNCH(e, serving(e) ? K_SERVE_ROW : K_PREDICT_ROW, row_mask_fn(m.lat_fmt, m.n_factors), cdiv(rows.n_rows, kPredRows),
+         64 * kPredRows, mask_lds_bytes(lds_cap), m, rows, e->sc[e->cur], row_cap, lds_cap, out, output_prob, e->d_pair_mask);
+}
+
 // row_cap: the longest row of the block where the caller knows it (rows that came in host memory), 0 = unknown
 // (device callers: max_row_nnz).  The row kernels size their LDS by it, which decides how many rows a CU holds.
 // weight: the block's sample weights (device) or null; only the launches that produce tmp_grad
@@ -52,6 +61,10 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, int row_cap, bool
                               const float *weight = nullptr) {
   if (row_cap <= 0) row_cap = e->max_row_nnz;
   if (rows.n_rows == 0) return;
+  if (!train && e->pair_mask_on) {  // (training is refused while a mask is set) -- the masked kernel and nothing else
+    launch_row_mask(e, rows, row_cap, out, output_prob);
+    return;
+  }
   if (serving(e)) {  // (predict only: every training entry point is refused) -- its own kernel and nothing else
     launch_row_waves(e, rows, row_cap, out, output_prob);
     return;
@@ -238,6 +251,7 @@ static int prepare_submit(ffm_engine *e, const PrepPlan &pl, bool timed) {
 int ffm_engine_prepare_device(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
                               const int32_t *field, const int32_t *feat, const float *val) {
   SERVE_REFUSE(e, "ffm_engine_prepare_device");
+  MASK_REFUSE(e, "training");
   int rc = check_block(e, n_rows, nnz, row_ptr, field, feat, val);
   if (rc) return rc;
   if ((rc = e->drain())) return rc;  // (staged blocks' submissions come first on the prep stream)
@@ -258,6 +272,7 @@ static int train_forward_core(ffm_engine *e, const Rows &rows, const float *weig
                               const ForwardOpts &opts) {
   ScopedTimer tm_fwd("train:forward");
   SERVE_REFUSE(e, "training");
+  MASK_REFUSE(e, "training");
   const int32_t n_rows = rows.n_rows;
   int rc = check_block(e, n_rows, rows.nnz, rows.row_ptr, rows.field, rows.feat, rows.val);
   if (rc) return rc;
@@ -318,6 +333,7 @@ int ffm_engine_train_update_device(ffm_engine *e, const float *logit, float *log
                                    double *loss_sum_out) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
   SERVE_REFUSE(e, "training");
+  MASK_REFUSE(e, "training");
   if (!e->has_pending) return fail(FFM_E_INVALID, "train_update without a preceding train_forward");
   ScopedTimer tm_upd("train:update");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
@@ -662,6 +678,7 @@ int ffm_engine_train_batch_weighted(ffm_engine *e, int32_t n_rows, const int32_t
                                     const int32_t *label, const float *weight, float *logit_out,
                                     double *loss_sum_out) {
   SERVE_REFUSE(e, "training");  // (before anything of the block is copied)
+  MASK_REFUSE(e, "training");
   Rows dev{};
   int row_cap = 0;
   int rc = stage_block(e, n_rows, row_ptr, field, feat, val, label, &dev, &row_cap, weight);

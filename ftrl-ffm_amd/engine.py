@@ -281,6 +281,9 @@ ABI = [
     ("ffm_engine_predict_pair_ablated_device", ctypes.c_int,
      [_vp, ctypes.c_int32, ctypes.c_int32] + _DCSR + [ctypes.c_int32, _vp, _vp]),
     ("ffm_engine_pair_ablation_read", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(Metrics)]),
+    # predict with the kept field pairs only (include/ffm_engine.h "Pair masks")
+    ("ffm_engine_set_pair_mask", ctypes.c_int, [_vp, _vp, ctypes.c_int32]),
+    ("ffm_engine_get_pair_mask", ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_int32)]),
     # sync a serving engine, publish only what moved (include/ffm_engine.h "Serving deltas")
     ("ffm_engine_sync_weights", ctypes.c_int, [_vp, _vp, ctypes.POINTER(SyncStats)]),
     ("ffm_engine_sync_moved", ctypes.c_int, [_vp, _i32p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
@@ -708,6 +711,62 @@ def drop_pair_weights(vec_w, ids_of_field_f, g):
     ids = np.asarray(ids_of_field_f, np.int64).reshape(-1)
     w[ids, int(g), :] = np.float32(0.0)
     return w
+
+
+def pair_mask(n_fields, kept_pairs):
+    """keep[n_fields] (uint64) of a pair mask (include/ffm_engine.h "Pair masks") from the kept pairs (f, g), each in
+    either order, (f, f) the diagonal: bit g of keep[f] and bit f of keep[g] -- symmetric by construction."""
+    n_fields = int(n_fields)
+    if n_fields < 1 or n_fields > 64:
+        raise ValueError("a pair mask is for 1 .. 64 fields, got n_fields = %d" % n_fields)
+    words = [0] * n_fields
+    for f, g in kept_pairs:
+        f, g = int(f), int(g)
+        if f < 0 or g < 0 or f >= n_fields or g >= n_fields:
+            raise ValueError("pair (%d, %d) names a field outside [0, %d)" % (f, g, n_fields))
+        words[f] |= 1 << g
+        words[g] |= 1 << f
+    return np.array(words, np.uint64)
+
+
+def pair_mask_pairs(words):
+    """The kept pairs of a mask, sorted (f, g) with f <= g: pair_mask's inverse.  An asymmetric mask or a bit at or
+    above the number of words is a ValueError."""
+    w = [int(x) for x in np.asarray(words, np.uint64).reshape(-1)]
+    n = len(w)
+    if n < 1 or n > 64:
+        raise ValueError("a pair mask is for 1 .. 64 fields, got %d words" % n)
+    pairs = []
+    for f in range(n):
+        if w[f] >> n:
+            raise ValueError("keep[%d] has a bit at or above n_fields = %d" % (f, n))
+        for g in range(n):
+            if (w[f] >> g) & 1 != (w[g] >> f) & 1:
+                raise ValueError("the mask is not symmetric in (%d, %d)" % (f, g))
+            if g >= f and (w[f] >> g) & 1:
+                pairs.append((f, g))
+    return pairs
+
+
+def pair_mask_top(n_fields, loss, n_keep):
+    """The mask of the n_keep pairs whose removal costs most.  loss[V + 1] as predict_pair_ablated sums it (V =
+    pair_count(n_fields)): loss[v] the loss without pair v, loss[V] the loss of the rows.  The pairs are ranked by
+    delta = loss[v] - loss[V], largest first, ties to the lower pair index; the first n_keep are kept (0 <= n_keep
+    <= V).  A delta that is not finite is a ValueError: "pair mask: loss without pair f g is not finite"."""
+    V = pair_count(n_fields)
+    loss = np.asarray(loss, np.float64).reshape(-1)
+    if loss.shape[0] != V + 1:
+        raise ValueError("loss: one sum per pair and the rows' own, %d in all, got %d" % (V + 1, loss.shape[0]))
+    n_keep = int(n_keep)
+    if n_keep < 0 or n_keep > V:
+        raise ValueError("n_keep must lie in [0, %d], got %d" % (V, n_keep))
+    with np.errstate(invalid="ignore", over="ignore"):
+        delta = loss[:V] - loss[V]
+    bad = np.flatnonzero(~np.isfinite(delta))
+    if bad.size:
+        raise ValueError("pair mask: loss without pair %d %d is not finite" % pair_fields(n_fields, int(bad[0])))
+    order = sorted(range(V), key=lambda v: -delta[v])  # (stable: ties stay in index order)
+    return pair_mask(n_fields, [pair_fields(n_fields, v) for v in sorted(order[:n_keep])])
 
 
 def spell_out_candidates(ctx, cand_req_ptr, cand):
@@ -1424,6 +1483,27 @@ class Engine:
         m = (Metrics * (self.n_fields * (self.n_fields + 1) // 2 + 1))()
         self._check(self.lib.ffm_engine_pair_ablation_read(self.h, int(bool(reset)), m))
         return [x.as_dict() for x in m]
+
+    # ---- pair masks (include/ffm_engine.h "Pair masks") ----
+    def set_pair_mask(self, keep=None):
+        """Every row prediction from now on leaves out the pair terms whose fields' bit is clear.  keep: the words
+        (uint64[n_fields], as pair_mask returns them) or an iterable of kept pairs (f, g); None clears the mask.
+        While a mask is set, training, score_candidates and the ablation predictions are refused."""
+        if keep is None:
+            self._check(self.lib.ffm_engine_set_pair_mask(self.h, None, 0))
+            return
+        if isinstance(keep, np.ndarray) and keep.ndim == 1 and keep.dtype.kind in "ui":
+            words = np.ascontiguousarray(keep, np.uint64)
+        else:
+            words = pair_mask(self.n_fields, keep)
+        self._check(self.lib.ffm_engine_set_pair_mask(self.h, words.ctypes.data_as(_vp), int(words.shape[0])))
+
+    def pair_mask(self):
+        """The words of the mask in force (uint64[n_fields]), or None without one."""
+        words = np.zeros(max(1, self.n_fields), np.uint64)
+        is_set = ctypes.c_int32(0)
+        self._check(self.lib.ffm_engine_get_pair_mask(self.h, words.ctypes.data_as(_vp), ctypes.byref(is_set)))
+        return words[:self.n_fields] if is_set.value else None
 
     # ---- the grouped AUC (include/ffm_engine.h "Metrics", keyed capture) ----
     def metrics_key_field(self, field, capacity_rows=1 << 24, eval=True, train=False):

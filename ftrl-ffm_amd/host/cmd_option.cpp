@@ -128,6 +128,17 @@ const std::string_view cmd_help =
     "              per pair on the device (13 GB at 39 fields, 35 GB at 64; printed before it is allocated).  Reads through\n"
     "              the host parser.  Needs --eval_data; FFM only, one GPU, --n_fields <= 64, --n_factors 4, 8, 16, 32 or\n"
     "              64, rows of at most 128 entries.  Nothing else of the output changes\tdefault:false\n"
+    "--pair_keep <N> --pair_mask_out <file>: with --pair_importance true: rank all V pairs by delta = loss without the pair\n"
+    "              minus loss of the rows (largest first, ties to the lower pair index), keep the first N (0 <= N <= V) and\n"
+    "              write them as a mask file: `ffm-pair-mask 1 <n_fields> <n_kept>`, then one `f g` line per kept pair.\n"
+    "              Prints `pair mask: kept N of V pairs, smallest kept delta D -> FILE`; a delta that is not finite ends the\n"
+    "              run.  Both flags go together\tdefault:(none)\n"
+    "--pair_mask <@file>: a run that trains nothing (--n_epochs 0 with --resume_from ck, --serve_weights or not, or with\n"
+    "              --apply_deltas) predicts with the file's pairs only: the terms of every other pair are left out, and\n"
+    "              their gathers are not made.  --eval_data, --metrics auc, --auc_key_field, --predict_data / --predict_out\n"
+    "              and --device_rows true then give the masked model's numbers.  Prints `pair mask: K of V pairs kept, from\n"
+    "              FILE`.  FFM only, one GPU, --n_fields <= 64, --n_factors 4, 8, 16, 32 or 64; not with --n_epochs > 0,\n"
+    "              --field_importance, --pair_importance or --cmd true\tdefault:(none)\n"
     "--publish_path <prefix>: after every epoch's training (after that epoch's --refresh_weights refresh when it is on,\n"
     "              before its evaluation) write <prefix>.<epochs_done>.delta: the features whose serving bits moved since\n"
     "              the previous delta, in a serving engine's own format -- delta 1 is relative to a fresh serving engine of\n"
@@ -275,6 +286,16 @@ void config_options::parse_option(int argc, char *argv[]) {
     else if (k == "--compact_rows") compact_rows = assign_bool(v);
     else if (k == "--field_importance") field_importance = assign_bool(v);
     else if (k == "--pair_importance") pair_importance = assign_bool(v);
+    else if (k == "--pair_keep") {
+      long long x = -1;
+      size_t used = 0;
+      try { x = std::stoll(v, &used); } catch (const std::exception &) { used = 0; }
+      if (used != v.size() || used == 0 || x < 0 || x > 2080)
+        throw std::invalid_argument("--pair_keep takes a number of pairs in [0, 2080], got `" + v + "`");
+      pair_keep = static_cast<int>(x);
+    }
+    else if (k == "--pair_mask_out") pair_mask_out = v;
+    else if (k == "--pair_mask") pair_mask = v;
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
     else if (k == "--field_ranges") field_ranges = v;
     else if (k == "--field_ranges_out") field_ranges_out = v;
@@ -532,6 +553,31 @@ void config_options::parse_option(int argc, char *argv[]) {
   if (field_importance) check_importance("--field_importance true ", "fields", "keeps one lane of a 64-lane wave per field");
   if (pair_importance)
     check_importance("--pair_importance true ", "field pairs", "keeps the pairs of at most 64 fields in the registers of a 64-lane wave");
+  // --pair_keep N --pair_mask_out FILE: the pair importance pass's answer as a mask file (refused here, before a device is opened)
+  if (pair_keep >= 0 || !pair_mask_out.empty()) {
+    if (pair_keep < 0) throw std::invalid_argument("--pair_mask_out writes the pairs --pair_keep N selects: it needs --pair_keep");
+    if (pair_mask_out.empty()) throw std::invalid_argument("--pair_keep selects the pairs --pair_mask_out FILE writes: it needs --pair_mask_out");
+    if (!pair_importance)
+      throw std::invalid_argument("--pair_keep " + std::to_string(pair_keep) + " ranks the pairs by the pair importance pass: it needs --pair_importance true");
+    const int V = n_fields * (n_fields + 1) / 2;
+    if (pair_keep > V)
+      throw std::invalid_argument("--pair_keep " + std::to_string(pair_keep) + " is more than the " + std::to_string(V) + " pairs of --n_fields " + std::to_string(n_fields));
+  }
+  // --pair_mask @FILE: one whole FFM model that trains nothing predicts with the kept pairs (refused here, before a device is opened)
+  if (!pair_mask.empty()) {
+    const std::string what = "--pair_mask " + pair_mask + " ";
+    if (pair_mask[0] != '@' || pair_mask.size() == 1)
+      throw std::invalid_argument("--pair_mask takes @FILE, the mask --pair_mask_out wrote, got `" + pair_mask + "`");
+    if (epoch > 0) throw std::invalid_argument(what + "masks prediction, not training: it needs --n_epochs 0 (got --n_epochs " + std::to_string(epoch) + ")");
+    if (field_importance) throw std::invalid_argument(what + "is not allowed with --field_importance true: the variants are the whole model's");
+    if (pair_importance) throw std::invalid_argument(what + "is not allowed with --pair_importance true: the variants are the whole model's");
+    if (n_gpus > 1) throw std::invalid_argument(what + "masks one whole model on one GPU: --n_gpus > 1 is not allowed with it");
+    if (model_type != "FFM") throw std::invalid_argument(what + "names field pairs, which only FFM rows have (got --model_type " + model_type + ")");
+    if (cmd) throw std::invalid_argument(what + "scores files: --cmd true is not allowed with it");
+    if (n_fields > 64) throw std::invalid_argument(what + "keeps a field's partners in one 64-bit word: --n_fields is " + std::to_string(n_fields) + ", at most 64");
+    if (n_factors != 4 && n_factors != 8 && n_factors != 16 && n_factors != 32 && n_factors != 64)
+      throw std::invalid_argument(what + "runs the one-wave-per-row kernel: --n_factors must be 4, 8, 16, 32 or 64 (got " + std::to_string(n_factors) + ")");
+  }
   // (--n_epochs 0 with a file to score needs no training file: the format is then the scored file's)
   file_type = detect_file_type(train_path.empty() && epoch == 0 && !predict_path.empty() ? predict_path : train_path);
   if (model_type == "FFM" && file_type != "libffm") {

@@ -70,6 +70,11 @@ struct config_options {
   // --pair_importance true: the same for every field pair -- the model without the interaction of fields f and g,
   // all n_fields (n_fields + 1) / 2 of them from one more pass (include/ffm_engine.h "Pair ablation", importance.h)
   bool pair_importance = false;
+  // --pair_keep N --pair_mask_out FILE (with --pair_importance true): the N pairs whose removal costs most, written as a
+  // mask file (pair_mask.h); -1 = not asked for.  --pair_mask @FILE (a run that trains nothing): the loaded model
+  // predicts with the file's pairs only (include/ffm_engine.h "Pair masks")
+  int pair_keep = -1;
+  std::string pair_mask_out, pair_mask;
   // --publish_path PREFIX [--publish_weights f32|f16]: after every epoch's training (and refresh) a serving delta
   // PREFIX.<epochs_done>.delta -- what a shadow serving engine had to move to follow the model (serve_delta.h)
   std::string publish_path, publish_weights = "f32";

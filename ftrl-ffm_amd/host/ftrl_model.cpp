@@ -437,6 +437,13 @@ void FtrlModel::enable_ablation(Ablation kind, bool with_auc) {
   else check(ffm_engine_ablation_enable(eng_, with_auc ? 1 : 0), "ffm_engine_ablation_enable");
 }
 
+void FtrlModel::set_pair_mask(const std::vector<uint64_t> &keep) {
+  if (grp_) throw std::invalid_argument("a pair mask: one GPU only");
+  const int rc = ffm_engine_set_pair_mask(eng_, keep.data(), static_cast<int32_t>(keep.size()));
+  if (rc == FFM_E_INVALID || rc == FFM_E_UNSUPPORTED) throw std::invalid_argument(std::string("pair mask: ") + ffm_engine_last_error());
+  check(rc, "ffm_engine_set_pair_mask");
+}
+
 void FtrlModel::predict_ablated_block(Ablation kind, const CsrBlock &blk, std::vector<double> &loss_sums) {
   if (grp_) throw std::invalid_argument(ablation_noun(kind) + ": one GPU only");
   const bool pairs = kind == Ablation::Pairs;

@@ -175,6 +175,10 @@ class FtrlModel {
   void enable_ablation(Ablation kind, bool with_auc);
   void predict_ablated_block(Ablation kind, const CsrBlock &blk, std::vector<double> &loss_sums);
   std::vector<ffm_metrics> read_ablation_metrics(Ablation kind, bool reset);
+  // Pair mask (include/ffm_engine.h "Pair masks"; pair_mask.h makes the words): from now on every prediction of this
+  // model leaves out the terms of the pairs whose bit is clear, and training is refused.  keep[n_fields]; one FFM
+  // engine only (throws std::invalid_argument otherwise, with the engine's reason).
+  void set_pair_mask(const std::vector<uint64_t> &keep);
 
   // Model files in the reference's formats (ffm.cpp:138-200, lr.cpp:26-39); available for every
   // model type here (the reference has none for FM).  save_state/load_state add the FTRL

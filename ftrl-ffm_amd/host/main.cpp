@@ -59,11 +59,14 @@ int main(int argc, char *argv[]) {
         behind.epochs_done = applied;
         task.restore(behind);
       }
+      // --pair_mask @FILE: once, on the model as loaded (the run trains nothing: cmd_option refused --n_epochs > 0)
+      if (!opt.pair_mask.empty()) ftrl::load_pair_mask(opt, *task.model_ptr);
       task.train();
       // --auc_key_field on a run that trains nothing (--resume_from ck --n_epochs 0 --eval_data F): one evaluation pass
       // of the loaded model, numbered by the epochs it has behind it -- there is no epoch to print the line after
       // (--field_importance asks for the same one pass: its lines follow an evaluation)
-      if ((opt.auc_key_field >= 0 || opt.field_importance || opt.pair_importance) && opt.epoch <= 0 && !opt.cmd && !opt.eval_path.empty())
+      // (--pair_mask: the masked model's evaluation is what the run is for)
+      if ((opt.auc_key_field >= 0 || opt.field_importance || opt.pair_importance || !opt.pair_mask.empty()) && opt.epoch <= 0 && !opt.cmd && !opt.eval_path.empty())
         task.evaluate(static_cast<int>(task.progress().epochs_done));
       task.model_ptr->print_norm_rows();  // (--normalize_rows: one line, after the last epoch or that one evaluation)
       // --field_importance: after the last evaluation, the same model without each field (importance.h);

@@ -13,6 +13,7 @@
 #include <thread>
 
 #include "importance.h"
+#include "pair_mask.h"
 #include "score_writer.h"
 
 namespace ftrl {
@@ -65,6 +66,21 @@ void run_importance(const config_options &opt, FtrlModel &m, FtrlModel::Ablation
   std::vector<ffm_metrics> auc;
   if (want_auc) auc = m.read_ablation_metrics(kind, true);
   (pairs ? print_pair_importance : print_field_importance)(stdout, opt.n_fields, rows, loss, want_auc ? &auc : nullptr);
+  // --pair_keep N --pair_mask_out FILE: the pass's answer as a mask file (pair_mask.h: the rule and the format)
+  if (pairs && opt.pair_keep >= 0) {
+    double smallest = 0.0;
+    const PairList kept = select_pairs(opt.n_fields, loss, opt.pair_keep, &smallest);
+    write_pair_mask(opt.pair_mask_out, opt.n_fields, kept);
+    std::printf("pair mask: kept %zu of %d pairs, smallest kept delta %+.6lf -> %s\n", kept.size(), pair_count(opt.n_fields),
+                smallest / (rows ? static_cast<double>(rows) : 1.0), opt.pair_mask_out.c_str());
+  }
+}
+
+void load_pair_mask(const config_options &opt, FtrlModel &m) {
+  const std::string file = opt.pair_mask.substr(1);  // (@FILE: cmd_option checked the form)
+  const PairList kept = read_pair_mask(file, opt.n_fields);
+  m.set_pair_mask(pair_mask_words(opt.n_fields, kept));
+  std::printf("pair mask: %zu of %d pairs kept, from %s\n", kept.size(), pair_count(opt.n_fields), file.c_str());
 }
 
 void publish_and_print(FtrlModel &m, const std::string &prefix, const std::string &fmt, long long epoch, long long n_feats) {

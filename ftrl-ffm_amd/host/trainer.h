@@ -133,7 +133,12 @@ void refresh_and_print(FtrlModel &m, long long epoch);
 // FtrlModel::predict_ablated_block (the host parser's blocks, the synchronous call, loss sums added in block order)
 // and the kind's lines of importance.h; for the pairs with --metrics auc the histograms' memory is printed before
 // FtrlModel::enable_ablation allocates it.
+// With --pair_keep N --pair_mask_out FILE the pairs' pass then ranks them (pair_mask.h), writes the mask file and
+// prints `pair mask: kept N of V pairs, smallest kept delta D -> FILE` (D per row, as the pairs' lines print it).
 void run_importance(const config_options &opt, FtrlModel &m, FtrlModel::Ablation kind);
+// --pair_mask @FILE: reads the file against the run's --n_fields, sets the mask on the loaded model
+// (FtrlModel::set_pair_mask) and prints `pair mask: K of V pairs kept, from FILE`.
+void load_pair_mask(const config_options &opt, FtrlModel &m);
 // --publish_path: FtrlModel::publish_delta(prefix, fmt, epoch) and its line,
 // `epoch N published: M of F features moved, B bytes -> FILE`
 void publish_and_print(FtrlModel &m, const std::string &prefix, const std::string &fmt, long long epoch, long long n_feats);

@@ -1163,8 +1163,9 @@ int ffm_engine_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out /* [
  * ablation.  An engine that never enables pair ablation allocates nothing, launches nothing and changes in
  * nothing; the section adds functions only: no struct, no existing kernel, launch or argument list changed, and
  * FFM_ENGINE_ABI_VERSION is what it was.
- * OUT OF SCOPE  pair masks or pruned tables on the prediction and serving kernels; pair variants of
- *   ffm_engine_score_candidates; groups, shards, LR and FM; a pipelined or staged form. */
+ * Acting on the answer -- predicting without the pairs that carry nothing -- is "Pair masks" below.
+ * OUT OF SCOPE  pair variants of ffm_engine_score_candidates; groups, shards, LR and FM; a pipelined or staged
+ *   form. */
 int32_t ffm_engine_pair_count(int32_t n_fields);
 int32_t ffm_engine_pair_index(int32_t n_fields, int32_t f, int32_t g);
 int ffm_engine_pair_fields(int32_t n_fields, int32_t v, int32_t *f, int32_t *g);
@@ -1177,6 +1178,54 @@ int ffm_engine_predict_pair_ablated_device(ffm_engine *e, int32_t n_rows, int32_
                                            const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
                                            int32_t output_prob, float *out, double *loss_sum_out);
 int ffm_engine_pair_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out /* [V + 1] */);
+
+/* ---- Pair masks: predict with the kept field pairs only ----------------------------------------------------
+ * Pair ablation says which pairs carry the model; a mask acts on it.  A prediction row is its pair gathers (39
+ * fields: 741 pairs x two 64-byte slots), and under a mask the pairs left out are gathers not made: the masked
+ * kernel's loads, dots and ordered-sum steps are those of the kept pairs.
+ * DEFINITION  keep[n_fields], one uint64_t per field, n_fields <= 64.  Bit g of keep[f]: "the terms between an
+ *   entry of field f and an entry of field g are part of the prediction".  The mask is symmetric (bit g of keep[f]
+ *   equals bit f of keep[g]); bit f of keep[f] is the diagonal, two entries of one field; bits at or above
+ *   n_fields are zero.  The masked prediction of a row is ffm_engine_predict_batch's ordered sum -- the bias, the
+ *   survivors' linear products in row order, then the kept pair terms in predict_batch's pair order (a outer, b
+ *   inner), every addition sequential -- with every pair term whose two surviving entries' fields (f, g) have the
+ *   bit clear LEFT OUT (not added as zero).  Linear terms always stay.  remove_out_range, rows without values,
+ *   hashed ids, the rare fold, buckets and FFM_FLAG_NORM_ROWS act exactly as they do without a mask, before it: the
+ *   norm is not recomputed for the pairs that go.
+ *   all bits set      is ffm_engine_predict_batch, bit for bit.
+ *   one pair dropped  is variant (f, g) of "Pair ablation", bit for bit, on any block.
+ *   as weights        under the two conditions of "Pair ablation" (one field per id in the block, a bias other than
+ *                     -0.0f) it is predict_batch on the model with the slot towards g zeroed for field f's ids, for
+ *                     every dropped pair (f, g) in both directions.
+ * ffm_engine_set_pair_mask  keep == NULL clears the mask.  Otherwise the words are copied to the device, ordered on
+ *   the engine's stream; a deferred evaluation block (ffm_engine_predict_batch_async) is launched first, as by every
+ *   entry point that queues work, so blocks queued earlier are scored under the earlier mask and later ones under
+ *   the new one.  Nothing of the caller's is read after the call returns.
+ *   FFM_E_UNSUPPORTED, with a message that says why: LR and FM; n_shards > 1; a group's engine; compact storage;
+ *   n_factors outside {4, 8, 16, 32, 64}; n_fields > 64; a training engine created with FFM_PREDICT_WAVE=0.
+ *   FFM_E_INVALID, leaving the previous mask in force: n_fields other than the engine's; an asymmetric mask; a bit
+ *   at or above n_fields; staged training blocks still waiting.
+ * ffm_engine_get_pair_mask  *is_set is 1 or 0; keep_out[n_fields] (may be NULL) the words in force, zeros without.
+ * WHERE IT APPLIES  every row-prediction entry point of an engine with a mask launches the masked kernel:
+ *   ffm_engine_predict_batch, _predict_batch_device, _predict_batch_async[_scores] (zero_copy 0 and 1) and
+ *   _predict_batch_async_resident, on training engines and on FFM_FLAG_SERVE_F32 / _F16 engines.  What they feed
+ *   sees masked scores because it reads those outputs: the loss sums, FFM_METRIC_EVAL, keyed capture on the eval
+ *   channel, streamed scores.
+ * rows too long  a row longer than max_row_nnz, or than the 128 entries a wave stages, is NaN and reported as
+ *   FFM_E_CAPACITY -- on a training engine too: a masked engine launches no other row kernel.
+ * WHILE A MASK IS SET  FFM_E_INVALID, before anything is queued, model and state unchanged: every training entry
+ *   point, ffm_engine_score_candidates[_device], ffm_engine_predict_ablated* and ffm_engine_predict_pair_ablated*.
+ *   Masked training and masked candidates are different features; refusing keeps anything from silently running
+ *   unmasked.
+ * The mask is not part of the model: weights and state in and out, ffm_engine_pack_weights, _sync_weights, deltas,
+ * _refresh_weights and checkpoints neither read nor record it, exactly as they do not record field ranges.  An
+ * engine that never sets a mask allocates nothing, launches the kernels it launched before with the arguments it
+ * passed before; the section adds functions only, and FFM_ENGINE_ABI_VERSION is what it was.
+ * OUT OF SCOPE  pruned or re-packed tables that drop the masked slots from memory; masks in
+ *   ffm_engine_score_candidates and in the ablation kernels; training under a mask; groups, shards, LR and FM;
+ *   recording the mask in checkpoints. */
+int ffm_engine_set_pair_mask(ffm_engine *e, const uint64_t *keep /* [n_fields], NULL clears */, int32_t n_fields);
+int ffm_engine_get_pair_mask(ffm_engine *e, uint64_t *keep_out /* [n_fields], may be NULL */, int32_t *is_set);
 
 /* ---- Serving deltas: sync a serving engine, publish only what moved --------------------------------------
  * ffm_engine_pack_weights takes all of a model: it streams every record of the training engine and writes the
