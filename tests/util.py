@@ -697,3 +697,247 @@ def assert_rank_rows(e, rank, ids, field_of, want, plan, k, what, chunk=16384):
                 for key in ("lin_n", "lin_z", "lin_w"):
                     assert_bitwise(got[key], np.asarray(want[key][lo:hi]), "%s rank %d field %d %s" % (
                         what, rank, f, key))
+
+
+# ---- tables past 2^31 and 2^32 elements (tests/test_gpu_big_offsets.py, tests/test_big_offsets_host.py) ----------
+# FFM 39 x 16: a feature's record is 624 elements in a serving table (fp16: 2 bytes each, fp32: 4) and 3 * 624 in
+# a training engine ([n][z][w], 4 bytes each).  FM k = 64 training engine: 3 * 64.
+BIG_F, BIG_K, BIG_L = 39, 16, 624
+BIG_LAYOUTS = {"f16": (BIG_L, 2), "f32": (BIG_L, 4), "train": (3 * BIG_L, 4)}  # kind -> (stride in elements, element bytes)
+BIG_FM_K, BIG_FM_STRIDE = 64, 3 * 64
+BIG_HP = STRESS_HP  # weights that move (W(n, z) ~ 1e-2); with n >= BIG_N_ADD the oracle stays finite (checked on the CPU)
+BIG_N_ADD = 0.05
+
+
+def count_past(limit, stride, n_whole=8):
+    """The smallest feature count with at least n_whole records wholly at or past element `limit`."""
+    return -(-int(limit) // int(stride)) + int(n_whole)
+
+
+BIG_NF = count_past(2 ** 32, BIG_L)                # 6 882 969
+BIG_NF_FM = count_past(2 ** 32, BIG_FM_STRIDE)     # 22 369 630
+BIG_NF_TRAIN_INIT = count_past(2 ** 32, 3 * BIG_L)  # 2 294 329: a training engine's own layout past 2^32
+# The prediction, pack, sync and refresh kernels count in vectors of four factors: their index passes 2^32 at element
+# 2^34 -- 27 531 850 features of a serving table (34.4 GB in fp16), 9 177 289 of a training engine (68.7 GB)
+BIG_NF_VEC_SERVE = count_past(2 ** 34, BIG_L)
+BIG_NF_VEC_TRAIN = count_past(2 ** 34, 3 * BIG_L)
+
+
+def offset_thresholds(elem_bytes, unit=1):
+    """The element offsets at which an index can break: 2^31 and 2^32 as indices counted in units of `unit` elements
+    (1: an element index; 4: the index of a vector of four factors, which several kernels count in), and byte offsets
+    2^32, 2^33 and 2^34 as the element they fall on."""
+    return sorted({2 ** 31 * int(unit), 2 ** 32 * int(unit)} | {2 ** b // int(elem_bytes) for b in (32, 33, 34)})
+
+
+def straddling_ids(n_feats, stride_elems, elem_bytes, unit=1):
+    """The features whose record contains one of offset_thresholds, where that lies inside the table."""
+    return sorted({t // int(stride_elems) for t in offset_thresholds(elem_bytes, unit) if t // int(stride_elems) < int(n_feats)})
+
+
+def edge_ids(n_feats, stride_elems, elem_bytes, unit=1):
+    """straddling_ids with both neighbours each (clipped to the table), ascending int64."""
+    out = {h + d for h in straddling_ids(n_feats, stride_elems, elem_bytes, unit) for d in (-1, 0, 1)}
+    return np.array(sorted(h for h in out if 0 <= h < int(n_feats)), np.int64)
+
+
+def alias_ids(ids, stride, n_feats, elem_bytes=1, unit=1):
+    """The low features a wrapped index of a probe id h would hit: the records that [x, x + stride) overlaps for x =
+    h * stride mod 2^32 * unit and mod 2^31 * unit (an index in 32 bits, unsigned or signed, counted in units of `unit`
+    elements), and -- with elem_bytes > 1 -- mod 2^32 / elem_bytes (a byte offset in 32 bits).  Only those that are no
+    probe ids themselves and lie in the table."""
+    stride, probes = int(stride), {int(h) for h in ids}
+    mods = {2 ** 32 * int(unit), 2 ** 31 * int(unit)} | ({2 ** 32 // int(elem_bytes)} if elem_bytes > 1 else set())
+    out = set()
+    for h in probes:
+        for m in mods:
+            x = h * stride % m
+            out.update((x // stride, (x + stride - 1) // stride))
+    return np.array(sorted(a for a in out if a not in probes and 0 <= a < int(n_feats)), np.int64)
+
+
+def offset_tier(ids, stride, unit=1):
+    """Per id: 0 = the record lies wholly below index 2^31 (counted in units of `unit` elements), 1 = wholly in [2^31,
+    2^32), 2 = wholly at or past 2^32, -1 = it straddles one of the two."""
+    lo = np.asarray(ids, np.int64) * int(stride)
+    hi = lo + int(stride)
+    a, b = 2 ** 31 * int(unit), 2 ** 32 * int(unit)
+    return np.where(hi <= a, 0, np.where((lo >= a) & (hi <= b), 1, np.where(lo >= b, 2, -1)))
+
+
+def big_probe_ids(n_feats, layouts, seed, n_random=200, unit=1):
+    """The probe set of a table of n_feats features read under `layouts` [(stride, element bytes)]: edge_ids of every
+    layout; ids 0, 1 and n_feats - 1; the 8 records wholly past 2^32 at the smallest stride; the ids next to the last
+    edge between two 64-feature bitmap words, and n_feats - 1 - 64 (64 apart from the last id, across that edge); and
+    n_random ids drawn uniformly over [0, n_feats).  Ascending int64, no id twice."""
+    n = int(n_feats)
+    w0 = (n - 1) // 64 * 64
+    parts = [edge_ids(n, s, b, u) for s, b in layouts for u in {1, unit}]
+    parts += [np.array([0, 1, n - 1, w0 - 1, w0, n - 1 - 64], np.int64), np.arange(n - 8, n, dtype=np.int64),
+              np.random.default_rng(seed).integers(0, n, n_random)]
+    return np.unique(np.concatenate(parts).astype(np.int64))
+
+
+class BigCase:
+    """One model too large to hold twice, and its id-remapped compact twin for the oracle (renaming ids is exact for FFM
+    and FM: the arithmetic depends on (field, record) only).
+
+    probes: the probe ids, ascending.  Probe number j belongs to field j % F and is compact id (j % F) * per + j // F, so
+    that field f owns the compact ids [f * per, (f + 1) * per) -- the layout drop_pair_weights' callers expect (FM: the
+    fields only deal the ids to the columns of a row; the block's field array is 0).
+    block / compact_block: ~64 rows of one entry per column with ids from the probe set, an empty row and a row that
+    holds one entry twice, under the big ids / the compact ones.
+    state: rand_state on the compact oracle, BIG_N_ADD added to n; rows(): the probes' rows of it, in probe order."""
+
+    def __init__(self, mt, n_feats, k, layouts, seed, n_rows=64, hp=None, unit=1, tier_kinds=None):
+        """unit: the tiers (and the block's mix of them) are those of an index counted in units of `unit` elements;
+        tier_kinds: the layouts whose tiers the table reaches (default: all)."""
+        self.mt, self.n_feats, self.k, self.layouts, self.seed = mt, int(n_feats), int(k), dict(layouts), seed
+        self.unit, self.tier_kinds = int(unit), tuple(tier_kinds or layouts)
+        self.F = BIG_F
+        self.hp = dict(hp or BIG_HP)
+        self.probes = big_probe_ids(n_feats, list(self.layouts.values()), seed, unit=self.unit)
+        assert self.probes[-1] < 2 ** 31
+        P = self.probes.size
+        self.per = -(-P // self.F)
+        rank = np.arange(P)
+        self.field_of = (rank % self.F).astype(np.int32)
+        self.compact = (self.field_of.astype(np.int64) * self.per + rank // self.F).astype(np.int32)
+        self.n_compact = self.F * self.per
+        self.probes32 = self.probes.astype(np.int32)
+        self.block = self._block(n_rows, seed + 1)
+        self.compact_block = self.remap(self.block)
+        o = self.oracle()
+        st = rand_state(np.random.default_rng(seed + 2), o)
+        st["vec_n"] += np.float32(BIG_N_ADD)
+        st["lin_n"] += np.float32(BIG_N_ADD)
+        for a in st.values():
+            a.setflags(write=False)
+        self.state = st
+
+    def oracle(self, state=None, **weights):
+        """A compact oracle holding `state` (or nothing yet); weights: arrays that replace the state's."""
+        o = CpuModel("oracle", self.mt, self.n_compact, self.F if self.mt == "FFM" else 1, self.k, **self.hp)
+        if state is not None:
+            o.set_state(dict(state, **weights))
+        return o
+
+    def weights_oracle(self, vec_w, lin_w=None, bias=None):
+        """A compact oracle that holds weights alone (what a serving engine holds): (n, z) zero."""
+        o = self.oracle()
+        z = o.zero_state()
+        z["bias3"][0] = self.state["bias3"][0] if bias is None else bias
+        z["lin_w"][...] = self.state["lin_w"] if lin_w is None else lin_w
+        z["vec_w"][...] = vec_w
+        o.set_state(z)
+        return o
+
+    def compact_of(self, ids):
+        at = np.searchsorted(self.probes, np.asarray(ids, np.int64))
+        assert np.array_equal(self.probes[at], np.asarray(ids, np.int64)), "an id outside the probe set"
+        return self.compact[at]
+
+    def remap(self, blk):
+        return Csr(blk.row_ptr, blk.field, self.compact_of(blk.feat), blk.val, blk.label)
+
+    def rows(self, state=None, keys=None, ids=None):
+        """{key: the rows of the compact `state` (default: the start state) for the probe ids (or `ids`)}."""
+        state = self.state if state is None else state
+        at = self.compact if ids is None else self.compact_of(ids)
+        return {key: np.ascontiguousarray(state[key][at]) for key in (keys or ("lin_w", "lin_n", "lin_z", "vec_w", "vec_n", "vec_z"))}
+
+    def straddlers(self):
+        return sorted({h for s, b in self.layouts.values() for u in {1, self.unit} for h in straddling_ids(self.n_feats, s, b, u)})
+
+    def tiers(self, kind, ids=None):
+        return offset_tier(self.probes if ids is None else ids, self.layouts[kind][0], self.unit)
+
+    def aliases(self, kind):
+        """alias_ids of the probes under layout `kind`: wraps of an element index and of this case's unit."""
+        stride, eb = self.layouts[kind]
+        out = [alias_ids(self.probes, stride, self.n_feats, eb, u) for u in {1, self.unit}]
+        return np.unique(np.concatenate(out)).astype(np.int32)
+
+    def _block(self, n_rows, seed):
+        """Each entry: a tier of the smallest-stride layout drawn uniformly among those the column's ids have, then an
+        id of it; every row gets an id past 2^32 in every layout; every straddling id is placed once."""
+        rng = np.random.default_rng(seed)
+        F = self.F
+        stride0 = min(self.layouts[kind][0] for kind in self.tier_kinds)
+        tier0 = offset_tier(self.probes, stride0, self.unit)
+        cols = [np.flatnonzero(self.field_of == f) for f in range(F)]
+        top = np.flatnonzero(tier0 == 2)
+        feat = np.zeros((n_rows, F), np.int64)
+        for r in range(n_rows):
+            for f in range(F):
+                t = rng.choice(np.unique(tier0[cols[f]]))
+                feat[r, f] = self.probes[rng.choice(cols[f][tier0[cols[f]] == t])]
+        strad = self.straddlers()
+        assert len(strad) <= n_rows
+        held = np.full(n_rows, -1)  # the column of the row's straddling id
+        for r, h in enumerate(strad):
+            j = int(np.searchsorted(self.probes, h))
+            held[r] = self.field_of[j]
+            feat[r, held[r]] = h
+        for r in range(n_rows):
+            if not np.isin(feat[r], self.probes[top]).any():
+                j = int(rng.choice(top[self.field_of[top] != held[r]]))
+                feat[r, self.field_of[j]] = self.probes[j]
+        val = (rng.random((n_rows, F)) + 0.25).astype(np.float32)
+        val[rng.random((n_rows, F)) < 0.5] = 1.0
+        rows = [[(f if self.mt == "FFM" else 0, int(feat[r, f]), float(val[r, f])) for f in range(F)] for r in range(n_rows)]
+        twice = list(rows[n_rows // 2])
+        twice.append(twice[5])  # one (field, id) again, at the row's end
+        rows = rows[:n_rows // 3] + [[]] + rows[n_rows // 3:] + [twice]
+        label = (rng.random(len(rows)) < 0.4).astype(np.int32)
+        return Csr.from_rows(rows, label)
+
+
+_BIG_CASES = {}
+
+
+def big_case(name):
+    """"ffm": FFM 39 x 16 at BIG_NF under the three layouts; "fm": FM k = 64 at BIG_NF_FM (training engine); "vec_serve" /
+    "vec_train": FFM 39 x 16 at BIG_NF_VEC_SERVE / BIG_NF_VEC_TRAIN, where the index of a vector of four factors passes
+    2^32 in a serving table / in a training engine's records (an fp16 table of the latter count stays below 2^31
+    vectors: it is the destination of pack_from and sync_from there).  Built once per process; read-only."""
+    if name not in _BIG_CASES:
+        if name == "ffm":
+            _BIG_CASES[name] = BigCase("FFM", BIG_NF, BIG_K, BIG_LAYOUTS, seed=31)
+        elif name == "vec_serve":
+            _BIG_CASES[name] = BigCase("FFM", BIG_NF_VEC_SERVE, BIG_K, {"f16": BIG_LAYOUTS["f16"]}, seed=41, unit=4)
+        elif name == "vec_train":
+            _BIG_CASES[name] = BigCase("FFM", BIG_NF_VEC_TRAIN, BIG_K, {"train": BIG_LAYOUTS["train"], "f16": BIG_LAYOUTS["f16"]},
+                                       seed=43, unit=4, tier_kinds=("train",))
+        else:
+            _BIG_CASES[name] = BigCase("FM", BIG_NF_FM, BIG_FM_K, {"train": (BIG_FM_STRIDE, 4)}, seed=37)
+    return _BIG_CASES[name]
+
+
+def big_tier_entries(case, kind):
+    """{tier: the block's entries whose record lies in it} under layout `kind` (-1: straddling)."""
+    t = case.tiers(kind, case.block.feat)
+    return {int(v): int((t == v).sum()) for v in (-1, 0, 1, 2)}
+
+
+def big_upper_zeroed(case, kind, tiers=(1, 2, -1)):
+    """(vec_w, lin_w) of the start state with the weights of the probe ids in the given tiers of layout `kind` zeroed
+    (default: everything not wholly below 2^31)."""
+    hit = case.compact[np.isin(case.tiers(kind), tiers)]
+    vw, lw = case.state["vec_w"].copy(), case.state["lin_w"].copy()
+    vw[hit] = 0
+    lw[hit] = 0
+    return vw, lw
+
+
+def big_step(case):
+    """(logits, loss sum, state after) of one oracle train_batch of the block from the start state."""
+    o = case.oracle(case.state)
+    lg, ls = o.train_batch(case.compact_block)
+    return lg, ls, o.get_state()
+
+
+def nonfinite_share(logits, st0, st1):
+    """(share of non-finite logits, share of non-finite words among the state words the step changed, their count)."""
+    t = np.concatenate([st1[key].ravel()[bits(st1[key]).ravel() != bits(st0[key]).ravel()] for key in STATE_KEYS])
+    return float((~np.isfinite(logits)).mean()), float((~np.isfinite(t)).mean()) if t.size else 0.0, int(t.size)
