@@ -7,7 +7,7 @@ from .engine import (ABI, FFM, FM, LR, METRIC_BINS, METRIC_EVAL, METRIC_TRAIN, C
                      EngineError, FieldSketch, Group, KeyedMetrics, LIB_PATH, Metrics, default_batch_ramp, hash_ids, init_weights_host,
                      keyed_auc_reference, metrics_from_keyed,
                      load_library, metrics_from_histogram, page_aligned, shard_plan, sketch_estimate, field_ranges, spell_out_candidates, drop_field,
-                     pair_count, pair_index, pair_fields, drop_pair_weights, pair_mask, pair_mask_pairs, pair_mask_top,
+                     pair_count, pair_index, pair_fields, drop_pair_weights, pair_mask, pair_mask_pairs, pair_mask_top, pair_curve_levels, pair_curve_mask,
                      IdCounter, RARE_ID, fold_rare, rare_slot,
                      ValueHistogram, BUCKET_BINS, BUCKET_MAX_EDGES, BUCKET_NAN_ID, value_bins, bucket_edges, bucket_ids,
                      FLAG_NORM_ROWS, normalize_rows, normalize_rows_host,

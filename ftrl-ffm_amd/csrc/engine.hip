@@ -53,6 +53,7 @@
 #include "kernels_delta.h"
 #include "kernels_ablate.h"
 #include "kernels_ablate_pairs.h"
+#include "kernels_curve.h"
 #include "kernels_mask.h"
 #include "kernels_stage.h"
 #include "kernels_sketch.h"
@@ -450,10 +451,15 @@ struct ffm_engine {
   // sums' partial sums and tickets, hist [V][2 * kMetricBins + 1] with with_auc
   struct AblateSet {
     bool on = false, auc = false;
+    int variants = 0;  // V of the arrays below (the curve's changes with its cuts: its set is then made again)
     float *out = nullptr;
     double *loss = nullptr, *sums = nullptr, *part = nullptr;
     unsigned long long *hist = nullptr;
-  } abl, pabl;
+  } abl, pabl, cabl;
+  // the pruning curve (include/ffm_engine.h "Pruning curve"; engine_ablate.h): cabl above for its n_cuts + 1 variants,
+  // and the level table and cuts in force in HBM, made by the first ffm_engine_pair_curve_enable
+  unsigned short *d_curve_level = nullptr;  // [kCurveFields * kCurveFields], the first n_fields * n_fields in use
+  int *d_curve_cut = nullptr;               // [kCurveCuts], the first cabl.variants - 1 in use
   // ffm_engine_set_pair_mask (include/ffm_engine.h "Pair masks", engine_mask.h): the words in HBM (made by the first
   // call that sets a mask) and their copy on the host; pair_mask_on == false: no mask, and nothing here is read
   bool pair_mask_on = false;

@@ -169,6 +169,16 @@ inline AblateWaveFn ablate_pairs_fn(int fmt, int n_factors, int rounds) {
     default: return nullptr;
   }
 }
+// the pruning curve (kernels_curve.h): ffm_ablate_wave_kernel's arguments, then the level table and the cuts in HBM
+using CurveWaveFn = void (*)(ModelDev, Rows, int *, int, int, float *, double *, int, int, CurveDev);
+inline CurveWaveFn curve_wave_fn(int fmt, int n_factors) {
+  switch (n_factors) {
+#define X(K, LPP, VPL, U) case K: return FFM_BY_ANY_FMT(ffm_curve_wave_kernel, LPP, VPL, U);
+    FFM_LANE_SHAPES(X)
+#undef X
+    default: return nullptr;
+  }
+}
 #undef FFM_BY_ANY_FMT
 #undef FFM_BY_FMT
 #undef FFM_LANE_SHAPES

@@ -284,6 +284,12 @@ ABI = [
     # predict with the kept field pairs only (include/ffm_engine.h "Pair masks")
     ("ffm_engine_set_pair_mask", ctypes.c_int, [_vp, _vp, ctypes.c_int32]),
     ("ffm_engine_get_pair_mask", ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_int32)]),
+    # the loss and AUC of up to 64 pair masks, in one pass (include/ffm_engine.h "Pruning curve")
+    ("ffm_engine_pair_curve_enable", ctypes.c_int, [_vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32]),
+    ("ffm_engine_predict_pair_curve", ctypes.c_int, [_vp, ctypes.c_int32] + _CSR + [ctypes.c_int32, _f32p, _f64p]),
+    ("ffm_engine_predict_pair_curve_device", ctypes.c_int,
+     [_vp, ctypes.c_int32, ctypes.c_int32] + _DCSR + [ctypes.c_int32, _vp, _vp]),
+    ("ffm_engine_pair_curve_read", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(Metrics)]),
     # sync a serving engine, publish only what moved (include/ffm_engine.h "Serving deltas")
     ("ffm_engine_sync_weights", ctypes.c_int, [_vp, _vp, ctypes.POINTER(SyncStats)]),
     ("ffm_engine_sync_moved", ctypes.c_int, [_vp, _i32p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
@@ -767,6 +773,44 @@ def pair_mask_top(n_fields, loss, n_keep):
         raise ValueError("pair mask: loss without pair %d %d is not finite" % pair_fields(n_fields, int(bad[0])))
     order = sorted(range(V), key=lambda v: -delta[v])  # (stable: ties stay in index order)
     return pair_mask(n_fields, [pair_fields(n_fields, v) for v in sorted(order[:n_keep])])
+
+
+def pair_curve_levels(n_fields, order):
+    """The level table of a ladder (include/ffm_engine.h "Pruning curve"): order is a permutation of the V =
+    n_fields (n_fields + 1) / 2 pair indices, best first; level[f][g] = level[g][f] = the position of pair (f, g) in
+    it, so that cut N keeps the best N pairs.  uint16[n_fields, n_fields].  Pure numpy."""
+    n_fields = int(n_fields)
+    if n_fields < 1 or n_fields > 64:
+        raise ValueError("a level table is for 1 .. 64 fields, got n_fields = %d" % n_fields)
+    V = n_fields * (n_fields + 1) // 2
+    order = np.asarray(order, np.int64).reshape(-1)
+    if order.shape[0] != V or not np.array_equal(np.sort(order), np.arange(V)):
+        raise ValueError("order must be a permutation of the %d pair indices of %d fields" % (V, n_fields))
+    rank = np.empty(V, np.int64)
+    rank[order] = np.arange(V)
+    f, g = np.triu_indices(n_fields)  # (row-major over f <= g: the pairs in pair_index order)
+    level = np.zeros((n_fields, n_fields), np.uint16)
+    level[f, g] = rank
+    level[g, f] = rank
+    return level
+
+
+def pair_curve_mask(level, cut):
+    """The mask that one cut of a level table stands for, in pair_mask's format: bit g of words[f] is
+    level[f][g] < cut (include/ffm_engine.h "Pruning curve", "as masks").  Pure numpy."""
+    level = np.asarray(level)
+    if level.ndim != 2 or level.shape[0] != level.shape[1] or not 1 <= level.shape[0] <= 64:
+        raise ValueError("level: a square table of 1 .. 64 fields")
+    if level.dtype.kind not in "ui" or level.min() < 0 or level.max() > 65535:
+        raise ValueError("level: unsigned 16-bit entries")
+    if not np.array_equal(level, level.T):
+        raise ValueError("the level table is not symmetric")
+    cut = int(cut)
+    if cut < 0 or cut > 65536:
+        raise ValueError("a cut lies in [0, 65536], got %d" % cut)
+    kept = level.astype(np.int64) < cut
+    bit = np.uint64(1) << np.arange(level.shape[0], dtype=np.uint64)
+    return (kept.astype(np.uint64) * bit[None, :]).sum(axis=1, dtype=np.uint64)
 
 
 def spell_out_candidates(ctx, cand_req_ptr, cand):
@@ -1482,6 +1526,60 @@ class Engine:
         over every labelled block predict_pair_ablated has seen (pair_ablation_enable(auc=True))."""
         m = (Metrics * (self.n_fields * (self.n_fields + 1) // 2 + 1))()
         self._check(self.lib.ffm_engine_pair_ablation_read(self.h, int(bool(reset)), m))
+        return [x.as_dict() for x in m]
+
+    # ---- the pruning curve (include/ffm_engine.h "Pruning curve") ----
+    def pair_curve_enable(self, level, cuts, auc=False):
+        """Sets the level table (uint16[n_fields, n_fields], symmetric; pair_curve_levels makes a ladder's) and 1 .. 64
+        cuts, each in [0, 65536], and allocates what predict_pair_curve needs: (n_cuts + 1) x max_batch_rows scores and
+        losses and, with auc, n_cuts + 1 score histograms of 16.8 MB each.  Calling it again replaces table and cuts;
+        with the same number of cuts the histograms keep their counts, which then mix two ladders: call
+        pair_curve_metrics(reset=True) before changing the table.
+        The engines of the ablations: FFM, one whole model on one device, n_factors in {4, 8, 16, 32, 64}, at most
+        64 fields; training and serving engines."""
+        lv = np.asarray(level)
+        if lv.ndim != 2 or lv.shape[0] != lv.shape[1]:
+            raise ValueError("level: a square table [n_fields, n_fields]")
+        if lv.dtype.kind not in "ui" or (lv.size and (lv.min() < 0 or lv.max() > 65535)):
+            raise ValueError("level: unsigned 16-bit entries")
+        lv = np.ascontiguousarray(lv, np.uint16)
+        ct = np.ascontiguousarray(np.asarray(cuts, np.int64).reshape(-1))
+        if ct.size and (ct.min() < -(1 << 31) or ct.max() >= (1 << 31)):
+            raise ValueError("a cut lies in [0, 65536]")
+        ct = np.ascontiguousarray(ct, np.int32)
+        self._check(self.lib.ffm_engine_pair_curve_enable(self.h, lv.ctypes.data_as(_vp), int(lv.shape[0]),
+                                                          ct.ctypes.data_as(_i32p), int(ct.shape[0]), int(bool(auc))))
+        self._curve_variants = int(ct.shape[0]) + 1
+
+    def _curve_v(self):
+        v = getattr(self, "_curve_variants", 0)
+        if not v:
+            raise EngineError(E_INVALID, "the pruning curve is off (pair_curve_enable)")
+        return v
+
+    def predict_pair_curve(self, c, output_prob=False, with_loss=True, scores=True):
+        """(out[n_cuts + 1, n_rows] or None, loss_sums[n_cuts + 1]): row i is predict_batch(c) under
+        set_pair_mask(pair_curve_mask(level, cuts[i])), row n_cuts is predict_batch(c), bit for bit, from one pass
+        over c.  scores=False leaves the scores in HBM and returns None for them."""
+        V = self._curve_v()
+        out = np.zeros((V, c.n_rows), np.float32) if scores else None  # (variant-major with stride n_rows)
+        loss = np.zeros(V, np.float64)
+        n, rp, fld, ft, v, lab = self._csr(c)
+        self._check(self.lib.ffm_engine_predict_pair_curve(self.h, n, rp, fld, ft, v, lab if with_loss else None,
+                                                           int(output_prob), _f(out), loss.ctypes.data_as(_f64p)))
+        return out, loss
+
+    def predict_pair_curve_device(self, n_rows, nnz, row_ptr, field, feat, val, label, output_prob, out, loss_sum_out=None):
+        """predict_pair_curve on arrays already in HBM (device addresses; out[(n_cuts + 1) * n_rows] variant-major or
+        None, loss_sum_out[n_cuts + 1]).  Asynchronous on the engine's stream; sync() reports a too-long row."""
+        self._check(self.lib.ffm_engine_predict_pair_curve_device(self.h, int(n_rows), int(nnz), row_ptr, field, feat, val,
+                                                                  label, int(output_prob), out, loss_sum_out))
+
+    def pair_curve_metrics(self, reset=False):
+        """One dict per variant (n_cuts + 1), as metrics() returns for a channel: the AUC under each cut's mask over
+        every labelled block predict_pair_curve has seen (pair_curve_enable(auc=True))."""
+        m = (Metrics * self._curve_v())()
+        self._check(self.lib.ffm_engine_pair_curve_read(self.h, int(bool(reset)), m))
         return [x.as_dict() for x in m]
 
     # ---- pair masks (include/ffm_engine.h "Pair masks") ----

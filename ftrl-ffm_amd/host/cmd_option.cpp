@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -133,6 +134,16 @@ const std::string_view cmd_help =
     "              write them as a mask file: `ffm-pair-mask 1 <n_fields> <n_kept>`, then one `f g` line per kept pair.\n"
     "              Prints `pair mask: kept N of V pairs, smallest kept delta D -> FILE`; a delta that is not finite ends the\n"
     "              run.  Both flags go together\tdefault:(none)\n"
+    "--pair_curve <LIST|auto>: with --pair_importance true: where does pruning start to hurt?  After the pairs' pass, rank\n"
+    "              the pairs as --pair_keep does and make one more pass over --eval_data that predicts every row under\n"
+    "              `keep the best N pairs` for every listed N at once, on the device, exactly.  LIST is 1 to 64\n"
+    "              comma-separated N in [0, V]; auto is round(i V / 63) for i = 0 .. 63.  Prints `pair curve: R rows, loss L,\n"
+    "              auc A`, then, ascending in N, `keep N of V pairs: loss L (delta D), auc A (delta D)`; the AUC parts\n"
+    "              only with --metrics auc (a 16.8 MB histogram per listed N)\tdefault:(none)\n"
+    "--pair_loss_budget <T>: with --pair_curve and --pair_mask_out <file>, in place of --pair_keep: write the mask of the\n"
+    "              smallest listed N whose per-row loss delta is <= T.  Prints `pair mask: kept N of V pairs, loss delta D\n"
+    "              within budget T -> FILE`; if no listed N meets the budget nothing is written, a line says so and the\n"
+    "              run exits non-zero\tdefault:(none)\n"
     "--pair_mask <@file>: a run that trains nothing (--n_epochs 0 with --resume_from ck, --serve_weights or not, or with\n"
     "              --apply_deltas) predicts with the file's pairs only: the terms of every other pair are left out, and\n"
     "              their gathers are not made.  --eval_data, --metrics auc, --auc_key_field, --predict_data / --predict_out\n"
@@ -295,6 +306,33 @@ void config_options::parse_option(int argc, char *argv[]) {
       pair_keep = static_cast<int>(x);
     }
     else if (k == "--pair_mask_out") pair_mask_out = v;
+    else if (k == "--pair_curve") {
+      // the form only: what the N may be depends on --n_fields, which may come later (checked below)
+      pair_curve = v;
+      pair_curve_keep.clear();
+      if (v != "auto") {
+        const std::string bad = "--pair_curve takes auto or 1 to 64 comma-separated numbers of pairs, got `" + v + "`";
+        size_t at = 0;
+        for (;;) {
+          const size_t end = std::min(v.find(',', at), v.size());
+          const std::string t = v.substr(at, end - at);
+          if (t.empty() || t.size() > 4 || t.find_first_not_of("0123456789") != std::string::npos) throw std::invalid_argument(bad);
+          if (pair_curve_keep.size() == 64) throw std::invalid_argument("--pair_curve takes at most 64 numbers of pairs (one pass has 64 cuts), got more");
+          pair_curve_keep.push_back(std::stoi(t));
+          if (end == v.size()) break;
+          at = end + 1;
+        }
+      }
+    }
+    else if (k == "--pair_loss_budget") {
+      double x = 0.0;
+      size_t used = 0;
+      try { x = std::stod(v, &used); } catch (const std::exception &) { used = 0; }
+      if (used != v.size() || used == 0 || !std::isfinite(x))
+        throw std::invalid_argument("--pair_loss_budget takes a finite per-row loss delta, got `" + v + "`");
+      pair_loss_budget = x;
+      pair_loss_budget_set = true;
+    }
     else if (k == "--pair_mask") pair_mask = v;
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
     else if (k == "--field_ranges") field_ranges = v;
@@ -553,8 +591,31 @@ void config_options::parse_option(int argc, char *argv[]) {
   if (field_importance) check_importance("--field_importance true ", "fields", "keeps one lane of a 64-lane wave per field");
   if (pair_importance)
     check_importance("--pair_importance true ", "field pairs", "keeps the pairs of at most 64 fields in the registers of a 64-lane wave");
+  // --pair_curve LIST|auto, --pair_loss_budget T: the pruning curve behind the pair importance pass, and the mask its
+  // budget picks (refused here, before a device is opened)
+  if (!pair_curve.empty()) {
+    if (!pair_importance)
+      throw std::invalid_argument("--pair_curve " + pair_curve + " ranks the pairs by the pair importance pass: it needs --pair_importance true");
+    const int V = n_fields * (n_fields + 1) / 2;
+    if (pair_curve == "auto") {
+      pair_curve_keep.clear();
+      for (int i = 0; i < 64; i++) pair_curve_keep.push_back((2 * i * V + 63) / 126);  // round(i V / 63): never a tie
+    }
+    for (int n : pair_curve_keep)
+      if (n > V)
+        throw std::invalid_argument("--pair_curve " + pair_curve + ": " + std::to_string(n) + " is more than the " + std::to_string(V) +
+                                    " pairs of --n_fields " + std::to_string(n_fields));
+    std::sort(pair_curve_keep.begin(), pair_curve_keep.end());
+    pair_curve_keep.erase(std::unique(pair_curve_keep.begin(), pair_curve_keep.end()), pair_curve_keep.end());
+  }
+  if (pair_loss_budget_set) {
+    if (pair_keep >= 0)
+      throw std::invalid_argument("--pair_loss_budget picks the number of pairs --pair_keep would give: the two are not allowed together");
+    if (pair_curve.empty()) throw std::invalid_argument("--pair_loss_budget picks from the curve's listed numbers of pairs: it needs --pair_curve");
+    if (pair_mask_out.empty()) throw std::invalid_argument("--pair_loss_budget picks the pairs --pair_mask_out FILE writes: it needs --pair_mask_out");
+  }
   // --pair_keep N --pair_mask_out FILE: the pair importance pass's answer as a mask file (refused here, before a device is opened)
-  if (pair_keep >= 0 || !pair_mask_out.empty()) {
+  if (pair_keep >= 0 || (!pair_mask_out.empty() && !pair_loss_budget_set)) {
     if (pair_keep < 0) throw std::invalid_argument("--pair_mask_out writes the pairs --pair_keep N selects: it needs --pair_keep");
     if (pair_mask_out.empty()) throw std::invalid_argument("--pair_keep selects the pairs --pair_mask_out FILE writes: it needs --pair_mask_out");
     if (!pair_importance)

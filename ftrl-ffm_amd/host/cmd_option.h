@@ -75,6 +75,15 @@ struct config_options {
   // predicts with the file's pairs only (include/ffm_engine.h "Pair masks")
   int pair_keep = -1;
   std::string pair_mask_out, pair_mask;
+  // --pair_curve LIST|auto (with --pair_importance true): after the pairs' pass, one more pass over --eval_data gives the
+  // loss (and AUC) of "keep the best N pairs" for every listed N at once (include/ffm_engine.h "Pruning curve").
+  // pair_curve is the flag as given ("" = not asked for); pair_curve_keep its N, ascending and without duplicates
+  // (auto: round(i V / 63), i = 0 .. 63), made once --n_fields is known.  --pair_loss_budget T (with --pair_curve and
+  // --pair_mask_out, in place of --pair_keep): the mask of the smallest listed N whose per-row loss delta is <= T.
+  std::string pair_curve;
+  std::vector<int> pair_curve_keep;
+  bool pair_loss_budget_set = false;
+  double pair_loss_budget = 0.0;
   // --publish_path PREFIX [--publish_weights f32|f16]: after every epoch's training (and refresh) a serving delta
   // PREFIX.<epochs_done>.delta -- what a shadow serving engine had to move to follow the model (serve_delta.h)
   std::string publish_path, publish_weights = "f32";

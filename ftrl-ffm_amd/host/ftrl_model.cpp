@@ -467,6 +467,36 @@ std::vector<ffm_metrics> FtrlModel::read_ablation_metrics(Ablation kind, bool re
   return m;
 }
 
+void FtrlModel::enable_pair_curve(const std::vector<uint16_t> &level, const std::vector<int32_t> &cuts, bool with_auc) {
+  if (grp_) throw std::invalid_argument("the pruning curve: one GPU only");
+  if (level.size() != static_cast<size_t>(n_fields) * static_cast<size_t>(n_fields))
+    throw std::invalid_argument("the pruning curve: level needs n_fields * n_fields entries");
+  const int rc = ffm_engine_pair_curve_enable(eng_, level.data(), n_fields, cuts.data(), static_cast<int32_t>(cuts.size()), with_auc ? 1 : 0);
+  if (rc == FFM_E_INVALID || rc == FFM_E_UNSUPPORTED) throw std::invalid_argument(std::string("pair curve: ") + ffm_engine_last_error());
+  check(rc, "ffm_engine_pair_curve_enable");
+  curve_variants_ = cuts.size() + 1;
+}
+
+void FtrlModel::predict_curve_block(const CsrBlock &blk, std::vector<double> &loss_sums) {
+  if (grp_) throw std::invalid_argument("the pruning curve: one GPU only");
+  if (curve_variants_ == 0 || loss_sums.size() != curve_variants_)
+    throw std::invalid_argument("the pruning curve: loss_sums needs one entry per cut and one for the rows (enable_pair_curve first)");
+  std::vector<double> part(curve_variants_);
+  for_each_fitting(blk, [&](const CsrBlock &b, int) {
+    check(ffm_engine_predict_pair_curve(eng_, b.n_rows(), b.row_ptr.data(), b.field.data(), b.feat.data(), b.val.data(), b.label.data(), 0,
+                                        nullptr, part.data()),
+          "ffm_engine_predict_pair_curve");
+    for (size_t v = 0; v < curve_variants_; v++) loss_sums[v] += part[v];
+  });
+}
+
+std::vector<ffm_metrics> FtrlModel::read_curve_metrics(bool reset) {
+  if (grp_) throw std::invalid_argument("the pruning curve: one GPU only");
+  std::vector<ffm_metrics> m(std::max<size_t>(1, curve_variants_));
+  check(ffm_engine_pair_curve_read(eng_, reset ? 1 : 0, m.data()), "ffm_engine_pair_curve_read");
+  return m;
+}
+
 long long FtrlModel::predict_block_async(const CsrBlock &blk, bool pinned, float *scores, bool output_prob, bool *complete) {
   const int n = blk.n_rows();
   bool fits = n <= max_rows_ && blk.row_ptr[n] <= max_nnz_;

@@ -175,6 +175,13 @@ class FtrlModel {
   void enable_ablation(Ablation kind, bool with_auc);
   void predict_ablated_block(Ablation kind, const CsrBlock &blk, std::vector<double> &loss_sums);
   std::vector<ffm_metrics> read_ablation_metrics(Ablation kind, bool reset);
+  // Pruning curve (include/ffm_engine.h "Pruning curve"; pair_mask.h makes the table): level[n_fields * n_fields] and 1 ..
+  // 64 cuts give cuts.size() + 1 variants, the rows themselves last.  enable_pair_curve sets them on the one FFM engine
+  // (throws std::invalid_argument with the engine's reason when it refuses); predict_curve_block ADDS one block's
+  // per-variant loss sums to loss_sums[cuts.size() + 1]; read_curve_metrics as read_ablation_metrics.
+  void enable_pair_curve(const std::vector<uint16_t> &level, const std::vector<int32_t> &cuts, bool with_auc);
+  void predict_curve_block(const CsrBlock &blk, std::vector<double> &loss_sums);
+  std::vector<ffm_metrics> read_curve_metrics(bool reset);
   // Pair mask (include/ffm_engine.h "Pair masks"; pair_mask.h makes the words): from now on every prediction of this
   // model leaves out the terms of the pairs whose bit is clear, and training is refused.  keep[n_fields]; one FFM
   // engine only (throws std::invalid_argument otherwise, with the engine's reason).
@@ -243,6 +250,7 @@ class FtrlModel {
   int n_gpus_ = 1;
   int metrics_mask_ = 0;
   int keyed_mask_ = 0, keyed_field_ = -1;  // --auc_key_field (-1: not asked for)
+  size_t curve_variants_ = 0;               // enable_pair_curve: its cuts + 1 (0: not enabled)
   long long keyed_rows_ = 0;               // --auc_key_rows
   std::vector<int32_t> lin_owner_of_field_;  // [n_fields] shard that owns a field's linear terms
   int bias_owner_ = 0;

@@ -52,4 +52,20 @@ int print_pair_importance(std::FILE *out, int n_fields, unsigned long long rows,
   return listed;
 }
 
+int print_pair_curve(std::FILE *out, int n_fields, unsigned long long rows, const std::vector<int> &keep, const std::vector<double> &loss,
+                     const std::vector<ffm_metrics> *auc) {
+  const size_t whole = keep.size();
+  if (loss.size() != whole + 1 || (auc && auc->size() != whole + 1)) return -1;
+  const double n = rows ? static_cast<double>(rows) : 1.0;
+  std::fprintf(out, "pair curve: %llu rows, loss %.6lf", rows, loss[whole] / n);
+  if (auc) std::fprintf(out, ", auc %.6lf", (*auc)[whole].auc);
+  std::fprintf(out, "\n");
+  for (size_t i = 0; i < whole; i++) {
+    std::fprintf(out, "keep %d of %d pairs: loss %.6lf (delta %+.6lf)", keep[i], pair_count(n_fields), loss[i] / n, (loss[i] - loss[whole]) / n);
+    if (auc) std::fprintf(out, ", auc %.6lf (delta %+.6lf)", (*auc)[i].auc, (*auc)[i].auc - (*auc)[whole].auc);
+    std::fprintf(out, "\n");
+  }
+  return static_cast<int>(whole);
+}
+
 }  // namespace ftrl

@@ -38,5 +38,12 @@ int print_field_importance(std::FILE *out, int n_fields, unsigned long long rows
                            const std::vector<ffm_metrics> *auc);
 int print_pair_importance(std::FILE *out, int n_fields, unsigned long long rows, const std::vector<double> &loss,
                           const std::vector<ffm_metrics> *auc);
+// --pair_curve (include/ffm_engine.h "Pruning curve"):
+//   pair curve: R rows, loss L[, auc A]
+//   keep N of V pairs: loss L (delta D)[, auc A (delta D)]       one line per listed N, ascending
+// keep: the listed N; loss / auc: one per listed N, the rows themselves last.  Returns the lines per N, or -1 with
+// nothing printed when a length is another.
+int print_pair_curve(std::FILE *out, int n_fields, unsigned long long rows, const std::vector<int> &keep, const std::vector<double> &loss,
+                     const std::vector<ffm_metrics> *auc);
 
 }  // namespace ftrl

@@ -19,6 +19,25 @@ void check_fields(int n_fields) {
 }
 }  // namespace
 
+std::vector<int> rank_pairs(int n_fields, const std::vector<double> &loss) {
+  check_fields(n_fields);
+  const int V = count_of(n_fields);
+  if (loss.size() != static_cast<size_t>(V) + 1)
+    throw std::invalid_argument("pair mask: " + std::to_string(V + 1) + " loss sums expected, got " + std::to_string(loss.size()));
+  std::vector<double> delta(static_cast<size_t>(V));
+  size_t v = 0;
+  for (int f = 0; f < n_fields; f++)
+    for (int g = f; g < n_fields; g++, v++) {  // (v == index_of(n_fields, f, g): the pairs in index order)
+      delta[v] = loss[v] - loss[static_cast<size_t>(V)];
+      if (!std::isfinite(delta[v]))
+        throw std::runtime_error("pair mask: loss without pair " + std::to_string(f) + " " + std::to_string(g) + " is not finite");
+    }
+  std::vector<int> order(static_cast<size_t>(V));
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return delta[a] > delta[b]; });
+  return order;
+}
+
 PairList select_pairs(int n_fields, const std::vector<double> &loss, int n_keep, double *smallest_kept) {
   check_fields(n_fields);
   const int V = count_of(n_fields);
@@ -26,25 +45,48 @@ PairList select_pairs(int n_fields, const std::vector<double> &loss, int n_keep,
     throw std::invalid_argument("pair mask: " + std::to_string(V + 1) + " loss sums expected, got " + std::to_string(loss.size()));
   if (n_keep < 0 || n_keep > V)
     throw std::invalid_argument("--pair_keep must lie in [0, " + std::to_string(V) + "], got " + std::to_string(n_keep));
-  PairList all;
-  std::vector<double> delta(static_cast<size_t>(V));
-  for (int f = 0; f < n_fields; f++)
-    for (int g = f; g < n_fields; g++) {
-      const size_t v = all.size();  // (== index_of(n_fields, f, g): the pairs in index order)
-      delta[v] = loss[v] - loss[static_cast<size_t>(V)];
-      if (!std::isfinite(delta[v]))
-        throw std::runtime_error("pair mask: loss without pair " + std::to_string(f) + " " + std::to_string(g) + " is not finite");
-      all.emplace_back(f, g);
-    }
-  std::vector<int> order(static_cast<size_t>(V));
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return delta[a] > delta[b]; });
-  if (smallest_kept) *smallest_kept = n_keep > 0 ? delta[order[static_cast<size_t>(n_keep) - 1]] : 0.0;
+  std::vector<int> order = rank_pairs(n_fields, loss);
+  if (smallest_kept) {
+    const size_t last = n_keep > 0 ? static_cast<size_t>(order[static_cast<size_t>(n_keep) - 1]) : 0;
+    *smallest_kept = n_keep > 0 ? loss[last] - loss[static_cast<size_t>(V)] : 0.0;
+  }
   order.resize(static_cast<size_t>(n_keep));
   std::sort(order.begin(), order.end());
+  PairList all;
+  for (int f = 0; f < n_fields; f++)
+    for (int g = f; g < n_fields; g++) all.emplace_back(f, g);
   PairList kept;
   for (int v : order) kept.push_back(all[static_cast<size_t>(v)]);
   return kept;
+}
+
+std::vector<uint16_t> pair_curve_levels(int n_fields, const std::vector<int> &order) {
+  check_fields(n_fields);
+  const int V = count_of(n_fields);
+  std::vector<int> rank(static_cast<size_t>(V), -1);
+  if (order.size() != static_cast<size_t>(V)) throw std::invalid_argument("pair curve: the order must list all " + std::to_string(V) + " pairs");
+  for (int at = 0; at < V; at++) {
+    const int v = order[static_cast<size_t>(at)];
+    if (v < 0 || v >= V || rank[static_cast<size_t>(v)] >= 0) throw std::invalid_argument("pair curve: the order is no permutation of the pairs");
+    rank[static_cast<size_t>(v)] = at;
+  }
+  std::vector<uint16_t> level(static_cast<size_t>(n_fields) * n_fields);
+  for (int f = 0; f < n_fields; f++)
+    for (int g = f; g < n_fields; g++) {
+      const uint16_t at = static_cast<uint16_t>(rank[static_cast<size_t>(index_of(n_fields, f, g))]);  // (V <= 2080)
+      level[static_cast<size_t>(f) * n_fields + g] = level[static_cast<size_t>(g) * n_fields + f] = at;
+    }
+  return level;
+}
+
+int pick_by_budget(const std::vector<int> &keep, const std::vector<double> &curve_loss, unsigned long long rows, double budget) {
+  if (curve_loss.size() != keep.size() + 1) throw std::invalid_argument("pair curve: one loss sum per listed number of pairs and the rows' own");
+  const double n = rows ? static_cast<double>(rows) : 1.0;
+  for (size_t i = 0; i < keep.size(); i++) {
+    const double delta = (curve_loss[i] - curve_loss.back()) / n;
+    if (std::isfinite(delta) && delta <= budget) return static_cast<int>(i);
+  }
+  return -1;
 }
 
 std::vector<uint64_t> pair_mask_words(int n_fields, const PairList &pairs) {

@@ -10,6 +10,7 @@
 #include <mutex>
 #include <numeric>
 #include <random>
+#include <stdexcept>
 #include <thread>
 
 #include "importance.h"
@@ -66,6 +67,8 @@ void run_importance(const config_options &opt, FtrlModel &m, FtrlModel::Ablation
   std::vector<ffm_metrics> auc;
   if (want_auc) auc = m.read_ablation_metrics(kind, true);
   (pairs ? print_pair_importance : print_field_importance)(stdout, opt.n_fields, rows, loss, want_auc ? &auc : nullptr);
+  // --pair_curve LIST|auto [--pair_loss_budget T --pair_mask_out FILE]: the ranking as a ladder, one more pass
+  if (pairs && !opt.pair_curve.empty()) run_pair_curve(opt, m, loss);
   // --pair_keep N --pair_mask_out FILE: the pass's answer as a mask file (pair_mask.h: the rule and the format)
   if (pairs && opt.pair_keep >= 0) {
     double smallest = 0.0;
@@ -74,6 +77,41 @@ void run_importance(const config_options &opt, FtrlModel &m, FtrlModel::Ablation
     std::printf("pair mask: kept %zu of %d pairs, smallest kept delta %+.6lf -> %s\n", kept.size(), pair_count(opt.n_fields),
                 smallest / (rows ? static_cast<double>(rows) : 1.0), opt.pair_mask_out.c_str());
   }
+}
+
+void run_pair_curve(const config_options &opt, FtrlModel &m, const std::vector<double> &pair_loss) {
+  const bool want_auc = opt.metrics == "auc";
+  const std::vector<int> &keep = opt.pair_curve_keep;  // ascending, no duplicates (cmd_option)
+  // level = a pair's rank under select_pairs' own rule, so cut N keeps the pairs --pair_keep N would write
+  const std::vector<uint16_t> level = pair_curve_levels(opt.n_fields, rank_pairs(opt.n_fields, pair_loss));
+  m.enable_pair_curve(level, std::vector<int32_t>(keep.begin(), keep.end()), want_auc);
+  CsrStream stream(opt.eval_path, opt.file_type, opt.thread_num);
+  const size_t batch = static_cast<size_t>(std::max(1, opt.batch_size));
+  std::vector<double> loss(keep.size() + 1, 0.0);
+  CsrBlock blk;
+  unsigned long long rows = 0;
+  for (;;) {
+    const size_t got = stream.next(batch, blk);
+    if (got == 0) break;
+    m.predict_curve_block(blk, loss);
+    rows += got;
+  }
+  std::vector<ffm_metrics> auc;
+  if (want_auc) auc = m.read_curve_metrics(true);
+  print_pair_curve(stdout, opt.n_fields, rows, keep, loss, want_auc ? &auc : nullptr);
+  if (!opt.pair_loss_budget_set) return;
+  const int at = pick_by_budget(keep, loss, rows, opt.pair_loss_budget);
+  const double n = rows ? static_cast<double>(rows) : 1.0;
+  if (at < 0) {
+    std::printf("pair mask: no listed number of pairs has a loss delta within budget %.6lf: nothing written\n", opt.pair_loss_budget);
+    std::fflush(stdout);
+    throw std::runtime_error("--pair_loss_budget: no listed number of pairs meets the budget");
+  }
+  const size_t i = static_cast<size_t>(at);
+  const PairList kept = select_pairs(opt.n_fields, pair_loss, keep[i]);
+  write_pair_mask(opt.pair_mask_out, opt.n_fields, kept);
+  std::printf("pair mask: kept %zu of %d pairs, loss delta %+.6lf within budget %.6lf -> %s\n", kept.size(), pair_count(opt.n_fields),
+              (loss[i] - loss.back()) / n, opt.pair_loss_budget, opt.pair_mask_out.c_str());
 }
 
 void load_pair_mask(const config_options &opt, FtrlModel &m) {

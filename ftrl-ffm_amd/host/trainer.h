@@ -136,6 +136,13 @@ void refresh_and_print(FtrlModel &m, long long epoch);
 // With --pair_keep N --pair_mask_out FILE the pairs' pass then ranks them (pair_mask.h), writes the mask file and
 // prints `pair mask: kept N of V pairs, smallest kept delta D -> FILE` (D per row, as the pairs' lines print it).
 void run_importance(const config_options &opt, FtrlModel &m, FtrlModel::Ablation kind);
+// --pair_curve LIST|auto, behind the pairs' pass (pair_loss: its V + 1 sums): ranks the pairs by select_pairs' rule,
+// makes one more pass over --eval_data through FtrlModel::predict_curve_block with level = rank and the listed N as
+// cuts (include/ffm_engine.h "Pruning curve"), and prints importance.h's `pair curve` lines.  With --pair_loss_budget T
+// --pair_mask_out FILE it then writes the mask of the smallest listed N whose per-row loss delta is <= T and prints
+// `pair mask: kept N of V pairs, loss delta D within budget T -> FILE`; when no listed N meets the budget it writes
+// nothing, prints a line that says so and throws std::runtime_error (the run exits non-zero).
+void run_pair_curve(const config_options &opt, FtrlModel &m, const std::vector<double> &pair_loss);
 // --pair_mask @FILE: reads the file against the run's --n_fields, sets the mask on the loaded model
 // (FtrlModel::set_pair_mask) and prints `pair mask: K of V pairs kept, from FILE`.
 void load_pair_mask(const config_options &opt, FtrlModel &m);

@@ -1214,7 +1214,8 @@ int ffm_engine_pair_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out
  * rows too long  a row longer than max_row_nnz, or than the 128 entries a wave stages, is NaN and reported as
  *   FFM_E_CAPACITY -- on a training engine too: a masked engine launches no other row kernel.
  * WHILE A MASK IS SET  FFM_E_INVALID, before anything is queued, model and state unchanged: every training entry
- *   point, ffm_engine_score_candidates[_device], ffm_engine_predict_ablated* and ffm_engine_predict_pair_ablated*.
+ *   point, ffm_engine_score_candidates[_device], ffm_engine_predict_ablated*, ffm_engine_predict_pair_ablated* and
+ *   ffm_engine_predict_pair_curve*.
  *   Masked training and masked candidates are different features; refusing keeps anything from silently running
  *   unmasked.
  * The mask is not part of the model: weights and state in and out, ffm_engine_pack_weights, _sync_weights, deltas,
@@ -1226,6 +1227,60 @@ int ffm_engine_pair_ablation_read(ffm_engine *e, int32_t reset, ffm_metrics *out
  *   recording the mask in checkpoints. */
 int ffm_engine_set_pair_mask(ffm_engine *e, const uint64_t *keep /* [n_fields], NULL clears */, int32_t n_fields);
 int ffm_engine_get_pair_mask(ffm_engine *e, uint64_t *keep_out /* [n_fields], may be NULL */, int32_t *is_set);
+
+/* ---- Pruning curve: the loss and AUC of up to 64 pair masks, in one pass -----------------------------------
+ * Pair ablation says what ONE pair is worth to the whole model; those deltas do not add up when hundreds of pairs go
+ * together.  Where pruning starts to hurt is the curve "loss and AUC against kept pairs", and by hand every point of
+ * it is one masked evaluation pass.  Here the gathers and the k-long dots are made once per row, as for the two
+ * ablations, and every point is one more ordered sum of the same terms.
+ * DEFINITION  A level table is level[n_fields][n_fields]: uint16_t, row-major with stride n_fields, symmetric, the
+ *   diagonal included.  A list of n_cuts cuts goes with it, 1 <= n_cuts <= 64; each cut is an int32_t in [0, 65536],
+ *   in any order, duplicates allowed.
+ *   variant c         (c < n_cuts) of a row is the prediction's ordered sum -- the bias, the survivors' linear
+ *                     products, then the pair terms in ffm_engine_predict_batch's pair order -- with the terms
+ *                     between an entry of field f and an entry of field g left out wherever level[f][g] >= cut[c].
+ *                     Linear terms always stay.  Leaving a term out and adding -0.0f in its place are the same bits.
+ *   variant n_cuts    is ffm_engine_predict_batch of the block, bit for bit.
+ *   as masks          variant c is, bit for bit, ffm_engine_predict_batch of the same block on the same engine under
+ *                     ffm_engine_set_pair_mask(M_c), bit g of M_c[f] = (level[f][g] < cut[c]) -- on any block, with
+ *                     no condition on the ids (engine.py: pair_curve_mask is this sentence in numpy).  Cut 0 keeps no
+ *                     pair, cut 65536 keeps all.
+ *   a ladder          with level = a pair's rank in an importance order (engine.py: pair_curve_levels), cut N is
+ *                     "keep the best N pairs": nested masks.  The engine requires neither nesting nor ranks.
+ * ffm_engine_pair_curve_enable  the engine restrictions and messages of the ablations (FFM_E_UNSUPPORTED: anything
+ *   but a whole FFM model on one device; n_factors outside {4, 8, 16, 32, 64}; n_fields > 64).  FFM_E_INVALID,
+ *   leaving what was in force: n_fields other than the engine's, an asymmetric table, n_cuts outside [1, 64], a cut
+ *   outside [0, 65536].  Allocates the (n_cuts + 1) x max_batch_rows score and loss scratch and, with with_auc,
+ *   n_cuts + 1 score histograms of 16.8 MB each, as ffm_engine_pair_ablation_enable does and with with_auc meaning
+ *   what it means there.  The table and the cuts are copied to engine-owned device memory before the call returns,
+ *   on the engine's stream and into arrays of their own: the kernels queued so far go on reading the previous ones.
+ *   Calling it again replaces the table and the cuts; if n_cuts changed, the scratch is made again and the
+ *   histograms start from zero.  With n_cuts unchanged the histograms KEEP their counts, as with_auc says, also when
+ *   the table or the cuts are others: the counts then mix two ladders, so read them with reset = 1
+ *   (ffm_engine_pair_curve_read) before changing the table.  A failed allocation is FFM_E_NOMEM, a failed copy
+ *   FFM_E_DEVICE; either leaves the engine as it was (the curve off, or the previous table, cuts and counts in force).
+ * ffm_engine_predict_pair_curve[_device]  the arguments, staging and errors of ffm_engine_predict_pair_ablated
+ *   [_device]; out[(n_cuts + 1) * n_rows] variant-major, may be NULL; loss_sum_out[n_cuts + 1], may be NULL.
+ *   Before ffm_engine_pair_curve_enable, and while a pair mask is set: FFM_E_INVALID.
+ * rows too long  a row longer than max_row_nnz, or than the 128 entries a wave stages, is NaN in all n_cuts + 1
+ *   variants and reported as FFM_E_CAPACITY.
+ * ffm_engine_pair_curve_read  out[n_cuts + 1]: per variant the ffm_metrics of its histogram.  Without with_auc:
+ *   FFM_E_INVALID.
+ * The calls feed neither metric channel, no keyed capture and nothing of the two ablations.  An engine that never
+ * enables the curve allocates nothing and launches nothing of it; the section adds functions only, and
+ * FFM_ENGINE_ABI_VERSION is what it was.
+ * OUT OF SCOPE  more than 64 cuts a pass (a second call with other cuts covers that); groups, shards, LR and FM;
+ *   training under a mask. */
+int ffm_engine_pair_curve_enable(ffm_engine *e, const uint16_t *level /* [n_fields * n_fields] */, int32_t n_fields,
+                                 const int32_t *cut /* [n_cuts] */, int32_t n_cuts, int32_t with_auc);
+int ffm_engine_predict_pair_curve(ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
+                                  const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob,
+                                  float *out /* [(n_cuts + 1) * n_rows], variant-major, may be NULL */,
+                                  double *loss_sum_out /* [n_cuts + 1], may be NULL */);
+int ffm_engine_predict_pair_curve_device(ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
+                                         const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
+                                         int32_t output_prob, float *out, double *loss_sum_out);
+int ffm_engine_pair_curve_read(ffm_engine *e, int32_t reset, ffm_metrics *out /* [n_cuts + 1] */);
 
 /* ---- Serving deltas: sync a serving engine, publish only what moved --------------------------------------
  * ffm_engine_pack_weights takes all of a model: it streams every record of the training engine and writes the
