@@ -51,17 +51,70 @@ static int slot_weights_init(ffm_engine *e) {
   return FFM_OK;
 }
 
+// Whether the device can already read the byte at p: memory allocated page-locked, or registered.
+static bool is_mapped_host(const void *p) {
+  void *mapped = nullptr;
+  const bool yes = hipHostGetDevicePointer(&mapped, const_cast<void *>(p), 0) == hipSuccess && mapped;
+  if (!yes) (void)hipGetLastError();  // (the runtime keeps the refusal for the next launch to report)
+  return yes;
+}
+
+// The ranges ffm_engine_pin_host registered itself: the only ones ffm_engine_unpin_host hands back to the runtime.
+static std::mutex g_registered_mu;
+static std::vector<void *> g_registered;
+
+int ffm_engine_alloc_host(void **p, size_t bytes) {
+  if (!p) return fail(FFM_E_INVALID, "null pointer");
+  *p = nullptr;
+  if (!bytes) return fail(FFM_E_INVALID, "null range");
+  void *got = nullptr;
+  // whole pages; portable: page-locked for every GPU of the process (as the registration below)
+  const hipError_t err = hipHostMalloc(&got, (bytes + 4095) & ~static_cast<size_t>(4095), hipHostMallocPortable | hipHostMallocMapped);
+  if (err != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(err == hipErrorOutOfMemory ? FFM_E_NOMEM : FFM_E_DEVICE, std::string("hipHostMalloc: ") + hipGetErrorString(err));
+  }
+  *p = got;
+  return FFM_OK;
+}
+int ffm_engine_free_host(void *p) {
+  if (!p) return FFM_OK;
+  HIP_TRY(hipHostFree(p));
+  return FFM_OK;
+}
+
 int ffm_engine_pin_host(void *p, size_t bytes) {
   if (!p || !bytes) return fail(FFM_E_INVALID, "null range");
+  // memory that was allocated page-locked (ffm_engine_alloc_host, hipHostMalloc) is what the caller wants already
+  if (is_mapped_host(p) && is_mapped_host(static_cast<char *>(p) + bytes - 1)) return FFM_OK;
   // portable: one registration serves every GPU of the process (an ffm_group stages the same host
   // block on all of its engines; without the flag only the current device may read it)
-  HIP_TRY(hipHostRegister(p, bytes, hipHostRegisterPortable | hipHostRegisterMapped));
+  const hipError_t err = hipHostRegister(p, bytes, hipHostRegisterPortable | hipHostRegisterMapped);
+  if (err != hipSuccess) {
+    // (not every system lets the runtime lock pages it did not allocate; the refusal must not stay behind
+    // for the caller's next launch to report)
+    (void)hipGetLastError();
+    return fail(err == hipErrorOutOfMemory ? FFM_E_NOMEM : FFM_E_DEVICE,
+                std::string("hipHostRegister: ") + hipGetErrorString(err) + " (ffm_engine_alloc_host allocates page-locked memory)");
+  }
+  std::lock_guard<std::mutex> lock(g_registered_mu);
+  g_registered.push_back(p);
   return FFM_OK;
 }
 int ffm_engine_unpin_host(void *p) {
   if (!p) return fail(FFM_E_INVALID, "null pointer");
-  HIP_TRY(hipHostUnregister(p));
-  return FFM_OK;
+  {
+    std::lock_guard<std::mutex> lock(g_registered_mu);
+    const auto at = std::find(g_registered.begin(), g_registered.end(), p);
+    if (at != g_registered.end()) {
+      g_registered.erase(at);
+      HIP_TRY(hipHostUnregister(p));
+      return FFM_OK;
+    }
+  }
+  // allocated page-locked: it stays so until its owner frees it
+  if (is_mapped_host(p)) return FFM_OK;
+  return fail(FFM_E_INVALID, "not page-locked by ffm_engine_pin_host");
 }
 
 // The device's address of host memory that the 16-byte lanes of the upload and download kernels can move:

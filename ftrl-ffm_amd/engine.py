@@ -161,6 +161,8 @@ ABI = [
     ("ffm_engine_train_staged", ctypes.c_int, [_vp, _vp, _vp]),
     ("ffm_engine_pin_host", ctypes.c_int, [_vp, ctypes.c_size_t]),
     ("ffm_engine_unpin_host", ctypes.c_int, [_vp]),
+    ("ffm_engine_alloc_host", ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_size_t]),
+    ("ffm_engine_free_host", ctypes.c_int, [_vp]),
     ("ffm_engine_prepare_device", ctypes.c_int,
      [_vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp]),
     ("ffm_engine_train_forward_device", ctypes.c_int,
@@ -865,13 +867,28 @@ def load_library(path=None):
 
 
 def page_aligned(n, dtype):
-    """A numpy array of n elements in an anonymous mapping of its own: page-aligned, whole pages,
-    shared with nothing else -- what Engine.pin_block should be given.  (hipHostRegister locks whole
-    pages; an array in the middle of the Python heap shares its pages with whatever lives next to
-    it, and the runtime then meets half-registered ranges in later copies.)"""
+    """A numpy array of n elements in whole pages of its own, page-aligned and shared with nothing else -- what
+    Engine.pin_block should be given.  The pages are allocated page-locked (ffm_engine_alloc_host) and go back
+    when the last view of the array is gone: not every system lets the runtime lock pages it did not allocate,
+    and pin_block finds nothing left to do on these.  Where none can be had (no GPU, no library) they are an
+    anonymous mapping, which pin_block locks in place.  (hipHostRegister locks whole pages; an array in the
+    middle of the Python heap shares its pages with whatever lives next to it, and the runtime then meets
+    half-registered ranges in later copies.)"""
     import mmap
+    import weakref
     nbytes = max(1, int(n)) * np.dtype(dtype).itemsize
     size = (nbytes + mmap.PAGESIZE - 1) // mmap.PAGESIZE * mmap.PAGESIZE
+    p = _vp()
+    try:
+        lib = load_library()
+    except (FileNotFoundError, OSError):
+        lib = None
+    if lib is not None and lib.ffm_engine_alloc_host(ctypes.byref(p), size) == 0 and p.value % mmap.PAGESIZE == 0:
+        buf = (ctypes.c_char * size).from_address(p.value)
+        weakref.finalize(buf, lib.ffm_engine_free_host, p.value).atexit = False  # (the process's end frees them all)
+        return np.frombuffer(buf, dtype=dtype, count=int(n))
+    if p.value:
+        lib.ffm_engine_free_host(p.value)
     return np.frombuffer(mmap.mmap(-1, size), dtype=dtype, count=int(n))
 
 
@@ -1227,7 +1244,7 @@ class Engine:
 
     def pin_block(self, c):
         """Page-locks the block's five arrays in place (for stage_batch(zero_copy=True)).  Give it
-        arrays that own their pages (page_aligned)."""
+        arrays that own their pages (page_aligned: where those were allocated page-locked, nothing is left to do)."""
         for a in (c.row_ptr, c.field, c.feat, c.val, c.label):
             if a is not None and a.size:
                 self._check(self.lib.ffm_engine_pin_host(a.ctypes.data, a.nbytes))
@@ -1286,7 +1303,8 @@ class Engine:
 
     def score_buffer(self, n):
         """A page-locked float32 array of n elements for predict_batch_async(scores=...): pages of
-        its own (page_aligned), locked in place (ffm_engine_pin_host).  Release with free_score_buffer."""
+        its own (page_aligned; locked in place by ffm_engine_pin_host where they were not allocated so).
+        Release with free_score_buffer."""
         a = page_aligned(n, np.float32)
         self._check(self.lib.ffm_engine_pin_host(a.ctypes.data, max(1, a.size) * 4))
         return a

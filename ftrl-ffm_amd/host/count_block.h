@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/ffm_engine.h"
 #include "csr_stream.h"
+#include "locked_pages.h"
 
 namespace ftrl {
 
@@ -17,6 +18,10 @@ struct CountBlock {
   explicit CountBlock(bool with_val = false) {
     blk.row_ptr.reserve(kCountRows + 1);
     blk.label.reserve(kCountRows);
+    // (what the device reads: into pages allocated page-locked, where there are any -- locked_pages.h)
+    to_locked_pages(blk.field, kCountNnz);
+    to_locked_pages(blk.feat, kCountNnz);
+    if (with_val) to_locked_pages(blk.val, kCountNnz);
     blk.field.reserve(kCountNnz);
     blk.feat.reserve(kCountNnz);
     blk.val.reserve(kCountNnz);

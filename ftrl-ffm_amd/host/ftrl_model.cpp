@@ -1,4 +1,5 @@
 #include "ftrl_model.h"
+#include "locked_pages.h"
 
 #include "persist.h"
 #include "serve_delta.h"
@@ -321,6 +322,13 @@ void FtrlModel::train_block_async(const CsrBlock &blk) {
 }
 
 bool FtrlModel::pin_block(CsrBlock &blk, bool with_weights) {
+  // (into pages allocated page-locked, where there are any: locked_pages.h)
+  to_locked_pages(blk.row_ptr, static_cast<size_t>(max_rows_) + 1);
+  to_locked_pages(blk.label, static_cast<size_t>(max_rows_));
+  to_locked_pages(blk.field, static_cast<size_t>(max_nnz_));
+  to_locked_pages(blk.feat, static_cast<size_t>(max_nnz_));
+  to_locked_pages(blk.val, static_cast<size_t>(max_nnz_));
+  if (with_weights) to_locked_pages(blk.weight, static_cast<size_t>(max_rows_));
   blk.row_ptr.reserve(static_cast<size_t>(max_rows_) + 1);
   blk.label.reserve(static_cast<size_t>(max_rows_));
   blk.field.reserve(static_cast<size_t>(max_nnz_));

@@ -49,15 +49,22 @@ TextChunkStream::TextChunkStream(const std::string &path, int n_threads, size_t 
   }
   size_ = static_cast<unsigned long long>(st.st_size);
   for (int s = 0; s < 2; s++) {
-    slot_[s] = static_cast<char *>(std::aligned_alloc(4096, slot_bytes_));
+    // allocated page-locked where that can be had, else the heap's pages locked in place
+    // (neither: the parser copies each chunk into its own)
+    void *locked = nullptr;
+    allocated_locked_[s] = ffm_engine_alloc_host(&locked, slot_bytes_) == FFM_OK;
+    slot_[s] = static_cast<char *>(allocated_locked_[s] ? locked : std::aligned_alloc(4096, slot_bytes_));
     if (!slot_[s]) throw std::bad_alloc();
-    // (no page-locked memory to be had: the parser copies each chunk into its own)
-    pinned_[s] = ffm_engine_pin_host(slot_[s], slot_bytes_) == FFM_OK;
+    pinned_[s] = allocated_locked_[s] || ffm_engine_pin_host(slot_[s], slot_bytes_) == FFM_OK;
   }
 }
 
 TextChunkStream::~TextChunkStream() {
   for (int s = 0; s < 2; s++) {
+    if (allocated_locked_[s]) {
+      ffm_engine_free_host(slot_[s]);
+      continue;
+    }
     if (pinned_[s]) ffm_engine_unpin_host(slot_[s]);
     std::free(slot_[s]);
   }

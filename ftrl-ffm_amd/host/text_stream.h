@@ -48,6 +48,7 @@ class TextChunkStream {
   size_t slot_bytes_ = 0;
   char *slot_[2] = {nullptr, nullptr};
   bool pinned_[2] = {false, false};
+  bool allocated_locked_[2] = {false, false};  // the slot came from ffm_engine_alloc_host (else from the heap)
   const char *tail_ = nullptr;  // the bytes behind the last chunk's last '\n', still in that chunk's slot
   size_t tail_len_ = 0;
   std::vector<char> long_line_[2];

@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "importance.h"
+#include "locked_pages.h"
 #include "pair_mask.h"
 #include "score_writer.h"
 
@@ -520,6 +521,7 @@ unsigned long long Scorer::run() {
   };
   std::vector<Entry> ent(kScoreRing);
   for (auto &en : ent) {
+    to_locked_pages(en.buf, static_cast<size_t>(batch_));  // (pages allocated page-locked, where there are any)
     en.buf.resize(static_cast<size_t>(batch_));
     en.pinned = model_->pin_scores(en.buf.data(), en.buf.size());
   }

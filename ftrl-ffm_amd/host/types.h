@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <new>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 typedef int8_t int8;
@@ -26,22 +27,40 @@ struct Sample {
   int y;
 };
 
+// Where a PageAllocator's pages come from when not from the heap: take(bytes) gives whole pages, page-aligned, or
+// null; give(p) takes them back.  (locked_pages.h: pages the device's runtime allocated page-locked.)
+struct PageSource {
+  void *(*take)(size_t bytes);
+  void (*give)(void *p);
+};
+
 // Whole pages per array: a block's arrays can then be page-locked one by one (hipHostRegister
 // works on pages: two small arrays sharing a heap page cannot both be registered).
+// With a source, the pages are that source's; the source goes where the array's storage goes (move, swap), and a
+// copy of the array lies in the heap's pages again.
 template <typename T>
 struct PageAllocator {
   using value_type = T;
+  using propagate_on_container_move_assignment = std::true_type;
+  using propagate_on_container_swap = std::true_type;
+  using is_always_equal = std::false_type;
+  const PageSource *source = nullptr;
   PageAllocator() = default;
-  template <typename U> PageAllocator(const PageAllocator<U> &) {}
+  explicit PageAllocator(const PageSource *s) : source(s) {}
+  template <typename U> PageAllocator(const PageAllocator<U> &o) : source(o.source) {}
+  PageAllocator select_on_container_copy_construction() const { return PageAllocator(); }
   T *allocate(size_t n) {
     const size_t bytes = (n * sizeof(T) + 4095) & ~static_cast<size_t>(4095);
-    void *p = std::aligned_alloc(4096, bytes ? bytes : 4096);
+    void *p = source ? source->take(bytes ? bytes : 4096) : std::aligned_alloc(4096, bytes ? bytes : 4096);
     if (!p) throw std::bad_alloc();
     return static_cast<T *>(p);
   }
-  void deallocate(T *p, size_t) { std::free(p); }
-  template <typename U> bool operator==(const PageAllocator<U> &) const { return true; }
-  template <typename U> bool operator!=(const PageAllocator<U> &) const { return false; }
+  void deallocate(T *p, size_t) {
+    if (source) source->give(p);
+    else std::free(p);
+  }
+  template <typename U> bool operator==(const PageAllocator<U> &o) const { return source == o.source; }
+  template <typename U> bool operator!=(const PageAllocator<U> &o) const { return source != o.source; }
 };
 
 // What the readers note about a row while they write its entries (one byte per row; a block's two facts are

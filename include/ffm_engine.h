@@ -351,9 +351,18 @@ int ffm_engine_train_staged(ffm_engine *e, float *logit_out, double *loss_sum_ou
 /* hipHostRegister / hipHostUnregister for callers that do not link the HIP runtime themselves.
  * Give it ranges that own their pages (page-aligned, whole pages: mmap, posix_memalign): the
  * runtime locks whole pages, and a range in the middle of a heap shares its first and last page
- * with whatever the allocator placed next to it. */
+ * with whatever the allocator placed next to it.
+ *   Not every system lets the runtime lock pages that it did not allocate itself (a GPU passed through
+ * to a virtual machine, for one): ffm_engine_pin_host then fails with FFM_E_DEVICE and leaves nothing
+ * behind.  Memory that is page-locked everywhere comes from ffm_engine_alloc_host (hipHostMalloc:
+ * whole pages, page-aligned, device-mapped, for every GPU of the process; ffm_engine_free_host gives
+ * it back).  On such memory, or on a caller's own hipHostMalloc, ffm_engine_pin_host and
+ * ffm_engine_unpin_host succeed and do nothing, so a caller that allocates with ffm_engine_alloc_host
+ * and falls back to its own pages + ffm_engine_pin_host runs on both kinds of system. */
 int ffm_engine_pin_host(void *p, size_t bytes);
 int ffm_engine_unpin_host(void *p);
+int ffm_engine_alloc_host(void **p, size_t bytes);
+int ffm_engine_free_host(void *p);
 
 /* Optional look-ahead of the mini-batch scheduler: start grouping the NEXT block by feature (the
  * integer-only first stage of training) on a side stream while the current block is still being

@@ -570,7 +570,8 @@ def test_bad_weights_are_refused_and_leave_the_model_untouched():
         # a zero_copy weight array that is page-locked but not 16-byte aligned, and one that is not page-locked
         assert e.lib.ffm_engine_stage_batch_weighted(e.h, *e._csr(cp), wp.ctypes.data + 4, 1) == fa.engine.E_INVALID
         assert b"16-byte aligned" in e.lib.ffm_engine_last_error()
-        loose = fa.page_aligned(16, f32)
+        import mmap
+        loose = np.frombuffer(mmap.mmap(-1, mmap.PAGESIZE), f32, 16)  # (pages of its own that nobody locked)
         loose[:] = 1.0
         assert e.lib.ffm_engine_stage_batch_weighted(e.h, *e._csr(cp), loose.ctypes.data, 1) == fa.engine.E_INVALID
         assert b"page-locked" in e.lib.ffm_engine_last_error()
