@@ -11,6 +11,7 @@ from .engine import (ABI, FFM, FM, LR, METRIC_BINS, METRIC_EVAL, METRIC_TRAIN, C
                      IdCounter, RARE_ID, fold_rare, rare_slot,
                      ValueHistogram, BUCKET_BINS, BUCKET_MAX_EDGES, BUCKET_NAN_ID, value_bins, bucket_edges, bucket_ids,
                      FLAG_NORM_ROWS, normalize_rows, normalize_rows_host,
+                     FLAG_SERVE_F8, SERVE_F8_VALUE, serve_f8_encode, serve_f8_decode, serve_f8_stride,
                      TextParser, TextBlock, parse_text_host, TEXT_MAX_LINE, TEXT_TILE_BYTES, TEXT_SCAN_BYTES, TEXT_LINE_TILE,
                      TEXT_SCAN_CHUNK, RowCutter, RowsBlock)
 

@@ -50,6 +50,7 @@
 #include "kernels_metric.h"
 #include "kernels_keyed.h"
 #include "kernels_serve.h"
+#include "kernels_serve8.h"
 #include "kernels_delta.h"
 #include "kernels_ablate.h"
 #include "kernels_ablate_pairs.h"
@@ -433,6 +434,7 @@ struct ffm_engine {
   int refresh_grid = 0;
   // ffm_engine_pack_weights (engine_serve.h): the four counters of a serving engine, made by the first call
   unsigned long long *d_pack = nullptr;
+  unsigned long long *d_enc8 = nullptr;  // an f8 serving engine: what set_weights / set_rows encoded (ffm_engine_encode_stats)
   // ffm_engine_sync_weights (engine_delta.h), both made by a serving engine's first call: its four counters, and
   // the features the LAST call moved as a bitmap of ceil(n_feats / 64) words
   unsigned long long *d_sync = nullptr, *d_moved = nullptr;
@@ -656,10 +658,18 @@ struct ffm_engine {
 
 // A serving engine (FFM_FLAG_SERVE_F32 / _F16, engine_serve.h) stores w alone: whatever needs (n, z) is refused.
 static inline bool serving(const ffm_engine *e) { return e->m.lat_fmt != SERVE_NONE; }
+constexpr int kServeFlags = FFM_FLAG_SERVE_F32 | FFM_FLAG_SERVE_F16 | FFM_FLAG_SERVE_F8;
 static int serve_refuse(const char *what) {
   return fail(FFM_E_UNSUPPORTED, std::string("a serving engine holds no accumulators: ") + what + " needs a training engine");
 }
 #define SERVE_REFUSE(e, what) do { if ((e) && serving(e)) return serve_refuse(what); } while (0)
+// An f8 serving engine (FFM_FLAG_SERVE_F8, kernels_serve8.h) has its row kernel and the encoder: what the other
+// serving formats do beyond rows is not built for it yet.
+static int f8_refuse(const std::string &what) {
+  return fail(FFM_E_UNSUPPORTED, what + " is not available on an f8 serving engine (FFM_FLAG_SERVE_F8): the f8 table has "
+                                        "a row prediction kernel and nothing else; use FFM_FLAG_SERVE_F32 or _F16");
+}
+#define F8_REFUSE(e, what) do { if ((e) && (e)->m.lat_fmt == SERVE_F8) return f8_refuse(what); } while (0)
 // An engine with a pair mask (engine_mask.h) predicts rows and nothing else: whatever would run unmasked is refused.
 static int mask_refuse(const char *what) {
   return fail(FFM_E_INVALID, std::string(what) + " is not available while a pair mask is set (ffm_engine_set_pair_mask "

@@ -89,6 +89,7 @@ static int ablate_supported(const AblateKind &k, ffm_engine *e) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
   const ModelDev &m = e->m;
   const std::string noun = k.noun;
+  F8_REFUSE(e, noun);
   if (m.type != FFM_MODEL_FFM) return fail(FFM_E_UNSUPPORTED, noun + " is FFM only: LR and FM rows have no fields");
   if (m.n_shards > 1 || e->in_group)
     return fail(FFM_E_UNSUPPORTED, noun + " needs a whole model on one device (n_shards == 1, not a group's engine)");
@@ -246,6 +247,7 @@ static int ablate_ready(const AblateKind &k, ffm_engine *e) {
 static int ablate_predict_device(const AblateKind &k, ffm_engine *e, int32_t n_rows, int32_t nnz, const int32_t *row_ptr,
                                  const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
                                  int32_t output_prob, float *out, double *loss_sum_out) {
+  F8_REFUSE(e, k.noun);
   int rc = ablate_ready(k, e);
   if (rc) return rc;
   MASK_REFUSE(e, k.noun);  // (its variants are the whole model's: include/ffm_engine.h "Pair masks")
@@ -257,6 +259,7 @@ static int ablate_predict_device(const AblateKind &k, ffm_engine *e, int32_t n_r
 static int ablate_predict(const AblateKind &k, ffm_engine *e, int32_t n_rows, const int32_t *row_ptr, const int32_t *field,
                           const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob, float *out,
                           double *loss_sum_out) {
+  F8_REFUSE(e, k.noun);
   int rc = ablate_ready(k, e);
   if (rc) return rc;
   MASK_REFUSE(e, k.noun);  // (its variants are the whole model's: include/ffm_engine.h "Pair masks")

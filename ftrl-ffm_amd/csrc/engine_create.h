@@ -7,6 +7,7 @@
 
 static int hash_ids_check(int32_t model_type, int32_t n_feats, int32_t n_fields, const int32_t *field_start);  // (engine_hash.h)
 static int serve_create_check(const ffm_engine_config *cfg);  // (engine_serve.h)
+static void serve8_launch_init(ffm_engine *e, bool zero);      // (engine_serve.h)
 static int norm_ready(ffm_engine *e);  // (engine_norm.h)
 
 // What the environment sets.  An empty optional: the switch is not set, and the default -- an ffm_engine member's
@@ -98,8 +99,8 @@ static int check_config(const ffm_engine_config *cfg, bool hash_ids) {
   // FFM_FLAG_NORM_ROWS (engine_norm.h): a row's length is a sum over ALL of its entries
   if ((cfg->flags & FFM_FLAG_NORM_ROWS) && cfg->n_shards > 1)
     return fail(FFM_E_INVALID, "FFM_FLAG_NORM_ROWS needs a whole model (n_shards == 1): a shard does not own whole rows");
-  // FFM_FLAG_SERVE_F32 / _F16: a serving engine (engine_serve.h) -- its shape is checked like the arguments above
-  if (cfg->flags & (FFM_FLAG_SERVE_F32 | FFM_FLAG_SERVE_F16))
+  // FFM_FLAG_SERVE_F32 / _F16 / _F8: a serving engine (engine_serve.h) -- its shape is checked like the arguments above
+  if (cfg->flags & kServeFlags)
     if (int rc_s = serve_create_check(cfg)) return rc_s;
   // (an argument error like the ones above: reported whether or not there is a device)
   if (hash_ids)
@@ -177,7 +178,8 @@ static int plan_model(ffm_engine *e, const Switches &sw, ShardPlan *plan) {
   take(m.super_min, sw.super_min);
   m.few_stage = 1;
   take(m.few_stage, sw.few_stage);
-  m.lat_fmt = (cfg->flags & FFM_FLAG_SERVE_F32 ? SERVE_F32 : 0) | (cfg->flags & FFM_FLAG_SERVE_F16 ? SERVE_F16 : 0);
+  m.lat_fmt = (cfg->flags & FFM_FLAG_SERVE_F32 ? SERVE_F32 : 0) | (cfg->flags & FFM_FLAG_SERVE_F16 ? SERVE_F16 : 0) |
+              (cfg->flags & FFM_FLAG_SERVE_F8 ? SERVE_F8 : 0);
   m.rec_slots = m.n_fields;
   e->n_records = cfg->n_feats;
   // field-pair partition: this shard's ranges, and (with per-field id ranges) compact storage
@@ -247,9 +249,11 @@ static int alloc_model(ffm_engine *e, const ShardPlan &plan) {
   int rc;
   const size_t nf = static_cast<size_t>(cfg->n_feats);
   // floats allocated for the latent part: records of (n, z, w), or a serving engine's table of w alone in
-  // 4- or 2-byte elements (row_len is a multiple of 4 there) -- and then no (n, z) of the bias or the linear part
+  // 4- or 2-byte elements (row_len is a multiple of 4 there) or in f8 rows (kernels_serve8.h: a multiple of 16
+  // bytes each) -- and then no (n, z) of the bias or the linear part
   const size_t n_w = static_cast<size_t>(e->n_records) * static_cast<size_t>(m.row_len);
-  const size_t n_lat = m.lat_fmt == SERVE_F16 ? n_w / 2 : m.lat_fmt == SERVE_F32 ? n_w : 3 * n_w;
+  const size_t n_lat = m.lat_fmt == SERVE_F8    ? static_cast<size_t>(e->n_records) * static_cast<size_t>(serve8_stride(m.row_len)) / 4
+                       : m.lat_fmt == SERVE_F16 ? n_w / 2 : m.lat_fmt == SERVE_F32 ? n_w : 3 * n_w;
   const size_t n_bias = serving(e) ? 1 : 4;
   if ((rc = e->alloc(&m.bias3, n_bias))) return rc;
   HIP_TRY(hipMemsetAsync(m.bias3, 0, n_bias * sizeof(float), e->stream));
@@ -531,7 +535,9 @@ static int opt_in_lds(ffm_engine *e) {
 static int init_weights(ffm_engine *e) {
   const ffm_engine_config *cfg = &e->cfg;
   const bool skip = (cfg->flags & FFM_FLAG_SKIP_INIT) != 0;  // (the caller sets the state; the arrays are zeroed)
-  if (!skip && serving(e))
+  if (e->m.lat_fmt == SERVE_F8)  // (skipped too: a row of zero bytes still has a head)
+    serve8_launch_init(e, skip);
+  else if (!skip && serving(e))
     hipLaunchKernelGGL(serve_init_kernel, dim3(2048), dim3(256), 0, e->stream, e->m, cfg->init_mean, cfg->init_stddev, cfg->seed);
   else if (!skip)
     hipLaunchKernelGGL(init_weights_kernel, dim3(2048), dim3(256), 0, e->stream, e->m, e->logical_len,
@@ -557,7 +563,7 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   e->max_rows = cfg->max_batch_rows;
   e->max_nnz = cfg->max_batch_nnz;
   if (cfg->max_row_nnz > 0) e->max_row_nnz = cfg->max_row_nnz;
-  else if (cfg->flags & (FFM_FLAG_SERVE_F32 | FFM_FLAG_SERVE_F16)) e->max_row_nnz = kPredLdsCap;  // (a serving engine's rows are one wave's: no longer ones)
+  else if (cfg->flags & kServeFlags) e->max_row_nnz = kPredLdsCap;  // (a serving engine's rows are one wave's: no longer ones)
   apply_switches(e, sw);
   ShardPlan plan;
   Scratch shared{};

@@ -147,7 +147,7 @@ extern "C" {
 int ffm_group_create(const ffm_engine_config *cfg, int32_t n, const int32_t *device_ids, ffm_group **out) {
   if (!cfg || !out || n < 1 || n > 16 || !device_ids) return fail(FFM_E_INVALID, "bad group arguments (1 .. 16 engines)");
   *out = nullptr;
-  if (cfg->flags & (FFM_FLAG_SERVE_F32 | FFM_FLAG_SERVE_F16))
+  if (cfg->flags & kServeFlags)
     return fail(FFM_E_UNSUPPORTED, "a serving engine is one whole model on one device: not inside ffm_group_create");
   if (cfg->flags & FFM_FLAG_NORM_ROWS)
     return fail(FFM_E_INVALID, "FFM_FLAG_NORM_ROWS needs a whole model on one device: not inside ffm_group_create "

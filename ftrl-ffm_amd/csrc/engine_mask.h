@@ -16,6 +16,7 @@ int ffm_engine_set_pair_mask(ffm_engine *e, const uint64_t *keep, int32_t n_fiel
     return FFM_OK;
   }
   const std::string noun = "a pair mask";
+  F8_REFUSE(e, noun);
   if (m.type != FFM_MODEL_FFM) return fail(FFM_E_UNSUPPORTED, noun + " is FFM only: LR and FM rows have no fields");
   if (m.n_shards > 1 || e->in_group)
     return fail(FFM_E_UNSUPPORTED, noun + " needs a whole model on one device (n_shards == 1, not a group's engine)");

@@ -92,6 +92,7 @@ using ServeContextFn = void (*)(ModelDev, int, const int *, const int *, const i
 using ServeCandidateFn = void (*)(ModelDev, int, const int *, CandCtx, Rows, int, int, int *, float *, int);
 
 // fmt: ModelDev::lat_fmt -- SERVE_NONE (a training engine's records), SERVE_F32 or SERVE_F16 (a packed table of w).
+// (SERVE_F8 is in none of these families -- every selector here is null for it -- and has row8_wave_fn.)
 // FFM_BY_FMT: a family of the packed tables alone (a context and a candidate exist on a serving engine only: null
 // for SERVE_NONE); FFM_BY_ANY_FMT: one of all three (rows, field ablation).
 #define FFM_BY_FMT(KERNEL, LPP, VPL, U) \
@@ -103,6 +104,17 @@ inline RowWaveFn row_wave_fn(int fmt, int n_factors) {
 #define X(K, LPP, VPL, U) case K: return FFM_BY_ANY_FMT(ffm_row_wave_kernel, LPP, VPL, U);
     FFM_LANE_SHAPES(X)
 #undef X
+    default: return nullptr;
+  }
+}
+// the f8 table's row kernel (kernels_serve8.h: a pair per lane up to k = 16, then 2 / 4 lanes); <k, steps in flight>
+inline RowWaveFn row8_wave_fn(int n_factors) {
+  switch (n_factors) {
+    case 4: return ffm_row8_wave_kernel<4, 4>;
+    case 8: return ffm_row8_wave_kernel<8, 4>;
+    case 16: return ffm_row8_wave_kernel<16, 4>;
+    case 32: return ffm_row8_wave_kernel<32, 2>;
+    case 64: return ffm_row8_wave_kernel<64, 2>;
     default: return nullptr;
   }
 }

@@ -1,4 +1,4 @@
-// engine_serve.h -- serving engines (include/ffm_engine.h "Serving engines"): FFM_FLAG_SERVE_F32 / _F16 make
+// engine_serve.h -- serving engines (include/ffm_engine.h "Serving engines"): FFM_FLAG_SERVE_F32 / _F16 / _F8 make
 // an engine that stores the bias, lin_w and a packed table of w alone (kernels_serve.h) and answers every
 // prediction entry point; this file holds what create checks, the predict dispatch, the transfers between
 // the packed table and host arrays, ffm_engine_pack_weights and ffm_engine_model_bytes.
@@ -11,6 +11,8 @@ static_assert(sizeof(ffm_pack_stats) == PK_COUNT * sizeof(int64_t), "the kernel 
 static int serve_create_check(const ffm_engine_config *cfg) {
   if ((cfg->flags & FFM_FLAG_SERVE_F32) && (cfg->flags & FFM_FLAG_SERVE_F16))
     return fail(FFM_E_INVALID, "FFM_FLAG_SERVE_F32 and FFM_FLAG_SERVE_F16 exclude each other");
+  if ((cfg->flags & FFM_FLAG_SERVE_F8) && (cfg->flags & (FFM_FLAG_SERVE_F32 | FFM_FLAG_SERVE_F16)))
+    return fail(FFM_E_INVALID, "FFM_FLAG_SERVE_F8 excludes FFM_FLAG_SERVE_F32 and FFM_FLAG_SERVE_F16: a serving engine has one format");
   if (cfg->max_row_nnz > kPredLdsCap)
     return fail(FFM_E_INVALID, "a serving engine takes rows of at most " + std::to_string(kPredLdsCap) +
                                    " entries (max_row_nnz): it has no kernel for longer ones");
@@ -28,6 +30,7 @@ static int cand_common_check(ffm_engine *e, int32_t n_req, int32_t n_cand) {
   if (!serving(e))
     return fail(FFM_E_UNSUPPORTED, "score_candidates needs a serving engine (FFM_FLAG_SERVE_F32 / _F16): "
                                    "ffm_engine_pack_weights copies a training engine's weights into one");
+  F8_REFUSE(e, "score_candidates");
   MASK_REFUSE(e, "score_candidates");
   if (e->norm_rows_on)
     return fail(FFM_E_INVALID, "score_candidates is not available on an engine with FFM_FLAG_NORM_ROWS: the shared context "
@@ -151,6 +154,51 @@ int ffm_engine_score_candidates(ffm_engine *e, int32_t n_req, const int32_t *ctx
 
 // ---- packed table <-> host arrays (fp32 on the host; rounded / decoded on the device) ------------------
 
+// ---- the f8 table (kernels_serve8.h): whole rows through the encoder, or decoded ------------------------
+// A group of 16 or 64 lanes per row (serve8_group), grid-stride over the rows.
+static int serve8_grid(int64_t n_rows, int group) {
+  return static_cast<int>(std::min<int64_t>(2048, std::max<int64_t>(1, (n_rows * group + kServe8Threads - 1) / kServe8Threads)));
+}
+static void serve8_launch_init(ffm_engine *e, bool zero) {
+  const int G = serve8_group(e->m.row_len), grid = serve8_grid(e->m.n_feats, G);
+  hipLaunchKernelGGL(G == 16 ? serve8_init_kernel<16> : serve8_init_kernel<64>, dim3(grid), dim3(kServe8Threads), 0, e->stream, e->m,
+                     e->cfg.init_mean, e->cfg.init_stddev, e->cfg.seed, zero ? 1 : 0);
+}
+// nf rows in e->d_stage <-> features ids[j] (device; null: feat0 + j).  What the encoder rounded is added to
+// e->d_enc8 (made and cleared by the first call), for ffm_engine_encode_stats.
+static int serve8_launch_copy(ffm_engine *e, const int *ids, int64_t feat0, int64_t nf, bool to_host) {
+  if (to_host) {
+    hipLaunchKernelGGL(serve8_decode_kernel, dim3(1024), dim3(256), 0, e->stream, e->m, e->d_stage, ids, feat0, nf);
+    return FFM_OK;
+  }
+  if (!e->d_enc8) {
+    if (int rc = e->alloc(&e->d_enc8, static_cast<size_t>(PK_COUNT * kPackLine))) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_enc8, 0, PK_COUNT * kPackLine * sizeof(unsigned long long), e->stream));
+  }
+  const int G = serve8_group(e->m.row_len), grid = serve8_grid(nf, G);
+  hipLaunchKernelGGL(G == 16 ? serve8_encode_kernel<16> : serve8_encode_kernel<64>, dim3(grid), dim3(kServe8Threads), 0, e->stream, e->m,
+                     e->d_stage, ids, feat0, nf, e->d_enc8);
+  return FFM_OK;
+}
+
+// The counters of every latent element set_weights / set_rows have encoded on this f8 engine since create or the
+// last reset, as ffm_engine_pack_weights counts them.
+int ffm_engine_encode_stats(ffm_engine *e, int32_t reset, ffm_pack_stats *out) {
+  if (out) std::memset(out, 0, sizeof(*out));
+  if (!e) return fail(FFM_E_INVALID, "null engine");
+  if (e->m.lat_fmt != SERVE_F8) return fail(FFM_E_UNSUPPORTED, "encode_stats counts what an f8 serving engine (FFM_FLAG_SERVE_F8) encoded");
+  if (!e->d_enc8) return FFM_OK;
+  HIP_TRY(hipSetDevice(e->cfg.device_id));
+  unsigned long long h[PK_COUNT * kPackLine] = {};
+  HIP_TRY(hipMemcpyAsync(h, e->d_enc8, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+  if (reset) HIP_TRY(hipMemsetAsync(e->d_enc8, 0, sizeof(h), e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (out)
+    *out = ffm_pack_stats{static_cast<int64_t>(h[PK_LATENT * kPackLine]), static_cast<int64_t>(h[PK_INEXACT * kPackLine]),
+                          static_cast<int64_t>(h[PK_TO_INF * kPackLine]), static_cast<int64_t>(h[PK_TO_ZERO * kPackLine])};
+  return FFM_OK;
+}
+
 static int serve_vec_transfer(ffm_engine *e, float *host, bool to_host) {
   const int64_t RL = e->logical_len;
   const int64_t chunk = e->stage_floats / RL;
@@ -158,7 +206,10 @@ static int serve_vec_transfer(ffm_engine *e, float *host, bool to_host) {
     const int64_t nf = std::min<int64_t>(chunk, e->m.n_feats - f0);
     const size_t bytes = static_cast<size_t>(nf * RL) * sizeof(float);
     if (!to_host) HIP_TRY(hipMemcpyAsync(e->d_stage, host + f0 * RL, bytes, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(serve_dense_copy_kernel, dim3(1024), dim3(256), 0, e->stream, e->m, e->d_stage, f0, nf, to_host ? 1 : 0);
+    if (e->m.lat_fmt == SERVE_F8) {
+      if (int rc8 = serve8_launch_copy(e, nullptr, f0, nf, to_host)) return rc8;
+    } else
+      hipLaunchKernelGGL(serve_dense_copy_kernel, dim3(1024), dim3(256), 0, e->stream, e->m, e->d_stage, f0, nf, to_host ? 1 : 0);
     if (to_host) HIP_TRY(hipMemcpyAsync(host + f0 * RL, e->d_stage, bytes, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
   }
@@ -169,8 +220,11 @@ static int serve_vec_transfer(ffm_engine *e, float *host, bool to_host) {
 static int serve_rows_vec_transfer(ffm_engine *e, int nf, float *host, bool to_host) {
   const size_t bytes = static_cast<size_t>(nf) * e->logical_len * sizeof(float);
   if (!to_host) HIP_TRY(hipMemcpyAsync(e->d_stage, host, bytes, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(serve_rows_copy_kernel, dim3(1024), dim3(256), 0, e->stream, e->m, e->d_stage, e->d_ids,
-                     static_cast<int64_t>(nf), to_host ? 1 : 0);
+  if (e->m.lat_fmt == SERVE_F8) {
+    if (int rc8 = serve8_launch_copy(e, e->d_ids, 0, nf, to_host)) return rc8;
+  } else
+    hipLaunchKernelGGL(serve_rows_copy_kernel, dim3(1024), dim3(256), 0, e->stream, e->m, e->d_stage, e->d_ids,
+                       static_cast<int64_t>(nf), to_host ? 1 : 0);
   if (to_host) HIP_TRY(hipMemcpyAsync(host, e->d_stage, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return FFM_OK;
@@ -204,8 +258,15 @@ int ffm_engine_pack_weights(ffm_engine *dst, ffm_engine *src, ffm_pack_stats *ou
   const int64_t items = std::max<int64_t>(static_cast<int64_t>(src->m.n_feats) * (src->m.row_len / 4), src->m.n_feats);
   const int grid = static_cast<int>(std::min<int64_t>(std::max(1, cus) * 8, std::max<int64_t>(1, (items + kPackThreads - 1) / kPackThreads)));
   HIP_TRY(hipMemsetAsync(dst->d_pack, 0, PK_COUNT * kPackLine * sizeof(unsigned long long), dst->stream));
-  const auto pack = dst->m.lat_fmt == SERVE_F16 ? serve_pack_kernel<SERVE_F16> : serve_pack_kernel<SERVE_F32>;
-  hipLaunchKernelGGL(pack, dim3(grid), dim3(kPackThreads), 0, dst->stream, src->m, dst->m, dst->d_pack);
+  if (dst->m.lat_fmt == SERVE_F8) {  // a group of lanes per feature row (kernels_serve8.h)
+    const int G = serve8_group(dst->m.row_len);
+    const int grid8 = std::min(std::max(1, cus) * 8, serve8_grid(dst->m.n_feats, G));
+    hipLaunchKernelGGL(G == 16 ? serve_pack8_kernel<16> : serve_pack8_kernel<64>, dim3(grid8), dim3(kServe8Threads), 0, dst->stream,
+                       src->m, dst->m, dst->d_pack);
+  } else {
+    const auto pack = dst->m.lat_fmt == SERVE_F16 ? serve_pack_kernel<SERVE_F16> : serve_pack_kernel<SERVE_F32>;
+    hipLaunchKernelGGL(pack, dim3(grid), dim3(kPackThreads), 0, dst->stream, src->m, dst->m, dst->d_pack);
+  }
   HIP_TRY(hipGetLastError());
   unsigned long long h[PK_COUNT * kPackLine] = {};
   HIP_TRY(hipMemcpyAsync(h, dst->d_pack, sizeof(h), hipMemcpyDeviceToHost, dst->stream));
@@ -223,6 +284,7 @@ int ffm_engine_pack_weights(ffm_engine *dst, ffm_engine *src, ffm_pack_stats *ou
 int64_t ffm_engine_model_bytes(const ffm_engine *e) {
   if (!e) return 0;
   const int64_t nf = e->m.n_feats, n_w = e->n_records * static_cast<int64_t>(e->m.row_len);
+  if (e->m.lat_fmt == SERVE_F8) return 4 + 4 * nf + e->n_records * serve8_stride(e->m.row_len);
   if (serving(e)) return 4 + 4 * nf + (e->m.lat_fmt == SERVE_F16 ? 2 : 4) * n_w;
   return 12 + 12 * nf + 12 * n_w;
 }

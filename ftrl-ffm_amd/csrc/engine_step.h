@@ -36,7 +36,7 @@ static int check_block(ffm_engine *e, int32_t n_rows, int32_t nnz, const void *r
 static bool launch_row_waves(ffm_engine *e, const Rows &rows, int row_cap, float *out, int output_prob) {
   const ModelDev &m = e->m;
   if (!serving(e) && (!e->predict_waves || m.type != FFM_MODEL_FFM || m.n_shards > 1 || m.field_start || m.own_n || m.lin_own)) return false;
-  const RowWaveFn fn = row_wave_fn(m.lat_fmt, m.n_factors);
+  const RowWaveFn fn = m.lat_fmt == SERVE_F8 ? row8_wave_fn(m.n_factors) : row_wave_fn(m.lat_fmt, m.n_factors);
   if (!fn) return false;
   const int lds_cap = std::min(row_cap, kPredLdsCap);
   LAUNCH(e, serving(e) ? K_SERVE_ROW : K_PREDICT_ROW, fn, cdiv(rows.n_rows, kPredRows), 64 * kPredRows, pred_lds_bytes(lds_cap),

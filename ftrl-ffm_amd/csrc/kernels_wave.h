@@ -62,7 +62,7 @@ constexpr int wave_pairs_per_step() {
 }
 
 // ---- the formats of a slot -------------------------------------------------------------------------------
-enum { SERVE_NONE = 0, SERVE_F32 = 1, SERVE_F16 = 2 };  // ModelDev::lat_fmt
+enum { SERVE_NONE = 0, SERVE_F32 = 1, SERVE_F16 = 2, SERVE_F8 = 4 };  // ModelDev::lat_fmt (SERVE_F8: kernels_serve8.h, a row kernel of its own)
 
 __device__ __forceinline__ float serve_dec16(unsigned short h) { return __half2float(__ushort_as_half(h)); }
 // four consecutive halves as a lane loads them (8 bytes): element j in bits [16 j, 16 j + 16)

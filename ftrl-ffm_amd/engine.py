@@ -17,7 +17,8 @@ FLAG_LEARN = 4
 FLAG_HASH_IDS = 8
 FLAG_SERVE_F32, FLAG_SERVE_F16 = 16, 32
 FLAG_NORM_ROWS = 64
-SERVE_FLAGS = {None: 0, "none": 0, "f32": FLAG_SERVE_F32, "f16": FLAG_SERVE_F16}
+FLAG_SERVE_F8 = 128
+SERVE_FLAGS = {None: 0, "none": 0, "f32": FLAG_SERVE_F32, "f16": FLAG_SERVE_F16, "f8": FLAG_SERVE_F8}
 E_INVALID, E_DEVICE, E_NOMEM, E_CAPACITY, E_UNSUPPORTED = -1, -2, -3, -4, -5  # FFM_E_*
 
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -227,6 +228,7 @@ ABI = [
      [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.c_int32, _i32p, _i32p, _i32p]),
     # weights only, for prediction (include/ffm_engine.h "Serving engines")
     ("ffm_engine_pack_weights", ctypes.c_int, [_vp, _vp, ctypes.POINTER(PackStats)]),
+    ("ffm_engine_encode_stats", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(PackStats)]),
     ("ffm_engine_model_bytes", ctypes.c_int64, [_vp]),
     # one context against many candidates (include/ffm_engine.h "Scoring candidates")
     ("ffm_engine_score_candidates", ctypes.c_int,
@@ -449,6 +451,65 @@ def init_weights_host(seed, mean, stddev, latent, first, count):
     if rc != 0:
         raise EngineError(rc, load_library().ffm_engine_last_error().decode())
     return out
+
+
+# ---- the `f8` serving format (include/ffm_engine.h "Serving engines"), defined the plain way: what
+# numpy's astype(float16) is to "f16".  A row is e4m3fn bytes behind one power-of-two scale.
+def _f8_table():
+    """value of each of the 256 e4m3fn codes (1 sign, 4 exponent, 3 mantissa bits, bias 7; S.1111.111 is NaN)."""
+    code = np.arange(256)
+    e, m = (code >> 3) & 15, (code & 7).astype(np.float64)
+    mag = np.where(e == 0, m * 2.0 ** -9, (8.0 + m) * 2.0 ** (e.astype(np.float64) - 10.0))
+    mag[(code & 127) == 127] = np.nan
+    return np.where(code >= 128, -mag, mag).astype(np.float32)
+
+
+SERVE_F8_VALUE = _f8_table()
+
+
+def serve_f8_stride(row_len):
+    """Bytes of one feature row of an f8 table: a 16-byte head (the scale, twelve zero bytes), then the padded bytes."""
+    return 16 + (int(row_len) + 15) // 16 * 16
+
+
+def serve_f8_encode(rows):
+    """rows float32 [n, row_len] -> (bytes uint8 [n, round_up(row_len, 16)], scales float32 [n]).  Per row: A = the
+    largest finite |w|; scale 1.0 if that is 0, else 2^s with s = clamp(floor(log2 A) - 8, -117, 119) from A's
+    exponent field (a subnormal A: -117), plus 1 if A * 2^-s > 448.  Byte = nearest-even e4m3fn of w * 2^-s among
+    the finite codes, the sign of a zero kept; NaN and +-inf become the NaN byte with their sign.  Padding is zero."""
+    w = np.atleast_2d(np.ascontiguousarray(rows, np.float32))
+    n, rl = w.shape
+    bits = w.view(np.uint32)
+    ab = bits & 0x7fffffff
+    finite = ab < 0x7f800000
+    a_bits = np.where(finite, ab, 0).max(axis=1, initial=0).astype(np.uint32)
+    e = (a_bits >> 23).astype(np.int64)
+    s = np.where(e == 0, -117, np.clip(e - 127 - 8, -117, 119))
+    s = np.where(a_bits == 0, 0, s)
+    with np.errstate(all="ignore"):
+        over = a_bits.view(np.float32) * np.ldexp(np.float32(1), -s).astype(np.float32) > np.float32(448)
+        s = s + over
+        inv, scales = np.ldexp(np.float32(1), -s).astype(np.float32), np.ldexp(np.float32(1), s).astype(np.float32)
+        x = np.abs(w * inv[:, None]).astype(np.float64)  # (float32 product first: exact, or far below 2^-10)
+    pos = SERVE_F8_VALUE[:127].astype(np.float64)        # codes 0 .. 126 ascend
+    mid = (pos[:-1] + pos[1:]) / 2
+    x_f = np.where(finite, x, 0.0)
+    lo = np.searchsorted(mid, x_f, side="left")          # mid[lo - 1] < x <= mid[lo]
+    tie = (lo < 126) & (x_f == mid[np.minimum(lo, 125)])
+    q = np.where(tie & (lo % 2 == 1), lo + 1, lo).astype(np.uint8)  # a tie goes to the even code
+    q = np.where(finite, q, 0x7f).astype(np.uint8) | ((bits >> 24) & 0x80).astype(np.uint8)
+    out = np.zeros((n, (rl + 15) // 16 * 16), np.uint8)
+    out[:, :rl] = q
+    return out, scales
+
+
+def serve_f8_decode(q, scales, row_len=None):
+    """The reverse: fl(value(byte) * scale) in float32 (exact; the NaN byte decodes to NaN), [n, row_len]."""
+    q = np.atleast_2d(np.asarray(q, np.uint8))
+    if row_len is not None:
+        q = q[:, :row_len]
+    with np.errstate(all="ignore"):
+        return (SERVE_F8_VALUE[q] * np.asarray(scales, np.float32).reshape(-1, 1)).astype(np.float32)
 
 
 def hash_ids(field, feat, n_feats, field_start=None, model="ffm", n_fields=None):
@@ -921,11 +982,12 @@ class Engine:
                  serve=None, normalize=False):
         """normalize: every row handed over in host memory is scaled to unit Euclidean length on the device before
         any kernel reads its values (include/ffm_engine.h "Normalised rows"; normalize_rows is the same on the host).
-        serve: None = a training engine; "f32" / "f16" = a serving engine (include/ffm_engine.h "Serving
-        engines"): bias, lin_w and a latent table of w alone in fp32 bits or IEEE binary16 -- prediction only."""
+        serve: None = a training engine; "f32" / "f16" / "f8" = a serving engine (include/ffm_engine.h "Serving
+        engines"): bias, lin_w and a latent table of w alone in fp32 bits, IEEE binary16 or block-scaled e4m3
+        (serve_f8_encode is that format's definition) -- prediction only."""
         self.lib = load_library()
         if serve not in SERVE_FLAGS:
-            raise ValueError("serve: None, 'f32' or 'f16'")
+            raise ValueError("serve: None, 'f32', 'f16' or 'f8'")
         self.serve = serve if SERVE_FLAGS[serve] else None
         cfg = Config()
         self.lib.ffm_engine_default_config(ctypes.byref(cfg))
@@ -1001,6 +1063,13 @@ class Engine:
         self._check(self.lib.ffm_engine_pack_weights(self.h, src.h, ctypes.byref(st)))
         return st.as_dict()
 
+    def encode_stats(self, reset=False):
+        """An f8 serving engine: pack_from's counters over what set_weights / set_rows have encoded since create or the
+        last reset (ffm_engine_encode_stats)."""
+        st = PackStats()
+        self._check(self.lib.ffm_engine_encode_stats(self.h, int(bool(reset)), ctypes.byref(st)))
+        return st.as_dict()
+
     # ---- serving deltas (include/ffm_engine.h "Serving deltas") ----
     def sync_from(self, src):
         """pack_from(src) by comparison (ffm_engine_sync_weights): afterwards this serving engine holds, bit for
@@ -1021,6 +1090,8 @@ class Engine:
     def _raw_dtype(self):
         if not self.serve:
             raise EngineError(E_UNSUPPORTED, "raw rows are a serving engine's: a training engine has get_rows / set_rows")
+        if self.serve not in RAW_DTYPES:
+            raise EngineError(E_UNSUPPORTED, "raw rows and serving deltas are not available on an %s serving engine" % self.serve)
         return RAW_DTYPES[self.serve]
 
     def get_rows_raw(self, ids):

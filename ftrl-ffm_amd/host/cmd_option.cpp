@@ -99,7 +99,9 @@ const std::string_view cmd_help =
     "              model, the checkpoint and every id printed are hashed ids; --n_feats bounds the model, not the data\tdefault:false\n"
     "--serve_weights <none|f32|f16>: score a saved model from a serving engine, which holds the weights alone (no n, z):\n"
     "              f32 = the same fp32 bits in a third of the memory, the same predictions bit for bit; f16 = IEEE half\n"
-    "              precision (round to nearest even) in a sixth of the memory, half the bytes read per prediction.  Only\n"
+    "              precision (round to nearest even) in a sixth of the memory, half the bytes read per prediction.  Also\n"
+    "              f8 = block-scaled e4m3 bytes (one power-of-two scale per feature row) in a twelfth of the memory, scored by a\n"
+    "              kernel of its own; prints `f8 pack: n_latent .. n_inexact .. n_to_inf .. n_to_zero ..` after the load.  Only\n"
     "              with --resume_from ck --n_epochs 0 (then --predict_data / --predict_out, --predict_output, --metrics auc\n"
     "              and --hash_feats as always); FFM only, one GPU, rows of at most 128 entries, no training: refused with\n"
     "              --n_epochs > 0, --model_path, --checkpoint_path, --n_gpus > 1 and --refresh_weights true (write the\n"
@@ -352,7 +354,7 @@ void config_options::parse_option(int argc, char *argv[]) {
     }
     else if (k == "--weight_data") { weight_path = v; weights_given = true; }
     else if (k == "--serve_weights") {
-      if (v != "none" && v != "f32" && v != "f16") throw std::invalid_argument("--serve_weights takes none, f32 or f16");
+      if (v != "none" && v != "f32" && v != "f16" && v != "f8") throw std::invalid_argument("--serve_weights takes none, f32 or f16 (or f8, block-scaled e4m3)");
       serve_weights = v;
     }
     else if (k == "--auc_key_field" || k == "--auc_key_rows") {
@@ -369,6 +371,7 @@ void config_options::parse_option(int argc, char *argv[]) {
       publish_path = v;
     }
     else if (k == "--publish_weights") {
+      if (v == "f8") throw std::invalid_argument("--publish_weights f8: serving deltas are not available in the f8 format (f32 or f16)");
       if (v != "f32" && v != "f16") throw std::invalid_argument("--publish_weights takes f32 or f16");
       publish_weights = v;
     }
@@ -451,6 +454,7 @@ void config_options::parse_option(int argc, char *argv[]) {
     // a fresh serving engine plus the published deltas (refused here, before a device is opened)
     const std::string what = "--apply_deltas " + apply_deltas + " ";
     if (serve_weights == "none") throw std::invalid_argument(what + "fills a serving engine: it needs --serve_weights f32 or f16");
+    if (serve_weights == "f8") throw std::invalid_argument(what + "is not available with --serve_weights f8: serving deltas are f32 or f16");
     if (!resume_from.empty()) throw std::invalid_argument(what + "starts from a fresh serving engine: --resume_from is not allowed with it");
     if (epoch > 0) throw std::invalid_argument(what + "cannot train: it needs --n_epochs 0 (got --n_epochs " + std::to_string(epoch) + ")");
     const std::string first = apply_deltas + ".1.delta";

@@ -54,7 +54,7 @@ struct config_options {
   // --device_rows: online training, evaluation and --predict_data read their files as raw bytes, the device parses
   // them and cuts the blocks in HBM (include/ffm_engine.h "Resident rows", row_stream.h); no result changes
   bool device_rows = false;
-  // --serve_weights none | f32 | f16: score a saved model from a serving engine (FFM_FLAG_SERVE_F32 / _F16: the
+  // --serve_weights none | f32 | f16 | f8: score a saved model from a serving engine (FFM_FLAG_SERVE_F32 / _F16 / _F8: the
   // weights alone, in fp32 bits or IEEE binary16); only with --resume_from ck --n_epochs 0
   std::string serve_weights = "none";
   // --compact_rows: blocks whose values are all 1.0f / whose rows are one entry per field in field order cross

@@ -68,9 +68,10 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
   serve_fmt_ = opt.serve_weights;
   device_ = opt.device;
   if (serving_) {
-    if (opt.serve_weights != "f32" && opt.serve_weights != "f16") throw std::invalid_argument("serve_weights: none, f32 or f16");
+    if (opt.serve_weights != "f32" && opt.serve_weights != "f16" && opt.serve_weights != "f8")
+      throw std::invalid_argument("serve_weights: none, f32, f16 or f8");
     if (opt.n_gpus > 1) throw std::invalid_argument("a serving engine is one whole model on one GPU (n_gpus == 1)");
-    cfg.flags |= opt.serve_weights == "f16" ? FFM_FLAG_SERVE_F16 : FFM_FLAG_SERVE_F32;
+    cfg.flags |= opt.serve_weights == "f8" ? FFM_FLAG_SERVE_F8 : opt.serve_weights == "f16" ? FFM_FLAG_SERVE_F16 : FFM_FLAG_SERVE_F32;
     max_row_nnz_ = 128;
     max_nnz_ = static_cast<int>(std::min<long long>(std::max<long long>(256ll * max_rows_, max_row_nnz_), 1ll << 28));
     cfg.max_batch_nnz = max_nnz_;
@@ -895,6 +896,9 @@ FtrlModel::TrainProgress FtrlModel::load_checkpoint(std::string_view file_name) 
   const size_t rl = static_cast<size_t>(row_len_), n = r.ids().size();
   const size_t cap = std::min(static_cast<size_t>(h.chunk), std::max<size_t>(n, 1));
   std::vector<float> lin(3 * cap), vec(3 * cap * rl);
+  // an f8 serving model: the rows are packed as they arrive, and the encoder counts them (ffm_engine_encode_stats)
+  const bool pack8 = serving_ && serve_fmt_ == "f8";
+  if (pack8) check(ffm_engine_encode_stats(eng_, 1, nullptr), "ffm_engine_encode_stats");
   size_t j0 = 0;
   while (const size_t c = r.next_chunk_size()) {
     float *lw = lin.data(), *ln = lw + c, *lz = ln + c;
@@ -908,6 +912,11 @@ FtrlModel::TrainProgress FtrlModel::load_checkpoint(std::string_view file_name) 
   }
   r.finish();
   std::printf("loading from %s, changed features: %zu of %d\n", name.c_str(), n, n_feats);
+  ffm_pack_stats packed{};
+  if (pack8) check(ffm_engine_encode_stats(eng_, 0, &packed), "ffm_engine_encode_stats");
+  if (pack8)
+    std::printf("f8 pack: n_latent %lld, n_inexact %lld, n_to_inf %lld, n_to_zero %lld\n", static_cast<long long>(packed.n_latent),
+                static_cast<long long>(packed.n_inexact), static_cast<long long>(packed.n_to_inf), static_cast<long long>(packed.n_to_zero));
   pull_linear();
   vec_w.dense_ready_ = false;
   vec_w.dense_.clear();

@@ -117,9 +117,11 @@ enum {
                            * before any kernel reads them: "Hashed ids" below */
   FFM_FLAG_SERVE_F32 = 16, /* a SERVING engine: weights only, for prediction -- "Serving engines" below; */
   FFM_FLAG_SERVE_F16 = 32, /* its latent table in fp32 bits or in IEEE binary16 (both: FFM_E_INVALID) */
-  FFM_FLAG_NORM_ROWS = 64  /* every HOST row is scaled to unit Euclidean length on the device before any kernel
+  FFM_FLAG_NORM_ROWS = 64, /* every HOST row is scaled to unit Euclidean length on the device before any kernel
                             * reads its values (libffm's and xLearn's instance-wise normalisation):
                             * "Normalised rows" below */
+  FFM_FLAG_SERVE_F8 = 128  /* a SERVING engine whose latent table is block-scaled OCP e4m3 (the `f8` format of
+                            * "Serving engines" below); more than one FFM_FLAG_SERVE_* is FFM_E_INVALID */
 };
 
 void ffm_engine_default_config(ffm_engine_config *cfg);
@@ -976,6 +978,27 @@ int ffm_group_refresh_weights(ffm_group *g, ffm_refresh_stats *out);
  *         half range to +-inf, NaN stays NaN (payload unspecified) -- numpy's astype(float16); decoding is the
  *         exact half -> float conversion.  A prediction is, bit for bit, the fp32 arithmetic of
  *         ffm_engine_predict_batch on the DECODED weights, in the same order.  The linear weights stay fp32.
+ * f8      FFM_FLAG_SERVE_F8 (more than one FFM_FLAG_SERVE_* is FFM_E_INVALID): block-scaled OCP e4m3, a twelfth of
+ *         a training engine's latent bytes.  Fixed bit for bit:
+ *         layout   one row per feature of 16 + round_up(row_len, 16) bytes (row_len = n_fields * n_factors): bytes
+ *                  0-3 the row's scale, an fp32 power of two; bytes 4-15 zero; element j at byte 16 + j; padding
+ *                  zero.  Slot (feat, field) starts at 16 + field * n_factors, aligned to min(n_factors, 16).
+ *         element  e4m3fn: 1 sign, 4 exponent, 3 mantissa bits, bias 7; subnormals are multiples of 2^-9; the largest
+ *                  finite value is 448; no infinity; S.1111.111 is NaN.
+ *         scale    A = the largest |w| over the row's finite elements.  A == 0 or no finite element: 1.0f.  Otherwise
+ *                  s = clamp(floor(log2 A) - 8, -117, 119) from A's exponent field (a subnormal A: -117), plus 1 if
+ *                  A * 2^-s > 448; the scale is 2^s.  The lower clamp keeps every decoded value normal or zero.
+ *         encode   q = e4m3fn(w * 2^-s), nearest even among the finite values, the sign of a zero kept (no finite w
+ *                  exceeds 448 after scaling); a NaN or an infinity becomes the NaN byte with its sign.
+ *         decode   fl(value(q) * scale) in fp32, which is exact; the NaN byte is NaN.  A prediction is, bit for bit,
+ *                  the fp32 arithmetic of ffm_engine_predict_batch on the DECODED weights, in the same order -- the
+ *                  statement the fp16 table makes.  ffm_pack_stats keeps its meaning (n_to_inf is reachable only
+ *                  within a factor of two of FLT_MAX).  ftrl_ffm_amd.serve_f8_encode / serve_f8_decode are this
+ *                  definition in numpy.
+ *         writes   set_weights / set_rows write WHOLE rows: a row's scale is recomputed from the values given.
+ *         refused  FFM_E_UNSUPPORTED with a message naming the format, the model unchanged: score_candidates,
+ *                  set_pair_mask, the ablation and curve calls, sync_weights, get_rows_raw / set_rows_raw.  Rows are
+ *                  scored by a kernel of its own (csrc/kernels_serve8.h); the profile label stays "serve_wave_kernel".
  * create  every element is what a training engine of the same config would draw
  *         (ffm_engine_init_weights_host: same seed and index), rounded to the format; FFM_FLAG_SKIP_INIT gives
  *         zero bits.  So a sparse checkpoint -- a delta to a fresh engine -- means on a serving engine what it
@@ -1005,9 +1028,15 @@ int ffm_group_refresh_weights(ffm_group *g, ffm_refresh_stats *out);
 typedef struct { int64_t n_latent, n_inexact, n_to_inf, n_to_zero; } ffm_pack_stats;
 int ffm_engine_pack_weights(ffm_engine *dst, ffm_engine *src, ffm_pack_stats *out);
 
+/* An f8 serving engine only (anything else: FFM_E_UNSUPPORTED): the same counters over every latent element that
+ * ffm_engine_set_weights / set_rows have encoded since create or the last call with reset != 0 -- what loading a
+ * checkpoint row by row rounded, where ffm_engine_pack_weights was not the way in.  out may be NULL.  Synchronous. */
+int ffm_engine_encode_stats(ffm_engine *e, int32_t reset, ffm_pack_stats *out);
+
 /* Bytes of HBM requested for the model arrays (bias, linear, latent) of any engine: an unsharded FFM
  * training engine 12 + 12 * n_feats + 12 * n_feats * row_len, a serving engine 4 + 4 * n_feats +
- * B * n_feats * row_len with B = 4 (fp32) or 2 (fp16); a shard counts the records it stores. */
+ * B * n_feats * row_len with B = 4 (fp32) or 2 (fp16), an f8 serving engine 4 + 4 * n_feats + n_feats *
+ * (16 + round_up(row_len, 16)); a shard counts the records it stores. */
 int64_t ffm_engine_model_bytes(const ffm_engine *e);
 
 /* ---- Scoring candidates: one context against many candidates, on a serving engine ----------------------

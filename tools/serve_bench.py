@@ -4,7 +4,7 @@
 
   python tools/serve_bench.py                 the three kinds, one process each, one after another (the three
                                               models do not fit in HBM together), a summary at the end
-  python tools/serve_bench.py --kind f16      one kind, one JSON line
+  python tools/serve_bench.py --kind f16      one kind (training, f32, f16, f8), one JSON line
   python tools/serve_bench.py --candidates 26:13:64
                                               one context against many candidates (include/ffm_engine.h "Scoring
                                               candidates"; profiles/score_candidates.md): per serving format,
@@ -28,16 +28,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 N_FIELDS, N_FACTORS, FEATS, ROWS = 39, 16, 33_000_000, 8192
-KINDS = ("training", "f32", "f16")
+KINDS = ("training", "f32", "f16", "f8")
 HBM_PEAK = 8e12  # bytes/s (spec)
 
 
 def bytes_per_row(kind, n_fields=N_FIELDS, k=N_FACTORS):
     """Bytes the algorithm needs per row: both slots of every field pair (k elements of 4 or 2 bytes each),
     the entries (field, id, value), their linear weights, the row's pointer, label and output."""
-    elem = 2 if kind == "f16" else 4
+    elem = 1 if kind == "f8" else 2 if kind == "f16" else 4
     pairs = n_fields * (n_fields - 1) // 2
-    return pairs * 2 * k * elem + n_fields * (12 + 4) + 4 + 4 + 4
+    scales = 4 * n_fields if kind == "f8" else 0  # (one scale word per entry: kernels_serve8.h)
+    return pairs * 2 * k * elem + n_fields * (12 + 4) + scales + 4 + 4 + 4
 
 
 def run_kind(args):
@@ -311,8 +312,8 @@ def main():
     ap.add_argument("--out", help="also write the results there as JSON")
     args = ap.parse_args()
     if args.candidates:
-        if args.kind == "training":
-            raise SystemExit("--candidates needs a serving kind (f32 or f16)")
+        if args.kind in ("training", "f8"):  # (an f8 engine refuses score_candidates)
+            raise SystemExit("--candidates needs a serving kind that scores candidates (f32 or f16)")
         return run_candidates(args) if args.kind else main_candidates(args)
     if args.kind:
         return run_kind(args)
