@@ -6,11 +6,11 @@ import numpy as np
 import pytest
 
 import ftrl_ffm_amd as fa
-from util import (BIG_F, BIG_FM_STRIDE, BIG_K, BIG_L, BIG_NF, BIG_NF_FM, BIG_NF_TRAIN_INIT, BIG_NF_VEC_SERVE, BIG_NF_VEC_TRAIN, alias_ids, big_case,
+from util import (BIG_F, BIG_FM_STRIDE, BIG_K, BIG_L, BIG_LAYOUTS, BIG_NF, BIG_NF_FM, BIG_NF_TRAIN_INIT, BIG_NF_VEC_SERVE, BIG_NF_VEC_TRAIN, alias_ids, big_case,
                   big_step, big_tier_entries, big_upper_zeroed, bits, count_past, edge_ids, nonfinite_share, offset_tier,
                   straddling_ids)
 
-CASES = ("ffm", "fm", "vec_serve", "vec_train")
+CASES = ("ffm", "fm", "vec_serve", "vec_train", "ffm_f8")
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -38,7 +38,7 @@ def test_feature_counts_cross_both_thresholds():
 
 @pytest.mark.parametrize("n_feats,stride,elem_bytes,unit", [
     (BIG_NF, BIG_L, 2, 1), (BIG_NF, BIG_L, 4, 1), (BIG_NF, 3 * BIG_L, 4, 1), (BIG_NF_FM, BIG_FM_STRIDE, 4, 1), (3441481, BIG_L, 4, 1),
-    (1000, 16, 4, 1), (BIG_NF_VEC_SERVE, BIG_L, 2, 4), (BIG_NF_VEC_TRAIN, 3 * BIG_L, 4, 4)])
+    (1000, 16, 4, 1), (BIG_NF_VEC_SERVE, BIG_L, 2, 4), (BIG_NF_VEC_TRAIN, 3 * BIG_L, 4, 4), (BIG_NF, BIG_LAYOUTS["f8"][0], 1, 1)])
 def test_edge_ids_against_brute_force(n_feats, stride, elem_bytes, unit):
     elems = [2 ** 31 * unit, 2 ** 32 * unit]
     byte_offsets = [2 ** 32, 2 ** 33, 2 ** 34]
@@ -173,3 +173,35 @@ def test_at_most_a_tenth_is_non_finite(name):
     assert np.array_equal(changed, np.unique(c.compact_block.feat))
     # prediction on the stepped model, which the GPU module compares as well
     assert np.isfinite(c.oracle(after).predict_batch(c.compact_block)[0]).mean() >= 0.9
+
+
+def test_the_f8_case_on_its_decoded_table():
+    """The f8 table's layout is bytes: 640 per feature at 39 x 16, so byte 2^31 falls in feature 3 355 443 and byte 2^32
+    in feature 6 710 886, both inside BIG_NF features.  What tests/test_gpu_big_offsets.py's f8 cases take for granted,
+    on the weights an f8 engine holds (serve_f8_decode of serve_f8_encode): the oracle stays finite, and a byte offset
+    wrapped at 2^31 or 2^32 -- which lands on zeros or on another probe's row -- changes every row."""
+    c = big_case("ffm_f8")
+    stride, eb = c.layouts["f8"]
+    assert (stride, eb) == (fa.serve_f8_stride(BIG_L), 1) and stride == 640 and list(c.layouts) == ["f8"]
+    assert c.straddlers() == [2 ** 31 // stride, 2 ** 32 // stride] == [3355443, 6710886] and c.n_feats * stride > 2 ** 32
+    assert set(c.straddlers()) <= set(c.block.feat.tolist())
+    n = big_tier_entries(c, "f8")
+    assert min(n[0], n[1], n[2]) >= 100, n
+    held = fa.serve_f8_decode(*fa.serve_f8_encode(c.state["vec_w"]), row_len=BIG_L)
+    assert not ((held != 0) & (np.abs(held) < np.float32(2.0 ** -126))).any()
+    whole = c.weights_oracle(held).predict_batch(c.compact_block)[0]
+    nonempty = np.diff(c.block.row_ptr) > 0
+    assert np.isfinite(whole).all()
+    assert np.isfinite(c.weights_oracle(held).predict_batch(c.compact_block, output_prob=True)[0]).all()
+    for tiers in ((1, 2, -1), (2,)):  # a wrapped offset that finds zeros
+        hit = c.compact[np.isin(c.tiers("f8"), tiers)]
+        vw, lw = held.copy(), c.state["lin_w"].copy()
+        vw[hit] = 0
+        lw[hit] = 0
+        assert (bits(c.weights_oracle(vw, lw).predict_batch(c.compact_block)[0]) != bits(whole))[nonempty].all(), tiers
+    up = c.compact[c.tiers("f8") != 0]  # ... or another probe's row
+    vw = held.copy()
+    vw[up] = held[np.roll(up, 1)]
+    assert (bits(c.weights_oracle(vw).predict_batch(c.compact_block)[0]) != bits(whole))[nonempty].all()
+    # ... and the decoded weights are not the fp32 ones: the f8 engine has a reference of its own
+    assert (bits(c.weights_oracle(c.state["vec_w"]).predict_batch(c.compact_block)[0]) != bits(whole))[nonempty].all()

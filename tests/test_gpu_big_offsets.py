@@ -3,9 +3,12 @@
 FFM 39 x 16 at util.BIG_NF = 6 882 969 features -- the smallest count with 8 records wholly past element 2^32 of a
 serving table (624 elements per feature): an fp16 serving engine (8.6 GB), an fp32 one (17.2 GB) and a training
 engine (records of 3 x 624: 51.5 GB), all created with skip_init and held for the module; FM k = 64 at util.BIG_NF_FM
-= 22 369 630 features (records of 192: 17.2 GB).  The module needs about 80 GB of HBM for its three engines and up
-to 52 GB more while a case holds a second engine (130 GB at its peak; case 12 holds 92 GB after the others are
-closed); a fixture or case that finds less skips, as tests/test_gpu_scale.py does.  A signed 32-bit element index breaks at 2^31; an unsigned one, or a 32-bit byte offset into 4-byte elements,
+= 22 369 630 features (records of 192: 17.2 GB).  An f8 serving engine at the same count (rows of 640 bytes: 4.4 GB;
+byte 2^31 lies in feature 3 355 443, byte 2^32 in feature 6 710 886) is held from case 13 to case 15, with a probe
+set, block and alias ids of its own (util.big_case("ffm_f8")), so that the twelve cases before it keep theirs.  The
+module needs about 80 GB of HBM for its three engines and up to 52 GB more while a case holds a second engine (130 GB
+at its peak; cases 13 to 15 add 4.4 GB to the three, case 16 holds 4.4 GB more for its own engine; case 12 holds 92 GB
+after the others are closed); a fixture or case that finds less skips, as tests/test_gpu_scale.py does.  A signed 32-bit element index breaks at 2^31; an unsigned one, or a 32-bit byte offset into 4-byte elements,
 at 2^32 -- the probe ids (util.big_probe_ids) sit on both sides of both, in every layout, with the records that
 straddle them and their neighbours.
 
@@ -34,10 +37,19 @@ case  what runs -- the kernel it is there for -- the yardstick
 10    create without skip_init -- init_weights_kernel, serve_init_kernel -- init_weights_host at the draw indices
 11    train_batch (FFM; FM k = 64 with predict_batch) -- the row and update kernels -- the oracle's train_batch
 12    cases 1-4, 6-9 and 11 where the index of a vector of four factors passes 2^31 and 2^32 (see there)
+13    f8: set_rows of the probes, predict_batch, predict_batch_async with scores -- ffm_row8_wave_kernel's byte
+      addressing -- the oracle on serve_f8_decode(serve_f8_encode(probe rows))
+14    f8: set_rows / get_rows -- serve8_encode_kernel, serve8_decode_kernel -- numpy's bytes decoded, encode_stats equal
+      to numpy's counts, alias rows zero (a zero row decodes to +0.0 under scale 1.0)
+15    f8: pack_from the held training engine -- serve_pack8_kernel -- decoded compact state, numpy's counts, alias rows
+      zero (the training engine holds this case's probe rows meanwhile, and case 1's again afterwards)
+16    f8: create without skip_init -- serve8_init_kernel -- init_weights_host at the draw indices, encoded by numpy;
+      model_bytes
+(The module's order is 1-11, 13-16, 12: the f8 cases run while the training engine is held.)
 
 Left out on purpose: get_weights / set_weights of a whole table move 9 to 17 GB across PCIe into a host array of that
 size, which is no test of a few seconds -- serve_dense_copy_kernel stays pinned at small sizes only
-(tests/test_gpu_serve.py)."""
+(tests/test_gpu_serve.py; the f8 table's whole-table transfers: tests/test_gpu_serve_f8.py, past their first chunk)."""
 import ctypes
 import functools
 
@@ -51,6 +63,8 @@ from ftrl_ffm_amd.synth import Block
 from test_gpu_pair_mask import all_pairs, masked_weights, seeded_pairs
 from test_gpu_refresh_weights import _expected as refresh_expected
 from test_gpu_serve import decoded, rounding_table
+from test_gpu_serve_f8 import counted
+from test_serve_f8_host import edge_rows
 from util import (BIG_F, BIG_FM_K, BIG_K, BIG_L, BIG_LAYOUTS, BIG_NF, BIG_NF_FM, BIG_NF_TRAIN_INIT, assert_bitwise,
                   big_case, big_step, bits, edge_ids, get_bias3, loss_close, nonfinite_share, set_bias3, straddling_ids)
 
@@ -79,7 +93,7 @@ def table_gb(kind, n_feats):
 
 
 def fmt_of(kind):
-    return "f16" if kind == "f16" else "f32"  # (a training engine and an fp32 serving engine hold the same w bits)
+    return kind if kind in ("f16", "f8") else "f32"  # (a training engine and an fp32 serving engine hold the same w bits)
 
 
 def make(kind, n_feats=BIG_NF, **kw):
@@ -149,7 +163,7 @@ def assert_aliases_zero(e, c, what):
     got = e.get_rows(c.aliases(kind_of(e)))
     for key, a in got.items():
         assert not bits(a).any(), "%s: %s of a record a wrapped index would hit is no longer zero" % (what, key)
-    if e.serve:
+    if e.serve and e.serve != "f8":  # (an f8 engine has no raw rows)
         lw, lat = e.get_rows_raw(c.aliases(kind_of(e)))
         assert not bits(lw).any() and not lat.view(np.uint16).any(), what
 
@@ -563,10 +577,11 @@ def assert_changed_are_the_probes(t, c):
 
 # ---- 10. create-time contents ------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("kind,n_feats", [("train", BIG_NF_TRAIN_INIT), ("f16", BIG_NF)])
+@pytest.mark.parametrize("kind,n_feats", [("train", BIG_NF_TRAIN_INIT), ("f16", BIG_NF), ("f8", BIG_NF)])
 def test_create_time_contents(kind, n_feats):
+    """(case 10; case 16 is its f8 parameter: serve8_init_kernel, and model_bytes of a table counted in bytes)"""
     stride, eb = BIG_LAYOUTS[kind]
-    assert (n_feats - 8) * stride >= 2 ** 32 > (n_feats - 9) * stride
+    assert (n_feats - 8) * stride >= 2 ** 32 and (kind == "f8" or 2 ** 32 > (n_feats - 9) * stride)
     need(table_gb(kind, n_feats))
     seed, mean, sd = 1234, 0.01, 0.05
     e = make(kind, n_feats, skip_init=False, seed=seed, init_mean=mean, init_stddev=sd)
@@ -582,6 +597,8 @@ def test_create_time_contents(kind, n_feats):
             for key in ("lin_n", "lin_z", "vec_n", "vec_z"):
                 assert not bits(got[key]).any(), key
             assert e.changed_features().size == 0  # every w against its draw, the records past 2^32 among them
+        if kind == "f8":
+            assert stride == fa.serve_f8_stride(BIG_L) and e.model_bytes() == 4 + 4 * n_feats + n_feats * stride > 2 ** 32
     finally:
         e.close()
 
@@ -630,6 +647,91 @@ def test_one_training_step_fm():
         e.close()
 
 
+# ---- 13 - 15. the f8 table past byte 2^31 and byte 2^32 -------------------------------------------------------------
+# (case 16 is test_create_time_contents[f8-...])
+
+@pytest.fixture(scope="module")
+def f8_case():
+    c = big_case("ffm_f8")
+    stride = c.layouts["f8"][0]
+    assert stride == fa.serve_f8_stride(BIG_L) and c.n_feats == BIG_NF and c.straddlers() == [2 ** 31 // stride, 2 ** 32 // stride]
+    t = c.tiers("f8", c.block.feat)  # (tests/test_big_offsets_host.py checks the rest)
+    assert min((t == 0).sum(), (t == 1).sum(), (t == 2).sum()) >= 100 and set(c.straddlers()) <= set(c.block.feat.tolist())
+    return c
+
+
+def zero_rows(e, ids):
+    keys = ("lin_w", "vec_w") if e.serve else ROW_KEYS
+    e.set_rows(ids, {key: np.zeros((ids.size, e.row_len) if key.startswith("vec") else ids.size, np.float32) for key in keys})
+
+
+def test_f8_prediction(f8_case, engines):
+    run_prediction(f8_case, engines("f8", "ffm_f8"), "ffm_f8")
+    assert_aliases_zero(engines("f8", "ffm_f8"), f8_case, "f8 after set_rows")
+
+
+def test_f8_rows_in_and_out(f8_case, engines):
+    c, e = f8_case, engines("f8", "ffm_f8")
+    e.encode_stats(reset=True)
+    load(e, c)
+    rows = c.rows()
+    want = decoded(rows["vec_w"], "f8")
+    assert e.encode_stats(reset=True) == counted(rows["vec_w"], want)
+    got = e.get_rows(c.probes32)
+    assert sorted(got) == ["lin_w", "vec_w"]
+    assert_bitwise(got["vec_w"], want, "f8 get_rows vec_w")
+    assert_bitwise(got["lin_w"], rows["lin_w"], "f8 get_rows lin_w")
+    order = np.random.default_rng(3).permutation(c.probes.size)  # a shuffled id list, ids twice
+    order = np.concatenate([order, order[:7]])
+    assert_bitwise(e.get_rows(c.probes32[order])["vec_w"], want[order], "f8 get_rows shuffled")
+    assert_aliases_zero(e, c, "f8 after set_rows")
+    # the format's edge rows (scale 2^-117 and 2^120, ties, the NaN byte, zero rows) on the records past 2^31 and 2^32
+    high = c.probes32[c.tiers("f8") != 0]
+    assert high.size >= 32 and (c.tiers("f8")[c.tiers("f8") != 0] == 2).sum() >= 8
+    special = edge_rows(BIG_L, n_rows=high.size)[::-1].copy()  # (the edge rows last: on the highest ids)
+    e.set_rows(high, dict(vec_w=special))
+    want = decoded(special, "f8")
+    counts = counted(special, want)
+    assert e.encode_stats(reset=True) == counts and counts["n_to_inf"] >= 2 and counts["n_to_zero"] >= 6
+    assert_bitwise(e.get_rows(high)["vec_w"], want, "f8 edge rows on the high ids")
+    assert_aliases_zero(e, c, "f8 after the edge rows")
+    load(e, c)
+
+
+def test_f8_pack_from(case, f8_case, engines):
+    """The training engine is the module's: it holds case 1's probe rows, which are zeroed for the pass and loaded again
+    after it, as this case's are loaded for it and zeroed after it -- so that the source holds this case's probe rows
+    and zeros, and whatever runs later finds the engine as every case leaves it."""
+    c, t, s = f8_case, engines("train"), engines("f8", "ffm_f8")
+    zero_rows(t, case.probes32)
+    st = planted_state(c)
+    try:
+        load(t, c, st)
+        stats = s.pack_from(t)
+        w = c.rows(st, ("vec_w",))["vec_w"]
+        want = decoded(w, "f8")
+        counts = dict(counted(w, want), n_latent=c.n_feats * BIG_L)  # (every other row is zeros: exact, nothing counted)
+        assert counts["n_inexact"] > w.size // 2 and counts["n_to_zero"] >= 6
+        assert stats == counts, (stats, counts)
+        got = s.get_rows(c.probes32)
+        assert_bitwise(got["vec_w"], want, "pack_from f8 vec_w")
+        assert_bitwise(got["lin_w"], c.rows(st, ("lin_w",))["lin_w"], "pack_from f8 lin_w")
+        assert bits(bias_of(s))[0] == bits(st["bias3"][:1])[0]
+        assert_aliases_zero(s, c, "pack_from f8")
+        src = t.get_rows(c.probes32)
+        for key, a in c.rows(st).items():
+            assert_bitwise(src[key], a, "pack_from left the source's %s alone" % key)
+    finally:
+        zero_rows(t, c.probes32)
+        load(t, case)
+    got = t.get_rows(case.probes32)
+    for key, a in case.rows().items():
+        assert_bitwise(got[key], a, "the training engine holds case 1's rows again: " + key)
+    only_f8 = np.setdiff1d(c.probes32, case.probes32)
+    assert only_f8.size > 100 and not any(bits(a).any() for a in t.get_rows(only_f8).values())
+    engines.release("ffm_f8")
+
+
 # ---- 12. where the index of a vector of four factors passes 2^31 and 2^32 ------------------------------------------
 # WaveTable<FMT>::slot, serve_pack_kernel, serve_sync_kernel and refresh_weights_kernel count in vectors of four
 # factors (16 bytes; 8 of an fp16 table): at BIG_NF their index reaches 1.07e9 in a serving table and 3.2e9 in a
@@ -653,6 +755,7 @@ def vec_case(name, kinds):
 def test_vector_index_serving(engines):
     c = vec_case("vec_serve", ["f16"])
     engines.release("ffm")
+    engines.release("ffm_f8")
     e = engines("f16", "vec_serve")
     run_prediction(c, e, "vec_serve")
     run_score_candidates(c, e)
@@ -665,6 +768,7 @@ def test_vector_index_serving(engines):
 def test_vector_index_training(engines):
     c = vec_case("vec_train", ["train"])
     engines.release("ffm")
+    engines.release("ffm_f8")
     engines.release("vec_serve")
     t = engines("train", "vec_train")
     run_prediction(c, t, "vec_train")

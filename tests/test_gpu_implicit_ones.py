@@ -412,7 +412,7 @@ def test_stale_slots_in_one_pipeline(zero_copy):
 # ---- 4. serving engines and groups ----------------------------------------------------------------------
 
 
-@pytest.mark.parametrize("fmt", ["f32", "f16"])
+@pytest.mark.parametrize("fmt", ["f32", "f16", "f8"])
 def test_serving_engines(fmt):
     t = fa.Engine("FFM", NF, F, K, max_batch_rows=ROWS_MAX, max_batch_nnz=ROWS_MAX * F, max_row_nnz=F, seed=9, **STRESS_HP)
     t.fill_state(seed=6)

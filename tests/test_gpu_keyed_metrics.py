@@ -371,11 +371,12 @@ def test_every_training_path_feeds_the_train_capture(path):
 
 
 def test_a_serving_engine_and_hashed_ids():
-    s = make_engine(serve="f16")
     blocks = [make_block(np.random.default_rng(70 + i).integers(0, 90, n), 80 + i) for i, n in enumerate((2000, 500))]
-    m, _, _ = run_eval(s, blocks, "serving engine, f16")
-    assert m["n_keys_mixed"] > 0
-    s.close()
+    for fmt in ("f16", "f8"):  # (f8: the capture behind a row kernel of its own, ffm_row8_wave_kernel)
+        s = make_engine(serve=fmt)
+        m, _, _ = run_eval(s, blocks, "serving engine, " + fmt)
+        assert m["n_keys_mixed"] > 0
+        s.close()
     # hashed ids: the key is the id the kernels see, the hashed one; raw ids far outside the model
     lin = LEVELS[np.arange(NF) % 5].astype(np.float32)
     h = make_engine(lin=lin, hash_ids=True)

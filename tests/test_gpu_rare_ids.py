@@ -524,13 +524,14 @@ def test_blocks_without_a_field_array():
     b.close()
 
 
-def test_serving_engine_and_candidates():
+@pytest.mark.parametrize("serve", ["f32", "f16", "f8"])
+def test_serving_engine_and_candidates(serve):
     _, words = _map("FFM", False)
     t = _engine("FFM")
     t.fill_state(seed=6)
     w = t.get_weights()
     t.close()
-    mk = lambda: fa.Engine("FFM", NF, F, K, skip_init=True, serve="f32", max_batch_rows=4 * ROWS, max_batch_nnz=4 * ROWS * ROW_NNZ,  # noqa: E731
+    mk = lambda: fa.Engine("FFM", NF, F, K, skip_init=True, serve=serve, max_batch_rows=4 * ROWS, max_batch_nnz=4 * ROWS * ROW_NNZ,  # noqa: E731
                            field_start=FS, hash_ids=True, **STRESS_HP)
     a, b = mk(), mk()
     for e in (a, b):
@@ -551,13 +552,19 @@ def test_serving_engine_and_candidates():
     fctx = _variant(ctx, feat=rare_ref.np_fold(ctx.field, ctx.feat, F, BITS, words))
     fcand = _variant(cand, feat=rare_ref.np_fold(cand.field, cand.feat, F, BITS, words))
     assert (fctx.feat != ctx.feat).any() and (fcand.feat != cand.feat).any()
+    if serve == "f8":  # an f8 engine has no candidate kernels (refused as such): the candidates' rows spelled out instead
+        with pytest.raises(fa.EngineError, match="f8") as err:
+            a.score_candidates(ctx, rq, cand)
+        assert err.value.code == fa.engine.E_UNSUPPORTED
+    score = lambda e, x, y, prob=False: (e.predict_batch(fa.spell_out_candidates(x, rq, y), output_prob=prob)[0] if serve == "f8"  # noqa: E731
+                                         else e.score_candidates(x, rq, y, output_prob=prob))
     for prob in (False, True):
-        got = a.score_candidates(ctx, rq, cand, output_prob=prob)
-        assert_bitwise(got, b.score_candidates(fctx, rq, fcand, output_prob=prob), "score_candidates")
+        got = score(a, ctx, cand, prob)
+        assert_bitwise(got, score(b, fctx, fcand, prob), "score_candidates")
         assert_bitwise(got, a.predict_batch(fa.spell_out_candidates(ctx, rq, cand), output_prob=prob)[0], "candidates vs predict_batch")
-    assert not np.array_equal(a.score_candidates(ctx, rq, cand), b.score_candidates(ctx, rq, cand)), "the fold changes the scores"
+    assert not np.array_equal(score(a, ctx, cand), score(b, ctx, cand)), "the fold changes the scores"
     a.set_rare_fold(None)
-    assert_bitwise(a.score_candidates(ctx, rq, cand), b.score_candidates(ctx, rq, cand), "fold off")
+    assert_bitwise(score(a, ctx, cand), score(b, ctx, cand), "fold off")
     a.close()
     b.close()
 

@@ -249,13 +249,13 @@ def _check_prediction(e, has_field, slow=False, counts=None, slot=SLOT):
         assert np.float64(loss).tobytes() == np.float64(sum(ls for _, ls in want)).tobytes()
 
 
-@pytest.mark.parametrize("kind", ["a", "b", "c_f16", "fm", "lr"])
+@pytest.mark.parametrize("kind", ["a", "b", "c_f16", "c_f8", "fm", "lr"])
 def test_predict_resident_is_predict_batch_of_the_host_block(kind):
     has_field = kind not in ("fm", "lr")
-    if kind == "c_f16":
+    if kind in ("c_f16", "c_f8"):
         t = _engine("a")
         t.fill_state(seed=6)
-        e = fa.Engine("FFM", NF, F, K, serve="f16", skip_init=True, max_batch_rows=ROWS, max_batch_nnz=NNZ, max_row_nnz=128, **STRESS_HP)
+        e = fa.Engine("FFM", NF, F, K, serve=kind[2:], skip_init=True, max_batch_rows=ROWS, max_batch_nnz=NNZ, max_row_nnz=128, **STRESS_HP)
         e.pack_from(t)
         t.close()
     else:

@@ -251,7 +251,7 @@ def test_predict_ablated_drops_a_field_after_normalising():
     b.close()
 
 
-@pytest.mark.parametrize("fmt", ["f32", "f16"])
+@pytest.mark.parametrize("fmt", ["f32", "f16", "f8"])
 def test_serving_engines(fmt):
     kw = dict(max_batch_rows=ROWS_MAX, max_batch_nnz=ROWS_MAX * 8, max_row_nnz=128, **STRESS_HP)
     t = fa.Engine("FFM", NF, F, K, seed=9, **kw)
@@ -268,6 +268,14 @@ def test_serving_engines(fmt):
     # scoring candidates would need a scale per candidate: refused before anything is queued
     ctx = Csr(np.array([0, 1], np.int32), np.array([0], np.int32), np.array([3], np.int32), np.ones(1, f32), np.zeros(1, np.int32))
     cand = Csr(np.array([0, 1], np.int32), np.array([1], np.int32), np.array([PER + 3], np.int32), np.ones(1, f32), np.zeros(1, np.int32))
+    if fmt == "f8":  # (an f8 engine has no candidate kernels: refused as such, with or without the flag)
+        for e in (a, b):
+            with pytest.raises(fa.EngineError, match="f8") as ei:
+                e.score_candidates(ctx, np.array([0, 1], np.int32), cand)
+            assert ei.value.code == fa.engine.E_UNSUPPORTED
+        for e in (a, b, t):
+            e.close()
+        return
     with pytest.raises(fa.EngineError, match="scale per candidate") as ei:
         a.score_candidates(ctx, np.array([0, 1], np.int32), cand)
     assert ei.value.code == fa.engine.E_INVALID

@@ -27,10 +27,15 @@ MAX_ROWS = 128
 REFUSAL = "a serving engine holds no accumulators"
 
 
-def decoded(w, fmt):
-    """What a serving engine of format `fmt` holds for the fp32 weights w, as fp32."""
+def decoded(w, fmt, row_len=None):
+    """What a serving engine of format `fmt` holds for the fp32 weights w, as fp32 ("f8": w is [n, row_len] whole
+    rows, each behind the scale of its own values -- ftrl_ffm_amd.serve_f8_encode is that format's definition)."""
     if fmt == "f32":
         return np.ascontiguousarray(w, np.float32)
+    if fmt == "f8":
+        w = np.ascontiguousarray(w, np.float32)
+        assert w.ndim == 2 and (row_len is None or row_len == w.shape[1]), "f8 encodes whole rows"
+        return fa.serve_f8_decode(*fa.serve_f8_encode(w), row_len=w.shape[1])
     with np.errstate(over="ignore"):
         return np.asarray(w, np.float32).astype(np.float16).astype(np.float32)
 

@@ -531,7 +531,7 @@ def test_blocks_without_a_field_array(with_map):
     b.close()
 
 
-@pytest.mark.parametrize("serve", ["f32", "f16"])
+@pytest.mark.parametrize("serve", ["f32", "f16", "f8"])
 def test_serving_engines_and_candidates(serve):
     table, words = _table(False), _keep_map(False)
     t = _engine()
@@ -563,14 +563,20 @@ def test_serving_engines_and_candidates(serve):
         assert hit.any()
         return _variant(blk, feat=np.where(hit, ft, fa.fold_rare(blk.field, blk.feat, F, BITS, words)).astype(np.int32), val=v)
 
+    if serve == "f8":  # an f8 engine has no candidate kernels (refused as such): the candidates' rows spelled out instead
+        with pytest.raises(fa.EngineError, match="f8") as err:
+            a.score_candidates(ctx, rq, cand)
+        assert err.value.code == fa.engine.E_UNSUPPORTED
+    score = lambda e, x, y, prob=False: (e.predict_batch(fa.spell_out_candidates(x, rq, y), output_prob=prob)[0] if serve == "f8"  # noqa: E731
+                                         else e.score_candidates(x, rq, y, output_prob=prob))
     for prob in (False, True):
-        got = a.score_candidates(ctx, rq, cand, output_prob=prob)
-        assert_bitwise(got, b.score_candidates(bucketed(ctx), rq, bucketed(cand), output_prob=prob), "score_candidates")
+        got = score(a, ctx, cand, prob)
+        assert_bitwise(got, score(b, bucketed(ctx), bucketed(cand), prob), "score_candidates")
         assert_bitwise(got, a.predict_batch(fa.spell_out_candidates(ctx, rq, cand), output_prob=prob)[0], "candidates vs predict_batch")
-    assert not np.array_equal(a.score_candidates(ctx, rq, cand), b.score_candidates(ctx, rq, cand)), "the table changes the scores"
+    assert not np.array_equal(score(a, ctx, cand), score(b, ctx, cand)), "the table changes the scores"
     a.set_buckets(None)
     a.set_rare_fold(None)
-    assert_bitwise(a.score_candidates(ctx, rq, cand), b.score_candidates(ctx, rq, cand), "table off")
+    assert_bitwise(score(a, ctx, cand), score(b, ctx, cand), "table off")
     a.close()
     b.close()
 

@@ -79,6 +79,105 @@ def test_encode_and_decode_match_the_search(row_len):
     assert np.isinf(d).sum() == 2  # 3.4e38 and the largest float: only within a factor of two of FLT_MAX
 
 
+# ---- scales that differ, and the extremes (the GPU side: tests/test_gpu_serve_f8.py::test_rows_of_mixed_scales) ------
+# F = 6 fields of SCALE_PER ids each; feature i belongs to field i // SCALE_PER.  The first ids of the LAST field are the
+# extreme features, one edge_rows row each; every other feature is a varied one: N(0, 1) * 2^m(i), m(i) uniform in
+# SCALE_M per feature.  With m <= 20 a pair term stays below 2^45 * k and a logit below 2^60: the varied rows are finite
+# by construction (checked below), so a kernel cannot pass on NaN == NaN.
+SCALE_F, SCALE_PER, SCALE_M, SCALE_KS = 6, 64, (-40, 20), (4, 16, 64)
+SCALE_NF = SCALE_F * SCALE_PER
+# name -> (the edge_rows row it carries, the scale numpy gives it, the class of the named row's oracle logit)
+EXTREMES = {
+    "scale 2^-117, one value left": (10, 2.0 ** -117, "finite"),
+    "scale 2^-117, all rounded to zero": (9, 2.0 ** -117, "finite"),
+    "scale 2^120": (11, 2.0 ** 120, "inf"),       # 3.4e38 decodes to 256 * 2^120: the one infinity of the row
+    "zeros, +-inf, +-NaN": (14, 2.0 ** -9, "nan"),
+    "+inf alone": (15, 1.0, "nan"),
+    "NaN, -inf, 1e-3": (16, 2.0 ** -18, "nan"),
+    "-0.0 alone": (17, 1.0, "finite"),
+    "one nonzero value": (18, 2.0 ** -14, "finite"),
+    "all zero": (19, 1.0, "finite"),
+    "no finite element": (20, 1.0, "nan"),
+}
+
+
+def scale_case(k, seed=71, n_varied_rows=56):
+    """dict(w [SCALE_NF, 6 k], lin_w, bias, block, extreme_ids {name: id}, named {name: row index}, varied_rows): the
+    table and block of the mixed-scale case at k factors.  The block's first n_varied_rows rows (1 .. 40 entries, any
+    field, ids of varied features only) are followed by one named row per extreme feature: a varied entry in each of
+    the fields 0 .. 4 and the extreme feature in field 5, so that its slots 0 .. 4 -- elements 0 .. 5 k - 1, every value
+    an edge_rows row holds -- are read and nothing else of the row is extreme."""
+    from oracle.pyoracle import Csr
+    rng = np.random.default_rng(seed + k)
+    L = SCALE_F * k
+    m = rng.integers(SCALE_M[0], SCALE_M[1] + 1, SCALE_NF)
+    w = (rng.standard_normal((SCALE_NF, L)) * 2.0 ** m[:, None]).astype(F32)
+    edge = edge_rows(L, n_rows=32)
+    first = (SCALE_F - 1) * SCALE_PER
+    extreme_ids = {name: first + j for j, name in enumerate(EXTREMES)}
+    for name, i in extreme_ids.items():
+        w[i] = edge[EXTREMES[name][0]]
+    varied = np.setdiff1d(np.arange(SCALE_NF), list(extreme_ids.values()))
+    rows = []
+    for r in range(n_varied_rows):
+        ids = rng.choice(varied, int(rng.integers(1, 41)), replace=False)
+        rows.append([(int(i) // SCALE_PER, int(i), 1.0 if rng.random() < 0.5 else float(F32(rng.random() + 0.25))) for i in ids])
+    named = {}
+    for name, i in extreme_ids.items():
+        named[name] = len(rows)
+        row = [(f, int(rng.choice(varied[varied // SCALE_PER == f])), float(F32(rng.random() + 0.25))) for f in range(SCALE_F - 1)]
+        rows.append(row + [(SCALE_F - 1, i, 1.0)])
+    block = Csr.from_rows(rows, [r % 2 for r in range(len(rows))])
+    return dict(w=w, m=m, lin_w=rng.normal(0, 0.02, SCALE_NF).astype(F32), bias=F32(0.013), block=block,
+                extreme_ids=extreme_ids, named=named, varied_rows=np.arange(n_varied_rows))
+
+
+def scale_oracle(c, k):
+    """The oracle holding the decoded table of scale_case(k), and that table."""
+    from oracle.pyoracle import CpuModel
+    from util import STRESS_HP
+    d = fa.serve_f8_decode(*fa.serve_f8_encode(c["w"]), row_len=SCALE_F * k)
+    o = CpuModel("oracle", "FFM", SCALE_NF, SCALE_F, k, **STRESS_HP)
+    st = o.zero_state()
+    st["bias3"][0], st["lin_w"][...], st["vec_w"][...] = c["bias"], c["lin_w"], d
+    o.set_state(st)
+    return o, d
+
+
+def logit_class(x):
+    return "nan" if np.isnan(x) else "inf" if np.isinf(x) else "finite"
+
+
+@pytest.mark.parametrize("k", SCALE_KS)
+def test_mixed_scale_case_cannot_pass_on_nan_alone(k):
+    """What tests/test_gpu_serve_f8.py::test_rows_of_mixed_scales takes for granted, on the oracle alone: no decoded
+    value is subnormal, at most 1 varied row in 8 has a non-finite logit (here: none), every named row has its class,
+    the extreme features carry the scales they are named for, and a varied row mixes scales dozens of binades apart."""
+    c = scale_case(k)
+    o, d = scale_oracle(c, k)
+    assert not ((d != 0) & (np.abs(d) < F32(2.0 ** -126))).any(), "a decoded value is subnormal"
+    scales = fa.serve_f8_encode(c["w"])[1]
+    for name, i in c["extreme_ids"].items():
+        assert scales[i] == F32(EXTREMES[name][1]), (name, scales[i])
+    assert np.isinf(d[c["extreme_ids"]["scale 2^120"]]).sum() == 1 and (d[c["extreme_ids"]["scale 2^-117, one value left"]] != 0).sum() == 1
+    blk = c["block"]
+    assert not np.isin(take_feats(blk, c["varied_rows"]), list(c["extreme_ids"].values())).any()
+    lg = o.predict_batch(blk)[0]
+    assert (~np.isfinite(lg[c["varied_rows"]])).mean() <= 1 / 8
+    for name, r in c["named"].items():
+        feats = blk.feat[blk.row_ptr[r]:blk.row_ptr[r + 1]]
+        assert np.isin(feats, list(c["extreme_ids"].values())).sum() == 1 and feats[-1] == c["extreme_ids"][name]
+        assert logit_class(lg[r]) == EXTREMES[name][2], (name, lg[r])
+    # the scale exponents within a row: dozens of binades apart in most rows of more than a few entries
+    exps = np.log2(scales.astype(np.float64))
+    spread = [np.ptp(exps[blk.feat[blk.row_ptr[r]:blk.row_ptr[r + 1]]]) for r in c["varied_rows"] if blk.row_ptr[r + 1] - blk.row_ptr[r] >= 6]
+    assert len(spread) >= 30 and np.median(spread) >= 36 and exps.min() == -117 and exps.max() == 120
+
+
+def take_feats(blk, rows):
+    return np.concatenate([blk.feat[blk.row_ptr[r]:blk.row_ptr[r + 1]] for r in rows])
+
+
 @pytest.mark.parametrize("flags", [["--publish_path", "P", "--publish_weights", "f8", "--n_epochs", "1"],
                                    ["--apply_deltas", "P", "--serve_weights", "f8", "--n_epochs", "0"]])
 def test_the_cli_refuses_f8_deltas_before_it_opens_a_device(tmp_path, flags):

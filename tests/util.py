@@ -5,6 +5,7 @@ import os
 
 import numpy as np
 
+import ftrl_ffm_amd as fa
 from oracle.pyoracle import CpuModel, Csr
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -702,8 +703,11 @@ def assert_rank_rows(e, rank, ids, field_of, want, plan, k, what, chunk=16384):
 # ---- tables past 2^31 and 2^32 elements (tests/test_gpu_big_offsets.py, tests/test_big_offsets_host.py) ----------
 # FFM 39 x 16: a feature's record is 624 elements in a serving table (fp16: 2 bytes each, fp32: 4) and 3 * 624 in
 # a training engine ([n][z][w], 4 bytes each).  FM k = 64 training engine: 3 * 64.
+# An f8 serving table is addressed in bytes: a feature's row is 16 + round_up(624, 16) = 640 one-byte elements.
 BIG_F, BIG_K, BIG_L = 39, 16, 624
-BIG_LAYOUTS = {"f16": (BIG_L, 2), "f32": (BIG_L, 4), "train": (3 * BIG_L, 4)}  # kind -> (stride in elements, element bytes)
+BIG_LAYOUTS = {"f16": (BIG_L, 2), "f32": (BIG_L, 4), "train": (3 * BIG_L, 4),  # kind -> (stride in elements, element bytes)
+               "f8": (fa.serve_f8_stride(BIG_L), 1)}
+BIG_FFM_KINDS = ("f16", "f32", "train")  # the layouts of the "ffm" case; "ffm_f8" has the f8 layout alone, and probes of its own
 BIG_FM_K, BIG_FM_STRIDE = 64, 3 * 64
 BIG_HP = STRESS_HP  # weights that move (W(n, z) ~ 1e-2); with n >= BIG_N_ADD the oracle stays finite (checked on the CPU)
 BIG_N_ADD = 0.05
@@ -897,13 +901,16 @@ _BIG_CASES = {}
 
 
 def big_case(name):
-    """"ffm": FFM 39 x 16 at BIG_NF under the three layouts; "fm": FM k = 64 at BIG_NF_FM (training engine); "vec_serve" /
+    """"ffm": FFM 39 x 16 at BIG_NF under the three layouts of BIG_FFM_KINDS; "ffm_f8": the same model under the f8 table's
+    byte layout (byte 2^31 falls in feature 3 355 443, byte 2^32 in feature 6 710 886: both inside BIG_NF features); "fm": FM k = 64 at BIG_NF_FM (training engine); "vec_serve" /
     "vec_train": FFM 39 x 16 at BIG_NF_VEC_SERVE / BIG_NF_VEC_TRAIN, where the index of a vector of four factors passes
     2^32 in a serving table / in a training engine's records (an fp16 table of the latter count stays below 2^31
     vectors: it is the destination of pack_from and sync_from there).  Built once per process; read-only."""
     if name not in _BIG_CASES:
         if name == "ffm":
-            _BIG_CASES[name] = BigCase("FFM", BIG_NF, BIG_K, BIG_LAYOUTS, seed=31)
+            _BIG_CASES[name] = BigCase("FFM", BIG_NF, BIG_K, {kind: BIG_LAYOUTS[kind] for kind in BIG_FFM_KINDS}, seed=31)
+        elif name == "ffm_f8":
+            _BIG_CASES[name] = BigCase("FFM", BIG_NF, BIG_K, {"f8": BIG_LAYOUTS["f8"]}, seed=47)
         elif name == "vec_serve":
             _BIG_CASES[name] = BigCase("FFM", BIG_NF_VEC_SERVE, BIG_K, {"f16": BIG_LAYOUTS["f16"]}, seed=41, unit=4)
         elif name == "vec_train":
