@@ -56,6 +56,7 @@
 #include "kernels_ablate_pairs.h"
 #include "kernels_curve.h"
 #include "kernels_mask.h"
+#include "kernels_pruned.h"
 #include "kernels_stage.h"
 #include "kernels_sketch.h"
 #include "kernels_idcount.h"
@@ -467,6 +468,12 @@ struct ffm_engine {
   bool pair_mask_on = false;
   unsigned long long *d_pair_mask = nullptr;  // [kMaskFields]
   uint64_t pair_mask[ftrl_dev::kMaskFields] = {};
+  // ffm_engine_create_pruned (include/ffm_engine.h "Pruned serving tables", engine_pruned.h): m.lat is the pruned table
+  // of pruned_slots slots, pd its mask words, id ranges and bases in HBM; the words' host copy is pair_mask above.
+  // pruned == false: any other engine, and nothing here is read
+  bool pruned = false;
+  ftrl_dev::PrunedDev pd{};
+  int64_t pruned_slots = 0;
   std::vector<void *> allocs;
   // split-phase bookkeeping
   Rows pending{};
@@ -676,6 +683,13 @@ static int mask_refuse(const char *what) {
                                                  "with keep == NULL clears it): it would run without the mask");
 }
 #define MASK_REFUSE(e, what) do { if ((e) && (e)->pair_mask_on) return mask_refuse(what); } while (0)
+// A pruned serving table (engine_pruned.h) predicts rows and moves weights in and out: whatever reads the table by the
+// full-length layout is refused.
+static int pruned_refuse(const std::string &what) {
+  return fail(FFM_E_UNSUPPORTED, what + " is not available on a pruned serving table (ffm_engine_create_pruned): the table "
+                                        "holds the kept pairs' slots alone; use an unpruned FFM_FLAG_SERVE_F32 or _F16 engine");
+}
+#define PRUNED_REFUSE(e, what) do { if ((e) && (e)->pruned) return pruned_refuse(what); } while (0)
 
 #define LAUNCH_ON(e, st, kid, kernel, grid, block, shmem, ...)                   \
   do {                                                                           \
@@ -899,6 +913,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_rows.h"
 #include "engine_ablate.h"
 #include "engine_mask.h"
+#include "engine_pruned.h"
 }  // extern "C"
 
 #include "engine_group.h"

@@ -90,6 +90,7 @@ static int ablate_supported(const AblateKind &k, ffm_engine *e) {
   const ModelDev &m = e->m;
   const std::string noun = k.noun;
   F8_REFUSE(e, noun);
+  PRUNED_REFUSE(e, noun);
   if (m.type != FFM_MODEL_FFM) return fail(FFM_E_UNSUPPORTED, noun + " is FFM only: LR and FM rows have no fields");
   if (m.n_shards > 1 || e->in_group)
     return fail(FFM_E_UNSUPPORTED, noun + " needs a whole model on one device (n_shards == 1, not a group's engine)");
@@ -248,6 +249,7 @@ static int ablate_predict_device(const AblateKind &k, ffm_engine *e, int32_t n_r
                                  const int32_t *field, const int32_t *feat, const float *val, const int32_t *label,
                                  int32_t output_prob, float *out, double *loss_sum_out) {
   F8_REFUSE(e, k.noun);
+  PRUNED_REFUSE(e, k.noun);
   int rc = ablate_ready(k, e);
   if (rc) return rc;
   MASK_REFUSE(e, k.noun);  // (its variants are the whole model's: include/ffm_engine.h "Pair masks")
@@ -260,6 +262,7 @@ static int ablate_predict(const AblateKind &k, ffm_engine *e, int32_t n_rows, co
                           const int32_t *feat, const float *val, const int32_t *label, int32_t output_prob, float *out,
                           double *loss_sum_out) {
   F8_REFUSE(e, k.noun);
+  PRUNED_REFUSE(e, k.noun);
   int rc = ablate_ready(k, e);
   if (rc) return rc;
   MASK_REFUSE(e, k.noun);  // (its variants are the whole model's: include/ffm_engine.h "Pair masks")

@@ -9,6 +9,9 @@ static int hash_ids_check(int32_t model_type, int32_t n_feats, int32_t n_fields,
 static int serve_create_check(const ffm_engine_config *cfg);  // (engine_serve.h)
 static void serve8_launch_init(ffm_engine *e, bool zero);      // (engine_serve.h)
 static int norm_ready(ffm_engine *e);  // (engine_norm.h)
+static int pruned_plan(ffm_engine *e);      // (engine_pruned.h)
+static int pruned_tables(ffm_engine *e);
+static void pruned_launch_init(ffm_engine *e);
 
 // What the environment sets.  An empty optional: the switch is not set, and the default -- an ffm_engine member's
 // initializer, or what a later step works out for the shape -- stands.
@@ -251,7 +254,8 @@ static int alloc_model(ffm_engine *e, const ShardPlan &plan) {
   // floats allocated for the latent part: records of (n, z, w), or a serving engine's table of w alone in
   // 4- or 2-byte elements (row_len is a multiple of 4 there) or in f8 rows (kernels_serve8.h: a multiple of 16
   // bytes each) -- and then no (n, z) of the bias or the linear part
-  const size_t n_w = static_cast<size_t>(e->n_records) * static_cast<size_t>(m.row_len);
+  const size_t n_w = e->pruned ? static_cast<size_t>(std::max<int64_t>(1, e->pruned_slots)) * static_cast<size_t>(m.n_factors)
+                               : static_cast<size_t>(e->n_records) * static_cast<size_t>(m.row_len);
   const size_t n_lat = m.lat_fmt == SERVE_F8    ? static_cast<size_t>(e->n_records) * static_cast<size_t>(serve8_stride(m.row_len)) / 4
                        : m.lat_fmt == SERVE_F16 ? n_w / 2 : m.lat_fmt == SERVE_F32 ? n_w : 3 * n_w;
   const size_t n_bias = serving(e) ? 1 : 4;
@@ -299,6 +303,7 @@ static int alloc_model(ffm_engine *e, const ShardPlan &plan) {
       m.rec_base = d_base;
     }
   }
+  if (e->pruned && (rc = pruned_tables(e))) return rc;
   if (e->hash_ids) {
     e->hm = ftrl_hash::Map{nullptr, cfg->n_feats, m.n_fields, m.type == FFM_MODEL_FFM ? 1 : 0};
     if (!e->field_start.empty()) {  // (kept for FFM only; widths checked above)
@@ -535,7 +540,9 @@ static int opt_in_lds(ffm_engine *e) {
 static int init_weights(ffm_engine *e) {
   const ffm_engine_config *cfg = &e->cfg;
   const bool skip = (cfg->flags & FFM_FLAG_SKIP_INIT) != 0;  // (the caller sets the state; the arrays are zeroed)
-  if (e->m.lat_fmt == SERVE_F8)  // (skipped too: a row of zero bytes still has a head)
+  if (e->pruned) {
+    if (!skip) pruned_launch_init(e);
+  } else if (e->m.lat_fmt == SERVE_F8)  // (skipped too: a row of zero bytes still has a head)
     serve8_launch_init(e, skip);
   else if (!skip && serving(e))
     hipLaunchKernelGGL(serve_init_kernel, dim3(2048), dim3(256), 0, e->stream, e->m, cfg->init_mean, cfg->init_stddev, cfg->seed);
@@ -547,7 +554,8 @@ static int init_weights(ffm_engine *e) {
   return FFM_OK;
 }
 
-int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
+// prune_keep: null, or the checked mask words of ffm_engine_create_pruned (engine_pruned.h) for cfg->n_fields fields.
+static int engine_create(const ffm_engine_config *cfg, const uint64_t *prune_keep, ffm_engine **out) {
   if (!cfg || !out) return fail(FFM_E_INVALID, "null config or output pointer");
   *out = nullptr;
   const Switches sw = read_switches();
@@ -568,7 +576,11 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   ShardPlan plan;
   Scratch shared{};
   int rc;
-  if ((rc = plan_model(e, sw, &plan)) || (rc = create_streams(e)) || (rc = alloc_model(e, plan)) || (rc = alloc_shared(e, &shared)))
+  if (prune_keep) {
+    e->pruned = true;
+    std::copy(prune_keep, prune_keep + cfg->n_fields, e->pair_mask);
+  }
+  if ((rc = plan_model(e, sw, &plan)) || (e->pruned && (rc = pruned_plan(e))) || (rc = create_streams(e)) || (rc = alloc_model(e, plan)) || (rc = alloc_shared(e, &shared)))
     return rc;
   for (int si = 0; si < ffm_engine::kSets; si++)
     if ((rc = alloc_set(e, si, shared))) return rc;
@@ -580,3 +592,5 @@ int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) {
   *out = guard.release();
   return FFM_OK;
 }
+
+int ffm_engine_create(const ffm_engine_config *cfg, ffm_engine **out) { return engine_create(cfg, nullptr, out); }

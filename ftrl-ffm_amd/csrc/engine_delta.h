@@ -11,6 +11,7 @@ int ffm_engine_sync_weights(ffm_engine *dst, ffm_engine *src, ffm_sync_stats *ou
   if (!dst || !src) return fail(FFM_E_INVALID, "null engine");
   if (!serving(dst)) return fail(FFM_E_INVALID, "sync_weights: dst must be a serving engine (FFM_FLAG_SERVE_F32 / _F16)");
   F8_REFUSE(dst, "sync_weights");
+  PRUNED_REFUSE(dst, "sync_weights");
   if (serving(src)) return fail(FFM_E_INVALID, "sync_weights: src must be a training engine");
   if (src->m.type != FFM_MODEL_FFM || src->m.n_shards > 1)
     return fail(FFM_E_INVALID, "sync_weights: src must be a whole (unsharded) FFM model");
@@ -86,6 +87,7 @@ static int rows_raw_transfer(ffm_engine *e, int32_t n, const int32_t *ids, float
     return fail(FFM_E_UNSUPPORTED, std::string(what) + " moves a serving engine's table in its own bits: a training engine "
                                        "has ffm_engine_get_rows / set_rows");
   F8_REFUSE(e, what);
+  PRUNED_REFUSE(e, what);
   if (n < 0 || (n > 0 && !ids)) return fail(FFM_E_INVALID, "bad feature id list");
   for (int32_t j = 0; j < n; j++)
     if (ids[j] < 0 || ids[j] >= e->m.n_feats) return fail(FFM_E_INVALID, "feature id out of range");

@@ -5,8 +5,22 @@
 // nothing and launches what it launched before.
 // Part of engine.hip's translation unit (included inside its extern "C" block).
 
+// What the words of a mask for n_fields (1 .. 64) fields must be, whoever takes them (ffm_engine_create_pruned too).
+static int pair_mask_words_check(const uint64_t *keep, int32_t n_fields) {
+  for (int f = 0; f < n_fields; f++) {
+    if (n_fields < 64 && (keep[f] >> n_fields) != 0)
+      return fail(FFM_E_INVALID, "keep[" + std::to_string(f) + "] has a bit at or above n_fields");
+    for (int g = 0; g < f; g++)
+      if (((keep[f] >> g) & 1u) != ((keep[g] >> f) & 1u))
+        return fail(FFM_E_INVALID, "the mask is not symmetric: bit " + std::to_string(g) + " of keep[" + std::to_string(f) +
+                                       "] differs from bit " + std::to_string(f) + " of keep[" + std::to_string(g) + "]");
+  }
+  return FFM_OK;
+}
+
 int ffm_engine_set_pair_mask(ffm_engine *e, const uint64_t *keep, int32_t n_fields) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
+  PRUNED_REFUSE(e, "set_pair_mask (the mask is the table's shape)");
   const ModelDev &m = e->m;
   if (!keep) {  // clears: blocks queued so far keep the mask they were queued under
     if (!e->pair_mask_on) return FFM_OK;
@@ -30,14 +44,7 @@ int ffm_engine_set_pair_mask(ffm_engine *e, const uint64_t *keep, int32_t n_fiel
   // ---- what a mask must be; a refused one leaves the previous mask in force
   if (n_fields != m.n_fields)
     return fail(FFM_E_INVALID, "the mask is for " + std::to_string(n_fields) + " fields, the engine has " + std::to_string(m.n_fields));
-  for (int f = 0; f < n_fields; f++) {
-    if (n_fields < 64 && (keep[f] >> n_fields) != 0)
-      return fail(FFM_E_INVALID, "keep[" + std::to_string(f) + "] has a bit at or above n_fields");
-    for (int g = 0; g < f; g++)
-      if (((keep[f] >> g) & 1u) != ((keep[g] >> f) & 1u))
-        return fail(FFM_E_INVALID, "the mask is not symmetric: bit " + std::to_string(g) + " of keep[" + std::to_string(f) +
-                                       "] differs from bit " + std::to_string(f) + " of keep[" + std::to_string(g) + "]");
-  }
+  if (int rc_w = pair_mask_words_check(keep, n_fields)) return rc_w;
   if (e->n_staged > 0 || e->has_pending) return fail(FFM_E_INVALID, "staged training blocks are still waiting");
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   if (int rc_e = eval_launch_pending(e)) return rc_e;  // (a deferred block is scored under the mask it was queued under)
@@ -55,8 +62,9 @@ int ffm_engine_set_pair_mask(ffm_engine *e, const uint64_t *keep, int32_t n_fiel
 
 int ffm_engine_get_pair_mask(ffm_engine *e, uint64_t *keep_out, int32_t *is_set) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
-  if (is_set) *is_set = e->pair_mask_on ? 1 : 0;
+  const bool on = e->pair_mask_on || e->pruned;  // (a pruned table's mask is its shape: always in force)
+  if (is_set) *is_set = on ? 1 : 0;
   if (keep_out && e->m.n_fields <= kMaskFields)
-    for (int f = 0; f < e->m.n_fields; f++) keep_out[f] = e->pair_mask_on ? e->pair_mask[f] : 0;
+    for (int f = 0; f < e->m.n_fields; f++) keep_out[f] = on ? e->pair_mask[f] : 0;
   return FFM_OK;
 }

@@ -128,6 +128,16 @@ inline RowMaskFn row_mask_fn(int fmt, int n_factors) {
     default: return nullptr;
   }
 }
+// a pruned serving table's rows (kernels_pruned.h): ffm_row_wave_kernel's arguments, then the table's mask and ranges
+using RowPrunedFn = void (*)(ModelDev, Rows, Scratch, int, int, float *, int, PrunedDev);
+inline RowPrunedFn row_pruned_fn(int fmt, int n_factors) {
+  switch (n_factors) {
+#define X(K, LPP, VPL, U) case K: return FFM_BY_FMT(ffm_row_pruned_kernel, LPP, VPL, U);
+    FFM_LANE_SHAPES(X)
+#undef X
+    default: return nullptr;
+  }
+}
 inline ServeContextFn serve_context_fn(int fmt, int n_factors) {
   switch (n_factors) {
 #define X(K, LPP, VPL, U) case K: return FFM_BY_FMT(serve_context_kernel, LPP, VPL, U);
@@ -200,6 +210,19 @@ using ServeSyncFn = void (*)(ModelDev, ModelDev, int64_t, unsigned long long *, 
 using ServeRowsRawFn = void (*)(ModelDev, void *, const int *, int64_t, int);
 inline ServeSyncFn serve_sync_fn(int fmt) {
   return fmt == SERVE_F16 ? serve_sync_kernel<SERVE_F16> : fmt == SERVE_F32 ? serve_sync_kernel<SERVE_F32> : nullptr;
+}
+// ffm_engine_pack_weights into a pruned table: <format, vectors per 16-byte item, lanes per feature>; row4: the
+// longest pruned row in vectors of four factors.  *lanes: the lanes per feature of the kernel returned (16 where one
+// pass of 16 lanes covers the longest row, 64 otherwise), which the launch sizes its grid by
+using ServePackPrunedFn = void (*)(ModelDev, ModelDev, PrunedDev, unsigned long long *);
+inline ServePackPrunedFn serve_pack_pruned_fn(int fmt, int n_factors, int row4, int *lanes) {
+  const int vpi = fmt == SERVE_F16 && n_factors >= 8 ? 2 : 1;
+  const bool narrow = row4 <= 16 * vpi;
+  *lanes = narrow ? 16 : 64;
+  if (fmt == SERVE_F32) return narrow ? serve_pack_pruned_kernel<SERVE_F32, 1, 16> : serve_pack_pruned_kernel<SERVE_F32, 1, 64>;
+  if (fmt != SERVE_F16) return nullptr;
+  if (vpi == 1) return narrow ? serve_pack_pruned_kernel<SERVE_F16, 1, 16> : serve_pack_pruned_kernel<SERVE_F16, 1, 64>;
+  return narrow ? serve_pack_pruned_kernel<SERVE_F16, 2, 16> : serve_pack_pruned_kernel<SERVE_F16, 2, 64>;
 }
 inline ServeRowsRawFn serve_rows_raw_fn(int fmt) {  // elements of 2 or 4 bytes, moved as they are
   return fmt == SERVE_F16 ? serve_rows_raw_kernel<unsigned short> : fmt == SERVE_F32 ? serve_rows_raw_kernel<unsigned> : nullptr;

@@ -31,6 +31,7 @@ static int cand_common_check(ffm_engine *e, int32_t n_req, int32_t n_cand) {
     return fail(FFM_E_UNSUPPORTED, "score_candidates needs a serving engine (FFM_FLAG_SERVE_F32 / _F16): "
                                    "ffm_engine_pack_weights copies a training engine's weights into one");
   F8_REFUSE(e, "score_candidates");
+  PRUNED_REFUSE(e, "score_candidates");
   MASK_REFUSE(e, "score_candidates");
   if (e->norm_rows_on)
     return fail(FFM_E_INVALID, "score_candidates is not available on an engine with FFM_FLAG_NORM_ROWS: the shared context "
@@ -199,6 +200,9 @@ int ffm_engine_encode_stats(ffm_engine *e, int32_t reset, ffm_pack_stats *out) {
   return FFM_OK;
 }
 
+static void pruned_launch_copy(ffm_engine *e, const int *ids, int64_t feat0, int64_t nf, bool to_host);  // (engine_pruned.h)
+static void pruned_launch_pack(ffm_engine *dst, ffm_engine *src, int cus);
+
 static int serve_vec_transfer(ffm_engine *e, float *host, bool to_host) {
   const int64_t RL = e->logical_len;
   const int64_t chunk = e->stage_floats / RL;
@@ -206,7 +210,9 @@ static int serve_vec_transfer(ffm_engine *e, float *host, bool to_host) {
     const int64_t nf = std::min<int64_t>(chunk, e->m.n_feats - f0);
     const size_t bytes = static_cast<size_t>(nf * RL) * sizeof(float);
     if (!to_host) HIP_TRY(hipMemcpyAsync(e->d_stage, host + f0 * RL, bytes, hipMemcpyHostToDevice, e->stream));
-    if (e->m.lat_fmt == SERVE_F8) {
+    if (e->pruned) {
+      pruned_launch_copy(e, nullptr, f0, nf, to_host);
+    } else if (e->m.lat_fmt == SERVE_F8) {
       if (int rc8 = serve8_launch_copy(e, nullptr, f0, nf, to_host)) return rc8;
     } else
       hipLaunchKernelGGL(serve_dense_copy_kernel, dim3(1024), dim3(256), 0, e->stream, e->m, e->d_stage, f0, nf, to_host ? 1 : 0);
@@ -220,7 +226,9 @@ static int serve_vec_transfer(ffm_engine *e, float *host, bool to_host) {
 static int serve_rows_vec_transfer(ffm_engine *e, int nf, float *host, bool to_host) {
   const size_t bytes = static_cast<size_t>(nf) * e->logical_len * sizeof(float);
   if (!to_host) HIP_TRY(hipMemcpyAsync(e->d_stage, host, bytes, hipMemcpyHostToDevice, e->stream));
-  if (e->m.lat_fmt == SERVE_F8) {
+  if (e->pruned) {
+    pruned_launch_copy(e, e->d_ids, 0, nf, to_host);
+  } else if (e->m.lat_fmt == SERVE_F8) {
     if (int rc8 = serve8_launch_copy(e, e->d_ids, 0, nf, to_host)) return rc8;
   } else
     hipLaunchKernelGGL(serve_rows_copy_kernel, dim3(1024), dim3(256), 0, e->stream, e->m, e->d_stage, e->d_ids,
@@ -258,7 +266,9 @@ int ffm_engine_pack_weights(ffm_engine *dst, ffm_engine *src, ffm_pack_stats *ou
   const int64_t items = std::max<int64_t>(static_cast<int64_t>(src->m.n_feats) * (src->m.row_len / 4), src->m.n_feats);
   const int grid = static_cast<int>(std::min<int64_t>(std::max(1, cus) * 8, std::max<int64_t>(1, (items + kPackThreads - 1) / kPackThreads)));
   HIP_TRY(hipMemsetAsync(dst->d_pack, 0, PK_COUNT * kPackLine * sizeof(unsigned long long), dst->stream));
-  if (dst->m.lat_fmt == SERVE_F8) {  // a group of lanes per feature row (kernels_serve8.h)
+  if (dst->pruned) {  // the kept slots alone, a group of lanes per feature (kernels_pruned.h)
+    pruned_launch_pack(dst, src, cus);
+  } else if (dst->m.lat_fmt == SERVE_F8) {  // a group of lanes per feature row (kernels_serve8.h)
     const int G = serve8_group(dst->m.row_len);
     const int grid8 = std::min(std::max(1, cus) * 8, serve8_grid(dst->m.n_feats, G));
     hipLaunchKernelGGL(G == 16 ? serve_pack8_kernel<16> : serve_pack8_kernel<64>, dim3(grid8), dim3(kServe8Threads), 0, dst->stream,
@@ -284,6 +294,7 @@ int ffm_engine_pack_weights(ffm_engine *dst, ffm_engine *src, ffm_pack_stats *ou
 int64_t ffm_engine_model_bytes(const ffm_engine *e) {
   if (!e) return 0;
   const int64_t nf = e->m.n_feats, n_w = e->n_records * static_cast<int64_t>(e->m.row_len);
+  if (e->pruned) return 4 + 4 * nf + e->pruned_slots * e->m.n_factors * (e->m.lat_fmt == SERVE_F16 ? 2 : 4);
   if (e->m.lat_fmt == SERVE_F8) return 4 + 4 * nf + e->n_records * serve8_stride(e->m.row_len);
   if (serving(e)) return 4 + 4 * nf + (e->m.lat_fmt == SERVE_F16 ? 2 : 4) * n_w;
   return 12 + 12 * nf + 12 * n_w;

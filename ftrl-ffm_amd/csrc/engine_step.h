@@ -53,6 +53,14 @@ static void launch_row_mask(ffm_engine *e, const Rows &rows, int row_cap, float 
          64 * kPredRows, mask_lds_bytes(lds_cap), m, rows, e->sc[e->cur], row_cap, lds_cap, out, output_prob, e->d_pair_mask);
 }
 
+// A pruned serving table (engine_pruned.h) predicts every row through ffm_row_pruned_kernel (kernels_pruned.h).
+static void launch_row_pruned(ffm_engine *e, const Rows &rows, int row_cap, float *out, int output_prob) {
+  const ModelDev &m = e->m;
+  const int lds_cap = std::min(row_cap, kPredLdsCap);
+  LAUNCH(e, K_SERVE_ROW, row_pruned_fn(m.lat_fmt, m.n_factors), cdiv(rows.n_rows, kPredRows), 64 * kPredRows,
+         pruned_lds_bytes(lds_cap), m, rows, e->sc[e->cur], row_cap, lds_cap, out, output_prob, e->pd);
+}
+
 // row_cap: the longest row of the block where the caller knows it (rows that came in host memory), 0 = unknown
 // (device callers: max_row_nnz).  The row kernels size their LDS by it, which decides how many rows a CU holds.
 // weight: the block's sample weights (device) or null; only the launches that produce tmp_grad
@@ -61,6 +69,10 @@ static void launch_row_kernel(ffm_engine *e, const Rows &rows, int row_cap, bool
                               const float *weight = nullptr) {
   if (row_cap <= 0) row_cap = e->max_row_nnz;
   if (rows.n_rows == 0) return;
+  if (e->pruned) {  // (a serving engine: predict only) -- the pruned table's kernel and nothing else
+    launch_row_pruned(e, rows, row_cap, out, output_prob);
+    return;
+  }
   if (!train && e->pair_mask_on) {  // (training is refused while a mask is set) -- the masked kernel and nothing else
     launch_row_mask(e, rows, row_cap, out, output_prob);
     return;

@@ -107,6 +107,8 @@ __device__ __forceinline__ WaveLds wave_lds(char *smem, int wv, int lds_cap, int
 // store(position, {feature, field, value bits, 0}, lin_w * value) with positions from nv on; the linear logit
 // result + sum lin_w * x in row order (compute_linear_logit, ftrl_model.cpp:44-50) as a strictly sequential
 // prefix.  What store wrote to LDS is the wave's to read when this returns.
+// (kernels_pruned.h's pruned_stage_entries is this function with a field-range test beside remove_out_range: a change
+// to what survives, or to the order of the linear prefix, is made in both.)
 template <typename Store>
 __device__ __forceinline__ void wave_stage_entries(const ModelDev &m, const int *feat, const int *field, const float *val, int b,
                                                    int nnz, int lane, float &result, int &nv, Store store) {

@@ -294,6 +294,9 @@ ABI = [
     ("ffm_engine_predict_pair_curve_device", ctypes.c_int,
      [_vp, ctypes.c_int32, ctypes.c_int32] + _DCSR + [ctypes.c_int32, _vp, _vp]),
     ("ffm_engine_pair_curve_read", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.POINTER(Metrics)]),
+    # store and gather only the kept pairs' slots (include/ffm_engine.h "Pruned serving tables")
+    ("ffm_engine_create_pruned", ctypes.c_int, [ctypes.POINTER(Config), _vp, ctypes.c_int32, ctypes.POINTER(_vp)]),
+    ("ffm_engine_pruned_layout_host", ctypes.c_int, [_vp, ctypes.c_int32, _i32p, _i64p]),
     # sync a serving engine, publish only what moved (include/ffm_engine.h "Serving deltas")
     ("ffm_engine_sync_weights", ctypes.c_int, [_vp, _vp, ctypes.POINTER(SyncStats)]),
     ("ffm_engine_sync_moved", ctypes.c_int, [_vp, _i32p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
@@ -817,6 +820,41 @@ def pair_mask_pairs(words):
     return pairs
 
 
+def _mask_words(n_fields, keep):
+    """keep as set_pair_mask and Engine(prune=) take it: the words themselves, or an iterable of kept pairs."""
+    if isinstance(keep, np.ndarray) and keep.ndim == 1 and keep.dtype.kind in "ui":
+        return np.ascontiguousarray(keep, np.uint64)
+    return pair_mask(n_fields, keep)
+
+
+def pruned_layout(keep, field_start):
+    """(base int64[n_fields + 1], P int64[n_fields]) of a pruned serving table (include/ffm_engine.h "Pruned serving
+    tables"): a feature i of field f owns P[f] = popcount(keep[f]) slots from base[f] + (i - field_start[f]) * P[f], its
+    slot towards partner g at rank popcount(keep[f] & ((1 << g) - 1)); base[n_fields] is the table's slots."""
+    w = [int(x) for x in np.asarray(keep, np.uint64).reshape(-1)]
+    pair_mask_pairs(w)  # (the mask's own checks)
+    start = np.asarray(field_start, np.int64).reshape(-1)
+    if start.shape[0] != len(w) + 1 or start[0] != 0 or (np.diff(start) < 0).any():
+        raise ValueError("field_start: n_fields + 1 ascending ids from 0")
+    P = np.array([bin(x).count("1") for x in w], np.int64)
+    return np.concatenate([[0], np.cumsum(np.diff(start) * P)]).astype(np.int64), P
+
+
+def prune_rows(vec_w, keep, field_start):
+    """Full-length rows [n_feats, n_fields * k] as a pruned table of (keep, field_start) holds them: a copy with the slot
+    towards g of every feature of field f set to +0.0 wherever bit g of keep[f] is clear."""
+    w = [int(x) for x in np.asarray(keep, np.uint64).reshape(-1)]
+    F = len(w)
+    start = np.asarray(field_start, np.int64).reshape(-1)
+    out = np.array(vec_w, np.float32, copy=True)
+    rows = out.reshape(out.shape[0], F, -1)
+    for f in range(F):
+        for g in range(F):
+            if not (w[f] >> g) & 1:
+                rows[start[f]:start[f + 1], g, :] = np.float32(0.0)
+    return out
+
+
 def pair_mask_top(n_fields, loss, n_keep):
     """The mask of the n_keep pairs whose removal costs most.  loss[V + 1] as predict_pair_ablated sums it (V =
     pair_count(n_fields)): loss[v] the loss without pair v, loss[V] the loss of the rows.  The pairs are ranked by
@@ -979,12 +1017,15 @@ class Engine:
                  w_beta=1.0, w_l1=0.1, w_l2=5.0, init_mean=0.0, init_stddev=0.02, seed=42,
                  max_batch_rows=8192, max_batch_nnz=None, device_id=0, n_shards=1, shard_rank=0,
                  stream=None, skip_init=False, max_row_nnz=0, learn=False, field_start=None, hash_ids=False,
-                 serve=None, normalize=False):
+                 serve=None, normalize=False, prune=None):
         """normalize: every row handed over in host memory is scaled to unit Euclidean length on the device before
         any kernel reads its values (include/ffm_engine.h "Normalised rows"; normalize_rows is the same on the host).
         serve: None = a training engine; "f32" / "f16" / "f8" = a serving engine (include/ffm_engine.h "Serving
         engines"): bias, lin_w and a latent table of w alone in fp32 bits, IEEE binary16 or block-scaled e4m3
-        (serve_f8_encode is that format's definition) -- prediction only."""
+        (serve_f8_encode is that format's definition) -- prediction only.
+        prune: with serve "f32" / "f16" and field_start, a PRUNED serving table (include/ffm_engine.h "Pruned serving
+        tables"): the mask whose kept pairs' slots the table stores, as set_pair_mask takes one -- the words or an
+        iterable of kept pairs (pruned_layout and prune_rows are the layout and the contents in numpy)."""
         self.lib = load_library()
         if serve not in SERVE_FLAGS:
             raise ValueError("serve: None, 'f32', 'f16' or 'f8'")
@@ -1008,7 +1049,13 @@ class Engine:
             cfg.field_start = _i(self._field_start)
         self.cfg = cfg
         self.h = _vp()
-        self._check(self.lib.ffm_engine_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+        self._prune = None
+        if prune is None:
+            self._check(self.lib.ffm_engine_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+        else:
+            self._prune = _mask_words(cfg.n_fields, prune)
+            self._check(self.lib.ffm_engine_create_pruned(ctypes.byref(cfg), self._prune.ctypes.data_as(_vp),
+                                                          int(self._prune.shape[0]), ctypes.byref(self.h)))
         self.model_type = cfg.model_type
         self.n_feats, self.n_fields, self.n_factors = cfg.n_feats, cfg.n_fields, cfg.n_factors
         self.row_len = int(self.lib.ffm_engine_row_len(self.h))
@@ -1051,6 +1098,15 @@ class Engine:
         self._check(self.lib.ffm_engine_set_weights(self.h, _f(b.reshape(-1)[:1].copy()) if b is not None else None,
                                                     _f(lw), _f(vw) if vw is not None and vw.size else None))
 
+    def pruned_layout(self):
+        """(base int64[n_fields + 1], P int64[n_fields]) of this pruned serving table (ffm_engine_pruned_layout_host)."""
+        if getattr(self, "_prune", None) is None:  # (a group's shards are built without __init__)
+            raise EngineError(E_INVALID, "pruned_layout: not a pruned serving table (Engine(..., prune=...))")
+        base = np.zeros(self.n_fields + 1, np.int64)
+        self._check(self.lib.ffm_engine_pruned_layout_host(self._prune.ctypes.data_as(_vp), self.n_fields, _i(self._field_start),
+                                                           base.ctypes.data_as(_i64p)))
+        return base, np.array([bin(int(x)).count("1") for x in self._prune], np.int64)
+
     def model_bytes(self):
         """Bytes of HBM requested for the model arrays: bias, linear, latent (ffm_engine_model_bytes)."""
         return int(self.lib.ffm_engine_model_bytes(self.h))
@@ -1092,6 +1148,9 @@ class Engine:
             raise EngineError(E_UNSUPPORTED, "raw rows are a serving engine's: a training engine has get_rows / set_rows")
         if self.serve not in RAW_DTYPES:
             raise EngineError(E_UNSUPPORTED, "raw rows and serving deltas are not available on an %s serving engine" % self.serve)
+        if getattr(self, "_prune", None) is not None:
+            raise EngineError(E_UNSUPPORTED, "export_delta / apply_delta are not available on a pruned serving table: a delta "
+                                             "holds full-length rows in the table's own bits")
         return RAW_DTYPES[self.serve]
 
     def get_rows_raw(self, ids):
@@ -1679,10 +1738,7 @@ class Engine:
         if keep is None:
             self._check(self.lib.ffm_engine_set_pair_mask(self.h, None, 0))
             return
-        if isinstance(keep, np.ndarray) and keep.ndim == 1 and keep.dtype.kind in "ui":
-            words = np.ascontiguousarray(keep, np.uint64)
-        else:
-            words = pair_mask(self.n_fields, keep)
+        words = _mask_words(self.n_fields, keep)
         self._check(self.lib.ffm_engine_set_pair_mask(self.h, words.ctypes.data_as(_vp), int(words.shape[0])))
 
     def pair_mask(self):

@@ -152,6 +152,14 @@ const std::string_view cmd_help =
     "              and --device_rows true then give the masked model's numbers.  Prints `pair mask: K of V pairs kept, from\n"
     "              FILE`.  FFM only, one GPU, --n_fields <= 64, --n_factors 4, 8, 16, 32 or 64; not with --n_epochs > 0,\n"
     "              --field_importance, --pair_importance or --cmd true\tdefault:(none)\n"
+    "--serve_pruned <bool>: with --serve_weights f32|f16 --pair_mask @FILE --hash_feats true --field_ranges uniform|@FILE: the\n"
+    "              serving engine is created in the mask's shape, a pruned serving table: a feature of field f stores only its\n"
+    "              slots towards the partners the file keeps for f (every hashed id lies in its field's range, so no other\n"
+    "              slot is ever read), and a row kernel of its own gathers from that layout.  Used as --pair_mask is:\n"
+    "              --resume_from ck --n_epochs 0 with --eval_data, --metrics auc, --predict_data / --predict_out, --device_rows\n"
+    "              true; every loss, AUC and score is the one the same run prints and writes without the flag, bit for bit.\n"
+    "              Prints `pruned serving table: S of T slots kept, B bytes of model`.  Not with --serve_weights f8,\n"
+    "              --apply_deltas, --field_importance or --pair_importance\tdefault:false\n"
     "--publish_path <prefix>: after every epoch's training (after that epoch's --refresh_weights refresh when it is on,\n"
     "              before its evaluation) write <prefix>.<epochs_done>.delta: the features whose serving bits moved since\n"
     "              the previous delta, in a serving engine's own format -- delta 1 is relative to a fresh serving engine of\n"
@@ -336,6 +344,7 @@ void config_options::parse_option(int argc, char *argv[]) {
       pair_loss_budget_set = true;
     }
     else if (k == "--pair_mask") pair_mask = v;
+    else if (k == "--serve_pruned") serve_pruned = assign_bool(v);
     else if (k == "--n_gpus") n_gpus = std::stoi(v);
     else if (k == "--field_ranges") field_ranges = v;
     else if (k == "--field_ranges_out") field_ranges_out = v;
@@ -440,6 +449,25 @@ void config_options::parse_option(int argc, char *argv[]) {
     if (refresh_weights)
       throw std::invalid_argument(what + "holds no accumulators to refresh from: write the checkpoint with --refresh_weights true instead");
     if (model_type != "FFM") throw std::invalid_argument(what + "is for FFM models only (got --model_type " + model_type + ")");
+  }
+  // --serve_pruned true: a serving engine in the shape of its mask, which needs the mask, a format with a pruned layout
+  // and every id inside its field's range (refused here, before a device is opened)
+  if (serve_pruned) {
+    const std::string what = "--serve_pruned true ";
+    if (serve_weights == "none") throw std::invalid_argument(what + "shapes a serving engine's table: it needs --serve_weights f32 or f16");
+    if (serve_weights == "f8")
+      throw std::invalid_argument(what + "is not available with --serve_weights f8: a pruned serving table is f32 or f16");
+    if (pair_mask.empty()) throw std::invalid_argument(what + "stores the kept pairs' slots only: it needs --pair_mask @FILE");
+    if (!apply_deltas.empty())
+      throw std::invalid_argument(what + "is not allowed with --apply_deltas: a serving delta speaks full-length rows");
+    if (field_importance) throw std::invalid_argument(what + "is not allowed with --field_importance true: the variants are the whole model's");
+    if (pair_importance) throw std::invalid_argument(what + "is not allowed with --pair_importance true: the variants are the whole model's");
+    if (!hash_feats)
+      throw std::invalid_argument(what + "needs --hash_feats true: only then does every id lie in its field's range");
+    const bool ranged = field_ranges == "uniform" || (!field_ranges.empty() && field_ranges[0] == '@');
+    if (!ranged) throw std::invalid_argument(what + "lays the table out by the fields' id ranges: it needs --field_ranges uniform or @FILE");
+    if (field_ranges == "uniform" && n_feats < n_fields)
+      throw std::invalid_argument(what + "with --field_ranges uniform needs --n_feats >= --n_fields: every field owns an id range");
   }
   if (!publish_path.empty()) {
     // a shadow serving engine beside one whole FFM training engine (refused here, before a device is opened)

@@ -75,6 +75,11 @@ struct config_options {
   // predicts with the file's pairs only (include/ffm_engine.h "Pair masks")
   int pair_keep = -1;
   std::string pair_mask_out, pair_mask;
+  // --serve_pruned true (with --serve_weights f32 | f16, --pair_mask @FILE, --hash_feats true and --field_ranges uniform |
+  // @FILE): the serving engine stores the kept pairs' slots only (include/ffm_engine.h "Pruned serving tables").
+  // prune_keep: the file's mask words (filled by main.cpp before a model exists, which is created in their shape)
+  bool serve_pruned = false;
+  std::vector<uint64_t> prune_keep;
   // --pair_curve LIST|auto (with --pair_importance true): after the pairs' pass, one more pass over --eval_data gives the
   // loss (and AUC) of "keep the best N pairs" for every listed N at once (include/ffm_engine.h "Pruning curve").
   // pair_curve is the flag as given ("" = not asked for); pair_curve_keep its N, ascending and without duplicates

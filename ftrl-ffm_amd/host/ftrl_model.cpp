@@ -89,6 +89,7 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
     // [f * n_feats / n_fields, (f + 1) * n_feats / n_fields) (python/generate_data.py:272-306 lays
     // ids out per field); every shard then stores only the slots it owns
     if (mt != FFM_MODEL_FFM) throw std::invalid_argument("--n_gpus > 1 shards the FFM field pairs: model_type must be FFM");
+    if (opt.serve_pruned) throw std::invalid_argument("--serve_pruned true is one engine's table: the group path has none");
     if (n_gpus_ > 1 && opt.field_ranges != "uniform")
       throw std::invalid_argument("--n_gpus > 1 needs --field_ranges uniform (per-field id ranges)");
     if (!opt.field_start.empty())
@@ -133,9 +134,20 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
       cfg.field_start = fs.data();  // (copied by ffm_engine_create)
     }
     field_start_ = fs;
-    rc = ffm_engine_create(&cfg, &eng_);
-    if (rc == FFM_E_INVALID) throw std::invalid_argument(ffm_engine_last_error());
-    check(rc, "ffm_engine_create");
+    if (opt.serve_pruned) {
+      // --serve_pruned: the serving engine in the shape of the mask main.cpp read (include/ffm_engine.h "Pruned serving
+      // tables"); load_checkpoint's full-length rows then leave their dropped slots behind
+      rc = ffm_engine_create_pruned(&cfg, opt.prune_keep.data(), static_cast<int32_t>(opt.prune_keep.size()), &eng_);
+      if (rc == FFM_E_INVALID || rc == FFM_E_UNSUPPORTED) throw std::invalid_argument(std::string("--serve_pruned true: ") + ffm_engine_last_error());
+      check(rc, "ffm_engine_create_pruned");
+      std::vector<int64_t> base(static_cast<size_t>(opt.n_fields) + 1);
+      check(ffm_engine_pruned_layout_host(opt.prune_keep.data(), opt.n_fields, fs.data(), base.data()), "ffm_engine_pruned_layout_host");
+      pruned_slots_ = base.back();
+    } else {
+      rc = ffm_engine_create(&cfg, &eng_);
+      if (rc == FFM_E_INVALID) throw std::invalid_argument(ffm_engine_last_error());
+      check(rc, "ffm_engine_create");
+    }
   }
   // --min_count / --rare_ids: the keep-map main.cpp resolved -- training, serving and scoring engines alike fold by
   // it wherever they hash (include/ffm_engine.h "Rare ids"; a group is refused there as on the command line)
@@ -153,6 +165,9 @@ FtrlModel::FtrlModel(const config_options &opt, int mt)
   }
   if (serving_)
     std::printf("serving weights: %s, %lld bytes of model\n", opt.serve_weights.c_str(), static_cast<long long>(ffm_engine_model_bytes(eng_)));
+  if (opt.serve_pruned)
+    std::printf("pruned serving table: %lld of %lld slots kept, %lld bytes of model\n", static_cast<long long>(pruned_slots_),
+                static_cast<long long>(opt.n_feats) * opt.n_fields, static_cast<long long>(ffm_engine_model_bytes(eng_)));
   row_len_ = ffm_engine_row_len(eng_);
   lin_w.resize(static_cast<size_t>(n_feats));
   vec_w.owner_ = this;

@@ -271,6 +271,7 @@ class FtrlModel {
   int32_t flags_ = 0;
   bool serving_ = false;   // --serve_weights f32 | f16: a serving engine behind this model (prediction only)
   std::string serve_fmt_ = "none";  // ... its format
+  int64_t pruned_slots_ = 0;  // --serve_pruned true: the slots its table stores
   // serving deltas: the shadow serving engine of publish_delta (null until asked for), its format, the deltas it
   // has behind it; deltas_applied_: those apply_delta has pushed into this (serving) model
   ffm_engine *shadow_ = nullptr;

@@ -60,7 +60,8 @@ int main(int argc, char *argv[]) {
         task.restore(behind);
       }
       // --pair_mask @FILE: once, on the model as loaded (the run trains nothing: cmd_option refused --n_epochs > 0)
-      if (!opt.pair_mask.empty()) ftrl::load_pair_mask(opt, *task.model_ptr);
+      // (--serve_pruned true: the mask is the table's shape, set when the engine was created)
+      if (!opt.pair_mask.empty() && !opt.serve_pruned) ftrl::load_pair_mask(opt, *task.model_ptr);
       task.train();
       // --auc_key_field on a run that trains nothing (--resume_from ck --n_epochs 0 --eval_data F): one evaluation pass
       // of the loaded model, numbered by the epochs it has behind it -- there is no epoch to print the line after
@@ -101,6 +102,8 @@ int main(int argc, char *argv[]) {
     ftrl::resolve_value_buckets(opt);
     ftrl::resolve_rare_ids(opt);
     ftrl::resolve_field_ranges(opt);
+    // --serve_pruned true: the mask file, read before a model exists: the serving engine is created in its shape
+    ftrl::resolve_serve_pruned(opt);
     if (opt.online) {
       ftrl::FtrlOnline task(opt);
       if (weights.on) task.set_sample_weights(std::move(weights));

@@ -122,6 +122,14 @@ void load_pair_mask(const config_options &opt, FtrlModel &m) {
   std::printf("pair mask: %zu of %d pairs kept, from %s\n", kept.size(), pair_count(opt.n_fields), file.c_str());
 }
 
+void resolve_serve_pruned(config_options &opt) {
+  if (!opt.serve_pruned) return;
+  const std::string file = opt.pair_mask.substr(1);  // (@FILE: cmd_option checked the form)
+  const PairList kept = read_pair_mask(file, opt.n_fields);
+  opt.prune_keep = pair_mask_words(opt.n_fields, kept);
+  std::printf("pair mask: %zu of %d pairs kept, from %s\n", kept.size(), pair_count(opt.n_fields), file.c_str());
+}
+
 void publish_and_print(FtrlModel &m, const std::string &prefix, const std::string &fmt, long long epoch, long long n_feats) {
   const FtrlModel::DeltaResult r = m.publish_delta(prefix, fmt, epoch);
   std::printf("epoch %lld published: %lld of %lld features moved, %lld bytes -> %s\n", epoch, r.n_moved, n_feats, r.bytes, r.file.c_str());

@@ -146,6 +146,9 @@ void run_pair_curve(const config_options &opt, FtrlModel &m, const std::vector<d
 // --pair_mask @FILE: reads the file against the run's --n_fields, sets the mask on the loaded model
 // (FtrlModel::set_pair_mask) and prints `pair mask: K of V pairs kept, from FILE`.
 void load_pair_mask(const config_options &opt, FtrlModel &m);
+// --serve_pruned true: the same file, read before a model exists into opt.prune_keep, in whose shape the serving engine
+// is then created (FtrlModel's constructor: ffm_engine_create_pruned); prints the same line.
+void resolve_serve_pruned(config_options &opt);
 // --publish_path: FtrlModel::publish_delta(prefix, fmt, epoch) and its line,
 // `epoch N published: M of F features moved, B bytes -> FILE`
 void publish_and_print(FtrlModel &m, const std::string &prefix, const std::string &fmt, long long epoch, long long n_feats);

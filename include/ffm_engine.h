@@ -1320,6 +1320,50 @@ int ffm_engine_predict_pair_curve_device(ffm_engine *e, int32_t n_rows, int32_t 
                                          int32_t output_prob, float *out, double *loss_sum_out);
 int ffm_engine_pair_curve_read(ffm_engine *e, int32_t reset, ffm_metrics *out /* [n_cuts + 1] */);
 
+/* ---- Pruned serving tables: store and gather only the kept pairs' slots -----------------------------------
+ * A pair mask prunes a serving engine's time; its table still holds every slot, [n_feats][n_fields * n_factors].
+ * Where every id belongs to exactly one field (per-field id ranges, field_start: what hashed ids give), a feature
+ * of field f only ever needs the slots towards the partners in keep[f].  A pruned serving table stores those and
+ * nothing else, and its row kernel gathers from them.
+ * ffm_engine_create_pruned  cfg is a serving config with exactly one of FFM_FLAG_SERVE_F32 / FFM_FLAG_SERVE_F16
+ *   (FFM_FLAG_SERVE_F8: FFM_E_UNSUPPORTED; neither or both: FFM_E_INVALID) and everything "Serving engines" asks.
+ *   cfg->field_start must be non-NULL, ascend, start at 0 and end at n_feats (FFM_E_INVALID).  keep is a pair mask
+ *   exactly as ffm_engine_set_pair_mask defines and checks one, with its messages: n_fields the config's and at most
+ *   64 (FFM_E_UNSUPPORTED above), symmetric, no bit at or above n_fields (FFM_E_INVALID).  All of this is checked
+ *   before a device is asked for.  ffm_engine_config does not change, and ffm_engine_create is what it was.
+ * LAYOUT, bit for bit.  P[f] = popcount(keep[f]).  A feature i of field f (field_start[f] <= i < field_start[f + 1])
+ *   owns P[f] consecutive slots of n_factors elements; its slot towards partner g (bit g of keep[f] set) has rank
+ *   popcount(keep[f] & ((1 << g) - 1)); its first slot is base[f] + (i - field_start[f]) * P[f], base the prefix sum
+ *   of (field_start[f + 1] - field_start[f]) * P[f] in field order, base[n_fields] the table's slots.  A field with
+ *   P[f] == 0 stores nothing.  Elements are fp32 bits or IEEE binary16 as on the unpruned formats.  2^32 slots or
+ *   more: FFM_E_UNSUPPORTED.  Element and byte offsets are 64-bit everywhere.
+ * ffm_engine_pruned_layout_host  base_out[n_fields + 1] of a mask and ranges, on the host with no device; the mask
+ *   and range checks and messages of ffm_engine_create_pruned (engine.py: pruned_layout is the numpy definition).
+ * PREDICTIONS  On a row in which every entry's id lies in its field's range, every row-prediction entry point
+ *   (ffm_engine_predict_batch, _predict_batch_device, _predict_batch_async[_scores], _predict_batch_async_resident)
+ *   gives the bits of an unpruned serving engine of the same format holding the same weights under
+ *   ffm_engine_set_pair_mask(keep): linear terms stay, the ordered sum runs over the kept pairs' terms in pair order,
+ *   dropped pairs are neither gathered nor added.  An entry whose id lies OUTSIDE its field's range is erased whole,
+ *   linear term included, exactly as an id >= n_feats is: it has no slots in this table.  Rows of more than 128
+ *   entries (or max_row_nnz) are NaN and FFM_E_CAPACITY, as on every serving engine.
+ * CONTENTS  At create a stored element is the value a training engine of the same config draws at the element's
+ *   full-length index (feat * n_fields * n_factors + g * n_factors + j), rounded to the format; FFM_FLAG_SKIP_INIT
+ *   gives zero bits.  ffm_engine_pack_weights(dst = pruned, src = training engine) copies the kept slots (and bias,
+ *   lin_w) in one streaming pass; its ffm_pack_stats count the elements written.  ffm_engine_set_weights, _set_rows,
+ *   _get_weights and _get_rows speak full-length fp32 rows: a write ignores the dropped slots, a read gives +0.0f
+ *   for them (engine.py: prune_rows).  ffm_engine_model_bytes is 4 + 4 * n_feats + slots * n_factors * (4 or 2).
+ *   ffm_engine_get_pair_mask reports the table's mask, is_set = 1.
+ * REFUSED, FFM_E_UNSUPPORTED, the model unchanged: ffm_engine_set_pair_mask (clearing too: the mask is the table's
+ *   shape), ffm_engine_score_candidates[_device], the ablation and curve calls, ffm_engine_sync_weights,
+ *   ffm_engine_get_rows_raw / _set_rows_raw (and with them deltas); every training entry point as on any serving
+ *   engine.
+ * OUT OF SCOPE  f8 pruned tables; deltas and sync into a pruned table; pruned tables without field ranges;
+ *   n_fields > 64; groups and shards. */
+int ffm_engine_create_pruned(const ffm_engine_config *cfg, const uint64_t *keep /* [n_fields] */, int32_t n_fields,
+                             ffm_engine **out);
+int ffm_engine_pruned_layout_host(const uint64_t *keep /* [n_fields] */, int32_t n_fields,
+                                  const int32_t *field_start /* [n_fields + 1] */, int64_t *base_out /* [n_fields + 1] */);
+
 /* ---- Serving deltas: sync a serving engine, publish only what moved --------------------------------------
  * ffm_engine_pack_weights takes all of a model: it streams every record of the training engine and writes the
  * whole table.  A trainer that never stops moves a few per cent of its features between two publications;

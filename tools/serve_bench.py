@@ -5,6 +5,10 @@
   python tools/serve_bench.py                 the three kinds, one process each, one after another (the three
                                               models do not fit in HBM together), a summary at the end
   python tools/serve_bench.py --kind f16      one kind (training, f32, f16, f8), one JSON line
+  python tools/serve_bench.py --pruned --kind f16
+                                              pruned serving tables (include/ffm_engine.h "Pruned serving tables"):
+                                              model bytes and per-block time against the unpruned engine under the
+                                              same mask, keeping all, half, a quarter and a tenth of the cross pairs
   python tools/serve_bench.py --candidates 26:13:64
                                               one context against many candidates (include/ffm_engine.h "Scoring
                                               candidates"; profiles/score_candidates.md): per serving format,
@@ -296,6 +300,61 @@ def main_candidates(args):
             json.dump(dict(results=results), f, indent=1)
 
 
+def run_pruned(args):
+    """--pruned: per kept share of the 741 cross pairs (all, half, a quarter, a tenth; the diagonal kept), a pruned
+    serving table (include/ffm_engine.h "Pruned serving tables") against the unpruned engine of the same format under
+    the same mask, same process, alternating windows: model bytes, and predict_batch_device per block."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("serve_bench needs a GPU: none found")
+    import ftrl_ffm_amd as fa
+    from ftrl_ffm_amd import synth
+    fa.build()
+    fmt = args.kind or "f16"
+    nf = args.n_feats - args.n_feats % N_FIELDS
+    fs = (np.arange(N_FIELDS + 1, dtype=np.int64) * (nf // N_FIELDS)).astype(np.int32)
+    kw = dict(max_batch_rows=ROWS, max_batch_nnz=ROWS * N_FIELDS, seed=42, max_row_nnz=N_FIELDS, field_start=fs, serve=fmt)
+    gen = synth.Generator(N_FIELDS, nf, dist="zipf", seed=42)
+    blocks = []
+    for _ in range(args.blocks):
+        b = gen.block(ROWS)
+        blocks.append((b.n_rows, int(b.row_ptr[-1]),
+                       [torch.from_numpy(np.ascontiguousarray(getattr(b, key))).cuda() for key in ("row_ptr", "field", "feat", "val", "label")]))
+    out = torch.zeros(ROWS, dtype=torch.float32, device="cuda")
+    loss = torch.zeros(1, dtype=torch.float64, device="cuda")
+    masked = fa.Engine("FFM", nf, N_FIELDS, N_FACTORS, **kw)
+    cross = [(f, g) for f in range(N_FIELDS) for g in range(f + 1, N_FIELDS)]
+    order = np.random.default_rng(7).permutation(len(cross))
+
+    def window(eng, steps):
+        t0 = time.perf_counter()
+        for i in range(steps):
+            n, nnz, d = blocks[i % len(blocks)]
+            eng.predict_batch_device(n, nnz, *[a.data_ptr() for a in d], 0, out.data_ptr(), loss.data_ptr())
+        eng.sync()
+        return 1e6 * (time.perf_counter() - t0) / steps
+
+    for share in (1.0, 0.5, 0.25, 0.1):
+        kept = [cross[v] for v in order[:int(round(share * len(cross)))]] + [(f, f) for f in range(N_FIELDS)]
+        words = fa.pair_mask(N_FIELDS, kept)
+        masked.set_pair_mask(words)
+        pruned = fa.Engine("FFM", nf, N_FIELDS, N_FACTORS, prune=words, **kw)
+        steps = max(64, int(args.window / (window(masked, 64) * 1e-6)) + 1)  # (also the warm-up of both)
+        window(pruned, 64)
+        us = {"masked": [], "pruned": []}
+        for _ in range(args.repeats):
+            us["masked"].append(window(masked, steps))
+            us["pruned"].append(window(pruned, steps))
+        res = dict(fmt=fmt, n_feats=nf, kept_cross_pairs=len(kept) - N_FIELDS, steps_per_window=steps,
+                   model_bytes_unpruned=masked.model_bytes(), model_bytes_pruned=pruned.model_bytes(),
+                   **{key + "_us_per_block": dict(median=sorted(v)[len(v) // 2], min=min(v), max=max(v)) for key, v in us.items()})
+        res["pruned_over_masked"] = res["pruned_us_per_block"]["median"] / res["masked_us_per_block"]["median"]
+        pruned.close()
+        print("SERVE_BENCH " + json.dumps(res), flush=True)
+    masked.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--candidates", metavar="CTXFIELDS:CANDFIELDS:PER_REQUEST",
@@ -310,7 +369,13 @@ def main():
     ap.add_argument("--profile-blocks", type=int, default=200)
     ap.add_argument("--timeout", type=int, default=240, help="seconds a child process may take")
     ap.add_argument("--out", help="also write the results there as JSON")
+    ap.add_argument("--pruned", action="store_true",
+                    help="pruned serving tables against the masked unpruned engine, --kind f32 or f16 (default f16)")
     args = ap.parse_args()
+    if args.pruned:
+        if args.kind in ("training", "f8"):
+            raise SystemExit("--pruned needs a format with a pruned layout (f32 or f16)")
+        return run_pruned(args)
     if args.candidates:
         if args.kind in ("training", "f8"):  # (an f8 engine refuses score_candidates)
             raise SystemExit("--candidates needs a serving kind that scores candidates (f32 or f16)")
