@@ -51,6 +51,7 @@
 #include "kernels_keyed.h"
 #include "kernels_serve.h"
 #include "kernels_serve8.h"
+#include "kernels_catalog.h"
 #include "kernels_delta.h"
 #include "kernels_ablate.h"
 #include "kernels_ablate_pairs.h"
@@ -128,7 +129,7 @@ enum KernelId {
   K_GROUP_KEYS, K_GROUP_SORT, K_GROUP_FINISH, K_ROW, K_TMP_GRAD,
   K_LOSS_SUM, K_LINEAR_UPDATE, K_BIAS_UPDATE, K_LATENT_UPDATE, K_LATENT_UPDATE_FEW, K_LATENT_UPDATE_WALK, K_LATENT_UPDATE_GIANT,
   K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC, K_PUSH_SCORES, K_SERVE_ROW,
-  K_SERVE_CTX, K_SERVE_CAND,
+  K_SERVE_CTX, K_SERVE_CAND, K_CATALOG_U, K_CATALOG_GEMM,
   K_KEYED_CAPTURE, K_KEYED_SORT_HIST, K_KEYED_SORT_SCAN, K_KEYED_SORT_SCATTER, K_KEYED_RANK,
   K_UPLOAD, K_NORM_ROWS,
   K_COUNT
@@ -137,7 +138,7 @@ const char *kKernelNames[K_COUNT] = {
     "group_keys_kernel", "group_radix_sort", "group_finish_kernel", "row_kernel<train>", "tmp_grad_kernel", "loss_sum_kernel",
     "linear_update_kernel", "bias_update_kernel", "update_kernel", "update_few_kernel", "update_walk_kernel", "update_giant_kernel",
     "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel", "push_scores_kernel", "serve_wave_kernel",
-    "serve_context_kernel", "serve_candidate_kernel",
+    "serve_context_kernel", "serve_candidate_kernel", "catalog_u_kernel", "catalog_gemm_kernel",
     "keyed_capture_kernel", "keyed_sort_hist_kernel", "keyed_sort_scan_kernels", "keyed_sort_scatter_kernel", "keyed_rank_kernels",
     "pull_block_kernel", "normalize_rows_kernel"};
 
@@ -448,6 +449,13 @@ struct ffm_engine {
   float *d_ctx_val = nullptr;
   size_t cx_ent_cap = 0, cx_head_cap = 0, cx_terms_cap = 0, cx_cand_cap = 0;
   size_t ctx_ptr_cap = 0, req_ptr_cap = 0, ctx_field_cap = 0, ctx_feat_cap = 0, ctx_val_cap = 0;
+  // ffm_engine_score_catalog[_device] (engine_catalog.h): what catalog_u_kernel leaves for catalog_gemm_kernel (base, U
+  // and the shifts; cat.u in bytes) and the host call's output [n_req][n_cand], all made by the first call, grown to the
+  // largest call seen; an engine that never scores a catalogue holds none of it
+  ftrl_dev::CatalogDev cat{};
+  char *cat_u = nullptr;
+  float *cat_out = nullptr;
+  size_t cat_base_cap = 0, cat_shift_cap = 0, cat_u_cap = 0, cat_out_cap = 0;
   // field and pair ablation (include/ffm_engine.h "Field ablation", "Pair ablation"; engine_ablate.h), each set all
   // made by its enable call for its V variants -- n_fields + 1, or n_fields (n_fields + 1) / 2 + 1 --: out [V][max_rows]
   // scores and loss the same shape (the kernel's variant-major outputs), sums [V], part [V][kLossParts + 1] the loss
@@ -902,6 +910,7 @@ int ffm_engine_shard_plan(int32_t n_fields, int32_t n_shards, int32_t field_map,
 #include "engine_stage.h"
 #include "engine_refresh.h"
 #include "engine_serve.h"
+#include "engine_catalog.h"
 #include "engine_delta.h"
 #include "engine_profile.h"
 #include "engine_metrics.h"

@@ -1,0 +1,120 @@
+// engine_catalog.h -- request contexts against a whole id range of one field (include/ffm_engine.h "Scoring a
+// catalogue"; kernels_catalog.h): what the two entry points check, the buffers they grow, and the three launches --
+// the engine's own row kernel over the contexts (base), catalog_u_kernel, catalog_gemm_kernel per 128 requests.
+// Part of engine.hip's translation unit (included inside its extern "C" block).
+
+static int catalog_check(ffm_engine *e, int32_t n_req, int32_t cand_field, int32_t cand_first, int32_t n_cand) {
+  if (!e) return fail(FFM_E_INVALID, "null engine");
+  if (!serving(e))
+    return fail(FFM_E_UNSUPPORTED, "score_catalog needs a serving engine (FFM_FLAG_SERVE_F32 / _F16): "
+                                   "ffm_engine_pack_weights copies a training engine's weights into one");
+  F8_REFUSE(e, "score_catalog");
+  PRUNED_REFUSE(e, "score_catalog");
+  MASK_REFUSE(e, "score_catalog");
+  if (e->norm_rows_on)
+    return fail(FFM_E_INVALID, "score_catalog is not available on an engine with FFM_FLAG_NORM_ROWS: a candidate would change "
+                               "the scale of its context's terms");
+  if (e->in_group || e->m.n_shards > 1)
+    return fail(FFM_E_UNSUPPORTED, "score_catalog is not available on a group's or a shard's engine: it reads one whole table");
+  if (n_req < 0 || n_cand < 0) return fail(FFM_E_INVALID, "negative n_req / n_cand");
+  if (cand_field < 0 || cand_field >= e->m.n_fields)
+    return fail(FFM_E_INVALID, "cand_field " + std::to_string(cand_field) + " lies outside [0, n_fields)");
+  if (cand_first < 0 || static_cast<int64_t>(cand_first) + n_cand > e->m.n_feats)
+    return fail(FFM_E_INVALID, "the candidate range [cand_first, cand_first + n_cand) lies outside [0, n_feats]");
+  if (n_req > e->max_rows) return fail(FFM_E_CAPACITY, "more requests than max_batch_rows");
+  if (static_cast<int64_t>(n_req) * n_cand > 2147483647ll)
+    return fail(FFM_E_CAPACITY, "n_req * n_cand exceeds 2^31 - 1 scores: split the range");
+  HIP_TRY(hipSetDevice(e->cfg.device_id));
+  return eval_launch_pending(e);
+}
+
+// The requests in whole tiles of their launches: 128 per launch, the last one 32, 64 or 128.
+static int catalog_rows(int n_req) {
+  const int rest = n_req % 128;
+  return n_req - rest + (rest ? kCatTile * catalog_rt(cdiv(rest, kCatTile)) : 0);
+}
+
+// The launches, on arrays in device memory.  cap: the longest context, in [1, max_row_nnz].
+static int catalog_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                          const float *ctx_val, int32_t ctx_nnz, int cap, int32_t g, int32_t first, int32_t n_cand, float v,
+                          int32_t output_prob, float *out) {
+  const ModelDev &m = e->m;
+  const int L = m.row_len, es = m.lat_fmt == SERVE_F16 ? 2 : 4;
+  const int rows = catalog_rows(n_req), lp = catalog_lp(m.lat_fmt, L);
+  int rc;
+  if ((rc = e->grow(&e->cat.base, &e->cat_base_cap, static_cast<size_t>(rows)))) return rc;
+  if ((rc = e->grow(&e->cat.shift, &e->cat_shift_cap, static_cast<size_t>(rows)))) return rc;
+  if ((rc = e->grow(&e->cat_u, &e->cat_u_cap, static_cast<size_t>(rows) * lp * 4))) return rc;  // (fp32, or two planes of halves)
+  CatalogDev cd = e->cat;
+  cd.u = e->cat_u;
+  cd.rows = rows;
+  cd.lp = lp;
+  // base_r: the bits of predict_batch on the context rows
+  launch_row_kernel(e, Rows{n_req, ctx_nnz, ctx_ptr, ctx_field, ctx_feat, ctx_val, nullptr}, cap, false, cd.base, 0);
+  const int lds_cap = std::min(cap, kPredLdsCap);
+  LAUNCH(e, K_CATALOG_U, catalog_u_fn(m.lat_fmt), cdiv(rows, kPredRows), 64 * kPredRows, cand_ctx_lds_bytes(lds_cap), m, n_req, ctx_ptr,
+         ctx_field, ctx_feat, ctx_val, g, cd, cap, lds_cap);
+  const char *const tab = reinterpret_cast<const char *>(m.lat) + static_cast<int64_t>(first) * L * es;
+  const int grid = static_cast<int>((static_cast<int64_t>(n_cand) + kCatCands - 1) / kCatCands);
+  for (int r0 = 0; r0 < n_req; r0 += 128) {
+    const int rt = catalog_rt(cdiv(std::min(128, n_req - r0), kCatTile));
+    LAUNCH(e, K_CATALOG_GEMM, catalog_gemm_fn(m.lat_fmt, rt), grid, 64 * kCatWaves, 0, tab, m.lin_w + first, L, cd, r0, n_req,
+           static_cast<int64_t>(n_cand), v, output_prob, out);
+  }
+  HIP_TRY(hipGetLastError());
+  return FFM_OK;
+}
+
+int ffm_engine_score_catalog_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                    const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
+                                    int32_t n_cand, float cand_val, int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob,
+                                    float *out) {
+  if (int rc = catalog_check(e, n_req, cand_field, cand_first, n_cand)) return rc;
+  if (n_req == 0 || n_cand == 0) return FFM_OK;
+  if (ctx_nnz < 0 || ctx_cap < 0) return fail(FFM_E_INVALID, "negative ctx_nnz / ctx_cap");
+  if (!ctx_ptr || !out || (ctx_nnz > 0 && (!ctx_field || !ctx_feat || !ctx_val))) return fail(FFM_E_INVALID, "null array");
+  // (a context beyond the engine's row limit is flagged by the row kernel whatever the cap says)
+  const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
+  return catalog_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, cand_field, cand_first, n_cand, cand_val,
+                        output_prob, out);
+}
+
+int ffm_engine_score_catalog(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                             const float *ctx_val, int32_t cand_field, int32_t cand_first, int32_t n_cand, float cand_val,
+                             int32_t output_prob, float *out) {
+  int rc = catalog_check(e, n_req, cand_field, cand_first, n_cand);
+  if (rc) return rc;
+  if (n_req == 0 || n_cand == 0) return FFM_OK;
+  // ---- on the caller's thread, before anything is queued
+  if (!ctx_ptr || !out) return fail(FFM_E_INVALID, "null array");
+  if ((rc = cand_check_ptr(ctx_ptr, n_req, "ctx_ptr"))) return rc;
+  const int32_t ctx_nnz = ctx_ptr[n_req];
+  if (ctx_nnz > 0 && (!ctx_field || !ctx_feat)) return fail(FFM_E_INVALID, "null field / feat array");
+  int longest = 1;  // (a context beyond max_row_nnz is the row kernel's to flag: NaN for its request, FFM_E_CAPACITY below)
+  for (int32_t r = 0; r < n_req; r++) longest = std::max(longest, ctx_ptr[r + 1] - ctx_ptr[r]);
+  const size_t n_ptr = static_cast<size_t>(n_req) + 1, n_ctx = std::max<size_t>(1, static_cast<size_t>(ctx_nnz));
+  const size_t n_out = static_cast<size_t>(n_req) * n_cand;
+  if ((rc = e->grow(&e->d_ctx_ptr, &e->ctx_ptr_cap, n_ptr))) return rc;
+  if ((rc = e->grow(&e->d_ctx_field, &e->ctx_field_cap, n_ctx))) return rc;
+  if ((rc = e->grow(&e->d_ctx_feat, &e->ctx_feat_cap, n_ctx))) return rc;
+  if ((rc = e->grow(&e->d_ctx_val, &e->ctx_val_cap, n_ctx))) return rc;
+  if ((rc = e->grow(&e->cat_out, &e->cat_out_cap, n_out))) return rc;
+  // ---- copies, the values nobody sent, hashed ids: behind one another on the engine's stream, as score_candidates
+  hipStream_t st = e->stream;
+  HIP_TRY(hipMemcpyAsync(e->d_ctx_ptr, ctx_ptr, sizeof(int32_t) * n_ptr, hipMemcpyHostToDevice, st));
+  if (ctx_nnz > 0) {
+    HIP_TRY(hipMemcpyAsync(e->d_ctx_field, ctx_field, sizeof(int32_t) * ctx_nnz, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_ctx_feat, ctx_feat, sizeof(int32_t) * ctx_nnz, hipMemcpyHostToDevice, st));
+    if (ctx_val) HIP_TRY(hipMemcpyAsync(e->d_ctx_val, ctx_val, sizeof(float) * ctx_nnz, hipMemcpyHostToDevice, st));
+    else
+      hipLaunchKernelGGL(fill_ones_kernel, dim3(std::max(1, std::min(256, cdiv(cdiv(ctx_nnz, 4), 256)))), dim3(256), 0, st,
+                         e->d_ctx_val, static_cast<unsigned>(ctx_nnz));
+    if (e->hash_ids) launch_hash_ids(e, st, ctx_nnz, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_feat, e->d_ctx_val);
+  }
+  const int cap = std::min(longest, e->max_row_nnz);
+  rc = catalog_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, cand_field, cand_first, n_cand,
+                      cand_val, output_prob, e->cat_out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, e->cat_out, sizeof(float) * n_out, hipMemcpyDeviceToHost, st));
+  return check_device_errors(e);
+}

@@ -154,6 +154,21 @@ inline ServeCandidateFn serve_candidate_fn(int fmt, int n_factors) {
     default: return nullptr;
   }
 }
+// a catalogue (kernels_catalog.h): U per request, then <format, request tiles of 32 per launch>
+using CatalogUFn = void (*)(ModelDev, int, const int *, const int *, const int *, const float *, int, CatalogDev, int, int);
+using CatalogGemmFn = void (*)(const char *, const float *, int, CatalogDev, int, int, int64_t, float, int, float *);
+inline CatalogUFn catalog_u_fn(int fmt) {
+  return fmt == SERVE_F16 ? catalog_u_kernel<SERVE_F16> : fmt == SERVE_F32 ? catalog_u_kernel<SERVE_F32> : nullptr;
+}
+// tiles: request tiles of the launch; the smallest RT that covers them (1, 2 or 4)
+inline int catalog_rt(int tiles) { return tiles <= 1 ? 1 : tiles <= 2 ? 2 : 4; }
+template <int FMT>
+CatalogGemmFn catalog_gemm_rt(int rt) {
+  return rt == 1 ? catalog_gemm_kernel<FMT, 1> : rt == 2 ? catalog_gemm_kernel<FMT, 2> : rt == 4 ? catalog_gemm_kernel<FMT, 4> : nullptr;
+}
+inline CatalogGemmFn catalog_gemm_fn(int fmt, int rt) {
+  return fmt == SERVE_F16 ? catalog_gemm_rt<SERVE_F16>(rt) : fmt == SERVE_F32 ? catalog_gemm_rt<SERVE_F32>(rt) : nullptr;
+}
 // field ablation (kernels_ablate.h)
 using AblateWaveFn = void (*)(ModelDev, Rows, int *, int, int, float *, double *, int, int);
 inline AblateWaveFn ablate_wave_fn(int fmt, int n_factors) {

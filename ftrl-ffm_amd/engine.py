@@ -237,6 +237,13 @@ ABI = [
     ("ffm_engine_score_candidates_device", ctypes.c_int,
      [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp,
       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp]),
+    # request contexts against a whole id range of one field (include/ffm_engine.h "Scoring a catalogue")
+    ("ffm_engine_score_catalog", ctypes.c_int,
+     [_vp, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+      ctypes.c_int32, _f32p]),
+    ("ffm_engine_score_catalog_device", ctypes.c_int,
+     [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp]),
     # the fields' cardinalities counted on the device, id ranges sized by them (include/ffm_engine.h "Field sketches")
     ("ffm_engine_sketch_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("ffm_engine_sketch_add", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32]),
@@ -946,6 +953,33 @@ def spell_out_candidates(ctx, cand_req_ptr, cand):
                  merged(ctx.val, cand.val, np.float32), np.zeros(n_cand, np.int32))
 
 
+def score_catalog_reference(weights, ctx, field, first, count, val=1.0, n_fields=None):
+    """Engine.score_catalog's definition (include/ffm_engine.h "Scoring a catalogue") in float64, on the weights
+    get_weights() returns; numpy only.  Returns (dot64, scale), both [n_req, count]:
+    dot64 = v lin_w[c] + v sum_j U_r[j] W[c][j] and scale = |v lin_w[c]| + |v| max_j |U_r[j]| sum_j |W[c][j]|, with
+    U_r[f * k + t] the sum over the context's surviving entries i of field f of val_i * w[id_i][field * k + t] and
+    W[c] the whole row of candidate c = first + column.  The score is base_r + dot64, base_r being
+    predict_batch(ctx).  n_fields: the model's (get_weights() does not carry it); k = row length / n_fields."""
+    lin = np.asarray(weights["lin_w"], np.float64)
+    n_feats = lin.shape[0]
+    W = np.asarray(weights["vec_w"], np.float64).reshape(n_feats, -1)
+    L = W.shape[1]
+    if n_fields is None or n_fields <= 0 or L % n_fields:
+        raise ValueError("n_fields must divide the table's row length %d" % L)
+    k, g, v = L // n_fields, int(field), float(val)
+    U = np.zeros((ctx.n_rows, L))
+    cval = np.ones(len(ctx.feat), np.float64) if ctx.val is None else np.asarray(ctx.val, np.float64)
+    for r in range(ctx.n_rows):
+        for p in range(int(ctx.row_ptr[r]), int(ctx.row_ptr[r + 1])):
+            f, i = int(ctx.field[p]), int(ctx.feat[p])
+            if 0 <= i < n_feats and 0 <= f < n_fields:
+                U[r, f * k:(f + 1) * k] += cval[p] * W[i, g * k:(g + 1) * k]
+    Wc, lc = W[first:first + count], lin[first:first + count]
+    dot64 = v * lc[None, :] + v * (U @ Wc.T)
+    scale = np.abs(v * lc)[None, :] + abs(v) * np.abs(U).max(axis=1, initial=0.0)[:, None] * np.abs(Wc).sum(axis=1)[None, :]
+    return dot64, scale
+
+
 def load_library(path=None):
     """dlopen libffm_engine.so and bind every ABI symbol.  Raises if it is missing."""
     global _lib
@@ -1477,6 +1511,25 @@ class Engine:
         self._check(self.lib.ffm_engine_score_candidates(self.h, ctx.n_rows, cp, cfld, cft, cv, _i(rq), n_cand, kp, kfld,
                                                          kft, kv, int(output_prob), _f(out)))
         return out[:cand.n_rows]
+
+    def score_catalog(self, ctx, field, first, count, val=1.0, output_prob=False):
+        """Every request of ctx (one row each) against the candidates (field, c, val), c in [first, first + count):
+        float32[n_req, count] (include/ffm_engine.h "Scoring a catalogue"; score_catalog_reference is the
+        definition).  Matrix instructions over the table's slab; within the header's bound of base + dot64, not
+        bit for bit.  val == 0 gives predict_batch(ctx) in every column."""
+        out = np.zeros((ctx.n_rows, max(int(count), 0)), np.float32)
+        _, cp, cfld, cft, cv, _ = self._csr(ctx)
+        self._check(self.lib.ffm_engine_score_catalog(self.h, ctx.n_rows, cp, cfld, cft, cv, int(field), int(first), int(count),
+                                                      float(val), int(output_prob), _f(out)))
+        return out
+
+    def score_catalog_device(self, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, field, first, count, val, ctx_nnz, ctx_cap,
+                             output_prob, out):
+        """score_catalog on arrays already in HBM (device addresses), out[n_req][count] there too; ctx_cap: the
+        longest context of the call.  Asynchronous on the engine's stream; sync() reports a too-long context."""
+        self._check(self.lib.ffm_engine_score_catalog_device(
+            self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, int(field), int(first), int(count), float(val),
+            int(ctx_nnz), int(ctx_cap), int(output_prob), out))
 
     # ---- blocks already in HBM (raw device addresses as ints) ----
     def score_candidates_device(self, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, cand_req_ptr, n_cand, cand_ptr,

@@ -1091,6 +1091,49 @@ int ffm_engine_score_candidates_device(ffm_engine *e, int32_t n_req, const int32
                                        const int32_t *cand_feat, const float *cand_val, int32_t ctx_nnz,
                                        int32_t cand_nnz, int32_t ctx_cap, int32_t output_prob, float *out);
 
+/* ---- Scoring a catalogue: request contexts against a whole id range of one field ------------------------
+ * The retrieval question: for these requests, score every id of field g, or every id of a range.  A candidate is
+ * the single entry (g, c, v) with c in [cand_first, cand_first + n_cand) -- model ids, a contiguous slab of the
+ * table -- and its score against the context of request r is
+ *   score(r, c) = base_r + v * lin_w[c] + v * sum_{j < L} U_r[j] * W[c][j]          L = n_fields * n_factors
+ *   W[c]    candidate c's whole serving-table row;
+ *   U_r[f * k + t] = the sum over the context's entries i of field f, in entry order, of fl(val_i * w[id_i][g * k + t]);
+ *   base_r  what ffm_engine_predict_batch gives the context row alone (bias, linear terms, context x context pairs):
+ *           the same bits, from the same kernel.
+ * A context entry of field g itself lands in U_r's block g: the diagonal needs no special case.  The pair sum of
+ * all requests and candidates is one dense product out[R][C] = U[R][L] * W[C][L]^T, computed by matrix instructions
+ * (csrc/kernels_catalog.h) while the slab streams through once per 128 requests.
+ * CONTRACT  Not bit for bit against the spelled-out rows: the sum over j runs in the matrix unit's order.  For
+ *   finite tables
+ *     |score - (base_r + dot64)| <= (L + 32) * 2^-24 * (|base_r| + scale)
+ *   with dot64 = v lin_w[c] + v sum_j U_r[j] W[c][j] in float64 and scale = |v lin_w[c]| + |v| max_j |U_r[j]| sum_j |W[c][j]|
+ *   (score_catalog_reference of the Python binding computes both).  cand_val == 0 gives base_r by value; output_prob
+ *   applies the engine's sigmoid to the logit.
+ * CONTEXTS are treated as ffm_engine_score_candidates treats them: an entry with an id outside [0, n_feats) or a field
+ *   outside [0, n_fields) is erased; a context without survivors scores as the bias; ctx_val == NULL (host call) is
+ *   ones; an engine with FFM_FLAG_HASH_IDS hashes, folds and buckets the host call's ids on the device behind their
+ *   copy.  A context longer than max_row_nnz (device call: or than ctx_cap) is flagged: NaN for every candidate of
+ *   its request alone, FFM_E_CAPACITY from the host call or the next ffm_engine_sync.
+ * ffm_engine_score_catalog: arrays in host memory, out[n_req][n_cand] request-major in host memory; synchronous.
+ * ffm_engine_score_catalog_device: the same on device addresses (values required, ids taken as they are), ctx_nnz
+ *   entries in all, ctx_cap the longest context; asynchronous on the engine's stream.
+ * Both: FFM_E_INVALID for cand_field outside [0, n_fields), a range outside [0, n_feats], a negative count or a null
+ *   array; FFM_E_CAPACITY for n_req > max_batch_rows or n_req * n_cand > 2^31 - 1 (out is indexed in 64 bits);
+ *   n_req == 0 or n_cand == 0 is FFM_OK with nothing written.  REFUSED by name, before anything is queued or written:
+ *   a training engine, FFM_FLAG_SERVE_F8 and a pruned table (FFM_E_UNSUPPORTED), an engine with a pair mask set or
+ *   with FFM_FLAG_NORM_ROWS (FFM_E_INVALID), a group's or a shard's engine (FFM_E_UNSUPPORTED).  The buffers (base, U,
+ *   the host call's output) are allocated by the first call, grown to the largest call seen and freed by
+ *   ffm_engine_destroy; an engine that never calls this allocates and launches nothing new.  The profile calls label
+ *   the kernels "catalog_u_kernel" and "catalog_gemm_kernel".  FFM_ENGINE_ABI_VERSION is what it was.
+ * OUT OF SCOPE  a top-K epilogue and the CLI (follow-ups); candidates of more than one entry; LR and FM. */
+int ffm_engine_score_catalog(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                             const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
+                             int32_t n_cand, float cand_val, int32_t output_prob, float *out);
+int ffm_engine_score_catalog_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                    const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
+                                    int32_t n_cand, float cand_val, int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob,
+                                    float *out);
+
 /* ---- Field ablation: the loss and AUC of the model without each field, in one pass -------------------
  * Which fields earn their place?  The standard answer is the evaluation loss and AUC of the same model with
  * field f removed from every row -- n_fields more passes over rewritten copies of the evaluation data.  The

@@ -15,6 +15,12 @@
                                               ffm_engine_score_candidates[_device] against the same data spelled out
                                               as rows through ffm_engine_predict_batch[_device], same engine, same
                                               process, alternating windows
+  python tools/serve_bench.py --catalog --kind f16
+                                              request contexts against a whole id range (include/ffm_engine.h "Scoring
+                                              a catalogue"; profiles/score_catalog.md): ffm_engine_score_catalog_device
+                                              for 32 and 128 requests x 65536 and 1048576 candidates, against the rate
+                                              of ffm_engine_predict_batch_device on the same scores spelled out as rows,
+                                              same engine, same process
 
 Shape: the headline one -- 39 fields x 16 factors, 33 M features --, Zipf blocks of 8192 rows from synth.py,
 resident in HBM, through ffm_engine_predict_batch_device with labels (logits + logloss sum, as the evaluation
@@ -115,6 +121,82 @@ def run_kind(args):
                out_checksum=checksum, profile=dump.strip().splitlines())
     eng.close()
     print("SERVE_BENCH " + json.dumps(res), flush=True)
+
+
+def run_catalog(args):
+    """One JSON line per (requests, candidates): median and spread of score_catalog_device's time, candidate-scores
+    per second, bytes per second of the slab (n_cand rows of the table per pass of 128 requests); and the same
+    engine's predict_batch_device on blocks of spelled-out rows [context..., (g, c, 1)], whose rate gives the time
+    the same scores take as rows (measured on --blocks blocks of 8192 such rows, not on all of them)."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("serve_bench needs a GPU: none found")
+    import ftrl_ffm_amd as fa
+    from ftrl_ffm_amd import synth
+    fa.build()
+    nf = min(args.n_feats, 4_000_000)
+    nf -= nf % N_FIELDS
+    g, first, cf = N_FIELDS - 1, 1000, N_FIELDS - 1  # contexts: one entry in each of the other 38 fields
+    eng = fa.Engine("FFM", nf, N_FIELDS, N_FACTORS, max_batch_rows=ROWS, max_batch_nnz=ROWS * N_FIELDS, seed=42,
+                    max_row_nnz=N_FIELDS, serve=args.kind)
+    elem = 2 if args.kind == "f16" else 4
+    blk = synth.Generator(N_FIELDS, nf, dist="zipf", seed=42).block(128)
+    keep = blk.field != g
+    ctx = synth.Block(np.arange(129, dtype=np.int32) * cf, blk.field[keep], blk.feat[keep], blk.val[keep], np.zeros(128, np.int32))
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    d = [up(ctx.row_ptr), up(ctx.field), up(ctx.feat), up(ctx.val)]
+    out = torch.zeros(128 * (1 << 20), dtype=torch.float32, device="cuda")
+
+    def windows(call, repeats=args.repeats, window=args.window):
+        for _ in range(3):
+            call()
+        eng.sync()
+        t0 = time.perf_counter()
+        call()
+        eng.sync()
+        n = max(4, int(window / max(time.perf_counter() - t0, 1e-6)) + 1)
+        us = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                call()
+            eng.sync()
+            us.append(1e6 * (time.perf_counter() - t0) / n)
+        return sorted(us)
+
+    # the baseline: spelled-out rows of request r against candidates first + j, blocks of 8192 rows, cycled
+    rows = []
+    for b in range(args.blocks):
+        cand = synth.Block(np.arange(ROWS + 1, dtype=np.int32), np.full(ROWS, g, np.int32),
+                           (first + b * ROWS + np.arange(ROWS)).astype(np.int32), np.ones(ROWS, np.float32), np.zeros(ROWS, np.int32))
+        one = synth.Block(ctx.row_ptr[b % 128:b % 128 + 2] - ctx.row_ptr[b % 128], *[a[(b % 128) * cf:(b % 128 + 1) * cf] for a in (ctx.field, ctx.feat, ctx.val)], np.zeros(1, np.int32))
+        s = fa.spell_out_candidates(one, np.array([0, ROWS], np.int32), cand)
+        rows.append((int(s.row_ptr[-1]), [up(a) for a in (s.row_ptr, s.field, s.feat, s.val)]))
+    turn = [0]
+
+    def spelled():
+        nnz, a = rows[turn[0] % len(rows)]
+        turn[0] += 1
+        eng.predict_batch_device(ROWS, nnz, a[0].data_ptr(), a[1].data_ptr(), a[2].data_ptr(), a[3].data_ptr(), None, 0, out.data_ptr(), None)
+    base_us = windows(spelled)
+    base_rate = ROWS / (base_us[len(base_us) // 2] * 1e-6)
+    for n_req in (32, 128):
+        for n_cand in (65536, 1 << 20):
+            us = windows(lambda: eng.score_catalog_device(n_req, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), g, first,
+                                                          n_cand, 1.0, n_req * cf, cf, 0, out.data_ptr()))
+            med = us[len(us) // 2]
+            slab = n_cand * N_FIELDS * N_FACTORS * elem
+            print("SERVE_BENCH " + json.dumps(dict(
+                catalog=True, kind=args.kind, n_req=n_req, n_cand=n_cand, us_median=round(med, 1), us_min=round(us[0], 1),
+                us_max=round(us[-1], 1), scores_per_s=n_req * n_cand / (med * 1e-6), slab_bytes=slab,
+                slab_bytes_per_s=slab * ((n_req + 127) // 128) / (med * 1e-6), share_of_hbm_peak=slab / (med * 1e-6) / HBM_PEAK,
+                rows_baseline_us_per_8192=[round(x, 1) for x in base_us], rows_baseline_scores_per_s=base_rate,
+                rows_baseline_us_for_the_same_scores=round(n_req * n_cand / base_rate * 1e6, 1),
+                speedup=n_req * n_cand / base_rate * 1e6 / med, checksum=float(out[:n_req * n_cand:4099].double().sum().cpu()))), flush=True)
+    eng.close()
 
 
 def candidate_bytes(kind, cf, kf, per, k=N_FACTORS):
@@ -371,7 +453,13 @@ def main():
     ap.add_argument("--out", help="also write the results there as JSON")
     ap.add_argument("--pruned", action="store_true",
                     help="pruned serving tables against the masked unpruned engine, --kind f32 or f16 (default f16)")
+    ap.add_argument("--catalog", action="store_true",
+                    help="request contexts against a whole id range (include/ffm_engine.h \"Scoring a catalogue\"), --kind f32 or f16")
     args = ap.parse_args()
+    if args.catalog:
+        if args.kind not in ("f32", "f16"):
+            raise SystemExit("--catalog needs --kind f32 or f16")
+        return run_catalog(args)
     if args.pruned:
         if args.kind in ("training", "f8"):
             raise SystemExit("--pruned needs a format with a pruned layout (f32 or f16)")
