@@ -52,6 +52,7 @@
 #include "kernels_serve.h"
 #include "kernels_serve8.h"
 #include "kernels_catalog.h"
+#include "kernels_catalog_topk.h"
 #include "kernels_delta.h"
 #include "kernels_ablate.h"
 #include "kernels_ablate_pairs.h"
@@ -129,7 +130,7 @@ enum KernelId {
   K_GROUP_KEYS, K_GROUP_SORT, K_GROUP_FINISH, K_ROW, K_TMP_GRAD,
   K_LOSS_SUM, K_LINEAR_UPDATE, K_BIAS_UPDATE, K_LATENT_UPDATE, K_LATENT_UPDATE_FEW, K_LATENT_UPDATE_WALK, K_LATENT_UPDATE_GIANT,
   K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC, K_PUSH_SCORES, K_SERVE_ROW,
-  K_SERVE_CTX, K_SERVE_CAND, K_CATALOG_U, K_CATALOG_GEMM,
+  K_SERVE_CTX, K_SERVE_CAND, K_CATALOG_U, K_CATALOG_GEMM, K_CATALOG_TOPK, K_CATALOG_TOPK_MERGE,
   K_KEYED_CAPTURE, K_KEYED_SORT_HIST, K_KEYED_SORT_SCAN, K_KEYED_SORT_SCATTER, K_KEYED_RANK,
   K_UPLOAD, K_NORM_ROWS,
   K_COUNT
@@ -139,6 +140,7 @@ const char *kKernelNames[K_COUNT] = {
     "linear_update_kernel", "bias_update_kernel", "update_kernel", "update_few_kernel", "update_walk_kernel", "update_giant_kernel",
     "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel", "push_scores_kernel", "serve_wave_kernel",
     "serve_context_kernel", "serve_candidate_kernel", "catalog_u_kernel", "catalog_gemm_kernel",
+    "catalog_topk_kernel", "catalog_topk_merge_kernel",
     "keyed_capture_kernel", "keyed_sort_hist_kernel", "keyed_sort_scan_kernels", "keyed_sort_scatter_kernel", "keyed_rank_kernels",
     "pull_block_kernel", "normalize_rows_kernel"};
 
@@ -456,6 +458,14 @@ struct ffm_engine {
   char *cat_u = nullptr;
   float *cat_out = nullptr;
   size_t cat_base_cap = 0, cat_shift_cap = 0, cat_u_cap = 0, cat_out_cap = 0;
+  // ffm_engine_score_catalog_topk[_device] (include/ffm_engine.h "Scoring a catalogue: the best K"): the waves' partial
+  // lists [n_req][grid * 4][Kp] and the host call's two outputs [n_req][top_k], made and grown like the arrays above.
+  // grid_catalog: the workgroups of catalog_topk_kernel at the most (FFM_GRID_CATALOG; 0: two per CU)
+  unsigned long long *topk_part = nullptr;
+  float *topk_score = nullptr;
+  int *topk_id = nullptr;
+  size_t topk_part_cap = 0, topk_score_cap = 0, topk_id_cap = 0;
+  int grid_catalog = 0, cu_count = 0;
   // field and pair ablation (include/ffm_engine.h "Field ablation", "Pair ablation"; engine_ablate.h), each set all
   // made by its enable call for its V variants -- n_fields + 1, or n_fields (n_fields + 1) / 2 + 1 --: out [V][max_rows]
   // scores and loss the same shape (the kernel's variant-major outputs), sums [V], part [V][kLossParts + 1] the loss

@@ -1,6 +1,7 @@
 // engine_catalog.h -- request contexts against a whole id range of one field (include/ffm_engine.h "Scoring a
-// catalogue"; kernels_catalog.h): what the two entry points check, the buffers they grow, and the three launches --
-// the engine's own row kernel over the contexts (base), catalog_u_kernel, catalog_gemm_kernel per 128 requests.
+// catalogue" and "... the best K"; kernels_catalog.h, kernels_catalog_topk.h): what the entry points check, the buffers
+// they grow, and the launches -- the engine's own row kernel over the contexts (base), catalog_u_kernel, then either
+// catalog_gemm_kernel per 128 requests or catalog_topk_kernel per 32 RT requests and catalog_topk_merge_kernel.
 // Part of engine.hip's translation unit (included inside its extern "C" block).
 
 static int catalog_check(ffm_engine *e, int32_t n_req, int32_t cand_field, int32_t cand_first, int32_t n_cand) {
@@ -22,8 +23,16 @@ static int catalog_check(ffm_engine *e, int32_t n_req, int32_t cand_field, int32
   if (cand_first < 0 || static_cast<int64_t>(cand_first) + n_cand > e->m.n_feats)
     return fail(FFM_E_INVALID, "the candidate range [cand_first, cand_first + n_cand) lies outside [0, n_feats]");
   if (n_req > e->max_rows) return fail(FFM_E_CAPACITY, "more requests than max_batch_rows");
+  return FFM_OK;
+}
+// ... and of the two calls that write the whole matrix
+static int catalog_matrix_check(int32_t n_req, int32_t n_cand) {
   if (static_cast<int64_t>(n_req) * n_cand > 2147483647ll)
     return fail(FFM_E_CAPACITY, "n_req * n_cand exceeds 2^31 - 1 scores: split the range");
+  return FFM_OK;
+}
+// Behind the checks, before anything is queued.
+static int catalog_ready(ffm_engine *e) {
   HIP_TRY(hipSetDevice(e->cfg.device_id));
   return eval_launch_pending(e);
 }
@@ -34,13 +43,12 @@ static int catalog_rows(int n_req) {
   return n_req - rest + (rest ? kCatTile * catalog_rt(cdiv(rest, kCatTile)) : 0);
 }
 
-// The launches, on arrays in device memory.  cap: the longest context, in [1, max_row_nnz].
-static int catalog_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
-                          const float *ctx_val, int32_t ctx_nnz, int cap, int32_t g, int32_t first, int32_t n_cand, float v,
-                          int32_t output_prob, float *out) {
+// What both kinds of launches start with, on arrays in device memory: base and U of the requests, padded to `rows`
+// (whole tiles of the launches that follow).  cap: the longest context, in [1, max_row_nnz].
+static int catalog_prepare(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                           const float *ctx_val, int32_t ctx_nnz, int cap, int32_t g, int rows, CatalogDev *out_cd) {
   const ModelDev &m = e->m;
-  const int L = m.row_len, es = m.lat_fmt == SERVE_F16 ? 2 : 4;
-  const int rows = catalog_rows(n_req), lp = catalog_lp(m.lat_fmt, L);
+  const int lp = catalog_lp(m.lat_fmt, m.row_len);
   int rc;
   if ((rc = e->grow(&e->cat.base, &e->cat_base_cap, static_cast<size_t>(rows)))) return rc;
   if ((rc = e->grow(&e->cat.shift, &e->cat_shift_cap, static_cast<size_t>(rows)))) return rc;
@@ -54,6 +62,17 @@ static int catalog_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, 
   const int lds_cap = std::min(cap, kPredLdsCap);
   LAUNCH(e, K_CATALOG_U, catalog_u_fn(m.lat_fmt), cdiv(rows, kPredRows), 64 * kPredRows, cand_ctx_lds_bytes(lds_cap), m, n_req, ctx_ptr,
          ctx_field, ctx_feat, ctx_val, g, cd, cap, lds_cap);
+  *out_cd = cd;
+  return FFM_OK;
+}
+
+static int catalog_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                          const float *ctx_val, int32_t ctx_nnz, int cap, int32_t g, int32_t first, int32_t n_cand, float v,
+                          int32_t output_prob, float *out) {
+  const ModelDev &m = e->m;
+  const int L = m.row_len, es = m.lat_fmt == SERVE_F16 ? 2 : 4;
+  CatalogDev cd;
+  if (int rc = catalog_prepare(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, g, catalog_rows(n_req), &cd)) return rc;
   const char *const tab = reinterpret_cast<const char *>(m.lat) + static_cast<int64_t>(first) * L * es;
   const int grid = static_cast<int>((static_cast<int64_t>(n_cand) + kCatCands - 1) / kCatCands);
   for (int r0 = 0; r0 < n_req; r0 += 128) {
@@ -65,11 +84,46 @@ static int catalog_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, 
   return FFM_OK;
 }
 
+// The host calls' contexts into the engine's staging arrays (d_ctx_*), checked on the caller's thread before anything
+// is queued.  *ctx_nnz: their entries; *cap: the longest context, at most max_row_nnz.
+static int catalog_stage_contexts(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                                  const float *ctx_val, int32_t *out_nnz, int *out_cap) {
+  int rc;
+  if (!ctx_ptr) return fail(FFM_E_INVALID, "null array");
+  if ((rc = cand_check_ptr(ctx_ptr, n_req, "ctx_ptr"))) return rc;
+  const int32_t ctx_nnz = ctx_ptr[n_req];
+  if (ctx_nnz > 0 && (!ctx_field || !ctx_feat)) return fail(FFM_E_INVALID, "null field / feat array");
+  int longest = 1;  // (a context beyond max_row_nnz is the row kernel's to flag: NaN for its request, FFM_E_CAPACITY from the call)
+  for (int32_t r = 0; r < n_req; r++) longest = std::max(longest, ctx_ptr[r + 1] - ctx_ptr[r]);
+  const size_t n_ptr = static_cast<size_t>(n_req) + 1, n_ctx = std::max<size_t>(1, static_cast<size_t>(ctx_nnz));
+  if ((rc = e->grow(&e->d_ctx_ptr, &e->ctx_ptr_cap, n_ptr))) return rc;
+  if ((rc = e->grow(&e->d_ctx_field, &e->ctx_field_cap, n_ctx))) return rc;
+  if ((rc = e->grow(&e->d_ctx_feat, &e->ctx_feat_cap, n_ctx))) return rc;
+  if ((rc = e->grow(&e->d_ctx_val, &e->ctx_val_cap, n_ctx))) return rc;
+  // ---- copies, the values nobody sent, hashed ids: behind one another on the engine's stream, as score_candidates
+  hipStream_t st = e->stream;
+  HIP_TRY(hipMemcpyAsync(e->d_ctx_ptr, ctx_ptr, sizeof(int32_t) * n_ptr, hipMemcpyHostToDevice, st));
+  if (ctx_nnz > 0) {
+    HIP_TRY(hipMemcpyAsync(e->d_ctx_field, ctx_field, sizeof(int32_t) * ctx_nnz, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_ctx_feat, ctx_feat, sizeof(int32_t) * ctx_nnz, hipMemcpyHostToDevice, st));
+    if (ctx_val) HIP_TRY(hipMemcpyAsync(e->d_ctx_val, ctx_val, sizeof(float) * ctx_nnz, hipMemcpyHostToDevice, st));
+    else
+      hipLaunchKernelGGL(fill_ones_kernel, dim3(std::max(1, std::min(256, cdiv(cdiv(ctx_nnz, 4), 256)))), dim3(256), 0, st,
+                         e->d_ctx_val, static_cast<unsigned>(ctx_nnz));
+    if (e->hash_ids) launch_hash_ids(e, st, ctx_nnz, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_feat, e->d_ctx_val);
+  }
+  *out_nnz = ctx_nnz;
+  *out_cap = std::min(longest, e->max_row_nnz);
+  return FFM_OK;
+}
+
 int ffm_engine_score_catalog_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
                                     const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
                                     int32_t n_cand, float cand_val, int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob,
                                     float *out) {
   if (int rc = catalog_check(e, n_req, cand_field, cand_first, n_cand)) return rc;
+  if (int rc = catalog_matrix_check(n_req, n_cand)) return rc;
+  if (int rc = catalog_ready(e)) return rc;
   if (n_req == 0 || n_cand == 0) return FFM_OK;
   if (ctx_nnz < 0 || ctx_cap < 0) return fail(FFM_E_INVALID, "negative ctx_nnz / ctx_cap");
   if (!ctx_ptr || !out || (ctx_nnz > 0 && (!ctx_field || !ctx_feat || !ctx_val))) return fail(FFM_E_INVALID, "null array");
@@ -83,38 +137,101 @@ int ffm_engine_score_catalog(ffm_engine *e, int32_t n_req, const int32_t *ctx_pt
                              const float *ctx_val, int32_t cand_field, int32_t cand_first, int32_t n_cand, float cand_val,
                              int32_t output_prob, float *out) {
   int rc = catalog_check(e, n_req, cand_field, cand_first, n_cand);
-  if (rc) return rc;
+  if (rc || (rc = catalog_matrix_check(n_req, n_cand)) || (rc = catalog_ready(e))) return rc;
   if (n_req == 0 || n_cand == 0) return FFM_OK;
-  // ---- on the caller's thread, before anything is queued
-  if (!ctx_ptr || !out) return fail(FFM_E_INVALID, "null array");
-  if ((rc = cand_check_ptr(ctx_ptr, n_req, "ctx_ptr"))) return rc;
-  const int32_t ctx_nnz = ctx_ptr[n_req];
-  if (ctx_nnz > 0 && (!ctx_field || !ctx_feat)) return fail(FFM_E_INVALID, "null field / feat array");
-  int longest = 1;  // (a context beyond max_row_nnz is the row kernel's to flag: NaN for its request, FFM_E_CAPACITY below)
-  for (int32_t r = 0; r < n_req; r++) longest = std::max(longest, ctx_ptr[r + 1] - ctx_ptr[r]);
-  const size_t n_ptr = static_cast<size_t>(n_req) + 1, n_ctx = std::max<size_t>(1, static_cast<size_t>(ctx_nnz));
+  if (!out) return fail(FFM_E_INVALID, "null array");
   const size_t n_out = static_cast<size_t>(n_req) * n_cand;
-  if ((rc = e->grow(&e->d_ctx_ptr, &e->ctx_ptr_cap, n_ptr))) return rc;
-  if ((rc = e->grow(&e->d_ctx_field, &e->ctx_field_cap, n_ctx))) return rc;
-  if ((rc = e->grow(&e->d_ctx_feat, &e->ctx_feat_cap, n_ctx))) return rc;
-  if ((rc = e->grow(&e->d_ctx_val, &e->ctx_val_cap, n_ctx))) return rc;
-  if ((rc = e->grow(&e->cat_out, &e->cat_out_cap, n_out))) return rc;
-  // ---- copies, the values nobody sent, hashed ids: behind one another on the engine's stream, as score_candidates
-  hipStream_t st = e->stream;
-  HIP_TRY(hipMemcpyAsync(e->d_ctx_ptr, ctx_ptr, sizeof(int32_t) * n_ptr, hipMemcpyHostToDevice, st));
-  if (ctx_nnz > 0) {
-    HIP_TRY(hipMemcpyAsync(e->d_ctx_field, ctx_field, sizeof(int32_t) * ctx_nnz, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(e->d_ctx_feat, ctx_feat, sizeof(int32_t) * ctx_nnz, hipMemcpyHostToDevice, st));
-    if (ctx_val) HIP_TRY(hipMemcpyAsync(e->d_ctx_val, ctx_val, sizeof(float) * ctx_nnz, hipMemcpyHostToDevice, st));
-    else
-      hipLaunchKernelGGL(fill_ones_kernel, dim3(std::max(1, std::min(256, cdiv(cdiv(ctx_nnz, 4), 256)))), dim3(256), 0, st,
-                         e->d_ctx_val, static_cast<unsigned>(ctx_nnz));
-    if (e->hash_ids) launch_hash_ids(e, st, ctx_nnz, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_feat, e->d_ctx_val);
-  }
-  const int cap = std::min(longest, e->max_row_nnz);
+  int32_t ctx_nnz = 0;
+  int cap = 1;
+  if ((rc = e->grow(&e->cat_out, &e->cat_out_cap, n_out))) return rc;  // (before anything is queued)
+  if ((rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap))) return rc;
   rc = catalog_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, cand_field, cand_first, n_cand,
                       cand_val, output_prob, e->cat_out);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, e->cat_out, sizeof(float) * n_out, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(out, e->cat_out, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
+  return check_device_errors(e);
+}
+
+// ---- the best K (include/ffm_engine.h "Scoring a catalogue: the best K") -------------------------------------------
+
+static int catalog_topk_check(ffm_engine *e, int32_t n_req, int32_t cand_field, int32_t cand_first, int32_t n_cand, int32_t top_k) {
+  if (int rc = catalog_check(e, n_req, cand_field, cand_first, n_cand)) return rc;
+  if (top_k < 1 || top_k > kTopkMax)
+    return fail(FFM_E_INVALID, "top_k " + std::to_string(top_k) + " lies outside [1, " + std::to_string(kTopkMax) + "]");
+  return catalog_ready(e);
+}
+
+// Request tiles of the launch that starts at request r0: what top_k allows, no more than are left.
+static int catalog_topk_tiles(int n_req, int r0, int top_k) {
+  return std::min(catalog_topk_rt(top_k), catalog_rt(cdiv(n_req - r0, kCatTile)));
+}
+
+// The launches, on arrays in device memory; out_score / out_id [n_req][top_k] there too.  n_req > 0.
+static int catalog_topk_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                               const float *ctx_val, int32_t ctx_nnz, int cap, int32_t g, int32_t first, int32_t n_cand, float v,
+                               int32_t top_k, int32_t output_prob, float *out_score, int32_t *out_id) {
+  const ModelDev &m = e->m;
+  const int kp = catalog_topk_kp(top_k);
+  if (n_cand == 0) {  // nothing to rank: the fill alone
+    LAUNCH(e, K_CATALOG_TOPK_MERGE, catalog_topk_merge_kernel, n_req, kTopkMergeThreads, 0, static_cast<const unsigned long long *>(nullptr),
+           static_cast<int64_t>(0), kp, top_k, static_cast<const float *>(nullptr), first, output_prob, out_score, out_id);
+    HIP_TRY(hipGetLastError());
+    return FFM_OK;
+  }
+  const int L = m.row_len, es = m.lat_fmt == SERVE_F16 ? 2 : 4;
+  int rows = 0;
+  while (rows < n_req) rows += kCatTile * catalog_topk_tiles(n_req, rows, top_k);
+  const int64_t slabs = (static_cast<int64_t>(n_cand) + kCatCands - 1) / kCatCands;
+  const int grid = static_cast<int>(std::min<int64_t>(slabs, e->grid_catalog > 0 ? e->grid_catalog : 2 * e->cu_count));
+  const int64_t P = static_cast<int64_t>(grid) * kCatWaves;
+  int rc;
+  if ((rc = e->grow(&e->topk_part, &e->topk_part_cap, static_cast<size_t>(n_req) * P * kp))) return rc;
+  CatalogDev cd;
+  if ((rc = catalog_prepare(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, g, rows, &cd))) return rc;
+  const char *const tab = reinterpret_cast<const char *>(m.lat) + static_cast<int64_t>(first) * L * es;
+  for (int r0 = 0; r0 < n_req;) {
+    const int rt = catalog_topk_tiles(n_req, r0, top_k);
+    LAUNCH(e, K_CATALOG_TOPK, catalog_topk_fn(m.lat_fmt, rt), grid, 64 * kCatWaves, catalog_topk_lds_bytes(rt, kp), tab, m.lin_w + first, L,
+           cd, r0, n_req, static_cast<int64_t>(n_cand), v, top_k, kp, e->topk_part);
+    r0 += kCatTile * rt;
+  }
+  LAUNCH(e, K_CATALOG_TOPK_MERGE, catalog_topk_merge_kernel, n_req, kTopkMergeThreads, 0, static_cast<const unsigned long long *>(e->topk_part),
+         P, kp, top_k, static_cast<const float *>(cd.base), first, output_prob, out_score, out_id);
+  HIP_TRY(hipGetLastError());
+  return FFM_OK;
+}
+
+int ffm_engine_score_catalog_topk_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                         const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
+                                         int32_t n_cand, float cand_val, int32_t top_k, int32_t ctx_nnz, int32_t ctx_cap,
+                                         int32_t output_prob, float *out_score, int32_t *out_id) {
+  if (int rc = catalog_topk_check(e, n_req, cand_field, cand_first, n_cand, top_k)) return rc;
+  if (n_req == 0) return FFM_OK;
+  if (ctx_nnz < 0 || ctx_cap < 0) return fail(FFM_E_INVALID, "negative ctx_nnz / ctx_cap");
+  if (!out_score || !out_id || (n_cand > 0 && (!ctx_ptr || (ctx_nnz > 0 && (!ctx_field || !ctx_feat || !ctx_val)))))
+    return fail(FFM_E_INVALID, "null array");
+  const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
+  return catalog_topk_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, cand_field, cand_first, n_cand, cand_val,
+                             top_k, output_prob, out_score, out_id);
+}
+
+int ffm_engine_score_catalog_topk(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                  const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
+                                  int32_t n_cand, float cand_val, int32_t top_k, int32_t output_prob, float *out_score,
+                                  int32_t *out_id) {
+  int rc = catalog_topk_check(e, n_req, cand_field, cand_first, n_cand, top_k);
+  if (rc) return rc;
+  if (n_req == 0) return FFM_OK;
+  if (!out_score || !out_id) return fail(FFM_E_INVALID, "null array");
+  const size_t n_out = static_cast<size_t>(n_req) * top_k;
+  if ((rc = e->grow(&e->topk_score, &e->topk_score_cap, n_out)) || (rc = e->grow(&e->topk_id, &e->topk_id_cap, n_out))) return rc;
+  int32_t ctx_nnz = 0;
+  int cap = 1;
+  if (n_cand > 0 && (rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap))) return rc;
+  rc = catalog_topk_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, cand_field, cand_first,
+                           n_cand, cand_val, top_k, output_prob, e->topk_score, e->topk_id);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out_score, e->topk_score, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_id, e->topk_id, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, e->stream));
   return check_device_errors(e);
 }

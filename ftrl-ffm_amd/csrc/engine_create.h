@@ -20,7 +20,7 @@ struct Switches {
   int metrics = 0;        // FFM_ENGINE_METRICS=<mask>: channels on from the start (rank 0 of a group keeps them)
   char row_refresh = 0;   // FFM_ENGINE_ROW_REFRESH: its first character ('0' .. '3')
   std::optional<bool> serial, super_wait, prep_after_row, pull_after_row, eval_defer_off, predict_waves, few_stage, own_sort;
-  std::optional<int> update_split, update_order, wide_max_nnz, grid_pull, grid_push, grid_hot, grid_small, grid_walk, grid_giant, grid_norm;
+  std::optional<int> update_split, update_order, wide_max_nnz, grid_pull, grid_push, grid_hot, grid_small, grid_walk, grid_giant, grid_norm, grid_catalog;
   std::optional<int> row_threads, row_park, row_park_budget, row_hold, super_min;
   std::optional<int> range_sort;  // FFM_RANGE_SORT: 0 off, 1 on, more: that many equal ranges
 };
@@ -69,6 +69,7 @@ static Switches read_switches() {
   if (const char *sv = std::getenv("FFM_GRID_SMALL")) sw.grid_small = std::max(1, std::atoi(sv));
   if (const char *sv = std::getenv("FFM_GRID_WALK")) sw.grid_walk = std::max(1, std::atoi(sv));
   if (const char *sv = std::getenv("FFM_GRID_GIANT")) sw.grid_giant = std::max(1, std::atoi(sv));
+  if (const char *sv = std::getenv("FFM_GRID_CATALOG")) sw.grid_catalog = std::max(1, std::atoi(sv));
   if (const char *sv = std::getenv("FFM_ROW_THREADS")) sw.row_threads = std::max(64, std::min(kRowMaxThreads, std::atoi(sv) / 64 * 64));
   if (const char *sv = std::getenv("FFM_ROW_PARK")) sw.row_park = std::atoi(sv);
   if (const char *sv = std::getenv("FFM_ROW_PARK_BUDGET")) sw.row_park_budget = std::atoi(sv);
@@ -135,6 +136,7 @@ static void apply_switches(ffm_engine *e, const Switches &sw) {
   take(e->grid_small, sw.grid_small);
   take(e->grid_walk, sw.grid_walk);
   take(e->grid_giant, sw.grid_giant);
+  take(e->grid_catalog, sw.grid_catalog);
   // (a sharded rank's row holds 1/n_shards of the pairs and facts, walked directly; 64-thread row
   // workgroups measured the same as 256)
   // a shard's row holds ~1/n_shards of the pairs: one wave per row, so that (with the small LDS
@@ -462,6 +464,7 @@ static int choose_sort(ffm_engine *e, const Switches &sw) {
   int per_cu = 0;
   HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, group_sort_kernel, kSortThreads, 0));
   e->sort_grid_cap = std::max(1, per_cu * prop.multiProcessorCount);
+  e->cu_count = std::max(1, prop.multiProcessorCount);
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0 && std::strncmp(prop.gcnArchName, "gfx942", 6) != 0) e->own_sort = false;
   return FFM_OK;
 }
@@ -534,6 +537,9 @@ static int opt_in_lds(ffm_engine *e) {
     for (int kinds = 1; kinds <= UPD_ALL; kinds++)
       for (int waves : {tile_waves(nf), kWideWaves})
         if ((rc = lds_opt_in(update_all_fn(nf, kinds, waves), tile_lds_bytes(nf, waves)))) return rc;
+  // the best K of a catalogue: the lists of the largest top_k a launch of rt request tiles can see
+  for (int rt = 1; rt <= 4; rt *= 2)
+    if ((rc = lds_opt_in(catalog_topk_fn(e->m.lat_fmt, rt), catalog_topk_lds_bytes(rt, catalog_topk_kp(catalog_topk_max_k(rt)))))) return rc;
   return FFM_OK;
 }
 

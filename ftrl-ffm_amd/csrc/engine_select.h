@@ -169,6 +169,20 @@ CatalogGemmFn catalog_gemm_rt(int rt) {
 inline CatalogGemmFn catalog_gemm_fn(int fmt, int rt) {
   return fmt == SERVE_F16 ? catalog_gemm_rt<SERVE_F16>(rt) : fmt == SERVE_F32 ? catalog_gemm_rt<SERVE_F32>(rt) : nullptr;
 }
+// the best K of a catalogue (kernels_catalog_topk.h): <format, request tiles of 32 per launch>.  Request tiles per
+// launch by top_k: the lists of a workgroup (1024 RT Kp bytes, Kp = top_k rounded up to a power of two) stay at or
+// under 32 KB up to K = 32 -- beside the 34 KB of operand tiles that leaves two workgroups per CU -- and are 64 KB at
+// K = 64; more tiles mean fewer passes over the slab, fewer tiles more waves in flight.
+using CatalogTopkFn = void (*)(const char *, const float *, int, CatalogDev, int, int, int64_t, float, int, int, unsigned long long *);
+inline int catalog_topk_rt(int top_k) { return top_k <= 8 ? 4 : top_k <= 16 ? 2 : 1; }
+inline int catalog_topk_max_k(int rt) { return rt == 4 ? 8 : rt == 2 ? 16 : kTopkMax; }  // the largest top_k a launch of rt tiles sees
+template <int FMT>
+CatalogTopkFn catalog_topk_by_rt(int rt) {
+  return rt == 1 ? catalog_topk_kernel<FMT, 1> : rt == 2 ? catalog_topk_kernel<FMT, 2> : rt == 4 ? catalog_topk_kernel<FMT, 4> : nullptr;
+}
+inline CatalogTopkFn catalog_topk_fn(int fmt, int rt) {
+  return fmt == SERVE_F16 ? catalog_topk_by_rt<SERVE_F16>(rt) : fmt == SERVE_F32 ? catalog_topk_by_rt<SERVE_F32>(rt) : nullptr;
+}
 // field ablation (kernels_ablate.h)
 using AblateWaveFn = void (*)(ModelDev, Rows, int *, int, int, float *, double *, int, int);
 inline AblateWaveFn ablate_wave_fn(int fmt, int n_factors) {

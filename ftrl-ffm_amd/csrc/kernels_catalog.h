@@ -168,27 +168,21 @@ __device__ __forceinline__ uint4 catalog_load(const char *tab, int64_t row_bytes
   return v;
 }
 
-// Requests [r0, r0 + 32 RT) (rows of cd, whole tiles; stores for r < n_req only) against candidates
-// [128 blockIdx.x, ...) of the range's n_cand; tab: row 0 of the range (cand_first's), lin: its lin_w.
+// The contraction of one wave: its 32 candidates [c0, c0 + 32) against the RT request tiles from r0 on, every chunk of
+// the row through the wave's own tile T, one chunk prefetched.  acc[t][x] of a lane afterwards: request row
+// 8 (x / 4) + 4 (lane / 32) + x % 4 of tile t, candidate lane % 32.  The sequence of matrix instructions of a tile
+// does not depend on RT: catalog_gemm_kernel and catalog_topk_kernel (kernels_catalog_topk.h) both run this and no
+// other, so a (request, candidate) pair gets the same accumulator bits from either, at any RT.
 template <int FMT, int RT>
-__global__ __launch_bounds__(64 * kCatWaves) void catalog_gemm_kernel(const char *tab, const float *lin, int L, CatalogDev cd, int r0,
-                                                                     int n_req, int64_t n_cand, float v, int output_prob,
-                                                                     float *out) {
-  static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
-  static_assert(RT == 1 || RT == 2 || RT == 4, "request tiles per launch");
+__device__ __forceinline__ void catalog_accumulate(const char *tab, int L, const CatalogDev &cd, int r0, int64_t c0, int64_t n_cand,
+                                                   char *T, int lane, cat_v16f (&acc)[RT]) {
   constexpr int ES = FMT == SERVE_F16 ? 2 : 4;
-  __shared__ __attribute__((aligned(16))) char tile[kCatWaves][32 * kCatRowBytes];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t c0 = static_cast<int64_t>(blockIdx.x) * kCatCands + wv * 32;  // the wave's first candidate
-  if (c0 >= n_cand) return;  // (nothing below waits for another wave)
-  char *const T = tile[wv];
   const int64_t row_bytes = static_cast<int64_t>(L) * ES;
   const bool even16 = (row_bytes & 15) == 0;
   const int n_chunks = cd.lp * ES / kCatChunkBytes;
   const int row4 = lane >> 4, sub = lane & 15;  // the loads: four rows per instruction, 16 lanes along a row
   const int j = lane & 31, h = lane >> 5;       // the fragments: row j of the tile, k-block h of a step
 
-  cat_v16f acc[RT];
 #pragma unroll
   for (int t = 0; t < RT; t++)
 #pragma unroll
@@ -232,6 +226,31 @@ __global__ __launch_bounds__(64 * kCatWaves) void catalog_gemm_kernel(const char
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   }
+}
+
+// The epilogue of one accumulator, shared for the same reason: candidate value v, its linear weight lw, the request's
+// base and (f16) shift.
+template <int FMT>
+__device__ __forceinline__ float catalog_logit(float a, float v, float lw, float base, int shift) {
+  if (FMT == SERVE_F16) a = ldexpf(a, -shift);
+  return __fmaf_rn(v, a, __fmaf_rn(v, lw, base));
+}
+
+// Requests [r0, r0 + 32 RT) (rows of cd, whole tiles; stores for r < n_req only) against candidates
+// [128 blockIdx.x, ...) of the range's n_cand; tab: row 0 of the range (cand_first's), lin: its lin_w.
+template <int FMT, int RT>
+__global__ __launch_bounds__(64 * kCatWaves) void catalog_gemm_kernel(const char *tab, const float *lin, int L, CatalogDev cd, int r0,
+                                                                     int n_req, int64_t n_cand, float v, int output_prob,
+                                                                     float *out) {
+  static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
+  static_assert(RT == 1 || RT == 2 || RT == 4, "request tiles per launch");
+  __shared__ __attribute__((aligned(16))) char tile[kCatWaves][32 * kCatRowBytes];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t c0 = static_cast<int64_t>(blockIdx.x) * kCatCands + wv * 32;  // the wave's first candidate
+  if (c0 >= n_cand) return;  // (nothing below waits for another wave)
+  const int j = lane & 31, h = lane >> 5;
+  cat_v16f acc[RT];
+  catalog_accumulate<FMT, RT>(tab, L, cd, r0, c0, n_cand, tile[wv], lane, acc);
 
   // ---- accumulator x of a lane: request row 8 (x / 4) + 4 (lane / 32) + x % 4 of the tile, candidate lane % 32
   const int64_t c = c0 + j;
@@ -243,9 +262,7 @@ __global__ __launch_bounds__(64 * kCatWaves) void catalog_gemm_kernel(const char
     for (int x = 0; x < 16; x++) {
       const int r = r0 + kCatTile * t + 8 * (x >> 2) + 4 * h + (x & 3);
       if (r >= n_req) continue;
-      float a = acc[t][x];
-      if (FMT == SERVE_F16) a = ldexpf(a, -cd.shift[r]);
-      const float score = __fmaf_rn(v, a, __fmaf_rn(v, lw, cd.base[r]));
+      const float score = catalog_logit<FMT>(acc[t][x], v, lw, cd.base[r], FMT == SERVE_F16 ? cd.shift[r] : 0);
       out[static_cast<int64_t>(r) * n_cand + c] = output_prob ? sigmoid_ref(score) : score;
     }
 }

@@ -244,6 +244,13 @@ ABI = [
     ("ffm_engine_score_catalog_device", ctypes.c_int,
      [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp]),
+    # ... and the best K per request (include/ffm_engine.h "Scoring a catalogue: the best K")
+    ("ffm_engine_score_catalog_topk", ctypes.c_int,
+     [_vp, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+      ctypes.c_int32, ctypes.c_int32, _f32p, _i32p]),
+    ("ffm_engine_score_catalog_topk_device", ctypes.c_int,
+     [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     # the fields' cardinalities counted on the device, id ranges sized by them (include/ffm_engine.h "Field sketches")
     ("ffm_engine_sketch_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("ffm_engine_sketch_add", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32]),
@@ -980,6 +987,27 @@ def score_catalog_reference(weights, ctx, field, first, count, val=1.0, n_fields
     return dot64, scale
 
 
+def catalog_topk_reference(scores, first, k):
+    """Engine.score_catalog_topk's definition (include/ffm_engine.h "Scoring a catalogue: the best K") on a
+    score_catalog matrix of logits float32[n_req, count]; numpy only.  Returns (scores float32[n_req, k], ids
+    int32[n_req, k]): per request the k candidates with the largest key = key32(score) << 32 | ~uint32(column), key32
+    flipping all bits of a negative float and the sign bit of any other (-0.0 < +0.0 < ... < +inf < a NaN with a clear
+    sign bit; ties to the lower id), ids first + column; slots from count on hold -1 and the NaN 0x7FC00000."""
+    s = np.ascontiguousarray(scores, np.float32)
+    n_req, count = s.shape
+    bits = s.view(np.uint32).astype(np.uint64)
+    key32 = np.where(bits >> np.uint64(31) != 0, bits ^ np.uint64(0xFFFFFFFF), bits ^ np.uint64(0x80000000))
+    key = (key32 << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - np.arange(count, dtype=np.uint64))[None, :]
+    out_s = np.full((n_req, int(k)), 0x7FC00000, np.uint32)
+    out_i = np.full((n_req, int(k)), -1, np.int32)
+    n = min(int(k), count)
+    col = np.argpartition(key, count - n, axis=1)[:, count - n:] if 0 < n < count else np.tile(np.arange(count), (n_req, 1))
+    col = np.take_along_axis(col, np.argsort(np.take_along_axis(key, col, axis=1), axis=1)[:, ::-1], axis=1)  # (keys are unique)
+    out_s[:, :n] = np.take_along_axis(s.view(np.uint32), col, axis=1)
+    out_i[:, :n] = int(first) + col
+    return out_s.view(np.float32), out_i
+
+
 def load_library(path=None):
     """dlopen libffm_engine.so and bind every ABI symbol.  Raises if it is missing."""
     global _lib
@@ -1530,6 +1558,26 @@ class Engine:
         self._check(self.lib.ffm_engine_score_catalog_device(
             self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, int(field), int(first), int(count), float(val),
             int(ctx_nnz), int(ctx_cap), int(output_prob), out))
+
+    def score_catalog_topk(self, ctx, field, first, count, k, val=1.0, output_prob=False):
+        """The k best candidates of score_catalog per request, selected on the device without writing the matrix:
+        (scores float32[n_req, k], ids int32[n_req, k]), best first (include/ffm_engine.h "Scoring a catalogue: the
+        best K"; catalog_topk_reference on score_catalog's matrix is the definition).  Ranked by logit, ties to the
+        lower id; the scores are score_catalog's bits; slots from count on hold id -1 and NaN."""
+        scores = np.zeros((ctx.n_rows, max(int(k), 0)), np.float32)
+        ids = np.zeros((ctx.n_rows, max(int(k), 0)), np.int32)
+        _, cp, cfld, cft, cv, _ = self._csr(ctx)
+        self._check(self.lib.ffm_engine_score_catalog_topk(self.h, ctx.n_rows, cp, cfld, cft, cv, int(field), int(first), int(count),
+                                                           float(val), int(k), int(output_prob), _f(scores), _i(ids)))
+        return scores, ids
+
+    def score_catalog_topk_device(self, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, field, first, count, val, k, ctx_nnz,
+                                  ctx_cap, output_prob, out_score, out_id):
+        """score_catalog_topk on arrays already in HBM (device addresses), out_score / out_id [n_req][k] there too.
+        Asynchronous on the engine's stream; sync() reports a too-long context."""
+        self._check(self.lib.ffm_engine_score_catalog_topk_device(
+            self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, int(field), int(first), int(count), float(val), int(k),
+            int(ctx_nnz), int(ctx_cap), int(output_prob), out_score, out_id))
 
     # ---- blocks already in HBM (raw device addresses as ints) ----
     def score_candidates_device(self, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, cand_req_ptr, n_cand, cand_ptr,

@@ -1125,7 +1125,7 @@ int ffm_engine_score_candidates_device(ffm_engine *e, int32_t n_req, const int32
  *   the host call's output) are allocated by the first call, grown to the largest call seen and freed by
  *   ffm_engine_destroy; an engine that never calls this allocates and launches nothing new.  The profile calls label
  *   the kernels "catalog_u_kernel" and "catalog_gemm_kernel".  FFM_ENGINE_ABI_VERSION is what it was.
- * OUT OF SCOPE  a top-K epilogue and the CLI (follow-ups); candidates of more than one entry; LR and FM. */
+ * OUT OF SCOPE  the CLI (a follow-up); candidates of more than one entry; LR and FM.  The best K per request: below. */
 int ffm_engine_score_catalog(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
                              const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
                              int32_t n_cand, float cand_val, int32_t output_prob, float *out);
@@ -1133,6 +1133,46 @@ int ffm_engine_score_catalog_device(ffm_engine *e, int32_t n_req, const int32_t 
                                     const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
                                     int32_t n_cand, float cand_val, int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob,
                                     float *out);
+
+/* ---- Scoring a catalogue: the best K ---------------------------------------------------------------------
+ * What a retrieval caller wants of the section above: per request the top_k largest scores and their ids, not
+ * n_req * n_cand floats.  The selection runs inside the contraction (csrc/kernels_catalog_topk.h); the matrix of
+ * scores is never written, and the n_req * n_cand <= 2^31 - 1 limit of the two calls above does not apply.
+ * ORDER  For request r the candidates are ordered by a total order on the LOGIT:
+ *   key32   the monotone map of a float's bits to an unsigned: all bits of a negative float flipped, only the sign
+ *           bit of any other.  So -0.0 < +0.0, and a NaN with the sign bit clear ranks above +inf.
+ *   ties    go to the lower id.  As one 64-bit word: key = key32 << 32 | ~uint32(c - cand_first), the larger first.
+ *   Keys are unique: nothing depends on the order in which partial results meet.  catalog_topk_reference of the
+ *   Python binding is this definition on a score_catalog matrix.
+ * SLOTS  out_score[n_req][top_k] and out_id[n_req][top_k], request-major.  Slot j < min(top_k, n_cand) holds the j-th
+ *   candidate in that order, out_id the model id cand_first + column; slots from n_cand on hold id -1 and the NaN
+ *   with bits 0x7FC00000.
+ * SCORES  bit for bit what ffm_engine_score_catalog returns for the same request and candidate (the same chunk and
+ *   step order, the same epilogue, whatever number of request tiles either launch carries), and so under its
+ *   float64 contract.  With output_prob the ranking is still by logit and the stored scores are the engine's sigmoid
+ *   of the selected logits.  cand_val < 0 simply ranks by the resulting score.
+ * FLAGGED  A context longer than max_row_nnz (device call: or than ctx_cap) makes its request's base NaN: that request
+ *   gets -1 / NaN in all top_k slots, the others are untouched; FFM_E_CAPACITY from the host call or the next
+ *   ffm_engine_sync.
+ * ffm_engine_score_catalog_topk: arrays in host memory; synchronous; copies n_req * top_k * 8 bytes back.
+ * ffm_engine_score_catalog_topk_device: device addresses, as ffm_engine_score_catalog_device; asynchronous on the
+ *   engine's stream.
+ * Both: top_k in [1, 64], else FFM_E_INVALID naming top_k; every other check and refusal of the section above but the
+ *   n_req * n_cand one.  n_req == 0 is FFM_OK with nothing written; n_cand == 0 with n_req > 0 fills the outputs with
+ *   -1 / NaN.  The partial lists (n_req * 4 G * Kp words of 8 bytes: G workgroups, at most two per CU or the
+ *   environment's FFM_GRID_CATALOG, Kp = top_k rounded up to a power of two) and the host call's two outputs are
+ *   allocated by the first call and grown to the largest call seen; an engine that never calls this allocates nothing.
+ *   The profile calls label the kernels "catalog_topk_kernel" and "catalog_topk_merge_kernel".
+ *   FFM_ENGINE_ABI_VERSION is what it was.
+ * OUT OF SCOPE  the CLI; top_k > 64; FFM_FLAG_SERVE_F8 and pruned tables. */
+int ffm_engine_score_catalog_topk(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                  const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
+                                  int32_t n_cand, float cand_val, int32_t top_k, int32_t output_prob, float *out_score,
+                                  int32_t *out_id);
+int ffm_engine_score_catalog_topk_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                         const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
+                                         int32_t n_cand, float cand_val, int32_t top_k, int32_t ctx_nnz, int32_t ctx_cap,
+                                         int32_t output_prob, float *out_score, int32_t *out_id);
 
 /* ---- Field ablation: the loss and AUC of the model without each field, in one pass -------------------
  * Which fields earn their place?  The standard answer is the evaluation loss and AUC of the same model with

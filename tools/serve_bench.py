@@ -15,7 +15,7 @@
                                               ffm_engine_score_candidates[_device] against the same data spelled out
                                               as rows through ffm_engine_predict_batch[_device], same engine, same
                                               process, alternating windows
-  python tools/serve_bench.py --catalog --kind f16
+  python tools/serve_bench.py --catalog --kind f16 [--topk 8 16 64]
                                               request contexts against a whole id range (include/ffm_engine.h "Scoring
                                               a catalogue"; profiles/score_catalog.md): ffm_engine_score_catalog_device
                                               for 32 and 128 requests x 65536 and 1048576 candidates, against the rate
@@ -196,7 +196,44 @@ def run_catalog(args):
                 rows_baseline_us_per_8192=[round(x, 1) for x in base_us], rows_baseline_scores_per_s=base_rate,
                 rows_baseline_us_for_the_same_scores=round(n_req * n_cand / base_rate * 1e6, 1),
                 speedup=n_req * n_cand / base_rate * 1e6 / med, checksum=float(out[:n_req * n_cand:4099].double().sum().cpu()))), flush=True)
+            for K in args.topk:
+                catalog_topk_line(args, eng, windows, d, out, g, first, cf, n_req, n_cand, K, med)
     eng.close()
+
+
+def catalog_topk_line(args, eng, windows, d, out, g, first, cf, n_req, n_cand, K, matrix_us):
+    """score_catalog_topk_device against what a caller does without it -- score_catalog_device, then torch.topk on its
+    matrix -- in this process; the profile calls' split between the two kernels; the bytes of partial lists a call
+    writes and reads again."""
+    import torch
+    ptrs = [t.data_ptr() for t in d]
+    score = torch.zeros(n_req * K, dtype=torch.float32, device="cuda")
+    ids = torch.zeros(n_req * K, dtype=torch.int32, device="cuda")
+    stream = torch.cuda.ExternalStream(eng.stream)
+
+    def topk():
+        eng.score_catalog_topk_device(n_req, *ptrs, g, first, n_cand, 1.0, K, n_req * cf, cf, 0, score.data_ptr(), ids.data_ptr())
+
+    def matrix_then_topk():
+        eng.score_catalog_device(n_req, *ptrs, g, first, n_cand, 1.0, n_req * cf, cf, 0, out.data_ptr())
+        with torch.cuda.stream(stream):
+            torch.topk(out[:n_req * n_cand].view(n_req, n_cand), K, dim=1)
+    us, base = windows(topk), windows(matrix_then_topk)
+    eng.profile_enable(True)
+    for _ in range(20):
+        topk()
+    eng.sync()
+    dump = eng.profile_dump()
+    eng.profile_enable(False)
+    kp = 1 << (K - 1).bit_length()
+    grid = min((n_cand + 127) // 128, 2 * torch.cuda.get_device_properties(0).multi_processor_count)
+    med, bmed = us[len(us) // 2], base[len(base) // 2]
+    print("SERVE_BENCH " + json.dumps(dict(
+        catalog_topk=True, kind=args.kind, n_req=n_req, n_cand=n_cand, top_k=K, us_median=round(med, 1), us_min=round(us[0], 1),
+        us_max=round(us[-1], 1), matrix_then_torch_topk_us_median=round(bmed, 1), matrix_then_torch_topk_us_min=round(base[0], 1),
+        matrix_then_torch_topk_us_max=round(base[-1], 1), matrix_alone_us_median=round(matrix_us, 1), speedup=bmed / med,
+        over_matrix_alone=med / matrix_us, partial_list_bytes=n_req * grid * 4 * kp * 8,
+        profile=[ln for ln in dump.strip().splitlines() if "catalog" in ln])), flush=True)
 
 
 def candidate_bytes(kind, cf, kf, per, k=N_FACTORS):
@@ -455,6 +492,9 @@ def main():
                     help="pruned serving tables against the masked unpruned engine, --kind f32 or f16 (default f16)")
     ap.add_argument("--catalog", action="store_true",
                     help="request contexts against a whole id range (include/ffm_engine.h \"Scoring a catalogue\"), --kind f32 or f16")
+    ap.add_argument("--topk", type=int, nargs="*", default=[], metavar="K",
+                    help="with --catalog: also the best K per request (score_catalog_topk_device) against the matrix call "
+                         "followed by torch.topk")
     args = ap.parse_args()
     if args.catalog:
         if args.kind not in ("f32", "f16"):
