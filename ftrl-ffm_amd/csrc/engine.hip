@@ -53,6 +53,7 @@
 #include "kernels_serve8.h"
 #include "kernels_catalog.h"
 #include "kernels_catalog_topk.h"
+#include "kernels_catalog_items.h"
 #include "kernels_delta.h"
 #include "kernels_ablate.h"
 #include "kernels_ablate_pairs.h"
@@ -131,6 +132,7 @@ enum KernelId {
   K_LOSS_SUM, K_LINEAR_UPDATE, K_BIAS_UPDATE, K_LATENT_UPDATE, K_LATENT_UPDATE_FEW, K_LATENT_UPDATE_WALK, K_LATENT_UPDATE_GIANT,
   K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC, K_PUSH_SCORES, K_SERVE_ROW,
   K_SERVE_CTX, K_SERVE_CAND, K_CATALOG_U, K_CATALOG_GEMM, K_CATALOG_TOPK, K_CATALOG_TOPK_MERGE,
+  K_CATALOG_ITEMS_U, K_CATALOG_ITEMS_SELF, K_CATALOG_ITEMS_GEMM, K_CATALOG_ITEMS_TOPK,
   K_KEYED_CAPTURE, K_KEYED_SORT_HIST, K_KEYED_SORT_SCAN, K_KEYED_SORT_SCATTER, K_KEYED_RANK,
   K_UPLOAD, K_NORM_ROWS,
   K_COUNT
@@ -141,6 +143,7 @@ const char *kKernelNames[K_COUNT] = {
     "row_kernel<predict>", "refresh_kernel", "update_single_kernel", "metric_hist_kernel", "push_scores_kernel", "serve_wave_kernel",
     "serve_context_kernel", "serve_candidate_kernel", "catalog_u_kernel", "catalog_gemm_kernel",
     "catalog_topk_kernel", "catalog_topk_merge_kernel",
+    "catalog_items_u_kernel", "catalog_items_self_kernel", "catalog_items_gemm_kernel", "catalog_items_topk_kernel",
     "keyed_capture_kernel", "keyed_sort_hist_kernel", "keyed_sort_scan_kernels", "keyed_sort_scatter_kernel", "keyed_rank_kernels",
     "pull_block_kernel", "normalize_rows_kernel"};
 
@@ -466,6 +469,12 @@ struct ffm_engine {
   int *topk_id = nullptr;
   size_t topk_part_cap = 0, topk_score_cap = 0, topk_id_cap = 0;
   int grid_catalog = 0, cu_count = 0;
+  // ffm_engine_score_items[_topk][_device] (include/ffm_engine.h "Scoring a catalogue: items of several entries"): S_c
+  // of the call's items, and the host calls' copy of item_feat with the fields of its entries beside it (written and
+  // read by the hashing of an engine with FFM_FLAG_HASH_IDS alone); made and grown like the arrays above
+  float *item_s = nullptr;
+  int *d_item_feat = nullptr, *d_item_field = nullptr;
+  size_t item_s_cap = 0, item_feat_cap = 0, item_field_cap = 0;
   // field and pair ablation (include/ffm_engine.h "Field ablation", "Pair ablation"; engine_ablate.h), each set all
   // made by its enable call for its V variants -- n_fields + 1, or n_fields (n_fields + 1) / 2 + 1 --: out [V][max_rows]
   // scores and loss the same shape (the kernel's variant-major outputs), sums [V], part [V][kLossParts + 1] the loss

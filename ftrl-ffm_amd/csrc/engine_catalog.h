@@ -2,21 +2,29 @@
 // catalogue" and "... the best K"; kernels_catalog.h, kernels_catalog_topk.h): what the entry points check, the buffers
 // they grow, and the launches -- the engine's own row kernel over the contexts (base), catalog_u_kernel, then either
 // catalog_gemm_kernel per 128 requests or catalog_topk_kernel per 32 RT requests and catalog_topk_merge_kernel.
+// The same launches serve a table of items of several entries ("... items of several entries",
+// kernels_catalog_items.h): S_c per item first, U towards every slot's field, the kernels over CatalogItems.
 // Part of engine.hip's translation unit (included inside its extern "C" block).
 
-static int catalog_check(ffm_engine *e, int32_t n_req, int32_t cand_field, int32_t cand_first, int32_t n_cand) {
+// The engines every call of this file refuses, by name; what: "score_catalog" or "score_items".
+static int catalog_engine_check(ffm_engine *e, const char *what) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
   if (!serving(e))
-    return fail(FFM_E_UNSUPPORTED, "score_catalog needs a serving engine (FFM_FLAG_SERVE_F32 / _F16): "
-                                   "ffm_engine_pack_weights copies a training engine's weights into one");
-  F8_REFUSE(e, "score_catalog");
-  PRUNED_REFUSE(e, "score_catalog");
-  MASK_REFUSE(e, "score_catalog");
+    return fail(FFM_E_UNSUPPORTED, std::string(what) + " needs a serving engine (FFM_FLAG_SERVE_F32 / _F16): "
+                                                       "ffm_engine_pack_weights copies a training engine's weights into one");
+  F8_REFUSE(e, what);
+  PRUNED_REFUSE(e, what);
+  MASK_REFUSE(e, what);
   if (e->norm_rows_on)
-    return fail(FFM_E_INVALID, "score_catalog is not available on an engine with FFM_FLAG_NORM_ROWS: a candidate would change "
-                               "the scale of its context's terms");
+    return fail(FFM_E_INVALID, std::string(what) + " is not available on an engine with FFM_FLAG_NORM_ROWS: a candidate would change "
+                                                   "the scale of its context's terms");
   if (e->in_group || e->m.n_shards > 1)
-    return fail(FFM_E_UNSUPPORTED, "score_catalog is not available on a group's or a shard's engine: it reads one whole table");
+    return fail(FFM_E_UNSUPPORTED, std::string(what) + " is not available on a group's or a shard's engine: it reads one whole table");
+  return FFM_OK;
+}
+
+static int catalog_check(ffm_engine *e, int32_t n_req, int32_t cand_field, int32_t cand_first, int32_t n_cand) {
+  if (int rc = catalog_engine_check(e, "score_catalog")) return rc;
   if (n_req < 0 || n_cand < 0) return fail(FFM_E_INVALID, "negative n_req / n_cand");
   if (cand_field < 0 || cand_field >= e->m.n_fields)
     return fail(FFM_E_INVALID, "cand_field " + std::to_string(cand_field) + " lies outside [0, n_fields)");
@@ -43,12 +51,21 @@ static int catalog_rows(int n_req) {
   return n_req - rest + (rest ? kCatTile * catalog_rt(cdiv(rest, kCatTile)) : 0);
 }
 
+// The columns of a call when they are items of several entries (kernels_catalog_items.h) and not a field's id range:
+// the slots by value, feat[n_items][slots.n] in device memory.
+struct ItemTable {
+  CatalogItemSlots slots;
+  const int32_t *feat;
+  int32_t n_items;
+};
+
 // What both kinds of launches start with, on arrays in device memory: base and U of the requests, padded to `rows`
-// (whole tiles of the launches that follow).  cap: the longest context, in [1, max_row_nnz].
+// (whole tiles of the launches that follow).  cap: the longest context, in [1, max_row_nnz].  items: U towards every
+// slot's field, one block behind the other, instead of towards g.
 static int catalog_prepare(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
-                           const float *ctx_val, int32_t ctx_nnz, int cap, int32_t g, int rows, CatalogDev *out_cd) {
+                           const float *ctx_val, int32_t ctx_nnz, int cap, int32_t g, const ItemTable *items, int rows, CatalogDev *out_cd) {
   const ModelDev &m = e->m;
-  const int lp = catalog_lp(m.lat_fmt, m.row_len);
+  const int lp = catalog_lp(m.lat_fmt, m.row_len) * (items ? items->slots.n : 1);
   int rc;
   if ((rc = e->grow(&e->cat.base, &e->cat_base_cap, static_cast<size_t>(rows)))) return rc;
   if ((rc = e->grow(&e->cat.shift, &e->cat_shift_cap, static_cast<size_t>(rows)))) return rc;
@@ -60,25 +77,51 @@ static int catalog_prepare(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr,
   // base_r: the bits of predict_batch on the context rows
   launch_row_kernel(e, Rows{n_req, ctx_nnz, ctx_ptr, ctx_field, ctx_feat, ctx_val, nullptr}, cap, false, cd.base, 0);
   const int lds_cap = std::min(cap, kPredLdsCap);
-  LAUNCH(e, K_CATALOG_U, catalog_u_fn(m.lat_fmt), cdiv(rows, kPredRows), 64 * kPredRows, cand_ctx_lds_bytes(lds_cap), m, n_req, ctx_ptr,
-         ctx_field, ctx_feat, ctx_val, g, cd, cap, lds_cap);
+  if (items)
+    LAUNCH(e, K_CATALOG_ITEMS_U, catalog_items_u_fn(m.lat_fmt), cdiv(rows, kPredRows), 64 * kPredRows, cand_ctx_lds_bytes(lds_cap), m, n_req,
+           ctx_ptr, ctx_field, ctx_feat, ctx_val, items->slots, cd, cap, lds_cap);
+  else
+    LAUNCH(e, K_CATALOG_U, catalog_u_fn(m.lat_fmt), cdiv(rows, kPredRows), 64 * kPredRows, cand_ctx_lds_bytes(lds_cap), m, n_req, ctx_ptr,
+           ctx_field, ctx_feat, ctx_val, g, cd, cap, lds_cap);
   *out_cd = cd;
   return FFM_OK;
 }
 
+// S_c of every item of the table into e->item_s, ahead of the launches that read it.
+static int catalog_items_self(ffm_engine *e, const ItemTable &items) {
+  if (int rc = e->grow(&e->item_s, &e->item_s_cap, static_cast<size_t>(items.n_items))) return rc;
+  const int grid = static_cast<int>((static_cast<int64_t>(items.n_items) * 4 + 255) / 256);
+  LAUNCH(e, K_CATALOG_ITEMS_SELF, catalog_items_self_fn(e->m.lat_fmt), grid, 256, 0, e->m, items.slots, items.feat,
+         static_cast<int64_t>(items.n_items), e->item_s);
+  return FFM_OK;
+}
+
+// What the item source takes behind the kernels' common arguments (cd.lp: U's whole row, slots.n blocks of Lp).
+static CatalogItemSrc::Args catalog_items_args(const ffm_engine *e, const ItemTable &items, const CatalogDev &cd) {
+  const int es = e->m.lat_fmt == SERVE_F16 ? 2 : 4;
+  return CatalogItemSrc::Args{items.feat, e->m.n_feats, items.slots.n, cd.lp / items.slots.n * es / kCatChunkBytes};
+}
+
+// items: the columns are its n_cand items (g, first and v unused, first == 0), else the range's candidates.
 static int catalog_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
                           const float *ctx_val, int32_t ctx_nnz, int cap, int32_t g, int32_t first, int32_t n_cand, float v,
-                          int32_t output_prob, float *out) {
+                          const ItemTable *items, int32_t output_prob, float *out) {
   const ModelDev &m = e->m;
   const int L = m.row_len, es = m.lat_fmt == SERVE_F16 ? 2 : 4;
   CatalogDev cd;
-  if (int rc = catalog_prepare(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, g, catalog_rows(n_req), &cd)) return rc;
+  if (int rc = items ? catalog_items_self(e, *items) : FFM_OK) return rc;
+  if (int rc = catalog_prepare(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, g, items, catalog_rows(n_req), &cd)) return rc;
   const char *const tab = reinterpret_cast<const char *>(m.lat) + static_cast<int64_t>(first) * L * es;
   const int grid = static_cast<int>((static_cast<int64_t>(n_cand) + kCatCands - 1) / kCatCands);
   for (int r0 = 0; r0 < n_req; r0 += 128) {
     const int rt = catalog_rt(cdiv(std::min(128, n_req - r0), kCatTile));
-    LAUNCH(e, K_CATALOG_GEMM, catalog_gemm_fn(m.lat_fmt, rt), grid, 64 * kCatWaves, 0, tab, m.lin_w + first, L, cd, r0, n_req,
-           static_cast<int64_t>(n_cand), v, output_prob, out);
+    if (items)
+      LAUNCH(e, K_CATALOG_ITEMS_GEMM, catalog_gemm_fn<CatalogItemSrc>(m.lat_fmt, rt), grid, 64 * kCatWaves, 0, tab,
+             static_cast<const float *>(e->item_s), L, cd, r0, n_req, static_cast<int64_t>(n_cand), 1.0f, output_prob, out,
+             catalog_items_args(e, *items, cd));
+    else
+      LAUNCH(e, K_CATALOG_GEMM, catalog_gemm_fn(m.lat_fmt, rt), grid, 64 * kCatWaves, 0, tab, static_cast<const float *>(m.lin_w + first), L, cd,
+             r0, n_req, static_cast<int64_t>(n_cand), v, output_prob, out, CatalogSlabSrc::Args{});
   }
   HIP_TRY(hipGetLastError());
   return FFM_OK;
@@ -130,7 +173,7 @@ int ffm_engine_score_catalog_device(ffm_engine *e, int32_t n_req, const int32_t 
   // (a context beyond the engine's row limit is flagged by the row kernel whatever the cap says)
   const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
   return catalog_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, cand_field, cand_first, n_cand, cand_val,
-                        output_prob, out);
+                        nullptr, output_prob, out);
 }
 
 int ffm_engine_score_catalog(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
@@ -146,7 +189,7 @@ int ffm_engine_score_catalog(ffm_engine *e, int32_t n_req, const int32_t *ctx_pt
   if ((rc = e->grow(&e->cat_out, &e->cat_out_cap, n_out))) return rc;  // (before anything is queued)
   if ((rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap))) return rc;
   rc = catalog_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, cand_field, cand_first, n_cand,
-                      cand_val, output_prob, e->cat_out);
+                      cand_val, nullptr, output_prob, e->cat_out);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, e->cat_out, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
   return check_device_errors(e);
@@ -166,10 +209,11 @@ static int catalog_topk_tiles(int n_req, int r0, int top_k) {
   return std::min(catalog_topk_rt(top_k), catalog_rt(cdiv(n_req - r0, kCatTile)));
 }
 
-// The launches, on arrays in device memory; out_score / out_id [n_req][top_k] there too.  n_req > 0.
+// The launches, on arrays in device memory; out_score / out_id [n_req][top_k] there too.  n_req > 0.  items: as
+// catalog_launch.
 static int catalog_topk_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
                                const float *ctx_val, int32_t ctx_nnz, int cap, int32_t g, int32_t first, int32_t n_cand, float v,
-                               int32_t top_k, int32_t output_prob, float *out_score, int32_t *out_id) {
+                               const ItemTable *items, int32_t top_k, int32_t output_prob, float *out_score, int32_t *out_id) {
   const ModelDev &m = e->m;
   const int kp = catalog_topk_kp(top_k);
   if (n_cand == 0) {  // nothing to rank: the fill alone
@@ -187,12 +231,19 @@ static int catalog_topk_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_
   int rc;
   if ((rc = e->grow(&e->topk_part, &e->topk_part_cap, static_cast<size_t>(n_req) * P * kp))) return rc;
   CatalogDev cd;
-  if ((rc = catalog_prepare(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, g, rows, &cd))) return rc;
+  if (items && (rc = catalog_items_self(e, *items))) return rc;
+  if ((rc = catalog_prepare(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, g, items, rows, &cd))) return rc;
   const char *const tab = reinterpret_cast<const char *>(m.lat) + static_cast<int64_t>(first) * L * es;
   for (int r0 = 0; r0 < n_req;) {
     const int rt = catalog_topk_tiles(n_req, r0, top_k);
-    LAUNCH(e, K_CATALOG_TOPK, catalog_topk_fn(m.lat_fmt, rt), grid, 64 * kCatWaves, catalog_topk_lds_bytes(rt, kp), tab, m.lin_w + first, L,
-           cd, r0, n_req, static_cast<int64_t>(n_cand), v, top_k, kp, e->topk_part);
+    if (items)
+      LAUNCH(e, K_CATALOG_ITEMS_TOPK, catalog_topk_fn<CatalogItemSrc>(m.lat_fmt, rt), grid, 64 * kCatWaves, catalog_topk_lds_bytes(rt, kp), tab,
+             static_cast<const float *>(e->item_s), L, cd, r0, n_req, static_cast<int64_t>(n_cand), 1.0f, top_k, kp, e->topk_part,
+             catalog_items_args(e, *items, cd));
+    else
+      LAUNCH(e, K_CATALOG_TOPK, catalog_topk_fn(m.lat_fmt, rt), grid, 64 * kCatWaves, catalog_topk_lds_bytes(rt, kp), tab,
+             static_cast<const float *>(m.lin_w + first), L, cd, r0, n_req, static_cast<int64_t>(n_cand), v, top_k, kp, e->topk_part,
+             CatalogSlabSrc::Args{});
     r0 += kCatTile * rt;
   }
   LAUNCH(e, K_CATALOG_TOPK_MERGE, catalog_topk_merge_kernel, n_req, kTopkMergeThreads, 0, static_cast<const unsigned long long *>(e->topk_part),
@@ -212,7 +263,7 @@ int ffm_engine_score_catalog_topk_device(ffm_engine *e, int32_t n_req, const int
     return fail(FFM_E_INVALID, "null array");
   const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
   return catalog_topk_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, cand_field, cand_first, n_cand, cand_val,
-                             top_k, output_prob, out_score, out_id);
+                             nullptr, top_k, output_prob, out_score, out_id);
 }
 
 int ffm_engine_score_catalog_topk(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
@@ -229,7 +280,137 @@ int ffm_engine_score_catalog_topk(ffm_engine *e, int32_t n_req, const int32_t *c
   int cap = 1;
   if (n_cand > 0 && (rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap))) return rc;
   rc = catalog_topk_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, cand_field, cand_first,
-                           n_cand, cand_val, top_k, output_prob, e->topk_score, e->topk_id);
+                           n_cand, cand_val, nullptr, top_k, output_prob, e->topk_score, e->topk_id);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out_score, e->topk_score, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_id, e->topk_id, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, e->stream));
+  return check_device_errors(e);
+}
+
+// ---- items of several entries (include/ffm_engine.h "Scoring a catalogue: items of several entries") ----------------
+
+// catalog_check's checks for an item table, and the table's slots into *t (t->feat: item_feat as it came).  No range
+// check of ids: an id outside [0, n_feats) is an erased slot.
+static int items_check(ffm_engine *e, int32_t n_req, int32_t n_slots, const int32_t *item_field, const int32_t *item_feat,
+                       const float *item_val, int32_t n_items, ItemTable *t) {
+  if (int rc = catalog_engine_check(e, "score_items")) return rc;
+  if (n_req < 0 || n_items < 0) return fail(FFM_E_INVALID, "negative n_req / n_items");
+  if (n_slots < 1 || n_slots > kItemSlots)
+    return fail(FFM_E_INVALID, "item_field: n_slots " + std::to_string(n_slots) + " lies outside [1, " + std::to_string(kItemSlots) + "]");
+  if (!item_field) return fail(FFM_E_INVALID, "null array (item_field)");
+  *t = ItemTable{};
+  for (int a = 0; a < n_slots; a++) {
+    if (item_field[a] < 0 || item_field[a] >= e->m.n_fields)
+      return fail(FFM_E_INVALID, "item_field[" + std::to_string(a) + "] = " + std::to_string(item_field[a]) + " lies outside [0, n_fields)");
+    for (int b = 0; b < a; b++)
+      if (item_field[b] == item_field[a])
+        return fail(FFM_E_INVALID, "item_field names field " + std::to_string(item_field[a]) + " twice: an item has one entry per field");
+    t->slots.field[a] = item_field[a];
+    t->slots.val[a] = item_val ? item_val[a] : 1.0f;
+  }
+  t->slots.n = n_slots;
+  t->feat = item_feat;
+  t->n_items = n_items;
+  if (n_req > e->max_rows) return fail(FFM_E_CAPACITY, "more requests than max_batch_rows");
+  return FFM_OK;
+}
+
+// The host calls' item_feat into the engine's copy (t->feat: in host memory on entry, the copy afterwards), hashed
+// under its slot's field on an engine with FFM_FLAG_HASH_IDS, behind one another on the engine's stream.
+static int items_stage(ffm_engine *e, ItemTable *t) {
+  const int m = t->slots.n;
+  const size_t n = static_cast<size_t>(t->n_items) * m;
+  int rc;
+  if ((rc = e->grow(&e->d_item_feat, &e->item_feat_cap, n))) return rc;
+  if (e->hash_ids && (rc = e->grow(&e->d_item_field, &e->item_field_cap, n))) return rc;
+  hipStream_t st = e->stream;
+  HIP_TRY(hipMemcpyAsync(e->d_item_feat, t->feat, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+  if (e->hash_ids) {
+    hipLaunchKernelGGL(catalog_items_fields_kernel, dim3(static_cast<unsigned>(std::min<size_t>(1024, (n + 255) / 256))), dim3(256), 0, st,
+                       t->slots, static_cast<int64_t>(n), e->d_item_field);
+    const size_t piece = static_cast<size_t>(m) << 27;  // whole items, and entries an int32 counts
+    for (size_t at = 0; at < n; at += piece)
+      launch_hash_ids(e, st, static_cast<int32_t>(std::min(piece, n - at)), e->d_item_field + at, e->d_item_feat + at, e->d_item_feat + at);
+  }
+  t->feat = e->d_item_feat;
+  return FFM_OK;
+}
+
+int ffm_engine_score_items_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                                  const float *ctx_val, int32_t n_slots, const int32_t *item_field, const int32_t *item_feat,
+                                  const float *item_val, int32_t n_items, int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob,
+                                  float *out) {
+  ItemTable t;
+  if (int rc = items_check(e, n_req, n_slots, item_field, item_feat, item_val, n_items, &t)) return rc;
+  if (int rc = catalog_matrix_check(n_req, n_items)) return rc;
+  if (int rc = catalog_ready(e)) return rc;
+  if (n_req == 0 || n_items == 0) return FFM_OK;
+  if (ctx_nnz < 0 || ctx_cap < 0) return fail(FFM_E_INVALID, "negative ctx_nnz / ctx_cap");
+  if (!ctx_ptr || !out || !item_feat || (ctx_nnz > 0 && (!ctx_field || !ctx_feat || !ctx_val))) return fail(FFM_E_INVALID, "null array");
+  const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
+  return catalog_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, output_prob, out);
+}
+
+int ffm_engine_score_items(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                           const float *ctx_val, int32_t n_slots, const int32_t *item_field, const int32_t *item_feat,
+                           const float *item_val, int32_t n_items, int32_t output_prob, float *out) {
+  ItemTable t;
+  int rc = items_check(e, n_req, n_slots, item_field, item_feat, item_val, n_items, &t);
+  if (rc || (rc = catalog_matrix_check(n_req, n_items)) || (rc = catalog_ready(e))) return rc;
+  if (n_req == 0 || n_items == 0) return FFM_OK;
+  if (!out || !item_feat) return fail(FFM_E_INVALID, "null array");
+  const size_t n_out = static_cast<size_t>(n_req) * n_items;
+  int32_t ctx_nnz = 0;
+  int cap = 1;
+  if ((rc = e->grow(&e->cat_out, &e->cat_out_cap, n_out))) return rc;  // (before anything is queued)
+  if ((rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap)) || (rc = items_stage(e, &t))) return rc;
+  rc = catalog_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, output_prob,
+                      e->cat_out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, e->cat_out, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
+  return check_device_errors(e);
+}
+
+static int items_topk_check(ffm_engine *e, int32_t n_req, int32_t n_slots, const int32_t *item_field, const int32_t *item_feat,
+                            const float *item_val, int32_t n_items, int32_t top_k, ItemTable *t) {
+  if (int rc = items_check(e, n_req, n_slots, item_field, item_feat, item_val, n_items, t)) return rc;
+  if (top_k < 1 || top_k > kTopkMax)
+    return fail(FFM_E_INVALID, "top_k " + std::to_string(top_k) + " lies outside [1, " + std::to_string(kTopkMax) + "]");
+  return catalog_ready(e);
+}
+
+int ffm_engine_score_items_topk_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                       const int32_t *ctx_feat, const float *ctx_val, int32_t n_slots, const int32_t *item_field,
+                                       const int32_t *item_feat, const float *item_val, int32_t n_items, int32_t top_k, int32_t ctx_nnz,
+                                       int32_t ctx_cap, int32_t output_prob, float *out_score, int32_t *out_id) {
+  ItemTable t;
+  if (int rc = items_topk_check(e, n_req, n_slots, item_field, item_feat, item_val, n_items, top_k, &t)) return rc;
+  if (n_req == 0) return FFM_OK;
+  if (ctx_nnz < 0 || ctx_cap < 0) return fail(FFM_E_INVALID, "negative ctx_nnz / ctx_cap");
+  if (!out_score || !out_id || (n_items > 0 && (!ctx_ptr || !item_feat || (ctx_nnz > 0 && (!ctx_field || !ctx_feat || !ctx_val)))))
+    return fail(FFM_E_INVALID, "null array");
+  const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
+  return catalog_topk_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, top_k, output_prob,
+                             out_score, out_id);
+}
+
+int ffm_engine_score_items_topk(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                                const float *ctx_val, int32_t n_slots, const int32_t *item_field, const int32_t *item_feat,
+                                const float *item_val, int32_t n_items, int32_t top_k, int32_t output_prob, float *out_score,
+                                int32_t *out_id) {
+  ItemTable t;
+  int rc = items_topk_check(e, n_req, n_slots, item_field, item_feat, item_val, n_items, top_k, &t);
+  if (rc) return rc;
+  if (n_req == 0) return FFM_OK;
+  if (!out_score || !out_id || (n_items > 0 && !item_feat)) return fail(FFM_E_INVALID, "null array");
+  const size_t n_out = static_cast<size_t>(n_req) * top_k;
+  if ((rc = e->grow(&e->topk_score, &e->topk_score_cap, n_out)) || (rc = e->grow(&e->topk_id, &e->topk_id_cap, n_out))) return rc;
+  int32_t ctx_nnz = 0;
+  int cap = 1;
+  if (n_items > 0 && ((rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap)) || (rc = items_stage(e, &t))))
+    return rc;
+  rc = catalog_topk_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, top_k,
+                           output_prob, e->topk_score, e->topk_id);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out_score, e->topk_score, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(out_id, e->topk_id, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, e->stream));

@@ -539,7 +539,9 @@ static int opt_in_lds(ffm_engine *e) {
         if ((rc = lds_opt_in(update_all_fn(nf, kinds, waves), tile_lds_bytes(nf, waves)))) return rc;
   // the best K of a catalogue: the lists of the largest top_k a launch of rt request tiles can see
   for (int rt = 1; rt <= 4; rt *= 2)
-    if ((rc = lds_opt_in(catalog_topk_fn(e->m.lat_fmt, rt), catalog_topk_lds_bytes(rt, catalog_topk_kp(catalog_topk_max_k(rt)))))) return rc;
+    if ((rc = lds_opt_in(catalog_topk_fn(e->m.lat_fmt, rt), catalog_topk_lds_bytes(rt, catalog_topk_kp(catalog_topk_max_k(rt))))) ||
+        (rc = lds_opt_in(catalog_topk_fn<CatalogItemSrc>(e->m.lat_fmt, rt), catalog_topk_lds_bytes(rt, catalog_topk_kp(catalog_topk_max_k(rt))))))
+      return rc;
   return FFM_OK;
 }
 

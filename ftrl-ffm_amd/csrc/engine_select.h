@@ -156,35 +156,52 @@ inline ServeCandidateFn serve_candidate_fn(int fmt, int n_factors) {
 }
 // a catalogue (kernels_catalog.h): U per request, then <format, request tiles of 32 per launch>
 using CatalogUFn = void (*)(ModelDev, int, const int *, const int *, const int *, const float *, int, CatalogDev, int, int);
-using CatalogGemmFn = void (*)(const char *, const float *, int, CatalogDev, int, int, int64_t, float, int, float *);
+// Src: the row source -- CatalogSlabSrc (a range) or CatalogItemSrc (items of several entries, kernels_catalog_items.h)
+template <typename Src>
+using CatalogGemmFn = void (*)(const char *, const float *, int, CatalogDev, int, int, int64_t, float, int, float *, typename Src::Args);
 inline CatalogUFn catalog_u_fn(int fmt) {
   return fmt == SERVE_F16 ? catalog_u_kernel<SERVE_F16> : fmt == SERVE_F32 ? catalog_u_kernel<SERVE_F32> : nullptr;
 }
 // tiles: request tiles of the launch; the smallest RT that covers them (1, 2 or 4)
 inline int catalog_rt(int tiles) { return tiles <= 1 ? 1 : tiles <= 2 ? 2 : 4; }
-template <int FMT>
-CatalogGemmFn catalog_gemm_rt(int rt) {
-  return rt == 1 ? catalog_gemm_kernel<FMT, 1> : rt == 2 ? catalog_gemm_kernel<FMT, 2> : rt == 4 ? catalog_gemm_kernel<FMT, 4> : nullptr;
+template <int FMT, typename Src>
+CatalogGemmFn<Src> catalog_gemm_rt(int rt) {
+  return rt == 1 ? catalog_gemm_kernel<FMT, 1, Src> : rt == 2 ? catalog_gemm_kernel<FMT, 2, Src> : rt == 4 ? catalog_gemm_kernel<FMT, 4, Src> : nullptr;
 }
-inline CatalogGemmFn catalog_gemm_fn(int fmt, int rt) {
-  return fmt == SERVE_F16 ? catalog_gemm_rt<SERVE_F16>(rt) : fmt == SERVE_F32 ? catalog_gemm_rt<SERVE_F32>(rt) : nullptr;
+template <typename Src = CatalogSlabSrc>
+CatalogGemmFn<Src> catalog_gemm_fn(int fmt, int rt) {
+  return fmt == SERVE_F16 ? catalog_gemm_rt<SERVE_F16, Src>(rt) : fmt == SERVE_F32 ? catalog_gemm_rt<SERVE_F32, Src>(rt) : nullptr;
 }
 // the best K of a catalogue (kernels_catalog_topk.h): <format, request tiles of 32 per launch>.  Request tiles per
 // launch by top_k: the lists of a workgroup (1024 RT Kp bytes, Kp = top_k rounded up to a power of two) stay at or
 // under 32 KB up to K = 32 -- beside the 34 KB of operand tiles that leaves two workgroups per CU -- and are 64 KB at
 // K = 64; more tiles mean fewer passes over the slab, fewer tiles more waves in flight.
-using CatalogTopkFn = void (*)(const char *, const float *, int, CatalogDev, int, int, int64_t, float, int, int, unsigned long long *);
+template <typename Src>
+using CatalogTopkFn = void (*)(const char *, const float *, int, CatalogDev, int, int, int64_t, float, int, int, unsigned long long *,
+                               typename Src::Args);
 inline int catalog_topk_rt(int top_k) { return top_k <= 8 ? 4 : top_k <= 16 ? 2 : 1; }
 inline int catalog_topk_max_k(int rt) { return rt == 4 ? 8 : rt == 2 ? 16 : kTopkMax; }  // the largest top_k a launch of rt tiles sees
-template <int FMT>
-CatalogTopkFn catalog_topk_by_rt(int rt) {
-  return rt == 1 ? catalog_topk_kernel<FMT, 1> : rt == 2 ? catalog_topk_kernel<FMT, 2> : rt == 4 ? catalog_topk_kernel<FMT, 4> : nullptr;
+template <int FMT, typename Src>
+CatalogTopkFn<Src> catalog_topk_by_rt(int rt) {
+  return rt == 1 ? catalog_topk_kernel<FMT, 1, Src> : rt == 2 ? catalog_topk_kernel<FMT, 2, Src> : rt == 4 ? catalog_topk_kernel<FMT, 4, Src> : nullptr;
 }
-inline CatalogTopkFn catalog_topk_fn(int fmt, int rt) {
-  return fmt == SERVE_F16 ? catalog_topk_by_rt<SERVE_F16>(rt) : fmt == SERVE_F32 ? catalog_topk_by_rt<SERVE_F32>(rt) : nullptr;
+template <typename Src = CatalogSlabSrc>
+CatalogTopkFn<Src> catalog_topk_fn(int fmt, int rt) {
+  return fmt == SERVE_F16 ? catalog_topk_by_rt<SERVE_F16, Src>(rt) : fmt == SERVE_F32 ? catalog_topk_by_rt<SERVE_F32, Src>(rt) : nullptr;
+}
+// a catalogue of items of several entries (kernels_catalog_items.h): U and S_c per format; its gemm and top-K kernels
+// are the two families above over CatalogItemSrc -- catalog_gemm_fn<CatalogItemSrc>, catalog_topk_fn<CatalogItemSrc> -- by
+// the same rules (catalog_rt, catalog_topk_rt)
+using CatalogItemsUFn = void (*)(ModelDev, int, const int *, const int *, const int *, const float *, CatalogItemSlots, CatalogDev, int, int);
+using CatalogItemsSelfFn = void (*)(ModelDev, CatalogItemSlots, const int *, int64_t, float *);
+inline CatalogItemsUFn catalog_items_u_fn(int fmt) {
+  return fmt == SERVE_F16 ? catalog_items_u_kernel<SERVE_F16> : fmt == SERVE_F32 ? catalog_items_u_kernel<SERVE_F32> : nullptr;
+}
+inline CatalogItemsSelfFn catalog_items_self_fn(int fmt) {
+  return fmt == SERVE_F16 ? catalog_items_self_kernel<SERVE_F16> : fmt == SERVE_F32 ? catalog_items_self_kernel<SERVE_F32> : nullptr;
 }
 // field ablation (kernels_ablate.h)
-using AblateWaveFn = void (*)(ModelDev, Rows, int *, int, int, float *, double *, int, int);
+using AblateWaveFn =void (*)(ModelDev, Rows, int *, int, int, float *, double *, int, int);
 inline AblateWaveFn ablate_wave_fn(int fmt, int n_factors) {
   switch (n_factors) {
 #define X(K, LPP, VPL, U) case K: return FFM_BY_ANY_FMT(ffm_ablate_wave_kernel, LPP, VPL, U);

@@ -74,43 +74,11 @@ struct CatalogDev {
 typedef _Float16 cat_v8h __attribute__((ext_vector_type(8)));
 typedef float cat_v16f __attribute__((ext_vector_type(16)));
 
-// One wave per request of the padded range [0, cd.rows); kPredRows per workgroup.  A context the row kernel
-// refuses (longer than max_row_nnz or than a wave stages) gets zeros here and its NaN from base.
-template <int FMT>
-__global__ __launch_bounds__(64 * kPredRows) void catalog_u_kernel(ModelDev m, int n_req, const int *ctx_ptr, const int *field,
-                                                                  const int *feat, const float *val, int g, CatalogDev cd,
-                                                                  int max_row_nnz, int lds_cap) {
-  static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int r = wave_uniform(blockIdx.x * kPredRows + wv);
-  if (r >= cd.rows) return;
-  int4 *const E = wave_lds(smem, wv, lds_cap, 0).E;
-  int nv = 0;
-  if (r < n_req) {
-    const int b = wave_uniform(ctx_ptr[r]);
-    const int nnz = wave_uniform(ctx_ptr[r + 1]) - b;
-    if (nnz <= max_row_nnz && nnz <= lds_cap) {
-      float unused = 0.0f;
-      wave_stage_entries(m, feat, field, val, b, nnz, lane, unused, nv, [&](int at, int4 en, float) { E[at] = en; });
-    }
-  }
-  const int k = m.n_factors, L = m.row_len;
-  // element j = f * k + t of U_r: the entries of field f in order, each fl(val * w[id][g * k + t])
-  auto element = [&](int j) {
-    float acc = 0.0f;
-    if (j < L) {
-      const int f = j / k, t = j - f * k;
-      for (int p = 0; p < nv; p++) {
-        const int4 en = E[p];
-        if (en.y != f) continue;
-        const int64_t at = static_cast<int64_t>(en.x) * L + g * k + t;
-        const float w = FMT == SERVE_F16 ? serve_dec16(reinterpret_cast<const unsigned short *>(m.lat)[at]) : m.lat[at];
-        acc = __fadd_rn(acc, __fmul_rn(__int_as_float(en.z), w));
-      }
-    }
-    return acc;
-  };
+// What a wave writes of its request r: element(j) for j < cd.lp (0 from the live length on) as U's row, on f16 as the
+// two planes under the request's one shift.  n_scan: the elements the largest magnitude is looked for among (the rest
+// are zero).
+template <int FMT, typename Element>
+__device__ __forceinline__ void catalog_u_store(Element element, int n_scan, const CatalogDev &cd, int r, int lane) {
   const int64_t row = static_cast<int64_t>(r) * cd.lp;
   if (FMT == SERVE_F32) {
     float *const U = static_cast<float *>(cd.u) + row;
@@ -121,7 +89,7 @@ __global__ __launch_bounds__(64 * kPredRows) void catalog_u_kernel(ModelDev m, i
   // f16: the largest magnitude first, then the same sums again, scaled and split
   float big = 0.0f;
   bool odd = false;  // a NaN or an infinity
-  for (int j = lane; j < L; j += 64) {
+  for (int j = lane; j < n_scan; j += 64) {
     const float u = fabsf(element(j));
     odd = odd || !(u <= 3.4028234664e38f);
     big = fmaxf(big, u);
@@ -142,6 +110,54 @@ __global__ __launch_bounds__(64 * kPredRows) void catalog_u_kernel(ModelDev m, i
     lo[j] = __float2half_rn(__fsub_rn(x, __half2float(h)));
   }
   if (lane == 0) cd.shift[r] = s;
+}
+
+// The context of request r into the wave's LDS (E; *nv survivors).  A context the row kernel refuses (longer than
+// max_row_nnz or than a wave stages) and a row of the padding stage nothing: zeros in U, and the NaN comes from base.
+__device__ __forceinline__ void catalog_stage_context(const ModelDev &m, int r, int n_req, const int *ctx_ptr, const int *field,
+                                                      const int *feat, const float *val, int max_row_nnz, int lds_cap, int lane,
+                                                      int4 *E, int &nv) {
+  if (r >= n_req) return;
+  const int b = wave_uniform(ctx_ptr[r]);
+  const int nnz = wave_uniform(ctx_ptr[r + 1]) - b;
+  if (nnz <= max_row_nnz && nnz <= lds_cap) {
+    float unused = 0.0f;
+    wave_stage_entries(m, feat, field, val, b, nnz, lane, unused, nv, [&](int at, int4 en, float) { E[at] = en; });
+  }
+}
+
+// Element f * k + t of U_r towards field g: the staged entries of field f in order, each fl(val * w[id][g * k + t]).
+template <int FMT>
+__device__ __forceinline__ float catalog_u_element(const ModelDev &m, const int4 *E, int nv, int g, int j) {
+  const int k = m.n_factors, L = m.row_len;
+  float acc = 0.0f;
+  if (j < L) {
+    const int f = j / k, t = j - f * k;
+    for (int p = 0; p < nv; p++) {
+      const int4 en = E[p];
+      if (en.y != f) continue;
+      const int64_t at = static_cast<int64_t>(en.x) * L + g * k + t;
+      const float w = FMT == SERVE_F16 ? serve_dec16(reinterpret_cast<const unsigned short *>(m.lat)[at]) : m.lat[at];
+      acc = __fadd_rn(acc, __fmul_rn(__int_as_float(en.z), w));
+    }
+  }
+  return acc;
+}
+
+// One wave per request of the padded range [0, cd.rows); kPredRows per workgroup.
+template <int FMT>
+__global__ __launch_bounds__(64 * kPredRows) void catalog_u_kernel(ModelDev m, int n_req, const int *ctx_ptr, const int *field,
+                                                                  const int *feat, const float *val, int g, CatalogDev cd,
+                                                                  int max_row_nnz, int lds_cap) {
+  static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int r = wave_uniform(blockIdx.x * kPredRows + wv);
+  if (r >= cd.rows) return;
+  int4 *const E = wave_lds(smem, wv, lds_cap, 0).E;
+  int nv = 0;
+  catalog_stage_context(m, r, n_req, ctx_ptr, field, feat, val, max_row_nnz, lds_cap, lane, E, nv);
+  catalog_u_store<FMT>([&](int j) { return catalog_u_element<FMT>(m, E, nv, g, j); }, m.row_len, cd, r, lane);
 }
 
 // The wave's 16-byte vector of chunk `ch`: row `row4 + 4 it` of its 32, bytes [16 sub, 16 sub + 16) of the chunk.
@@ -168,14 +184,39 @@ __device__ __forceinline__ uint4 catalog_load(const char *tab, int64_t row_bytes
   return v;
 }
 
-// The contraction of one wave: its 32 candidates [c0, c0 + 32) against the RT request tiles from r0 on, every chunk of
-// the row through the wave's own tile T, one chunk prefetched.  acc[t][x] of a lane afterwards: request row
+// ROW SOURCES  Where the B operand's rows come from is a policy of catalog_accumulate and of the two kernels: a slab of
+// one field's ids (CatalogSlabSrc, here: stateless, so the slab's kernels are instruction for instruction what they
+// were before there was a second source) or a table of items of several entries (kernels_catalog_items.h).  A source has
+//   Args                  what its kernels take behind the common arguments (the slab: nothing)
+//   kLdsInts              ints of LDS of its own per wave
+//   Src(args, lds, c0, n_cols, lane)   made when the wave turns to the columns [c0, c0 + 32)
+//   seek(ch)              chunk ch is the next to be loaded (chunks come in order from 0; wave-uniform)
+//   load(tab, row_bytes, c0, row4, it, n_cols, ch, sub, even16)   16 bytes: row row4 + 4 it of the wave's 32, bytes
+//                         [16 sub, 16 sub + 16) of chunk ch -- or zero registers where there is no such row or byte
+//   logit<FMT>(a, v, col, base, shift)   the score of accumulator a; col: the column's own term (lin[c])
+// U's row has the chunks in the source's order: chunk ch pairs with bytes [256 ch, 256 ch + 256) of U_r.
+struct CatalogSlabSrc {
+  struct Args {};
+  static constexpr int kLdsInts = 0;
+  __device__ __forceinline__ CatalogSlabSrc() {}
+  __device__ __forceinline__ CatalogSlabSrc(const Args &, int *, int64_t, int64_t, int) {}
+  __device__ __forceinline__ void seek(int) {}
+  __device__ __forceinline__ uint4 load(const char *tab, int64_t row_bytes, int64_t c0, int row4, int it, int64_t n_cand, int ch, int sub,
+                                        bool even16) const {
+    return catalog_load(tab, row_bytes, c0 + row4 + 4 * it, n_cand, ch * kCatChunkBytes + 16 * sub, even16);
+  }
+  template <int FMT>
+  static __device__ __forceinline__ float logit(float a, float v, float lw, float base, int shift);  // (catalog_logit, below)
+};
+
+// The contraction of one wave: its 32 columns [c0, c0 + 32) against the RT request tiles from r0 on, every chunk of
+// U's row through the wave's own tile T, one chunk prefetched.  acc[t][x] of a lane afterwards: request row
 // 8 (x / 4) + 4 (lane / 32) + x % 4 of tile t, candidate lane % 32.  The sequence of matrix instructions of a tile
 // does not depend on RT: catalog_gemm_kernel and catalog_topk_kernel (kernels_catalog_topk.h) both run this and no
 // other, so a (request, candidate) pair gets the same accumulator bits from either, at any RT.
-template <int FMT, int RT>
+template <int FMT, int RT, typename Src = CatalogSlabSrc>
 __device__ __forceinline__ void catalog_accumulate(const char *tab, int L, const CatalogDev &cd, int r0, int64_t c0, int64_t n_cand,
-                                                   char *T, int lane, cat_v16f (&acc)[RT]) {
+                                                   char *T, int lane, cat_v16f (&acc)[RT], Src src = Src()) {
   constexpr int ES = FMT == SERVE_F16 ? 2 : 4;
   const int64_t row_bytes = static_cast<int64_t>(L) * ES;
   const bool even16 = (row_bytes & 15) == 0;
@@ -189,8 +230,9 @@ __device__ __forceinline__ void catalog_accumulate(const char *tab, int L, const
     for (int x = 0; x < 16; x++) acc[t][x] = 0.0f;
 
   uint4 next[8];
+  src.seek(0);
 #pragma unroll
-  for (int it = 0; it < 8; it++) next[it] = catalog_load(tab, row_bytes, c0 + row4 + 4 * it, n_cand, 16 * sub, even16);
+  for (int it = 0; it < 8; it++) next[it] = src.load(tab, row_bytes, c0, row4, it, n_cand, 0, sub, even16);
 
   const char *const U = static_cast<const char *>(cd.u);
   const int64_t u_row = static_cast<int64_t>(cd.lp) * ES, plane = static_cast<int64_t>(cd.rows) * u_row;
@@ -199,9 +241,9 @@ __device__ __forceinline__ void catalog_accumulate(const char *tab, int L, const
     for (int it = 0; it < 8; it++) *reinterpret_cast<uint4 *>(T + (row4 + 4 * it) * kCatRowBytes + 16 * sub) = next[it];
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     if (ch + 1 < n_chunks) {
+      src.seek(ch + 1);
 #pragma unroll
-      for (int it = 0; it < 8; it++)
-        next[it] = catalog_load(tab, row_bytes, c0 + row4 + 4 * it, n_cand, (ch + 1) * kCatChunkBytes + 16 * sub, even16);
+      for (int it = 0; it < 8; it++) next[it] = src.load(tab, row_bytes, c0, row4, it, n_cand, ch + 1, sub, even16);
     }
 #pragma unroll
     for (int q = 0; q < 8; q++) {
@@ -235,22 +277,28 @@ __device__ __forceinline__ float catalog_logit(float a, float v, float lw, float
   if (FMT == SERVE_F16) a = ldexpf(a, -shift);
   return __fmaf_rn(v, a, __fmaf_rn(v, lw, base));
 }
+template <int FMT>
+__device__ __forceinline__ float CatalogSlabSrc::logit(float a, float v, float lw, float base, int shift) {
+  return catalog_logit<FMT>(a, v, lw, base, shift);
+}
 
 // Requests [r0, r0 + 32 RT) (rows of cd, whole tiles; stores for r < n_req only) against candidates
-// [128 blockIdx.x, ...) of the range's n_cand; tab: row 0 of the range (cand_first's), lin: its lin_w.
-template <int FMT, int RT>
+// [128 blockIdx.x, ...) of the range's n_cand; tab: row 0 of the range (cand_first's), lin: its lin_w.  Over another row
+// source (kernels_catalog_items.h) the columns are its n_cand items, tab the whole table, lin the items' own terms.
+template <int FMT, int RT, typename Src = CatalogSlabSrc>
 __global__ __launch_bounds__(64 * kCatWaves) void catalog_gemm_kernel(const char *tab, const float *lin, int L, CatalogDev cd, int r0,
                                                                      int n_req, int64_t n_cand, float v, int output_prob,
-                                                                     float *out) {
+                                                                     float *out, typename Src::Args args) {
   static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
   static_assert(RT == 1 || RT == 2 || RT == 4, "request tiles per launch");
   __shared__ __attribute__((aligned(16))) char tile[kCatWaves][32 * kCatRowBytes];
+  __shared__ int own[kCatWaves][Src::kLdsInts > 0 ? Src::kLdsInts : 1];  // (unused, and then not allocated, for the slab)
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t c0 = static_cast<int64_t>(blockIdx.x) * kCatCands + wv * 32;  // the wave's first candidate
   if (c0 >= n_cand) return;  // (nothing below waits for another wave)
   const int j = lane & 31, h = lane >> 5;
   cat_v16f acc[RT];
-  catalog_accumulate<FMT, RT>(tab, L, cd, r0, c0, n_cand, tile[wv], lane, acc);
+  catalog_accumulate<FMT, RT>(tab, L, cd, r0, c0, n_cand, tile[wv], lane, acc, Src(args, own[wv], c0, n_cand, lane));
 
   // ---- accumulator x of a lane: request row 8 (x / 4) + 4 (lane / 32) + x % 4 of the tile, candidate lane % 32
   const int64_t c = c0 + j;
@@ -262,7 +310,7 @@ __global__ __launch_bounds__(64 * kCatWaves) void catalog_gemm_kernel(const char
     for (int x = 0; x < 16; x++) {
       const int r = r0 + kCatTile * t + 8 * (x >> 2) + 4 * h + (x & 3);
       if (r >= n_req) continue;
-      const float score = catalog_logit<FMT>(acc[t][x], v, lw, cd.base[r], FMT == SERVE_F16 ? cd.shift[r] : 0);
+      const float score = Src::template logit<FMT>(acc[t][x], v, lw, cd.base[r], FMT == SERVE_F16 ? cd.shift[r] : 0);
       out[static_cast<int64_t>(r) * n_cand + c] = output_prob ? sigmoid_ref(score) : score;
     }
 }

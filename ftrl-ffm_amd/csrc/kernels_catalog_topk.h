@@ -72,15 +72,17 @@ __device__ __forceinline__ unsigned topk_key32(float x) {
 }
 __device__ __forceinline__ float topk_unkey32(unsigned k) { return __uint_as_float((k >> 31) ? k ^ 0x80000000u : ~k); }
 
-// Requests [r0, r0 + 32 RT) against all n_cand candidates of the range; kp: catalog_topk_kp(top_k);
-// part[n_req][gridDim.x * 4][kp].  Dynamic LDS: catalog_topk_lds_bytes(RT, kp).
-template <int FMT, int RT>
+// Requests [r0, r0 + 32 RT) against all n_cand candidates of the range (over another row source: its n_cand columns,
+// as catalog_gemm_kernel); kp: catalog_topk_kp(top_k); part[n_req][gridDim.x * 4][kp].  Dynamic LDS:
+// catalog_topk_lds_bytes(RT, kp).
+template <int FMT, int RT, typename Src = CatalogSlabSrc>
 __global__ __launch_bounds__(64 * kCatWaves) void catalog_topk_kernel(const char *tab, const float *lin, int L, CatalogDev cd, int r0,
                                                                      int n_req, int64_t n_cand, float v, int top_k, int kp,
-                                                                     unsigned long long *part) {
+                                                                     unsigned long long *part, typename Src::Args args) {
   static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
   static_assert(RT == 1 || RT == 2 || RT == 4, "request tiles per launch");
   __shared__ __attribute__((aligned(16))) char tile[kCatWaves][32 * kCatRowBytes];
+  __shared__ int own[kCatWaves][Src::kLdsInts > 0 ? Src::kLdsInts : 1];  // (as catalog_gemm_kernel's)
   extern __shared__ __attribute__((aligned(16))) unsigned long long topk_lists[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int j = lane & 31, h = lane >> 5;
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(64 * kCatWaves) void catalog_topk_kernel(const char
     const int64_t c0 = slab * kCatCands + wv * 32;  // the wave's first candidate of the slab
     if (c0 >= n_cand) break;                        // (its later slabs lie beyond too; the final store still runs)
     cat_v16f acc[RT];
-    catalog_accumulate<FMT, RT>(tab, L, cd, r0, c0, n_cand, T, lane, acc);
+    catalog_accumulate<FMT, RT>(tab, L, cd, r0, c0, n_cand, T, lane, acc, Src(args, own[wv], c0, n_cand, lane));
     const int64_t c = c0 + j;
     const float lw = c < n_cand ? lin[c] : 0.0f;
     const int n_col = static_cast<int>(n_cand - c0 < 32 ? n_cand - c0 : 32);  // columns of the tile that are candidates
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(64 * kCatWaves) void catalog_topk_kernel(const char
 #pragma unroll
       for (int x = 0; x < 16; x++) {
         const int row = 8 * (x >> 2) + 4 * h + (x & 3), q = kCatTile * t + row;
-        if (r0 + q < n_req) S[row * kTopkRowFloats + j] = catalog_logit<FMT>(acc[t][x], v, lw, Bw[q], FMT == SERVE_F16 ? Hw[q] : 0);
+        if (r0 + q < n_req) S[row * kTopkRowFloats + j] = Src::template logit<FMT>(acc[t][x], v, lw, Bw[q], FMT == SERVE_F16 ? Hw[q] : 0);
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       const bool mine = h == 0 && r0 + kCatTile * t + j < n_req;

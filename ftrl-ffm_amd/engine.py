@@ -251,6 +251,19 @@ ABI = [
     ("ffm_engine_score_catalog_topk_device", ctypes.c_int,
      [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
+    # ... and items of several entries (include/ffm_engine.h "Scoring a catalogue: items of several entries");
+    # item_field / item_val are host arrays in the device calls too
+    ("ffm_engine_score_items", ctypes.c_int,
+     [_vp, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, ctypes.c_int32, _i32p, _i32p, _f32p, ctypes.c_int32, ctypes.c_int32, _f32p]),
+    ("ffm_engine_score_items_device", ctypes.c_int,
+     [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, _i32p, _vp, _f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+      ctypes.c_int32, _vp]),
+    ("ffm_engine_score_items_topk", ctypes.c_int,
+     [_vp, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, ctypes.c_int32, _i32p, _i32p, _f32p, ctypes.c_int32, ctypes.c_int32,
+      ctypes.c_int32, _f32p, _i32p]),
+    ("ffm_engine_score_items_topk_device", ctypes.c_int,
+     [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, _i32p, _vp, _f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+      ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     # the fields' cardinalities counted on the device, id ranges sized by them (include/ffm_engine.h "Field sketches")
     ("ffm_engine_sketch_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("ffm_engine_sketch_add", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32]),
@@ -1008,6 +1021,67 @@ def catalog_topk_reference(scores, first, k):
     return out_s.view(np.float32), out_i
 
 
+def _item_table(item_field, item_feat, item_val):
+    """The three arrays of an item table as (int32[m], int32[n_items, m] contiguous, float32[m])."""
+    fld = np.ascontiguousarray(item_field, np.int32).reshape(-1)
+    feat = np.ascontiguousarray(item_feat, np.int32)
+    if feat.ndim != 2 or feat.shape[1] != fld.shape[0]:
+        raise ValueError("item_feat must be [n_items, %d]: one id per slot of item_field" % fld.shape[0])
+    val = np.ones(fld.shape[0], np.float32) if item_val is None else np.ascontiguousarray(item_val, np.float32).reshape(-1)
+    if val.shape != fld.shape:
+        raise ValueError("item_val needs one value per slot")
+    return fld, feat, val
+
+
+def spell_out_items(ctx, item_field, item_feat, item_val=None):
+    """The rows [context entries ..., (g_0, c_0, v_0), ..., (g_{m-1}, c_{m-1}, v_{m-1})] that Engine.score_items scores,
+    request-major: row r * n_items + c is request r against item c (include/ffm_engine.h "Scoring a catalogue: items
+    of several entries" in executable form; numpy only).  A val of None reads as ones; labels are 0."""
+    from .synth import Block
+    fld, feat, val = _item_table(item_field, item_feat, item_val)
+    n_items, m = feat.shape
+    cand = Block((np.arange(ctx.n_rows * n_items + 1, dtype=np.int64) * m).astype(np.int32), np.tile(fld, ctx.n_rows * n_items),
+                 np.tile(feat.reshape(-1), ctx.n_rows), np.tile(val, ctx.n_rows * n_items), np.zeros(ctx.n_rows * n_items, np.int32))
+    return spell_out_candidates(ctx, np.arange(ctx.n_rows + 1, dtype=np.int64) * n_items, cand)
+
+
+def score_items_reference(weights, ctx, item_field, item_feat, item_val=None, n_fields=None):
+    """Engine.score_items' definition (include/ffm_engine.h "Scoring a catalogue: items of several entries") in
+    float64, on the weights get_weights() returns; numpy only.  Returns (ref64, scale), both [n_req, n_items]:
+    ref64 = S_c + sum_a sum_j U_r^a[j] W[c_a][j] and scale = sum_a |v_a lin_w[c_a]| + sum_{a<b} |v_a v_b| sum_t |w w| +
+    sum_a max_j |U_r^a[j]| sum_j |W[c_a][j]|.  A slot whose id lies outside [0, n_feats) is erased.  The score is
+    base_r + ref64, base_r being predict_batch(ctx)."""
+    lin = np.asarray(weights["lin_w"], np.float64)
+    n_feats = lin.shape[0]
+    W = np.asarray(weights["vec_w"], np.float64).reshape(n_feats, -1)
+    L = W.shape[1]
+    if n_fields is None or n_fields <= 0 or L % n_fields:
+        raise ValueError("n_fields must divide the table's row length %d" % L)
+    fld, feat, val = _item_table(item_field, item_feat, item_val)
+    k, m, v = L // n_fields, fld.shape[0], val.astype(np.float64)
+    live = (feat >= 0) & (feat < n_feats)                      # [n_items, m]
+    rows = W[np.where(live, feat, 0)] * live[:, :, None]       # [n_items, m, L]: an erased slot's row reads as zeros
+    lw = lin[np.where(live, feat, 0)] * live
+    cval = np.ones(len(ctx.feat), np.float64) if ctx.val is None else np.asarray(ctx.val, np.float64)
+    U = np.zeros((ctx.n_rows, m, L))
+    for r in range(ctx.n_rows):
+        for p in range(int(ctx.row_ptr[r]), int(ctx.row_ptr[r + 1])):
+            f, i = int(ctx.field[p]), int(ctx.feat[p])
+            if 0 <= i < n_feats and 0 <= f < n_fields:
+                for a in range(m):
+                    U[r, a, f * k:(f + 1) * k] += v[a] * cval[p] * W[i, fld[a] * k:(fld[a] + 1) * k]
+    S = (v[None, :] * lw).sum(axis=1)
+    S_abs = np.abs(v[None, :] * lw).sum(axis=1)
+    for a in range(m):
+        for b in range(a + 1, m):
+            prod = rows[:, a, fld[b] * k:(fld[b] + 1) * k] * rows[:, b, fld[a] * k:(fld[a] + 1) * k]
+            S += v[a] * v[b] * prod.sum(axis=1)
+            S_abs += abs(v[a] * v[b]) * np.abs(prod).sum(axis=1)
+    ref64 = S[None, :] + np.einsum("raj,caj->rc", U, rows)
+    scale = S_abs[None, :] + np.einsum("ra,ca->rc", np.abs(U).max(axis=2, initial=0.0), np.abs(rows).sum(axis=2))
+    return ref64, scale
+
+
 def load_library(path=None):
     """dlopen libffm_engine.so and bind every ABI symbol.  Raises if it is missing."""
     global _lib
@@ -1577,6 +1651,50 @@ class Engine:
         Asynchronous on the engine's stream; sync() reports a too-long context."""
         self._check(self.lib.ffm_engine_score_catalog_topk_device(
             self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, int(field), int(first), int(count), float(val), int(k),
+            int(ctx_nnz), int(ctx_cap), int(output_prob), out_score, out_id))
+
+    def score_items(self, ctx, item_field, item_feat, item_val=None, output_prob=False):
+        """Every request of ctx against the items of a table: item c is the entries (item_field[a], item_feat[c][a],
+        item_val[a]), a < m <= 8, in distinct fields; float32[n_req, n_items] (include/ffm_engine.h "Scoring a
+        catalogue: items of several entries"; score_items_reference is the definition).  An id outside [0, n_feats)
+        erases its slot.  Matrix instructions over the gathered rows; within the header's bound, not bit for bit."""
+        fld, feat, val = _item_table(item_field, item_feat, item_val)
+        out = np.zeros((ctx.n_rows, feat.shape[0]), np.float32)
+        _, cp, cfld, cft, cv, _ = self._csr(ctx)
+        self._check(self.lib.ffm_engine_score_items(self.h, ctx.n_rows, cp, cfld, cft, cv, fld.shape[0], _i(fld), _i(feat), _f(val),
+                                                    feat.shape[0], int(output_prob), _f(out)))
+        return out
+
+    def score_items_device(self, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, item_field, item_feat, item_val, n_items, ctx_nnz,
+                           ctx_cap, output_prob, out):
+        """score_items on arrays already in HBM (device addresses: the contexts, item_feat[n_items][m], out[n_req][n_items]);
+        item_field and item_val (or None) are host arrays of m elements, read by the call.  Asynchronous on the
+        engine's stream; sync() reports a too-long context."""
+        fld = np.ascontiguousarray(item_field, np.int32).reshape(-1)
+        val = None if item_val is None else np.ascontiguousarray(item_val, np.float32).reshape(-1)
+        self._check(self.lib.ffm_engine_score_items_device(
+            self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, fld.shape[0], _i(fld), item_feat, _f(val), int(n_items),
+            int(ctx_nnz), int(ctx_cap), int(output_prob), out))
+
+    def score_items_topk(self, ctx, item_field, item_feat, k, item_val=None, output_prob=False):
+        """The k best items of score_items per request, selected on the device without writing the matrix: (scores
+        float32[n_req, k], ids int32[n_req, k]), best first, an id being the item's index in the table
+        (catalog_topk_reference(score_items(...), 0, k) is the definition; the scores are score_items' bits)."""
+        fld, feat, val = _item_table(item_field, item_feat, item_val)
+        scores = np.zeros((ctx.n_rows, max(int(k), 0)), np.float32)
+        ids = np.zeros((ctx.n_rows, max(int(k), 0)), np.int32)
+        _, cp, cfld, cft, cv, _ = self._csr(ctx)
+        self._check(self.lib.ffm_engine_score_items_topk(self.h, ctx.n_rows, cp, cfld, cft, cv, fld.shape[0], _i(fld), _i(feat), _f(val),
+                                                         feat.shape[0], int(k), int(output_prob), _f(scores), _i(ids)))
+        return scores, ids
+
+    def score_items_topk_device(self, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, item_field, item_feat, item_val, n_items, k,
+                                ctx_nnz, ctx_cap, output_prob, out_score, out_id):
+        """score_items_topk on arrays already in HBM, as score_items_device; out_score / out_id [n_req][k] there too."""
+        fld = np.ascontiguousarray(item_field, np.int32).reshape(-1)
+        val = None if item_val is None else np.ascontiguousarray(item_val, np.float32).reshape(-1)
+        self._check(self.lib.ffm_engine_score_items_topk_device(
+            self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, fld.shape[0], _i(fld), item_feat, _f(val), int(n_items), int(k),
             int(ctx_nnz), int(ctx_cap), int(output_prob), out_score, out_id))
 
     # ---- blocks already in HBM (raw device addresses as ints) ----

@@ -1125,7 +1125,8 @@ int ffm_engine_score_candidates_device(ffm_engine *e, int32_t n_req, const int32
  *   the host call's output) are allocated by the first call, grown to the largest call seen and freed by
  *   ffm_engine_destroy; an engine that never calls this allocates and launches nothing new.  The profile calls label
  *   the kernels "catalog_u_kernel" and "catalog_gemm_kernel".  FFM_ENGINE_ABI_VERSION is what it was.
- * OUT OF SCOPE  the CLI (a follow-up); candidates of more than one entry; LR and FM.  The best K per request: below. */
+ * OUT OF SCOPE  the CLI (a follow-up); LR and FM.  The best K per request: below.  Candidates of more than one entry:
+ *   "Scoring a catalogue: items of several entries" below. */
 int ffm_engine_score_catalog(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
                              const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
                              int32_t n_cand, float cand_val, int32_t output_prob, float *out);
@@ -1173,6 +1174,69 @@ int ffm_engine_score_catalog_topk_device(ffm_engine *e, int32_t n_req, const int
                                          const int32_t *ctx_feat, const float *ctx_val, int32_t cand_field, int32_t cand_first,
                                          int32_t n_cand, float cand_val, int32_t top_k, int32_t ctx_nnz, int32_t ctx_cap,
                                          int32_t output_prob, float *out_score, int32_t *out_id);
+
+/* ---- Scoring a catalogue: items of several entries -------------------------------------------------------
+ * A real ad, product or video is an id together with its advertiser, campaign, category, size: a few entries in
+ * fields of their own.  An ITEM TABLE is three arrays:
+ *   item_field[n_slots]           distinct fields, n_slots = m in [1, 8];
+ *   item_feat[n_items][n_slots]   model ids, row-major;
+ *   item_val[n_slots]             one value per slot, shared by all items; NULL is ones.
+ * With g_a = item_field[a], c_a = item_feat[c][a], v_a = item_val[a], k = n_factors, L = n_fields * k:
+ *   score(r, c) = base_r + S_c + sum_a sum_{j < L} U_r^a[j] * W[c_a][j]
+ *   U_r^a[f * k + t] = v_a * the sum over the context's entries i of field f, in entry order, of fl(val_i * w[id_i][g_a * k + t])
+ *   S_c    = sum_a v_a lin_w[c_a] + sum_{a < b} v_a v_b sum_t w[c_a][g_b * k + t] * w[c_b][g_a * k + t]
+ *   base_r = the bits of ffm_engine_predict_batch on the context row (as ffm_engine_score_catalog).
+ * Up to rounding this is ffm_engine_predict_batch of the row [context ..., (g_0, c_0, v_0), ..., (g_{m-1}, c_{m-1}, v_{m-1})]
+ * (spell_out_items of the Python binding builds those rows).  The contraction is the dense product of the section
+ * above with a B operand gathered row by row from the table (csrc/kernels_catalog_items.h); S_c is computed once per
+ * call and item.
+ * ERASED SLOTS  A slot whose id lies outside [0, n_feats) is erased, as an erased entry of a row is: its table row reads
+ *   as zeros, its linear term is 0 and so is every pair of S_c it is in.  Ids are therefore not range-checked.
+ * CONTRACT  Not bit for bit against the rows.  For finite tables, with N = m L + m + m (m - 1) / 2 * k,
+ *     |score - (base_r + ref64)| <= (N + 32) * 2^-24 * (|base_r| + scale)
+ *   ref64 = S_c plus the contraction in float64; scale = sum_a |v_a lin_w[c_a]| + sum_{a < b} |v_a v_b| sum_t |w w| +
+ *   sum_a max_j |U_r^a[j]| sum_j |W[c_a][j]| (score_items_reference of the Python binding computes both).  N * 2^-24
+ *   is the any-order bound of an fp32 sum of N products; the 32 covers what it covers in the section above and the one
+ *   rounding of v_a into U.  On an f16 engine U's two planes share ONE shift per request over all m blocks.
+ * CONTEXTS  exactly as ffm_engine_score_catalog: erased entries, an empty context, ctx_val == NULL, hashing in the host
+ *   call, a context too long giving NaN for its request alone and FFM_E_CAPACITY.
+ * HASHED IDS  On an engine with FFM_FLAG_HASH_IDS the host calls hash (and fold) item_feat under its slot's field on
+ *   the device behind the copy, as they do the contexts' ids; the device calls take ids as they are.
+ * TOP K  ffm_engine_score_items_topk: keys, ties, slots, NaN handling and the flagged-request rule are those of
+ *   "Scoring a catalogue: the best K" with cand_first = 0: out_id is the item's index in the table, and the scores are
+ *   ffm_engine_score_items' bits for the same request and item.
+ * ffm_engine_score_items / _topk: every array in host memory; synchronous.  item_feat is copied into a buffer of the
+ *   engine's.
+ * ffm_engine_score_items_device / _topk_device: the contexts, item_feat and the outputs are device addresses (values
+ *   required, ids as they are); item_field and item_val are HOST arrays of n_slots elements here too -- the call reads
+ *   and checks them and hands them to the kernels by value; asynchronous on the engine's stream.
+ * All four: the checks of ffm_engine_score_catalog without the range check of ids, and FFM_E_INVALID naming item_field
+ *   for n_slots outside [1, 8], a field outside [0, n_fields) or a field named twice; FFM_E_INVALID for a null array;
+ *   FFM_E_CAPACITY for n_req > max_batch_rows and, in the two matrix calls, n_req * n_items > 2^31 - 1; top_k as above.
+ *   The same engines are REFUSED by name: training, FFM_FLAG_SERVE_F8, a pruned table, a pair mask, FFM_FLAG_NORM_ROWS,
+ *   a group's or a shard's engine.  n_req == 0 or n_items == 0 behave as in the one-entry calls.  The buffers (S_c, the
+ *   host calls' copy of item_feat, U grown to rows * m * Lp) are allocated by the first call, grown to the largest
+ *   call seen and freed by ffm_engine_destroy; an engine that never calls this allocates and launches nothing new.
+ *   The profile calls label the kernels "catalog_items_u_kernel", "catalog_items_self_kernel",
+ *   "catalog_items_gemm_kernel" and "catalog_items_topk_kernel".  FFM_ENGINE_ABI_VERSION is what it was.
+ * OUT OF SCOPE  per-item values; repeated fields in an item; m > 8; FFM_FLAG_SERVE_F8 and pruned tables; the CLI;
+ *   caching S_c across calls; bucketing item values; the factorised form (a slot with few distinct ids scored once per
+ *   id through ffm_engine_score_catalog and added by lookup). */
+int ffm_engine_score_items(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                           const float *ctx_val, int32_t n_slots, const int32_t *item_field, const int32_t *item_feat,
+                           const float *item_val, int32_t n_items, int32_t output_prob, float *out);
+int ffm_engine_score_items_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                  const int32_t *ctx_feat, const float *ctx_val, int32_t n_slots, const int32_t *item_field,
+                                  const int32_t *item_feat, const float *item_val, int32_t n_items, int32_t ctx_nnz,
+                                  int32_t ctx_cap, int32_t output_prob, float *out);
+int ffm_engine_score_items_topk(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                const int32_t *ctx_feat, const float *ctx_val, int32_t n_slots, const int32_t *item_field,
+                                const int32_t *item_feat, const float *item_val, int32_t n_items, int32_t top_k,
+                                int32_t output_prob, float *out_score, int32_t *out_id);
+int ffm_engine_score_items_topk_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                       const int32_t *ctx_feat, const float *ctx_val, int32_t n_slots, const int32_t *item_field,
+                                       const int32_t *item_feat, const float *item_val, int32_t n_items, int32_t top_k,
+                                       int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob, float *out_score, int32_t *out_id);
 
 /* ---- Field ablation: the loss and AUC of the model without each field, in one pass -------------------
  * Which fields earn their place?  The standard answer is the evaluation loss and AUC of the same model with

@@ -138,8 +138,9 @@ def run_catalog(args):
     nf = min(args.n_feats, 4_000_000)
     nf -= nf % N_FIELDS
     g, first, cf = N_FIELDS - 1, 1000, N_FIELDS - 1  # contexts: one entry in each of the other 38 fields
-    eng = fa.Engine("FFM", nf, N_FIELDS, N_FACTORS, max_batch_rows=ROWS, max_batch_nnz=ROWS * N_FIELDS, seed=42,
-                    max_row_nnz=N_FIELDS, serve=args.kind)
+    longest = N_FIELDS + args.catalog_items  # (a spelled-out item row: the context and the item's entries)
+    eng = fa.Engine("FFM", nf, N_FIELDS, N_FACTORS, max_batch_rows=ROWS, max_batch_nnz=ROWS * longest, seed=42,
+                    max_row_nnz=longest, serve=args.kind)
     elem = 2 if args.kind == "f16" else 4
     blk = synth.Generator(N_FIELDS, nf, dist="zipf", seed=42).block(128)
     keep = blk.field != g
@@ -198,7 +199,57 @@ def run_catalog(args):
                 speedup=n_req * n_cand / base_rate * 1e6 / med, checksum=float(out[:n_req * n_cand:4099].double().sum().cpu()))), flush=True)
             for K in args.topk:
                 catalog_topk_line(args, eng, windows, d, out, g, first, cf, n_req, n_cand, K, med)
+    if args.catalog_items:
+        catalog_items_lines(args, eng, windows, d, out, ctx, cf, up, nf)
     eng.close()
+
+
+def catalog_items_lines(args, eng, windows, d, out, ctx, cf, up, nf):
+    """--catalog-items M: 2^20 items of M slots (the last M fields; slot 0's ids distinct, the others drawn from 1000,
+    100, 10, 10, ... ids) through score_items_device and score_items_topk_device (K = 8), beside score_catalog_device on
+    as many candidates and the spelled-out rows (65 536 of them, scaled), per 32 and 128 requests: one JSON line each."""
+    import numpy as np
+    import torch
+    import ftrl_ffm_amd as fa
+    M, n_items, K = args.catalog_items, 1 << 20, 8
+    per = nf // N_FIELDS
+    rng = np.random.default_rng(42)
+    fld = np.arange(N_FIELDS - M, N_FIELDS, dtype=np.int32)[::-1].copy()  # slot 0: the catalogue's own field
+    pool = [n_items] + [max(1, 1000 // 10 ** a) for a in range(M - 1)]
+    feat = np.stack([1000 + np.arange(n_items) if a == 0 else fld[a] * per + rng.integers(pool[a], size=n_items) for a in range(M)],
+                    axis=1).astype(np.int32)
+    d_feat = up(feat)
+    ptrs = [t.data_ptr() for t in d]
+    score = torch.zeros(128 * K, dtype=torch.float32, device="cuda")
+    ids = torch.zeros(128 * K, dtype=torch.int32, device="cuda")
+    blocks, turn = [], [0]
+    for b in range(8):  # 65 536 spelled-out rows as blocks of 8192, cycled
+        sp = fa.spell_out_items(ctx.rows(b, b + 1), fld, feat[b * ROWS:(b + 1) * ROWS])
+        blocks.append((int(sp.row_ptr[-1]), [up(a) for a in (sp.row_ptr, sp.field, sp.feat, sp.val)]))
+
+    def spelled():
+        nnz, a = blocks[turn[0] % len(blocks)]
+        turn[0] += 1
+        eng.predict_batch_device(ROWS, nnz, a[0].data_ptr(), a[1].data_ptr(), a[2].data_ptr(), a[3].data_ptr(), None, 0, out.data_ptr(), None)
+    spelled_us = windows(spelled)
+    rate = ROWS / (spelled_us[len(spelled_us) // 2] * 1e-6)
+    for n_req in (32, 128):
+        cells = dict(
+            score_items_device=lambda: eng.score_items_device(n_req, *ptrs, fld, d_feat.data_ptr(), None, n_items, n_req * cf, cf, 0,
+                                                              out.data_ptr()),
+            score_items_topk_device=lambda: eng.score_items_topk_device(n_req, *ptrs, fld, d_feat.data_ptr(), None, n_items, K, n_req * cf,
+                                                                        cf, 0, score.data_ptr(), ids.data_ptr()),
+            score_catalog_device=lambda: eng.score_catalog_device(n_req, *ptrs, N_FIELDS - 1, 1000, n_items, 1.0, n_req * cf, cf, 0,
+                                                                  out.data_ptr()))
+        res = dict(catalog_items=M, kind=args.kind, n_req=n_req, n_items=n_items, top_k=K)
+        for name, call in cells.items():
+            us = windows(call, window=max(args.window, 0.3))
+            res[name + "_us"] = dict(median=round(us[len(us) // 2], 1), min=round(us[0], 1), max=round(us[-1], 1))
+        res["rows_us_for_the_same_scores"] = round(n_req * n_items / rate * 1e6, 1)
+        res["rows_scores_per_s"] = rate
+        res["items_over_catalog"] = res["score_items_device_us"]["median"] / res["score_catalog_device_us"]["median"]
+        res["items_scores_per_s"] = n_req * n_items / (res["score_items_device_us"]["median"] * 1e-6)
+        print("SERVE_BENCH " + json.dumps(res), flush=True)
 
 
 def catalog_topk_line(args, eng, windows, d, out, g, first, cf, n_req, n_cand, K, matrix_us):
@@ -495,6 +546,9 @@ def main():
     ap.add_argument("--topk", type=int, nargs="*", default=[], metavar="K",
                     help="with --catalog: also the best K per request (score_catalog_topk_device) against the matrix call "
                          "followed by torch.topk")
+    ap.add_argument("--catalog-items", type=int, default=0, metavar="M",
+                    help="with --catalog: also items of M slots (score_items_device, its top 8) against score_catalog_device on as "
+                         "many candidates and against spelled-out rows, in the same process (profiles/score_items.md)")
     args = ap.parse_args()
     if args.catalog:
         if args.kind not in ("f32", "f16"):
