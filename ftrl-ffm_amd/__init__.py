@@ -7,7 +7,7 @@ from .engine import (ABI, FFM, FM, LR, METRIC_BINS, METRIC_EVAL, METRIC_TRAIN, C
                      EngineError, FieldSketch, Group, KeyedMetrics, LIB_PATH, Metrics, default_batch_ramp, hash_ids, init_weights_host,
                      keyed_auc_reference, metrics_from_keyed,
                      load_library, metrics_from_histogram, page_aligned, shard_plan, sketch_estimate, field_ranges, spell_out_candidates, score_catalog_reference, catalog_topk_reference, drop_field,
-                     spell_out_items, score_items_reference,
+                     spell_out_items, score_items_reference, factor_items, expand_items,
                      pair_count, pair_index, pair_fields, drop_pair_weights, pair_mask, pair_mask_pairs, pair_mask_top, pair_curve_levels, pair_curve_mask,
                      pruned_layout, prune_rows,
                      IdCounter, RARE_ID, fold_rare, rare_slot,

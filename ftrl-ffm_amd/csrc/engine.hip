@@ -54,6 +54,7 @@
 #include "kernels_catalog.h"
 #include "kernels_catalog_topk.h"
 #include "kernels_catalog_items.h"
+#include "kernels_catalog_dict.h"
 #include "kernels_delta.h"
 #include "kernels_ablate.h"
 #include "kernels_ablate_pairs.h"
@@ -133,6 +134,7 @@ enum KernelId {
   K_PREDICT_ROW, K_REFRESH, K_LATENT_UPDATE_SINGLE, K_METRIC, K_PUSH_SCORES, K_SERVE_ROW,
   K_SERVE_CTX, K_SERVE_CAND, K_CATALOG_U, K_CATALOG_GEMM, K_CATALOG_TOPK, K_CATALOG_TOPK_MERGE,
   K_CATALOG_ITEMS_U, K_CATALOG_ITEMS_SELF, K_CATALOG_ITEMS_GEMM, K_CATALOG_ITEMS_TOPK,
+  K_CATALOG_DICT_U, K_CATALOG_DICT, K_CATALOG_DICT_SELF, K_CATALOG_DICT_GEMM, K_CATALOG_DICT_TOPK,
   K_KEYED_CAPTURE, K_KEYED_SORT_HIST, K_KEYED_SORT_SCAN, K_KEYED_SORT_SCATTER, K_KEYED_RANK,
   K_UPLOAD, K_NORM_ROWS,
   K_COUNT
@@ -144,6 +146,7 @@ const char *kKernelNames[K_COUNT] = {
     "serve_context_kernel", "serve_candidate_kernel", "catalog_u_kernel", "catalog_gemm_kernel",
     "catalog_topk_kernel", "catalog_topk_merge_kernel",
     "catalog_items_u_kernel", "catalog_items_self_kernel", "catalog_items_gemm_kernel", "catalog_items_topk_kernel",
+    "catalog_dict_u_kernel", "catalog_dict_kernel", "catalog_dict_self_kernel", "catalog_dict_gemm_kernel", "catalog_dict_topk_kernel",
     "keyed_capture_kernel", "keyed_sort_hist_kernel", "keyed_sort_scan_kernels", "keyed_sort_scatter_kernel", "keyed_rank_kernels",
     "pull_block_kernel", "normalize_rows_kernel"};
 
@@ -475,6 +478,14 @@ struct ffm_engine {
   float *item_s = nullptr;
   int *d_item_feat = nullptr, *d_item_field = nullptr;
   size_t item_s_cap = 0, item_feat_cap = 0, item_field_cap = 0;
+  // ffm_engine_score_items_dict[_topk][_device] (include/ffm_engine.h "Scoring a catalogue: dictionary slots"): the
+  // dictionary slots' U blocks (bytes) and shifts [n_dict][rows], the partial scores P [columns][rows], and the host
+  // calls' copies of item_code and dict_feat with the fields of dict_feat's entries beside it (hashing engines alone);
+  // made and grown like the arrays above
+  char *dict_u = nullptr;
+  int *dict_shift = nullptr, *d_item_code = nullptr, *d_dict_feat = nullptr, *d_dict_field = nullptr;
+  float *dict_p = nullptr;
+  size_t dict_u_cap = 0, dict_shift_cap = 0, dict_p_cap = 0, item_code_cap = 0, dict_feat_cap = 0, dict_field_cap = 0;
   // field and pair ablation (include/ffm_engine.h "Field ablation", "Pair ablation"; engine_ablate.h), each set all
   // made by its enable call for its V variants -- n_fields + 1, or n_fields (n_fields + 1) / 2 + 1 --: out [V][max_rows]
   // scores and loss the same shape (the kernel's variant-major outputs), sums [V], part [V][kLossParts + 1] the loss

@@ -3,7 +3,9 @@
 // they grow, and the launches -- the engine's own row kernel over the contexts (base), catalog_u_kernel, then either
 // catalog_gemm_kernel per 128 requests or catalog_topk_kernel per 32 RT requests and catalog_topk_merge_kernel.
 // The same launches serve a table of items of several entries ("... items of several entries",
-// kernels_catalog_items.h): S_c per item first, U towards every slot's field, the kernels over CatalogItems.
+// kernels_catalog_items.h): S_c per item first, U towards every slot's field, the kernels over CatalogItemSrc -- and a
+// table whose last slots are dictionary slots ("... dictionary slots", kernels_catalog_dict.h): the dictionary slots' U
+// and partial scores between U and the kernels, which then run over CatalogDictSrc.
 // Part of engine.hip's translation unit (included inside its extern "C" block).
 
 // The engines every call of this file refuses, by name; what: "score_catalog" or "score_items".
@@ -59,6 +61,16 @@ struct ItemTable {
   int32_t n_items;
 };
 
+// An item table whose last slots are dictionary slots (kernels_catalog_dict.h): items holds the gathered slots alone
+// (feat [n_items][items.slots.n]); code [n_items][dd.n] and dict_feat in device memory.
+struct DictTable {
+  ItemTable items;
+  CatalogItemSlots all;     // every slot, the gathered ones first: S_c
+  CatalogItemSlots dslots;  // the dictionary slots alone: their U
+  CatalogDicts dd;
+  const int32_t *code, *dict_feat;
+};
+
 // What both kinds of launches start with, on arrays in device memory: base and U of the requests, padded to `rows`
 // (whole tiles of the launches that follow).  cap: the longest context, in [1, max_row_nnz].  items: U towards every
 // slot's field, one block behind the other, instead of towards g.
@@ -102,20 +114,66 @@ static CatalogItemSrc::Args catalog_items_args(const ffm_engine *e, const ItemTa
   return CatalogItemSrc::Args{items.feat, e->m.n_feats, items.slots.n, cd.lp / items.slots.n * es / kCatChunkBytes};
 }
 
-// items: the columns are its n_cand items (g, first and v unused, first == 0), else the range's candidates.
+// ---- dictionary slots (include/ffm_engine.h "Scoring a catalogue: dictionary slots"; kernels_catalog_dict.h) ---------
+
+// S_c of every item of a table with dictionary slots into e->item_s.
+static int catalog_dict_self(ffm_engine *e, const DictTable &t) {
+  if (int rc = e->grow(&e->item_s, &e->item_s_cap, static_cast<size_t>(t.items.n_items))) return rc;
+  const int grid = static_cast<int>((static_cast<int64_t>(t.items.n_items) * 4 + 255) / 256);
+  LAUNCH(e, K_CATALOG_DICT_SELF, catalog_dict_self_fn(e->m.lat_fmt), grid, 256, 0, e->m, t.all, t.items.slots.n, t.items.feat, t.code, t.dd,
+         t.dict_feat, static_cast<int64_t>(t.items.n_items), e->item_s);
+  return FFM_OK;
+}
+
+// U of the dictionary slots and the partial scores P of every dictionary entry against the `rows` padded requests
+// (the rows of the launches that follow: whole tiles), into e->dict_p [t.dd.col[t.dd.n]][rows].
+static int catalog_dict_partials(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                                 const float *ctx_val, int cap, const DictTable &t, int rows) {
+  const ModelDev &m = e->m;
+  const int lp = catalog_lp(m.lat_fmt, m.row_len), nd = t.dd.n, cols = t.dd.col[nd];
+  int rc;
+  if ((rc = e->grow(&e->dict_u, &e->dict_u_cap, static_cast<size_t>(nd) * rows * lp * 4))) return rc;
+  if ((rc = e->grow(&e->dict_shift, &e->dict_shift_cap, static_cast<size_t>(nd) * rows))) return rc;
+  if ((rc = e->grow(&e->dict_p, &e->dict_p_cap, std::max<size_t>(1, static_cast<size_t>(cols) * rows)))) return rc;
+  if (cols == 0) return FFM_OK;  // (empty dictionaries: every code is erased, and P is never read)
+  const CatalogDev cd0{nullptr, e->dict_u, e->dict_shift, rows, lp};
+  const int lds_cap = std::min(cap, kPredLdsCap);
+  LAUNCH(e, K_CATALOG_DICT_U, catalog_dict_u_fn(m.lat_fmt), cdiv(rows * nd, kPredRows), 64 * kPredRows, cand_ctx_lds_bytes(lds_cap), m, n_req,
+         ctx_ptr, ctx_field, ctx_feat, ctx_val, t.dslots, cd0, cap, lds_cap);
+  for (int r0 = 0; r0 < rows;) {
+    const int rt = catalog_dict_rt((rows - r0) / kCatTile);
+    LAUNCH(e, K_CATALOG_DICT, catalog_dict_fn(m.lat_fmt, rt), cdiv(cols, kCatCands), 64 * kCatWaves, 0, reinterpret_cast<const char *>(m.lat),
+           m.row_len, cd0, r0, t.dd, t.dict_feat, m.n_feats, e->dict_p);
+    r0 += kCatTile * rt;
+  }
+  return FFM_OK;
+}
+
+// What the dictionary source takes behind the kernels' common arguments; cd: the gathered slots' (catalog_prepare).
+static CatalogDictSrc::Args catalog_dict_args(const ffm_engine *e, const DictTable &t, const CatalogDev &cd) {
+  return CatalogDictSrc::Args{catalog_items_args(e, t.items, cd), t.code, e->dict_p, t.dd, cd.rows};
+}
+
+// items: the columns are its n_cand items (g, first and v unused, first == 0), else the range's candidates.  dict: the
+// items' table has dictionary slots (items == &dict->items then).
 static int catalog_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
                           const float *ctx_val, int32_t ctx_nnz, int cap, int32_t g, int32_t first, int32_t n_cand, float v,
-                          const ItemTable *items, int32_t output_prob, float *out) {
+                          const ItemTable *items, const DictTable *dict, int32_t output_prob, float *out) {
   const ModelDev &m = e->m;
   const int L = m.row_len, es = m.lat_fmt == SERVE_F16 ? 2 : 4;
   CatalogDev cd;
-  if (int rc = items ? catalog_items_self(e, *items) : FFM_OK) return rc;
+  if (int rc = dict ? catalog_dict_self(e, *dict) : items ? catalog_items_self(e, *items) : FFM_OK) return rc;
   if (int rc = catalog_prepare(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, g, items, catalog_rows(n_req), &cd)) return rc;
+  if (int rc = dict ? catalog_dict_partials(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, cap, *dict, cd.rows) : FFM_OK) return rc;
   const char *const tab = reinterpret_cast<const char *>(m.lat) + static_cast<int64_t>(first) * L * es;
   const int grid = static_cast<int>((static_cast<int64_t>(n_cand) + kCatCands - 1) / kCatCands);
   for (int r0 = 0; r0 < n_req; r0 += 128) {
     const int rt = catalog_rt(cdiv(std::min(128, n_req - r0), kCatTile));
-    if (items)
+    if (dict)
+      LAUNCH(e, K_CATALOG_DICT_GEMM, catalog_gemm_fn<CatalogDictSrc>(m.lat_fmt, rt), grid, 64 * kCatWaves, 0, tab,
+             static_cast<const float *>(e->item_s), L, cd, r0, n_req, static_cast<int64_t>(n_cand), 1.0f, output_prob, out,
+             catalog_dict_args(e, *dict, cd));
+    else if (items)
       LAUNCH(e, K_CATALOG_ITEMS_GEMM, catalog_gemm_fn<CatalogItemSrc>(m.lat_fmt, rt), grid, 64 * kCatWaves, 0, tab,
              static_cast<const float *>(e->item_s), L, cd, r0, n_req, static_cast<int64_t>(n_cand), 1.0f, output_prob, out,
              catalog_items_args(e, *items, cd));
@@ -173,7 +231,7 @@ int ffm_engine_score_catalog_device(ffm_engine *e, int32_t n_req, const int32_t 
   // (a context beyond the engine's row limit is flagged by the row kernel whatever the cap says)
   const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
   return catalog_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, cand_field, cand_first, n_cand, cand_val,
-                        nullptr, output_prob, out);
+                        nullptr, nullptr, output_prob, out);
 }
 
 int ffm_engine_score_catalog(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
@@ -189,7 +247,7 @@ int ffm_engine_score_catalog(ffm_engine *e, int32_t n_req, const int32_t *ctx_pt
   if ((rc = e->grow(&e->cat_out, &e->cat_out_cap, n_out))) return rc;  // (before anything is queued)
   if ((rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap))) return rc;
   rc = catalog_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, cand_field, cand_first, n_cand,
-                      cand_val, nullptr, output_prob, e->cat_out);
+                      cand_val, nullptr, nullptr, output_prob, e->cat_out);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, e->cat_out, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
   return check_device_errors(e);
@@ -209,11 +267,19 @@ static int catalog_topk_tiles(int n_req, int r0, int top_k) {
   return std::min(catalog_topk_rt(top_k), catalog_rt(cdiv(n_req - r0, kCatTile)));
 }
 
-// The launches, on arrays in device memory; out_score / out_id [n_req][top_k] there too.  n_req > 0.  items: as
+// The requests of a top-K call in whole tiles of its launches.
+static int catalog_topk_rows(int n_req, int top_k) {
+  int rows = 0;
+  while (rows < n_req) rows += kCatTile * catalog_topk_tiles(n_req, rows, top_k);
+  return rows;
+}
+
+// The launches, on arrays in device memory; out_score / out_id [n_req][top_k] there too.  n_req > 0.  items, dict: as
 // catalog_launch.
 static int catalog_topk_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
                                const float *ctx_val, int32_t ctx_nnz, int cap, int32_t g, int32_t first, int32_t n_cand, float v,
-                               const ItemTable *items, int32_t top_k, int32_t output_prob, float *out_score, int32_t *out_id) {
+                               const ItemTable *items, const DictTable *dict, int32_t top_k, int32_t output_prob, float *out_score,
+                               int32_t *out_id) {
   const ModelDev &m = e->m;
   const int kp = catalog_topk_kp(top_k);
   if (n_cand == 0) {  // nothing to rank: the fill alone
@@ -223,20 +289,24 @@ static int catalog_topk_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_
     return FFM_OK;
   }
   const int L = m.row_len, es = m.lat_fmt == SERVE_F16 ? 2 : 4;
-  int rows = 0;
-  while (rows < n_req) rows += kCatTile * catalog_topk_tiles(n_req, rows, top_k);
+  const int rows = catalog_topk_rows(n_req, top_k);
   const int64_t slabs = (static_cast<int64_t>(n_cand) + kCatCands - 1) / kCatCands;
   const int grid = static_cast<int>(std::min<int64_t>(slabs, e->grid_catalog > 0 ? e->grid_catalog : 2 * e->cu_count));
   const int64_t P = static_cast<int64_t>(grid) * kCatWaves;
   int rc;
   if ((rc = e->grow(&e->topk_part, &e->topk_part_cap, static_cast<size_t>(n_req) * P * kp))) return rc;
   CatalogDev cd;
-  if (items && (rc = catalog_items_self(e, *items))) return rc;
+  if ((rc = dict ? catalog_dict_self(e, *dict) : items ? catalog_items_self(e, *items) : FFM_OK)) return rc;
   if ((rc = catalog_prepare(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, g, items, rows, &cd))) return rc;
+  if (dict && (rc = catalog_dict_partials(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, cap, *dict, rows))) return rc;
   const char *const tab = reinterpret_cast<const char *>(m.lat) + static_cast<int64_t>(first) * L * es;
   for (int r0 = 0; r0 < n_req;) {
     const int rt = catalog_topk_tiles(n_req, r0, top_k);
-    if (items)
+    if (dict)
+      LAUNCH(e, K_CATALOG_DICT_TOPK, catalog_topk_fn<CatalogDictSrc>(m.lat_fmt, rt), grid, 64 * kCatWaves, catalog_topk_lds_bytes(rt, kp), tab,
+             static_cast<const float *>(e->item_s), L, cd, r0, n_req, static_cast<int64_t>(n_cand), 1.0f, top_k, kp, e->topk_part,
+             catalog_dict_args(e, *dict, cd));
+    else if (items)
       LAUNCH(e, K_CATALOG_ITEMS_TOPK, catalog_topk_fn<CatalogItemSrc>(m.lat_fmt, rt), grid, 64 * kCatWaves, catalog_topk_lds_bytes(rt, kp), tab,
              static_cast<const float *>(e->item_s), L, cd, r0, n_req, static_cast<int64_t>(n_cand), 1.0f, top_k, kp, e->topk_part,
              catalog_items_args(e, *items, cd));
@@ -263,7 +333,7 @@ int ffm_engine_score_catalog_topk_device(ffm_engine *e, int32_t n_req, const int
     return fail(FFM_E_INVALID, "null array");
   const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
   return catalog_topk_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, cand_field, cand_first, n_cand, cand_val,
-                             nullptr, top_k, output_prob, out_score, out_id);
+                             nullptr, nullptr, top_k, output_prob, out_score, out_id);
 }
 
 int ffm_engine_score_catalog_topk(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
@@ -280,7 +350,7 @@ int ffm_engine_score_catalog_topk(ffm_engine *e, int32_t n_req, const int32_t *c
   int cap = 1;
   if (n_cand > 0 && (rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap))) return rc;
   rc = catalog_topk_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, cand_field, cand_first,
-                           n_cand, cand_val, nullptr, top_k, output_prob, e->topk_score, e->topk_id);
+                           n_cand, cand_val, nullptr, nullptr, top_k, output_prob, e->topk_score, e->topk_id);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out_score, e->topk_score, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(out_id, e->topk_id, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, e->stream));
@@ -348,7 +418,7 @@ int ffm_engine_score_items_device(ffm_engine *e, int32_t n_req, const int32_t *c
   if (ctx_nnz < 0 || ctx_cap < 0) return fail(FFM_E_INVALID, "negative ctx_nnz / ctx_cap");
   if (!ctx_ptr || !out || !item_feat || (ctx_nnz > 0 && (!ctx_field || !ctx_feat || !ctx_val))) return fail(FFM_E_INVALID, "null array");
   const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
-  return catalog_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, output_prob, out);
+  return catalog_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, nullptr, output_prob, out);
 }
 
 int ffm_engine_score_items(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
@@ -364,7 +434,7 @@ int ffm_engine_score_items(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr,
   int cap = 1;
   if ((rc = e->grow(&e->cat_out, &e->cat_out_cap, n_out))) return rc;  // (before anything is queued)
   if ((rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap)) || (rc = items_stage(e, &t))) return rc;
-  rc = catalog_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, output_prob,
+  rc = catalog_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, nullptr, output_prob,
                       e->cat_out);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, e->cat_out, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
@@ -390,7 +460,7 @@ int ffm_engine_score_items_topk_device(ffm_engine *e, int32_t n_req, const int32
   if (!out_score || !out_id || (n_items > 0 && (!ctx_ptr || !item_feat || (ctx_nnz > 0 && (!ctx_field || !ctx_feat || !ctx_val)))))
     return fail(FFM_E_INVALID, "null array");
   const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
-  return catalog_topk_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, top_k, output_prob,
+  return catalog_topk_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, nullptr, top_k, output_prob,
                              out_score, out_id);
 }
 
@@ -409,8 +479,164 @@ int ffm_engine_score_items_topk(ffm_engine *e, int32_t n_req, const int32_t *ctx
   int cap = 1;
   if (n_items > 0 && ((rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap)) || (rc = items_stage(e, &t))))
     return rc;
-  rc = catalog_topk_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, top_k,
+  rc = catalog_topk_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t, nullptr, top_k,
                            output_prob, e->topk_score, e->topk_id);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out_score, e->topk_score, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_id, e->topk_id, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, e->stream));
+  return check_device_errors(e);
+}
+
+// ---- dictionary slots: the entry points (include/ffm_engine.h "Scoring a catalogue: dictionary slots") ---------------
+
+// items_check's checks over all n_gather + n_dict slots, the counts and dict_ptr, and the table into *t (t->items.feat,
+// t->code, t->dict_feat: the arrays as they came).  top_k: 0 for the matrix calls (it decides the padded requests, and
+// with them the size of P).
+static int dict_check(ffm_engine *e, int32_t n_req, int32_t n_gather, int32_t n_dict, const int32_t *item_field, const int32_t *item_feat,
+                      const int32_t *item_code, const int32_t *dict_ptr, const int32_t *dict_feat, const float *item_val, int32_t n_items,
+                      int32_t top_k, DictTable *t) {
+  if (int rc = catalog_engine_check(e, "score_items_dict")) return rc;
+  if (n_gather < 1) return fail(FFM_E_INVALID, "n_gather " + std::to_string(n_gather) + " lies below 1: ffm_engine_score_catalog scores a lone dictionary");
+  if (n_dict < 1) return fail(FFM_E_INVALID, "n_dict " + std::to_string(n_dict) + " lies below 1: ffm_engine_score_items scores a table without dictionaries");
+  ItemTable all;
+  const int32_t n_slots = static_cast<int32_t>(std::min<int64_t>(static_cast<int64_t>(n_gather) + n_dict, kItemSlots + 1));
+  if (int rc = items_check(e, n_req, n_slots, item_field, item_feat, item_val, n_items, &all)) return rc;
+  if (!dict_ptr) return fail(FFM_E_INVALID, "null array (dict_ptr)");
+  if (int rc = cand_check_ptr(dict_ptr, n_dict, "dict_ptr")) return rc;
+  *t = DictTable{};
+  t->all = all.slots;
+  t->items = all;
+  t->items.slots.n = n_gather;
+  t->dslots.n = t->dd.n = n_dict;
+  int64_t cols = 0;
+  for (int a = 0; a <= n_dict; a++) {
+    t->dd.ptr[a] = dict_ptr[a];
+    t->dd.col[a] = static_cast<int>(std::min<int64_t>(cols, 2147483647ll));
+    if (a == n_dict) break;
+    t->dslots.field[a] = all.slots.field[n_gather + a];
+    t->dslots.val[a] = all.slots.val[n_gather + a];
+    cols += (static_cast<int64_t>(dict_ptr[a + 1]) - dict_ptr[a] + 31) / 32 * 32;
+  }
+  t->code = item_code;
+  t->dict_feat = dict_feat;
+  const int rows = top_k > 0 ? catalog_topk_rows(n_req, std::min(top_k, kTopkMax)) : catalog_rows(n_req);
+  if (cols * std::max(rows, 1) > 2147483647ll)
+    return fail(FFM_E_CAPACITY, "the padded requests times the dictionaries' padded entries exceed 2^31 - 1 partial scores: split the requests");
+  return FFM_OK;
+}
+
+// The host calls' item_feat, item_code and dict_feat into the engine's copies (t's three arrays: in host memory on entry,
+// the copies afterwards), behind one another on the engine's stream; on an engine with FFM_FLAG_HASH_IDS item_feat is
+// hashed under its slots' fields (items_stage) and dict_feat under each dictionary's field.
+static int dict_stage(ffm_engine *e, DictTable *t) {
+  int rc;
+  if ((rc = items_stage(e, &t->items))) return rc;
+  const size_t n_code = static_cast<size_t>(t->items.n_items) * t->dd.n, n_ids = static_cast<size_t>(t->dd.ptr[t->dd.n]);
+  if ((rc = e->grow(&e->d_item_code, &e->item_code_cap, std::max<size_t>(1, n_code)))) return rc;
+  if ((rc = e->grow(&e->d_dict_feat, &e->dict_feat_cap, std::max<size_t>(1, n_ids)))) return rc;
+  if (e->hash_ids && (rc = e->grow(&e->d_dict_field, &e->dict_field_cap, std::max<size_t>(1, n_ids)))) return rc;
+  hipStream_t st = e->stream;
+  HIP_TRY(hipMemcpyAsync(e->d_item_code, t->code, sizeof(int32_t) * n_code, hipMemcpyHostToDevice, st));
+  if (n_ids > 0) {
+    HIP_TRY(hipMemcpyAsync(e->d_dict_feat, t->dict_feat, sizeof(int32_t) * n_ids, hipMemcpyHostToDevice, st));
+    if (e->hash_ids) {  // under each dictionary's field; codes are positions, never hashed
+      hipLaunchKernelGGL(catalog_dict_fields_kernel, dim3(static_cast<unsigned>(std::min<size_t>(1024, (n_ids + 255) / 256))), dim3(256), 0, st,
+                         t->dslots, t->dd, static_cast<int>(n_ids), e->d_dict_field);
+      launch_hash_ids(e, st, static_cast<int32_t>(n_ids), e->d_dict_field, e->d_dict_feat, e->d_dict_feat);
+    }
+  }
+  t->code = e->d_item_code;
+  t->dict_feat = e->d_dict_feat;
+  return FFM_OK;
+}
+
+// (dict_feat may be null when every dictionary is empty)
+static bool dict_arrays_null(const DictTable &t) { return !t.items.feat || !t.code || (t.dd.ptr[t.dd.n] > 0 && !t.dict_feat); }
+
+int ffm_engine_score_items_dict_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                       const int32_t *ctx_feat, const float *ctx_val, int32_t n_gather, int32_t n_dict,
+                                       const int32_t *item_field, const int32_t *item_feat, const int32_t *item_code,
+                                       const int32_t *dict_ptr, const int32_t *dict_feat, const float *item_val, int32_t n_items,
+                                       int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob, float *out) {
+  DictTable t;
+  if (int rc = dict_check(e, n_req, n_gather, n_dict, item_field, item_feat, item_code, dict_ptr, dict_feat, item_val, n_items, 0, &t)) return rc;
+  if (int rc = catalog_matrix_check(n_req, n_items)) return rc;
+  if (int rc = catalog_ready(e)) return rc;
+  if (n_req == 0 || n_items == 0) return FFM_OK;
+  if (ctx_nnz < 0 || ctx_cap < 0) return fail(FFM_E_INVALID, "negative ctx_nnz / ctx_cap");
+  if (!ctx_ptr || !out || dict_arrays_null(t) || (ctx_nnz > 0 && (!ctx_field || !ctx_feat || !ctx_val))) return fail(FFM_E_INVALID, "null array");
+  const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
+  return catalog_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t.items, &t, output_prob, out);
+}
+
+int ffm_engine_score_items_dict(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                                const float *ctx_val, int32_t n_gather, int32_t n_dict, const int32_t *item_field,
+                                const int32_t *item_feat, const int32_t *item_code, const int32_t *dict_ptr, const int32_t *dict_feat,
+                                const float *item_val, int32_t n_items, int32_t output_prob, float *out) {
+  DictTable t;
+  int rc = dict_check(e, n_req, n_gather, n_dict, item_field, item_feat, item_code, dict_ptr, dict_feat, item_val, n_items, 0, &t);
+  if (rc || (rc = catalog_matrix_check(n_req, n_items)) || (rc = catalog_ready(e))) return rc;
+  if (n_req == 0 || n_items == 0) return FFM_OK;
+  if (!out || dict_arrays_null(t)) return fail(FFM_E_INVALID, "null array");
+  const size_t n_out = static_cast<size_t>(n_req) * n_items;
+  int32_t ctx_nnz = 0;
+  int cap = 1;
+  if ((rc = e->grow(&e->cat_out, &e->cat_out_cap, n_out))) return rc;  // (before anything is queued)
+  if ((rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap)) || (rc = dict_stage(e, &t))) return rc;
+  rc = catalog_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t.items, &t,
+                      output_prob, e->cat_out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, e->cat_out, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
+  return check_device_errors(e);
+}
+
+static int dict_topk_check(ffm_engine *e, int32_t n_req, int32_t n_gather, int32_t n_dict, const int32_t *item_field,
+                           const int32_t *item_feat, const int32_t *item_code, const int32_t *dict_ptr, const int32_t *dict_feat,
+                           const float *item_val, int32_t n_items, int32_t top_k, DictTable *t) {
+  if (int rc = dict_check(e, n_req, n_gather, n_dict, item_field, item_feat, item_code, dict_ptr, dict_feat, item_val, n_items,
+                          std::max(top_k, 1), t))
+    return rc;
+  if (top_k < 1 || top_k > kTopkMax)
+    return fail(FFM_E_INVALID, "top_k " + std::to_string(top_k) + " lies outside [1, " + std::to_string(kTopkMax) + "]");
+  return catalog_ready(e);
+}
+
+int ffm_engine_score_items_dict_topk_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                            const int32_t *ctx_feat, const float *ctx_val, int32_t n_gather, int32_t n_dict,
+                                            const int32_t *item_field, const int32_t *item_feat, const int32_t *item_code,
+                                            const int32_t *dict_ptr, const int32_t *dict_feat, const float *item_val, int32_t n_items,
+                                            int32_t top_k, int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob, float *out_score,
+                                            int32_t *out_id) {
+  DictTable t;
+  if (int rc = dict_topk_check(e, n_req, n_gather, n_dict, item_field, item_feat, item_code, dict_ptr, dict_feat, item_val, n_items, top_k, &t))
+    return rc;
+  if (n_req == 0) return FFM_OK;
+  if (ctx_nnz < 0 || ctx_cap < 0) return fail(FFM_E_INVALID, "negative ctx_nnz / ctx_cap");
+  if (!out_score || !out_id || (n_items > 0 && (!ctx_ptr || dict_arrays_null(t) || (ctx_nnz > 0 && (!ctx_field || !ctx_feat || !ctx_val)))))
+    return fail(FFM_E_INVALID, "null array");
+  const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
+  return catalog_topk_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t.items, &t, top_k,
+                             output_prob, out_score, out_id);
+}
+
+int ffm_engine_score_items_dict_topk(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                     const int32_t *ctx_feat, const float *ctx_val, int32_t n_gather, int32_t n_dict,
+                                     const int32_t *item_field, const int32_t *item_feat, const int32_t *item_code,
+                                     const int32_t *dict_ptr, const int32_t *dict_feat, const float *item_val, int32_t n_items,
+                                     int32_t top_k, int32_t output_prob, float *out_score, int32_t *out_id) {
+  DictTable t;
+  int rc = dict_topk_check(e, n_req, n_gather, n_dict, item_field, item_feat, item_code, dict_ptr, dict_feat, item_val, n_items, top_k, &t);
+  if (rc) return rc;
+  if (n_req == 0) return FFM_OK;
+  if (!out_score || !out_id || (n_items > 0 && dict_arrays_null(t))) return fail(FFM_E_INVALID, "null array");
+  const size_t n_out = static_cast<size_t>(n_req) * top_k;
+  if ((rc = e->grow(&e->topk_score, &e->topk_score_cap, n_out)) || (rc = e->grow(&e->topk_id, &e->topk_id_cap, n_out))) return rc;
+  int32_t ctx_nnz = 0;
+  int cap = 1;
+  if (n_items > 0 && ((rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap)) || (rc = dict_stage(e, &t))))
+    return rc;
+  rc = catalog_topk_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, 0, 0, n_items, 1.0f, &t.items, &t,
+                           top_k, output_prob, e->topk_score, e->topk_id);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out_score, e->topk_score, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(out_id, e->topk_id, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, e->stream));

@@ -540,7 +540,8 @@ static int opt_in_lds(ffm_engine *e) {
   // the best K of a catalogue: the lists of the largest top_k a launch of rt request tiles can see
   for (int rt = 1; rt <= 4; rt *= 2)
     if ((rc = lds_opt_in(catalog_topk_fn(e->m.lat_fmt, rt), catalog_topk_lds_bytes(rt, catalog_topk_kp(catalog_topk_max_k(rt))))) ||
-        (rc = lds_opt_in(catalog_topk_fn<CatalogItemSrc>(e->m.lat_fmt, rt), catalog_topk_lds_bytes(rt, catalog_topk_kp(catalog_topk_max_k(rt))))))
+        (rc = lds_opt_in(catalog_topk_fn<CatalogItemSrc>(e->m.lat_fmt, rt), catalog_topk_lds_bytes(rt, catalog_topk_kp(catalog_topk_max_k(rt))))) ||
+        (rc = lds_opt_in(catalog_topk_fn<CatalogDictSrc>(e->m.lat_fmt, rt), catalog_topk_lds_bytes(rt, catalog_topk_kp(catalog_topk_max_k(rt))))))
       return rc;
   return FFM_OK;
 }

@@ -200,6 +200,26 @@ inline CatalogItemsUFn catalog_items_u_fn(int fmt) {
 inline CatalogItemsSelfFn catalog_items_self_fn(int fmt) {
   return fmt == SERVE_F16 ? catalog_items_self_kernel<SERVE_F16> : fmt == SERVE_F32 ? catalog_items_self_kernel<SERVE_F32> : nullptr;
 }
+// the factorised item table (kernels_catalog_dict.h): U of the dictionary slots, S_c and the partial scores P per
+// format; its gemm and top-K kernels are the two families above over CatalogDictSrc, by the same rules
+using CatalogDictUFn = CatalogItemsUFn;
+using CatalogDictSelfFn = void (*)(ModelDev, CatalogItemSlots, int, const int *, const int *, CatalogDicts, const int *, int64_t, float *);
+using CatalogDictFn = void (*)(const char *, int, CatalogDev, int, CatalogDicts, const int *, int, float *);
+inline CatalogDictUFn catalog_dict_u_fn(int fmt) {
+  return fmt == SERVE_F16 ? catalog_dict_u_kernel<SERVE_F16> : fmt == SERVE_F32 ? catalog_dict_u_kernel<SERVE_F32> : nullptr;
+}
+inline CatalogDictSelfFn catalog_dict_self_fn(int fmt) {
+  return fmt == SERVE_F16 ? catalog_dict_self_kernel<SERVE_F16> : fmt == SERVE_F32 ? catalog_dict_self_kernel<SERVE_F32> : nullptr;
+}
+// tiles: whole request tiles left of the padded range; the largest RT that stays inside them (4, 2 or 1)
+inline int catalog_dict_rt(int tiles) { return tiles >= 4 ? 4 : tiles >= 2 ? 2 : 1; }
+template <int FMT>
+CatalogDictFn catalog_dict_by_rt(int rt) {
+  return rt == 1 ? catalog_dict_kernel<FMT, 1> : rt == 2 ? catalog_dict_kernel<FMT, 2> : rt == 4 ? catalog_dict_kernel<FMT, 4> : nullptr;
+}
+inline CatalogDictFn catalog_dict_fn(int fmt, int rt) {
+  return fmt == SERVE_F16 ? catalog_dict_by_rt<SERVE_F16>(rt) : fmt == SERVE_F32 ? catalog_dict_by_rt<SERVE_F32>(rt) : nullptr;
+}
 // field ablation (kernels_ablate.h)
 using AblateWaveFn =void (*)(ModelDev, Rows, int *, int, int, float *, double *, int, int);
 inline AblateWaveFn ablate_wave_fn(int fmt, int n_factors) {

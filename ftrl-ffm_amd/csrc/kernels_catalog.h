@@ -194,9 +194,20 @@ __device__ __forceinline__ uint4 catalog_load(const char *tab, int64_t row_bytes
 //   load(tab, row_bytes, c0, row4, it, n_cols, ch, sub, even16)   16 bytes: row row4 + 4 it of the wave's 32, bytes
 //                         [16 sub, 16 sub + 16) of chunk ch -- or zero registers where there is no such row or byte
 //   logit<FMT>(a, v, col, base, shift)   the score of accumulator a; col: the column's own term (lin[c])
+//   Term(args, c, n_cols)               made by a lane for its column c behind the accumulation (c may lie beyond n_cols)
+//   term.add<FMT>(acc_t, r_tile, h, shift)   a term per (request, column) into the lane's 16 accumulators of the tile
+//                         whose first request is r_tile, before logit sees them; shift: the tile's 32 shifts.
+//                         CatalogNoTerm adds nothing and compiles to nothing (kernels_catalog_dict.h has the one that does)
 // U's row has the chunks in the source's order: chunk ch pairs with bytes [256 ch, 256 ch + 256) of U_r.
+struct CatalogNoTerm {
+  template <typename Args>
+  __device__ __forceinline__ CatalogNoTerm(const Args &, int64_t, int64_t) {}
+  template <int FMT>
+  __device__ __forceinline__ void add(cat_v16f &, int, int, const int *) const {}
+};
 struct CatalogSlabSrc {
   struct Args {};
+  using Term = CatalogNoTerm;
   static constexpr int kLdsInts = 0;
   __device__ __forceinline__ CatalogSlabSrc() {}
   __device__ __forceinline__ CatalogSlabSrc(const Args &, int *, int64_t, int64_t, int) {}
@@ -304,8 +315,10 @@ __global__ __launch_bounds__(64 * kCatWaves) void catalog_gemm_kernel(const char
   const int64_t c = c0 + j;
   if (c >= n_cand) return;
   const float lw = lin[c];
+  const typename Src::Term term(args, c, n_cand);
 #pragma unroll
-  for (int t = 0; t < RT; t++)
+  for (int t = 0; t < RT; t++) {
+    term.template add<FMT>(acc[t], r0 + kCatTile * t, h, cd.shift + r0 + kCatTile * t);
 #pragma unroll
     for (int x = 0; x < 16; x++) {
       const int r = r0 + kCatTile * t + 8 * (x >> 2) + 4 * h + (x & 3);
@@ -313,6 +326,7 @@ __global__ __launch_bounds__(64 * kCatWaves) void catalog_gemm_kernel(const char
       const float score = Src::template logit<FMT>(acc[t][x], v, lw, cd.base[r], FMT == SERVE_F16 ? cd.shift[r] : 0);
       out[static_cast<int64_t>(r) * n_cand + c] = output_prob ? sigmoid_ref(score) : score;
     }
+  }
 }
 
 }  // namespace ftrl_dev

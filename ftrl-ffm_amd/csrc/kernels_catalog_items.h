@@ -32,7 +32,7 @@
 // RESOURCES (hipcc --offload-arch=gfx950 -O3, kernel-resource-usage; no scratch in any of them; the static LDS of
 // the gemm and top-K instantiations is 38 912 bytes; waves per SIMD as the registers admit them)
 //   catalog_items_u_kernel<f32>      22 VGPRs, 8 waves     <f16>  21 VGPRs, 8 waves
-//   catalog_items_self_kernel<f32>   44 VGPRs, 8 waves     <f16>  32 VGPRs, 8 waves      catalog_items_fields_kernel  28 VGPRs
+//   catalog_items_self_kernel<f32>   38 VGPRs, 8 waves    <f16>  32 VGPRs, 8 waves      catalog_items_fields_kernel  28 VGPRs
 //   gemm <f32, 1>   62 VGPRs, 16 AGPRs, 4 waves      <f16, 1>   68 VGPRs, 16 AGPRs, 4 waves
 //   gemm <f32, 2>   64 VGPRs, 32 AGPRs, 4 waves      <f16, 2>   84 VGPRs, 32 AGPRs, 4 waves
 //   gemm <f32, 4>   88 VGPRs, 64 AGPRs, 3 waves      <f16, 4>  114 VGPRs, 64 AGPRs, 2 waves
@@ -103,24 +103,13 @@ __global__ __launch_bounds__(64 * kPredRows) void catalog_items_u_kernel(ModelDe
 // factors of each of the m (m - 1) / 2 pairs' two slots (k % 4 == 0; else single factors q, q + 4, ...), and lane 0 the
 // linear terms; two shuffles add the four partial sums.  A slot with an id outside [0, n_feats) is erased: its linear
 // term and every pair it is in are skipped.  No LDS, no barrier.
+// id[a]: slot a's id, or -1 for an erased slot and for every slot from sl.n on; q: the lane's place among its item's four.
+// Returns S_c in all four lanes.  (catalog_dict_self_kernel, kernels_catalog_dict.h, resolves its ids otherwise and adds
+// them by this function too.)
 template <int FMT>
-__global__ __launch_bounds__(256) void catalog_items_self_kernel(ModelDev m, CatalogItemSlots sl, const int *item_feat, int64_t n_items,
-                                                                 float *item_s) {
-  static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
+__device__ __forceinline__ float catalog_items_self_sum(const ModelDev &m, const CatalogItemSlots &sl, const int (&id)[kItemSlots], int q) {
   using Raw = typename WaveTable<FMT>::Raw;
-  const int64_t c = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) >> 2;
-  const int q = threadIdx.x & 3;
-  const bool live = c < n_items;  // (the four lanes of an item agree; idle lanes still take part in the shuffles)
   const int k = m.n_factors, L = m.row_len;
-  int id[kItemSlots];
-#pragma unroll
-  for (int a = 0; a < kItemSlots; a++) {
-    id[a] = -1;
-    if (live && a < sl.n) {
-      const int i = item_feat[c * sl.n + a];
-      id[a] = i >= 0 && i < m.n_feats ? i : -1;
-    }
-  }
   float sum = 0.0f;
   if (q == 0) {
 #pragma unroll
@@ -154,7 +143,26 @@ __global__ __launch_bounds__(256) void catalog_items_self_kernel(ModelDev m, Cat
       sum = __fmaf_rn(__fmul_rn(sl.val[a], sl.val[b]), dot, sum);
     }
   sum = __fadd_rn(sum, __shfl_xor(sum, 1, 64));
-  sum = __fadd_rn(sum, __shfl_xor(sum, 2, 64));
+  return __fadd_rn(sum, __shfl_xor(sum, 2, 64));
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void catalog_items_self_kernel(ModelDev m, CatalogItemSlots sl, const int *item_feat, int64_t n_items,
+                                                                 float *item_s) {
+  static_assert(FMT == SERVE_F32 || FMT == SERVE_F16, "a packed table of w alone");
+  const int64_t c = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) >> 2;
+  const int q = threadIdx.x & 3;
+  const bool live = c < n_items;  // (the four lanes of an item agree; idle lanes still take part in the shuffles)
+  int id[kItemSlots];
+#pragma unroll
+  for (int a = 0; a < kItemSlots; a++) {
+    id[a] = -1;
+    if (live && a < sl.n) {
+      const int i = item_feat[c * sl.n + a];
+      id[a] = i >= 0 && i < m.n_feats ? i : -1;
+    }
+  }
+  const float sum = catalog_items_self_sum<FMT>(m, sl, id, q);
   if (live && q == 0) item_s[c] = sum;
 }
 
@@ -173,6 +181,7 @@ struct CatalogItemSrc {
     int n_feats, n_slots;
     int chunks_per_row;    // Lp * ES / 256: chunks of one slot's block
   };
+  using Term = CatalogNoTerm;
   static constexpr int kLdsInts = kItemSlots * 32;  // the ids of the wave's 32 items, [n_slots][32]; n_feats: reads as zeros
   const int *ids;
   int n_feats, chunks_per_row;

@@ -114,8 +114,10 @@ __global__ __launch_bounds__(64 * kCatWaves) void catalog_topk_kernel(const char
     const int64_t c = c0 + j;
     const float lw = c < n_cand ? lin[c] : 0.0f;
     const int n_col = static_cast<int>(n_cand - c0 < 32 ? n_cand - c0 : 32);  // columns of the tile that are candidates
+    const typename Src::Term term(args, c, n_cand);
 #pragma unroll
     for (int t = 0; t < RT; t++) {
+      term.template add<FMT>(acc[t], r0 + kCatTile * t, h, Hw + kCatTile * t);
 #pragma unroll
       for (int x = 0; x < 16; x++) {
         const int row = 8 * (x >> 2) + 4 * h + (x & 3), q = kCatTile * t + row;

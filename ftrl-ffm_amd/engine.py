@@ -264,6 +264,20 @@ ABI = [
     ("ffm_engine_score_items_topk_device", ctypes.c_int,
      [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, _i32p, _vp, _f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
       ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
+    # ... whose last slots are codes into small dictionaries (include/ffm_engine.h "Scoring a catalogue: dictionary
+    # slots"); item_field / item_val / dict_ptr are host arrays in the device calls too
+    ("ffm_engine_score_items_dict", ctypes.c_int,
+     [_vp, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p,
+      ctypes.c_int32, ctypes.c_int32, _f32p]),
+    ("ffm_engine_score_items_dict_device", ctypes.c_int,
+     [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i32p, _vp, _vp, _i32p, _vp, _f32p, ctypes.c_int32,
+      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp]),
+    ("ffm_engine_score_items_dict_topk", ctypes.c_int,
+     [_vp, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p,
+      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _f32p, _i32p]),
+    ("ffm_engine_score_items_dict_topk_device", ctypes.c_int,
+     [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i32p, _vp, _vp, _i32p, _vp, _f32p, ctypes.c_int32,
+      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     # the fields' cardinalities counted on the device, id ranges sized by them (include/ffm_engine.h "Field sketches")
     ("ffm_engine_sketch_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("ffm_engine_sketch_add", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32]),
@@ -1082,6 +1096,40 @@ def score_items_reference(weights, ctx, item_field, item_feat, item_val=None, n_
     return ref64, scale
 
 
+def factor_items(item_feat, n_gather):
+    """An item table int32[n_items, m] split for Engine.score_items_dict: (item_feat[:, :n_gather], item_code
+    int32[n_items, m - n_gather], dicts), dicts[a] the sorted distinct ids of column n_gather + a (np.unique) and
+    item_code[c][a] the place of item c's id in it.  numpy only; expand_items is the inverse."""
+    feat = np.ascontiguousarray(item_feat, np.int32)
+    if feat.ndim != 2 or not 1 <= int(n_gather) < feat.shape[1]:
+        raise ValueError("item_feat must be [n_items, m] with 1 <= n_gather < m")
+    pairs = [np.unique(feat[:, a], return_inverse=True) for a in range(int(n_gather), feat.shape[1])]
+    code = np.stack([inv.reshape(-1) for _, inv in pairs], axis=1).astype(np.int32)
+    return np.ascontiguousarray(feat[:, :int(n_gather)]), code, [d.astype(np.int32) for d, _ in pairs]
+
+
+def _dict_arrays(dicts):
+    """(dict_ptr int32[n_dict + 1], dict_feat int32[dict_ptr[-1]]) of a sequence of dictionaries."""
+    dicts = [np.ascontiguousarray(d, np.int32).reshape(-1) for d in dicts]
+    ptr = np.cumsum([0] + [d.shape[0] for d in dicts]).astype(np.int32)
+    return ptr, np.ascontiguousarray(np.concatenate(dicts + [np.zeros(0, np.int32)]), np.int32)
+
+
+def expand_items(item_feat, item_code, dicts, n_feats):
+    """The [n_items, n_gather + n_dict] id table Engine.score_items_dict scores (include/ffm_engine.h "Scoring a
+    catalogue: dictionary slots"): the gathered ids, then per dictionary slot dicts[a][item_code[c][a]] -- n_feats, an
+    erased slot, for a code outside the dictionary.  score_items_reference on it is the definition; numpy only."""
+    feat, code = np.ascontiguousarray(item_feat, np.int32), np.ascontiguousarray(item_code, np.int32)
+    if feat.ndim != 2 or code.ndim != 2 or code.shape != (feat.shape[0], len(dicts)):
+        raise ValueError("item_code must be [n_items, %d]: one code per dictionary" % len(dicts))
+    cols = []
+    for a, d in enumerate(dicts):
+        d = np.asarray(d, np.int32).reshape(-1)
+        ok = (code[:, a] >= 0) & (code[:, a] < d.shape[0])
+        cols.append(np.where(ok, np.append(d, 0)[np.where(ok, code[:, a], 0)], n_feats))
+    return np.concatenate([feat, np.stack(cols, axis=1).astype(np.int32)], axis=1)
+
+
 def load_library(path=None):
     """dlopen libffm_engine.so and bind every ABI symbol.  Raises if it is missing."""
     global _lib
@@ -1696,6 +1744,66 @@ class Engine:
         self._check(self.lib.ffm_engine_score_items_topk_device(
             self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, fld.shape[0], _i(fld), item_feat, _f(val), int(n_items), int(k),
             int(ctx_nnz), int(ctx_cap), int(output_prob), out_score, out_id))
+
+    @staticmethod
+    def _dict_table(item_field, item_feat, item_code, dicts, item_val):
+        """The arrays of a table with dictionary slots: (field int32[m], feat int32[n_items, n_gather], code
+        int32[n_items, n_dict], dict_ptr, dict_feat, val float32[m])."""
+        feat, code = np.ascontiguousarray(item_feat, np.int32), np.ascontiguousarray(item_code, np.int32)
+        ptr, dfeat = _dict_arrays(dicts)
+        if feat.ndim != 2 or code.ndim != 2 or code.shape != (feat.shape[0], len(ptr) - 1):
+            raise ValueError("item_feat must be [n_items, n_gather] and item_code [n_items, %d]: one code per dictionary" % (len(ptr) - 1))
+        fld = np.ascontiguousarray(item_field, np.int32).reshape(-1)
+        val = np.ones(fld.shape[0], np.float32) if item_val is None else np.ascontiguousarray(item_val, np.float32).reshape(-1)
+        if fld.shape[0] != feat.shape[1] + code.shape[1] or val.shape != fld.shape:
+            raise ValueError("item_field and item_val need one element per slot, the gathered slots first")
+        return fld, feat, code, ptr, dfeat, val
+
+    def score_items_dict(self, ctx, item_field, item_feat, item_code, dicts, item_val=None, output_prob=False):
+        """score_items on a factorised table: the first n_gather slots hold ids (item_feat[n_items, n_gather]), the
+        others codes (item_code[n_items, n_dict]) into dicts, a sequence of int32 arrays of ids, one per dictionary
+        slot; float32[n_req, n_items] (include/ffm_engine.h "Scoring a catalogue: dictionary slots";
+        score_items_reference on expand_items(...) is the definition).  A dictionary slot is scored once per
+        dictionary entry and added per item by lookup.  A code outside its dictionary erases its slot."""
+        fld, feat, code, ptr, dfeat, val = self._dict_table(item_field, item_feat, item_code, dicts, item_val)
+        out = np.zeros((ctx.n_rows, feat.shape[0]), np.float32)
+        _, cp, cfld, cft, cv, _ = self._csr(ctx)
+        self._check(self.lib.ffm_engine_score_items_dict(self.h, ctx.n_rows, cp, cfld, cft, cv, feat.shape[1], code.shape[1], _i(fld), _i(feat),
+                                                         _i(code), _i(ptr), _i(dfeat), _f(val), feat.shape[0], int(output_prob), _f(out)))
+        return out
+
+    def score_items_dict_topk(self, ctx, item_field, item_feat, item_code, dicts, k, item_val=None, output_prob=False):
+        """The k best items of score_items_dict per request: (scores float32[n_req, k], ids int32[n_req, k]), as
+        score_items_topk (catalog_topk_reference(score_items_dict(...), 0, k) is the definition; the scores are
+        score_items_dict's bits)."""
+        fld, feat, code, ptr, dfeat, val = self._dict_table(item_field, item_feat, item_code, dicts, item_val)
+        scores = np.zeros((ctx.n_rows, max(int(k), 0)), np.float32)
+        ids = np.zeros((ctx.n_rows, max(int(k), 0)), np.int32)
+        _, cp, cfld, cft, cv, _ = self._csr(ctx)
+        self._check(self.lib.ffm_engine_score_items_dict_topk(self.h, ctx.n_rows, cp, cfld, cft, cv, feat.shape[1], code.shape[1], _i(fld),
+                                                              _i(feat), _i(code), _i(ptr), _i(dfeat), _f(val), feat.shape[0], int(k),
+                                                              int(output_prob), _f(scores), _i(ids)))
+        return scores, ids
+
+    def score_items_dict_device(self, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, n_gather, item_field, item_feat, item_code, dict_ptr,
+                                dict_feat, item_val, n_items, ctx_nnz, ctx_cap, output_prob, out):
+        """score_items_dict on arrays already in HBM (device addresses: the contexts, item_feat[n_items][n_gather],
+        item_code[n_items][n_dict], dict_feat, out); item_field, item_val (or None) and dict_ptr[n_dict + 1] are host
+        arrays, read by the call.  Asynchronous on the engine's stream; sync() reports a too-long context."""
+        fld, ptr = np.ascontiguousarray(item_field, np.int32).reshape(-1), np.ascontiguousarray(dict_ptr, np.int32).reshape(-1)
+        val = None if item_val is None else np.ascontiguousarray(item_val, np.float32).reshape(-1)
+        self._check(self.lib.ffm_engine_score_items_dict_device(
+            self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, int(n_gather), ptr.shape[0] - 1, _i(fld), item_feat, item_code, _i(ptr),
+            dict_feat, _f(val), int(n_items), int(ctx_nnz), int(ctx_cap), int(output_prob), out))
+
+    def score_items_dict_topk_device(self, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, n_gather, item_field, item_feat, item_code,
+                                     dict_ptr, dict_feat, item_val, n_items, k, ctx_nnz, ctx_cap, output_prob, out_score, out_id):
+        """score_items_dict_topk on arrays already in HBM, as score_items_dict_device; out_score / out_id [n_req][k]."""
+        fld, ptr = np.ascontiguousarray(item_field, np.int32).reshape(-1), np.ascontiguousarray(dict_ptr, np.int32).reshape(-1)
+        val = None if item_val is None else np.ascontiguousarray(item_val, np.float32).reshape(-1)
+        self._check(self.lib.ffm_engine_score_items_dict_topk_device(
+            self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, int(n_gather), ptr.shape[0] - 1, _i(fld), item_feat, item_code, _i(ptr),
+            dict_feat, _f(val), int(n_items), int(k), int(ctx_nnz), int(ctx_cap), int(output_prob), out_score, out_id))
 
     # ---- blocks already in HBM (raw device addresses as ints) ----
     def score_candidates_device(self, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, cand_req_ptr, n_cand, cand_ptr,

@@ -1220,8 +1220,8 @@ int ffm_engine_score_catalog_topk_device(ffm_engine *e, int32_t n_req, const int
  *   The profile calls label the kernels "catalog_items_u_kernel", "catalog_items_self_kernel",
  *   "catalog_items_gemm_kernel" and "catalog_items_topk_kernel".  FFM_ENGINE_ABI_VERSION is what it was.
  * OUT OF SCOPE  per-item values; repeated fields in an item; m > 8; FFM_FLAG_SERVE_F8 and pruned tables; the CLI;
- *   caching S_c across calls; bucketing item values; the factorised form (a slot with few distinct ids scored once per
- *   id through ffm_engine_score_catalog and added by lookup). */
+ *   caching S_c across calls; bucketing item values.  (The factorised form -- a slot with few distinct ids scored once
+ *   per id and added by lookup -- is the next section.) */
 int ffm_engine_score_items(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
                            const float *ctx_val, int32_t n_slots, const int32_t *item_field, const int32_t *item_feat,
                            const float *item_val, int32_t n_items, int32_t output_prob, float *out);
@@ -1237,6 +1237,80 @@ int ffm_engine_score_items_topk_device(ffm_engine *e, int32_t n_req, const int32
                                        const int32_t *ctx_feat, const float *ctx_val, int32_t n_slots, const int32_t *item_field,
                                        const int32_t *item_feat, const float *item_val, int32_t n_items, int32_t top_k,
                                        int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob, float *out_score, int32_t *out_id);
+
+/* ---- Scoring a catalogue: dictionary slots ---------------------------------------------------------------
+ * Real item tables are a few thousand advertisers and a few dozen categories and sizes under millions of ads.  A
+ * slot's contribution sum_j U_r^a[j] * W[c_a][j] depends on the request and the slot's id alone, so for a slot with
+ * few distinct ids it is computed once per DISTINCT id and added per item by lookup (the factorised form), and only
+ * the remaining slots pay for a gathered table row per item.  The item table of the section above is split in two:
+ *   item_field[n_slots], item_val[n_slots]   all slots, the gathered ones first; n_slots = n_gather + n_dict <= 8,
+ *                                  n_gather >= 1, n_dict >= 1, fields distinct over all slots; item_val NULL is ones;
+ *   item_feat[n_items][n_gather]   model ids of the first n_gather slots (GATHERED slots), as above;
+ *   item_code[n_items][n_dict]     for the last n_dict slots (DICTIONARY slots) indices into the slot's dictionary;
+ *   dict_ptr[n_dict + 1]           non-decreasing, dict_ptr[0] == 0: dictionary a' is the D_a' = dict_ptr[a' + 1] -
+ *                                  dict_ptr[a'] model ids dict_feat[dict_ptr[a'] ...];
+ *   dict_feat[dict_ptr[n_dict]]    model ids.
+ * Dictionary slot a = n_gather + a' of item c stands for the entry (g_a, dict_feat[dict_ptr[a'] + item_code[c][a']], v_a),
+ * and the score is EXACTLY the formula of the section above, score(r, c) = base_r + S_c + sum_a sum_j U_r^a[j] W[c_a][j],
+ * on that expanded table (expand_items of the Python binding builds it; score_items_reference on it is the definition).
+ * ERASED SLOTS  A dictionary slot is erased, as an id outside the table is above, when its code lies outside [0, D_a') or
+ *   its dictionary id lies outside [0, n_feats): a zero contribution, a zero linear term, no part in any pair of S_c.
+ *   Neither codes nor ids are range-checked.
+ * HOW (csrc/kernels_catalog_dict.h)  U of every dictionary slot as a block of its own (on f16 with a shift of its own per
+ *   slot and request); one launch of the contraction over all dictionaries laid end to end, each padded to whole waves
+ *   of 32 columns, writes the partial scores P[column][padded requests] in fp32; S_c per item with the dictionary slots'
+ *   ids read through their dictionaries (pairs between two dictionary slots are computed per item: no pair tables); the
+ *   matrix and top-K kernels of the sections above over the n_gather gathered slots, whose epilogue adds P by lookup:
+ *     t = acc' (un-shifted on f16);  t = fadd(t, P_a') for a' = 0 .. n_dict - 1 in slot order;  score = fadd(t, fadd(S_c, base_r))
+ *   -- one function in both kernels, so ffm_engine_score_items_dict_topk's scores are ffm_engine_score_items_dict's bits.
+ * CONTRACT  Not bit for bit against ffm_engine_score_items or the rows.  For finite tables the bound above carries over
+ *   unchanged, with m = n_gather + n_dict, N = m L + m + m (m - 1) / 2 * k, ref64 and scale of the expanded table:
+ *     |score - (base_r + ref64)| <= (N + 32) * 2^-24 * (|base_r| + scale)
+ *   The N products are the same; each P_a' is its slot's L products summed in fp32 in the matrix unit's order and
+ *   rounded once, and the partial sums are added in slot order -- one more summation order of the same N products,
+ *   which the any-order term N * 2^-24 covers.  A dictionary slot's own shift on f16 is taken from its own block's
+ *   largest magnitude and is at least as tight as the shared shift the 32 covers above.
+ * CONTEXTS, TOP K  as in the section above.
+ * HASHED IDS  On an engine with FFM_FLAG_HASH_IDS the host calls hash (and fold) item_feat under the gathered slots'
+ *   fields and dict_feat under each dictionary's field, by the path ffm_engine_score_items uses; codes are positions
+ *   and are never hashed; the device calls take ids as they are.
+ * ffm_engine_score_items_dict / _topk: every array in host memory; synchronous; item_feat, item_code and dict_feat are
+ *   copied into buffers of the engine's.
+ * ffm_engine_score_items_dict_device / _topk_device: the contexts, item_feat, item_code, dict_feat and the outputs are
+ *   device addresses; item_field, item_val and dict_ptr are HOST arrays here too, checked before anything is queued and
+ *   handed to the kernels by value; asynchronous on the engine's stream.
+ * All four: every check of the ffm_engine_score_items calls with n_slots = n_gather + n_dict; FFM_E_INVALID naming
+ *   n_gather or n_dict for a count below 1, and naming dict_ptr for a first element other than 0 or a decreasing pair;
+ *   FFM_E_CAPACITY when the padded requests times the dictionaries' padded entries exceed 2^31 - 1.  The same engines
+ *   are REFUSED by name with the same codes: training, FFM_FLAG_SERVE_F8, a pruned table, a pair mask,
+ *   FFM_FLAG_NORM_ROWS, a group's or a shard's engine.  The buffers (P, the dictionary slots' U and shifts, the host
+ *   calls' copies) are allocated by the first call, grown to the largest call seen and freed by ffm_engine_destroy;
+ *   an engine that never calls this allocates and launches nothing new.  The profile calls label the kernels
+ *   "catalog_dict_u_kernel", "catalog_dict_kernel", "catalog_dict_self_kernel", "catalog_dict_gemm_kernel" and
+ *   "catalog_dict_topk_kernel".  FFM_ENGINE_ABI_VERSION is what it was.
+ * OUT OF SCOPE  deduplicating ids on the device (factor_items of the Python binding does it on the host); pair tables
+ *   between dictionary slots; staging P in LDS; per-item values; FFM_FLAG_SERVE_F8 and pruned tables; the CLI; caching
+ *   P or S_c across calls. */
+int ffm_engine_score_items_dict(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                                const float *ctx_val, int32_t n_gather, int32_t n_dict, const int32_t *item_field,
+                                const int32_t *item_feat, const int32_t *item_code, const int32_t *dict_ptr, const int32_t *dict_feat,
+                                const float *item_val, int32_t n_items, int32_t output_prob, float *out);
+int ffm_engine_score_items_dict_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                       const int32_t *ctx_feat, const float *ctx_val, int32_t n_gather, int32_t n_dict,
+                                       const int32_t *item_field, const int32_t *item_feat, const int32_t *item_code,
+                                       const int32_t *dict_ptr, const int32_t *dict_feat, const float *item_val, int32_t n_items,
+                                       int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob, float *out);
+int ffm_engine_score_items_dict_topk(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                     const int32_t *ctx_feat, const float *ctx_val, int32_t n_gather, int32_t n_dict,
+                                     const int32_t *item_field, const int32_t *item_feat, const int32_t *item_code,
+                                     const int32_t *dict_ptr, const int32_t *dict_feat, const float *item_val, int32_t n_items,
+                                     int32_t top_k, int32_t output_prob, float *out_score, int32_t *out_id);
+int ffm_engine_score_items_dict_topk_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                            const int32_t *ctx_feat, const float *ctx_val, int32_t n_gather, int32_t n_dict,
+                                            const int32_t *item_field, const int32_t *item_feat, const int32_t *item_code,
+                                            const int32_t *dict_ptr, const int32_t *dict_feat, const float *item_val, int32_t n_items,
+                                            int32_t top_k, int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob, float *out_score,
+                                            int32_t *out_id);
 
 /* ---- Field ablation: the loss and AUC of the model without each field, in one pass -------------------
  * Which fields earn their place?  The standard answer is the evaluation loss and AUC of the same model with

@@ -168,6 +168,10 @@ def run_catalog(args):
             us.append(1e6 * (time.perf_counter() - t0) / n)
         return sorted(us)
 
+    if args.dict_slots:  # (its own baselines, in this process: no spelled-out rows)
+        catalog_dict_lines(args, eng, windows, d, out, cf, up, nf)
+        eng.close()
+        return
     # the baseline: spelled-out rows of request r against candidates first + j, blocks of 8192 rows, cycled
     rows = []
     for b in range(args.blocks):
@@ -249,6 +253,58 @@ def catalog_items_lines(args, eng, windows, d, out, ctx, cf, up, nf):
         res["rows_scores_per_s"] = rate
         res["items_over_catalog"] = res["score_items_device_us"]["median"] / res["score_catalog_device_us"]["median"]
         res["items_scores_per_s"] = n_req * n_items / (res["score_items_device_us"]["median"] * 1e-6)
+        print("SERVE_BENCH " + json.dumps(res), flush=True)
+
+
+def catalog_dict_lines(args, eng, windows, d, out, cf, up, nf):
+    """--catalog-items M --dict-slots D: catalog_items_lines' table (2^20 items; slot 0's ids distinct, the others drawn
+    from 1000, 100, 10, ... ids) with its last D slots as dictionaries (factor_items), through score_items_dict_device
+    and its top 8, beside score_items_device on the expanded table and score_catalog_device on as many candidates, per
+    32 and 128 requests: one JSON line each, medians of the windows with min .. max; score_items_device is measured
+    twice, and the distance of the two medians is the run-to-run spread of this process."""
+    import numpy as np
+    import torch
+    import ftrl_ffm_amd as fa
+    M, D, n_items, K = args.catalog_items, args.dict_slots, 1 << 20, 8
+    per = nf // N_FIELDS
+    rng = np.random.default_rng(42)
+    fld = np.arange(N_FIELDS - M, N_FIELDS, dtype=np.int32)[::-1].copy()
+    pool = [n_items] + [max(1, 1000 // 10 ** a) for a in range(M - 1)]
+    feat = np.stack([1000 + np.arange(n_items) if a == 0 else fld[a] * per + rng.integers(pool[a], size=n_items) for a in range(M)],
+                    axis=1).astype(np.int32)
+    gathered, code, dicts = fa.factor_items(feat, M - D)
+    ptr = np.cumsum([0] + [len(x) for x in dicts]).astype(np.int32)
+    d_feat, d_gath, d_code, d_dict = up(feat), up(gathered), up(code), up(np.concatenate(dicts))
+    ptrs = [t.data_ptr() for t in d]
+    score = torch.zeros(128 * K, dtype=torch.float32, device="cuda")
+    ids = torch.zeros(128 * K, dtype=torch.int32, device="cuda")
+    for n_req in (32, 128):
+        def items():
+            eng.score_items_device(n_req, *ptrs, fld, d_feat.data_ptr(), None, n_items, n_req * cf, cf, 0, out.data_ptr())
+        cells = dict(
+            score_items_dict_device=lambda: eng.score_items_dict_device(n_req, *ptrs, M - D, fld, d_gath.data_ptr(), d_code.data_ptr(), ptr,
+                                                                        d_dict.data_ptr(), None, n_items, n_req * cf, cf, 0, out.data_ptr()),
+            score_items_dict_topk_device=lambda: eng.score_items_dict_topk_device(
+                n_req, *ptrs, M - D, fld, d_gath.data_ptr(), d_code.data_ptr(), ptr, d_dict.data_ptr(), None, n_items, K, n_req * cf, cf, 0,
+                score.data_ptr(), ids.data_ptr()),
+            score_items_device=items,
+            score_items_topk_device=lambda: eng.score_items_topk_device(n_req, *ptrs, fld, d_feat.data_ptr(), None, n_items, K, n_req * cf, cf,
+                                                                        0, score.data_ptr(), ids.data_ptr()),
+            score_catalog_device=lambda: eng.score_catalog_device(n_req, *ptrs, N_FIELDS - 1, 1000, n_items, 1.0, n_req * cf, cf, 0,
+                                                                  out.data_ptr()),
+            score_items_device_again=items)
+        res = dict(catalog_items=M, dict_slots=D, dict_sizes=[len(x) for x in dicts], kind=args.kind, n_req=n_req, n_items=n_items, top_k=K)
+        for name, call in cells.items():
+            us = windows(call, window=max(args.window, 0.3))
+            res[name + "_us"] = dict(median=round(us[len(us) // 2], 1), min=round(us[0], 1), max=round(us[-1], 1))
+        res["items_over_dict"] = res["score_items_device_us"]["median"] / res["score_items_dict_device_us"]["median"]
+        res["dict_over_catalog"] = res["score_items_dict_device_us"]["median"] / res["score_catalog_device_us"]["median"]
+        eng.profile_enable(True)
+        for _ in range(10):
+            cells["score_items_dict_device"]()
+        eng.sync()
+        res["profile"] = [ln for ln in eng.profile_dump().strip().splitlines() if "catalog" in ln]
+        eng.profile_enable(False)
         print("SERVE_BENCH " + json.dumps(res), flush=True)
 
 
@@ -549,8 +605,13 @@ def main():
     ap.add_argument("--catalog-items", type=int, default=0, metavar="M",
                     help="with --catalog: also items of M slots (score_items_device, its top 8) against score_catalog_device on as "
                          "many candidates and against spelled-out rows, in the same process (profiles/score_items.md)")
+    ap.add_argument("--dict-slots", type=int, default=0, metavar="D",
+                    help="with --catalog-items M: the last D of the M slots as dictionaries (score_items_dict_device, its top 8) "
+                         "against score_items_device on the expanded table and score_catalog_device (profiles/score_items_dict.md)")
     args = ap.parse_args()
-    if args.catalog:
+    if args.dict_slots and not 1 <= args.dict_slots < args.catalog_items:
+        raise SystemExit("--dict-slots D needs --catalog-items M with 1 <= D < M")
+    if args.catalog or args.dict_slots:
         if args.kind not in ("f32", "f16"):
             raise SystemExit("--catalog needs --kind f32 or f16")
         return run_catalog(args)
