@@ -55,6 +55,7 @@
 #include "kernels_catalog_topk.h"
 #include "kernels_catalog_items.h"
 #include "kernels_catalog_dict.h"
+#include "kernels_catalog_lists.h"
 #include "kernels_delta.h"
 #include "kernels_ablate.h"
 #include "kernels_ablate_pairs.h"
@@ -135,6 +136,7 @@ enum KernelId {
   K_SERVE_CTX, K_SERVE_CAND, K_CATALOG_U, K_CATALOG_GEMM, K_CATALOG_TOPK, K_CATALOG_TOPK_MERGE,
   K_CATALOG_ITEMS_U, K_CATALOG_ITEMS_SELF, K_CATALOG_ITEMS_GEMM, K_CATALOG_ITEMS_TOPK,
   K_CATALOG_DICT_U, K_CATALOG_DICT, K_CATALOG_DICT_SELF, K_CATALOG_DICT_GEMM, K_CATALOG_DICT_TOPK,
+  K_CATALOG_LISTS_U, K_CATALOG_LISTS_SELF, K_CATALOG_LISTS,
   K_KEYED_CAPTURE, K_KEYED_SORT_HIST, K_KEYED_SORT_SCAN, K_KEYED_SORT_SCATTER, K_KEYED_RANK,
   K_UPLOAD, K_NORM_ROWS,
   K_COUNT
@@ -147,6 +149,7 @@ const char *kKernelNames[K_COUNT] = {
     "catalog_topk_kernel", "catalog_topk_merge_kernel",
     "catalog_items_u_kernel", "catalog_items_self_kernel", "catalog_items_gemm_kernel", "catalog_items_topk_kernel",
     "catalog_dict_u_kernel", "catalog_dict_kernel", "catalog_dict_self_kernel", "catalog_dict_gemm_kernel", "catalog_dict_topk_kernel",
+    "catalog_lists_u_kernel", "catalog_lists_self_kernel", "catalog_lists_kernel",
     "keyed_capture_kernel", "keyed_sort_hist_kernel", "keyed_sort_scan_kernels", "keyed_sort_scatter_kernel", "keyed_rank_kernels",
     "pull_block_kernel", "normalize_rows_kernel"};
 
@@ -486,6 +489,12 @@ struct ffm_engine {
   int *dict_shift = nullptr, *d_item_code = nullptr, *d_dict_feat = nullptr, *d_dict_field = nullptr;
   float *dict_p = nullptr;
   size_t dict_u_cap = 0, dict_shift_cap = 0, dict_p_cap = 0, item_code_cap = 0, dict_feat_cap = 0, dict_field_cap = 0;
+  // ffm_engine_score_item_lists[_device] (include/ffm_engine.h "Scoring a catalogue: per-request item lists"): S of the
+  // call's list entries, and the host call's copies of list_ptr and list_item and its output [n_list]; U is cat_u, as
+  // plain floats; made and grown like the arrays above
+  float *list_s = nullptr, *list_out = nullptr;
+  int *d_list_ptr = nullptr, *d_list_item = nullptr;
+  size_t list_s_cap = 0, list_out_cap = 0, list_ptr_cap = 0, list_item_cap = 0;
   // field and pair ablation (include/ffm_engine.h "Field ablation", "Pair ablation"; engine_ablate.h), each set all
   // made by its enable call for its V variants -- n_fields + 1, or n_fields (n_fields + 1) / 2 + 1 --: out [V][max_rows]
   // scores and loss the same shape (the kernel's variant-major outputs), sums [V], part [V][kLossParts + 1] the loss

@@ -6,9 +6,11 @@
 // kernels_catalog_items.h): S_c per item first, U towards every slot's field, the kernels over CatalogItemSrc -- and a
 // table whose last slots are dictionary slots ("... dictionary slots", kernels_catalog_dict.h): the dictionary slots' U
 // and partial scores between U and the kernels, which then run over CatalogDictSrc.
+// Per-request item lists ("... per-request item lists", kernels_catalog_lists.h) share the base, the table's checks and
+// the staging, and have three launches of their own: catalog_lists_launch, at the end of this file.
 // Part of engine.hip's translation unit (included inside its extern "C" block).
 
-// The engines every call of this file refuses, by name; what: "score_catalog" or "score_items".
+// The engines every call of this file refuses, by name; what: "score_catalog", "score_items", "score_item_lists".
 static int catalog_engine_check(ffm_engine *e, const char *what) {
   if (!e) return fail(FFM_E_INVALID, "null engine");
   if (!serving(e))
@@ -362,8 +364,8 @@ int ffm_engine_score_catalog_topk(ffm_engine *e, int32_t n_req, const int32_t *c
 // catalog_check's checks for an item table, and the table's slots into *t (t->feat: item_feat as it came).  No range
 // check of ids: an id outside [0, n_feats) is an erased slot.
 static int items_check(ffm_engine *e, int32_t n_req, int32_t n_slots, const int32_t *item_field, const int32_t *item_feat,
-                       const float *item_val, int32_t n_items, ItemTable *t) {
-  if (int rc = catalog_engine_check(e, "score_items")) return rc;
+                       const float *item_val, int32_t n_items, ItemTable *t, const char *what = "score_items") {
+  if (int rc = catalog_engine_check(e, what)) return rc;
   if (n_req < 0 || n_items < 0) return fail(FFM_E_INVALID, "negative n_req / n_items");
   if (n_slots < 1 || n_slots > kItemSlots)
     return fail(FFM_E_INVALID, "item_field: n_slots " + std::to_string(n_slots) + " lies outside [1, " + std::to_string(kItemSlots) + "]");
@@ -640,5 +642,103 @@ int ffm_engine_score_items_dict_topk(ffm_engine *e, int32_t n_req, const int32_t
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out_score, e->topk_score, sizeof(float) * n_out, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(out_id, e->topk_id, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, e->stream));
+  return check_device_errors(e);
+}
+
+// ---- per-request item lists (include/ffm_engine.h "Scoring a catalogue: per-request item lists"; kernels_catalog_lists.h)
+
+// items_check under the call's own name, and what the lists' kernel asks of the shape.
+static int lists_check(ffm_engine *e, int32_t n_req, int32_t n_slots, const int32_t *item_field, const int32_t *item_feat,
+                       const float *item_val, int32_t n_items, ItemTable *t) {
+  if (int rc = items_check(e, n_req, n_slots, item_field, item_feat, item_val, n_items, t, "score_item_lists")) return rc;
+  if (catalog_lists_lu(e->m.row_len) > kListMaxLu)
+    return fail(FFM_E_UNSUPPORTED, "score_item_lists stages a block of U in LDS: n_fields * n_factors above " + std::to_string(kListMaxLu) +
+                                       " is not supported");
+  return catalog_ready(e);
+}
+
+// The workgroups of catalog_lists_kernel for lists of up to list_cap entries.
+static int lists_grid_check(int32_t n_req, int32_t list_cap) {
+  if (static_cast<int64_t>(n_req) * cdiv(list_cap, kListSeg) > (1ll << 23))
+    return fail(FFM_E_CAPACITY, "n_req times the longest list exceeds 2^30 list positions: split the call");
+  return FFM_OK;
+}
+
+// The launches, on arrays in device memory: base, U as plain floats, S of the n_list entries, the dot products.
+// n_req, n_list, list_cap > 0; cap: the longest context, in [1, max_row_nnz].
+static int catalog_lists_launch(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                                const float *ctx_val, int32_t ctx_nnz, int cap, const ItemTable &t, const int32_t *list_ptr,
+                                const int32_t *list_item, int32_t n_list, int32_t list_cap, int32_t output_prob, float *out) {
+  const ModelDev &m = e->m;
+  const int lu = catalog_lists_lu(m.row_len), n_slots = t.slots.n;
+  int rc;
+  if ((rc = e->grow(&e->cat.base, &e->cat_base_cap, static_cast<size_t>(n_req)))) return rc;
+  if ((rc = e->grow(&e->cat_u, &e->cat_u_cap, static_cast<size_t>(n_req) * n_slots * lu * sizeof(float)))) return rc;
+  if ((rc = e->grow(&e->list_s, &e->list_s_cap, static_cast<size_t>(n_list)))) return rc;
+  float *const u = reinterpret_cast<float *>(e->cat_u);
+  // base_r: the bits of predict_batch on the context rows (as catalog_prepare)
+  launch_row_kernel(e, Rows{n_req, ctx_nnz, ctx_ptr, ctx_field, ctx_feat, ctx_val, nullptr}, cap, false, e->cat.base, 0);
+  const int lds_cap = std::min(cap, kPredLdsCap);
+  const int parts = cdiv(n_slots * lu, kListURun);  // (at most 512 a request: the grid stays far inside 2^31)
+  LAUNCH(e, K_CATALOG_LISTS_U, catalog_lists_u_fn(m.lat_fmt), cdiv(n_req * parts, kPredRows), 64 * kPredRows, cand_ctx_lds_bytes(lds_cap), m,
+         n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, t.slots, u, lu, parts, cap, lds_cap);
+  const int grid_s = static_cast<int>((static_cast<int64_t>(n_list) * 4 + 255) / 256);
+  LAUNCH(e, K_CATALOG_LISTS_SELF, catalog_lists_self_fn(m.lat_fmt), grid_s, 256, 0, m, t.slots, t.feat, t.n_items, list_item,
+         static_cast<int64_t>(n_list), e->list_s);
+  LAUNCH(e, K_CATALOG_LISTS, catalog_lists_fn(m.lat_fmt), dim3(n_req, cdiv(list_cap, kListSeg)), 256, 2 * lu * sizeof(float),
+         reinterpret_cast<const char *>(m.lat), m.row_len, m.n_feats, n_slots, t.feat, t.n_items, list_ptr, list_item,
+         static_cast<int64_t>(n_list), list_cap, static_cast<const float *>(u), lu, static_cast<const float *>(e->list_s),
+         static_cast<const float *>(e->cat.base), output_prob, out);
+  HIP_TRY(hipGetLastError());
+  return FFM_OK;
+}
+
+int ffm_engine_score_item_lists_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                       const int32_t *ctx_feat, const float *ctx_val, int32_t n_slots, const int32_t *item_field,
+                                       const int32_t *item_feat, const float *item_val, int32_t n_items, const int32_t *list_ptr,
+                                       const int32_t *list_item, int32_t ctx_nnz, int32_t ctx_cap, int32_t n_list, int32_t list_cap,
+                                       int32_t output_prob, float *out) {
+  ItemTable t;
+  if (int rc = lists_check(e, n_req, n_slots, item_field, item_feat, item_val, n_items, &t)) return rc;
+  if (ctx_nnz < 0 || ctx_cap < 0 || n_list < 0 || list_cap < 0) return fail(FFM_E_INVALID, "negative ctx_nnz / ctx_cap / n_list / list_cap");
+  if (n_req == 0 || n_list == 0 || list_cap == 0) return FFM_OK;
+  if (int rc = lists_grid_check(n_req, list_cap)) return rc;
+  if (!ctx_ptr || !out || !list_ptr || !list_item || (n_items > 0 && !item_feat) || (ctx_nnz > 0 && (!ctx_field || !ctx_feat || !ctx_val)))
+    return fail(FFM_E_INVALID, "null array");
+  const int cap = std::max(1, std::min(ctx_cap, e->max_row_nnz));
+  return catalog_lists_launch(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, ctx_nnz, cap, t, list_ptr, list_item, n_list, list_cap,
+                              output_prob, out);
+}
+
+int ffm_engine_score_item_lists(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                                const float *ctx_val, int32_t n_slots, const int32_t *item_field, const int32_t *item_feat,
+                                const float *item_val, int32_t n_items, const int32_t *list_ptr, const int32_t *list_item,
+                                int32_t output_prob, float *out) {
+  ItemTable t;
+  int rc = lists_check(e, n_req, n_slots, item_field, item_feat, item_val, n_items, &t);
+  if (rc) return rc;
+  if (n_req == 0) return FFM_OK;
+  if (!list_ptr) return fail(FFM_E_INVALID, "null array (list_ptr)");
+  if ((rc = cand_check_ptr(list_ptr, n_req, "list_ptr"))) return rc;
+  const int32_t n_list = list_ptr[n_req];
+  if (n_list == 0) return FFM_OK;
+  if (!out || !list_item || (n_items > 0 && !item_feat)) return fail(FFM_E_INVALID, "null array");
+  int32_t list_cap = 0;
+  for (int32_t r = 0; r < n_req; r++) list_cap = std::max(list_cap, list_ptr[r + 1] - list_ptr[r]);
+  if ((rc = lists_grid_check(n_req, list_cap))) return rc;
+  int32_t ctx_nnz = 0;
+  int cap = 1;
+  if ((rc = e->grow(&e->list_out, &e->list_out_cap, static_cast<size_t>(n_list))) ||  // (before anything is queued)
+      (rc = e->grow(&e->d_list_ptr, &e->list_ptr_cap, static_cast<size_t>(n_req) + 1)) ||
+      (rc = e->grow(&e->d_list_item, &e->list_item_cap, static_cast<size_t>(n_list))))
+    return rc;
+  if ((rc = catalog_stage_contexts(e, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, &ctx_nnz, &cap))) return rc;
+  if (n_items > 0 && (rc = items_stage(e, &t))) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_list_ptr, list_ptr, sizeof(int32_t) * (static_cast<size_t>(n_req) + 1), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_list_item, list_item, sizeof(int32_t) * n_list, hipMemcpyHostToDevice, e->stream));
+  rc = catalog_lists_launch(e, n_req, e->d_ctx_ptr, e->d_ctx_field, e->d_ctx_feat, e->d_ctx_val, ctx_nnz, cap, t, e->d_list_ptr, e->d_list_item,
+                            n_list, list_cap, output_prob, e->list_out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, e->list_out, sizeof(float) * n_list, hipMemcpyDeviceToHost, e->stream));
   return check_device_errors(e);
 }

@@ -220,6 +220,21 @@ CatalogDictFn catalog_dict_by_rt(int rt) {
 inline CatalogDictFn catalog_dict_fn(int fmt, int rt) {
   return fmt == SERVE_F16 ? catalog_dict_by_rt<SERVE_F16>(rt) : fmt == SERVE_F32 ? catalog_dict_by_rt<SERVE_F32>(rt) : nullptr;
 }
+// per-request item lists (kernels_catalog_lists.h): U as plain floats, S of the list entries and the gathered dot
+// products, each per format
+using CatalogListsUFn = void (*)(ModelDev, int, const int *, const int *, const int *, const float *, CatalogItemSlots, float *, int, int, int, int);
+using CatalogListsSelfFn = void (*)(ModelDev, CatalogItemSlots, const int *, int, const int *, int64_t, float *);
+using CatalogListsFn = void (*)(const char *, int, int, int, const int *, int, const int *, const int *, int64_t, int, const float *, int,
+                                const float *, const float *, int, float *);
+inline CatalogListsUFn catalog_lists_u_fn(int fmt) {
+  return fmt == SERVE_F16 ? catalog_lists_u_kernel<SERVE_F16> : fmt == SERVE_F32 ? catalog_lists_u_kernel<SERVE_F32> : nullptr;
+}
+inline CatalogListsSelfFn catalog_lists_self_fn(int fmt) {
+  return fmt == SERVE_F16 ? catalog_lists_self_kernel<SERVE_F16> : fmt == SERVE_F32 ? catalog_lists_self_kernel<SERVE_F32> : nullptr;
+}
+inline CatalogListsFn catalog_lists_fn(int fmt) {
+  return fmt == SERVE_F16 ? catalog_lists_kernel<SERVE_F16> : fmt == SERVE_F32 ? catalog_lists_kernel<SERVE_F32> : nullptr;
+}
 // field ablation (kernels_ablate.h)
 using AblateWaveFn =void (*)(ModelDev, Rows, int *, int, int, float *, double *, int, int);
 inline AblateWaveFn ablate_wave_fn(int fmt, int n_factors) {

@@ -278,6 +278,13 @@ ABI = [
     ("ffm_engine_score_items_dict_topk_device", ctypes.c_int,
      [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i32p, _vp, _vp, _i32p, _vp, _f32p, ctypes.c_int32,
       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
+    # ... and per-request lists of a table's items (include/ffm_engine.h "Scoring a catalogue: per-request item lists")
+    ("ffm_engine_score_item_lists", ctypes.c_int,
+     [_vp, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, ctypes.c_int32, _i32p, _i32p, _f32p, ctypes.c_int32, _i32p, _i32p,
+      ctypes.c_int32, _f32p]),
+    ("ffm_engine_score_item_lists_device", ctypes.c_int,
+     [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, _i32p, _vp, _f32p, ctypes.c_int32, _vp, _vp, ctypes.c_int32,
+      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp]),
     # the fields' cardinalities counted on the device, id ranges sized by them (include/ffm_engine.h "Field sketches")
     ("ffm_engine_sketch_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("ffm_engine_sketch_add", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32]),
@@ -1744,6 +1751,35 @@ class Engine:
         self._check(self.lib.ffm_engine_score_items_topk_device(
             self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, fld.shape[0], _i(fld), item_feat, _f(val), int(n_items), int(k),
             int(ctx_nnz), int(ctx_cap), int(output_prob), out_score, out_id))
+
+    def score_item_lists(self, ctx, item_field, item_feat, list_ptr, list_item, item_val=None, output_prob=False):
+        """Request r of ctx against ITS OWN list of a table's items, list_item[list_ptr[r]:list_ptr[r + 1]] (indices into
+        the table of score_items): float32[list_ptr[-1]], out[list_ptr[r] + p] the score_items formula for request r and
+        that item (include/ffm_engine.h "Scoring a catalogue: per-request item lists"; score_items_reference plus
+        predict_batch is the definition).  Gathered fp32 dot products; a score's bits depend on (request, item) only.  An
+        index outside the table scores as an item with every slot erased."""
+        fld, feat, val = _item_table(item_field, item_feat, item_val)
+        ptr = np.ascontiguousarray(list_ptr, np.int32).reshape(-1)
+        lst = np.ascontiguousarray(list_item, np.int32).reshape(-1)
+        if ptr.shape[0] != ctx.n_rows + 1 or (ptr[-1] if ptr.shape[0] else 0) != lst.shape[0]:
+            raise ValueError("list_ptr needs n_req + 1 elements, the last one len(list_item)")
+        out = np.zeros(lst.shape[0], np.float32)
+        _, cp, cfld, cft, cv, _ = self._csr(ctx)
+        self._check(self.lib.ffm_engine_score_item_lists(self.h, ctx.n_rows, cp, cfld, cft, cv, fld.shape[0], _i(fld), _i(feat), _f(val),
+                                                         feat.shape[0], _i(ptr), _i(lst), int(output_prob), _f(out)))
+        return out
+
+    def score_item_lists_device(self, n_req, ctx_ptr, ctx_field, ctx_feat, ctx_val, item_field, item_feat, item_val, n_items, list_ptr,
+                                list_item, ctx_nnz, ctx_cap, n_list, list_cap, output_prob, out):
+        """score_item_lists on arrays already in HBM (device addresses: the contexts, item_feat[n_items][m],
+        list_ptr[n_req + 1], list_item[n_list], out[n_list]); item_field and item_val (or None) are host arrays.  list_cap
+        is the caller's promise of the longest list: the tail of a longer one is left unwritten.  Asynchronous on the
+        engine's stream; sync() reports a too-long context."""
+        fld = np.ascontiguousarray(item_field, np.int32).reshape(-1)
+        val = None if item_val is None else np.ascontiguousarray(item_val, np.float32).reshape(-1)
+        self._check(self.lib.ffm_engine_score_item_lists_device(
+            self.h, int(n_req), ctx_ptr, ctx_field, ctx_feat, ctx_val, fld.shape[0], _i(fld), item_feat, _f(val), int(n_items), list_ptr,
+            list_item, int(ctx_nnz), int(ctx_cap), int(n_list), int(list_cap), int(output_prob), out))
 
     @staticmethod
     def _dict_table(item_field, item_feat, item_code, dicts, item_val):

@@ -1312,6 +1312,63 @@ int ffm_engine_score_items_dict_topk_device(ffm_engine *e, int32_t n_req, const 
                                             int32_t top_k, int32_t ctx_nnz, int32_t ctx_cap, int32_t output_prob, float *out_score,
                                             int32_t *out_id);
 
+/* ---- Scoring a catalogue: per-request item lists ---------------------------------------------------------
+ * Retrieval is followed by RANKING: every request arrives with a short list of its own -- a few dozen to a few
+ * thousand items picked from millions by an index, a budget filter, a targeting rule -- and wants the model's score of
+ * those items alone.  The item table is exactly the one of "items of several entries" (item_field[n_slots] distinct,
+ * n_slots = m in [1, 8]; item_feat[n_items][n_slots]; item_val[n_slots] or NULL for ones), and beside it come
+ *   list_ptr[n_req + 1]            non-decreasing, list_ptr[0] == 0: request r's list is the entries
+ *                                  [list_ptr[r], list_ptr[r + 1]) of list_item;
+ *   list_item[list_ptr[n_req]]     indices into the table; an item may stand in many lists and twice in one.
+ * DEFINITION  out[list_ptr[r] + p] is score(r, c) of "items of several entries" for c = list_item[list_ptr[r] + p]:
+ *   base_r + S_c + sum_a sum_j U_r^a[j] * W[c_a][j]; in float64, score_items_reference(...)[0][r, c] plus
+ *   ffm_engine_predict_batch of the context.  m = 1 is the one-entry candidate.
+ * HOW (csrc/kernels_catalog_lists.h)  Every request has one row of U against table rows of its own: nothing is shared
+ *   between requests, so this is no matrix product but a batch of gathered dot products on the VALU.  U is kept in fp32
+ *   on both formats; S is computed for the listed entries only (the bits of ffm_engine_score_items' S_c); a group of 16
+ *   lanes streams the m table rows of four list entries at a time in 16-byte vectors against U in LDS, one fp32
+ *   accumulator per entry and lane, the 16 partial sums added in one fixed order;
+ *   score = fadd(acc, fadd(S_c, base_r)), the sigmoid of it under output_prob.
+ * CONTRACT  Not bit for bit against the rows or against ffm_engine_score_items.  For finite tables the bound of "items
+ *   of several entries" holds unchanged, N = m L + m + m (m - 1) / 2 * k:
+ *     |score - (base_r + ref64)| <= (N + 32) * 2^-24 * (|base_r| + scale)
+ *   (the any-order bound of fp32 sums, which a chain of fp32 FMAs and a tree of fp32 adds satisfy; U's elements are the
+ *   fp32 sums the 32 already covers, with no second plane and no shift on f16).  A score's bits depend on (request, item)
+ *   ONLY: not on the entry's position, the list's length or what else is in the call.  The device and the host entry
+ *   point give the same bits.
+ * EDGES  A slot id outside [0, n_feats) is erased, as in ffm_engine_score_items.  A list entry outside [0, n_items)
+ *   scores as an item whose slots are all erased -- base_r -- because the device call cannot refuse it.  An empty list
+ *   writes nothing.  A context that is too long gives NaN for its own list's outputs alone and FFM_E_CAPACITY (from the
+ *   host call; from ffm_engine_sync behind the device call).  Contexts otherwise as in ffm_engine_score_catalog: erased
+ *   entries, an empty context, ctx_val == NULL and hashing in the host call (item_feat under its slots' fields too).
+ * ffm_engine_score_item_lists: every array in host memory; synchronous; item_feat, list_ptr and list_item are copied
+ *   into buffers of the engine's.
+ * ffm_engine_score_item_lists_device: the contexts, item_feat, list_ptr, list_item and out are device addresses;
+ *   item_field and item_val are HOST arrays here too; asynchronous on the engine's stream.  n_list is the number of
+ *   entries of list_item (and of out), list_cap the caller's promise of the longest list: of a list longer than
+ *   list_cap the entries from list_cap on are LEFT UNWRITTEN, as are entries at or beyond n_list and the list of a
+ *   list_ptr pair that is negative or descends -- nothing is read or written outside the n_list entries.
+ * Both: the checks of ffm_engine_score_items on the table (FFM_E_INVALID naming item_field; FFM_E_CAPACITY for n_req >
+ *   max_batch_rows), FFM_E_INVALID naming list_ptr when it does not start at 0 or descends (host call), FFM_E_INVALID
+ *   for a null array or a negative count, FFM_E_CAPACITY when n_req times the longest list exceeds 2^30 positions,
+ *   FFM_E_UNSUPPORTED for n_fields * n_factors above 8192.  The same engines are REFUSED by name, as "score_item_lists":
+ *   training, FFM_FLAG_SERVE_F8, a pruned table, a pair mask, FFM_FLAG_NORM_ROWS, a group's or a shard's engine.  The
+ *   buffers (S of the entries, the host call's copies and output; U and base are the catalogue calls') are allocated by
+ *   the first call, grown to the largest call seen and freed by ffm_engine_destroy; an engine that never makes the call
+ *   allocates and launches nothing new.  The profile calls label the kernels "catalog_lists_u_kernel",
+ *   "catalog_lists_self_kernel" and "catalog_lists_kernel".  FFM_ENGINE_ABI_VERSION is what it was.
+ * OUT OF SCOPE  top-K inside a list; dictionary slots in lists; FFM_FLAG_SERVE_F8 and pruned tables; per-item values;
+ *   the CLI; caching S across calls. */
+int ffm_engine_score_item_lists(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field, const int32_t *ctx_feat,
+                                const float *ctx_val, int32_t n_slots, const int32_t *item_field, const int32_t *item_feat,
+                                const float *item_val, int32_t n_items, const int32_t *list_ptr, const int32_t *list_item,
+                                int32_t output_prob, float *out);
+int ffm_engine_score_item_lists_device(ffm_engine *e, int32_t n_req, const int32_t *ctx_ptr, const int32_t *ctx_field,
+                                       const int32_t *ctx_feat, const float *ctx_val, int32_t n_slots, const int32_t *item_field,
+                                       const int32_t *item_feat, const float *item_val, int32_t n_items, const int32_t *list_ptr,
+                                       const int32_t *list_item, int32_t ctx_nnz, int32_t ctx_cap, int32_t n_list, int32_t list_cap,
+                                       int32_t output_prob, float *out);
+
 /* ---- Field ablation: the loss and AUC of the model without each field, in one pass -------------------
  * Which fields earn their place?  The standard answer is the evaluation loss and AUC of the same model with
  * field f removed from every row -- n_fields more passes over rewritten copies of the evaluation data.  The

@@ -138,8 +138,10 @@ def run_catalog(args):
     nf = min(args.n_feats, 4_000_000)
     nf -= nf % N_FIELDS
     g, first, cf = N_FIELDS - 1, 1000, N_FIELDS - 1  # contexts: one entry in each of the other 38 fields
-    longest = N_FIELDS + args.catalog_items  # (a spelled-out item row: the context and the item's entries)
-    eng = fa.Engine("FFM", nf, N_FIELDS, N_FACTORS, max_batch_rows=ROWS, max_batch_nnz=ROWS * longest, seed=42,
+    lists = [int(x) for x in args.item_lists.replace(":", ",").split(",")] if args.item_lists else None  # [slots, len, len, ...]
+    longest = N_FIELDS + max(args.catalog_items, lists[0] if lists else 0)  # (a spelled-out item row: the context and the item's entries)
+    rows_cap = max(ROWS, 128 * max(lists[1:])) if lists else ROWS  # (the lists' baselines score every entry as a row)
+    eng = fa.Engine("FFM", nf, N_FIELDS, N_FACTORS, max_batch_rows=rows_cap, max_batch_nnz=rows_cap * longest, seed=42,
                     max_row_nnz=longest, serve=args.kind)
     elem = 2 if args.kind == "f16" else 4
     blk = synth.Generator(N_FIELDS, nf, dist="zipf", seed=42).block(128)
@@ -170,6 +172,10 @@ def run_catalog(args):
 
     if args.dict_slots:  # (its own baselines, in this process: no spelled-out rows)
         catalog_dict_lines(args, eng, windows, d, out, cf, up, nf)
+        eng.close()
+        return
+    if lists:  # (its own baselines too)
+        item_lists_lines(args, eng, windows, d, out, ctx, cf, up, nf, lists[0], lists[1:], elem)
         eng.close()
         return
     # the baseline: spelled-out rows of request r against candidates first + j, blocks of 8192 rows, cycled
@@ -306,6 +312,69 @@ def catalog_dict_lines(args, eng, windows, d, out, cf, up, nf):
         res["profile"] = [ln for ln in eng.profile_dump().strip().splitlines() if "catalog" in ln]
         eng.profile_enable(False)
         print("SERVE_BENCH " + json.dumps(res), flush=True)
+
+
+def item_lists_lines(args, eng, windows, d, out, ctx, cf, up, nf, M, lens, elem):
+    """--item-lists SLOTS:LEN[,LEN...]: catalog_items_lines' table of 2^20 items of SLOTS slots; per 32 and 128 requests
+    and per LEN, lists of LEN items drawn from the whole table through score_item_lists_device, beside (a)
+    score_candidates_device on the same lists as candidates of SLOTS entries, (b) the same entries spelled out as rows
+    through predict_batch_device and (c) score_items_device over the whole table: one JSON line each, medians of the
+    windows with min .. max.  The list call is measured twice: the distance of its two medians is the run-to-run spread
+    of this process.  gather_bytes: the table rows a call must read, entries * SLOTS * row bytes."""
+    import numpy as np
+    import ftrl_ffm_amd as fa
+    from ftrl_ffm_amd import synth
+    n_items, per = 1 << 20, nf // N_FIELDS
+    rng = np.random.default_rng(42)
+    fld = np.arange(N_FIELDS - M, N_FIELDS, dtype=np.int32)[::-1].copy()
+    pool = [n_items] + [max(1, 1000 // 10 ** a) for a in range(M - 1)]
+    feat = np.stack([1000 + np.arange(n_items) if a == 0 else fld[a] * per + rng.integers(pool[a], size=n_items) for a in range(M)],
+                    axis=1).astype(np.int32)
+    d_feat, ptrs = up(feat), [t.data_ptr() for t in d]
+    for n_req in (32, 128):
+        whole = windows(lambda: eng.score_items_device(n_req, *ptrs, fld, d_feat.data_ptr(), None, n_items, n_req * cf, cf, 0, out.data_ptr()),
+                        window=max(args.window, 0.3))
+        for ln in lens:
+            n_list = n_req * ln
+            lptr = (np.arange(n_req + 1, dtype=np.int64) * ln).astype(np.int32)
+            item = rng.integers(n_items, size=n_list).astype(np.int32)
+            cand = synth.Block((np.arange(n_list + 1, dtype=np.int64) * M).astype(np.int32), np.tile(fld, n_list), feat[item].reshape(-1),
+                               np.ones(n_list * M, np.float32), np.zeros(n_list, np.int32))
+            rows = fa.spell_out_candidates(ctx.rows(0, n_req), lptr, cand)
+            keep =[up(a) for a in (lptr, item, cand.row_ptr, cand.field, cand.feat, cand.val, rows.row_ptr, rows.field, rows.feat, rows.val)]
+            d_l, d_c, d_r = [t.data_ptr() for t in keep[:2]], [t.data_ptr() for t in keep[2:6]], [t.data_ptr() for t in keep[6:]]
+
+            def listed():
+                eng.score_item_lists_device(n_req, *ptrs, fld, d_feat.data_ptr(), None, n_items, *d_l, n_req * cf, cf, n_list, ln, 0,
+                                            out.data_ptr())
+            cells = dict(
+                score_item_lists_device=listed,
+                score_candidates_device=lambda: eng.score_candidates_device(n_req, *ptrs, d_l[0], n_list, *d_c, n_req * cf, n_list * M, cf, 0,
+                                                                            out.data_ptr()),
+                rows_predict_batch_device=lambda: eng.predict_batch_device(n_list, int(rows.row_ptr[-1]), *d_r, None, 0, out.data_ptr(), None),
+                score_item_lists_device_again=listed)
+            res = dict(item_lists=M, list_len=ln, kind=args.kind, n_req=n_req, n_items=n_items, entries=n_list,
+                       gather_bytes=n_list * M * N_FIELDS * N_FACTORS * elem)
+            for name, call in cells.items():
+                us = windows(call, window=max(args.window, 0.3))
+                res[name + "_us"] = dict(median=round(us[len(us) // 2], 1), min=round(us[0], 1), max=round(us[-1], 1))
+            med = res["score_item_lists_device_us"]["median"]
+            res["score_items_device_whole_table_us"] = dict(median=round(whole[len(whole) // 2], 1), min=round(whole[0], 1), max=round(whole[-1], 1))
+            res["entries_per_s"] = n_list / (med * 1e-6)
+            res["over_score_candidates"] = res["score_candidates_device_us"]["median"] / med
+            res["over_rows"] = res["rows_predict_batch_device_us"]["median"] / med
+            # the list length, as a share of the table, at which scoring the whole table costs what the lists cost (linear in LEN)
+            res["break_even_share_of_table"] = whole[len(whole) // 2] / med * ln / n_items
+            listed()
+            eng.sync()
+            res["checksum"] = float(out[:n_list].double().sum().cpu())
+            eng.profile_enable(True)
+            for _ in range(10):
+                listed()
+            eng.sync()
+            res["profile"] = [x for x in eng.profile_dump().strip().splitlines() if "catalog_lists" in x or "row" in x]
+            eng.profile_enable(False)
+            print("SERVE_BENCH " + json.dumps(res), flush=True)
 
 
 def catalog_topk_line(args, eng, windows, d, out, g, first, cf, n_req, n_cand, K, matrix_us):
@@ -608,10 +677,14 @@ def main():
     ap.add_argument("--dict-slots", type=int, default=0, metavar="D",
                     help="with --catalog-items M: the last D of the M slots as dictionaries (score_items_dict_device, its top 8) "
                          "against score_items_device on the expanded table and score_catalog_device (profiles/score_items_dict.md)")
+    ap.add_argument("--item-lists", metavar="SLOTS:LEN[,LEN...]",
+                    help="per-request lists of LEN items of SLOTS slots out of 2^20 (score_item_lists_device) against "
+                         "score_candidates_device, spelled-out rows and score_items_device over the whole table, --kind f32 or f16 "
+                         "(profiles/score_item_lists.md)")
     args = ap.parse_args()
     if args.dict_slots and not 1 <= args.dict_slots < args.catalog_items:
         raise SystemExit("--dict-slots D needs --catalog-items M with 1 <= D < M")
-    if args.catalog or args.dict_slots:
+    if args.catalog or args.dict_slots or args.item_lists:
         if args.kind not in ("f32", "f16"):
             raise SystemExit("--catalog needs --kind f32 or f16")
         return run_catalog(args)
